@@ -13,9 +13,18 @@ LoadAudio -> EgregoraAudioUpscaler -> EgregoraFatLlamaGPU): per GPU 60 s of ster
   stage 2  Fat-Llama: each rank enhances its own 60 s slice of the stage-1 output, max_iterations = 800,
            threshold 0.6, normalise on, autoscale off, factor 1, PCM_16 hops included, every iteration executed.
 A step = stage 1 + stage 2; value = N x 60 audio-seconds / max-over-ranks step time  (weak scaling: per-GPU work
-is fixed as N grows).  `parts` reports each stage alone, BASELINE configs[1] (one stereo 5.12 s chunk), the Fat-Llama stage on
-lengths WITHOUT a packed plan (60 s + 2 samples, 60 s + 1 sample: the paired chirp-z path most real files take) and, with N > 1,
-BASELINE configs[3] (one 10-minute file chunk-sharded over the N GPUs: the strong-scaling claim of north_star).
+is fixed as N grows).
+
+A plain run sets up, warms up, times the K steps, writes the outputs (--dump-outputs) and prints the headline line (metric, value,
+unit, higher_is_better, dtype, ms_per_step, ...).  Everything else is behind --full: the sanity checks outside the timed region
+(finite outputs, 800 iterations land where one lands), `parts` (each stage alone, BASELINE configs[1] = one stereo 5.12 s chunk,
+the Fat-Llama stage on lengths WITHOUT a packed plan -- 60 s + 2 samples, 60 s + 1 sample: the paired chirp-z path most real files
+take -- and, with N > 1, BASELINE configs[3]: one 10-minute file chunk-sharded over the N GPUs, the strong-scaling claim of
+north_star), the other threshold readings, the node-boundary figure, the rooflines and the CPU baseline (--no-cpu-baseline drops it).
+--lean drops the extra workloads of `parts`, the other readings and the node boundary again (used with --full under rocprofv3).
+
+--dump-outputs DIR: after the timed steps, rank 0 writes what its last timed step returned (the enhanced audio [C, T]) as
+DIR/<name>.npy in float32; the inputs are seeded, so two builds can be compared output for output.
 
 --dry-run: no GPU; gloo process group, stub stages (a sleep and the real chunk sharding + all-gather on CPU tensors): checks the
 launch / rank plumbing of this file on a CPU box (tests/test_bench_launch.py).
@@ -68,6 +77,20 @@ def csrc_sha():
         h.update(f.name.encode())
         h.update(f.read_bytes())
     return h.hexdigest()[:16]
+
+
+def dump_outputs(d, arrays, budget=64_000_000):
+    """--dump-outputs: every array as d/<name>.npy in float32, at most `budget` bytes in all; an array larger than its share is
+    replaced by a fixed, seeded sample of its elements (flat order, sorted indices)"""
+    d = Path(d)
+    d.mkdir(parents=True, exist_ok=True)
+    cap = (budget - 1024 * len(arrays)) // (4 * len(arrays))          # float32 values per array, .npy headers aside
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if a.size > cap:
+            idx = np.sort(np.random.Generator(np.random.PCG64(0)).choice(a.size, cap, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(d / f"{name}.npy", a)
 
 
 def cpu_model():
@@ -155,6 +178,20 @@ def cpu_baseline_fatllama(x, budget_s, gpu_c1=None):
                                "flips on ~2 % of samples of an eight-tone signal over a -40 dB floor -- the quantiser, not the loop)"}}
 
 
+def one_gpu_override(out, world):
+    if os.environ.get("EGREGORA_BENCH_ONE_GPU", "0") == "1":
+        # a test-only override (tests/test_gpu_bench_ranks.py): every rank shared device 0 and the collectives ran over gloo.  The line
+        # says so and carries no headline number, so a leaked environment variable cannot pass for a multi-GPU measurement.
+        out["one_gpu_override"] = True
+        out["value_one_gpu_override"] = out["value"]
+        out["value"] = None
+        for k in ("value_relative_threshold", "value_arbitrary_length", "value_arbitrary_length_relative_threshold"):
+            if k in out:
+                out[k + "_one_gpu_override"] = out.pop(k)
+        out["note"] = "EGREGORA_BENCH_ONE_GPU=1: all %d ranks on ONE device, gloo collectives -- a path check, not a measurement" % world
+    return out
+
+
 def free_port():
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
@@ -210,6 +247,8 @@ def dry_run(args, rank, world, dist):
         step()
     el, preds = timed(args.steps)
     ok = bool(torch.equal(preds[:, 0, 0], torch.arange(n_chunks, dtype=torch.float32)))
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"gathered_chunks": preds.numpy()})
     if rank == 0:
         print(json.dumps({"metric": METRIC, "value": args.steps * (total / SR) / el, "unit": "audio-sec/sec", "n_gpus": world,
                           "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * el / args.steps, "higher_is_better": True,
@@ -233,8 +272,12 @@ def main():
                     help="chain60 (default, weak scaling: 60 s per GPU through FlashSR + Fat-Llama) or c4 = BASELINE configs[3]: "
                          "FlashSR long-form, ONE 10-minute stereo file chunk-sharded over the N GPUs with one all-gather + WOLA "
                          "(strong scaling: north_star's '>= 6x chunk-parallel speed-up at 8 GPUs')")
-    ap.add_argument("--lean", action="store_true", help="skip the untimed extras (parts); used under rocprofv3 so the "
+    ap.add_argument("--full", action="store_true", help="after the headline, everything else: sanity checks, parts, other threshold "
+                                                        "readings, node boundary, rooflines, CPU baseline (a plain run measures the headline only)")
+    ap.add_argument("--lean", action="store_true", help="with --full: skip the untimed extras (parts); used under rocprofv3 so the "
                                                         "per-kernel averages cover the timed workload only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write what the last timed step returned as DIR/<name>.npy (float32, rank 0)")
     ap.add_argument("--dry-run", action="store_true", help="CPU plumbing check (gloo, stub stages)")
     args = ap.parse_args()
 
@@ -336,7 +379,8 @@ def main():
         return time.perf_counter() - t0, r
 
     # what the FIRST call of a handle costs (scratch arena allocation, side-stream check; the arithmetic is the steady state's:
-    # include/egregora_amd.h egr_flashsr_set_split) -- timed before the warm-up, outside the timed region
+    # include/egregora_amd.h egr_flashsr_set_split) -- timed before the warm-up, outside the timed region; a plain run makes the same
+    # calls (reported only with --full), so the steps it times start from the same state
     el_first = None
     el_torch_warm = None
     if args.only != "fatllama" and not args.lean:
@@ -351,7 +395,33 @@ def main():
         el_first, _ = timed(stage_flashsr, 1)
     for _ in range(args.warmup):
         step()
-    el, _ = timed(step, args.steps)
+    el, y_last = timed(step, args.steps)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {("flashsr_output" if args.only == "flashsr" else "fatllama_output"): y_last.cpu().numpy()})
+    del y_last
+
+    split = eng.split_info() if eng.mfma != "f32" else {"enabled": False}
+    head = {"metric": METRIC, "value": args.steps * (total / SR) / el, "unit": "audio-sec/sec", "n_gpus": world,
+            "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * el / args.steps, "higher_is_better": True,
+            "scaling": "strong" if c4 else "weak", "vs_baseline": None,
+            "dtype": "f32" if eng.mfma == "f32" else ("f32(f16x2)" if split.get("enabled") else "f32(bf16x3)"), "data": "synthetic"}
+    workload = (("c4: BASELINE configs[3], ONE 10 min stereo 48 kHz file, FlashSR (5.12 s chunks, hop 4.62 s, "
+                 "student_ldm 1-step + VAE + sr_vocoder, declared architecture, synthetic weights) chunk-sharded over "
+                 "the GPUs with one all-gather, WOLA on every rank; total work fixed as N grows" if c4 else
+                 "chain60: per GPU 60 s stereo 48 kHz; FlashSR (5.12 s chunks, hop 4.62 s, student_ldm "
+                 "1-step + VAE + sr_vocoder, declared architecture, synthetic weights, chunk-sharded with one "
+                 "all-gather, WOLA) then Fat-Llama max_iterations=%d thr=0.6 normalize on autoscale off, "
+                 "threshold reading of the HEADLINE value: '%s' (SPEC.md section 3 default = absolute level on int16-scale "
+                 "samples, hard threshold, time-domain pre-threshold, linear up-rating unless listed; the relative-to-maximum "
+                 "reading is value_relative_threshold)" % (args.iters, os.environ.get("EGREGORA_FATLLAMA_SPEC", "") or "default"))
+                + (f" [only={args.only}]" if args.only and not c4 else ""))
+    if not args.full:
+        if rank == 0:
+            out = {**head, "config": {"workload": workload, "arch": arch, "chunks": n_chunks, "rows_per_pass": E.ROWS_PER_PASS}}
+            print(json.dumps(one_gpu_override(out, world)))
+        if dist:
+            dist.destroy_process_group()
+        return
 
     # ---- untimed extras: per-stage times, configs[1], per-kernel HIP-event timing for the rooflines ----
     el_fs, y48 = timed_med(stage_flashsr)
@@ -555,20 +625,8 @@ def main():
             pass
         info = fe.plan_info(SEG, 1)
         out = {
-            "metric": METRIC, "value": args.steps * audio_s / el, "unit": "audio-sec/sec", "n_gpus": world,
-            "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * el / args.steps, "higher_is_better": True,
-            "scaling": "strong" if c4 else "weak", "vs_baseline": None, "dtype": "f32" if eng.mfma == "f32" else ("f32(f16x2)" if split.get("enabled") else "f32(bf16x3)"),
-            "data": "synthetic",
-            "config": {"workload": ("c4: BASELINE configs[3], ONE 10 min stereo 48 kHz file, FlashSR (5.12 s chunks, hop 4.62 s, "
-                                    "student_ldm 1-step + VAE + sr_vocoder, declared architecture, synthetic weights) chunk-sharded over "
-                                    "the GPUs with one all-gather, WOLA on every rank; total work fixed as N grows" if c4 else
-                                    "chain60: per GPU 60 s stereo 48 kHz; FlashSR (5.12 s chunks, hop 4.62 s, student_ldm "
-                                    "1-step + VAE + sr_vocoder, declared architecture, synthetic weights, chunk-sharded with one "
-                                    "all-gather, WOLA) then Fat-Llama max_iterations=%d thr=0.6 normalize on autoscale off, "
-                                    "threshold reading of the HEADLINE value: '%s' (SPEC.md section 3 default = absolute level on int16-scale "
-                                    "samples, hard threshold, time-domain pre-threshold, linear up-rating unless listed; the relative-to-maximum "
-                                    "reading is value_relative_threshold)" % (args.iters, os.environ.get("EGREGORA_FATLLAMA_SPEC", "") or "default"))
-                                   + (f" [only={args.only}]" if args.only and not c4 else ""),
+            **head,
+            "config": {"workload": workload,
                        "flashsr_executor": "egr_flashsr_infer (C ABI, csrc/egr_flashsr.cpp)",
                        "lsd_800_vs_1_iteration_db": lsd_iters[0],
                        "mfma": (("fp32 operands as two fp16 terms, every batch row of every contraction input scaled by a power of two "
@@ -672,16 +730,7 @@ def main():
                 "survey_32N": {"bytes_total": 32.0 * a["samples"] * C * args.iters,
                                "achieved": 32.0 * a["samples"] * C * args.iters / (a["ms"] * 1e6),
                                "frac": 32.0 * a["samples"] * C * args.iters / (a["ms"] * 1e6) / HBM_PEAK_GBS}}
-        if os.environ.get("EGREGORA_BENCH_ONE_GPU", "0") == "1":
-            # a test-only override (tests/test_gpu_bench_ranks.py): every rank shared device 0 and the collectives ran over gloo.  The line
-            # says so and carries no headline number, so a leaked environment variable cannot pass for a multi-GPU measurement.
-            out["one_gpu_override"] = True
-            out["value_one_gpu_override"] = out["value"]
-            out["value"] = None
-            for k in ("value_relative_threshold", "value_arbitrary_length", "value_arbitrary_length_relative_threshold"):
-                if k in out:
-                    out[k + "_one_gpu_override"] = out.pop(k)
-            out["note"] = "EGREGORA_BENCH_ONE_GPU=1: all %d ranks on ONE device, gloo collectives -- a path check, not a measurement" % world
+        one_gpu_override(out, world)
         if not args.no_cpu_baseline and world == 1:
             def gpu_c1(c1, sr1, cpu_out, cpu_raw, f1):
                 from packload import load_pack as _lp

@@ -6,6 +6,8 @@ import subprocess
 import sys
 from pathlib import Path
 
+import numpy as np
+
 ROOT = Path(__file__).resolve().parent.parent
 
 
@@ -30,6 +32,18 @@ def test_single_rank_dry_run():
     assert r.returncode == 0, r.stderr[-2000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
     assert out["n_gpus"] == 1
+
+
+def test_dry_run_dump_outputs_float32_and_repeatable(tmp_path):
+    # --dump-outputs writes the last timed step's result; the same arguments give the same arrays; --full is accepted
+    for d, extra in ((tmp_path / "a", []), (tmp_path / "b", ["--full"])):
+        r = _run(["--dry-run", "--steps", "3", "--warmup", "0", "--dump-outputs", str(d)] + extra)
+        assert r.returncode == 0, r.stderr[-2000:]
+        out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
+        assert out["steps"] == 3 and out["ms_per_step"] > 0
+    a, b = np.load(tmp_path / "a" / "gathered_chunks.npy"), np.load(tmp_path / "b" / "gathered_chunks.npy")
+    assert a.dtype == np.float32 and a.ndim == 3 and a.shape[1:] == (2, 8)
+    assert np.array_equal(a, b) and np.array_equal(a[:, 0, 0], np.arange(a.shape[0], dtype=np.float32))
 
 
 def test_launcher_mismatch_is_loud():

@@ -19,7 +19,7 @@ def test_two_ranks_share_one_gpu_and_report_one_line():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["EGREGORA_BENCH_ONE_GPU"] = "1"
     r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--iters", "40",
-                        "--no-cpu-baseline", "--lean"], capture_output=True, text=True, timeout=1200, env=env, cwd=str(ROOT))
+                        "--no-cpu-baseline", "--full", "--lean"], capture_output=True, text=True, timeout=1200, env=env, cwd=str(ROOT))
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
