@@ -1,0 +1,367 @@
+"""DeepFilterNet3 model directory discovery, config.ini, checkpoint validation and packing for the native denoiser
+(SPEC.md "DeepFilterNet3 (UPSTREAM-RECALL)").
+
+A model directory is what upstream's `df` keeps per model: `config.ini` plus `checkpoints/*.ckpt.best` (a state dict saved
+with torch.save).  It is looked for, in this order, in
+  1. EGREGORA_DFN_MODEL_DIR
+  2. models/audio/deepfilternet/<model> at both places `models/` can mean (flashsr_weights.candidate_dirs, quirk Q2)
+  3. df's own cache, ~/.cache/DeepFilterNet/<model>
+No download is attempted.  Every hyperparameter comes from config.ini; the layer counts and widths the checkpoint's tensor
+shapes imply are checked against it, and every tensor name and shape against the committed key table `dfn3_keymap.json`.
+Anything unmapped, missing or mismatched raises with the full list.
+"""
+import configparser
+import json
+import math
+import os
+import re
+from pathlib import Path
+from typing import Dict, List, Optional, Tuple
+
+import numpy as np
+import torch
+
+MODEL = "DeepFilterNet3"
+KEYMAP_PATH = Path(__file__).resolve().parent / "dfn3_keymap.json"
+BN_EPS = 1e-5
+
+# (section, key, type) of every hyperparameter the forward pass reads; all must be present in config.ini
+_INT, _FLOAT, _STR, _BOOL, _PAIR = int, float, str, "bool", "pair"
+PARAMS = [
+    ("df", "sr", _INT), ("df", "fft_size", _INT), ("df", "hop_size", _INT), ("df", "nb_erb", _INT), ("df", "nb_df", _INT),
+    ("df", "norm_tau", _FLOAT), ("df", "lsnr_max", _INT), ("df", "lsnr_min", _INT), ("df", "min_nb_erb_freqs", _INT),
+    ("df", "df_order", _INT), ("df", "df_lookahead", _INT), ("df", "pad_mode", _STR),
+    ("deepfilternet", "conv_lookahead", _INT), ("deepfilternet", "conv_ch", _INT), ("deepfilternet", "conv_depthwise", _BOOL),
+    ("deepfilternet", "convt_depthwise", _BOOL), ("deepfilternet", "conv_kernel", _PAIR), ("deepfilternet", "convt_kernel", _PAIR),
+    ("deepfilternet", "conv_kernel_inp", _PAIR), ("deepfilternet", "emb_hidden_dim", _INT), ("deepfilternet", "emb_num_layers", _INT),
+    ("deepfilternet", "emb_gru_skip_enc", _STR), ("deepfilternet", "emb_gru_skip", _STR), ("deepfilternet", "df_hidden_dim", _INT),
+    ("deepfilternet", "df_gru_skip", _STR), ("deepfilternet", "df_pathway_kernel_size_t", _INT), ("deepfilternet", "enc_concat", _BOOL),
+    ("deepfilternet", "df_num_layers", _INT), ("deepfilternet", "df_n_iter", _INT), ("deepfilternet", "lin_groups", _INT),
+    ("deepfilternet", "enc_lin_groups", _INT), ("deepfilternet", "mask_pf", _BOOL),
+]
+
+
+# ------------------------------------------------------------------------------------------------ discovery
+def pack_root() -> Path:
+    return Path(__file__).resolve().parent
+
+
+def candidate_dirs(model: str = MODEL) -> List[Path]:
+    """Where a `model` directory may be, in search order (duplicates removed)."""
+    root = pack_root()
+    env = os.environ.get("EGREGORA_DFN_MODEL_DIR", "")
+    cands = [Path(env)] if env else []
+    cands.append(root.parents[1] / "models" / "audio" / "deepfilternet" / model)
+    if len(root.parents) > 2:
+        cands.append(root.parents[2] / "models" / "audio" / "deepfilternet" / model)
+    cands.append(Path(os.path.expanduser("~")) / ".cache" / "DeepFilterNet" / model)
+    out, seen = [], set()
+    for c in cands:
+        if str(c) not in seen:
+            seen.add(str(c))
+            out.append(c)
+    return out
+
+
+def checkpoint_file(d: Path) -> Optional[Path]:
+    """The newest `checkpoints/*.ckpt.best` (highest epoch number in the name), None when there is none."""
+    cks = sorted(Path(d).glob("checkpoints/*.ckpt.best"))
+    if not cks:
+        return None
+    def epoch(p: Path):
+        m = re.search(r"(\d+)", p.name)
+        return (int(m.group(1)) if m else -1, p.name)
+    return max(cks, key=epoch)
+
+
+def is_model_dir(d: Path) -> bool:
+    return (Path(d) / "config.ini").is_file() and checkpoint_file(d) is not None
+
+
+def discover(model: str = MODEL) -> Optional[Path]:
+    """The first candidate that holds a model directory, else None (only DeepFilterNet3 is served natively)."""
+    if model != MODEL:
+        return None
+    for d in candidate_dirs(model):
+        if is_model_dir(d):
+            return d
+    return None
+
+
+# ------------------------------------------------------------------------------------------------ config
+def parse_config(path: Path) -> dict:
+    """config.ini -> {key: value} for every entry of PARAMS; raises listing every absent or unreadable key."""
+    cp = configparser.ConfigParser()
+    cp.read(str(path), encoding="utf-8")
+    cfg, bad = {}, []
+    for sec, key, typ in PARAMS:
+        if not cp.has_option(sec, key):
+            bad.append(f"[{sec}] {key}: missing")
+            continue
+        raw = cp.get(sec, key).strip()
+        try:
+            if typ == _BOOL:
+                v = raw.lower() in ("1", "true", "yes", "on")
+                if raw.lower() not in ("1", "0", "true", "false", "yes", "no", "on", "off"):
+                    raise ValueError(raw)
+            elif typ == _PAIR:
+                v = tuple(int(s) for s in raw.split(","))
+                if len(v) != 2:
+                    raise ValueError(raw)
+            elif typ == _STR:
+                v = raw.lower()
+            else:
+                v = typ(raw)
+        except ValueError:
+            bad.append(f"[{sec}] {key}: cannot read {raw!r}")
+            continue
+        cfg[key] = v
+    if bad:
+        raise RuntimeError(f"DeepFilterNet3 config {path} is incomplete:\n  " + "\n  ".join(bad))
+    return cfg
+
+
+def check_supported(cfg: dict):
+    """The structure variants the native forward pass implements; anything else raises (no silent approximation)."""
+    bad = []
+    want = {"conv_depthwise": True, "convt_depthwise": True, "enc_concat": False, "df_n_iter": 1, "mask_pf": False,
+            "emb_gru_skip_enc": "none", "emb_gru_skip": "none"}
+    for k, v in want.items():
+        if cfg[k] != v:
+            bad.append(f"{k} = {cfg[k]!r} (supported: {v!r})")
+    if cfg["df_gru_skip"] not in ("none", "groupedlinear"):
+        bad.append(f"df_gru_skip = {cfg['df_gru_skip']!r} (supported: 'none', 'groupedlinear')")
+    if cfg["convt_kernel"][0] != 1:
+        bad.append(f"convt_kernel = {cfg['convt_kernel']} (time extent must be 1)")
+    if cfg["fft_size"] % cfg["hop_size"] or cfg["fft_size"] % 2:
+        bad.append(f"fft_size {cfg['fft_size']} must be even and a multiple of hop_size {cfg['hop_size']}")
+    if cfg["nb_erb"] % 4 or cfg["nb_df"] % 2 or cfg["nb_erb"] > 64:
+        bad.append(f"nb_erb = {cfg['nb_erb']} (multiple of 4, <= 64), nb_df = {cfg['nb_df']} (even)")
+    if cfg["nb_df"] > cfg["fft_size"] // 2 + 1 or cfg["fft_size"] > 4096:
+        bad.append(f"nb_df = {cfg['nb_df']} / fft_size = {cfg['fft_size']} out of range")
+    for k in ("emb_hidden_dim", "df_hidden_dim"):
+        if cfg[k] > 256 or cfg[k] % 4:
+            bad.append(f"{k} = {cfg[k]} (the recurrence kernel holds H <= 256, H % 4 == 0)")
+    if cfg["conv_lookahead"] < 0 or cfg["df_lookahead"] < 0 or cfg["df_lookahead"] > cfg["df_order"] - 1:
+        bad.append(f"conv_lookahead = {cfg['conv_lookahead']}, df_lookahead = {cfg['df_lookahead']} out of range")
+    if bad:
+        raise RuntimeError("DeepFilterNet3 config not supported by the native forward pass:\n  " + "\n  ".join(bad))
+
+
+def norm_alpha(cfg: dict) -> float:
+    """df.utils.get_norm_alpha: exp(-hop / (sr tau)) rounded to the fewest decimals (from 3) that keep it below 1."""
+    a_ = math.exp(-cfg["hop_size"] / (cfg["sr"] * cfg["norm_tau"]))
+    prec, a = 3, 1.0
+    while a >= 1.0:
+        a = round(a_, prec)
+        prec += 1
+    return a
+
+
+def erb_widths(sr: int, fft_size: int, nb_bands: int, min_nb_freqs: int) -> List[int]:
+    """libdf's erb_fb band widths (float32 arithmetic like the Rust original); they sum to fft_size / 2 + 1."""
+    f32 = np.float32
+    def freq2erb(f):
+        return f32(9.265) * f32(np.log1p(f32(f) / (f32(24.7) * f32(9.265))))
+    def erb2freq(e):
+        return f32(24.7) * f32(9.265) * (f32(np.exp(f32(e) / f32(9.265))) - f32(1.0))
+    freq_width = f32(sr) / f32(fft_size)
+    lo, hi = freq2erb(0.0), freq2erb(sr // 2)
+    step = (hi - lo) / f32(nb_bands)
+    widths, prev, over = [], 0, 0
+    for i in range(1, nb_bands + 1):
+        fb = int(np.round(erb2freq(lo + f32(i) * step) / freq_width))
+        nb = fb - prev - over
+        if nb < min_nb_freqs:
+            over = min_nb_freqs - nb
+            nb = min_nb_freqs
+        else:
+            over = 0
+        widths.append(nb)
+        prev = fb
+    widths[-1] += 1
+    too_large = sum(widths) - (fft_size // 2 + 1)
+    if too_large > 0:
+        widths[-1] -= too_large
+    if sum(widths) != fft_size // 2 + 1 or min(widths) < 1:
+        raise RuntimeError(f"ERB widths {widths} do not tile {fft_size // 2 + 1} bins")
+    return widths
+
+
+def erb_matrices(widths: List[int]) -> Tuple[torch.Tensor, torch.Tensor]:
+    """df.modules.erb_fb: (forward [F, E] normalised per band, inverse [E, F] of ones) as DfNet registers them."""
+    n = sum(widths)
+    fb = torch.zeros(n, len(widths))
+    b = 0
+    for i, w in enumerate(widths):
+        fb[b:b + w, i] = 1.0
+        b += w
+    return fb / fb.sum(dim=0), fb.t().contiguous()
+
+
+def derived_vars(cfg: dict) -> dict:
+    """Names the key table's shape expressions use."""
+    v = dict(cfg)
+    v.update(kt_inp=cfg["conv_kernel_inp"][0], kf_inp=cfg["conv_kernel_inp"][1], kt=cfg["conv_kernel"][0], kf=cfg["conv_kernel"][1],
+             n_freqs=cfg["fft_size"] // 2 + 1, emb_dim=cfg["conv_ch"] * cfg["nb_erb"] // 4, df_out_ch=2 * cfg["df_order"],
+             df_path_groups=math.gcd(cfg["conv_ch"], 2 * cfg["df_order"]), enc_gru_layers=1, erb_gru_layers=cfg["emb_num_layers"] - 1)
+    return v
+
+
+# ------------------------------------------------------------------------------------------------ key table
+def expected_table(cfg: dict, keymap_path: Optional[Path] = None) -> Dict[str, Tuple[int, ...]]:
+    """{tensor name: shape} the key table prescribes for this config."""
+    spec = json.loads(Path(keymap_path or KEYMAP_PATH).read_text(encoding="utf-8"))
+    env = derived_vars(cfg)
+    ev = lambda s: int(eval(str(s), {"__builtins__": {}}, env))      # noqa: S307 (repo-owned JSON, integer expressions)
+    out = {}
+    for e in spec["entries"]:
+        if "when" in e and not eval(e["when"], {"__builtins__": {}}, env):  # noqa: S307
+            continue
+        shape = tuple(ev(s) for s in e["shape"])
+        if "layers" in e:
+            for k in range(env[e["layers"]]):
+                out[e["name"].replace("{k}", str(k))] = shape
+        else:
+            out[e["name"]] = shape
+    return out
+
+
+def layer_table(sd: Dict[str, torch.Tensor]) -> dict:
+    """Layer counts and widths read from the tensor shapes alone (no config)."""
+    def nlayers(prefix):
+        return len([k for k in sd if re.fullmatch(re.escape(prefix) + r"\.weight_hh_l\d+", k)])
+    t = {}
+    def get(name):
+        return sd[name].shape if name in sd else None
+    s = get("enc.erb_conv0.1.weight")
+    if s is not None:
+        t["conv_ch"], t["conv_kernel_inp"] = int(s[0]), (int(s[2]), int(s[3]))
+    s = get("enc.erb_conv1.0.weight")
+    if s is not None:
+        t["conv_kernel"] = (int(s[2]), int(s[3]))
+    s = get("erb_fb")
+    if s is not None:
+        t["fft_size"], t["nb_erb"] = 2 * (int(s[0]) - 1), int(s[1])
+    s = get("enc.emb_gru.gru.weight_hh_l0")
+    if s is not None:
+        t["emb_hidden_dim"] = int(s[1])
+    s = get("df_dec.df_gru.gru.weight_hh_l0")
+    if s is not None:
+        t["df_hidden_dim"] = int(s[1])
+    t["emb_num_layers"] = nlayers("enc.emb_gru.gru") + nlayers("erb_dec.emb_gru.gru")
+    t["df_num_layers"] = nlayers("df_dec.df_gru.gru")
+    s = get("enc.emb_gru.linear_in.0.weight")
+    if s is not None:
+        t["lin_groups"] = int(s[0])
+    s = get("enc.df_fc_emb.0.weight")
+    if s is not None:
+        t["enc_lin_groups"] = int(s[0])
+        if "conv_ch" in t:
+            t["nb_df"] = 2 * int(s[0]) * int(s[1]) // t["conv_ch"]
+    s = get("df_dec.df_convp.1.weight")
+    if s is not None:
+        t["df_order"], t["df_pathway_kernel_size_t"] = int(s[0]) // 2, int(s[2])
+    t["df_gru_skip"] = "groupedlinear" if "df_dec.df_skip.weight" in sd else "none"
+    return t
+
+
+def validate(sd: Dict[str, torch.Tensor], cfg: dict, keymap_path: Optional[Path] = None):
+    """Raise with every unmapped / missing / mismatched tensor and every config field the shapes contradict."""
+    want = expected_table(cfg, keymap_path)
+    unmapped = sorted(k for k in sd if k not in want)
+    missing = sorted(k for k in want if k not in sd)
+    wrong = sorted(f"{k}: checkpoint {tuple(sd[k].shape)} != table {want[k]}" for k in want if k in sd and tuple(sd[k].shape) != want[k])
+    lt = layer_table(sd)
+    conflict = sorted(f"{k}: shapes say {v!r}, config.ini says {cfg[k]!r}" for k, v in lt.items() if k in cfg and cfg[k] != v)
+    if unmapped or missing or wrong or conflict:
+        parts = []
+        for title, lst in (("unmapped tensors", unmapped), ("missing tensors", missing), ("shape mismatches", wrong),
+                           ("config / checkpoint disagreements", conflict)):
+            if lst:
+                parts.append(f"{title} ({len(lst)}):\n    " + "\n    ".join(lst))
+        raise RuntimeError("DeepFilterNet3 checkpoint does not match dfn3_keymap.json / config.ini:\n  " + "\n  ".join(parts))
+    widths = erb_widths(cfg["sr"], cfg["fft_size"], cfg["nb_erb"], cfg["min_nb_erb_freqs"])
+    fb, ifb = erb_matrices(widths)
+    if not (torch.allclose(sd["erb_fb"].float(), fb, atol=1e-6) and torch.allclose(sd["mask.erb_inv_fb"].float(), ifb, atol=1e-6)):
+        raise RuntimeError(f"DeepFilterNet3 checkpoint: erb_fb / mask.erb_inv_fb differ from the ERB bank of config.ini (widths {widths})")
+
+
+def read_state_dict(path: Path) -> Dict[str, torch.Tensor]:
+    sd = torch.load(str(path), map_location="cpu", weights_only=True)
+    for w in ("state_dict", "model"):
+        if isinstance(sd, dict) and w in sd and isinstance(sd[w], dict):
+            sd = sd[w]
+    if not isinstance(sd, dict):
+        raise RuntimeError(f"{path}: not a state dict")
+    return {k.replace("clc_dec", "df_dec"): v for k, v in sd.items() if torch.is_tensor(v)}
+
+
+# ------------------------------------------------------------------------------------------------ packing
+def pack_order(cfg: dict) -> List[Tuple[str, str]]:
+    """(tensor name, kind) in the order egr_dfn3_create reads them (csrc/egr_dfn3.hip, read_weights).  kind "w": the tensor as
+    stored (torch layout, fp32); "bn": a BatchNorm folded to eval-mode per-channel scale then shift."""
+    o = [("enc.erb_conv0.1.weight", "w"), ("enc.erb_conv0.2", "bn")]
+    for i in (1, 2, 3):
+        o += [(f"enc.erb_conv{i}.0.weight", "w"), (f"enc.erb_conv{i}.1.weight", "w"), (f"enc.erb_conv{i}.2", "bn")]
+    o += [("enc.df_conv0.1.weight", "w"), ("enc.df_conv0.2.weight", "w"), ("enc.df_conv0.3", "bn"),
+          ("enc.df_conv1.0.weight", "w"), ("enc.df_conv1.1.weight", "w"), ("enc.df_conv1.2", "bn"), ("enc.df_fc_emb.0.weight", "w")]
+
+    def sq(prefix, n):
+        r = [(f"{prefix}.linear_in.0.weight", "w")]
+        for k in range(n):
+            r += [(f"{prefix}.gru.{p}_l{k}", "w") for p in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")]
+        return r
+    o += sq("enc.emb_gru", 1) + [("enc.emb_gru.linear_out.0.weight", "w")]
+    o += sq("erb_dec.emb_gru", cfg["emb_num_layers"] - 1) + [("erb_dec.emb_gru.linear_out.0.weight", "w")]
+    for i in (3, 2, 1):
+        o += [(f"erb_dec.conv{i}p.0.weight", "w"), (f"erb_dec.conv{i}p.1", "bn"), (f"erb_dec.convt{i}.0.weight", "w"),
+              (f"erb_dec.convt{i}.1.weight", "w"), (f"erb_dec.convt{i}.2", "bn")]
+    o += [("erb_dec.conv0p.0.weight", "w"), ("erb_dec.conv0p.1", "bn"), ("erb_dec.conv0_out.0.weight", "w"), ("erb_dec.conv0_out.1", "bn")]
+    o += sq("df_dec.df_gru", cfg["df_num_layers"])
+    if cfg["df_gru_skip"] == "groupedlinear":
+        o += [("df_dec.df_skip.weight", "w")]
+    o += [("df_dec.df_out.0.weight", "w"), ("df_dec.df_convp.1.weight", "w"), ("df_dec.df_convp.2.weight", "w"), ("df_dec.df_convp.3", "bn")]
+    return o
+
+
+def fold_bn(sd, prefix) -> Tuple[torch.Tensor, torch.Tensor]:
+    w, b = sd[prefix + ".weight"].double(), sd[prefix + ".bias"].double()
+    m, v = sd[prefix + ".running_mean"].double(), sd[prefix + ".running_var"].double()
+    s = w / torch.sqrt(v + BN_EPS)
+    return s, b - m * s
+
+
+def pack(sd: Dict[str, torch.Tensor], cfg: dict) -> np.ndarray:
+    parts = []
+    for name, kind in pack_order(cfg):
+        if kind == "bn":
+            s, t = fold_bn(sd, name)
+            parts += [s.float().reshape(-1), t.float().reshape(-1)]
+        else:
+            parts.append(sd[name].float().reshape(-1))
+    return torch.cat(parts).numpy().astype(np.float32)
+
+
+class DFN3Model:
+    """A validated model directory: config (dict), state dict, ERB widths, norm alpha, packed fp32 weights."""
+
+    def __init__(self, cfg: dict, sd: Dict[str, torch.Tensor], directory: Optional[Path] = None):
+        check_supported(cfg)
+        validate(sd, cfg)
+        self.cfg, self.sd, self.dir = cfg, sd, directory
+        self.widths = erb_widths(cfg["sr"], cfg["fft_size"], cfg["nb_erb"], cfg["min_nb_erb_freqs"])
+        self.alpha = norm_alpha(cfg)
+
+    def packed(self) -> np.ndarray:
+        return pack(self.sd, self.cfg)
+
+
+def load(model_dir: Optional[Path] = None) -> DFN3Model:
+    d = Path(model_dir) if model_dir else discover()
+    if d is None:
+        raise RuntimeError("no DeepFilterNet3 model directory found; searched:\n  " + "\n  ".join(map(str, candidate_dirs())))
+    ck = checkpoint_file(d)
+    if not (d / "config.ini").is_file() or ck is None:
+        raise RuntimeError(f"{d} is not a DeepFilterNet model directory (config.ini + checkpoints/*.ckpt.best)")
+    return DFN3Model(parse_config(d / "config.ini"), read_state_dict(ck), d)

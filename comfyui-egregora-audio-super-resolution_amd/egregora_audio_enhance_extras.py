@@ -1,9 +1,11 @@
 """`Egregora DeepFilterNet Denoise` (the first stage of BASELINE configs[4]) with the
 reference's plugin surface (egregora_audio_enhance_extras.py:450-724, fixture G11).
 
-What runs where: the DeepFilterNet network itself is upstream's PyTorch package (`df`), exactly as in the reference -- it
-is absent from this build's image and is NOT re-implemented here; when `df` is not importable and no enhancer was
-registered with `set_enhancer`, execute() raises.  Everything around the model -- 10 ms RMS VAD with its 95th-percentile
+What runs where: the DeepFilterNet network is, in this order, a backend registered with `set_enhancer`, upstream's PyTorch
+package (`df`) exactly as in the reference, or -- for DeepFilterNet3 when a model directory is found (dfn_weights.discover:
+EGREGORA_DFN_MODEL_DIR, models/audio/deepfilternet/DeepFilterNet3, ~/.cache/DeepFilterNet/DeepFilterNet3) -- the native HIP
+forward pass (dfn_engine.py, egr_dfn3_*), which takes the 48 kHz signal on the device.  With none of them execute() raises.
+Everything around the model -- 10 ms RMS VAD with its 95th-percentile
 normalisation, one-pole smoothing, adaptive strength, equal-power / linear wet-dry gains, clip, post-gain, ceiling limiter,
 and the 48 kHz rate conversion -- runs in libegregora_amd.so (egr_dfn_vad_gains, egr_dfn_mix, egr_resample_poly), with
 float32 roundings placed exactly where numpy places them in the reference (oracle/dfn_mix.py reproduces G11 bit for bit).
@@ -24,7 +26,7 @@ _ENHANCER: Optional[Callable[[torch.Tensor, str], torch.Tensor]] = None
 
 def set_enhancer(fn: Optional[Callable[[torch.Tensor, str], torch.Tensor]]):
     """Register the denoiser backend: fn(x48 [1,T] float32 CPU tensor, model_name) -> [1,T] tensor.  None restores the
-    default (upstream `df.enhance`)."""
+    default (upstream `df.enhance`, else the native DeepFilterNet3 when a model directory is found)."""
     global _ENHANCER
     _ENHANCER = fn
 
@@ -127,13 +129,19 @@ class Egregora_DeepFilterNet_Denoise:
             return "cuda:0" if torch.cuda.is_available() else "cpu"
         return choice
 
-    def _enhance(self, x48_cpu: torch.Tensor, model_name: str, dev: str) -> torch.Tensor:
-        """The denoiser proper: a registered backend, else upstream DeepFilterNet as the reference drives it (:509-517,636-647)."""
+    def _enhance(self, x48: torch.Tensor, model_name: str, dev: str) -> torch.Tensor:
+        """The denoiser proper on x48 [C, T] (device): a registered backend, else upstream DeepFilterNet as the reference drives it
+        (:509-517,636-647), else the native DeepFilterNet3 when a model directory is found."""
         if _ENHANCER is not None:
+            x48_cpu = x48.cpu()
             return torch.cat([_ENHANCER(x48_cpu[c:c + 1], model_name) for c in range(x48_cpu.shape[0])], 0)
         try:
             from df.enhance import enhance, init_df
         except Exception as e:      # noqa: BLE001
+            from . import dfn_engine, dfn_weights
+            model_dir = dfn_weights.discover(model_name)
+            if model_dir is not None:
+                return dfn_engine.engine(model_dir, x48.device.index).enhance(x48)
             raise RuntimeError("DeepFilterNet (python package `df`) is not installed; this pack runs the stage around the "
                                "model on the GPU but does not re-implement the upstream network "
                                "(register one with egregora_audio_enhance_extras.set_enhancer).") from e
@@ -142,6 +150,7 @@ class Egregora_DeepFilterNet_Denoise:
             model, df_state, _ = init_df(model_name, config_allow_defaults=True)
             self._DF_CACHE[key] = (model.to(dev).eval(), df_state)
         model, df_state = self._DF_CACHE[key]
+        x48_cpu = x48.cpu()
         with torch.no_grad():
             return torch.cat([enhance(model, df_state, x48_cpu[c:c + 1]) for c in range(x48_cpu.shape[0])], 0)
 
@@ -157,7 +166,7 @@ class Egregora_DeepFilterNet_Denoise:
         dry = wav.reshape(-1, T).to(torch.float32).contiguous().cuda()
         dry48 = resample.resample_hq(dry, sr, 48000) if sr != 48000 else dry
         dev = self._pick_device(device)
-        wet48 = self._enhance(dry48.cpu(), dfn_model, dev).to(torch.float32).cuda().contiguous()
+        wet48 = self._enhance(dry48.contiguous(), dfn_model, dev).to(torch.float32).cuda().contiguous()
         wet = resample.resample_hq(wet48, 48000, sr) if sr != 48000 else wet48
         if wet.shape[1] != T:                      # polyphase lengths can differ by a sample after the round trip
             wet = torch.nn.functional.pad(wet, (0, max(0, T - wet.shape[1])))[:, :T].contiguous()

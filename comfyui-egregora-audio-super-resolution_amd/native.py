@@ -48,6 +48,12 @@ SIGNATURES = {
     "egr_dfn_workspace_bytes": (C.c_size_t, [_i, _i64]),
     "egr_dfn_vad_gains": (_i, [_vp, _i, _i64, C.c_double, _i, C.c_double, C.c_double, C.c_double, _i, _vp, _vp, _vp, _vp]),
     "egr_dfn_mix": (_i, [_vp, _vp, _vp, _vp, _i, _i64, _i64, _i, _f, _i, _i, C.c_double, _vp, _vp, _vp]),
+    "egr_dfn3_create": (_i, [C.POINTER(_vp), _vp, _vp, _i64, _i]),
+    "egr_dfn3_workspace_bytes": (C.c_size_t, [_vp, _i, _i64]),
+    "egr_dfn3_enhance": (_i, [_vp, _vp, _i, _i64, _vp, _vp]),
+    "egr_dfn3_stage": (_i, [_vp, _i, _vp, _i64, C.POINTER(_i64), _vp]),
+    "egr_dfn3_time_gru": (_i, [_vp, _i, _i, _i64, C.POINTER(C.c_double)]),
+    "egr_dfn3_destroy": (_i, [_vp]),
     "egr_shift_fir": (_i, [_vp, _i, _i64, _i64, _vp, _i, _vp, _i64, _vp]),
     "egr_gcc_phat": (_i, [_vp, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp]),
     "egr_band_filter": (_i, [_vp, _vp, _i64, _vp, _vp]),
@@ -159,6 +165,20 @@ class FlashSRConfigC(C.Structure):
 class TensorDescC(C.Structure):
     """egr_tensor_desc."""
     _fields_ = [("name", C.c_char_p), ("data", _vp), ("ndim", _i), ("shape", _i64 * 4)]
+
+
+DFN3_MAX_ERB = 64
+DFN3_STAGE = {"spec": 0, "feat_erb": 1, "feat_spec": 2, "e0": 3, "e1": 4, "e2": 5, "e3": 6, "c0": 7, "emb": 8, "mask": 9, "coefs": 10,
+              "spec_e": 11, "gru0": 16}
+
+
+class Dfn3ConfigC(C.Structure):
+    """egr_dfn3_config (include/egregora_amd.h)."""
+    _fields_ = [("struct_bytes", _i), ("sr", _i), ("fft_size", _i), ("hop_size", _i), ("nb_erb", _i), ("nb_df", _i), ("df_order", _i),
+                ("df_lookahead", _i), ("conv_lookahead", _i), ("conv_ch", _i), ("kt_inp", _i), ("kf_inp", _i), ("kt", _i), ("kf", _i),
+                ("convt_kf", _i), ("emb_hidden_dim", _i), ("emb_num_layers", _i), ("df_hidden_dim", _i), ("df_num_layers", _i),
+                ("df_gru_skip", _i), ("lin_groups", _i), ("enc_lin_groups", _i), ("df_pathway_kt", _i), ("path_groups", _i),
+                ("df_path_groups", _i), ("norm_alpha", _f), ("erb_widths", _i * DFN3_MAX_ERB)]
 
 
 def flashsr_config_c(cfg) -> FlashSRConfigC:

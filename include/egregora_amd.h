@@ -171,6 +171,49 @@ int egr_dfn_mix(const float* dry, const float* wet, const float* g_dry, const fl
                 int64_t n_frames, int hop, float post_gain, int use_gain, int limit, double ceiling, float* y, void* peak_ws,
                 void* stream);
 
+/* DeepFilterNet3 forward pass (csrc/egr_dfn3.hip; SPEC.md "DeepFilterNet3 (UPSTREAM-RECALL)"): what df.enhance.enhance(model, df_state, x)
+ * computes on x48 [C][T] (48 kHz, device fp32), channels independent, including enhance's n_fft right pad and n_fft - hop trim.
+ *   egr_dfn3_create  : config (every field from config.ini / the checkpoint's shapes, dfn_weights.py) + the packed fp32 weights in
+ *                      dfn_weights.pack_order order (BatchNorms folded to scale, shift) -> a handle on `device` (uploads; synchronous)
+ *   egr_dfn3_enhance : y [C][T]; enqueued on `stream`, nothing synchronises.  The current device must be the handle's.  The handle
+ *                      owns its workspace (grown with hipMallocAsync on `stream`): one call at a time per handle, one stream per handle
+ *   egr_dfn3_workspace_bytes : that workspace for (C, T)
+ *   egr_dfn3_stage   : copy an intermediate of the LAST enhance call (EGR_DFN3_STAGE_*; GRU layer g at EGR_DFN3_STAGE_GRU0 + g, layers
+ *                      in the order encoder, ERB decoder, DF decoder) into dst (device, `capacity` floats) on `stream`; dst NULL: only
+ *                      *count.  Layouts are channels-last: [C][nF][F][ch], complex as (re, im) pairs
+ *   egr_dfn3_time_gru: one recurrence layer alone on zero projections, `steps` steps x `channels` workgroups, timed with events
+ *                      (synchronous; a tool, not a pipeline call) */
+#define EGR_DFN3_MAX_ERB 64
+#define EGR_DFN3_MAX_GRU 8
+#define EGR_DFN3_STAGE_SPEC 0
+#define EGR_DFN3_STAGE_FEAT_ERB 1
+#define EGR_DFN3_STAGE_FEAT_SPEC 2
+#define EGR_DFN3_STAGE_E0 3
+#define EGR_DFN3_STAGE_E1 4
+#define EGR_DFN3_STAGE_E2 5
+#define EGR_DFN3_STAGE_E3 6
+#define EGR_DFN3_STAGE_C0 7
+#define EGR_DFN3_STAGE_EMB 8
+#define EGR_DFN3_STAGE_MASK 9
+#define EGR_DFN3_STAGE_COEFS 10
+#define EGR_DFN3_STAGE_SPEC_E 11
+#define EGR_DFN3_STAGE_GRU0 16
+typedef struct egr_dfn3_config {
+    int struct_bytes;                      /* sizeof(egr_dfn3_config) */
+    int sr, fft_size, hop_size, nb_erb, nb_df, df_order, df_lookahead, conv_lookahead;
+    int conv_ch, kt_inp, kf_inp, kt, kf, convt_kf;
+    int emb_hidden_dim, emb_num_layers, df_hidden_dim, df_num_layers, df_gru_skip;     /* df_gru_skip: 0 none, 1 groupedlinear */
+    int lin_groups, enc_lin_groups, df_pathway_kt, path_groups, df_path_groups;
+    float norm_alpha;
+    int erb_widths[EGR_DFN3_MAX_ERB];
+} egr_dfn3_config;
+int egr_dfn3_create(void** handle, const egr_dfn3_config* cfg, const float* packed, int64_t n_floats, int device);
+size_t egr_dfn3_workspace_bytes(void* handle, int channels, int64_t n);
+int egr_dfn3_enhance(void* handle, const float* x48, int channels, int64_t n, float* y, void* stream);
+int egr_dfn3_stage(void* handle, int stage, float* dst, int64_t capacity, int64_t* count, void* stream);
+int egr_dfn3_time_gru(void* handle, int layer, int channels, int64_t steps, double* us_per_step);
+int egr_dfn3_destroy(void* handle);
+
 /* Linear-interpolation resampler of the "Resample Audio (HQ)" node's fallback branch: y[c][j] = np.interp at
  * j * n_in / n_out input samples, clamped to the last sample (egregora_audio_eval_pack.py:515-519). */
 int egr_resample_linear(const float* x, int channels, int64_t n_in, float* y, int64_t n_out, void* stream);

@@ -12,6 +12,8 @@ fraction of PCM_16 samples that differ.  Until someone runs this, parity with up
 every disagreement maps to one named field of oracle.fatllama.FatLlamaSpec (factor rounding, interpolation kernel, threshold
 reference / kind, autoscale / normalise definitions, PCM scales); `--variants` sweeps the device-side readings of SPEC.md
 section 3.  `--flashsr CKPT_DIR` does the same for FlashSR through the node's own checkpoint loader (flashsr_weights.load).
+`--dfn3 MODEL_DIR` runs upstream `df.enhance.enhance` and the native DeepFilterNet3 forward pass (dfn_engine, dfn_weights.load) on
+the same seeded input and prints the relative error per channel (SPEC.md section 4b; parity unpinned until this has been run).
 """
 import argparse
 import sys
@@ -35,9 +37,14 @@ def main():
     ap.add_argument("--flashsr", default="", metavar="CKPT_DIR",
                     help="instead: compare FlashSR_Inference (importable) with this pack on one seeded chunk; CKPT_DIR holds "
                          "student_ldm.pth / sr_vocoder.pth / vae.pth and is read through flashsr_weights.load (the node's loader)")
+    ap.add_argument("--dfn3", default="", metavar="MODEL_DIR",
+                    help="instead: compare upstream df.enhance.enhance (importable) with the native DeepFilterNet3 on MODEL_DIR "
+                         "(config.ini + checkpoints/*.ckpt.best)")
     args = ap.parse_args()
     if args.flashsr:
         return compare_flashsr(args.flashsr)
+    if args.dfn3:
+        return compare_dfn3(args.dfn3, args.seconds)
     try:
         import soundfile as sf
         from fat_llama_fftw.audio_fattener import feed
@@ -78,6 +85,32 @@ def main():
         print(f"[{combo or 'default'}] upstream {up.shape} @ {sr_up} Hz vs this pack {mine.shape} @ {res['sample_rate']} Hz: "
               f"LSD mean/p95 = {lsd[0]:.4g} / {lsd[1]:.4g} dB   SI-SDR = {om.si_sdr(up[:m], mine[:m]):.2f} dB   "
               f"PCM_16 samples differing = {np.mean(np.abs(up[:m] - mine[:m]) * 32768 > 0.5):.4f}")
+
+
+def compare_dfn3(model_dir, seconds):
+    """Upstream DeepFilterNet3 (df.enhance with the checkpoint in MODEL_DIR) vs the native forward pass, 48 kHz stereo."""
+    import torch
+    try:
+        from df.enhance import enhance, init_df
+    except Exception as e:
+        sys.exit(f"df (DeepFilterNet) not importable here ({e}); this tool is opt-in")
+    from packload import load_pack
+    load_pack()
+    from egregora_amd import dfn_engine, dfn_weights
+    rng = np.random.Generator(np.random.PCG64(1234))
+    n = int(seconds * 48000)
+    t = np.arange(n) / 48000.0
+    x = np.stack([0.3 * np.sin(2 * np.pi * (220 + 30 * c) * t) * (0.5 + 0.5 * np.sin(2 * np.pi * 1.7 * t)) + 0.05 * rng.standard_normal(n)
+                  for c in range(2)]).astype(np.float32)
+    model, df_state, _ = init_df(model_dir, config_allow_defaults=False)
+    model = model.eval()
+    with torch.no_grad():
+        up = torch.cat([enhance(model, df_state, torch.from_numpy(x[c:c + 1])) for c in range(2)], 0).numpy()
+    eng = dfn_engine.Dfn3Engine(dfn_weights.load(Path(model_dir)), torch.cuda.current_device())
+    ours = eng.enhance(torch.from_numpy(x).cuda()).cpu().numpy()
+    for c in range(2):
+        e = float(np.linalg.norm(ours[c] - up[c]) / max(np.linalg.norm(up[c]), 1e-30))
+        print(f"channel {c}: relative rms error native vs df {e:.3e} (max abs {float(np.abs(ours[c] - up[c]).max()):.3e})")
 
 
 def compare_flashsr(ckpt_dir):
