@@ -31,6 +31,7 @@ constexpr int GRU_NLDS = 2 * GRU_K;                         // tasks 3-4 in LDS 
 constexpr int GRU_NGLB = GRU_TASKS * GRU_K - GRU_NREG - GRU_NLDS;   // tasks 5-11 streamed from L2 every step (448 KiB)
 constexpr int GRU_PER_THREAD = GRU_TASKS * GRU_K;           // 192
 static_assert(GRU_NGLB % GRU_K == 0 && GRU_NGLB > 0, "streamed W_hh part is whole tasks");
+constexpr int DFN_LDS_MAX = 152 * 1024;                     // dynamic LDS cap: a gfx950 CU's 160 KiB minus room for static arrays
 
 // ------------------------------------------------------------------------------------------------ analysis / features
 __global__ __launch_bounds__(256) void k_dfn_analysis(const float* __restrict__ x, int64_t T, int nF, int N, int hop,
@@ -596,7 +597,10 @@ extern "C" int egr_dfn3_create(void** handle, const egr_dfn3_config* cfg, const 
     EGR_CHECK(c.df_order >= 1 && c.df_lookahead >= 0 && c.df_lookahead < c.df_order && c.conv_lookahead >= 0, EGR_ERR_UNSUPPORTED,
               "egr_dfn3: df_order / lookaheads");
     EGR_CHECK(ch > 0 && c.lin_groups > 0 && c.enc_lin_groups > 0 && c.path_groups > 0 && ch % c.path_groups == 0 && c.df_path_groups > 0 &&
-              ch % c.df_path_groups == 0 && O2 % c.df_path_groups == 0 && c.convt_kf == c.kf, EGR_ERR_UNSUPPORTED, "egr_dfn3: conv groups");
+              ch % c.df_path_groups == 0 && O2 % c.df_path_groups == 0, EGR_ERR_UNSUPPORTED, "egr_dfn3: conv groups");
+    // a stride-2 transposed conv with padding kf / 2 and output_padding kf / 2 doubles the width only for kf = 3 (torch refuses
+    // output_padding >= stride for the wider kernels)
+    EGR_CHECK(c.convt_kf == 3, EGR_ERR_UNSUPPORTED, "egr_dfn3: transposed conv kernel width %d (supported: 3)", c.convt_kf);
     EGR_CHECK(c.kf % 2 == 1 && c.kf_inp % 2 == 1 && c.kt >= 1 && c.kt_inp >= 1 && c.df_pathway_kt >= 1, EGR_ERR_UNSUPPORTED,
               "egr_dfn3: frequency kernels must be odd (same-size padding)");
     int wsum = 0;
@@ -705,6 +709,25 @@ extern "C" int egr_dfn3_create(void** handle, const egr_dfn3_config* cfg, const 
         hipMemcpy(m->dev_w, img.data(), sizeof(float) * total, hipMemcpyHostToDevice) != hipSuccess) {
         set_error("egr_dfn3_create: device allocation / upload failed on device %d", device);
         if (m->dev_w) (void)hipFree(m->dev_w);
+        (void)hipSetDevice(prev);
+        delete m;
+        return EGR_ERR_HIP;
+    }
+    // the analysis / synthesis DFTs keep a frame and the twiddles in dynamic LDS: 24 N and 16 (1.5 N + 1) bytes, above the 64 KiB
+    // default from N = 2732 on.  The attribute is a process-wide cap per kernel, so it is raised to the CU's maximum (as the Fat-Llama
+    // plans do), never to this config's need.
+    const size_t lds_an = (size_t)N * 24, lds_syn = (size_t)(m->Fq + N) * 16;
+    hipError_t ea = hipSuccess;
+    if (lds_an > (size_t)DFN_LDS_MAX || lds_syn > (size_t)DFN_LDS_MAX) {
+        set_error("egr_dfn3_create: fft_size %d needs %zu / %zu bytes of LDS (limit %d)", N, lds_an, lds_syn, DFN_LDS_MAX);
+        ea = hipErrorInvalidValue;
+    }
+    if (ea == hipSuccess) ea = hipFuncSetAttribute((const void*)k_dfn_analysis, hipFuncAttributeMaxDynamicSharedMemorySize, DFN_LDS_MAX);
+    if (ea == hipSuccess) ea = hipFuncSetAttribute((const void*)k_dfn_synth, hipFuncAttributeMaxDynamicSharedMemorySize, DFN_LDS_MAX);
+    if (ea != hipSuccess) {
+        if (lds_an <= (size_t)DFN_LDS_MAX && lds_syn <= (size_t)DFN_LDS_MAX)
+            set_error("egr_dfn3_create: hipFuncSetAttribute(MaxDynamicSharedMemorySize) -> %s", hipGetErrorString(ea));
+        (void)hipFree(m->dev_w);
         (void)hipSetDevice(prev);
         delete m;
         return EGR_ERR_HIP;

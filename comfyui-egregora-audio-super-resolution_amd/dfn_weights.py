@@ -121,29 +121,64 @@ def parse_config(path: Path) -> dict:
     return cfg
 
 
+MAX_GRU_LAYERS = 8                  # EGR_DFN3_MAX_GRU (include/egregora_amd.h)
+MAX_NB_ERB = 64                     # EGR_DFN3_MAX_ERB
+
+
 def check_supported(cfg: dict):
-    """The structure variants the native forward pass implements; anything else raises (no silent approximation)."""
+    """The structure variants the native forward pass implements; anything else raises (no silent approximation).  Accepts exactly
+    what egr_dfn3_create and its run() accept and upstream can build; every accepted variant runs (tests/test_gpu_dfn3_configs.py)."""
     bad = []
     want = {"conv_depthwise": True, "convt_depthwise": True, "enc_concat": False, "df_n_iter": 1, "mask_pf": False,
             "emb_gru_skip_enc": "none", "emb_gru_skip": "none"}
     for k, v in want.items():
         if cfg[k] != v:
             bad.append(f"{k} = {cfg[k]!r} (supported: {v!r})")
+    if not cfg["norm_tau"] > 0:
+        bad.append(f"norm_tau = {cfg['norm_tau']} (> 0)")
+    if cfg["sr"] != 48000:
+        bad.append(f"sr = {cfg['sr']} (the node always hands the model a 48 kHz signal)")
     if cfg["df_gru_skip"] not in ("none", "groupedlinear"):
         bad.append(f"df_gru_skip = {cfg['df_gru_skip']!r} (supported: 'none', 'groupedlinear')")
-    if cfg["convt_kernel"][0] != 1:
-        bad.append(f"convt_kernel = {cfg['convt_kernel']} (time extent must be 1)")
-    if cfg["fft_size"] % cfg["hop_size"] or cfg["fft_size"] % 2:
-        bad.append(f"fft_size {cfg['fft_size']} must be even and a multiple of hop_size {cfg['hop_size']}")
-    if cfg["nb_erb"] % 4 or cfg["nb_df"] % 2 or cfg["nb_erb"] > 64:
-        bad.append(f"nb_erb = {cfg['nb_erb']} (multiple of 4, <= 64), nb_df = {cfg['nb_df']} (even)")
-    if cfg["nb_df"] > cfg["fft_size"] // 2 + 1 or cfg["fft_size"] > 4096:
+    if tuple(cfg["convt_kernel"]) != (1, 3):
+        bad.append(f"convt_kernel = {cfg['convt_kernel']} (supported: (1, 3), the only width a stride-2 transposed conv doubles)")
+    for k in ("conv_kernel", "conv_kernel_inp"):
+        kt, kf = cfg[k]
+        if kt < 1 or kf < 1 or kf % 2 == 0:
+            bad.append(f"{k} = {cfg[k]} (time extent >= 1, odd frequency extent)")
+    if cfg["df_pathway_kernel_size_t"] < 1:
+        bad.append(f"df_pathway_kernel_size_t = {cfg['df_pathway_kernel_size_t']} (>= 1)")
+    if cfg["hop_size"] < 1 or cfg["fft_size"] < 2 or cfg["fft_size"] % cfg["hop_size"] or cfg["fft_size"] % 2 or cfg["fft_size"] > 4096:
+        bad.append(f"fft_size {cfg['fft_size']} must be even, <= 4096 and a multiple of hop_size {cfg['hop_size']}")
+    if cfg["nb_erb"] < 4 or cfg["nb_erb"] % 4 or cfg["nb_erb"] > MAX_NB_ERB or cfg["nb_df"] < 2 or cfg["nb_df"] % 2:
+        bad.append(f"nb_erb = {cfg['nb_erb']} (multiple of 4, <= {MAX_NB_ERB}), nb_df = {cfg['nb_df']} (even)")
+    if cfg["nb_df"] > cfg["fft_size"] // 2 + 1:
         bad.append(f"nb_df = {cfg['nb_df']} / fft_size = {cfg['fft_size']} out of range")
     for k in ("emb_hidden_dim", "df_hidden_dim"):
-        if cfg[k] > 256 or cfg[k] % 4:
-            bad.append(f"{k} = {cfg[k]} (the recurrence kernel holds H <= 256, H % 4 == 0)")
-    if cfg["conv_lookahead"] < 0 or cfg["df_lookahead"] < 0 or cfg["df_lookahead"] > cfg["df_order"] - 1:
-        bad.append(f"conv_lookahead = {cfg['conv_lookahead']}, df_lookahead = {cfg['df_lookahead']} out of range")
+        if not 1 <= cfg[k] <= 256:
+            bad.append(f"{k} = {cfg[k]} (the recurrence kernel holds 1 <= H <= 256)")
+    n_gru = cfg["emb_num_layers"] + cfg["df_num_layers"]
+    if cfg["emb_num_layers"] < 2 or cfg["df_num_layers"] < 1 or n_gru > MAX_GRU_LAYERS:
+        bad.append(f"emb_num_layers = {cfg['emb_num_layers']} (>= 2: one encoder layer, at least one ERB-decoder layer), "
+                   f"df_num_layers = {cfg['df_num_layers']} (>= 1), {n_gru} GRU layers in total (<= {MAX_GRU_LAYERS})")
+    if cfg["df_order"] < 1 or cfg["conv_lookahead"] < 0 or cfg["df_lookahead"] < 0 or cfg["df_lookahead"] > cfg["df_order"] - 1:
+        bad.append(f"df_order = {cfg['df_order']}, conv_lookahead = {cfg['conv_lookahead']}, df_lookahead = {cfg['df_lookahead']} "
+                   "out of range")
+    if cfg["conv_ch"] < 1 or cfg["lin_groups"] < 1 or cfg["enc_lin_groups"] < 1:
+        bad.append(f"conv_ch = {cfg['conv_ch']}, lin_groups = {cfg['lin_groups']}, enc_lin_groups = {cfg['enc_lin_groups']} (>= 1)")
+    elif not bad:
+        # every grouped linear (GroupedLinearEinsum) splits its input and its output evenly over its groups
+        emb = cfg["conv_ch"] * cfg["nb_erb"] // 4
+        G, Ge = cfg["lin_groups"], cfg["enc_lin_groups"]
+        lins = [("enc.df_fc_emb", cfg["conv_ch"] * cfg["nb_df"] // 2, emb, Ge),
+                ("emb_gru linear_in", emb, cfg["emb_hidden_dim"], G), ("emb_gru linear_out", cfg["emb_hidden_dim"], emb, G),
+                ("df_gru linear_in", emb, cfg["df_hidden_dim"], G),
+                ("df_out", cfg["df_hidden_dim"], cfg["nb_df"] * 2 * cfg["df_order"], G)]
+        if cfg["df_gru_skip"] == "groupedlinear":
+            lins.append(("df_skip", emb, cfg["df_hidden_dim"], G))
+        for name, i, o, g in lins:
+            if i % g or o % g:
+                bad.append(f"{name}: {i} -> {o} features do not split over {g} groups")
     if bad:
         raise RuntimeError("DeepFilterNet3 config not supported by the native forward pass:\n  " + "\n  ".join(bad))
 
@@ -203,6 +238,7 @@ def derived_vars(cfg: dict) -> dict:
     """Names the key table's shape expressions use."""
     v = dict(cfg)
     v.update(kt_inp=cfg["conv_kernel_inp"][0], kf_inp=cfg["conv_kernel_inp"][1], kt=cfg["conv_kernel"][0], kf=cfg["conv_kernel"][1],
+             convt_kt=cfg["convt_kernel"][0], convt_kf=cfg["convt_kernel"][1],
              n_freqs=cfg["fft_size"] // 2 + 1, emb_dim=cfg["conv_ch"] * cfg["nb_erb"] // 4, df_out_ch=2 * cfg["df_order"],
              df_path_groups=math.gcd(cfg["conv_ch"], 2 * cfg["df_order"]), enc_gru_layers=1, erb_gru_layers=cfg["emb_num_layers"] - 1)
     return v

@@ -4,25 +4,17 @@ Synthetic model directory (DeepFilterNet3-default config.ini, seeded random weig
 rms error against the float64 restatement is at most 1.5x the float32 restatement's own error plus a few float32 ulps, and below an
 absolute cap.  Stages are read back with egr_dfn3_stage after one enhance call, so each carries the error of everything before it.
 """
+import gc
 import math
 
-import numpy as np
 import pytest
 import torch
 
+import dfn3_check as K
 import dfn3_torch as R
+from dfn3_check import CAP, FLOOR, gate, nhwc, rel, speechy   # noqa: F401 (the gates and the signal every DFN3 GPU test uses)
 
 pytestmark = pytest.mark.gpu
-FLOOR, CAP = 3e-7, 1e-4
-
-
-def speechy(seed, n, C, sr=48000):
-    rng = np.random.Generator(np.random.PCG64(seed))
-    t = np.arange(n) / sr
-    env = 0.5 + 0.5 * np.sin(2 * np.pi * 2.3 * t) ** 2
-    x = np.stack([env * sum(np.sin(2 * np.pi * f * (1 + 0.01 * c) * t) / (k + 1) for k, f in enumerate((150, 310, 620, 1240, 2900)))
-                  + 0.05 * rng.standard_normal(n) for c in range(C)])
-    return torch.from_numpy((0.4 * x / np.abs(x).max()).astype(np.float32))
 
 
 @pytest.fixture(scope="module")
@@ -33,21 +25,6 @@ def model(pack, tmp_path_factory):
     cfg, sd = R.write_model_dir(d, seed=5)
     eng = dfn_engine.Dfn3Engine(dfn_weights.load(d), torch.cuda.current_device())
     return d, cfg, sd, eng
-
-
-def rel(a, ref):
-    a, ref = a.double().cpu().reshape(-1), ref.double().cpu().reshape(-1)
-    return float((a - ref).norm() / max(float(ref.norm()), 1e-300))
-
-
-def gate(name, got, r64, r32, floor=FLOOR, cap=CAP):
-    e, e32 = rel(got, r64), rel(r32, r64)
-    assert e <= 1.5 * e32 + floor and e <= cap, (name, e, e32)
-    return e, e32
-
-
-def nhwc(t):
-    return t.permute(0, 2, 3, 1)
 
 
 def test_every_stage_against_the_float64_restatement(model):
@@ -162,3 +139,136 @@ def test_c5_cut_down_with_the_denoiser_stage(pack, model, monkeypatch):
     n96 = int(math.ceil(x.shape[1] * 48000 / 44100)) * 2
     assert out["sample_rate"] == 96000 and y.shape[:2] == (1, 2) and abs(y.shape[2] - n96) <= 4 and bool(torch.isfinite(y).all())
     assert 0.0 < float(y.abs().max()) <= 1.0
+
+
+# ------------------------------------------------------------------------------------------------ local gates, edges, engine state
+def _engine(d):
+    from egregora_amd import dfn_engine, dfn_weights
+    return dfn_engine.Dfn3Engine(dfn_weights.load(d), torch.cuda.current_device())
+
+
+@pytest.fixture(scope="module")
+def model_hop240(pack, tmp_path_factory):
+    from egregora_amd import native
+    native.require_device()
+    d = tmp_path_factory.mktemp("dfn240") / "DeepFilterNet3"
+    cfg, sd = R.write_model_dir(d, seed=5, cfg_text=R.config_text(hop_size=240))
+    return d, cfg, sd, _engine(d)
+
+
+def test_every_stage_against_its_own_restatement(model):
+    """Local gates: each stage restated alone from the device's read-back inputs (dfn3_check.local), so a local precision loss
+    (a fast expf, a changed reduction order) cannot hide under the error accumulated before it."""
+    d, cfg, sd, eng = model
+    x = speechy(1, 48000, 2)
+    y = eng.enhance(x.cuda())
+    torch.cuda.synchronize()
+    cum, dev, _ = K.cumulative(eng, x, y, cfg, sd)
+    loc = K.local(eng, x, y, cfg, sd, dev)
+    print("\nDFN3 local stage errors (rms, rms fp32, max, max fp32) vs float64:", K.fmt(loc))
+
+
+@pytest.mark.parametrize("T", [1, 2, 479, 480, 481, 959, 960, 961])
+@pytest.mark.parametrize("which", ["default", "hop240"])
+def test_short_lengths(model, model_hop240, which, T):
+    d, cfg, sd, eng = model if which == "default" else model_hop240
+    x = speechy(T, T, 2)
+    y = eng.enhance(x.cuda())
+    torch.cuda.synchronize()
+    assert y.shape == x.shape and bool(torch.isfinite(y).all())
+    n, ng = K.stage_counts(cfg, 2, T)
+    assert all(eng.stage(k).numel() == v for k, v in n.items())
+    cum, dev, _ = K.cumulative(eng, x, y, cfg, sd)
+    loc = K.local(eng, x, y, cfg, sd, dev)
+    print(f"\nDFN3 {which} T={T} y (device, fp32): {cum['y'][0]:.2e}/{cum['y'][1]:.2e}; local:", K.fmt(loc))
+
+
+def test_digital_silence_gives_exact_zero(model):
+    """An all-zero input: every stage finite and y exactly zero (spec_e is a product with the all-zero spectrum)."""
+    d, cfg, sd, eng = model
+    x = torch.zeros(2, 2 * 48000)
+    y = eng.enhance(x.cuda())
+    torch.cuda.synchronize()
+    assert not y.any()
+    for name in K.PICK:
+        assert bool(torch.isfinite(eng.stage(name)).all()), name
+    for g in range(K.n_grus(cfg)):
+        assert bool(torch.isfinite(eng.stage("gru0", g)).all()), g
+    assert not eng.stage("spec").any() and not eng.stage("spec_e").any() and not eng.stage("feat_spec").any()
+
+
+def test_long_silence_then_speech_keeps_the_norm_state_finite(pack, tmp_path):
+    """norm_tau 0.1: 12 s of zeros drive the unit-norm state below the float32 normal range (~8 s) into its smallest subnormal,
+    where x / sqrt(s) is 0 / 0 if denormals are ever flushed; the 3 s of speech after it are held to the cumulative gate."""
+    d = tmp_path / "DeepFilterNet3"
+    cfg, sd = R.write_model_dir(d, seed=7, cfg_text=R.config_text(norm_tau=0.1))
+    eng = _engine(d)
+    w = 3 * 48000
+    x = torch.cat([torch.zeros(1, 12 * 48000), speechy(12, w, 1)], 1)
+    y = eng.enhance(x.cuda()).cpu()
+    assert bool(torch.isfinite(y).all())
+    for name in K.PICK:
+        assert bool(torch.isfinite(eng.stage(name)).all()), name
+    y64 = R.enhance(x, cfg, sd, torch.float64)
+    y32 = R.enhance(x, cfg, sd, torch.float32)
+    assert bool(torch.isfinite(y32).all())
+    K.gate("silence + speech", y, y64, y32)
+    K.gate("last 3 s", y[:, -w:], y64[:, -w:], y32[:, -w:])
+    del eng
+    gc.collect()
+
+
+def _square(n):
+    t = torch.arange(n, dtype=torch.float64)
+    return torch.where(torch.sin(2 * torch.pi * 220.0 * t / 48000) >= 0, 1.0, -1.0).float()[None].repeat(2, 1)
+
+
+@pytest.mark.parametrize("level", ["1e-6", "square", "dc"])
+def test_signal_levels(model, level):
+    d, cfg, sd, eng = model
+    s = speechy(21, 48000, 2)
+    x = {"1e-6": s * 1e-6, "square": _square(48000), "dc": s + 0.5}[level].contiguous()
+    y = eng.enhance(x.cuda())
+    torch.cuda.synchronize()
+    assert bool(torch.isfinite(y).all())
+    cum, dev, _ = K.cumulative(eng, x, y, cfg, sd)
+    loc = K.local(eng, x, y, cfg, sd, dev)
+    print(f"\nDFN3 level {level} y (device, fp32): {cum['y'][0]:.2e}/{cum['y'][1]:.2e}; local:", K.fmt(loc))
+
+
+@pytest.mark.parametrize("C", [3, 5, 8])
+def test_channels_are_bit_exact_independent(model, C):
+    """Every kernel computes a (channel, frame) element in a loop order that does not depend on C, and egr_bgemm picks its tile by N
+    alone: each channel of a C-channel call equals that channel run alone, bit for bit."""
+    d, cfg, sd, eng = model
+    x = speechy(30 + C, 48000, C).cuda()
+    y = eng.enhance(x).cpu()
+    for c in range(C):
+        yc = eng.enhance(x[c:c + 1].contiguous()).cpu()
+        assert torch.equal(yc[0], y[c]), (C, c, float((yc[0] - y[c]).abs().max()))
+
+
+def test_engine_state_repeat_regrow_and_interleave(model, model_hop240):
+    """One engine: identical calls give identical bits; 1 s stereo -> 7.3 s mono -> 1 s stereo (the workspace grows, then is reused
+    larger than needed) gives a fresh engine's bits, and stage() reports each call's own element counts.  Two engines of different
+    configs with their calls interleaved each give the bits they give alone."""
+    d, cfg, sd, eng = model
+    d2, cfg2, sd2, eng2 = model_hop240
+    a, b = speechy(41, 48000, 2), speechy(42, int(7.3 * 48000) + 17, 1)
+    fresh = _engine(d)
+    want = {k: fresh.enhance(v.cuda()).cpu() for k, v in (("a", a), ("b", b))}
+    del fresh
+    gc.collect()
+    y1 = eng.enhance(a.cuda()).cpu()
+    y2 = eng.enhance(a.cuda()).cpu()
+    assert torch.equal(y1, y2) and torch.equal(y1, want["a"])
+    for key, x in (("a", a), ("b", b), ("a", a)):
+        y = eng.enhance(x.cuda()).cpu()
+        assert torch.equal(y, want[key]), key
+        n, ng = K.stage_counts(cfg, x.shape[0], x.shape[1])
+        assert {k: eng.stage(k).numel() for k in n} == n
+        assert [eng.stage("gru0", g).numel() for g in range(len(ng))] == ng
+    alone2 = {k: eng2.enhance(v.cuda()).cpu() for k, v in (("a", a), ("b", b))}
+    for key, x in (("b", b), ("a", a), ("a", a), ("b", b)):
+        assert torch.equal(eng.enhance(x.cuda()).cpu(), want[key])
+        assert torch.equal(eng2.enhance(x.cuda()).cpu(), alone2[key])
