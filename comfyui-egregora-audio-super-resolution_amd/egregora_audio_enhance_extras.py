@@ -2,9 +2,11 @@
 reference's plugin surface (egregora_audio_enhance_extras.py:450-724, fixture G11).
 
 What runs where: the DeepFilterNet network is, in this order, a backend registered with `set_enhancer`, upstream's PyTorch
-package (`df`) exactly as in the reference, or -- for DeepFilterNet3 when a model directory is found (dfn_weights.discover:
-EGREGORA_DFN_MODEL_DIR, models/audio/deepfilternet/DeepFilterNet3, ~/.cache/DeepFilterNet/DeepFilterNet3) -- the native HIP
-forward pass (dfn_engine.py, egr_dfn3_*), which takes the 48 kHz signal on the device.  With none of them execute() raises.
+package (`df`) exactly as in the reference, or -- when a model directory of the chosen model is found (EGREGORA_DFN_MODEL_DIR,
+models/audio/deepfilternet/<model>, ~/.cache/DeepFilterNet/<model>) -- the native HIP forward pass, which takes the 48 kHz
+signal on the device: DeepFilterNet3 through dfn_weights.discover and dfn_engine.py (egr_dfn3_*), DeepFilterNet2 (the node's
+default) through dfn2_weights.discover, which takes only a directory whose config.ini says `[train] model = deepfilternet2`, and
+dfn2_engine.py (egr_dfn2_*).  With none of them execute() raises.
 Everything around the model -- 10 ms RMS VAD with its 95th-percentile
 normalisation, one-pole smoothing, adaptive strength, equal-power / linear wet-dry gains, clip, post-gain, ceiling limiter,
 and the 48 kHz rate conversion -- runs in libegregora_amd.so (egr_dfn_vad_gains, egr_dfn_mix, egr_resample_poly), with
@@ -26,7 +28,7 @@ _ENHANCER: Optional[Callable[[torch.Tensor, str], torch.Tensor]] = None
 
 def set_enhancer(fn: Optional[Callable[[torch.Tensor, str], torch.Tensor]]):
     """Register the denoiser backend: fn(x48 [1,T] float32 CPU tensor, model_name) -> [1,T] tensor.  None restores the
-    default (upstream `df.enhance`, else the native DeepFilterNet3 when a model directory is found)."""
+    default (upstream `df.enhance`, else the native DeepFilterNet3 / DeepFilterNet2 when a model directory is found)."""
     global _ENHANCER
     _ENHANCER = fn
 
@@ -131,17 +133,22 @@ class Egregora_DeepFilterNet_Denoise:
 
     def _enhance(self, x48: torch.Tensor, model_name: str, dev: str) -> torch.Tensor:
         """The denoiser proper on x48 [C, T] (device): a registered backend, else upstream DeepFilterNet as the reference drives it
-        (:509-517,636-647), else the native DeepFilterNet3 when a model directory is found."""
+        (:509-517,636-647), else the native DeepFilterNet3 / DeepFilterNet2 when a model directory of that model is found."""
         if _ENHANCER is not None:
             x48_cpu = x48.cpu()
             return torch.cat([_ENHANCER(x48_cpu[c:c + 1], model_name) for c in range(x48_cpu.shape[0])], 0)
         try:
             from df.enhance import enhance, init_df
         except Exception as e:      # noqa: BLE001
-            from . import dfn_engine, dfn_weights
+            from . import dfn2_weights, dfn_weights
             model_dir = dfn_weights.discover(model_name)
             if model_dir is not None:
+                from . import dfn_engine
                 return dfn_engine.engine(model_dir, x48.device.index).enhance(x48)
+            model_dir = dfn2_weights.discover(model_name)
+            if model_dir is not None:
+                from . import dfn2_engine
+                return dfn2_engine.engine(model_dir, x48.device.index).enhance(x48)
             raise RuntimeError("DeepFilterNet (python package `df`) is not installed; this pack runs the stage around the "
                                "model on the GPU but does not re-implement the upstream network "
                                "(register one with egregora_audio_enhance_extras.set_enhancer).") from e

@@ -54,6 +54,12 @@ SIGNATURES = {
     "egr_dfn3_stage": (_i, [_vp, _i, _vp, _i64, C.POINTER(_i64), _vp]),
     "egr_dfn3_time_gru": (_i, [_vp, _i, _i, _i64, C.POINTER(C.c_double)]),
     "egr_dfn3_destroy": (_i, [_vp]),
+    "egr_dfn2_create": (_i, [C.POINTER(_vp), _vp, _vp, _i64, _i]),
+    "egr_dfn2_workspace_bytes": (C.c_size_t, [_vp, _i, _i64]),
+    "egr_dfn2_enhance": (_i, [_vp, _vp, _i, _i64, _vp, _vp]),
+    "egr_dfn2_stage": (_i, [_vp, _i, _vp, _i64, C.POINTER(_i64), _vp]),
+    "egr_dfn2_time_gru": (_i, [_vp, _i, _i, _i64, C.POINTER(C.c_double)]),
+    "egr_dfn2_destroy": (_i, [_vp]),
     "egr_shift_fir": (_i, [_vp, _i, _i64, _i64, _vp, _i, _vp, _i64, _vp]),
     "egr_gcc_phat": (_i, [_vp, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp]),
     "egr_band_filter": (_i, [_vp, _vp, _i64, _vp, _vp]),
@@ -179,6 +185,18 @@ class Dfn3ConfigC(C.Structure):
                 ("convt_kf", _i), ("emb_hidden_dim", _i), ("emb_num_layers", _i), ("df_hidden_dim", _i), ("df_num_layers", _i),
                 ("df_gru_skip", _i), ("lin_groups", _i), ("enc_lin_groups", _i), ("df_pathway_kt", _i), ("path_groups", _i),
                 ("df_path_groups", _i), ("norm_alpha", _f), ("erb_widths", _i * DFN3_MAX_ERB)]
+
+
+DFN2_STAGE = dict(DFN3_STAGE, alpha=12, gru0=16, sum0=32)
+
+
+class Dfn2ConfigC(C.Structure):
+    """egr_dfn2_config (include/egregora_amd.h)."""
+    _fields_ = [("struct_bytes", _i), ("sr", _i), ("fft_size", _i), ("hop_size", _i), ("nb_erb", _i), ("nb_df", _i), ("df_order", _i),
+                ("df_lookahead", _i), ("conv_lookahead", _i), ("conv_ch", _i), ("kt_inp", _i), ("kf_inp", _i), ("kt", _i), ("kf", _i),
+                ("emb_hidden_dim", _i), ("emb_num_layers", _i), ("df_hidden_dim", _i), ("df_num_layers", _i), ("gru_groups", _i),
+                ("lin_groups", _i), ("group_shuffle", _i), ("df_gru_skip", _i), ("df_output_layer", _i), ("df_pathway_kt", _i),
+                ("path_groups", _i), ("df_path_groups", _i), ("norm_alpha", _f), ("erb_widths", _i * DFN3_MAX_ERB)]
 
 
 def flashsr_config_c(cfg) -> FlashSRConfigC:

@@ -214,6 +214,34 @@ int egr_dfn3_stage(void* handle, int stage, float* dst, int64_t capacity, int64_
 int egr_dfn3_time_gru(void* handle, int layer, int channels, int64_t steps, double* us_per_step);
 int egr_dfn3_destroy(void* handle);
 
+/* DeepFilterNet2 forward pass (csrc/egr_dfn3.hip; SPEC.md "4c. DeepFilterNet2 (UPSTREAM-RECALL)"): the same contract
+ * as egr_dfn3_* above, for a DeepFilterNet2 model (dfn2_weights.py; weights in dfn2_weights.pack_order order).  Stages as
+ * EGR_DFN3_STAGE_* (EMB is the encoder GroupedGRU's output) plus ALPHA [C][nF]; GroupedGRU layer g (encoder, ERB decoder, DF decoder,
+ * in that order) at EGR_DFN2_STAGE_GRU0 + g as it is passed on (after the inter-layer shuffle) and at EGR_DFN2_STAGE_SUM0 + g as the
+ * running sum of its GroupedGRU's layer outputs up to it (the module output at its last layer).
+ *   egr_dfn2_time_gru: one GroupedGRU layer alone on zero projections, `steps` steps x `channels` x gru_groups workgroups */
+#define EGR_DFN2_STAGE_ALPHA 12
+#define EGR_DFN2_STAGE_GRU0 16
+#define EGR_DFN2_STAGE_SUM0 32
+typedef struct egr_dfn2_config {
+    int struct_bytes;                      /* sizeof(egr_dfn2_config) */
+    int sr, fft_size, hop_size, nb_erb, nb_df, df_order, df_lookahead, conv_lookahead;
+    int conv_ch, kt_inp, kf_inp, kt, kf;
+    int emb_hidden_dim, emb_num_layers, df_hidden_dim, df_num_layers;
+    int gru_groups, lin_groups, group_shuffle;
+    int df_gru_skip;                       /* 0 none, 1 groupedlinear (GroupedLinearEinsum) */
+    int df_output_layer;                   /* 0 groupedlinear (GroupedLinearEinsum), 1 linear (nn.Linear with bias) */
+    int df_pathway_kt, path_groups, df_path_groups;
+    float norm_alpha;
+    int erb_widths[EGR_DFN3_MAX_ERB];
+} egr_dfn2_config;
+int egr_dfn2_create(void** handle, const egr_dfn2_config* cfg, const float* packed, int64_t n_floats, int device);
+size_t egr_dfn2_workspace_bytes(void* handle, int channels, int64_t n);
+int egr_dfn2_enhance(void* handle, const float* x48, int channels, int64_t n, float* y, void* stream);
+int egr_dfn2_stage(void* handle, int stage, float* dst, int64_t capacity, int64_t* count, void* stream);
+int egr_dfn2_time_gru(void* handle, int layer, int channels, int64_t steps, double* us_per_step);
+int egr_dfn2_destroy(void* handle);
+
 /* Linear-interpolation resampler of the "Resample Audio (HQ)" node's fallback branch: y[c][j] = np.interp at
  * j * n_in / n_out input samples, clamped to the last sample (egregora_audio_eval_pack.py:515-519). */
 int egr_resample_linear(const float* x, int channels, int64_t n_in, float* y, int64_t n_out, void* stream);

@@ -14,6 +14,7 @@ reference / kind, autoscale / normalise definitions, PCM scales); `--variants` s
 section 3.  `--flashsr CKPT_DIR` does the same for FlashSR through the node's own checkpoint loader (flashsr_weights.load).
 `--dfn3 MODEL_DIR` runs upstream `df.enhance.enhance` and the native DeepFilterNet3 forward pass (dfn_engine, dfn_weights.load) on
 the same seeded input and prints the relative error per channel (SPEC.md section 4b; parity unpinned until this has been run).
+`--dfn2 MODEL_DIR` does the same for DeepFilterNet2 (dfn2_engine, dfn2_weights.load; SPEC.md section 4c).
 """
 import argparse
 import sys
@@ -40,11 +41,15 @@ def main():
     ap.add_argument("--dfn3", default="", metavar="MODEL_DIR",
                     help="instead: compare upstream df.enhance.enhance (importable) with the native DeepFilterNet3 on MODEL_DIR "
                          "(config.ini + checkpoints/*.ckpt.best)")
+    ap.add_argument("--dfn2", default="", metavar="MODEL_DIR",
+                    help="instead: the same for the native DeepFilterNet2 on MODEL_DIR ([train] model = deepfilternet2)")
     args = ap.parse_args()
     if args.flashsr:
         return compare_flashsr(args.flashsr)
     if args.dfn3:
         return compare_dfn3(args.dfn3, args.seconds)
+    if args.dfn2:
+        return compare_dfn3(args.dfn2, args.seconds, dfn2=True)
     try:
         import soundfile as sf
         from fat_llama_fftw.audio_fattener import feed
@@ -87,8 +92,9 @@ def main():
               f"PCM_16 samples differing = {np.mean(np.abs(up[:m] - mine[:m]) * 32768 > 0.5):.4f}")
 
 
-def compare_dfn3(model_dir, seconds):
-    """Upstream DeepFilterNet3 (df.enhance with the checkpoint in MODEL_DIR) vs the native forward pass, 48 kHz stereo."""
+def compare_dfn3(model_dir, seconds, dfn2=False):
+    """Upstream DeepFilterNet3 (DeepFilterNet2 with dfn2) -- df.enhance with the checkpoint in MODEL_DIR -- vs the native forward pass,
+    48 kHz stereo."""
     import torch
     try:
         from df.enhance import enhance, init_df
@@ -96,7 +102,10 @@ def compare_dfn3(model_dir, seconds):
         sys.exit(f"df (DeepFilterNet) not importable here ({e}); this tool is opt-in")
     from packload import load_pack
     load_pack()
-    from egregora_amd import dfn_engine, dfn_weights
+    if dfn2:
+        from egregora_amd import dfn2_engine as dfn_engine, dfn2_weights as dfn_weights
+    else:
+        from egregora_amd import dfn_engine, dfn_weights
     rng = np.random.Generator(np.random.PCG64(1234))
     n = int(seconds * 48000)
     t = np.arange(n) / 48000.0
@@ -106,7 +115,8 @@ def compare_dfn3(model_dir, seconds):
     model = model.eval()
     with torch.no_grad():
         up = torch.cat([enhance(model, df_state, torch.from_numpy(x[c:c + 1])) for c in range(2)], 0).numpy()
-    eng = dfn_engine.Dfn3Engine(dfn_weights.load(Path(model_dir)), torch.cuda.current_device())
+    make = dfn_engine.Dfn2Engine if dfn2 else dfn_engine.Dfn3Engine
+    eng = make(dfn_weights.load(Path(model_dir)), torch.cuda.current_device())
     ours = eng.enhance(torch.from_numpy(x).cuda()).cpu().numpy()
     for c in range(2):
         e = float(np.linalg.norm(ours[c] - up[c]) / max(np.linalg.norm(up[c]), 1e-30))
