@@ -11,10 +11,11 @@
 //   k_dfn_assemble   : ERB mask through the inverse map above nb_df, the deep filter (df_order complex taps, df_lookahead) below
 //   k_dfn_synth      : libdf frame_synthesis (unnormalised inverse real DFT in double, window); k_dfn_ola: overlap-add + trim
 // Work is enqueued on the caller's stream; nothing synchronises (the workspace grows with hipMallocAsync on that stream).
-// DeepFilterNet2 (egr_dfn2_*) reuses these kernels; its own ones follow the DeepFilterNet3 entry points below.
+// DeepFilterNet2 (egr_dfn2_*) reuses these kernels and the host path around them; its own kernels follow them.
 #include <math.h>
 #include <string.h>
 
+#include <memory>
 #include <vector>
 
 #include "egr_common.h"
@@ -352,514 +353,6 @@ __global__ void k_dfn_ola(const float* __restrict__ frames, int C, int nF, int N
     }
 }
 
-// ------------------------------------------------------------------------------------------------ host side
-inline unsigned grid_for(int64_t n, int bs = 256) {
-    int64_t g = (n + bs - 1) / bs;
-    if (g > 65536) g = 65536;
-    return (unsigned)(g < 1 ? 1 : g);
-}
-
-struct Conv {                 // one convolution with its (optional) BN affine
-    const float* w = nullptr; const float* scale = nullptr; const float* shift = nullptr;
-    int cin = 0, cout = 0, groups = 1, kt = 1, kf = 1, transposed = 0;
-};
-struct Gru {
-    const float* wih = nullptr; const float* bih = nullptr; const float* bhh = nullptr; float* whh_pk = nullptr;
-    int in = 0, H = 0;
-};
-
-}  // namespace
-
-struct Dfn3 {
-    egr_dfn3_config cfg;
-    int device = 0, Fq = 0, E4 = 0, embd = 0;
-    float* dev_w = nullptr;                 // packed weights + repacked W_hh + tables (one allocation)
-    const double2* tw = nullptr; const float* win = nullptr; const int* band_lo = nullptr; const int* band_w = nullptr;
-    const int* band_of = nullptr;
-    float wnorm = 0.f;
-    // layers
-    Conv erb0, erb_dw[3], erb_pw[3], df0, df0_pw, df1_dw, df1_pw, path[4], ct_dw[3], ct_pw[3], out0, convp, convp_pw;
-    const float *fc_emb = nullptr, *enc_lin_in = nullptr, *enc_lin_out = nullptr, *erb_lin_in = nullptr, *erb_lin_out = nullptr;
-    const float *df_lin_in = nullptr, *df_skip = nullptr, *df_out = nullptr;
-    std::vector<Gru> grus;                  // enc (1), erb decoder (emb_num_layers - 1), df decoder (df_num_layers)
-    // workspace of the last call
-    void* ws = nullptr; size_t ws_bytes = 0;
-    int lastC = 0, lastF = 0; int64_t lastT = 0;
-    struct Bufs {
-        float2 *spec, *spec_e, *fspec; float *db, *ferb, *e[4], *c0, *c1, *tmp, *emb0, *emb, *gx, *proj, *gout[EGR_DFN3_MAX_GRU];
-        float *demb, *pbuf, *dbuf, *mask, *dfc, *tcoef, *cpt, *cp, *coefs, *frames;
-    } B;
-};
-
-namespace {
-
-size_t layout(const Dfn3& m, int C, int nF, Dfn3::Bufs* B, char* base) {
-    const egr_dfn3_config& c = m.cfg;
-    const int64_t R = (int64_t)C * nF;
-    const int ch = c.conv_ch, E = c.nb_erb, nb = c.nb_df, O2 = 2 * c.df_order;
-    const int Hm = c.emb_hidden_dim > c.df_hidden_dim ? c.emb_hidden_dim : c.df_hidden_dim;
-    const int Fm = E > nb ? E : nb;
-    size_t off = 0;
-    auto take = [&](int64_t nfl) -> float* {
-        float* p = base ? (float*)(base + off) : nullptr;
-        off += ((size_t)nfl * sizeof(float) + 255) & ~(size_t)255;
-        return p;
-    };
-    Dfn3::Bufs b;
-    b.spec = (float2*)take(R * m.Fq * 2);
-    b.spec_e = (float2*)take(R * m.Fq * 2);
-    b.fspec = (float2*)take(R * nb * 2);
-    b.db = take(R * E);
-    b.ferb = take(R * E);
-    b.e[0] = take(R * E * ch);
-    b.e[1] = take(R * (E / 2) * ch);
-    b.e[2] = take(R * (E / 4) * ch);
-    b.e[3] = take(R * (E / 4) * ch);
-    b.c0 = take(R * nb * ch);
-    b.c1 = take(R * (nb / 2) * ch);
-    b.tmp = take(R * Fm * ch);
-    b.emb0 = take(R * m.embd);
-    b.emb = take(R * m.embd);
-    b.gx = take(R * Hm);
-    b.proj = take(R * 3 * Hm);
-    for (size_t g = 0; g < EGR_DFN3_MAX_GRU; ++g) b.gout[g] = g < m.grus.size() ? take(R * m.grus[g].H) : nullptr;
-    b.demb = take(R * m.embd);
-    b.pbuf = take(R * E * ch);
-    b.dbuf = take(R * E * ch);
-    b.mask = take(R * E);
-    b.dfc = take(R * c.df_hidden_dim);
-    b.tcoef = take(R * nb * O2);
-    b.cpt = take(R * nb * O2);
-    b.cp = take(R * nb * O2);
-    b.coefs = take(R * nb * O2);
-    b.frames = take(R * c.fft_size);
-    if (B) *B = b;
-    return off;
-}
-
-int conv(const Conv& L, const float* x, float* y, int B, int T, int Fin, int fstride, int act, const float* res, hipStream_t st,
-         int* Fout_ret = nullptr) {
-    ConvArgs p;
-    p.x = x; p.w = L.w; p.scale = L.scale; p.shift = L.shift; p.res = res; p.y = y;
-    p.B = B; p.T = T; p.Fin = Fin; p.Cin = L.cin; p.Cout = L.cout; p.groups = L.groups; p.kt = L.kt; p.kf = L.kf; p.fstride = fstride;
-    p.transposed = L.transposed; p.act = act;
-    if (L.transposed) {
-        p.fpad = L.kf / 2;
-        p.Fout = (Fin - 1) * fstride - 2 * p.fpad + (L.kf - 1) + L.kf / 2 + 1;
-    } else {
-        p.fpad = L.kf / 2;
-        p.Fout = (Fin + 2 * p.fpad - L.kf) / fstride + 1;
-    }
-    if (Fout_ret) *Fout_ret = p.Fout;
-    hipLaunchKernelGGL(k_dfn_conv, dim3(grid_for((int64_t)B * T * p.Fout * p.Cout)), dim3(256), 0, st, p);
-    return EGR_OK;
-}
-
-// x [rows][G * I] . w [G][I][O / G] -> y [rows][O]
-int grouped_linear(const float* x, const float* w, float* y, int64_t rows, int in, int out, int G, hipStream_t st) {
-    const int I = in / G, Oh = out / G;
-    return egr_bgemm(x, w, y, 1, G, (int)rows, Oh, I, in, Oh, out, 0, I, 0, (int64_t)I * Oh, 0, Oh, 0, 1.f, st);
-}
-
-int rows_op(const float* a, const float* bias, const float* res, float* y, int64_t n, int cols, int act, hipStream_t st) {
-    hipLaunchKernelGGL(k_dfn_rows, dim3(grid_for(n)), dim3(256), 0, st, a, bias, res, y, n, cols, act);
-    return EGR_OK;
-}
-
-#define EGR_TRY(x) do { int rc__ = (x); if (rc__ != EGR_OK) return rc__; } while (0)
-
-// x [C * nF][in] -> out [C * nF][H] through one GRU layer
-int gru_layer(const Gru& g, const float* x, float* proj, float* out, int C, int nF, hipStream_t st) {
-    const int64_t R = (int64_t)C * nF;
-    EGR_TRY(egr_bgemm(x, g.wih, proj, 1, 1, (int)R, 3 * g.H, g.in, g.in, g.in, 3 * g.H, 0, 0, 0, 0, 0, 0, 1, 1.f, st));
-    EGR_TRY(rows_op(proj, g.bih, nullptr, proj, R * 3 * g.H, 3 * g.H, 0, st));
-    hipLaunchKernelGGL(k_dfn_gru, dim3(C), dim3(GRU_THREADS), 0, st, proj, g.whh_pk, g.bhh, g.H, nF, out);
-    return EGR_OK;
-}
-
-int run(Dfn3& m, const float* x, int C, int64_t T, float* y, hipStream_t st) {
-    const egr_dfn3_config& c = m.cfg;
-    const int N = c.fft_size, hop = c.hop_size, nF = (int)((T + N) / hop);
-    const int64_t R = (int64_t)C * nF;
-    const int ch = c.conv_ch, E = c.nb_erb, nb = c.nb_df, O2 = 2 * c.df_order;
-    const size_t need = layout(m, C, nF, nullptr, nullptr);
-    if (need > m.ws_bytes) {
-        if (m.ws) EGR_HIP(hipFreeAsync(m.ws, st));
-        m.ws = nullptr;
-        m.ws_bytes = 0;
-        EGR_HIP(hipMallocAsync(&m.ws, need, st));
-        m.ws_bytes = need;
-    }
-    Dfn3::Bufs& B = m.B;
-    layout(m, C, nF, &B, (char*)m.ws);
-    m.lastC = C; m.lastF = nF; m.lastT = T;
-    // features
-    hipLaunchKernelGGL(k_dfn_analysis, dim3(nF, C), dim3(256), (size_t)N * 24, st, x, T, nF, N, hop, m.tw, m.win, m.wnorm, B.spec);
-    hipLaunchKernelGGL(k_dfn_erb_db, dim3(grid_for(R * E)), dim3(256), 0, st, B.spec, R, m.Fq, E, m.band_lo, m.band_w, B.db);
-    const int la = c.conv_lookahead;
-    hipLaunchKernelGGL(k_dfn_norm_scan, dim3((C * (E + nb) + 63) / 64), dim3(64), 0, st, B.db, B.spec, C, nF, m.Fq, E, nb,
-                       c.norm_alpha, la, B.ferb, B.fspec);
-    // encoder
-    int F1 = 0, F2 = 0, F3 = 0, Fc = 0;
-    EGR_TRY(conv(m.erb0, B.ferb, B.e[0], C, nF, E, 1, 1, nullptr, st));
-    const int strides[3] = {2, 2, 1};
-    int Fi = E;
-    for (int i = 0; i < 3; ++i) {
-        int Fo;
-        EGR_TRY(conv(m.erb_dw[i], B.e[i], B.tmp, C, nF, Fi, strides[i], 0, nullptr, st, &Fo));
-        EGR_TRY(conv(m.erb_pw[i], B.tmp, B.e[i + 1], C, nF, Fo, 1, 1, nullptr, st));
-        Fi = Fo;
-        if (i == 0) F1 = Fo; else if (i == 1) F2 = Fo; else F3 = Fo;
-    }
-    EGR_TRY(conv(m.df0, (const float*)B.fspec, B.tmp, C, nF, nb, 1, 0, nullptr, st));
-    EGR_TRY(conv(m.df0_pw, B.tmp, B.c0, C, nF, nb, 1, 1, nullptr, st));
-    EGR_TRY(conv(m.df1_dw, B.c0, B.tmp, C, nF, nb, 2, 0, nullptr, st, &Fc));
-    EGR_TRY(conv(m.df1_pw, B.tmp, B.c1, C, nF, Fc, 1, 1, nullptr, st));
-    EGR_CHECK(F3 * ch == m.embd && Fc * ch == ch * nb / 2 && F1 == E / 2 && F2 == E / 4, EGR_ERR_UNSUPPORTED, "egr_dfn3: encoder widths");
-    EGR_TRY(grouped_linear(B.c1, m.fc_emb, B.emb0, R, Fc * ch, m.embd, c.enc_lin_groups, st));
-    EGR_TRY(rows_op(B.emb0, nullptr, B.e[3], B.emb0, R * m.embd, m.embd, 1, st));      // emb = e3 + relu(fc_emb(c1))
-    const int He = c.emb_hidden_dim, Hd = c.df_hidden_dim;
-    int g = 0;
-    EGR_TRY(grouped_linear(B.emb0, m.enc_lin_in, B.gx, R, m.embd, He, c.lin_groups, st));
-    EGR_TRY(rows_op(B.gx, nullptr, nullptr, B.gx, R * He, He, 1, st));
-    EGR_TRY(gru_layer(m.grus[g], B.gx, B.proj, B.gout[g], C, nF, st));
-    EGR_TRY(grouped_linear(B.gout[g], m.enc_lin_out, B.emb, R, He, m.embd, c.lin_groups, st));
-    EGR_TRY(rows_op(B.emb, nullptr, nullptr, B.emb, R * m.embd, m.embd, 1, st));
-    ++g;
-    // ERB decoder
-    EGR_TRY(grouped_linear(B.emb, m.erb_lin_in, B.gx, R, m.embd, He, c.lin_groups, st));
-    EGR_TRY(rows_op(B.gx, nullptr, nullptr, B.gx, R * He, He, 1, st));
-    const float* xin = B.gx;
-    for (int k = 0; k < c.emb_num_layers - 1; ++k, ++g) {
-        EGR_TRY(gru_layer(m.grus[g], xin, B.proj, B.gout[g], C, nF, st));
-        xin = B.gout[g];
-    }
-    EGR_TRY(grouped_linear(xin, m.erb_lin_out, B.demb, R, He, m.embd, c.lin_groups, st));
-    EGR_TRY(rows_op(B.demb, nullptr, nullptr, B.demb, R * m.embd, m.embd, 1, st));
-    EGR_TRY(conv(m.path[3], B.e[3], B.pbuf, C, nF, F3, 1, 1, B.demb, st));
-    EGR_TRY(conv(m.ct_dw[0], B.pbuf, B.tmp, C, nF, F3, 1, 0, nullptr, st));
-    EGR_TRY(conv(m.ct_pw[0], B.tmp, B.dbuf, C, nF, F3, 1, 1, nullptr, st));
-    for (int i = 0; i < 2; ++i) {             // convt2 (E/4 -> E/2) on conv2p(e2) + d, convt1 (E/2 -> E) on conv1p(e1) + d
-        const int Fin = i == 0 ? F2 : F1, Fwant = i == 0 ? F1 : E;
-        EGR_TRY(conv(m.path[2 - i], B.e[2 - i], B.pbuf, C, nF, Fin, 1, 1, B.dbuf, st));
-        int Fo = 0;
-        EGR_TRY(conv(m.ct_dw[1 + i], B.pbuf, B.tmp, C, nF, Fin, 2, 0, nullptr, st, &Fo));
-        EGR_CHECK(Fo == Fwant, EGR_ERR_UNSUPPORTED, "egr_dfn3: transposed conv width %d != %d", Fo, Fwant);
-        EGR_TRY(conv(m.ct_pw[1 + i], B.tmp, B.dbuf, C, nF, Fo, 1, 1, nullptr, st));
-    }
-    EGR_TRY(conv(m.path[0], B.e[0], B.pbuf, C, nF, E, 1, 1, B.dbuf, st));
-    EGR_TRY(conv(m.out0, B.pbuf, B.mask, C, nF, E, 1, 2, nullptr, st));
-    // DF decoder
-    EGR_TRY(grouped_linear(B.emb, m.df_lin_in, B.gx, R, m.embd, Hd, c.lin_groups, st));
-    EGR_TRY(rows_op(B.gx, nullptr, nullptr, B.gx, R * Hd, Hd, 1, st));
-    xin = B.gx;
-    for (int k = 0; k < c.df_num_layers; ++k, ++g) {
-        EGR_TRY(gru_layer(m.grus[g], xin, B.proj, B.gout[g], C, nF, st));
-        xin = B.gout[g];
-    }
-    if (m.df_skip) {
-        EGR_TRY(grouped_linear(B.emb, m.df_skip, B.dfc, R, m.embd, Hd, c.lin_groups, st));
-        EGR_TRY(rows_op(B.dfc, nullptr, xin, B.dfc, R * Hd, Hd, 0, st));
-        xin = B.dfc;
-    }
-    EGR_TRY(grouped_linear(xin, m.df_out, B.tcoef, R, Hd, nb * O2, c.lin_groups, st));
-    EGR_TRY(conv(m.convp, B.c0, B.cpt, C, nF, nb, 1, 0, nullptr, st));
-    EGR_TRY(conv(m.convp_pw, B.cpt, B.cp, C, nF, nb, 1, 1, nullptr, st));
-    EGR_TRY(rows_op(B.tcoef, nullptr, B.cp, B.coefs, R * nb * O2, nb * O2, 3, st));      // tanh(df_out(c)) + df_convp(c0)
-    // mask + deep filter, synthesis
-    hipLaunchKernelGGL(k_dfn_assemble, dim3(grid_for(R * m.Fq)), dim3(256), 0, st, B.spec, B.mask, B.coefs, m.band_of, C, nF, m.Fq, E,
-                       nb, c.df_order, c.df_lookahead, B.spec_e);
-    hipLaunchKernelGGL(k_dfn_synth, dim3(nF, C), dim3(256), (size_t)(m.Fq + N) * 16, st, B.spec_e, nF, N, m.tw, m.win, B.frames);
-    hipLaunchKernelGGL(k_dfn_ola, dim3(grid_for((int64_t)C * T)), dim3(256), 0, st, B.frames, C, nF, N, hop, T, y);
-    EGR_HIP(hipGetLastError());
-    return EGR_OK;
-}
-
-}  // namespace
-}  // namespace egr
-
-using egr::Dfn3;
-
-extern "C" int egr_dfn3_create(void** handle, const egr_dfn3_config* cfg, const float* packed, int64_t n_floats, int device) {
-    using namespace egr;
-    EGR_CHECK(handle && cfg && packed && n_floats > 0, EGR_ERR_ARG, "egr_dfn3_create: null argument");
-    EGR_CHECK(cfg->struct_bytes == (int)sizeof(egr_dfn3_config), EGR_ERR_ARG, "egr_dfn3_create: struct_bytes %d != %d",
-              cfg->struct_bytes, (int)sizeof(egr_dfn3_config));
-    const egr_dfn3_config& c = *cfg;
-    const int ch = c.conv_ch, E = c.nb_erb, nb = c.nb_df, O2 = 2 * c.df_order;
-    const int ngru = 1 + (c.emb_num_layers - 1) + c.df_num_layers;
-    EGR_CHECK(c.fft_size > 0 && c.hop_size > 0 && c.fft_size % c.hop_size == 0 && c.fft_size % 2 == 0 && c.fft_size <= 4096, EGR_ERR_UNSUPPORTED,
-              "egr_dfn3: fft_size %d / hop_size %d", c.fft_size, c.hop_size);
-    EGR_CHECK(E > 0 && E <= EGR_DFN3_MAX_ERB && E % 4 == 0 && nb > 0 && nb % 2 == 0 && nb <= c.fft_size / 2 + 1, EGR_ERR_UNSUPPORTED,
-              "egr_dfn3: nb_erb %d / nb_df %d", E, nb);
-    EGR_CHECK(c.emb_hidden_dim > 0 && c.emb_hidden_dim <= GRU_HMAX && c.df_hidden_dim > 0 && c.df_hidden_dim <= GRU_HMAX,
-              EGR_ERR_UNSUPPORTED, "egr_dfn3: GRU widths must be <= %d", GRU_HMAX);
-    EGR_CHECK(c.emb_num_layers >= 2 && c.df_num_layers >= 1 && ngru <= EGR_DFN3_MAX_GRU, EGR_ERR_UNSUPPORTED, "egr_dfn3: GRU layer counts");
-    EGR_CHECK(c.df_order >= 1 && c.df_lookahead >= 0 && c.df_lookahead < c.df_order && c.conv_lookahead >= 0, EGR_ERR_UNSUPPORTED,
-              "egr_dfn3: df_order / lookaheads");
-    EGR_CHECK(ch > 0 && c.lin_groups > 0 && c.enc_lin_groups > 0 && c.path_groups > 0 && ch % c.path_groups == 0 && c.df_path_groups > 0 &&
-              ch % c.df_path_groups == 0 && O2 % c.df_path_groups == 0, EGR_ERR_UNSUPPORTED, "egr_dfn3: conv groups");
-    // a stride-2 transposed conv with padding kf / 2 and output_padding kf / 2 doubles the width only for kf = 3 (torch refuses
-    // output_padding >= stride for the wider kernels)
-    EGR_CHECK(c.convt_kf == 3, EGR_ERR_UNSUPPORTED, "egr_dfn3: transposed conv kernel width %d (supported: 3)", c.convt_kf);
-    EGR_CHECK(c.kf % 2 == 1 && c.kf_inp % 2 == 1 && c.kt >= 1 && c.kt_inp >= 1 && c.df_pathway_kt >= 1, EGR_ERR_UNSUPPORTED,
-              "egr_dfn3: frequency kernels must be odd (same-size padding)");
-    int wsum = 0;
-    for (int e = 0; e < E; ++e) { EGR_CHECK(c.erb_widths[e] > 0, EGR_ERR_ARG, "egr_dfn3: ERB width %d", e); wsum += c.erb_widths[e]; }
-    EGR_CHECK(wsum == c.fft_size / 2 + 1, EGR_ERR_ARG, "egr_dfn3: ERB widths sum %d != %d", wsum, c.fft_size / 2 + 1);
-
-    Dfn3* m = new Dfn3();
-    m->cfg = c;
-    m->device = device;
-    m->Fq = c.fft_size / 2 + 1;
-    m->E4 = E / 4;
-    m->embd = ch * E / 4;
-    // packed order: dfn_weights.pack_order
-    int64_t pos = 0;                                        // floats consumed so far
-    auto W = [&](int64_t k) { pos += k; return pos - k; };
-    struct ConvSpec { Conv* L; int64_t w, s, t; };
-    std::vector<ConvSpec> convs;
-    auto cv = [&](Conv& L, int cin, int cout, int groups, int kt, int kf, int transposed = 0) {
-        L.cin = cin; L.cout = cout; L.groups = groups; L.kt = kt; L.kf = kf; L.transposed = transposed;
-        ConvSpec s{&L, W((int64_t)(transposed ? cin * (cout / groups) : cout * (cin / groups)) * kt * kf), -1, -1};
-        convs.push_back(s);
-    };
-    auto bn = [&](int n) { ConvSpec& s = convs.back(); s.s = W(n); s.t = W(n); };
-    cv(m->erb0, 1, ch, 1, c.kt_inp, c.kf_inp); bn(ch);
-    for (int i = 0; i < 3; ++i) { cv(m->erb_dw[i], ch, ch, ch, c.kt, c.kf); cv(m->erb_pw[i], ch, ch, 1, 1, 1); bn(ch); }
-    cv(m->df0, 2, ch, 2, c.kt_inp, c.kf_inp); cv(m->df0_pw, ch, ch, 1, 1, 1); bn(ch);
-    cv(m->df1_dw, ch, ch, ch, c.kt, c.kf); cv(m->df1_pw, ch, ch, 1, 1, 1); bn(ch);
-    const int64_t o_fc = W((int64_t)(ch * nb / 2) * m->embd / c.enc_lin_groups);
-    struct GruSpec { int64_t lin_in = -1, wih, whh, bih, bhh; int in, H; };
-    std::vector<GruSpec> gs;
-    auto sq = [&](int in, int H, int layers, int64_t* lin_in) {
-        *lin_in = W((int64_t)in * H / c.lin_groups);
-        for (int k = 0; k < layers; ++k) {
-            GruSpec g;
-            g.in = H; g.H = H;
-            g.wih = W((int64_t)3 * H * H); g.whh = W((int64_t)3 * H * H); g.bih = W(3 * H); g.bhh = W(3 * H);
-            gs.push_back(g);
-        }
-    };
-    int64_t o_enc_in, o_enc_out, o_erb_in, o_erb_out, o_df_in, o_skip = -1, o_dfout;
-    sq(m->embd, c.emb_hidden_dim, 1, &o_enc_in);
-    o_enc_out = W((int64_t)c.emb_hidden_dim * m->embd / c.lin_groups);
-    sq(m->embd, c.emb_hidden_dim, c.emb_num_layers - 1, &o_erb_in);
-    o_erb_out = W((int64_t)c.emb_hidden_dim * m->embd / c.lin_groups);
-    for (int i = 0; i < 3; ++i) {
-        cv(m->path[3 - i], ch, ch, c.path_groups, 1, 1); bn(ch);
-        if (i == 0) cv(m->ct_dw[0], ch, ch, ch, c.kt, c.kf);
-        else cv(m->ct_dw[i], ch, ch, ch, 1, c.convt_kf, 1);
-        cv(m->ct_pw[i], ch, ch, 1, 1, 1); bn(ch);
-    }
-    cv(m->path[0], ch, ch, c.path_groups, 1, 1); bn(ch);
-    cv(m->out0, ch, 1, 1, c.kt, c.kf); bn(1);
-    sq(m->embd, c.df_hidden_dim, c.df_num_layers, &o_df_in);
-    if (c.df_gru_skip) o_skip = W((int64_t)m->embd * c.df_hidden_dim / c.lin_groups);
-    o_dfout = W((int64_t)c.df_hidden_dim * nb * O2 / c.lin_groups);
-    cv(m->convp, ch, O2, c.df_path_groups, c.df_pathway_kt, 1);
-    cv(m->convp_pw, O2, O2, 1, 1, 1); bn(O2);
-    if (pos != n_floats) {
-        set_error("egr_dfn3_create: packed weights hold %lld floats, the config needs %lld", (long long)n_floats, (long long)pos);
-        delete m;
-        return EGR_ERR_ARG;
-    }
-    // device image: packed weights | repacked W_hh per layer | twiddles (double2) | window | band tables
-    const int64_t n_whh = (int64_t)GRU_PER_THREAD * GRU_THREADS;
-    const int N = c.fft_size;
-    const int64_t o_whh = (n_floats + 63) & ~63LL;
-    const int64_t o_tw = o_whh + (int64_t)gs.size() * n_whh;
-    const int64_t o_win = o_tw + 4LL * N;
-    const int64_t o_tab = o_win + N;
-    const int64_t total = o_tab + 2 * E + m->Fq;
-    std::vector<float> img((size_t)total, 0.f);
-    memcpy(img.data(), packed, sizeof(float) * n_floats);
-    for (size_t g = 0; g < gs.size(); ++g) {            // W_hh [3H][H] -> thread-minor (element, thread) order of k_dfn_gru
-        const int H = gs[g].H;
-        const float* w = packed + gs[g].whh;
-        float* dst = img.data() + o_whh + g * n_whh;
-        for (int t = 0; t < GRU_THREADS; ++t)
-            for (int e = 0; e < GRU_PER_THREAD; ++e) {
-                const int j = e / GRU_K, k = e % GRU_K;
-                const int q = j * GRU_THREADS + t, row = q / GRU_SEG, col = GRU_SEG * k + q % GRU_SEG;
-                dst[(int64_t)e * GRU_THREADS + t] = (row < 3 * H && col < H) ? w[(int64_t)row * H + col] : 0.f;
-            }
-    }
-    double* twd = (double*)(img.data() + o_tw);
-    for (int n = 0; n < N; ++n) {
-        twd[2 * n] = cos(2.0 * M_PI * n / N);
-        twd[2 * n + 1] = sin(2.0 * M_PI * n / N);
-    }
-    const int h = N / 2;
-    for (int n = 0; n < N; ++n) {
-        const double s = sin(0.5 * M_PI * (n + 0.5) / h);
-        img[o_win + n] = (float)sin(0.5 * M_PI * s * s);
-    }
-    int* tab = (int*)(img.data() + o_tab);
-    int lo = 0;
-    for (int e = 0; e < E; ++e) {
-        tab[e] = lo;
-        tab[E + e] = c.erb_widths[e];
-        for (int j = 0; j < c.erb_widths[e]; ++j) tab[2 * E + lo + j] = e;
-        lo += c.erb_widths[e];
-    }
-    m->wnorm = 1.f / ((float)N * (float)N / (float)(2 * c.hop_size));
-    int prev = 0;
-    if (hipGetDevice(&prev) != hipSuccess || hipSetDevice(device) != hipSuccess ||
-        hipMalloc(&m->dev_w, sizeof(float) * total) != hipSuccess ||
-        hipMemcpy(m->dev_w, img.data(), sizeof(float) * total, hipMemcpyHostToDevice) != hipSuccess) {
-        set_error("egr_dfn3_create: device allocation / upload failed on device %d", device);
-        if (m->dev_w) (void)hipFree(m->dev_w);
-        (void)hipSetDevice(prev);
-        delete m;
-        return EGR_ERR_HIP;
-    }
-    // the analysis / synthesis DFTs keep a frame and the twiddles in dynamic LDS: 24 N and 16 (1.5 N + 1) bytes, above the 64 KiB
-    // default from N = 2732 on.  The attribute is a process-wide cap per kernel, so it is raised to the CU's maximum (as the Fat-Llama
-    // plans do), never to this config's need.
-    const size_t lds_an = (size_t)N * 24, lds_syn = (size_t)(m->Fq + N) * 16;
-    hipError_t ea = hipSuccess;
-    if (lds_an > (size_t)DFN_LDS_MAX || lds_syn > (size_t)DFN_LDS_MAX) {
-        set_error("egr_dfn3_create: fft_size %d needs %zu / %zu bytes of LDS (limit %d)", N, lds_an, lds_syn, DFN_LDS_MAX);
-        ea = hipErrorInvalidValue;
-    }
-    if (ea == hipSuccess) ea = hipFuncSetAttribute((const void*)k_dfn_analysis, hipFuncAttributeMaxDynamicSharedMemorySize, DFN_LDS_MAX);
-    if (ea == hipSuccess) ea = hipFuncSetAttribute((const void*)k_dfn_synth, hipFuncAttributeMaxDynamicSharedMemorySize, DFN_LDS_MAX);
-    if (ea != hipSuccess) {
-        if (lds_an <= (size_t)DFN_LDS_MAX && lds_syn <= (size_t)DFN_LDS_MAX)
-            set_error("egr_dfn3_create: hipFuncSetAttribute(MaxDynamicSharedMemorySize) -> %s", hipGetErrorString(ea));
-        (void)hipFree(m->dev_w);
-        (void)hipSetDevice(prev);
-        delete m;
-        return EGR_ERR_HIP;
-    }
-    (void)hipSetDevice(prev);
-    float* D = m->dev_w;
-    for (auto& s : convs) {
-        s.L->w = D + s.w;
-        if (s.s >= 0) { s.L->scale = D + s.s; s.L->shift = D + s.t; }
-    }
-    m->fc_emb = D + o_fc;
-    m->enc_lin_in = D + o_enc_in; m->enc_lin_out = D + o_enc_out;
-    m->erb_lin_in = D + o_erb_in; m->erb_lin_out = D + o_erb_out;
-    m->df_lin_in = D + o_df_in; m->df_skip = o_skip >= 0 ? D + o_skip : nullptr; m->df_out = D + o_dfout;
-    for (size_t g = 0; g < gs.size(); ++g) {
-        Gru G;
-        G.in = gs[g].in; G.H = gs[g].H;
-        G.wih = D + gs[g].wih; G.bih = D + gs[g].bih; G.bhh = D + gs[g].bhh; G.whh_pk = D + o_whh + g * n_whh;
-        m->grus.push_back(G);
-    }
-    m->tw = (const double2*)(D + o_tw);
-    m->win = D + o_win;
-    m->band_lo = (const int*)(D + o_tab);
-    m->band_w = (const int*)(D + o_tab) + E;
-    m->band_of = (const int*)(D + o_tab) + 2 * E;
-    *handle = m;
-    return EGR_OK;
-}
-
-extern "C" size_t egr_dfn3_workspace_bytes(void* handle, int channels, int64_t n) {
-    if (!handle || channels < 1 || n < 1) return 0;
-    Dfn3* m = (Dfn3*)handle;
-    return egr::layout(*m, channels, (int)((n + m->cfg.fft_size) / m->cfg.hop_size), nullptr, nullptr);
-}
-
-extern "C" int egr_dfn3_enhance(void* handle, const float* x48, int channels, int64_t n, float* y, void* stream) {
-    using namespace egr;
-    EGR_CHECK(handle && x48 && y && channels >= 1 && channels <= 65535 && n >= 1, EGR_ERR_ARG, "egr_dfn3_enhance: bad argument");
-    Dfn3* m = (Dfn3*)handle;
-    EGR_CHECK((n + m->cfg.fft_size) / m->cfg.hop_size <= 65535LL * 4096, EGR_ERR_UNSUPPORTED, "egr_dfn3_enhance: input too long");
-    EGR_CHECK((n + m->cfg.fft_size) / m->cfg.hop_size <= 2147483647LL / 4096, EGR_ERR_UNSUPPORTED, "egr_dfn3_enhance: input too long");
-    int cur = -1;
-    EGR_HIP(hipGetDevice(&cur));
-    EGR_CHECK(cur == m->device, EGR_ERR_ARG, "egr_dfn3_enhance: handle belongs to device %d, current device is %d", m->device, cur);
-    return run(*m, x48, channels, n, y, (hipStream_t)stream);
-}
-
-extern "C" int egr_dfn3_stage(void* handle, int stage, float* dst, int64_t capacity, int64_t* count, void* stream) {
-    using namespace egr;
-    EGR_CHECK(handle && count, EGR_ERR_ARG, "egr_dfn3_stage: null argument");
-    Dfn3* m = (Dfn3*)handle;
-    EGR_CHECK(m->ws, EGR_ERR_ARG, "egr_dfn3_stage: no enhance call yet");
-    const int64_t R = (int64_t)m->lastC * m->lastF;
-    const egr_dfn3_config& c = m->cfg;
-    const Dfn3::Bufs& B = m->B;
-    const float* src = nullptr;
-    int64_t n = 0;
-    switch (stage) {
-        case EGR_DFN3_STAGE_SPEC: src = (const float*)B.spec; n = R * m->Fq * 2; break;
-        case EGR_DFN3_STAGE_FEAT_ERB: src = B.ferb; n = R * c.nb_erb; break;
-        case EGR_DFN3_STAGE_FEAT_SPEC: src = (const float*)B.fspec; n = R * c.nb_df * 2; break;
-        case EGR_DFN3_STAGE_E0: src = B.e[0]; n = R * c.nb_erb * c.conv_ch; break;
-        case EGR_DFN3_STAGE_E1: src = B.e[1]; n = R * (c.nb_erb / 2) * c.conv_ch; break;
-        case EGR_DFN3_STAGE_E2: src = B.e[2]; n = R * (c.nb_erb / 4) * c.conv_ch; break;
-        case EGR_DFN3_STAGE_E3: src = B.e[3]; n = R * (c.nb_erb / 4) * c.conv_ch; break;
-        case EGR_DFN3_STAGE_C0: src = B.c0; n = R * c.nb_df * c.conv_ch; break;
-        case EGR_DFN3_STAGE_EMB: src = B.emb; n = R * m->embd; break;
-        case EGR_DFN3_STAGE_MASK: src = B.mask; n = R * c.nb_erb; break;
-        case EGR_DFN3_STAGE_COEFS: src = B.coefs; n = R * c.nb_df * 2 * c.df_order; break;
-        case EGR_DFN3_STAGE_SPEC_E: src = (const float*)B.spec_e; n = R * m->Fq * 2; break;
-        default:
-            if (stage >= EGR_DFN3_STAGE_GRU0 && stage < EGR_DFN3_STAGE_GRU0 + (int)m->grus.size()) {
-                const int g = stage - EGR_DFN3_STAGE_GRU0;
-                src = B.gout[g];
-                n = R * m->grus[g].H;
-            }
-    }
-    EGR_CHECK(src, EGR_ERR_ARG, "egr_dfn3_stage: unknown stage %d", stage);
-    *count = n;
-    if (!dst) return EGR_OK;
-    EGR_CHECK(capacity >= n, EGR_ERR_ARG, "egr_dfn3_stage: capacity %lld < %lld", (long long)capacity, (long long)n);
-    EGR_HIP(hipMemcpyAsync(dst, src, sizeof(float) * n, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    return EGR_OK;
-}
-
-extern "C" int egr_dfn3_time_gru(void* handle, int layer, int channels, int64_t steps, double* us_per_step) {
-    using namespace egr;
-    EGR_CHECK(handle && us_per_step && channels >= 1 && channels <= 64 && steps >= 1 && steps <= 10000000, EGR_ERR_ARG,
-              "egr_dfn3_time_gru: bad argument");
-    Dfn3* m = (Dfn3*)handle;
-    EGR_CHECK(layer >= 0 && layer < (int)m->grus.size(), EGR_ERR_ARG, "egr_dfn3_time_gru: layer %d", layer);
-    const Gru& g = m->grus[layer];
-    float *proj = nullptr, *out = nullptr;
-    hipEvent_t e0, e1;
-    EGR_HIP(hipMalloc(&proj, sizeof(float) * channels * steps * 3 * g.H));
-    EGR_HIP(hipMalloc(&out, sizeof(float) * channels * steps * g.H));
-    EGR_HIP(hipMemset(proj, 0, sizeof(float) * channels * steps * 3 * g.H));
-    EGR_HIP(hipEventCreate(&e0));
-    EGR_HIP(hipEventCreate(&e1));
-    hipLaunchKernelGGL(k_dfn_gru, dim3(channels), dim3(GRU_THREADS), 0, 0, proj, g.whh_pk, g.bhh, g.H, (int)(steps < 64 ? steps : 64), out);
-    EGR_HIP(hipEventRecord(e0, 0));
-    hipLaunchKernelGGL(k_dfn_gru, dim3(channels), dim3(GRU_THREADS), 0, 0, proj, g.whh_pk, g.bhh, g.H, (int)steps, out);
-    EGR_HIP(hipEventRecord(e1, 0));
-    EGR_HIP(hipEventSynchronize(e1));
-    float ms = 0.f;
-    EGR_HIP(hipEventElapsedTime(&ms, e0, e1));
-    *us_per_step = 1e3 * ms / (double)steps;
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    (void)hipFree(proj);
-    (void)hipFree(out);
-    EGR_HIP(hipGetLastError());
-    return EGR_OK;
-}
-
-extern "C" int egr_dfn3_destroy(void* handle) {
-    if (!handle) return EGR_OK;
-    Dfn3* m = (Dfn3*)handle;
-    int prev = 0;
-    (void)hipGetDevice(&prev);
-    (void)hipSetDevice(m->device);
-    if (m->ws) {                               // hipMallocAsync memory: returned stream-ordered, then waited for (not a pipeline call)
-        (void)hipFreeAsync(m->ws, nullptr);
-        (void)hipDeviceSynchronize();
-    }
-    if (m->dev_w) (void)hipFree(m->dev_w);
-    (void)hipSetDevice(prev);
-    delete m;
-    return EGR_OK;
-}
-
 // ================================================================================================ DeepFilterNet2
 // SPEC.md "4c. DeepFilterNet2 (UPSTREAM-RECALL)".  The signal path, the convolutions, the grouped linears without bias
 // (GroupedLinearEinsum) and the synthesis are the DeepFilterNet3 kernels above, launched through the same host helpers; what is new:
@@ -868,9 +361,6 @@ extern "C" int egr_dfn3_destroy(void* handle) {
 //   k_dfn2_epi      : bias / activation / P3 output shuffle / residual epilogue of the GroupedLinear GEMMs
 //   k_dfn2_alpha    : alpha = sigmoid(Linear(H_df -> 1)(c)) per frame
 //   k_dfn2_assemble : ERB mask on every bin, the deep filter on the MASKED bins below nb_df, blended with alpha (P7)
-namespace egr {
-namespace {
-
 constexpr int G2_HMAX = 128;                // per-group width k_dfn2_gru holds (h = H / G > 128 only for G = 1: the dense k_dfn_gru)
 
 // Thread (j, s) = (threadIdx.x / S, threadIdx.x % S) of workgroup (g, b) owns gate rows j, h + j, 2h + j of group g's W_hh over the
@@ -1000,6 +490,581 @@ __global__ void k_dfn2_assemble(const float2* __restrict__ spec, const float* __
     }
 }
 
+// ------------------------------------------------------------------------------------------------ host side: what both models share
+// DfnCore is the part of a handle the two models have in common: the signal path (analysis, ERB / dB, norm scan, every convolution,
+// synthesis, overlap-add), its tables and weights, the workspace.  Dfn3 and Dfn2 hold one plus their own linears and GRU layers; their
+// run() and create() call the stages below and keep only the middle of the network.
+inline unsigned grid_for(int64_t n, int bs = 256) {
+    int64_t g = (n + bs - 1) / bs;
+    if (g > 65536) g = 65536;
+    return (unsigned)(g < 1 ? 1 : g);
+}
+inline int64_t align64(int64_t n) { return (n + 63) & ~63LL; }
+
+#define EGR_TRY(x) do { int rc__ = (x); if (rc__ != EGR_OK) return rc__; } while (0)
+
+struct Conv {                 // one convolution with its (optional) BN affine
+    const float* w = nullptr; const float* scale = nullptr; const float* shift = nullptr;
+    int cin = 0, cout = 0, groups = 1, kt = 1, kf = 1, transposed = 0;
+};
+
+struct DfnDims {              // the hyper-parameters the shared code reads, from egr_dfn3_config / egr_dfn2_config
+    int fft_size, hop_size, nb_erb, nb_df, df_order, df_lookahead, conv_lookahead, conv_ch, kt, kf, kt_inp, kf_inp, convt_kf;
+    int df_pathway_kt, path_groups, df_path_groups, emb_hidden_dim, emb_num_layers, df_hidden_dim, df_num_layers;
+    float norm_alpha;
+    int erb_widths[EGR_DFN3_MAX_ERB];
+};
+
+struct Bufs {                 // workspace buffers of the shared path; the models add theirs (Dfn3::X, Dfn2::X)
+    float2 *spec, *spec_e, *fspec;
+    float *db, *ferb, *e[4], *c0, *c1, *tmp, *emb0, *proj, *gout[EGR_DFN3_MAX_GRU], *dfc, *demb, *pbuf, *dbuf, *mask, *tcoef, *cpt, *cp;
+    float *coefs, *frames;
+};
+
+struct DfnCore {
+    DfnDims d;
+    int device = 0, Fq = 0, embd = 0;
+    float* dev_w = nullptr;                 // packed weights + repacked W_hh + tables (one allocation)
+    const double2* tw = nullptr; const float* win = nullptr; const int* band_lo = nullptr; const int* band_w = nullptr;
+    const int* band_of = nullptr;
+    float wnorm = 0.f;
+    Conv erb0, erb_dw[3], erb_pw[3], df0, df0_pw, df1_dw, df1_pw, path[4], ct_dw[3], ct_pw[3], out0, convp, convp_pw;
+    // workspace of the last call
+    void* ws = nullptr; size_t ws_bytes = 0;
+    int lastC = 0, lastF = 0; int64_t lastT = 0;
+    Bufs B;
+    // GRU layers in the order encoder (1), ERB decoder (emb_num_layers - 1), DF decoder (df_num_layers)
+    int ngru() const { return d.emb_num_layers + d.df_num_layers; }
+    int gru_width(int g) const { return g < d.emb_num_layers ? d.emb_hidden_dim : d.df_hidden_dim; }
+    int64_t frames_of(int64_t n) const { return (n + d.fft_size) / d.hop_size; }
+};
+
+struct Take {                 // the workspace allocator: 256-byte slots one after another; base null only measures
+    char* base;
+    size_t off = 0;
+    float* operator()(int64_t nfl) {
+        float* p = base ? (float*)(base + off) : nullptr;
+        off += ((size_t)nfl * sizeof(float) + 255) & ~(size_t)255;
+        return p;
+    }
+};
+
+void layout_common(const DfnCore& m, int64_t R, Take& take, Bufs& b) {
+    const DfnDims& d = m.d;
+    const int ch = d.conv_ch, E = d.nb_erb, nb = d.nb_df, O2 = 2 * d.df_order;
+    const int Hm = d.emb_hidden_dim > d.df_hidden_dim ? d.emb_hidden_dim : d.df_hidden_dim;
+    const int Fm = E > nb ? E : nb;
+    b.spec = (float2*)take(R * m.Fq * 2);
+    b.spec_e = (float2*)take(R * m.Fq * 2);
+    b.fspec = (float2*)take(R * nb * 2);
+    b.db = take(R * E);
+    b.ferb = take(R * E);
+    b.e[0] = take(R * E * ch);
+    b.e[1] = take(R * (E / 2) * ch);
+    b.e[2] = take(R * (E / 4) * ch);
+    b.e[3] = take(R * (E / 4) * ch);
+    b.c0 = take(R * nb * ch);
+    b.c1 = take(R * (nb / 2) * ch);
+    b.tmp = take(R * Fm * ch);
+    b.emb0 = take(R * m.embd);
+    b.proj = take(R * 3 * Hm);
+    for (int g = 0; g < EGR_DFN3_MAX_GRU; ++g) b.gout[g] = g < m.ngru() ? take(R * m.gru_width(g)) : nullptr;
+    b.dfc = take(R * d.df_hidden_dim);
+    b.demb = take(R * m.embd);
+    b.pbuf = take(R * E * ch);
+    b.dbuf = take(R * E * ch);
+    b.mask = take(R * E);
+    b.tcoef = take(R * nb * O2);
+    b.cpt = take(R * nb * O2);
+    b.cp = take(R * nb * O2);
+    b.coefs = take(R * nb * O2);
+    b.frames = take(R * d.fft_size);
+}
+
+int conv(const Conv& L, const float* x, float* y, int B, int T, int Fin, int fstride, int act, const float* res, hipStream_t st,
+         int* Fout_ret = nullptr) {
+    ConvArgs p;
+    p.x = x; p.w = L.w; p.scale = L.scale; p.shift = L.shift; p.res = res; p.y = y;
+    p.B = B; p.T = T; p.Fin = Fin; p.Cin = L.cin; p.Cout = L.cout; p.groups = L.groups; p.kt = L.kt; p.kf = L.kf; p.fstride = fstride;
+    p.transposed = L.transposed; p.act = act;
+    if (L.transposed) {
+        p.fpad = L.kf / 2;
+        p.Fout = (Fin - 1) * fstride - 2 * p.fpad + (L.kf - 1) + L.kf / 2 + 1;
+    } else {
+        p.fpad = L.kf / 2;
+        p.Fout = (Fin + 2 * p.fpad - L.kf) / fstride + 1;
+    }
+    if (Fout_ret) *Fout_ret = p.Fout;
+    hipLaunchKernelGGL(k_dfn_conv, dim3(grid_for((int64_t)B * T * p.Fout * p.Cout)), dim3(256), 0, st, p);
+    return EGR_OK;
+}
+
+// x [rows][G * I] . w [G][I][O / G] -> y [rows][O]
+int grouped_linear(const float* x, const float* w, float* y, int64_t rows, int in, int out, int G, hipStream_t st) {
+    const int I = in / G, Oh = out / G;
+    return egr_bgemm(x, w, y, 1, G, (int)rows, Oh, I, in, Oh, out, 0, I, 0, (int64_t)I * Oh, 0, Oh, 0, 1.f, st);
+}
+
+int rows_op(const float* a, const float* bias, const float* res, float* y, int64_t n, int cols, int act, hipStream_t st) {
+    hipLaunchKernelGGL(k_dfn_rows, dim3(grid_for(n)), dim3(256), 0, st, a, bias, res, y, n, cols, act);
+    return EGR_OK;
+}
+
+// ---- run stages, in the order both run()s call them; the models' own launches come between encoder_convs and erb_decoder_convs and
+// ---- between erb_decoder_convs and df_pathway_and_coefs, their assemble kernel before synthesis
+// Grows the workspace to `need` bytes on `st` and notes the call's shape; the caller lays its buffers out over m.ws afterwards.
+int ensure_workspace(DfnCore& m, size_t need, int C, int nF, int64_t T, hipStream_t st) {
+    if (need > m.ws_bytes) {
+        if (m.ws) EGR_HIP(hipFreeAsync(m.ws, st));
+        m.ws = nullptr;
+        m.ws_bytes = 0;
+        EGR_HIP(hipMallocAsync(&m.ws, need, st));
+        m.ws_bytes = need;
+    }
+    m.lastC = C; m.lastF = nF; m.lastT = T;
+    return EGR_OK;
+}
+
+// analysis -> ERB dB -> the two norms (with the conv_lookahead shift whenever it is > 0)
+void features(const DfnCore& m, const float* x, int C, int nF, int64_t T, hipStream_t st) {
+    const DfnDims& d = m.d;
+    const Bufs& B = m.B;
+    const int N = d.fft_size, E = d.nb_erb, nb = d.nb_df;
+    const int64_t R = (int64_t)C * nF;
+    hipLaunchKernelGGL(k_dfn_analysis, dim3(nF, C), dim3(256), (size_t)N * 24, st, x, T, nF, N, d.hop_size, m.tw, m.win, m.wnorm, B.spec);
+    hipLaunchKernelGGL(k_dfn_erb_db, dim3(grid_for(R * E)), dim3(256), 0, st, B.spec, R, m.Fq, E, m.band_lo, m.band_w, B.db);
+    hipLaunchKernelGGL(k_dfn_norm_scan, dim3((C * (E + nb) + 63) / 64), dim3(64), 0, st, B.db, B.spec, C, nF, m.Fq, E, nb,
+                       d.norm_alpha, d.conv_lookahead, B.ferb, B.fspec);
+}
+
+struct EncWidths { int F1 = 0, F2 = 0, F3 = 0, Fc = 0; };      // frequency widths of e1, e2, e3 and c1
+
+// ferb -> e[0..3], fspec -> c0, c1
+int encoder_convs(const DfnCore& m, const char* who, int C, int nF, EncWidths* w, hipStream_t st) {
+    const Bufs& B = m.B;
+    const int ch = m.d.conv_ch, E = m.d.nb_erb, nb = m.d.nb_df;
+    EGR_TRY(conv(m.erb0, B.ferb, B.e[0], C, nF, E, 1, 1, nullptr, st));
+    const int strides[3] = {2, 2, 1};
+    int* Fo[3] = {&w->F1, &w->F2, &w->F3};
+    int Fi = E;
+    for (int i = 0; i < 3; ++i) {
+        EGR_TRY(conv(m.erb_dw[i], B.e[i], B.tmp, C, nF, Fi, strides[i], 0, nullptr, st, Fo[i]));
+        EGR_TRY(conv(m.erb_pw[i], B.tmp, B.e[i + 1], C, nF, *Fo[i], 1, 1, nullptr, st));
+        Fi = *Fo[i];
+    }
+    EGR_TRY(conv(m.df0, (const float*)B.fspec, B.tmp, C, nF, nb, 1, 0, nullptr, st));
+    EGR_TRY(conv(m.df0_pw, B.tmp, B.c0, C, nF, nb, 1, 1, nullptr, st));
+    EGR_TRY(conv(m.df1_dw, B.c0, B.tmp, C, nF, nb, 2, 0, nullptr, st, &w->Fc));
+    EGR_TRY(conv(m.df1_pw, B.tmp, B.c1, C, nF, w->Fc, 1, 1, nullptr, st));
+    EGR_CHECK(w->F3 * ch == m.embd && w->Fc * ch == ch * nb / 2 && w->F1 == E / 2 && w->F2 == E / 4, EGR_ERR_UNSUPPORTED,
+              "%s: encoder widths", who);
+    return EGR_OK;
+}
+
+// demb (the ERB decoder's embedding) and e[3..0] -> mask
+int erb_decoder_convs(const DfnCore& m, const char* who, int C, int nF, const EncWidths& w, hipStream_t st) {
+    const Bufs& B = m.B;
+    const int E = m.d.nb_erb;
+    EGR_TRY(conv(m.path[3], B.e[3], B.pbuf, C, nF, w.F3, 1, 1, B.demb, st));
+    EGR_TRY(conv(m.ct_dw[0], B.pbuf, B.tmp, C, nF, w.F3, 1, 0, nullptr, st));
+    EGR_TRY(conv(m.ct_pw[0], B.tmp, B.dbuf, C, nF, w.F3, 1, 1, nullptr, st));
+    for (int i = 0; i < 2; ++i) {             // convt2 (E/4 -> E/2) on conv2p(e2) + d, convt1 (E/2 -> E) on conv1p(e1) + d
+        const int Fin = i == 0 ? w.F2 : w.F1, Fwant = i == 0 ? w.F1 : E;
+        EGR_TRY(conv(m.path[2 - i], B.e[2 - i], B.pbuf, C, nF, Fin, 1, 1, B.dbuf, st));
+        int Fo = 0;
+        EGR_TRY(conv(m.ct_dw[1 + i], B.pbuf, B.tmp, C, nF, Fin, 2, 0, nullptr, st, &Fo));
+        EGR_CHECK(Fo == Fwant, EGR_ERR_UNSUPPORTED, "%s: transposed conv width %d != %d", who, Fo, Fwant);
+        EGR_TRY(conv(m.ct_pw[1 + i], B.tmp, B.dbuf, C, nF, Fo, 1, 1, nullptr, st));
+    }
+    EGR_TRY(conv(m.path[0], B.e[0], B.pbuf, C, nF, E, 1, 1, B.dbuf, st));
+    return conv(m.out0, B.pbuf, B.mask, C, nF, E, 1, 2, nullptr, st);
+}
+
+// coefs = tanh(tcoef + bias) + df_convp(c0); tcoef is the model's df_out product, bias null without one
+int df_pathway_and_coefs(const DfnCore& m, int C, int nF, const float* bias, hipStream_t st) {
+    const Bufs& B = m.B;
+    const int nb = m.d.nb_df, O2 = 2 * m.d.df_order;
+    EGR_TRY(conv(m.convp, B.c0, B.cpt, C, nF, nb, 1, 0, nullptr, st));
+    EGR_TRY(conv(m.convp_pw, B.cpt, B.cp, C, nF, nb, 1, 1, nullptr, st));
+    return rows_op(B.tcoef, bias, B.cp, B.coefs, (int64_t)C * nF * nb * O2, nb * O2, 3, st);
+}
+
+// spec_e (written by the model's assemble kernel) -> y
+int synthesis(const DfnCore& m, int C, int nF, int64_t T, float* y, hipStream_t st) {
+    const int N = m.d.fft_size;
+    hipLaunchKernelGGL(k_dfn_synth, dim3(nF, C), dim3(256), (size_t)(m.Fq + N) * 16, st, m.B.spec_e, nF, N, m.tw, m.win, m.B.frames);
+    hipLaunchKernelGGL(k_dfn_ola, dim3(grid_for((int64_t)C * T)), dim3(256), 0, st, m.B.frames, C, nF, N, m.d.hop_size, T, y);
+    EGR_HIP(hipGetLastError());
+    return EGR_OK;
+}
+
+// ---- create stages
+// The range checks both models make; `who` is the model's prefix in the messages ("egr_dfn3" / "egr_dfn2").
+int check_common(const DfnDims& d, const char* who) {
+    const int E = d.nb_erb, nb = d.nb_df, ch = d.conv_ch, O2 = 2 * d.df_order;
+    EGR_CHECK(d.fft_size > 0 && d.hop_size > 0 && d.fft_size % d.hop_size == 0 && d.fft_size % 2 == 0 && d.fft_size <= 4096, EGR_ERR_UNSUPPORTED,
+              "%s: fft_size %d / hop_size %d", who, d.fft_size, d.hop_size);
+    EGR_CHECK(E > 0 && E <= EGR_DFN3_MAX_ERB && E % 4 == 0 && nb > 0 && nb % 2 == 0 && nb <= d.fft_size / 2 + 1, EGR_ERR_UNSUPPORTED,
+              "%s: nb_erb %d / nb_df %d", who, E, nb);
+    EGR_CHECK(d.emb_hidden_dim > 0 && d.emb_hidden_dim <= GRU_HMAX && d.df_hidden_dim > 0 && d.df_hidden_dim <= GRU_HMAX,
+              EGR_ERR_UNSUPPORTED, "%s: GRU widths must be <= %d", who, GRU_HMAX);
+    EGR_CHECK(d.emb_num_layers >= 2 && d.df_num_layers >= 1 && d.emb_num_layers + d.df_num_layers <= EGR_DFN3_MAX_GRU, EGR_ERR_UNSUPPORTED,
+              "%s: GRU layer counts", who);
+    EGR_CHECK(d.df_order >= 1 && d.df_lookahead >= 0 && d.df_lookahead < d.df_order && d.conv_lookahead >= 0, EGR_ERR_UNSUPPORTED,
+              "%s: df_order / lookaheads", who);
+    EGR_CHECK(ch > 0 && d.path_groups > 0 && ch % d.path_groups == 0 && d.df_path_groups > 0 && ch % d.df_path_groups == 0 &&
+              O2 % d.df_path_groups == 0, EGR_ERR_UNSUPPORTED, "%s: conv groups", who);
+    // a stride-2 transposed conv with padding kf / 2 and output_padding kf / 2 doubles the width only for kf = 3 (torch refuses
+    // output_padding >= stride for the wider kernels)
+    EGR_CHECK(d.convt_kf == 3, EGR_ERR_UNSUPPORTED, "%s: transposed conv kernel width %d (supported: 3)", who, d.convt_kf);
+    EGR_CHECK(d.kf % 2 == 1 && d.kf_inp % 2 == 1 && d.kt >= 1 && d.kt_inp >= 1 && d.df_pathway_kt >= 1, EGR_ERR_UNSUPPORTED,
+              "%s: frequency kernels must be odd (same-size padding)", who);
+    int wsum = 0;
+    for (int e = 0; e < E; ++e) { EGR_CHECK(d.erb_widths[e] > 0, EGR_ERR_ARG, "%s: ERB width %d", who, e); wsum += d.erb_widths[e]; }
+    EGR_CHECK(wsum == d.fft_size / 2 + 1, EGR_ERR_ARG, "%s: ERB widths sum %d != %d", who, wsum, d.fft_size / 2 + 1);
+    return EGR_OK;
+}
+
+void init_core(DfnCore& m, const DfnDims& d, int device) {
+    m.d = d;
+    m.device = device;
+    m.Fq = d.fft_size / 2 + 1;
+    m.embd = d.conv_ch * d.nb_erb / 4;
+    m.wnorm = 1.f / ((float)d.fft_size * (float)d.fft_size / (float)(2 * d.hop_size));
+}
+
+// Walks the packed weights in pack order (dfn_weights.pack_order / dfn2_weights.pack_order): W(k) takes the next k floats and returns
+// their offset, cv / bn describe a convolution and the BatchNorm affine behind it.  The three conv stacks are the shared fragments of
+// the pack order; the models take their linears and GRUs with W between them.
+struct WeightCursor {
+    struct ConvSpec { Conv* L; int64_t w, s, t; };
+    int64_t pos = 0;                                        // floats consumed so far
+    std::vector<ConvSpec> convs;
+    int64_t W(int64_t k) { pos += k; return pos - k; }
+    void cv(Conv& L, int cin, int cout, int groups, int kt, int kf, int transposed = 0) {
+        L.cin = cin; L.cout = cout; L.groups = groups; L.kt = kt; L.kf = kf; L.transposed = transposed;
+        convs.push_back({&L, W((int64_t)(transposed ? cin * (cout / groups) : cout * (cin / groups)) * kt * kf), -1, -1});
+    }
+    void bn(int n) { ConvSpec& s = convs.back(); s.s = W(n); s.t = W(n); }
+    void encoder_convs(DfnCore& m) {
+        const DfnDims& d = m.d;
+        const int ch = d.conv_ch;
+        cv(m.erb0, 1, ch, 1, d.kt_inp, d.kf_inp); bn(ch);
+        for (int i = 0; i < 3; ++i) { cv(m.erb_dw[i], ch, ch, ch, d.kt, d.kf); cv(m.erb_pw[i], ch, ch, 1, 1, 1); bn(ch); }
+        cv(m.df0, 2, ch, 2, d.kt_inp, d.kf_inp); cv(m.df0_pw, ch, ch, 1, 1, 1); bn(ch);
+        cv(m.df1_dw, ch, ch, ch, d.kt, d.kf); cv(m.df1_pw, ch, ch, 1, 1, 1); bn(ch);
+    }
+    void erb_decoder_convs(DfnCore& m) {
+        const DfnDims& d = m.d;
+        const int ch = d.conv_ch;
+        for (int i = 0; i < 3; ++i) {
+            cv(m.path[3 - i], ch, ch, d.path_groups, 1, 1); bn(ch);
+            if (i == 0) cv(m.ct_dw[0], ch, ch, ch, d.kt, d.kf);
+            else cv(m.ct_dw[i], ch, ch, ch, 1, d.convt_kf, 1);
+            cv(m.ct_pw[i], ch, ch, 1, 1, 1); bn(ch);
+        }
+        cv(m.path[0], ch, ch, d.path_groups, 1, 1); bn(ch);
+        cv(m.out0, ch, 1, 1, d.kt, d.kf); bn(1);
+    }
+    void df_pathway_convs(DfnCore& m) {
+        const int O2 = 2 * m.d.df_order;
+        cv(m.convp, m.d.conv_ch, O2, m.d.df_path_groups, m.d.df_pathway_kt, 1);
+        cv(m.convp_pw, O2, O2, 1, 1, 1); bn(O2);
+    }
+};
+
+constexpr int64_t DENSE_WHH_FLOATS = (int64_t)GRU_PER_THREAD * GRU_THREADS;
+
+// W_hh [3H][H] -> thread-minor (element, thread) order of k_dfn_gru, DENSE_WHH_FLOATS floats
+void repack_dense_whh(const float* w, int H, float* dst) {
+    for (int t = 0; t < GRU_THREADS; ++t)
+        for (int e = 0; e < GRU_PER_THREAD; ++e) {
+            const int j = e / GRU_K, k = e % GRU_K;
+            const int q = j * GRU_THREADS + t, row = q / GRU_SEG, col = GRU_SEG * k + q % GRU_SEG;
+            dst[(int64_t)e * GRU_THREADS + t] = (row < 3 * H && col < H) ? w[(int64_t)row * H + col] : 0.f;
+        }
+}
+
+// device image: packed weights | repacked W_hh per layer (the model fills [align64(n_floats), o_tw)) | twiddles (double2) | window |
+// band tables (band_lo [E], band_w [E], band_of [Fq])
+struct Image {
+    std::vector<float> host;
+    int64_t o_tw = 0, o_win = 0, o_tab = 0;
+};
+
+Image build_tables(const DfnDims& d, const float* packed, int64_t n_floats, int64_t o_tw) {
+    const int N = d.fft_size, E = d.nb_erb;
+    Image im;
+    im.o_tw = o_tw;
+    im.o_win = o_tw + 4LL * N;
+    im.o_tab = im.o_win + N;
+    im.host.assign((size_t)(im.o_tab + 2 * E + N / 2 + 1), 0.f);
+    memcpy(im.host.data(), packed, sizeof(float) * n_floats);
+    double* twd = (double*)(im.host.data() + im.o_tw);
+    for (int n = 0; n < N; ++n) {
+        twd[2 * n] = cos(2.0 * M_PI * n / N);
+        twd[2 * n + 1] = sin(2.0 * M_PI * n / N);
+    }
+    const int h = N / 2;
+    for (int n = 0; n < N; ++n) {
+        const double s = sin(0.5 * M_PI * (n + 0.5) / h);
+        im.host[im.o_win + n] = (float)sin(0.5 * M_PI * s * s);
+    }
+    int* tab = (int*)(im.host.data() + im.o_tab);
+    int lo = 0;
+    for (int e = 0; e < E; ++e) {
+        tab[e] = lo;
+        tab[E + e] = d.erb_widths[e];
+        for (int j = 0; j < d.erb_widths[e]; ++j) tab[2 * E + lo + j] = e;
+        lo += d.erb_widths[e];
+    }
+    return im;
+}
+
+// The image onto m.device as m.dev_w, and the dynamic-LDS cap of the analysis / synthesis kernels.  `who` is the create function's
+// name.  On failure nothing stays allocated; either way the device that was current is current again.
+int upload(DfnCore& m, const char* who, const Image& im) {
+    const size_t bytes = sizeof(float) * im.host.size();
+    int prev = 0;
+    if (hipGetDevice(&prev) != hipSuccess || hipSetDevice(m.device) != hipSuccess || hipMalloc(&m.dev_w, bytes) != hipSuccess ||
+        hipMemcpy(m.dev_w, im.host.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) {
+        set_error("%s: device allocation / upload failed on device %d", who, m.device);
+        if (m.dev_w) (void)hipFree(m.dev_w);
+        m.dev_w = nullptr;
+        (void)hipSetDevice(prev);
+        return EGR_ERR_HIP;
+    }
+    // the analysis / synthesis DFTs keep a frame and the twiddles in dynamic LDS: 24 N and 16 (1.5 N + 1) bytes, above the 64 KiB
+    // default from N = 2732 on.  The attribute is a process-wide cap per kernel, so it is raised to the CU's maximum (as the Fat-Llama
+    // plans do), never to this config's need.
+    const int N = m.d.fft_size;
+    const size_t lds_an = (size_t)N * 24, lds_syn = (size_t)(m.Fq + N) * 16;
+    hipError_t ea = hipSuccess;
+    if (lds_an > (size_t)DFN_LDS_MAX || lds_syn > (size_t)DFN_LDS_MAX) {
+        set_error("%s: fft_size %d needs %zu / %zu bytes of LDS (limit %d)", who, N, lds_an, lds_syn, DFN_LDS_MAX);
+        ea = hipErrorInvalidValue;
+    }
+    if (ea == hipSuccess) ea = hipFuncSetAttribute((const void*)k_dfn_analysis, hipFuncAttributeMaxDynamicSharedMemorySize, DFN_LDS_MAX);
+    if (ea == hipSuccess) ea = hipFuncSetAttribute((const void*)k_dfn_synth, hipFuncAttributeMaxDynamicSharedMemorySize, DFN_LDS_MAX);
+    if (ea != hipSuccess) {
+        if (lds_an <= (size_t)DFN_LDS_MAX && lds_syn <= (size_t)DFN_LDS_MAX)
+            set_error("%s: hipFuncSetAttribute(MaxDynamicSharedMemorySize) -> %s", who, hipGetErrorString(ea));
+        (void)hipFree(m.dev_w);
+        m.dev_w = nullptr;
+        (void)hipSetDevice(prev);
+        return EGR_ERR_HIP;
+    }
+    (void)hipSetDevice(prev);
+    return EGR_OK;
+}
+
+// Points the convolutions and the tables into the uploaded image.
+void bind(DfnCore& m, const WeightCursor& wc, const Image& im) {
+    float* D = m.dev_w;
+    for (const auto& s : wc.convs) {
+        s.L->w = D + s.w;
+        if (s.s >= 0) { s.L->scale = D + s.s; s.L->shift = D + s.t; }
+    }
+    m.tw = (const double2*)(D + im.o_tw);
+    m.win = D + im.o_win;
+    m.band_lo = (const int*)(D + im.o_tab);
+    m.band_w = m.band_lo + m.d.nb_erb;
+    m.band_of = m.band_lo + 2 * m.d.nb_erb;
+}
+
+// ---- entry-point bodies; `who` is the extern "C" function's name
+int enhance_checks(const DfnCore* m, const char* who, const float* x48, int channels, int64_t n, const float* y) {
+    EGR_CHECK(m && x48 && y && channels >= 1 && channels <= 65535 && n >= 1, EGR_ERR_ARG, "%s: bad argument", who);
+    // nF * 4096 fits an int (which also keeps nF below 65535 * 4096)
+    EGR_CHECK(m->frames_of(n) <= 2147483647LL / 4096, EGR_ERR_UNSUPPORTED, "%s: input too long", who);
+    int cur = -1;
+    EGR_HIP(hipGetDevice(&cur));
+    EGR_CHECK(cur == m->device, EGR_ERR_ARG, "%s: handle belongs to device %d, current device is %d", who, m->device, cur);
+    return EGR_OK;
+}
+
+void destroy(DfnCore& m) {
+    int prev = 0;
+    (void)hipGetDevice(&prev);
+    (void)hipSetDevice(m.device);
+    if (m.ws) {                                // hipMallocAsync memory: returned stream-ordered, then waited for (not a pipeline call)
+        (void)hipFreeAsync(m.ws, nullptr);
+        (void)hipDeviceSynchronize();
+    }
+    if (m.dev_w) (void)hipFree(m.dev_w);
+    (void)hipSetDevice(prev);
+}
+
+static_assert(EGR_DFN2_STAGE_GRU0 == EGR_DFN3_STAGE_GRU0, "one GRU stage range for both models");
+
+// The stages both models keep in the shared buffers (all but EMB), GRU layer g at EGR_DFN3_STAGE_GRU0 + g; false: not one of them.
+bool stage_common(const DfnCore& m, int stage, const float** src, int64_t* n) {
+    const int64_t R = (int64_t)m.lastC * m.lastF;
+    const DfnDims& d = m.d;
+    const Bufs& B = m.B;
+    switch (stage) {
+        case EGR_DFN3_STAGE_SPEC: *src = (const float*)B.spec; *n = R * m.Fq * 2; return true;
+        case EGR_DFN3_STAGE_FEAT_ERB: *src = B.ferb; *n = R * d.nb_erb; return true;
+        case EGR_DFN3_STAGE_FEAT_SPEC: *src = (const float*)B.fspec; *n = R * d.nb_df * 2; return true;
+        case EGR_DFN3_STAGE_E0: *src = B.e[0]; *n = R * d.nb_erb * d.conv_ch; return true;
+        case EGR_DFN3_STAGE_E1: *src = B.e[1]; *n = R * (d.nb_erb / 2) * d.conv_ch; return true;
+        case EGR_DFN3_STAGE_E2: *src = B.e[2]; *n = R * (d.nb_erb / 4) * d.conv_ch; return true;
+        case EGR_DFN3_STAGE_E3: *src = B.e[3]; *n = R * (d.nb_erb / 4) * d.conv_ch; return true;
+        case EGR_DFN3_STAGE_C0: *src = B.c0; *n = R * d.nb_df * d.conv_ch; return true;
+        case EGR_DFN3_STAGE_MASK: *src = B.mask; *n = R * d.nb_erb; return true;
+        case EGR_DFN3_STAGE_COEFS: *src = B.coefs; *n = R * d.nb_df * 2 * d.df_order; return true;
+        case EGR_DFN3_STAGE_SPEC_E: *src = (const float*)B.spec_e; *n = R * m.Fq * 2; return true;
+    }
+    if (stage < EGR_DFN3_STAGE_GRU0 || stage >= EGR_DFN3_STAGE_GRU0 + m.ngru()) return false;
+    *src = B.gout[stage - EGR_DFN3_STAGE_GRU0];
+    *n = R * m.gru_width(stage - EGR_DFN3_STAGE_GRU0);
+    return true;
+}
+
+// own(stage, &src, &n) names the model's own stages (it is asked first and leaves src null for every other)
+template <class Own>
+int stage_copy(const DfnCore& m, const char* who, int stage, float* dst, int64_t capacity, int64_t* count, void* stream, Own own) {
+    EGR_CHECK(m.ws, EGR_ERR_ARG, "%s: no enhance call yet", who);
+    const float* src = nullptr;
+    int64_t n = 0;
+    own(stage, &src, &n);
+    EGR_CHECK(src || stage_common(m, stage, &src, &n), EGR_ERR_ARG, "%s: unknown stage %d", who, stage);
+    *count = n;
+    if (!dst) return EGR_OK;
+    EGR_CHECK(capacity >= n, EGR_ERR_ARG, "%s: capacity %lld < %lld", who, (long long)capacity, (long long)n);
+    EGR_HIP(hipMemcpyAsync(dst, src, sizeof(float) * n, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return EGR_OK;
+}
+
+// One recurrence layer alone on zero projections: launch(proj, out, sum, nF) runs it for nF steps on the null stream; a short warm-up
+// launch, then the timed one.  sum is room for DeepFilterNet2's running sum when with_sum, else null.
+template <class Launch>
+int time_gru_harness(const DfnCore* m, const char* who, int layer, int channels, int64_t steps, bool with_sum, double* us_per_step,
+                     Launch launch) {
+    EGR_CHECK(m && us_per_step && channels >= 1 && channels <= 64 && steps >= 1 && steps <= 10000000, EGR_ERR_ARG, "%s: bad argument", who);
+    EGR_CHECK(layer >= 0 && layer < m->ngru(), EGR_ERR_ARG, "%s: layer %d", who, layer);
+    const size_t nh = (size_t)channels * steps * m->gru_width(layer);
+    float *proj = nullptr, *out = nullptr;
+    hipEvent_t e0, e1;
+    EGR_HIP(hipMalloc(&proj, sizeof(float) * 3 * nh));
+    EGR_HIP(hipMalloc(&out, sizeof(float) * (with_sum ? 2 : 1) * nh));
+    float* sum = with_sum ? out + nh : nullptr;
+    EGR_HIP(hipMemset(proj, 0, sizeof(float) * 3 * nh));
+    EGR_HIP(hipEventCreate(&e0));
+    EGR_HIP(hipEventCreate(&e1));
+    launch(proj, out, sum, (int)(steps < 64 ? steps : 64));
+    EGR_HIP(hipEventRecord(e0, 0));
+    launch(proj, out, sum, (int)steps);
+    EGR_HIP(hipEventRecord(e1, 0));
+    EGR_HIP(hipEventSynchronize(e1));
+    float ms = 0.f;
+    EGR_HIP(hipEventElapsedTime(&ms, e0, e1));
+    *us_per_step = 1e3 * ms / (double)steps;
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    (void)hipFree(proj);
+    (void)hipFree(out);
+    EGR_HIP(hipGetLastError());
+    return EGR_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ DeepFilterNet3
+struct Gru {
+    const float* wih = nullptr; const float* bih = nullptr; const float* bhh = nullptr; float* whh_pk = nullptr;
+    int in = 0, H = 0;
+};
+
+struct Dfn3 {
+    egr_dfn3_config cfg;
+    DfnCore core;
+    const float *fc_emb = nullptr, *enc_lin_in = nullptr, *enc_lin_out = nullptr, *erb_lin_in = nullptr, *erb_lin_out = nullptr;
+    const float *df_lin_in = nullptr, *df_skip = nullptr, *df_out = nullptr;
+    std::vector<Gru> grus;
+    struct Extra { float *emb, *gx; } X;
+};
+
+size_t layout(const Dfn3& m, int C, int nF, char* base, Bufs& B, Dfn3::Extra& X) {
+    const int64_t R = (int64_t)C * nF;
+    const int Hm = m.cfg.emb_hidden_dim > m.cfg.df_hidden_dim ? m.cfg.emb_hidden_dim : m.cfg.df_hidden_dim;
+    Take take{base};
+    layout_common(m.core, R, take, B);
+    X.emb = take(R * m.core.embd);
+    X.gx = take(R * Hm);
+    return take.off;
+}
+
+size_t workspace_need(const Dfn3& m, int C, int nF) {       // measures only: the handle's buffers stay those of the last call
+    Bufs B;
+    Dfn3::Extra X;
+    return layout(m, C, nF, nullptr, B, X);
+}
+
+// x [C * nF][in] -> out [C * nF][H] through one GRU layer
+int gru_layer(const Gru& g, const float* x, float* proj, float* out, int C, int nF, hipStream_t st) {
+    const int64_t R = (int64_t)C * nF;
+    EGR_TRY(egr_bgemm(x, g.wih, proj, 1, 1, (int)R, 3 * g.H, g.in, g.in, g.in, 3 * g.H, 0, 0, 0, 0, 0, 0, 1, 1.f, st));
+    EGR_TRY(rows_op(proj, g.bih, nullptr, proj, R * 3 * g.H, 3 * g.H, 0, st));
+    hipLaunchKernelGGL(k_dfn_gru, dim3(C), dim3(GRU_THREADS), 0, st, proj, g.whh_pk, g.bhh, g.H, nF, out);
+    return EGR_OK;
+}
+
+int run(Dfn3& m, const float* x, int C, int64_t T, float* y, hipStream_t st) {
+    const egr_dfn3_config& c = m.cfg;
+    DfnCore& k = m.core;
+    const char* who = "egr_dfn3";
+    const int nF = (int)k.frames_of(T);
+    const int64_t R = (int64_t)C * nF;
+    const int nb = c.nb_df, O2 = 2 * c.df_order, embd = k.embd;
+    Bufs& B = k.B;
+    Dfn3::Extra& X = m.X;
+    EGR_TRY(ensure_workspace(k, workspace_need(m, C, nF), C, nF, T, st));
+    layout(m, C, nF, (char*)k.ws, B, X);
+    features(k, x, C, nF, T, st);
+    EncWidths w;
+    EGR_TRY(encoder_convs(k, who, C, nF, &w, st));
+    EGR_TRY(grouped_linear(B.c1, m.fc_emb, B.emb0, R, w.Fc * c.conv_ch, embd, c.enc_lin_groups, st));
+    EGR_TRY(rows_op(B.emb0, nullptr, B.e[3], B.emb0, R * embd, embd, 1, st));      // emb = e3 + relu(fc_emb(c1))
+    const int He = c.emb_hidden_dim, Hd = c.df_hidden_dim;
+    int g = 0;
+    EGR_TRY(grouped_linear(B.emb0, m.enc_lin_in, X.gx, R, embd, He, c.lin_groups, st));
+    EGR_TRY(rows_op(X.gx, nullptr, nullptr, X.gx, R * He, He, 1, st));
+    EGR_TRY(gru_layer(m.grus[g], X.gx, B.proj, B.gout[g], C, nF, st));
+    EGR_TRY(grouped_linear(B.gout[g], m.enc_lin_out, X.emb, R, He, embd, c.lin_groups, st));
+    EGR_TRY(rows_op(X.emb, nullptr, nullptr, X.emb, R * embd, embd, 1, st));
+    ++g;
+    // ERB decoder
+    EGR_TRY(grouped_linear(X.emb, m.erb_lin_in, X.gx, R, embd, He, c.lin_groups, st));
+    EGR_TRY(rows_op(X.gx, nullptr, nullptr, X.gx, R * He, He, 1, st));
+    const float* xin = X.gx;
+    for (int l = 0; l < c.emb_num_layers - 1; ++l, ++g) {
+        EGR_TRY(gru_layer(m.grus[g], xin, B.proj, B.gout[g], C, nF, st));
+        xin = B.gout[g];
+    }
+    EGR_TRY(grouped_linear(xin, m.erb_lin_out, B.demb, R, He, embd, c.lin_groups, st));
+    EGR_TRY(rows_op(B.demb, nullptr, nullptr, B.demb, R * embd, embd, 1, st));
+    EGR_TRY(erb_decoder_convs(k, who, C, nF, w, st));
+    // DF decoder
+    EGR_TRY(grouped_linear(X.emb, m.df_lin_in, X.gx, R, embd, Hd, c.lin_groups, st));
+    EGR_TRY(rows_op(X.gx, nullptr, nullptr, X.gx, R * Hd, Hd, 1, st));
+    xin = X.gx;
+    for (int l = 0; l < c.df_num_layers; ++l, ++g) {
+        EGR_TRY(gru_layer(m.grus[g], xin, B.proj, B.gout[g], C, nF, st));
+        xin = B.gout[g];
+    }
+    if (m.df_skip) {
+        EGR_TRY(grouped_linear(X.emb, m.df_skip, B.dfc, R, embd, Hd, c.lin_groups, st));
+        EGR_TRY(rows_op(B.dfc, nullptr, xin, B.dfc, R * Hd, Hd, 0, st));
+        xin = B.dfc;
+    }
+    EGR_TRY(grouped_linear(xin, m.df_out, B.tcoef, R, Hd, nb * O2, c.lin_groups, st));
+    EGR_TRY(df_pathway_and_coefs(k, C, nF, nullptr, st));                            // tanh(df_out(c)) + df_convp(c0)
+    // mask + deep filter, synthesis
+    hipLaunchKernelGGL(k_dfn_assemble, dim3(grid_for(R * k.Fq)), dim3(256), 0, st, B.spec, B.mask, B.coefs, k.band_of, C, nF, k.Fq,
+                       c.nb_erb, nb, c.df_order, c.df_lookahead, B.spec_e);
+    return synthesis(k, C, nF, T, y, st);
+}
+
+// ------------------------------------------------------------------------------------------------ DeepFilterNet2
 struct GGru {                 // one GroupedGRU layer: G GRUs of width h on input slices of width in / G
     const float* wih = nullptr; const float* bih = nullptr; const float* bhh = nullptr; float* whh_pk = nullptr;
     int in = 0, H = 0, G = 1, h = 0, K = 0, S = 1, shuffle = 0;
@@ -1013,73 +1078,31 @@ inline void ggru_shape(int h, int* K, int* S) {
     while (*K * *S < h) *S *= 2;
 }
 
-}  // namespace
-
 struct Dfn2 {
     egr_dfn2_config cfg;
-    int device = 0, Fq = 0, embd = 0;
-    float* dev_w = nullptr;
-    const double2* tw = nullptr; const float* win = nullptr; const int* band_lo = nullptr; const int* band_w = nullptr;
-    const int* band_of = nullptr;
-    float wnorm = 0.f;
-    Conv erb0, erb_dw[3], erb_pw[3], df0, df0_pw, df1_dw, df1_pw, path[4], ct_dw[3], ct_pw[3], out0, convp, convp_pw;
+    DfnCore core;
     const float *fc_emb_w = nullptr, *fc_emb_b = nullptr, *erb_fc_w = nullptr, *erb_fc_b = nullptr;
     const float *df_skip = nullptr, *df_out = nullptr, *df_out_b = nullptr, *fc_a_w = nullptr, *fc_a_b = nullptr;
-    std::vector<GGru> grus;                 // enc (1), erb decoder (emb_num_layers - 1), df decoder (df_num_layers)
-    void* ws = nullptr; size_t ws_bytes = 0;
-    int lastC = 0, lastF = 0; int64_t lastT = 0;
-    struct Bufs {
-        float2 *spec, *spec_e, *fspec; float *db, *ferb, *e[4], *c0, *c1, *tmp, *lin, *emb0, *proj, *gout[EGR_DFN3_MAX_GRU];
-        float *gsum[EGR_DFN3_MAX_GRU], *dfc, *alpha, *demb, *pbuf, *dbuf, *mask, *tcoef, *cpt, *cp, *coefs, *frames;
-    } B;
+    std::vector<GGru> grus;
+    struct Extra { float *lin, *gsum[EGR_DFN3_MAX_GRU], *alpha; } X;
 };
 
-namespace {
-
-size_t layout2(const Dfn2& m, int C, int nF, Dfn2::Bufs* B, char* base) {
-    const egr_dfn2_config& c = m.cfg;
+size_t layout(const Dfn2& m, int C, int nF, char* base, Bufs& B, Dfn2::Extra& X) {
+    const DfnCore& k = m.core;
     const int64_t R = (int64_t)C * nF;
-    const int ch = c.conv_ch, E = c.nb_erb, nb = c.nb_df, O2 = 2 * c.df_order;
-    const int Hm = c.emb_hidden_dim > c.df_hidden_dim ? c.emb_hidden_dim : c.df_hidden_dim;
-    const int Fm = E > nb ? E : nb;
-    const int Lm = m.embd > nb * O2 ? m.embd : nb * O2;
-    size_t off = 0;
-    auto take = [&](int64_t nfl) -> float* {
-        float* p = base ? (float*)(base + off) : nullptr;
-        off += ((size_t)nfl * sizeof(float) + 255) & ~(size_t)255;
-        return p;
-    };
-    Dfn2::Bufs b;
-    b.spec = (float2*)take(R * m.Fq * 2);
-    b.spec_e = (float2*)take(R * m.Fq * 2);
-    b.fspec = (float2*)take(R * nb * 2);
-    b.db = take(R * E);
-    b.ferb = take(R * E);
-    b.e[0] = take(R * E * ch);
-    b.e[1] = take(R * (E / 2) * ch);
-    b.e[2] = take(R * (E / 4) * ch);
-    b.e[3] = take(R * (E / 4) * ch);
-    b.c0 = take(R * nb * ch);
-    b.c1 = take(R * (nb / 2) * ch);
-    b.tmp = take(R * Fm * ch);
-    b.lin = take(R * Lm);
-    b.emb0 = take(R * m.embd);
-    b.proj = take(R * 3 * Hm);
-    for (size_t g = 0; g < EGR_DFN3_MAX_GRU; ++g) b.gout[g] = g < m.grus.size() ? take(R * m.grus[g].H) : nullptr;
-    for (size_t g = 0; g < EGR_DFN3_MAX_GRU; ++g) b.gsum[g] = g < m.grus.size() ? take(R * m.grus[g].H) : nullptr;
-    b.dfc = take(R * c.df_hidden_dim);
-    b.alpha = take(R);
-    b.demb = take(R * m.embd);
-    b.pbuf = take(R * E * ch);
-    b.dbuf = take(R * E * ch);
-    b.mask = take(R * E);
-    b.tcoef = take(R * nb * O2);
-    b.cpt = take(R * nb * O2);
-    b.cp = take(R * nb * O2);
-    b.coefs = take(R * nb * O2);
-    b.frames = take(R * c.fft_size);
-    if (B) *B = b;
-    return off;
+    const int no = m.cfg.nb_df * 2 * m.cfg.df_order;
+    Take take{base};
+    layout_common(k, R, take, B);
+    X.lin = take(R * (k.embd > no ? k.embd : no));
+    for (int g = 0; g < EGR_DFN3_MAX_GRU; ++g) X.gsum[g] = g < k.ngru() ? take(R * k.gru_width(g)) : nullptr;
+    X.alpha = take(R);
+    return take.off;
+}
+
+size_t workspace_need(const Dfn2& m, int C, int nF) {       // measures only: the handle's buffers stay those of the last call
+    Bufs B;
+    Dfn2::Extra X;
+    return layout(m, C, nF, nullptr, B, X);
 }
 
 int epi(const float* a, const float* bias, const float* res, float* y, int64_t n, int cols, int G, int act, hipStream_t st) {
@@ -1117,227 +1140,235 @@ int ggru_layer(const GGru& g, const float* x, float* proj, const float* sum_in, 
     return EGR_OK;
 }
 
-int run2(Dfn2& m, const float* x, int C, int64_t T, float* y, hipStream_t st) {
+int run(Dfn2& m, const float* x, int C, int64_t T, float* y, hipStream_t st) {
     const egr_dfn2_config& c = m.cfg;
-    const int N = c.fft_size, hop = c.hop_size, nF = (int)((T + N) / hop);
+    DfnCore& k = m.core;
+    const char* who = "egr_dfn2";
+    const int nF = (int)k.frames_of(T);
     const int64_t R = (int64_t)C * nF;
-    const int ch = c.conv_ch, E = c.nb_erb, nb = c.nb_df, O2 = 2 * c.df_order;
-    const size_t need = layout2(m, C, nF, nullptr, nullptr);
-    if (need > m.ws_bytes) {
-        if (m.ws) EGR_HIP(hipFreeAsync(m.ws, st));
-        m.ws = nullptr;
-        m.ws_bytes = 0;
-        EGR_HIP(hipMallocAsync(&m.ws, need, st));
-        m.ws_bytes = need;
-    }
-    Dfn2::Bufs& B = m.B;
-    layout2(m, C, nF, &B, (char*)m.ws);
-    m.lastC = C; m.lastF = nF; m.lastT = T;
-    // features (P1: the conv_lookahead shift whenever it is > 0)
-    hipLaunchKernelGGL(k_dfn_analysis, dim3(nF, C), dim3(256), (size_t)N * 24, st, x, T, nF, N, hop, m.tw, m.win, m.wnorm, B.spec);
-    hipLaunchKernelGGL(k_dfn_erb_db, dim3(grid_for(R * E)), dim3(256), 0, st, B.spec, R, m.Fq, E, m.band_lo, m.band_w, B.db);
-    hipLaunchKernelGGL(k_dfn_norm_scan, dim3((C * (E + nb) + 63) / 64), dim3(64), 0, st, B.db, B.spec, C, nF, m.Fq, E, nb,
-                       c.norm_alpha, c.conv_lookahead, B.ferb, B.fspec);
-    // encoder (P2)
-    int F1 = 0, F2 = 0, F3 = 0, Fc = 0;
-    EGR_TRY(conv(m.erb0, B.ferb, B.e[0], C, nF, E, 1, 1, nullptr, st));
-    const int strides[3] = {2, 2, 1};
-    int Fi = E;
-    for (int i = 0; i < 3; ++i) {
-        int Fo;
-        EGR_TRY(conv(m.erb_dw[i], B.e[i], B.tmp, C, nF, Fi, strides[i], 0, nullptr, st, &Fo));
-        EGR_TRY(conv(m.erb_pw[i], B.tmp, B.e[i + 1], C, nF, Fo, 1, 1, nullptr, st));
-        Fi = Fo;
-        if (i == 0) F1 = Fo; else if (i == 1) F2 = Fo; else F3 = Fo;
-    }
-    EGR_TRY(conv(m.df0, (const float*)B.fspec, B.tmp, C, nF, nb, 1, 0, nullptr, st));
-    EGR_TRY(conv(m.df0_pw, B.tmp, B.c0, C, nF, nb, 1, 1, nullptr, st));
-    EGR_TRY(conv(m.df1_dw, B.c0, B.tmp, C, nF, nb, 2, 0, nullptr, st, &Fc));
-    EGR_TRY(conv(m.df1_pw, B.tmp, B.c1, C, nF, Fc, 1, 1, nullptr, st));
-    EGR_CHECK(F3 * ch == m.embd && Fc * ch == ch * nb / 2 && F1 == E / 2 && F2 == E / 4, EGR_ERR_UNSUPPORTED, "egr_dfn2: encoder widths");
+    const int nb = c.nb_df, O2 = 2 * c.df_order, Hd = c.df_hidden_dim;
+    Bufs& B = k.B;
+    Dfn2::Extra& X = m.X;
+    EGR_TRY(ensure_workspace(k, workspace_need(m, C, nF), C, nF, T, st));
+    layout(m, C, nF, (char*)k.ws, B, X);
+    features(k, x, C, nF, T, st);                                                     // P1
+    EncWidths w;
+    EGR_TRY(encoder_convs(k, who, C, nF, &w, st));                                    // P2
     // emb0 = e3 + GroupedLinear(c1) (no activation)
-    EGR_TRY(glinear(B.c1, m.fc_emb_w, m.fc_emb_b, B.lin, B.emb0, R, Fc * ch, m.embd, c.lin_groups, c.group_shuffle, 0, B.e[3], st));
+    EGR_TRY(glinear(B.c1, m.fc_emb_w, m.fc_emb_b, X.lin, B.emb0, R, w.Fc * c.conv_ch, k.embd, c.lin_groups, c.group_shuffle, 0, B.e[3], st));
     size_t g = 0;
-    EGR_TRY(ggru_layer(m.grus[g], B.emb0, B.proj, nullptr, B.gout[g], B.gsum[g], C, nF, st));
-    const float* emb = B.gsum[g];
+    EGR_TRY(ggru_layer(m.grus[g], B.emb0, B.proj, nullptr, B.gout[g], X.gsum[g], C, nF, st));
+    const float* emb = X.gsum[g];
     ++g;
     // ERB decoder (P5)
     const float* xin = emb;
     const float* sum = nullptr;
-    for (int k = 0; k < c.emb_num_layers - 1; ++k, ++g) {
-        EGR_TRY(ggru_layer(m.grus[g], xin, B.proj, sum, B.gout[g], B.gsum[g], C, nF, st));
+    for (int l = 0; l < c.emb_num_layers - 1; ++l, ++g) {
+        EGR_TRY(ggru_layer(m.grus[g], xin, B.proj, sum, B.gout[g], X.gsum[g], C, nF, st));
         xin = B.gout[g];
-        sum = B.gsum[g];
+        sum = X.gsum[g];
     }
-    EGR_TRY(glinear(sum, m.erb_fc_w, m.erb_fc_b, B.lin, B.demb, R, c.emb_hidden_dim, m.embd, c.lin_groups, c.group_shuffle, 1, nullptr, st));
-    EGR_TRY(conv(m.path[3], B.e[3], B.pbuf, C, nF, F3, 1, 1, B.demb, st));
-    EGR_TRY(conv(m.ct_dw[0], B.pbuf, B.tmp, C, nF, F3, 1, 0, nullptr, st));
-    EGR_TRY(conv(m.ct_pw[0], B.tmp, B.dbuf, C, nF, F3, 1, 1, nullptr, st));
-    for (int i = 0; i < 2; ++i) {
-        const int Fin = i == 0 ? F2 : F1, Fwant = i == 0 ? F1 : E;
-        EGR_TRY(conv(m.path[2 - i], B.e[2 - i], B.pbuf, C, nF, Fin, 1, 1, B.dbuf, st));
-        int Fo = 0;
-        EGR_TRY(conv(m.ct_dw[1 + i], B.pbuf, B.tmp, C, nF, Fin, 2, 0, nullptr, st, &Fo));
-        EGR_CHECK(Fo == Fwant, EGR_ERR_UNSUPPORTED, "egr_dfn2: transposed conv width %d != %d", Fo, Fwant);
-        EGR_TRY(conv(m.ct_pw[1 + i], B.tmp, B.dbuf, C, nF, Fo, 1, 1, nullptr, st));
-    }
-    EGR_TRY(conv(m.path[0], B.e[0], B.pbuf, C, nF, E, 1, 1, B.dbuf, st));
-    EGR_TRY(conv(m.out0, B.pbuf, B.mask, C, nF, E, 1, 2, nullptr, st));
+    EGR_TRY(glinear(sum, m.erb_fc_w, m.erb_fc_b, X.lin, B.demb, R, c.emb_hidden_dim, k.embd, c.lin_groups, c.group_shuffle, 1, nullptr, st));
+    EGR_TRY(erb_decoder_convs(k, who, C, nF, w, st));
     // DF decoder (P6)
     xin = emb;
     sum = nullptr;
-    for (int k = 0; k < c.df_num_layers; ++k, ++g) {
-        EGR_TRY(ggru_layer(m.grus[g], xin, B.proj, sum, B.gout[g], B.gsum[g], C, nF, st));
+    for (int l = 0; l < c.df_num_layers; ++l, ++g) {
+        EGR_TRY(ggru_layer(m.grus[g], xin, B.proj, sum, B.gout[g], X.gsum[g], C, nF, st));
         xin = B.gout[g];
-        sum = B.gsum[g];
+        sum = X.gsum[g];
     }
-    const int Hd = c.df_hidden_dim;
     if (m.df_skip) {
         EGR_TRY(grouped_linear(emb, m.df_skip, B.dfc, R, c.emb_hidden_dim, Hd, c.lin_groups, st));
         EGR_TRY(rows_op(sum, nullptr, B.dfc, B.dfc, R * Hd, Hd, 0, st));            // c = s + skip(emb)
         sum = B.dfc;
     }
-    hipLaunchKernelGGL(k_dfn2_alpha, dim3(grid_for(R)), dim3(256), 0, st, sum, m.fc_a_w, m.fc_a_b, R, Hd, B.alpha);
+    hipLaunchKernelGGL(k_dfn2_alpha, dim3(grid_for(R)), dim3(256), 0, st, sum, m.fc_a_w, m.fc_a_b, R, Hd, X.alpha);
     if (c.df_output_layer == 1)
         EGR_TRY(egr_bgemm(sum, m.df_out, B.tcoef, 1, 1, (int)R, nb * O2, Hd, Hd, Hd, nb * O2, 0, 0, 0, 0, 0, 0, 1, 1.f, st));
     else
         EGR_TRY(grouped_linear(sum, m.df_out, B.tcoef, R, Hd, nb * O2, c.lin_groups, st));
-    EGR_TRY(conv(m.convp, B.c0, B.cpt, C, nF, nb, 1, 0, nullptr, st));
-    EGR_TRY(conv(m.convp_pw, B.cpt, B.cp, C, nF, nb, 1, 1, nullptr, st));
-    EGR_TRY(rows_op(B.tcoef, m.df_out_b, B.cp, B.coefs, R * nb * O2, nb * O2, 3, st));     // tanh(df_out(c)) + df_convp(c0)
+    EGR_TRY(df_pathway_and_coefs(k, C, nF, m.df_out_b, st));                         // tanh(df_out(c)) + df_convp(c0)
     // mask, then deep filter (P7), synthesis
-    hipLaunchKernelGGL(k_dfn2_assemble, dim3(grid_for(R * m.Fq)), dim3(256), 0, st, B.spec, B.mask, B.coefs, B.alpha, m.band_of, C, nF,
-                       m.Fq, E, nb, c.df_order, c.df_lookahead, B.spec_e);
-    hipLaunchKernelGGL(k_dfn_synth, dim3(nF, C), dim3(256), (size_t)(m.Fq + N) * 16, st, B.spec_e, nF, N, m.tw, m.win, B.frames);
-    hipLaunchKernelGGL(k_dfn_ola, dim3(grid_for((int64_t)C * T)), dim3(256), 0, st, B.frames, C, nF, N, hop, T, y);
-    EGR_HIP(hipGetLastError());
-    return EGR_OK;
+    hipLaunchKernelGGL(k_dfn2_assemble, dim3(grid_for(R * k.Fq)), dim3(256), 0, st, B.spec, B.mask, B.coefs, X.alpha, k.band_of, C, nF,
+                       k.Fq, c.nb_erb, nb, c.df_order, c.df_lookahead, B.spec_e);
+    return synthesis(k, C, nF, T, y, st);
 }
 
 }  // namespace
 }  // namespace egr
 
-using egr::Dfn2;
+// ================================================================================================ DeepFilterNet3 entry points
+extern "C" int egr_dfn3_create(void** handle, const egr_dfn3_config* cfg, const float* packed, int64_t n_floats, int device) {
+    using namespace egr;
+    EGR_CHECK(handle && cfg && packed && n_floats > 0, EGR_ERR_ARG, "egr_dfn3_create: null argument");
+    EGR_CHECK(cfg->struct_bytes == (int)sizeof(egr_dfn3_config), EGR_ERR_ARG, "egr_dfn3_create: struct_bytes %d != %d",
+              cfg->struct_bytes, (int)sizeof(egr_dfn3_config));
+    const egr_dfn3_config& c = *cfg;
+    DfnDims d{c.fft_size, c.hop_size, c.nb_erb, c.nb_df, c.df_order, c.df_lookahead, c.conv_lookahead, c.conv_ch, c.kt, c.kf, c.kt_inp,
+              c.kf_inp, c.convt_kf, c.df_pathway_kt, c.path_groups, c.df_path_groups, c.emb_hidden_dim, c.emb_num_layers, c.df_hidden_dim,
+              c.df_num_layers, c.norm_alpha, {}};
+    memcpy(d.erb_widths, c.erb_widths, sizeof(d.erb_widths));
+    EGR_TRY(check_common(d, "egr_dfn3"));
+    EGR_CHECK(c.lin_groups > 0 && c.enc_lin_groups > 0, EGR_ERR_UNSUPPORTED, "egr_dfn3: conv groups");
 
+    std::unique_ptr<Dfn3> m(new Dfn3());
+    m->cfg = c;
+    DfnCore& k = m->core;
+    init_core(k, d, device);
+    const int nb = c.nb_df, O2 = 2 * c.df_order, embd = k.embd;
+    // packed order: dfn_weights.pack_order
+    WeightCursor wc;
+    wc.encoder_convs(k);
+    const int64_t o_fc = wc.W((int64_t)(c.conv_ch * nb / 2) * embd / c.enc_lin_groups);
+    struct GruSpec { int64_t wih, whh, bih, bhh; int H; };
+    std::vector<GruSpec> gs;
+    auto sq = [&](int in, int H, int layers, int64_t* lin_in) {        // SqueezedGRU: linear_in, then `layers` GRU layers of width H
+        *lin_in = wc.W((int64_t)in * H / c.lin_groups);
+        for (int l = 0; l < layers; ++l) gs.push_back({wc.W((int64_t)3 * H * H), wc.W((int64_t)3 * H * H), wc.W(3 * H), wc.W(3 * H), H});
+    };
+    int64_t o_enc_in, o_enc_out, o_erb_in, o_erb_out, o_df_in, o_skip = -1, o_dfout;
+    sq(embd, c.emb_hidden_dim, 1, &o_enc_in);
+    o_enc_out = wc.W((int64_t)c.emb_hidden_dim * embd / c.lin_groups);
+    sq(embd, c.emb_hidden_dim, c.emb_num_layers - 1, &o_erb_in);
+    o_erb_out = wc.W((int64_t)c.emb_hidden_dim * embd / c.lin_groups);
+    wc.erb_decoder_convs(k);
+    sq(embd, c.df_hidden_dim, c.df_num_layers, &o_df_in);
+    if (c.df_gru_skip) o_skip = wc.W((int64_t)embd * c.df_hidden_dim / c.lin_groups);
+    o_dfout = wc.W((int64_t)c.df_hidden_dim * nb * O2 / c.lin_groups);
+    wc.df_pathway_convs(k);
+    EGR_CHECK(wc.pos == n_floats, EGR_ERR_ARG, "egr_dfn3_create: packed weights hold %lld floats, the config needs %lld",
+              (long long)n_floats, (long long)wc.pos);
+    const int64_t o_whh = align64(n_floats);
+    Image im = build_tables(d, packed, n_floats, o_whh + (int64_t)gs.size() * DENSE_WHH_FLOATS);
+    for (size_t g = 0; g < gs.size(); ++g) repack_dense_whh(packed + gs[g].whh, gs[g].H, im.host.data() + o_whh + g * DENSE_WHH_FLOATS);
+    EGR_TRY(upload(k, "egr_dfn3_create", im));
+    bind(k, wc, im);
+    float* D = k.dev_w;
+    m->fc_emb = D + o_fc;
+    m->enc_lin_in = D + o_enc_in; m->enc_lin_out = D + o_enc_out;
+    m->erb_lin_in = D + o_erb_in; m->erb_lin_out = D + o_erb_out;
+    m->df_lin_in = D + o_df_in; m->df_skip = o_skip >= 0 ? D + o_skip : nullptr; m->df_out = D + o_dfout;
+    for (size_t g = 0; g < gs.size(); ++g) {
+        Gru G;
+        G.in = G.H = gs[g].H;
+        G.wih = D + gs[g].wih; G.bih = D + gs[g].bih; G.bhh = D + gs[g].bhh; G.whh_pk = D + o_whh + g * DENSE_WHH_FLOATS;
+        m->grus.push_back(G);
+    }
+    *handle = m.release();
+    return EGR_OK;
+}
+
+extern "C" size_t egr_dfn3_workspace_bytes(void* handle, int channels, int64_t n) {
+    if (!handle || channels < 1 || n < 1) return 0;
+    const egr::Dfn3* m = (const egr::Dfn3*)handle;
+    return egr::workspace_need(*m, channels, (int)m->core.frames_of(n));
+}
+
+extern "C" int egr_dfn3_enhance(void* handle, const float* x48, int channels, int64_t n, float* y, void* stream) {
+    using namespace egr;
+    Dfn3* m = (Dfn3*)handle;
+    EGR_TRY(enhance_checks(m ? &m->core : nullptr, "egr_dfn3_enhance", x48, channels, n, y));
+    return run(*m, x48, channels, n, y, (hipStream_t)stream);
+}
+
+extern "C" int egr_dfn3_stage(void* handle, int stage, float* dst, int64_t capacity, int64_t* count, void* stream) {
+    using namespace egr;
+    EGR_CHECK(handle && count, EGR_ERR_ARG, "egr_dfn3_stage: null argument");
+    const Dfn3* m = (const Dfn3*)handle;
+    const DfnCore& k = m->core;
+    return stage_copy(k, "egr_dfn3_stage", stage, dst, capacity, count, stream, [&](int s, const float** src, int64_t* cnt) {
+        if (s == EGR_DFN3_STAGE_EMB) { *src = m->X.emb; *cnt = (int64_t)k.lastC * k.lastF * k.embd; }
+    });
+}
+
+extern "C" int egr_dfn3_time_gru(void* handle, int layer, int channels, int64_t steps, double* us_per_step) {
+    using namespace egr;
+    const Dfn3* m = (const Dfn3*)handle;
+    return time_gru_harness(m ? &m->core : nullptr, "egr_dfn3_time_gru", layer, channels, steps, false, us_per_step,
+                            [&](const float* proj, float* out, float*, int nF) {
+        const Gru& g = m->grus[layer];
+        hipLaunchKernelGGL(k_dfn_gru, dim3(channels), dim3(GRU_THREADS), 0, 0, proj, g.whh_pk, g.bhh, g.H, nF, out);
+    });
+}
+
+extern "C" int egr_dfn3_destroy(void* handle) {
+    if (!handle) return EGR_OK;
+    egr::Dfn3* m = (egr::Dfn3*)handle;
+    egr::destroy(m->core);
+    delete m;
+    return EGR_OK;
+}
+
+// ================================================================================================ DeepFilterNet2 entry points
 extern "C" int egr_dfn2_create(void** handle, const egr_dfn2_config* cfg, const float* packed, int64_t n_floats, int device) {
     using namespace egr;
     EGR_CHECK(handle && cfg && packed && n_floats > 0, EGR_ERR_ARG, "egr_dfn2_create: null argument");
     EGR_CHECK(cfg->struct_bytes == (int)sizeof(egr_dfn2_config), EGR_ERR_ARG, "egr_dfn2_create: struct_bytes %d != %d",
               cfg->struct_bytes, (int)sizeof(egr_dfn2_config));
     const egr_dfn2_config& c = *cfg;
-    const int ch = c.conv_ch, E = c.nb_erb, nb = c.nb_df, O2 = 2 * c.df_order, G = c.gru_groups, Gl = c.lin_groups;
-    const int ngru = 1 + (c.emb_num_layers - 1) + c.df_num_layers;
-    const int embd = ch * E / 4, He = c.emb_hidden_dim, Hd = c.df_hidden_dim;
-    EGR_CHECK(c.fft_size > 0 && c.hop_size > 0 && c.fft_size % c.hop_size == 0 && c.fft_size % 2 == 0 && c.fft_size <= 4096, EGR_ERR_UNSUPPORTED,
-              "egr_dfn2: fft_size %d / hop_size %d", c.fft_size, c.hop_size);
-    EGR_CHECK(E > 0 && E <= EGR_DFN3_MAX_ERB && E % 4 == 0 && nb > 0 && nb % 2 == 0 && nb <= c.fft_size / 2 + 1, EGR_ERR_UNSUPPORTED,
-              "egr_dfn2: nb_erb %d / nb_df %d", E, nb);
-    EGR_CHECK(He > 0 && He <= GRU_HMAX && Hd > 0 && Hd <= GRU_HMAX, EGR_ERR_UNSUPPORTED, "egr_dfn2: GRU widths must be <= %d", GRU_HMAX);
-    EGR_CHECK(c.emb_num_layers >= 2 && c.df_num_layers >= 1 && ngru <= EGR_DFN3_MAX_GRU, EGR_ERR_UNSUPPORTED, "egr_dfn2: GRU layer counts");
-    EGR_CHECK(c.df_order >= 1 && c.df_lookahead >= 0 && c.df_lookahead < c.df_order && c.conv_lookahead >= 0 &&
-              (c.conv_lookahead == 0 || c.conv_lookahead >= c.df_lookahead), EGR_ERR_UNSUPPORTED, "egr_dfn2: df_order / lookaheads");
-    EGR_CHECK(ch > 0 && c.path_groups > 0 && ch % c.path_groups == 0 && c.df_path_groups > 0 && ch % c.df_path_groups == 0 &&
-              O2 % c.df_path_groups == 0, EGR_ERR_UNSUPPORTED, "egr_dfn2: conv groups");
+    DfnDims d{c.fft_size, c.hop_size, c.nb_erb, c.nb_df, c.df_order, c.df_lookahead, c.conv_lookahead, c.conv_ch, c.kt, c.kf, c.kt_inp,
+              c.kf_inp, 3 /* SPEC DFN2-P9: the transposed convs are (1, 3) */, c.df_pathway_kt, c.path_groups, c.df_path_groups,
+              c.emb_hidden_dim, c.emb_num_layers, c.df_hidden_dim, c.df_num_layers, c.norm_alpha, {}};
+    memcpy(d.erb_widths, c.erb_widths, sizeof(d.erb_widths));
+    EGR_TRY(check_common(d, "egr_dfn2"));
+    const int ch = c.conv_ch, nb = c.nb_df, O2 = 2 * c.df_order, G = c.gru_groups, Gl = c.lin_groups;
+    const int embd = ch * c.nb_erb / 4, He = c.emb_hidden_dim, Hd = c.df_hidden_dim;
+    EGR_CHECK(c.conv_lookahead == 0 || c.conv_lookahead >= c.df_lookahead, EGR_ERR_UNSUPPORTED, "egr_dfn2: df_order / lookaheads");
     EGR_CHECK(G > 0 && embd % G == 0 && He % G == 0 && Hd % G == 0, EGR_ERR_UNSUPPORTED, "egr_dfn2: gru_groups %d", G);
     EGR_CHECK(Gl > 0 && (ch * nb / 2) % Gl == 0 && embd % Gl == 0 && He % Gl == 0 && (!c.df_gru_skip || Hd % Gl == 0) &&
               (c.df_output_layer == 1 || (Hd % Gl == 0 && (nb * O2) % Gl == 0)), EGR_ERR_UNSUPPORTED, "egr_dfn2: lin_groups %d", Gl);
     EGR_CHECK((c.df_gru_skip == 0 || c.df_gru_skip == 1) && (c.df_output_layer == 0 || c.df_output_layer == 1) &&
               (c.group_shuffle == 0 || c.group_shuffle == 1), EGR_ERR_UNSUPPORTED, "egr_dfn2: df_gru_skip / df_output_layer / group_shuffle");
-    EGR_CHECK(c.kf % 2 == 1 && c.kf_inp % 2 == 1 && c.kt >= 1 && c.kt_inp >= 1 && c.df_pathway_kt >= 1, EGR_ERR_UNSUPPORTED,
-              "egr_dfn2: frequency kernels must be odd (same-size padding)");
-    int wsum = 0;
-    for (int e = 0; e < E; ++e) { EGR_CHECK(c.erb_widths[e] > 0, EGR_ERR_ARG, "egr_dfn2: ERB width %d", e); wsum += c.erb_widths[e]; }
-    EGR_CHECK(wsum == c.fft_size / 2 + 1, EGR_ERR_ARG, "egr_dfn2: ERB widths sum %d != %d", wsum, c.fft_size / 2 + 1);
 
-    Dfn2* m = new Dfn2();
+    std::unique_ptr<Dfn2> m(new Dfn2());
     m->cfg = c;
-    m->device = device;
-    m->Fq = c.fft_size / 2 + 1;
-    m->embd = embd;
+    DfnCore& k = m->core;
+    init_core(k, d, device);
     // packed order: dfn2_weights.pack_order
-    int64_t pos = 0;
-    auto W = [&](int64_t k) { pos += k; return pos - k; };
-    struct ConvSpec { Conv* L; int64_t w, s, t; };
-    std::vector<ConvSpec> convs;
-    auto cv = [&](Conv& L, int cin, int cout, int groups, int kt, int kf, int transposed = 0) {
-        L.cin = cin; L.cout = cout; L.groups = groups; L.kt = kt; L.kf = kf; L.transposed = transposed;
-        ConvSpec s{&L, W((int64_t)(transposed ? cin * (cout / groups) : cout * (cin / groups)) * kt * kf), -1, -1};
-        convs.push_back(s);
-    };
-    auto bn = [&](int n) { ConvSpec& s = convs.back(); s.s = W(n); s.t = W(n); };
-    cv(m->erb0, 1, ch, 1, c.kt_inp, c.kf_inp); bn(ch);
-    for (int i = 0; i < 3; ++i) { cv(m->erb_dw[i], ch, ch, ch, c.kt, c.kf); cv(m->erb_pw[i], ch, ch, 1, 1, 1); bn(ch); }
-    cv(m->df0, 2, ch, 2, c.kt_inp, c.kf_inp); cv(m->df0_pw, ch, ch, 1, 1, 1); bn(ch);
-    cv(m->df1_dw, ch, ch, ch, c.kt, c.kf); cv(m->df1_pw, ch, ch, 1, 1, 1); bn(ch);
-    const int64_t o_fcw = W((int64_t)(ch * nb / 2) * embd / Gl), o_fcb = W(embd);
-    struct GruSpec { int64_t wih, whh, bih, bhh; int in, H; int shuffle; };
-    std::vector<GruSpec> gs;
-    auto ggru = [&](int in0, int H, int layers) {
+    WeightCursor wc;
+    wc.encoder_convs(k);
+    const int64_t o_fcw = wc.W((int64_t)(ch * nb / 2) * embd / Gl), o_fcb = wc.W(embd);
+    struct GruOff { int64_t wih, whh, bih, bhh, pk; };
+    std::vector<GruOff> go;                                             // of m->grus[l], until the image is on the device
+    auto ggru = [&](int in0, int H, int layers) {                       // GroupedGRU: `layers` layers of G GRUs of width H / G
         for (int l = 0; l < layers; ++l) {
-            GruSpec s;
-            s.in = l == 0 ? in0 : H; s.H = H;
-            s.shuffle = c.group_shuffle && G > 1 && l < layers - 1;
-            s.wih = W((int64_t)3 * H * s.in / G); s.whh = W((int64_t)3 * H * H / G); s.bih = W(3 * H); s.bhh = W(3 * H);
-            gs.push_back(s);
+            GGru L;
+            L.in = l == 0 ? in0 : H; L.H = H; L.G = G; L.h = H / G;
+            L.shuffle = c.group_shuffle && G > 1 && l < layers - 1;
+            if (!L.dense()) ggru_shape(L.h, &L.K, &L.S);
+            m->grus.push_back(L);
+            go.push_back({wc.W((int64_t)3 * H * L.in / G), wc.W((int64_t)3 * H * H / G), wc.W(3 * H), wc.W(3 * H), 0});
         }
     };
     ggru(embd, He, 1);
     ggru(He, He, c.emb_num_layers - 1);
-    const int64_t o_erbw = W((int64_t)He * embd / Gl), o_erbb = W(embd);
-    for (int i = 0; i < 3; ++i) {
-        cv(m->path[3 - i], ch, ch, c.path_groups, 1, 1); bn(ch);
-        if (i == 0) cv(m->ct_dw[0], ch, ch, ch, c.kt, c.kf);
-        else cv(m->ct_dw[i], ch, ch, ch, 1, 3, 1);                  // SPEC DFN2-P9: the transposed convs are (1, 3)
-        cv(m->ct_pw[i], ch, ch, 1, 1, 1); bn(ch);
-    }
-    cv(m->path[0], ch, ch, c.path_groups, 1, 1); bn(ch);
-    cv(m->out0, ch, 1, 1, c.kt, c.kf); bn(1);
+    const int64_t o_erbw = wc.W((int64_t)He * embd / Gl), o_erbb = wc.W(embd);
+    wc.erb_decoder_convs(k);
     ggru(He, Hd, c.df_num_layers);
-    const int64_t o_skip = c.df_gru_skip ? W((int64_t)He * Hd / Gl) : -1;
-    const int64_t o_out = W(c.df_output_layer == 1 ? (int64_t)nb * O2 * Hd : (int64_t)Hd * nb * O2 / Gl);
-    const int64_t o_outb = c.df_output_layer == 1 ? W(nb * O2) : -1;
-    const int64_t o_aw = W(Hd), o_ab = W(1);
-    cv(m->convp, ch, O2, c.df_path_groups, c.df_pathway_kt, 1);
-    cv(m->convp_pw, O2, O2, 1, 1, 1); bn(O2);
-    if (pos != n_floats) {
-        set_error("egr_dfn2_create: packed weights hold %lld floats, the config needs %lld", (long long)n_floats, (long long)pos);
-        delete m;
-        return EGR_ERR_ARG;
+    const int64_t o_skip = c.df_gru_skip ? wc.W((int64_t)He * Hd / Gl) : -1;
+    const int64_t o_out = wc.W(c.df_output_layer == 1 ? (int64_t)nb * O2 * Hd : (int64_t)Hd * nb * O2 / Gl);
+    const int64_t o_outb = c.df_output_layer == 1 ? wc.W(nb * O2) : -1;
+    const int64_t o_aw = wc.W(Hd), o_ab = wc.W(1);
+    wc.df_pathway_convs(k);
+    EGR_CHECK(wc.pos == n_floats, EGR_ERR_ARG, "egr_dfn2_create: packed weights hold %lld floats, the config needs %lld",
+              (long long)n_floats, (long long)wc.pos);
+    int64_t o_cur = align64(n_floats);
+    for (size_t l = 0; l < go.size(); ++l) {
+        const GGru& L = m->grus[l];
+        go[l].pk = o_cur;
+        o_cur = align64(o_cur + (L.dense() ? DENSE_WHH_FLOATS : (int64_t)G * 3 * L.K * L.h * L.S));
     }
-    // device image: packed weights | repacked W_hh per layer | twiddles (double2) | window | band tables
-    std::vector<int64_t> o_pk(gs.size());
-    int64_t o_cur = (n_floats + 63) & ~63LL;
-    for (size_t l = 0; l < gs.size(); ++l) {
-        o_pk[l] = o_cur;
-        const int h = gs[l].H / G;
-        int K = 0, S = 1;
-        if (h <= G2_HMAX) ggru_shape(h, &K, &S);
-        o_cur += h > G2_HMAX ? (int64_t)GRU_PER_THREAD * GRU_THREADS : (int64_t)G * 3 * K * h * S;
-        o_cur = (o_cur + 63) & ~63LL;
-    }
-    const int N = c.fft_size;
-    const int64_t o_tw = o_cur;
-    const int64_t o_win = o_tw + 4LL * N;
-    const int64_t o_tab = o_win + N;
-    const int64_t total = o_tab + 2 * E + m->Fq;
-    std::vector<float> img((size_t)total, 0.f);
-    memcpy(img.data(), packed, sizeof(float) * n_floats);
-    for (size_t l = 0; l < gs.size(); ++l) {
-        const int H = gs[l].H, h = H / G;
-        const float* w = packed + gs[l].whh;                    // [G][3h][h]
-        float* dst = img.data() + o_pk[l];
-        if (h > G2_HMAX) {                                      // G = 1: k_dfn_gru's thread-minor (element, thread) order
-            for (int t = 0; t < GRU_THREADS; ++t)
-                for (int e = 0; e < GRU_PER_THREAD; ++e) {
-                    const int j = e / GRU_K, k = e % GRU_K;
-                    const int q = j * GRU_THREADS + t, row = q / GRU_SEG, col = GRU_SEG * k + q % GRU_SEG;
-                    dst[(int64_t)e * GRU_THREADS + t] = (row < 3 * H && col < H) ? w[(int64_t)row * H + col] : 0.f;
-                }
+    Image im = build_tables(d, packed, n_floats, o_cur);
+    for (size_t l = 0; l < go.size(); ++l) {
+        const GGru& L = m->grus[l];
+        const float* w = packed + go[l].whh;                    // [G][3h][h]
+        float* dst = im.host.data() + go[l].pk;
+        if (L.dense()) {                                        // G = 1: k_dfn_gru's order
+            repack_dense_whh(w, L.H, dst);
             continue;
         }
-        int K, S;
-        ggru_shape(h, &K, &S);
-        const int NT = h * S;
+        const int h = L.h, K = L.K, S = L.S, NT = h * S;        // k_dfn2_gru's thread-minor order, group after group
         for (int g = 0; g < G; ++g)
             for (int t = 0; t < NT; ++t)
                 for (int e = 0; e < 3 * K; ++e) {
@@ -1345,191 +1376,68 @@ extern "C" int egr_dfn2_create(void** handle, const egr_dfn2_config* cfg, const 
                     dst[((int64_t)g * 3 * K + e) * NT + t] = col < h ? w[((int64_t)g * 3 * h + q * h + j) * h + col] : 0.f;
                 }
     }
-    double* twd = (double*)(img.data() + o_tw);
-    for (int n = 0; n < N; ++n) {
-        twd[2 * n] = cos(2.0 * M_PI * n / N);
-        twd[2 * n + 1] = sin(2.0 * M_PI * n / N);
-    }
-    const int hN = N / 2;
-    for (int n = 0; n < N; ++n) {
-        const double s = sin(0.5 * M_PI * (n + 0.5) / hN);
-        img[o_win + n] = (float)sin(0.5 * M_PI * s * s);
-    }
-    int* tab = (int*)(img.data() + o_tab);
-    int lo = 0;
-    for (int e = 0; e < E; ++e) {
-        tab[e] = lo;
-        tab[E + e] = c.erb_widths[e];
-        for (int j = 0; j < c.erb_widths[e]; ++j) tab[2 * E + lo + j] = e;
-        lo += c.erb_widths[e];
-    }
-    m->wnorm = 1.f / ((float)N * (float)N / (float)(2 * c.hop_size));
-    int prev = 0;
-    if (hipGetDevice(&prev) != hipSuccess || hipSetDevice(device) != hipSuccess ||
-        hipMalloc(&m->dev_w, sizeof(float) * total) != hipSuccess ||
-        hipMemcpy(m->dev_w, img.data(), sizeof(float) * total, hipMemcpyHostToDevice) != hipSuccess) {
-        set_error("egr_dfn2_create: device allocation / upload failed on device %d", device);
-        if (m->dev_w) (void)hipFree(m->dev_w);
-        (void)hipSetDevice(prev);
-        delete m;
-        return EGR_ERR_HIP;
-    }
-    // the analysis / synthesis kernels are DeepFilterNet3's: the same process-wide dynamic-LDS cap (egr_dfn3_create)
-    const size_t lds_an = (size_t)N * 24, lds_syn = (size_t)(m->Fq + N) * 16;
-    hipError_t ea = hipSuccess;
-    if (lds_an > (size_t)DFN_LDS_MAX || lds_syn > (size_t)DFN_LDS_MAX) {
-        set_error("egr_dfn2_create: fft_size %d needs %zu / %zu bytes of LDS (limit %d)", N, lds_an, lds_syn, DFN_LDS_MAX);
-        ea = hipErrorInvalidValue;
-    }
-    if (ea == hipSuccess) ea = hipFuncSetAttribute((const void*)k_dfn_analysis, hipFuncAttributeMaxDynamicSharedMemorySize, DFN_LDS_MAX);
-    if (ea == hipSuccess) ea = hipFuncSetAttribute((const void*)k_dfn_synth, hipFuncAttributeMaxDynamicSharedMemorySize, DFN_LDS_MAX);
-    if (ea != hipSuccess) {
-        if (lds_an <= (size_t)DFN_LDS_MAX && lds_syn <= (size_t)DFN_LDS_MAX)
-            set_error("egr_dfn2_create: hipFuncSetAttribute(MaxDynamicSharedMemorySize) -> %s", hipGetErrorString(ea));
-        (void)hipFree(m->dev_w);
-        (void)hipSetDevice(prev);
-        delete m;
-        return EGR_ERR_HIP;
-    }
-    (void)hipSetDevice(prev);
-    float* D = m->dev_w;
-    for (auto& s : convs) {
-        s.L->w = D + s.w;
-        if (s.s >= 0) { s.L->scale = D + s.s; s.L->shift = D + s.t; }
-    }
+    EGR_TRY(upload(k, "egr_dfn2_create", im));
+    bind(k, wc, im);
+    float* D = k.dev_w;
     m->fc_emb_w = D + o_fcw; m->fc_emb_b = D + o_fcb;
     m->erb_fc_w = D + o_erbw; m->erb_fc_b = D + o_erbb;
     m->df_skip = o_skip >= 0 ? D + o_skip : nullptr;
     m->df_out = D + o_out; m->df_out_b = o_outb >= 0 ? D + o_outb : nullptr;
     m->fc_a_w = D + o_aw; m->fc_a_b = D + o_ab;
-    for (size_t l = 0; l < gs.size(); ++l) {
-        GGru L;
-        L.in = gs[l].in; L.H = gs[l].H; L.G = G; L.h = L.H / G; L.shuffle = gs[l].shuffle;
-        if (!L.dense()) ggru_shape(L.h, &L.K, &L.S);
-        L.wih = D + gs[l].wih; L.bih = D + gs[l].bih; L.bhh = D + gs[l].bhh; L.whh_pk = D + o_pk[l];
-        m->grus.push_back(L);
+    for (size_t l = 0; l < go.size(); ++l) {
+        GGru& L = m->grus[l];
+        L.wih = D + go[l].wih; L.bih = D + go[l].bih; L.bhh = D + go[l].bhh; L.whh_pk = D + go[l].pk;
     }
-    m->tw = (const double2*)(D + o_tw);
-    m->win = D + o_win;
-    m->band_lo = (const int*)(D + o_tab);
-    m->band_w = (const int*)(D + o_tab) + E;
-    m->band_of = (const int*)(D + o_tab) + 2 * E;
-    *handle = m;
+    *handle = m.release();
     return EGR_OK;
 }
 
 extern "C" size_t egr_dfn2_workspace_bytes(void* handle, int channels, int64_t n) {
     if (!handle || channels < 1 || n < 1) return 0;
-    Dfn2* m = (Dfn2*)handle;
-    return egr::layout2(*m, channels, (int)((n + m->cfg.fft_size) / m->cfg.hop_size), nullptr, nullptr);
+    const egr::Dfn2* m = (const egr::Dfn2*)handle;
+    return egr::workspace_need(*m, channels, (int)m->core.frames_of(n));
 }
 
 extern "C" int egr_dfn2_enhance(void* handle, const float* x48, int channels, int64_t n, float* y, void* stream) {
     using namespace egr;
-    EGR_CHECK(handle && x48 && y && channels >= 1 && channels <= 65535 && n >= 1, EGR_ERR_ARG, "egr_dfn2_enhance: bad argument");
     Dfn2* m = (Dfn2*)handle;
-    EGR_CHECK((n + m->cfg.fft_size) / m->cfg.hop_size <= 65535LL * 4096, EGR_ERR_UNSUPPORTED, "egr_dfn2_enhance: input too long");
-    EGR_CHECK((n + m->cfg.fft_size) / m->cfg.hop_size <= 2147483647LL / 4096, EGR_ERR_UNSUPPORTED, "egr_dfn2_enhance: input too long");
-    int cur = -1;
-    EGR_HIP(hipGetDevice(&cur));
-    EGR_CHECK(cur == m->device, EGR_ERR_ARG, "egr_dfn2_enhance: handle belongs to device %d, current device is %d", m->device, cur);
-    return run2(*m, x48, channels, n, y, (hipStream_t)stream);
+    EGR_TRY(enhance_checks(m ? &m->core : nullptr, "egr_dfn2_enhance", x48, channels, n, y));
+    return run(*m, x48, channels, n, y, (hipStream_t)stream);
 }
 
 extern "C" int egr_dfn2_stage(void* handle, int stage, float* dst, int64_t capacity, int64_t* count, void* stream) {
     using namespace egr;
     EGR_CHECK(handle && count, EGR_ERR_ARG, "egr_dfn2_stage: null argument");
-    Dfn2* m = (Dfn2*)handle;
-    EGR_CHECK(m->ws, EGR_ERR_ARG, "egr_dfn2_stage: no enhance call yet");
-    const int64_t R = (int64_t)m->lastC * m->lastF;
-    const egr_dfn2_config& c = m->cfg;
-    const Dfn2::Bufs& B = m->B;
-    const float* src = nullptr;
-    int64_t n = 0;
-    const int ng = (int)m->grus.size();
-    switch (stage) {
-        case EGR_DFN3_STAGE_SPEC: src = (const float*)B.spec; n = R * m->Fq * 2; break;
-        case EGR_DFN3_STAGE_FEAT_ERB: src = B.ferb; n = R * c.nb_erb; break;
-        case EGR_DFN3_STAGE_FEAT_SPEC: src = (const float*)B.fspec; n = R * c.nb_df * 2; break;
-        case EGR_DFN3_STAGE_E0: src = B.e[0]; n = R * c.nb_erb * c.conv_ch; break;
-        case EGR_DFN3_STAGE_E1: src = B.e[1]; n = R * (c.nb_erb / 2) * c.conv_ch; break;
-        case EGR_DFN3_STAGE_E2: src = B.e[2]; n = R * (c.nb_erb / 4) * c.conv_ch; break;
-        case EGR_DFN3_STAGE_E3: src = B.e[3]; n = R * (c.nb_erb / 4) * c.conv_ch; break;
-        case EGR_DFN3_STAGE_C0: src = B.c0; n = R * c.nb_df * c.conv_ch; break;
-        case EGR_DFN3_STAGE_EMB: src = B.gsum[0]; n = R * c.emb_hidden_dim; break;
-        case EGR_DFN3_STAGE_MASK: src = B.mask; n = R * c.nb_erb; break;
-        case EGR_DFN3_STAGE_COEFS: src = B.coefs; n = R * c.nb_df * 2 * c.df_order; break;
-        case EGR_DFN3_STAGE_SPEC_E: src = (const float*)B.spec_e; n = R * m->Fq * 2; break;
-        case EGR_DFN2_STAGE_ALPHA: src = B.alpha; n = R; break;
-        default:
-            if (stage >= EGR_DFN2_STAGE_GRU0 && stage < EGR_DFN2_STAGE_GRU0 + ng) {
-                const int g = stage - EGR_DFN2_STAGE_GRU0;
-                src = B.gout[g];
-                n = R * m->grus[g].H;
-            } else if (stage >= EGR_DFN2_STAGE_SUM0 && stage < EGR_DFN2_STAGE_SUM0 + ng) {
-                const int g = stage - EGR_DFN2_STAGE_SUM0;
-                src = B.gsum[g];
-                n = R * m->grus[g].H;
-            }
-    }
-    EGR_CHECK(src, EGR_ERR_ARG, "egr_dfn2_stage: unknown stage %d", stage);
-    *count = n;
-    if (!dst) return EGR_OK;
-    EGR_CHECK(capacity >= n, EGR_ERR_ARG, "egr_dfn2_stage: capacity %lld < %lld", (long long)capacity, (long long)n);
-    EGR_HIP(hipMemcpyAsync(dst, src, sizeof(float) * n, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    return EGR_OK;
+    const Dfn2* m = (const Dfn2*)handle;
+    const DfnCore& k = m->core;
+    return stage_copy(k, "egr_dfn2_stage", stage, dst, capacity, count, stream, [&](int s, const float** src, int64_t* cnt) {
+        const int64_t R = (int64_t)k.lastC * k.lastF;
+        if (s == EGR_DFN3_STAGE_EMB) { *src = m->X.gsum[0]; *cnt = R * k.gru_width(0); }
+        else if (s == EGR_DFN2_STAGE_ALPHA) { *src = m->X.alpha; *cnt = R; }
+        else if (s >= EGR_DFN2_STAGE_SUM0 && s < EGR_DFN2_STAGE_SUM0 + k.ngru()) {
+            *src = m->X.gsum[s - EGR_DFN2_STAGE_SUM0];
+            *cnt = R * k.gru_width(s - EGR_DFN2_STAGE_SUM0);
+        }
+    });
 }
 
 extern "C" int egr_dfn2_time_gru(void* handle, int layer, int channels, int64_t steps, double* us_per_step) {
     using namespace egr;
-    EGR_CHECK(handle && us_per_step && channels >= 1 && channels <= 64 && steps >= 1 && steps <= 10000000, EGR_ERR_ARG,
-              "egr_dfn2_time_gru: bad argument");
-    Dfn2* m = (Dfn2*)handle;
-    EGR_CHECK(layer >= 0 && layer < (int)m->grus.size(), EGR_ERR_ARG, "egr_dfn2_time_gru: layer %d", layer);
-    const GGru& g = m->grus[layer];
-    float *proj = nullptr, *out = nullptr, *sum = nullptr;
-    hipEvent_t e0, e1;
-    EGR_HIP(hipMalloc(&proj, sizeof(float) * channels * steps * 3 * g.H));
-    EGR_HIP(hipMalloc(&out, sizeof(float) * channels * steps * g.H));
-    EGR_HIP(hipMalloc(&sum, sizeof(float) * channels * steps * g.H));
-    EGR_HIP(hipMemset(proj, 0, sizeof(float) * channels * steps * 3 * g.H));
-    EGR_HIP(hipEventCreate(&e0));
-    EGR_HIP(hipEventCreate(&e1));
-    const int warm = (int)(steps < 64 ? steps : 64);
-    for (int rep = 0; rep < 2; ++rep) {                    // a short warm-up launch, then the timed one
-        const int nF = rep == 0 ? warm : (int)steps;
-        if (rep == 1) EGR_HIP(hipEventRecord(e0, 0));
+    const Dfn2* m = (const Dfn2*)handle;
+    return time_gru_harness(m ? &m->core : nullptr, "egr_dfn2_time_gru", layer, channels, steps, true, us_per_step,
+                            [&](const float* proj, float* out, float* sum, int nF) {
+        const GGru& g = m->grus[layer];
         if (g.dense())
             hipLaunchKernelGGL(k_dfn_gru, dim3(channels), dim3(GRU_THREADS), 0, 0, proj, g.whh_pk, g.bhh, g.H, nF, out);
         else
             launch_ggru(g, proj, nullptr, out, sum, channels, nF, 0);
-    }
-    EGR_HIP(hipEventRecord(e1, 0));
-    EGR_HIP(hipEventSynchronize(e1));
-    float ms = 0.f;
-    EGR_HIP(hipEventElapsedTime(&ms, e0, e1));
-    *us_per_step = 1e3 * ms / (double)steps;
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    (void)hipFree(proj);
-    (void)hipFree(out);
-    (void)hipFree(sum);
-    EGR_HIP(hipGetLastError());
-    return EGR_OK;
+    });
 }
 
 extern "C" int egr_dfn2_destroy(void* handle) {
     if (!handle) return EGR_OK;
-    Dfn2* m = (Dfn2*)handle;
-    int prev = 0;
-    (void)hipGetDevice(&prev);
-    (void)hipSetDevice(m->device);
-    if (m->ws) {
-        (void)hipFreeAsync(m->ws, nullptr);
-        (void)hipDeviceSynchronize();
-    }
-    if (m->dev_w) (void)hipFree(m->dev_w);
-    (void)hipSetDevice(prev);
+    egr::Dfn2* m = (egr::Dfn2*)handle;
+    egr::destroy(m->core);
     delete m;
     return EGR_OK;
 }

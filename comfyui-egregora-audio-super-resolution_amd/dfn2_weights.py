@@ -1,6 +1,6 @@
 """DeepFilterNet2 model directory discovery, config.ini, checkpoint validation and packing for the native denoiser (SPEC.md
-"4c. DeepFilterNet2 (UPSTREAM-RECALL)").  Function for function the DeepFilterNet3 module dfn_weights.py, whose helpers (ERB bank,
-norm alpha, BatchNorm folding, checkpoint reading, search path) are used as they are.
+"4c. DeepFilterNet2 (UPSTREAM-RECALL)").  Everything the two models share (config parsing, the key-table and checkpoint checks, the
+ERB bank, norm alpha, BatchNorm folding, packing, the search path) is dfn_weights.py's; this module holds what is DeepFilterNet2's.
 
 A directory serves DeepFilterNet2 only when its config.ini names the model (`[train] model = deepfilternet2`, SPEC DFN2-P8), so a
 DeepFilterNet3 directory -- EGREGORA_DFN_MODEL_DIR included -- is skipped by this search and never loaded as DeepFilterNet2.
@@ -9,9 +9,9 @@ checked against it, and every tensor name and shape against the committed key ta
 missing or mismatched raises with the full list.
 """
 import configparser
-import json
 import math
 import re
+import sys
 from pathlib import Path
 from typing import Dict, List, Optional, Tuple
 
@@ -19,7 +19,7 @@ import numpy as np
 import torch
 
 from . import dfn_weights
-from .dfn_weights import checkpoint_file, erb_matrices, erb_widths, fold_bn, norm_alpha, read_state_dict
+from .dfn_weights import checkpoint_file, erb_matrices, erb_widths, fold_bn, norm_alpha, read_state_dict  # noqa: F401 (kept importable here)
 
 MODEL = "DeepFilterNet2"
 MODEL_ID = "deepfilternet2"                 # [train] model
@@ -73,34 +73,7 @@ def discover(model: str = MODEL) -> Optional[Path]:
 # ------------------------------------------------------------------------------------------------ config
 def parse_config(path: Path) -> dict:
     """config.ini -> {key: value} for every entry of PARAMS; raises listing every absent or unreadable key."""
-    cp = configparser.ConfigParser()
-    cp.read(str(path), encoding="utf-8")
-    cfg, bad = {}, []
-    for sec, key, typ in PARAMS:
-        if not cp.has_option(sec, key):
-            bad.append(f"[{sec}] {key}: missing")
-            continue
-        raw = cp.get(sec, key).strip()
-        try:
-            if typ == _BOOL:
-                v = raw.lower() in ("1", "true", "yes", "on")
-                if raw.lower() not in ("1", "0", "true", "false", "yes", "no", "on", "off"):
-                    raise ValueError(raw)
-            elif typ == _PAIR:
-                v = tuple(int(s) for s in raw.split(","))
-                if len(v) != 2:
-                    raise ValueError(raw)
-            elif typ == _STR:
-                v = raw.lower()
-            else:
-                v = typ(raw)
-        except ValueError:
-            bad.append(f"[{sec}] {key}: cannot read {raw!r}")
-            continue
-        cfg[key] = v
-    if bad:
-        raise RuntimeError(f"DeepFilterNet2 config {path} is incomplete:\n  " + "\n  ".join(bad))
-    return cfg
+    return dfn_weights.parse_config(path, PARAMS, MODEL)
 
 
 def check_supported(cfg: dict):
@@ -122,29 +95,8 @@ def check_supported(cfg: dict):
         bad.append(f"norm_tau = {cfg['norm_tau']} (> 0)")
     if cfg["sr"] != 48000:
         bad.append(f"sr = {cfg['sr']} (the node always hands the model a 48 kHz signal)")
-    for k in ("conv_kernel", "conv_kernel_inp"):
-        kt, kf = cfg[k]
-        if kt < 1 or kf < 1 or kf % 2 == 0:
-            bad.append(f"{k} = {cfg[k]} (time extent >= 1, odd frequency extent)")
-    if cfg["df_pathway_kernel_size_t"] < 1:
-        bad.append(f"df_pathway_kernel_size_t = {cfg['df_pathway_kernel_size_t']} (>= 1)")
-    if cfg["hop_size"] < 1 or cfg["fft_size"] < 2 or cfg["fft_size"] % cfg["hop_size"] or cfg["fft_size"] % 2 or cfg["fft_size"] > 4096:
-        bad.append(f"fft_size {cfg['fft_size']} must be even, <= 4096 and a multiple of hop_size {cfg['hop_size']}")
-    if cfg["nb_erb"] < 4 or cfg["nb_erb"] % 4 or cfg["nb_erb"] > MAX_NB_ERB or cfg["nb_df"] < 2 or cfg["nb_df"] % 2:
-        bad.append(f"nb_erb = {cfg['nb_erb']} (multiple of 4, <= {MAX_NB_ERB}), nb_df = {cfg['nb_df']} (even)")
-    if cfg["nb_df"] > cfg["fft_size"] // 2 + 1:
-        bad.append(f"nb_df = {cfg['nb_df']} / fft_size = {cfg['fft_size']} out of range")
-    for k in ("emb_hidden_dim", "df_hidden_dim"):
-        if not 1 <= cfg[k] <= 256:
-            bad.append(f"{k} = {cfg[k]} (the recurrence kernels hold 1 <= H <= 256)")
-    n_gru = cfg["emb_num_layers"] + cfg["df_num_layers"]
-    if cfg["emb_num_layers"] < 2 or cfg["df_num_layers"] < 1 or n_gru > MAX_GRU_LAYERS:
-        bad.append(f"emb_num_layers = {cfg['emb_num_layers']} (>= 2: one encoder layer, at least one ERB-decoder layer), "
-                   f"df_num_layers = {cfg['df_num_layers']} (>= 1), {n_gru} GRU layers in total (<= {MAX_GRU_LAYERS})")
-    if cfg["df_order"] < 1 or cfg["conv_lookahead"] < 0 or cfg["df_lookahead"] < 0 or cfg["df_lookahead"] > cfg["df_order"] - 1:
-        bad.append(f"df_order = {cfg['df_order']}, conv_lookahead = {cfg['conv_lookahead']}, df_lookahead = {cfg['df_lookahead']} "
-                   "out of range")
-    elif 0 < cfg["conv_lookahead"] < cfg["df_lookahead"]:
+    dfn_weights.check_common(cfg, bad, "the recurrence kernels hold")
+    if 0 < cfg["conv_lookahead"] < cfg["df_lookahead"] <= cfg["df_order"] - 1:
         bad.append(f"conv_lookahead = {cfg['conv_lookahead']} (0 or >= df_lookahead = {cfg['df_lookahead']})")
     if cfg["conv_ch"] < 1 or cfg["lin_groups"] < 1 or cfg["gru_groups"] < 1:
         bad.append(f"conv_ch = {cfg['conv_ch']}, lin_groups = {cfg['lin_groups']}, gru_groups = {cfg['gru_groups']} (>= 1)")
@@ -180,20 +132,7 @@ def derived_vars(cfg: dict) -> dict:
 # ------------------------------------------------------------------------------------------------ key table
 def expected_table(cfg: dict, keymap_path: Optional[Path] = None) -> Dict[str, Tuple[int, ...]]:
     """{tensor name: shape} the key table prescribes for this config."""
-    spec = json.loads(Path(keymap_path or KEYMAP_PATH).read_text(encoding="utf-8"))
-    env = derived_vars(cfg)
-    ev = lambda s: int(eval(str(s), {"__builtins__": {}}, env))      # noqa: S307 (repo-owned JSON, integer expressions)
-    out = {}
-    for e in spec["entries"]:
-        if "when" in e and not eval(e["when"], {"__builtins__": {}}, env):  # noqa: S307
-            continue
-        shape = tuple(ev(s) for s in e["shape"])
-        ls = range(ev(e["l"][0]), ev(e["l"][1])) if "l" in e else [None]
-        gs = range(env[e["g"]]) if "g" in e else [None]
-        for l in ls:
-            for g in gs:
-                out[e["name"].replace("{l}", str(l)).replace("{g}", str(g))] = shape
-    return out
+    return dfn_weights.expected_table(cfg, keymap_path or KEYMAP_PATH, derived_vars(cfg))
 
 
 def _count(sd, pattern: str) -> int:
@@ -203,18 +142,9 @@ def _count(sd, pattern: str) -> int:
 
 def layer_table(sd: Dict[str, torch.Tensor]) -> dict:
     """Layer counts, widths and group counts read from the tensor shapes alone (no config)."""
-    t = {}
+    t = dfn_weights.layer_table_common(sd)
     def get(name):
         return sd[name].shape if name in sd else None
-    s = get("enc.erb_conv0.1.weight")
-    if s is not None:
-        t["conv_ch"], t["conv_kernel_inp"] = int(s[0]), (int(s[2]), int(s[3]))
-    s = get("enc.erb_conv1.0.weight")
-    if s is not None:
-        t["conv_kernel"] = (int(s[2]), int(s[3]))
-    s = get("erb_fb")
-    if s is not None:
-        t["fft_size"], t["nb_erb"] = 2 * (int(s[0]) - 1), int(s[1])
     G = _count(sd, r"enc\.emb_gru\.grus\.0\.layers\.(\d+)\.weight_hh_l0")
     if G:
         t["gru_groups"] = G
@@ -229,10 +159,6 @@ def layer_table(sd: Dict[str, torch.Tensor]) -> dict:
         t["lin_groups"] = Gl
         if "conv_ch" in t:
             t["nb_df"] = 2 * Gl * int(sd["enc.df_fc_emb.layers.0.weight"].shape[1]) // t["conv_ch"]
-    s = get("df_dec.df_convp.1.weight")
-    if s is not None:
-        t["df_order"], t["df_pathway_kernel_size_t"] = int(s[0]) // 2, int(s[2])
-    t["df_gru_skip"] = "groupedlinear" if "df_dec.df_skip.weight" in sd else "none"
     s = get("df_dec.df_out.0.weight")
     if s is not None:
         t["df_output_layer"] = "linear" if "df_dec.df_out.0.bias" in sd else "groupedlinear"
@@ -241,23 +167,7 @@ def layer_table(sd: Dict[str, torch.Tensor]) -> dict:
 
 def validate(sd: Dict[str, torch.Tensor], cfg: dict, keymap_path: Optional[Path] = None):
     """Raise with every unmapped / missing / mismatched tensor and every config field the shapes contradict."""
-    want = expected_table(cfg, keymap_path)
-    unmapped = sorted(k for k in sd if k not in want)
-    missing = sorted(k for k in want if k not in sd)
-    wrong = sorted(f"{k}: checkpoint {tuple(sd[k].shape)} != table {want[k]}" for k in want if k in sd and tuple(sd[k].shape) != want[k])
-    lt = layer_table(sd)
-    conflict = sorted(f"{k}: shapes say {v!r}, config.ini says {cfg[k]!r}" for k, v in lt.items() if k in cfg and cfg[k] != v)
-    if unmapped or missing or wrong or conflict:
-        parts = []
-        for title, lst in (("unmapped tensors", unmapped), ("missing tensors", missing), ("shape mismatches", wrong),
-                           ("config / checkpoint disagreements", conflict)):
-            if lst:
-                parts.append(f"{title} ({len(lst)}):\n    " + "\n    ".join(lst))
-        raise RuntimeError("DeepFilterNet2 checkpoint does not match dfn2_keymap.json / config.ini:\n  " + "\n  ".join(parts))
-    widths = erb_widths(cfg["sr"], cfg["fft_size"], cfg["nb_erb"], cfg["min_nb_erb_freqs"])
-    fb, ifb = erb_matrices(widths)
-    if not (torch.allclose(sd["erb_fb"].float(), fb, atol=1e-6) and torch.allclose(sd["mask.erb_inv_fb"].float(), ifb, atol=1e-6)):
-        raise RuntimeError(f"DeepFilterNet2 checkpoint: erb_fb / mask.erb_inv_fb differ from the ERB bank of config.ini (widths {widths})")
+    dfn_weights.validate_against(sd, cfg, expected_table(cfg, keymap_path), layer_table(sd), MODEL, KEYMAP_PATH.name)
 
 
 # ------------------------------------------------------------------------------------------------ packing
@@ -266,11 +176,6 @@ def pack_order(cfg: dict) -> List[Tuple[str, str]]:
     stored (torch layout, fp32); "bn": a BatchNorm folded to eval-mode per-channel scale then shift.  A grouped module's tensors
     come group after group for each parameter, so each parameter is one [G][...] block."""
     G, Gl = cfg["gru_groups"], cfg["lin_groups"]
-    o = [("enc.erb_conv0.1.weight", "w"), ("enc.erb_conv0.2", "bn")]
-    for i in (1, 2, 3):
-        o += [(f"enc.erb_conv{i}.0.weight", "w"), (f"enc.erb_conv{i}.1.weight", "w"), (f"enc.erb_conv{i}.2", "bn")]
-    o += [("enc.df_conv0.1.weight", "w"), ("enc.df_conv0.2.weight", "w"), ("enc.df_conv0.3", "bn"),
-          ("enc.df_conv1.0.weight", "w"), ("enc.df_conv1.1.weight", "w"), ("enc.df_conv1.2", "bn")]
 
     def glin(prefix):
         return [(f"{prefix}.layers.{g}.{p}", "w") for p in ("weight", "bias") for g in range(Gl)]
@@ -278,56 +183,27 @@ def pack_order(cfg: dict) -> List[Tuple[str, str]]:
     def ggru(prefix, n):
         return [(f"{prefix}.grus.{l}.layers.{g}.{p}", "w") for l in range(n)
                 for p in ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0") for g in range(G)]
-    o += glin("enc.df_fc_emb") + ggru("enc.emb_gru", 1)
+    o = dfn_weights.encoder_order() + glin("enc.df_fc_emb") + ggru("enc.emb_gru", 1)
     o += ggru("erb_dec.emb_gru", cfg["emb_num_layers"] - 1) + glin("erb_dec.fc_emb.0")
-    for i in (3, 2, 1):
-        o += [(f"erb_dec.conv{i}p.0.weight", "w"), (f"erb_dec.conv{i}p.1", "bn"), (f"erb_dec.convt{i}.0.weight", "w"),
-              (f"erb_dec.convt{i}.1.weight", "w"), (f"erb_dec.convt{i}.2", "bn")]
-    o += [("erb_dec.conv0p.0.weight", "w"), ("erb_dec.conv0p.1", "bn"), ("erb_dec.conv0_out.0.weight", "w"), ("erb_dec.conv0_out.1", "bn")]
-    o += ggru("df_dec.df_gru", cfg["df_num_layers"])
+    o += dfn_weights.erb_decoder_order() + ggru("df_dec.df_gru", cfg["df_num_layers"])
     if cfg["df_gru_skip"] == "groupedlinear":
         o += [("df_dec.df_skip.weight", "w")]
     o += [("df_dec.df_out.0.weight", "w")]
     if cfg["df_output_layer"] == "linear":
         o += [("df_dec.df_out.0.bias", "w")]
-    o += [("df_dec.df_fc_a.0.weight", "w"), ("df_dec.df_fc_a.0.bias", "w")]
-    o += [("df_dec.df_convp.1.weight", "w"), ("df_dec.df_convp.2.weight", "w"), ("df_dec.df_convp.3", "bn")]
-    return o
+    return o + [("df_dec.df_fc_a.0.weight", "w"), ("df_dec.df_fc_a.0.bias", "w")] + dfn_weights.DF_PATHWAY_ORDER
 
 
 def pack(sd: Dict[str, torch.Tensor], cfg: dict) -> np.ndarray:
-    parts = []
-    for name, kind in pack_order(cfg):
-        if kind == "bn":
-            s, t = fold_bn(sd, name)
-            parts += [s.float().reshape(-1), t.float().reshape(-1)]
-        else:
-            parts.append(sd[name].float().reshape(-1))
-    return torch.cat(parts).numpy().astype(np.float32)
+    return dfn_weights.pack_tensors(sd, pack_order(cfg))
 
 
-class DFN2Model:
-    """A validated DeepFilterNet2 model directory: config (dict), state dict, ERB widths, norm alpha, packed fp32 weights."""
-
-    def __init__(self, cfg: dict, sd: Dict[str, torch.Tensor], directory: Optional[Path] = None):
-        check_supported(cfg)
-        validate(sd, cfg)
-        self.cfg, self.sd, self.dir = cfg, sd, directory
-        self.widths = erb_widths(cfg["sr"], cfg["fft_size"], cfg["nb_erb"], cfg["min_nb_erb_freqs"])
-        self.alpha = norm_alpha(cfg)
-
-    def packed(self) -> np.ndarray:
-        return pack(self.sd, self.cfg)
+class DFN2Model(dfn_weights.Model):
+    weights = sys.modules[__name__]
 
 
 def load(model_dir: Optional[Path] = None) -> DFN2Model:
-    d = Path(model_dir) if model_dir else discover()
-    if d is None:
-        raise RuntimeError("no DeepFilterNet2 model directory found; searched:\n  " +
-                           "\n  ".join(map(str, dfn_weights.candidate_dirs(MODEL))))
-    ck = checkpoint_file(d)
-    if not (d / "config.ini").is_file() or ck is None:
-        raise RuntimeError(f"{d} is not a DeepFilterNet model directory (config.ini + checkpoints/*.ckpt.best)")
+    d, ck = dfn_weights.model_files(model_dir, None if model_dir else discover(), MODEL)
     if model_id(d) != MODEL_ID:
         raise RuntimeError(f"{d} holds [train] model = {model_id(d)!r}, not {MODEL_ID!r}")
     return DFN2Model(parse_config(d / "config.ini"), read_state_dict(ck), d)

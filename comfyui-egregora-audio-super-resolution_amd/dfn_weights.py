@@ -15,6 +15,7 @@ import json
 import math
 import os
 import re
+import sys
 from pathlib import Path
 from typing import Dict, List, Optional, Tuple
 
@@ -89,12 +90,12 @@ def discover(model: str = MODEL) -> Optional[Path]:
 
 
 # ------------------------------------------------------------------------------------------------ config
-def parse_config(path: Path) -> dict:
-    """config.ini -> {key: value} for every entry of PARAMS; raises listing every absent or unreadable key."""
+def parse_config(path: Path, params=PARAMS, model: str = MODEL) -> dict:
+    """config.ini -> {key: value} for every entry of params (a module's PARAMS); raises listing every absent or unreadable key."""
     cp = configparser.ConfigParser()
     cp.read(str(path), encoding="utf-8")
     cfg, bad = {}, []
-    for sec, key, typ in PARAMS:
+    for sec, key, typ in params:
         if not cp.has_option(sec, key):
             bad.append(f"[{sec}] {key}: missing")
             continue
@@ -117,12 +118,39 @@ def parse_config(path: Path) -> dict:
             continue
         cfg[key] = v
     if bad:
-        raise RuntimeError(f"DeepFilterNet3 config {path} is incomplete:\n  " + "\n  ".join(bad))
+        raise RuntimeError(f"{model} config {path} is incomplete:\n  " + "\n  ".join(bad))
     return cfg
 
 
 MAX_GRU_LAYERS = 8                  # EGR_DFN3_MAX_GRU (include/egregora_amd.h)
 MAX_NB_ERB = 64                     # EGR_DFN3_MAX_ERB
+
+
+def check_common(cfg: dict, bad: List[str], recurrence: str = "the recurrence kernel holds"):
+    """The range checks of the signal path and the GRU stacks both models share; appends what is out of range to bad.  recurrence
+    is the subject of the GRU-width message: DeepFilterNet2 has two recurrence kernels and says so, and the messages keep their text."""
+    for k in ("conv_kernel", "conv_kernel_inp"):
+        kt, kf = cfg[k]
+        if kt < 1 or kf < 1 or kf % 2 == 0:
+            bad.append(f"{k} = {cfg[k]} (time extent >= 1, odd frequency extent)")
+    if cfg["df_pathway_kernel_size_t"] < 1:
+        bad.append(f"df_pathway_kernel_size_t = {cfg['df_pathway_kernel_size_t']} (>= 1)")
+    if cfg["hop_size"] < 1 or cfg["fft_size"] < 2 or cfg["fft_size"] % cfg["hop_size"] or cfg["fft_size"] % 2 or cfg["fft_size"] > 4096:
+        bad.append(f"fft_size {cfg['fft_size']} must be even, <= 4096 and a multiple of hop_size {cfg['hop_size']}")
+    if cfg["nb_erb"] < 4 or cfg["nb_erb"] % 4 or cfg["nb_erb"] > MAX_NB_ERB or cfg["nb_df"] < 2 or cfg["nb_df"] % 2:
+        bad.append(f"nb_erb = {cfg['nb_erb']} (multiple of 4, <= {MAX_NB_ERB}), nb_df = {cfg['nb_df']} (even)")
+    if cfg["nb_df"] > cfg["fft_size"] // 2 + 1:
+        bad.append(f"nb_df = {cfg['nb_df']} / fft_size = {cfg['fft_size']} out of range")
+    for k in ("emb_hidden_dim", "df_hidden_dim"):
+        if not 1 <= cfg[k] <= 256:
+            bad.append(f"{k} = {cfg[k]} ({recurrence} 1 <= H <= 256)")
+    n_gru = cfg["emb_num_layers"] + cfg["df_num_layers"]
+    if cfg["emb_num_layers"] < 2 or cfg["df_num_layers"] < 1 or n_gru > MAX_GRU_LAYERS:
+        bad.append(f"emb_num_layers = {cfg['emb_num_layers']} (>= 2: one encoder layer, at least one ERB-decoder layer), "
+                   f"df_num_layers = {cfg['df_num_layers']} (>= 1), {n_gru} GRU layers in total (<= {MAX_GRU_LAYERS})")
+    if cfg["df_order"] < 1 or cfg["conv_lookahead"] < 0 or cfg["df_lookahead"] < 0 or cfg["df_lookahead"] > cfg["df_order"] - 1:
+        bad.append(f"df_order = {cfg['df_order']}, conv_lookahead = {cfg['conv_lookahead']}, df_lookahead = {cfg['df_lookahead']} "
+                   "out of range")
 
 
 def check_supported(cfg: dict):
@@ -142,28 +170,7 @@ def check_supported(cfg: dict):
         bad.append(f"df_gru_skip = {cfg['df_gru_skip']!r} (supported: 'none', 'groupedlinear')")
     if tuple(cfg["convt_kernel"]) != (1, 3):
         bad.append(f"convt_kernel = {cfg['convt_kernel']} (supported: (1, 3), the only width a stride-2 transposed conv doubles)")
-    for k in ("conv_kernel", "conv_kernel_inp"):
-        kt, kf = cfg[k]
-        if kt < 1 or kf < 1 or kf % 2 == 0:
-            bad.append(f"{k} = {cfg[k]} (time extent >= 1, odd frequency extent)")
-    if cfg["df_pathway_kernel_size_t"] < 1:
-        bad.append(f"df_pathway_kernel_size_t = {cfg['df_pathway_kernel_size_t']} (>= 1)")
-    if cfg["hop_size"] < 1 or cfg["fft_size"] < 2 or cfg["fft_size"] % cfg["hop_size"] or cfg["fft_size"] % 2 or cfg["fft_size"] > 4096:
-        bad.append(f"fft_size {cfg['fft_size']} must be even, <= 4096 and a multiple of hop_size {cfg['hop_size']}")
-    if cfg["nb_erb"] < 4 or cfg["nb_erb"] % 4 or cfg["nb_erb"] > MAX_NB_ERB or cfg["nb_df"] < 2 or cfg["nb_df"] % 2:
-        bad.append(f"nb_erb = {cfg['nb_erb']} (multiple of 4, <= {MAX_NB_ERB}), nb_df = {cfg['nb_df']} (even)")
-    if cfg["nb_df"] > cfg["fft_size"] // 2 + 1:
-        bad.append(f"nb_df = {cfg['nb_df']} / fft_size = {cfg['fft_size']} out of range")
-    for k in ("emb_hidden_dim", "df_hidden_dim"):
-        if not 1 <= cfg[k] <= 256:
-            bad.append(f"{k} = {cfg[k]} (the recurrence kernel holds 1 <= H <= 256)")
-    n_gru = cfg["emb_num_layers"] + cfg["df_num_layers"]
-    if cfg["emb_num_layers"] < 2 or cfg["df_num_layers"] < 1 or n_gru > MAX_GRU_LAYERS:
-        bad.append(f"emb_num_layers = {cfg['emb_num_layers']} (>= 2: one encoder layer, at least one ERB-decoder layer), "
-                   f"df_num_layers = {cfg['df_num_layers']} (>= 1), {n_gru} GRU layers in total (<= {MAX_GRU_LAYERS})")
-    if cfg["df_order"] < 1 or cfg["conv_lookahead"] < 0 or cfg["df_lookahead"] < 0 or cfg["df_lookahead"] > cfg["df_order"] - 1:
-        bad.append(f"df_order = {cfg['df_order']}, conv_lookahead = {cfg['conv_lookahead']}, df_lookahead = {cfg['df_lookahead']} "
-                   "out of range")
+    check_common(cfg, bad)
     if cfg["conv_ch"] < 1 or cfg["lin_groups"] < 1 or cfg["enc_lin_groups"] < 1:
         bad.append(f"conv_ch = {cfg['conv_ch']}, lin_groups = {cfg['lin_groups']}, enc_lin_groups = {cfg['enc_lin_groups']} (>= 1)")
     elif not bad:
@@ -245,10 +252,12 @@ def derived_vars(cfg: dict) -> dict:
 
 
 # ------------------------------------------------------------------------------------------------ key table
-def expected_table(cfg: dict, keymap_path: Optional[Path] = None) -> Dict[str, Tuple[int, ...]]:
-    """{tensor name: shape} the key table prescribes for this config."""
+def expected_table(cfg: dict, keymap_path: Optional[Path] = None, env: Optional[dict] = None) -> Dict[str, Tuple[int, ...]]:
+    """{tensor name: shape} the key table prescribes for this config; env: the names its expressions use (derived_vars(cfg)).  An
+    entry repeats over '{k}' for the layer count named by 'layers', or over '{l}' for the layer range 'l' = [first, end expression]
+    and over '{g}' for the group count named by 'g'."""
     spec = json.loads(Path(keymap_path or KEYMAP_PATH).read_text(encoding="utf-8"))
-    env = derived_vars(cfg)
+    env = env or derived_vars(cfg)
     ev = lambda s: int(eval(str(s), {"__builtins__": {}}, env))      # noqa: S307 (repo-owned JSON, integer expressions)
     out = {}
     for e in spec["entries"]:
@@ -256,17 +265,21 @@ def expected_table(cfg: dict, keymap_path: Optional[Path] = None) -> Dict[str, T
             continue
         shape = tuple(ev(s) for s in e["shape"])
         if "layers" in e:
-            for k in range(env[e["layers"]]):
-                out[e["name"].replace("{k}", str(k))] = shape
+            layers = range(env[e["layers"]])
+        elif "l" in e:
+            layers = range(ev(e["l"][0]), ev(e["l"][1]))
         else:
-            out[e["name"]] = shape
+            layers = [None]
+        groups = range(env[e["g"]]) if "g" in e else [None]
+        for l in layers:
+            name = e["name"].replace("{k}", str(l)).replace("{l}", str(l))
+            for g in groups:
+                out[name.replace("{g}", str(g))] = shape
     return out
 
 
-def layer_table(sd: Dict[str, torch.Tensor]) -> dict:
-    """Layer counts and widths read from the tensor shapes alone (no config)."""
-    def nlayers(prefix):
-        return len([k for k in sd if re.fullmatch(re.escape(prefix) + r"\.weight_hh_l\d+", k)])
+def layer_table_common(sd: Dict[str, torch.Tensor]) -> dict:
+    """What the convolutions, the ERB bank and df_skip say in both models' checkpoints."""
     t = {}
     def get(name):
         return sd[name].shape if name in sd else None
@@ -279,6 +292,20 @@ def layer_table(sd: Dict[str, torch.Tensor]) -> dict:
     s = get("erb_fb")
     if s is not None:
         t["fft_size"], t["nb_erb"] = 2 * (int(s[0]) - 1), int(s[1])
+    s = get("df_dec.df_convp.1.weight")
+    if s is not None:
+        t["df_order"], t["df_pathway_kernel_size_t"] = int(s[0]) // 2, int(s[2])
+    t["df_gru_skip"] = "groupedlinear" if "df_dec.df_skip.weight" in sd else "none"
+    return t
+
+
+def layer_table(sd: Dict[str, torch.Tensor]) -> dict:
+    """Layer counts and widths read from the tensor shapes alone (no config)."""
+    def nlayers(prefix):
+        return len([k for k in sd if re.fullmatch(re.escape(prefix) + r"\.weight_hh_l\d+", k)])
+    t = layer_table_common(sd)
+    def get(name):
+        return sd[name].shape if name in sd else None
     s = get("enc.emb_gru.gru.weight_hh_l0")
     if s is not None:
         t["emb_hidden_dim"] = int(s[1])
@@ -295,20 +322,15 @@ def layer_table(sd: Dict[str, torch.Tensor]) -> dict:
         t["enc_lin_groups"] = int(s[0])
         if "conv_ch" in t:
             t["nb_df"] = 2 * int(s[0]) * int(s[1]) // t["conv_ch"]
-    s = get("df_dec.df_convp.1.weight")
-    if s is not None:
-        t["df_order"], t["df_pathway_kernel_size_t"] = int(s[0]) // 2, int(s[2])
-    t["df_gru_skip"] = "groupedlinear" if "df_dec.df_skip.weight" in sd else "none"
     return t
 
 
-def validate(sd: Dict[str, torch.Tensor], cfg: dict, keymap_path: Optional[Path] = None):
-    """Raise with every unmapped / missing / mismatched tensor and every config field the shapes contradict."""
-    want = expected_table(cfg, keymap_path)
+def validate_against(sd: Dict[str, torch.Tensor], cfg: dict, want: Dict[str, Tuple[int, ...]], lt: dict, model: str, keymap: str):
+    """Raise with every unmapped / missing / mismatched tensor against the expected table `want` and every config field the layer
+    table `lt` contradicts; model and the key table's file name go into the messages."""
     unmapped = sorted(k for k in sd if k not in want)
     missing = sorted(k for k in want if k not in sd)
     wrong = sorted(f"{k}: checkpoint {tuple(sd[k].shape)} != table {want[k]}" for k in want if k in sd and tuple(sd[k].shape) != want[k])
-    lt = layer_table(sd)
     conflict = sorted(f"{k}: shapes say {v!r}, config.ini says {cfg[k]!r}" for k, v in lt.items() if k in cfg and cfg[k] != v)
     if unmapped or missing or wrong or conflict:
         parts = []
@@ -316,11 +338,16 @@ def validate(sd: Dict[str, torch.Tensor], cfg: dict, keymap_path: Optional[Path]
                            ("config / checkpoint disagreements", conflict)):
             if lst:
                 parts.append(f"{title} ({len(lst)}):\n    " + "\n    ".join(lst))
-        raise RuntimeError("DeepFilterNet3 checkpoint does not match dfn3_keymap.json / config.ini:\n  " + "\n  ".join(parts))
+        raise RuntimeError(f"{model} checkpoint does not match {keymap} / config.ini:\n  " + "\n  ".join(parts))
     widths = erb_widths(cfg["sr"], cfg["fft_size"], cfg["nb_erb"], cfg["min_nb_erb_freqs"])
     fb, ifb = erb_matrices(widths)
     if not (torch.allclose(sd["erb_fb"].float(), fb, atol=1e-6) and torch.allclose(sd["mask.erb_inv_fb"].float(), ifb, atol=1e-6)):
-        raise RuntimeError(f"DeepFilterNet3 checkpoint: erb_fb / mask.erb_inv_fb differ from the ERB bank of config.ini (widths {widths})")
+        raise RuntimeError(f"{model} checkpoint: erb_fb / mask.erb_inv_fb differ from the ERB bank of config.ini (widths {widths})")
+
+
+def validate(sd: Dict[str, torch.Tensor], cfg: dict, keymap_path: Optional[Path] = None):
+    """Raise with every unmapped / missing / mismatched tensor and every config field the shapes contradict."""
+    validate_against(sd, cfg, expected_table(cfg, keymap_path), layer_table(sd), MODEL, KEYMAP_PATH.name)
 
 
 def read_state_dict(path: Path) -> Dict[str, torch.Tensor]:
@@ -334,14 +361,31 @@ def read_state_dict(path: Path) -> Dict[str, torch.Tensor]:
 
 
 # ------------------------------------------------------------------------------------------------ packing
-def pack_order(cfg: dict) -> List[Tuple[str, str]]:
-    """(tensor name, kind) in the order egr_dfn3_create reads them (csrc/egr_dfn3.hip, read_weights).  kind "w": the tensor as
-    stored (torch layout, fp32); "bn": a BatchNorm folded to eval-mode per-channel scale then shift."""
+# The conv stacks both models pack alike (WeightCursor::encoder_convs / erb_decoder_convs / df_pathway_convs, csrc/egr_dfn3.hip)
+def encoder_order() -> List[Tuple[str, str]]:
     o = [("enc.erb_conv0.1.weight", "w"), ("enc.erb_conv0.2", "bn")]
     for i in (1, 2, 3):
         o += [(f"enc.erb_conv{i}.0.weight", "w"), (f"enc.erb_conv{i}.1.weight", "w"), (f"enc.erb_conv{i}.2", "bn")]
-    o += [("enc.df_conv0.1.weight", "w"), ("enc.df_conv0.2.weight", "w"), ("enc.df_conv0.3", "bn"),
-          ("enc.df_conv1.0.weight", "w"), ("enc.df_conv1.1.weight", "w"), ("enc.df_conv1.2", "bn"), ("enc.df_fc_emb.0.weight", "w")]
+    return o + [("enc.df_conv0.1.weight", "w"), ("enc.df_conv0.2.weight", "w"), ("enc.df_conv0.3", "bn"),
+                ("enc.df_conv1.0.weight", "w"), ("enc.df_conv1.1.weight", "w"), ("enc.df_conv1.2", "bn")]
+
+
+def erb_decoder_order() -> List[Tuple[str, str]]:
+    o = []
+    for i in (3, 2, 1):
+        o += [(f"erb_dec.conv{i}p.0.weight", "w"), (f"erb_dec.conv{i}p.1", "bn"), (f"erb_dec.convt{i}.0.weight", "w"),
+              (f"erb_dec.convt{i}.1.weight", "w"), (f"erb_dec.convt{i}.2", "bn")]
+    return o + [("erb_dec.conv0p.0.weight", "w"), ("erb_dec.conv0p.1", "bn"), ("erb_dec.conv0_out.0.weight", "w"),
+                ("erb_dec.conv0_out.1", "bn")]
+
+
+DF_PATHWAY_ORDER = [("df_dec.df_convp.1.weight", "w"), ("df_dec.df_convp.2.weight", "w"), ("df_dec.df_convp.3", "bn")]
+
+
+def pack_order(cfg: dict) -> List[Tuple[str, str]]:
+    """(tensor name, kind) in the order egr_dfn3_create reads them (csrc/egr_dfn3.hip).  kind "w": the tensor as stored (torch
+    layout, fp32); "bn": a BatchNorm folded to eval-mode per-channel scale then shift."""
+    o = encoder_order() + [("enc.df_fc_emb.0.weight", "w")]
 
     def sq(prefix, n):
         r = [(f"{prefix}.linear_in.0.weight", "w")]
@@ -350,15 +394,10 @@ def pack_order(cfg: dict) -> List[Tuple[str, str]]:
         return r
     o += sq("enc.emb_gru", 1) + [("enc.emb_gru.linear_out.0.weight", "w")]
     o += sq("erb_dec.emb_gru", cfg["emb_num_layers"] - 1) + [("erb_dec.emb_gru.linear_out.0.weight", "w")]
-    for i in (3, 2, 1):
-        o += [(f"erb_dec.conv{i}p.0.weight", "w"), (f"erb_dec.conv{i}p.1", "bn"), (f"erb_dec.convt{i}.0.weight", "w"),
-              (f"erb_dec.convt{i}.1.weight", "w"), (f"erb_dec.convt{i}.2", "bn")]
-    o += [("erb_dec.conv0p.0.weight", "w"), ("erb_dec.conv0p.1", "bn"), ("erb_dec.conv0_out.0.weight", "w"), ("erb_dec.conv0_out.1", "bn")]
-    o += sq("df_dec.df_gru", cfg["df_num_layers"])
+    o += erb_decoder_order() + sq("df_dec.df_gru", cfg["df_num_layers"])
     if cfg["df_gru_skip"] == "groupedlinear":
         o += [("df_dec.df_skip.weight", "w")]
-    o += [("df_dec.df_out.0.weight", "w"), ("df_dec.df_convp.1.weight", "w"), ("df_dec.df_convp.2.weight", "w"), ("df_dec.df_convp.3", "bn")]
-    return o
+    return o + [("df_dec.df_out.0.weight", "w")] + DF_PATHWAY_ORDER
 
 
 def fold_bn(sd, prefix) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -368,9 +407,10 @@ def fold_bn(sd, prefix) -> Tuple[torch.Tensor, torch.Tensor]:
     return s, b - m * s
 
 
-def pack(sd: Dict[str, torch.Tensor], cfg: dict) -> np.ndarray:
+def pack_tensors(sd: Dict[str, torch.Tensor], order: List[Tuple[str, str]]) -> np.ndarray:
+    """The tensors of a pack order as one fp32 array."""
     parts = []
-    for name, kind in pack_order(cfg):
+    for name, kind in order:
         if kind == "bn":
             s, t = fold_bn(sd, name)
             parts += [s.float().reshape(-1), t.float().reshape(-1)]
@@ -379,25 +419,42 @@ def pack(sd: Dict[str, torch.Tensor], cfg: dict) -> np.ndarray:
     return torch.cat(parts).numpy().astype(np.float32)
 
 
-class DFN3Model:
-    """A validated model directory: config (dict), state dict, ERB widths, norm alpha, packed fp32 weights."""
+def pack(sd: Dict[str, torch.Tensor], cfg: dict) -> np.ndarray:
+    return pack_tensors(sd, pack_order(cfg))
+
+
+class Model:
+    """A validated model directory: config (dict), state dict, ERB widths, norm alpha, packed fp32 weights.  check_supported,
+    validate and pack are those of `weights`, the weights module a subclass names."""
+    weights = None
 
     def __init__(self, cfg: dict, sd: Dict[str, torch.Tensor], directory: Optional[Path] = None):
-        check_supported(cfg)
-        validate(sd, cfg)
+        self.weights.check_supported(cfg)
+        self.weights.validate(sd, cfg)
         self.cfg, self.sd, self.dir = cfg, sd, directory
         self.widths = erb_widths(cfg["sr"], cfg["fft_size"], cfg["nb_erb"], cfg["min_nb_erb_freqs"])
         self.alpha = norm_alpha(cfg)
 
     def packed(self) -> np.ndarray:
-        return pack(self.sd, self.cfg)
+        return self.weights.pack(self.sd, self.cfg)
 
 
-def load(model_dir: Optional[Path] = None) -> DFN3Model:
-    d = Path(model_dir) if model_dir else discover()
+class DFN3Model(Model):
+    weights = sys.modules[__name__]
+
+
+def model_files(model_dir: Optional[Path], found: Optional[Path], model: str) -> Tuple[Path, Path]:
+    """(directory, checkpoint file) of model_dir, or of `found` (the module's discover()) when it is None; raises when neither is
+    a model directory."""
+    d = Path(model_dir) if model_dir else found
     if d is None:
-        raise RuntimeError("no DeepFilterNet3 model directory found; searched:\n  " + "\n  ".join(map(str, candidate_dirs())))
+        raise RuntimeError(f"no {model} model directory found; searched:\n  " + "\n  ".join(map(str, candidate_dirs(model))))
     ck = checkpoint_file(d)
     if not (d / "config.ini").is_file() or ck is None:
         raise RuntimeError(f"{d} is not a DeepFilterNet model directory (config.ini + checkpoints/*.ckpt.best)")
+    return d, ck
+
+
+def load(model_dir: Optional[Path] = None) -> DFN3Model:
+    d, ck = model_files(model_dir, None if model_dir else discover(), MODEL)
     return DFN3Model(parse_config(d / "config.ini"), read_state_dict(ck), d)

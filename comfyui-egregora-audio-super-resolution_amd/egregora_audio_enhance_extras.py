@@ -140,15 +140,11 @@ class Egregora_DeepFilterNet_Denoise:
         try:
             from df.enhance import enhance, init_df
         except Exception as e:      # noqa: BLE001
-            from . import dfn2_weights, dfn_weights
-            model_dir = dfn_weights.discover(model_name)
-            if model_dir is not None:
-                from . import dfn_engine
-                return dfn_engine.engine(model_dir, x48.device.index).enhance(x48)
-            model_dir = dfn2_weights.discover(model_name)
-            if model_dir is not None:
-                from . import dfn2_engine
-                return dfn2_engine.engine(model_dir, x48.device.index).enhance(x48)
+            from . import dfn2_engine, dfn2_weights, dfn_engine, dfn_weights
+            for weights, eng in ((dfn_weights, dfn_engine), (dfn2_weights, dfn2_engine)):
+                model_dir = weights.discover(model_name)
+                if model_dir is not None:
+                    return eng.engine(model_dir, x48.device.index).enhance(x48)
             raise RuntimeError("DeepFilterNet (python package `df`) is not installed; this pack runs the stage around the "
                                "model on the GPU but does not re-implement the upstream network "
                                "(register one with egregora_audio_enhance_extras.set_enhancer).") from e
