@@ -826,6 +826,12 @@ static bool pz_length(int64_t D, FlSplit* sp_out);
 static inline int pz_kind_for(int64_t N) { return (N & 1) ? 2 : 1; }
 // LDS of k_rowconv: two rows, stages in place
 static size_t rowconv_lds(int L) { return EGR_LDS((size_t)EGR_FL_CONV_ROWS * (L + (EGR_FL_CONV_PAD ? L >> EGR_FL_CONV_PAD : 0)) * sizeof(cplx)); }
+// blocks of 256 threads striding over n elements of a channel
+static int fl_grid(long long n) { return (int)std::min<long long>((n + 255) / 256, 2048); }
+// dynamic LDS of the scheduled loop kernels: k_row<., 1> has no ping-pong buffer and pads its two rows by one element per
+// 2^EGR_FL_ROW_PAD; k_col<., 2> transforms in place
+static size_t row_sched_lds(int L) { return EGR_LDS((size_t)2 * (L + (EGR_FL_ROW_PAD ? L >> EGR_FL_ROW_PAD : 0)) * sizeof(cplx)); }
+static size_t col_sched_lds(const egr_fatllama_plan* p) { return EGR_LDS(p->sp.lds_col / 2); }
 // workgroup size of the chirp-z loop kernels (their tiles take most of a CU's LDS: one workgroup per CU, so a large one)
 static int blue_threads() {
     static const int t = [] { const char* e = getenv("EGR_FL_BLUE_THREADS"); const int v = e ? atoi(e) : 1024; return (v == 256 || v == 512 || v == 1024) ? v : 1024; }();
@@ -861,13 +867,21 @@ extern "C" int egr_fatllama_plan_query(int64_t n_in, int factor, int m1_hint, in
     return EGR_OK;
 }
 
+int fl_drop_graph(egr_fatllama_plan* p) {
+    if (!p->gexec) return EGR_OK;
+    EGR_HIP(hipDeviceSynchronize());
+    EGR_HIP(hipGraphExecDestroy(p->gexec));
+    p->gexec = nullptr;
+    return EGR_OK;
+}
+
 extern "C" int egr_fatllama_plan_destroy(egr_fatllama_plan* p) {
     if (!p) return EGR_OK;
     hipDeviceSynchronize();          // nothing of the plan may still be in flight when its graph, streams and buffers go
+    fl_drop_graph(p);
     pz_destroy(p);
     for (void* q : p->dev_allocs) hipFree(q);
     hipFree(p->d_work); hipFree(p->d_peaks); hipFree(p->d_bhat); hipFree(p->d_max2);
-    if (p->gexec) hipGraphExecDestroy(p->gexec);
     if (p->cap) hipStreamDestroy(p->cap);
     if (p->side && p->side_owned) hipStreamDestroy(p->side);
     if (p->ev_fork) hipEventDestroy(p->ev_fork);
@@ -887,7 +901,7 @@ static int build_plan(egr_fatllama_plan** out, int64_t n_in, int channels, int f
     p->nstreams = 2;
     if (const char* e = getenv("EGR_FL_STREAMS")) { const int t = atoi(e); if (t == 1 || t == 2) p->nstreams = t; }
     p->side = nullptr; p->side_owned = 0; p->ev_fork = nullptr; p->ev_join = nullptr;
-    p->cap = nullptr; p->gexec = nullptr; p->g_out = nullptr; p->g_thr = 0.f; p->g_groups = 0; p->g_iter_odd = 0;
+    p->cap = nullptr; p->gexec = nullptr; p->g_thr = 0.f; p->g_groups = 0; p->g_hook_kind = 0;
     p->use_graph = !(getenv("EGR_FL_GRAPH") && atoi(getenv("EGR_FL_GRAPH")) == 0);
     p->threads = 512;    // 16 waves per CU at 2 workgroups per CU: measured 1.4x over 256
     if (const char* e = getenv("EGR_FL_THREADS")) { const int t = atoi(e); if (t == 256 || t == 512 || t == 1024) p->threads = t; }
@@ -1177,32 +1191,38 @@ static int create_for_length(egr_fatllama_plan** out, int64_t n_in, int channels
     return build_plan(out, n_in, channels, factor, sp, 0, 0, N);
 }
 
-extern "C" int egr_fatllama_plan_create(egr_fatllama_plan** out, int64_t n_in, int channels, int factor,
-                                        int m1_hint, int tc_hint) {
+// The preamble of the egr_fatllama_plan_create* entry points: `out` reset, sizes in range (the chirp-z ones need n_in * factor >= 2;
+// egr_fatllama_plan_create_n gives its output length instead of a factor).
+static int create_check(egr_fatllama_plan** out, int64_t n_in, int channels, int factor, int64_t min_n, const int64_t* n_out = nullptr) {
     EGR_CHECK(out != nullptr, EGR_ERR_ARG, "out is null");
     *out = nullptr;
-    EGR_CHECK(n_in >= 1 && factor >= 1 && channels >= 1 && channels <= 64, EGR_ERR_ARG,
+    if (n_out) {
+        EGR_CHECK(n_in >= 1 && *n_out >= n_in && channels >= 1 && channels <= 64, EGR_ERR_ARG,
+                  "n_in=%lld n_out=%lld channels=%d out of range", (long long)n_in, (long long)*n_out, channels);
+        return EGR_OK;
+    }
+    EGR_CHECK(n_in >= 1 && factor >= 1 && channels >= 1 && channels <= 64 && n_in * factor >= min_n, EGR_ERR_ARG,
               "n_in=%lld channels=%d factor=%d out of range", (long long)n_in, channels, factor);
+    return EGR_OK;
+}
+
+extern "C" int egr_fatllama_plan_create(egr_fatllama_plan** out, int64_t n_in, int channels, int factor,
+                                        int m1_hint, int tc_hint) {
+    if (int rc = create_check(out, n_in, channels, factor, 1)) return rc;
     return create_for_length(out, n_in, channels, factor, n_in * factor, m1_hint, tc_hint);
 }
 
 // A plan whose output length is given explicitly (n_out >= n_in, not necessarily a multiple of it): SPEC.md factor_mode
 // "ratio_then_int".  egr_fatllama_enhance on such a plan needs EGR_FL_INTERP_LINSPACE (the only up-rating defined for a ratio).
 extern "C" int egr_fatllama_plan_create_n(egr_fatllama_plan** out, int64_t n_in, int64_t n_out, int channels) {
-    EGR_CHECK(out != nullptr, EGR_ERR_ARG, "out is null");
-    *out = nullptr;
-    EGR_CHECK(n_in >= 1 && n_out >= n_in && channels >= 1 && channels <= 64, EGR_ERR_ARG,
-              "n_in=%lld n_out=%lld channels=%d out of range", (long long)n_in, (long long)n_out, channels);
+    if (int rc = create_check(out, n_in, channels, 0, 0, &n_out)) return rc;
     return create_for_length(out, n_in, channels, 0, n_out, 0, 0);
 }
 
 // Force a chirp-z plan on any length (tests, A/B runs): kind 1 = paired, even/odd packing (N even); 2 = paired, channel pairs
 // (any N); 3 = the legacy full-complex form (one P >= 2N - 1 state per channel).
 extern "C" int egr_fatllama_plan_create_chirpz(egr_fatllama_plan** out, int64_t n_in, int channels, int factor, int kind) {
-    EGR_CHECK(out != nullptr, EGR_ERR_ARG, "out is null");
-    *out = nullptr;
-    EGR_CHECK(n_in >= 1 && factor >= 1 && channels >= 1 && channels <= 64 && n_in * factor >= 2, EGR_ERR_ARG,
-              "n_in=%lld channels=%d factor=%d out of range", (long long)n_in, channels, factor);
+    if (int rc = create_check(out, n_in, channels, factor, 2)) return rc;
     const int64_t N = n_in * factor;
     if (kind == 0) kind = pz_kind_for(N);
     if (kind == 3) return egr_fatllama_plan_create_bluestein(out, n_in, channels, factor);
@@ -1217,10 +1237,7 @@ extern "C" int egr_fatllama_plan_create_chirpz(egr_fatllama_plan** out, int64_t 
 }
 
 extern "C" int egr_fatllama_plan_create_bluestein(egr_fatllama_plan** out, int64_t n_in, int channels, int factor) {
-    EGR_CHECK(out != nullptr, EGR_ERR_ARG, "out is null");
-    *out = nullptr;
-    EGR_CHECK(n_in >= 1 && factor >= 1 && channels >= 1 && channels <= 64 && n_in * factor >= 2, EGR_ERR_ARG,
-              "n_in=%lld channels=%d factor=%d out of range", (long long)n_in, channels, factor);
+    if (int rc = create_check(out, n_in, channels, factor, 2)) return rc;
     const int64_t N = n_in * factor;
     FlSplit sp;
     if (!bluestein_length(2 * N - 1, &sp)) {
@@ -1232,10 +1249,7 @@ extern "C" int egr_fatllama_plan_create_bluestein(egr_fatllama_plan** out, int64
 
 extern "C" int egr_fatllama_plan_create_ex(egr_fatllama_plan** out, int64_t n_in, int channels, int factor, int m1,
                                            int m2, int m3, int tc_hint) {
-    EGR_CHECK(out != nullptr, EGR_ERR_ARG, "out is null");
-    *out = nullptr;
-    EGR_CHECK(n_in >= 1 && factor >= 1 && channels >= 1 && channels <= 64, EGR_ERR_ARG,
-              "n_in=%lld channels=%d factor=%d out of range", (long long)n_in, channels, factor);
+    if (int rc = create_check(out, n_in, channels, factor, 1)) return rc;
     FlSplit sp = plan_split_explicit(n_in * factor, m1, m2, m3, tc_hint);
     if (!sp.ok) {
         set_error("explicit split %d x %d x %d does not fit N=%lld", m1, m2, m3, (long long)(n_in * factor));
@@ -1267,12 +1281,12 @@ extern "C" int egr_fatllama_trace_once(egr_fatllama_plan* p, void* stream) {
                     const WlRowEntry* e = (const WlRowEntry*)p->wl_row_entry;
                     hipLaunchKernelGGL(e->fn, grow, dim3(e->threads), EGR_LDS(e->lds), st, R, p->wl_rt, M, p->d_work);
                 }
-                else if (p->row_sched == 1) hipLaunchKernelGGL((k_row<false, 1>), grow, blk, EGR_LDS((size_t)2 * (R.L + (EGR_FL_ROW_PAD ? R.L >> EGR_FL_ROW_PAD : 0)) * sizeof(cplx)), st, R, M, p->d_work);
+                else if (p->row_sched == 1) hipLaunchKernelGGL((k_row<false, 1>), grow, blk, row_sched_lds(R.L), st, R, M, p->d_work);
                 else hipLaunchKernelGGL(k_row<false>, grow, blk, EGR_LDS(p->sp.lds_row), st, R, M, p->d_work);
             } else {
                 if (p->wl_col) {
                     wl_launch_col(A, p->wl_ct, M, p->d_work, C, st);
-                } else if (p->col_sched == 2) hipLaunchKernelGGL((k_col<1, 2>), gA, dim3(EGR_FL_COL_THREADS), EGR_LDS(p->sp.lds_col / 2), st, A, M, N, 0.6f, p->d_work, (float*)nullptr, (unsigned*)nullptr, (const unsigned*)nullptr);
+                } else if (p->col_sched == 2) hipLaunchKernelGGL((k_col<1, 2>), gA, dim3(EGR_FL_COL_THREADS), col_sched_lds(p), st, A, M, N, 0.6f, p->d_work, (float*)nullptr, (unsigned*)nullptr, (const unsigned*)nullptr);
                 else hipLaunchKernelGGL(k_col<1>, gA, blk, EGR_LDS(p->sp.lds_col), st, A, M, N, 0.6f, p->d_work, (float*)nullptr, (unsigned*)nullptr);
             }
         }
@@ -1331,247 +1345,228 @@ void fl_prof_end(egr_fatllama_plan* p, hipStream_t st, size_t* slot) {
     *slot += 2;
 }
 
-extern "C" int egr_fatllama_enhance(egr_fatllama_plan* p, const float* x, float* out, int max_iter, float thr,
-                                    unsigned flags, void* stream) {
-    EGR_CHECK(p && x && out, EGR_ERR_ARG, "null plan/x/out");
-    EGR_CHECK(max_iter >= 0, EGR_ERR_ARG, "max_iter=%d < 0", max_iter);
-    hipStream_t st = (hipStream_t)stream;
+// k_finalize over `out`, or (out == nullptr) one workgroup that only leaves the joint peak in joint_out
+static void launch_finalize(egr_fatllama_plan* p, float* out, unsigned flags, const float* joint_in, float* joint_out, hipStream_t st) {
+    const long long Nr = out ? (long long)p->n_out : 0LL;
+    hipLaunchKernelGGL(k_finalize, out ? dim3(fl_grid(Nr), p->C) : dim3(1, 1), dim3(out ? 256 : 64), 0, st, out, Nr, p->C, flags, p->d_peaks,
+                       p->d_peaks + p->C, joint_in, joint_out);
+}
+
+namespace {
+// one egr_fatllama_enhance call
+struct FlCall {
+    egr_fatllama_plan* p; float* out; int max_iter; float thr; unsigned flags; hipStream_t st;      // as given
+    bool relative, recompute;
+    int soft;
+    float thr0;                  // time-domain level of the opening pass: thr, thr * max|y| (relative, thr0_rel) or none (-1: every sample kept)
+    const unsigned* thr0_rel;
+    unsigned* peak_out;
+};
+}  // namespace
+
+// Argument and flag checks; clears the peaks and the ring of spectrum maxima of the relative threshold.
+static int enhance_begin(FlCall& c, const float* x) {
+    egr_fatllama_plan* p = c.p;
+    EGR_CHECK(p && x && c.out, EGR_ERR_ARG, "null plan/x/out");
+    EGR_CHECK(c.max_iter >= 0, EGR_ERR_ARG, "max_iter=%d < 0", c.max_iter);
+    const bool lin = (c.flags & EGR_FL_INTERP_LINSPACE) != 0;
+    EGR_CHECK(lin || p->factor >= 1, EGR_ERR_ARG, "a plan with an explicit output length (egr_fatllama_plan_create_n) needs EGR_FL_INTERP_LINSPACE");
+    EGR_CHECK(!(lin && (c.flags & EGR_FL_ZERO_STUFF)), EGR_ERR_ARG, "EGR_FL_INTERP_LINSPACE and EGR_FL_ZERO_STUFF exclude each other");
     const int C = p->C;
-    const long long M = p->sp.M, N = p->sp.N;
-    const bool three = p->sp.levels == 3;
-    ColP A = p->colA, B = p->colB;
-    RowP R = p->row;
-    R.thr2 = thr * thr;
-    R.thr = thr;
-    R.soft = (flags & EGR_FL_THR_SOFT) ? 1 : 0;
-    const bool relative = (flags & EGR_FL_THR_RELATIVE) != 0;
-    const bool no_init = (flags & EGR_FL_NO_INIT_THR) != 0;
-    unsigned* peak_in = p->d_peaks;
-    unsigned* peak_out = p->d_peaks + C;
-    unsigned* peak_y = p->d_peaks + 2 * C;
-    EGR_HIP(hipMemsetAsync(p->d_peaks, 0, 3 * C * sizeof(unsigned), st));
+    c.soft = (c.flags & EGR_FL_THR_SOFT) ? 1 : 0;
+    c.relative = (c.flags & EGR_FL_THR_RELATIVE) != 0;
     // EGR_FL_THR_RECOMPUTE: the maximum of every iteration's spectrum from a read-only pass of its own (rounds 1-5) instead of the
     // one the previous iteration's hook carried forward; the two agree to the round-off of one float32 transform pair
-    const bool recompute = relative && (flags & EGR_FL_THR_RECOMPUTE) != 0;
-    if (relative && max_iter > 0) {
+    c.recompute = c.relative && (c.flags & EGR_FL_THR_RECOMPUTE) != 0;
+    const bool no_init = (c.flags & EGR_FL_NO_INIT_THR) != 0;
+    c.thr0 = no_init ? -1.0f : c.thr;
+    c.thr0_rel = (c.relative && !no_init) ? p->d_peaks + 2 * C : nullptr;
+    c.peak_out = p->d_peaks + C;
+    EGR_HIP(hipMemsetAsync(p->d_peaks, 0, 3 * C * sizeof(unsigned), c.st));
+    if (c.relative && c.max_iter > 0) {
         // a ring of EGR_FL_MAX_RING slots (fl_max2_*): iteration it reads slot it, leaves the next maximum in slot it + 1 and clears
         // slot it + 2 (mod ring).  The legacy chirp-z loop keeps one slot per iteration.
-        const size_t nslots = (p->bluestein && !p->pz) ? (size_t)max_iter : (size_t)EGR_FL_MAX_RING;
+        const size_t nslots = (p->bluestein && !p->pz) ? (size_t)c.max_iter : (size_t)EGR_FL_MAX_RING;
         const size_t need = nslots * C * EGR_FL_MAX_STRIDE;
         if (need > p->max2_cap) {
-            if (p->gexec) { EGR_HIP(hipDeviceSynchronize()); EGR_HIP(hipGraphExecDestroy(p->gexec)); p->gexec = nullptr; }      // it recorded the old ring
+            const int rc = fl_drop_graph(p);      // it recorded the old ring
+            if (rc) return rc;
             if (p->d_max2) { EGR_HIP(hipFree(p->d_max2)); p->d_max2 = nullptr; p->max2_cap = 0; }
             EGR_HIP(hipMalloc((void**)&p->d_max2, need * sizeof(unsigned)));
             p->max2_cap = need;
         }
-        EGR_HIP(hipMemsetAsync(p->d_max2, 0, need * sizeof(unsigned), st));
+        EGR_HIP(hipMemsetAsync(p->d_max2, 0, need * sizeof(unsigned), c.st));
     }
-    auto max2_slot = [&](int it, int ch0) { return p->d_max2 + ((size_t)(it % EGR_FL_MAX_RING) * C + ch0) * EGR_FL_MAX_STRIDE; };
-    // time-domain level of the opening pass: thr, thr * max|y| (relative) or none (every sample kept)
-    const float thr0 = no_init ? -1.0f : thr;
-    const unsigned* thr0_rel = (relative && !no_init) ? peak_y : nullptr;
-    {
-        const int nb = (int)((p->n_in + 255) / 256 < 2048 ? (p->n_in + 255) / 256 : 2048);
-        const int lin = (flags & EGR_FL_INTERP_LINSPACE) ? 1 : 0;
-        EGR_CHECK(lin || p->factor >= 1, EGR_ERR_ARG, "a plan with an explicit output length (egr_fatllama_plan_create_n) needs EGR_FL_INTERP_LINSPACE");
-        EGR_CHECK(!(lin && (flags & EGR_FL_ZERO_STUFF)), EGR_ERR_ARG, "EGR_FL_INTERP_LINSPACE and EGR_FL_ZERO_STUFF exclude each other");
-        hipLaunchKernelGGL(k_prepare, dim3(nb, C), dim3(256), 0, st, x, out, (long long)p->n_in, p->factor > 0 ? p->factor : 1,
-                           (flags & EGR_FL_PCM_IN) ? 1 : 0, (flags & EGR_FL_ZERO_STUFF) ? 1 : 0, peak_in, peak_y, lin, (long long)p->n_out);
+    return EGR_OK;
+}
+
+// x -> y in `out` (PCM rounding, up-rating), peaks of x and y
+static void launch_prepare(const FlCall& c, const float* x) {
+    egr_fatllama_plan* p = c.p;
+    hipLaunchKernelGGL(k_prepare, dim3(fl_grid(p->n_in), p->C), dim3(256), 0, c.st, x, c.out, (long long)p->n_in, p->factor > 0 ? p->factor : 1,
+                       (c.flags & EGR_FL_PCM_IN) ? 1 : 0, (c.flags & EGR_FL_ZERO_STUFF) ? 1 : 0, p->d_peaks, p->d_peaks + 2 * p->C,
+                       (c.flags & EGR_FL_INTERP_LINSPACE) ? 1 : 0, (long long)p->n_out);
+}
+
+// max_iter == 0: the time-domain threshold alone
+static int loop_none(const FlCall& c) {
+    const long long Nr = (long long)c.p->n_out;
+    hipLaunchKernelGGL(k_noiter, dim3(fl_grid(Nr), c.p->C), dim3(256), 0, c.st, c.out, Nr, c.thr0, c.peak_out, c.thr0_rel);
+    return EGR_OK;
+}
+
+// The convolution with the chirp of the legacy chirp-z passes: row FFT, times Bhat, inverse row FFT (inside the inner column pass
+// of a three-level plan) over all C states.
+static void legacy_conv(egr_fatllama_plan* p, dim3 blk, float thr, float* out, unsigned* pk, hipStream_t st) {
+    const long long P = p->sp.M, N = p->sp.N;
+    const bool three = p->sp.levels == 3;
+    const ColP& B = p->colB;
+    const RowP& R = p->row;
+    const dim3 gB(8 * B.tiles_per_xcd, p->C * (three ? B.nplanes : 1)), grc((R.R + EGR_FL_CONV_ROWS - 1) / EGR_FL_CONV_ROWS, p->C);
+    const size_t lb = EGR_LDS(p->sp.lds_colb);
+    if (three) hipLaunchKernelGGL(k_col<4>, gB, blk, lb, st, B, P, N, thr, p->d_work, out, pk);
+    hipLaunchKernelGGL(k_rowconv<true>, grc, dim3(EGR_FL_CONV_THREADS), rowconv_lds(R.L), st, R.f, R.L, R.R, R.tw, (const cplx*)p->d_bhat, 1.0f, P, p->d_work);
+    if (three) hipLaunchKernelGGL(k_col<3>, gB, blk, lb, st, B, P, N, thr, p->d_work, out, pk);
+}
+
+// The legacy full-complex chirp-z loop: one state of P >= 2N - 1 points per channel, one stream, plain launches.
+static int loop_legacy_chirpz(const FlCall& c) {
+    egr_fatllama_plan* p = c.p;
+    const int C = p->C;
+    hipStream_t st = c.st; float* out = c.out; unsigned* peak_out = c.peak_out;
+    const float thr = c.thr, thr2 = thr * thr;
+    const long long P = p->sp.M;
+    const ColP& A = p->colA;
+    ChirpP cp = p->chirp;
+    cp.soft = c.soft;
+    const dim3 gA(8 * A.tiles_per_xcd, C), blk(blue_threads());
+    const size_t lc = EGR_LDS(p->sp.lds_col);
+    auto conv = [&]() { legacy_conv(p, blk, thr, out, peak_out, st); };
+    hipLaunchKernelGGL((k_colz<0, 0>), gA, blk, lc, st, A, cp, P, c.thr0, thr2, p->d_work, out, peak_out, c.thr0_rel);
+    for (int it = 0; it < c.max_iter; ++it) {
+        conv();
+        if (c.relative) {                 // this iteration's spectrum maximum first (same pass, no write-back)
+            cp.max2_out = p->d_max2 + (size_t)it * C * EGR_FL_MAX_STRIDE;
+            hipLaunchKernelGGL((k_colz<3, 1>), gA, blk, lc, st, A, cp, P, thr, thr2, p->d_work, out, peak_out, (const unsigned*)nullptr);
+            cp.max2 = cp.max2_out;
+        }
+        hipLaunchKernelGGL((k_colz<1, 1>), gA, blk, lc, st, A, cp, P, thr, thr2, p->d_work, out, peak_out);
+        conv();
+        if (it + 1 < c.max_iter)
+            hipLaunchKernelGGL((k_colz<1, 2>), gA, blk, lc, st, A, cp, P, thr, thr2, p->d_work, out, peak_out);
     }
-    const dim3 gA(8 * A.tiles_per_xcd, C), gB(8 * B.tiles_per_xcd, C * (three ? B.nplanes : 1)), grow(R.R / 2 + 1, C),
-        blk(p->bluestein ? blue_threads() : p->threads), blk256(256);
+    hipLaunchKernelGGL((k_colz<2, 0>), gA, blk, lc, st, A, cp, P, thr, thr2, p->d_work, out, peak_out);
+    return EGR_OK;
+}
+
+// The packed-real loop: two channel groups as concurrent pipelines (fl_run_pipelines), one group's k_row overlapping the
+// other's k_col.
+static int loop_packed(const FlCall& c) {
+    egr_fatllama_plan* p = c.p;
+    const int C = p->C, max_iter = c.max_iter;
+    const long long M = p->sp.M, N = p->sp.N;
+    const bool three = p->sp.levels == 3, relative = c.relative, recompute = c.recompute;
+    const float thr = c.thr;
+    const ColP &A = p->colA, &B = p->colB;
+    RowP R = p->row;
+    R.thr2 = thr * thr;
+    R.thr = thr;
+    R.soft = c.soft;
+    const dim3 gA(8 * A.tiles_per_xcd, C), gB(8 * B.tiles_per_xcd, C * (three ? B.nplanes : 1)), grow(R.R / 2 + 1, C), blk(p->threads);
     const size_t lc = EGR_LDS(p->sp.lds_col), lb = EGR_LDS(p->sp.lds_colb), lr = EGR_LDS(p->sp.lds_row);
+    const int ngroups = (p->nstreams == 2 && C >= 2) ? 2 : 1;
+    // the in-place schedules need one thread per butterfly (288 / 512 row, 200 column butterflies per stage): 512 threads
+    const bool sched_ok = p->threads == 512;
+    const dim3 blkc(EGR_FL_COL_THREADS);      // the scheduled column kernels' own workgroup size
+    const bool rs1 = p->row_sched == 1 && sched_ok, cs2 = p->col_sched == 2 && sched_ok && !three;
+    // the two-barrier kernels serve the default hook (hard threshold against an absolute level) and the middle column pass
+    const WlRowEntry* wle = (const WlRowEntry*)p->wl_row_entry;
+    const bool wl_variant = relative || R.soft != 0;          // k_row_wl<.., 1>: level from the iteration's maximum and / or soft shrink
+    const bool wlr = p->wl_row != 0 && wle, wlc = p->wl_col != 0;
+    const size_t lrs = row_sched_lds(R.L), lcs = col_sched_lds(p);
+    auto max2_slot = [&](int it, int ch0) { return p->d_max2 + ((size_t)(it % EGR_FL_MAX_RING) * C + ch0) * EGR_FL_MAX_STRIDE; };
     size_t slot = 0;
-    if (max_iter == 0) {
-        const long long Nr = (long long)p->n_out;
-        const int nb = (int)((Nr + 255) / 256 < 2048 ? (Nr + 255) / 256 : 2048);
-        hipLaunchKernelGGL(k_noiter, dim3(nb, C), blk256, 0, st, out, Nr, thr0, peak_out, thr0_rel);
-    } else if (p->pz) {
-        const int rc = pz_loop(p, out, max_iter, thr, thr0, thr0_rel, flags, peak_out, st);
-        if (rc) return rc;
-    } else if (p->bluestein) {
-        ChirpP cp = p->chirp;
-        cp.soft = R.soft;
-        const long long P = M;
-        const dim3 grc((R.R + EGR_FL_CONV_ROWS - 1) / EGR_FL_CONV_ROWS, C);
-        const float thr2 = thr * thr;
-        auto conv = [&]() {
-            if (three) hipLaunchKernelGGL(k_col<4>, gB, blk, lb, st, B, P, N, thr, p->d_work, out, peak_out);
-            hipLaunchKernelGGL(k_rowconv<true>, grc, dim3(EGR_FL_CONV_THREADS), rowconv_lds(R.L), st, R.f, R.L, R.R, R.tw, (const cplx*)p->d_bhat, 1.0f, P,
-                               p->d_work);
-            if (three) hipLaunchKernelGGL(k_col<3>, gB, blk, lb, st, B, P, N, thr, p->d_work, out, peak_out);
+    // One group's launches for iterations [it0, it1); `first` adds the opening time-domain pass, `last` the closing one.
+    auto run_group = [&](hipStream_t s0, int g, int it0, int it1, bool first, bool last, bool prof) {
+        const int c0 = g == 0 ? 0 : C / 2, cn = ngroups == 1 ? C : (g == 0 ? C / 2 : C - C / 2);
+        hipStream_t sg = g == 0 ? s0 : p->side;
+        cplx* wk = p->d_work + (size_t)c0 * M;
+        float* og = c.out + (size_t)c0 * N;
+        unsigned* pk = c.peak_out + c0;
+        const dim3 gAg(gA.x, cn), gBg(gB.x, cn * (three ? B.nplanes : 1)), growg(grow.x, cn);
+        auto inner = [&](bool forward) {          // the inner column pass of a three-level plan
+            if (p->wl_inner) wl_launch_inner(p->wl_colB, p->wl_it, forward, M, wk, cn, sg);
+            else if (forward) hipLaunchKernelGGL(k_col<4>, gBg, blk, lb, sg, B, M, N, thr, wk, og, pk);
+            else hipLaunchKernelGGL(k_col<3>, gBg, blk, lb, sg, B, M, N, thr, wk, og, pk);
         };
-        hipLaunchKernelGGL((k_colz<0, 0>), gA, blk, lc, st, A, cp, P, thr0, thr2, p->d_work, out, peak_out, thr0_rel);
-        for (int it = 0; it < max_iter; ++it) {
-            conv();
-            if (relative) {                 // this iteration's spectrum maximum first (same pass, no write-back)
-                cp.max2_out = p->d_max2 + (size_t)it * C * EGR_FL_MAX_STRIDE;
-                hipLaunchKernelGGL((k_colz<3, 1>), gA, blk, lc, st, A, cp, P, thr, thr2, p->d_work, out, peak_out, (const unsigned*)nullptr);
-                cp.max2 = cp.max2_out;
+        if (first) {
+            if (cs2) hipLaunchKernelGGL((k_col<0, 2>), gAg, blkc, lcs, sg, A, M, N, c.thr0, wk, og, pk, c.thr0_rel ? c.thr0_rel + c0 : nullptr);
+            else hipLaunchKernelGGL(k_col<0>, gAg, blk, lc, sg, A, M, N, c.thr0, wk, og, pk, c.thr0_rel ? c.thr0_rel + c0 : nullptr);
+            if (three) inner(true);
+        }
+        // the spectrum maximum by a pass of its own (forward row transforms + split, no write-back): only the FIRST iteration
+        // needs it -- d0 = T0(y) is not the image of a shrunk spectrum -- every later one finds the maximum its predecessor's hook left
+        auto max_pass = [&](int it) {
+            RowP Rm = R;
+            Rm.max2_out = max2_slot(it, c0);
+            if (wlr) hipLaunchKernelGGL(wle->fn_max, growg, dim3(wle->threads), EGR_LDS(wle->lds), sg, Rm, p->wl_rt, M, wk);
+            else if (rs1) hipLaunchKernelGGL((k_row<true, 1>), growg, blk, lrs, sg, Rm, M, wk);
+            else hipLaunchKernelGGL(k_row<true>, growg, blk, lr, sg, Rm, M, wk);
+        };
+        if (first && relative) max_pass(0);
+        for (int it = it0; it < it1; ++it) {
+            RowP Rg = R;
+            if (relative) {
+                if (recompute && it > 0) max_pass(it);
+                Rg.max2 = max2_slot(it, c0);
+                Rg.max2_next = recompute ? nullptr : max2_slot(it + 1, c0);
+                Rg.max2_zero = max2_slot(it + 2, c0);
             }
-            hipLaunchKernelGGL((k_colz<1, 1>), gA, blk, lc, st, A, cp, P, thr, thr2, p->d_work, out, peak_out);
-            conv();
-            if (it + 1 < max_iter)
-                hipLaunchKernelGGL((k_colz<1, 2>), gA, blk, lc, st, A, cp, P, thr, thr2, p->d_work, out, peak_out);
-        }
-        hipLaunchKernelGGL((k_colz<2, 0>), gA, blk, lc, st, A, cp, P, thr, thr2, p->d_work, out, peak_out);
-    } else {
-        // The channels are independent until k_finalize.  Each loop kernel alone fills barely more than one wave of
-        // workgroups, so two channel groups run as concurrent pipelines on two streams (fork/join by events) and one
-        // group's k_row overlaps the other's k_col.
-        const int ngroups = (p->nstreams == 2 && C >= 2) ? 2 : 1;
-        // the in-place schedules need one thread per butterfly (288 / 512 row, 200 column butterflies per stage): 512 threads
-        const bool sched_ok = p->threads == 512;
-        const dim3 blkc(EGR_FL_COL_THREADS);      // the scheduled column kernels' own workgroup size
-        const bool rs1 = p->row_sched == 1 && sched_ok, cs2 = p->col_sched == 2 && sched_ok && !three;
-        // the two-barrier kernels serve the default hook (hard threshold against an absolute level) and the middle column pass
-        const WlRowEntry* wle = (const WlRowEntry*)p->wl_row_entry;
-        const bool wl_variant = relative || R.soft != 0;          // k_row_wl<.., 1>: level from the iteration's maximum and / or soft shrink
-        const bool wlr = p->wl_row != 0 && wle, wlc = p->wl_col != 0;
-        // no ping-pong buffer; the row kernel's two rows are padded by one element per 2^EGR_FL_ROW_PAD
-        const size_t lrs = EGR_LDS((size_t)2 * (R.L + (EGR_FL_ROW_PAD ? R.L >> EGR_FL_ROW_PAD : 0)) * sizeof(cplx));
-        const size_t lcs = EGR_LDS(p->sp.lds_col / 2);
-        if (ngroups == 2 && !p->side) {
-            EGR_HIP(hipStreamCreateWithFlags(&p->side, hipStreamNonBlocking));
-            p->side_owned = 1;
-        }
-        if (ngroups == 2 && !p->ev_fork) {
-            EGR_HIP(hipEventCreateWithFlags(&p->ev_fork, hipEventDisableTiming));
-            EGR_HIP(hipEventCreateWithFlags(&p->ev_join, hipEventDisableTiming));
-        }
-        // One group's launches for iterations [it0, it1); `first` adds the opening time-domain pass, `last` the closing one.
-        auto run_group = [&](hipStream_t s0, int g, int it0, int it1, bool first, bool last, bool prof) {
-            const int c0 = g == 0 ? 0 : C / 2, cn = ngroups == 1 ? C : (g == 0 ? C / 2 : C - C / 2);
-            hipStream_t sg = g == 0 ? s0 : p->side;
-            cplx* wk = p->d_work + (size_t)c0 * M;
-            float* og = out + (size_t)c0 * N;
-            unsigned* pk = peak_out + c0;
-            const dim3 gAg(gA.x, cn), gBg(gB.x, cn * (three ? B.nplanes : 1)), growg(grow.x, cn);
-            if (first) {
-                if (cs2) hipLaunchKernelGGL((k_col<0, 2>), gAg, blkc, lcs, sg, A, M, N, thr0, wk, og, pk, thr0_rel ? thr0_rel + c0 : nullptr);
-                else hipLaunchKernelGGL(k_col<0>, gAg, blk, lc, sg, A, M, N, thr0, wk, og, pk, thr0_rel ? thr0_rel + c0 : nullptr);
-                if (three) {
-                    if (p->wl_inner) wl_launch_inner(p->wl_colB, p->wl_it, true, M, wk, cn, sg);
-                    else hipLaunchKernelGGL(k_col<4>, gBg, blk, lb, sg, B, M, N, thr, wk, og, pk);
-                }
+            if (prof) fl_prof_begin(p, 0, sg, &slot);
+            if (wlr && wl_variant) hipLaunchKernelGGL(wle->fn_variant, growg, dim3(wle->threads), EGR_LDS(wle->lds), sg, Rg, p->wl_rt, M, wk);
+            else if (wlr) hipLaunchKernelGGL(wle->fn, growg, dim3(wle->threads), EGR_LDS(wle->lds), sg, Rg, p->wl_rt, M, wk);
+            else if (rs1) hipLaunchKernelGGL((k_row<false, 1>), growg, blk, lrs, sg, Rg, M, wk);
+            else hipLaunchKernelGGL(k_row<false>, growg, blk, lr, sg, Rg, M, wk);
+            if (prof) fl_prof_end(p, sg, &slot);
+            if (three) {
+                if (prof) fl_prof_begin(p, 2, sg, &slot);
+                inner(false);
+                if (prof) fl_prof_end(p, sg, &slot);
             }
-            // the spectrum maximum by a pass of its own (forward row transforms + split, no write-back): only the FIRST iteration
-            // needs it -- d0 = T0(y) is not the image of a shrunk spectrum -- every later one finds the maximum its predecessor's hook left
-            auto max_pass = [&](int it) {
-                RowP Rm = R;
-                Rm.max2_out = max2_slot(it, c0);
-                if (wlr) hipLaunchKernelGGL(wle->fn_max, growg, dim3(wle->threads), EGR_LDS(wle->lds), sg, Rm, p->wl_rt, M, wk);
-                else if (rs1) hipLaunchKernelGGL((k_row<true, 1>), growg, blk, lrs, sg, Rm, M, wk);
-                else hipLaunchKernelGGL(k_row<true>, growg, blk, lr, sg, Rm, M, wk);
-            };
-            if (first && relative) max_pass(0);
-            for (int it = it0; it < it1; ++it) {
-                RowP Rg = R;
-                if (relative) {
-                    if (recompute && it > 0) max_pass(it);
-                    Rg.max2 = max2_slot(it, c0);
-                    Rg.max2_next = recompute ? nullptr : max2_slot(it + 1, c0);
-                    Rg.max2_zero = max2_slot(it + 2, c0);
-                }
-                if (prof) fl_prof_begin(p, 0, sg, &slot);
-                if (wlr && wl_variant) hipLaunchKernelGGL(wle->fn_variant, growg, dim3(wle->threads), EGR_LDS(wle->lds), sg, Rg, p->wl_rt, M, wk);
-                else if (wlr) hipLaunchKernelGGL(wle->fn, growg, dim3(wle->threads), EGR_LDS(wle->lds), sg, Rg, p->wl_rt, M, wk);
-                else if (rs1) hipLaunchKernelGGL((k_row<false, 1>), growg, blk, lrs, sg, Rg, M, wk);
-                else hipLaunchKernelGGL(k_row<false>, growg, blk, lr, sg, Rg, M, wk);
+            if (it + 1 < max_iter) {
+                if (prof) fl_prof_begin(p, 1, sg, &slot);
+                if (wlc) wl_launch_col(A, p->wl_ct, M, wk, cn, sg);
+                else if (cs2) hipLaunchKernelGGL((k_col<1, 2>), gAg, blkc, lcs, sg, A, M, N, thr, wk, og, pk, (const unsigned*)nullptr);
+                else hipLaunchKernelGGL(k_col<1>, gAg, blk, lc, sg, A, M, N, thr, wk, og, pk);
                 if (prof) fl_prof_end(p, sg, &slot);
                 if (three) {
                     if (prof) fl_prof_begin(p, 2, sg, &slot);
-                    if (p->wl_inner) wl_launch_inner(p->wl_colB, p->wl_it, false, M, wk, cn, sg);
-                    else hipLaunchKernelGGL(k_col<3>, gBg, blk, lb, sg, B, M, N, thr, wk, og, pk);
+                    inner(true);
                     if (prof) fl_prof_end(p, sg, &slot);
                 }
-                if (it + 1 < max_iter) {
-                    if (prof) fl_prof_begin(p, 1, sg, &slot);
-                    if (wlc) wl_launch_col(A, p->wl_ct, M, wk, cn, sg);
-                    else if (cs2) hipLaunchKernelGGL((k_col<1, 2>), gAg, blkc, lcs, sg, A, M, N, thr, wk, og, pk, (const unsigned*)nullptr);
-                    else hipLaunchKernelGGL(k_col<1>, gAg, blk, lc, sg, A, M, N, thr, wk, og, pk);
-                    if (prof) fl_prof_end(p, sg, &slot);
-                    if (three) {
-                        if (prof) fl_prof_begin(p, 2, sg, &slot);
-                        if (p->wl_inner) wl_launch_inner(p->wl_colB, p->wl_it, true, M, wk, cn, sg);
-                        else hipLaunchKernelGGL(k_col<4>, gBg, blk, lb, sg, B, M, N, thr, wk, og, pk);
-                        if (prof) fl_prof_end(p, sg, &slot);
-                    }
-                }
             }
-            if (last) {
-                if (cs2) hipLaunchKernelGGL((k_col<2, 2>), gAg, blkc, lcs, sg, A, M, N, thr, wk, og, pk, (const unsigned*)nullptr);
-                else hipLaunchKernelGGL(k_col<2>, gAg, blk, lc, sg, A, M, N, thr, wk, og, pk);
-            }
-        };
-        auto fork = [&](hipStream_t s0) -> int {
-            if (ngroups == 2) {
-                EGR_HIP(hipEventRecord(p->ev_fork, s0));
-                EGR_HIP(hipStreamWaitEvent(p->side, p->ev_fork, 0));
-            }
-            return EGR_OK;
-        };
-        auto join = [&](hipStream_t s0) -> int {
-            if (ngroups == 2) {
-                EGR_HIP(hipEventRecord(p->ev_join, p->side));
-                EGR_HIP(hipStreamWaitEvent(s0, p->ev_join, 0));
-            }
-            return EGR_OK;
-        };
-        // The loop body is the same pair of launches every iteration: CH iterations of both pipelines are captured once
-        // into a hipGraph and replayed (inter-kernel gaps of ~8 us on the streams shrink to the graph's ~1 us); the
-        // executable graph is kept while (out, threshold, geometry) stay the same.  Profiling runs use plain launches.
-        constexpr int CH = 25;
-        const bool profiling = p->profiling != 0;
-        static_assert(CH == EGR_FL_MAX_RING, "the captured iterations address the ring of maxima by iteration mod CH");
-        const int n_graph = (!profiling && p->use_graph && !recompute && max_iter > 2 * CH) ? (max_iter - 1) / CH : 0;
-        const int g_kind = R.soft | (relative ? 2 : 0);
-        int rc = fork(st);
-        if (rc) return rc;
-        for (int g = 0; g < ngroups; ++g) run_group(st, g, 0, 0, true, false, false);
-        if (n_graph > 0) {
-            rc = join(st);
-            if (rc) return rc;
-            // The captured middle iterations touch the plan's own state only (the row pass and the middle column pass never see
-            // `out`), so the executable graph is keyed by (threshold, pipelines, hook kind) and survives calls with other buffers.
-            // An executable graph is never destroyed while a launch of it may still be in flight (calls return asynchronously):
-            // the device is drained first -- a re-capture is a rare, millisecond-scale event anyway.
-            if (!(p->gexec && p->g_thr == thr && p->g_groups == ngroups && p->g_iter_odd == g_kind)) {
-                if (p->gexec) { EGR_HIP(hipDeviceSynchronize()); EGR_HIP(hipGraphExecDestroy(p->gexec)); p->gexec = nullptr; }
-                hipGraph_t graph = nullptr;
-                // captured on a private stream (the caller's may be the legacy default stream, which cannot capture)
-                if (!p->cap) EGR_HIP(hipStreamCreateWithFlags(&p->cap, hipStreamNonBlocking));
-                EGR_HIP(hipStreamBeginCapture(p->cap, hipStreamCaptureModeThreadLocal));
-                rc = fork(p->cap);
-                // iterations 0..CH-1 of a run with more than CH + 1 iterations: every one is a "middle" iteration
-                if (!rc) for (int g = 0; g < ngroups; ++g) run_group(p->cap, g, 0, CH, false, false, false);
-                if (!rc) rc = join(p->cap);
-                hipError_t ce = hipStreamEndCapture(p->cap, &graph);
-                if (rc || ce != hipSuccess) {          // leave no half-captured state behind: the next call starts from scratch
-                    if (graph) hipGraphDestroy(graph);
-                    hipStreamDestroy(p->cap);
-                    p->cap = nullptr;
-                    if (rc) return rc;
-                    EGR_HIP(ce);
-                }
-                hipError_t ie = hipGraphInstantiate(&p->gexec, graph, nullptr, nullptr, 0);
-                hipGraphDestroy(graph);
-                if (ie != hipSuccess) { p->gexec = nullptr; EGR_HIP(ie); }
-                p->g_out = out; p->g_thr = thr; p->g_groups = ngroups; p->g_iter_odd = g_kind;
-            }
-            for (int i = 0; i < n_graph; ++i) EGR_HIP(hipGraphLaunch(p->gexec, st));
-            rc = fork(st);
-            if (rc) return rc;
         }
-        for (int g = 0; g < ngroups; ++g) run_group(st, g, n_graph * CH, max_iter, false, true, profiling);
-        rc = join(st);
-        if (rc) return rc;
-    }
-    if ((flags & (EGR_FL_NORMALIZE | EGR_FL_AUTOSCALE | EGR_FL_NODE_POST)) && !(flags & EGR_FL_DEFER_FINALIZE)) {
-        const long long Nr = (long long)p->n_out;
-        const int nb = (int)((Nr + 255) / 256 < 2048 ? (Nr + 255) / 256 : 2048);
-        hipLaunchKernelGGL(k_finalize, dim3(nb, C), blk256, 0, st, out, Nr, C, flags, peak_in, peak_out, (const float*)nullptr, (float*)nullptr);
-    }
+        if (last) {
+            if (cs2) hipLaunchKernelGGL((k_col<2, 2>), gAg, blkc, lcs, sg, A, M, N, thr, wk, og, pk, (const unsigned*)nullptr);
+            else hipLaunchKernelGGL(k_col<2>, gAg, blk, lc, sg, A, M, N, thr, wk, og, pk);
+        }
+    };
+    // every iteration is a middle iteration (the maximum pass of the relative threshold belongs to the opening pass);
+    // EGR_FL_THR_RECOMPUTE uses plain launches
+    return fl_run_pipelines(p, c.st, ngroups, max_iter, 0, !recompute, thr, R.soft | (relative ? 2 : 0), run_group);
+}
+
+extern "C" int egr_fatllama_enhance(egr_fatllama_plan* p, const float* x, float* out, int max_iter, float thr,
+                                    unsigned flags, void* stream) {
+    FlCall c{p, out, max_iter, thr, flags, (hipStream_t)stream};
+    int rc = enhance_begin(c, x);
+    if (rc) return rc;
+    launch_prepare(c, x);
+    rc = max_iter == 0 ? loop_none(c) : p->pz ? pz_loop(p, out, max_iter, thr, c.thr0, c.thr0_rel, flags, c.peak_out, c.st)
+         : p->bluestein ? loop_legacy_chirpz(c) : loop_packed(c);
+    if (rc) return rc;
+    if ((flags & (EGR_FL_NORMALIZE | EGR_FL_AUTOSCALE | EGR_FL_NODE_POST)) && !(flags & EGR_FL_DEFER_FINALIZE))
+        launch_finalize(p, out, flags, nullptr, nullptr, c.st);
     EGR_HIP(hipGetLastError());
     return EGR_OK;
 }
@@ -1582,8 +1577,7 @@ extern "C" int egr_fatllama_enhance(egr_fatllama_plan* p, const float* x, float*
 // write patch / PCM_16 with the all-reduced value.  `flags` as given to enhance.
 extern "C" int egr_fatllama_joint_peak(egr_fatllama_plan* p, unsigned flags, float* joint_dev, void* stream) {
     EGR_CHECK(p && joint_dev, EGR_ERR_ARG, "null plan / joint_dev");
-    hipLaunchKernelGGL(k_finalize, dim3(1, 1), dim3(64), 0, (hipStream_t)stream, (float*)nullptr, 0LL, p->C, flags, p->d_peaks, p->d_peaks + p->C,
-                       (const float*)nullptr, joint_dev);
+    launch_finalize(p, nullptr, flags, nullptr, joint_dev, (hipStream_t)stream);
     EGR_HIP(hipGetLastError());
     return EGR_OK;
 }
@@ -1591,9 +1585,7 @@ extern "C" int egr_fatllama_joint_peak(egr_fatllama_plan* p, unsigned flags, flo
 extern "C" int egr_fatllama_finalize(egr_fatllama_plan* p, float* out, unsigned flags, const float* joint_dev, void* stream) {
     EGR_CHECK(p && out, EGR_ERR_ARG, "null plan / out");
     if (!(flags & (EGR_FL_NORMALIZE | EGR_FL_AUTOSCALE | EGR_FL_NODE_POST))) return EGR_OK;
-    const long long Nr = (long long)p->n_out;
-    const int nb = (int)((Nr + 255) / 256 < 2048 ? (Nr + 255) / 256 : 2048);
-    hipLaunchKernelGGL(k_finalize, dim3(nb, p->C), dim3(256), 0, (hipStream_t)stream, out, Nr, p->C, flags, p->d_peaks, p->d_peaks + p->C, joint_dev, (float*)nullptr);
+    launch_finalize(p, out, flags, joint_dev, nullptr, (hipStream_t)stream);
     EGR_HIP(hipGetLastError());
     return EGR_OK;
 }
@@ -1607,8 +1599,7 @@ extern "C" int egr_fatllama_set_side_stream(egr_fatllama_plan* p, void* stream) 
     if (p->side && p->side_owned) EGR_HIP(hipStreamDestroy(p->side));
     p->side = (hipStream_t)stream;
     p->side_owned = 0;
-    if (p->gexec) { EGR_HIP(hipDeviceSynchronize()); EGR_HIP(hipGraphExecDestroy(p->gexec)); p->gexec = nullptr; }
-    return EGR_OK;
+    return fl_drop_graph(p);
 }
 
 // Replay of the loop from a captured hipGraph on / off (default on unless EGR_FL_GRAPH=0).  The two ways give identical bits;
@@ -1631,27 +1622,6 @@ extern "C" int egr_fatllama_last_peaks(egr_fatllama_plan* p, float* host_pin, fl
     return EGR_OK;
 }
 
-extern "C" int egr_fatllama_kernel_times(egr_fatllama_plan* p, double* row_ms_avg, double* col_ms_avg,
-                                         int64_t* row_launches, int64_t* col_launches) {
-    EGR_CHECK(p != nullptr, EGR_ERR_ARG, "plan is null");
-    double sum[3] = {0, 0, 0};
-    int64_t cnt[3] = {0, 0, 0};
-    EGR_HIP(hipDeviceSynchronize());
-    for (size_t i = 0; i + 1 < p->ev.size(); i += 2) {
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, p->ev[i], p->ev[i + 1]) != hipSuccess) continue;
-        const int k = p->ev_kind[i / 2];
-        sum[k] += ms;
-        cnt[k] += 1;
-    }
-    // the inner column pass (3-level plans) is reported together with the outer one
-    if (row_ms_avg) *row_ms_avg = cnt[0] ? sum[0] / cnt[0] : 0.0;
-    if (col_ms_avg) *col_ms_avg = (cnt[1] + cnt[2]) ? (sum[1] + sum[2]) / (cnt[1] + cnt[2]) : 0.0;
-    if (row_launches) *row_launches = cnt[0];
-    if (col_launches) *col_launches = cnt[1] + cnt[2];
-    return EGR_OK;
-}
-
 extern "C" int egr_fatllama_kernel_times3(egr_fatllama_plan* p, double ms_avg[3], int64_t launches[3]) {
     EGR_CHECK(p && ms_avg && launches, EGR_ERR_ARG, "null argument");
     double sum[3] = {0, 0, 0};
@@ -1669,6 +1639,21 @@ extern "C" int egr_fatllama_kernel_times3(egr_fatllama_plan* p, double ms_avg[3]
     return EGR_OK;
 }
 
+// The same averages with the inner column pass (3-level plans) reported together with the outer one.
+extern "C" int egr_fatllama_kernel_times(egr_fatllama_plan* p, double* row_ms_avg, double* col_ms_avg,
+                                         int64_t* row_launches, int64_t* col_launches) {
+    EGR_CHECK(p != nullptr, EGR_ERR_ARG, "plan is null");
+    double ms[3];
+    int64_t cnt[3];
+    if (int rc = egr_fatllama_kernel_times3(p, ms, cnt)) return rc;
+    const int64_t ncol = cnt[1] + cnt[2];
+    if (row_ms_avg) *row_ms_avg = ms[0];
+    if (col_ms_avg) *col_ms_avg = ncol ? (ms[1] * cnt[1] + ms[2] * cnt[2]) / ncol : 0.0;
+    if (row_launches) *row_launches = cnt[0];
+    if (col_launches) *col_launches = ncol;
+    return EGR_OK;
+}
+
 // inner column pass of a three-level plan over `nstates` consecutive states (used by the chirp-z loops around their row pass)
 void fl_launch_inner(egr_fatllama_plan* p, bool forward, cplx* work, int nstates, hipStream_t st) {
     const ColP& B = p->colB;
@@ -1678,25 +1663,30 @@ void fl_launch_inner(egr_fatllama_plan* p, bool forward, cplx* work, int nstates
     else hipLaunchKernelGGL(k_col<3>, gB, blk, EGR_LDS(p->sp.lds_colb), st, B, M, N, 0.f, work, (float*)nullptr, (unsigned*)nullptr);
 }
 
+// One forward transform, the row pass with the hook `R` selects, one inverse, on the run-time-schedule kernels: src -> dst ([C][N] reals
+// each; src is only read, by the MODE 0 pass).
+static void launch_single_pass(egr_fatllama_plan* p, const RowP& R, const float* src, float* dst, hipStream_t st) {
+    const int C = p->C;
+    const long long M = p->sp.M, N = p->sp.N;
+    const bool three = p->sp.levels == 3;
+    const ColP &A = p->colA, &B = p->colB;
+    const dim3 gA(8 * A.tiles_per_xcd, C), gB(8 * B.tiles_per_xcd, C * (three ? B.nplanes : 1)), grow(R.R / 2 + 1, C), blk(256);
+    const size_t lc = EGR_LDS(p->sp.lds_col), lb = EGR_LDS(p->sp.lds_colb), lr = EGR_LDS(p->sp.lds_row);
+    hipLaunchKernelGGL(k_col<0>, gA, blk, lc, st, A, M, N, -1.0f, p->d_work, const_cast<float*>(src), (unsigned*)nullptr);
+    if (three) hipLaunchKernelGGL(k_col<4>, gB, blk, lb, st, B, M, N, 0.f, p->d_work, dst, (unsigned*)nullptr);
+    hipLaunchKernelGGL(k_row<false>, grow, blk, lr, st, R, M, p->d_work);
+    if (three) hipLaunchKernelGGL(k_col<3>, gB, blk, lb, st, B, M, N, 0.f, p->d_work, dst, (unsigned*)nullptr);
+    hipLaunchKernelGGL(k_col<5>, gA, blk, lc, st, A, M, N, 0.f, p->d_work, dst, (unsigned*)nullptr);
+}
+
 // y = irfft(rfft(x) * gain): one forward transform, a real per-bin gain, one inverse, on the plan's passes.
 extern "C" int egr_spectral_gain(egr_fatllama_plan* p, const float* x, const float* gain, float* y, void* stream) {
     EGR_CHECK(p && x && gain && y, EGR_ERR_ARG, "null argument");
     EGR_CHECK(!p->bluestein && p->factor == 1, EGR_ERR_UNSUPPORTED, "spectral gain needs a packed-real plan with factor 1");
-    hipStream_t st = (hipStream_t)stream;
-    const int C = p->C;
-    const long long M = p->sp.M, N = p->sp.N;
-    const bool three = p->sp.levels == 3;
-    ColP A = p->colA, B = p->colB;
     RowP R = p->row;
     R.gain = gain;
     R.phat = 0;
-    const dim3 gA(8 * A.tiles_per_xcd, C), gB(8 * B.tiles_per_xcd, C * (three ? B.nplanes : 1)), grow(R.R / 2 + 1, C), blk(256);
-    const size_t lc = EGR_LDS(p->sp.lds_col), lb = EGR_LDS(p->sp.lds_colb), lr = EGR_LDS(p->sp.lds_row);
-    hipLaunchKernelGGL(k_col<0>, gA, blk, lc, st, A, M, N, -1.0f, p->d_work, const_cast<float*>(x), (unsigned*)nullptr);
-    if (three) hipLaunchKernelGGL(k_col<4>, gB, blk, lb, st, B, M, N, 0.f, p->d_work, y, (unsigned*)nullptr);
-    hipLaunchKernelGGL(k_row<false>, grow, blk, lr, st, R, M, p->d_work);
-    if (three) hipLaunchKernelGGL(k_col<3>, gB, blk, lb, st, B, M, N, 0.f, p->d_work, y, (unsigned*)nullptr);
-    hipLaunchKernelGGL(k_col<5>, gA, blk, lc, st, A, M, N, 0.f, p->d_work, y, (unsigned*)nullptr);
+    launch_single_pass(p, R, x, y, (hipStream_t)stream);
     EGR_HIP(hipGetLastError());
     return EGR_OK;
 }
@@ -1709,39 +1699,27 @@ extern "C" int egr_band_filter(egr_fatllama_plan* p, const float* x, int64_t ban
     EGR_CHECK(p->factor == 1, EGR_ERR_UNSUPPORTED, "band filter needs a plan with factor 1");
     hipStream_t st = (hipStream_t)stream;
     if (p->pz) return pz_band_filter(p, x, band_lo, y, st);
-    const int C = p->C;
-    const long long M = p->sp.M, N = p->sp.N;
-    const bool three = p->sp.levels == 3;
-    ColP A = p->colA, B = p->colB;
     RowP R = p->row;
     R.gain = nullptr; R.phat = 0; R.band = 1; R.band_lo = band_lo;
-    const dim3 gA(8 * A.tiles_per_xcd, C), gB(8 * B.tiles_per_xcd, C * (three ? B.nplanes : 1)), blk(256);
-    const size_t lc = EGR_LDS(p->sp.lds_col), lb = EGR_LDS(p->sp.lds_colb), lr = EGR_LDS(p->sp.lds_row);
-    float* xs = const_cast<float*>(x);          // read only (MODE 0 passes)
-    if (p->bluestein) {
+    if (!p->bluestein) {
+        launch_single_pass(p, R, x, y, st);
+    } else {
+        const int C = p->C;
+        const long long P = p->sp.M;
+        const ColP& A = p->colA;
+        const dim3 gA(8 * A.tiles_per_xcd, C), blk(256);
+        const size_t lc = EGR_LDS(p->sp.lds_col);
+        float* xs = const_cast<float*>(x);          // read only (MODE 0 pass)
         ChirpP cp = p->chirp;
         cp.band = 1; cp.band_lo = (unsigned long long)band_lo;
-        const long long P = M;
-        const dim3 grc((R.R + EGR_FL_CONV_ROWS - 1) / EGR_FL_CONV_ROWS, C);
         unsigned* pk = p->d_peaks + C;
-        auto conv = [&]() {
-            if (three) hipLaunchKernelGGL(k_col<4>, gB, blk, lb, st, B, P, N, 0.f, p->d_work, y, pk);
-            hipLaunchKernelGGL(k_rowconv<true>, grc, dim3(EGR_FL_CONV_THREADS), rowconv_lds(R.L), st, R.f, R.L, R.R, R.tw, (const cplx*)p->d_bhat, 1.0f, P, p->d_work);
-            if (three) hipLaunchKernelGGL(k_col<3>, gB, blk, lb, st, B, P, N, 0.f, p->d_work, y, pk);
-        };
+        auto conv = [&]() { legacy_conv(p, blk, 0.f, y, pk, st); };
         hipLaunchKernelGGL((k_colz<0, 0>), gA, blk, lc, st, A, cp, P, -1.0f, 0.f, p->d_work, xs, pk);
         conv();
         hipLaunchKernelGGL((k_colz<1, 1>), gA, blk, lc, st, A, cp, P, 0.f, 0.f, p->d_work, y, pk);
         conv();
         EGR_HIP(hipMemsetAsync(y, 0, (size_t)C * cp.N * sizeof(float), st));      // the closing pass adds d to what y holds
         hipLaunchKernelGGL((k_colz<2, 0>), gA, blk, lc, st, A, cp, P, 0.f, 0.f, p->d_work, y, pk);
-    } else {
-        const dim3 grow(R.R / 2 + 1, C);
-        hipLaunchKernelGGL(k_col<0>, gA, blk, lc, st, A, M, N, -1.0f, p->d_work, xs, (unsigned*)nullptr);
-        if (three) hipLaunchKernelGGL(k_col<4>, gB, blk, lb, st, B, M, N, 0.f, p->d_work, y, (unsigned*)nullptr);
-        hipLaunchKernelGGL(k_row<false>, grow, blk, lr, st, R, M, p->d_work);
-        if (three) hipLaunchKernelGGL(k_col<3>, gB, blk, lb, st, B, M, N, 0.f, p->d_work, y, (unsigned*)nullptr);
-        hipLaunchKernelGGL(k_col<5>, gA, blk, lc, st, A, M, N, 0.f, p->d_work, y, (unsigned*)nullptr);
     }
     EGR_HIP(hipGetLastError());
     return EGR_OK;
@@ -1804,12 +1782,10 @@ extern "C" int egr_gcc_phat(egr_fatllama_plan* p, const float* a, int64_t na, co
                             float* work, float* out4, void* stream) {
     EGR_CHECK(p && a && b && work && out4 && na >= 1 && nb >= 1, EGR_ERR_ARG, "null / empty argument");
     EGR_CHECK(!p->bluestein && p->factor == 1 && p->C == 1, EGR_ERR_UNSUPPORTED, "GCC-PHAT needs a one-channel packed-real plan");
-    const long long M = p->sp.M, N = p->sp.N, n = M;
+    const long long n = p->sp.M;
     EGR_CHECK((n & (n - 1)) == 0 && n >= na + nb, EGR_ERR_ARG, "plan length must be 2 n with n = 2^k >= na + nb");
     EGR_CHECK(max_shift >= 0 && max_shift < n / 2 - 1, EGR_ERR_ARG, "max_shift out of range");
     hipStream_t st = (hipStream_t)stream;
-    const bool three = p->sp.levels == 3;
-    ColP A = p->colA, B = p->colB;
     RowP R = p->row;
     R.gain = nullptr;
     R.phat = 1;
@@ -1818,13 +1794,7 @@ extern "C" int egr_gcc_phat(egr_fatllama_plan* p, const float* a, int64_t na, co
     long long nbk = (n + 255) / 256;
     if (nbk > 4096) nbk = 4096;
     hipLaunchKernelGGL(k_phat_pack, dim3((unsigned)nbk), dim3(256), 0, st, a, (long long)na, b, (long long)nb, n, (float2*)z);
-    const dim3 gA(8 * A.tiles_per_xcd, 1), gB(8 * B.tiles_per_xcd, three ? B.nplanes : 1), grow(R.R / 2 + 1, 1), blk(256);
-    const size_t lc = EGR_LDS(p->sp.lds_col), lb = EGR_LDS(p->sp.lds_colb), lr = EGR_LDS(p->sp.lds_row);
-    hipLaunchKernelGGL(k_col<0>, gA, blk, lc, st, A, M, N, -1.0f, p->d_work, z, (unsigned*)nullptr);
-    if (three) hipLaunchKernelGGL(k_col<4>, gB, blk, lb, st, B, M, N, 0.f, p->d_work, y, (unsigned*)nullptr);
-    hipLaunchKernelGGL(k_row<false>, grow, blk, lr, st, R, M, p->d_work);
-    if (three) hipLaunchKernelGGL(k_col<3>, gB, blk, lb, st, B, M, N, 0.f, p->d_work, y, (unsigned*)nullptr);
-    hipLaunchKernelGGL(k_col<5>, gA, blk, lc, st, A, M, N, 0.f, p->d_work, y, (unsigned*)nullptr);
+    launch_single_pass(p, R, z, y, st);          // (one channel: the plan's C, checked above)
     hipLaunchKernelGGL(k_phat_peak, dim3(1), dim3(1024), 0, st, (const float2*)y, n, (long long)max_shift, out4);
     EGR_HIP(hipGetLastError());
     return EGR_OK;

@@ -247,8 +247,9 @@ struct egr_fatllama_plan {
     int side_owned;               // 0: `side` was handed in by egr_fatllama_set_side_stream (not destroyed with the plan)
     hipEvent_t ev_fork, ev_join;
     hipStream_t cap;              // private capture stream
-    hipGraphExec_t gexec;         // CH captured loop iterations of all pipelines (egr_fatllama_enhance)
-    const float* g_out; float g_thr; int g_groups, g_iter_odd, use_graph;
+    hipGraphExec_t gexec;         // EGR_FL_MAX_RING captured loop iterations of all pipelines (fl_run_pipelines)
+    float g_thr; int g_groups, g_hook_kind;      // what gexec was captured for: threshold, pipelines, hook kind (soft | relative << 1)
+    int use_graph;
     std::vector<hipEvent_t> ev;   // pairs (start, stop) tagged by kind
     std::vector<int> ev_kind;     // 0 = row, 1 = outer column pass, 2 = inner column pass
 };
@@ -265,6 +266,83 @@ void fl_prof_begin(egr_fatllama_plan* p, int kind, hipStream_t st, size_t* slot)
 void fl_prof_end(egr_fatllama_plan* p, hipStream_t st, size_t* slot);
 // inner column pass of a three-level plan over `nstates` states of the plan (forward: FFT . twiddle, else twiddle^-1 . IFFT)
 void fl_launch_inner(egr_fatllama_plan* p, bool forward, egr::cplx* work, int nstates, hipStream_t st);
+
+// Drains the device, then destroys the executable loop graph: it is never destroyed while a launch of it may still be in flight
+// (calls return asynchronously).  Rare, millisecond-scale: a re-capture, a grown ring of maxima, a new side stream, the plan's end.
+int fl_drop_graph(egr_fatllama_plan* p);
+
+// The two-pipeline driver of the loops between k_prepare and k_finalize (packed: egr_fatllama.hip, paired chirp-z:
+// egr_fatllama_pz.hip).  The channels (states) are independent until k_finalize and a loop kernel alone fills barely more than one
+// wave of workgroups, so `ngroups` = 2 groups run as concurrent pipelines on the caller's stream and the plan's side stream, forked
+// and joined by events.  run_group(s0, g, it0, it1, first, last, prof) issues group g's launches for iterations [it0, it1) on s0
+// (g = 0) or the side stream; `first` adds the opening pass, `last` the closing one, `prof` the profiling events.
+// Schedule: the opening pass with iterations [0, pre) -- leading ones that differ from a middle iteration --, n_graph replays of CH
+// captured iterations, the tail [pre + n_graph CH, max_iter) with the closing pass; without replay the tail runs every iteration.
+// A middle iteration is the same launches every time and touches the plan's own state only (never `out`): CH of them, all pipelines,
+// are captured once into a hipGraph and replayed (inter-kernel gaps of ~8 us on the streams shrink to the graph's ~1 us).  The
+// executable graph is keyed by (threshold, pipelines, hook kind) and survives calls with other buffers; its iterations address the
+// ring of carried maxima by iteration mod CH.  `graph_allowed`: the loop's own conditions for replay; profiling runs and
+// egr_fatllama_set_graph(0) use plain launches.  A template, not std::function: plain-launch mode issues a few thousand launches
+// per call through run_group.
+template <class RunGroup>
+static inline int fl_run_pipelines(egr_fatllama_plan* p, hipStream_t st, int ngroups, int max_iter, int pre, bool graph_allowed,
+                                   float thr, int hook_kind, RunGroup&& run_group) {
+    constexpr int CH = 25;
+    static_assert(CH == EGR_FL_MAX_RING, "the captured iterations address the ring of maxima by iteration mod CH");
+    if (ngroups == 2 && !p->side) {
+        EGR_HIP(hipStreamCreateWithFlags(&p->side, hipStreamNonBlocking));
+        p->side_owned = 1;
+    }
+    if (ngroups == 2 && !p->ev_fork) {
+        EGR_HIP(hipEventCreateWithFlags(&p->ev_fork, hipEventDisableTiming));
+        EGR_HIP(hipEventCreateWithFlags(&p->ev_join, hipEventDisableTiming));
+    }
+    // fork: the side stream waits for what s0 holds so far; join: s0 waits for the side stream (one pipeline: nothing to do)
+    auto link = [&](hipEvent_t ev, hipStream_t from, hipStream_t to) -> int {
+        if (ngroups == 2) { EGR_HIP(hipEventRecord(ev, from)); EGR_HIP(hipStreamWaitEvent(to, ev, 0)); }
+        return EGR_OK;
+    };
+    auto fork = [&](hipStream_t s0) { return link(p->ev_fork, s0, p->side); };
+    auto join = [&](hipStream_t s0) { return link(p->ev_join, p->side, s0); };
+    const bool profiling = p->profiling;
+    const int n_graph = (graph_allowed && !profiling && p->use_graph && max_iter > 2 * CH) ? (max_iter - 1 - pre) / CH : 0;
+    int rc = fork(st);
+    if (rc) return rc;
+    for (int g = 0; g < ngroups; ++g) run_group(st, g, 0, n_graph > 0 ? pre : 0, true, false, false);
+    if (n_graph > 0) {
+        rc = join(st);
+        if (rc) return rc;
+        if (!(p->gexec && p->g_thr == thr && p->g_groups == ngroups && p->g_hook_kind == hook_kind)) {
+            rc = fl_drop_graph(p);
+            if (rc) return rc;
+            hipGraph_t graph = nullptr;
+            // captured on a private stream (the caller's may be the legacy default stream, which cannot capture)
+            if (!p->cap) EGR_HIP(hipStreamCreateWithFlags(&p->cap, hipStreamNonBlocking));
+            EGR_HIP(hipStreamBeginCapture(p->cap, hipStreamCaptureModeThreadLocal));
+            rc = fork(p->cap);
+            // max_iter > 2 CH: every one of the iterations [pre, pre + CH) is a "middle" iteration
+            if (!rc) for (int g = 0; g < ngroups; ++g) run_group(p->cap, g, pre, pre + CH, false, false, false);
+            if (!rc) rc = join(p->cap);
+            hipError_t ce = hipStreamEndCapture(p->cap, &graph);
+            if (rc || ce != hipSuccess) {          // leave no half-captured state behind: the next call starts from scratch
+                if (graph) hipGraphDestroy(graph);
+                hipStreamDestroy(p->cap);
+                p->cap = nullptr;
+                if (rc) return rc;
+                EGR_HIP(ce);
+            }
+            hipError_t ie = hipGraphInstantiate(&p->gexec, graph, nullptr, nullptr, 0);
+            hipGraphDestroy(graph);
+            if (ie != hipSuccess) { p->gexec = nullptr; EGR_HIP(ie); }
+            p->g_thr = thr; p->g_groups = ngroups; p->g_hook_kind = hook_kind;
+        }
+        for (int i = 0; i < n_graph; ++i) EGR_HIP(hipGraphLaunch(p->gexec, st));
+        rc = fork(st);
+        if (rc) return rc;
+    }
+    for (int g = 0; g < ngroups; ++g) run_group(st, g, n_graph > 0 ? pre + n_graph * CH : 0, max_iter, false, true, profiling);
+    return join(st);
+}
 
 // paired chirp-z (egr_fatllama_pz.hip)
 int pz_build(egr_fatllama_plan* p, int kind);

@@ -1253,30 +1253,7 @@ int pz_loop(egr_fatllama_plan* plan, float* out, int max_iter, float thr, float 
     // states are independent until k_finalize: two groups of states run as concurrent pipelines on two streams
     const int ns_all = z->nstates;
     const int ngroups = (plan->nstreams == 2 && ns_all >= 2) ? 2 : 1;
-    if (ngroups == 2 && !plan->side) {
-        EGR_HIP(hipStreamCreateWithFlags(&plan->side, hipStreamNonBlocking));
-        plan->side_owned = 1;
-    }
-    if (ngroups == 2 && !plan->ev_fork) {
-        EGR_HIP(hipEventCreateWithFlags(&plan->ev_fork, hipEventDisableTiming));
-        EGR_HIP(hipEventCreateWithFlags(&plan->ev_join, hipEventDisableTiming));
-    }
     size_t slot = 0;
-    const bool prof = plan->profiling;
-    auto fork = [&](hipStream_t s0) -> int {
-        if (ngroups == 2) {
-            EGR_HIP(hipEventRecord(plan->ev_fork, s0));
-            EGR_HIP(hipStreamWaitEvent(plan->side, plan->ev_fork, 0));
-        }
-        return EGR_OK;
-    };
-    auto join = [&](hipStream_t s0) -> int {
-        if (ngroups == 2) {
-            EGR_HIP(hipEventRecord(plan->ev_join, plan->side));
-            EGR_HIP(hipStreamWaitEvent(s0, plan->ev_join, 0));
-        }
-        return EGR_OK;
-    };
     // One group's launches: `first` adds the opening pass, iterations [it0, it1), `last` the closing pass.
     auto run_group = [&](hipStream_t s0, int g, int it0, int it1, bool first, bool last, bool profiling) {
         const int sb = g == 0 ? 0 : ns_all / 2, ns = ngroups == 1 ? ns_all : (g == 0 ? ns_all / 2 : ns_all - ns_all / 2);
@@ -1319,50 +1296,12 @@ int pz_loop(egr_fatllama_plan* plan, float* out, int max_iter, float thr, float 
         }
         if (last) hipLaunchKernelGGL(z->last, gc, bc, z->lds_col, sg, qg, thr, work, og, pk, (const unsigned*)nullptr);
     };
-    // The four launches of a middle iteration are the same every iteration and touch the plan's own state only: CH iterations of all
-    // pipelines are captured once into a hipGraph and replayed (as the packed loop does, egr_fatllama.hip); keyed by (threshold,
-    // pipelines, hook kind), never destroyed while a launch of it may be in flight.  Profiling and EGR_FL_THR_RECOMPUTE use plain
-    // launches; the relative threshold's carried maxima live in a ring of CH slots addressed by iteration mod CH.
-    constexpr int CH = 25;
-    // (two pipelines: 113.9 -> 103.4 ms per 800 iterations of 60 s + 2 samples; a single pipeline measures the same either way)
-    static_assert(CH == EGR_FL_MAX_RING, "the captured iterations address the ring of maxima by iteration mod CH");
-    // relative threshold: iteration 0 (the one with a maximum pass of its own, behind its first convolution) stays outside the graph
-    const int pre = relative ? 1 : 0;
-    const int n_graph = (!prof && plan->use_graph && !recompute && ngroups == 2 && max_iter > 2 * CH) ? (max_iter - 1 - pre) / CH : 0;
-    const int g_kind = h.soft | (relative ? 2 : 0);
-    int rc = fork(st);
-    if (rc) return rc;
-    for (int g = 0; g < ngroups; ++g) run_group(st, g, 0, n_graph > 0 ? pre : 0, true, false, false);
-    if (n_graph > 0) {
-        rc = join(st);
-        if (rc) return rc;
-        if (!(plan->gexec && plan->g_thr == thr && plan->g_groups == ngroups && plan->g_iter_odd == g_kind)) {
-            if (plan->gexec) { EGR_HIP(hipDeviceSynchronize()); EGR_HIP(hipGraphExecDestroy(plan->gexec)); plan->gexec = nullptr; }
-            hipGraph_t graph = nullptr;
-            if (!plan->cap) EGR_HIP(hipStreamCreateWithFlags(&plan->cap, hipStreamNonBlocking));
-            EGR_HIP(hipStreamBeginCapture(plan->cap, hipStreamCaptureModeThreadLocal));
-            rc = fork(plan->cap);
-            if (!rc) for (int g = 0; g < ngroups; ++g) run_group(plan->cap, g, pre, pre + CH, false, false, false);
-            if (!rc) rc = join(plan->cap);
-            hipError_t ce = hipStreamEndCapture(plan->cap, &graph);
-            if (rc || ce != hipSuccess) {
-                if (graph) hipGraphDestroy(graph);
-                hipStreamDestroy(plan->cap);
-                plan->cap = nullptr;
-                if (rc) return rc;
-                EGR_HIP(ce);
-            }
-            hipError_t ie = hipGraphInstantiate(&plan->gexec, graph, nullptr, nullptr, 0);
-            hipGraphDestroy(graph);
-            if (ie != hipSuccess) { plan->gexec = nullptr; EGR_HIP(ie); }
-            plan->g_out = out; plan->g_thr = thr; plan->g_groups = ngroups; plan->g_iter_odd = g_kind;
-        }
-        for (int i = 0; i < n_graph; ++i) EGR_HIP(hipGraphLaunch(plan->gexec, st));
-        rc = fork(st);
-        if (rc) return rc;
-    }
-    for (int g = 0; g < ngroups; ++g) run_group(st, g, n_graph > 0 ? pre + n_graph * CH : 0, max_iter, false, true, prof);
-    return join(st);
+    // The four launches of a middle iteration are the same every iteration: fl_run_pipelines replays them from a captured graph
+    // (two pipelines: 113.9 -> 103.4 ms per 800 iterations of 60 s + 2 samples; a single pipeline measures the same either way).
+    // Relative threshold: iteration 0 (the one with a maximum pass of its own, behind its first convolution) stays outside the graph;
+    // EGR_FL_THR_RECOMPUTE uses plain launches.
+    return fl_run_pipelines(plan, st, ngroups, max_iter, relative ? 1 : 0, !recompute && ngroups == 2, thr, h.soft | (relative ? 2 : 0),
+                            run_group);
 }
 
 // y = irfft(rfft(x) * [k >= band_lo]) per channel on a paired chirp-z plan (factor 1): first pass without a threshold, one

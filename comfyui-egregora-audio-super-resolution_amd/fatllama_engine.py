@@ -37,14 +37,31 @@ def upscale_ratio(sr: int, channels: int, target_bitrate_kbps: int) -> float:
 
 
 def variant_flags(names=None) -> int:
-    names = os.environ.get("EGREGORA_FATLLAMA_SPEC", "") if names is None else names
     flags = 0
-    for tok in (t.strip() for t in str(names).split(",")):
-        if tok:
-            if tok not in VARIANT_FLAGS:
-                raise RuntimeError(f"EGREGORA_FATLLAMA_SPEC: unknown variant {tok!r} (known: {sorted(VARIANT_FLAGS)})")
-            flags |= VARIANT_FLAGS[tok]
+    for tok in variant_names(names):
+        if tok not in VARIANT_FLAGS:
+            raise RuntimeError(f"EGREGORA_FATLLAMA_SPEC: unknown variant {tok!r} (known: {sorted(VARIANT_FLAGS)})")
+        flags |= VARIANT_FLAGS[tok]
     return flags
+
+
+def _flags(normalize, autoscale, pcm_in, node_post, variant) -> int:
+    """The flag word of egr_fatllama_enhance / _joint_peak / _finalize."""
+    return ((native.FL_NORMALIZE if normalize else 0) | (native.FL_AUTOSCALE if autoscale else 0) |
+            (native.FL_PCM_IN if pcm_in else 0) | (native.FL_NODE_POST if node_post else 0) | variant_flags(variant))
+
+
+def _request(who: str, x_ct, factor: int, n_out):
+    """-> the contiguous [C,T] input, the n_out its plan is keyed by (None for T * factor: one request, one plan on every path), t_out."""
+    if not (x_ct.is_cuda and x_ct.dtype == torch.float32 and x_ct.dim() == 2):
+        raise RuntimeError(f"{who} wants a [C,T] float32 tensor on the GPU")
+    x_ct = x_ct.contiguous()
+    T = x_ct.shape[1]
+    if T < 1:
+        raise RuntimeError("empty audio")
+    if n_out is not None and int(n_out) == T * factor:
+        n_out = None
+    return x_ct, n_out, (T * factor if n_out is None else int(n_out))
 
 _PLANS: "OrderedDict[tuple, int]" = OrderedDict()
 _MAX_PLANS = 8          # (a plan of 60 s stereo holds 46 MB; EGREGORA_DEVICES adds one per device)
@@ -84,18 +101,20 @@ def _plan(n_in: int, channels: int, factor: int, device: int, m1_hint: int = 0, 
                      "egr_fatllama_plan_create")
     _PLANS[key] = out.value
     while len(_PLANS) > _MAX_PLANS:
-        _, old = _PLANS.popitem(last=False)
-        _SIDE_SET.difference_update({k for k in _SIDE_SET if k[0] == old})
-        L.egr_fatllama_plan_destroy(C.c_void_p(old))
+        _drop()
     return out.value
 
 
+def _drop():
+    """Destroys the least recently used plan."""
+    _, old = _PLANS.popitem(last=False)
+    _SIDE_SET.difference_update({k for k in _SIDE_SET if k[0] == old})
+    native.lib().egr_fatllama_plan_destroy(C.c_void_p(old))
+
+
 def release_plans():
-    L = native.lib()
     while _PLANS:
-        _, old = _PLANS.popitem(last=False)
-        _SIDE_SET.difference_update({k for k in _SIDE_SET if k[0] == old})
-        L.egr_fatllama_plan_destroy(C.c_void_p(old))
+        _drop()
 
 
 def plan_info(n_in: int, factor: int, m1_hint: int = 0) -> dict:
@@ -160,18 +179,11 @@ def enhance_device(x_ct: torch.Tensor, factor: int, max_iterations: int, thresho
                    m1_hint: int = 0, tc_hint: int = 0, profile: bool = False, split=None, variant=None, n_out=None):
     """x_ct: [C,T] float32 CUDA tensor.  Returns [C,T*factor] float32 CUDA tensor (same stream); with n_out (and the linspace
     variant) [C,n_out] instead.  variant: comma list for variant_flags (None: the EGREGORA_FATLLAMA_SPEC environment variable)."""
-    if not (x_ct.is_cuda and x_ct.dtype == torch.float32 and x_ct.dim() == 2):
-        raise RuntimeError("enhance_device wants a [C,T] float32 tensor on the GPU")
-    x_ct = x_ct.contiguous()
+    x_ct, n_out, t_out = _request("enhance_device", x_ct, factor, n_out)
     Cn, T = x_ct.shape
-    if T < 1:
-        raise RuntimeError("empty audio")
-    if n_out is not None and int(n_out) == T * factor:
-        n_out = None
     plan = _plan(T, Cn, factor, x_ct.device.index or 0, m1_hint, tc_hint, split, n_out)
-    out = torch.empty((Cn, T * factor if n_out is None else int(n_out)), dtype=torch.float32, device=x_ct.device)
-    flags = ((native.FL_NORMALIZE if normalize else 0) | (native.FL_AUTOSCALE if autoscale else 0) |
-             (native.FL_PCM_IN if pcm_in else 0) | (native.FL_NODE_POST if node_post else 0) | variant_flags(variant))
+    out = torch.empty((Cn, t_out), dtype=torch.float32, device=x_ct.device)
+    flags = _flags(normalize, autoscale, pcm_in, node_post, variant)
     L = native.lib()
     # (paired chirp-z plans keep their own side stream and the graph replay: tuning them by 76-iteration runs measured 9 % slower)
     if Cn >= 2 and max_iterations > 100 and not profile and not isinstance(split, str) and n_out is None and not plan_info(T, factor)["bluestein"]:
@@ -188,8 +200,8 @@ class _ChannelBlockBackend:
     egr_fatllama_finalize with the all-reduced peak (include/egregora_amd.h)."""
 
     def __init__(self, x_ct, factor, max_iterations, threshold_value, flags, n_out=None):
-        self.x, self.factor, self.iters, self.thr, self.flags, self.n_out = x_ct, factor, int(max_iterations), float(threshold_value), flags, n_out
-        self.t_out = x_ct.shape[1] * factor if n_out is None else int(n_out)
+        self.x, self.n_out, self.t_out = _request("enhance_channel_parallel", x_ct, factor, n_out)
+        self.factor, self.iters, self.thr, self.flags = factor, int(max_iterations), float(threshold_value), flags
         self.L = native.lib()
 
     def empty(self, rows):
@@ -222,11 +234,7 @@ def enhance_channel_parallel(x_ct: torch.Tensor, factor: int, max_iterations: in
     """enhance_device with the channels of x_ct [C, T] (replicated on every rank) spread over the ranks of `group` (SURVEY.md section
     8(e): at most C ranks work; one 4-byte all-reduce(MAX) before the joint normalise).  Bit-identical to enhance_device on one rank."""
     from . import shard
-    if not (x_ct.is_cuda and x_ct.dtype == torch.float32 and x_ct.dim() == 2):
-        raise RuntimeError("enhance_channel_parallel wants a [C,T] float32 tensor on the GPU")
-    flags = ((native.FL_NORMALIZE if normalize else 0) | (native.FL_AUTOSCALE if autoscale else 0) |
-             (native.FL_PCM_IN if pcm_in else 0) | (native.FL_NODE_POST if node_post else 0) | variant_flags(variant))
-    be = _ChannelBlockBackend(x_ct.contiguous(), factor, max_iterations, threshold_value, flags, n_out)
+    be = _ChannelBlockBackend(x_ct, factor, max_iterations, threshold_value, _flags(normalize, autoscale, pcm_in, node_post, variant), n_out)
     return shard.sharded_channels(be, x_ct.shape[0], group=group, gather=gather)
 
 
@@ -240,14 +248,10 @@ def enhance_devices(x_ct: torch.Tensor, factor: int, max_iterations: int, thresh
     lengths.  UNMEASURED on two physical GPUs in this repository's test pool (EGREGORA_DEVICES=0,0 exercises it on one)."""
     import threading
     from . import shard
-    if not (x_ct.is_cuda and x_ct.dtype == torch.float32 and x_ct.dim() == 2):
-        raise RuntimeError("enhance_devices wants a [C,T] float32 tensor on the GPU")
-    x_ct = x_ct.contiguous()
+    x_ct, n_out, t_out = _request("enhance_devices", x_ct, factor, n_out)
     Cn, T = x_ct.shape
     home = x_ct.device
-    t_out = T * factor if n_out is None else int(n_out)
-    flags = ((native.FL_NORMALIZE if normalize else 0) | (native.FL_AUTOSCALE if autoscale else 0) |
-             (native.FL_PCM_IN if pcm_in else 0) | (native.FL_NODE_POST if node_post else 0) | variant_flags(variant))
+    flags = _flags(normalize, autoscale, pcm_in, node_post, variant)
     jobs = [(i, d, lo, hi) for i, (d, (lo, hi)) in enumerate(zip(devs, shard.block_bounds(Cn, min(len(devs), Cn)))) if hi > lo]
     out = torch.empty((Cn, t_out), dtype=torch.float32, device=home)
     torch.cuda.current_stream(home).synchronize()            # x_ct is complete before another device's stream reads it

@@ -115,3 +115,15 @@ def test_deferred_finalize_equals_the_one_call_form_without_a_process_group(pack
     native.check(L.egr_fatllama_finalize(C.c_void_p(plan), native.ptr(y), flags, C.c_void_p(0), native.stream_ptr()), "finalize")
     torch.cuda.synchronize()
     assert torch.equal(y, want)
+
+
+def test_explicit_output_length_equal_to_the_factor_builds_the_same_plan_on_one_rank(pack):
+    """n_out == T * factor with the linspace variant: enhance_channel_parallel on one rank keys its plan as enhance_device does (the
+    explicit length names the factor's own output), so the two are the same arithmetic on the same plan -- bit for bit."""
+    from egregora_amd import fatllama_engine as fe
+    T, factor = 24000, 2
+    x = torch.from_numpy(_signal(2, T)).cuda()
+    want = fe.enhance_device(x, factor, 30, 0.6, True, True, True, True, variant="linspace", n_out=T * factor)
+    got = fe.enhance_channel_parallel(x, factor, 30, 0.6, True, True, True, True, variant="linspace", n_out=T * factor)
+    assert got.shape == (2, T * factor)
+    assert np.array_equal(got.cpu().numpy(), want.cpu().numpy())
