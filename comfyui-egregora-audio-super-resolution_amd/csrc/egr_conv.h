@@ -1,6 +1,8 @@
 // Shared parameter block of the implicit-GEMM convolution kernels (egr_nn_gemm.hip: v_mfma_f32_32x32x2_f32 operands;
 // egr_nn_gemm_s3.hip: exact three-way bf16 split of the same fp32 operands on v_mfma_f32_32x32x16_bf16).
 #pragma once
+#include <string>
+
 #include "egr_common.h"
 
 namespace egr {
@@ -389,18 +391,45 @@ __device__ __forceinline__ void out_amax_commit(const ConvP& p, const unsigned* 
     }
 }
 
-// egr_nn_gemm.hip: 4 KiB of zeros on the current device (created on first use, one per device)
+// ---------------------------------------------------------------------------------------------------------------- host side
+// One convolution call: the fields of egr_conv_desc (include/egregora_amd.h), defaulted to one 1x1 stride-1 problem on one pixel
+// per batch entry with identity placement.  The extern "C" entry points and egr_flashsr.cpp fill it by name.
+struct ConvCall : egr_conv_desc {
+    ConvCall() : egr_conv_desc() { B = H = W = OH = OW = KH = KW = stride = dil = osy = osx = OHF = OWF = nz = 1; w_scale = 1.f; }
+};
+
+// What conv_choose picked: one kernel instantiation (conv_choice_name spells it) and its launch geometry
+enum ConvFamily { CONV_NONE = 0, CONV_IGEMM, CONV_S3, CONV1D_S3, CONV3X3_IS };
+struct ConvChoice {
+    int family = CONV_NONE;
+    int bm = 128, bn = 0, pf = 1, sch = 0, cc = 0;      // k_conv_s3<BM, BN, PF, ZS, SCH>, k_conv1d_s3<BN, CC, SCH>
+    bool zs = false, vec = false, gn = false, silu = false;   // k_conv_igemm<BN, VEC, GN>, k_conv3x3_isp<BN, 32, GN, SILU>
+    dim3 grid;
+    int ksplit = 1, kt_per = 0, zs_nzb = 0;
+};
+
+// egr_nn_gemm.hip.  conv_choose is THE selection: a pure host function of the parameter block of a checked call (no HIP call, no
+// allocation; the EGR_S3_* switches are read once per process).  conv_call checks, chooses, launches exactly that choice and hands
+// it back (`ran`, optional); the thread's last launch backs egr_conv_last_kernel.
+ConvChoice conv_choose(const ConvP& p);
+std::string conv_choice_name(const ConvChoice& k);
+int conv_call(const ConvCall& c, hipStream_t st, ConvChoice* ran = nullptr);
+// 4 KiB of zeros on the current device (created on first use, one per device)
 int zero_page(const float** out);
 
-// egr_nn_gemm_s3.hip: launches k_conv_s3<bm, bn> (bm = s3_bm(...), bn in {32, 64, 128}; grid.x = ceil(M / bm));
-// p.w3 must be set and Cin % 16 == 0
+// egr_nn_gemm_s3.hip: tile of k_conv_s3 (bn in {32, 64, 128, 256}, bm in {128, 256}), z problems per workgroup of a streamed stack, prefetch depth
 int s3_bn(int Cout);
 int s3_bm(long long M, int Cout, int bn);
 int s3_zs_nzb(long long M, int Cout, int bm, int bn, int nz, int K);
-// input-stationary stride-1 1-D convolution (k_conv1d_s3); returns false when the shape does not qualify
-bool launch_conv1d_s3(const ConvP& p, hipStream_t st);
-// input-stationary 3x3 convolution of big images (k_conv3x3_is, scheme 1; optional fused input GroupNorm); false: does not qualify
-bool launch_conv3x3_is(const ConvP& p, hipStream_t st);
-void launch_conv_s3(int bm, int bn, dim3 grid, hipStream_t st, const ConvP& p);
+int s3_pf();
+void launch_conv_s3(const ConvChoice& k, hipStream_t st, const ConvP& p);
+// input-stationary stride-1 1-D convolution (k_conv1d_s3): false when the shape does not qualify, else k holds the instantiation
+bool conv1d_s3_applies(const ConvP& p, ConvChoice& k);
+void launch_conv1d_s3(const ConvChoice& k, hipStream_t st, const ConvP& p);
+// egr_nn_conv3x3.hip: input-stationary 3x3 convolution of big images (k_conv3x3_isp, scheme 1; optional fused input GroupNorm)
+bool conv3x3_is_applies(const ConvP& p, ConvChoice& k);
+void launch_conv3x3_is(const ConvChoice& k, hipStream_t st, const ConvP& p);
+// egr_nn_amp.hip: the instantiation egr_amp_unit_h2 launches, spelled as conv_choice_name spells the convolutions
+const char* amp_unit_name();
 
 }  // namespace egr

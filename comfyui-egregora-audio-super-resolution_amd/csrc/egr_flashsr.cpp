@@ -21,7 +21,7 @@
 #include <unordered_map>
 #include <vector>
 
-#include "egr_common.h"
+#include "egr_conv.h"
 
 extern "C" {
 int egr_pack_weight(const float* src, float* dst, int layout, int K, int N, int Ci, int Co, int KH, int KW, void* stream);
@@ -32,6 +32,8 @@ int egr_winograd_pack_u(const float* w_oihw, float* dst, const double* G_dev, in
 namespace {
 
 using egr::set_error;
+using egr::ConvCall;
+using egr::ConvChoice;
 
 enum { ACT_NONE = 0, ACT_SILU = 1, ACT_TANH = 2, ACT_LEAKY = 3, ACT_LOGCLAMP = 4 };
 enum { EW_ADD = 0, EW_AXPBY = 1, EW_SILU = 2, EW_SCALE = 3, EW_COPY = 4, EW_ADD_SCALE = 5 };
@@ -461,21 +463,6 @@ int pack_all(M* m, const egr_tensor_desc* ts, int n) {
 }
 
 // ------------------------------------------------------------------------------------------------ profiling helpers
-std::string kind_of(long long Mrows, int Cin, int Cout, bool s3, bool vec = true, long long K = -1) {
-    int bn = Cout > 64 ? 128 : (Cout > 32 ? 64 : 32);
-    char buf[96];
-    if (s3) {
-        if (Cout >= 256 && Cout % 256 == 0) bn = 256;
-        if (K >= 0 && (K + 15) / 16 < 32)
-            while (bn > 64 && ((Mrows + 127) / 128) * ((Cout + bn - 1) / bn) < 256) bn >>= 1;
-        const int bm = (bn == 128 && ((Mrows + 255) / 256) * ((Cout + 127) / 128) >= 1024) ? 256 : 128;
-        snprintf(buf, sizeof(buf), "k_conv_s3<%d, %d, 1, false>", bm, bn);
-    } else {
-        snprintf(buf, sizeof(buf), "k_conv_igemm<%d, %s>", bn, vec ? "true" : "false");
-    }
-    return buf;
-}
-
 struct ProfScope {
     M* m; bool on; hipEvent_t a = nullptr, b = nullptr;
     explicit ProfScope(M* mm) : m(mm), on(mm->profiling) {
@@ -496,8 +483,6 @@ const void* s3_of(const M* m, const Wt* w, int Cin, const float* x) {
     return w->w3;
 }
 
-// One split contraction (egr_conv_s3's argument list; zfloats: floats per z problem of a stacked pack, 0 otherwise) in the operand
-// scheme of the forward being enqueued.  *h2 tells the profiler which kernel family ran.
 // R-entry slice of the context's pool of per-row maxima (zero at the start of the forward)
 unsigned* rs_take(M* m) {
     FsrCtx* c = m->cx;
@@ -538,34 +523,30 @@ int row_amax_of(M* m, const float* x, int64_t numel, int nz, int64_t zx, unsigne
     return EGR_OK;
 }
 
+// One contraction with the weight `w` (named `key` in errors): completes `c` (the caller filled x, y, geometry and epilogue; zfloats: floats
+// per z problem of a stacked pack, 0 otherwise) and launches it -- on the split kernels in the operand scheme of the forward being enqueued,
+// or on the fp32 pack when the call cannot be split.  *ran: the kernel the launcher chose (what the profiler reports).
 // y_rs (optional): the launch leaves the per-row maxima of y there (fp16 scheme, nz == 1; a fresh slice is taken when *y_rs is null
 // -- the four phase launches of an up-sampling convolution share one)
-int s3_launch(M* m, const Wt* w, const float* x, int64_t x_numel, unsigned** x_rs, const float* bias, const float* res, float* y, int B, int H, int W, int Cin,
-              int OH, int OW, int Cout, int KH, int KW, int stride, int dil, int pad_t, int pad_l, int up2, int act, float act_param, int osy, int osx,
-              int ooy, int oox, int OHF, int OWF, int nz, int64_t zx, int64_t zfloats, int64_t zy, bool* h2 = nullptr, unsigned** y_rs = nullptr) {
-    const bool use = m->h2 && w->w2 && m->h2_mode == 1 && ((int64_t)B * OH * OW) % m->R == 0;
-    if (h2) *h2 = use;
+int s3_launch(M* m, const Wt* w, const std::string& key, ConvCall& c, int64_t x_numel, unsigned** x_rs, int64_t zfloats, ConvChoice* ran, unsigned** y_rs = nullptr) {
+    if (!s3_of(m, w, c.Cin, c.x)) {
+        EGR_CHECK(w->w != nullptr, EGR_ERR_ARG, "FlashSR: no fp32 pack for %s", key.c_str());
+        c.w = w->w; c.zw = zfloats;
+        return egr::conv_call(c, m->st, ran);
+    }
+    const bool use = m->h2 && w->w2 && m->h2_mode == 1 && ((int64_t)c.B * c.OH * c.OW) % m->R == 0;
+    c.w3 = use ? w->w2 : w->w3;
+    c.zw = zfloats * (use ? 2 : 3) / 8;
     if (use) {
-        unsigned* local = nullptr;
-        if (!x_rs) x_rs = &local;
-        OKR(row_amax_of(m, x, nz > 1 ? x_numel / nz : x_numel, nz, zx, x_rs));
-        float* out_ra = nullptr;
-        if (y_rs && nz == 1 && m->out_amax_on) {
+        OKR(row_amax_of(m, c.x, c.nz > 1 ? x_numel / c.nz : x_numel, c.nz, c.zx, x_rs));
+        if (y_rs && c.nz == 1 && m->out_amax_on) {
             if (!*y_rs) *y_rs = rs_take(m);
             if (!*y_rs) return EGR_ERR_ALLOC;
-            out_ra = (float*)*y_rs;
+            c.out_amax = (float*)*y_rs;
         }
-        return egr_conv_h2(x, w->w2, bias, nullptr, res, y, B, H, W, Cin, OH, OW, Cout, KH, KW, stride, dil, pad_t, pad_l, up2, act, act_param, osy,
-                           osx, ooy, oox, OHF, OWF, nz, zx, zfloats * 2 / 8, zy, w->w_scale, (const float*)*x_rs, m->R, out_ra, m->st);
+        c.sch = 1; c.w_scale = w->w_scale; c.row_amax = (const float*)*x_rs; c.batch_rows = m->R;
     }
-    return egr_conv_s3(x, w->w3, bias, nullptr, res, y, B, H, W, Cin, OH, OW, Cout, KH, KW, stride, dil, pad_t, pad_l, up2, act, act_param, osy, osx,
-                       ooy, oox, OHF, OWF, nz, zx, zfloats * 3 / 8, zy, m->st);
-}
-
-std::string h2_kind(std::string kind, bool h2) {      // "k_conv_s3<128, 256, 1, false>" -> "k_conv_s3<128, 256, 1, false, 1>"
-    if (h2 && kind.rfind("k_conv_s3<256, 128", 0) == 0) kind.replace(0, 18, "k_conv_s3<128, 128");      // the fp16-term path has no 256 x 128 tile
-    if (h2 && !kind.empty() && kind.back() == '>' && kind.rfind("k_conv", 0) == 0) { kind.pop_back(); kind += ", 1>"; }
-    return kind;
+    return egr::conv_call(c, m->st, ran);
 }
 
 // general convolution: weights by key (key + ".weight", bias key + ".bias") or explicit entry `wk`
@@ -580,28 +561,15 @@ int conv(M* m, Ten& y, const Ten& x, const std::string& wkey, int B, int H, int 
     const float* bt = bias_t ? bias_t : (bias && !wk ? m->ptr(wkey + ".bias") : nullptr);
     const double fl = 2.0 * B * OH * OW * Cout * KH * KW * Cin;
     ProfScope ps(m);
-    const void* w3 = s3_of(m, w, Cin, x.p);
-    bool h2 = false;
-    if (w3) {
-        OKR(s3_launch(m, w, x.p, (int64_t)B * H * W * Cin, &x.rs, bt, res, y.p, B, H, W, Cin, OH, OW, Cout, KH, KW, stride, dil, pad_t, pad_l, up2, act,
-                      act_param, 1, 1, 0, 0, OH, OW, 1, 0, 0, 0, &h2, want_out_amax ? &y.rs : nullptr));
-    } else {
-        EGR_CHECK(w->w != nullptr, EGR_ERR_ARG, "FlashSR: no fp32 pack for %s", wkey.c_str());
-        OKR(egr_conv_nhwc(x.p, w->w, bt, nullptr, res, y.p, B, H, W, Cin, OH, OW, Cout, KH, KW, stride, dil, pad_t, pad_l, up2, act, act_param,
-                          m->st));
-    }
+    ConvCall c; ConvChoice ran;
+    c.x = x.p; c.bias = bt; c.res = res; c.y = y.p;
+    c.B = B; c.H = H; c.W = W; c.Cin = Cin; c.OH = c.OHF = OH; c.OW = c.OWF = OW; c.Cout = Cout; c.KH = KH; c.KW = KW;
+    c.stride = stride; c.dil = dil; c.pad_t = pad_t; c.pad_l = pad_l; c.up2 = up2; c.act = act; c.act_param = act_param;
+    OKR(s3_launch(m, w, wkey, c, (int64_t)B * H * W * Cin, &x.rs, 0, &ran, want_out_amax ? &y.rs : nullptr));
     if (ps.on) {
-        const bool vec = Cin % 16 == 0 && (((uintptr_t)x.p) & 15) == 0;
-        std::string kind = kind_of((long long)B * OH * OW, Cin, Cout, w3 != nullptr, vec, (long long)KH * KW * Cin);
-        if (w3 && H == 1 && KH == 1 && KW >= 2 && stride == 1 && !up2 && OW == W && W % 128 == 0 && dil * (KW - 1) <= 50 &&
-            2 * pad_l == dil * (KW - 1)) {                        // launch_conv1d_s3's conditions
-            char buf[64];
-            snprintf(buf, sizeof(buf), "k_conv1d_s3<%d, %d>", Cout > 64 ? 128 : (Cout > 32 ? 64 : 32), Cin % 32 == 0 ? 32 : 16);
-            kind = buf;
-        }
         char det[160];
         snprintf(det, sizeof(det), "%s B%d %dx%d Cin%d -> %dx%d Cout%d k%dx%d s%d d%d up%d", wkey.c_str(), B, H, W, Cin, OH, OW, Cout, KH, KW, stride, dil, up2);
-        ps.end(h2_kind(kind, h2), fl, det);
+        ps.end(egr::conv_choice_name(ran), fl, det);
     }
     if (m->count_flops) m->flops += fl;
     return EGR_OK;
@@ -673,29 +641,10 @@ int conv_winograd(M* m, Ten& y, const Ten& x, const std::string& key, int act, c
     const double fl = nz * 2.0 * (double)P * Cin * Cout;
     {
         ProfScope ps(m);
-        const void* w3 = s3_of(m, wz, Cin, V.p);
-        bool h2 = false;
-        if (w3) {
-            OKR(s3_launch(m, wz, V.p, (int64_t)nz * P * Cin, &V.rs, nullptr, nullptr, Mx.p, (int)P, 1, 1, Cin, 1, 1, Cout, 1, 1, 1, 1, 0, 0, 0, 0, 0.0f, 1, 1,
-                          0, 0, 1, 1, nz, P * Cin, wz->zfloats, P * Cout, &h2));
-        } else {
-            EGR_CHECK(wz->w != nullptr, EGR_ERR_ARG, "FlashSR: no fp32 Winograd pack for %s", key.c_str());
-            OKR(egr_gemm_zbatched(V.p, wz->w, Mx.p, nz, (int)P, Cin, Cout, P * Cin, wz->zfloats, P * Cout, m->st));
-        }
-        if (ps.on) {
-            std::string kind = kind_of(P, Cin, Cout, w3 != nullptr);
-            if (w3 && Cout > 64) {          // s3_zs_nzb (csrc/egr_nn_gemm_s3.hip): z-streamed when >= 2 z per workgroup
-                const int bn = (Cout >= 256 && Cout % 256 == 0) ? 256 : 128;
-                const long long tiles = ((P + 127) / 128) * ((Cout + bn - 1) / bn);
-                const long long groups = std::min<long long>(std::max<long long>((2048 + tiles - 1) / tiles, 1), nz);
-                if ((nz + groups - 1) / groups >= 2 && !(bn == 256 && Cin > 256)) {
-                    char buf[64];
-                    snprintf(buf, sizeof(buf), "k_conv_s3<128, %d, 1, true>", bn);
-                    kind = buf;
-                }
-            }
-            ps.end(h2_kind(kind, h2), fl);
-        }
+        ConvCall c; ConvChoice ran;                    // nz independent [P][Cin] x [Cin][Cout] products
+        c.x = V.p; c.y = Mx.p; c.B = (int)P; c.Cin = Cin; c.Cout = Cout; c.nz = nz; c.zx = P * Cin; c.zy = P * Cout;
+        OKR(s3_launch(m, wz, key + (f4 ? ".weight.wino4" : ".weight.wino"), c, (int64_t)nz * P * Cin, &V.rs, wz->zfloats, &ran));
+        if (ps.on) ps.end(egr::conv_choice_name(ran), fl);
     }
     if (m->count_flops) m->flops += fl;
     V.release();
@@ -734,15 +683,11 @@ int conv_up2_phases(M* m, Ten& y, const Ten& x, const std::string& key, int act)
             const Wt* w = m->get(key + ".weight.ph" + std::to_string(a) + std::to_string(b));
             const double fl = 2.0 * B * H * W * Cout * 4 * Cin;
             ProfScope ps(m);
-            const void* w3 = s3_of(m, w, Cin, x.p);
-            bool h2 = false;
-            if (w3)
-                OKR(s3_launch(m, w, x.p, (int64_t)B * H * W * Cin, &x.rs, bt, nullptr, y.p, B, H, W, Cin, H, W, Cout, 2, 2, 1, 1, 1 - a, 1 - b, 0, act, 0.0f, 2, 2,
-                              a, b, 2 * H, 2 * W, 1, 0, 0, 0, &h2, &y.rs));
-            else
-                OKR(egr_conv_nhwc_placed(x.p, w->w, bt, nullptr, nullptr, y.p, B, H, W, Cin, H, W, Cout, 2, 2, 1, 1, 1 - a, 1 - b, 0, act, 0.0f, 2, 2,
-                                         a, b, 2 * H, 2 * W, m->st));
-            if (ps.on) ps.end(h2_kind(kind_of((long long)B * H * W, Cin, Cout, w3 != nullptr, Cin % 16 == 0, 4LL * Cin), h2), fl);
+            ConvCall c; ConvChoice ran;               // 2x2 kernel on the low-res input, written to phase (a, b) of the 2H x 2W output
+            c.x = x.p; c.bias = bt; c.y = y.p; c.B = B; c.H = c.OH = H; c.W = c.OW = W; c.Cin = Cin; c.Cout = Cout; c.KH = c.KW = 2;
+            c.pad_t = 1 - a; c.pad_l = 1 - b; c.act = act; c.osy = c.osx = 2; c.ooy = a; c.oox = b; c.OHF = 2 * H; c.OWF = 2 * W;
+            OKR(s3_launch(m, w, key + ".weight.ph", c, (int64_t)B * H * W * Cin, &x.rs, 0, &ran, &y.rs));
+            if (ps.on) ps.end(egr::conv_choice_name(ran), fl);
             if (m->count_flops) m->flops += fl;
         }
     return EGR_OK;
@@ -843,10 +788,12 @@ int gn_conv3(M* m, Ten& y, const Ten& x, const std::string& norm_key, float eps,
                 y.part_tiles = H * W / 32;
             }
             ProfScope ps(m);
-            OKR(egr_conv_h2_gn(x.p, sc.p, sh.p, 1, wd->w2, bt, res, y.p, B, H, W, Cin, wd->Cout, ACT_NONE, wd->w_scale, (const float*)bound, out_ra, gpart, m->st));
-            if (ps.on) {
-                ps.end(egr::conv3x3_is_name(wd->Cout, true, true), fl, conv_key);       // (the launcher's own choice: egr_nn_conv3x3.hip)
-            }
+            ConvCall c; ConvChoice ran;
+            c.x = x.p; c.w3 = wd->w2; c.bias = bt; c.res = res; c.y = y.p; c.gn_scale = sc.p; c.gn_shift = sh.p; c.gn_silu = 1;
+            c.B = B; c.H = c.OH = c.OHF = H; c.W = c.OW = c.OWF = W; c.Cin = Cin; c.Cout = wd->Cout; c.KH = c.KW = 3; c.pad_t = c.pad_l = 1;
+            c.sch = 1; c.w_scale = wd->w_scale; c.row_amax = (const float*)bound; c.batch_rows = B; c.out_amax = out_ra; c.gn_part = gpart;
+            OKR(egr::conv_call(c, m->st, &ran));
+            if (ps.on) ps.end(egr::conv_choice_name(ran), fl, conv_key);
             if (m->count_flops) m->flops += fl;
             return EGR_OK;
         }
@@ -1204,7 +1151,7 @@ int amp(M* m, Ten& y, Ten&& h, int j) {
                                         m->ptr(b + ".conv1.bias"), m->ptr(b + ".alpha2"), m->ptr(b + ".beta2"), w2->w2, w2->w_scale, m->ptr(b + ".conv2.bias"),
                                         m->filt, c.aa_taps, m->st));
                     const double fl = 2.0 * 2.0 * (double)cur->d[0] * cur->d[1] * Cc * Cc * k;
-                    if (ps.on) ps.end(Cc == 16 ? "k_amp_unit<16>" : "k_amp_unit<32>", fl, b);
+                    if (ps.on) ps.end(egr::amp_unit_name(), fl, b);
                     if (m->count_flops) m->flops += fl;
                     x = std::move(xn);
                     cur = &x;

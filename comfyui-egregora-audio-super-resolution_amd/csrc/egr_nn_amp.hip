@@ -298,6 +298,10 @@ __global__ __launch_bounds__(256, C == 16 ? AMP_LB16 : 2) void k_amp_unit(AmpP p
     }
 }
 
+#define AMP_STR_(x) #x
+#define AMP_STR(x) AMP_STR_(x)
+const char* amp_unit_name() { return "k_amp_unit<16, " AMP_STR(AMP_TL16) ">"; }
+
 }  // namespace egr
 
 using namespace egr;

@@ -213,38 +213,31 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_isp(ConvP p) {
     if (om) out_amax_commit(p, om_tab, (b * p.H + y0) * p.W + x0, 1);
 }
 
-// the instantiation launch_conv3x3_is picks for (Cout, fused GroupNorm, SiLU): what the per-kernel profile and profiles/traffic.json key on
-const char* conv3x3_is_name(int cout, bool gn, bool silu) {
-    const bool wide = cout > 64;
-    if (gn && silu) return wide ? "k_conv3x3_isp<128, 32, true, true>" : "k_conv3x3_isp<64, 32, true, true>";
-    if (gn) return wide ? "k_conv3x3_isp<128, 32, true, false>" : "k_conv3x3_isp<64, 32, true, false>";
-    return wide ? "k_conv3x3_isp<128, 32, false, false>" : "k_conv3x3_isp<64, 32, false, false>";
-}
-
-// true when the input-stationary 3x3 kernel applies (scheme 1, big images, Cin <= 512, one image < 2^31 elements); launches it
-bool launch_conv3x3_is(const ConvP& p, hipStream_t st) {
+// true when the input-stationary 3x3 kernel applies (scheme 1, big images, Cin <= 512, one image < 2^31 elements): k then holds its
+// instantiation and grid
+bool conv3x3_is_applies(const ConvP& p, ConvChoice& k) {
     static const bool off = getenv("EGR_S3_CONV3X3") && atoi(getenv("EGR_S3_CONV3X3")) == 0;
     if (off || !p.sch || !p.w3 || p.KH != 3 || p.KW != 3 || p.stride != 1 || p.dil != 1 || p.pad_t != 1 || p.pad_l != 1 || p.up2 ||
-        p.OH != p.H || p.OW != p.W || (p.W % 32) != 0 || (p.H % 4) != 0 || (p.Cin % 32) != 0 || (p.Cout % 4) != 0 || p.ksplit > 1 ||
-        p.zs_nzb > 0 || p.nz > 1 || p.osy != 1 || p.osx != 1 || p.OHF != p.OH || p.OWF != p.OW || p.bias_b || p.B > 65535 ||
+        p.OH != p.H || p.OW != p.W || (p.W % 32) != 0 || (p.H % 4) != 0 || (p.Cin % 32) != 0 || (p.Cout % 4) != 0 || k.ksplit > 1 ||
+        k.zs_nzb > 0 || p.nz > 1 || p.osy != 1 || p.osx != 1 || p.OHF != p.OH || p.OWF != p.OW || p.bias_b || p.B > 65535 ||
         p.rows_div != p.H * p.W || (long long)(p.H / 4) * (p.W / 32) * p.B < 512 ||
         (size_t)p.H * p.W * p.Cin >= ((size_t)1 << 31) || p.Cin > C3P_MAX_CIN)
         return false;
-    const int bn = p.Cout > 64 ? 128 : 64;
-    const dim3 grid((p.H / 4) * (p.W / 32), (p.Cout + bn - 1) / bn, p.B);
-    if (p.gn_scale && p.gn_silu) {
-        if (bn == 128) hipLaunchKernelGGL((k_conv3x3_isp<128, 32, true, true>), grid, dim3(256), 0, st, p);
-        else hipLaunchKernelGGL((k_conv3x3_isp<64, 32, true, true>), grid, dim3(256), 0, st, p);
-    } else if (p.gn_scale) {
-        if (bn == 128) hipLaunchKernelGGL((k_conv3x3_isp<128, 32, true, false>), grid, dim3(256), 0, st, p);
-        else hipLaunchKernelGGL((k_conv3x3_isp<64, 32, true, false>), grid, dim3(256), 0, st, p);
-    } else {
-        if (bn == 128) hipLaunchKernelGGL((k_conv3x3_isp<128, 32, false, false>), grid, dim3(256), 0, st, p);
-        else hipLaunchKernelGGL((k_conv3x3_isp<64, 32, false, false>), grid, dim3(256), 0, st, p);
-    }
+    k.bn = p.Cout > 64 ? 128 : 64;
+    k.gn = p.gn_scale != nullptr;
+    k.silu = k.gn && p.gn_silu;
+    k.grid = dim3((p.H / 4) * (p.W / 32), (p.Cout + k.bn - 1) / k.bn, p.B);
     return true;
 }
 
+void launch_conv3x3_is(const ConvChoice& k, hipStream_t st, const ConvP& p) {
+#define C3_LAUNCH(GN_, SILU_)                                                                                        \
+    if (k.bn == 128) hipLaunchKernelGGL((k_conv3x3_isp<128, 32, GN_, SILU_>), k.grid, dim3(256), 0, st, p);          \
+    else hipLaunchKernelGGL((k_conv3x3_isp<64, 32, GN_, SILU_>), k.grid, dim3(256), 0, st, p)
+    if (k.silu) { C3_LAUNCH(true, true); }
+    else if (k.gn) { C3_LAUNCH(true, false); }
+    else { C3_LAUNCH(false, false); }
+#undef C3_LAUNCH
+}
+
 }  // namespace egr
-
-

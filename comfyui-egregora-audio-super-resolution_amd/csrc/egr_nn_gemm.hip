@@ -488,20 +488,179 @@ __global__ void k_spin(long long ticks, unsigned* sink) {
     if (sink && n == 0xffffffffu) *sink = n;
 }
 
+// ------------------------------------------------ one convolution call: checks, parameter block, THE kernel selection, its name, the launch
+static int conv_check(const ConvCall& c) {
+    EGR_CHECK(c.x && (c.w || c.w3) && c.y, EGR_ERR_ARG, "null x/w/y");
+    EGR_CHECK(c.nz >= 1 && c.nz <= 65535, EGR_ERR_ARG, "bad nz");
+    EGR_CHECK(c.sch == 0 || (c.w3 && c.w_scale > 0.f && c.row_amax && c.batch_rows >= 1 && ((long long)c.B * c.OH * c.OW) % c.batch_rows == 0),
+              EGR_ERR_ARG, "bad operand scheme: needs w_scale > 0, row_amax and a batch row count that divides the GEMM rows");
+    EGR_CHECK(!c.w3 || ((c.Cin % BK) == 0 && (((uintptr_t)c.x) & 15) == 0 && (((uintptr_t)c.w3) & 15) == 0 && (!c.gn_scale || c.sch == 1)), EGR_ERR_ARG,
+              "split conv needs Cin %% 16 == 0, 16-byte aligned x / w3 and no fused input affine (scheme 1: only the input-stationary 3x3 kernel fuses one)");
+    EGR_CHECK(!c.gn_scale || (c.gn_shift && (c.Cin % BK) == 0 && (((uintptr_t)c.x) & 15) == 0), EGR_ERR_ARG,
+              "fused input affine needs Cin %% 16 == 0 and a 16-byte aligned input");
+    EGR_CHECK(c.B >= 1 && c.H >= 1 && c.W >= 1 && c.Cin >= 1 && c.OH >= 1 && c.OW >= 1 && c.Cout >= 1 && c.KH >= 1 && c.KW >= 1 && c.stride >= 1 &&
+                  c.dil >= 1, EGR_ERR_ARG, "bad conv geometry");
+    EGR_CHECK((long long)c.B * c.OH * c.OW < (1LL << 31) && (long long)c.KH * c.KW * c.Cin < (1LL << 31), EGR_ERR_ARG, "conv too large for 32-bit indexing");
+    EGR_CHECK(c.osy >= 1 && c.osx >= 1 && c.ooy >= 0 && c.oox >= 0 && (c.OH - 1) * c.osy + c.ooy < c.OHF && (c.OW - 1) * c.osx + c.oox < c.OWF,
+              EGR_ERR_ARG, "bad output placement");
+    return EGR_OK;
+}
+
+// everything of the kernels' parameter block that does not depend on the choice (a checked call; zeros and ws: conv_call)
+static ConvP conv_params(const ConvCall& c) {
+    ConvP p;
+    memset(&p, 0, sizeof(p));
+    p.x = c.x; p.w = c.w; p.w3 = (const uint4*)c.w3; p.bias = c.bias; p.bias_b = c.bias_b; p.res = c.res; p.y = c.y;
+    p.B = c.B; p.H = c.H; p.W = c.W; p.Cin = c.Cin; p.OH = c.OH; p.OW = c.OW; p.Cout = c.Cout; p.KH = c.KH; p.KW = c.KW;
+    p.stride = c.stride; p.dil = c.dil; p.pad_t = c.pad_t; p.pad_l = c.pad_l; p.up2 = c.up2; p.act = c.act; p.act_param = c.act_param;
+    p.M = c.B * c.OH * c.OW; p.K = c.KH * c.KW * c.Cin;
+    p.osy = c.osy; p.osx = c.osx; p.ooy = c.ooy; p.oox = c.oox; p.OHF = c.OHF; p.OWF = c.OWF;
+    p.nz = c.nz; p.zx = c.zx; p.zw = c.zw; p.zy = c.zy;
+    p.gn_scale = c.gn_scale; p.gn_shift = c.gn_shift; p.gn_silu = c.gn_silu;
+    p.sch = c.sch; p.out_scale = c.sch ? 1.0f / c.w_scale : 1.0f; p.row_amax = c.sch ? (const unsigned*)c.row_amax : nullptr;
+    p.rows_div = c.sch ? p.M / c.batch_rows : 1;
+    p.out_amax = (c.sch && c.nz == 1) ? (unsigned*)c.out_amax : nullptr; p.gn_part = (float2*)c.gn_part;
+    p.ksplit = 1; p.kt_per = (p.K + BK - 1) / BK;
+    return p;
+}
+
+ConvChoice conv_choose(const ConvP& p) {
+    ConvChoice k;
+    const long long M = p.M; const int ktiles = (p.K + BK - 1) / BK;
+    k.sch = p.sch; k.gn = p.gn_scale != nullptr;
+    k.vec = (p.Cin % BK) == 0 && (((uintptr_t)p.x) & 15) == 0;
+    k.bn = p.w3 ? s3_bn(p.Cout) : (p.Cout > 64 ? 128 : (p.Cout > 32 ? 64 : 32));
+    // short-K layers that cannot use split-K (the transformer blocks' linears: a few thousand rows, K <= 496): narrower column
+    // tiles until the grid covers the 256 CUs
+    static const bool narrow = !(getenv("EGR_S3_NARROW") && atoi(getenv("EGR_S3_NARROW")) == 0);
+    if (p.w3 && narrow && p.nz <= 1 && ktiles < 32)
+        while (k.bn > 64 && ((M + 127) / 128) * ((p.Cout + k.bn - 1) / k.bn) < 256) k.bn >>= 1;
+    // (fp16 terms: the 256 x 128 tile loses to 128 x 128 on every layer that took it -- short-K streaming GEMMs with 128 outputs, 5 per
+    // forward: 5.1 -> 3.1 ms, profiles/r05/flashsr_kernel_experiments.log item 6 -- half the registers per workgroup, twice the workgroups in flight)
+    k.bm = p.w3 ? (p.sch ? 128 : s3_bm(M, p.Cout, k.bn)) : BM;
+    k.grid = dim3((unsigned)((M + k.bm - 1) / k.bm), (unsigned)((p.Cout + k.bn - 1) / k.bn), (unsigned)p.nz);
+    k.kt_per = ktiles;
+    const int tiles = (int)(k.grid.x * k.grid.y);
+    if (p.w3 && p.nz > 1 && p.KH == 1 && p.KW == 1 && p.H == 1 && p.W == 1 && p.stride == 1 && p.zw == (long long)(p.K / BK) * p.Cout * (p.sch ? 4 : 6) &&
+        !p.bias && !p.bias_b && !p.res && p.act == 0 && p.osy == 1 && p.osx == 1 && p.OHF == p.OH && p.OWF == p.OW) {
+        k.zs_nzb = s3_zs_nzb(M, p.Cout, 128, k.bn, p.nz, p.K);      // Winograd GEMMs: stream several z per workgroup
+        if (k.zs_nzb > 0) {                                       // (128-row tiles: the 256-row variant would spill)
+            k.zs = true; k.bm = 128;
+            k.grid.x = (unsigned)((M + k.bm - 1) / k.bm);
+            k.grid.z = (p.nz + k.zs_nzb - 1) / k.zs_nzb;
+        }
+    }
+    // split-K when the output tiles alone cannot fill the chip and the K loop is long (deep UNet / latent layers)
+    if (p.nz == 1 && tiles < 192 && ktiles >= 32) {
+        int S = (768 + tiles - 1) / tiles;
+        if (S > ktiles / 8) S = ktiles / 8;
+        if (S > 64) S = 64;
+        if (S >= 2) {
+            k.kt_per = (ktiles + S - 1) / S;
+            k.ksplit = (ktiles + k.kt_per - 1) / k.kt_per;
+            k.grid.z = k.ksplit;
+        }
+    }
+    if (p.w3 && conv3x3_is_applies(p, k)) k.family = CONV3X3_IS;
+    else if (p.w3 && k.gn) k.family = CONV_NONE;                  // scheme 1 fuses the input affine in the 3x3 kernel only
+    else if (p.w3 && conv1d_s3_applies(p, k)) k.family = CONV1D_S3;
+    else if (p.w3) {
+        k.family = CONV_S3;
+        if (!p.sch && !k.zs && k.bn != 256 && k.bm != 256) k.pf = s3_pf();
+    } else k.family = CONV_IGEMM;                                 // (k.gn: conv_check made sure of the vector loader's conditions)
+    return k;
+}
+
+// the instantiation as rocprofv3 prints it (the keys of profiles/traffic.json)
+std::string conv_choice_name(const ConvChoice& k) {
+    char b[64] = "";
+    auto tf = [](bool v) { return v ? "true" : "false"; };
+    switch (k.family) {
+        case CONV_IGEMM: snprintf(b, sizeof(b), "k_conv_igemm<%d, %s, %s>", k.bn, tf(k.vec), tf(k.gn)); break;
+        case CONV_S3: snprintf(b, sizeof(b), "k_conv_s3<%d, %d, %d, %s, %d>", k.bm, k.bn, k.pf, tf(k.zs), k.sch); break;
+        case CONV1D_S3: snprintf(b, sizeof(b), "k_conv1d_s3<%d, %d, %d>", k.bn, k.cc, k.sch); break;
+        case CONV3X3_IS: snprintf(b, sizeof(b), "k_conv3x3_isp<%d, 32, %s, %s>", k.bn, tf(k.gn), tf(k.silu)); break;
+    }
+    return b;
+}
+
+static thread_local ConvChoice t_last;          // of the calling thread's last launch (egr_conv_last_kernel)
+
+// everything short of the launch: checks, parameter block, choice, and what the choice rules out
+static int conv_resolve(const ConvCall& c, ConvP& p, ConvChoice& k) {
+    { const int rc = conv_check(c); if (rc) return rc; }
+    p = conv_params(c);
+    k = conv_choose(p);
+    if (k.family == CONV_NONE) {
+        set_error("egr_conv_h2_gn: the shape does not qualify for the input-stationary 3x3 kernel (stride 1, pad 1, H %% 4 == 0, W %% 32 == 0, "
+                  "Cin %% 32 == 0, >= 512 tiles, one batch row per image)");
+        return EGR_ERR_UNSUPPORTED;
+    }
+    // (with out_amax: the reduction kernel writes y and tracks the row maxima)
+    EGR_CHECK(!(k.ksplit > 1 && p.out_amax) || c.batch_rows <= 1024, EGR_ERR_UNSUPPORTED, "out_amax with split-K serves up to 1024 batch rows");
+    return EGR_OK;
+}
+
+int conv_call(const ConvCall& c, hipStream_t st, ConvChoice* ran) {
+    ConvP p; ConvChoice k;
+    { const int rc = conv_resolve(c, p, k); if (rc) return rc; }
+    p.ksplit = k.ksplit; p.kt_per = k.kt_per; p.zs_nzb = k.zs_nzb;
+    { const int rc = zero_page(&p.zeros); if (rc) return rc; }     // (every kernel below reads padded / out-of-range rows from it)
+    if (k.ksplit > 1) { const int rc = splitk_workspace((size_t)k.ksplit * p.M * p.Cout * sizeof(float), st, &p.ws); if (rc) return rc; }
+#define LAUNCH(BN_, V_, GN_) hipLaunchKernelGGL((k_conv_igemm<BN_, V_, GN_>), k.grid, dim3(256), 0, st, p)
+    if (k.family == CONV3X3_IS) launch_conv3x3_is(k, st, p);
+    else if (k.family == CONV1D_S3) launch_conv1d_s3(k, st, p);
+    else if (k.family == CONV_S3) launch_conv_s3(k, st, p);
+    else if (k.gn) {            // fused-GroupNorm loader: separate instantiations so the plain kernels pay nothing for it
+        if (k.bn == 128) LAUNCH(128, true, true); else if (k.bn == 64) LAUNCH(64, true, true); else LAUNCH(32, true, true);
+    }
+    else if (k.bn == 128) { if (k.vec) LAUNCH(128, true, false); else LAUNCH(128, false, false); }
+    else if (k.bn == 64) { if (k.vec) LAUNCH(64, true, false); else LAUNCH(64, false, false); }
+    else { if (k.vec) LAUNCH(32, true, false); else LAUNCH(32, false, false); }
+#undef LAUNCH
+    if (k.ksplit > 1) {
+        long long nb = ((long long)p.M * p.Cout + 255) / 256;
+        if (nb > 2048) nb = 2048;
+        if (p.out_amax) hipLaunchKernelGGL(k_splitk_reduce<true>, dim3((unsigned)nb), dim3(256), 0, st, p);
+        else hipLaunchKernelGGL(k_splitk_reduce<false>, dim3((unsigned)nb), dim3(256), 0, st, p);
+    }
+    EGR_HIP(hipGetLastError());
+    t_last = k;
+    if (ran) *ran = k;
+    return EGR_OK;
+}
+
 }  // namespace egr
 
 using namespace egr;
 
+extern "C" int egr_conv_kernel_name(const egr_conv_desc* d, char* name, size_t buflen, int* ksplit, int* zs_nzb) {
+    EGR_CHECK(d && name && buflen >= 1, EGR_ERR_ARG, "egr_conv_kernel_name: null argument");
+    ConvCall c;
+    (egr_conv_desc&)c = *d;
+    ConvP p; ConvChoice k;
+    { const int rc = conv_resolve(c, p, k); if (rc) return rc; }
+    snprintf(name, buflen, "%s", conv_choice_name(k).c_str());
+    if (ksplit) *ksplit = k.ksplit; if (zs_nzb) *zs_nzb = k.zs_nzb;
+    return EGR_OK;
+}
+
+extern "C" const char* egr_conv_last_kernel(void) {
+    static thread_local std::string name;
+    return (name = conv_choice_name(t_last)).c_str();
+}
+
 extern "C" int egr_conv_nhwc_placed(const float* x, const float* w, const float* bias, const float* bias_b,
                                     const float* res, float* y, int B, int H, int W, int Cin, int OH, int OW, int Cout,
                                     int KH, int KW, int stride, int dil, int pad_t, int pad_l, int up2, int act,
-                                    float act_param, int osy, int osx, int ooy, int oox, int OHF, int OWF, void* stream);
-static int conv_launch(const float* x, const float* w, const float* bias, const float* bias_b, const float* res, float* y,
-                       int B, int H, int W, int Cin, int OH, int OW, int Cout, int KH, int KW, int stride, int dil, int pad_t,
-                       int pad_l, int up2, int act, float act_param, int osy, int osx, int ooy, int oox, int OHF, int OWF,
-                       int nz, long long zx, long long zw, long long zy, const float* gn_scale, const float* gn_shift,
-                       int gn_silu, void* stream, const void* w3 = nullptr, int sch = 0, float w_scale = 1.f,
-                       const float* row_amax = nullptr, int batch_rows = 0, float* out_amax = nullptr, void* gn_part = nullptr);
+                                    float act_param, int osy, int osx, int ooy, int oox, int OHF, int OWF, void* stream) {
+    ConvCall c;
+    c.x = x; c.w = w; c.bias = bias; c.bias_b = bias_b; c.res = res; c.y = y;
+    c.B = B; c.H = H; c.W = W; c.Cin = Cin; c.OH = OH; c.OW = OW; c.Cout = Cout; c.KH = KH; c.KW = KW;
+    c.stride = stride; c.dil = dil; c.pad_t = pad_t; c.pad_l = pad_l; c.up2 = up2; c.act = act; c.act_param = act_param;
+    c.osy = osy; c.osx = osx; c.ooy = ooy; c.oox = oox; c.OHF = OHF; c.OWF = OWF;
+    return conv_call(c, (hipStream_t)stream);
+}
 
 extern "C" int egr_conv_nhwc(const float* x, const float* w, const float* bias, const float* bias_b, const float* res,
                              float* y, int B, int H, int W, int Cin, int OH, int OW, int Cout, int KH, int KW,
@@ -511,29 +670,24 @@ extern "C" int egr_conv_nhwc(const float* x, const float* w, const float* bias, 
                                 up2, act, act_param, 1, 1, 0, 0, OH, OW, stream);
 }
 
-extern "C" int egr_conv_nhwc_placed(const float* x, const float* w, const float* bias, const float* bias_b,
-                                    const float* res, float* y, int B, int H, int W, int Cin, int OH, int OW, int Cout,
-                                    int KH, int KW, int stride, int dil, int pad_t, int pad_l, int up2, int act,
-                                    float act_param, int osy, int osx, int ooy, int oox, int OHF, int OWF, void* stream) {
-    return conv_launch(x, w, bias, bias_b, res, y, B, H, W, Cin, OH, OW, Cout, KH, KW, stride, dil, pad_t, pad_l, up2, act,
-                       act_param, osy, osx, ooy, oox, OHF, OWF, 1, 0, 0, 0, nullptr, nullptr, 0, stream);
-}
-
 // egr_conv_nhwc with the producer's GroupNorm (+SiLU) applied to the input while it is loaded.
 extern "C" int egr_conv_nhwc_gn(const float* x, const float* gn_scale, const float* gn_shift, int gn_silu, const float* w,
                                 const float* bias, const float* res, float* y, int B, int H, int W, int Cin, int OH, int OW,
                                 int Cout, int KH, int KW, int stride, int pad_t, int pad_l, int act, void* stream) {
     EGR_CHECK(gn_scale && gn_shift, EGR_ERR_ARG, "null scale/shift");
-    return conv_launch(x, w, bias, nullptr, res, y, B, H, W, Cin, OH, OW, Cout, KH, KW, stride, 1, pad_t, pad_l, 0, act, 0.f, 1,
-                       1, 0, 0, OH, OW, 1, 0, 0, 0, gn_scale, gn_shift, gn_silu, stream);
+    ConvCall c;
+    c.x = x; c.w = w; c.bias = bias; c.res = res; c.y = y; c.gn_scale = gn_scale; c.gn_shift = gn_shift; c.gn_silu = gn_silu;
+    c.B = B; c.H = H; c.W = W; c.Cin = Cin; c.OH = c.OHF = OH; c.OW = c.OWF = OW; c.Cout = Cout; c.KH = KH; c.KW = KW;
+    c.stride = stride; c.pad_t = pad_t; c.pad_l = pad_l; c.act = act;
+    return conv_call(c, (hipStream_t)stream);
 }
 
 // nz independent GEMMs y[z] = x[z] * w[z] ([rows][Cin] x [Cin][Cout], weights packed per z), offsets in elements.
 extern "C" int egr_gemm_zbatched(const float* x, const float* w, float* y, int nz, int rows, int Cin, int Cout, int64_t zx,
                                  int64_t zw, int64_t zy, void* stream) {
-    EGR_CHECK(nz >= 1 && nz <= 65535, EGR_ERR_ARG, "bad nz");
-    return conv_launch(x, w, nullptr, nullptr, nullptr, y, rows, 1, 1, Cin, 1, 1, Cout, 1, 1, 1, 1, 0, 0, 0, 0, 0.f, 1, 1, 0, 0,
-                       1, 1, nz, zx, zw, zy, nullptr, nullptr, 0, stream);
+    ConvCall c;
+    c.x = x; c.w = w; c.y = y; c.B = rows; c.Cin = Cin; c.Cout = Cout; c.nz = nz; c.zx = zx; c.zw = zw; c.zy = zy;
+    return conv_call(c, (hipStream_t)stream);
 }
 
 // Same contraction on the bf16 matrix pipe: w3 = egr_split3_pack(w) (csrc/egr_nn_gemm_s3.hip).  nz > 1: independent
@@ -543,145 +697,44 @@ extern "C" int egr_conv_s3(const float* x, const void* w3, const float* bias, co
                            int pad_t, int pad_l, int up2, int act, float act_param, int osy, int osx, int ooy, int oox,
                            int OHF, int OWF, int nz, int64_t zx, int64_t zw3, int64_t zy, void* stream) {
     EGR_CHECK(w3, EGR_ERR_ARG, "null w3");
-    EGR_CHECK(nz >= 1 && nz <= 65535, EGR_ERR_ARG, "bad nz");
-    return conv_launch(x, nullptr, bias, bias_b, res, y, B, H, W, Cin, OH, OW, Cout, KH, KW, stride, dil, pad_t, pad_l, up2, act,
-                       act_param, osy, osx, ooy, oox, OHF, OWF, nz, zx, zw3, zy, nullptr, nullptr, 0, stream, w3);
+    ConvCall c;
+    c.x = x; c.w3 = w3; c.bias = bias; c.bias_b = bias_b; c.res = res; c.y = y;
+    c.B = B; c.H = H; c.W = W; c.Cin = Cin; c.OH = OH; c.OW = OW; c.Cout = Cout; c.KH = KH; c.KW = KW;
+    c.stride = stride; c.dil = dil; c.pad_t = pad_t; c.pad_l = pad_l; c.up2 = up2; c.act = act; c.act_param = act_param;
+    c.osy = osy; c.osx = osx; c.ooy = ooy; c.oox = oox; c.OHF = OHF; c.OWF = OWF;
+    c.nz = nz; c.zx = zx; c.zw = zw3; c.zy = zy;
+    return conv_call(c, (hipStream_t)stream);
 }
 
-// The same on two fp16 terms per operand (csrc/egr_nn_gemm_s3.hip, scheme 1): w2 = egr_split2h_pack(w, w_scale).  The GEMM rows
-// (B * OH * OW of them) belong to `batch_rows` equal consecutive groups -- the rows of the batch -- and every group is scaled by its
-// own power of two, derived in the kernel from row_amax[group] (bits of the group's max |x|: egr_absmax_rows, or the producer of
-// x); nothing about the scale travels through the host.  out_amax (optional, [batch_rows] floats the caller zeroed): raised to
-// max |y| per batch row by the epilogue (not when the launch takes the split-K path: the caller checks with egr_conv_h2_splits_k).
+// The same on two fp16 terms per operand (csrc/egr_nn_gemm_s3.hip, scheme 1): w2 = egr_split2h_pack(w, w_scale); the scales of the
+// batch rows are derived in the kernel from row_amax (include/egregora_amd.h has the contract).
 extern "C" int egr_conv_h2(const float* x, const void* w2, const float* bias, const float* bias_b, const float* res, float* y,
                            int B, int H, int W, int Cin, int OH, int OW, int Cout, int KH, int KW, int stride, int dil,
                            int pad_t, int pad_l, int up2, int act, float act_param, int osy, int osx, int ooy, int oox,
                            int OHF, int OWF, int nz, int64_t zx, int64_t zw2, int64_t zy, float w_scale, const float* row_amax,
                            int batch_rows, float* out_amax, void* stream) {
     EGR_CHECK(w2 && row_amax, EGR_ERR_ARG, "null w2 / row_amax");
-    EGR_CHECK(nz >= 1 && nz <= 65535, EGR_ERR_ARG, "bad nz");
-    return conv_launch(x, nullptr, bias, bias_b, res, y, B, H, W, Cin, OH, OW, Cout, KH, KW, stride, dil, pad_t, pad_l, up2, act,
-                       act_param, osy, osx, ooy, oox, OHF, OWF, nz, zx, zw2, zy, nullptr, nullptr, 0, stream, w2, 1, w_scale, row_amax,
-                       batch_rows, out_amax);
+    ConvCall c;
+    c.x = x; c.w3 = w2; c.bias = bias; c.bias_b = bias_b; c.res = res; c.y = y;
+    c.B = B; c.H = H; c.W = W; c.Cin = Cin; c.OH = OH; c.OW = OW; c.Cout = Cout; c.KH = KH; c.KW = KW;
+    c.stride = stride; c.dil = dil; c.pad_t = pad_t; c.pad_l = pad_l; c.up2 = up2; c.act = act; c.act_param = act_param;
+    c.osy = osy; c.osx = osx; c.ooy = ooy; c.oox = oox; c.OHF = OHF; c.OWF = OWF;
+    c.nz = nz; c.zx = zx; c.zw = zw2; c.zy = zy;
+    c.sch = 1; c.w_scale = w_scale; c.row_amax = row_amax; c.batch_rows = batch_rows; c.out_amax = out_amax;
+    return conv_call(c, (hipStream_t)stream);
 }
 
-// 3x3 stride-1 pad-1 convolution on two fp16 terms with the producer's GroupNorm (+ SiLU) applied to x while it is loaded:
-// x' = x * gn_scale[b][c] + gn_shift[b][c] (then SiLU), zero padding after it.  Only the input-stationary kernel (k_conv3x3_is)
-// serves it: H %% 4 == 0, W %% 32 == 0, Cin %% 32 == 0, >= 512 tiles of 4 x 32 pixels, otherwise EGR_ERR_UNSUPPORTED (nothing is
-// launched).  row_amax[b] must bound max |x'| of image b from above (egr_gn_operand_bound); it need not be tight.
-// gn_part (optional, [B * H * W / 32][Cout / 4] float2): GroupNorm partial statistics of y, (sum, sum of squares) per 32-pixel row
-// segment and channel quad -- egr_groupnorm_stats_from_partials(part, B, H * W / 32, Cout, G) then gives the statistics of y
-// without a pass over it ((Cout / G) % 4 == 0).
+// 3x3 stride-1 pad-1 convolution on two fp16 terms with the producer's GroupNorm (+ SiLU) applied to x while it is loaded; only the
+// input-stationary kernel (k_conv3x3_isp) serves it, else EGR_ERR_UNSUPPORTED with nothing launched (contract: include/egregora_amd.h).
 extern "C" int egr_conv_h2_gn(const float* x, const float* gn_scale, const float* gn_shift, int gn_silu, const void* w2, const float* bias,
                               const float* res, float* y, int B, int H, int W, int Cin, int Cout, int act, float w_scale, const float* row_amax,
                               float* out_amax, void* gn_part, void* stream) {
     EGR_CHECK(w2 && row_amax && gn_scale && gn_shift, EGR_ERR_ARG, "null w2 / row_amax / gn_scale / gn_shift");
-    return conv_launch(x, nullptr, bias, nullptr, res, y, B, H, W, Cin, H, W, Cout, 3, 3, 1, 1, 1, 1, 0, act, 0.f, 1, 1, 0, 0, H, W, 1, 0, 0, 0,
-                       gn_scale, gn_shift, gn_silu, stream, w2, 1, w_scale, row_amax, B, out_amax, gn_part);
-}
-
-static int conv_launch(const float* x, const float* w, const float* bias, const float* bias_b, const float* res, float* y,
-                       int B, int H, int W, int Cin, int OH, int OW, int Cout, int KH, int KW, int stride, int dil, int pad_t,
-                       int pad_l, int up2, int act, float act_param, int osy, int osx, int ooy, int oox, int OHF, int OWF,
-                       int nz, long long zx, long long zw, long long zy, const float* gn_scale, const float* gn_shift,
-                       int gn_silu, void* stream, const void* w3, int sch, float w_scale, const float* row_amax, int batch_rows,
-                       float* out_amax, void* gn_part) {
-    EGR_CHECK(x && (w || w3) && y, EGR_ERR_ARG, "null x/w/y");
-    EGR_CHECK(sch == 0 || (w3 && w_scale > 0.f && row_amax && batch_rows >= 1 && ((long long)B * OH * OW) % batch_rows == 0), EGR_ERR_ARG,
-              "bad operand scheme: needs w_scale > 0, row_amax and a batch row count that divides the GEMM rows");
-    EGR_CHECK(!w3 || ((Cin % BK) == 0 && (((uintptr_t)x) & 15) == 0 && (((uintptr_t)w3) & 15) == 0 && (!gn_scale || sch == 1)), EGR_ERR_ARG,
-              "split conv needs Cin %% 16 == 0, 16-byte aligned x / w3 and no fused input affine (scheme 1: only the input-stationary 3x3 kernel fuses one)");
-    EGR_CHECK(!gn_scale || (gn_shift && (Cin % BK) == 0 && (((uintptr_t)x) & 15) == 0), EGR_ERR_ARG,
-              "fused input affine needs Cin %% 16 == 0 and a 16-byte aligned input");
-    EGR_CHECK(B >= 1 && H >= 1 && W >= 1 && Cin >= 1 && OH >= 1 && OW >= 1 && Cout >= 1 && KH >= 1 && KW >= 1 &&
-                  stride >= 1 && dil >= 1,
-              EGR_ERR_ARG, "bad conv geometry");
-    const long long M = (long long)B * OH * OW;
-    EGR_CHECK(M < (1LL << 31) && (long long)KH * KW * Cin < (1LL << 31), EGR_ERR_ARG, "conv too large for 32-bit indexing");
-    ConvP p;
-    memset(&p, 0, sizeof(p));
-    p.x = x; p.w = w; p.w3 = (const uint4*)w3; p.bias = bias; p.bias_b = bias_b; p.res = res; p.y = y;
-    p.B = B; p.H = H; p.W = W; p.Cin = Cin; p.OH = OH; p.OW = OW; p.Cout = Cout; p.KH = KH; p.KW = KW;
-    p.stride = stride; p.dil = dil; p.pad_t = pad_t; p.pad_l = pad_l; p.up2 = up2; p.act = act; p.act_param = act_param;
-    p.M = (int)M; p.K = KH * KW * Cin;
-    p.sch = sch; p.out_scale = sch ? 1.0f / w_scale : 1.0f; p.row_amax = sch ? (const unsigned*)row_amax : nullptr;
-    p.rows_div = sch ? (int)(M / batch_rows) : 1;
-    p.out_amax = (sch && nz == 1) ? (unsigned*)out_amax : nullptr;
-    p.gn_part = (float2*)gn_part;
-    EGR_CHECK(osy >= 1 && osx >= 1 && ooy >= 0 && oox >= 0 && (OH - 1) * osy + ooy < OHF && (OW - 1) * osx + oox < OWF,
-              EGR_ERR_ARG, "bad output placement");
-    p.osy = osy; p.osx = osx; p.ooy = ooy; p.oox = oox; p.OHF = OHF; p.OWF = OWF;
-    const bool vec = (Cin % BK) == 0 && (((uintptr_t)x) & 15) == 0;
-    int bn = w3 ? s3_bn(Cout) : (Cout > 64 ? 128 : (Cout > 32 ? 64 : 32));
-    // short-K layers that cannot use split-K (the transformer blocks' linears: a few thousand rows, K <= 496): narrower column
-    // tiles until the grid covers the 256 CUs
-    static const bool narrow = !(getenv("EGR_S3_NARROW") && atoi(getenv("EGR_S3_NARROW")) == 0);
-    if (w3 && narrow && nz <= 1 && (KH * KW * Cin + BK - 1) / BK < 32)
-        while (bn > 64 && ((M + 127) / 128) * ((Cout + bn - 1) / bn) < 256) bn >>= 1;
-    // (fp16 terms: the 256 x 128 tile loses to 128 x 128 on every layer that took it -- short-K streaming GEMMs with 128 outputs, 5 per
-    // forward: 5.1 -> 3.1 ms, profiles/r05/flashsr_kernel_experiments.log item 6 -- half the registers per workgroup, twice the workgroups in flight)
-    int bm = w3 ? (sch ? 128 : s3_bm(M, Cout, bn)) : BM;
-    dim3 grid((unsigned)((M + bm - 1) / bm), (unsigned)((Cout + bn - 1) / bn));
-    hipStream_t st = (hipStream_t)stream;
-    // split-K when the output tiles alone cannot fill the chip and the K loop is long (deep UNet / latent layers)
-    const int tiles = (int)(grid.x * grid.y), ktiles = (p.K + BK - 1) / BK;
-    p.ksplit = 1; p.kt_per = ktiles; p.ws = nullptr;
-    p.zx = zx; p.zw = zw; p.zy = zy;
-    p.gn_scale = gn_scale; p.gn_shift = gn_shift; p.gn_silu = gn_silu;
-    { int zrc = zero_page(&p.zeros); if (zrc) return zrc; }
-    p.nz = nz; p.zs_nzb = 0;
-    if (nz > 1) grid.z = nz;
-    if (w3 && nz > 1 && KH == 1 && KW == 1 && H == 1 && W == 1 && stride == 1 && zw == (long long)(p.K / BK) * Cout * (sch ? 4 : 6) &&
-        !bias && !bias_b && !res && act == 0 && osy == 1 && osx == 1 && OHF == OH && OWF == OW) {
-        p.zs_nzb = s3_zs_nzb(M, Cout, 128, bn, nz, p.K);          // Winograd GEMMs: stream several z per workgroup
-        if (p.zs_nzb > 0) {                                       // (128-row tiles: the 256-row variant would spill)
-            bm = 128;
-            grid.x = (unsigned)((M + bm - 1) / bm);
-            grid.z = (nz + p.zs_nzb - 1) / p.zs_nzb;
-        }
-    }
-    if (nz == 1 && tiles < 192 && ktiles >= 32) {
-        int S = (768 + tiles - 1) / tiles;
-        if (S > ktiles / 8) S = ktiles / 8;
-        if (S > 64) S = 64;
-        if (S >= 2) {
-            const int per = (ktiles + S - 1) / S;
-            S = (ktiles + per - 1) / per;
-            float* ws = nullptr;
-            int rc = splitk_workspace((size_t)S * M * Cout * sizeof(float), st, &ws);
-            if (rc) return rc;
-            p.ksplit = S; p.kt_per = per; p.ws = ws;
-            grid.z = S;
-            // (with out_amax: the reduction kernel writes y and tracks the row maxima)
-            EGR_CHECK(!p.out_amax || batch_rows <= 1024, EGR_ERR_UNSUPPORTED, "out_amax with split-K serves up to 1024 batch rows");
-        }
-    }
-#define LAUNCH(BN_, V_) hipLaunchKernelGGL((k_conv_igemm<BN_, V_>), grid, dim3(256), 0, st, p)
-    if (w3 && launch_conv3x3_is(p, st)) {}
-    else if (w3 && gn_scale) {
-        set_error("egr_conv_h2_gn: the shape does not qualify for the input-stationary 3x3 kernel (stride 1, pad 1, H %% 4 == 0, W %% 32 == 0, "
-                  "Cin %% 32 == 0, >= 512 tiles, one batch row per image)");
-        return EGR_ERR_UNSUPPORTED;
-    }
-    else if (w3 && launch_conv1d_s3(p, st)) {}
-    else if (w3) launch_conv_s3(bm, bn, grid, st, p);
-    else if (gn_scale) {        // fused-GroupNorm loader: separate instantiations so the plain kernels pay nothing for it
-        if (bn == 128) hipLaunchKernelGGL((k_conv_igemm<128, true, true>), grid, dim3(256), 0, st, p);
-        else if (bn == 64) hipLaunchKernelGGL((k_conv_igemm<64, true, true>), grid, dim3(256), 0, st, p);
-        else hipLaunchKernelGGL((k_conv_igemm<32, true, true>), grid, dim3(256), 0, st, p);
-    } else
-    if (bn == 128) { if (vec) LAUNCH(128, true); else LAUNCH(128, false); }
-    else if (bn == 64) { if (vec) LAUNCH(64, true); else LAUNCH(64, false); }
-    else { if (vec) LAUNCH(32, true); else LAUNCH(32, false); }
-#undef LAUNCH
-    if (p.ksplit > 1) {
-        long long nb = (M * Cout + 255) / 256;
-        if (nb > 2048) nb = 2048;
-        if (p.out_amax) hipLaunchKernelGGL(k_splitk_reduce<true>, dim3((unsigned)nb), dim3(256), 0, st, p);
-        else hipLaunchKernelGGL(k_splitk_reduce<false>, dim3((unsigned)nb), dim3(256), 0, st, p);
-    }
-    EGR_HIP(hipGetLastError());
-    return EGR_OK;
+    ConvCall c;
+    c.x = x; c.w3 = w2; c.bias = bias; c.res = res; c.y = y; c.gn_scale = gn_scale; c.gn_shift = gn_shift; c.gn_silu = gn_silu;
+    c.B = B; c.H = c.OH = c.OHF = H; c.W = c.OW = c.OWF = W; c.Cin = Cin; c.Cout = Cout; c.KH = c.KW = 3; c.pad_t = c.pad_l = 1; c.act = act;
+    c.sch = 1; c.w_scale = w_scale; c.row_amax = row_amax; c.batch_rows = B; c.out_amax = out_amax; c.gn_part = gn_part;
+    return conv_call(c, (hipStream_t)stream);
 }
 
 extern "C" int egr_bgemm(const float* a, const float* b, float* c, int nb1, int nb2, int M, int N, int K, int lda,

@@ -581,34 +581,31 @@ int s3_zs_nzb(long long M, int Cout, int bm, int bn, int nz, int K) {
     return nzb >= 2 ? nzb : 0;
 }
 
-void launch_conv_s3(int bm, int bn, dim3 grid, hipStream_t st, const ConvP& p_in) {
+// prefetch depth of the bf16-term 128-row kernels with 32 / 64 / 128 columns (the other instantiations exist with 1 only)
+int s3_pf() {
     static const int pf = getenv("EGR_S3_PF") ? atoi(getenv("EGR_S3_PF")) : 1;
+    return pf == 2 ? 2 : 1;
+}
+
+void launch_conv_s3(const ConvChoice& k, hipStream_t st, const ConvP& p_in) {
     static const bool remap = !(getenv("EGR_S3_XCD") && atoi(getenv("EGR_S3_XCD")) == 0);
     ConvP p = p_in;
-    p.xcd_remap = (remap && grid.y > 1 && ((grid.x * grid.y) & 7) == 0) ? 1 : 0;
-    if (p.sch) {                                  // two-term fp16 scheme (PF = 1 only)
-        if (p.zs_nzb > 0) {
-            if (bn == 256) hipLaunchKernelGGL((k_conv_s3<128, 256, 1, true, 1>), grid, dim3(256), 0, st, p);
-            else hipLaunchKernelGGL((k_conv_s3<128, 128, 1, true, 1>), grid, dim3(256), 0, st, p);
-        } else if (bn == 256) hipLaunchKernelGGL((k_conv_s3<128, 256, 1, false, 1>), grid, dim3(256), 0, st, p);
-        else if (bn == 128) hipLaunchKernelGGL((k_conv_s3<128, 128, 1, false, 1>), grid, dim3(256), 0, st, p);
-        else if (bn == 64) hipLaunchKernelGGL((k_conv_s3<128, 64, 1, false, 1>), grid, dim3(256), 0, st, p);
-        else hipLaunchKernelGGL((k_conv_s3<128, 32, 1, false, 1>), grid, dim3(256), 0, st, p);
-        return;
-    }
-    if (p.zs_nzb > 0) {
-        if (bn == 256) hipLaunchKernelGGL((k_conv_s3<128, 256, 1, true>), grid, dim3(256), 0, st, p);
-        else hipLaunchKernelGGL((k_conv_s3<128, 128, 1, true>), grid, dim3(256), 0, st, p);
-        return;
-    }
-    if (bn == 256) {
-        hipLaunchKernelGGL((k_conv_s3<128, 256, 1>), grid, dim3(256), 0, st, p);
-        return;
-    }
-    if (bm == 256) hipLaunchKernelGGL((k_conv_s3<256, 128, 1>), grid, dim3(256), 0, st, p);
-    else if (bn == 128) { if (pf == 2) hipLaunchKernelGGL((k_conv_s3<128, 128, 2>), grid, dim3(256), 0, st, p); else hipLaunchKernelGGL((k_conv_s3<128, 128, 1>), grid, dim3(256), 0, st, p); }
-    else if (bn == 64) { if (pf == 2) hipLaunchKernelGGL((k_conv_s3<128, 64, 2>), grid, dim3(256), 0, st, p); else hipLaunchKernelGGL((k_conv_s3<128, 64, 1>), grid, dim3(256), 0, st, p); }
-    else { if (pf == 2) hipLaunchKernelGGL((k_conv_s3<128, 32, 2>), grid, dim3(256), 0, st, p); else hipLaunchKernelGGL((k_conv_s3<128, 32, 1>), grid, dim3(256), 0, st, p); }
+    p.xcd_remap = (remap && k.grid.y > 1 && ((k.grid.x * k.grid.y) & 7) == 0) ? 1 : 0;
+    const int bn = k.bn;
+#define S3_LAUNCH(BM_, BN_, PF_, ZS_, SCH_) hipLaunchKernelGGL((k_conv_s3<BM_, BN_, PF_, ZS_, SCH_>), k.grid, dim3(256), 0, st, p)
+    if (k.sch) {                                  // two-term fp16 scheme (PF = 1, 128 rows only)
+        if (k.zs) { if (bn == 256) S3_LAUNCH(128, 256, 1, true, 1); else S3_LAUNCH(128, 128, 1, true, 1); }
+        else if (bn == 256) S3_LAUNCH(128, 256, 1, false, 1);
+        else if (bn == 128) S3_LAUNCH(128, 128, 1, false, 1);
+        else if (bn == 64) S3_LAUNCH(128, 64, 1, false, 1);
+        else S3_LAUNCH(128, 32, 1, false, 1);
+    } else if (k.zs) { if (bn == 256) S3_LAUNCH(128, 256, 1, true, 0); else S3_LAUNCH(128, 128, 1, true, 0); }
+    else if (bn == 256) S3_LAUNCH(128, 256, 1, false, 0);
+    else if (k.bm == 256) S3_LAUNCH(256, 128, 1, false, 0);
+    else if (bn == 128) { if (k.pf == 2) S3_LAUNCH(128, 128, 2, false, 0); else S3_LAUNCH(128, 128, 1, false, 0); }
+    else if (bn == 64) { if (k.pf == 2) S3_LAUNCH(128, 64, 2, false, 0); else S3_LAUNCH(128, 64, 1, false, 0); }
+    else { if (k.pf == 2) S3_LAUNCH(128, 32, 2, false, 0); else S3_LAUNCH(128, 32, 1, false, 0); }
+#undef S3_LAUNCH
 }
 
 }  // namespace egr
@@ -849,18 +846,23 @@ __global__ __launch_bounds__(256, 2) void k_conv1d_s3(ConvP p) {
     }
 }
 
-// true when the input-stationary 1-D kernel applies; launches it
-bool launch_conv1d_s3(const ConvP& p, hipStream_t st) {
+// true when the input-stationary 1-D kernel applies: k then holds its instantiation and grid
+bool conv1d_s3_applies(const ConvP& p, ConvChoice& k) {
     static const bool off = getenv("EGR_S3_CONV1D") && atoi(getenv("EGR_S3_CONV1D")) == 0;
     if (off || !p.w3 || p.H != 1 || p.KH != 1 || p.KW < 2 || p.stride != 1 || p.up2 || p.OW != p.W || (p.W % 128) != 0 ||
-        p.dil * (p.KW - 1) > 50 || 2 * p.pad_l != p.dil * (p.KW - 1) || (p.Cin % 16) != 0 || p.ksplit > 1 || p.zs_nzb > 0 ||
-        p.nz > 1 || p.osy != 1 || p.osx != 1 || p.OHF != p.OH || p.OWF != p.OW || (p.sch && (p.rows_div % 128) != 0))
+        p.dil * (p.KW - 1) > 50 || 2 * p.pad_l != p.dil * (p.KW - 1) || (p.Cin % 16) != 0 || k.ksplit > 1 || k.zs_nzb > 0 ||
+        p.nz > 1 || p.osy != 1 || p.osx != 1 || p.OHF != p.OH || p.OWF != p.OW || (p.sch && (p.rows_div % 128) != 0) || p.B > 65535)
         return false;
-    const int bn = p.Cout > 64 ? 128 : (p.Cout > 32 ? 64 : 32);
-    const dim3 grid(p.W / 128, (p.Cout + bn - 1) / bn, p.B);
-    if (p.B > 65535) return false;
+    k.bn = p.Cout > 64 ? 128 : (p.Cout > 32 ? 64 : 32);
+    k.cc = p.Cin % 32 == 0 ? 32 : 16;
+    k.grid = dim3(p.W / 128, (p.Cout + k.bn - 1) / k.bn, p.B);
+    return true;
+}
+
+void launch_conv1d_s3(const ConvChoice& k, hipStream_t st, const ConvP& p) {
+    const int bn = k.bn; const dim3 grid = k.grid;
 #define C1_LAUNCH(SCH_)                                                                                   \
-    if (p.Cin % 32 == 0) {                                                                                \
+    if (k.cc == 32) {                                                                                     \
         if (bn == 128) hipLaunchKernelGGL((k_conv1d_s3<128, 32, SCH_>), grid, dim3(256), 0, st, p);       \
         else if (bn == 64) hipLaunchKernelGGL((k_conv1d_s3<64, 32, SCH_>), grid, dim3(256), 0, st, p);    \
         else hipLaunchKernelGGL((k_conv1d_s3<32, 32, SCH_>), grid, dim3(256), 0, st, p);                  \
@@ -871,7 +873,6 @@ bool launch_conv1d_s3(const ConvP& p, hipStream_t st) {
     }
     if (p.sch) { C1_LAUNCH(1) } else { C1_LAUNCH(0) }
 #undef C1_LAUNCH
-    return true;
 }
 
 }  // namespace egr

@@ -81,6 +81,8 @@ SIGNATURES = {
     "egr_conv_nhwc_placed": (_i, [_vp] * 6 + [_i] * 15 + [_f] + [_i] * 6 + [_vp]),
     "egr_split3_pack": (_i, [_vp, _vp, _i64, _i, _vp]),
     "egr_conv_s3": (_i, [_vp] * 6 + [_i] * 15 + [_f] + [_i] * 7 + [_i64] * 3 + [_vp]),
+    "egr_conv_kernel_name": (_i, [_vp, C.c_char_p, C.c_size_t, C.POINTER(_i), C.POINTER(_i)]),
+    "egr_conv_last_kernel": (C.c_char_p, []),
     "egr_split2h_pack": (_i, [_vp, _vp, _i64, _i, _f, _vp]),
     "egr_absmax": (_i, [_vp, _i64, _vp, _vp]),
     "egr_absmax_rows": (_i, [_vp, _i, _i64, _i, _i64, _vp, _vp]),
@@ -171,6 +173,32 @@ class FlashSRConfigC(C.Structure):
 class TensorDescC(C.Structure):
     """egr_tensor_desc."""
     _fields_ = [("name", C.c_char_p), ("data", _vp), ("ndim", _i), ("shape", _i64 * 4)]
+
+
+class ConvDescC(C.Structure):
+    """egr_conv_desc (include/egregora_amd.h): one convolution call as data."""
+    _fields_ = ([(n, _vp) for n in ("x", "w", "w3", "bias", "bias_b", "res", "y")] +
+                [(n, _i) for n in ("B", "H", "W", "Cin", "OH", "OW", "Cout", "KH", "KW", "stride", "dil", "pad_t", "pad_l", "up2", "act")] +
+                [("act_param", _f)] + [(n, _i) for n in ("osy", "osx", "ooy", "oox", "OHF", "OWF", "nz")] +
+                [("zx", _i64), ("zw", _i64), ("zy", _i64), ("gn_scale", _vp), ("gn_shift", _vp), ("gn_silu", _i), ("sch", _i),
+                 ("w_scale", _f), ("row_amax", _vp), ("batch_rows", _i), ("out_amax", _vp), ("gn_part", _vp)])
+
+
+def conv_kernel_name(**fields):
+    """(name, ksplit, zs_nzb) of the kernel the library's launcher picks for the call `fields` describes (egr_conv_kernel_name: host
+    only).  Defaults: one 1x1 stride-1 problem, identity placement (OHF / OWF follow OH / OW); pointers are never dereferenced."""
+    d = ConvDescC(B=1, H=1, W=1, OH=1, OW=1, KH=1, KW=1, stride=1, dil=1, osy=1, osx=1, nz=1, w_scale=1.0)
+    for k, v in fields.items():
+        setattr(d, k, v)
+    d.OHF, d.OWF = fields.get("OHF", d.OH), fields.get("OWF", d.OW)
+    buf, ks, zs = C.create_string_buffer(96), _i(), _i()
+    check(lib().egr_conv_kernel_name(C.byref(d), buf, 96, C.byref(ks), C.byref(zs)), "egr_conv_kernel_name")
+    return buf.value.decode(), ks.value, zs.value
+
+
+def last_conv_kernel() -> str:
+    """Name of the kernel this thread's last convolution launch ran (egr_conv_last_kernel)."""
+    return lib().egr_conv_last_kernel().decode()
 
 
 DFN3_MAX_ERB = 64

@@ -412,6 +412,29 @@ int egr_conv_s3(const float* x, const void* w3, const float* bias, const float* 
                 int up2, int act, float act_param, int osy, int osx, int ooy, int oox, int OHF, int OWF, int nz, int64_t zx,
                 int64_t zw3, int64_t zy, void* stream);
 
+/* One convolution call as data: the union of what egr_conv_nhwc / _placed / _gn, egr_conv_s3, egr_conv_h2 / _gn and
+ * egr_gemm_zbatched accept (those functions fill it and hand it to one launcher, csrc/egr_nn_gemm.hip).  w3 is the split pack of
+ * either scheme (sch 0: egr_split3_pack, three bf16 terms; sch 1: egr_split2h_pack, two fp16 terms) and zw counts floats of w or
+ * 16-byte units of w3. */
+typedef struct egr_conv_desc {
+    const float* x; const float* w; const void* w3; const float* bias; const float* bias_b; const float* res; float* y;
+    int B, H, W, Cin, OH, OW, Cout, KH, KW, stride, dil, pad_t, pad_l, up2, act;
+    float act_param;
+    int osy, osx, ooy, oox, OHF, OWF;
+    int nz;
+    int64_t zx, zw, zy;
+    const float* gn_scale; const float* gn_shift; int gn_silu;
+    int sch; float w_scale; const float* row_amax; int batch_rows; float* out_amax; void* gn_part;
+} egr_conv_desc;
+/* Host only (no GPU is touched, nothing is dereferenced: of the pointers only null / non-null and the alignment of x and w3 count):
+ * the kernel instantiation the launcher would run for `d`, spelled as rocprofv3 prints it ("k_conv_s3<128, 256, 1, false, 1>"),
+ * with its split-K factor (1: none) and the z problems a workgroup streams (0: one).  Bad descriptions and shapes no kernel serves
+ * fail exactly as the launch would.  The EGR_S3_* environment switches are read once per process. */
+int egr_conv_kernel_name(const egr_conv_desc* d, char* name, size_t buflen, int* ksplit, int* zs_nzb);
+/* The name, spelled the same way, of the kernel the calling thread's last convolution launch (any egr_conv_* / egr_gemm_zbatched
+ * entry point) ran; "" before the first.  The string is the thread's own and valid until its next launch. */
+const char* egr_conv_last_kernel(void);
+
 /* Winograd F(2x2,3x3) for stride-1 pad-1 3x3 convolutions with many channels (2.25x fewer multiplies):
  *   egr_winograd_input : x [B][H][W][C] -> V [16][P][C], P = B*ceil(H/2)*ceil(W/2) tiles, V[4i+j] = (B^T d B)[i][j]
  *   egr_gemm_zbatched  : M[xi] = V[xi] ([P][Cin]) x U[xi] ([Cin][Cout], each packed like egr_conv_nhwc weights), xi < nz

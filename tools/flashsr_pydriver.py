@@ -7,8 +7,6 @@ csrc/egr_flashsr_pack.hip with the handle, so both hold identical operands, and 
 bit-for-bit equal to egr_flashsr_forward.  Nothing under comfyui-egregora-audio-super-resolution_amd/ imports this file.
 """
 import ctypes as C
-import math
-import os
 import sys
 from pathlib import Path
 from typing import Dict, List, Optional
@@ -32,7 +30,7 @@ class PyDriverEngine(E.FlashSREngine):
         super().__init__(cfg, params, device)
         self.flops = 0.0            # dense-contraction flops of the last forward (per call, all rows)
         self.count_flops = False
-        self.prof = None            # when a list: (kind, flops, start_event, end_event) per MFMA kernel launch
+        self.prof = None            # when a list: (kernel name, flops, start_event, end_event, shape) per MFMA kernel launch
         self.blocks = arch.unet_blocks(cfg)
         # packed fp32 weights, bf16x3 splits, Winograd U, folded time embedding: built on first use of self.w / w3 / wz / wshape
         self._w: Dict[str, torch.Tensor] = {}
@@ -175,15 +173,7 @@ class PyDriverEngine(E.FlashSREngine):
         else:
             native.check(self.L.egr_gemm_zbatched(_p(V), _p(self.w[wkey]), _p(Mx), nz, P, Cin, Cout, P * Cin, zw, P * Cout,
                                                   self._st()), "egr_gemm_zbatched")
-        if ev is not None:
-            kind = self._kind(P, Cin, Cout, w3 is not None)
-            if w3 is not None and Cout > 64:        # s3_zs_nzb (csrc/egr_nn_gemm_s3.hip): z-streamed when >= 2 z per workgroup
-                bn = 256 if (Cout >= 256 and Cout % 256 == 0) else 128
-                tiles = ((P + 127) // 128) * ((Cout + bn - 1) // bn)
-                groups = min(max((2048 + tiles - 1) // tiles, 1), nz)
-                if (nz + groups - 1) // groups >= 2 and not (bn == 256 and Cin > 256):
-                    kind = f"k_conv_s3<128, {bn}, 1, true>"
-            self._prof_end(ev, kind, fl, (B, H, W, Cin, H, W, Cout, 3, 3, 1, 1, nz))
+        self._prof_end(ev, fl, (B, H, W, Cin, H, W, Cout, 3, 3, 1, 1, nz))
         if self.count_flops:
             self.flops += fl
         y = torch.empty((B, H, W, Cout), dtype=torch.float32, device=self.dev)
@@ -200,7 +190,6 @@ class PyDriverEngine(E.FlashSREngine):
             native.check(fn_out(_p(Mx), _p(bt), _p(res), _p(y), B, H, W, Cout, 1 if act == ACT_SILU else 0, self._st()),
                          "egr_winograd_output")
         return y
-
 
     def add_weight(self, key: str, v: torch.Tensor):
         """Register a weight given in torch layout; self.w[key] holds the packed tensor, self.wshape[key] the
@@ -258,30 +247,10 @@ class PyDriverEngine(E.FlashSREngine):
             native.check(self.L.egr_conv_nhwc(_p(x), _p(wt), _p(bt), _p(None), _p(res), _p(y), B, H, W, Cin, OH, OW, Cout, KH,
                                               KW, stride, dil, pad_t, pad_l, up2, act, float(act_param), self._st()),
                          "egr_conv_nhwc")
-        if ev is not None:
-            vec = Cin % 16 == 0 and x.data_ptr() % 16 == 0
-            kind = self._kind(B * OH * OW, Cin, Cout, w3 is not None, vec, KH * KW * Cin)
-            if (w3 is not None and H == 1 and KH == 1 and KW >= 2 and stride == 1 and not up2 and OW == W and W % 128 == 0
-                    and dil * (KW - 1) <= 50 and 2 * pad_l == dil * (KW - 1)):       # launch_conv1d_s3's conditions
-                kind = f"k_conv1d_s3<{128 if Cout > 64 else (64 if Cout > 32 else 32)}, {32 if Cin % 32 == 0 else 16}>"
-            self._prof_end(ev, kind, fl, (B, H, W, Cin, OH, OW, Cout, KH, KW, stride, dil, up2))
+        self._prof_end(ev, fl, (B, H, W, Cin, OH, OW, Cout, KH, KW, stride, dil, up2))
         if self.count_flops:
             self.flops += fl
         return y
-
-    @staticmethod
-    def _kind(M, Cin, Cout, s3, vec=True, K=None):
-        """Name of the kernel instantiation a contraction lands on (same selection as conv_launch, csrc/egr_nn_gemm.hip)."""
-        bn = 128 if Cout > 64 else (64 if Cout > 32 else 32)
-        if s3:
-            if Cout >= 256 and Cout % 256 == 0:         # s3_bn
-                bn = 256
-            if K is not None and (K + 15) // 16 < 32:   # short-K, under-filled grid: narrower column tiles
-                while bn > 64 and ((M + 127) // 128) * ((Cout + bn - 1) // bn) < 256:
-                    bn >>= 1
-            bm = 256 if (bn == 128 and ((M + 255) // 256) * ((Cout + 127) // 128) >= 1024) else 128
-            return f"k_conv_s3<{bm}, {bn}, 1, false>"        # <BM, BN, PF, ZS> as rocprofv3 prints the instantiation
-        return f"k_conv_igemm<{bn}, {'true' if vec else 'false'}>"
 
     def _prof_begin(self):
         if self.prof is None:
@@ -290,12 +259,13 @@ class PyDriverEngine(E.FlashSREngine):
         ev.record()                      # torch's current stream == the stream the kernel is launched on
         return ev
 
-    def _prof_end(self, ev, kind, flops, shape=None):
+    def _prof_end(self, ev, flops, shape=None):
+        """Closes the record of the convolution just launched under the name the library's launcher gave its kernel."""
         if ev is None:
             return
         e2 = torch.cuda.Event(enable_timing=True)
         e2.record()
-        self.prof.append((kind, flops, ev, e2, shape))
+        self.prof.append((native.last_conv_kernel(), flops, ev, e2, shape))
 
     def prof_summary(self):
         """{kind: (launches, total_flops, total_ms)} from the events collected while self.prof was a list."""
@@ -352,9 +322,7 @@ class PyDriverEngine(E.FlashSREngine):
                                                              _p(None), _p(y), B, H, W, Cin, H, W, Cout, 2, 2, 1, 1, 1 - a, 1 - b,
                                                              0, act, 0.0, 2, 2, a, b, 2 * H, 2 * W, self._st()),
                                  "egr_conv_nhwc_placed")
-                if ev is not None:
-                    self._prof_end(ev, self._kind(B * H * W, Cin, Cout, w3 is not None, Cin % 16 == 0, 4 * Cin), fl,
-                                   (B, H, W, Cin, H, W, Cout, 2, 2, 1, 1, 2))
+                self._prof_end(ev, fl, (B, H, W, Cin, H, W, Cout, 2, 2, 1, 1, 2))
                 if self.count_flops:
                     self.flops += fl
         return y
@@ -440,13 +408,10 @@ class PyDriverEngine(E.FlashSREngine):
         ev = self._prof_begin()
         native.check(self.L.egr_conv_nhwc_gn(_p(x), _p(sc), _p(sh), 1, _p(self.w[conv_key + ".weight"]), _p(bt), _p(res), _p(y),
                                              B, H, W, Cin, H, W, Cout, 3, 3, 1, 1, 1, ACT_NONE, self._st()), "egr_conv_nhwc_gn")
-        if ev is not None:
-            bn = 128 if Cout > 64 else (64 if Cout > 32 else 32)
-            self._prof_end(ev, f"k_conv_igemm<{bn}, true>", fl, (B, H, W, Cin, H, W, Cout, 3, 3, 1, 1, 0))
+        self._prof_end(ev, fl, (B, H, W, Cin, H, W, Cout, 3, 3, 1, 1, 0))
         if self.count_flops:
             self.flops += fl
         return y
-
 
     def layernorm(self, x2, key):
         rows, Cc = x2.shape

@@ -41,16 +41,18 @@ int main(int argc, char** argv) {
     if (getenv("S3_XCD")) p.xcd_remap = 1;
     const int bn = getenv("S3_BN") ? atoi(getenv("S3_BN")) : (Co > 64 ? 128 : (Co > 32 ? 64 : 32));
     const int bm = getenv("S3_BM") ? atoi(getenv("S3_BM")) : egr::s3_bm(M, Co, bn);
-    dim3 grid((unsigned)((M + bm - 1) / bm), (unsigned)((Co + bn - 1) / bn));
+    egr::ConvChoice kc;
+    kc.bm = bm; kc.bn = bn; kc.sch = sch; kc.pf = (sch || bn == 256 || bm == 256) ? 1 : egr::s3_pf();
+    kc.grid = dim3((unsigned)((M + bm - 1) / bm), (unsigned)((Co + bn - 1) / bn));
     hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
-    egr::launch_conv_s3(bm, bn, grid, 0, p); hipDeviceSynchronize();
+    egr::launch_conv_s3(kc, 0, p); hipDeviceSynchronize();
     hipEventRecord(e0);
-    for (int i = 0; i < reps; ++i) egr::launch_conv_s3(bm, bn, grid, 0, p);
+    for (int i = 0; i < reps; ++i) egr::launch_conv_s3(kc, 0, p);
     hipEventRecord(e1); hipDeviceSynchronize();
     float ms; hipEventElapsedTime(&ms, e0, e1); ms /= reps;
     if (getenv("S3_CHECK")) {          // determinism: a second launch into another buffer must match bit for bit
         float* y2; hipMalloc(&y2, M * Co * 4); hipMemset(y2, 0xff, M * Co * 4);
-        egr::ConvP q = p; q.y = y2; egr::launch_conv_s3(bm, bn, grid, 0, q); hipDeviceSynchronize();
+        egr::ConvP q = p; q.y = y2; egr::launch_conv_s3(kc, 0, q); hipDeviceSynchronize();
         std::vector<float> ha(M * Co), hb(M * Co);
         hipMemcpy(ha.data(), y, M * Co * 4, hipMemcpyDeviceToHost); hipMemcpy(hb.data(), y2, M * Co * 4, hipMemcpyDeviceToHost);
         long long bad = 0; for (long long i = 0; i < M * Co; ++i) bad += memcmp(&ha[i], &hb[i], 4) != 0;
