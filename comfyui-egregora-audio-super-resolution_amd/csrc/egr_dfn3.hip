@@ -36,7 +36,8 @@ static_assert(GRU_NGLB % GRU_K == 0 && GRU_NGLB > 0, "streamed W_hh part is whol
 constexpr int DFN_LDS_MAX = 152 * 1024;                     // dynamic LDS cap: a gfx950 CU's 160 KiB minus room for static arrays
 
 // ------------------------------------------------------------------------------------------------ analysis / features
-__global__ __launch_bounds__(256) void k_dfn_analysis(const float* __restrict__ x, int64_t T, int nF, int N, int hop,
+// Block (f, b) analyses frame f0 + f of channel b into row f of spec [C][nF][Fq] (f0 = 0: the whole file; a segment otherwise).
+__global__ __launch_bounds__(256) void k_dfn_analysis(const float* __restrict__ x, int64_t T, int nF, int64_t f0, int N, int hop,
                                                        const double2* __restrict__ tw, const float* __restrict__ win, float wnorm,
                                                        float2* __restrict__ spec) {
     extern __shared__ double sm[];
@@ -44,7 +45,7 @@ __global__ __launch_bounds__(256) void k_dfn_analysis(const float* __restrict__ 
     double2* tws = (double2*)(sm + N);     // N twiddles
     const int f = blockIdx.x, b = blockIdx.y, Fq = N / 2 + 1;
     const float* xb = x + (int64_t)b * T;
-    const int64_t s0 = (int64_t)f * hop - (N - hop);
+    const int64_t s0 = (f0 + f) * hop - (N - hop);
     for (int n = threadIdx.x; n < N; n += blockDim.x) {
         const int64_t s = s0 + n;
         fr[n] = (s >= 0 && s < T) ? (double)(xb[s] * win[n]) : 0.0;
@@ -80,58 +81,75 @@ __global__ void k_dfn_erb_db(const float2* __restrict__ spec, int64_t rows, int 
 
 // lane < E: ERB dB lane (state s0 = linspace(-60, -90)), out (x - s) / 40; lane >= E: complex bin lane - E (state linspace(1e-3, 1e-4)),
 // out x / sqrt(s).  Output frame t - la (DfNet.pad_feat); the last la frames are zero.
-__global__ void k_dfn_norm_scan(const float* __restrict__ db, const float2* __restrict__ spec, int C, int nF, int Fq, int E, int nbdf,
-                                float alpha, int la, float* __restrict__ ferb, float2* __restrict__ fspec) {
+// The scan reads `cnt` input rows from row src0 of db / spec ([C][nS] rows) and stores input row t at row t + shift of ferb / fspec
+// ([C][nD] rows) when that is >= 0; rows [zlo, zhi) of the destination are zeroed.  The whole file: src0 = 0, cnt = nS = nD = nF,
+// shift = -la, zlo = max(nF - la, 0), zhi = nF, state null.  A segment continues the lane states in state [C][E + nbdf] (read unless
+// `init`, which starts from the linspace values; written back at the end).
+struct ScanArgs {
+    const float* db; const float2* spec; float* ferb; float2* fspec; float* state;
+    int C, nS, src0, cnt, nD, shift, zlo, zhi, Fq, E, nbdf, la, init;
+    float alpha;
+};
+
+__global__ void k_dfn_norm_scan(ScanArgs p) {
+    const int E = p.E, nbdf = p.nbdf, Fq = p.Fq, cnt = p.cnt;
     const int lanes = E + nbdf;
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= C * lanes) return;
+    if (i >= p.C * lanes) return;
     const int b = i / lanes, l = i - b * lanes;
-    const float a = alpha, a1 = 1.f - alpha;
+    const float a = p.alpha, a1 = 1.f - p.alpha;
     constexpr int U = 16;
     if (l < E) {
         float s = -60.f + (-90.f + 60.f) * (E > 1 ? (float)l / (float)(E - 1) : 0.f);
-        const float* src = db + (int64_t)b * nF * E + l;
-        float* dst = ferb + (int64_t)b * nF * E + l;
-        for (int t0 = 0; t0 < nF; t0 += U) {
+        if (!p.init) s = p.state[i];
+        const float* src = p.db + ((int64_t)b * p.nS + p.src0) * E + l;
+        float* dst = p.ferb + (int64_t)b * p.nD * E + l;
+        for (int t0 = 0; t0 < cnt; t0 += U) {
             float v[U];
 #pragma unroll
-            for (int u = 0; u < U; ++u) v[u] = (t0 + u < nF) ? src[(int64_t)(t0 + u) * E] : 0.f;
+            for (int u = 0; u < U; ++u) v[u] = (t0 + u < cnt) ? src[(int64_t)(t0 + u) * E] : 0.f;
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 const int t = t0 + u;
-                if (t < nF) {
+                if (t < cnt) {
                     s = v[u] * a1 + s * a;
-                    if (t - la >= 0) dst[(int64_t)(t - la) * E] = (v[u] - s) / 40.f;
+                    if (t + p.shift >= 0) dst[(int64_t)(t + p.shift) * E] = (v[u] - s) / 40.f;
                 }
             }
         }
-        for (int t = (nF - la > 0 ? nF - la : 0); t < nF; ++t) dst[(int64_t)t * E] = 0.f;
+        for (int t = p.zlo; t < p.zhi; ++t) dst[(int64_t)t * E] = 0.f;
+        if (p.state) p.state[i] = s;
     } else {
         const int f = l - E;
         float s = 0.001f + (0.0001f - 0.001f) * (nbdf > 1 ? (float)f / (float)(nbdf - 1) : 0.f);
-        const float2* src = spec + (int64_t)b * nF * Fq + f;
-        float2* dst = fspec + (int64_t)b * nF * nbdf + f;
-        for (int t0 = 0; t0 < nF; t0 += U) {
+        if (!p.init) s = p.state[i];
+        const float2* src = p.spec + ((int64_t)b * p.nS + p.src0) * Fq + f;
+        float2* dst = p.fspec + (int64_t)b * p.nD * nbdf + f;
+        for (int t0 = 0; t0 < cnt; t0 += U) {
             float2 v[U];
 #pragma unroll
-            for (int u = 0; u < U; ++u) v[u] = (t0 + u < nF) ? src[(int64_t)(t0 + u) * Fq] : make_float2(0.f, 0.f);
+            for (int u = 0; u < U; ++u) v[u] = (t0 + u < cnt) ? src[(int64_t)(t0 + u) * Fq] : make_float2(0.f, 0.f);
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 const int t = t0 + u;
-                if (t < nF) {
+                if (t < cnt) {
                     s = hypotf(v[u].x, v[u].y) * a1 + s * a;
                     const float r = sqrtf(s);
-                    if (t - la >= 0) dst[(int64_t)(t - la) * nbdf] = make_float2(v[u].x / r, v[u].y / r);
+                    if (t + p.shift >= 0) dst[(int64_t)(t + p.shift) * nbdf] = make_float2(v[u].x / r, v[u].y / r);
                 }
             }
         }
-        for (int t = (nF - la > 0 ? nF - la : 0); t < nF; ++t) dst[(int64_t)t * nbdf] = make_float2(0.f, 0.f);
+        for (int t = p.zlo; t < p.zhi; ++t) dst[(int64_t)t * nbdf] = make_float2(0.f, 0.f);
+        if (p.state) p.state[i] = s;
     }
 }
 
 // ------------------------------------------------------------------------------------------------ convolutions (NHWC: [B][T][F][C])
+// t0 is the global frame index of row 0 of x and y (0: the whole file), hist [B][kt - 1][Fin][Cin] the kt - 1 input rows in front of
+// row 0 (read only where the global index is >= 0; null with t0 = 0).
 struct ConvArgs {
-    const float* x; const float* w; const float* scale; const float* shift; const float* res; float* y;
+    const float* x; const float* w; const float* scale; const float* shift; const float* res; float* y; const float* hist;
+    int64_t t0;
     int B, T, Fin, Cin, Fout, Cout, groups, kt, kf, fstride, fpad, transposed, act;
 };
 
@@ -158,11 +176,13 @@ __global__ void k_dfn_conv(ConvArgs p) {
             const float* wc = p.w + (int64_t)co * cig * p.kt * p.kf;
             for (int it = 0; it < p.kt; ++it) {
                 const int ti = t - (p.kt - 1) + it;
-                if (ti < 0) continue;
+                if (p.t0 + ti < 0) continue;
+                const float* xr = ti >= 0 ? p.x + ((int64_t)b * p.T + ti) * p.Fin * p.Cin
+                                          : p.hist + ((int64_t)b * (p.kt - 1) + (ti + p.kt - 1)) * p.Fin * p.Cin;
                 for (int j = 0; j < p.kf; ++j) {
                     const int fi = fo * p.fstride - p.fpad + j;
                     if (fi < 0 || fi >= p.Fin) continue;
-                    const float* xv = p.x + (((int64_t)b * p.T + ti) * p.Fin + fi) * p.Cin + g * cig;
+                    const float* xv = xr + ((int64_t)fi * p.Cin + g * cig);
                     const float* wv = wc + it * p.kf + j;
                     for (int c = 0; c < cig; ++c) acc = fmaf(xv[c], wv[(int64_t)c * p.kt * p.kf], acc);
                 }
@@ -197,14 +217,30 @@ __global__ void k_dfn_rows(const float* __restrict__ a, const float* __restrict_
     }
 }
 
+// hist [B][P][len] <- the last P rows of (hist | x [B][S][len]): what a consumer of x reads in front of the next segment.  One thread
+// owns one column (b, e) and walks its P rows upwards, so the shift by S < P rows reads only rows it has not written yet.
+__global__ void k_dfn_hist_push(const float* __restrict__ x, float* hist, int B, int S, int P, int len) {
+    const int64_t n = (int64_t)B * len;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t b = i / len, e = i - b * len;
+        for (int p = 0; p < P; ++p) {
+            const int r = p + S - P;
+            hist[(b * P + p) * len + e] = r >= 0 ? x[(b * S + r) * len + e] : hist[(b * P + p + S) * len + e];
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ GRU recurrence
 // One workgroup per audio channel runs all nF steps of one layer.  Gate row r (torch order r | z | n, 3H rows) is split over GRU_SEG
 // lanes; thread t owns the (row, lane) tasks q = j * 1024 + t, j < 12, row q / 16, lane q % 16, columns 16 k + lane (k < 16).  Its 192
 // W_hh values (zero-padded beyond H) sit: tasks 0-2 in VGPRs, 3-4 in LDS, 5-11 in global memory (L2-resident, 448 KiB per step), all
 // in thread-minor order so every load is coalesced.  Per step: 16 h values from LDS, 192 FMAs, a 16-lane shuffle sum per task, the
 // gate sums to LDS, one barrier, the H gate updates, one barrier.  proj = W_ih x + b_ih of all frames comes from one GEMM beforehand.
+// h_in [C][H] is the state in front of step 0 (null: zeros), h_out [C][H] takes the state after the last step (null: not kept); they
+// may be the same array.
 __global__ __launch_bounds__(GRU_THREADS) void k_dfn_gru(const float* __restrict__ proj, const float* __restrict__ whh_pk,
-                                                          const float* __restrict__ bhh, int H, int nF, float* __restrict__ out) {
+                                                          const float* __restrict__ bhh, int H, int nF, float* __restrict__ out,
+                                                          const float* h_in, float* h_out) {
     __shared__ float wl[GRU_NLDS * GRU_THREADS];
     __shared__ float hs[GRU_HMAX];
     __shared__ float gs[3 * GRU_HMAX];
@@ -216,7 +252,7 @@ __global__ __launch_bounds__(GRU_THREADS) void k_dfn_gru(const float* __restrict
     for (int e = 0; e < GRU_NREG; ++e) wr[e] = whh_pk[(int64_t)e * GRU_THREADS + t];
     for (int e = 0; e < GRU_NLDS; ++e) wl[e * GRU_THREADS + t] = whh_pk[(int64_t)(GRU_NREG + e) * GRU_THREADS + t];
     const float* wg = whh_pk + (int64_t)(GRU_NREG + GRU_NLDS) * GRU_THREADS + t;
-    if (t < GRU_HMAX) hs[t] = 0.f;
+    if (t < GRU_HMAX) hs[t] = (h_in && t < H) ? h_in[(int64_t)b * H + t] : 0.f;
     float br = 0.f, bz = 0.f, bn = 0.f, xr = 0.f, xz = 0.f, xn = 0.f;
     if (t < H) {
         br = bhh[t]; bz = bhh[H + t]; bn = bhh[2 * H + t];
@@ -277,36 +313,53 @@ __global__ __launch_bounds__(GRU_THREADS) void k_dfn_gru(const float* __restrict
         xr = nxr; xz = nxz; xn = nxn;
         __syncthreads();
     }
+    if (h_out && t < H) h_out[(int64_t)b * H + t] = hs[t];
 }
 
 // ------------------------------------------------------------------------------------------------ mask + deep filter, synthesis
-__global__ void k_dfn_assemble(const float2* __restrict__ spec, const float* __restrict__ mask, const float* __restrict__ coefs,
-                               const int* __restrict__ band_of, int C, int nF, int Fq, int E, int nbdf, int order, int look,
-                               float2* __restrict__ out) {
-    const int64_t n = (int64_t)C * nF * Fq;
+// The assemble kernels work on nA frames from global frame asm_lo of a file of nF frames and write out [C][nA][Fq].  spec holds
+// [C][nS] rows from global frame spec_lo.  mask, coefs (and alpha) hold [C][S] rows from global frame a; a row in front of a comes from
+// the history arrays [C][P][...] (P_m rows of mask, look rows of coefs and alpha), which hold the rows just before a.  The whole file:
+// asm_lo = spec_lo = a = 0, nA = nS = S = nF, no history.
+struct AsmArgs {
+    const float2* spec; const float* mask; const float* coefs; const float* alpha;
+    const float* mask_h; const float* coefs_h; const float* alpha_h; const int* band_of; float2* out;
+    int64_t nF, asm_lo, spec_lo, a;
+    int C, nA, nS, S, P_m, Fq, E, nbdf, order, look;
+};
+
+// row l of cur [C][S][len] (l >= 0) or row l + P of hist [C][P][len] (l < 0), channel b
+__device__ __forceinline__ const float* lag_row(const float* cur, const float* hist, int64_t b, int l, int S, int P, int len) {
+    return l >= 0 ? cur + (b * S + l) * len : hist + (b * P + (l + P)) * len;
+}
+
+__global__ void k_dfn_assemble(AsmArgs p) {
+    const int Fq = p.Fq, nbdf = p.nbdf, order = p.order, look = p.look;
+    const int64_t n = (int64_t)p.C * p.nA * Fq;
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         const int f = (int)(i % Fq);
-        const int64_t r = i / Fq;                  // b * nF + t
-        const int t = (int)(r % nF);
-        const int64_t b = r / nF;
+        const int64_t r = i / Fq;                  // b * nA + local frame
+        const int64_t t = p.asm_lo + r % p.nA;     // global frame
+        const int64_t b = r / p.nA;
+        const int la = (int)(t - p.a);             // row of mask / coefs relative to a
         float2 y;
         if (f < nbdf) {
-            const float* c = coefs + (r * nbdf + f) * 2 * order;
+            const float* c = lag_row(p.coefs, p.coefs_h, b, la, p.S, look, nbdf * 2 * order) + f * 2 * order;
             float re = 0.f, im = 0.f;
             for (int k = 0; k < order; ++k) {
-                const int ts = t - (order - 1 - look) + k;
-                if (ts < 0 || ts >= nF) continue;
-                const float2 s = spec[(b * nF + ts) * Fq + f];
+                const int64_t ts = t - (order - 1 - look) + k;
+                if (ts < 0 || ts >= p.nF) continue;
+                const float2 s = p.spec[(b * p.nS + (ts - p.spec_lo)) * Fq + f];
                 re = fmaf(s.x, c[2 * k], fmaf(-s.y, c[2 * k + 1], re));
                 im = fmaf(s.x, c[2 * k + 1], fmaf(s.y, c[2 * k], im));
             }
             y = make_float2(re, im);
         } else {
-            const float m = mask[r * E + band_of[f]];
-            const float2 s = spec[i];
+            const float m = lag_row(p.mask, p.mask_h, b, la, p.S, p.P_m, p.E)[p.band_of[f]];
+            const float2 s = p.spec[(b * p.nS + (t - p.spec_lo)) * Fq + f];
             y = make_float2(s.x * m, s.y * m);
         }
-        out[i] = y;
+        p.out[i] = y;
     }
 }
 
@@ -335,11 +388,15 @@ __global__ __launch_bounds__(256) void k_dfn_synth(const float2* __restrict__ sp
     }
 }
 
-__global__ void k_dfn_ola(const float* __restrict__ frames, int C, int nF, int N, int hop, int64_t T, float* __restrict__ y) {
-    const int64_t n = (int64_t)C * T;
+// Output samples [out_lo, out_lo + cnt) of every channel of y [C][T].  frames [C][nA][N] are the synthesised frames from global frame
+// asm_lo of a file of nF frames, hist [C][ov - 1][N] the ov - 1 frames in front of them (the whole file: asm_lo = out_lo = 0, nA = nF,
+// cnt = T, no history).
+__global__ void k_dfn_ola(const float* __restrict__ frames, const float* __restrict__ hist, int C, int nA, int64_t asm_lo, int64_t nF,
+                          int N, int hop, int64_t T, int64_t out_lo, int64_t cnt, float* __restrict__ y) {
+    const int64_t n = (int64_t)C * cnt;
     const int d = N - hop, ov = N / hop;
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t b = i / T, s = i - b * T;
+        const int64_t b = i / cnt, s = out_lo + (i - b * cnt);
         const int64_t o = s + d;
         const int64_t k = o / hop;
         const int j = (int)(o - k * hop);
@@ -347,9 +404,10 @@ __global__ void k_dfn_ola(const float* __restrict__ frames, int C, int nF, int N
         for (int m = ov - 1; m >= 0; --m) {
             const int64_t fk = k - m;
             if (fk < 0 || fk >= nF) continue;
-            acc += frames[(b * nF + fk) * N + m * hop + j];
+            const int64_t lf = fk - asm_lo;
+            acc += lf >= 0 ? frames[(b * nA + lf) * N + m * hop + j] : hist[(b * (ov - 1) + (lf + ov - 1)) * N + m * hop + j];
         }
-        y[i] = acc;
+        y[b * T + s] = acc;
     }
 }
 
@@ -372,7 +430,7 @@ template <int K>
 __global__ __launch_bounds__(512) void k_dfn2_gru(const float* __restrict__ proj, const float* __restrict__ whh_pk,
                                                    const float* __restrict__ bih, const float* __restrict__ bhh, int G, int h, int S,
                                                    int nF, int shuffle, const float* __restrict__ sum_in, float* __restrict__ out,
-                                                   float* __restrict__ sum_out) {
+                                                   float* __restrict__ sum_out, const float* h_in, float* h_out) {
     __shared__ float hs[2][G2_HMAX];
     const int t = threadIdx.x, NT = h * S, j = t / S, s = t - j * S;
     const int g = blockIdx.x, b = blockIdx.y, H = G * h, H3 = 3 * H;
@@ -386,11 +444,11 @@ __global__ __launch_bounds__(512) void k_dfn2_gru(const float* __restrict__ proj
     const float* wp = whh_pk + (int64_t)g * 3 * K * NT + t;
 #pragma unroll
     for (int e = 0; e < 3 * K; ++e) w[e] = wp[(int64_t)e * NT];
-    for (int i = t; i < 2 * G2_HMAX; i += NT) hs[i / G2_HMAX][i % G2_HMAX] = 0.f;
+    for (int i = t; i < 2 * G2_HMAX; i += NT) hs[i / G2_HMAX][i % G2_HMAX] = (h_in && i < h) ? h_in[(int64_t)b * H + g * h + i] : 0.f;
     const int rj = g * 3 * h + j;
     const float br = bhh[rj], bz = bhh[rj + h], bn = bhh[rj + 2 * h];
     const float ir = bih[rj], iz = bih[rj + h], in_ = bih[rj + 2 * h];
-    float xr = 0.f, xz = 0.f, xn = 0.f, hp = 0.f;
+    float xr = 0.f, xz = 0.f, xn = 0.f, hp = h_in ? h_in[(int64_t)b * H + n] : 0.f;
     if (nF > 0) { xr = pb[j] + ir; xz = pb[h + j] + iz; xn = pb[2 * h + j] + in_; }
     __syncthreads();
     for (int st = 0; st < nF; ++st) {
@@ -426,6 +484,7 @@ __global__ __launch_bounds__(512) void k_dfn2_gru(const float* __restrict__ proj
         xr = nxr; xz = nxz; xn = nxn;
         __syncthreads();
     }
+    if (h_out && s == 0) h_out[(int64_t)b * H + n] = hp;
 }
 
 // y[r][m] = act(a[r][src] + bias[src]) (+ res[r][m]), src = m, or with the P3 shuffle over G groups of width h = cols / G:
@@ -456,37 +515,36 @@ __global__ void k_dfn2_alpha(const float* __restrict__ c, const float* __restric
 }
 
 // P7: S_m = mask X on every bin; below nb_df Y = alpha DF(S_m) + (1 - alpha) S_m, DF the DFN3-P5 window over the masked frames.
-__global__ void k_dfn2_assemble(const float2* __restrict__ spec, const float* __restrict__ mask, const float* __restrict__ coefs,
-                                const float* __restrict__ alpha, const int* __restrict__ band_of, int C, int nF, int Fq, int E, int nbdf,
-                                int order, int look, float2* __restrict__ out) {
-    const int64_t n = (int64_t)C * nF * Fq;
+__global__ void k_dfn2_assemble(AsmArgs p) {
+    const int Fq = p.Fq, nbdf = p.nbdf, order = p.order, look = p.look, E = p.E;
+    const int64_t n = (int64_t)p.C * p.nA * Fq;
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         const int f = (int)(i % Fq);
-        const int64_t r = i / Fq;                  // b * nF + t
-        const int t = (int)(r % nF);
-        const int64_t b = r / nF;
-        const int band = band_of[f];
-        const float m = mask[r * E + band];
-        const float2 s = spec[i];
+        const int64_t r = i / Fq;                  // b * nA + local frame
+        const int64_t t = p.asm_lo + r % p.nA;     // global frame
+        const int64_t b = r / p.nA;
+        const int la = (int)(t - p.a);             // row of mask / coefs / alpha relative to a
+        const int band = p.band_of[f];
+        const float m = lag_row(p.mask, p.mask_h, b, la, p.S, p.P_m, E)[band];
+        const float2 s = p.spec[(b * p.nS + (t - p.spec_lo)) * Fq + f];
         const float2 sm = make_float2(s.x * m, s.y * m);
         float2 y = sm;
         if (f < nbdf) {
-            const float* c = coefs + (r * nbdf + f) * 2 * order;
+            const float* c = lag_row(p.coefs, p.coefs_h, b, la, p.S, look, nbdf * 2 * order) + f * 2 * order;
             float re = 0.f, im = 0.f;
             for (int k = 0; k < order; ++k) {
-                const int ts = t - (order - 1 - look) + k;
-                if (ts < 0 || ts >= nF) continue;
-                const int64_t rs = b * nF + ts;
-                const float ms = mask[rs * E + band];
-                const float2 x = spec[rs * Fq + f];
+                const int64_t ts = t - (order - 1 - look) + k;
+                if (ts < 0 || ts >= p.nF) continue;
+                const float ms = lag_row(p.mask, p.mask_h, b, (int)(ts - p.a), p.S, p.P_m, E)[band];
+                const float2 x = p.spec[(b * p.nS + (ts - p.spec_lo)) * Fq + f];
                 const float2 xm = make_float2(x.x * ms, x.y * ms);
                 re = fmaf(xm.x, c[2 * k], fmaf(-xm.y, c[2 * k + 1], re));
                 im = fmaf(xm.x, c[2 * k + 1], fmaf(xm.y, c[2 * k], im));
             }
-            const float a = alpha[r], a1 = 1.f - a;
+            const float a = lag_row(p.alpha, p.alpha_h, b, la, p.S, look, 1)[0], a1 = 1.f - a;
             y = make_float2(re * a + sm.x * a1, im * a + sm.y * a1);
         }
-        out[i] = y;
+        p.out[i] = y;
     }
 }
 
@@ -506,6 +564,9 @@ inline int64_t align64(int64_t n) { return (n + 63) & ~63LL; }
 struct Conv {                 // one convolution with its (optional) BN affine
     const float* w = nullptr; const float* scale = nullptr; const float* shift = nullptr;
     int cin = 0, cout = 0, groups = 1, kt = 1, kf = 1, transposed = 0;
+    // a segmented call only (null / 0 in a one-pass call): the kt - 1 input rows in front of the segment, the segment's first frame
+    float* hist = nullptr;
+    int64_t t0 = 0;
 };
 
 struct DfnDims {              // the hyper-parameters the shared code reads, from egr_dfn3_config / egr_dfn2_config
@@ -521,6 +582,18 @@ struct Bufs {                 // workspace buffers of the shared path; the model
     float *coefs, *frames;
 };
 
+struct Rows {                 // rows (channels x frames) of the three kinds of workspace buffers; one-pass: all C * nF
+    int64_t net;              // everything the network computes
+    int64_t spec;             // spec, db
+    int64_t asmr;             // spec_e, frames
+};
+
+struct SegState {             // what a segmented call carries besides the GRU states and the convolutions' histories
+    float *norm = nullptr, *mask_h = nullptr, *coefs_h = nullptr, *alpha_h = nullptr, *frames_h = nullptr;
+};
+
+constexpr int N_HIST_CONV = 9;
+
 struct DfnCore {
     DfnDims d;
     int device = 0, Fq = 0, embd = 0;
@@ -532,6 +605,8 @@ struct DfnCore {
     // workspace of the last call
     void* ws = nullptr; size_t ws_bytes = 0;
     int lastC = 0, lastF = 0; int64_t lastT = 0;
+    bool segmented = false;                 // the last call was a segmented one (its buffers hold the last segment only)
+    SegState sg;
     Bufs B;
     // GRU layers in the order encoder (1), ERB decoder (emb_num_layers - 1), DF decoder (df_num_layers)
     int ngru() const { return d.emb_num_layers + d.df_num_layers; }
@@ -549,15 +624,16 @@ struct Take {                 // the workspace allocator: 256-byte slots one aft
     }
 };
 
-void layout_common(const DfnCore& m, int64_t R, Take& take, Bufs& b) {
+void layout_common(const DfnCore& m, const Rows& rows, Take& take, Bufs& b) {
+    const int64_t R = rows.net, Rs = rows.spec, Ra = rows.asmr;
     const DfnDims& d = m.d;
     const int ch = d.conv_ch, E = d.nb_erb, nb = d.nb_df, O2 = 2 * d.df_order;
     const int Hm = d.emb_hidden_dim > d.df_hidden_dim ? d.emb_hidden_dim : d.df_hidden_dim;
     const int Fm = E > nb ? E : nb;
-    b.spec = (float2*)take(R * m.Fq * 2);
-    b.spec_e = (float2*)take(R * m.Fq * 2);
+    b.spec = (float2*)take(Rs * m.Fq * 2);
+    b.spec_e = (float2*)take(Ra * m.Fq * 2);
     b.fspec = (float2*)take(R * nb * 2);
-    b.db = take(R * E);
+    b.db = take(Rs * E);
     b.ferb = take(R * E);
     b.e[0] = take(R * E * ch);
     b.e[1] = take(R * (E / 2) * ch);
@@ -578,13 +654,19 @@ void layout_common(const DfnCore& m, int64_t R, Take& take, Bufs& b) {
     b.cpt = take(R * nb * O2);
     b.cp = take(R * nb * O2);
     b.coefs = take(R * nb * O2);
-    b.frames = take(R * d.fft_size);
+    b.frames = take(Ra * d.fft_size);
+}
+
+// hist [B][P][len] <- the last P rows of (hist | x [B][S][len])
+void hist_push(const float* x, float* hist, int B, int S, int P, int len, hipStream_t st) {
+    if (P < 1 || S < 1) return;
+    hipLaunchKernelGGL(k_dfn_hist_push, dim3(grid_for((int64_t)B * len)), dim3(256), 0, st, x, hist, B, S, P, len);
 }
 
 int conv(const Conv& L, const float* x, float* y, int B, int T, int Fin, int fstride, int act, const float* res, hipStream_t st,
          int* Fout_ret = nullptr) {
     ConvArgs p;
-    p.x = x; p.w = L.w; p.scale = L.scale; p.shift = L.shift; p.res = res; p.y = y;
+    p.x = x; p.w = L.w; p.scale = L.scale; p.shift = L.shift; p.res = res; p.y = y; p.hist = L.hist; p.t0 = L.t0;
     p.B = B; p.T = T; p.Fin = Fin; p.Cin = L.cin; p.Cout = L.cout; p.groups = L.groups; p.kt = L.kt; p.kf = L.kf; p.fstride = fstride;
     p.transposed = L.transposed; p.act = act;
     if (L.transposed) {
@@ -596,6 +678,7 @@ int conv(const Conv& L, const float* x, float* y, int B, int T, int Fin, int fst
     }
     if (Fout_ret) *Fout_ret = p.Fout;
     hipLaunchKernelGGL(k_dfn_conv, dim3(grid_for((int64_t)B * T * p.Fout * p.Cout)), dim3(256), 0, st, p);
+    if (L.hist) hist_push(x, L.hist, B, T, L.kt - 1, Fin * L.cin, st);
     return EGR_OK;
 }
 
@@ -613,7 +696,7 @@ int rows_op(const float* a, const float* bias, const float* res, float* y, int64
 // ---- run stages, in the order both run()s call them; the models' own launches come between encoder_convs and erb_decoder_convs and
 // ---- between erb_decoder_convs and df_pathway_and_coefs, their assemble kernel before synthesis
 // Grows the workspace to `need` bytes on `st` and notes the call's shape; the caller lays its buffers out over m.ws afterwards.
-int ensure_workspace(DfnCore& m, size_t need, int C, int nF, int64_t T, hipStream_t st) {
+int ensure_workspace(DfnCore& m, size_t need, int C, int nF, int64_t T, bool segmented, hipStream_t st) {
     if (need > m.ws_bytes) {
         if (m.ws) EGR_HIP(hipFreeAsync(m.ws, st));
         m.ws = nullptr;
@@ -622,19 +705,21 @@ int ensure_workspace(DfnCore& m, size_t need, int C, int nF, int64_t T, hipStrea
         m.ws_bytes = need;
     }
     m.lastC = C; m.lastF = nF; m.lastT = T;
+    m.segmented = segmented;
     return EGR_OK;
 }
 
-// analysis -> ERB dB -> the two norms (with the conv_lookahead shift whenever it is > 0)
+// analysis -> ERB dB -> the two norms (with the conv_lookahead shift whenever it is > 0) of the whole file
 void features(const DfnCore& m, const float* x, int C, int nF, int64_t T, hipStream_t st) {
     const DfnDims& d = m.d;
     const Bufs& B = m.B;
-    const int N = d.fft_size, E = d.nb_erb, nb = d.nb_df;
+    const int N = d.fft_size, E = d.nb_erb, nb = d.nb_df, la = d.conv_lookahead;
     const int64_t R = (int64_t)C * nF;
-    hipLaunchKernelGGL(k_dfn_analysis, dim3(nF, C), dim3(256), (size_t)N * 24, st, x, T, nF, N, d.hop_size, m.tw, m.win, m.wnorm, B.spec);
+    hipLaunchKernelGGL(k_dfn_analysis, dim3(nF, C), dim3(256), (size_t)N * 24, st, x, T, nF, (int64_t)0, N, d.hop_size, m.tw, m.win, m.wnorm,
+                       B.spec);
     hipLaunchKernelGGL(k_dfn_erb_db, dim3(grid_for(R * E)), dim3(256), 0, st, B.spec, R, m.Fq, E, m.band_lo, m.band_w, B.db);
-    hipLaunchKernelGGL(k_dfn_norm_scan, dim3((C * (E + nb) + 63) / 64), dim3(64), 0, st, B.db, B.spec, C, nF, m.Fq, E, nb,
-                       d.norm_alpha, d.conv_lookahead, B.ferb, B.fspec);
+    ScanArgs p{B.db, B.spec, B.ferb, B.fspec, nullptr, C, nF, 0, nF, nF, -la, nF - la > 0 ? nF - la : 0, nF, m.Fq, E, nb, la, 1, d.norm_alpha};
+    hipLaunchKernelGGL(k_dfn_norm_scan, dim3((C * (E + nb) + 63) / 64), dim3(64), 0, st, p);
 }
 
 struct EncWidths { int F1 = 0, F2 = 0, F3 = 0, Fc = 0; };      // frequency widths of e1, e2, e3 and c1
@@ -689,13 +774,33 @@ int df_pathway_and_coefs(const DfnCore& m, int C, int nF, const float* bias, hip
     return rows_op(B.tcoef, bias, B.cp, B.coefs, (int64_t)C * nF * nb * O2, nb * O2, 3, st);
 }
 
-// spec_e (written by the model's assemble kernel) -> y
-int synthesis(const DfnCore& m, int C, int nF, int64_t T, float* y, hipStream_t st) {
+// spec_e (written by the model's assemble kernel: nA frames from global frame asm_lo of nF) -> y[out_lo, out_lo + cnt).  The whole
+// file: nA = nF, asm_lo = out_lo = 0, cnt = T.
+int synthesis(const DfnCore& m, int C, int nA, int64_t asm_lo, int64_t nF, int64_t T, int64_t out_lo, int64_t cnt, float* y,
+              hipStream_t st) {
     const int N = m.d.fft_size;
-    hipLaunchKernelGGL(k_dfn_synth, dim3(nF, C), dim3(256), (size_t)(m.Fq + N) * 16, st, m.B.spec_e, nF, N, m.tw, m.win, m.B.frames);
-    hipLaunchKernelGGL(k_dfn_ola, dim3(grid_for((int64_t)C * T)), dim3(256), 0, st, m.B.frames, C, nF, N, m.d.hop_size, T, y);
+    if (nA > 0)
+        hipLaunchKernelGGL(k_dfn_synth, dim3(nA, C), dim3(256), (size_t)(m.Fq + N) * 16, st, m.B.spec_e, nA, N, m.tw, m.win, m.B.frames);
+    if (cnt > 0)
+        hipLaunchKernelGGL(k_dfn_ola, dim3(grid_for((int64_t)C * cnt)), dim3(256), 0, st, m.B.frames, m.sg.frames_h, C, nA, asm_lo, nF, N,
+                           m.d.hop_size, T, out_lo, cnt, y);
     EGR_HIP(hipGetLastError());
     return EGR_OK;
+}
+
+// The arguments of the models' assemble kernels: nA frames from asm_lo; spec holds nS frames from spec_lo, mask / coefs / alpha S
+// frames from a (one-pass: everything the whole file from 0).
+AsmArgs assemble_args(const DfnCore& m, const float* alpha, int C, int64_t nF, int64_t asm_lo, int nA, int64_t spec_lo, int nS,
+                      int64_t a, int S) {
+    const DfnDims& d = m.d;
+    const Bufs& B = m.B;
+    AsmArgs p;
+    p.spec = B.spec; p.mask = B.mask; p.coefs = B.coefs; p.alpha = alpha;
+    p.mask_h = m.sg.mask_h; p.coefs_h = m.sg.coefs_h; p.alpha_h = m.sg.alpha_h; p.band_of = m.band_of; p.out = B.spec_e;
+    p.nF = nF; p.asm_lo = asm_lo; p.spec_lo = spec_lo; p.a = a;
+    p.C = C; p.nA = nA; p.nS = nS; p.S = S; p.P_m = d.df_order - 1; p.Fq = m.Fq; p.E = d.nb_erb; p.nbdf = d.nb_df; p.order = d.df_order;
+    p.look = d.df_lookahead;
+    return p;
 }
 
 // ---- create stages
@@ -873,10 +978,13 @@ void bind(DfnCore& m, const WeightCursor& wc, const Image& im) {
 }
 
 // ---- entry-point bodies; `who` is the extern "C" function's name
-int enhance_checks(const DfnCore* m, const char* who, const float* x48, int channels, int64_t n, const float* y) {
+constexpr int64_t MAX_FRAMES = 2147483647LL / 4096;          // frames of one pass (a whole file, or a segment with the rows around it)
+
+// `whole`: a one-pass call, the file's frames are bounded; a segmented call bounds its segments instead (seg_clamp)
+int enhance_checks(const DfnCore* m, const char* who, const float* x48, int channels, int64_t n, const float* y, bool whole = true) {
     EGR_CHECK(m && x48 && y && channels >= 1 && channels <= 65535 && n >= 1, EGR_ERR_ARG, "%s: bad argument", who);
     // nF * 4096 fits an int (which also keeps nF below 65535 * 4096)
-    EGR_CHECK(m->frames_of(n) <= 2147483647LL / 4096, EGR_ERR_UNSUPPORTED, "%s: input too long", who);
+    EGR_CHECK(!whole || m->frames_of(n) <= MAX_FRAMES, EGR_ERR_UNSUPPORTED, "%s: input too long", who);
     int cur = -1;
     EGR_HIP(hipGetDevice(&cur));
     EGR_CHECK(cur == m->device, EGR_ERR_ARG, "%s: handle belongs to device %d, current device is %d", who, m->device, cur);
@@ -925,6 +1033,7 @@ bool stage_common(const DfnCore& m, int stage, const float** src, int64_t* n) {
 template <class Own>
 int stage_copy(const DfnCore& m, const char* who, int stage, float* dst, int64_t capacity, int64_t* count, void* stream, Own own) {
     EGR_CHECK(m.ws, EGR_ERR_ARG, "%s: no enhance call yet", who);
+    EGR_CHECK(!m.segmented, EGR_ERR_ARG, "%s: the last call was segmented; stages belong to one-pass calls", who);
     const float* src = nullptr;
     int64_t n = 0;
     own(stage, &src, &n);
@@ -972,6 +1081,7 @@ int time_gru_harness(const DfnCore* m, const char* who, int layer, int channels,
 struct Gru {
     const float* wih = nullptr; const float* bih = nullptr; const float* bhh = nullptr; float* whh_pk = nullptr;
     int in = 0, H = 0;
+    float* hst = nullptr;                   // a segmented call only: the state [C][H] across the cuts
 };
 
 struct Dfn3 {
@@ -983,20 +1093,12 @@ struct Dfn3 {
     struct Extra { float *emb, *gx; } X;
 };
 
-size_t layout(const Dfn3& m, int C, int nF, char* base, Bufs& B, Dfn3::Extra& X) {
-    const int64_t R = (int64_t)C * nF;
+void layout(const Dfn3& m, const Rows& rows, Take& take, Bufs& B, Dfn3::Extra& X) {
+    const int64_t R = rows.net;
     const int Hm = m.cfg.emb_hidden_dim > m.cfg.df_hidden_dim ? m.cfg.emb_hidden_dim : m.cfg.df_hidden_dim;
-    Take take{base};
-    layout_common(m.core, R, take, B);
+    layout_common(m.core, rows, take, B);
     X.emb = take(R * m.core.embd);
     X.gx = take(R * Hm);
-    return take.off;
-}
-
-size_t workspace_need(const Dfn3& m, int C, int nF) {       // measures only: the handle's buffers stay those of the last call
-    Bufs B;
-    Dfn3::Extra X;
-    return layout(m, C, nF, nullptr, B, X);
 }
 
 // x [C * nF][in] -> out [C * nF][H] through one GRU layer
@@ -1004,22 +1106,19 @@ int gru_layer(const Gru& g, const float* x, float* proj, float* out, int C, int 
     const int64_t R = (int64_t)C * nF;
     EGR_TRY(egr_bgemm(x, g.wih, proj, 1, 1, (int)R, 3 * g.H, g.in, g.in, g.in, 3 * g.H, 0, 0, 0, 0, 0, 0, 1, 1.f, st));
     EGR_TRY(rows_op(proj, g.bih, nullptr, proj, R * 3 * g.H, 3 * g.H, 0, st));
-    hipLaunchKernelGGL(k_dfn_gru, dim3(C), dim3(GRU_THREADS), 0, st, proj, g.whh_pk, g.bhh, g.H, nF, out);
+    hipLaunchKernelGGL(k_dfn_gru, dim3(C), dim3(GRU_THREADS), 0, st, proj, g.whh_pk, g.bhh, g.H, nF, out, g.hst, g.hst);
     return EGR_OK;
 }
 
-int run(Dfn3& m, const float* x, int C, int64_t T, float* y, hipStream_t st) {
+// features (ferb, fspec) -> mask, coefs over nF frames of C channels: the whole file, or one segment
+int network(Dfn3& m, int C, int nF, hipStream_t st) {
     const egr_dfn3_config& c = m.cfg;
     DfnCore& k = m.core;
     const char* who = "egr_dfn3";
-    const int nF = (int)k.frames_of(T);
     const int64_t R = (int64_t)C * nF;
     const int nb = c.nb_df, O2 = 2 * c.df_order, embd = k.embd;
     Bufs& B = k.B;
     Dfn3::Extra& X = m.X;
-    EGR_TRY(ensure_workspace(k, workspace_need(m, C, nF), C, nF, T, st));
-    layout(m, C, nF, (char*)k.ws, B, X);
-    features(k, x, C, nF, T, st);
     EncWidths w;
     EGR_TRY(encoder_convs(k, who, C, nF, &w, st));
     EGR_TRY(grouped_linear(B.c1, m.fc_emb, B.emb0, R, w.Fc * c.conv_ch, embd, c.enc_lin_groups, st));
@@ -1057,17 +1156,19 @@ int run(Dfn3& m, const float* x, int C, int64_t T, float* y, hipStream_t st) {
         xin = B.dfc;
     }
     EGR_TRY(grouped_linear(xin, m.df_out, B.tcoef, R, Hd, nb * O2, c.lin_groups, st));
-    EGR_TRY(df_pathway_and_coefs(k, C, nF, nullptr, st));                            // tanh(df_out(c)) + df_convp(c0)
-    // mask + deep filter, synthesis
-    hipLaunchKernelGGL(k_dfn_assemble, dim3(grid_for(R * k.Fq)), dim3(256), 0, st, B.spec, B.mask, B.coefs, k.band_of, C, nF, k.Fq,
-                       c.nb_erb, nb, c.df_order, c.df_lookahead, B.spec_e);
-    return synthesis(k, C, nF, T, y, st);
+    return df_pathway_and_coefs(k, C, nF, nullptr, st);                              // tanh(df_out(c)) + df_convp(c0)
+}
+
+// mask + deep filter
+void assemble(const Dfn3& m, const AsmArgs& p, hipStream_t st) {
+    hipLaunchKernelGGL(k_dfn_assemble, dim3(grid_for((int64_t)p.C * p.nA * p.Fq)), dim3(256), 0, st, p);
 }
 
 // ------------------------------------------------------------------------------------------------ DeepFilterNet2
 struct GGru {                 // one GroupedGRU layer: G GRUs of width h on input slices of width in / G
     const float* wih = nullptr; const float* bih = nullptr; const float* bhh = nullptr; float* whh_pk = nullptr;
     int in = 0, H = 0, G = 1, h = 0, K = 0, S = 1, shuffle = 0;
+    float* hst = nullptr;                   // a segmented call only: the state [C][H] across the cuts, groups in pre-shuffle order
     bool dense() const { return h > G2_HMAX; }
 };
 
@@ -1087,22 +1188,14 @@ struct Dfn2 {
     struct Extra { float *lin, *gsum[EGR_DFN3_MAX_GRU], *alpha; } X;
 };
 
-size_t layout(const Dfn2& m, int C, int nF, char* base, Bufs& B, Dfn2::Extra& X) {
+void layout(const Dfn2& m, const Rows& rows, Take& take, Bufs& B, Dfn2::Extra& X) {
     const DfnCore& k = m.core;
-    const int64_t R = (int64_t)C * nF;
+    const int64_t R = rows.net;
     const int no = m.cfg.nb_df * 2 * m.cfg.df_order;
-    Take take{base};
-    layout_common(k, R, take, B);
+    layout_common(k, rows, take, B);
     X.lin = take(R * (k.embd > no ? k.embd : no));
     for (int g = 0; g < EGR_DFN3_MAX_GRU; ++g) X.gsum[g] = g < k.ngru() ? take(R * k.gru_width(g)) : nullptr;
     X.alpha = take(R);
-    return take.off;
-}
-
-size_t workspace_need(const Dfn2& m, int C, int nF) {       // measures only: the handle's buffers stay those of the last call
-    Bufs B;
-    Dfn2::Extra X;
-    return layout(m, C, nF, nullptr, B, X);
 }
 
 int epi(const float* a, const float* bias, const float* res, float* y, int64_t n, int cols, int G, int act, hipStream_t st) {
@@ -1121,9 +1214,11 @@ int glinear(const float* x, const float* w, const float* bias, float* lin, float
 void launch_ggru(const GGru& g, const float* proj, const float* sum_in, float* out, float* sum_out, int C, int nF, hipStream_t st) {
     const dim3 grid(g.G, C), block(g.h * g.S);
     if (g.K == 16)
-        hipLaunchKernelGGL(k_dfn2_gru<16>, grid, block, 0, st, proj, g.whh_pk, g.bih, g.bhh, g.G, g.h, g.S, nF, g.shuffle, sum_in, out, sum_out);
+        hipLaunchKernelGGL(k_dfn2_gru<16>, grid, block, 0, st, proj, g.whh_pk, g.bih, g.bhh, g.G, g.h, g.S, nF, g.shuffle, sum_in, out, sum_out,
+                           g.hst, g.hst);
     else
-        hipLaunchKernelGGL(k_dfn2_gru<32>, grid, block, 0, st, proj, g.whh_pk, g.bih, g.bhh, g.G, g.h, g.S, nF, g.shuffle, sum_in, out, sum_out);
+        hipLaunchKernelGGL(k_dfn2_gru<32>, grid, block, 0, st, proj, g.whh_pk, g.bih, g.bhh, g.G, g.h, g.S, nF, g.shuffle, sum_in, out, sum_out,
+                           g.hst, g.hst);
 }
 
 // x [C * nF][in] -> out (the layer output as passed on) and sum_out (= sum_in + out) [C * nF][H] through one GroupedGRU layer
@@ -1133,25 +1228,22 @@ int ggru_layer(const GGru& g, const float* x, float* proj, const float* sum_in, 
     EGR_TRY(egr_bgemm(x, g.wih, proj, 1, g.G, (int)R, h3, I, g.in, I, 3 * g.H, 0, I, 0, (int64_t)h3 * I, 0, h3, 1, 1.f, st));
     if (g.dense()) {                       // G = 1 and H > 128: a plain nn.GRU layer, no shuffle
         EGR_TRY(rows_op(proj, g.bih, nullptr, proj, R * 3 * g.H, 3 * g.H, 0, st));
-        hipLaunchKernelGGL(k_dfn_gru, dim3(C), dim3(GRU_THREADS), 0, st, proj, g.whh_pk, g.bhh, g.H, nF, out);
+        hipLaunchKernelGGL(k_dfn_gru, dim3(C), dim3(GRU_THREADS), 0, st, proj, g.whh_pk, g.bhh, g.H, nF, out, g.hst, g.hst);
         return rows_op(out, nullptr, sum_in, sum_out, R * g.H, g.H, 0, st);
     }
     launch_ggru(g, proj, sum_in, out, sum_out, C, nF, st);
     return EGR_OK;
 }
 
-int run(Dfn2& m, const float* x, int C, int64_t T, float* y, hipStream_t st) {
+// features (ferb, fspec) -> mask, coefs, alpha over nF frames of C channels: the whole file, or one segment
+int network(Dfn2& m, int C, int nF, hipStream_t st) {
     const egr_dfn2_config& c = m.cfg;
     DfnCore& k = m.core;
     const char* who = "egr_dfn2";
-    const int nF = (int)k.frames_of(T);
     const int64_t R = (int64_t)C * nF;
     const int nb = c.nb_df, O2 = 2 * c.df_order, Hd = c.df_hidden_dim;
     Bufs& B = k.B;
     Dfn2::Extra& X = m.X;
-    EGR_TRY(ensure_workspace(k, workspace_need(m, C, nF), C, nF, T, st));
-    layout(m, C, nF, (char*)k.ws, B, X);
-    features(k, x, C, nF, T, st);                                                     // P1
     EncWidths w;
     EGR_TRY(encoder_convs(k, who, C, nF, &w, st));                                    // P2
     // emb0 = e3 + GroupedLinear(c1) (no activation)
@@ -1188,15 +1280,189 @@ int run(Dfn2& m, const float* x, int C, int64_t T, float* y, hipStream_t st) {
         EGR_TRY(egr_bgemm(sum, m.df_out, B.tcoef, 1, 1, (int)R, nb * O2, Hd, Hd, Hd, nb * O2, 0, 0, 0, 0, 0, 0, 1, 1.f, st));
     else
         EGR_TRY(grouped_linear(sum, m.df_out, B.tcoef, R, Hd, nb * O2, c.lin_groups, st));
-    EGR_TRY(df_pathway_and_coefs(k, C, nF, m.df_out_b, st));                         // tanh(df_out(c)) + df_convp(c0)
-    // mask, then deep filter (P7), synthesis
-    hipLaunchKernelGGL(k_dfn2_assemble, dim3(grid_for(R * k.Fq)), dim3(256), 0, st, B.spec, B.mask, B.coefs, X.alpha, k.band_of, C, nF,
-                       k.Fq, c.nb_erb, nb, c.df_order, c.df_lookahead, B.spec_e);
-    return synthesis(k, C, nF, T, y, st);
+    return df_pathway_and_coefs(k, C, nF, m.df_out_b, st);                           // tanh(df_out(c)) + df_convp(c0)
+}
+
+// mask, then deep filter (P7)
+void assemble(const Dfn2& m, const AsmArgs& p, hipStream_t st) {
+    hipLaunchKernelGGL(k_dfn2_assemble, dim3(grid_for((int64_t)p.C * p.nA * p.Fq)), dim3(256), 0, st, p);
+}
+
+inline const float* alpha_of(const Dfn3&) { return nullptr; }
+inline const float* alpha_of(const Dfn2& m) { return m.X.alpha; }
+
+// ------------------------------------------------------------------------------------------------ the two ways to run a file
+// One pass: every buffer holds the whole file.
+template <class M>
+size_t workspace_need(const M& m, int C, int nF) {           // measures only: the handle's buffers stay those of the last call
+    Bufs B;
+    typename M::Extra X;
+    Take take{nullptr};
+    const int64_t R = (int64_t)C * nF;
+    layout(m, Rows{R, R, R}, take, B, X);
+    return take.off;
+}
+
+// The convolutions with kt > 1 possible, each with the frequency width of its input: the consumers that carry kt - 1 rows.
+template <class Core, class ConvT>
+void hist_convs(Core& k, ConvT* c[N_HIST_CONV], int fin[N_HIST_CONV]) {
+    const int E = k.d.nb_erb, nb = k.d.nb_df;
+    ConvT* cs[N_HIST_CONV] = {&k.erb0, &k.df0, &k.erb_dw[0], &k.erb_dw[1], &k.erb_dw[2], &k.df1_dw, &k.ct_dw[0], &k.out0, &k.convp};
+    const int fs[N_HIST_CONV] = {E, nb, E, E / 2, E / 4, nb, E / 4, E, nb};
+    for (int i = 0; i < N_HIST_CONV; ++i) { c[i] = cs[i]; fin[i] = fs[i]; }
+}
+
+// A one-pass call carries nothing: no histories, no states, frame 0 first.
+template <class M>
+void unbind_segments(M& m) {
+    Conv* c[N_HIST_CONV];
+    int fin[N_HIST_CONV];
+    hist_convs(m.core, c, fin);
+    for (int i = 0; i < N_HIST_CONV; ++i) { c[i]->hist = nullptr; c[i]->t0 = 0; }
+    for (auto& g : m.grus) g.hst = nullptr;
+    m.core.sg = SegState();
+}
+
+template <class M>
+int run(M& m, const float* x, int C, int64_t T, float* y, hipStream_t st) {
+    DfnCore& k = m.core;
+    const int nF = (int)k.frames_of(T);
+    const int64_t R = (int64_t)C * nF;
+    EGR_TRY(ensure_workspace(k, workspace_need(m, C, nF), C, nF, T, false, st));
+    Take take{(char*)k.ws};
+    layout(m, Rows{R, R, R}, take, k.B, m.X);
+    unbind_segments(m);
+    features(k, x, C, nF, T, st);
+    EGR_TRY(network(m, C, nF, st));
+    assemble(m, assemble_args(k, alpha_of(m), C, nF, 0, nF, 0, nF, 0, nF), st);
+    return synthesis(k, C, nF, 0, nF, T, 0, T, y, st);
+}
+
+// Segments: the buffers hold seg_frames network frames (plus the lookahead and deep-filter rows of spec, the lagged
+// rows of spec_e / frames); behind them sits what crosses a cut.
+struct SegLayout {
+    size_t state_off = 0, end = 0;
+    SegState sg;
+    float* conv_h[N_HIST_CONV];
+    float* gru_h[EGR_DFN3_MAX_GRU];
+};
+
+// the largest segment whose rows (with the lookahead and deep-filter rows around it) stay within MAX_FRAMES
+inline int64_t seg_clamp(const DfnCore& k, int64_t S) {
+    const int64_t cap = MAX_FRAMES - k.d.conv_lookahead - k.d.df_order;
+    return S < cap ? S : cap;
+}
+
+template <class M>
+void layout_segments(const M& m, int C, int64_t S, char* base, Bufs& B, typename M::Extra& X, SegLayout& L) {
+    const DfnCore& k = m.core;
+    const DfnDims& d = k.d;
+    const int64_t Cn = C;
+    Take take{base};
+    layout(m, Rows{Cn * S, Cn * (S + d.conv_lookahead + d.df_order - 1), Cn * (S + d.df_lookahead)}, take, B, X);
+    L.state_off = take.off;
+    L.sg.norm = take(Cn * (d.nb_erb + d.nb_df));
+    const Conv* c[N_HIST_CONV];
+    int fin[N_HIST_CONV];
+    hist_convs(k, c, fin);
+    for (int i = 0; i < N_HIST_CONV; ++i) L.conv_h[i] = c[i]->kt > 1 ? take(Cn * (c[i]->kt - 1) * fin[i] * c[i]->cin) : nullptr;
+    for (int g = 0; g < EGR_DFN3_MAX_GRU; ++g) L.gru_h[g] = g < k.ngru() ? take(Cn * k.gru_width(g)) : nullptr;
+    L.sg.mask_h = take(Cn * (d.df_order - 1) * d.nb_erb);
+    L.sg.coefs_h = take(Cn * d.df_lookahead * d.nb_df * 2 * d.df_order);
+    L.sg.alpha_h = take(Cn * d.df_lookahead);
+    L.sg.frames_h = take(Cn * (d.fft_size / d.hop_size - 1) * d.fft_size);
+    L.end = take.off;
+}
+
+template <class M>
+size_t segment_need(const M& m, int C, int64_t S) {
+    Bufs B;
+    typename M::Extra X;
+    SegLayout L;
+    layout_segments(m, C, seg_clamp(m.core, S), nullptr, B, X, L);
+    return L.end;
+}
+
+template <class M>
+int run_segmented(M& m, const float* x, int C, int64_t T, float* y, int64_t seg_frames, hipStream_t st) {
+    DfnCore& k = m.core;
+    const DfnDims& d = k.d;
+    const Bufs& B = k.B;
+    const int64_t S = seg_clamp(k, seg_frames), nF = k.frames_of(T);
+    const int N = d.fft_size, E = d.nb_erb, nb = d.nb_df, la = d.conv_lookahead, O2 = 2 * d.df_order;
+    EGR_TRY(ensure_workspace(k, segment_need(m, C, S), C, 0, T, true, st));
+    SegLayout L;
+    layout_segments(m, C, S, (char*)k.ws, k.B, m.X, L);
+    Conv* hc[N_HIST_CONV];
+    int fin[N_HIST_CONV];
+    hist_convs(k, hc, fin);
+    for (int i = 0; i < N_HIST_CONV; ++i) hc[i]->hist = L.conv_h[i];
+    for (size_t g = 0; g < m.grus.size(); ++g) m.grus[g].hst = L.gru_h[g];
+    k.sg = L.sg;
+    // nothing of an earlier call survives: zero states and histories (the norm states start from their linspace values in segment 0)
+    EGR_HIP(hipMemsetAsync((char*)k.ws + L.state_off, 0, L.end - L.state_off, st));
+    int64_t nseg = 0;
+    egr_dfn_segment sp;
+    EGR_TRY(egr_dfn_segment_plan(N, d.hop_size, la, d.df_order, d.df_lookahead, T, S, 0, nullptr, &nseg));
+    for (int64_t j = 0; j < nseg; ++j) {
+        EGR_TRY(egr_dfn_segment_plan(N, d.hop_size, la, d.df_order, d.df_lookahead, T, S, j, &sp, nullptr));
+        const int Sj = (int)(sp.net_hi - sp.net_lo), nS = (int)(sp.spec_hi - sp.spec_lo);
+        const int nA = sp.asm_hi > sp.asm_lo ? (int)(sp.asm_hi - sp.asm_lo) : 0;
+        const int64_t Rs = (int64_t)C * nS;
+        hipLaunchKernelGGL(k_dfn_analysis, dim3(nS, C), dim3(256), (size_t)N * 24, st, x, T, nS, sp.spec_lo, N, d.hop_size, k.tw, k.win,
+                           k.wnorm, B.spec);
+        hipLaunchKernelGGL(k_dfn_erb_db, dim3(grid_for(Rs * E)), dim3(256), 0, st, B.spec, Rs, k.Fq, E, k.band_lo, k.band_w, B.db);
+        // input frames [scan_lo, scan_hi) -> feature rows t - la; the rows >= nF - la of this segment are zero
+        int64_t zlo = nF - la - sp.net_lo;
+        zlo = zlo < 0 ? 0 : (zlo > Sj ? Sj : zlo);
+        ScanArgs sa{B.db, B.spec, B.ferb, B.fspec, k.sg.norm, C, nS, (int)(sp.scan_lo - sp.spec_lo), (int)(sp.scan_hi - sp.scan_lo), Sj,
+                    (int)(sp.scan_lo - la - sp.net_lo), (int)zlo, Sj, k.Fq, E, nb, la, j == 0, d.norm_alpha};
+        hipLaunchKernelGGL(k_dfn_norm_scan, dim3((C * (E + nb) + 63) / 64), dim3(64), 0, st, sa);
+        for (int i = 0; i < N_HIST_CONV; ++i) hc[i]->t0 = sp.net_lo;
+        EGR_TRY(network(m, C, Sj, st));
+        // the assemble step lags the network by df_lookahead frames: its rows in front of net_lo come from the histories
+        if (nA > 0) assemble(m, assemble_args(k, alpha_of(m), C, nF, sp.asm_lo, nA, sp.spec_lo, nS, sp.net_lo, Sj), st);
+        hist_push(B.mask, k.sg.mask_h, C, Sj, d.df_order - 1, E, st);
+        hist_push(B.coefs, k.sg.coefs_h, C, Sj, d.df_lookahead, nb * O2, st);
+        if (alpha_of(m)) hist_push(alpha_of(m), k.sg.alpha_h, C, Sj, d.df_lookahead, 1, st);
+        EGR_TRY(synthesis(k, C, nA, sp.asm_lo, nF, T, sp.out_lo, sp.out_hi - sp.out_lo, y, st));
+        hist_push(B.frames, k.sg.frames_h, C, nA, N / d.hop_size - 1, N, st);
+    }
+    return EGR_OK;
 }
 
 }  // namespace
 }  // namespace egr
+
+// ================================================================================================ the segment plan (host only)
+// Segment `index` of a file of n samples cut every seg_frames network frames; all ranges are half-open, in frames
+// (out: samples).  The non-empty ranges of every kind partition their axis in segment order; a range with hi <= lo is empty.
+extern "C" int egr_dfn_segment_plan(int fft_size, int hop_size, int conv_lookahead, int df_order, int df_lookahead, int64_t n,
+                                    int64_t seg_frames, int64_t index, egr_dfn_segment* seg, int64_t* n_segments) {
+    EGR_CHECK(fft_size > 0 && hop_size > 0 && fft_size % hop_size == 0 && conv_lookahead >= 0 && df_order >= 1 && df_lookahead >= 0 &&
+              df_lookahead < df_order && n >= 1 && seg_frames >= 1, EGR_ERR_ARG, "egr_dfn_segment_plan: bad argument");
+    const int64_t nF = (n + fft_size) / hop_size, ov = fft_size / hop_size, la = conv_lookahead, look = df_lookahead;
+    const int64_t nseg = (nF - 1) / seg_frames + 1;
+    if (n_segments) *n_segments = nseg;
+    if (!seg) return EGR_OK;
+    EGR_CHECK(index >= 0 && index < nseg, EGR_ERR_ARG, "egr_dfn_segment_plan: segment %lld of %lld", (long long)index, (long long)nseg);
+    const auto lo0 = [](int64_t v) { return v < 0 ? (int64_t)0 : v; };
+    const auto mn = [](int64_t a, int64_t b) { return a < b ? a : b; };
+    const bool first = index == 0, last = index == nseg - 1;
+    const int64_t a = index * seg_frames, b = last ? nF : a + seg_frames;
+    seg->net_lo = a;
+    seg->net_hi = b;
+    seg->scan_lo = first ? 0 : mn(nF, a + la);              // the norms see input frame t + la for network frame t
+    seg->scan_hi = last ? nF : mn(nF, b + la);
+    seg->asm_lo = lo0(a - look);                            // mask and deep filter lag the network by df_lookahead frames
+    seg->asm_hi = last ? nF : b - look;                     // at or below asm_lo (even negative): nothing to assemble yet
+    seg->spec_lo = lo0(seg->asm_lo - (df_order - 1 - look));
+    const int64_t win_hi = mn(nF, seg->asm_hi + look);
+    seg->spec_hi = seg->scan_hi > win_hi ? seg->scan_hi : win_hi;
+    seg->out_lo = first ? 0 : mn(n, lo0(seg->asm_lo - ov + 1) * hop_size);     // samples whose ov frames are all assembled
+    seg->out_hi = last ? n : mn(n, lo0(seg->asm_hi - ov + 1) * hop_size);
+    return EGR_OK;
+}
 
 // ================================================================================================ DeepFilterNet3 entry points
 extern "C" int egr_dfn3_create(void** handle, const egr_dfn3_config* cfg, const float* packed, int64_t n_floats, int device) {
@@ -1272,6 +1538,24 @@ extern "C" int egr_dfn3_enhance(void* handle, const float* x48, int channels, in
     return run(*m, x48, channels, n, y, (hipStream_t)stream);
 }
 
+extern "C" int egr_dfn3_enhance_segmented(void* handle, const float* x48, int channels, int64_t n, float* y, int64_t seg_frames,
+                                          void* stream) {
+    using namespace egr;
+    Dfn3* m = (Dfn3*)handle;
+    EGR_TRY(enhance_checks(m ? &m->core : nullptr, "egr_dfn3_enhance_segmented", x48, channels, n, y, false));
+    EGR_CHECK(seg_frames >= 1, EGR_ERR_ARG, "egr_dfn3_enhance_segmented: seg_frames %lld < 1", (long long)seg_frames);
+    return run_segmented(*m, x48, channels, n, y, seg_frames, (hipStream_t)stream);
+}
+
+extern "C" size_t egr_dfn3_segment_workspace_bytes(void* handle, int channels, int64_t seg_frames) {
+    if (!handle || channels < 1 || seg_frames < 1) return 0;
+    return egr::segment_need(*(const egr::Dfn3*)handle, channels, seg_frames);
+}
+
+extern "C" size_t egr_dfn3_workspace_held(void* handle) {
+    return handle ? ((const egr::Dfn3*)handle)->core.ws_bytes : 0;
+}
+
 extern "C" int egr_dfn3_stage(void* handle, int stage, float* dst, int64_t capacity, int64_t* count, void* stream) {
     using namespace egr;
     EGR_CHECK(handle && count, EGR_ERR_ARG, "egr_dfn3_stage: null argument");
@@ -1288,7 +1572,8 @@ extern "C" int egr_dfn3_time_gru(void* handle, int layer, int channels, int64_t 
     return time_gru_harness(m ? &m->core : nullptr, "egr_dfn3_time_gru", layer, channels, steps, false, us_per_step,
                             [&](const float* proj, float* out, float*, int nF) {
         const Gru& g = m->grus[layer];
-        hipLaunchKernelGGL(k_dfn_gru, dim3(channels), dim3(GRU_THREADS), 0, 0, proj, g.whh_pk, g.bhh, g.H, nF, out);
+        hipLaunchKernelGGL(k_dfn_gru, dim3(channels), dim3(GRU_THREADS), 0, 0, proj, g.whh_pk, g.bhh, g.H, nF, out, (const float*)nullptr,
+                           (float*)nullptr);
     });
 }
 
@@ -1405,6 +1690,24 @@ extern "C" int egr_dfn2_enhance(void* handle, const float* x48, int channels, in
     return run(*m, x48, channels, n, y, (hipStream_t)stream);
 }
 
+extern "C" int egr_dfn2_enhance_segmented(void* handle, const float* x48, int channels, int64_t n, float* y, int64_t seg_frames,
+                                          void* stream) {
+    using namespace egr;
+    Dfn2* m = (Dfn2*)handle;
+    EGR_TRY(enhance_checks(m ? &m->core : nullptr, "egr_dfn2_enhance_segmented", x48, channels, n, y, false));
+    EGR_CHECK(seg_frames >= 1, EGR_ERR_ARG, "egr_dfn2_enhance_segmented: seg_frames %lld < 1", (long long)seg_frames);
+    return run_segmented(*m, x48, channels, n, y, seg_frames, (hipStream_t)stream);
+}
+
+extern "C" size_t egr_dfn2_segment_workspace_bytes(void* handle, int channels, int64_t seg_frames) {
+    if (!handle || channels < 1 || seg_frames < 1) return 0;
+    return egr::segment_need(*(const egr::Dfn2*)handle, channels, seg_frames);
+}
+
+extern "C" size_t egr_dfn2_workspace_held(void* handle) {
+    return handle ? ((const egr::Dfn2*)handle)->core.ws_bytes : 0;
+}
+
 extern "C" int egr_dfn2_stage(void* handle, int stage, float* dst, int64_t capacity, int64_t* count, void* stream) {
     using namespace egr;
     EGR_CHECK(handle && count, EGR_ERR_ARG, "egr_dfn2_stage: null argument");
@@ -1428,9 +1731,13 @@ extern "C" int egr_dfn2_time_gru(void* handle, int layer, int channels, int64_t 
                             [&](const float* proj, float* out, float* sum, int nF) {
         const GGru& g = m->grus[layer];
         if (g.dense())
-            hipLaunchKernelGGL(k_dfn_gru, dim3(channels), dim3(GRU_THREADS), 0, 0, proj, g.whh_pk, g.bhh, g.H, nF, out);
-        else
-            launch_ggru(g, proj, nullptr, out, sum, channels, nF, 0);
+            hipLaunchKernelGGL(k_dfn_gru, dim3(channels), dim3(GRU_THREADS), 0, 0, proj, g.whh_pk, g.bhh, g.H, nF, out, (const float*)nullptr,
+                           (float*)nullptr);
+        else {
+            GGru z = g;                                             // no carried state
+            z.hst = nullptr;
+            launch_ggru(z, proj, nullptr, out, sum, channels, nF, 0);
+        }
     });
 }
 

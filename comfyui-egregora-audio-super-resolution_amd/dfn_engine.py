@@ -3,11 +3,16 @@
 One handle per (model directory, device), created from a validated model directory (dfn_weights.load / dfn2_weights.load) and kept
 for the life of the process.  enhance() takes the 48 kHz signal while it is on the device and returns the denoised signal there, on
 the current stream.  DfnEngine is the engine of both models; this module holds the DeepFilterNet3 one, dfn2_engine.py the other.
+
+A long input runs in segments of `seg_frames` network frames with the state carried across the cuts (egr_dfn*_enhance_segmented,
+DESIGN.md 7.3): the same bits as the one-pass call, a workspace that depends on seg_frames and not on the length.  enhance() picks the
+path with choose_path() from the workspace budget EGREGORA_DFN_WORKSPACE_GB.
 """
 import ctypes as C
+import os
 import threading
 from pathlib import Path
-from typing import Dict, Optional, Tuple
+from typing import Callable, Dict, NamedTuple, Optional, Tuple
 
 import torch
 
@@ -15,6 +20,96 @@ from . import dfn_weights, native
 
 _CACHE: Dict[Tuple[str, str, int], "DfnEngine"] = {}
 _LOCK = threading.Lock()
+
+
+ONE_PASS_MAX_FRAMES = (2 ** 31 - 1) // 4096     # egr_dfn*_enhance refuses more frames ("input too long")
+SEGMENT_STEP = 64                               # choose_path picks segment lengths in multiples of this many frames
+WORKSPACE_GB_ENV = "EGREGORA_DFN_WORKSPACE_GB"
+# A choice, not a measurement: above the 52 GB of the longest case the repository documents (30 minutes of stereo), so
+# every run measured so far stays on the one-pass path.  The two paths give the same bits, so the switch does not show in the output.
+WORKSPACE_GB_DEFAULT = 64.0
+
+
+class Segment(NamedTuple):
+    """egr_dfn_segment (include/egregora_amd.h): half-open ranges, frames except out (samples); hi <= lo is an empty range."""
+    net_lo: int
+    net_hi: int
+    scan_lo: int
+    scan_hi: int
+    spec_lo: int
+    spec_hi: int
+    asm_lo: int
+    asm_hi: int
+    out_lo: int
+    out_hi: int
+
+
+class SegmentC(C.Structure):
+    _fields_ = [(f, C.c_int64) for f in Segment._fields]
+
+
+def segment_count(fft_size: int, hop_size: int, n: int, seg_frames: int) -> int:
+    return ((n + fft_size) // hop_size - 1) // seg_frames + 1
+
+
+def segment_plan(fft_size: int, hop_size: int, conv_lookahead: int, df_order: int, df_lookahead: int, n: int, seg_frames: int,
+                 index: int) -> Segment:
+    """Segment `index` of a file of n samples cut every seg_frames network frames: the Python twin of egr_dfn_segment_plan.  The
+    norms see input frame t + conv_lookahead for network frame t; mask, deep filter and synthesis lag the network by df_lookahead
+    frames; a sample is written once all fft/hop frames over it are synthesised."""
+    if not (fft_size > 0 and hop_size > 0 and fft_size % hop_size == 0 and conv_lookahead >= 0 and df_order >= 1
+            and 0 <= df_lookahead < df_order and n >= 1 and seg_frames >= 1):
+        raise ValueError("segment_plan: bad argument")
+    nF, ov = (n + fft_size) // hop_size, fft_size // hop_size
+    nseg = segment_count(fft_size, hop_size, n, seg_frames)
+    if not 0 <= index < nseg:
+        raise ValueError(f"segment_plan: segment {index} of {nseg}")
+    first, last = index == 0, index == nseg - 1
+    a = index * seg_frames
+    b = nF if last else a + seg_frames
+    scan_lo = 0 if first else min(nF, a + conv_lookahead)
+    scan_hi = nF if last else min(nF, b + conv_lookahead)
+    asm_lo = max(0, a - df_lookahead)
+    asm_hi = nF if last else b - df_lookahead              # at or below asm_lo (even negative): nothing to assemble yet
+    spec_lo = max(0, asm_lo - (df_order - 1 - df_lookahead))
+    spec_hi = max(scan_hi, min(nF, asm_hi + df_lookahead))
+    out_lo = 0 if first else min(n, max(0, asm_lo - ov + 1) * hop_size)
+    out_hi = n if last else min(n, max(0, asm_hi - ov + 1) * hop_size)
+    return Segment(a, b, scan_lo, scan_hi, spec_lo, spec_hi, asm_lo, asm_hi, out_lo, out_hi)
+
+
+def segment_plan_c(fft_size: int, hop_size: int, conv_lookahead: int, df_order: int, df_lookahead: int, n: int, seg_frames: int,
+                   index: int) -> Tuple[Segment, int]:
+    """(segment, number of segments) from egr_dfn_segment_plan (host only: needs no GPU)."""
+    sc, cnt = SegmentC(), C.c_int64()
+    native.check(native.lib().egr_dfn_segment_plan(fft_size, hop_size, conv_lookahead, df_order, df_lookahead, n, seg_frames, index,
+                                                   C.byref(sc), C.byref(cnt)), "egr_dfn_segment_plan")
+    return Segment(*(int(getattr(sc, f)) for f in Segment._fields)), int(cnt.value)
+
+
+def workspace_budget_bytes() -> int:
+    return int(float(os.environ.get(WORKSPACE_GB_ENV, WORKSPACE_GB_DEFAULT)) * 2 ** 30)
+
+
+def choose_path(nF: int, one_pass_bytes: int, budget_bytes: int, bytes_for: Callable[[int], int]) -> Optional[int]:
+    """None: run the nF frames in one pass (they are within its limit and its workspace within the budget).  Else the segment length:
+    the largest multiple of SEGMENT_STEP frames whose workspace bytes_for(seg_frames) fits the budget (bytes_for grows with
+    seg_frames) and that a segment can have; raises when even SEGMENT_STEP frames do not fit."""
+    if nF <= ONE_PASS_MAX_FRAMES and one_pass_bytes <= budget_bytes:
+        return None
+    if bytes_for(SEGMENT_STEP) > budget_bytes:
+        raise RuntimeError(f"DeepFilterNet: a segment of {SEGMENT_STEP} frames needs {bytes_for(SEGMENT_STEP)} bytes of workspace, "
+                           f"the budget ({WORKSPACE_GB_ENV}) is {budget_bytes}")
+    lo, hi = 1, ONE_PASS_MAX_FRAMES // SEGMENT_STEP                                             # in steps; lo fits
+    if bytes_for(hi * SEGMENT_STEP) <= budget_bytes:
+        return hi * SEGMENT_STEP
+    while hi - lo > 1:                                                                          # hi does not fit
+        mid = (lo + hi) // 2
+        if bytes_for(mid * SEGMENT_STEP) <= budget_bytes:
+            lo = mid
+        else:
+            hi = mid
+    return lo * SEGMENT_STEP
 
 
 def config_common(s, m):
@@ -69,19 +164,42 @@ class DfnEngine:
         except Exception:           # noqa: BLE001 (interpreter shutdown)
             pass
 
-    def enhance(self, x48: torch.Tensor) -> torch.Tensor:
-        """x48 [C, T] float32 on this engine's device -> [C, T] on the same device, enqueued on the current stream."""
+    def enhance(self, x48: torch.Tensor, seg_frames: Optional[int] = None) -> torch.Tensor:
+        """x48 [C, T] float32 on this engine's device -> [C, T] on the same device, enqueued on the current stream.  seg_frames: run
+        in segments of that many frames; None: one pass when the file is within its limit and its workspace within the budget
+        (EGREGORA_DFN_WORKSPACE_GB), else the longest segments that fit (choose_path).  Both paths give the same bits."""
         if x48.dim() != 2 or not x48.is_cuda or x48.device.index != self.device:
             raise ValueError(f"{self.prefix}: expected [C, T] on cuda:{self.device}, got {tuple(x48.shape)} on {x48.device}")
         x = x48.to(torch.float32).contiguous()
         y = torch.empty_like(x)
+        ch, n = x.shape
+        if seg_frames is None and n >= 1:
+            nF = (n + self._cfg.fft_size) // self._cfg.hop_size
+            one_pass = self.workspace_bytes(ch, n) if nF <= ONE_PASS_MAX_FRAMES else 0
+            seg_frames = choose_path(nF, one_pass, workspace_budget_bytes(), lambda s: self.segment_workspace_bytes(ch, s))
         with torch.cuda.device(self.device):
-            native.check(self._fn("enhance")(self.h, native.ptr(x), x.shape[0], x.shape[1], native.ptr(y), native.stream_ptr()),
-                         f"{self.prefix}_enhance")
+            if seg_frames is None:
+                native.check(self._fn("enhance")(self.h, native.ptr(x), ch, n, native.ptr(y), native.stream_ptr()), f"{self.prefix}_enhance")
+            else:
+                native.check(self._fn("enhance_segmented")(self.h, native.ptr(x), ch, n, native.ptr(y), int(seg_frames), native.stream_ptr()),
+                             f"{self.prefix}_enhance_segmented")
         return y
 
     def workspace_bytes(self, channels: int, n: int) -> int:
         return int(self._fn("workspace_bytes")(self.h, int(channels), int(n)))
+
+    def segment_workspace_bytes(self, channels: int, seg_frames: int) -> int:
+        """The workspace of a segmented call: it depends on the segment length, not on the input's."""
+        return int(self._fn("segment_workspace_bytes")(self.h, int(channels), int(seg_frames)))
+
+    def workspace_held(self) -> int:
+        """Bytes of workspace the handle holds now (it grows to the largest call so far and is kept)."""
+        return int(self._fn("workspace_held")(self.h))
+
+    def segment_plan(self, n: int, seg_frames: int, index: int) -> Segment:
+        """Segment `index` of an n-sample input as this model's handle cuts it."""
+        c = self._cfg
+        return segment_plan(c.fft_size, c.hop_size, c.conv_lookahead, c.df_order, c.df_lookahead, n, seg_frames, index)
 
     def stage(self, name: str, layer: int = 0) -> torch.Tensor:
         """An intermediate of the last enhance call as a flat float32 device tensor (layouts: include/egregora_amd.h); the names in

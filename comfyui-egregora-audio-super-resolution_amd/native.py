@@ -48,18 +48,25 @@ SIGNATURES = {
     "egr_dfn_workspace_bytes": (C.c_size_t, [_i, _i64]),
     "egr_dfn_vad_gains": (_i, [_vp, _i, _i64, C.c_double, _i, C.c_double, C.c_double, C.c_double, _i, _vp, _vp, _vp, _vp]),
     "egr_dfn_mix": (_i, [_vp, _vp, _vp, _vp, _i, _i64, _i64, _i, _f, _i, _i, C.c_double, _vp, _vp, _vp]),
+    "egr_dfn_segment_plan": (_i, [_i, _i, _i, _i, _i, _i64, _i64, _i64, _vp, C.POINTER(_i64)]),
     "egr_dfn3_create": (_i, [C.POINTER(_vp), _vp, _vp, _i64, _i]),
     "egr_dfn3_workspace_bytes": (C.c_size_t, [_vp, _i, _i64]),
     "egr_dfn3_enhance": (_i, [_vp, _vp, _i, _i64, _vp, _vp]),
     "egr_dfn3_stage": (_i, [_vp, _i, _vp, _i64, C.POINTER(_i64), _vp]),
     "egr_dfn3_time_gru": (_i, [_vp, _i, _i, _i64, C.POINTER(C.c_double)]),
     "egr_dfn3_destroy": (_i, [_vp]),
+    "egr_dfn3_enhance_segmented": (_i, [_vp, _vp, _i, _i64, _vp, _i64, _vp]),
+    "egr_dfn3_segment_workspace_bytes": (C.c_size_t, [_vp, _i, _i64]),
+    "egr_dfn3_workspace_held": (C.c_size_t, [_vp]),
     "egr_dfn2_create": (_i, [C.POINTER(_vp), _vp, _vp, _i64, _i]),
     "egr_dfn2_workspace_bytes": (C.c_size_t, [_vp, _i, _i64]),
     "egr_dfn2_enhance": (_i, [_vp, _vp, _i, _i64, _vp, _vp]),
     "egr_dfn2_stage": (_i, [_vp, _i, _vp, _i64, C.POINTER(_i64), _vp]),
     "egr_dfn2_time_gru": (_i, [_vp, _i, _i, _i64, C.POINTER(C.c_double)]),
     "egr_dfn2_destroy": (_i, [_vp]),
+    "egr_dfn2_enhance_segmented": (_i, [_vp, _vp, _i, _i64, _vp, _i64, _vp]),
+    "egr_dfn2_segment_workspace_bytes": (C.c_size_t, [_vp, _i, _i64]),
+    "egr_dfn2_workspace_held": (C.c_size_t, [_vp]),
     "egr_shift_fir": (_i, [_vp, _i, _i64, _i64, _vp, _i, _vp, _i64, _vp]),
     "egr_gcc_phat": (_i, [_vp, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp]),
     "egr_band_filter": (_i, [_vp, _vp, _i64, _vp, _vp]),

@@ -214,6 +214,28 @@ int egr_dfn3_stage(void* handle, int stage, float* dst, int64_t capacity, int64_
 int egr_dfn3_time_gru(void* handle, int layer, int channels, int64_t steps, double* us_per_step);
 int egr_dfn3_destroy(void* handle);
 
+/* Long inputs in segments, for both models (X = 3, 2).  The forward pass walks the frame axis in segments of
+ * seg_frames network frames and carries the norm states, the GRU states, the kt - 1 rows in front of each causal convolution, the
+ * lagged mask / coefficient rows and the last fft/hop - 1 synthesised frames across the cuts; y has the bits of egr_dfnX_enhance.
+ *   egr_dfnX_enhance_segmented       : as egr_dfnX_enhance (x48 and y whole on the device, enqueued on `stream`, nothing
+ *                                      synchronises), without its limit on n; seg_frames < 1 is EGR_ERR_ARG, a seg_frames whose rows
+ *                                      would not index with an int is clamped to the largest that does.  Nothing is carried from one
+ *                                      call to the next.  egr_dfnX_stage after it is EGR_ERR_ARG (stages belong to one-pass calls)
+ *   egr_dfnX_segment_workspace_bytes : the workspace of such a call; it depends on (channels, seg_frames), not on n
+ *   egr_dfnX_workspace_held          : bytes of workspace the handle holds now (it grows to the largest call and is kept)
+ *   egr_dfn_segment_plan             : host only, no device or handle: segment `index` of a file of n samples as half-open ranges:
+ *                                      net (network frames), scan (input frames of the norms), spec (frames analysed), asm (frames
+ *                                      masked / deep-filtered / synthesised), out (samples written); *n_segments the number of
+ *                                      segments.  seg NULL: only *n_segments.  hi <= lo is an empty range; the others of a kind partition its axis. */
+typedef struct egr_dfn_segment {
+    int64_t net_lo, net_hi, scan_lo, scan_hi, spec_lo, spec_hi, asm_lo, asm_hi, out_lo, out_hi;
+} egr_dfn_segment;
+int egr_dfn_segment_plan(int fft_size, int hop_size, int conv_lookahead, int df_order, int df_lookahead, int64_t n, int64_t seg_frames,
+                         int64_t index, egr_dfn_segment* seg, int64_t* n_segments);
+int egr_dfn3_enhance_segmented(void* handle, const float* x48, int channels, int64_t n, float* y, int64_t seg_frames, void* stream);
+size_t egr_dfn3_segment_workspace_bytes(void* handle, int channels, int64_t seg_frames);
+size_t egr_dfn3_workspace_held(void* handle);
+
 /* DeepFilterNet2 forward pass (csrc/egr_dfn3.hip; SPEC.md "4c. DeepFilterNet2 (UPSTREAM-RECALL)"): the same contract
  * as egr_dfn3_* above, for a DeepFilterNet2 model (dfn2_weights.py; weights in dfn2_weights.pack_order order).  Stages as
  * EGR_DFN3_STAGE_* (EMB is the encoder GroupedGRU's output) plus ALPHA [C][nF]; GroupedGRU layer g (encoder, ERB decoder, DF decoder,
@@ -241,6 +263,9 @@ int egr_dfn2_enhance(void* handle, const float* x48, int channels, int64_t n, fl
 int egr_dfn2_stage(void* handle, int stage, float* dst, int64_t capacity, int64_t* count, void* stream);
 int egr_dfn2_time_gru(void* handle, int layer, int channels, int64_t steps, double* us_per_step);
 int egr_dfn2_destroy(void* handle);
+int egr_dfn2_enhance_segmented(void* handle, const float* x48, int channels, int64_t n, float* y, int64_t seg_frames, void* stream);
+size_t egr_dfn2_segment_workspace_bytes(void* handle, int channels, int64_t seg_frames);
+size_t egr_dfn2_workspace_held(void* handle);
 
 /* Linear-interpolation resampler of the "Resample Audio (HQ)" node's fallback branch: y[c][j] = np.interp at
  * j * n_in / n_out input samples, clamped to the last sample (egregora_audio_eval_pack.py:515-519). */
