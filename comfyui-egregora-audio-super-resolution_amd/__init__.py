@@ -5,7 +5,12 @@ display names, same INPUT_TYPES / RETURN_TYPES / FUNCTION surface -- plus the ev
 stage that run on this pack's kernels (merged the way the reference merges its ENHANCE_MAP / EVAL_MAP, __init__.py:9-23,47-53).  Compute runs in libegregora_amd.so
 (hand-written HIP, C ABI in include/egregora_amd.h); importing this package needs neither the library
 nor a GPU -- the nodes raise at run() time when either is missing.
+
+The evaluation pack's loudness meter, 1770 gain match and ABX nodes (egregora_audio_eval_loudness.py) are registered only when the
+environment variable EGREGORA_EVAL_NODES is "1" at import; without it the registered set is the one listed above.
 """
+import os
+
 from .egregora_audio_super_resolution import EgregoraAudioSuperResolution
 from .egregora_fat_llama_cpu import EgregoraFatLlamaCPU
 from .egregora_fat_llama_gpu import EgregoraFatLlamaGPU
@@ -31,5 +36,10 @@ NODE_CLASS_MAPPINGS.update(NULL_MAP)
 NODE_DISPLAY_NAME_MAPPINGS.update(ENHANCE_NAMES)
 NODE_DISPLAY_NAME_MAPPINGS.update(EVAL_NAMES)
 NODE_DISPLAY_NAME_MAPPINGS.update(NULL_NAMES)
+
+if os.environ.get("EGREGORA_EVAL_NODES") == "1":
+    from .egregora_audio_eval_loudness import (NODE_CLASS_MAPPINGS as LOUD_MAP, NODE_DISPLAY_NAME_MAPPINGS as LOUD_NAMES)
+    NODE_CLASS_MAPPINGS.update(LOUD_MAP)
+    NODE_DISPLAY_NAME_MAPPINGS.update(LOUD_NAMES)
 
 __all__ = ["NODE_CLASS_MAPPINGS", "NODE_DISPLAY_NAME_MAPPINGS"]

@@ -471,6 +471,98 @@ __global__ __launch_bounds__(256) void k_frame_meansq(const float* __restrict__ 
     if (threadIdx.x == 0) out[blockIdx.x] = red[0] / (double)(b - a);
 }
 
+// ---------------------------------------------------------------- evaluation pack loudness meter (egregora_audio_eval_pack.py:132-214)
+// K-weighting of every channel and the channel mean in one pass: mono[i] = mean_c kweight(x[c])[i].  Per channel the arithmetic is
+// k_kweight's (same roundings, same order, same restart W samples ahead of the thread's L-sample chunk), the mean is mono_mean's
+// (rows added in order, one division).  CT > 0: CT channels advance together with their states in registers (x read once, mono
+// written once).  CT = 0: any channel count, one channel after the other, the running sum kept in the thread's own stretch of mono.
+template <int CT>
+__global__ __launch_bounds__(64) void k_kweight_mono(const float* __restrict__ x, int C, long long n, float a1, float kf, int L, int W,
+                                                     float* __restrict__ mono) {
+    const long long s = ((long long)blockIdx.x * 64 + threadIdx.x) * L;
+    if (s >= n) return;
+    long long i0 = s - W - 1;
+    if (i0 < 0) i0 = 0;
+    const long long e = s + L < n ? s + L : n;
+    if constexpr (CT > 0) {
+        float z[CT > 0 ? CT : 1], yp[CT > 0 ? CT : 1];
+#pragma unroll
+        for (int c = 0; c < CT; ++c) z[c] = yp[c] = 0.f;
+        long long i = i0;
+        for (; i < s; ++i) {
+#pragma unroll
+            for (int c = 0; c < CT; ++c) {
+                const float xv = x[(size_t)c * n + i];
+                z[c] = __fadd_rn(__fmul_rn(a1, xv), __fmul_rn(kf, z[c]));
+                yp[c] = __fsub_rn(xv, z[c]);
+            }
+        }
+        for (; i < e; ++i) {
+            float m = 0.f;
+#pragma unroll
+            for (int c = 0; c < CT; ++c) {
+                const float xv = x[(size_t)c * n + i];
+                z[c] = __fadd_rn(__fmul_rn(a1, xv), __fmul_rn(kf, z[c]));
+                const float yv = __fsub_rn(xv, z[c]);
+                const float v = i > 0 ? __fadd_rn(yv, __fmul_rn(0.02f, __fsub_rn(yv, yp[c]))) : yv;
+                yp[c] = yv;
+                m = c ? __fadd_rn(m, v) : v;
+            }
+            mono[i] = CT > 1 ? __fdiv_rn(m, (float)CT) : m;
+        }
+    } else {
+        for (int c = 0; c < C; ++c) {
+            const float* xc = x + (size_t)c * n;
+            float z = 0.f, yp = 0.f;
+            long long i = i0;
+            for (; i < s; ++i) {
+                const float xv = xc[i];
+                z = __fadd_rn(__fmul_rn(a1, xv), __fmul_rn(kf, z));
+                yp = __fsub_rn(xv, z);
+            }
+            for (; i < e; ++i) {
+                const float xv = xc[i];
+                z = __fadd_rn(__fmul_rn(a1, xv), __fmul_rn(kf, z));
+                const float yv = __fsub_rn(xv, z);
+                const float v = i > 0 ? __fadd_rn(yv, __fmul_rn(0.02f, __fsub_rn(yv, yp))) : yv;
+                yp = yv;
+                float m = c ? __fadd_rn(mono[i], v) : v;
+                if (c == C - 1 && C > 1) m = __fdiv_rn(m, (float)C);
+                mono[i] = m;
+            }
+        }
+    }
+}
+
+// *slot (bits of a non-negative float, zeroed by the call) raised to max_m |y[m]|, y = resample_poly(mono_mean(x), up, 1) with
+// k_resample_poly's per-output accumulation (down = 1) on the channel mean formed on the fly; the up * n samples are never stored.
+// up = 1: y is the channel mean itself (scipy returns a copy, no filter).
+__global__ __launch_bounds__(256) void k_true_peak(const float* __restrict__ x, int C, long long n, int up, const float* __restrict__ h,
+                                                   int half, unsigned* __restrict__ slot) {
+    __shared__ float red[4];
+    const long long n_out = n * up, hl = 2LL * half;
+    float mx = 0.f;
+    for (long long m = (long long)blockIdx.x * 256 + threadIdx.x; m < n_out; m += (long long)gridDim.x * 256) {
+        float acc;
+        if (up == 1) {
+            acc = mono_mean(x, C, n, m);
+        } else {
+            const long long t = m + half;
+            long long k_hi = t / up;
+            if (k_hi > n - 1) k_hi = n - 1;
+            const long long k_lo = t - hl <= 0 ? 0 : (t - hl + up - 1) / up;
+            acc = 0.f;
+            for (long long k = k_lo; k <= k_hi; ++k) acc = __fadd_rn(acc, __fmul_rn(mono_mean(x, C, n, k), h[t - k * up]));
+        }
+        mx = fmaxf(mx, fabsf(acc));
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
+    __syncthreads();
+    if (threadIdx.x == 0) atomicMax(slot, __float_as_uint(fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]))));
+}
+
 template <int K>
 __device__ __forceinline__ void block_add_f64(double (&v)[K], double* __restrict__ out) {
     __shared__ double red[K][4];
@@ -757,6 +849,48 @@ extern "C" int egr_frame_meansq(const float* x, int channels, int64_t n, int64_t
               "bad argument");
     hipLaunchKernelGGL(k_frame_meansq, dim3((unsigned)frames), dim3(256), 0, (hipStream_t)stream, x, channels, (long long)n,
                        (long long)block, (long long)hop, out);
+    EGR_HIP(hipGetLastError());
+    return EGR_OK;
+}
+
+extern "C" int egr_loudness_frames(const float* x, int channels, int64_t n, float one_minus_k, float k, int64_t blk_a, int64_t hop_a,
+                                   int64_t frames_a, int64_t blk_b, int64_t hop_b, int64_t frames_b, float* kmono_ws, double* out_a,
+                                   double* out_b, void* stream) {
+    EGR_CHECK(x && kmono_ws && out_a && channels >= 1 && n >= 1 && k > 0.f && k < 1.f, EGR_ERR_ARG, "bad argument");
+    EGR_CHECK(blk_a >= 1 && hop_a >= 1 && frames_a >= 1 && frames_a < (1LL << 31) && (frames_a - 1) * hop_a < n, EGR_ERR_ARG,
+              "bad first block family");
+    EGR_CHECK(frames_b == 0 || (out_b && blk_b >= 1 && hop_b >= 1 && frames_b >= 1 && frames_b < (1LL << 31) && (frames_b - 1) * hop_b < n),
+              EGR_ERR_ARG, "bad second block family");
+    hipStream_t st = (hipStream_t)stream;
+    int W = (int)ceil(26.0 / -log((double)k));       // the restart rule of egr_kweight: k^W < 6e-12
+    if (W < 64) W = 64;
+    const int L = (W + 2) / 3;
+    const long long chunks = (n + L - 1) / L;
+    const dim3 grid((unsigned)((chunks + 63) / 64));
+    const long long nn = (long long)n;
+    switch (channels) {
+    case 1: hipLaunchKernelGGL(k_kweight_mono<1>, grid, dim3(64), 0, st, x, channels, nn, one_minus_k, k, L, W, kmono_ws); break;
+    case 2: hipLaunchKernelGGL(k_kweight_mono<2>, grid, dim3(64), 0, st, x, channels, nn, one_minus_k, k, L, W, kmono_ws); break;
+    case 3: hipLaunchKernelGGL(k_kweight_mono<3>, grid, dim3(64), 0, st, x, channels, nn, one_minus_k, k, L, W, kmono_ws); break;
+    case 4: hipLaunchKernelGGL(k_kweight_mono<4>, grid, dim3(64), 0, st, x, channels, nn, one_minus_k, k, L, W, kmono_ws); break;
+    default: hipLaunchKernelGGL(k_kweight_mono<0>, grid, dim3(64), 0, st, x, channels, nn, one_minus_k, k, L, W, kmono_ws); break;
+    }
+    hipLaunchKernelGGL(k_frame_meansq, dim3((unsigned)frames_a), dim3(256), 0, st, (const float*)kmono_ws, 1, nn, (long long)blk_a,
+                       (long long)hop_a, out_a);
+    if (frames_b)
+        hipLaunchKernelGGL(k_frame_meansq, dim3((unsigned)frames_b), dim3(256), 0, st, (const float*)kmono_ws, 1, nn, (long long)blk_b,
+                           (long long)hop_b, out_b);
+    EGR_HIP(hipGetLastError());
+    return EGR_OK;
+}
+
+extern "C" int egr_true_peak(const float* x, int channels, int64_t n, int up, const float* h, int half, float* peak_slot, void* stream) {
+    EGR_CHECK(x && peak_slot && channels >= 1 && n >= 1 && up >= 1 && half >= 0 && (up == 1 || h), EGR_ERR_ARG, "bad argument");
+    hipStream_t st = (hipStream_t)stream;
+    EGR_HIP(hipMemsetAsync(peak_slot, 0, sizeof(unsigned), st));
+    long long nb = ((long long)n * up + 255) / 256;
+    if (nb > 4096) nb = 4096;
+    hipLaunchKernelGGL(k_true_peak, dim3((unsigned)nb), dim3(256), 0, st, x, channels, (long long)n, up, h, half, (unsigned*)peak_slot);
     EGR_HIP(hipGetLastError());
     return EGR_OK;
 }

@@ -5,7 +5,8 @@ INPUT_TYPES / RETURN_TYPES / RETURN_NAMES / FUNCTION / CATEGORY and `execute` si
 STFT, per-frame LSD, the percentile's order statistics, the SI-SDR sums and both resamplers run in libegregora_amd.so
 (csrc/egr_glue.hip); the host keeps only the AUDIO coercion rules of the reference (`to_internal_audio`,
 `_normalize_CN`, `make_audio`, :60-103).  No CPU fallback: without the library or a gfx950 device `execute` raises.
-The reference's other evaluation nodes (ABX, BS.1770 loudness) are host-side bookkeeping and are not part of this pack.
+The reference's other four evaluation nodes (loudness meter, 1770 gain match, ABX Prepare / Judge) live in
+egregora_audio_eval_loudness.py and are registered when EGREGORA_EVAL_NODES=1.
 """
 from typing import Any, Dict
 

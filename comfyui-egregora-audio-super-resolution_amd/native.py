@@ -73,6 +73,8 @@ SIGNATURES = {
     "egr_kweight": (_i, [_vp, _i, _i64, _f, _f, _vp, _vp]),
     "egr_mono_mean": (_i, [_vp, _i, _i64, _i64, _vp, _vp]),
     "egr_frame_meansq": (_i, [_vp, _i, _i64, _i64, _i64, _i64, _vp, _vp]),
+    "egr_loudness_frames": (_i, [_vp, _i, _i64, _f, _f, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
+    "egr_true_peak": (_i, [_vp, _i, _i64, _i, _vp, _i, _vp, _vp]),
     "egr_pair_stats": (_i, [_vp, _i, _i64, _vp, _i, _i64, _i64, _f, _i, _vp, _vp]),
     "egr_null_mix": (_i, [_vp, _i64, _vp, _i64, _i, _i64, _f, _i, _i, _vp, _vp, _vp]),
     "egr_band_sums": (_i, [_vp, _vp, _i64, _vp, _vp]),

@@ -296,6 +296,19 @@ int egr_mono_mean(const float* x, int channels, int64_t stride, int64_t n, float
 /* out[f] (device, double) = mean over [f hop, min(f hop + block, n)) of mono(x)^2: the 400 ms / 100 ms blocks of integrated_lufs
  * (:143-165) and, with one block of n samples, _rms_db (:119-122) */
 int egr_frame_meansq(const float* x, int channels, int64_t n, int64_t block, int64_t hop, int64_t frames, double* out, void* stream);
+/* The evaluation pack's loudness meter (egregora_audio_eval_pack.py:132-200) in one call: kmono_ws[i] (device, n floats) = float32
+ * mean over channels of egr_kweight(x) -- per channel the same roundings in the same order, the mean as egr_mono_mean -- formed in
+ * one pass over x without storing the K-weighted channels; then two families of block mean squares of that signal, each as
+ * egr_frame_meansq with one channel: out_a[frames_a] from (blk_a, hop_a) (the 400 ms / 100 ms blocks of integrated_lufs and the
+ * momentary series), out_b[frames_b] from (blk_b, hop_b) (the 3 s / 1 s blocks of the short-term series and LRA; frames_b = 0:
+ * skipped).  Blocks are cut at n.  Any channels >= 1 and n >= 1.  Only enqueues work on `stream`. */
+int egr_loudness_frames(const float* x, int channels, int64_t n, float one_minus_k, float k, int64_t blk_a, int64_t hop_a,
+                        int64_t frames_a, int64_t blk_b, int64_t hop_b, int64_t frames_b, float* kmono_ws, double* out_a, double* out_b,
+                        void* stream);
+/* *peak_slot (device, 4 bytes, cleared by the call) = max |resample_poly(mono_mean(x), up, 1)| as a float: the linear true peak of
+ * true_peak_dbfs (:203-214) with egr_resample_poly's accumulation (h, half as there, designed for (up, 1)); the up * n oversampled
+ * signal is not stored.  up = 1: the maximum of |mono_mean(x)| (h may be NULL).  Only enqueues work on `stream`. */
+int egr_true_peak(const float* x, int channels, int64_t n, int up, const float* h, int half, float* peak_slot, void* stream);
 /* out5 (device, double) = {sum a, sum b, sum ab, sum aa, sum bb} over the mono downmixes of a[ca][n] and b[cb][n] (b scaled by the
  * float32 k first when use_k): least-squares scale and correlation coefficient of Audio Null Test (:431-447) */
 int egr_pair_stats(const float* a, int ca, int64_t stride_a, const float* b, int cb, int64_t stride_b, int64_t n, float k, int use_k,
