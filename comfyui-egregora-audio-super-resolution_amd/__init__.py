@@ -7,7 +7,8 @@ stage that run on this pack's kernels (merged the way the reference merges its E
 nor a GPU -- the nodes raise at run() time when either is missing.
 
 The evaluation pack's loudness meter, 1770 gain match and ABX nodes (egregora_audio_eval_loudness.py) are registered only when the
-environment variable EGREGORA_EVAL_NODES is "1" at import; without it the registered set is the one listed above.
+environment variable EGREGORA_EVAL_NODES is "1" at import; the WPE dereverberation node (egregora_audio_enhance_wpe.py) only when
+EGREGORA_ENHANCE_NODES is "1".  Without them the registered set is the one listed above.
 """
 import os
 
@@ -41,5 +42,10 @@ if os.environ.get("EGREGORA_EVAL_NODES") == "1":
     from .egregora_audio_eval_loudness import (NODE_CLASS_MAPPINGS as LOUD_MAP, NODE_DISPLAY_NAME_MAPPINGS as LOUD_NAMES)
     NODE_CLASS_MAPPINGS.update(LOUD_MAP)
     NODE_DISPLAY_NAME_MAPPINGS.update(LOUD_NAMES)
+
+if os.environ.get("EGREGORA_ENHANCE_NODES") == "1":
+    from .egregora_audio_enhance_wpe import (NODE_CLASS_MAPPINGS as WPE_MAP, NODE_DISPLAY_NAME_MAPPINGS as WPE_NAMES)
+    NODE_CLASS_MAPPINGS.update(WPE_MAP)
+    NODE_DISPLAY_NAME_MAPPINGS.update(WPE_NAMES)
 
 __all__ = ["NODE_CLASS_MAPPINGS", "NODE_DISPLAY_NAME_MAPPINGS"]

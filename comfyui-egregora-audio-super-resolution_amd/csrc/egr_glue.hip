@@ -9,6 +9,7 @@
 #include "egr_common.h"
 #include "egr_fft_device.h"
 #include "egr_plan.h"
+#include "egr_stft_tables.h"
 
 namespace egr {
 
@@ -127,14 +128,10 @@ __global__ __launch_bounds__(256) void k_stft_mag(const float* __restrict__ x, i
     }
 }
 
-struct StftTables {
-    FftDesc fd;
-    cplx *tw, *wsplit;
-};
 static std::mutex g_stft_mu;
 static std::map<std::pair<int, int>, StftTables> g_stft;   // (device, n_fft)
 
-static int stft_tables(int n_fft, StftTables* out) {
+int stft_tables(int n_fft, StftTables* out) {
     int dev = 0;
     EGR_HIP(hipGetDevice(&dev));
     std::lock_guard<std::mutex> lk(g_stft_mu);

@@ -160,6 +160,12 @@ SIGNATURES = {
     "egr_pack_weight": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "egr_phase_weights": (_i, [_vp, _vp, _i, _i, _vp]),
     "egr_winograd_pack_u": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
+    "egr_wpe_frames": (_i64, [_i64, _i, _i]),
+    "egr_wpe_workspace_bytes": (C.c_size_t, [_i, _i64, _i, _i, _i]),
+    "egr_wpe_stft": (_i, [_vp, _i, _i64, _i, _i, _vp, _vp]),
+    "egr_wpe_istft": (_i, [_vp, _i, _i64, _i, _i, _vp, _i64, _vp]),
+    "egr_wpe_iterate": (_i, [_vp, _vp, _i, _i, _i64, _i, _i, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "egr_wpe_dereverb": (_i, [_vp, _i, _i64, _i, _i, _i, _i, _i, _vp, _i64, _vp, C.c_size_t, _vp]),
 }
 
 FSR_MAX = 8

@@ -708,6 +708,31 @@ int egr_pack_weight(const float* src, float* dst, int layout, int K, int N, int 
 int egr_phase_weights(const float* w_oihw, float* dst4, int Co, int Ci, void* stream);
 int egr_winograd_pack_u(const float* w_oihw, float* dst, const double* G_dev, int np, int Co, int Ci, void* stream);
 
+/* WPE dereverberation (csrc/egr_wpe.hip; SPEC.md 4d): per-bin multi-channel weighted prediction error over STFT frames, the job of
+ * the reference's Egregora_WPE_Dereverb node as its docstring describes it.  All calls enqueue on `stream`; the first call with a
+ * new (n_fft, hop) on a device builds its tables with a blocking copy.
+ *   framing  : periodic Blackman window of n_fft points, n_fft - hop zeros in front and behind, hop must divide n_fft with
+ *              n_fft / hop >= 2, n_fft even and <= 4096 (otherwise EGR_ERR_UNSUPPORTED; egr_wpe_frames / _workspace_bytes return 0)
+ *   frames   = ceil((n + n_fft - 2 hop) / hop) + 1,  n_out = frames hop - (n_fft - hop) >= n  (not trimmed to n)
+ *   spectra  : complex64 [bins = n_fft / 2 + 1][channels][frames]
+ * egr_wpe_iterate runs ONE iteration on every bin: with K = channels taps (<= 64, else EGR_ERR_UNSUPPORTED) and stacked history
+ * Yt[k channels + d][t] = Y[d][t - delay - k],
+ *   R = sum_t inv[t] Yt[t] Yt[t]^H,  P = sum_t inv[t] Yt[t] Y[t]^H,  G = R^-1 P,  X[t] = Y[t] - G^H Yt[t]
+ * in double.  inv_in: [bins][frames] double, or NULL: inv[t] = 1 / max(p[t], 1e-10 max_t p[t]), p[t] = mean_d |Y[d][t]|^2, is formed
+ * from Y and left in ws (ws_bytes >= bins frames 8).  Each of the outputs may be NULL: X [bins][channels][frames] complex64;
+ * G [bins][K][channels] complex double; inv_out [bins][frames] double, the weights of the NEXT iteration formed from X before it is
+ * rounded; flags_out [bins] int, 1 where a Cholesky pivot fell to <= 1e-13 max diag(R): that bin keeps X = Y and G = 0.
+ * egr_wpe_dereverb: stft, `iterations` iterations (Yt always from the observed Y, only inv changes), istft; x [channels][n],
+ * y [channels][n_out], ws of egr_wpe_workspace_bytes bytes.  Its result equals the staged calls bit for bit. */
+int64_t egr_wpe_frames(int64_t n, int n_fft, int hop);
+size_t egr_wpe_workspace_bytes(int channels, int64_t n, int n_fft, int hop, int taps);
+int egr_wpe_stft(const float* x, int channels, int64_t n, int n_fft, int hop, void* Y, void* stream);
+int egr_wpe_istft(const void* Y, int channels, int64_t frames, int n_fft, int hop, float* y, int64_t n_out, void* stream);
+int egr_wpe_iterate(const void* Y, const double* inv_in, int bins, int channels, int64_t frames, int taps, int delay, void* X, double* G,
+                    double* inv_out, int* flags_out, void* ws, size_t ws_bytes, void* stream);
+int egr_wpe_dereverb(const float* x, int channels, int64_t n, int n_fft, int hop, int taps, int delay, int iterations, float* y,
+                     int64_t n_out, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,6 +15,8 @@ section 3.  `--flashsr CKPT_DIR` does the same for FlashSR through the node's ow
 `--dfn3 MODEL_DIR` runs upstream `df.enhance.enhance` and the native DeepFilterNet3 forward pass (dfn_engine, dfn_weights.load) on
 the same seeded input and prints the relative error per channel (SPEC.md section 4b; parity unpinned until this has been run).
 `--dfn2 MODEL_DIR` does the same for DeepFilterNet2 (dfn2_engine, dfn2_weights.load; SPEC.md section 4c).
+`--wpe` runs nara_wpe's documented call -- stft, wpe() on (bins, channels, frames), istft, in float64 -- and this pack's
+egr_wpe_dereverb on the same seeded reverberant input and prints the relative error (SPEC.md section 4d; parity unpinned until run).
 """
 import argparse
 import sys
@@ -43,7 +45,10 @@ def main():
                          "(config.ini + checkpoints/*.ckpt.best)")
     ap.add_argument("--dfn2", default="", metavar="MODEL_DIR",
                     help="instead: the same for the native DeepFilterNet2 on MODEL_DIR ([train] model = deepfilternet2)")
+    ap.add_argument("--wpe", action="store_true", help="instead: compare nara_wpe (importable) with egr_wpe_dereverb (SPEC.md 4d)")
     args = ap.parse_args()
+    if args.wpe:
+        return compare_wpe(args.seconds)
     if args.flashsr:
         return compare_flashsr(args.flashsr)
     if args.dfn3:
@@ -90,6 +95,32 @@ def main():
         print(f"[{combo or 'default'}] upstream {up.shape} @ {sr_up} Hz vs this pack {mine.shape} @ {res['sample_rate']} Hz: "
               f"LSD mean/p95 = {lsd[0]:.4g} / {lsd[1]:.4g} dB   SI-SDR = {om.si_sdr(up[:m], mine[:m]):.2f} dB   "
               f"PCM_16 samples differing = {np.mean(np.abs(up[:m] - mine[:m]) * 32768 > 0.5):.4f}")
+
+
+def compare_wpe(seconds, n_fft=1024, hop=256, taps=10, delay=3, iterations=3):
+    """nara_wpe (float64, statistics mode "full") vs egr_wpe_dereverb at the node's default widgets, 16 kHz stereo."""
+    import torch
+    try:
+        from nara_wpe import wpe as np_wpe
+        from nara_wpe.utils import istft, stft
+    except Exception as e:
+        sys.exit(f"nara_wpe not importable here ({e}); this tool is opt-in")
+    from packload import load_pack
+    load_pack()
+    from egregora_amd import wpe_engine
+    sys.path.insert(0, str(ROOT / "tests"))
+    import wpe_cases
+    x = wpe_cases.signal(2, int(seconds * wpe_cases.SR), 4242)
+    Y = stft(x.astype(np.float64), size=n_fft, shift=hop)                      # [C, frames, bins] (SPEC WPE-Q1)
+    Z = np_wpe.wpe(Y.transpose(2, 0, 1), taps=taps, delay=delay, iterations=iterations, statistics_mode="full")
+    up = istft(Z.transpose(1, 2, 0), size=n_fft, shift=hop)
+    ours = wpe_engine.dereverb(torch.from_numpy(x).cuda(), n_fft, hop, taps, delay, iterations).cpu().numpy()
+    m = min(up.shape[-1], ours.shape[-1])
+    print(f"upstream {up.shape} vs this pack {ours.shape}")
+    for c in range(2):
+        e = float(np.linalg.norm(ours[c, :m] - up[c, :m]) / max(np.linalg.norm(up[c, :m]), 1e-30))
+        print(f"channel {c}: relative rms error egr_wpe_dereverb vs nara_wpe {e:.3e}; change against the input "
+              f"{float(np.linalg.norm(up[c, :x.shape[1]] - x[c]) / np.linalg.norm(x[c])):.3f}")
 
 
 def compare_dfn3(model_dir, seconds, dfn2=False):
