@@ -37,6 +37,8 @@ using egr::ConvChoice;
 
 enum { ACT_NONE = 0, ACT_SILU = 1, ACT_TANH = 2, ACT_LEAKY = 3, ACT_LOGCLAMP = 4 };
 enum { EW_ADD = 0, EW_AXPBY = 1, EW_SILU = 2, EW_SCALE = 3, EW_COPY = 4, EW_ADD_SCALE = 5 };
+// the want_ra argument of an operator, by name: its output feeds a split contraction directly, so the producer leaves its row maxima
+const bool WANT_RA = true, NO_RA = false;
 
 #define OKR(call)                 \
     do {                          \
@@ -238,10 +240,10 @@ struct egr_flashsr {
     bool out_amax_on = true;                          // contraction epilogues leave the row maxima of their outputs (EGREGORA_FLASHSR_OUT_AMAX=0: off)
     int direct3x3_max_cout = 128;                     // EGREGORA_FLASHSR_DIRECT3X3_MAX_COUT (0: off): see gn_conv3
     bool fused_amp = true;                            // EGREGORA_FLASHSR_FUSED_AMP=0: the thin AMP units as four launches each
-    bool next_out_ra = false;                         // set by a call site whose output feeds another split contraction directly; consumed by the next conv()
     int64_t h2_calls = 0;
 
     bool f32_mfma() const { return (flags & EGR_FSR_F32_MFMA) != 0; }
+    bool h2_on() const { return h2 && h2_mode == 1; } // the forward being enqueued runs the fp16 terms
     bool has(const std::string& k) const { return W.find(k) != W.end(); }
     const Wt* get(const std::string& k) const { auto it = W.find(k); return it == W.end() ? nullptr : &it->second; }
     float* ptr(const std::string& k) const { auto it = W.find(k); return it == W.end() ? nullptr : it->second.w; }
@@ -267,6 +269,13 @@ int new_ten(M* m, Ten& t, std::initializer_list<int64_t> shape) {
     t.p = (float*)m->cx->arena.get(t.bytes);
     if (!t.p) return EGR_ERR_ALLOC;
     t.a = &m->cx->arena;
+    return EGR_OK;
+}
+
+// a fresh arena tensor of x's shape
+int new_like(M* m, Ten& y, const Ten& x) {
+    OKR(new_ten(m, y, {x.numel()}));
+    y.nd = x.nd; memcpy(y.d, x.d, sizeof(y.d));
     return EGR_OK;
 }
 
@@ -501,14 +510,18 @@ unsigned* rs_take(M* m) {
     return p;
 }
 
-// slice for the row maxima of a tensor an element-wise producer is about to write (null outside the fp16 scheme)
-int rs_for_output(M* m, Ten& y, float** ra) {
-    *ra = nullptr;
-    if (!(m->h2 && m->h2_mode == 1 && m->out_amax_on) || y.numel() % m->R != 0) return EGR_OK;
+// Slice for the row maxima of the fresh tensor y, for a producer that leaves them as it writes y.  y.rs stays null -- the producer
+// runs its plain form, and the first split contraction that reads y measures it (row_amax_of) -- outside the fp16 scheme, when the
+// producer is switched off, or when y does not split into the forward's rows.
+//   sw:   RS_SWITCHED producers are turned off by EGREGORA_FLASHSR_OUT_AMAX=0; RS_ALWAYS ones (snake, the Winograd input transform) are not
+//   test: n (y's batch dimension, or its row / element count) must equal R (ROWS_EQUAL) or be a multiple of it (ROWS_DIVIDE)
+// (ROWS_EQUAL on the batch dimension B also covers "y's elements split into R rows": numel is a multiple of B)
+enum RsSwitch { RS_ALWAYS, RS_SWITCHED };
+enum RsRows { ROWS_EQUAL, ROWS_DIVIDE };
+int rs_for_output(M* m, Ten& y, RsSwitch sw, RsRows test, int64_t n) {
+    if (!m->h2_on() || (sw == RS_SWITCHED && !m->out_amax_on) || (test == ROWS_EQUAL ? n != m->R : n % m->R != 0)) return EGR_OK;
     y.rs = rs_take(m);
-    if (!y.rs) return EGR_ERR_ALLOC;
-    *ra = (float*)y.rs;
-    return EGR_OK;
+    return y.rs ? EGR_OK : EGR_ERR_ALLOC;
 }
 
 // per-batch-row max |x| of a tensor whose leading dimension runs over the R rows of the forward (nz > 1: nz blocks zx floats
@@ -534,7 +547,7 @@ int s3_launch(M* m, const Wt* w, const std::string& key, ConvCall& c, int64_t x_
         c.w = w->w; c.zw = zfloats;
         return egr::conv_call(c, m->st, ran);
     }
-    const bool use = m->h2 && w->w2 && m->h2_mode == 1 && ((int64_t)c.B * c.OH * c.OW) % m->R == 0;
+    const bool use = m->h2_on() && w->w2 && ((int64_t)c.B * c.OH * c.OW) % m->R == 0;
     c.w3 = use ? w->w2 : w->w3;
     c.zw = zfloats * (use ? 2 : 3) / 8;
     if (use) {
@@ -549,26 +562,24 @@ int s3_launch(M* m, const Wt* w, const std::string& key, ConvCall& c, int64_t x_
     return egr::conv_call(c, m->st, ran);
 }
 
-// general convolution: weights by key (key + ".weight", bias key + ".bias") or explicit entry `wk`
-int conv(M* m, Ten& y, const Ten& x, const std::string& wkey, int B, int H, int W, int Cin, int OH, int OW, int Cout, int KH, int KW,
-         int stride = 1, int dil = 1, int pad_t = 0, int pad_l = 0, int up2 = 0, int act = ACT_NONE, bool bias = true,
-         const float* bias_t = nullptr, const float* res = nullptr, float act_param = 0.f, const Wt* wk = nullptr) {
-    OKR(new_ten(m, y, {B, OH, OW, Cout}));
-    const bool want_out_amax = m->next_out_ra;
-    m->next_out_ra = false;
+// general convolution described by `c`: the caller fills geometry, epilogue and any explicit bias / residual by name; conv() allocates
+// y and completes x, y and the full output extent.  Weights by key (key + ".weight"; the bias is key + ".bias" when key_bias and c.bias
+// is null) or the explicit entry `wk` (no bias from the key).  want_ra: y feeds another split contraction directly, so the epilogue
+// leaves its row maxima.
+int conv(M* m, Ten& y, const Ten& x, const std::string& wkey, ConvCall& c, bool want_ra = false, const Wt* wk = nullptr, bool key_bias = true) {
+    OKR(new_ten(m, y, {c.B, c.OH, c.OW, c.Cout}));
     const Wt* w = wk ? wk : m->get(wkey + ".weight");
     EGR_CHECK(w != nullptr, EGR_ERR_ARG, "FlashSR: weight %s.weight missing", wkey.c_str());
-    const float* bt = bias_t ? bias_t : (bias && !wk ? m->ptr(wkey + ".bias") : nullptr);
-    const double fl = 2.0 * B * OH * OW * Cout * KH * KW * Cin;
+    if (!c.bias && key_bias && !wk) c.bias = m->ptr(wkey + ".bias");
+    const double fl = 2.0 * c.B * c.OH * c.OW * c.Cout * c.KH * c.KW * c.Cin;
     ProfScope ps(m);
-    ConvCall c; ConvChoice ran;
-    c.x = x.p; c.bias = bt; c.res = res; c.y = y.p;
-    c.B = B; c.H = H; c.W = W; c.Cin = Cin; c.OH = c.OHF = OH; c.OW = c.OWF = OW; c.Cout = Cout; c.KH = KH; c.KW = KW;
-    c.stride = stride; c.dil = dil; c.pad_t = pad_t; c.pad_l = pad_l; c.up2 = up2; c.act = act; c.act_param = act_param;
-    OKR(s3_launch(m, w, wkey, c, (int64_t)B * H * W * Cin, &x.rs, 0, &ran, want_out_amax ? &y.rs : nullptr));
+    ConvChoice ran;
+    c.x = x.p; c.y = y.p; c.OHF = c.OH; c.OWF = c.OW;
+    OKR(s3_launch(m, w, wkey, c, (int64_t)c.B * c.H * c.W * c.Cin, &x.rs, 0, &ran, want_ra ? &y.rs : nullptr));
     if (ps.on) {
         char det[160];
-        snprintf(det, sizeof(det), "%s B%d %dx%d Cin%d -> %dx%d Cout%d k%dx%d s%d d%d up%d", wkey.c_str(), B, H, W, Cin, OH, OW, Cout, KH, KW, stride, dil, up2);
+        snprintf(det, sizeof(det), "%s B%d %dx%d Cin%d -> %dx%d Cout%d k%dx%d s%d d%d up%d", wkey.c_str(), c.B, c.H, c.W, c.Cin, c.OH, c.OW, c.Cout,
+                 c.KH, c.KW, c.stride, c.dil, c.up2);
         ps.end(egr::conv_choice_name(ran), fl, det);
     }
     if (m->count_flops) m->flops += fl;
@@ -590,15 +601,10 @@ int groupnorm(M* m, Ten& y, const Ten& x, const std::string& key, float eps, boo
     const int HW = (int)(x.numel() / ((int64_t)B * Cc));
     const int G = m->cfg.gn_groups;
     OKR(gn_scratch(m, egr_groupnorm_workspace_bytes(B, Cc, G)));
-    y.release();
-    y.nd = x.nd; memcpy(y.d, x.d, sizeof(y.d));
-    y.bytes = (size_t)y.numel() * 4;
-    y.p = (float*)m->cx->arena.get(y.bytes);
-    if (!y.p) return EGR_ERR_ALLOC;
-    y.a = &m->cx->arena;
-    float* ra = nullptr;
-    if (B == m->R) OKR(rs_for_output(m, y, &ra));
-    return egr_groupnorm_nhwc_ra(x.p, m->ptr(key + ".weight"), m->ptr(key + ".bias"), y.p, B, HW, Cc, G, eps, silu ? 1 : 0, m->cx->gn_ws, ra, m->st);
+    OKR(new_like(m, y, x));
+    OKR(rs_for_output(m, y, RS_SWITCHED, ROWS_EQUAL, B));
+    return egr_groupnorm_nhwc_ra(x.p, m->ptr(key + ".weight"), m->ptr(key + ".bias"), y.p, B, HW, Cc, G, eps, silu ? 1 : 0, m->cx->gn_ws, (float*)y.rs,
+                                 m->st);
 }
 
 int gn_coeff(M* m, Ten& sc, Ten& sh, const Ten& x, const std::string& key, float eps) {
@@ -630,12 +636,9 @@ int conv_winograd(M* m, Ten& y, const Ten& x, const std::string& key, int act, c
     Ten V, Mx;
     OKR(new_ten(m, V, {nz, P, Cin}));
     // fp16 operand scheme: the F(4x4) input transform leaves the per-row maxima of V as it writes it
-    const bool v_h2 = m->h2 && m->h2_mode == 1 && wz && wz->w2 && Cin % 16 == 0 && B == m->R;
-    if (f4 && v_h2) {
-        V.rs = rs_take(m);
-        if (!V.rs) return EGR_ERR_ALLOC;
-        OKR(egr_winograd4_input_ra(x.p, gsc, gsh, gsilu, B, H, W, Cin, V.p, (float*)V.rs, m->st));
-    } else if (f4) OKR(egr_winograd4_input(x.p, gsc, gsh, gsilu, B, H, W, Cin, V.p, m->st));
+    if (f4 && wz && wz->w2 && Cin % 16 == 0) OKR(rs_for_output(m, V, RS_ALWAYS, ROWS_EQUAL, B));
+    if (V.rs) OKR(egr_winograd4_input_ra(x.p, gsc, gsh, gsilu, B, H, W, Cin, V.p, (float*)V.rs, m->st));
+    else if (f4) OKR(egr_winograd4_input(x.p, gsc, gsh, gsilu, B, H, W, Cin, V.p, m->st));
     else OKR(egr_winograd_input(x.p, gsc, gsh, gsilu, B, H, W, Cin, V.p, m->st));
     OKR(new_ten(m, Mx, {nz, P, Cout}));
     const double fl = nz * 2.0 * (double)P * Cin * Cout;
@@ -653,12 +656,8 @@ int conv_winograd(M* m, Ten& y, const Ten& x, const std::string& key, int act, c
     const int G = m->cfg.gn_groups;
     const int silu = act == ACT_SILU ? 1 : 0;
     // fp16 operand scheme: the output transform leaves the per-row maxima of y (it may feed a 1x1 / strided / phase convolution)
-    float* y_ra = nullptr;
-    if (f4 && m->h2 && m->h2_mode == 1 && m->out_amax_on && B == m->R) {
-        y.rs = rs_take(m);
-        if (!y.rs) return EGR_ERR_ALLOC;
-        y_ra = (float*)y.rs;
-    }
+    if (f4) OKR(rs_for_output(m, y, RS_SWITCHED, ROWS_EQUAL, B));
+    float* const y_ra = (float*)y.rs;
     if (f4 && !(m->flags & EGR_FSR_NO_GN_PARTIALS) && Cout % G == 0 && (Cout / G) % 4 == 0) {
         auto part = std::make_shared<Ten>();
         OKR(new_ten(m, *part, {P, Cout / 4, 2}));
@@ -693,14 +692,13 @@ int conv_up2_phases(M* m, Ten& y, const Ten& x, const std::string& key, int act)
     return EGR_OK;
 }
 
+// want_ra reaches only the generic exit; the phase, Winograd, tap-gather and one-input-channel exits track y's row maxima, or not, on their own
 int conv3(M* m, Ten& y, const Ten& x, const std::string& key, int stride = 1, int up2 = 0, int act = ACT_NONE, const float* res = nullptr,
-          int pad = 1, const float* bias_t = nullptr) {
+          int pad = 1, const float* bias_t = nullptr, bool want_ra = false) {
     const int B = (int)x.d[0], H = (int)x.d[1], W = (int)x.d[2], Cin = (int)x.d[3];
     const Wt* wb = m->get(key + ".weight");
     EGR_CHECK(wb != nullptr, EGR_ERR_ARG, "FlashSR: weight %s.weight missing", key.c_str());
     const int Cout = wb->Cout;
-    const bool want_ra = m->next_out_ra;            // only the generic path below hands it to conv(); the other paths track on their own
-    m->next_out_ra = false;
     if (up2 && m->has(key + ".weight.ph00") && stride == 1 && pad == 1 && !res && !bias_t) return conv_up2_phases(m, y, x, key, act);
     if (m->has(key + ".weight.wino") && !up2 && stride == 1 && pad == 1 && (act == ACT_NONE || act == ACT_SILU) && H % 2 == 0 && W % 2 == 0 &&
         Cin % 16 == 0)
@@ -710,7 +708,9 @@ int conv3(M* m, Ten& y, const Ten& x, const std::string& key, int stride = 1, in
     const Wt* taps = m->get(key + ".weight.taps");
     if (plain && taps && s3_of(m, taps, Cin, x.p)) {
         Ten P;
-        OKR(conv(m, P, x, key, B, H, W, Cin, H, W, 9 * Cout, 1, 1, 1, 1, 0, 0, 0, ACT_NONE, false, nullptr, nullptr, 0.f, taps));
+        ConvCall c;                                   // 1x1 contraction onto the nine per-tap products
+        c.B = B; c.H = c.OH = H; c.W = c.OW = W; c.Cin = Cin; c.Cout = 9 * Cout;
+        OKR(conv(m, P, x, key, c, NO_RA, taps));
         OKR(new_ten(m, y, {B, H, W, Cout}));
         return egr_tap_gather(P.p, m->ptr(key + ".bias"), y.p, B, H, W, 3, 3, Cout, 1, 1, m->st);
     }
@@ -720,32 +720,37 @@ int conv3(M* m, Ten& y, const Ten& x, const std::string& key, int stride = 1, in
         if (m->count_flops) m->flops += 2.0 * B * H * W * Cout * 9;
         return EGR_OK;
     }
-    const int LH = up2 ? 2 * H : H, LW = up2 ? 2 * W : W;
-    m->next_out_ra = want_ra;
-    return conv(m, y, x, key, B, H, W, Cin, LH / stride, LW / stride, Cout, 3, 3, stride, 1, pad, pad, up2, act, true, bias_t, res);
+    ConvCall c;                                       // the generic exit: the only one that takes the request for y's row maxima
+    c.B = B; c.H = H; c.W = W; c.Cin = Cin; c.OH = (up2 ? 2 * H : H) / stride; c.OW = (up2 ? 2 * W : W) / stride; c.Cout = Cout; c.KH = c.KW = 3;
+    c.stride = stride; c.pad_t = c.pad_l = pad; c.up2 = up2; c.act = act; c.bias = bias_t; c.res = res;
+    return conv(m, y, x, key, c, want_ra);
 }
 
-int conv1x1(M* m, Ten& y, const Ten& x, const std::string& key, const float* res = nullptr, int act = ACT_NONE) {
-    const int B = (int)x.d[0], H = (int)x.d[1], W = (int)x.d[2], Cin = (int)x.d[3];
-    return conv(m, y, x, key, B, H, W, Cin, H, W, m->get(key + ".weight")->Cout, 1, 1, 1, 1, 0, 0, 0, act, true, nullptr, res);
+int conv1x1(M* m, Ten& y, const Ten& x, const std::string& key, const float* res = nullptr, int act = ACT_NONE, bool want_ra = false) {
+    ConvCall c;
+    c.B = (int)x.d[0]; c.H = c.OH = (int)x.d[1]; c.W = c.OW = (int)x.d[2]; c.Cin = (int)x.d[3]; c.Cout = m->get(key + ".weight")->Cout;
+    c.act = act; c.res = res;
+    return conv(m, y, x, key, c, want_ra);
 }
 
-int linear(M* m, Ten& y, const Ten& x2, const std::string& key, const float* res = nullptr, int act = ACT_NONE, bool bias = true) {
-    const int rows = (int)x2.d[0], Cin = (int)x2.d[1];
+int linear(M* m, Ten& y, const Ten& x2, const std::string& key, const float* res = nullptr, int act = ACT_NONE, bool bias = true,
+           bool want_ra = false) {
     const Wt* w = m->get(key + ".weight");
     EGR_CHECK(w != nullptr, EGR_ERR_ARG, "FlashSR: weight %s.weight missing", key.c_str());
-    OKR(conv(m, y, x2, key, rows, 1, 1, Cin, 1, 1, w->Cout, 1, 1, 1, 1, 0, 0, 0, act, bias, nullptr, res));
-    y.view({rows, w->Cout});
+    ConvCall c;
+    c.B = (int)x2.d[0]; c.Cin = (int)x2.d[1]; c.Cout = w->Cout; c.act = act; c.res = res;
+    OKR(conv(m, y, x2, key, c, want_ra, nullptr, bias));
+    y.view({c.B, w->Cout});
     return EGR_OK;
 }
 
 int conv1d(M* m, Ten& y, const Ten& x, const std::string& key, int k, int stride = 1, int dil = 1, int pad = 0, int act = ACT_NONE,
-           const float* res = nullptr) {
-    const int B = (int)x.d[0], L = (int)x.d[1], Cin = (int)x.d[2];
-    const int Cout = m->get(key + ".weight")->Cout;
-    const int OL = (L + 2 * pad - dil * (k - 1) - 1) / stride + 1;
-    OKR(conv(m, y, x, key, B, 1, L, Cin, 1, OL, Cout, 1, k, stride, dil, 0, pad, 0, act, true, nullptr, res));
-    y.view({B, OL, Cout});
+           const float* res = nullptr, bool want_ra = false) {
+    ConvCall c;
+    c.B = (int)x.d[0]; c.W = (int)x.d[1]; c.Cin = (int)x.d[2]; c.Cout = m->get(key + ".weight")->Cout; c.KW = k;
+    c.OW = (c.W + 2 * pad - dil * (k - 1) - 1) / stride + 1; c.stride = stride; c.dil = dil; c.pad_l = pad; c.act = act; c.res = res;
+    OKR(conv(m, y, x, key, c, want_ra));
+    y.view({c.B, c.OW, c.Cout});
     return EGR_OK;
 }
 
@@ -759,7 +764,7 @@ int gn_conv3(M* m, Ten& y, const Ten& x, const std::string& norm_key, float eps,
     {
         const Wt* wd = m->get(conv_key + ".weight");
         const int B = (int)x.d[0];
-        if (wd && wd->w2 && m->h2 && m->h2_mode == 1 && m->direct3x3_max_cout > 0 && wd->Cout <= m->direct3x3_max_cout && wd->KH == 3 &&
+        if (wd && wd->w2 && m->h2_on() && m->direct3x3_max_cout > 0 && wd->Cout <= m->direct3x3_max_cout && wd->KH == 3 &&
             wd->KW == 3 && B == m->R && H % 4 == 0 && W % 32 == 0 && Cin % 32 == 0 && (int64_t)(H / 4) * (W / 32) * B >= 512 &&
             Cin % m->cfg.gn_groups == 0 && (((uintptr_t)x.p) & 15) == 0) {
             Ten sc, sh;
@@ -769,12 +774,7 @@ int gn_conv3(M* m, Ten& y, const Ten& x, const std::string& norm_key, float eps,
             if (!bound) return EGR_ERR_ALLOC;
             OKR(egr_gn_operand_bound(sc.p, sh.p, B, Cin, (const float*)x.rs, (float*)bound, m->st));
             OKR(new_ten(m, y, {B, H, W, wd->Cout}));
-            float* out_ra = nullptr;
-            if (m->out_amax_on) {
-                y.rs = rs_take(m);
-                if (!y.rs) return EGR_ERR_ALLOC;
-                out_ra = (float*)y.rs;
-            }
+            OKR(rs_for_output(m, y, RS_SWITCHED, ROWS_EQUAL, B));
             const float* bt = bias_t ? bias_t : m->ptr(conv_key + ".bias");
             const double fl = 2.0 * B * H * W * (double)wd->Cout * 9 * Cin;
             // GroupNorm partial statistics of y from the epilogue (the next norm then reads 1/32 of y's bytes instead of y)
@@ -791,7 +791,7 @@ int gn_conv3(M* m, Ten& y, const Ten& x, const std::string& norm_key, float eps,
             ConvCall c; ConvChoice ran;
             c.x = x.p; c.w3 = wd->w2; c.bias = bt; c.res = res; c.y = y.p; c.gn_scale = sc.p; c.gn_shift = sh.p; c.gn_silu = 1;
             c.B = B; c.H = c.OH = c.OHF = H; c.W = c.OW = c.OWF = W; c.Cin = Cin; c.Cout = wd->Cout; c.KH = c.KW = 3; c.pad_t = c.pad_l = 1;
-            c.sch = 1; c.w_scale = wd->w_scale; c.row_amax = (const float*)bound; c.batch_rows = B; c.out_amax = out_ra; c.gn_part = gpart;
+            c.sch = 1; c.w_scale = wd->w_scale; c.row_amax = (const float*)bound; c.batch_rows = B; c.out_amax = (float*)y.rs; c.gn_part = gpart;
             OKR(egr::conv_call(c, m->st, &ran));
             if (ps.on) ps.end(egr::conv_choice_name(ran), fl, conv_key);
             if (m->count_flops) m->flops += fl;
@@ -812,23 +812,16 @@ int gn_conv3(M* m, Ten& y, const Ten& x, const std::string& norm_key, float eps,
 
 int layernorm(M* m, Ten& y, const Ten& x2, const std::string& key) {
     OKR(new_ten(m, y, {x2.d[0], x2.d[1]}));
-    float* ra = nullptr;
-    if (x2.d[0] % m->R == 0) OKR(rs_for_output(m, y, &ra));
-    if (!ra) return egr_layernorm_rows(x2.p, m->ptr(key + ".weight"), m->ptr(key + ".bias"), y.p, x2.d[0], (int)x2.d[1], 1e-5f, m->st);
-    return egr_layernorm_rows_ra(x2.p, m->ptr(key + ".weight"), m->ptr(key + ".bias"), y.p, x2.d[0], (int)x2.d[1], 1e-5f, m->R, ra, m->st);
+    OKR(rs_for_output(m, y, RS_SWITCHED, ROWS_DIVIDE, x2.d[0]));
+    if (!y.rs) return egr_layernorm_rows(x2.p, m->ptr(key + ".weight"), m->ptr(key + ".bias"), y.p, x2.d[0], (int)x2.d[1], 1e-5f, m->st);
+    return egr_layernorm_rows_ra(x2.p, m->ptr(key + ".weight"), m->ptr(key + ".bias"), y.p, x2.d[0], (int)x2.d[1], 1e-5f, m->R, (float*)y.rs, m->st);
 }
 
 int eltwise(M* m, Ten& y, const Ten& a, const float* b, int op, float s0 = 0.f, float s1 = 0.f, bool want_ra = false) {
-    y.release();
-    y.nd = a.nd; memcpy(y.d, a.d, sizeof(y.d));
-    y.bytes = (size_t)y.numel() * 4;
-    y.p = (float*)m->cx->arena.get(y.bytes);
-    if (!y.p) return EGR_ERR_ALLOC;
-    y.a = &m->cx->arena;
-    float* ra = nullptr;
-    if (want_ra) OKR(rs_for_output(m, y, &ra));
-    if (!ra) return egr_eltwise(a.p, b, y.p, a.numel(), op, s0, s1, m->st);
-    return egr_eltwise_ra(a.p, b, y.p, a.numel(), op, s0, s1, m->R, ra, m->st);
+    OKR(new_like(m, y, a));
+    if (want_ra) OKR(rs_for_output(m, y, RS_SWITCHED, ROWS_DIVIDE, y.numel()));
+    if (!y.rs) return egr_eltwise(a.p, b, y.p, a.numel(), op, s0, s1, m->st);
+    return egr_eltwise_ra(a.p, b, y.p, a.numel(), op, s0, s1, m->R, (float*)y.rs, m->st);
 }
 
 // q, k, v [B*T][C] -> [B*T][C]: softmax(q k^T / sqrt(d)) v per head
@@ -842,7 +835,7 @@ int attention(M* m, Ten& o, const Ten& q, const Ten& k, const Ten& v, int B, int
     (void)scale;
     // fp16 operand scheme: both products on two fp16 terms, every operand scaled per batch row from its own maximum (q / k / v carry
     // theirs from the epilogues of their projections; the soft-max output lies in [0, 1]: a constant)
-    const bool h2 = s3 && m->h2 && m->h2_mode == 1 && B == m->R;
+    const bool h2 = s3 && m->h2_on() && B == m->R;
     if (h2) {
         OKR(row_amax_of(m, q.p, q.numel(), 1, 0, &q.rs));
         OKR(row_amax_of(m, k.p, k.numel(), 1, 0, &k.rs));
@@ -862,10 +855,9 @@ int attention(M* m, Ten& o, const Ten& q, const Ten& k, const Ten& v, int B, int
         OKR(new_ten(m, vt, {B, Cc, T}));
         OKR(egr_transpose_batched(v.p, vt.p, B, T, Cc, m->st));
         if (h2) {
-            float* o_ra = nullptr;                 // o feeds the output projection: its row maxima ride along
-            OKR(rs_for_output(m, o, &o_ra));
+            OKR(rs_for_output(m, o, RS_SWITCHED, ROWS_EQUAL, B));   // o feeds the output projection (B == R here, so o splits into the rows)
             OKR(egr_bgemm_nt_h2(S.p, vt.p, o.p, B, heads, T, d, T, T, T, Cc, (int64_t)heads * T * T, (int64_t)T * T, (int64_t)Cc * T, (int64_t)d * T,
-                                (int64_t)T * Cc, d, 1.0f, (const float*)m->cx->rs_ones, (const float*)v.rs, o_ra, m->st));
+                                (int64_t)T * Cc, d, 1.0f, (const float*)m->cx->rs_ones, (const float*)v.rs, (float*)o.rs, m->st));
         } else
         OKR(egr_bgemm_nt_s3(S.p, vt.p, o.p, B, heads, T, d, T, T, T, Cc, (int64_t)heads * T * T, (int64_t)T * T, (int64_t)Cc * T, (int64_t)d * T,
                             (int64_t)T * Cc, d, 1.0f, m->st));
@@ -879,22 +871,16 @@ int attention(M* m, Ten& o, const Ten& q, const Ten& k, const Ten& v, int B, int
 
 int snake(M* m, Ten& y, const Ten& x, const std::string& akey, const std::string& bkey) {
     OKR(new_ten(m, y, {x.d[0], x.d[1], x.d[2]}));
-    float* ra = nullptr;                           // fp16 operand scheme: y feeds a 1-D convolution; its row maxima ride along
-    if (m->h2 && m->h2_mode == 1 && (int)x.d[0] == m->R) {
-        y.rs = rs_take(m);
-        if (!y.rs) return EGR_ERR_ALLOC;
-        ra = (float*)y.rs;
-    }
-    return egr_snake_aa_ra(x.p, m->ptr(akey), m->ptr(bkey), m->filt, y.p, (int)x.d[0], (int)x.d[1], (int)x.d[2], m->cfg.aa_taps, ra, m->st);
+    OKR(rs_for_output(m, y, RS_ALWAYS, ROWS_EQUAL, (int)x.d[0]));   // fp16 operand scheme: y feeds a 1-D convolution; its row maxima ride along
+    return egr_snake_aa_ra(x.p, m->ptr(akey), m->ptr(bkey), m->filt, y.p, (int)x.d[0], (int)x.d[1], (int)x.d[2], m->cfg.aa_taps, (float*)y.rs, m->st);
 }
 
 int concat(M* m, Ten& y, const Ten& a, const Ten& b) {
     const int64_t rows = a.d[0] * a.d[1] * a.d[2];
     OKR(new_ten(m, y, {a.d[0], a.d[1], a.d[2], a.d[3] + b.d[3]}));
-    float* ra = nullptr;
-    if ((int)a.d[0] == m->R) OKR(rs_for_output(m, y, &ra));
-    if (!ra) return egr_concat_channels(a.p, b.p, y.p, rows, (int)a.d[3], (int)b.d[3], m->st);
-    return egr_concat_channels_ra(a.p, b.p, y.p, rows, (int)a.d[3], (int)b.d[3], m->R, ra, m->st);
+    OKR(rs_for_output(m, y, RS_SWITCHED, ROWS_EQUAL, (int)a.d[0]));
+    if (!y.rs) return egr_concat_channels(a.p, b.p, y.p, rows, (int)a.d[3], (int)b.d[3], m->st);
+    return egr_concat_channels_ra(a.p, b.p, y.p, rows, (int)a.d[3], (int)b.d[3], m->R, (float*)y.rs, m->st);
 }
 
 // ------------------------------------------------------------------------------------------------ constant sub-graph
@@ -935,8 +921,9 @@ int log_mel(M* m, Ten& mel, const float* x, int B, int L) {
     OKR(new_ten(m, mag, {B, c.n_frames, m->ldm}));
     OKR(egr_stft_frames(x, B, L, c.n_fft, c.hop, rpad, c.n_frames, t_valid, m->ldm, m->window, mag.p, m->st));
     mag.view({(int64_t)B * c.n_frames, 1, 1, m->ldm});
-    OKR(conv(m, mel, mag, "mel_fb", B * c.n_frames, 1, 1, m->ldm, 1, 1, c.n_mels, 1, 1, 1, 1, 0, 0, 0, ACT_LOGCLAMP, false, nullptr, nullptr,
-             c.log_floor, m->get("mel_fb")));
+    ConvCall cc;
+    cc.B = B * c.n_frames; cc.Cin = m->ldm; cc.Cout = c.n_mels; cc.act = ACT_LOGCLAMP; cc.act_param = c.log_floor;
+    OKR(conv(m, mel, mag, "mel_fb", cc, NO_RA, m->get("mel_fb")));
     mel.view({B, c.n_frames, c.n_mels, 1});
     return EGR_OK;
 }
@@ -972,16 +959,12 @@ int vae_attn(M* m, Ten& y, const Ten& x, const std::string& name) {
     const int B = (int)x.d[0], H = (int)x.d[1], W = (int)x.d[2], Cc = (int)x.d[3];
     Ten h, q, k, v, o;
     OKR(groupnorm(m, h, x, name + ".norm", 1e-6f, false));
-    m->next_out_ra = true;
-    OKR(conv1x1(m, q, h, name + ".q"));
-    m->next_out_ra = true;
-    OKR(conv1x1(m, k, h, name + ".k"));
-    m->next_out_ra = true;
-    OKR(conv1x1(m, v, h, name + ".v"));
+    OKR(conv1x1(m, q, h, name + ".q", nullptr, ACT_NONE, WANT_RA));
+    OKR(conv1x1(m, k, h, name + ".k", nullptr, ACT_NONE, WANT_RA));
+    OKR(conv1x1(m, v, h, name + ".v", nullptr, ACT_NONE, WANT_RA));
     OKR(attention(m, o, q, k, v, B, H * W, Cc, 1));
     o.view({B, H, W, Cc});
-    m->next_out_ra = true;
-    return conv1x1(m, y, o, name + ".proj_out", x.p);
+    return conv1x1(m, y, o, name + ".proj_out", x.p, ACT_NONE, WANT_RA);
 }
 
 int vae_encode(M* m, Ten& z, const Ten& mel) {
@@ -994,8 +977,7 @@ int vae_encode(M* m, Ten& z, const Ten& mel) {
             h = std::move(t);
         }
         if (lv != c.vae_levels - 1) {
-            m->next_out_ra = true;
-            OKR(conv3(m, t, h, "vae.encoder.down." + std::to_string(lv) + ".downsample.conv", 2, 0, ACT_NONE, nullptr, 0));
+            OKR(conv3(m, t, h, "vae.encoder.down." + std::to_string(lv) + ".downsample.conv", 2, 0, ACT_NONE, nullptr, 0, nullptr, WANT_RA));
             h = std::move(t);
         }
     }
@@ -1016,8 +998,7 @@ int vae_encode(M* m, Ten& z, const Ten& mel) {
 int vae_decode(M* m, Ten& y, const Ten& z) {
     const egr_flashsr_config& c = m->cfg;
     Ten h, t;
-    m->next_out_ra = true;
-    OKR(conv1x1(m, t, z, "vae.post_quant_conv"));
+    OKR(conv1x1(m, t, z, "vae.post_quant_conv", nullptr, ACT_NONE, WANT_RA));
     OKR(conv3(m, h, t, "vae.decoder.conv_in"));
     OKR(vae_res(m, t, h, "vae.decoder.mid.block_1")); h = std::move(t);
     OKR(vae_attn(m, t, h, "vae.decoder.mid.attn_1")); h = std::move(t);
@@ -1056,12 +1037,10 @@ int unet_block(M* m, Ten& y, const Ten& x, const std::string& base, bool has_att
         const std::string an = base + ".st.attn" + std::to_string(a);
         Ten n_, q, k, v, o, t2;
         OKR(layernorm(m, n_, t, an + "_ln"));
-        m->next_out_ra = true;                         // q, k, v feed the attention products: their row maxima ride along
-        OKR(linear(m, q, n_, an + ".to_q", nullptr, ACT_NONE, false));
-        m->next_out_ra = true;
-        OKR(linear(m, k, n_, an + ".to_k", nullptr, ACT_NONE, false));
-        m->next_out_ra = true;
-        OKR(linear(m, v, n_, an + ".to_v", nullptr, ACT_NONE, false));
+        // q, k, v feed the attention products: their row maxima ride along
+        OKR(linear(m, q, n_, an + ".to_q", nullptr, ACT_NONE, /*bias*/ false, WANT_RA));
+        OKR(linear(m, k, n_, an + ".to_k", nullptr, ACT_NONE, /*bias*/ false, WANT_RA));
+        OKR(linear(m, v, n_, an + ".to_v", nullptr, ACT_NONE, /*bias*/ false, WANT_RA));
         OKR(attention(m, o, q, k, v, B, T, Cc, heads));
         OKR(linear(m, t2, o, an + ".to_out", t.p));
         t = std::move(t2);
@@ -1070,17 +1049,12 @@ int unet_block(M* m, Ten& y, const Ten& x, const std::string& base, bool has_att
     OKR(layernorm(m, ln, t, base + ".st.ff_ln"));
     OKR(linear(m, u, ln, base + ".st.ff.geglu"));
     OKR(new_ten(m, g, {(int64_t)B * T, 4 * Cc}));
-    {
-        float* ra = nullptr;
-        if (B == m->R) OKR(rs_for_output(m, g, &ra));
-        if (ra) OKR(egr_geglu_ra(u.p, g.p, (int64_t)B * T, 4 * Cc, m->R, ra, m->st));
-        else OKR(egr_geglu(u.p, g.p, (int64_t)B * T, 4 * Cc, m->st));
-    }
-    m->next_out_ra = true;
-    OKR(linear(m, t3, g, base + ".st.ff.out", t.p));
+    OKR(rs_for_output(m, g, RS_SWITCHED, ROWS_EQUAL, B));
+    if (g.rs) OKR(egr_geglu_ra(u.p, g.p, (int64_t)B * T, 4 * Cc, m->R, (float*)g.rs, m->st));
+    else OKR(egr_geglu(u.p, g.p, (int64_t)B * T, 4 * Cc, m->st));
+    OKR(linear(m, t3, g, base + ".st.ff.out", t.p, ACT_NONE, /*bias*/ true, WANT_RA));
     t3.view({B, H, W, Cc});
-    m->next_out_ra = true;
-    return conv1x1(m, y, t3, base + ".st.proj_out", r.p);
+    return conv1x1(m, y, t3, base + ".st.proj_out", r.p, ACT_NONE, WANT_RA);
 }
 
 int unet(M* m, Ten& out, Ten&& x0) {
@@ -1097,8 +1071,7 @@ int unet(M* m, Ten& out, Ten&& x0) {
             skips.push_back(std::move(t));
             h = std::move(cp);
         } else if (kind == "down") {
-            m->next_out_ra = true;
-            OKR(conv3(m, t, h, base + ".conv", 2, 0, ACT_NONE, nullptr, 1));
+            OKR(conv3(m, t, h, base + ".conv", 2, 0, ACT_NONE, nullptr, 1, nullptr, WANT_RA));
             Ten cp = t.alias();
             skips.push_back(std::move(t));
             h = std::move(cp);
@@ -1143,7 +1116,7 @@ int amp(M* m, Ten& y, Ten&& h, int j) {
                 const Wt* w1 = m->get(b + ".conv1.weight");
                 const Wt* w2 = m->get(b + ".conv2.weight");
                 const int Cc = (int)cur->d[2];
-                if (m->fused_amp && m->h2 && m->h2_mode == 1 && w1 && w2 && w1->w2 && w2->w2 && Cc == 16 && w1->Cout == Cc && w2->Cout == Cc && (k & 1) &&
+                if (m->fused_amp && m->h2_on() && w1 && w2 && w1->w2 && w2->w2 && Cc == 16 && w1->Cout == Cc && w2->Cout == Cc && (k & 1) &&
                     k <= 11 && d * (k - 1) / 2 <= 25 && c.aa_taps == 12 && cur->d[1] >= 16) {
                     OKR(new_ten(m, xn, {cur->d[0], cur->d[1], cur->d[2]}));
                     ProfScope ps(m);
@@ -1174,10 +1147,10 @@ int amp(M* m, Ten& y, Ten&& h, int j) {
             OKR(eltwise(m, s, acc, x.p, EW_ADD));
             acc = std::move(s);
         } else {                                   // last branch: the mean's scale rides on the last add
-            return eltwise(m, y, acc, x.p, EW_ADD_SCALE, 1.0f / c.voc_n_kernels, 0.f, true);   // feeds the next stage's up-sampling GEMM
+            return eltwise(m, y, acc, x.p, EW_ADD_SCALE, 1.0f / c.voc_n_kernels, 0.f, WANT_RA);   // feeds the next stage's up-sampling GEMM
         }
     }
-    return eltwise(m, y, acc, nullptr, EW_SCALE, 1.0f / c.voc_n_kernels, 0.f, true);
+    return eltwise(m, y, acc, nullptr, EW_SCALE, 1.0f / c.voc_n_kernels, 0.f, WANT_RA);
 }
 
 int vocoder(M* m, Ten& y, const Ten& mel_hat, const float* wave, int B) {
@@ -1192,8 +1165,8 @@ int vocoder(M* m, Ten& y, const Ten& mel_hat, const float* wave, int B) {
         const Ten* e = &e0;
         for (int i = 0; i < n; ++i) {
             const int r = c.voc_rates[n - 1 - i];
-            m->next_out_ra = i + 1 < n;                 // feeds the next strided convolution of the encoder
-            OKR(conv1d(m, feats[i], *e, "voc.wave_enc." + std::to_string(i), 2 * r + 1, r, 1, r, ACT_LEAKY));
+            const bool feeds_next = i + 1 < n;          // the next strided convolution of the encoder reads it
+            OKR(conv1d(m, feats[i], *e, "voc.wave_enc." + std::to_string(i), 2 * r + 1, r, 1, r, ACT_LEAKY, nullptr, feeds_next));
             e = &feats[i];
         }
     }
@@ -1201,8 +1174,7 @@ int vocoder(M* m, Ten& y, const Ten& mel_hat, const float* wave, int B) {
     mh.view({B, T, Fm});
     mh.p = mel_hat.p;
     Ten h;
-    m->next_out_ra = true;
-    OKR(conv1d(m, h, mh, "voc.conv_pre", 7, 1, 1, 3, ACT_NONE, feats[n - 1].p));
+    OKR(conv1d(m, h, mh, "voc.conv_pre", 7, 1, 1, 3, ACT_NONE, feats[n - 1].p, WANT_RA));
     feats[n - 1].release();
     for (int j = 0; j < n; ++j) {
         const int r = c.voc_rates[j];
@@ -1214,7 +1186,9 @@ int vocoder(M* m, Ten& y, const Ten& mel_hat, const float* wave, int B) {
         hx.view({(int64_t)Bc * Lin, 1, 1, Ci});
         hx.p = h.p;
         hx.rs = h.rs;                                  // (a view: the row maxima of h are its own)
-        OKR(conv(m, Y, hx, "voc.ups." + std::to_string(j), Bc * Lin, 1, 1, Ci, 1, 1, kt * Co, 1, 1, 1, 1, 0, 0, 0, ACT_NONE, false, nullptr, nullptr, 0.f, wt));
+        ConvCall cu;                                   // ConvTranspose1d as a GEMM onto [kt][Co] columns, gathered by col2im below
+        cu.B = Bc * Lin; cu.Cin = Ci; cu.Cout = kt * Co;
+        OKR(conv(m, Y, hx, "voc.ups." + std::to_string(j), cu, NO_RA, wt));
         OKR(new_ten(m, out, {Bc, (int64_t)Lin * r, Co}));
         const float* add = (j <= n - 2) ? feats[n - 2 - j].p : nullptr;
         OKR(egr_col2im_convtr1d(Y.p, m->ptr("voc.ups." + std::to_string(j) + ".bias"), add, out.p, Bc, Lin, Lin * r, Co, kt, r, (kt - r) / 2, m->st));

@@ -4,8 +4,6 @@
 #include <math.h>
 #include <string.h>
 
-#include <map>
-#include <mutex>
 #include <vector>
 
 #include <stdlib.h>
@@ -13,7 +11,7 @@
 
 #include "egr_common.h"
 #include "egr_rowmax.h"
-#include "egr_fft_device.h"
+#include "egr_stft_tables.h"
 #include "egr_plan.h"
 
 namespace egr {
@@ -751,31 +749,6 @@ __global__ __launch_bounds__(256) void k_cheby_gain(const int* __restrict__ cut,
     }
 }
 
-struct FrameTables { FftDesc fd; cplx *tw, *wsplit; };
-static std::mutex g_mu;
-static std::map<std::pair<int, int>, FrameTables> g_tabs;
-
-static int frame_tables(int n_fft, FrameTables* out) {
-    int dev = 0;
-    EGR_HIP(hipGetDevice(&dev));
-    std::lock_guard<std::mutex> lk(g_mu);
-    auto it = g_tabs.find({dev, n_fft});
-    if (it != g_tabs.end()) { *out = it->second; return EGR_OK; }
-    FrameTables t;
-    const int Mh = n_fft / 2;
-    EGR_CHECK(make_schedule(Mh, &t.fd, 127), EGR_ERR_UNSUPPORTED, "n_fft=%d: n_fft/2 has a prime factor above 127", n_fft);
-    std::vector<float2> h;
-    make_twiddles(h, Mh, 1, Mh);
-    EGR_HIP(hipMalloc((void**)&t.tw, h.size() * sizeof(float2)));
-    EGR_HIP(hipMemcpy(t.tw, h.data(), h.size() * sizeof(float2), hipMemcpyHostToDevice));
-    make_twiddles(h, Mh + 1, 1, n_fft);
-    EGR_HIP(hipMalloc((void**)&t.wsplit, h.size() * sizeof(float2)));
-    EGR_HIP(hipMemcpy(t.wsplit, h.data(), h.size() * sizeof(float2), hipMemcpyHostToDevice));
-    g_tabs[{dev, n_fft}] = t;
-    *out = t;
-    return EGR_OK;
-}
-
 // Thin ends of the VAE.  (1) A 3x3 convolution with very few outputs (conv_out: 128 -> 1) as a 1x1 contraction onto the kh*kw*Cout
 // per-tap partial products P[pixel][tap*Cout + co] (one ninth of the MFMA work an im2col tile with 31 idle columns needs)
 // followed by this gather: y[b,oy,ox,co] = bias[co] + sum over taps of P at the tap's source pixel (outside the image: nothing,
@@ -848,6 +821,24 @@ static inline int grid1d(long long n) {
 
 using namespace egr;
 
+// GroupNorm statistics of x into stats[B][G][2] (sum, sum of squares), then the per-(b, c) scale / shift: shared by the two entry points below
+static int gn_stats_coeff(const float* x, const float* gamma, const float* beta, int B, int HW, int C, int G, float eps, double* stats,
+                          float* scale, float* shift, hipStream_t st) {
+    EGR_HIP(hipMemsetAsync(stats, 0, sizeof(double) * B * G * 2, st));
+    int slab = (HW + 255) / 256;
+    if (slab < 16) slab = HW < 16 ? HW : 16;
+    const int nslab = (HW + slab - 1) / slab;
+    if (C % 4 == 0 && C / 4 <= 256 && (C / G) % 4 == 0 && G <= 64 && (((uintptr_t)x) & 15) == 0) {
+        int slab4 = (HW + 511) / 512;                   // >= 512 workgroups per image row, >= 64 positions each
+        if (slab4 < 64) slab4 = HW < 64 ? HW : 64;
+        hipLaunchKernelGGL(k_gn_stats_v4, dim3((HW + slab4 - 1) / slab4, B), dim3(256), 0, st, x, HW, C, G, stats, slab4);
+    } else
+        hipLaunchKernelGGL(k_gn_stats, dim3(nslab, B), dim3(C < 256 ? ((C + 63) / 64) * 64 : 256), 0, st, x, HW, C, G, stats, slab);
+    hipLaunchKernelGGL(k_gn_coeff, dim3((B * C + 255) / 256), dim3(256), 0, st, stats, gamma, beta, scale, shift, B, C, G,
+                       (double)HW * (C / G), eps);
+    return EGR_OK;
+}
+
 extern "C" int egr_groupnorm_nhwc_ra(const float* x, const float* gamma, const float* beta, float* y, int B, int HW, int C,
                                      int G, float eps, int silu, void* workspace, float* row_amax, void* stream);
 extern "C" int egr_groupnorm_nhwc(const float* x, const float* gamma, const float* beta, float* y, int B, int HW, int C,
@@ -866,18 +857,8 @@ extern "C" int egr_groupnorm_nhwc_ra(const float* x, const float* gamma, const f
     double* stats = (double*)workspace;
     float* scale = (float*)(stats + (size_t)B * G * 2);
     float* shift = scale + (size_t)B * C;
-    EGR_HIP(hipMemsetAsync(stats, 0, sizeof(double) * B * G * 2, st));
-    int slab = (HW + 255) / 256;
-    if (slab < 16) slab = HW < 16 ? HW : 16;
-    const int nslab = (HW + slab - 1) / slab;
-    if (C % 4 == 0 && C / 4 <= 256 && (C / G) % 4 == 0 && G <= 64 && (((uintptr_t)x) & 15) == 0) {
-        int slab4 = (HW + 511) / 512;                   // >= 512 workgroups per image row, >= 64 positions each
-        if (slab4 < 64) slab4 = HW < 64 ? HW : 64;
-        hipLaunchKernelGGL(k_gn_stats_v4, dim3((HW + slab4 - 1) / slab4, B), dim3(256), 0, st, x, HW, C, G, stats, slab4);
-    } else
-        hipLaunchKernelGGL(k_gn_stats, dim3(nslab, B), dim3(C < 256 ? ((C + 63) / 64) * 64 : 256), 0, st, x, HW, C, G, stats, slab);
-    hipLaunchKernelGGL(k_gn_coeff, dim3((B * C + 255) / 256), dim3(256), 0, st, stats, gamma, beta, scale, shift, B, C, G,
-                       (double)HW * (C / G), eps);
+    int rc = gn_stats_coeff(x, gamma, beta, B, HW, C, G, eps, stats, scale, shift, st);
+    if (rc) return rc;
     const long long n4 = (long long)HW * C / 4;
     hipLaunchKernelGGL(k_affine_c, dim3(row_grid_x(n4, B, 8192, 2), (unsigned)B), dim3(256), 0, st, x, scale, shift, y, n4, HW, C, silu,
                        (unsigned*)row_amax);
@@ -893,18 +874,8 @@ extern "C" int egr_groupnorm_coeff(const float* x, const float* gamma, const flo
     EGR_CHECK(B >= 1 && HW >= 1 && C >= 4 && G >= 1 && C % G == 0, EGR_ERR_ARG, "bad groupnorm geometry");
     hipStream_t st = (hipStream_t)stream;
     double* stats = (double*)workspace;
-    EGR_HIP(hipMemsetAsync(stats, 0, sizeof(double) * B * G * 2, st));
-    int slab = (HW + 255) / 256;
-    if (slab < 16) slab = HW < 16 ? HW : 16;
-    const int nslab = (HW + slab - 1) / slab;
-    if (C % 4 == 0 && C / 4 <= 256 && (C / G) % 4 == 0 && G <= 64 && (((uintptr_t)x) & 15) == 0) {
-        int slab4 = (HW + 511) / 512;                   // >= 512 workgroups per image row, >= 64 positions each
-        if (slab4 < 64) slab4 = HW < 64 ? HW : 64;
-        hipLaunchKernelGGL(k_gn_stats_v4, dim3((HW + slab4 - 1) / slab4, B), dim3(256), 0, st, x, HW, C, G, stats, slab4);
-    } else
-        hipLaunchKernelGGL(k_gn_stats, dim3(nslab, B), dim3(C < 256 ? ((C + 63) / 64) * 64 : 256), 0, st, x, HW, C, G, stats, slab);
-    hipLaunchKernelGGL(k_gn_coeff, dim3((B * C + 255) / 256), dim3(256), 0, st, stats, gamma, beta, scale, shift, B, C, G,
-                       (double)HW * (C / G), eps);
+    int rc = gn_stats_coeff(x, gamma, beta, B, HW, C, G, eps, stats, scale, shift, st);
+    if (rc) return rc;
     EGR_HIP(hipGetLastError());
     return EGR_OK;
 }
@@ -1104,8 +1075,8 @@ extern "C" int egr_stft_frames(const float* x, int B, int L, int n_fft, int hop,
               EGR_ERR_ARG, "bad argument");
     EGR_CHECK(n_fft >= 4 && n_fft % 2 == 0 && n_fft <= 8192 && ldm >= n_fft / 2 + 1 && rpad < L, EGR_ERR_UNSUPPORTED,
               "bad STFT geometry");
-    FrameTables t;
-    int rc = frame_tables(n_fft, &t);
+    StftTables t;
+    int rc = stft_tables(n_fft, &t);
     if (rc) return rc;
     const size_t lds = (size_t)2 * (n_fft / 2) * sizeof(float2);
     hipLaunchKernelGGL(k_stft_frames, dim3(T, B), dim3(256), lds, (hipStream_t)stream, x, L, n_fft, hop, rpad, T, t_valid,

@@ -1,4 +1,5 @@
-// Per-(device, n_fft) tables of the real-input LDS transforms (k_stft_mag, k_wpe_stft, k_wpe_istft): defined in egr_glue.hip.
+// Per-(device, n_fft) tables of the real-input LDS transforms (k_stft_mag, k_stft_frames, k_wpe_stft, k_wpe_istft):
+// defined in egr_glue.hip.
 #pragma once
 #include "egr_fft_device.h"
 

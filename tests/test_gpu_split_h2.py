@@ -315,6 +315,35 @@ def test_pool_of_row_maxima_grows_instead_of_failing_the_call(pack, monkeypatch)
         e_.close()
 
 
+def test_output_bits_do_not_depend_on_how_the_row_maxima_arrive(pack, monkeypatch):
+    """A row maximum is an exact maximum whether a producer's epilogue raises it or a k_absmax_rows pass reads the tensor back, so a
+    handle created with EGREGORA_FLASHSR_OUT_AMAX=0 (no switched producer leaves maxima; the split contractions measure their inputs)
+    returns the bits of a default handle on the fp16 terms.  That the switch took effect shows in the launches: the handle without
+    producer maxima runs many more k_absmax_rows passes per call (counted by torch.profiler, which sees every launch of the process)."""
+    from torch.profiler import ProfilerActivity, profile
+    cfg, (ea,) = _engines(1)
+    ea.handle
+    monkeypatch.setenv("EGREGORA_FLASHSR_OUT_AMAX", "0")
+    _, (eb,) = _engines(1)
+    eb.handle                                                   # egr_flashsr_create reads the switch: the handle is built lazily
+    monkeypatch.delenv("EGREGORA_FLASHSR_OUT_AMAX")
+    assert ea.split_info()["enabled"] and eb.split_info()["enabled"]
+    x = (0.05 * torch.randn(3, cfg.chunk, generator=torch.Generator().manual_seed(14))).cuda()
+    ids = torch.tensor([4, 0, 9], dtype=torch.int64, device="cuda")
+    ys, passes = [], []
+    for e_ in (ea, eb):
+        e_.c_infer(x, ids, 4)                                   # the first call sizes the scratch; the counted one is the steady state
+        with profile(activities=[ProfilerActivity.CUDA]) as prof:
+            ys.append(e_.c_infer(x, ids, 4))
+            torch.cuda.synchronize()
+        passes.append(sum("k_absmax_rows" in ev.name for ev in prof.events()))
+    print("k_absmax_rows passes per call: default %d, OUT_AMAX=0 %d" % tuple(passes))
+    assert torch.equal(ys[1], ys[0])
+    assert 0 < passes[0] < passes[1], passes
+    for e_ in (ea, eb):
+        e_.close()
+
+
 def test_warmup_changes_nothing_but_the_first_call_cost(pack):
     """egr_flashsr_warmup (one throw-away pass of silence when the engine is built): the next call's bits are those of a handle that was
     never warmed, the host's call counter does not see it, and the scratch it sized is reported."""
