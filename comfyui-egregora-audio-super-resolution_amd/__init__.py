@@ -8,7 +8,8 @@ nor a GPU -- the nodes raise at run() time when either is missing.
 
 The evaluation pack's loudness meter, 1770 gain match and ABX nodes (egregora_audio_eval_loudness.py) are registered only when the
 environment variable EGREGORA_EVAL_NODES is "1" at import; the WPE dereverberation node (egregora_audio_enhance_wpe.py) only when
-EGREGORA_ENHANCE_NODES is "1".  Without them the registered set is the one listed above.
+EGREGORA_ENHANCE_NODES is "1", the Descript Audio Codec encode / decode nodes (egregora_audio_codec_dac.py) only when
+EGREGORA_CODEC_NODES is "1".  Without them the registered set is the one listed above.
 """
 import os
 
@@ -47,5 +48,10 @@ if os.environ.get("EGREGORA_ENHANCE_NODES") == "1":
     from .egregora_audio_enhance_wpe import (NODE_CLASS_MAPPINGS as WPE_MAP, NODE_DISPLAY_NAME_MAPPINGS as WPE_NAMES)
     NODE_CLASS_MAPPINGS.update(WPE_MAP)
     NODE_DISPLAY_NAME_MAPPINGS.update(WPE_NAMES)
+
+if os.environ.get("EGREGORA_CODEC_NODES") == "1":
+    from .egregora_audio_codec_dac import (NODE_CLASS_MAPPINGS as DAC_MAP, NODE_DISPLAY_NAME_MAPPINGS as DAC_NAMES)
+    NODE_CLASS_MAPPINGS.update(DAC_MAP)
+    NODE_DISPLAY_NAME_MAPPINGS.update(DAC_NAMES)
 
 __all__ = ["NODE_CLASS_MAPPINGS", "NODE_DISPLAY_NAME_MAPPINGS"]

@@ -1,0 +1,928 @@
+// Descript Audio Codec forward pass on gfx950 (SPEC.md 4e): encoder, residual vector quantiser, decoder.
+//
+// The handle keeps the weights (weight norm already folded by the host, dac_weights.pack) repacked for the contraction launcher
+// (csrc/egr_nn_gemm.hip): every convolution with Cin % 16 == 0 runs on two fp16 terms per operand (scheme 1, egr_conv_h2's path), the
+// others on the fp32 MFMA kernel.  Activations are channels-last [rows][L][C]; rows are independent mono signals.  Own kernels:
+//   k_dac_snake    x + sin^2(alpha x) / (alpha + 1e-9) per channel, and the row's max |y| for the contraction that reads y
+//   k_dac_conv_in  the Cin = 1, k = 7 input convolution (with the right zero pad to a multiple of the hop)
+//   k_dac_conv_out the Cout = 1, k = 7 output convolution with tanh: per input row seven partial dots, then a 7-term gather
+//   k_dac_vq       all stages of the residual quantiser in one launch; a workgroup keeps the residuals and sums of its frames in LDS
+// Work is enqueued on the caller's stream; nothing synchronises (the workspace grows with hipMallocAsync on that stream; the launcher's
+// split-K scratch is allocated the first time a stream needs it).
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "egr_conv.h"
+
+namespace egr {
+namespace {
+
+constexpr int DAC_LDS_MAX = 160 * 1024;
+constexpr int DAC_LDS_BUDGET = 150 * 1024;
+constexpr int DAC_MAX_WIDTH = 2048, DAC_MAX_RATE = 16, DAC_MAX_CODEBOOKS = 32, DAC_MAX_CB_FLOATS = 16384, DAC_MAX_CB_DIM = 64;
+constexpr int DAC_AMAX_SLOTS = 8 * 7 + 4;          // snakes of one side (7 per block, one in front of the output convolution) + z
+
+// ------------------------------------------------------------------------------------------------------------------ kernels
+// y = x + sin^2(alpha[c] x) * inva[c] over rows of per_row = L * C floats (in place when y == x); row_amax[r * EGR_ROW_AMAX_STRIDE]
+// (zeroed by the host) is raised to the row's max |y|.
+__global__ __launch_bounds__(256) void k_dac_snake(const float* x, const float* __restrict__ alpha, const float* __restrict__ inva, float* y,
+                                                   long long per_row, int C, unsigned* __restrict__ row_amax) {
+    __shared__ float wmax[4];
+    const int r = blockIdx.y;
+    const float* xr = x + (size_t)r * per_row;
+    float* yr = y + (size_t)r * per_row;
+    float vm = 0.f;
+    if ((C & 3) == 0) {
+        for (long long i = ((long long)blockIdx.x * 256 + threadIdx.x) * 4; i < per_row; i += (long long)gridDim.x * 1024) {
+            const int c = (int)(i % C);
+            const float4 v = *(const float4*)(xr + i), a = *(const float4*)(alpha + c), q = *(const float4*)(inva + c);
+            float4 o;
+            float t;
+            t = sinf(a.x * v.x); o.x = fmaf(t * t, q.x, v.x);
+            t = sinf(a.y * v.y); o.y = fmaf(t * t, q.y, v.y);
+            t = sinf(a.z * v.z); o.z = fmaf(t * t, q.z, v.z);
+            t = sinf(a.w * v.w); o.w = fmaf(t * t, q.w, v.w);
+            *(float4*)(yr + i) = o;
+            vm = fmaxf(vm, fmaxf(fmaxf(fabsf(o.x), fabsf(o.y)), fmaxf(fabsf(o.z), fabsf(o.w))));
+        }
+    } else {
+        for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < per_row; i += (long long)gridDim.x * 256) {
+            const int c = (int)(i % C);
+            const float v = xr[i], t = sinf(alpha[c] * v), o = fmaf(t * t, inva[c], v);
+            yr[i] = o;
+            vm = fmaxf(vm, fabsf(o));
+        }
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) vm = fmaxf(vm, __shfl_xor(vm, o));
+    if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = vm;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const unsigned bits = __float_as_uint(fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3])));
+        unsigned* slot = row_amax + (size_t)r * EGR_ROW_AMAX_STRIDE;
+        if (bits > __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(slot, bits);
+    }
+}
+
+// y[r][l][c] = b[c] + sum_t w[t][c] x[r][l + t - 3], x [rows][n] read as zero outside [0, n), l < n_pad
+__global__ __launch_bounds__(256) void k_dac_conv_in(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ b,
+                                                     float* __restrict__ y, long long n, long long n_pad, int D, long long total) {
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+        const int c = (int)(i % D);
+        const long long t = i / D, l = t % n_pad, r = t / n_pad;
+        const float* xr = x + r * n;
+        float acc = b[c];
+#pragma unroll
+        for (int k = 0; k < 7; ++k) {
+            const long long li = l + k - 3;
+            const float xv = (li >= 0 && li < n) ? xr[li] : 0.f;
+            acc = fmaf(w[k * D + c], xv, acc);
+        }
+        y[i] = acc;
+    }
+}
+
+// y[r][l] = tanh(b + sum_t sum_c w[t][c] x[r][l + t - 3][c]): a workgroup owns 64 outputs of one row; each wave turns input rows into
+// their seven partial dots (lanes stride the channels, a fixed butterfly sums them), then 64 threads gather seven partials each.
+constexpr int DAC_OUT_TL = 64;
+__global__ __launch_bounds__(256) void k_dac_conv_out(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ b,
+                                                      float* __restrict__ y, long long L, int C) {
+    __shared__ float part[DAC_OUT_TL + 6][8];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long long r = blockIdx.y, l0 = (long long)blockIdx.x * DAC_OUT_TL;
+    for (int j = wave; j < DAC_OUT_TL + 6; j += 4) {
+        const long long li = l0 - 3 + j;
+        float acc[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        if (li >= 0 && li < L) {                       // wave-uniform
+            const float* xr = x + ((size_t)r * L + li) * C;
+            for (int c = lane; c < C; c += 64) {
+                const float xv = xr[c];
+#pragma unroll
+                for (int t = 0; t < 7; ++t) acc[t] = fmaf(w[t * C + c], xv, acc[t]);
+            }
+#pragma unroll
+            for (int t = 0; t < 7; ++t)
+#pragma unroll
+                for (int o = 32; o >= 1; o >>= 1) acc[t] += __shfl_xor(acc[t], o);
+        }
+        if (lane == 0) {
+#pragma unroll
+            for (int t = 0; t < 7; ++t) part[j][t] = acc[t];
+        }
+    }
+    __syncthreads();
+    const int o = threadIdx.x;
+    if (o < DAC_OUT_TL && l0 + o < L) {
+        float v = b[0];
+#pragma unroll
+        for (int t = 0; t < 7; ++t) v += part[o + t][t];
+        y[(size_t)r * L + l0 + o] = tanhf(v);
+    }
+}
+
+// The residual quantiser (DAC-P8).  Frame g = row * F + f of the channels-last input; a workgroup owns TF frames, 32 lanes each: lane
+// `sub` of a frame holds channels sub, sub + 32, ... of the frame's residual and sum in LDS (only that lane touches them), the stage's
+// pre-normalised codebook is staged in LDS for the search.  Ties go to the lowest index: a lane walks its codes in ascending order and
+// keeps the first maximum, the butterfly prefers the lower index on equal similarity.
+struct VqP {
+    const float* ze; float* z; int* codes; float* rdump;
+    const float* in_w;      // [ncb][latent][cd]
+    const float* in_b;      // [ncb][cd]
+    const float* cbn;       // [ncb][K][cd], rows of unit norm
+    const float* cb;        // [ncb][K][cd] as stored
+    const float* out_w;     // [ncb][latent][cd]
+    const float* out_b;     // [ncb][latent]
+    int latent, cd, K, ncb, TF;
+    long long total, F;
+};
+
+template <int CD>
+__global__ __launch_bounds__(256) void k_dac_vq(const VqP p) {
+    extern __shared__ float lds[];
+    const int cd = CD ? CD : p.cd, latent = p.latent, K = p.K;
+    float* cbs = lds;                                   // [K][cd]
+    float* rs = cbs + (size_t)K * cd;                   // [TF][latent]
+    float* zs = rs + (size_t)p.TF * latent;             // [TF][latent]
+    float* es = zs + (size_t)p.TF * latent;             // [TF][cd] projections
+    float* ehs = es + p.TF * cd;                        // [TF][cd] normalised
+    int* code_s = (int*)(ehs + p.TF * cd);              // [TF]
+    const int tid = threadIdx.x, nthr = blockDim.x, fl = tid >> 5, sub = tid & 31;
+    const long long g = (long long)blockIdx.x * p.TF + fl;
+    const bool active = g < p.total;
+    float* myr = rs + (size_t)fl * latent;
+    float* myz = zs + (size_t)fl * latent;
+    for (int c = sub; c < latent; c += 32) {
+        myr[c] = active ? p.ze[(size_t)g * latent + c] : 0.f;
+        myz[c] = 0.f;
+    }
+    for (int i = 0; i < p.ncb; ++i) {
+        __syncthreads();                                // the previous stage's search has left cbs / ehs / code_s
+        const float* src = p.cbn + (size_t)i * K * cd;
+        for (int t = tid; t < K * cd; t += nthr) cbs[t] = src[t];
+        if (p.rdump && active) {
+            float* rd = p.rdump + ((size_t)i * p.total + g) * latent;
+            for (int c = sub; c < latent; c += 32) rd[c] = myr[c];
+        }
+        // in_proj: e[j] = b[j] + sum_c W[c][j] r[c], eight outputs a pass
+        for (int j0 = 0; j0 < cd; j0 += 8) {
+            float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+            for (int c = sub; c < latent; c += 32) {
+                const float rv = myr[c];
+                const float* wp = p.in_w + ((size_t)i * latent + c) * cd + j0;
+                if (CD == 8) {                           // (rows of eight floats: 32-byte aligned)
+                    const float4 w0 = *(const float4*)wp, w1 = *(const float4*)(wp + 4);
+                    acc[0] = fmaf(w0.x, rv, acc[0]); acc[1] = fmaf(w0.y, rv, acc[1]); acc[2] = fmaf(w0.z, rv, acc[2]); acc[3] = fmaf(w0.w, rv, acc[3]);
+                    acc[4] = fmaf(w1.x, rv, acc[4]); acc[5] = fmaf(w1.y, rv, acc[5]); acc[6] = fmaf(w1.z, rv, acc[6]); acc[7] = fmaf(w1.w, rv, acc[7]);
+                } else {
+#pragma unroll
+                    for (int jj = 0; jj < 8; ++jj)
+                        if (j0 + jj < cd) acc[jj] = fmaf(wp[jj], rv, acc[jj]);
+                }
+            }
+#pragma unroll
+            for (int jj = 0; jj < 8; ++jj) {
+#pragma unroll
+                for (int o = 16; o >= 1; o >>= 1) acc[jj] += __shfl_xor(acc[jj], o);
+                if (sub == jj && j0 + jj < cd) es[fl * cd + j0 + jj] = acc[jj] + p.in_b[i * cd + j0 + jj];
+            }
+        }
+        __syncthreads();
+        float n2 = 0.f;
+        for (int j = 0; j < cd; ++j) { const float e = es[fl * cd + j]; n2 = fmaf(e, e, n2); }
+        const float inv = 1.0f / fmaxf(sqrtf(n2), 1e-12f);
+        for (int j = sub; j < cd; j += 32) ehs[fl * cd + j] = es[fl * cd + j] * inv;
+        __syncthreads();
+        float best = -INFINITY;
+        int bk = 0x7fffffff;
+        if (CD == 8) {
+            const float4 e0 = *(const float4*)(ehs + fl * 8), e1 = *(const float4*)(ehs + fl * 8 + 4);
+            for (int k = sub; k < K; k += 32) {
+                const float4 c0 = *(const float4*)(cbs + k * 8), c1 = *(const float4*)(cbs + k * 8 + 4);
+                float s = e0.x * c0.x;
+                s = fmaf(e0.y, c0.y, s); s = fmaf(e0.z, c0.z, s); s = fmaf(e0.w, c0.w, s);
+                s = fmaf(e1.x, c1.x, s); s = fmaf(e1.y, c1.y, s); s = fmaf(e1.z, c1.z, s); s = fmaf(e1.w, c1.w, s);
+                if (s > best) { best = s; bk = k; }
+            }
+        } else {
+            for (int k = sub; k < K; k += 32) {
+                float s = 0.f;
+                for (int j = 0; j < cd; ++j) s = fmaf(ehs[fl * cd + j], cbs[k * cd + j], s);
+                if (s > best) { best = s; bk = k; }
+            }
+        }
+#pragma unroll
+        for (int o = 16; o >= 1; o >>= 1) {
+            const float ob = __shfl_xor(best, o);
+            const int ok = __shfl_xor(bk, o);
+            if (ob > best || (ob == best && ok < bk)) { best = ob; bk = ok; }
+        }
+        if (sub == 0) code_s[fl] = (bk >= 0 && bk < K) ? bk : 0;       // (no finite similarity: code 0)
+        __syncthreads();
+        const int code = code_s[fl];
+        if (sub == 0 && active) {
+            const long long row = g / p.F, f = g % p.F;
+            p.codes[((size_t)row * p.ncb + i) * p.F + f] = code;
+        }
+        // out_proj of the stored codebook row, then z += q, r -= q
+        const float* crow = p.cb + ((size_t)i * K + code) * cd;
+        for (int c = sub; c < latent; c += 32) {
+            const float* wp = p.out_w + ((size_t)i * latent + c) * cd;
+            float q = p.out_b[(size_t)i * latent + c];
+            if (CD == 8) {
+                const float4 w0 = *(const float4*)wp, w1 = *(const float4*)(wp + 4), c0 = *(const float4*)crow, c1 = *(const float4*)(crow + 4);
+                q = fmaf(w0.x, c0.x, q); q = fmaf(w0.y, c0.y, q); q = fmaf(w0.z, c0.z, q); q = fmaf(w0.w, c0.w, q);
+                q = fmaf(w1.x, c1.x, q); q = fmaf(w1.y, c1.y, q); q = fmaf(w1.z, c1.z, q); q = fmaf(w1.w, c1.w, q);
+            } else {
+                for (int j = 0; j < cd; ++j) q = fmaf(wp[j], crow[j], q);
+            }
+            myz[c] += q;
+            myr[c] -= q;
+        }
+    }
+    if (active)
+        for (int c = sub; c < latent; c += 32) p.z[(size_t)g * latent + c] = myz[c];
+}
+
+size_t vq_lds_bytes(int K, int cd, int latent, int TF) {
+    return ((size_t)K * cd + 2 * (size_t)TF * latent + 2 * (size_t)TF * cd) * sizeof(float) + (size_t)TF * sizeof(int);
+}
+
+// ------------------------------------------------------------------------------------------------------------------ the handle
+struct Conv {                       // one convolution served by the contraction launcher
+    int Cin = 0, Cout = 0, K = 1, stride = 1, dil = 1, pad = 0;
+    const void* w2 = nullptr;       // two fp16 terms (Cin % 16 == 0)
+    float w_scale = 1.f;
+    const float* wf = nullptr;      // fp32 pack otherwise
+    const float* bias = nullptr;
+    size_t o_pack = 0, o_bias = 0, o_w2 = 0;   // offsets while the images are built
+    bool h2 = false;
+};
+struct Snake { const float* alpha = nullptr; const float* inva = nullptr; size_t o = 0; int C = 0; };
+struct ResUnit { Snake s1, s2; Conv c7, c1; };
+struct EncBlock { ResUnit ru[3]; Snake s; Conv down; };
+struct DecBlock { Snake s; Conv up; int k = 0, stride = 0, pad = 0, c_out = 0; ResUnit ru[3]; };
+struct StageRec { int kind, index; const float* p; int64_t count; };
+
+struct Dac {
+    egr_dac_config cfg;
+    int device = 0;
+    int latent = 0, TF = 8;
+    bool keep_vq_inputs = false;     // egr_dac_set_stages: the quantiser also writes the residual entering each stage
+    // encoder
+    const float* in_w = nullptr; const float* in_b = nullptr; size_t o_in_w = 0, o_in_b = 0;
+    std::vector<EncBlock> enc;
+    Snake enc_s; Conv enc_out;
+    // quantiser
+    VqP vq{};
+    size_t o_vq[6] = {0, 0, 0, 0, 0, 0};
+    // decoder
+    Conv dec_in;
+    std::vector<DecBlock> dec;
+    Snake dec_s;
+    const float* out_w = nullptr; const float* out_b = nullptr; size_t o_out_w = 0, o_out_b = 0; int c_last = 0;
+    float* d_misc = nullptr;        // biases, snake tables, thin convolutions, quantiser
+    float* d_f32 = nullptr;         // fp32 packs of the convolutions the split kernels do not take
+    void* d_w2 = nullptr;           // fp16 term packs
+    void* ws = nullptr;
+    size_t ws_bytes = 0;
+    std::vector<StageRec> stages;
+};
+
+int64_t conv_len(int64_t L, int s) {                 // Conv1d(k = 2 s, stride s, padding ceil(s / 2))
+    const int64_t num = L + 2 * ((s + 1) / 2) - 2 * s;
+    return num < 0 ? 0 : num / s + 1;
+}
+int64_t convtr_len(int64_t L, int s) { return (L - 1) * s - 2 * ((s + 1) / 2) + 2 * s; }
+
+int lengths(const egr_dac_config& c, int64_t n, int64_t* n_pad, int64_t* frames, int64_t* n_dec) {
+    int64_t hop = 1;
+    for (int i = 0; i < c.n_enc; ++i) hop *= c.enc_rates[i];
+    const int64_t np = (n + hop - 1) / hop * hop;
+    int64_t L = np;
+    for (int i = 0; i < c.n_enc; ++i) L = conv_len(L, c.enc_rates[i]);
+    const int64_t F = L;
+    for (int i = 0; i < c.n_dec; ++i) L = L >= 1 ? convtr_len(L, c.dec_rates[i]) : 0;
+    if (n_pad) *n_pad = np;
+    if (frames) *frames = F;
+    if (n_dec) *n_dec = L;
+    return EGR_OK;
+}
+int64_t decoded_len(const egr_dac_config& c, int64_t frames) {
+    int64_t L = frames;
+    for (int i = 0; i < c.n_dec; ++i) L = L >= 1 ? convtr_len(L, c.dec_rates[i]) : 0;
+    return L;
+}
+
+int check_config(const egr_dac_config* c, const char* who) {
+    EGR_CHECK(c && c->struct_bytes == (int)sizeof(egr_dac_config), EGR_ERR_ARG, "%s: bad config (struct_bytes)", who);
+    EGR_CHECK(c->n_enc >= 1 && c->n_enc <= EGR_DAC_MAX_RATES && c->n_dec >= 1 && c->n_dec <= EGR_DAC_MAX_RATES, EGR_ERR_UNSUPPORTED,
+              "%s: 1 .. %d rates per side (got %d / %d)", who, EGR_DAC_MAX_RATES, c->n_enc, c->n_dec);
+    for (int i = 0; i < c->n_enc; ++i)
+        EGR_CHECK(c->enc_rates[i] >= 1 && c->enc_rates[i] <= DAC_MAX_RATE, EGR_ERR_UNSUPPORTED, "%s: encoder rate %d outside 1 .. %d", who, c->enc_rates[i], DAC_MAX_RATE);
+    for (int i = 0; i < c->n_dec; ++i)
+        EGR_CHECK(c->dec_rates[i] >= 1 && c->dec_rates[i] <= DAC_MAX_RATE, EGR_ERR_UNSUPPORTED, "%s: decoder rate %d outside 1 .. %d", who, c->dec_rates[i], DAC_MAX_RATE);
+    EGR_CHECK(c->encoder_dim >= 1 && c->decoder_dim >= 1 && c->latent_dim >= 1 && c->n_codebooks >= 1 && c->codebook_size >= 1 && c->codebook_dim >= 1,
+              EGR_ERR_ARG, "%s: non-positive dimension", who);
+    EGR_CHECK(((long long)c->encoder_dim << c->n_enc) <= DAC_MAX_WIDTH && c->decoder_dim <= DAC_MAX_WIDTH && c->latent_dim <= DAC_MAX_WIDTH, EGR_ERR_UNSUPPORTED,
+              "%s: widths up to %d (encoder %lld, decoder %d, latent %d)", who, DAC_MAX_WIDTH, (long long)c->encoder_dim << c->n_enc, c->decoder_dim, c->latent_dim);
+    EGR_CHECK(c->decoder_dim % (1 << c->n_dec) == 0, EGR_ERR_UNSUPPORTED, "%s: decoder_dim %d does not halve %d times", who, c->decoder_dim, c->n_dec);
+    EGR_CHECK(c->n_codebooks <= DAC_MAX_CODEBOOKS, EGR_ERR_UNSUPPORTED, "%s: n_codebooks %d above %d", who, c->n_codebooks, DAC_MAX_CODEBOOKS);
+    EGR_CHECK((long long)c->codebook_size * c->codebook_dim <= DAC_MAX_CB_FLOATS && c->codebook_dim <= DAC_MAX_CB_DIM, EGR_ERR_UNSUPPORTED,
+              "%s: codebook_size * codebook_dim = %lld above %d, or codebook_dim %d above %d (a codebook must fit in LDS)", who,
+              (long long)c->codebook_size * c->codebook_dim, DAC_MAX_CB_FLOATS, c->codebook_dim, DAC_MAX_CB_DIM);
+    return EGR_OK;
+}
+
+// ---- building the device images from the packed blob
+struct Builder {
+    const float* src; int64_t n, pos = 0;
+    std::vector<float> misc, f32pack, stage;           // stage: fp32 packs that become fp16 term packs
+    size_t w2_bytes = 0;
+    std::vector<Conv*> convs;
+    bool ok = true;
+    const float* take(int64_t k) {
+        if (pos + k > n) { ok = false; return nullptr; }
+        const float* p = src + pos; pos += k; return p;
+    }
+    size_t put(const float* p, int64_t k) {            // into misc, 16-byte aligned
+        while (misc.size() % 4) misc.push_back(0.f);
+        const size_t o = misc.size();
+        misc.insert(misc.end(), p, p + k);
+        return o;
+    }
+    void snake(Snake& s, int C) {
+        const float* a = take(C);
+        if (!a) return;
+        s.C = C;
+        s.o = put(a, C);
+        std::vector<float> inv(C);
+        for (int c = 0; c < C; ++c) inv[c] = (float)(1.0 / ((double)a[c] + 1e-9));
+        put(inv.data(), C);                             // 1 / (alpha + 1e-9), at the next 16-byte boundary behind alpha
+    }
+    // torch Conv1d weight [Co][Ci][k] + bias -> slab-major [ceil(K/16)][Co][16], K ordered (tap, ci)
+    void conv(Conv& L, int Ci, int Co, int k, int stride, int dil, int pad) {
+        const float* w = take((int64_t)Co * Ci * k);
+        const float* b = take(Co);
+        if (!w || !b) return;
+        L.Cin = Ci; L.Cout = Co; L.K = k; L.stride = stride; L.dil = dil; L.pad = pad;
+        L.o_bias = put(b, Co);
+        pack(L, w, Ci, Co, k, false);
+    }
+    // torch ConvTranspose1d weight [Ci][Co][k] -> GEMM onto columns n = tap * Co + co
+    void convtr(Conv& L, int Ci, int Co, int k) {
+        const float* w = take((int64_t)Ci * Co * k);
+        const float* b = take(Co);
+        if (!w || !b) return;
+        L.Cin = Ci; L.Cout = k * Co; L.K = 1;
+        L.o_bias = put(b, Co);                          // [Co]: added by the gather, not by the GEMM
+        pack(L, w, Ci, Co, k, true);
+    }
+    void pack(Conv& L, const float* w, int Ci, int Co, int k, bool tr) {
+        const int Kd = tr ? Ci : k * Ci, N = tr ? k * Co : Co;
+        const size_t slabs = (Kd + 15) / 16, numel = slabs * N * 16;
+        L.h2 = Ci % 16 == 0;
+        std::vector<float>& dst = L.h2 ? stage : f32pack;
+        L.o_pack = dst.size();
+        dst.resize(dst.size() + numel, 0.f);
+        float* d = dst.data() + L.o_pack;
+        float wmax = 0.f;
+        if (tr) {
+            for (int ci = 0; ci < Ci; ++ci)
+                for (int co = 0; co < Co; ++co)
+                    for (int t = 0; t < k; ++t) {
+                        const float v = w[((size_t)ci * Co + co) * k + t];
+                        d[((size_t)(ci / 16) * N + (size_t)t * Co + co) * 16 + ci % 16] = v;
+                        wmax = std::max(wmax, std::fabs(v));
+                    }
+        } else {
+            for (int co = 0; co < Co; ++co)
+                for (int ci = 0; ci < Ci; ++ci)
+                    for (int t = 0; t < k; ++t) {
+                        const float v = w[((size_t)co * Ci + ci) * k + t];
+                        const int kk = t * Ci + ci;
+                        d[((size_t)(kk / 16) * N + co) * 16 + kk % 16] = v;
+                        wmax = std::max(wmax, std::fabs(v));
+                    }
+        }
+        if (L.h2) {
+            // power of two that brings the pack's largest magnitude into (2^12, 2^13] (the scale the FlashSR handle gives its weights)
+            L.w_scale = 1.f;
+            if (wmax > 0.f && std::isfinite(wmax)) {
+                int ex = 0;
+                const float fr = frexpf(wmax, &ex);
+                if (fr == 0.5f) --ex;
+                L.w_scale = ldexpf(1.f, std::max(-60, std::min(60, 13 - ex)));
+            }
+            L.o_w2 = w2_bytes;
+            w2_bytes += slabs * 2 * N * 16 * 2;
+        }
+        convs.push_back(&L);
+    }
+};
+
+void res_unit(Builder& B, ResUnit& u, int C, int d) {
+    B.snake(u.s1, C);
+    B.conv(u.c7, C, C, 7, 1, d, 3 * d);
+    B.snake(u.s2, C);
+    B.conv(u.c1, C, C, 1, 1, 1, 0);
+}
+
+void destroy(Dac* m) {
+    int prev = 0;
+    (void)hipGetDevice(&prev);
+    (void)hipSetDevice(m->device);
+    if (m->ws) {
+        (void)hipFreeAsync(m->ws, nullptr);
+        (void)hipDeviceSynchronize();
+    }
+    if (m->d_misc) (void)hipFree(m->d_misc);
+    if (m->d_f32) (void)hipFree(m->d_f32);
+    if (m->d_w2) (void)hipFree(m->d_w2);
+    (void)hipSetDevice(prev);
+    delete m;
+}
+
+int upload(Dac* m, Builder& B) {
+    float* d_stage = nullptr;
+    auto fail = [&](const char* what) {
+        set_error("egr_dac_create: %s failed on device %d", what, m->device);
+        if (d_stage) (void)hipFree(d_stage);
+        return EGR_ERR_HIP;
+    };
+    if (hipMalloc((void**)&m->d_misc, std::max<size_t>(16, B.misc.size() * 4)) != hipSuccess) return fail("hipMalloc(tables)");
+    if (hipMemcpy(m->d_misc, B.misc.data(), B.misc.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return fail("upload(tables)");
+    if (!B.f32pack.empty()) {
+        if (hipMalloc((void**)&m->d_f32, B.f32pack.size() * 4) != hipSuccess) return fail("hipMalloc(fp32 packs)");
+        if (hipMemcpy(m->d_f32, B.f32pack.data(), B.f32pack.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return fail("upload(fp32 packs)");
+    }
+    if (!B.stage.empty()) {
+        if (hipMalloc((void**)&d_stage, B.stage.size() * 4) != hipSuccess) return fail("hipMalloc(staging)");
+        if (hipMemcpy(d_stage, B.stage.data(), B.stage.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return fail("upload(staging)");
+        if (hipMalloc(&m->d_w2, B.w2_bytes) != hipSuccess) return fail("hipMalloc(fp16 terms)");
+    }
+    for (Conv* L : B.convs) {
+        if (L->h2) {
+            const int Kd = L->K * L->Cin;
+            void* w2 = (char*)m->d_w2 + L->o_w2;
+            const int rc = egr_split2h_pack(d_stage + L->o_pack, w2, (Kd + 15) / 16, L->Cout, L->w_scale, nullptr);
+            if (rc) { if (d_stage) (void)hipFree(d_stage); return rc; }
+            L->w2 = w2;
+        } else L->wf = m->d_f32 + L->o_pack;
+        L->bias = m->d_misc + L->o_bias;
+    }
+    if (hipDeviceSynchronize() != hipSuccess) return fail("weight repack");
+    if (d_stage) (void)hipFree(d_stage);
+    return EGR_OK;
+}
+
+// ---- one call: the walk lays the workspace out and (launch) enqueues the kernels
+struct Walk {
+    Dac& m; hipStream_t st; bool launch; int rows;
+    char* base = nullptr; size_t off = 0;
+    unsigned* amax_pool = nullptr; int amax_used = 0;
+    int rc = EGR_OK;
+    float* take(size_t floats) {
+        off = (off + 255) & ~(size_t)255;
+        float* p = launch ? (float*)(base + off) : nullptr;
+        off += floats * sizeof(float);
+        return p;
+    }
+    unsigned* amax_slot() {
+        if (amax_used >= DAC_AMAX_SLOTS) { if (!rc) { set_error("DAC: row maxima pool exhausted"); rc = EGR_ERR_UNSUPPORTED; } return amax_pool; }
+        unsigned* p = amax_pool + (size_t)amax_used * rows * EGR_ROW_AMAX_STRIDE;
+        ++amax_used;
+        return p;
+    }
+    void note(int kind, int index, const float* p, int64_t count) { if (launch) m.stages.push_back({kind, index, p, count}); }
+    bool go() const { return launch && rc == EGR_OK; }
+    // y = snake(x) (y may be x); returns the row maxima of y
+    const unsigned* snake(const Snake& s, const float* x, float* y, int64_t L) {
+        unsigned* slot = amax_slot();
+        if (!go()) return slot;
+        const long long per_row = (long long)L * s.C;
+        long long nb = (per_row / ((s.C & 3) ? 1 : 4) + 255) / 256;
+        nb = std::max(1LL, std::min(nb, std::max(1LL, 2048LL / rows)));
+        hipLaunchKernelGGL(k_dac_snake, dim3((unsigned)nb, (unsigned)rows), dim3(256), 0, st, x, s.alpha, s.inva, y, per_row, s.C, slot);
+        return slot;
+    }
+    void conv(const Conv& c, const float* x, const unsigned* x_amax, float* y, const float* res, const float* bias, int64_t Lin, int64_t Lout) {
+        if (!go()) return;
+        ConvCall cc;
+        cc.x = x; cc.y = y; cc.bias = bias; cc.res = res;
+        cc.B = rows; cc.W = (int)Lin; cc.Cin = c.Cin; cc.OW = cc.OWF = (int)Lout; cc.Cout = c.Cout; cc.KW = c.K;
+        cc.stride = c.stride; cc.dil = c.dil; cc.pad_l = c.pad;
+        if (c.h2) { cc.w3 = c.w2; cc.sch = 1; cc.w_scale = c.w_scale; cc.row_amax = (const float*)x_amax; cc.batch_rows = rows; }
+        else cc.w = c.wf;
+        rc = conv_call(cc, st);
+    }
+};
+
+// scratch rotation: a buffer of S that is none of the given ones
+float* other(float* const S[3], const float* a, const float* b = nullptr) {
+    for (int i = 0; i < 3; ++i)
+        if (S[i] != a && S[i] != b) return S[i];
+    return S[0];
+}
+
+// x -> snake -> k7 dilated -> snake -> k1 + x, into `out` (or a scratch buffer when out is null); returns where the result is
+float* run_res_unit(Walk& w, const ResUnit& u, float* cur, float* const S[3], float* out, int64_t L) {
+    float* a = other(S, cur), *b = other(S, cur, a);
+    const unsigned* ra = w.snake(u.s1, cur, a, L);
+    w.conv(u.c7, a, ra, b, nullptr, u.c7.bias, L, L);
+    const unsigned* rb = w.snake(u.s2, b, b, L);
+    float* y = out ? out : a;
+    w.conv(u.c1, b, rb, y, cur, u.c1.bias, L, L);
+    return y;
+}
+
+size_t max_enc_tensor(const Dac& m, int rows, int64_t n_pad) {
+    size_t mx = 0;
+    int64_t L = n_pad;
+    int C = m.cfg.encoder_dim;
+    for (int i = 0; i < m.cfg.n_enc; ++i) {
+        mx = std::max(mx, (size_t)rows * L * C);
+        L = conv_len(L, m.cfg.enc_rates[i]);
+        C *= 2;
+    }
+    return std::max(mx, (size_t)rows * L * C);
+}
+
+int launch_vq(Walk& w, const float* ze_cl, float* z_cl, int* codes, int64_t F) {
+    Dac& m = w.m;
+    const long long total = (long long)w.rows * F;
+    float* rdump = m.keep_vq_inputs ? w.take((size_t)m.cfg.n_codebooks * total * m.latent) : nullptr;
+    if (!w.go()) return w.rc;
+    VqP p = m.vq;
+    p.ze = ze_cl; p.z = z_cl; p.codes = codes; p.rdump = rdump; p.total = total; p.F = F; p.TF = m.TF;
+    const size_t lds = vq_lds_bytes(p.K, p.cd, p.latent, p.TF);
+    const unsigned grid = (unsigned)((total + p.TF - 1) / p.TF);
+    if (p.cd == 8) hipLaunchKernelGGL(k_dac_vq<8>, dim3(grid), dim3(p.TF * 32), lds, w.st, p);
+    else hipLaunchKernelGGL(k_dac_vq<0>, dim3(grid), dim3(p.TF * 32), lds, w.st, p);
+    for (int i = 0; rdump && i < m.cfg.n_codebooks; ++i) w.note(EGR_DAC_STAGE_VQ_IN, i, rdump + (size_t)i * total * m.latent, total * m.latent);
+    return EGR_OK;
+}
+
+int walk_encode(Walk& w, const float* x, int64_t n, float* z, int* codes) {
+    Dac& m = w.m;
+    const egr_dac_config& c = m.cfg;
+    int64_t n_pad, F;
+    lengths(c, n, &n_pad, &F, nullptr);
+    const int rows = w.rows;
+    w.amax_pool = (unsigned*)w.take((size_t)DAC_AMAX_SLOTS * rows * EGR_ROW_AMAX_STRIDE);
+    if (w.go()) EGR_HIP(hipMemsetAsync(w.amax_pool, 0, (size_t)DAC_AMAX_SLOTS * rows * EGR_ROW_AMAX_STRIDE * 4, w.st));
+    const size_t mx = max_enc_tensor(m, rows, n_pad);
+    float* S[3] = {w.take(mx), w.take(mx), w.take(mx)};
+    int C = c.encoder_dim;
+    int64_t L = n_pad;
+    float* cur = w.take((size_t)rows * L * C);
+    if (w.go()) {
+        const long long total = (long long)rows * L * C;
+        const unsigned nb = (unsigned)std::min<long long>((total + 255) / 256, 8192);
+        hipLaunchKernelGGL(k_dac_conv_in, dim3(nb), dim3(256), 0, w.st, x, m.in_w, m.in_b, cur, (long long)n, (long long)n_pad, C, total);
+    }
+    w.note(EGR_DAC_STAGE_ENC, 0, cur, (int64_t)rows * L * C);
+    for (int i = 0; i < c.n_enc; ++i) {
+        const EncBlock& b = m.enc[i];
+        for (int u = 0; u < 3; ++u) cur = run_res_unit(w, b.ru[u], cur, S, nullptr, L);
+        float* a = other(S, cur);
+        const unsigned* ra = w.snake(b.s, cur, a, L);
+        const int64_t Lo = conv_len(L, c.enc_rates[i]);
+        float* out = w.take((size_t)rows * Lo * C * 2);
+        w.conv(b.down, a, ra, out, nullptr, b.down.bias, L, Lo);
+        cur = out; L = Lo; C *= 2;
+        w.note(EGR_DAC_STAGE_ENC, i + 1, cur, (int64_t)rows * L * C);
+    }
+    float* a = other(S, cur);
+    const unsigned* ra = w.snake(m.enc_s, cur, a, L);
+    float* ze = w.take((size_t)rows * L * m.latent);
+    w.conv(m.enc_out, a, ra, ze, nullptr, m.enc_out.bias, L, L);
+    w.note(EGR_DAC_STAGE_ENC, c.n_enc + 1, ze, (int64_t)rows * L * m.latent);
+    float* z_cl = w.take((size_t)rows * L * m.latent);
+    { const int rc = launch_vq(w, ze, z_cl, codes, L); if (rc) return rc; }
+    if (w.go()) { const int rc = egr_transpose_batched(z_cl, z, rows, (int)L, m.latent, w.st); if (rc) return rc; }
+    if (w.go()) EGR_HIP(hipGetLastError());
+    return w.rc;
+}
+
+int walk_quantize(Walk& w, const float* ze, int64_t F, float* z, int* codes) {
+    Dac& m = w.m;
+    float* ze_cl = w.take((size_t)w.rows * F * m.latent);
+    float* z_cl = w.take((size_t)w.rows * F * m.latent);
+    if (w.go()) { const int rc = egr_transpose_batched(ze, ze_cl, w.rows, m.latent, (int)F, w.st); if (rc) return rc; }
+    { const int rc = launch_vq(w, ze_cl, z_cl, codes, F); if (rc) return rc; }
+    if (w.go()) { const int rc = egr_transpose_batched(z_cl, z, w.rows, (int)F, m.latent, w.st); if (rc) return rc; }
+    if (w.go()) EGR_HIP(hipGetLastError());
+    return w.rc;
+}
+
+int walk_decode(Walk& w, const float* z, int64_t F, float* y) {
+    Dac& m = w.m;
+    const egr_dac_config& c = m.cfg;
+    const int rows = w.rows;
+    w.amax_pool = (unsigned*)w.take((size_t)DAC_AMAX_SLOTS * rows * EGR_ROW_AMAX_STRIDE);
+    if (w.go()) EGR_HIP(hipMemsetAsync(w.amax_pool, 0, (size_t)DAC_AMAX_SLOTS * rows * EGR_ROW_AMAX_STRIDE * 4, w.st));
+    size_t mx = (size_t)rows * F * std::max(m.latent, c.decoder_dim), mxY = 0;
+    {
+        int64_t L = F;
+        int C = c.decoder_dim;
+        for (int i = 0; i < c.n_dec; ++i) {
+            const int s = c.dec_rates[i];
+            mx = std::max(mx, (size_t)rows * L * C);
+            mxY = std::max(mxY, (size_t)rows * L * 2 * s * (C / 2));
+            L = convtr_len(L, s);
+            C /= 2;
+            mx = std::max(mx, (size_t)rows * L * C);
+        }
+    }
+    float* S[3] = {w.take(mx), w.take(mx), w.take(mx)};
+    float* Y = w.take(mxY);
+    int64_t L = F;
+    float* z_cl = S[0];
+    const unsigned* rz = w.amax_slot();
+    if (w.go()) { const int rc = egr_transpose_batched(z, z_cl, rows, m.latent, (int)F, w.st); if (rc) return rc; }
+    if (w.go()) { const int rc = egr_absmax_rows(z_cl, rows, F * m.latent, 1, 0, (float*)rz, w.st); if (rc) return rc; }
+    int C = c.decoder_dim;
+    float* cur = w.take((size_t)rows * L * C);
+    w.conv(m.dec_in, z_cl, rz, cur, nullptr, m.dec_in.bias, L, L);
+    w.note(EGR_DAC_STAGE_DEC, 0, cur, (int64_t)rows * L * C);
+    for (int i = 0; i < c.n_dec; ++i) {
+        const DecBlock& b = m.dec[i];
+        float* a = other(S, cur);
+        const unsigned* ra = w.snake(b.s, cur, a, L);
+        // ConvTranspose1d: a GEMM onto [tap][co] columns of every input sample, gathered by egr_col2im_convtr1d
+        if (w.go()) {
+            ConvCall cc;
+            cc.x = a; cc.y = Y; cc.B = (int)(rows * L); cc.Cin = b.up.Cin; cc.Cout = b.up.Cout;
+            if (b.up.h2) { cc.w3 = b.up.w2; cc.sch = 1; cc.w_scale = b.up.w_scale; cc.row_amax = (const float*)ra; cc.batch_rows = rows; }
+            else cc.w = b.up.wf;
+            w.rc = conv_call(cc, w.st);
+        }
+        const int64_t Lo = convtr_len(L, b.stride);
+        float* up = other(S, a);
+        if (w.go()) w.rc = egr_col2im_convtr1d(Y, b.up.bias, nullptr, up, rows, (int)L, (int)Lo, b.c_out, b.k, b.stride, b.pad, w.st);
+        cur = up; L = Lo; C = b.c_out;
+        float* out = w.take((size_t)rows * L * C);
+        for (int u = 0; u < 3; ++u) cur = run_res_unit(w, b.ru[u], cur, S, u == 2 ? out : nullptr, L);
+        w.note(EGR_DAC_STAGE_DEC, i + 1, cur, (int64_t)rows * L * C);
+    }
+    float* a = other(S, cur);
+    w.snake(m.dec_s, cur, a, L);
+    if (w.go()) {
+        hipLaunchKernelGGL(k_dac_conv_out, dim3((unsigned)((L + DAC_OUT_TL - 1) / DAC_OUT_TL), (unsigned)rows), dim3(256), 0, w.st, a, m.out_w, m.out_b, y,
+                           (long long)L, C);
+        EGR_HIP(hipGetLastError());
+    }
+    return w.rc;
+}
+
+int begin_call(Dac* m, const char* who, int rows, int64_t len) {
+    EGR_CHECK(m && rows >= 1 && rows <= 65535 && len >= 1, EGR_ERR_ARG, "%s: bad argument", who);
+    int cur = -1;
+    EGR_HIP(hipGetDevice(&cur));
+    EGR_CHECK(cur == m->device, EGR_ERR_ARG, "%s: handle belongs to device %d, current device is %d", who, m->device, cur);
+    return EGR_OK;
+}
+
+int ensure_ws(Dac* m, size_t need, hipStream_t st) {
+    if (need > m->ws_bytes) {
+        if (m->ws) EGR_HIP(hipFreeAsync(m->ws, st));
+        m->ws = nullptr;
+        m->ws_bytes = 0;
+        EGR_HIP(hipMallocAsync(&m->ws, need, st));
+        m->ws_bytes = need;
+    }
+    m->stages.clear();
+    return EGR_OK;
+}
+
+}  // namespace
+}  // namespace egr
+
+using namespace egr;
+
+extern "C" int egr_dac_lengths(const egr_dac_config* cfg, int64_t n, int64_t* n_padded, int64_t* frames, int64_t* n_decoded) {
+    { const int rc = check_config(cfg, "egr_dac_lengths"); if (rc) return rc; }
+    EGR_CHECK(n >= 1, EGR_ERR_ARG, "egr_dac_lengths: n < 1");
+    return lengths(*cfg, n, n_padded, frames, n_decoded);
+}
+
+extern "C" int egr_dac_create(void** handle, const egr_dac_config* cfg, const float* packed, int64_t n_floats, int device) {
+    EGR_CHECK(handle && packed, EGR_ERR_ARG, "egr_dac_create: null argument");
+    { const int rc = check_config(cfg, "egr_dac_create"); if (rc) return rc; }
+    const egr_dac_config& c = *cfg;
+    Dac* m = new Dac();
+    m->cfg = c;
+    m->device = device;
+    m->latent = c.latent_dim;
+    m->TF = vq_lds_bytes(c.codebook_size, c.codebook_dim, c.latent_dim, 8) <= (size_t)DAC_LDS_BUDGET ? 8 : 4;
+    if (vq_lds_bytes(c.codebook_size, c.codebook_dim, c.latent_dim, m->TF) > (size_t)DAC_LDS_BUDGET) {
+        set_error("egr_dac_create: the quantiser needs %zu bytes of LDS (limit %d)", vq_lds_bytes(c.codebook_size, c.codebook_dim, c.latent_dim, m->TF), DAC_LDS_BUDGET);
+        delete m;
+        return EGR_ERR_UNSUPPORTED;
+    }
+    Builder B{packed, n_floats};
+    const int dils[3] = {1, 3, 9};
+    // encoder
+    {
+        const int D = c.encoder_dim;
+        const float* w = B.take((int64_t)D * 7);
+        const float* b = B.take(D);
+        if (w && b) {
+            std::vector<float> wt((size_t)7 * D);
+            for (int co = 0; co < D; ++co)
+                for (int t = 0; t < 7; ++t) wt[(size_t)t * D + co] = w[(size_t)co * 7 + t];
+            m->o_in_w = B.put(wt.data(), 7 * D);
+            m->o_in_b = B.put(b, D);
+        }
+        m->enc.resize(c.n_enc);
+        int C = D;
+        for (int i = 0; i < c.n_enc && B.ok; ++i) {
+            const int s = c.enc_rates[i];
+            for (int u = 0; u < 3; ++u) res_unit(B, m->enc[i].ru[u], C, dils[u]);
+            B.snake(m->enc[i].s, C);
+            B.conv(m->enc[i].down, C, 2 * C, 2 * s, s, 1, (s + 1) / 2);
+            C *= 2;
+        }
+        B.snake(m->enc_s, C);
+        B.conv(m->enc_out, C, c.latent_dim, 3, 1, 1, 1);
+    }
+    // quantiser: in_proj transposed to [latent][cd], codebooks as stored and with unit rows (float64)
+    {
+        const int cd = c.codebook_dim, K = c.codebook_size, lat = c.latent_dim, n = c.n_codebooks;
+        std::vector<float> in_w((size_t)n * lat * cd), in_b((size_t)n * cd), cbn((size_t)n * K * cd), cb((size_t)n * K * cd), out_w((size_t)n * lat * cd),
+            out_b((size_t)n * lat);
+        for (int i = 0; i < n && B.ok; ++i) {
+            const float* iw = B.take((int64_t)cd * lat);
+            const float* ib = B.take(cd);
+            const float* cw = B.take((int64_t)K * cd);
+            const float* ow = B.take((int64_t)lat * cd);
+            const float* ob = B.take(lat);
+            if (!B.ok) break;
+            for (int j = 0; j < cd; ++j)
+                for (int ch = 0; ch < lat; ++ch) in_w[((size_t)i * lat + ch) * cd + j] = iw[(size_t)j * lat + ch];
+            std::copy(ib, ib + cd, in_b.begin() + (size_t)i * cd);
+            std::copy(cw, cw + (size_t)K * cd, cb.begin() + (size_t)i * K * cd);
+            for (int k = 0; k < K; ++k) {
+                double s = 0.0;
+                for (int j = 0; j < cd; ++j) s += (double)cw[(size_t)k * cd + j] * cw[(size_t)k * cd + j];
+                const double inv = 1.0 / std::max(std::sqrt(s), 1e-12);
+                for (int j = 0; j < cd; ++j) cbn[((size_t)i * K + k) * cd + j] = (float)(cw[(size_t)k * cd + j] * inv);
+            }
+            std::copy(ow, ow + (size_t)lat * cd, out_w.begin() + (size_t)i * lat * cd);
+            std::copy(ob, ob + lat, out_b.begin() + (size_t)i * lat);
+        }
+        m->o_vq[0] = B.put(in_w.data(), in_w.size()); m->o_vq[1] = B.put(in_b.data(), in_b.size()); m->o_vq[2] = B.put(cbn.data(), cbn.size());
+        m->o_vq[3] = B.put(cb.data(), cb.size()); m->o_vq[4] = B.put(out_w.data(), out_w.size()); m->o_vq[5] = B.put(out_b.data(), out_b.size());
+    }
+    // decoder
+    {
+        int C = c.decoder_dim;
+        B.conv(m->dec_in, c.latent_dim, C, 7, 1, 1, 3);
+        m->dec.resize(c.n_dec);
+        for (int i = 0; i < c.n_dec && B.ok; ++i) {
+            DecBlock& d = m->dec[i];
+            const int s = c.dec_rates[i];
+            d.k = 2 * s; d.stride = s; d.pad = (s + 1) / 2; d.c_out = C / 2;
+            B.snake(d.s, C);
+            B.convtr(d.up, C, C / 2, 2 * s);
+            C /= 2;
+            for (int u = 0; u < 3; ++u) res_unit(B, d.ru[u], C, dils[u]);
+        }
+        B.snake(m->dec_s, C);
+        m->c_last = C;
+        const float* w = B.take((int64_t)C * 7);
+        const float* b = B.take(1);
+        if (w && b) {
+            std::vector<float> wt((size_t)7 * C);
+            for (int ci = 0; ci < C; ++ci)
+                for (int t = 0; t < 7; ++t) wt[(size_t)t * C + ci] = w[(size_t)ci * 7 + t];
+            m->o_out_w = B.put(wt.data(), 7 * C);
+            m->o_out_b = B.put(b, 1);
+        }
+    }
+    if (!B.ok || B.pos != n_floats) {
+        set_error("egr_dac_create: the packed weights hold %lld floats, the config describes %s%lld", (long long)n_floats, B.ok ? "" : "more than ",
+                  (long long)B.pos);
+        delete m;
+        return EGR_ERR_ARG;
+    }
+    int prev = 0;
+    if (hipGetDevice(&prev) != hipSuccess || hipSetDevice(device) != hipSuccess) {
+        set_error("egr_dac_create: cannot select device %d", device);
+        delete m;
+        return EGR_ERR_HIP;
+    }
+    int rc = upload(m, B);
+    if (rc == EGR_OK) {
+        hipError_t e = hipFuncSetAttribute((const void*)k_dac_vq<8>, hipFuncAttributeMaxDynamicSharedMemorySize, DAC_LDS_MAX);
+        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_dac_vq<0>, hipFuncAttributeMaxDynamicSharedMemorySize, DAC_LDS_MAX);
+        if (e != hipSuccess) { set_error("egr_dac_create: hipFuncSetAttribute(MaxDynamicSharedMemorySize) -> %s", hipGetErrorString(e)); rc = EGR_ERR_HIP; }
+    }
+    (void)hipSetDevice(prev);
+    if (rc) { destroy(m); return rc; }
+    // bind the tables
+    const float* D = m->d_misc;
+    auto bind_snake = [&](Snake& s) { s.alpha = D + s.o; s.inva = D + ((s.o + s.C + 3) & ~(size_t)3); };
+    auto bind_ru = [&](ResUnit& u) { bind_snake(u.s1); bind_snake(u.s2); };
+    m->in_w = D + m->o_in_w; m->in_b = D + m->o_in_b;
+    for (auto& b : m->enc) { for (auto& u : b.ru) bind_ru(u); bind_snake(b.s); }
+    bind_snake(m->enc_s);
+    for (auto& b : m->dec) { for (auto& u : b.ru) bind_ru(u); bind_snake(b.s); }
+    bind_snake(m->dec_s);
+    m->out_w = D + m->o_out_w; m->out_b = D + m->o_out_b;
+    m->vq.in_w = D + m->o_vq[0]; m->vq.in_b = D + m->o_vq[1]; m->vq.cbn = D + m->o_vq[2]; m->vq.cb = D + m->o_vq[3];
+    m->vq.out_w = D + m->o_vq[4]; m->vq.out_b = D + m->o_vq[5];
+    m->vq.latent = c.latent_dim; m->vq.cd = c.codebook_dim; m->vq.K = c.codebook_size; m->vq.ncb = c.n_codebooks;
+    *handle = m;
+    return EGR_OK;
+}
+
+extern "C" int egr_dac_set_stages(void* handle, int enable) {
+    EGR_CHECK(handle, EGR_ERR_ARG, "egr_dac_set_stages: null handle");
+    ((Dac*)handle)->keep_vq_inputs = enable != 0;
+    return EGR_OK;
+}
+
+extern "C" int egr_dac_destroy(void* handle) {
+    if (handle) destroy((Dac*)handle);
+    return EGR_OK;
+}
+
+extern "C" size_t egr_dac_workspace_bytes(void* handle, int rows, int64_t n) {
+    Dac* m = (Dac*)handle;
+    if (!m || rows < 1 || n < 1) return 0;
+    int64_t F = 0;
+    lengths(m->cfg, n, nullptr, &F, nullptr);
+    if (F < 1) return 0;
+    Walk we{*m, nullptr, false, rows}, wd{*m, nullptr, false, rows};
+    walk_encode(we, nullptr, n, nullptr, nullptr);
+    walk_decode(wd, nullptr, F, nullptr);
+    return std::max(we.off, wd.off) + 256;
+}
+
+extern "C" int egr_dac_encode(void* handle, const float* x, int rows, int64_t n, float* z, int* codes, void* stream) {
+    Dac* m = (Dac*)handle;
+    { const int rc = begin_call(m, "egr_dac_encode", rows, n); if (rc) return rc; }
+    EGR_CHECK(x && z && codes, EGR_ERR_ARG, "egr_dac_encode: null argument");
+    int64_t n_pad, F;
+    lengths(m->cfg, n, &n_pad, &F, nullptr);
+    EGR_CHECK(F >= 1, EGR_ERR_ARG, "egr_dac_encode: no frames");
+    EGR_CHECK((long long)rows * n_pad < (1LL << 31), EGR_ERR_UNSUPPORTED, "egr_dac_encode: rows * padded length = %lld does not index with an int (one pass only)",
+              (long long)rows * n_pad);
+    hipStream_t st = (hipStream_t)stream;
+    Walk dry{*m, st, false, rows};
+    walk_encode(dry, nullptr, n, nullptr, nullptr);
+    { const int rc = ensure_ws(m, dry.off + 256, st); if (rc) return rc; }
+    Walk w{*m, st, true, rows};
+    w.base = (char*)m->ws;
+    return walk_encode(w, x, n, z, codes);
+}
+
+extern "C" int egr_dac_quantize(void* handle, const float* ze, int rows, int64_t frames, float* z, int* codes, void* stream) {
+    Dac* m = (Dac*)handle;
+    { const int rc = begin_call(m, "egr_dac_quantize", rows, frames); if (rc) return rc; }
+    EGR_CHECK(ze && z && codes, EGR_ERR_ARG, "egr_dac_quantize: null argument");
+    EGR_CHECK((long long)rows * frames < (1LL << 31) / 32 && frames < (1LL << 31), EGR_ERR_UNSUPPORTED, "egr_dac_quantize: too many frames for one pass");
+    hipStream_t st = (hipStream_t)stream;
+    Walk dry{*m, st, false, rows};
+    walk_quantize(dry, nullptr, frames, nullptr, nullptr);
+    { const int rc = ensure_ws(m, dry.off + 256, st); if (rc) return rc; }
+    Walk w{*m, st, true, rows};
+    w.base = (char*)m->ws;
+    return walk_quantize(w, ze, frames, z, codes);
+}
+
+extern "C" int egr_dac_decode(void* handle, const float* z, int rows, int64_t frames, float* y, void* stream) {
+    Dac* m = (Dac*)handle;
+    { const int rc = begin_call(m, "egr_dac_decode", rows, frames); if (rc) return rc; }
+    EGR_CHECK(z && y, EGR_ERR_ARG, "egr_dac_decode: null argument");
+    const int64_t n_dec = decoded_len(m->cfg, frames);
+    EGR_CHECK(n_dec >= 1, EGR_ERR_ARG, "egr_dac_decode: %lld frames decode to nothing", (long long)frames);
+    EGR_CHECK((long long)rows * n_dec < (1LL << 31), EGR_ERR_UNSUPPORTED, "egr_dac_decode: rows * decoded length = %lld does not index with an int (one pass only)",
+              (long long)rows * n_dec);
+    hipStream_t st = (hipStream_t)stream;
+    Walk dry{*m, st, false, rows};
+    walk_decode(dry, nullptr, frames, nullptr);
+    { const int rc = ensure_ws(m, dry.off + 256, st); if (rc) return rc; }
+    Walk w{*m, st, true, rows};
+    w.base = (char*)m->ws;
+    return walk_decode(w, z, frames, y);
+}
+
+extern "C" int egr_dac_stage(void* handle, int stage, int index, float* dst, int64_t capacity, int64_t* count, void* stream) {
+    Dac* m = (Dac*)handle;
+    EGR_CHECK(m && count, EGR_ERR_ARG, "egr_dac_stage: null argument");
+    for (const StageRec& s : m->stages)
+        if (s.kind == stage && s.index == index) {
+            *count = s.count;
+            if (!dst) return EGR_OK;
+            EGR_CHECK(capacity >= s.count, EGR_ERR_ARG, "egr_dac_stage: %lld floats do not fit a capacity of %lld", (long long)s.count, (long long)capacity);
+            EGR_HIP(hipMemcpyAsync(dst, s.p, (size_t)s.count * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+            return EGR_OK;
+        }
+    set_error("egr_dac_stage: the last call left no stage (%d, %d)", stage, index);
+    return EGR_ERR_ARG;
+}

@@ -166,6 +166,15 @@ SIGNATURES = {
     "egr_wpe_istft": (_i, [_vp, _i, _i64, _i, _i, _vp, _i64, _vp]),
     "egr_wpe_iterate": (_i, [_vp, _vp, _i, _i, _i64, _i, _i, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     "egr_wpe_dereverb": (_i, [_vp, _i, _i64, _i, _i, _i, _i, _i, _vp, _i64, _vp, C.c_size_t, _vp]),
+    "egr_dac_lengths": (_i, [_vp, _i64, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]),
+    "egr_dac_create": (_i, [C.POINTER(_vp), _vp, _vp, _i64, _i]),
+    "egr_dac_destroy": (_i, [_vp]),
+    "egr_dac_set_stages": (_i, [_vp, _i]),
+    "egr_dac_workspace_bytes": (C.c_size_t, [_vp, _i, _i64]),
+    "egr_dac_encode": (_i, [_vp, _vp, _i, _i64, _vp, _vp, _vp]),
+    "egr_dac_quantize": (_i, [_vp, _vp, _i, _i64, _vp, _vp, _vp]),
+    "egr_dac_decode": (_i, [_vp, _vp, _i, _i64, _vp, _vp]),
+    "egr_dac_stage": (_i, [_vp, _i, _i, _vp, _i64, C.POINTER(_i64), _vp]),
 }
 
 FSR_MAX = 8
@@ -240,6 +249,17 @@ class Dfn2ConfigC(C.Structure):
                 ("emb_hidden_dim", _i), ("emb_num_layers", _i), ("df_hidden_dim", _i), ("df_num_layers", _i), ("gru_groups", _i),
                 ("lin_groups", _i), ("group_shuffle", _i), ("df_gru_skip", _i), ("df_output_layer", _i), ("df_pathway_kt", _i),
                 ("path_groups", _i), ("df_path_groups", _i), ("norm_alpha", _f), ("erb_widths", _i * DFN3_MAX_ERB)]
+
+
+DAC_MAX_RATES = 8
+DAC_STAGE = {"enc": 0, "vq_in": 1, "dec": 2}
+
+
+class DacConfigC(C.Structure):
+    """egr_dac_config (include/egregora_amd.h)."""
+    _fields_ = [("struct_bytes", _i), ("sample_rate", _i), ("encoder_dim", _i), ("n_enc", _i), ("enc_rates", _i * DAC_MAX_RATES),
+                ("decoder_dim", _i), ("n_dec", _i), ("dec_rates", _i * DAC_MAX_RATES), ("latent_dim", _i), ("n_codebooks", _i),
+                ("codebook_size", _i), ("codebook_dim", _i)]
 
 
 def flashsr_config_c(cfg) -> FlashSRConfigC:

@@ -733,6 +733,47 @@ int egr_wpe_iterate(const void* Y, const double* inv_in, int bins, int channels,
 int egr_wpe_dereverb(const float* x, int channels, int64_t n, int n_fft, int hop, int taps, int delay, int iterations, float* y,
                      int64_t n_out, void* ws, size_t ws_bytes, void* stream);
 
+/* Descript Audio Codec forward pass (csrc/egr_dac.hip; SPEC.md 4e): encoder, residual vector quantiser and decoder
+ * of a DAC model, the job of the reference's Egregora_DAC_Encode / Egregora_DAC_Decode nodes
+ * (egregora_audio_enhance_extras.py:730-857) as their docstrings describe it.  Rows are mono signals (DAC-Q1).
+ *   egr_dac_lengths  : host only, touches no GPU: n samples -> n_padded (right-padded to a multiple of hop = prod enc_rates), frames
+ *                      (the encoder's output length) and n_decoded (the decoder's output length from `frames`, not trimmed: DAC-P7)
+ *   egr_dac_create   : config + the packed fp32 weights in dac_weights.pack order (weight norm folded, torch layouts) -> a handle on
+ *                      `device` (repacks and uploads; synchronous).  EGR_ERR_UNSUPPORTED outside DAC-P9
+ *   egr_dac_encode   : x [rows][n] -> z [rows][latent][frames] (sum of the quantised stages), codes int32 [rows][n_codebooks][frames]
+ *   egr_dac_quantize : the quantiser alone on ze [rows][latent][frames]
+ *   egr_dac_decode   : z [rows][latent][frames] -> y [rows][n_decoded]
+ *                      All three enqueue on `stream` and synchronise nothing in the steady state; the handle owns its workspace
+ *                      (grown with hipMallocAsync on `stream`; egr_dac_workspace_bytes: the larger of encode's and decode's for (rows, n)):
+ *                      one call at a time per handle, one stream per handle.  The current device must be the handle's.
+ *   egr_dac_stage    : copy an intermediate of the LAST call into dst (device, `capacity` floats) on `stream`; dst NULL: only *count.
+ *                      Activations are channels-last [rows][L][C].  EGR_DAC_STAGE_ENC index 0: input convolution, 1 .. n_enc: encoder
+ *                      blocks, n_enc + 1: the encoder output ze; EGR_DAC_STAGE_DEC index 0: input convolution, 1 .. n_dec: decoder
+ *                      blocks (the walk holds these anyway); EGR_DAC_STAGE_VQ_IN index i: the residual entering quantiser stage i
+ *                      [rows][frames][latent], written only after egr_dac_set_stages(h, 1) (n_codebooks extra latent frames per
+ *                      frame: off by default), else EGR_ERR_ARG.  egr_dac_set_stages only sets a flag on the handle: it takes effect
+ *                      from the NEXT encode / quantize call (and from the next egr_dac_workspace_bytes query, which then counts the
+ *                      dumps); under the one-call-at-a-time rule above it is not ordered against a call still being enqueued.
+ *   egr_dac_workspace_bytes also bounds egr_dac_quantize on n / hop frames (its buffers are a subset of encode's). */
+#define EGR_DAC_MAX_RATES 8
+#define EGR_DAC_STAGE_ENC 0
+#define EGR_DAC_STAGE_VQ_IN 1
+#define EGR_DAC_STAGE_DEC 2
+typedef struct egr_dac_config {
+    int struct_bytes;                      /* sizeof(egr_dac_config) */
+    int sample_rate, encoder_dim, n_enc, enc_rates[EGR_DAC_MAX_RATES], decoder_dim, n_dec, dec_rates[EGR_DAC_MAX_RATES];
+    int latent_dim, n_codebooks, codebook_size, codebook_dim;
+} egr_dac_config;
+int egr_dac_lengths(const egr_dac_config* cfg, int64_t n, int64_t* n_padded, int64_t* frames, int64_t* n_decoded);
+int egr_dac_create(void** handle, const egr_dac_config* cfg, const float* packed, int64_t n_floats, int device);
+int egr_dac_destroy(void* handle);
+int egr_dac_set_stages(void* handle, int enable);
+size_t egr_dac_workspace_bytes(void* handle, int rows, int64_t n);
+int egr_dac_encode(void* handle, const float* x, int rows, int64_t n, float* z, int* codes, void* stream);
+int egr_dac_quantize(void* handle, const float* ze, int rows, int64_t frames, float* z, int* codes, void* stream);
+int egr_dac_decode(void* handle, const float* z, int rows, int64_t frames, float* y, void* stream);
+int egr_dac_stage(void* handle, int stage, int index, float* dst, int64_t capacity, int64_t* count, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,6 +17,9 @@ the same seeded input and prints the relative error per channel (SPEC.md section
 `--dfn2 MODEL_DIR` does the same for DeepFilterNet2 (dfn2_engine, dfn2_weights.load; SPEC.md section 4c).
 `--wpe` runs nara_wpe's documented call -- stft, wpe() on (bins, channels, frames), istft, in float64 -- and this pack's
 egr_wpe_dereverb on the same seeded reverberant input and prints the relative error (SPEC.md section 4d; parity unpinned until run).
+`--dac MODEL_TYPE` loads the checkpoint dac_weights.discover finds with upstream's `dac.DAC.load`, runs `preprocess` / `encode` /
+`decode` per mono row in float64, and the native codec (dac_engine) on the same seeded input: share of equal codes, relative error of
+z on the frames whose codes agree, and of the decoded signal (SPEC.md section 4e; parity unpinned until run).
 """
 import argparse
 import sys
@@ -46,7 +49,12 @@ def main():
     ap.add_argument("--dfn2", default="", metavar="MODEL_DIR",
                     help="instead: the same for the native DeepFilterNet2 on MODEL_DIR ([train] model = deepfilternet2)")
     ap.add_argument("--wpe", action="store_true", help="instead: compare nara_wpe (importable) with egr_wpe_dereverb (SPEC.md 4d)")
+    ap.add_argument("--dac", default="", metavar="MODEL_TYPE",
+                    help="instead: compare descript-audio-codec (importable) with the native codec on the discovered checkpoint "
+                         "of MODEL_TYPE (44khz / 24khz / 16khz; SPEC.md 4e)")
     args = ap.parse_args()
+    if args.dac:
+        return compare_dac(args.dac, args.seconds)
     if args.wpe:
         return compare_wpe(args.seconds)
     if args.flashsr:
@@ -121,6 +129,43 @@ def compare_wpe(seconds, n_fft=1024, hop=256, taps=10, delay=3, iterations=3):
         e = float(np.linalg.norm(ours[c, :m] - up[c, :m]) / max(np.linalg.norm(up[c, :m]), 1e-30))
         print(f"channel {c}: relative rms error egr_wpe_dereverb vs nara_wpe {e:.3e}; change against the input "
               f"{float(np.linalg.norm(up[c, :x.shape[1]] - x[c]) / np.linalg.norm(x[c])):.3f}")
+
+
+def compare_dac(model_type, seconds):
+    """Upstream DAC (float64, one mono row at a time) vs egr_dac_encode / egr_dac_decode on the same checkpoint file."""
+    import torch
+    try:
+        import dac
+    except Exception as e:
+        sys.exit(f"descript-audio-codec not importable here ({e}); this tool is opt-in")
+    from packload import load_pack
+    load_pack()
+    from egregora_amd import dac_engine, dac_weights
+    path = dac_weights.discover(model_type)
+    if path is None:
+        sys.exit(dac_weights.not_found_message(model_type))
+    eng = dac_engine.engine(path, 0)
+    up = dac.DAC.load(str(path)).double().eval()
+    sr = int(eng.cfg["sample_rate"])
+    n = int(seconds * sr)
+    rng = np.random.Generator(np.random.PCG64(4343))
+    t = np.arange(n) / sr
+    x = np.stack([sum(np.sin(2 * np.pi * f * (1 + 0.01 * c) * t) / (k + 1) for k, f in enumerate(np.geomspace(80, 6000, 8))) for c in range(2)])
+    x = (0.3 * x / np.abs(x).max() + 0.01 * rng.standard_normal(x.shape)).astype(np.float32)
+    xt = torch.from_numpy(x)
+    with torch.no_grad():
+        xp = up.preprocess(xt.double()[:, None], sr)
+        z_up, codes_up = up.encode(xp)[:2]
+        y_up = up.decode(z_up)[:, 0]
+    z, codes = eng.encode(xt.cuda())
+    y = eng.decode(z).cpu()
+    same = (codes.cpu().long() == codes_up).all(dim=1)
+    rel = lambda a, b: float((a.double() - b).norm() / max(float(b.norm()), 1e-30))
+    print(f"codes {tuple(codes.shape)}: frames with all codes equal {float(same.double().mean()):.4%}")
+    if same.any():
+        print(f"z on those frames: relative rms error {rel(z.cpu().transpose(1, 2)[same], z_up.transpose(1, 2)[same]):.3e}")
+    m = min(y.shape[-1], y_up.shape[-1])
+    print(f"decoded {tuple(y.shape)} vs upstream {tuple(y_up.shape)}: relative rms error {rel(y[:, :m], y_up[:, :m]):.3e}")
 
 
 def compare_dfn3(model_dir, seconds, dfn2=False):
