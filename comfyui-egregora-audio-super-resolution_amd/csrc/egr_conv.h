@@ -3,7 +3,7 @@
 #pragma once
 #include <string>
 
-#include "egr_common.h"
+#include "egr_weight_prep.h"
 
 namespace egr {
 
@@ -397,6 +397,14 @@ __device__ __forceinline__ void out_amax_commit(const ConvP& p, const unsigned* 
 struct ConvCall : egr_conv_desc {
     ConvCall() : egr_conv_desc() { B = H = W = OH = OW = KH = KW = stride = dil = osy = osx = OHF = OWF = nz = 1; w_scale = 1.f; }
 };
+
+// The weight operand of a call: the two fp16 terms (scheme 1) where x's row maxima over batch_rows rows are given and the weight holds
+// them, else the three bf16 terms where it holds those, else -- or when the call cannot run on the split kernels -- the fp32 pack.
+inline void set_weight(ConvCall& c, const PreparedWeight& w, const unsigned* row_amax, int batch_rows, bool split = true) {
+    if (split && row_amax && w.w2) { c.w3 = w.w2; c.sch = 1; c.w_scale = w.w_scale; c.row_amax = (const float*)row_amax; c.batch_rows = batch_rows; }
+    else if (split && w.w3) c.w3 = w.w3;
+    else c.w = w.w;
+}
 
 // What conv_choose picked: one kernel instantiation (conv_choice_name spells it) and its launch geometry
 enum ConvFamily { CONV_NONE = 0, CONV_IGEMM, CONV_S3, CONV1D_S3, CONV3X3_IS };

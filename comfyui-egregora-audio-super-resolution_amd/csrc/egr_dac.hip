@@ -1,8 +1,10 @@
 // Descript Audio Codec forward pass on gfx950 (SPEC.md 4e): encoder, residual vector quantiser, decoder.
 //
-// The handle keeps the weights (weight norm already folded by the host, dac_weights.pack) repacked for the contraction launcher
-// (csrc/egr_nn_gemm.hip): every convolution with Cin % 16 == 0 runs on two fp16 terms per operand (scheme 1, egr_conv_h2's path), the
-// others on the fp32 MFMA kernel.  Activations are channels-last [rows][L][C]; rows are independent mono signals.  Own kernels:
+// The handle keeps the weights (weight norm already folded by the host, dac_weights.pack) prepared for the contraction launcher
+// (csrc/egr_nn_gemm.hip) by the library's one weight path (egr_weight_prep.h: packed and split on the device at create): every
+// convolution with Cin % 16 == 0 runs on two fp16 terms per operand (scheme 1, egr_conv_h2's path), the others on the fp32 MFMA
+// kernel.  Workspace, device checks and the stage read are the handles' shared ones (egr_handle.h).  Activations are channels-last
+// [rows][L][C]; rows are independent mono signals.  Own kernels:
 //   k_dac_snake    x + sin^2(alpha x) / (alpha + 1e-9) per channel, and the row's max |y| for the contraction that reads y
 //   k_dac_conv_in  the Cin = 1, k = 7 input convolution (with the right zero pad to a multiple of the hop)
 //   k_dac_conv_out the Cout = 1, k = 7 output convolution with tanh: per input row seven partial dots, then a 7-term gather
@@ -16,6 +18,7 @@
 #include <vector>
 
 #include "egr_conv.h"
+#include "egr_handle.h"
 
 namespace egr {
 namespace {
@@ -253,12 +256,9 @@ size_t vq_lds_bytes(int K, int cd, int latent, int TF) {
 // ------------------------------------------------------------------------------------------------------------------ the handle
 struct Conv {                       // one convolution served by the contraction launcher
     int Cin = 0, Cout = 0, K = 1, stride = 1, dil = 1, pad = 0;
-    const void* w2 = nullptr;       // two fp16 terms (Cin % 16 == 0)
-    float w_scale = 1.f;
-    const float* wf = nullptr;      // fp32 pack otherwise
+    PreparedWeight w;               // two fp16 terms (Cin % 16 == 0), the fp32 pack otherwise
     const float* bias = nullptr;
-    size_t o_pack = 0, o_bias = 0, o_w2 = 0;   // offsets while the images are built
-    bool h2 = false;
+    size_t o_bias = 0;              // of the bias in the tables, while they are built
 };
 struct Snake { const float* alpha = nullptr; const float* inva = nullptr; size_t o = 0; int C = 0; };
 struct ResUnit { Snake s1, s2; Conv c7, c1; };
@@ -286,8 +286,7 @@ struct Dac {
     float* d_misc = nullptr;        // biases, snake tables, thin convolutions, quantiser
     float* d_f32 = nullptr;         // fp32 packs of the convolutions the split kernels do not take
     void* d_w2 = nullptr;           // fp16 term packs
-    void* ws = nullptr;
-    size_t ws_bytes = 0;
+    Workspace ws;
     std::vector<StageRec> stages;
 };
 
@@ -339,9 +338,10 @@ int check_config(const egr_dac_config* c, const char* who) {
 // ---- building the device images from the packed blob
 struct Builder {
     const float* src; int64_t n, pos = 0;
-    std::vector<float> misc, f32pack, stage;           // stage: fp32 packs that become fp16 term packs
-    size_t w2_bytes = 0;
-    std::vector<Conv*> convs;
+    std::vector<float> misc;
+    struct Job { Conv* L; int64_t o_src; int layout, Ci, Co, k; };      // a weight of the blob (torch layout, o_src floats in) to prepare
+    std::vector<Job> jobs;
+    size_t f32_bytes = 0, w2_bytes = 0, tmp_bytes = 0;   // fp32 packs kept, fp16 term packs, the largest fp32 pack that is only split
     bool ok = true;
     const float* take(int64_t k) {
         if (pos + k > n) { ok = false; return nullptr; }
@@ -362,14 +362,14 @@ struct Builder {
         for (int c = 0; c < C; ++c) inv[c] = (float)(1.0 / ((double)a[c] + 1e-9));
         put(inv.data(), C);                             // 1 / (alpha + 1e-9), at the next 16-byte boundary behind alpha
     }
-    // torch Conv1d weight [Co][Ci][k] + bias -> slab-major [ceil(K/16)][Co][16], K ordered (tap, ci)
+    // torch Conv1d weight [Co][Ci][k] + bias -> egr_pack_weight's layout 0, K ordered (tap, ci)
     void conv(Conv& L, int Ci, int Co, int k, int stride, int dil, int pad) {
         const float* w = take((int64_t)Co * Ci * k);
         const float* b = take(Co);
         if (!w || !b) return;
         L.Cin = Ci; L.Cout = Co; L.K = k; L.stride = stride; L.dil = dil; L.pad = pad;
         L.o_bias = put(b, Co);
-        pack(L, w, Ci, Co, k, false);
+        weight(L, w, 0, k * Ci, Co, Ci, Co, k);
     }
     // torch ConvTranspose1d weight [Ci][Co][k] -> GEMM onto columns n = tap * Co + co
     void convtr(Conv& L, int Ci, int Co, int k) {
@@ -378,48 +378,13 @@ struct Builder {
         if (!w || !b) return;
         L.Cin = Ci; L.Cout = k * Co; L.K = 1;
         L.o_bias = put(b, Co);                          // [Co]: added by the gather, not by the GEMM
-        pack(L, w, Ci, Co, k, true);
+        weight(L, w, 1, Ci, k * Co, Ci, Co, k);
     }
-    void pack(Conv& L, const float* w, int Ci, int Co, int k, bool tr) {
-        const int Kd = tr ? Ci : k * Ci, N = tr ? k * Co : Co;
-        const size_t slabs = (Kd + 15) / 16, numel = slabs * N * 16;
-        L.h2 = Ci % 16 == 0;
-        std::vector<float>& dst = L.h2 ? stage : f32pack;
-        L.o_pack = dst.size();
-        dst.resize(dst.size() + numel, 0.f);
-        float* d = dst.data() + L.o_pack;
-        float wmax = 0.f;
-        if (tr) {
-            for (int ci = 0; ci < Ci; ++ci)
-                for (int co = 0; co < Co; ++co)
-                    for (int t = 0; t < k; ++t) {
-                        const float v = w[((size_t)ci * Co + co) * k + t];
-                        d[((size_t)(ci / 16) * N + (size_t)t * Co + co) * 16 + ci % 16] = v;
-                        wmax = std::max(wmax, std::fabs(v));
-                    }
-        } else {
-            for (int co = 0; co < Co; ++co)
-                for (int ci = 0; ci < Ci; ++ci)
-                    for (int t = 0; t < k; ++t) {
-                        const float v = w[((size_t)co * Ci + ci) * k + t];
-                        const int kk = t * Ci + ci;
-                        d[((size_t)(kk / 16) * N + co) * 16 + kk % 16] = v;
-                        wmax = std::max(wmax, std::fabs(v));
-                    }
-        }
-        if (L.h2) {
-            // power of two that brings the pack's largest magnitude into (2^12, 2^13] (the scale the FlashSR handle gives its weights)
-            L.w_scale = 1.f;
-            if (wmax > 0.f && std::isfinite(wmax)) {
-                int ex = 0;
-                const float fr = frexpf(wmax, &ex);
-                if (fr == 0.5f) --ex;
-                L.w_scale = ldexpf(1.f, std::max(-60, std::min(60, 13 - ex)));
-            }
-            L.o_w2 = w2_bytes;
-            w2_bytes += slabs * 2 * N * 16 * 2;
-        }
-        convs.push_back(&L);
+    void weight(Conv& L, const float* w, int layout, int K, int N, int Ci, int Co, int k) {
+        weight_shape(L.w, K, N);
+        if (Ci % 16 == 0) { w2_bytes += L.w.term_bytes(2); tmp_bytes = std::max(tmp_bytes, L.w.pack_bytes()); }
+        else f32_bytes += L.w.pack_bytes();
+        jobs.push_back({&L, w - src, layout, Ci, Co, k});
     }
 };
 
@@ -431,50 +396,47 @@ void res_unit(Builder& B, ResUnit& u, int C, int d) {
 }
 
 void destroy(Dac* m) {
-    int prev = 0;
-    (void)hipGetDevice(&prev);
-    (void)hipSetDevice(m->device);
-    if (m->ws) {
-        (void)hipFreeAsync(m->ws, nullptr);
-        (void)hipDeviceSynchronize();
+    {
+        DeviceScope dev(m->device);
+        m->ws.release();
+        if (m->d_misc) (void)hipFree(m->d_misc);
+        if (m->d_f32) (void)hipFree(m->d_f32);
+        if (m->d_w2) (void)hipFree(m->d_w2);
     }
-    if (m->d_misc) (void)hipFree(m->d_misc);
-    if (m->d_f32) (void)hipFree(m->d_f32);
-    if (m->d_w2) (void)hipFree(m->d_w2);
-    (void)hipSetDevice(prev);
     delete m;
 }
 
-int upload(Dac* m, Builder& B) {
-    float* d_stage = nullptr;
+// The tables onto the current device, and the blob's convolution weights through prepare_weight on the null stream: the blob goes up
+// as it is (torch layouts); a weight that is split passes through one scratch pack behind it, which leaves with the blob.
+int upload(Dac* m, const Builder& B, const float* packed, int64_t n_floats) {
+    float* d_tmp = nullptr;                            // [blob][one float: a pack's largest magnitude, 16-byte slot][scratch pack]
+    const size_t blob_floats = ((size_t)n_floats + 3) & ~(size_t)3;
     auto fail = [&](const char* what) {
         set_error("egr_dac_create: %s failed on device %d", what, m->device);
-        if (d_stage) (void)hipFree(d_stage);
+        if (d_tmp) (void)hipFree(d_tmp);
         return EGR_ERR_HIP;
     };
     if (hipMalloc((void**)&m->d_misc, std::max<size_t>(16, B.misc.size() * 4)) != hipSuccess) return fail("hipMalloc(tables)");
     if (hipMemcpy(m->d_misc, B.misc.data(), B.misc.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return fail("upload(tables)");
-    if (!B.f32pack.empty()) {
-        if (hipMalloc((void**)&m->d_f32, B.f32pack.size() * 4) != hipSuccess) return fail("hipMalloc(fp32 packs)");
-        if (hipMemcpy(m->d_f32, B.f32pack.data(), B.f32pack.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return fail("upload(fp32 packs)");
-    }
-    if (!B.stage.empty()) {
-        if (hipMalloc((void**)&d_stage, B.stage.size() * 4) != hipSuccess) return fail("hipMalloc(staging)");
-        if (hipMemcpy(d_stage, B.stage.data(), B.stage.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return fail("upload(staging)");
-        if (hipMalloc(&m->d_w2, B.w2_bytes) != hipSuccess) return fail("hipMalloc(fp16 terms)");
-    }
-    for (Conv* L : B.convs) {
-        if (L->h2) {
-            const int Kd = L->K * L->Cin;
-            void* w2 = (char*)m->d_w2 + L->o_w2;
-            const int rc = egr_split2h_pack(d_stage + L->o_pack, w2, (Kd + 15) / 16, L->Cout, L->w_scale, nullptr);
-            if (rc) { if (d_stage) (void)hipFree(d_stage); return rc; }
-            L->w2 = w2;
-        } else L->wf = m->d_f32 + L->o_pack;
-        L->bias = m->d_misc + L->o_bias;
+    if (B.f32_bytes && hipMalloc((void**)&m->d_f32, B.f32_bytes) != hipSuccess) return fail("hipMalloc(fp32 packs)");
+    if (B.w2_bytes && hipMalloc(&m->d_w2, B.w2_bytes) != hipSuccess) return fail("hipMalloc(fp16 terms)");
+    if (hipMalloc((void**)&d_tmp, (blob_floats + 4) * 4 + B.tmp_bytes) != hipSuccess) return fail("hipMalloc(staging)");
+    if (hipMemcpy(d_tmp, packed, (size_t)n_floats * 4, hipMemcpyHostToDevice) != hipSuccess) return fail("upload(staging)");
+    float* slot = d_tmp + blob_floats;
+    char* f32 = (char*)m->d_f32;
+    char* w2 = (char*)m->d_w2;
+    for (const Builder::Job& j : B.jobs) {
+        PreparedWeight& w = j.L->w;
+        const bool h2 = j.Ci % 16 == 0;
+        if (h2) { w.w = slot + 4; w.w2 = w2; w2 += w.term_bytes(2); }
+        else { w.w = (float*)f32; f32 += w.pack_bytes(); }
+        const int rc = prepare_weight(d_tmp + j.o_src, j.layout, j.Ci, j.Co, 1, j.k, w, slot, nullptr);
+        if (rc) { (void)hipFree(d_tmp); return rc; }
+        if (h2) w.w = nullptr;                          // (the scratch pack)
+        j.L->bias = m->d_misc + j.L->o_bias;
     }
     if (hipDeviceSynchronize() != hipSuccess) return fail("weight repack");
-    if (d_stage) (void)hipFree(d_stage);
+    (void)hipFree(d_tmp);
     return EGR_OK;
 }
 
@@ -514,8 +476,7 @@ struct Walk {
         cc.x = x; cc.y = y; cc.bias = bias; cc.res = res;
         cc.B = rows; cc.W = (int)Lin; cc.Cin = c.Cin; cc.OW = cc.OWF = (int)Lout; cc.Cout = c.Cout; cc.KW = c.K;
         cc.stride = c.stride; cc.dil = c.dil; cc.pad_l = c.pad;
-        if (c.h2) { cc.w3 = c.w2; cc.sch = 1; cc.w_scale = c.w_scale; cc.row_amax = (const float*)x_amax; cc.batch_rows = rows; }
-        else cc.w = c.wf;
+        set_weight(cc, c.w, x_amax, rows);
         rc = conv_call(cc, st);
     }
 };
@@ -656,8 +617,7 @@ int walk_decode(Walk& w, const float* z, int64_t F, float* y) {
         if (w.go()) {
             ConvCall cc;
             cc.x = a; cc.y = Y; cc.B = (int)(rows * L); cc.Cin = b.up.Cin; cc.Cout = b.up.Cout;
-            if (b.up.h2) { cc.w3 = b.up.w2; cc.sch = 1; cc.w_scale = b.up.w_scale; cc.row_amax = (const float*)ra; cc.batch_rows = rows; }
-            else cc.w = b.up.wf;
+            set_weight(cc, b.up.w, ra, rows);
             w.rc = conv_call(cc, w.st);
         }
         const int64_t Lo = convtr_len(L, b.stride);
@@ -680,22 +640,24 @@ int walk_decode(Walk& w, const float* z, int64_t F, float* y) {
 
 int begin_call(Dac* m, const char* who, int rows, int64_t len) {
     EGR_CHECK(m && rows >= 1 && rows <= 65535 && len >= 1, EGR_ERR_ARG, "%s: bad argument", who);
-    int cur = -1;
-    EGR_HIP(hipGetDevice(&cur));
-    EGR_CHECK(cur == m->device, EGR_ERR_ARG, "%s: handle belongs to device %d, current device is %d", who, m->device, cur);
-    return EGR_OK;
+    return check_current_device(who, m->device);
 }
 
-int ensure_ws(Dac* m, size_t need, hipStream_t st) {
-    if (need > m->ws_bytes) {
-        if (m->ws) EGR_HIP(hipFreeAsync(m->ws, st));
-        m->ws = nullptr;
-        m->ws_bytes = 0;
-        EGR_HIP(hipMallocAsync(&m->ws, need, st));
-        m->ws_bytes = need;
-    }
-    m->stages.clear();
-    return EGR_OK;
+// One call: walk(w) lays the workspace out on a dry Walk (workspace_need), then enqueues the kernels on a launching one over the
+// workspace grown to that
+template <class F>
+size_t workspace_need(Dac& m, int rows, F walk) {
+    Walk dry{m, nullptr, false, rows};
+    walk(dry);
+    return dry.off + 256;
+}
+template <class F>
+int run(Dac& m, int rows, hipStream_t st, F walk) {
+    EGR_TRY(m.ws.grow(workspace_need(m, rows, walk), st));
+    m.stages.clear();
+    Walk w{m, st, true, rows};
+    w.base = (char*)m.ws.p;
+    return walk(w);
 }
 
 }  // namespace
@@ -809,19 +771,21 @@ extern "C" int egr_dac_create(void** handle, const egr_dac_config* cfg, const fl
         delete m;
         return EGR_ERR_ARG;
     }
-    int prev = 0;
-    if (hipGetDevice(&prev) != hipSuccess || hipSetDevice(device) != hipSuccess) {
-        set_error("egr_dac_create: cannot select device %d", device);
-        delete m;
-        return EGR_ERR_HIP;
+    int rc = EGR_OK;
+    {
+        DeviceScope dev(device);
+        if (!dev.ok) {
+            set_error("egr_dac_create: cannot select device %d", device);
+            delete m;
+            return EGR_ERR_HIP;
+        }
+        rc = upload(m, B, packed, n_floats);
+        if (rc == EGR_OK) {
+            hipError_t e = hipFuncSetAttribute((const void*)k_dac_vq<8>, hipFuncAttributeMaxDynamicSharedMemorySize, DAC_LDS_MAX);
+            if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_dac_vq<0>, hipFuncAttributeMaxDynamicSharedMemorySize, DAC_LDS_MAX);
+            if (e != hipSuccess) { set_error("egr_dac_create: hipFuncSetAttribute(MaxDynamicSharedMemorySize) -> %s", hipGetErrorString(e)); rc = EGR_ERR_HIP; }
+        }
     }
-    int rc = upload(m, B);
-    if (rc == EGR_OK) {
-        hipError_t e = hipFuncSetAttribute((const void*)k_dac_vq<8>, hipFuncAttributeMaxDynamicSharedMemorySize, DAC_LDS_MAX);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_dac_vq<0>, hipFuncAttributeMaxDynamicSharedMemorySize, DAC_LDS_MAX);
-        if (e != hipSuccess) { set_error("egr_dac_create: hipFuncSetAttribute(MaxDynamicSharedMemorySize) -> %s", hipGetErrorString(e)); rc = EGR_ERR_HIP; }
-    }
-    (void)hipSetDevice(prev);
     if (rc) { destroy(m); return rc; }
     // bind the tables
     const float* D = m->d_misc;
@@ -857,10 +821,8 @@ extern "C" size_t egr_dac_workspace_bytes(void* handle, int rows, int64_t n) {
     int64_t F = 0;
     lengths(m->cfg, n, nullptr, &F, nullptr);
     if (F < 1) return 0;
-    Walk we{*m, nullptr, false, rows}, wd{*m, nullptr, false, rows};
-    walk_encode(we, nullptr, n, nullptr, nullptr);
-    walk_decode(wd, nullptr, F, nullptr);
-    return std::max(we.off, wd.off) + 256;
+    return std::max(workspace_need(*m, rows, [&](Walk& w) { return walk_encode(w, nullptr, n, nullptr, nullptr); }),
+                    workspace_need(*m, rows, [&](Walk& w) { return walk_decode(w, nullptr, F, nullptr); }));
 }
 
 extern "C" int egr_dac_encode(void* handle, const float* x, int rows, int64_t n, float* z, int* codes, void* stream) {
@@ -872,13 +834,7 @@ extern "C" int egr_dac_encode(void* handle, const float* x, int rows, int64_t n,
     EGR_CHECK(F >= 1, EGR_ERR_ARG, "egr_dac_encode: no frames");
     EGR_CHECK((long long)rows * n_pad < (1LL << 31), EGR_ERR_UNSUPPORTED, "egr_dac_encode: rows * padded length = %lld does not index with an int (one pass only)",
               (long long)rows * n_pad);
-    hipStream_t st = (hipStream_t)stream;
-    Walk dry{*m, st, false, rows};
-    walk_encode(dry, nullptr, n, nullptr, nullptr);
-    { const int rc = ensure_ws(m, dry.off + 256, st); if (rc) return rc; }
-    Walk w{*m, st, true, rows};
-    w.base = (char*)m->ws;
-    return walk_encode(w, x, n, z, codes);
+    return run(*m, rows, (hipStream_t)stream, [&](Walk& w) { return walk_encode(w, x, n, z, codes); });
 }
 
 extern "C" int egr_dac_quantize(void* handle, const float* ze, int rows, int64_t frames, float* z, int* codes, void* stream) {
@@ -886,13 +842,7 @@ extern "C" int egr_dac_quantize(void* handle, const float* ze, int rows, int64_t
     { const int rc = begin_call(m, "egr_dac_quantize", rows, frames); if (rc) return rc; }
     EGR_CHECK(ze && z && codes, EGR_ERR_ARG, "egr_dac_quantize: null argument");
     EGR_CHECK((long long)rows * frames < (1LL << 31) / 32 && frames < (1LL << 31), EGR_ERR_UNSUPPORTED, "egr_dac_quantize: too many frames for one pass");
-    hipStream_t st = (hipStream_t)stream;
-    Walk dry{*m, st, false, rows};
-    walk_quantize(dry, nullptr, frames, nullptr, nullptr);
-    { const int rc = ensure_ws(m, dry.off + 256, st); if (rc) return rc; }
-    Walk w{*m, st, true, rows};
-    w.base = (char*)m->ws;
-    return walk_quantize(w, ze, frames, z, codes);
+    return run(*m, rows, (hipStream_t)stream, [&](Walk& w) { return walk_quantize(w, ze, frames, z, codes); });
 }
 
 extern "C" int egr_dac_decode(void* handle, const float* z, int rows, int64_t frames, float* y, void* stream) {
@@ -903,26 +853,14 @@ extern "C" int egr_dac_decode(void* handle, const float* z, int rows, int64_t fr
     EGR_CHECK(n_dec >= 1, EGR_ERR_ARG, "egr_dac_decode: %lld frames decode to nothing", (long long)frames);
     EGR_CHECK((long long)rows * n_dec < (1LL << 31), EGR_ERR_UNSUPPORTED, "egr_dac_decode: rows * decoded length = %lld does not index with an int (one pass only)",
               (long long)rows * n_dec);
-    hipStream_t st = (hipStream_t)stream;
-    Walk dry{*m, st, false, rows};
-    walk_decode(dry, nullptr, frames, nullptr);
-    { const int rc = ensure_ws(m, dry.off + 256, st); if (rc) return rc; }
-    Walk w{*m, st, true, rows};
-    w.base = (char*)m->ws;
-    return walk_decode(w, z, frames, y);
+    return run(*m, rows, (hipStream_t)stream, [&](Walk& w) { return walk_decode(w, z, frames, y); });
 }
 
 extern "C" int egr_dac_stage(void* handle, int stage, int index, float* dst, int64_t capacity, int64_t* count, void* stream) {
     Dac* m = (Dac*)handle;
     EGR_CHECK(m && count, EGR_ERR_ARG, "egr_dac_stage: null argument");
     for (const StageRec& s : m->stages)
-        if (s.kind == stage && s.index == index) {
-            *count = s.count;
-            if (!dst) return EGR_OK;
-            EGR_CHECK(capacity >= s.count, EGR_ERR_ARG, "egr_dac_stage: %lld floats do not fit a capacity of %lld", (long long)s.count, (long long)capacity);
-            EGR_HIP(hipMemcpyAsync(dst, s.p, (size_t)s.count * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
-            return EGR_OK;
-        }
+        if (s.kind == stage && s.index == index) return stage_copy_out("egr_dac_stage", s.p, s.count, dst, capacity, count, stream);
     set_error("egr_dac_stage: the last call left no stage (%d, %d)", stage, index);
     return EGR_ERR_ARG;
 }

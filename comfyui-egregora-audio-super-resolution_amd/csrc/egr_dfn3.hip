@@ -18,7 +18,7 @@
 #include <memory>
 #include <vector>
 
-#include "egr_common.h"
+#include "egr_handle.h"
 
 namespace egr {
 namespace {
@@ -559,7 +559,6 @@ inline unsigned grid_for(int64_t n, int bs = 256) {
 }
 inline int64_t align64(int64_t n) { return (n + 63) & ~63LL; }
 
-#define EGR_TRY(x) do { int rc__ = (x); if (rc__ != EGR_OK) return rc__; } while (0)
 
 struct Conv {                 // one convolution with its (optional) BN affine
     const float* w = nullptr; const float* scale = nullptr; const float* shift = nullptr;
@@ -603,7 +602,7 @@ struct DfnCore {
     float wnorm = 0.f;
     Conv erb0, erb_dw[3], erb_pw[3], df0, df0_pw, df1_dw, df1_pw, path[4], ct_dw[3], ct_pw[3], out0, convp, convp_pw;
     // workspace of the last call
-    void* ws = nullptr; size_t ws_bytes = 0;
+    Workspace ws;
     int lastC = 0, lastF = 0; int64_t lastT = 0;
     bool segmented = false;                 // the last call was a segmented one (its buffers hold the last segment only)
     SegState sg;
@@ -697,13 +696,7 @@ int rows_op(const float* a, const float* bias, const float* res, float* y, int64
 // ---- between erb_decoder_convs and df_pathway_and_coefs, their assemble kernel before synthesis
 // Grows the workspace to `need` bytes on `st` and notes the call's shape; the caller lays its buffers out over m.ws afterwards.
 int ensure_workspace(DfnCore& m, size_t need, int C, int nF, int64_t T, bool segmented, hipStream_t st) {
-    if (need > m.ws_bytes) {
-        if (m.ws) EGR_HIP(hipFreeAsync(m.ws, st));
-        m.ws = nullptr;
-        m.ws_bytes = 0;
-        EGR_HIP(hipMallocAsync(&m.ws, need, st));
-        m.ws_bytes = need;
-    }
+    EGR_TRY(m.ws.grow(need, st));
     m.lastC = C; m.lastF = nF; m.lastT = T;
     m.segmented = segmented;
     return EGR_OK;
@@ -930,13 +923,11 @@ Image build_tables(const DfnDims& d, const float* packed, int64_t n_floats, int6
 // name.  On failure nothing stays allocated; either way the device that was current is current again.
 int upload(DfnCore& m, const char* who, const Image& im) {
     const size_t bytes = sizeof(float) * im.host.size();
-    int prev = 0;
-    if (hipGetDevice(&prev) != hipSuccess || hipSetDevice(m.device) != hipSuccess || hipMalloc(&m.dev_w, bytes) != hipSuccess ||
-        hipMemcpy(m.dev_w, im.host.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) {
+    DeviceScope dev(m.device);
+    if (!dev.ok || hipMalloc(&m.dev_w, bytes) != hipSuccess || hipMemcpy(m.dev_w, im.host.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) {
         set_error("%s: device allocation / upload failed on device %d", who, m.device);
         if (m.dev_w) (void)hipFree(m.dev_w);
         m.dev_w = nullptr;
-        (void)hipSetDevice(prev);
         return EGR_ERR_HIP;
     }
     // the analysis / synthesis DFTs keep a frame and the twiddles in dynamic LDS: 24 N and 16 (1.5 N + 1) bytes, above the 64 KiB
@@ -956,10 +947,8 @@ int upload(DfnCore& m, const char* who, const Image& im) {
             set_error("%s: hipFuncSetAttribute(MaxDynamicSharedMemorySize) -> %s", who, hipGetErrorString(ea));
         (void)hipFree(m.dev_w);
         m.dev_w = nullptr;
-        (void)hipSetDevice(prev);
         return EGR_ERR_HIP;
     }
-    (void)hipSetDevice(prev);
     return EGR_OK;
 }
 
@@ -985,22 +974,13 @@ int enhance_checks(const DfnCore* m, const char* who, const float* x48, int chan
     EGR_CHECK(m && x48 && y && channels >= 1 && channels <= 65535 && n >= 1, EGR_ERR_ARG, "%s: bad argument", who);
     // nF * 4096 fits an int (which also keeps nF below 65535 * 4096)
     EGR_CHECK(!whole || m->frames_of(n) <= MAX_FRAMES, EGR_ERR_UNSUPPORTED, "%s: input too long", who);
-    int cur = -1;
-    EGR_HIP(hipGetDevice(&cur));
-    EGR_CHECK(cur == m->device, EGR_ERR_ARG, "%s: handle belongs to device %d, current device is %d", who, m->device, cur);
-    return EGR_OK;
+    return check_current_device(who, m->device);
 }
 
 void destroy(DfnCore& m) {
-    int prev = 0;
-    (void)hipGetDevice(&prev);
-    (void)hipSetDevice(m.device);
-    if (m.ws) {                                // hipMallocAsync memory: returned stream-ordered, then waited for (not a pipeline call)
-        (void)hipFreeAsync(m.ws, nullptr);
-        (void)hipDeviceSynchronize();
-    }
+    DeviceScope dev(m.device);
+    m.ws.release();
     if (m.dev_w) (void)hipFree(m.dev_w);
-    (void)hipSetDevice(prev);
 }
 
 static_assert(EGR_DFN2_STAGE_GRU0 == EGR_DFN3_STAGE_GRU0, "one GRU stage range for both models");
@@ -1032,17 +1012,13 @@ bool stage_common(const DfnCore& m, int stage, const float** src, int64_t* n) {
 // own(stage, &src, &n) names the model's own stages (it is asked first and leaves src null for every other)
 template <class Own>
 int stage_copy(const DfnCore& m, const char* who, int stage, float* dst, int64_t capacity, int64_t* count, void* stream, Own own) {
-    EGR_CHECK(m.ws, EGR_ERR_ARG, "%s: no enhance call yet", who);
+    EGR_CHECK(m.ws.p, EGR_ERR_ARG, "%s: no enhance call yet", who);
     EGR_CHECK(!m.segmented, EGR_ERR_ARG, "%s: the last call was segmented; stages belong to one-pass calls", who);
     const float* src = nullptr;
     int64_t n = 0;
     own(stage, &src, &n);
     EGR_CHECK(src || stage_common(m, stage, &src, &n), EGR_ERR_ARG, "%s: unknown stage %d", who, stage);
-    *count = n;
-    if (!dst) return EGR_OK;
-    EGR_CHECK(capacity >= n, EGR_ERR_ARG, "%s: capacity %lld < %lld", who, (long long)capacity, (long long)n);
-    EGR_HIP(hipMemcpyAsync(dst, src, sizeof(float) * n, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    return EGR_OK;
+    return stage_copy_out(who, src, n, dst, capacity, count, stream);
 }
 
 // One recurrence layer alone on zero projections: launch(proj, out, sum, nF) runs it for nF steps on the null stream; a short warm-up
@@ -1329,7 +1305,7 @@ int run(M& m, const float* x, int C, int64_t T, float* y, hipStream_t st) {
     const int nF = (int)k.frames_of(T);
     const int64_t R = (int64_t)C * nF;
     EGR_TRY(ensure_workspace(k, workspace_need(m, C, nF), C, nF, T, false, st));
-    Take take{(char*)k.ws};
+    Take take{(char*)k.ws.p};
     layout(m, Rows{R, R, R}, take, k.B, m.X);
     unbind_segments(m);
     features(k, x, C, nF, T, st);
@@ -1392,7 +1368,7 @@ int run_segmented(M& m, const float* x, int C, int64_t T, float* y, int64_t seg_
     const int N = d.fft_size, E = d.nb_erb, nb = d.nb_df, la = d.conv_lookahead, O2 = 2 * d.df_order;
     EGR_TRY(ensure_workspace(k, segment_need(m, C, S), C, 0, T, true, st));
     SegLayout L;
-    layout_segments(m, C, S, (char*)k.ws, k.B, m.X, L);
+    layout_segments(m, C, S, (char*)k.ws.p, k.B, m.X, L);
     Conv* hc[N_HIST_CONV];
     int fin[N_HIST_CONV];
     hist_convs(k, hc, fin);
@@ -1400,7 +1376,7 @@ int run_segmented(M& m, const float* x, int C, int64_t T, float* y, int64_t seg_
     for (size_t g = 0; g < m.grus.size(); ++g) m.grus[g].hst = L.gru_h[g];
     k.sg = L.sg;
     // nothing of an earlier call survives: zero states and histories (the norm states start from their linspace values in segment 0)
-    EGR_HIP(hipMemsetAsync((char*)k.ws + L.state_off, 0, L.end - L.state_off, st));
+    EGR_HIP(hipMemsetAsync((char*)k.ws.p + L.state_off, 0, L.end - L.state_off, st));
     int64_t nseg = 0;
     egr_dfn_segment sp;
     EGR_TRY(egr_dfn_segment_plan(N, d.hop_size, la, d.df_order, d.df_lookahead, T, S, 0, nullptr, &nseg));
@@ -1553,7 +1529,7 @@ extern "C" size_t egr_dfn3_segment_workspace_bytes(void* handle, int channels, i
 }
 
 extern "C" size_t egr_dfn3_workspace_held(void* handle) {
-    return handle ? ((const egr::Dfn3*)handle)->core.ws_bytes : 0;
+    return handle ? ((const egr::Dfn3*)handle)->core.ws.bytes : 0;
 }
 
 extern "C" int egr_dfn3_stage(void* handle, int stage, float* dst, int64_t capacity, int64_t* count, void* stream) {
@@ -1705,7 +1681,7 @@ extern "C" size_t egr_dfn2_segment_workspace_bytes(void* handle, int channels, i
 }
 
 extern "C" size_t egr_dfn2_workspace_held(void* handle) {
-    return handle ? ((const egr::Dfn2*)handle)->core.ws_bytes : 0;
+    return handle ? ((const egr::Dfn2*)handle)->core.ws.bytes : 0;
 }
 
 extern "C" int egr_dfn2_stage(void* handle, int stage, float* dst, int64_t capacity, int64_t* count, void* stream) {

@@ -165,14 +165,9 @@ struct Ten {                       // an fp32 activation owned by the arena (mov
     void view(std::initializer_list<int64_t> s) { nd = 0; for (int64_t v : s) d[nd++] = v; }
 };
 
-struct Wt {                        // one entry of the weight store
-    float* w = nullptr;            // raw tensor (norms, biases, snake parameters) or fp32 slab-major pack
-    void* w3 = nullptr;            // three-way bf16 split of the pack (egr_split3_pack)
-    void* w2 = nullptr;            // two fp16 terms of w * w_scale (egr_split2h_pack)
-    float w_scale = 1.f;
+struct Wt : egr::PreparedWeight {  // one entry of the weight store; w may also be a raw tensor (norms, biases, snake parameters)
     int KH = 0, KW = 0, Cin = 0, Cout = 0;   // logical shape of a packed contraction (Cout = GEMM N)
     int64_t zfloats = 0;           // floats per component of a z-stacked Winograd pack
-    int64_t numel = 0;
 };
 
 struct ProfRec { std::string kind; double flops; hipEvent_t a, b; std::string detail; };
@@ -319,50 +314,24 @@ void build_blocks(M* m) {
 int up_kernel(int r) { return 2 * r + (r % 2); }
 
 // ------------------------------------------------------------------------------------------------ weight packing
-// power of two that brings a tensor whose largest magnitude is amax to (2^(e-1), 2^e]; 1 for an empty / non-finite measurement
-float h2_scale_for(float amax, int e) {
-    if (!(amax > 0.f) || !std::isfinite(amax)) return 1.f;
-    int ex = 0;
-    const float fr = frexpf(amax, &ex);              // amax = fr 2^ex, fr in [0.5, 1)
-    if (fr == 0.5f) --ex;                            // exact power of two: 2^(ex-1)
-    int k = e - ex;
-    k = std::max(-60, std::min(60, k));
-    return ldexpf(1.f, k);
-}
-
+// the term packs of the packed w (N and numel set): three bf16 terms, and two fp16 terms of w * 2^k where the scheme is available
 int split3(M* m, Wt& w) {
     if (m->f32_mfma() || !w.w) return EGR_OK;
-    const int64_t ns = w.numel / ((int64_t)w.Cout * 16);
-    void* p3 = nullptr;
-    OKR(dev_alloc(m, (size_t)ns * 3 * w.Cout * 16 * 2, &p3));
-    OKR(egr_split3_pack(w.w, p3, ns, w.Cout, m->st));
-    w.w3 = p3;
-    if (m->h2) {                                      // fp16 terms of w * 2^k, k from the pack's largest magnitude
+    OKR(dev_alloc(m, w.term_bytes(3), &w.w3));
+    if (m->h2) {
         if (!m->d_wmax && hipMalloc((void**)&m->d_wmax, sizeof(float)) != hipSuccess) { set_error("hipMalloc(weight maximum) failed"); return EGR_ERR_ALLOC; }
-        float wmax = 0.f;
-        EGR_HIP(hipMemsetAsync(m->d_wmax, 0, sizeof(float), m->st));
-        OKR(egr_absmax(w.w, w.numel, m->d_wmax, m->st));
-        EGR_HIP(hipMemcpyAsync(&wmax, m->d_wmax, sizeof(float), hipMemcpyDeviceToHost, m->st));
-        EGR_HIP(hipStreamSynchronize(m->st));
-        w.w_scale = h2_scale_for(wmax, 13);
-        void* p2 = nullptr;
-        OKR(dev_alloc(m, (size_t)ns * 2 * w.Cout * 16 * 2, &p2));
-        OKR(egr_split2h_pack(w.w, p2, ns, w.Cout, w.w_scale, m->st));
-        w.w2 = p2;
+        OKR(dev_alloc(m, w.term_bytes(2), &w.w2));
         ++m->h2_nweights;
     }
-    return EGR_OK;
+    return egr::split_weight(w, m->d_wmax, m->st);
 }
 
 // src in torch layout on the device; layout as in egr_pack_weight; registers key with logical (KH, KW, Cin, N)
 int add_packed(M* m, const std::string& key, const float* src, int layout, int K, int N, int Ci, int Co, int KH, int KW, int logical_kh,
                int logical_kw, int logical_cin) {
     Wt w;
-    const int64_t slabs = (K + 15) / 16;
-    w.numel = slabs * N * 16;
-    void* p = nullptr;
-    OKR(dev_alloc(m, (size_t)w.numel * sizeof(float), &p));
-    w.w = (float*)p;
+    egr::weight_shape(w, K, N);
+    OKR(dev_alloc(m, w.pack_bytes(), (void**)&w.w));
     OKR(egr_pack_weight(src, w.w, layout, K, N, Ci, Co, KH, KW, m->st));
     w.KH = logical_kh; w.KW = logical_kw; w.Cin = logical_cin; w.Cout = N;
     if (logical_cin % 16 == 0) {
@@ -410,7 +379,7 @@ int add_winograd(M* m, const std::string& key, const egr_tensor_desc& t, const d
         Wt w;
         w.numel = (int64_t)np * np * zf;
         w.zfloats = zf;
-        w.KH = w.KW = 1; w.Cin = Ci; w.Cout = Co;
+        w.KH = w.KW = 1; w.Cin = w.K = Ci; w.Cout = w.N = Co;
         float* pk = nullptr;
         if (hipMalloc((void**)&pk, (size_t)w.numel * sizeof(float)) != hipSuccess) { set_error("hipMalloc(Winograd U) failed"); return EGR_ERR_ALLOC; }
         int rc = egr_winograd_pack_u(t.data, pk, pass == 0 ? G2_dev : G4_dev, np, Co, Ci, m->st);
@@ -542,14 +511,10 @@ int row_amax_of(M* m, const float* x, int64_t numel, int nz, int64_t zx, unsigne
 // y_rs (optional): the launch leaves the per-row maxima of y there (fp16 scheme, nz == 1; a fresh slice is taken when *y_rs is null
 // -- the four phase launches of an up-sampling convolution share one)
 int s3_launch(M* m, const Wt* w, const std::string& key, ConvCall& c, int64_t x_numel, unsigned** x_rs, int64_t zfloats, ConvChoice* ran, unsigned** y_rs = nullptr) {
-    if (!s3_of(m, w, c.Cin, c.x)) {
-        EGR_CHECK(w->w != nullptr, EGR_ERR_ARG, "FlashSR: no fp32 pack for %s", key.c_str());
-        c.w = w->w; c.zw = zfloats;
-        return egr::conv_call(c, m->st, ran);
-    }
-    const bool use = m->h2_on() && w->w2 && ((int64_t)c.B * c.OH * c.OW) % m->R == 0;
-    c.w3 = use ? w->w2 : w->w3;
-    c.zw = zfloats * (use ? 2 : 3) / 8;
+    const bool split = s3_of(m, w, c.Cin, c.x) != nullptr;
+    EGR_CHECK(split || w->w != nullptr, EGR_ERR_ARG, "FlashSR: no fp32 pack for %s", key.c_str());
+    const bool use = split && m->h2_on() && w->w2 && ((int64_t)c.B * c.OH * c.OW) % m->R == 0;
+    c.zw = split ? zfloats * (use ? 2 : 3) / 8 : zfloats;
     if (use) {
         OKR(row_amax_of(m, c.x, c.nz > 1 ? x_numel / c.nz : x_numel, c.nz, c.zx, x_rs));
         if (y_rs && c.nz == 1 && m->out_amax_on) {
@@ -557,8 +522,8 @@ int s3_launch(M* m, const Wt* w, const std::string& key, ConvCall& c, int64_t x_
             if (!*y_rs) return EGR_ERR_ALLOC;
             c.out_amax = (float*)*y_rs;
         }
-        c.sch = 1; c.w_scale = w->w_scale; c.row_amax = (const float*)*x_rs; c.batch_rows = m->R;
     }
+    egr::set_weight(c, *w, use ? *x_rs : nullptr, m->R, split);
     return egr::conv_call(c, m->st, ran);
 }
 
@@ -789,9 +754,10 @@ int gn_conv3(M* m, Ten& y, const Ten& x, const std::string& norm_key, float eps,
             }
             ProfScope ps(m);
             ConvCall c; ConvChoice ran;
-            c.x = x.p; c.w3 = wd->w2; c.bias = bt; c.res = res; c.y = y.p; c.gn_scale = sc.p; c.gn_shift = sh.p; c.gn_silu = 1;
+            c.x = x.p; c.bias = bt; c.res = res; c.y = y.p; c.gn_scale = sc.p; c.gn_shift = sh.p; c.gn_silu = 1;
             c.B = B; c.H = c.OH = c.OHF = H; c.W = c.OW = c.OWF = W; c.Cin = Cin; c.Cout = wd->Cout; c.KH = c.KW = 3; c.pad_t = c.pad_l = 1;
-            c.sch = 1; c.w_scale = wd->w_scale; c.row_amax = (const float*)bound; c.batch_rows = B; c.out_amax = (float*)y.rs; c.gn_part = gpart;
+            egr::set_weight(c, *wd, bound, B);
+            c.out_amax = (float*)y.rs; c.gn_part = gpart;
             OKR(egr::conv_call(c, m->st, &ran));
             if (ps.on) ps.end(egr::conv_choice_name(ran), fl, conv_key);
             if (m->count_flops) m->flops += fl;

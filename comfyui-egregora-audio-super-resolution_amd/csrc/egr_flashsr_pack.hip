@@ -1,7 +1,11 @@
-// Weight repacking for the FlashSR engine (gfx950): torch-layout fp32 tensors -> the layouts the contraction kernels read.
-// Done once per model build, on the device.  Shared by the C-ABI model handle (egr_flashsr.cpp) and the Python graph driver
-// (flashsr_engine.py) so that both executors hold bit-identical operands.
-#include "egr_common.h"
+// Weight repacking (gfx950): torch-layout fp32 tensors -> the layouts the contraction kernels read.  Done once per model build, on the
+// device.  Shared by the model handles behind the C ABI (egr_flashsr.cpp, egr_dac.hip: through prepare_weight, egr_weight_prep.h, whose
+// body is at the end of this file) and the Python graph driver (flashsr_engine.py), so that every executor holds bit-identical
+// operands.  The phase and Winograd packs are FlashSR's alone.
+#include <algorithm>
+#include <cmath>
+
+#include "egr_weight_prep.h"
 
 namespace egr {
 
@@ -124,4 +128,31 @@ extern "C" int egr_winograd_pack_u(const float* w_oihw, float* dst, const double
         hipLaunchKernelGGL(k_winograd_u<6>, dim3(grid_for(pairs)), dim3(256), 0, (hipStream_t)stream, w_oihw, dst, G_dev, Co, Ci, zfloats);
     EGR_HIP(hipGetLastError());
     return EGR_OK;
+}
+
+// ---- egr_weight_prep.h
+float egr::h2_scale_for(float amax, int e) {
+    if (!(amax > 0.f) || !std::isfinite(amax)) return 1.f;
+    int ex = 0;
+    const float fr = frexpf(amax, &ex);              // amax = fr 2^ex, fr in [0.5, 1)
+    if (fr == 0.5f) --ex;                            // exact power of two: 2^(ex-1)
+    return ldexpf(1.f, std::max(-60, std::min(60, e - ex)));
+}
+
+int egr::split_weight(PreparedWeight& w, float* amax_slot, hipStream_t st) {
+    int rc = EGR_OK;
+    if (w.w3 && (rc = egr_split3_pack(w.w, w.w3, w.slabs(), w.N, st))) return rc;
+    if (!w.w2) return EGR_OK;
+    float amax = 0.f;
+    EGR_HIP(hipMemsetAsync(amax_slot, 0, sizeof(float), st));
+    if ((rc = egr_absmax(w.w, w.numel, amax_slot, st))) return rc;
+    EGR_HIP(hipMemcpyAsync(&amax, amax_slot, sizeof(float), hipMemcpyDeviceToHost, st));
+    EGR_HIP(hipStreamSynchronize(st));
+    w.w_scale = h2_scale_for(amax, 13);
+    return egr_split2h_pack(w.w, w.w2, w.slabs(), w.N, w.w_scale, st);
+}
+
+int egr::prepare_weight(const float* src, int layout, int Ci, int Co, int KH, int KW, PreparedWeight& w, float* amax_slot, hipStream_t st) {
+    const int rc = egr_pack_weight(src, w.w, layout, w.K, w.N, Ci, Co, KH, KW, st);
+    return rc ? rc : split_weight(w, amax_slot, st);
 }

@@ -1,0 +1,60 @@
+// What the model handles that live inside the library (DfnCore, Dac) share around a call: the kept workspace, the device checks and the
+// stage copy-out.  WPE (caller-owned workspace) and the Fat-Llama plan (owns its buffers) have lifetimes of their own.
+#pragma once
+#include "egr_common.h"
+
+namespace egr {
+
+#define EGR_TRY(x) do { int rc__ = (x); if (rc__ != EGR_OK) return rc__; } while (0)
+
+// Selects `device` for a scope (create, upload, destroy) and makes the previous device current again; ok: both calls succeeded.
+struct DeviceScope {
+    int prev = 0;
+    bool ok;
+    explicit DeviceScope(int device) { ok = hipGetDevice(&prev) == hipSuccess && hipSetDevice(device) == hipSuccess; }
+    ~DeviceScope() { (void)hipSetDevice(prev); }
+    DeviceScope(const DeviceScope&) = delete;
+    DeviceScope& operator=(const DeviceScope&) = delete;
+};
+
+// A call works on the handle's device: the caller makes it current.
+inline int check_current_device(const char* who, int device) {
+    int cur = -1;
+    EGR_HIP(hipGetDevice(&cur));
+    EGR_CHECK(cur == device, EGR_ERR_ARG, "%s: handle belongs to device %d, current device is %d", who, device, cur);
+    return EGR_OK;
+}
+
+// The workspace a handle keeps between calls: grow-only, stream-ordered (nothing synchronises).
+struct Workspace {
+    void* p = nullptr;
+    size_t bytes = 0;
+    int grow(size_t need, hipStream_t st) {
+        if (need <= bytes) return EGR_OK;
+        if (p) EGR_HIP(hipFreeAsync(p, st));
+        p = nullptr;
+        bytes = 0;
+        EGR_HIP(hipMallocAsync(&p, need, st));
+        bytes = need;
+        return EGR_OK;
+    }
+    // at destroy, on the handle's device: hipMallocAsync memory is returned stream-ordered, then waited for (not a pipeline call)
+    void release() {
+        if (!p) return;
+        (void)hipFreeAsync(p, nullptr);
+        (void)hipDeviceSynchronize();
+        p = nullptr;
+        bytes = 0;
+    }
+};
+
+// The stage read of the C ABI: *count = n always; a null dst only asks for it; else n floats of src go to dst (device to device, on `stream`).
+inline int stage_copy_out(const char* who, const float* src, int64_t n, float* dst, int64_t capacity, int64_t* count, void* stream) {
+    *count = n;
+    if (!dst) return EGR_OK;
+    EGR_CHECK(capacity >= n, EGR_ERR_ARG, "%s: %lld floats do not fit a capacity of %lld", who, (long long)n, (long long)capacity);
+    EGR_HIP(hipMemcpyAsync(dst, src, sizeof(float) * (size_t)n, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return EGR_OK;
+}
+
+}  // namespace egr

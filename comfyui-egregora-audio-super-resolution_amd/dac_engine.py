@@ -160,12 +160,7 @@ class DacEngine:
     def stage(self, name: str, index: int = 0) -> torch.Tensor:
         """An intermediate of the last call as a flat float32 device tensor: "enc" / "dec" index 0 = the input convolution, then the
         blocks ("enc" n_enc + 1: the encoder output), "vq_in" i: the residual entering quantiser stage i (after keep_stages()); channels-last."""
-        f, sid = native.lib().egr_dac_stage, native.DAC_STAGE[name]
-        n = C.c_int64()
-        native.check(f(self.h, sid, int(index), None, 0, C.byref(n), native.stream_ptr()), "egr_dac_stage")
-        out = torch.empty(n.value, dtype=torch.float32, device=f"cuda:{self.device}")
-        native.check(f(self.h, sid, int(index), native.ptr(out), n.value, C.byref(n), native.stream_ptr()), "egr_dac_stage")
-        return out
+        return native.read_stage(native.lib().egr_dac_stage, "egr_dac_stage", self.device, self.h, native.DAC_STAGE[name], int(index))
 
 
 def engine(path: Path, device: Optional[int] = None) -> DacEngine:

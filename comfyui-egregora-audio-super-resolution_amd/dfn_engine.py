@@ -204,13 +204,8 @@ class DfnEngine:
     def stage(self, name: str, layer: int = 0) -> torch.Tensor:
         """An intermediate of the last enhance call as a flat float32 device tensor (layouts: include/egregora_amd.h); the names in
         `indexed` take the GRU layer index."""
-        f, what = self._fn("stage"), f"{self.prefix}_stage"
         sid = self.stages[name] + (layer if name in self.indexed else 0)
-        n = C.c_int64()
-        native.check(f(self.h, sid, None, 0, C.byref(n), native.stream_ptr()), what)
-        out = torch.empty(n.value, dtype=torch.float32, device=f"cuda:{self.device}")
-        native.check(f(self.h, sid, native.ptr(out), n.value, C.byref(n), native.stream_ptr()), what)
-        return out
+        return native.read_stage(self._fn("stage"), f"{self.prefix}_stage", self.device, self.h, sid)
 
     def time_gru(self, layer: int = 0, channels: int = 2, steps: int = 20000) -> float:
         us = C.c_double()

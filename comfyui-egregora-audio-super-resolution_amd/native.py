@@ -337,3 +337,14 @@ def stream_ptr():
 
 def ptr(t):
     return C.c_void_p(t.data_ptr())
+
+
+def read_stage(f, what: str, device: int, *ident):
+    """The two-call stage read of a model handle: f(*ident, dst, capacity, count, stream) first reports the float count (null dst),
+    then copies into a fresh flat float32 tensor on `device`."""
+    import torch
+    n = C.c_int64()
+    check(f(*ident, None, 0, C.byref(n), stream_ptr()), what)
+    out = torch.empty(n.value, dtype=torch.float32, device=f"cuda:{device}")
+    check(f(*ident, ptr(out), n.value, C.byref(n), stream_ptr()), what)
+    return out

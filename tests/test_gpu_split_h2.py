@@ -37,7 +37,7 @@ def p(t):
 
 
 def scale_for(amax, e):
-    """csrc/egr_flashsr.cpp h2_scale_for: the power of two that brings amax into (2^(e-1), 2^e]."""
+    """csrc/egr_weight_prep.h h2_scale_for: the power of two that brings amax into (2^(e-1), 2^e]."""
     return 2.0 ** (e - math.ceil(math.log2(amax)))
 
 
@@ -69,6 +69,64 @@ def h2_pack(e, wp, Co):
     w2 = torch.empty(ns * 2 * Co * 16, dtype=torch.float16, device="cuda")
     native.check(L.egr_split2h_pack(p(wp), p(w2), ns, Co, ws, e._st()), "split2h")
     return w2, ws
+
+
+def pack_ref(w, layout):
+    """The index formulas of csrc/egr_flashsr_pack.hip restated: dst[s][n][j] = W2[16 s + j][n], zero beyond K.  Layout 0: torch Conv1d
+    [Co][Ci][k], k index = tap * Ci + ci, n = co.  Layout 1: torch ConvTranspose1d [Ci][Co][k], k index = ci, n = tap * Co + co."""
+    import numpy as np
+    if layout == 0:
+        Co, Ci, k = w.shape
+        K, N = k * Ci, Co
+        w2 = np.zeros((K, N), np.float32)
+        for co in range(Co):
+            for ci in range(Ci):
+                for t in range(k):
+                    w2[t * Ci + ci, co] = w[co, ci, t]
+    else:
+        Ci, Co, k = w.shape
+        K, N = Ci, k * Co
+        w2 = np.zeros((K, N), np.float32)
+        for ci in range(Ci):
+            for co in range(Co):
+                for t in range(k):
+                    w2[ci, t * Co + co] = w[ci, co, t]
+    ns = (K + 15) // 16
+    dst = np.zeros((ns, N, 16), np.float32)
+    for kk in range(K):
+        dst[kk // 16, :, kk % 16] = w2[kk]
+    return dst, K, N
+
+
+def test_pack_weight_layouts_and_the_exact_power_of_two_scale(pack):
+    """egr_pack_weight alone (every model handle prepares its contraction weights through it): layouts 0 and 1 equal the numpy
+    restatement of the header's index formulas exactly -- a Conv1d [5][3][7] (K = 21: two slabs, 11 zero columns in the second,
+    Co != Ci) and a ConvTranspose1d [24][5][4] (K = 24, N = 20, a slab boundary inside Ci).  A [16][16][1] weight whose largest
+    magnitude is exactly 0.5 goes pack -> egr_absmax -> scale_for and gets 2^14: the fr == 0.5 branch of h2_scale_for."""
+    import numpy as np
+    from egregora_amd import native
+    L = native.lib()
+    st = native.stream_ptr()
+    rng = np.random.default_rng(7)
+
+    def run(w, layout):
+        ref, K, N = pack_ref(w, layout)
+        Ci, Co = (w.shape[1], w.shape[0]) if layout == 0 else (w.shape[0], w.shape[1])
+        src = torch.from_numpy(w).cuda()
+        dst = torch.full(ref.shape, float("nan"), device="cuda")
+        native.check(L.egr_pack_weight(p(src), p(dst), layout, K, N, Ci, Co, 1, w.shape[2], st), "egr_pack_weight")
+        assert np.array_equal(dst.cpu().numpy(), ref)
+        return dst
+
+    run(rng.standard_normal((5, 3, 7)).astype(np.float32), 0)
+    run(rng.standard_normal((24, 5, 4)).astype(np.float32), 1)
+    w = rng.uniform(-0.49, 0.49, (16, 16, 1)).astype(np.float32)
+    w[11, 6, 0] = -0.5
+    dst = run(w, 0)
+    slot = torch.zeros(1, device="cuda")
+    native.check(L.egr_absmax(p(dst), dst.numel(), p(slot), st), "absmax")
+    assert float(slot.item()) == 0.5
+    assert scale_for(float(slot.item()), 13) == 2.0 ** 14
 
 
 CASES = [(2, 16, 12, 128, 128, 3), (1, 9, 7, 256, 96, 3), (3, 8, 8, 512, 40, 1), (2, 10, 6, 64, 200, 3),
