@@ -17,12 +17,19 @@ _SMALL = dict(encoder_dim=16, latent_dim=64, decoder_dim=64, n_codebooks=3, code
 # the smallest shapes at which each code path can still go wrong: S pads (1003 is no multiple of the hop 8), O has odd strides
 # (a transposed conv gives L s - 1), W runs the 44 kHz widths (up to 1536 channels) on 8 frames, G takes the general paths: no Cin
 # is a multiple of 16 (fp32 MFMA contractions, K tails), widths 6 / 10 / 5 are no multiple of 4 (the snake's scalar branch) and
-# codebook_dim is 5 (the quantiser's generic instantiation)
+# codebook_dim is 5 (the quantiser's generic instantiation).  T and C are the quantiser's limits: T's codebook (1024 x 16 floats) plus
+# eight frames of its 2048-wide latent is 197 KiB, so the quantiser takes four frames a workgroup (131.6 KiB), and codebook_dim 16
+# is two passes of its projection loop; C has fewer codes (20) than the 32 lanes of a frame, a ragged second projection pass
+# (codebook_dim 12), a latent narrower than 32 and no Cin that is a multiple of 16 but the decoder's first
 CONFIGS = {"S": dict(_SMALL, encoder_rates=[2, 4], decoder_rates=[4, 2]), "O": dict(_SMALL, encoder_rates=[2, 5], decoder_rates=[5, 2]),
            "W": dict(DEFAULT),
            "G": dict(encoder_dim=6, encoder_rates=[2, 3], latent_dim=20, decoder_dim=20, decoder_rates=[3, 2], n_codebooks=2, codebook_size=48,
-                     codebook_dim=5, sample_rate=44100)}
-LENGTHS = {"S": 1003, "O": 1003, "W": 4091, "G": 601}
+                     codebook_dim=5, sample_rate=44100),
+           "T": dict(encoder_dim=4, encoder_rates=[2], latent_dim=2048, decoder_dim=8, decoder_rates=[2], n_codebooks=2, codebook_size=1024,
+                     codebook_dim=16, sample_rate=44100),
+           "C": dict(encoder_dim=8, encoder_rates=[2, 2], latent_dim=24, decoder_dim=16, decoder_rates=[2, 2], n_codebooks=3, codebook_size=20,
+                     codebook_dim=12, sample_rate=44100)}
+LENGTHS = {"S": 1003, "O": 1003, "W": 4091, "G": 601, "T": 301, "C": 515}
 ROWS = 2
 DILATIONS = (1, 3, 9)
 UNIT_GAIN = 0.3          # row norm of a residual unit's k = 1 conv and of the quantiser's out_proj: keeps the sums from growing

@@ -1,7 +1,8 @@
 """Descript Audio Codec (SPEC.md 4e), everything that needs no device: opt-in registration and the node surface against fixture G17
 (captured from the reference by tests/golden/make_golden_dac.py), the exported symbols, the length rules (egr_dac_lengths, its Python
 twin and the restatement's shapes), the checkpoint loader (weight-norm fold, layer table from shapes, refusals), discovery order, the
-level of the synthetic models, and the tie statistics the GPU test's code comparison rests on."""
+level of the synthetic models, and the tie statistics the GPU tests' code comparisons rest on: for every input of
+tests/test_gpu_dac.py and tests/test_gpu_dac_configs.py, float64 alone stays inside the caps those tests apply."""
 import ctypes
 import json
 import os
@@ -74,7 +75,7 @@ def test_symbols_are_declared_exported_and_bound(pack):
     assert ctypes.sizeof(native.DacConfigC) == 4 * (4 + 8 + 2 + 8 + 4)
 
 
-@pytest.mark.parametrize("name", ["S", "O", "W", "G"])
+@pytest.mark.parametrize("name", ["S", "O", "W", "G", "T", "C"])
 def test_lengths_agree(pack, name):
     """DAC-P7: egr_dac_lengths == dac_engine.lengths == the restatement's shapes, at the hop's edges and at the test length."""
     from egregora_amd import dac_engine
@@ -106,7 +107,7 @@ def test_weight_norm_fold_equals_torch(pack):
         assert torch.equal(got, R.fold({"a.weight_v": v, "a.weight_g": gg}, "a"))
 
 
-@pytest.mark.parametrize("name", ["S", "O", "W", "G"])
+@pytest.mark.parametrize("name", ["S", "O", "W", "G", "T", "C"])
 def test_layer_table_from_shapes_and_pack(pack, tmp_path, name):
     from egregora_amd import dac_weights
     cfg, sd, n64, n32 = K.model(name)
@@ -188,7 +189,7 @@ def test_discover_order(pack, tmp_path, monkeypatch):
     assert dac_weights.discover("44khz") == env_dir / "weights_44khz_x.pth"
 
 
-@pytest.mark.parametrize("name", ["S", "O", "W", "G"])
+@pytest.mark.parametrize("name", ["S", "O", "W", "G", "T", "C"])
 def test_synthetic_models_keep_their_level(name):
     """Every stage's rms stays in [0.1, 10] in float64, so the relative gates of the GPU tests mean something; alpha in [0.5, 2]."""
     cfg, sd, n64, n32 = K.model(name)
@@ -207,7 +208,7 @@ def test_synthetic_models_keep_their_level(name):
         assert 0.1 <= R.rms(v["ze"]) <= 10 and 0.1 <= R.rms(v["z64"]) <= 10
 
 
-@pytest.mark.parametrize("name", ["S", "W", "G"])
+@pytest.mark.parametrize("name", ["S", "W", "G", "T", "C"])
 def test_tie_statistics(name):
     """What the GPU test's code comparison rests on: in float64 alone at most 5 % of the 2 000 frames have a stage whose best and
     second-best similarities lie within 1e-4, and tau (4 x the fp32 restatement's similarity error) is far below that."""
@@ -221,3 +222,102 @@ def test_tie_statistics(name):
     # lowest index wins ties: argmax of a row with two equal maxima
     s = torch.tensor([[0.1, 0.7, 0.7, 0.2]], dtype=torch.float64)
     assert int(torch.argmax(s, dim=-1)) == 1
+
+
+def _print_and_check_caps(label, marg, tau):
+    """tau and the share of frames left out at 2 tau, per row; the caps of the GPU tests (dac_check)."""
+    excluded = 1.0 - K.safe_frames(marg, 2 * tau).double().mean(dim=1)
+    print(f"{label}: tau {tau:.2e}, frames left out at 2 tau per row: {[f'{float(e):.3%}' for e in excluded]}, smallest margin {float(marg.min()):.2e}")
+    assert 0 < 2 * tau <= K.MARGIN_CAP
+    assert float(excluded.max()) <= K.MAX_EXCLUDED
+    return excluded
+
+
+@pytest.mark.parametrize("name", ["T", "S"])
+def test_tie_statistics_ragged_frame_count(name):
+    """The quantiser alone at 3 rows x 667 frames (2 001: the last workgroup has idle frames, a frame group straddles a row)."""
+    rows, frames = K.VQ_RAGGED
+    v = K.vq_case(name, rows, frames)
+    assert v["margins"].shape == (rows, K.model(name)[0]["n_codebooks"], frames)
+    _print_and_check_caps(f"{name} {rows} x {frames}", v["margins"], v["tau"])
+    excluded = 1.0 - float(K.safe_frames(v["margins"], K.MARGIN_CAP).double().mean())
+    print(f"  frames left out at 1e-4: {excluded:.3%}")
+    assert excluded <= K.MAX_EXCLUDED
+
+
+@pytest.mark.parametrize("name,n,rows,seed", K.edge_cases())
+def test_edge_lengths_have_no_near_tie(name, n, rows, seed):
+    """Below 20 frames the 5 % cap means no frame may be left out: at the chosen seed every float64 margin exceeds 2 tau, and the
+    fp32 restatement chooses float64's codes (so that its z is a yardstick on every frame).  A seed that fails is changed, not the cap."""
+    f = K.forward(name, n, rows, seed)
+    tau = K.e2e_tau(name, n, rows, seed)
+    marg = K.margins(f["sims64"])
+    excluded = _print_and_check_caps(f"{name} n={n} rows={rows} seed={seed} ({marg.shape[-1]} frames)", marg, tau)
+    assert marg.shape[-1] == -(-n // R.hop(K.model(name)[0]))
+    if marg.shape[-1] < 20:
+        assert float(excluded.max()) == 0.0 and bool((marg > 2 * tau).all())
+    assert float((f["codes32"] == f["codes64"]).all(dim=1).double().mean()) >= 1 - K.MAX_EXCLUDED
+
+
+def test_rows_at_two_levels():
+    """tests/test_gpu_dac_configs.py runs config S with row 1 at 2^-10 of row 0 and gates every row against its own float64 rms.
+    This pins, from the restatement alone, that each row stays inside the code caps, and what that test can see of a row maximum
+    taken from the other row.  The device brings each row of a two-fp16-term contraction into [2^14, 2^15) by a power of two from
+    the row's own maximum (egr_conv.h, h2_row_scale):
+      * the LOUD row split at the QUIET row's scale overflows fp16, and its dec0 fails the gate: that exchange is visible;
+      * the QUIET row split at the LOUD row's scale (hi = fp16(x / s), lo = fp16(x / s - hi), x' = (hi + lo) s) is off by at most
+        2^-25 s per element whatever the row's level, since fp16's subnormals reach 2^-24.  Through the float64 dec_in convolution
+        that is 1.9e-10 of dec0's rms at 2^-10 (fp32 itself: 5.3e-8), and it only falls relative to the bias that carries a quiet
+        row's dec0 as the level drops (9.9e-12 at 2^-16, 8.8e-12 at 2^-24): it passes `gate` at every level, so no level makes
+        that exchange visible, and none makes it matter.  The level stays at 2^-10."""
+    import math
+    name, n, rows, seed, levels = K.LEVELS_CASE
+    cfg, sd, n64, n32 = K.model(name)
+    f = K.forward(*K.LEVELS_CASE)
+    tau = K.e2e_tau(*K.LEVELS_CASE)
+    _print_and_check_caps(f"{name} rows at {levels}", K.margins(f["sims64"]), tau)
+    agree = (f["codes32"] == f["codes64"]).all(dim=1).double().mean(dim=1)
+    assert float(agree.min()) >= 1 - K.MAX_EXCLUDED
+    zin = f["zin"].double()
+    scale = lambda row: 2.0 ** (math.floor(math.log2(float(zin[row].abs().max()))) - 14)       # the row's maximum lands in [2^14, 2^15)
+
+    def dec0_with(row, s):
+        v = zin[row] / s
+        hi = v.half().double()
+        lo = (v - hi).half().double()
+        z2 = zin.clone()
+        z2[row] = (hi + lo) * s
+        with torch.no_grad():
+            return n64.conv(z2, "decoder.model.0", pad=3)[row]
+
+    r64, r32 = f["dec64"][0], f["dec32"][0]
+    loud = dec0_with(0, scale(1))
+    assert not bool(torch.isfinite(loud).all())
+    with pytest.raises(AssertionError):
+        K.gate("dec0 of the loud row split at the quiet row's scale", loud, r64[0], r32[0])
+    quiet = dec0_with(1, scale(0))
+    e, e32 = K.rel(quiet, r64[1]), K.rel(r32[1], r64[1])
+    print(f"  dec0 of the quiet row split at the loud row's scale: rms {e:.2e} (fp32 {e32:.2e})")
+    assert e <= 2.0 ** -25 * scale(0) * 7 * cfg["latent_dim"] / R.rms(r64[1])      # at most 2^-25 s an element, |w| <= 1, 7 x latent terms
+
+
+def test_tie_case_has_exact_ties_off_the_near_ties():
+    """The ties test of tests/test_gpu_dac_configs.py: with rows 17 = 3 and 19 = 0 in every codebook, float64 (lowest index) returns
+    3 or 0 on many frames that are no near-tie between different rows, and the caps hold."""
+    t = K.tie_case()
+    _print_and_check_caps("C with duplicated rows", t["margins"], t["tau"])
+    safe = K.safe_frames(t["margins"], 2 * t["tau"])
+    kept = [k for k, _ in K.TIE_PAIRS]
+    hit = torch.isin(t["codes64"], torch.tensor(kept)).any(dim=1) & safe
+    print(f"  frames off the near-ties on which float64 returns one of {kept}: {int(hit.sum())} of {hit.numel()}")
+    assert int(hit.sum()) >= 100 and not bool(torch.isin(t["codes64"], torch.tensor([d for _, d in K.TIE_PAIRS])).any())
+    for q in range(t["cfg"]["n_codebooks"]):
+        cb = t["sd"][f"quantizer.quantizers.{q}.codebook.weight"]
+        assert all(torch.equal(cb[k], cb[d]) for k, d in K.TIE_PAIRS)
+
+
+def test_reuse_lengths_are_distinct_workloads(pack):
+    from egregora_amd import dac_engine
+    cfg = K.model("S")[0]
+    long, short = (dac_engine.lengths(cfg, n) for n in K.REUSE_LENGTHS)
+    assert long[1] > 500 and short == (16, 2, 16)

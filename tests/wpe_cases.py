@@ -17,6 +17,12 @@ CASES = {
     "C": dict(channels=2, n=32000, n_fft=256, hop=64, taps=10, delay=3, iterations=3, seed=103, cls="hard"),
     "D": dict(channels=2, n=48000, n_fft=256, hop=64, taps=32, delay=1, iterations=2, seed=104, cls="hard"),
     "E": dict(channels=2, n=64000, n_fft=768, hop=192, taps=10, delay=3, iterations=3, seed=105, cls="hard"),
+    # wide arrays on a short transform (33 bins, 753 / 503 frames), for tests/test_gpu_wpe_configs.py: F and G need two 4 x 4 blocks
+    # per thread, G, H and L the 32-frame tile of more than 32 channels, L the last delay whose tile still fits in LDS
+    "F": dict(channels=32, n=12000, n_fft=64, hop=16, taps=2, delay=1, iterations=2, seed=106, cls="well"),
+    "G": dict(channels=64, n=12000, n_fft=64, hop=16, taps=1, delay=2, iterations=2, seed=107, cls="well"),
+    "H": dict(channels=40, n=8000, n_fft=64, hop=16, taps=1, delay=1, iterations=2, seed=108, cls="well"),
+    "L": dict(channels=64, n=12000, n_fft=64, hop=16, taps=1, delay=122, iterations=2, seed=111, cls="well"),
 }
 
 

@@ -3,7 +3,8 @@
 //   c++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all tools/wpe_host_check.cpp -o wpe_host_check
 // Every tile is a heap block of exactly the kernel's size, so an index outside it is reported; block ownership is checked to cover
 // the needed part of [Ytilde ; Y] diag(inv) Ytilde^H exactly once.  Shapes: the frame counts, channels, taps and delays of the
-// cases A-E of tests/wpe_cases.py, an input with fewer frames than K, and a two-blocks-per-thread shape.  Exit status 0 = all pass.
+// cases A-E of tests/wpe_cases.py, an input with fewer frames than K, a two-blocks-per-thread shape, and the wide cases F, H, L
+// (32 channels x 2 taps; 40 channels on the 32-frame tile; 64 channels at delay 122, the longest history that fits).  Exit status 0 = all pass.
 #include <math.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -142,6 +143,7 @@ int main() {
     const Shape shapes[] = {
         {"A", 1, 253, 3, 1}, {"B", 3, 503, 5, 2}, {"C", 2, 503, 10, 3}, {"D", 2, 753, 32, 1}, {"E", 2, 337, 10, 3},
         {"frames<K", 1, 8, 10, 3}, {"one-frame", 2, 1, 3, 1}, {"K=15", 5, 130, 3, 16}, {"two-blocks", 64, 70, 1, 1}, {"K=63", 21, 65, 3, 2},
+        {"F", 32, 753, 2, 1}, {"H", 40, 503, 1, 1}, {"L", 64, 753, 1, 122},
     };
     int bad = 0;
     for (const Shape& s : shapes) bad += run(s);
