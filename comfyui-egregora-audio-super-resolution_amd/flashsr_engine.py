@@ -196,10 +196,11 @@ class FlashSREngine:
         native.check(self.L.egr_flashsr_split_info(C.c_void_p(self.handle), C.byref(en), C.byref(nw), C.byref(calls)), "egr_flashsr_split_info")
         return dict(enabled=bool(en.value), weights=nw.value, calls=calls.value)
 
-    def c_profile(self, fn) -> dict:
-        """{kernel instantiation: (launches, flops, ms)} of the MFMA contraction launches the handle made while fn() ran."""
+    def c_profile(self, fn, ops: bool = False) -> dict:
+        """{kernel instantiation: (launches, flops, ms)} of the MFMA contraction launches the handle made while fn() ran; ops=True adds
+        the graph's other operator launches under the names of their entry points (egr_flashsr_set_profiling level 2)."""
         h = C.c_void_p(self.handle)
-        native.check(self.L.egr_flashsr_set_profiling(h, 1), "egr_flashsr_set_profiling")
+        native.check(self.L.egr_flashsr_set_profiling(h, 2 if ops else 1), "egr_flashsr_set_profiling")
         fn()
         n = C.c_int()
         native.check(self.L.egr_flashsr_profile(h, 0, None, 0, None, None, None, C.byref(n)), "egr_flashsr_profile")

@@ -673,7 +673,10 @@ int egr_flashsr_split_info(egr_flashsr* h, int* enabled, int* weights, int64_t* 
  * verifies to sit on other hardware queues than the caller's; fork / join by events, so the call still looks single-stream. */
 int egr_flashsr_set_streams(egr_flashsr* h, int max_groups, int min_group_rows);
 /* HIP-event timing of the MFMA contraction launches, aggregated per kernel instantiation (bench.py's roofline): switch on, run,
- * then read entry `index` (kind_buf NULL: only *count).  egr_flashsr_flop_count: executed dense flops of one pass over `rows`. */
+ * then read entry `index` (kind_buf NULL: only *count).  enable = 2 also records the graph's other operator launches (transforms,
+ * GroupNorm statistics, norms, gathers, row-maxima passes), each under the name of the entry point of this header that the walk
+ * called, with zero flops: which of them a creation flag selected (tests/test_gpu_flashsr_flags.py).
+ * egr_flashsr_flop_count: executed dense flops of one pass over `rows`. */
 int egr_flashsr_set_profiling(egr_flashsr* h, int enable);
 int egr_flashsr_profile(egr_flashsr* h, int index, char* kind_buf, size_t buflen, int64_t* launches, double* flops, double* ms, int* count);
 int egr_flashsr_flop_count(egr_flashsr* h, int rows, double* flops, void* stream);
