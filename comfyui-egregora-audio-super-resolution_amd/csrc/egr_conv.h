@@ -157,27 +157,35 @@ __device__ __forceinline__ void conv_epilogue_rows(const ConvP& p, f32x16 (&acc)
 }
 
 // Accumulator layout of every 32x32 MFMA tile: register r of lane l holds row (r&3) + 8*(r>>2) + 4*(l>>5), column l&31.
+// Plain tile store: the accumulators times out_scale (and, with OST, the row's entry of os_tab) at [M][Cout] of y -- the raw partial
+// tiles of split-K, and the tiles of z-streamed GEMMs, which have no bias / residual / activation / placement
+template <int TM, int TN, bool OST = false>
+__device__ __forceinline__ void store_tile_plain(const ConvP& p, f32x16 (&acc)[TM][TN], float* __restrict__ y, int m0, int n0, int wm0, int wn0,
+                                                 const float* os_tab = nullptr) {
+    const int lane = threadIdx.x & 63, col = lane & 31, rhalf = lane >> 5;
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int m = m0 + wm0 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * rhalf;
+            if (m < p.M) {
+                float* row = y + (size_t)m * p.Cout + n0 + wn0 + col;
+                const float os = OST ? os_tab[m - m0] : 1.0f;
+#pragma unroll
+                for (int j = 0; j < TN; ++j)
+                    if (n0 + wn0 + j * 32 + col < p.Cout) row[j * 32] = (OST ? acc[i][j][r] * os : acc[i][j][r]) * p.out_scale;
+            }
+        }
+}
+
 // Writes raw split-K partials, or bias + per-row bias + residual + activation at the (possibly strided) output place.
 template <int TM, int TN, bool OST = false>
 __device__ __forceinline__ void conv_epilogue(const ConvP& p, f32x16 (&acc)[TM][TN], int m0, int n0, int wm0, int wn0,
                                               float* yb = nullptr, const float* os_tab = nullptr, unsigned* om_tab = nullptr) {
     float* const yout = yb ? yb : p.y;
-    const int lane = threadIdx.x & 63, col = lane & 31, rhalf = lane >> 5;
+    const int lane = threadIdx.x & 63, col = lane & 31;
     if (p.ksplit > 1) {        // raw partial sums; bias / residual / activation are applied by k_splitk_reduce
-        float* wz = p.ws + (size_t)blockIdx.z * p.M * p.Cout;
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int m = m0 + wm0 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * rhalf;
-                if (m < p.M) {
-                    float* row = wz + (size_t)m * p.Cout + n0 + wn0 + col;
-                    const float os = OST ? os_tab[m - m0] : 1.0f;
-#pragma unroll
-                    for (int j = 0; j < TN; ++j)
-                        if (n0 + wn0 + j * 32 + col < p.Cout) row[j * 32] = (OST ? acc[i][j][r] * os : acc[i][j][r]) * p.out_scale;
-                }
-            }
+        store_tile_plain<TM, TN, OST>(p, acc, p.ws + (size_t)blockIdx.z * p.M * p.Cout, m0, n0, wm0, wn0, os_tab);
         return;
     }
     float bv[TN];

@@ -72,12 +72,7 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_isp(ConvP p) {
     }
 
     f32x16 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    zero_acc(acc);
 
     const size_t b_slab = (size_t)p.Cout * 2 * NP;     // 16-byte chunks of one 16-k slab of the weight pack
     const int cpt = p.Cin / 16;                  // slabs per tap in the weight pack
@@ -110,7 +105,7 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_isp(ConvP p) {
         const int iy = y0 - 1 + pr, ix = x0 - 1 + pc;                                                                \
         OK = e < RMAX * NCH && (unsigned)iy < (unsigned)p.H && (unsigned)ix < (unsigned)p.W;                        \
         OFF = OK ? (iy * p.W + ix) * p.Cin + hch * 8 : hch * 8;                                                      \
-        SLOT = e < RMAX * NCH ? r * NCH + (hch ^ ((r / (16 / NCH)) & (NCH - 1))) : RMAX * NCH + (tid & 7);                \
+        SLOT = e < RMAX * NCH ? S3_HALO_SLOT(NCH, r, hch) : RMAX * NCH + (tid & 7);                                 \
     }
     C3_HSETUP(0, hoff0, hslot0, hok0)
     C3_HSETUP(1, hoff1, hslot1, hok1)
@@ -164,7 +159,7 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_isp(ConvP p) {
 #pragma unroll
         for (int i = 0; i < TM; ++i) {
             const int r = ((wm0 >> 5) + i + ky) * PW + li + kx;       // sub-tile (wm0 / 32 + i) = image row y0 + that
-            const int slot = r * NCH + (ch ^ ((r / (16 / NCH)) & (NCH - 1)));
+            const int slot = S3_HALO_SLOT(NCH, r, ch);
 #pragma unroll
             for (int q = 0; q < NP; ++q) aq[i][q] = As[ab][q][slot];
         }
@@ -175,13 +170,7 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_isp(ConvP p) {
         if (S == 8) halo_finish(hu2, hv2, hok2, hslot2, cc + 1, ab ^ 1);
         if (S == 10) halo_finish(hu3, hv3, hok3, hslot3, cc + 1, ab ^ 1);
         // weights as the first operand: transposed accumulators, 16-byte stores (conv_epilogue_t)
-#define C3_MMA(QA, QB)                                                                                                   \
-    _Pragma("unroll") for (int i = 0; i < TM; ++i) _Pragma("unroll") for (int j = 0; j < TN; ++j) acc[i][j] =            \
-        __builtin_amdgcn_mfma_f32_32x32x16_f16(as_hf(bq[j][QB]), as_hf(aq[i][QA]), acc[i][j], 0, 0, 0);
-        C3_MMA(1, 0)
-        C3_MMA(0, 1)
-        C3_MMA(0, 0)
-#undef C3_MMA
+        mma_terms<1, true, TM, TN>(aq, bq, acc);
         if (S == 4 || S == 6 || S == 8 || S == 10) {
             // the item's ~70 VALU / transcendental instructions go BETWEEN the slab's MFMAs, six per MFMA (the machine scheduler
             // otherwise issues them as one block in front: ~350 cycles in which this wave feeds nothing to the matrix pipe)

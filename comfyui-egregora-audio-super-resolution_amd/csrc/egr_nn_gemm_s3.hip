@@ -12,8 +12,7 @@
 //
 // Weights are split once on the device (egr_split3_pack -> [slab][3][Cout][16] bf16); activations are split by the
 // loader on their way into LDS (v_cvt_pk_bf16_f32 + two subtractions per term).  LDS tiles are per plane
-// [row][2 chunks of 8 bf16] with the chunk index XOR-ed by bit 3 of the row, which makes both the loader's
-// ds_write_b128 and the MFMA operand ds_read_b128 (lane l: row l&31, k-half l>>5) conflict-free at a 32-byte pitch.
+// [row][2 chunks of 8 bf16], swizzled by S3_TILE_SLOT; the partial products are issued by mma_terms (both in egr_s3_split.h).
 #include <stdlib.h>
 #include <string.h>
 
@@ -51,7 +50,7 @@ __global__ __launch_bounds__(256) void k_absmax(const float* __restrict__ x, lon
         m = fmaxf(fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))), m);
     }
     if (blockIdx.x == 0 && threadIdx.x < (n & 3)) m = fmaxf(m, fabsf(x[(n4 << 2) + threadIdx.x]));
-    amax_commit(slot, m);
+    row_amax_commit(slot, m);
 }
 
 // out[r] (bits of a non-negative float, zeroed by the caller) raised to max |x| over row r of x: nz segments of `per_row` floats
@@ -75,7 +74,7 @@ __global__ __launch_bounds__(256) void k_absmax_rows(const float* __restrict__ x
         m = fmaxf(fmaxf(fmaxf(fabsf(a.x), fabsf(a.y)), fmaxf(fabsf(a.z), fabsf(a.w))), m);
     }
     if (blockIdx.x == 0 && threadIdx.x < (per_row & 3)) m = fmaxf(m, fabsf(xr[(n4 << 2) + threadIdx.x]));
-    amax_commit(out + (size_t)blockIdx.y * EGR_ROW_AMAX_STRIDE, m);
+    row_amax_commit(out + (size_t)blockIdx.y * EGR_ROW_AMAX_STRIDE, m);
 }
 
 // the same for rows that are not 16-byte aligned (element loads)
@@ -83,7 +82,7 @@ __global__ __launch_bounds__(256) void k_absmax_rows_scalar(const float* __restr
     const float* xr = x + (size_t)blockIdx.z * zx + (size_t)blockIdx.y * per_row;
     float m = 0.f;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < per_row; i += (long long)gridDim.x * blockDim.x) m = fmaxf(m, fabsf(xr[i]));
-    amax_commit(out + (size_t)blockIdx.y * EGR_ROW_AMAX_STRIDE, m);
+    row_amax_commit(out + (size_t)blockIdx.y * EGR_ROW_AMAX_STRIDE, m);
 }
 
 __global__ __launch_bounds__(256) void k_split3_pack(const float* __restrict__ w, uint4* __restrict__ w3, long long nslabs,
@@ -103,26 +102,6 @@ __global__ __launch_bounds__(256) void k_split3_pack(const float* __restrict__ w
         dst[(size_t)Cout * 2] = q1;
         dst[(size_t)Cout * 4] = q2;
     }
-}
-
-// plain tile store (z-streamed GEMMs have no bias / residual / activation / placement)
-template <int TM, int TN, bool OST = false>
-__device__ __forceinline__ void store_tile_plain(f32x16 (&acc)[TM][TN], float* __restrict__ y, int M, int Cout, int m0, int n0,
-                                                 int wm0, int wn0, float os_u, const float* os_tab = nullptr) {
-    const int lane = threadIdx.x & 63, col = lane & 31, rhalf = lane >> 5;
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int m = m0 + wm0 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * rhalf;
-            if (m < M) {
-                float* row = y + (size_t)m * Cout + n0 + wn0 + col;
-                const float os = OST ? os_tab[m - m0] * os_u : os_u;
-#pragma unroll
-                for (int j = 0; j < TN; ++j)
-                    if (n0 + wn0 + j * 32 + col < Cout) row[j * 32] = acc[i][j][r] * os;
-            }
-        }
 }
 
 template <int BM, int BN, int PF, bool ZS = false, int SCH = 0>
@@ -156,12 +135,7 @@ __global__ __launch_bounds__(256, 2) void k_conv_s3(ConvP p) {
     }
 
     f32x16 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    zero_acc(acc);
 
     const int ktiles_all = p.K / S3_BK;
     const int kt_begin = p.ksplit > 1 ? blockIdx.z * p.kt_per : 0;
@@ -229,7 +203,7 @@ __global__ __launch_bounds__(256, 2) void k_conv_s3(ConvP p) {
         }
     };
     set_tap(tap);
-    const int a_slot = ar * 2 + (ah ^ ((ar >> 3) & 1));          // row ar + 128 lands 256 slots further
+    const int a_slot = S3_TILE_SLOT(ar, ah);                      // row ar + 128 lands 256 slots further
 
     // ---- B: 2*NP*BN 16-byte chunks per slab (NP planes x BN channels x 2 halves), up to 6 per thread ----
     constexpr int NBQ = 2 * NP * BN;
@@ -242,7 +216,7 @@ __global__ __launch_bounds__(256, 2) void k_conv_s3(ConvP p) {
         const int e = tid + 256 * (I);                                                                               \
         const int plane = e / (2 * BN), rem = e - plane * 2 * BN, nl = rem >> 1, half = rem & 1;                     \
         const bool ok = e < NBQ && n0 + nl < p.Cout;                                                                 \
-        SLOT = plane * (BN * 2) + nl * 2 + (half ^ ((nl >> 3) & 1));                                                 \
+        SLOT = plane * (BN * 2) + S3_TILE_SLOT(nl, half);                                                            \
         PTR = ok ? p.w3 + (size_t)kt_begin * b_slab + ((size_t)plane * p.Cout + n0 + nl) * 2 + half                  \
                  : (const uint4*)p.zeros;                                                                            \
         STEP = ok ? (unsigned)b_slab : 0u;                                                                                    \
@@ -314,7 +288,7 @@ __global__ __launch_bounds__(256, 2) void k_conv_s3(ConvP p) {
 
     // operand fetch: lane (li = lane&31, lk = lane>>5) reads chunk lk of row li (+32 i) — k 0..7 on lanes 0-31, 8..15 on 32-63
     const int li = lane & 31, lk = lane >> 5;
-    const int o_slot = li * 2 + (lk ^ ((li >> 3) & 1));
+    const int o_slot = S3_TILE_SLOT(li, lk);
 
     // one slab: MFMAs on LDS buffer `cur`; tile kt+1 (staged in SN) -> LDS buffer cur^1; tile kt+1+PF -> SN
     // FULL: a middle slab (tile kt+1 is stored, tile kt+1+PF is loaded, unconditionally): its body up to the pointer
@@ -349,27 +323,7 @@ __global__ __launch_bounds__(256, 2) void k_conv_s3(ConvP p) {
                     // at 128 x 256) and stay as they were
                     if constexpr (SCH == 1) __builtin_amdgcn_sched_barrier(0);
                 }
-                // SCH 0: the six bf16 products term by term over the sub-tiles (smallest terms first); SCH 1: three f16 products
-                if constexpr (SCH == 0) {
-#define S3_MMA(QA, QB)                                                                                                   \
-    _Pragma("unroll") for (int i = 0; i < TH; ++i) _Pragma("unroll") for (int j = 0; j < TNH; ++j) acc[i0 + i][j0 + j] =  \
-        __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf(a[i][QA]), as_bf(b[j][QB]), acc[i0 + i][j0 + j], 0, 0, 0);
-                    S3_MMA(2, 0)
-                    S3_MMA(0, 2)
-                    S3_MMA(1, 1)
-                    S3_MMA(1, 0)
-                    S3_MMA(0, 1)
-                    S3_MMA(0, 0)
-#undef S3_MMA
-                } else {
-#define S3_MMA(QA, QB)                                                                                                   \
-    _Pragma("unroll") for (int i = 0; i < TH; ++i) _Pragma("unroll") for (int j = 0; j < TNH; ++j) acc[i0 + i][j0 + j] =  \
-        __builtin_amdgcn_mfma_f32_32x32x16_f16(as_hf(a[i][QA]), as_hf(b[j][QB]), acc[i0 + i][j0 + j], 0, 0, 0);
-                    S3_MMA(1, 0)
-                    S3_MMA(0, 1)
-                    S3_MMA(0, 0)
-#undef S3_MMA
-                }
+                mma_terms<SCH, false, TH, TNH>(a, b, acc, i0, j0);
             }
         }
         if (FULL) load_tile_advance();
@@ -377,13 +331,8 @@ __global__ __launch_bounds__(256, 2) void k_conv_s3(ConvP p) {
             const int done = kt + 1;
             const int zl = done / ktiles_all;
             if (done - zl * ktiles_all == 0) {
-                store_tile_plain<TM, TN, SCH == 1>(acc, p.y + (size_t)(zl - 1) * p.zy, p.M, p.Cout, m0, n0, wm0, wn0, p.out_scale, os_tab);
-#pragma unroll
-                for (int i = 0; i < TM; ++i)
-#pragma unroll
-                    for (int j = 0; j < TN; ++j)
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+                store_tile_plain<TM, TN, SCH == 1>(p, acc, p.y + (size_t)(zl - 1) * p.zy, m0, n0, wm0, wn0, os_tab);
+                zero_acc(acc);
             }
         }
         __syncthreads();
@@ -475,12 +424,9 @@ __global__ __launch_bounds__(256, 2) void k_conv_s3(ConvP p) {
 #pragma unroll
                     for (int q = 0; q < 2; ++q) b[(j + 1) & 1][q] = Bs[cur][q][(wn0 + (j + 1) * 32) * 2 + o_slot];
                 }
-#pragma unroll
-                for (int i = 0; i < TM; ++i) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(as_hf(b[j & 1][0]), as_hf(a[i][1]), acc[i][j], 0, 0, 0);
-#pragma unroll
-                for (int i = 0; i < TM; ++i) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(as_hf(b[j & 1][1]), as_hf(a[i][0]), acc[i][j], 0, 0, 0);
-#pragma unroll
-                for (int i = 0; i < TM; ++i) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(as_hf(b[j & 1][0]), as_hf(a[i][0]), acc[i][j], 0, 0, 0);
+                mma_term<1, true, 1, 0, TM, 1>(a, b + (j & 1), acc, 0, j);
+                mma_term<1, true, 0, 1, TM, 1>(a, b + (j & 1), acc, 0, j);
+                mma_term<1, true, 0, 0, TM, 1>(a, b + (j & 1), acc, 0, j);
             }
             if (FULL || t + 2 < n) b_adv();
             if (FULL || t + 3 < n) a_adv();
@@ -489,12 +435,7 @@ __global__ __launch_bounds__(256, 2) void k_conv_s3(ConvP p) {
                 const int zl = done / ktiles_all;
                 if (done - zl * ktiles_all == 0) {
                     store_tile_plain_t<TM, TN>(acc, p.y + (size_t)(zl - 1) * p.zy, p.M, p.Cout, m0, n0, wm0, wn0, os_tab, p.out_scale);
-#pragma unroll
-                    for (int i = 0; i < TM; ++i)
-#pragma unroll
-                        for (int j = 0; j < TN; ++j)
-#pragma unroll
-                            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+                    zero_acc(acc);
                 }
             }
             __syncthreads();
@@ -587,24 +528,34 @@ int s3_pf() {
     return pf == 2 ? 2 : 1;
 }
 
+// f(std::integral_constant<int, BN>()) for the column tile bn of a 128-row kernel: 128, 64 or 32
+template <class F>
+static void with_bn(int bn, F&& f) {
+    if (bn == 128) f(std::integral_constant<int, 128>());
+    else if (bn == 64) f(std::integral_constant<int, 64>());
+    else f(std::integral_constant<int, 32>());
+}
+
 void launch_conv_s3(const ConvChoice& k, hipStream_t st, const ConvP& p_in) {
     static const bool remap = !(getenv("EGR_S3_XCD") && atoi(getenv("EGR_S3_XCD")) == 0);
     ConvP p = p_in;
     p.xcd_remap = (remap && k.grid.y > 1 && ((k.grid.x * k.grid.y) & 7) == 0) ? 1 : 0;
     const int bn = k.bn;
 #define S3_LAUNCH(BM_, BN_, PF_, ZS_, SCH_) hipLaunchKernelGGL((k_conv_s3<BM_, BN_, PF_, ZS_, SCH_>), k.grid, dim3(256), 0, st, p)
-    if (k.sch) {                                  // two-term fp16 scheme (PF = 1, 128 rows only)
-        if (k.zs) { if (bn == 256) S3_LAUNCH(128, 256, 1, true, 1); else S3_LAUNCH(128, 128, 1, true, 1); }
-        else if (bn == 256) S3_LAUNCH(128, 256, 1, false, 1);
-        else if (bn == 128) S3_LAUNCH(128, 128, 1, false, 1);
-        else if (bn == 64) S3_LAUNCH(128, 64, 1, false, 1);
-        else S3_LAUNCH(128, 32, 1, false, 1);
-    } else if (k.zs) { if (bn == 256) S3_LAUNCH(128, 256, 1, true, 0); else S3_LAUNCH(128, 128, 1, true, 0); }
-    else if (bn == 256) S3_LAUNCH(128, 256, 1, false, 0);
+    auto narrow = [&](auto pf, auto sch) {        // 128 x {128, 64, 32}
+        with_bn(bn, [&](auto n) { S3_LAUNCH(128, decltype(n)::value, decltype(pf)::value, false, decltype(sch)::value); });
+    };
+    typedef std::integral_constant<int, 0> I0;
+    typedef std::integral_constant<int, 1> I1;
+    typedef std::integral_constant<int, 2> I2;
+    if (k.zs) {                                   // (the two-term fp16 scheme: PF = 1, 128 rows only)
+        if (k.sch) { if (bn == 256) S3_LAUNCH(128, 256, 1, true, 1); else S3_LAUNCH(128, 128, 1, true, 1); }
+        else { if (bn == 256) S3_LAUNCH(128, 256, 1, true, 0); else S3_LAUNCH(128, 128, 1, true, 0); }
+    } else if (bn == 256) { if (k.sch) S3_LAUNCH(128, 256, 1, false, 1); else S3_LAUNCH(128, 256, 1, false, 0); }
+    else if (k.sch) narrow(I1(), I1());
     else if (k.bm == 256) S3_LAUNCH(256, 128, 1, false, 0);
-    else if (bn == 128) { if (k.pf == 2) S3_LAUNCH(128, 128, 2, false, 0); else S3_LAUNCH(128, 128, 1, false, 0); }
-    else if (bn == 64) { if (k.pf == 2) S3_LAUNCH(128, 64, 2, false, 0); else S3_LAUNCH(128, 64, 1, false, 0); }
-    else { if (k.pf == 2) S3_LAUNCH(128, 32, 2, false, 0); else S3_LAUNCH(128, 32, 1, false, 0); }
+    else if (k.pf == 2) narrow(I2(), I0());
+    else narrow(I1(), I0());
 #undef S3_LAUNCH
 }
 
@@ -669,8 +620,7 @@ extern "C" int egr_split3_pack(const float* w_packed, void* w3, int64_t nslabs, 
 // the implicit-GEMM loader above re-loads and re-splits every activation once per tap; here a workgroup splits its
 // (128 + dil (k-1)) x CC halo tile ONCE into LDS and every tap reads its MFMA operands from it at a row offset, so the
 // split work and the L2 traffic drop by the tap count.  Weights stream through the same double-buffered B tiles.
-// LDS halo tile per plane: [row][CC/8 chunks of 8 bf16], chunk index XOR-ed with (row / (16 / NCH)) & (NCH - 1): conflict-free
-// ds_read_b128 for any row offset (brute-forced over all offsets for NCH = 2, 4).
+// LDS halo tile per plane: [row][CC/8 chunks of 8 bf16], swizzled by S3_HALO_SLOT (egr_s3_split.h).
 namespace egr {
 
 template <int BN, int CC, int SCH = 0>
@@ -696,12 +646,7 @@ __global__ __launch_bounds__(256, 2) void k_conv1d_s3(ConvP p) {
     const float* xb = p.x + (size_t)b * L * p.Cin;
 
     f32x16 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    zero_acc(acc);
 
     // B tiles: 2*NP*BN chunks per slab, up to 3 per thread (as in k_conv_s3)
     constexpr int NBQ = 2 * NP * BN;
@@ -715,7 +660,7 @@ __global__ __launch_bounds__(256, 2) void k_conv1d_s3(ConvP p) {
         const int e = tid + 256 * (I);                                                                               \
         const int plane = e / (2 * BN), rem = e - plane * 2 * BN, nl = rem >> 1, half = rem & 1;                     \
         OK = e < NBQ && n0 + nl < p.Cout;                                                                            \
-        SLOT = plane * (BN * 2) + nl * 2 + (half ^ ((nl >> 3) & 1));                                                 \
+        SLOT = plane * (BN * 2) + S3_TILE_SLOT(nl, half);                                                            \
         OFF = ((size_t)plane * p.Cout + n0 + nl) * 2 + half;                                                         \
     }
     C1_BSETUP(0, boff0, bslot0, bok0)
@@ -746,7 +691,7 @@ __global__ __launch_bounds__(256, 2) void k_conv1d_s3(ConvP p) {
         if (tid + 512 < NBQ) Bs[buf][0][bslot2] = r.b2;
     };
     const int li = lane & 31, lk = lane >> 5;
-    const int ob_slot = li * 2 + (lk ^ ((li >> 3) & 1));
+    const int ob_slot = S3_TILE_SLOT(li, lk);
 
     // one slab; `nx` is the register set holding tile sg + 1 (tile T lives in set T % 4) and is refilled with tile sg + 5
     auto slab = [&](int sg, StageB& nx) {
@@ -774,7 +719,7 @@ __global__ __launch_bounds__(256, 2) void k_conv1d_s3(ConvP p) {
                     const int r = e / NCH, ch = e - r * NCH;
                     uint4 q[3];
                     split_x8<SCH>(hu[i], hv[i], a_scale, q);
-                    const int slot = r * NCH + (ch ^ ((r / (16 / NCH)) & (NCH - 1)));
+                    const int slot = S3_HALO_SLOT(NCH, r, ch);
 #pragma unroll
                     for (int pl = 0; pl < NP; ++pl) As[pl][slot] = q[pl];
                 }
@@ -791,33 +736,14 @@ __global__ __launch_bounds__(256, 2) void k_conv1d_s3(ConvP p) {
 #pragma unroll
         for (int i = 0; i < TM; ++i) {
             const int r = wm0 + i * 32 + li + tap * p.dil;
-            const int slot = r * NCH + (ch ^ ((r / (16 / NCH)) & (NCH - 1)));
+            const int slot = S3_HALO_SLOT(NCH, r, ch);
 #pragma unroll
             for (int q = 0; q < NP; ++q) aq[i][q] = As[q][slot];
         }
         if (sg + 1 < stotal) store_b(cur ^ 1, nx);   // buffer cur^1 was last read in iteration sg-1, before this barrier
         if (sg + 5 < stotal) load_b(sg + 5, nx);
-        if constexpr (SCH == 0) {
-#define C1_MMA(QA, QB)                                                                                                   \
-    _Pragma("unroll") for (int i = 0; i < TM; ++i) _Pragma("unroll") for (int j = 0; j < TN; ++j) acc[i][j] =            \
-        __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf(aq[i][QA]), as_bf(bq[j][QB]), acc[i][j], 0, 0, 0);
-            C1_MMA(2, 0)
-            C1_MMA(0, 2)
-            C1_MMA(1, 1)
-            C1_MMA(1, 0)
-            C1_MMA(0, 1)
-            C1_MMA(0, 0)
-#undef C1_MMA
-        } else {
-            // weights as the first operand: transposed accumulators, 16-byte stores (conv_epilogue_t)
-#define C1_MMA(QA, QB)                                                                                                   \
-    _Pragma("unroll") for (int i = 0; i < TM; ++i) _Pragma("unroll") for (int j = 0; j < TN; ++j) acc[i][j] =            \
-        __builtin_amdgcn_mfma_f32_32x32x16_f16(as_hf(bq[j][QB]), as_hf(aq[i][QA]), acc[i][j], 0, 0, 0);
-            C1_MMA(1, 0)
-            C1_MMA(0, 1)
-            C1_MMA(0, 0)
-#undef C1_MMA
-        }
+        // scheme 1: weights as the first operand -- transposed accumulators, 16-byte stores (conv_epilogue_t)
+        mma_terms<SCH, SCH == 1, TM, TN>(aq, bq, acc);
         if (s + 1 == spc) __syncthreads();       // last slab of the chunk: everyone is done with the halo tile
     };
 
@@ -860,19 +786,16 @@ bool conv1d_s3_applies(const ConvP& p, ConvChoice& k) {
 }
 
 void launch_conv1d_s3(const ConvChoice& k, hipStream_t st, const ConvP& p) {
-    const int bn = k.bn; const dim3 grid = k.grid;
-#define C1_LAUNCH(SCH_)                                                                                   \
-    if (k.cc == 32) {                                                                                     \
-        if (bn == 128) hipLaunchKernelGGL((k_conv1d_s3<128, 32, SCH_>), grid, dim3(256), 0, st, p);       \
-        else if (bn == 64) hipLaunchKernelGGL((k_conv1d_s3<64, 32, SCH_>), grid, dim3(256), 0, st, p);    \
-        else hipLaunchKernelGGL((k_conv1d_s3<32, 32, SCH_>), grid, dim3(256), 0, st, p);                  \
-    } else {                                                                                              \
-        if (bn == 128) hipLaunchKernelGGL((k_conv1d_s3<128, 16, SCH_>), grid, dim3(256), 0, st, p);       \
-        else if (bn == 64) hipLaunchKernelGGL((k_conv1d_s3<64, 16, SCH_>), grid, dim3(256), 0, st, p);    \
-        else hipLaunchKernelGGL((k_conv1d_s3<32, 16, SCH_>), grid, dim3(256), 0, st, p);                  \
-    }
-    if (p.sch) { C1_LAUNCH(1) } else { C1_LAUNCH(0) }
-#undef C1_LAUNCH
+    with_bn(k.bn, [&](auto n) {
+        constexpr int BN = decltype(n)::value;
+        if (p.sch) {
+            if (k.cc == 32) hipLaunchKernelGGL((k_conv1d_s3<BN, 32, 1>), k.grid, dim3(256), 0, st, p);
+            else hipLaunchKernelGGL((k_conv1d_s3<BN, 16, 1>), k.grid, dim3(256), 0, st, p);
+        } else {
+            if (k.cc == 32) hipLaunchKernelGGL((k_conv1d_s3<BN, 32, 0>), k.grid, dim3(256), 0, st, p);
+            else hipLaunchKernelGGL((k_conv1d_s3<BN, 16, 0>), k.grid, dim3(256), 0, st, p);
+        }
+    });
 }
 
 }  // namespace egr
@@ -916,12 +839,7 @@ __global__ __launch_bounds__(256, 2) void k_bgemm_s3(GemmS3P p) {
     }
 
     f32x16 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    zero_acc(acc);
 
     // each thread owns one 8-float chunk of the A tile and (tid < 2 BN) one of the B tile per slab
     const int ar = tid >> 1, ah = tid & 1;
@@ -929,9 +847,9 @@ __global__ __launch_bounds__(256, 2) void k_bgemm_s3(GemmS3P p) {
     const float* aptr = a_ok ? A + (size_t)(m0 + ar) * p.lda + ah * 8 : p.zeros;
     const float* bptr = b_ok ? Bm + (size_t)(n0 + ar) * p.ldb + ah * 8 : p.zeros;
     const int astep = a_ok ? 16 : 0, bstep = b_ok ? 16 : 0;
-    const int slot = ar * 2 + (ah ^ ((ar >> 3) & 1));
+    const int slot = S3_TILE_SLOT(ar, ah);
     const int li = lane & 31, lk = lane >> 5;
-    const int o_slot = li * 2 + (lk ^ ((li >> 3) & 1));
+    const int o_slot = S3_TILE_SLOT(li, lk);
     const int ktiles = p.K / S3_BK;
 
     float4 ra0, ra1, rb0, rb1;
@@ -975,26 +893,7 @@ __global__ __launch_bounds__(256, 2) void k_bgemm_s3(GemmS3P p) {
             for (int q = 0; q < NP; ++q) b[j][q] = Bs[cur][q][(wn0 + j * 32) * 2 + o_slot];
         if (kt + 1 < ktiles) store(cur ^ 1);
         if (kt + 2 < ktiles) load();
-        if constexpr (SCH == 0) {
-#define G3_MMA(QA, QB)                                                                                                   \
-    _Pragma("unroll") for (int i = 0; i < TM; ++i) _Pragma("unroll") for (int j = 0; j < TN; ++j) acc[i][j] =            \
-        __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf(a[i][QA]), as_bf(b[j][QB]), acc[i][j], 0, 0, 0);
-            G3_MMA(2, 0)
-            G3_MMA(0, 2)
-            G3_MMA(1, 1)
-            G3_MMA(1, 0)
-            G3_MMA(0, 1)
-            G3_MMA(0, 0)
-#undef G3_MMA
-        } else {
-#define G3_MMA(QA, QB)                                                                                                   \
-    _Pragma("unroll") for (int i = 0; i < TM; ++i) _Pragma("unroll") for (int j = 0; j < TN; ++j) acc[i][j] =            \
-        __builtin_amdgcn_mfma_f32_32x32x16_f16(as_hf(a[i][QA]), as_hf(b[j][QB]), acc[i][j], 0, 0, 0);
-            G3_MMA(1, 0)
-            G3_MMA(0, 1)
-            G3_MMA(0, 0)
-#undef G3_MMA
-        }
+        mma_terms<SCH, false, TM, TN>(a, b, acc);
         __syncthreads();
     }
     const int col = lane & 31, rhalf = lane >> 5;
@@ -1011,13 +910,8 @@ __global__ __launch_bounds__(256, 2) void k_bgemm_s3(GemmS3P p) {
                     if (n0 + wn0 + j * 32 + col < p.N) { const float v = alpha * acc[i][j][r]; row[j * 32] = v; vm = fmaxf(vm, fabsf(v)); }
             }
         }
-    if (SCH == 1 && p.out_amax) {                // max |C| per outer batch index: one checked atomic per wave
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) vm = fmaxf(vm, __shfl_xor(vm, o));
-        unsigned* slot_o = p.out_amax + (size_t)b1 * EGR_ROW_AMAX_STRIDE;
-        const unsigned bits = __float_as_uint(vm);
-        if (lane == 0 && bits > __hip_atomic_load(slot_o, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(slot_o, bits);
-    }
+    // max |C| per outer batch index: one checked atomic per wave
+    if (SCH == 1 && p.out_amax) row_amax_commit(p.out_amax + (size_t)b1 * EGR_ROW_AMAX_STRIDE, vm);
 }
 
 }  // namespace egr
@@ -1039,15 +933,10 @@ static int bgemm_nt_launch(const float* a, const float* b, float* c, int nb1, in
     const int bn = N > 64 ? 128 : (N > 32 ? 64 : 32);
     dim3 grid((M + 127) / 128, (N + bn - 1) / bn, nb1 * nb2);
     hipStream_t st = (hipStream_t)stream;
-    if (a_amax) {
-        if (bn == 128) hipLaunchKernelGGL((k_bgemm_s3<128, 1>), grid, dim3(256), 0, st, p);
-        else if (bn == 64) hipLaunchKernelGGL((k_bgemm_s3<64, 1>), grid, dim3(256), 0, st, p);
-        else hipLaunchKernelGGL((k_bgemm_s3<32, 1>), grid, dim3(256), 0, st, p);
-    } else {
-        if (bn == 128) hipLaunchKernelGGL((k_bgemm_s3<128>), grid, dim3(256), 0, st, p);
-        else if (bn == 64) hipLaunchKernelGGL((k_bgemm_s3<64>), grid, dim3(256), 0, st, p);
-        else hipLaunchKernelGGL((k_bgemm_s3<32>), grid, dim3(256), 0, st, p);
-    }
+    with_bn(bn, [&](auto n) {
+        if (a_amax) hipLaunchKernelGGL((k_bgemm_s3<decltype(n)::value, 1>), grid, dim3(256), 0, st, p);
+        else hipLaunchKernelGGL((k_bgemm_s3<decltype(n)::value, 0>), grid, dim3(256), 0, st, p);
+    });
     EGR_HIP(hipGetLastError());
     return EGR_OK;
 }

@@ -1,8 +1,9 @@
 // Device helpers shared by the split-operand contraction kernels (egr_nn_gemm_s3.hip: implicit-GEMM / 1-D / batched kernels;
 // egr_nn_conv3x3.hip: the input-stationary 3x3 kernels): the exact operand splits (three bf16 terms / two fp16 terms of the
-// pre-scaled operand), the partial-product sequences, and the wave layout of a block tile.
+// pre-scaled operand), the partial-product sequences, the LDS slots of operand and halo tiles, and the wave layout of a block tile.
 #pragma once
 #include "egr_conv.h"
+#include "egr_rowmax.h"
 
 namespace egr {
 
@@ -10,7 +11,6 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
-#define S3_BM 128
 #define S3_BK 16
 
 __device__ __forceinline__ uint32_t pk_bf16(float a, float b) {        // RNE; a -> bits 0..15, b -> bits 16..31
@@ -62,37 +62,11 @@ __device__ __forceinline__ void split2h_x8(const float4& u, const float4& v, flo
     split2h_pair(v.z, v.w, s, q0.w, q1.w);
 }
 
-// raises *slot (the bits of a non-negative float, which order like unsigned integers) to the wave's maximum
-__device__ __forceinline__ void amax_commit(unsigned* slot, float m) {
-    if (!slot) return;
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-    const unsigned bits = __float_as_uint(m);
-    if ((threadIdx.x & 63) == 0 && bits > __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(slot, bits);
-}
-
 // the operand split of scheme SCH into its NP planes q[0..NP)
 template <int SCH>
 __device__ __forceinline__ void split_x8(const float4& u, const float4& v, float s, uint4 (&q)[3]) {
     if constexpr (SCH == 0) split3_x8(u, v, q[0], q[1], q[2]);
     else split2h_x8(u, v, s, q[0], q[1]);
-}
-
-// the partial products of one 32x32x16 block, smallest terms first
-template <int SCH>
-__device__ __forceinline__ void mma_split(const uint4 (&a)[3], const uint4 (&b)[3], f32x16& acc) {
-    if constexpr (SCH == 0) {
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a[2]), __builtin_bit_cast(bf16x8, b[0]), acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a[0]), __builtin_bit_cast(bf16x8, b[2]), acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a[1]), __builtin_bit_cast(bf16x8, b[1]), acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a[1]), __builtin_bit_cast(bf16x8, b[0]), acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a[0]), __builtin_bit_cast(bf16x8, b[1]), acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a[0]), __builtin_bit_cast(bf16x8, b[0]), acc, 0, 0, 0);
-    } else {
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a[1]), __builtin_bit_cast(f16x8, b[0]), acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a[0]), __builtin_bit_cast(f16x8, b[1]), acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a[0]), __builtin_bit_cast(f16x8, b[0]), acc, 0, 0, 0);
-    }
 }
 
 // <BM, BN> block tile, 4 waves.  256x128: waves 2x2, each 128x64 (TM 4, TN 2; the large-M workhorse: half the split work and
@@ -106,5 +80,58 @@ template <> struct S3Cfg<128, 32> { static constexpr int WM = 4, WN = 1, TM = 1,
 
 __device__ __forceinline__ bf16x8 as_bf(const uint4& v) { return __builtin_bit_cast(bf16x8, v); }
 __device__ __forceinline__ f16x8 as_hf(const uint4& v) { return __builtin_bit_cast(f16x8, v); }
+
+template <int TM, int TN>
+__device__ __forceinline__ void zero_acc(f32x16 (&acc)[TM][TN]) {
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+}
+
+// ---- partial products.  a[i][q] / b[j][q]: plane q of the wave's 32-row sub-tile i of the first / 32-column sub-tile j of the second
+// tile (one uint4 = this lane's 8 k).  One term (plane QA of a times plane QB of b) over TA x TB sub-tiles, accumulated into
+// acc[i0 + i][j0 + j].  WFIRST issues mfma(b, a): the weight tile as the first operand, accumulators transposed (conv_epilogue_t).
+template <int SCH, bool WFIRST, int QA, int QB, int TA, int TB, int NA, int NB, int TM, int TN>
+__device__ __forceinline__ void mma_term(const uint4 (*a)[NA], const uint4 (*b)[NB], f32x16 (&acc)[TM][TN], int i0 = 0, int j0 = 0) {
+#pragma unroll
+    for (int i = 0; i < TA; ++i)
+#pragma unroll
+        for (int j = 0; j < TB; ++j) {
+            const uint4 &x = WFIRST ? b[j][QB] : a[i][QA], &y = WFIRST ? a[i][QA] : b[j][QB];
+            f32x16& c = acc[i0 + i][j0 + j];
+            if constexpr (SCH == 0) c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as_bf(x), as_bf(y), c, 0, 0, 0);
+            else c = __builtin_amdgcn_mfma_f32_32x32x16_f16(as_hf(x), as_hf(y), c, 0, 0, 0);
+        }
+}
+
+// All terms of scheme SCH for one 16-k slab, smallest terms first (the large products then meet a sum that already holds the small
+// ones): scheme 0 (2,0) (0,2) (1,1) (1,0) (0,1) (0,0), scheme 1 (1,0) (0,1) (0,0).  The order is TERM-outer, sub-tile-inner: an MFMA
+// that accumulates into the register block its predecessor wrote waits for that result, so each term runs across all TA x TB
+// accumulator blocks before the next term returns to the first of them and consecutive MFMAs are independent.  (All terms of one
+// block back to back would be the same sum in the same order per block, with every MFMA waiting for the one before it.)
+template <int SCH, bool WFIRST, int TA, int TB, int NA, int NB, int TM, int TN>
+__device__ __forceinline__ void mma_terms(const uint4 (*a)[NA], const uint4 (*b)[NB], f32x16 (&acc)[TM][TN], int i0 = 0, int j0 = 0) {
+    if constexpr (SCH == 0) {
+        mma_term<0, WFIRST, 2, 0, TA, TB>(a, b, acc, i0, j0);
+        mma_term<0, WFIRST, 0, 2, TA, TB>(a, b, acc, i0, j0);
+        mma_term<0, WFIRST, 1, 1, TA, TB>(a, b, acc, i0, j0);
+    }
+    mma_term<SCH, WFIRST, 1, 0, TA, TB>(a, b, acc, i0, j0);
+    mma_term<SCH, WFIRST, 0, 1, TA, TB>(a, b, acc, i0, j0);
+    mma_term<SCH, WFIRST, 0, 0, TA, TB>(a, b, acc, i0, j0);
+}
+
+// ---- LDS slots (uint4 units within one plane).  These two are macros, not functions: an inline function is simplified on its own
+// before it is inlined, and that changed the address arithmetic, VGPR counts and spills of the 128 x 256 and the 3x3 instantiations
+// (profiles/split_tile_helpers.md); the textual form compiles to what the kernels held before.
+// Operand tile [row][2 halves of 8 k]: the half is XOR-ed with bit 3 of the row, which makes the loaders' ds_write_b128 and the MFMA
+// operand ds_read_b128 (lane l: row l & 31, half l >> 5) conflict-free at a 32-byte pitch.
+#define S3_TILE_SLOT(row, half) ((row) * 2 + ((half) ^ (((row) >> 3) & 1)))
+// Halo tile [row][NCH chunks of 8 channels] of the input-stationary kernels, read at a row offset per tap: the chunk is XOR-ed with
+// (row / (16 / NCH)) & (NCH - 1) -- conflict-free ds_read_b128 for ANY row offset (brute-forced over all offsets for NCH = 2, 4).
+#define S3_HALO_SLOT(NCH, r, ch) ((r) * (NCH) + ((ch) ^ (((r) / (16 / (NCH))) & ((NCH) - 1))))
 
 }  // namespace egr
