@@ -21,7 +21,9 @@
 #include <unordered_map>
 #include <vector>
 
+#include "egr_arena.h"
 #include "egr_conv.h"
+#include "egr_handle.h"
 
 extern "C" {
 int egr_pack_weight(const float* src, float* dst, int layout, int K, int N, int Ci, int Co, int KH, int KW, void* stream);
@@ -40,97 +42,47 @@ enum { EW_ADD = 0, EW_AXPBY = 1, EW_SILU = 2, EW_SCALE = 3, EW_COPY = 4, EW_ADD_
 // the want_ra argument of an operator, by name: its output feeds a split contraction directly, so the producer leaves its row maxima
 const bool WANT_RA = true, NO_RA = false;
 
-#define OKR(call)                 \
-    do {                          \
-        int rc__ = (call);        \
-        if (rc__ != EGR_OK) return rc__; \
-    } while (0)
-
-// ------------------------------------------------------------------------------------------------ scratch arena
-// Best-fit allocator with splitting and coalescing over a few large hipMalloc'ed slabs.  Everything runs on ONE stream, so a
-// block may be handed out again as soon as the host has enqueued its last consumer (stream order does the rest).  After the first
-// forward of a given row count no allocation reaches the runtime, and the footprint stays near the peak of simultaneously live
-// activations (exact-size free lists, the first version, held 47 GB for a 26-row pass; this holds the live peak + slab slack).
+// ------------------------------------------------------------------------------------------------ device resources
 // host time spent in the arenas' hipMalloc calls, in microseconds (EGR_FSR_TRACE=1 prints it per call); forwards on different devices run
 // under different per-device locks, so the counter is atomic
 static std::atomic<long long> g_arena_malloc_us{0};
 static inline double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
-struct Arena {
-    struct Slab {
-        char* base = nullptr;
-        size_t size = 0;
-        std::map<char*, size_t> by_addr;                 // free blocks
-        std::multimap<size_t, char*> by_size;
-        void insert(char* p, size_t n) { by_addr[p] = n; by_size.emplace(n, p); }
-        void erase(char* p, size_t n) {
-            by_addr.erase(p);
-            auto r = by_size.equal_range(n);
-            for (auto it = r.first; it != r.second; ++it) if (it->second == p) { by_size.erase(it); break; }
-        }
-    };
-    std::vector<Slab> slabs;
-    size_t total = 0;
-    static size_t round_up(size_t b) { b = (b + 255) & ~(size_t)255; return b ? b : 256; }
+// the scratch arena (csrc/egr_arena.h) over hipMalloc'ed slabs
+struct HipSlabs {
     void* get(size_t bytes) {
-        bytes = round_up(bytes);
-        Slab* best = nullptr;
-        std::multimap<size_t, char*>::iterator bi;
-        for (auto& s : slabs) {
-            auto it = s.by_size.lower_bound(bytes);
-            if (it != s.by_size.end() && (!best || it->first < bi->first)) { best = &s; bi = it; }
-        }
-        if (!best) {
-            Slab s;
-            s.size = std::max(bytes, (size_t)1 << 31);                      // 2 GiB slabs, or one request if larger
-            const double t0 = now_ms();
-            struct T { double t0; ~T() { g_arena_malloc_us += (long long)((now_ms() - t0) * 1e3); } } timer{t0};
-            if (hipMalloc((void**)&s.base, s.size) != hipSuccess) {
-                s.size = bytes;                                             // memory is tight: exactly what is needed
-                if (hipMalloc((void**)&s.base, s.size) != hipSuccess) {
-                    set_error("FlashSR scratch arena: hipMalloc(%zu) failed (%zu bytes held)", bytes, total);
-                    return nullptr;
-                }
-            }
-            total += s.size;
-            s.insert(s.base, s.size);
-            slabs.push_back(std::move(s));
-            best = &slabs.back();
-            bi = best->by_size.lower_bound(bytes);
-        }
-        char* p = bi->second;
-        const size_t have = bi->first;
-        best->erase(p, have);
-        if (have > bytes) best->insert(p + bytes, have - bytes);
+        const double t0 = now_ms();
+        void* p = nullptr;
+        if (hipMalloc(&p, bytes) != hipSuccess) p = nullptr;
+        g_arena_malloc_us += (long long)((now_ms() - t0) * 1e3);
         return p;
     }
-    void put(void* ptr, size_t bytes) {
-        bytes = round_up(bytes);
-        char* p = (char*)ptr;
-        for (auto& s : slabs) {
-            if (p < s.base || p >= s.base + s.size) continue;
-            auto nx = s.by_addr.lower_bound(p);
-            if (nx != s.by_addr.end() && nx->first == p + bytes) {          // merge with the block behind
-                const size_t n = nx->second;
-                s.erase(nx->first, n);
-                bytes += n;
-            }
-            auto pv = s.by_addr.lower_bound(p);
-            if (pv != s.by_addr.begin()) {
-                --pv;
-                if (pv->first + pv->second == p) {                          // merge with the block in front
-                    char* q = pv->first;
-                    const size_t n = pv->second;
-                    s.erase(q, n);
-                    p = q;
-                    bytes += n;
-                }
-            }
-            s.insert(p, bytes);
-            return;
-        }
-    }
-    ~Arena() { for (auto& s : slabs) hipFree(s.base); }
+    void put(void* base) { hipFree(base); }
+};
+typedef egr::Arena<HipSlabs> Arena;
+
+// a hipMalloc'ed buffer and its hipFree (move-only); whoever must wait for the device before a free does so before reset()
+struct DevBuf {
+    void* p = nullptr;
+    DevBuf() {}
+    DevBuf(DevBuf&& o) noexcept : p(o.p) { o.p = nullptr; }
+    DevBuf& operator=(DevBuf&& o) noexcept { if (this != &o) { reset(); p = o.p; o.p = nullptr; } return *this; }
+    ~DevBuf() { reset(); }
+    bool alloc(size_t bytes) { reset(); if (hipMalloc(&p, bytes) != hipSuccess) p = nullptr; return p != nullptr; }
+    void reset() { if (p) hipFree(p); p = nullptr; }
+    void* release() { void* q = p; p = nullptr; return q; }
+    template <class T> T* as() const { return (T*)p; }
+};
+
+// the two events around a timed launch (move-only; empty until create())
+struct EventPair {
+    hipEvent_t a = nullptr, b = nullptr;
+    EventPair() {}
+    EventPair(EventPair&& o) noexcept : a(o.a), b(o.b) { o.a = o.b = nullptr; }
+    EventPair& operator=(EventPair&& o) noexcept { if (this != &o) { reset(); a = o.a; b = o.b; o.a = o.b = nullptr; } return *this; }
+    ~EventPair() { reset(); }
+    void create() { hipEventCreate(&a); hipEventCreate(&b); }
+    void reset() { if (a) hipEventDestroy(a); if (b) hipEventDestroy(b); a = b = nullptr; }
 };
 
 struct Ten {                       // an fp32 activation owned by the arena (move-only)
@@ -170,26 +122,86 @@ struct Wt : egr::PreparedWeight {  // one entry of the weight store; w may also 
     int64_t zfloats = 0;           // floats per component of a z-stacked Winograd pack
 };
 
-struct ProfRec { std::string kind; double flops; hipEvent_t a, b; std::string detail; };
+struct ProfRec { std::string kind; double flops; EventPair ev; std::string detail; };
 
 }  // namespace
 
 // Everything one in-flight forward owns: its stream, scratch arena and workspaces.  Context 0 runs on the caller's stream; the
-// others on the handle's side streams when a pass is split into concurrent row groups (egr_flashsr_infer).
+// others on the handle's side streams when a pass is split into concurrent row groups (egr_flashsr_infer).  The destructor is the one
+// place that releases them; whoever drops a context waits for its work first.
 struct FsrCtx {
     hipStream_t st = nullptr;
+    bool owns_st = false;                             // a side stream of the handle (context 0 runs on the caller's: not ours to destroy)
     Arena arena;
-    void* gn_ws = nullptr;
+    DevBuf gn_ws;
     size_t gn_ws_bytes = 0;
     std::map<int, egr_fatllama_plan*> lp_plans;       // input low-pass: spectral-gain plans per row count
     hipEvent_t done = nullptr;
     // per-row operand maxima of the forward in flight (fp16 operand scheme): one R-entry slice per measured tensor, zeroed as a
     // whole when a forward starts
-    unsigned* rs_pool = nullptr;
+    DevBuf rs_pool;
     size_t rs_cap = 0, rs_used = 0;
-    std::vector<unsigned*> rs_retired;                // pools outgrown in mid-forward: still read by enqueued kernels, freed when the next forward starts
-    unsigned* rs_ones = nullptr;                      // "maximum 1.0" for every row (operands known to lie in [0, 1]: soft-max outputs); rs_ones_rows entries
+    std::vector<DevBuf> rs_retired;                   // pools outgrown in mid-forward: still read by enqueued kernels, freed when the next forward starts
+    DevBuf rs_ones;                                   // "maximum 1.0" for every row (operands known to lie in [0, 1]: soft-max outputs); rs_ones_rows entries
     int rs_ones_rows = 0;
+
+    FsrCtx() {}
+    explicit FsrCtx(hipStream_t side) : st(side), owns_st(true) { hipEventCreateWithFlags(&done, hipEventDisableTiming); }
+    ~FsrCtx() {                                       // (the buffers and the arena's slabs free themselves)
+        for (auto& kv : lp_plans) egr_fatllama_plan_destroy(kv.second);
+        if (done) hipEventDestroy(done);
+        if (owns_st) hipStreamDestroy(st);
+    }
+    // a forward of R rows on the fp16 operand scheme starts: retired pools go, one zeroed pool sized from the weight count, the ones table
+    int begin_rows(int R, int h2_nweights) {
+        size_t slices = (size_t)(2 * h2_nweights + 64);
+        if (const char* e = getenv("EGR_FSR_RS_POOL_SLICES")) { const int v = atoi(e); if (v >= 1) slices = (size_t)v; }   // test knob: start small, exercise the growth in take_rows
+        const size_t need = slices * (size_t)R * EGR_ROW_AMAX_STRIDE;
+        if (!rs_retired.empty()) {                     // pools a previous forward outgrew (take_rows): its kernels are done once the stream is
+            hipStreamSynchronize(st);
+            rs_retired.clear();
+        }
+        if (rs_cap < need) {
+            if (rs_pool.p) { hipStreamSynchronize(st); rs_pool.reset(); rs_cap = 0; }
+            if (!rs_pool.alloc(need * sizeof(unsigned))) { set_error("hipMalloc(row maxima pool) failed"); return EGR_ERR_ALLOC; }
+            rs_cap = need;
+        }
+        EGR_HIP(hipMemsetAsync(rs_pool.p, 0, rs_cap * sizeof(unsigned), st));
+        rs_used = 0;
+        if (rs_ones_rows < R) {
+            if (rs_ones.p) { hipStreamSynchronize(st); rs_ones.reset(); }
+            const size_t n = (size_t)R * EGR_ROW_AMAX_STRIDE;
+            if (!rs_ones.alloc(n * sizeof(unsigned))) { set_error("hipMalloc(row maxima constants) failed"); return EGR_ERR_ALLOC; }
+            std::vector<unsigned> ones(n, 0x3f800000u);
+            EGR_HIP(hipMemcpy(rs_ones.p, ones.data(), n * sizeof(unsigned), hipMemcpyHostToDevice));
+            rs_ones_rows = R;
+        }
+        return EGR_OK;
+    }
+    // R-entry slice of the pool of per-row maxima (zero at the start of the forward)
+    unsigned* take_rows(int R) {
+        if (rs_used + (size_t)R * EGR_ROW_AMAX_STRIDE > rs_cap) {
+            // the start-of-forward size is a heuristic over the layer table; a graph that measures more tensors than it allowed for gets a
+            // second, larger pool here (zeroed on the forward's stream) instead of a failed call -- the next forward starts at that size
+            const size_t grown = std::max(2 * rs_cap, (size_t)64 * R * EGR_ROW_AMAX_STRIDE);
+            DevBuf np;
+            if (!np.alloc(grown * sizeof(unsigned))) { set_error("FlashSR: hipMalloc(row maxima pool, %zu entries) failed", grown); return nullptr; }
+            if (hipMemsetAsync(np.p, 0, grown * sizeof(unsigned), st) != hipSuccess) { set_error("FlashSR: hipMemsetAsync(row maxima pool) failed"); return nullptr; }
+            if (rs_pool.p) rs_retired.push_back(std::move(rs_pool));
+            rs_pool = std::move(np); rs_cap = grown; rs_used = 0;
+        }
+        unsigned* p = rs_pool.as<unsigned>() + rs_used;
+        rs_used += (size_t)R * EGR_ROW_AMAX_STRIDE;
+        return p;
+    }
+    int gn_scratch(size_t need) {
+        if (gn_ws_bytes < need) {
+            if (gn_ws.p) { hipStreamSynchronize(st); gn_ws.reset(); gn_ws_bytes = 0; }
+            if (!gn_ws.alloc(need + 1024)) { set_error("hipMalloc(GroupNorm workspace) failed"); return EGR_ERR_ALLOC; }
+            gn_ws_bytes = need + 1024;
+        }
+        return EGR_OK;
+    }
 };
 
 struct egr_flashsr {
@@ -197,8 +209,7 @@ struct egr_flashsr {
     unsigned flags = 0;
     int device = 0;
     std::vector<std::unique_ptr<FsrCtx>> ctxs;        // [0] = the caller's stream
-    FsrCtx* cx = nullptr;                             // context of the forward being enqueued
-    int max_groups = 2;                               // concurrent row groups per pass (EGREGORA_FLASHSR_STREAMS)
+    int max_groups = 2;                              // concurrent row groups per pass (EGREGORA_FLASHSR_STREAMS)
     int min_group_rows = 6;
     hipEvent_t ev_fork = nullptr;
     std::vector<hipStream_t> verified_for;            // caller streams the side streams were checked against
@@ -209,17 +220,14 @@ struct egr_flashsr {
     float* window = nullptr; float* filt = nullptr;
     int ldm = 0, lat_h = 0, lat_w = 0;
     float alpha = 0.f, sigma = 0.f;
-    float* d_wmax = nullptr;                          // one float: weight maxima at pack time
+    DevBuf d_wmax;                                    // one float: weight maxima at pack time
     int rows_per_pass = 32;
     // scratch budget (EGREGORA_FLASHSR_ARENA_GB / egr_flashsr_set_arena_cap; 0 = none): rows per pass are lowered until the arenas
     // of a pass are expected to fit (measured bytes per row once a pass has run, an estimate from the layer table before)
     double arena_cap = 0.0, arena_row_bytes = 0.0;
     int wino_min_ch = 128;
-    double flops = 0.0; bool count_flops = false;
     int profiling = 0;                                // egr_flashsr_set_profiling: 0 off, 1 contraction launches, 2 and the graph's other operator launches
     std::vector<ProfRec> prof;
-    hipStream_t st = nullptr;                         // stream of the forward being enqueued (= cx->st)
-    void use(FsrCtx* c) { cx = c; st = c->st; }
     // Two-term fp16 operand scheme of egr_flashsr_infer (csrc/egr_nn_gemm_s3.hip, scheme 1).  Every batch row of every split
     // contraction's input is scaled by its own power of two, which the kernel derives from that row's max |x|; the maxima are
     // written on the device by the tensor's producer (Winograd input transforms) or by one k_absmax_rows pass the first time a
@@ -228,17 +236,15 @@ struct egr_flashsr {
     // through tile choices; no value can leave fp16's range (the scale comes from the row's own maximum), so there is nothing to
     // verify or re-run, and the call is as asynchronous as the bf16 one.
     bool h2 = true;                                   // scheme available (off: EGR_FSR_SPLIT_BF16X3, EGREGORA_FLASHSR_SPLIT=bf16x3, f32 MFMA)
-    int h2_mode = -1;                                 // of the forward being enqueued: -1 bf16 terms, 1 fp16 terms
     bool h2_fwd = false;                              // egr_flashsr_forward too runs the fp16 terms (set_split 2: stage taps for tests)
     int h2_nweights = 0;                              // contraction weights that hold fp16 terms
-    int R = 1;                                        // batch rows of the forward being enqueued
     bool out_amax_on = true;                          // contraction epilogues leave the row maxima of their outputs (EGREGORA_FLASHSR_OUT_AMAX=0: off)
     int direct3x3_max_cout = 128;                     // EGREGORA_FLASHSR_DIRECT3X3_MAX_COUT (0: off): see gn_conv3
     bool fused_amp = true;                            // EGREGORA_FLASHSR_FUSED_AMP=0: the thin AMP units as four launches each
     int64_t h2_calls = 0;
 
     bool f32_mfma() const { return (flags & EGR_FSR_F32_MFMA) != 0; }
-    bool h2_on() const { return h2 && h2_mode == 1; } // the forward being enqueued runs the fp16 terms
+    bool h2_ready() const { return h2 && h2_nweights > 0; }   // egr_flashsr_infer runs the fp16 terms
     bool has(const std::string& k) const { return W.find(k) != W.end(); }
     const Wt* get(const std::string& k) const { auto it = W.find(k); return it == W.end() ? nullptr : &it->second; }
     float* ptr(const std::string& k) const { auto it = W.find(k); return it == W.end() ? nullptr : it->second.w; }
@@ -247,6 +253,22 @@ struct egr_flashsr {
 namespace {
 
 typedef egr_flashsr M;
+
+// What is true for ONE forward being enqueued.  The operators and stages take it; they read the model through `m` and write only
+// through the context, the profile sink and the flop sum named here.
+struct Fwd {
+    const M& m;
+    FsrCtx* cx;                        // its stream, arena, workspaces and row-maxima pool
+    hipStream_t st;                    // = cx->st
+    int R;                             // batch rows
+    bool h2;                           // runs the fp16 operand terms (else three bf16 terms)
+    std::vector<ProfRec>* prof;        // where timed launches are recorded, up to prof_level (0: nowhere)
+    int prof_level;
+    double* flops;                     // sum of contraction flops as executed, or null
+    Fwd(const M& model, FsrCtx* c, int rows, bool fp16_terms, std::vector<ProfRec>* rec = nullptr, int level = 0, double* flop_sum = nullptr)
+        : m(model), cx(c), st(c->st), R(rows), h2(fp16_terms), prof(rec), prof_level(rec ? level : 0), flops(flop_sum) {}
+    void count(double fl) { if (flops) *flops += fl; }
+};
 
 int dev_alloc(M* m, size_t bytes, void** out) {
     void* p = nullptr;
@@ -257,19 +279,20 @@ int dev_alloc(M* m, size_t bytes, void** out) {
     return EGR_OK;
 }
 
-int new_ten(M* m, Ten& t, std::initializer_list<int64_t> shape) {
+int new_ten(Fwd& f, Ten& t, std::initializer_list<int64_t> shape) {
     t.release();
     t.view(shape);
     t.bytes = (size_t)t.numel() * sizeof(float);
-    t.p = (float*)m->cx->arena.get(t.bytes);
-    if (!t.p) return EGR_ERR_ALLOC;
-    t.a = &m->cx->arena;
+    Arena& a = f.cx->arena;
+    t.p = (float*)a.get(t.bytes);
+    if (!t.p) { set_error("FlashSR scratch arena: hipMalloc(%zu) failed (%zu bytes held)", Arena::round_up(t.bytes), a.total); return EGR_ERR_ALLOC; }
+    t.a = &a;
     return EGR_OK;
 }
 
 // a fresh arena tensor of x's shape
-int new_like(M* m, Ten& y, const Ten& x) {
-    OKR(new_ten(m, y, {x.numel()}));
+int new_like(Fwd& f, Ten& y, const Ten& x) {
+    EGR_TRY(new_ten(f, y, {x.numel()}));
     y.nd = x.nd; memcpy(y.d, x.d, sizeof(y.d));
     return EGR_OK;
 }
@@ -317,13 +340,13 @@ int up_kernel(int r) { return 2 * r + (r % 2); }
 // the term packs of the packed w (N and numel set): three bf16 terms, and two fp16 terms of w * 2^k where the scheme is available
 int split3(M* m, Wt& w) {
     if (m->f32_mfma() || !w.w) return EGR_OK;
-    OKR(dev_alloc(m, w.term_bytes(3), &w.w3));
+    EGR_TRY(dev_alloc(m, w.term_bytes(3), &w.w3));
     if (m->h2) {
-        if (!m->d_wmax && hipMalloc((void**)&m->d_wmax, sizeof(float)) != hipSuccess) { set_error("hipMalloc(weight maximum) failed"); return EGR_ERR_ALLOC; }
-        OKR(dev_alloc(m, w.term_bytes(2), &w.w2));
+        if (!m->d_wmax.p && !m->d_wmax.alloc(sizeof(float))) { set_error("hipMalloc(weight maximum) failed"); return EGR_ERR_ALLOC; }
+        EGR_TRY(dev_alloc(m, w.term_bytes(2), &w.w2));
         ++m->h2_nweights;
     }
-    return egr::split_weight(w, m->d_wmax, m->st);
+    return egr::split_weight(w, m->d_wmax.as<float>(), m->ctxs[0]->st);
 }
 
 // src in torch layout on the device; layout as in egr_pack_weight; registers key with logical (KH, KW, Cin, N)
@@ -331,15 +354,15 @@ int add_packed(M* m, const std::string& key, const float* src, int layout, int K
                int logical_kw, int logical_cin) {
     Wt w;
     egr::weight_shape(w, K, N);
-    OKR(dev_alloc(m, w.pack_bytes(), (void**)&w.w));
-    OKR(egr_pack_weight(src, w.w, layout, K, N, Ci, Co, KH, KW, m->st));
+    EGR_TRY(dev_alloc(m, w.pack_bytes(), (void**)&w.w));
+    EGR_TRY(egr_pack_weight(src, w.w, layout, K, N, Ci, Co, KH, KW, m->ctxs[0]->st));
     w.KH = logical_kh; w.KW = logical_kw; w.Cin = logical_cin; w.Cout = N;
     if (logical_cin % 16 == 0) {
         const bool keep = m->h2;
         if (key == "mel_fb") m->h2 = false;          // spectra span > 90 dB and a log follows: the mel projection keeps three bf16 terms
         const int rc = split3(m, w);
         m->h2 = keep;
-        OKR(rc);
+        EGR_TRY(rc);
     }
     m->W[key] = w;
     return EGR_OK;
@@ -356,15 +379,14 @@ int add_weight(M* m, const std::string& key, const egr_tensor_desc& t) {
 
 int add_phases(M* m, const std::string& key, const egr_tensor_desc& t) {
     const int Co = (int)t.shape[0], Ci = (int)t.shape[1];
-    float* tmp = nullptr;
+    DevBuf tmp;
     const size_t n = (size_t)4 * Co * Ci * 4;
-    if (hipMalloc((void**)&tmp, n * sizeof(float)) != hipSuccess) { set_error("hipMalloc(phase weights) failed"); return EGR_ERR_ALLOC; }
-    int rc = egr_phase_weights(t.data, tmp, Co, Ci, m->st);
+    if (!tmp.alloc(n * sizeof(float))) { set_error("hipMalloc(phase weights) failed"); return EGR_ERR_ALLOC; }
+    int rc = egr_phase_weights(t.data, tmp.as<float>(), Co, Ci, m->ctxs[0]->st);
     for (int a = 0; a < 2 && rc == EGR_OK; ++a)
         for (int b = 0; b < 2 && rc == EGR_OK; ++b)
-            rc = add_packed(m, key + ".ph" + std::to_string(a) + std::to_string(b), tmp + (size_t)(2 * a + b) * Co * Ci * 4, 0, 4 * Ci, Co, Ci, Co, 2, 2, 2, 2, Ci);
-    hipStreamSynchronize(m->st);
-    hipFree(tmp);
+            rc = add_packed(m, key + ".ph" + std::to_string(a) + std::to_string(b), tmp.as<float>() + (size_t)(2 * a + b) * Co * Ci * 4, 0, 4 * Ci, Co, Ci, Co, 2, 2, 2, 2, Ci);
+    hipStreamSynchronize(m->ctxs[0]->st);          // the packs read tmp: wait before it goes
     return rc;
 }
 
@@ -380,20 +402,17 @@ int add_winograd(M* m, const std::string& key, const egr_tensor_desc& t, const d
         w.numel = (int64_t)np * np * zf;
         w.zfloats = zf;
         w.KH = w.KW = 1; w.Cin = w.K = Ci; w.Cout = w.N = Co;
-        float* pk = nullptr;
-        if (hipMalloc((void**)&pk, (size_t)w.numel * sizeof(float)) != hipSuccess) { set_error("hipMalloc(Winograd U) failed"); return EGR_ERR_ALLOC; }
-        int rc = egr_winograd_pack_u(t.data, pk, pass == 0 ? G2_dev : G4_dev, np, Co, Ci, m->st);
-        w.w = pk;
+        DevBuf pk;
+        if (!pk.alloc((size_t)w.numel * sizeof(float))) { set_error("hipMalloc(Winograd U) failed"); return EGR_ERR_ALLOC; }
+        int rc = egr_winograd_pack_u(t.data, pk.as<float>(), pass == 0 ? G2_dev : G4_dev, np, Co, Ci, m->ctxs[0]->st);
+        w.w = pk.as<float>();
         if (rc == EGR_OK && Ci % 16 == 0) rc = split3(m, w);
-        if (rc == EGR_OK && w.w3) {                         // the fp32 pack is not needed once split
-            hipStreamSynchronize(m->st);
-            hipFree(pk);
+        if (rc != EGR_OK) return rc;
+        if (w.w3) {                                         // the fp32 pack is not needed once split
+            hipStreamSynchronize(m->ctxs[0]->st);
             w.w = nullptr;
-        } else if (rc == EGR_OK) {
-            m->owned.push_back(pk);
         } else {
-            hipFree(pk);
-            return rc;
+            m->owned.push_back(pk.release());
         }
         m->W[key + (pass == 0 ? ".wino" : ".wino4")] = w;
     }
@@ -405,11 +424,11 @@ bool ends_with(const std::string& s, const char* suf) { const size_t n = strlen(
 
 int pack_all(M* m, const egr_tensor_desc* ts, int n) {
     double g4[18];
-    OKR(egr_winograd4_g(g4));
+    EGR_TRY(egr_winograd4_g(g4));
     double* Gd = nullptr;
-    OKR(dev_alloc(m, 30 * sizeof(double), (void**)&Gd));
-    EGR_HIP(hipMemcpyAsync(Gd, kG2, 12 * sizeof(double), hipMemcpyHostToDevice, m->st));
-    EGR_HIP(hipMemcpyAsync(Gd + 12, g4, 18 * sizeof(double), hipMemcpyHostToDevice, m->st));
+    EGR_TRY(dev_alloc(m, 30 * sizeof(double), (void**)&Gd));
+    EGR_HIP(hipMemcpyAsync(Gd, kG2, 12 * sizeof(double), hipMemcpyHostToDevice, m->ctxs[0]->st));
+    EGR_HIP(hipMemcpyAsync(Gd + 12, g4, 18 * sizeof(double), hipMemcpyHostToDevice, m->ctxs[0]->st));
     const bool thin = !(m->flags & EGR_FSR_NO_THIN_ENDS);
     for (int i = 0; i < n; ++i) {
         const egr_tensor_desc& t = ts[i];
@@ -417,22 +436,22 @@ int pack_all(M* m, const egr_tensor_desc* ts, int n) {
         const std::string k = t.name;
         if (k.rfind("const.", 0) == 0) continue;
         if (ends_with(k, ".weight") && t.ndim >= 2) {
-            OKR(add_weight(m, k, t));
+            EGR_TRY(add_weight(m, k, t));
             const int64_t* s = t.shape;
-            if (contains(k, ".upsample.conv.") || (k.rfind("unet.", 0) == 0 && contains(k, ".up.conv."))) OKR(add_phases(m, k, t));
+            if (contains(k, ".upsample.conv.") || (k.rfind("unet.", 0) == 0 && contains(k, ".up.conv."))) EGR_TRY(add_phases(m, k, t));
             if (thin && t.ndim == 4 && s[2] * s[3] * s[0] <= 32 && s[1] % 16 == 0)       // few outputs: 1x1 contraction onto per-tap products
-                OKR(add_packed(m, k + ".taps", t.data, 2, (int)s[1], (int)(s[2] * s[3] * s[0]), (int)s[1], (int)s[0], (int)s[2], (int)s[3], 1, 1, (int)s[1]));
+                EGR_TRY(add_packed(m, k + ".taps", t.data, 2, (int)s[1], (int)(s[2] * s[3] * s[0]), (int)s[1], (int)s[0], (int)s[2], (int)s[3], 1, 1, (int)s[1]));
             if (!(m->flags & EGR_FSR_NO_WINOGRAD) && t.ndim == 4 && s[2] == 3 && s[3] == 3 && std::min(s[0], s[1]) >= m->wino_min_ch &&
                 !contains(k, "downsample") && !contains(k, ".down.conv") && !contains(k, "upsample") && !contains(k, ".up.conv"))
-                OKR(add_winograd(m, k, t, Gd, Gd + 12));
+                EGR_TRY(add_winograd(m, k, t, Gd, Gd + 12));
         } else {
             Wt w;
             int64_t ne = 1;
             for (int d = 0; d < t.ndim; ++d) ne *= t.shape[d];
             w.numel = ne;
             void* p = nullptr;
-            OKR(dev_alloc(m, (size_t)ne * sizeof(float), &p));
-            EGR_HIP(hipMemcpyAsync(p, t.data, (size_t)ne * sizeof(float), hipMemcpyDeviceToDevice, m->st));
+            EGR_TRY(dev_alloc(m, (size_t)ne * sizeof(float), &p));
+            EGR_HIP(hipMemcpyAsync(p, t.data, (size_t)ne * sizeof(float), hipMemcpyDeviceToDevice, m->ctxs[0]->st));
             w.w = (float*)p;
             m->W[k] = w;
         }
@@ -442,51 +461,44 @@ int pack_all(M* m, const egr_tensor_desc* ts, int n) {
 
 // ------------------------------------------------------------------------------------------------ profiling helpers
 struct ProfScope {
-    M* m; bool on; hipEvent_t a = nullptr, b = nullptr;
-    explicit ProfScope(M* mm, int level = 1) : m(mm), on(mm->profiling >= level) {
-        if (on) { hipEventCreate(&a); hipEventCreate(&b); hipEventRecord(a, m->st); }
+    Fwd& f; bool on; EventPair ev;
+    explicit ProfScope(Fwd& ff, int level = 1) : f(ff), on(ff.prof_level >= level) {
+        if (on) { ev.create(); hipEventRecord(ev.a, f.st); }
     }
     void end(const std::string& kind, double flops, const std::string& detail = std::string()) {
         if (!on) return;
-        hipEventRecord(b, m->st);
-        m->prof.push_back(ProfRec{kind, flops, a, b, detail});
+        hipEventRecord(ev.b, f.st);
+        f.prof->push_back(ProfRec{kind, flops, std::move(ev), detail});
         on = false;
     }
-    ~ProfScope() { if (on) { hipEventDestroy(a); hipEventDestroy(b); } }
 };
+
+// One timed contraction: `launch(ConvChoice*)` enqueues it between the two events of a profile record, which carries the kernel the
+// launcher chose (or `kind`), the flops and `detail`; the flops also go to the forward's sum.
+template <class Launch>
+int timed(Fwd& f, double flops, const char* detail, Launch&& launch, const char* kind = nullptr) {
+    ProfScope ps(f);
+    ConvChoice ran;
+    EGR_TRY(launch(&ran));
+    if (ps.on) ps.end(kind ? kind : egr::conv_choice_name(ran), flops, detail);
+    f.count(flops);
+    return EGR_OK;
+}
 
 // A launch of the graph that is no contraction -- transforms, statistics, norms, gathers, row-maxima passes: at profiling level 2 it
 // shows in egr_flashsr_profile under the name of the entry point called (zero flops), so that a test can see which of them a
 // creation flag selected; at levels 0 and 1 this is the bare call.
 #define OP(fn, ...)                              \
     do {                                         \
-        ProfScope ps__(m, 2);                    \
-        OKR(fn(__VA_ARGS__));                    \
+        ProfScope ps__(f, 2);                    \
+        EGR_TRY(fn(__VA_ARGS__));                    \
         ps__.end(#fn, 0.0);                      \
     } while (0)
 
 // ------------------------------------------------------------------------------------------------ operators
-const void* s3_of(const M* m, const Wt* w, int Cin, const float* x) {
-    if (m->f32_mfma() || !w || Cin % 16 != 0 || (((uintptr_t)x) & 15) != 0) return nullptr;
+const void* s3_of(const Fwd& f, const Wt* w, int Cin, const float* x) {
+    if (f.m.f32_mfma() || !w || Cin % 16 != 0 || (((uintptr_t)x) & 15) != 0) return nullptr;
     return w->w3;
-}
-
-// R-entry slice of the context's pool of per-row maxima (zero at the start of the forward)
-unsigned* rs_take(M* m) {
-    FsrCtx* c = m->cx;
-    if (c->rs_used + (size_t)m->R * EGR_ROW_AMAX_STRIDE > c->rs_cap) {
-        // the start-of-forward size is a heuristic over the layer table; a graph that measures more tensors than it allowed for gets a
-        // second, larger pool here (zeroed on the forward's stream) instead of a failed call -- the next forward starts at that size
-        const size_t grown = std::max(2 * c->rs_cap, (size_t)64 * m->R * EGR_ROW_AMAX_STRIDE);
-        unsigned* np = nullptr;
-        if (hipMalloc((void**)&np, grown * sizeof(unsigned)) != hipSuccess) { set_error("FlashSR: hipMalloc(row maxima pool, %zu entries) failed", grown); return nullptr; }
-        if (hipMemsetAsync(np, 0, grown * sizeof(unsigned), m->st) != hipSuccess) { hipFree(np); set_error("FlashSR: hipMemsetAsync(row maxima pool) failed"); return nullptr; }
-        if (c->rs_pool) c->rs_retired.push_back(c->rs_pool);
-        c->rs_pool = np; c->rs_cap = grown; c->rs_used = 0;
-    }
-    unsigned* p = c->rs_pool + c->rs_used;
-    c->rs_used += (size_t)m->R * EGR_ROW_AMAX_STRIDE;
-    return p;
 }
 
 // Slice for the row maxima of the fresh tensor y, for a producer that leaves them as it writes y.  y.rs stays null -- the producer
@@ -497,20 +509,20 @@ unsigned* rs_take(M* m) {
 // (ROWS_EQUAL on the batch dimension B also covers "y's elements split into R rows": numel is a multiple of B)
 enum RsSwitch { RS_ALWAYS, RS_SWITCHED };
 enum RsRows { ROWS_EQUAL, ROWS_DIVIDE };
-int rs_for_output(M* m, Ten& y, RsSwitch sw, RsRows test, int64_t n) {
-    if (!m->h2_on() || (sw == RS_SWITCHED && !m->out_amax_on) || (test == ROWS_EQUAL ? n != m->R : n % m->R != 0)) return EGR_OK;
-    y.rs = rs_take(m);
+int rs_for_output(Fwd& f, Ten& y, RsSwitch sw, RsRows test, int64_t n) {
+    if (!f.h2 || (sw == RS_SWITCHED && !f.m.out_amax_on) || (test == ROWS_EQUAL ? n != f.R : n % f.R != 0)) return EGR_OK;
+    y.rs = f.cx->take_rows(f.R);
     return y.rs ? EGR_OK : EGR_ERR_ALLOC;
 }
 
 // per-batch-row max |x| of a tensor whose leading dimension runs over the R rows of the forward (nz > 1: nz blocks zx floats
 // apart, the Winograd V layout); measured once per tensor, reused by every later contraction that reads it
-int row_amax_of(M* m, const float* x, int64_t numel, int nz, int64_t zx, unsigned** slot) {
+int row_amax_of(Fwd& f, const float* x, int64_t numel, int nz, int64_t zx, unsigned** slot) {
     if (*slot) return EGR_OK;
-    EGR_CHECK(numel % m->R == 0, EGR_ERR_ARG, "FlashSR: a tensor of %lld elements does not split into %d batch rows", (long long)numel, m->R);
-    unsigned* p = rs_take(m);
+    EGR_CHECK(numel % f.R == 0, EGR_ERR_ARG, "FlashSR: a tensor of %lld elements does not split into %d batch rows", (long long)numel, f.R);
+    unsigned* p = f.cx->take_rows(f.R);
     if (!p) return EGR_ERR_ALLOC;
-    OP(egr_absmax_rows, x, m->R, numel / m->R, nz, zx, (float*)p, m->st);
+    OP(egr_absmax_rows, x, f.R, numel / f.R, nz, zx, (float*)p, f.st);
     *slot = p;
     return EGR_OK;
 }
@@ -520,556 +532,529 @@ int row_amax_of(M* m, const float* x, int64_t numel, int nz, int64_t zx, unsigne
 // or on the fp32 pack when the call cannot be split.  *ran: the kernel the launcher chose (what the profiler reports).
 // y_rs (optional): the launch leaves the per-row maxima of y there (fp16 scheme, nz == 1; a fresh slice is taken when *y_rs is null
 // -- the four phase launches of an up-sampling convolution share one)
-int s3_launch(M* m, const Wt* w, const std::string& key, ConvCall& c, int64_t x_numel, unsigned** x_rs, int64_t zfloats, ConvChoice* ran, unsigned** y_rs = nullptr) {
-    const bool split = s3_of(m, w, c.Cin, c.x) != nullptr;
+int s3_launch(Fwd& f, const Wt* w, const std::string& key, ConvCall& c, int64_t x_numel, unsigned** x_rs, int64_t zfloats, ConvChoice* ran, unsigned** y_rs = nullptr) {
+    const bool split = s3_of(f, w, c.Cin, c.x) != nullptr;
     EGR_CHECK(split || w->w != nullptr, EGR_ERR_ARG, "FlashSR: no fp32 pack for %s", key.c_str());
-    const bool use = split && m->h2_on() && w->w2 && ((int64_t)c.B * c.OH * c.OW) % m->R == 0;
+    const bool use = split && f.h2 && w->w2 && ((int64_t)c.B * c.OH * c.OW) % f.R == 0;
     c.zw = split ? zfloats * (use ? 2 : 3) / 8 : zfloats;
     if (use) {
-        OKR(row_amax_of(m, c.x, c.nz > 1 ? x_numel / c.nz : x_numel, c.nz, c.zx, x_rs));
-        if (y_rs && c.nz == 1 && m->out_amax_on) {
-            if (!*y_rs) *y_rs = rs_take(m);
+        EGR_TRY(row_amax_of(f, c.x, c.nz > 1 ? x_numel / c.nz : x_numel, c.nz, c.zx, x_rs));
+        if (y_rs && c.nz == 1 && f.m.out_amax_on) {
+            if (!*y_rs) *y_rs = f.cx->take_rows(f.R);
             if (!*y_rs) return EGR_ERR_ALLOC;
             c.out_amax = (float*)*y_rs;
         }
     }
-    egr::set_weight(c, *w, use ? *x_rs : nullptr, m->R, split);
-    return egr::conv_call(c, m->st, ran);
+    egr::set_weight(c, *w, use ? *x_rs : nullptr, f.R, split);
+    return egr::conv_call(c, f.st, ran);
 }
 
 // general convolution described by `c`: the caller fills geometry, epilogue and any explicit bias / residual by name; conv() allocates
 // y and completes x, y and the full output extent.  Weights by key (key + ".weight"; the bias is key + ".bias" when key_bias and c.bias
 // is null) or the explicit entry `wk` (no bias from the key).  want_ra: y feeds another split contraction directly, so the epilogue
 // leaves its row maxima.
-int conv(M* m, Ten& y, const Ten& x, const std::string& wkey, ConvCall& c, bool want_ra = false, const Wt* wk = nullptr, bool key_bias = true) {
-    OKR(new_ten(m, y, {c.B, c.OH, c.OW, c.Cout}));
-    const Wt* w = wk ? wk : m->get(wkey + ".weight");
+int conv(Fwd& f, Ten& y, const Ten& x, const std::string& wkey, ConvCall& c, bool want_ra = false, const Wt* wk = nullptr, bool key_bias = true) {
+    EGR_TRY(new_ten(f, y, {c.B, c.OH, c.OW, c.Cout}));
+    const Wt* w = wk ? wk : f.m.get(wkey + ".weight");
     EGR_CHECK(w != nullptr, EGR_ERR_ARG, "FlashSR: weight %s.weight missing", wkey.c_str());
-    if (!c.bias && key_bias && !wk) c.bias = m->ptr(wkey + ".bias");
-    const double fl = 2.0 * c.B * c.OH * c.OW * c.Cout * c.KH * c.KW * c.Cin;
-    ProfScope ps(m);
-    ConvChoice ran;
+    if (!c.bias && key_bias && !wk) c.bias = f.m.ptr(wkey + ".bias");
     c.x = x.p; c.y = y.p; c.OHF = c.OH; c.OWF = c.OW;
-    OKR(s3_launch(m, w, wkey, c, (int64_t)c.B * c.H * c.W * c.Cin, &x.rs, 0, &ran, want_ra ? &y.rs : nullptr));
-    if (ps.on) {
-        char det[160];
+    char det[160] = "";
+    if (f.prof_level >= 1)
         snprintf(det, sizeof(det), "%s B%d %dx%d Cin%d -> %dx%d Cout%d k%dx%d s%d d%d up%d", wkey.c_str(), c.B, c.H, c.W, c.Cin, c.OH, c.OW, c.Cout,
                  c.KH, c.KW, c.stride, c.dil, c.up2);
-        ps.end(egr::conv_choice_name(ran), fl, det);
-    }
-    if (m->count_flops) m->flops += fl;
-    return EGR_OK;
+    return timed(f, 2.0 * c.B * c.OH * c.OW * c.Cout * c.KH * c.KW * c.Cin, det, [&](ConvChoice* ran) {
+        return s3_launch(f, w, wkey, c, (int64_t)c.B * c.H * c.W * c.Cin, &x.rs, 0, ran, want_ra ? &y.rs : nullptr);
+    });
 }
 
-int gn_scratch(M* m, size_t need) {
-    FsrCtx* c = m->cx;
-    if (c->gn_ws_bytes < need) {
-        if (c->gn_ws) { hipStreamSynchronize(m->st); hipFree(c->gn_ws); c->gn_ws = nullptr; c->gn_ws_bytes = 0; }
-        if (hipMalloc(&c->gn_ws, need + 1024) != hipSuccess) { set_error("hipMalloc(GroupNorm workspace) failed"); return EGR_ERR_ALLOC; }
-        c->gn_ws_bytes = need + 1024;
-    }
-    return EGR_OK;
-}
-
-int groupnorm(M* m, Ten& y, const Ten& x, const std::string& key, float eps, bool silu) {
+int groupnorm(Fwd& f, Ten& y, const Ten& x, const std::string& key, float eps, bool silu) {
     const int B = (int)x.d[0], Cc = (int)x.d[x.nd - 1];
     const int HW = (int)(x.numel() / ((int64_t)B * Cc));
-    const int G = m->cfg.gn_groups;
-    OKR(gn_scratch(m, egr_groupnorm_workspace_bytes(B, Cc, G)));
-    OKR(new_like(m, y, x));
-    OKR(rs_for_output(m, y, RS_SWITCHED, ROWS_EQUAL, B));
-    OP(egr_groupnorm_nhwc_ra, x.p, m->ptr(key + ".weight"), m->ptr(key + ".bias"), y.p, B, HW, Cc, G, eps, silu ? 1 : 0, m->cx->gn_ws, (float*)y.rs,
-       m->st);
+    const int G = f.m.cfg.gn_groups;
+    EGR_TRY(f.cx->gn_scratch(egr_groupnorm_workspace_bytes(B, Cc, G)));
+    EGR_TRY(new_like(f, y, x));
+    EGR_TRY(rs_for_output(f, y, RS_SWITCHED, ROWS_EQUAL, B));
+    OP(egr_groupnorm_nhwc_ra, x.p, f.m.ptr(key + ".weight"), f.m.ptr(key + ".bias"), y.p, B, HW, Cc, G, eps, silu ? 1 : 0, f.cx->gn_ws.p, (float*)y.rs,
+       f.st);
     return EGR_OK;
 }
 
-int gn_coeff(M* m, Ten& sc, Ten& sh, const Ten& x, const std::string& key, float eps) {
+int gn_coeff(Fwd& f, Ten& sc, Ten& sh, const Ten& x, const std::string& key, float eps) {
     const int B = (int)x.d[0], Cc = (int)x.d[x.nd - 1];
     const int HW = (int)(x.numel() / ((int64_t)B * Cc));
-    const int G = m->cfg.gn_groups;
-    OKR(gn_scratch(m, egr_groupnorm_workspace_bytes(B, Cc, G)));
-    OKR(new_ten(m, sc, {B, Cc}));
-    OKR(new_ten(m, sh, {B, Cc}));
+    const int G = f.m.cfg.gn_groups;
+    EGR_TRY(f.cx->gn_scratch(egr_groupnorm_workspace_bytes(B, Cc, G)));
+    EGR_TRY(new_ten(f, sc, {B, Cc}));
+    EGR_TRY(new_ten(f, sh, {B, Cc}));
     if (x.part) {        // x came out of egr_winograd4_output_stats: reduce its partials instead of re-reading x
         Ten stats;
-        OKR(new_ten(m, stats, {B, G, 4}));            // [B][G][2] doubles
-        OP(egr_groupnorm_stats_from_partials, x.part->p, B, x.part_tiles, Cc, G, (double*)stats.p, m->st);
-        OP(egr_groupnorm_coeff_from_stats, (const double*)stats.p, m->ptr(key + ".weight"), m->ptr(key + ".bias"), B, HW, Cc, G, eps, sc.p, sh.p, m->st);
+        EGR_TRY(new_ten(f, stats, {B, G, 4}));            // [B][G][2] doubles
+        OP(egr_groupnorm_stats_from_partials, x.part->p, B, x.part_tiles, Cc, G, (double*)stats.p, f.st);
+        OP(egr_groupnorm_coeff_from_stats, (const double*)stats.p, f.m.ptr(key + ".weight"), f.m.ptr(key + ".bias"), B, HW, Cc, G, eps, sc.p, sh.p, f.st);
         return EGR_OK;
     }
-    OP(egr_groupnorm_coeff, x.p, m->ptr(key + ".weight"), m->ptr(key + ".bias"), B, HW, Cc, G, eps, m->cx->gn_ws, sc.p, sh.p, m->st);
+    OP(egr_groupnorm_coeff, x.p, f.m.ptr(key + ".weight"), f.m.ptr(key + ".bias"), B, HW, Cc, G, eps, f.cx->gn_ws.p, sc.p, sh.p, f.st);
     return EGR_OK;
 }
 
-int conv_winograd(M* m, Ten& y, const Ten& x, const std::string& key, int act, const float* res, const float* bias_t, const float* gsc = nullptr,
+int conv_winograd(Fwd& f, Ten& y, const Ten& x, const std::string& key, int act, const float* res, const float* bias_t, const float* gsc = nullptr,
                   const float* gsh = nullptr, int gsilu = 0) {
     const int B = (int)x.d[0], H = (int)x.d[1], W = (int)x.d[2], Cin = (int)x.d[3];
-    const Wt* wb = m->get(key + ".weight");
+    const Wt* wb = f.m.get(key + ".weight");
     const int Cout = wb->Cout;
-    const bool f4 = m->has(key + ".weight.wino4") && H % 4 == 0 && W % 4 == 0;
-    const Wt* wz = m->get(key + (f4 ? ".weight.wino4" : ".weight.wino"));
+    const bool f4 = f.m.has(key + ".weight.wino4") && H % 4 == 0 && W % 4 == 0;
+    const Wt* wz = f.m.get(key + (f4 ? ".weight.wino4" : ".weight.wino"));
     const int nz = f4 ? 36 : 16, ts = f4 ? 4 : 2;
     const int TH = (H + ts - 1) / ts, TW = (W + ts - 1) / ts;
     const int64_t P = (int64_t)B * TH * TW;
     Ten V, Mx;
-    OKR(new_ten(m, V, {nz, P, Cin}));
+    EGR_TRY(new_ten(f, V, {nz, P, Cin}));
     // fp16 operand scheme: the F(4x4) input transform leaves the per-row maxima of V as it writes it
-    if (f4 && wz && wz->w2 && Cin % 16 == 0) OKR(rs_for_output(m, V, RS_ALWAYS, ROWS_EQUAL, B));
-    if (V.rs) OP(egr_winograd4_input_ra, x.p, gsc, gsh, gsilu, B, H, W, Cin, V.p, (float*)V.rs, m->st);
-    else if (f4) OP(egr_winograd4_input, x.p, gsc, gsh, gsilu, B, H, W, Cin, V.p, m->st);
-    else OP(egr_winograd_input, x.p, gsc, gsh, gsilu, B, H, W, Cin, V.p, m->st);
-    OKR(new_ten(m, Mx, {nz, P, Cout}));
-    const double fl = nz * 2.0 * (double)P * Cin * Cout;
-    {
-        ProfScope ps(m);
-        ConvCall c; ConvChoice ran;                    // nz independent [P][Cin] x [Cin][Cout] products
-        c.x = V.p; c.y = Mx.p; c.B = (int)P; c.Cin = Cin; c.Cout = Cout; c.nz = nz; c.zx = P * Cin; c.zy = P * Cout;
-        OKR(s3_launch(m, wz, key + (f4 ? ".weight.wino4" : ".weight.wino"), c, (int64_t)nz * P * Cin, &V.rs, wz->zfloats, &ran));
-        if (ps.on) ps.end(egr::conv_choice_name(ran), fl);
-    }
-    if (m->count_flops) m->flops += fl;
+    if (f4 && wz && wz->w2 && Cin % 16 == 0) EGR_TRY(rs_for_output(f, V, RS_ALWAYS, ROWS_EQUAL, B));
+    if (V.rs) OP(egr_winograd4_input_ra, x.p, gsc, gsh, gsilu, B, H, W, Cin, V.p, (float*)V.rs, f.st);
+    else if (f4) OP(egr_winograd4_input, x.p, gsc, gsh, gsilu, B, H, W, Cin, V.p, f.st);
+    else OP(egr_winograd_input, x.p, gsc, gsh, gsilu, B, H, W, Cin, V.p, f.st);
+    EGR_TRY(new_ten(f, Mx, {nz, P, Cout}));
+    ConvCall c;                                        // nz independent [P][Cin] x [Cin][Cout] products
+    c.x = V.p; c.y = Mx.p; c.B = (int)P; c.Cin = Cin; c.Cout = Cout; c.nz = nz; c.zx = P * Cin; c.zy = P * Cout;
+    EGR_TRY(timed(f, nz * 2.0 * (double)P * Cin * Cout, "", [&](ConvChoice* ran) {
+        return s3_launch(f, wz, key + (f4 ? ".weight.wino4" : ".weight.wino"), c, (int64_t)nz * P * Cin, &V.rs, wz->zfloats, ran);
+    }));
     V.release();
-    OKR(new_ten(m, y, {B, H, W, Cout}));
-    const float* bt = bias_t ? bias_t : m->ptr(key + ".bias");
-    const int G = m->cfg.gn_groups;
+    EGR_TRY(new_ten(f, y, {B, H, W, Cout}));
+    const float* bt = bias_t ? bias_t : f.m.ptr(key + ".bias");
+    const int G = f.m.cfg.gn_groups;
     const int silu = act == ACT_SILU ? 1 : 0;
     // fp16 operand scheme: the output transform leaves the per-row maxima of y (it may feed a 1x1 / strided / phase convolution)
-    if (f4) OKR(rs_for_output(m, y, RS_SWITCHED, ROWS_EQUAL, B));
+    if (f4) EGR_TRY(rs_for_output(f, y, RS_SWITCHED, ROWS_EQUAL, B));
     float* const y_ra = (float*)y.rs;
-    if (f4 && !(m->flags & EGR_FSR_NO_GN_PARTIALS) && Cout % G == 0 && (Cout / G) % 4 == 0) {
+    if (f4 && !(f.m.flags & EGR_FSR_NO_GN_PARTIALS) && Cout % G == 0 && (Cout / G) % 4 == 0) {
         auto part = std::make_shared<Ten>();
-        OKR(new_ten(m, *part, {P, Cout / 4, 2}));
-        OP(egr_winograd4_output_ra, Mx.p, bt, res, y.p, B, H, W, Cout, silu, part->p, y_ra, m->st);
+        EGR_TRY(new_ten(f, *part, {P, Cout / 4, 2}));
+        OP(egr_winograd4_output_ra, Mx.p, bt, res, y.p, B, H, W, Cout, silu, part->p, y_ra, f.st);
         y.part = part;
         y.part_tiles = TH * TW;
     } else if (f4) {
-        OP(egr_winograd4_output_ra, Mx.p, bt, res, y.p, B, H, W, Cout, silu, nullptr, y_ra, m->st);
+        OP(egr_winograd4_output_ra, Mx.p, bt, res, y.p, B, H, W, Cout, silu, nullptr, y_ra, f.st);
     } else {
-        OP(egr_winograd_output, Mx.p, bt, res, y.p, B, H, W, Cout, silu, m->st);
+        OP(egr_winograd_output, Mx.p, bt, res, y.p, B, H, W, Cout, silu, f.st);
     }
     return EGR_OK;
 }
 
-int conv_up2_phases(M* m, Ten& y, const Ten& x, const std::string& key, int act) {
+int conv_up2_phases(Fwd& f, Ten& y, const Ten& x, const std::string& key, int act) {
     const int B = (int)x.d[0], H = (int)x.d[1], W = (int)x.d[2], Cin = (int)x.d[3];
-    const int Cout = m->get(key + ".weight")->Cout;
-    OKR(new_ten(m, y, {B, 2 * H, 2 * W, Cout}));
-    const float* bt = m->ptr(key + ".bias");
+    const int Cout = f.m.get(key + ".weight")->Cout;
+    EGR_TRY(new_ten(f, y, {B, 2 * H, 2 * W, Cout}));
+    const float* bt = f.m.ptr(key + ".bias");
     for (int a = 0; a < 2; ++a)
         for (int b = 0; b < 2; ++b) {
-            const Wt* w = m->get(key + ".weight.ph" + std::to_string(a) + std::to_string(b));
-            const double fl = 2.0 * B * H * W * Cout * 4 * Cin;
-            ProfScope ps(m);
-            ConvCall c; ConvChoice ran;               // 2x2 kernel on the low-res input, written to phase (a, b) of the 2H x 2W output
+            const Wt* w = f.m.get(key + ".weight.ph" + std::to_string(a) + std::to_string(b));
+            ConvCall c;                               // 2x2 kernel on the low-res input, written to phase (a, b) of the 2H x 2W output
             c.x = x.p; c.bias = bt; c.y = y.p; c.B = B; c.H = c.OH = H; c.W = c.OW = W; c.Cin = Cin; c.Cout = Cout; c.KH = c.KW = 2;
             c.pad_t = 1 - a; c.pad_l = 1 - b; c.act = act; c.osy = c.osx = 2; c.ooy = a; c.oox = b; c.OHF = 2 * H; c.OWF = 2 * W;
-            OKR(s3_launch(m, w, key + ".weight.ph", c, (int64_t)B * H * W * Cin, &x.rs, 0, &ran, &y.rs));
-            if (ps.on) ps.end(egr::conv_choice_name(ran), fl);
-            if (m->count_flops) m->flops += fl;
+            EGR_TRY(timed(f, 2.0 * B * H * W * Cout * 4 * Cin, "", [&](ConvChoice* ran) {
+                return s3_launch(f, w, key + ".weight.ph", c, (int64_t)B * H * W * Cin, &x.rs, 0, ran, &y.rs);
+            }));
         }
     return EGR_OK;
 }
 
 // want_ra reaches only the generic exit; the phase, Winograd, tap-gather and one-input-channel exits track y's row maxima, or not, on their own
-int conv3(M* m, Ten& y, const Ten& x, const std::string& key, int stride = 1, int up2 = 0, int act = ACT_NONE, const float* res = nullptr,
+int conv3(Fwd& f, Ten& y, const Ten& x, const std::string& key, int stride = 1, int up2 = 0, int act = ACT_NONE, const float* res = nullptr,
           int pad = 1, const float* bias_t = nullptr, bool want_ra = false) {
     const int B = (int)x.d[0], H = (int)x.d[1], W = (int)x.d[2], Cin = (int)x.d[3];
-    const Wt* wb = m->get(key + ".weight");
+    const Wt* wb = f.m.get(key + ".weight");
     EGR_CHECK(wb != nullptr, EGR_ERR_ARG, "FlashSR: weight %s.weight missing", key.c_str());
     const int Cout = wb->Cout;
-    if (up2 && m->has(key + ".weight.ph00") && stride == 1 && pad == 1 && !res && !bias_t) return conv_up2_phases(m, y, x, key, act);
-    if (m->has(key + ".weight.wino") && !up2 && stride == 1 && pad == 1 && (act == ACT_NONE || act == ACT_SILU) && H % 2 == 0 && W % 2 == 0 &&
+    if (up2 && f.m.has(key + ".weight.ph00") && stride == 1 && pad == 1 && !res && !bias_t) return conv_up2_phases(f, y, x, key, act);
+    if (f.m.has(key + ".weight.wino") && !up2 && stride == 1 && pad == 1 && (act == ACT_NONE || act == ACT_SILU) && H % 2 == 0 && W % 2 == 0 &&
         Cin % 16 == 0)
-        return conv_winograd(m, y, x, key, act, res, bias_t);
+        return conv_winograd(f, y, x, key, act, res, bias_t);
     const bool plain = !up2 && stride == 1 && pad == 1 && act == ACT_NONE && !res && !bias_t;
-    const bool thin = !(m->flags & EGR_FSR_NO_THIN_ENDS);
-    const Wt* taps = m->get(key + ".weight.taps");
-    if (plain && taps && s3_of(m, taps, Cin, x.p)) {
+    const bool thin = !(f.m.flags & EGR_FSR_NO_THIN_ENDS);
+    const Wt* taps = f.m.get(key + ".weight.taps");
+    if (plain && taps && s3_of(f, taps, Cin, x.p)) {
         Ten P;
         ConvCall c;                                   // 1x1 contraction onto the nine per-tap products
         c.B = B; c.H = c.OH = H; c.W = c.OW = W; c.Cin = Cin; c.Cout = 9 * Cout;
-        OKR(conv(m, P, x, key, c, NO_RA, taps));
-        OKR(new_ten(m, y, {B, H, W, Cout}));
-        OP(egr_tap_gather, P.p, m->ptr(key + ".bias"), y.p, B, H, W, 3, 3, Cout, 1, 1, m->st);
+        EGR_TRY(conv(f, P, x, key, c, NO_RA, taps));
+        EGR_TRY(new_ten(f, y, {B, H, W, Cout}));
+        OP(egr_tap_gather, P.p, f.m.ptr(key + ".bias"), y.p, B, H, W, 3, 3, Cout, 1, 1, f.st);
         return EGR_OK;
     }
     if (plain && thin && Cin == 1 && Cout % 4 == 0 && 256 % (Cout / 4) == 0) {
-        OKR(new_ten(m, y, {B, H, W, Cout}));
-        OP(egr_conv_cin1, x.p, wb->w, m->ptr(key + ".bias"), y.p, B, H, W, Cout, 3, 3, 1, 1, m->st);
-        if (m->count_flops) m->flops += 2.0 * B * H * W * Cout * 9;
+        EGR_TRY(new_ten(f, y, {B, H, W, Cout}));
+        OP(egr_conv_cin1, x.p, wb->w, f.m.ptr(key + ".bias"), y.p, B, H, W, Cout, 3, 3, 1, 1, f.st);
+        f.count(2.0 * B * H * W * Cout * 9);
         return EGR_OK;
     }
     ConvCall c;                                       // the generic exit: the only one that takes the request for y's row maxima
     c.B = B; c.H = H; c.W = W; c.Cin = Cin; c.OH = (up2 ? 2 * H : H) / stride; c.OW = (up2 ? 2 * W : W) / stride; c.Cout = Cout; c.KH = c.KW = 3;
     c.stride = stride; c.pad_t = c.pad_l = pad; c.up2 = up2; c.act = act; c.bias = bias_t; c.res = res;
-    return conv(m, y, x, key, c, want_ra);
+    return conv(f, y, x, key, c, want_ra);
 }
 
-int conv1x1(M* m, Ten& y, const Ten& x, const std::string& key, const float* res = nullptr, int act = ACT_NONE, bool want_ra = false) {
+int conv1x1(Fwd& f, Ten& y, const Ten& x, const std::string& key, const float* res = nullptr, int act = ACT_NONE, bool want_ra = false) {
     ConvCall c;
-    c.B = (int)x.d[0]; c.H = c.OH = (int)x.d[1]; c.W = c.OW = (int)x.d[2]; c.Cin = (int)x.d[3]; c.Cout = m->get(key + ".weight")->Cout;
+    c.B = (int)x.d[0]; c.H = c.OH = (int)x.d[1]; c.W = c.OW = (int)x.d[2]; c.Cin = (int)x.d[3]; c.Cout = f.m.get(key + ".weight")->Cout;
     c.act = act; c.res = res;
-    return conv(m, y, x, key, c, want_ra);
+    return conv(f, y, x, key, c, want_ra);
 }
 
-int linear(M* m, Ten& y, const Ten& x2, const std::string& key, const float* res = nullptr, int act = ACT_NONE, bool bias = true,
+int linear(Fwd& f, Ten& y, const Ten& x2, const std::string& key, const float* res = nullptr, int act = ACT_NONE, bool bias = true,
            bool want_ra = false) {
-    const Wt* w = m->get(key + ".weight");
+    const Wt* w = f.m.get(key + ".weight");
     EGR_CHECK(w != nullptr, EGR_ERR_ARG, "FlashSR: weight %s.weight missing", key.c_str());
     ConvCall c;
     c.B = (int)x2.d[0]; c.Cin = (int)x2.d[1]; c.Cout = w->Cout; c.act = act; c.res = res;
-    OKR(conv(m, y, x2, key, c, want_ra, nullptr, bias));
+    EGR_TRY(conv(f, y, x2, key, c, want_ra, nullptr, bias));
     y.view({c.B, w->Cout});
     return EGR_OK;
 }
 
-int conv1d(M* m, Ten& y, const Ten& x, const std::string& key, int k, int stride = 1, int dil = 1, int pad = 0, int act = ACT_NONE,
+int conv1d(Fwd& f, Ten& y, const Ten& x, const std::string& key, int k, int stride = 1, int dil = 1, int pad = 0, int act = ACT_NONE,
            const float* res = nullptr, bool want_ra = false) {
     ConvCall c;
-    c.B = (int)x.d[0]; c.W = (int)x.d[1]; c.Cin = (int)x.d[2]; c.Cout = m->get(key + ".weight")->Cout; c.KW = k;
+    c.B = (int)x.d[0]; c.W = (int)x.d[1]; c.Cin = (int)x.d[2]; c.Cout = f.m.get(key + ".weight")->Cout; c.KW = k;
     c.OW = (c.W + 2 * pad - dil * (k - 1) - 1) / stride + 1; c.stride = stride; c.dil = dil; c.pad_l = pad; c.act = act; c.res = res;
-    OKR(conv(m, y, x, key, c, want_ra));
+    EGR_TRY(conv(f, y, x, key, c, want_ra));
     y.view({c.B, c.OW, c.Cout});
     return EGR_OK;
 }
 
 // conv3x3(silu(groupnorm(x))) with the normalisation fused into the Winograd input transform when the layer takes that path
-int gn_conv3(M* m, Ten& y, const Ten& x, const std::string& norm_key, float eps, const std::string& conv_key, const float* res = nullptr,
+int gn_conv3(Fwd& f, Ten& y, const Ten& x, const std::string& norm_key, float eps, const std::string& conv_key, const float* res = nullptr,
              const float* bias_t = nullptr) {
     const int H = (int)x.d[1], W = (int)x.d[2], Cin = (int)x.d[3];
     // The big, thin layers (128 output channels on 512 x 256 images) as DIRECT convolutions on the input-stationary kernel with the
     // GroupNorm + SiLU in its loader (fp16 operand scheme only): as an F(4x4) pipeline they are bound by V and M round trips
     // (~19 GB per layer against 3.5 GB of activations), here x is read once and y written once.
     {
-        const Wt* wd = m->get(conv_key + ".weight");
+        const Wt* wd = f.m.get(conv_key + ".weight");
         const int B = (int)x.d[0];
-        if (wd && wd->w2 && m->h2_on() && m->direct3x3_max_cout > 0 && wd->Cout <= m->direct3x3_max_cout && wd->KH == 3 &&
-            wd->KW == 3 && B == m->R && H % 4 == 0 && W % 32 == 0 && Cin % 32 == 0 && (int64_t)(H / 4) * (W / 32) * B >= 512 &&
-            Cin % m->cfg.gn_groups == 0 && (((uintptr_t)x.p) & 15) == 0) {
+        if (wd && wd->w2 && f.h2 && f.m.direct3x3_max_cout > 0 && wd->Cout <= f.m.direct3x3_max_cout && wd->KH == 3 &&
+            wd->KW == 3 && B == f.R && H % 4 == 0 && W % 32 == 0 && Cin % 32 == 0 && (int64_t)(H / 4) * (W / 32) * B >= 512 &&
+            Cin % f.m.cfg.gn_groups == 0 && (((uintptr_t)x.p) & 15) == 0) {
             Ten sc, sh;
-            OKR(gn_coeff(m, sc, sh, x, norm_key, eps));
-            OKR(row_amax_of(m, x.p, x.numel(), 1, 0, &x.rs));
-            unsigned* bound = rs_take(m);
+            EGR_TRY(gn_coeff(f, sc, sh, x, norm_key, eps));
+            EGR_TRY(row_amax_of(f, x.p, x.numel(), 1, 0, &x.rs));
+            unsigned* bound = f.cx->take_rows(f.R);
             if (!bound) return EGR_ERR_ALLOC;
-            OP(egr_gn_operand_bound, sc.p, sh.p, B, Cin, (const float*)x.rs, (float*)bound, m->st);
-            OKR(new_ten(m, y, {B, H, W, wd->Cout}));
-            OKR(rs_for_output(m, y, RS_SWITCHED, ROWS_EQUAL, B));
-            const float* bt = bias_t ? bias_t : m->ptr(conv_key + ".bias");
-            const double fl = 2.0 * B * H * W * (double)wd->Cout * 9 * Cin;
+            OP(egr_gn_operand_bound, sc.p, sh.p, B, Cin, (const float*)x.rs, (float*)bound, f.st);
+            EGR_TRY(new_ten(f, y, {B, H, W, wd->Cout}));
+            EGR_TRY(rs_for_output(f, y, RS_SWITCHED, ROWS_EQUAL, B));
+            const float* bt = bias_t ? bias_t : f.m.ptr(conv_key + ".bias");
             // GroupNorm partial statistics of y from the epilogue (the next norm then reads 1/32 of y's bytes instead of y)
             void* gpart = nullptr;
-            const int G = m->cfg.gn_groups;
-            if (!(m->flags & EGR_FSR_NO_GN_PARTIALS) && wd->Cout % G == 0 && (wd->Cout / G) % 4 == 0) {
+            const int G = f.m.cfg.gn_groups;
+            if (!(f.m.flags & EGR_FSR_NO_GN_PARTIALS) && wd->Cout % G == 0 && (wd->Cout / G) % 4 == 0) {
                 auto part = std::make_shared<Ten>();
-                OKR(new_ten(m, *part, {(int64_t)B * H * W / 32, wd->Cout / 4, 2}));
+                EGR_TRY(new_ten(f, *part, {(int64_t)B * H * W / 32, wd->Cout / 4, 2}));
                 gpart = part->p;
                 y.part = part;
                 y.part_tiles = H * W / 32;
             }
-            ProfScope ps(m);
-            ConvCall c; ConvChoice ran;
+            ConvCall c;
             c.x = x.p; c.bias = bt; c.res = res; c.y = y.p; c.gn_scale = sc.p; c.gn_shift = sh.p; c.gn_silu = 1;
             c.B = B; c.H = c.OH = c.OHF = H; c.W = c.OW = c.OWF = W; c.Cin = Cin; c.Cout = wd->Cout; c.KH = c.KW = 3; c.pad_t = c.pad_l = 1;
             egr::set_weight(c, *wd, bound, B);
             c.out_amax = (float*)y.rs; c.gn_part = gpart;
-            OKR(egr::conv_call(c, m->st, &ran));
-            if (ps.on) ps.end(egr::conv_choice_name(ran), fl, conv_key);
-            if (m->count_flops) m->flops += fl;
-            return EGR_OK;
+            return timed(f, 2.0 * B * H * W * (double)wd->Cout * 9 * Cin, conv_key.c_str(), [&](ConvChoice* ran) { return egr::conv_call(c, f.st, ran); });
         }
     }
-    const bool wino = m->has(conv_key + ".weight.wino") && H % 2 == 0 && W % 2 == 0;
-    const bool fused_ok = !(m->flags & EGR_FSR_NO_FUSE_GN) && Cin % 16 == 0 && Cin % m->cfg.gn_groups == 0 && wino;
+    const bool wino = f.m.has(conv_key + ".weight.wino") && H % 2 == 0 && W % 2 == 0;
+    const bool fused_ok = !(f.m.flags & EGR_FSR_NO_FUSE_GN) && Cin % 16 == 0 && Cin % f.m.cfg.gn_groups == 0 && wino;
     if (!fused_ok) {
         Ten h;
-        OKR(groupnorm(m, h, x, norm_key, eps, true));
-        return conv3(m, y, h, conv_key, 1, 0, ACT_NONE, res, 1, bias_t);
+        EGR_TRY(groupnorm(f, h, x, norm_key, eps, true));
+        return conv3(f, y, h, conv_key, 1, 0, ACT_NONE, res, 1, bias_t);
     }
     Ten sc, sh;
-    OKR(gn_coeff(m, sc, sh, x, norm_key, eps));
-    return conv_winograd(m, y, x, conv_key, ACT_NONE, res, bias_t, sc.p, sh.p, 1);
+    EGR_TRY(gn_coeff(f, sc, sh, x, norm_key, eps));
+    return conv_winograd(f, y, x, conv_key, ACT_NONE, res, bias_t, sc.p, sh.p, 1);
 }
 
-int layernorm(M* m, Ten& y, const Ten& x2, const std::string& key) {
-    OKR(new_ten(m, y, {x2.d[0], x2.d[1]}));
-    OKR(rs_for_output(m, y, RS_SWITCHED, ROWS_DIVIDE, x2.d[0]));
-    if (!y.rs) OP(egr_layernorm_rows, x2.p, m->ptr(key + ".weight"), m->ptr(key + ".bias"), y.p, x2.d[0], (int)x2.d[1], 1e-5f, m->st);
-    else OP(egr_layernorm_rows_ra, x2.p, m->ptr(key + ".weight"), m->ptr(key + ".bias"), y.p, x2.d[0], (int)x2.d[1], 1e-5f, m->R, (float*)y.rs, m->st);
+int layernorm(Fwd& f, Ten& y, const Ten& x2, const std::string& key) {
+    EGR_TRY(new_ten(f, y, {x2.d[0], x2.d[1]}));
+    EGR_TRY(rs_for_output(f, y, RS_SWITCHED, ROWS_DIVIDE, x2.d[0]));
+    if (!y.rs) OP(egr_layernorm_rows, x2.p, f.m.ptr(key + ".weight"), f.m.ptr(key + ".bias"), y.p, x2.d[0], (int)x2.d[1], 1e-5f, f.st);
+    else OP(egr_layernorm_rows_ra, x2.p, f.m.ptr(key + ".weight"), f.m.ptr(key + ".bias"), y.p, x2.d[0], (int)x2.d[1], 1e-5f, f.R, (float*)y.rs, f.st);
     return EGR_OK;
 }
 
-int eltwise(M* m, Ten& y, const Ten& a, const float* b, int op, float s0 = 0.f, float s1 = 0.f, bool want_ra = false) {
-    OKR(new_like(m, y, a));
-    if (want_ra) OKR(rs_for_output(m, y, RS_SWITCHED, ROWS_DIVIDE, y.numel()));
-    if (!y.rs) OP(egr_eltwise, a.p, b, y.p, a.numel(), op, s0, s1, m->st);
-    else OP(egr_eltwise_ra, a.p, b, y.p, a.numel(), op, s0, s1, m->R, (float*)y.rs, m->st);
+int eltwise(Fwd& f, Ten& y, const Ten& a, const float* b, int op, float s0 = 0.f, float s1 = 0.f, bool want_ra = false) {
+    EGR_TRY(new_like(f, y, a));
+    if (want_ra) EGR_TRY(rs_for_output(f, y, RS_SWITCHED, ROWS_DIVIDE, y.numel()));
+    if (!y.rs) OP(egr_eltwise, a.p, b, y.p, a.numel(), op, s0, s1, f.st);
+    else OP(egr_eltwise_ra, a.p, b, y.p, a.numel(), op, s0, s1, f.R, (float*)y.rs, f.st);
     return EGR_OK;
 }
 
 // q, k, v [B*T][C] -> [B*T][C]: softmax(q k^T / sqrt(d)) v per head
-int attention(M* m, Ten& o, const Ten& q, const Ten& k, const Ten& v, int B, int T, int Cc, int heads) {
+int attention(Fwd& f, Ten& o, const Ten& q, const Ten& k, const Ten& v, int B, int T, int Cc, int heads) {
     const int d = Cc / heads;
     Ten S;
-    OKR(new_ten(m, S, {B, heads, T, T}));
-    const bool s3 = !m->f32_mfma() && d % 16 == 0 && T % 16 == 0 && Cc % 4 == 0;
-    const float scale = 1.0f / sqrtf((float)d);
+    EGR_TRY(new_ten(f, S, {B, heads, T, T}));
+    const bool s3 = !f.m.f32_mfma() && d % 16 == 0 && T % 16 == 0 && Cc % 4 == 0;
     const float sc = (float)pow((double)d, -0.5);
-    (void)scale;
     // fp16 operand scheme: both products on two fp16 terms, every operand scaled per batch row from its own maximum (q / k / v carry
     // theirs from the epilogues of their projections; the soft-max output lies in [0, 1]: a constant)
-    const bool h2 = s3 && m->h2_on() && B == m->R;
+    const bool h2 = s3 && f.h2 && B == f.R;
     if (h2) {
-        OKR(row_amax_of(m, q.p, q.numel(), 1, 0, &q.rs));
-        OKR(row_amax_of(m, k.p, k.numel(), 1, 0, &k.rs));
-        OKR(row_amax_of(m, v.p, v.numel(), 1, 0, &v.rs));
-        OKR(egr_bgemm_nt_h2(q.p, k.p, S.p, B, heads, T, T, d, Cc, Cc, T, (int64_t)T * Cc, d, (int64_t)T * Cc, d, (int64_t)heads * T * T,
-                            (int64_t)T * T, sc, (const float*)q.rs, (const float*)k.rs, nullptr, m->st));
+        EGR_TRY(row_amax_of(f, q.p, q.numel(), 1, 0, &q.rs));
+        EGR_TRY(row_amax_of(f, k.p, k.numel(), 1, 0, &k.rs));
+        EGR_TRY(row_amax_of(f, v.p, v.numel(), 1, 0, &v.rs));
+        EGR_TRY(egr_bgemm_nt_h2(q.p, k.p, S.p, B, heads, T, T, d, Cc, Cc, T, (int64_t)T * Cc, d, (int64_t)T * Cc, d, (int64_t)heads * T * T,
+                            (int64_t)T * T, sc, (const float*)q.rs, (const float*)k.rs, nullptr, f.st));
     } else if (s3)
-        OKR(egr_bgemm_nt_s3(q.p, k.p, S.p, B, heads, T, T, d, Cc, Cc, T, (int64_t)T * Cc, d, (int64_t)T * Cc, d, (int64_t)heads * T * T,
-                            (int64_t)T * T, sc, m->st));
+        EGR_TRY(egr_bgemm_nt_s3(q.p, k.p, S.p, B, heads, T, T, d, Cc, Cc, T, (int64_t)T * Cc, d, (int64_t)T * Cc, d, (int64_t)heads * T * T,
+                            (int64_t)T * T, sc, f.st));
     else
-        OKR(egr_bgemm(q.p, k.p, S.p, B, heads, T, T, d, Cc, Cc, T, (int64_t)T * Cc, d, (int64_t)T * Cc, d, (int64_t)heads * T * T, (int64_t)T * T, 1,
-                      sc, m->st));
-    OKR(egr_softmax_rows(S.p, (int64_t)B * heads * T, T, m->st));
-    OKR(new_ten(m, o, {(int64_t)B * T, Cc}));
+        EGR_TRY(egr_bgemm(q.p, k.p, S.p, B, heads, T, T, d, Cc, Cc, T, (int64_t)T * Cc, d, (int64_t)T * Cc, d, (int64_t)heads * T * T, (int64_t)T * T, 1,
+                      sc, f.st));
+    EGR_TRY(egr_softmax_rows(S.p, (int64_t)B * heads * T, T, f.st));
+    EGR_TRY(new_ten(f, o, {(int64_t)B * T, Cc}));
     if (s3) {
         Ten vt;
-        OKR(new_ten(m, vt, {B, Cc, T}));
-        OKR(egr_transpose_batched(v.p, vt.p, B, T, Cc, m->st));
+        EGR_TRY(new_ten(f, vt, {B, Cc, T}));
+        EGR_TRY(egr_transpose_batched(v.p, vt.p, B, T, Cc, f.st));
         if (h2) {
-            OKR(rs_for_output(m, o, RS_SWITCHED, ROWS_EQUAL, B));   // o feeds the output projection (B == R here, so o splits into the rows)
-            OKR(egr_bgemm_nt_h2(S.p, vt.p, o.p, B, heads, T, d, T, T, T, Cc, (int64_t)heads * T * T, (int64_t)T * T, (int64_t)Cc * T, (int64_t)d * T,
-                                (int64_t)T * Cc, d, 1.0f, (const float*)m->cx->rs_ones, (const float*)v.rs, (float*)o.rs, m->st));
+            EGR_TRY(rs_for_output(f, o, RS_SWITCHED, ROWS_EQUAL, B));   // o feeds the output projection (B == R here, so o splits into the rows)
+            EGR_TRY(egr_bgemm_nt_h2(S.p, vt.p, o.p, B, heads, T, d, T, T, T, Cc, (int64_t)heads * T * T, (int64_t)T * T, (int64_t)Cc * T, (int64_t)d * T,
+                                (int64_t)T * Cc, d, 1.0f, f.cx->rs_ones.as<float>(), (const float*)v.rs, (float*)o.rs, f.st));
         } else
-        OKR(egr_bgemm_nt_s3(S.p, vt.p, o.p, B, heads, T, d, T, T, T, Cc, (int64_t)heads * T * T, (int64_t)T * T, (int64_t)Cc * T, (int64_t)d * T,
-                            (int64_t)T * Cc, d, 1.0f, m->st));
+        EGR_TRY(egr_bgemm_nt_s3(S.p, vt.p, o.p, B, heads, T, d, T, T, T, Cc, (int64_t)heads * T * T, (int64_t)T * T, (int64_t)Cc * T, (int64_t)d * T,
+                            (int64_t)T * Cc, d, 1.0f, f.st));
     } else {
-        OKR(egr_bgemm(S.p, v.p, o.p, B, heads, T, d, T, T, Cc, Cc, (int64_t)heads * T * T, (int64_t)T * T, (int64_t)T * Cc, d, (int64_t)T * Cc, d, 0,
-                      1.0f, m->st));
+        EGR_TRY(egr_bgemm(S.p, v.p, o.p, B, heads, T, d, T, T, Cc, Cc, (int64_t)heads * T * T, (int64_t)T * T, (int64_t)T * Cc, d, (int64_t)T * Cc, d, 0,
+                      1.0f, f.st));
     }
-    if (m->count_flops) m->flops += 4.0 * B * heads * (double)T * T * d;
+    f.count(4.0 * B * heads * (double)T * T * d);
     return EGR_OK;
 }
 
-int snake(M* m, Ten& y, const Ten& x, const std::string& akey, const std::string& bkey) {
-    OKR(new_ten(m, y, {x.d[0], x.d[1], x.d[2]}));
-    OKR(rs_for_output(m, y, RS_ALWAYS, ROWS_EQUAL, (int)x.d[0]));   // fp16 operand scheme: y feeds a 1-D convolution; its row maxima ride along
-    OP(egr_snake_aa_ra, x.p, m->ptr(akey), m->ptr(bkey), m->filt, y.p, (int)x.d[0], (int)x.d[1], (int)x.d[2], m->cfg.aa_taps, (float*)y.rs, m->st);
+int snake(Fwd& f, Ten& y, const Ten& x, const std::string& akey, const std::string& bkey) {
+    EGR_TRY(new_ten(f, y, {x.d[0], x.d[1], x.d[2]}));
+    EGR_TRY(rs_for_output(f, y, RS_ALWAYS, ROWS_EQUAL, (int)x.d[0]));   // fp16 operand scheme: y feeds a 1-D convolution; its row maxima ride along
+    OP(egr_snake_aa_ra, x.p, f.m.ptr(akey), f.m.ptr(bkey), f.m.filt, y.p, (int)x.d[0], (int)x.d[1], (int)x.d[2], f.m.cfg.aa_taps, (float*)y.rs, f.st);
     return EGR_OK;
 }
 
-int concat(M* m, Ten& y, const Ten& a, const Ten& b) {
+int concat(Fwd& f, Ten& y, const Ten& a, const Ten& b) {
     const int64_t rows = a.d[0] * a.d[1] * a.d[2];
-    OKR(new_ten(m, y, {a.d[0], a.d[1], a.d[2], a.d[3] + b.d[3]}));
-    OKR(rs_for_output(m, y, RS_SWITCHED, ROWS_EQUAL, (int)a.d[0]));
-    if (!y.rs) OP(egr_concat_channels, a.p, b.p, y.p, rows, (int)a.d[3], (int)b.d[3], m->st);
-    else OP(egr_concat_channels_ra, a.p, b.p, y.p, rows, (int)a.d[3], (int)b.d[3], m->R, (float*)y.rs, m->st);
+    EGR_TRY(new_ten(f, y, {a.d[0], a.d[1], a.d[2], a.d[3] + b.d[3]}));
+    EGR_TRY(rs_for_output(f, y, RS_SWITCHED, ROWS_EQUAL, (int)a.d[0]));
+    if (!y.rs) OP(egr_concat_channels, a.p, b.p, y.p, rows, (int)a.d[3], (int)b.d[3], f.st);
+    else OP(egr_concat_channels_ra, a.p, b.p, y.p, rows, (int)a.d[3], (int)b.d[3], f.R, (float*)y.rs, f.st);
     return EGR_OK;
 }
 
 // ------------------------------------------------------------------------------------------------ constant sub-graph
 // time embedding at t = T-1: silu(MLP(emb)) is shared by all res-blocks; each block's projection is folded into its conv bias
-int fold_time_embedding(M* m, const float* emb_dev) {
-    const egr_flashsr_config& c = m->cfg;
+int fold_time_embedding(M* model, const float* emb_dev) {
+    const egr_flashsr_config& c = model->cfg;
+    Fwd f(*model, model->ctxs[0].get(), 1, false);   // creation: one row on the bf16 terms, context 0, nothing recorded
     Ten emb, t1, t2;
-    OKR(new_ten(m, emb, {1, c.unet_ch}));
-    EGR_HIP(hipMemcpyAsync(emb.p, emb_dev, (size_t)c.unet_ch * 4, hipMemcpyDeviceToDevice, m->st));
-    OKR(linear(m, t1, emb, "unet.time_embed.0", nullptr, ACT_SILU));
-    OKR(linear(m, t2, t1, "unet.time_embed.2", nullptr, ACT_SILU));
-    for (size_t i = 0; i < m->blk_name.size(); ++i) {
-        const std::string& name = m->blk_name[i];
+    EGR_TRY(new_ten(f, emb, {1, c.unet_ch}));
+    EGR_HIP(hipMemcpyAsync(emb.p, emb_dev, (size_t)c.unet_ch * 4, hipMemcpyDeviceToDevice, f.st));
+    EGR_TRY(linear(f, t1, emb, "unet.time_embed.0", nullptr, ACT_SILU));
+    EGR_TRY(linear(f, t2, t1, "unet.time_embed.2", nullptr, ACT_SILU));
+    for (size_t i = 0; i < f.m.blk_name.size(); ++i) {
+        const std::string& name = f.m.blk_name[i];
         if (!ends_with(name, ".block")) continue;
         const std::string base = "unet." + name;
         Ten e;
-        OKR(linear(m, e, t2, base + ".res.emb"));
-        const Wt* b = m->get(base + ".res.in_conv.bias");
+        EGR_TRY(linear(f, e, t2, base + ".res.emb"));
+        const Wt* b = f.m.get(base + ".res.in_conv.bias");
         EGR_CHECK(b != nullptr, EGR_ERR_ARG, "FlashSR: %s.res.in_conv.bias missing", base.c_str());
         Wt bt;
         bt.numel = b->numel;
         void* p = nullptr;
-        OKR(dev_alloc(m, (size_t)b->numel * 4, &p));
+        EGR_TRY(dev_alloc(model, (size_t)b->numel * 4, &p));
         bt.w = (float*)p;
-        OKR(egr_eltwise(b->w, e.p, bt.w, b->numel, EW_ADD, 0.f, 0.f, m->st));
-        m->W[base + ".res.in_conv.bias_t"] = bt;
+        EGR_TRY(egr_eltwise(b->w, e.p, bt.w, b->numel, EW_ADD, 0.f, 0.f, f.st));
+        model->W[base + ".res.in_conv.bias_t"] = bt;
     }
-    EGR_HIP(hipStreamSynchronize(m->st));
+    EGR_HIP(hipStreamSynchronize(f.st));
     return EGR_OK;
 }
 
 // ------------------------------------------------------------------------------------------------ stages
-int log_mel(M* m, Ten& mel, const float* x, int B, int L) {
-    const egr_flashsr_config& c = m->cfg;
+int log_mel(Fwd& f, Ten& mel, const float* x, int B, int L) {
+    const egr_flashsr_config& c = f.m.cfg;
     const int rpad = (c.n_fft - c.hop) / 2;
     const int t_valid = std::min(c.n_frames, (L + 2 * rpad - c.n_fft) / c.hop + 1);
     Ten mag;
-    OKR(new_ten(m, mag, {B, c.n_frames, m->ldm}));
-    OKR(egr_stft_frames(x, B, L, c.n_fft, c.hop, rpad, c.n_frames, t_valid, m->ldm, m->window, mag.p, m->st));
-    mag.view({(int64_t)B * c.n_frames, 1, 1, m->ldm});
+    EGR_TRY(new_ten(f, mag, {B, c.n_frames, f.m.ldm}));
+    EGR_TRY(egr_stft_frames(x, B, L, c.n_fft, c.hop, rpad, c.n_frames, t_valid, f.m.ldm, f.m.window, mag.p, f.st));
+    mag.view({(int64_t)B * c.n_frames, 1, 1, f.m.ldm});
     ConvCall cc;
-    cc.B = B * c.n_frames; cc.Cin = m->ldm; cc.Cout = c.n_mels; cc.act = ACT_LOGCLAMP; cc.act_param = c.log_floor;
-    OKR(conv(m, mel, mag, "mel_fb", cc, NO_RA, m->get("mel_fb")));
+    cc.B = B * c.n_frames; cc.Cin = f.m.ldm; cc.Cout = c.n_mels; cc.act = ACT_LOGCLAMP; cc.act_param = c.log_floor;
+    EGR_TRY(conv(f, mel, mag, "mel_fb", cc, NO_RA, f.m.get("mel_fb")));
     mel.view({B, c.n_frames, c.n_mels, 1});
     return EGR_OK;
 }
 
 // lowpass_input=True: cutoff from the STFT energy, zero-phase 8th-order Chebyshev-I gain applied on the Fat-Llama transform passes
-int lowpass(M* m, Ten& y, const float* x, int B, int L) {
-    const egr_flashsr_config& c = m->cfg;
+int lowpass(Fwd& f, Ten& y, const float* x, int B, int L) {
+    const egr_flashsr_config& c = f.m.cfg;
     const int rpad = (c.n_fft - c.hop) / 2;
     const int T = (L + 2 * rpad - c.n_fft) / c.hop + 1;
     const int nb = c.n_fft / 2 + 1;
     Ten mag, cut, gain;
-    OKR(new_ten(m, mag, {B, T, m->ldm}));
-    OKR(egr_stft_frames(x, B, L, c.n_fft, c.hop, rpad, T, T, m->ldm, m->window, mag.p, m->st));
-    OKR(new_ten(m, cut, {B}));
+    EGR_TRY(new_ten(f, mag, {B, T, f.m.ldm}));
+    EGR_TRY(egr_stft_frames(x, B, L, c.n_fft, c.hop, rpad, T, T, f.m.ldm, f.m.window, mag.p, f.st));
+    EGR_TRY(new_ten(f, cut, {B}));
     const int64_t nbins = L / 2 + 1;
-    OKR(new_ten(m, gain, {B, nbins}));
-    OKR(egr_lowpass_gain(mag.p, B, T, m->ldm, nb, 0.985f, (float)c.sr, 8, 0.05f, nbins, (int*)cut.p, gain.p, m->st));
-    egr_fatllama_plan*& plan = m->cx->lp_plans[B];
-    if (!plan) OKR(egr_fatllama_plan_create(&plan, L, B, 1, 0, 0));
-    OKR(new_ten(m, y, {B, L}));
-    return egr_spectral_gain(plan, x, gain.p, y.p, m->st);
+    EGR_TRY(new_ten(f, gain, {B, nbins}));
+    EGR_TRY(egr_lowpass_gain(mag.p, B, T, f.m.ldm, nb, 0.985f, (float)c.sr, 8, 0.05f, nbins, (int*)cut.p, gain.p, f.st));
+    egr_fatllama_plan*& plan = f.cx->lp_plans[B];
+    if (!plan) EGR_TRY(egr_fatllama_plan_create(&plan, L, B, 1, 0, 0));
+    EGR_TRY(new_ten(f, y, {B, L}));
+    return egr_spectral_gain(plan, x, gain.p, y.p, f.st);
 }
 
-int vae_res(M* m, Ten& y, const Ten& x, const std::string& name) {
+int vae_res(Fwd& f, Ten& y, const Ten& x, const std::string& name) {
     Ten h, sc;
-    OKR(gn_conv3(m, h, x, name + ".norm1", 1e-6f, name + ".conv1"));
+    EGR_TRY(gn_conv3(f, h, x, name + ".norm1", 1e-6f, name + ".conv1"));
     const float* scp = x.p;
-    if (m->has(name + ".nin_shortcut.weight")) { OKR(conv1x1(m, sc, x, name + ".nin_shortcut")); scp = sc.p; }
-    return gn_conv3(m, y, h, name + ".norm2", 1e-6f, name + ".conv2", scp);
+    if (f.m.has(name + ".nin_shortcut.weight")) { EGR_TRY(conv1x1(f, sc, x, name + ".nin_shortcut")); scp = sc.p; }
+    return gn_conv3(f, y, h, name + ".norm2", 1e-6f, name + ".conv2", scp);
 }
 
-int vae_attn(M* m, Ten& y, const Ten& x, const std::string& name) {
+int vae_attn(Fwd& f, Ten& y, const Ten& x, const std::string& name) {
     const int B = (int)x.d[0], H = (int)x.d[1], W = (int)x.d[2], Cc = (int)x.d[3];
     Ten h, q, k, v, o;
-    OKR(groupnorm(m, h, x, name + ".norm", 1e-6f, false));
-    OKR(conv1x1(m, q, h, name + ".q", nullptr, ACT_NONE, WANT_RA));
-    OKR(conv1x1(m, k, h, name + ".k", nullptr, ACT_NONE, WANT_RA));
-    OKR(conv1x1(m, v, h, name + ".v", nullptr, ACT_NONE, WANT_RA));
-    OKR(attention(m, o, q, k, v, B, H * W, Cc, 1));
+    EGR_TRY(groupnorm(f, h, x, name + ".norm", 1e-6f, false));
+    EGR_TRY(conv1x1(f, q, h, name + ".q", nullptr, ACT_NONE, WANT_RA));
+    EGR_TRY(conv1x1(f, k, h, name + ".k", nullptr, ACT_NONE, WANT_RA));
+    EGR_TRY(conv1x1(f, v, h, name + ".v", nullptr, ACT_NONE, WANT_RA));
+    EGR_TRY(attention(f, o, q, k, v, B, H * W, Cc, 1));
     o.view({B, H, W, Cc});
-    return conv1x1(m, y, o, name + ".proj_out", x.p, ACT_NONE, WANT_RA);
+    return conv1x1(f, y, o, name + ".proj_out", x.p, ACT_NONE, WANT_RA);
 }
 
-int vae_encode(M* m, Ten& z, const Ten& mel) {
-    const egr_flashsr_config& c = m->cfg;
+int vae_encode(Fwd& f, Ten& z, const Ten& mel) {
+    const egr_flashsr_config& c = f.m.cfg;
     Ten h, t;
-    OKR(conv3(m, h, mel, "vae.encoder.conv_in"));
+    EGR_TRY(conv3(f, h, mel, "vae.encoder.conv_in"));
     for (int lv = 0; lv < c.vae_levels; ++lv) {
         for (int b = 0; b < c.vae_res; ++b) {
-            OKR(vae_res(m, t, h, "vae.encoder.down." + std::to_string(lv) + ".block." + std::to_string(b)));
+            EGR_TRY(vae_res(f, t, h, "vae.encoder.down." + std::to_string(lv) + ".block." + std::to_string(b)));
             h = std::move(t);
         }
         if (lv != c.vae_levels - 1) {
-            OKR(conv3(m, t, h, "vae.encoder.down." + std::to_string(lv) + ".downsample.conv", 2, 0, ACT_NONE, nullptr, 0, nullptr, WANT_RA));
+            EGR_TRY(conv3(f, t, h, "vae.encoder.down." + std::to_string(lv) + ".downsample.conv", 2, 0, ACT_NONE, nullptr, 0, nullptr, WANT_RA));
             h = std::move(t);
         }
     }
-    OKR(vae_res(m, t, h, "vae.encoder.mid.block_1")); h = std::move(t);
-    OKR(vae_attn(m, t, h, "vae.encoder.mid.attn_1")); h = std::move(t);
-    OKR(vae_res(m, t, h, "vae.encoder.mid.block_2")); h = std::move(t);
-    OKR(groupnorm(m, t, h, "vae.encoder.norm_out", 1e-6f, true));
-    OKR(conv3(m, h, t, "vae.encoder.conv_out"));
+    EGR_TRY(vae_res(f, t, h, "vae.encoder.mid.block_1")); h = std::move(t);
+    EGR_TRY(vae_attn(f, t, h, "vae.encoder.mid.attn_1")); h = std::move(t);
+    EGR_TRY(vae_res(f, t, h, "vae.encoder.mid.block_2")); h = std::move(t);
+    EGR_TRY(groupnorm(f, t, h, "vae.encoder.norm_out", 1e-6f, true));
+    EGR_TRY(conv3(f, h, t, "vae.encoder.conv_out"));
     Ten mom;
-    OKR(conv1x1(m, mom, h, "vae.quant_conv"));
+    EGR_TRY(conv1x1(f, mom, h, "vae.quant_conv"));
     // the mean half of the moments: channels [0, z_ch) of 2 z_ch
     const int64_t rows = mom.d[0] * mom.d[1] * mom.d[2];
-    OKR(new_ten(m, z, {mom.d[0], mom.d[1], mom.d[2], c.z_ch}));
-    EGR_HIP(hipMemcpy2DAsync(z.p, (size_t)c.z_ch * 4, mom.p, (size_t)2 * c.z_ch * 4, (size_t)c.z_ch * 4, (size_t)rows, hipMemcpyDeviceToDevice, m->st));
+    EGR_TRY(new_ten(f, z, {mom.d[0], mom.d[1], mom.d[2], c.z_ch}));
+    EGR_HIP(hipMemcpy2DAsync(z.p, (size_t)c.z_ch * 4, mom.p, (size_t)2 * c.z_ch * 4, (size_t)c.z_ch * 4, (size_t)rows, hipMemcpyDeviceToDevice, f.st));
     return EGR_OK;
 }
 
-int vae_decode(M* m, Ten& y, const Ten& z) {
-    const egr_flashsr_config& c = m->cfg;
+int vae_decode(Fwd& f, Ten& y, const Ten& z) {
+    const egr_flashsr_config& c = f.m.cfg;
     Ten h, t;
-    OKR(conv1x1(m, t, z, "vae.post_quant_conv", nullptr, ACT_NONE, WANT_RA));
-    OKR(conv3(m, h, t, "vae.decoder.conv_in"));
-    OKR(vae_res(m, t, h, "vae.decoder.mid.block_1")); h = std::move(t);
-    OKR(vae_attn(m, t, h, "vae.decoder.mid.attn_1")); h = std::move(t);
-    OKR(vae_res(m, t, h, "vae.decoder.mid.block_2")); h = std::move(t);
+    EGR_TRY(conv1x1(f, t, z, "vae.post_quant_conv", nullptr, ACT_NONE, WANT_RA));
+    EGR_TRY(conv3(f, h, t, "vae.decoder.conv_in"));
+    EGR_TRY(vae_res(f, t, h, "vae.decoder.mid.block_1")); h = std::move(t);
+    EGR_TRY(vae_attn(f, t, h, "vae.decoder.mid.attn_1")); h = std::move(t);
+    EGR_TRY(vae_res(f, t, h, "vae.decoder.mid.block_2")); h = std::move(t);
     for (int lv = c.vae_levels - 1; lv >= 0; --lv) {
         for (int b = 0; b <= c.vae_res; ++b) {
-            OKR(vae_res(m, t, h, "vae.decoder.up." + std::to_string(lv) + ".block." + std::to_string(b)));
+            EGR_TRY(vae_res(f, t, h, "vae.decoder.up." + std::to_string(lv) + ".block." + std::to_string(b)));
             h = std::move(t);
         }
         if (lv != 0) {
-            OKR(conv3(m, t, h, "vae.decoder.up." + std::to_string(lv) + ".upsample.conv", 1, 1));
+            EGR_TRY(conv3(f, t, h, "vae.decoder.up." + std::to_string(lv) + ".upsample.conv", 1, 1));
             h = std::move(t);
         }
     }
-    OKR(groupnorm(m, t, h, "vae.decoder.norm_out", 1e-6f, true));
-    return conv3(m, y, t, "vae.decoder.conv_out");
+    EGR_TRY(groupnorm(f, t, h, "vae.decoder.norm_out", 1e-6f, true));
+    return conv3(f, y, t, "vae.decoder.conv_out");
 }
 
-int unet_block(M* m, Ten& y, const Ten& x, const std::string& base, bool has_attn) {
-    const egr_flashsr_config& c = m->cfg;
+int unet_block(Fwd& f, Ten& y, const Ten& x, const std::string& base, bool has_attn) {
+    const egr_flashsr_config& c = f.m.cfg;
     Ten h, sc, r;
-    OKR(gn_conv3(m, h, x, base + ".res.in_norm", 1e-5f, base + ".res.in_conv", nullptr, m->ptr(base + ".res.in_conv.bias_t")));
+    EGR_TRY(gn_conv3(f, h, x, base + ".res.in_norm", 1e-5f, base + ".res.in_conv", nullptr, f.m.ptr(base + ".res.in_conv.bias_t")));
     const float* scp = x.p;
-    if (m->has(base + ".res.skip.weight")) { OKR(conv1x1(m, sc, x, base + ".res.skip")); scp = sc.p; }
-    OKR(gn_conv3(m, r, h, base + ".res.out_norm", 1e-5f, base + ".res.out_conv", scp));
+    if (f.m.has(base + ".res.skip.weight")) { EGR_TRY(conv1x1(f, sc, x, base + ".res.skip")); scp = sc.p; }
+    EGR_TRY(gn_conv3(f, r, h, base + ".res.out_norm", 1e-5f, base + ".res.out_conv", scp));
     h.release(); sc.release();
     if (!has_attn) { y = std::move(r); return EGR_OK; }
     const int B = (int)r.d[0], H = (int)r.d[1], W = (int)r.d[2], Cc = (int)r.d[3];
     const int T = H * W, heads = Cc / c.head_dim;
     Ten g0, t;
-    OKR(groupnorm(m, g0, r, base + ".st.norm", 1e-6f, false));
-    OKR(conv1x1(m, t, g0, base + ".st.proj_in"));
+    EGR_TRY(groupnorm(f, g0, r, base + ".st.norm", 1e-6f, false));
+    EGR_TRY(conv1x1(f, t, g0, base + ".st.proj_in"));
     g0.release();
     t.view({(int64_t)B * T, Cc});
     for (int a = 1; a <= 2; ++a) {
         const std::string an = base + ".st.attn" + std::to_string(a);
         Ten n_, q, k, v, o, t2;
-        OKR(layernorm(m, n_, t, an + "_ln"));
+        EGR_TRY(layernorm(f, n_, t, an + "_ln"));
         // q, k, v feed the attention products: their row maxima ride along
-        OKR(linear(m, q, n_, an + ".to_q", nullptr, ACT_NONE, /*bias*/ false, WANT_RA));
-        OKR(linear(m, k, n_, an + ".to_k", nullptr, ACT_NONE, /*bias*/ false, WANT_RA));
-        OKR(linear(m, v, n_, an + ".to_v", nullptr, ACT_NONE, /*bias*/ false, WANT_RA));
-        OKR(attention(m, o, q, k, v, B, T, Cc, heads));
-        OKR(linear(m, t2, o, an + ".to_out", t.p));
+        EGR_TRY(linear(f, q, n_, an + ".to_q", nullptr, ACT_NONE, /*bias*/ false, WANT_RA));
+        EGR_TRY(linear(f, k, n_, an + ".to_k", nullptr, ACT_NONE, /*bias*/ false, WANT_RA));
+        EGR_TRY(linear(f, v, n_, an + ".to_v", nullptr, ACT_NONE, /*bias*/ false, WANT_RA));
+        EGR_TRY(attention(f, o, q, k, v, B, T, Cc, heads));
+        EGR_TRY(linear(f, t2, o, an + ".to_out", t.p));
         t = std::move(t2);
     }
     Ten ln, u, g, t3;
-    OKR(layernorm(m, ln, t, base + ".st.ff_ln"));
-    OKR(linear(m, u, ln, base + ".st.ff.geglu"));
-    OKR(new_ten(m, g, {(int64_t)B * T, 4 * Cc}));
-    OKR(rs_for_output(m, g, RS_SWITCHED, ROWS_EQUAL, B));
-    if (g.rs) OP(egr_geglu_ra, u.p, g.p, (int64_t)B * T, 4 * Cc, m->R, (float*)g.rs, m->st);
-    else OP(egr_geglu, u.p, g.p, (int64_t)B * T, 4 * Cc, m->st);
-    OKR(linear(m, t3, g, base + ".st.ff.out", t.p, ACT_NONE, /*bias*/ true, WANT_RA));
+    EGR_TRY(layernorm(f, ln, t, base + ".st.ff_ln"));
+    EGR_TRY(linear(f, u, ln, base + ".st.ff.geglu"));
+    EGR_TRY(new_ten(f, g, {(int64_t)B * T, 4 * Cc}));
+    EGR_TRY(rs_for_output(f, g, RS_SWITCHED, ROWS_EQUAL, B));
+    if (g.rs) OP(egr_geglu_ra, u.p, g.p, (int64_t)B * T, 4 * Cc, f.R, (float*)g.rs, f.st);
+    else OP(egr_geglu, u.p, g.p, (int64_t)B * T, 4 * Cc, f.st);
+    EGR_TRY(linear(f, t3, g, base + ".st.ff.out", t.p, ACT_NONE, /*bias*/ true, WANT_RA));
     t3.view({B, H, W, Cc});
-    return conv1x1(m, y, t3, base + ".st.proj_out", r.p, ACT_NONE, WANT_RA);
+    return conv1x1(f, y, t3, base + ".st.proj_out", r.p, ACT_NONE, WANT_RA);
 }
 
-int unet(M* m, Ten& out, Ten&& x0) {
+int unet(Fwd& f, Ten& out, Ten&& x0) {
     std::vector<Ten> skips;
     Ten h = std::move(x0), t;
-    for (size_t i = 0; i < m->blk_name.size(); ++i) {
-        const std::string& name = m->blk_name[i];
+    for (size_t i = 0; i < f.m.blk_name.size(); ++i) {
+        const std::string& name = f.m.blk_name[i];
         const std::string base = "unet." + name;
         const std::string part = name.substr(0, name.find('.'));
         const std::string kind = name.substr(name.rfind('.') + 1);
         if (kind == "conv_in") {
-            OKR(conv3(m, t, h, base));
+            EGR_TRY(conv3(f, t, h, base));
             Ten cp = t.alias();                        // the skip stack owns the tensor, h views it
             skips.push_back(std::move(t));
             h = std::move(cp);
         } else if (kind == "down") {
-            OKR(conv3(m, t, h, base + ".conv", 2, 0, ACT_NONE, nullptr, 1, nullptr, WANT_RA));
+            EGR_TRY(conv3(f, t, h, base + ".conv", 2, 0, ACT_NONE, nullptr, 1, nullptr, WANT_RA));
             Ten cp = t.alias();
             skips.push_back(std::move(t));
             h = std::move(cp);
         } else if (kind == "up") {
-            OKR(conv3(m, t, h, base + ".conv", 1, 1));
+            EGR_TRY(conv3(f, t, h, base + ".conv", 1, 1));
             h = std::move(t);
         } else {
             if (part == "out") {
                 Ten cat;
-                OKR(concat(m, cat, h, skips.back()));
+                EGR_TRY(concat(f, cat, h, skips.back()));
                 skips.pop_back();
                 h = std::move(cat);
             }
-            OKR(unet_block(m, t, h, base, m->blk_attn[i] != 0));
+            EGR_TRY(unet_block(f, t, h, base, f.m.blk_attn[i] != 0));
             if (part == "in") {
                 Ten cp = t.alias();
                 skips.push_back(std::move(t));
@@ -1079,12 +1064,12 @@ int unet(M* m, Ten& out, Ten&& x0) {
             }
         }
     }
-    OKR(groupnorm(m, t, h, "unet.out_norm", 1e-5f, true));
-    return conv3(m, out, t, "unet.out_conv");
+    EGR_TRY(groupnorm(f, t, h, "unet.out_norm", 1e-5f, true));
+    return conv3(f, out, t, "unet.out_conv");
 }
 
-int amp(M* m, Ten& y, Ten&& h, int j) {
-    const egr_flashsr_config& c = m->cfg;
+int amp(Fwd& f, Ten& y, Ten&& h, int j) {
+    const egr_flashsr_config& c = f.m.cfg;
     Ten acc;
     for (int ki = 0; ki < c.voc_n_kernels; ++ki) {
         const int k = c.voc_kernels[ki];
@@ -1097,30 +1082,28 @@ int amp(M* m, Ten& y, Ten&& h, int j) {
             // the 16- and 32-channel stages (245 760 / 122 880 samples per row): the unit's four launches are pure streaming there -- one fused kernel
             // keeps the L-tile on the CU (csrc/egr_nn_amp.hip); fp16 operand scheme only
             {
-                const Wt* w1 = m->get(b + ".conv1.weight");
-                const Wt* w2 = m->get(b + ".conv2.weight");
+                const Wt* w1 = f.m.get(b + ".conv1.weight");
+                const Wt* w2 = f.m.get(b + ".conv2.weight");
                 const int Cc = (int)cur->d[2];
-                if (m->fused_amp && m->h2_on() && w1 && w2 && w1->w2 && w2->w2 && Cc == 16 && w1->Cout == Cc && w2->Cout == Cc && (k & 1) &&
+                if (f.m.fused_amp && f.h2 && w1 && w2 && w1->w2 && w2->w2 && Cc == 16 && w1->Cout == Cc && w2->Cout == Cc && (k & 1) &&
                     k <= 11 && d * (k - 1) / 2 <= 25 && c.aa_taps == 12 && cur->d[1] >= 16) {
-                    OKR(new_ten(m, xn, {cur->d[0], cur->d[1], cur->d[2]}));
-                    ProfScope ps(m);
-                    OKR(egr_amp_unit_h2(cur->p, xn.p, (int)cur->d[0], (int)cur->d[1], Cc, k, d, m->ptr(b + ".alpha1"), m->ptr(b + ".beta1"), w1->w2, w1->w_scale,
-                                        m->ptr(b + ".conv1.bias"), m->ptr(b + ".alpha2"), m->ptr(b + ".beta2"), w2->w2, w2->w_scale, m->ptr(b + ".conv2.bias"),
-                                        m->filt, c.aa_taps, m->st));
-                    const double fl = 2.0 * 2.0 * (double)cur->d[0] * cur->d[1] * Cc * Cc * k;
-                    if (ps.on) ps.end(egr::amp_unit_name(), fl, b);
-                    if (m->count_flops) m->flops += fl;
+                    EGR_TRY(new_ten(f, xn, {cur->d[0], cur->d[1], cur->d[2]}));
+                    EGR_TRY(timed(f, 2.0 * 2.0 * (double)cur->d[0] * cur->d[1] * Cc * Cc * k, b.c_str(), [&](ConvChoice*) {
+                        return egr_amp_unit_h2(cur->p, xn.p, (int)cur->d[0], (int)cur->d[1], Cc, k, d, f.m.ptr(b + ".alpha1"), f.m.ptr(b + ".beta1"), w1->w2, w1->w_scale,
+                                               f.m.ptr(b + ".conv1.bias"), f.m.ptr(b + ".alpha2"), f.m.ptr(b + ".beta2"), w2->w2, w2->w_scale, f.m.ptr(b + ".conv2.bias"),
+                                               f.m.filt, c.aa_taps, f.st);
+                    }, egr::amp_unit_name()));
                     x = std::move(xn);
                     cur = &x;
                     continue;
                 }
             }
-            OKR(snake(m, xt, *cur, b + ".alpha1", b + ".beta1"));
-            OKR(conv1d(m, xc, xt, b + ".conv1", k, 1, d, d * (k - 1) / 2));
+            EGR_TRY(snake(f, xt, *cur, b + ".alpha1", b + ".beta1"));
+            EGR_TRY(conv1d(f, xc, xt, b + ".conv1", k, 1, d, d * (k - 1) / 2));
             xt.release();
-            OKR(snake(m, xs, xc, b + ".alpha2", b + ".beta2"));
+            EGR_TRY(snake(f, xs, xc, b + ".alpha2", b + ".beta2"));
             xc.release();
-            OKR(conv1d(m, xn, xs, b + ".conv2", k, 1, 1, (k - 1) / 2, ACT_NONE, cur->p));
+            EGR_TRY(conv1d(f, xn, xs, b + ".conv2", k, 1, 1, (k - 1) / 2, ACT_NONE, cur->p));
             x = std::move(xn);
             cur = &x;
         }
@@ -1128,17 +1111,17 @@ int amp(M* m, Ten& y, Ten&& h, int j) {
             acc = std::move(x);
         } else if (ki + 1 < c.voc_n_kernels) {
             Ten s;
-            OKR(eltwise(m, s, acc, x.p, EW_ADD));
+            EGR_TRY(eltwise(f, s, acc, x.p, EW_ADD));
             acc = std::move(s);
         } else {                                   // last branch: the mean's scale rides on the last add
-            return eltwise(m, y, acc, x.p, EW_ADD_SCALE, 1.0f / c.voc_n_kernels, 0.f, WANT_RA);   // feeds the next stage's up-sampling GEMM
+            return eltwise(f, y, acc, x.p, EW_ADD_SCALE, 1.0f / c.voc_n_kernels, 0.f, WANT_RA);   // feeds the next stage's up-sampling GEMM
         }
     }
-    return eltwise(m, y, acc, nullptr, EW_SCALE, 1.0f / c.voc_n_kernels, 0.f, WANT_RA);
+    return eltwise(f, y, acc, nullptr, EW_SCALE, 1.0f / c.voc_n_kernels, 0.f, WANT_RA);
 }
 
-int vocoder(M* m, Ten& y, const Ten& mel_hat, const float* wave, int B) {
-    const egr_flashsr_config& c = m->cfg;
+int vocoder(Fwd& f, Ten& y, const Ten& mel_hat, const float* wave, int B) {
+    const egr_flashsr_config& c = f.m.cfg;
     const int T = (int)mel_hat.d[1], Fm = (int)mel_hat.d[2];
     const int n = c.voc_n_rates;
     std::vector<Ten> feats(n);
@@ -1150,7 +1133,7 @@ int vocoder(M* m, Ten& y, const Ten& mel_hat, const float* wave, int B) {
         for (int i = 0; i < n; ++i) {
             const int r = c.voc_rates[n - 1 - i];
             const bool feeds_next = i + 1 < n;          // the next strided convolution of the encoder reads it
-            OKR(conv1d(m, feats[i], *e, "voc.wave_enc." + std::to_string(i), 2 * r + 1, r, 1, r, ACT_LEAKY, nullptr, feeds_next));
+            EGR_TRY(conv1d(f, feats[i], *e, "voc.wave_enc." + std::to_string(i), 2 * r + 1, r, 1, r, ACT_LEAKY, nullptr, feeds_next));
             e = &feats[i];
         }
     }
@@ -1158,13 +1141,13 @@ int vocoder(M* m, Ten& y, const Ten& mel_hat, const float* wave, int B) {
     mh.view({B, T, Fm});
     mh.p = mel_hat.p;
     Ten h;
-    OKR(conv1d(m, h, mh, "voc.conv_pre", 7, 1, 1, 3, ACT_NONE, feats[n - 1].p, WANT_RA));
+    EGR_TRY(conv1d(f, h, mh, "voc.conv_pre", 7, 1, 1, 3, ACT_NONE, feats[n - 1].p, WANT_RA));
     feats[n - 1].release();
     for (int j = 0; j < n; ++j) {
         const int r = c.voc_rates[j];
         const int kt = up_kernel(r);
         const int Bc = (int)h.d[0], Lin = (int)h.d[1], Ci = (int)h.d[2];
-        const Wt* wt = m->get("voc.ups." + std::to_string(j) + ".weight");
+        const Wt* wt = f.m.get("voc.ups." + std::to_string(j) + ".weight");
         const int Co = wt->Cout / kt;
         Ten Y, out, hx;
         hx.view({(int64_t)Bc * Lin, 1, 1, Ci});
@@ -1172,60 +1155,35 @@ int vocoder(M* m, Ten& y, const Ten& mel_hat, const float* wave, int B) {
         hx.rs = h.rs;                                  // (a view: the row maxima of h are its own)
         ConvCall cu;                                   // ConvTranspose1d as a GEMM onto [kt][Co] columns, gathered by col2im below
         cu.B = Bc * Lin; cu.Cin = Ci; cu.Cout = kt * Co;
-        OKR(conv(m, Y, hx, "voc.ups." + std::to_string(j), cu, NO_RA, wt));
-        OKR(new_ten(m, out, {Bc, (int64_t)Lin * r, Co}));
+        EGR_TRY(conv(f, Y, hx, "voc.ups." + std::to_string(j), cu, NO_RA, wt));
+        EGR_TRY(new_ten(f, out, {Bc, (int64_t)Lin * r, Co}));
         const float* add = (j <= n - 2) ? feats[n - 2 - j].p : nullptr;
-        OKR(egr_col2im_convtr1d(Y.p, m->ptr("voc.ups." + std::to_string(j) + ".bias"), add, out.p, Bc, Lin, Lin * r, Co, kt, r, (kt - r) / 2, m->st));
+        EGR_TRY(egr_col2im_convtr1d(Y.p, f.m.ptr("voc.ups." + std::to_string(j) + ".bias"), add, out.p, Bc, Lin, Lin * r, Co, kt, r, (kt - r) / 2, f.st));
         Y.release();
         if (j <= n - 2) feats[n - 2 - j].release();
         Ten nx;
-        OKR(amp(m, nx, std::move(out), j));
+        EGR_TRY(amp(f, nx, std::move(out), j));
         h = std::move(nx);
     }
     Ten s;
-    OKR(snake(m, s, h, "voc.post.alpha", "voc.post.beta"));
-    OKR(conv1d(m, y, s, "voc.conv_post", 7, 1, 1, 3, ACT_TANH));
+    EGR_TRY(snake(f, s, h, "voc.post.alpha", "voc.post.beta"));
+    EGR_TRY(conv1d(f, y, s, "voc.conv_post", 7, 1, 1, 3, ACT_TANH));
     y.view({B, y.d[1]});
     return EGR_OK;
 }
 
-int copy_out(M* m, float* dst, const Ten& t) {
+int copy_out(Fwd& f, float* dst, const Ten& t) {
     if (!dst) return EGR_OK;
-    EGR_HIP(hipMemcpyAsync(dst, t.p, (size_t)t.numel() * 4, hipMemcpyDeviceToDevice, m->st));
+    EGR_HIP(hipMemcpyAsync(dst, t.p, (size_t)t.numel() * 4, hipMemcpyDeviceToDevice, f.st));
     return EGR_OK;
 }
 
 // x [R][chunk], noise [R][h][w][z] (channels-last) -> y [R][chunk]; stages (optional): mel, z_cond, v, z0, mel_hat, y_full
-int forward(M* m, const float* x_in, const float* noise, int R, int lowpass_on, float* y_out, float* const* stages) {
-    const egr_flashsr_config& c = m->cfg;
+int forward(Fwd& f, const float* x_in, const float* noise, int lowpass_on, float* y_out, float* const* stages) {
+    const egr_flashsr_config& c = f.m.cfg;
     const float* x = x_in;
-    m->R = R;
-    if (m->h2_mode == 1) {                         // per-row operand maxima of this forward: one zeroed pool per context
-        FsrCtx* cx = m->cx;
-        size_t slices = (size_t)(2 * m->h2_nweights + 64);
-        if (const char* e = getenv("EGR_FSR_RS_POOL_SLICES")) { const int v = atoi(e); if (v >= 1) slices = (size_t)v; }   // test knob: start small, exercise the growth in rs_take
-        const size_t need = slices * (size_t)R * EGR_ROW_AMAX_STRIDE;
-        if (!cx->rs_retired.empty()) {                 // pools a previous forward outgrew (rs_take): its kernels are done once the stream is
-            hipStreamSynchronize(m->st);
-            for (unsigned* q : cx->rs_retired) hipFree(q);
-            cx->rs_retired.clear();
-        }
-        if (cx->rs_cap < need) {
-            if (cx->rs_pool) { hipStreamSynchronize(m->st); hipFree(cx->rs_pool); cx->rs_pool = nullptr; cx->rs_cap = 0; }
-            if (hipMalloc((void**)&cx->rs_pool, need * sizeof(unsigned)) != hipSuccess) { set_error("hipMalloc(row maxima pool) failed"); return EGR_ERR_ALLOC; }
-            cx->rs_cap = need;
-        }
-        EGR_HIP(hipMemsetAsync(cx->rs_pool, 0, cx->rs_cap * sizeof(unsigned), m->st));
-        cx->rs_used = 0;
-        if (cx->rs_ones_rows < R) {
-            if (cx->rs_ones) { hipStreamSynchronize(m->st); hipFree(cx->rs_ones); cx->rs_ones = nullptr; }
-            const size_t n = (size_t)R * EGR_ROW_AMAX_STRIDE;
-            if (hipMalloc((void**)&cx->rs_ones, n * sizeof(unsigned)) != hipSuccess) { set_error("hipMalloc(row maxima constants) failed"); return EGR_ERR_ALLOC; }
-            std::vector<unsigned> ones(n, 0x3f800000u);
-            EGR_HIP(hipMemcpy(cx->rs_ones, ones.data(), n * sizeof(unsigned), hipMemcpyHostToDevice));
-            cx->rs_ones_rows = R;
-        }
-    }
+    const int R = f.R;
+    if (f.h2) EGR_TRY(f.cx->begin_rows(R, f.m.h2_nweights));   // per-row operand maxima of this forward: one zeroed pool per context
     // EGR_FSR_TRACE=2 (diagnosis of first-call costs): synchronise after every stage and print host / device-complete times
     static const int trace_lv = getenv("EGR_FSR_TRACE") ? atoi(getenv("EGR_FSR_TRACE")) : 0;
     const bool trace2 = trace_lv >= 2;
@@ -1234,37 +1192,37 @@ int forward(M* m, const float* x_in, const float* noise, int R, int lowpass_on, 
         if (trace_lv == 1) fprintf(stderr, "[egr_flashsr forward R=%d] %-10s enqueued at %8.1f ms\n", R, what, now_ms() - t_fwd);
         if (!trace2) return;
         const double t_host = now_ms() - t_fwd;
-        hipStreamSynchronize(m->st);
+        hipStreamSynchronize(f.st);
         fprintf(stderr, "[egr_flashsr forward R=%d] %-10s enqueued at %8.1f ms, complete at %8.1f ms (arena hipMalloc so far %.1f ms)\n", R, what, t_host,
                 now_ms() - t_fwd, 1e-3 * (double)g_arena_malloc_us.load());
     };
     Ten xl;
-    if (lowpass_on) { OKR(lowpass(m, xl, x_in, R, c.chunk)); x = xl.p; }
+    if (lowpass_on) { EGR_TRY(lowpass(f, xl, x_in, R, c.chunk)); x = xl.p; }
     Ten mel, z_c, v, z0, mel_hat, y;
-    OKR(log_mel(m, mel, x, R, c.chunk));
+    EGR_TRY(log_mel(f, mel, x, R, c.chunk));
     stage_mark("log_mel");
-    OKR(vae_encode(m, z_c, mel));
+    EGR_TRY(vae_encode(f, z_c, mel));
     stage_mark("vae_encode");
     {
         Ten nz, cat;                               // non-owning view of the caller's noise
-        nz.view({R, m->lat_h, m->lat_w, c.z_ch});
+        nz.view({R, f.m.lat_h, f.m.lat_w, c.z_ch});
         nz.p = const_cast<float*>(noise);
-        OKR(concat(m, cat, nz, z_c));
-        OKR(unet(m, v, std::move(cat)));
-        OKR(eltwise(m, z0, nz, v.p, EW_AXPBY, m->alpha, -m->sigma));
+        EGR_TRY(concat(f, cat, nz, z_c));
+        EGR_TRY(unet(f, v, std::move(cat)));
+        EGR_TRY(eltwise(f, z0, nz, v.p, EW_AXPBY, f.m.alpha, -f.m.sigma));
     }
     stage_mark("unet");
-    OKR(vae_decode(m, mel_hat, z0));
+    EGR_TRY(vae_decode(f, mel_hat, z0));
     stage_mark("vae_decode");
-    OKR(vocoder(m, y, mel_hat, x, R));
+    EGR_TRY(vocoder(f, y, mel_hat, x, R));
     stage_mark("vocoder");
     if (stages) {
-        OKR(copy_out(m, stages[0], mel)); OKR(copy_out(m, stages[1], z_c)); OKR(copy_out(m, stages[2], v));
-        OKR(copy_out(m, stages[3], z0)); OKR(copy_out(m, stages[4], mel_hat)); OKR(copy_out(m, stages[5], y));
+        EGR_TRY(copy_out(f, stages[0], mel)); EGR_TRY(copy_out(f, stages[1], z_c)); EGR_TRY(copy_out(f, stages[2], v));
+        EGR_TRY(copy_out(f, stages[3], z0)); EGR_TRY(copy_out(f, stages[4], mel_hat)); EGR_TRY(copy_out(f, stages[5], y));
     }
     const int64_t Ly = y.d[1];
     EGR_CHECK(Ly >= c.chunk, EGR_ERR_UNSUPPORTED, "FlashSR: vocoder output %lld shorter than the chunk %d", (long long)Ly, c.chunk);
-    EGR_HIP(hipMemcpy2DAsync(y_out, (size_t)c.chunk * 4, y.p, (size_t)Ly * 4, (size_t)c.chunk * 4, (size_t)R, hipMemcpyDeviceToDevice, m->st));
+    EGR_HIP(hipMemcpy2DAsync(y_out, (size_t)c.chunk * 4, y.p, (size_t)Ly * 4, (size_t)c.chunk * 4, (size_t)R, hipMemcpyDeviceToDevice, f.st));
     return EGR_OK;
 }
 
@@ -1332,20 +1290,8 @@ extern "C" int egr_flashsr_destroy(egr_flashsr* m) {
     if (!m) return EGR_OK;
     hipDeviceSynchronize();
     for (void* p : m->owned) hipFree(p);
-    for (size_t i = 0; i < m->ctxs.size(); ++i) {
-        FsrCtx* c = m->ctxs[i].get();
-        for (auto& kv : c->lp_plans) egr_fatllama_plan_destroy(kv.second);
-        if (c->gn_ws) hipFree(c->gn_ws);
-        if (c->rs_pool) hipFree(c->rs_pool);
-        for (unsigned* q : c->rs_retired) hipFree(q);
-        if (c->rs_ones) hipFree(c->rs_ones);
-        if (c->done) hipEventDestroy(c->done);
-        if (i > 0 && c->st) hipStreamDestroy(c->st);
-    }
     if (m->ev_fork) hipEventDestroy(m->ev_fork);
-    for (auto& r : m->prof) { hipEventDestroy(r.a); hipEventDestroy(r.b); }
-    if (m->d_wmax) hipFree(m->d_wmax);
-    delete m;
+    delete m;                                        // contexts, profile records and the weight maximum release themselves
     return EGR_OK;
 }
 
@@ -1364,7 +1310,6 @@ extern "C" int egr_flashsr_create(egr_flashsr** out, const egr_flashsr_config* c
     m->flags = flags;
     m->ctxs.emplace_back(new FsrCtx());
     m->ctxs[0]->st = (hipStream_t)stream;
-    m->use(m->ctxs[0].get());
     hipGetDevice(&m->device);
     if (const char* e = getenv("EGREGORA_FLASHSR_STREAMS")) { const int g = atoi(e); if (g >= 1 && g <= 4) m->max_groups = g; }
     if (const char* e = getenv("EGREGORA_FLASHSR_WINOGRAD_MIN_CH")) m->wino_min_ch = atoi(e);
@@ -1395,10 +1340,10 @@ extern "C" int egr_flashsr_create(egr_flashsr** out, const egr_flashsr_config* c
     void* p = nullptr;
     if ((rc = dev_alloc(m, (size_t)cfg->n_fft * 4, &p))) return fail(rc);
     m->window = (float*)p;
-    hipMemcpyAsync(m->window, tw->data, (size_t)cfg->n_fft * 4, hipMemcpyDeviceToDevice, m->st);
+    hipMemcpyAsync(m->window, tw->data, (size_t)cfg->n_fft * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream);
     if ((rc = dev_alloc(m, (size_t)cfg->aa_taps * 4, &p))) return fail(rc);
     m->filt = (float*)p;
-    hipMemcpyAsync(m->filt, tf->data, (size_t)cfg->aa_taps * 4, hipMemcpyDeviceToDevice, m->st);
+    hipMemcpyAsync(m->filt, tf->data, (size_t)cfg->aa_taps * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream);
     // mel filterbank [n_mels][nb] as a contraction weight: K = nb (padded to ldm), N = n_mels
     if ((rc = add_packed(m, "mel_fb", tm->data, 0, nb, cfg->n_mels, nb, cfg->n_mels, 1, 1, 1, 1, m->ldm))) return fail(rc);
     {   // cosine schedule at t = T-1 (Nichol & Dhariwal), alpha^2 + sigma^2 = 1
@@ -1409,7 +1354,7 @@ extern "C" int egr_flashsr_create(egr_flashsr** out, const egr_flashsr_config* c
         m->alpha = (float)sqrt(abar); m->sigma = (float)sqrt(1.0 - abar);
     }
     if ((rc = fold_time_embedding(m, te->data))) return fail(rc);
-    if (hipStreamSynchronize(m->st) != hipSuccess || hipGetLastError() != hipSuccess) { set_error("egr_flashsr_create: device work failed"); return fail(EGR_ERR_HIP); }
+    if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess || hipGetLastError() != hipSuccess) { set_error("egr_flashsr_create: device work failed"); return fail(EGR_ERR_HIP); }
     *out = m;
     return EGR_OK;
 }
@@ -1425,13 +1370,10 @@ extern "C" int egr_flashsr_forward(egr_flashsr* m, const float* x, const float* 
     EGR_CHECK(m && x && noise && y && rows >= 1, EGR_ERR_ARG, "egr_flashsr_forward: null / empty argument");
     ForwardGuard guard(m->device, (hipStream_t)stream);
     m->ctxs[0]->st = (hipStream_t)stream;
-    m->use(m->ctxs[0].get());
     // the introspection walk stays on the three-term kernels (bit-equal to the operator API) unless egr_flashsr_set_split(h, 2) asked
     // for the fp16 operand terms here too (stage taps for the tests)
-    m->h2_mode = (m->h2 && m->h2_fwd && m->h2_nweights > 0) ? 1 : -1;
-    const int rc = forward(m, x, noise, rows, lowpass, y, stages);
-    m->h2_mode = -1;
-    return rc;
+    Fwd f(*m, m->ctxs[0].get(), rows, m->h2_ready() && m->h2_fwd, &m->prof, m->profiling);
+    return forward(f, x, noise, lowpass, y, stages);
 }
 
 // x [rows][chunk] -> y [rows][chunk]; rows = chunks x channels ride the batch dimension (reference :366-368) and are processed
@@ -1454,13 +1396,6 @@ static int ensure_side_streams(egr_flashsr* m, hipStream_t caller, int want) {
         for (size_t i = 1; i < m->ctxs.size();) {
             if (overlaps(caller, m->ctxs[i]->st)) { ++i; continue; }
             hipStreamSynchronize(m->ctxs[i]->st);
-            for (auto& kv : m->ctxs[i]->lp_plans) egr_fatllama_plan_destroy(kv.second);
-            if (m->ctxs[i]->gn_ws) hipFree(m->ctxs[i]->gn_ws);
-            if (m->ctxs[i]->rs_pool) hipFree(m->ctxs[i]->rs_pool);
-            for (unsigned* q : m->ctxs[i]->rs_retired) hipFree(q);
-            if (m->ctxs[i]->rs_ones) hipFree(m->ctxs[i]->rs_ones);
-            if (m->ctxs[i]->done) hipEventDestroy(m->ctxs[i]->done);
-            hipStreamDestroy(m->ctxs[i]->st);
             m->ctxs.erase(m->ctxs.begin() + i);
         }
         m->verified_for.assign(1, caller);
@@ -1471,9 +1406,7 @@ static int ensure_side_streams(egr_flashsr* m, hipStream_t caller, int want) {
         bool ok = overlaps(caller, s);
         for (size_t i = 1; ok && i < m->ctxs.size(); ++i) ok = overlaps(m->ctxs[i]->st, s);
         if (!ok) { hipStreamDestroy(s); continue; }
-        m->ctxs.emplace_back(new FsrCtx());
-        m->ctxs.back()->st = s;
-        hipEventCreateWithFlags(&m->ctxs.back()->done, hipEventDisableTiming);
+        m->ctxs.emplace_back(new FsrCtx(s));
     }
     return (int)m->ctxs.size() - 1;
 }
@@ -1484,58 +1417,18 @@ static int ensure_side_streams(egr_flashsr* m, hipStream_t caller, int want) {
 // A pass of >= 2 * min_group_rows rows is split into up to max_groups contiguous ROW GROUPS that run as concurrent forwards on the
 // handle's verified side streams, each with its own scratch arena (fork / join by events around the pass): one group's
 // matrix-bound kernels overlap another's HBM-bound ones and fill each other's tails (26 rows: 260 ms in one forward).
-// h2_mode 0: the handle's scheme, decided under the device's forward lock; count_call: the call shows in egr_flashsr_split_info and in
-// the profile records (false for the warm-up pass)
+// rows of one call; row_ids NULL: implicit ids id_base .. id_base + rows - 1; count_call: the call shows in egr_flashsr_split_info and
+// in the profile records (false for the warm-up pass)
 static int infer_once(egr_flashsr* m, const float* x, int rows, int lowpass, uint64_t seed, const int64_t* row_ids, int64_t id_base, float* y,
-                      void* stream, int h2_mode, bool count_call);
-
-extern "C" int egr_flashsr_infer(egr_flashsr* m, const float* x, int rows, int lowpass, uint64_t seed, const int64_t* row_ids, float* y,
-                                 void* stream) {
-    EGR_CHECK(m && x && y && rows >= 1, EGR_ERR_ARG, "egr_flashsr_infer: null / empty argument");
-    // operand scheme of this call's forwards: two fp16 terms with per-row device-side scales (see the h2 fields of the handle), or
-    // three bf16 terms.  Either way the call only enqueues work: no read-back, no host synchronisation.
-    // (the scheme is handed to infer_once, which publishes it in the handle only while it holds the device's forward lock)
-    return infer_once(m, x, rows, lowpass, seed, row_ids, 0, y, stream, 0, true);
-}
-
-// enabled: egr_flashsr_infer runs the fp16 operand terms on this handle; weights: contraction weights that hold fp16 terms;
-// calls: egr_flashsr_infer calls made on the scheme.  (ABI 3 reported a calibration state and re-run count here: the scheme has
-// neither any more -- scales are per row and per call, derived on the device.)
-extern "C" int egr_flashsr_split_info(egr_flashsr* m, int* enabled, int* weights, int64_t* calls) {
-    EGR_CHECK(m != nullptr, EGR_ERR_ARG, "handle is null");
-    if (enabled) *enabled = m->h2 && m->h2_nweights > 0;
-    if (weights) *weights = m->h2_nweights;
-    if (calls) *calls = m->h2_calls;
-    return EGR_OK;
-}
-
-// scheme: 0 = three bf16 terms always, 1 = two fp16 terms with per-row device-side scales in egr_flashsr_infer (needs a handle
-// created with the scheme available), 2 = as 1 and egr_flashsr_forward runs the fp16 terms as well (stage taps for tests)
-extern "C" int egr_flashsr_set_split(egr_flashsr* m, int scheme) {
-    EGR_CHECK(m && scheme >= 0 && scheme <= 2, EGR_ERR_ARG, "bad argument");
-    EGR_CHECK(scheme == 0 || m->h2_nweights > 0, EGR_ERR_UNSUPPORTED, "this handle holds no fp16 weight terms");
-    m->h2 = scheme >= 1;
-    m->h2_fwd = scheme == 2;
-    return EGR_OK;
-}
-
-// rows of one call; row_ids NULL: implicit ids id_base .. id_base + rows - 1
-static int infer_once(egr_flashsr* m, const float* x, int rows, int lowpass, uint64_t seed, const int64_t* row_ids, int64_t id_base, float* y,
-                      void* stream, int h2_mode, bool count_call) {
+                      void* stream, bool count_call) {
     hipStream_t st0 = (hipStream_t)stream;
     ForwardGuard guard(m->device, st0);                  // everything below touches per-handle state: inside the device's forward lock
-    if (h2_mode == 0) h2_mode = (m->h2 && m->h2_nweights > 0 && !m->count_flops) ? 1 : -1;
-    struct ModeScope {                                   // the operand scheme of THIS call, visible to the operators while the lock is held
-        egr_flashsr* m; int prof;
-        ModeScope(egr_flashsr* mm, int mode, bool count) : m(mm), prof(mm->profiling) {
-            m->h2_mode = mode;
-            if (mode == 1 && count) ++m->h2_calls;
-            if (!count) m->profiling = 0;                // a warm-up pass leaves no profile records behind
-        }
-        ~ModeScope() { m->h2_mode = -1; m->profiling = prof; }
-    } mode_scope(m, h2_mode, count_call);
+    // operand scheme of THIS call's forwards: two fp16 terms with per-row device-side scales (see the h2 fields of the handle), or
+    // three bf16 terms.  Either way the call only enqueues work: no read-back, no host synchronisation.
+    const bool h2 = m->h2_ready();
+    if (h2 && count_call) ++m->h2_calls;
+    const int prof_level = count_call ? m->profiling : 0;   // a warm-up pass leaves no profile records behind
     m->ctxs[0]->st = st0;
-    m->use(m->ctxs[0].get());
     const egr_flashsr_config& c = m->cfg;
     const int64_t per_row = (int64_t)m->lat_h * m->lat_w * c.z_ch;
     // scratch budget: fewer rows per pass instead of an allocation failure next to the host's other models
@@ -1549,7 +1442,7 @@ static int infer_once(egr_flashsr* m, const float* x, int rows, int lowpass, uin
     static const bool trace = getenv("EGR_FSR_TRACE") && atoi(getenv("EGR_FSR_TRACE")) != 0;
     const double t_enter = now_ms(), malloc0 = 1e-3 * (double)g_arena_malloc_us.load();
     double t_side = 0.0;
-    int groups_max = m->profiling ? 1 : m->max_groups;          // per-kernel timing wants the kernels alone on the chip
+    int groups_max = prof_level ? 1 : m->max_groups;            // per-kernel timing wants the kernels alone on the chip
     if (groups_max > 1 && std::min(rows, rpp) >= 2 * m->min_group_rows) {
         const double t0 = now_ms();
         groups_max = std::min(m->max_groups, 1 + ensure_side_streams(m, st0, groups_max - 1));   // side contexts of an earlier, wider setting stay idle
@@ -1572,18 +1465,17 @@ static int infer_once(egr_flashsr* m, const float* x, int rows, int lowpass, uin
             const int glo = lo + done_rows;
             FsrCtx* cx = m->ctxs[g].get();
             if (g > 0) EGR_HIP(hipStreamWaitEvent(cx->st, m->ev_fork, 0));
-            m->use(cx);
+            Fwd f(*m, cx, ng, h2, &m->prof, prof_level);
             Ten nz;
-            rc = new_ten(m, nz, {ng, per_row});
-            if (rc == EGR_OK) rc = egr_randn_base(nz.p, per_row, ng, seed, row_ids ? row_ids + glo : nullptr, id_base + glo, m->st);
-            if (rc == EGR_OK) rc = forward(m, x + (size_t)glo * c.chunk, nz.p, ng, lowpass, y + (size_t)glo * c.chunk, nullptr);
+            rc = new_ten(f, nz, {ng, per_row});
+            if (rc == EGR_OK) rc = egr_randn_base(nz.p, per_row, ng, seed, row_ids ? row_ids + glo : nullptr, id_base + glo, f.st);
+            if (rc == EGR_OK) rc = forward(f, x + (size_t)glo * c.chunk, nz.p, lowpass, y + (size_t)glo * c.chunk, nullptr);
             if (g > 0) {                                          // join even after an error: nothing may outlive the call unordered
                 hipEventRecord(cx->done, cx->st);
                 hipStreamWaitEvent(st0, cx->done, 0);
             }
             done_rows += ng;
         }
-        m->use(m->ctxs[0].get());
     }
     if (rc == EGR_OK && per > 0) {                       // what a row of a pass of this size costs in scratch (the arenas never shrink)
         double tot = 0.0;
@@ -1593,6 +1485,33 @@ static int infer_once(egr_flashsr* m, const float* x, int rows, int lowpass, uin
     if (trace) fprintf(stderr, "[egr_flashsr_infer] rows %d: host %.1f ms (side-stream check %.1f, arena hipMalloc %.1f), arenas %.2f GB\n", rows,
                        now_ms() - t_enter, t_side, 1e-3 * (double)g_arena_malloc_us.load() - malloc0, (double)egr_flashsr_scratch_bytes(m) / 1e9);
     return rc;
+}
+
+extern "C" int egr_flashsr_infer(egr_flashsr* m, const float* x, int rows, int lowpass, uint64_t seed, const int64_t* row_ids, float* y,
+                                 void* stream) {
+    EGR_CHECK(m && x && y && rows >= 1, EGR_ERR_ARG, "egr_flashsr_infer: null / empty argument");
+    return infer_once(m, x, rows, lowpass, seed, row_ids, 0, y, stream, true);
+}
+
+// enabled: egr_flashsr_infer runs the fp16 operand terms on this handle; weights: contraction weights that hold fp16 terms;
+// calls: egr_flashsr_infer calls made on the scheme.  (ABI 3 reported a calibration state and re-run count here: the scheme has
+// neither any more -- scales are per row and per call, derived on the device.)
+extern "C" int egr_flashsr_split_info(egr_flashsr* m, int* enabled, int* weights, int64_t* calls) {
+    EGR_CHECK(m != nullptr, EGR_ERR_ARG, "handle is null");
+    if (enabled) *enabled = m->h2_ready();
+    if (weights) *weights = m->h2_nweights;
+    if (calls) *calls = m->h2_calls;
+    return EGR_OK;
+}
+
+// scheme: 0 = three bf16 terms always, 1 = two fp16 terms with per-row device-side scales in egr_flashsr_infer (needs a handle
+// created with the scheme available), 2 = as 1 and egr_flashsr_forward runs the fp16 terms as well (stage taps for tests)
+extern "C" int egr_flashsr_set_split(egr_flashsr* m, int scheme) {
+    EGR_CHECK(m && scheme >= 0 && scheme <= 2, EGR_ERR_ARG, "bad argument");
+    EGR_CHECK(scheme == 0 || m->h2_nweights > 0, EGR_ERR_UNSUPPORTED, "this handle holds no fp16 weight terms");
+    m->h2 = scheme >= 1;
+    m->h2_fwd = scheme == 2;
+    return EGR_OK;
 }
 
 // Scratch budget in bytes for the handle's arenas (0 = none; EGREGORA_FLASHSR_ARENA_GB sets it at creation): egr_flashsr_infer
@@ -1607,14 +1526,14 @@ extern "C" int egr_flashsr_set_arena_cap(egr_flashsr* m, double bytes) {
 extern "C" int egr_flashsr_warmup(egr_flashsr* m, int rows, void* stream) {
     EGR_CHECK(m && rows >= 1, EGR_ERR_ARG, "bad argument");
     const size_t n = (size_t)rows * m->cfg.chunk;
-    float* buf = nullptr;
-    if (hipMalloc((void**)&buf, 2 * n * sizeof(float)) != hipSuccess) { set_error("egr_flashsr_warmup: hipMalloc(%zu) failed", 2 * n * sizeof(float)); return EGR_ERR_ALLOC; }
+    DevBuf buf;
+    if (!buf.alloc(2 * n * sizeof(float))) { set_error("egr_flashsr_warmup: hipMalloc(%zu) failed", 2 * n * sizeof(float)); return EGR_ERR_ALLOC; }
+    float* const x = buf.as<float>();
     int rc = EGR_OK;
-    if (hipMemsetAsync(buf, 0, n * sizeof(float), (hipStream_t)stream) != hipSuccess) rc = EGR_ERR_HIP;
-    if (rc == EGR_OK) rc = infer_once(m, buf, rows, 0, 0, nullptr, 0, buf + n, stream, 0, false);      // (split_info counts the host's calls, not this one)
+    if (hipMemsetAsync(x, 0, n * sizeof(float), (hipStream_t)stream) != hipSuccess) rc = EGR_ERR_HIP;
+    if (rc == EGR_OK) rc = infer_once(m, x, rows, 0, 0, nullptr, 0, x + n, stream, false);      // (split_info counts the host's calls, not this one)
     if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess && rc == EGR_OK) { set_error("egr_flashsr_warmup: device work failed"); rc = EGR_ERR_HIP; }
-    hipFree(buf);
-    return rc;
+    return rc;                                           // (the buffer goes after the synchronise)
 }
 
 extern "C" int egr_flashsr_set_streams(egr_flashsr* m, int max_groups, int min_group_rows) {
@@ -1626,7 +1545,6 @@ extern "C" int egr_flashsr_set_streams(egr_flashsr* m, int max_groups, int min_g
 
 extern "C" int egr_flashsr_set_profiling(egr_flashsr* m, int enable) {
     EGR_CHECK(m != nullptr, EGR_ERR_ARG, "handle is null");
-    for (auto& r : m->prof) { hipEventDestroy(r.a); hipEventDestroy(r.b); }
     m->prof.clear();
     m->profiling = enable < 0 ? 0 : (enable > 2 ? 2 : enable);
     return EGR_OK;
@@ -1643,7 +1561,7 @@ extern "C" int egr_flashsr_profile(egr_flashsr* m, int index, char* kind_buf, si
     static const bool dump = getenv("EGR_FSR_PROFILE_DUMP") && atoi(getenv("EGR_FSR_PROFILE_DUMP")) != 0;
     for (auto& r : m->prof) {
         float t = 0.f;
-        hipEventElapsedTime(&t, r.a, r.b);
+        hipEventElapsedTime(&t, r.ev.a, r.ev.b);
         if (dump && count && !kind_buf)              // dev: every timed launch with its layer and shape (once per read-out)
             fprintf(stderr, "[egr_flashsr profile] %-36s %9.3f ms %8.1f GFLOP %7.1f TF/s-eq  %s\n", r.kind.c_str(), t, r.flops / 1e9, t > 0 ? r.flops / t / 1e9 : 0.0,
                     r.detail.c_str());
@@ -1665,21 +1583,20 @@ extern "C" int egr_flashsr_profile(egr_flashsr* m, int index, char* kind_buf, si
 // Dense-contraction flops of one forward over `rows` rows (dry run with counting on; 2 Cin Cout Kh Kw Hout Wout per conv as executed).
 extern "C" int egr_flashsr_flop_count(egr_flashsr* m, int rows, double* flops, void* stream) {
     EGR_CHECK(m && flops && rows >= 1, EGR_ERR_ARG, "bad argument");
+    ForwardGuard guard(m->device, (hipStream_t)stream);
     m->ctxs[0]->st = (hipStream_t)stream;
-    m->use(m->ctxs[0].get());
     const egr_flashsr_config& c = m->cfg;
+    double sum = 0.0;
+    Fwd f(*m, m->ctxs[0].get(), rows, false, &m->prof, m->profiling, &sum);   // the bf16 terms, counting
     Ten x, nz, y;
-    OKR(new_ten(m, x, {rows, c.chunk}));
-    OKR(new_ten(m, nz, {rows, (int64_t)m->lat_h * m->lat_w * c.z_ch}));
-    OKR(new_ten(m, y, {rows, c.chunk}));
-    EGR_HIP(hipMemsetAsync(x.p, 0, x.bytes, m->st));
-    OKR(egr_randn(nz.p, (int64_t)m->lat_h * m->lat_w * c.z_ch, rows, 0, nullptr, m->st));
-    m->count_flops = true; m->flops = 0.0;
-    m->h2_mode = -1;
-    const int rc = forward(m, x.p, nz.p, rows, 0, y.p, nullptr);
-    m->count_flops = false;
-    EGR_HIP(hipStreamSynchronize(m->st));
-    *flops = m->flops;
+    EGR_TRY(new_ten(f, x, {rows, c.chunk}));
+    EGR_TRY(new_ten(f, nz, {rows, (int64_t)m->lat_h * m->lat_w * c.z_ch}));
+    EGR_TRY(new_ten(f, y, {rows, c.chunk}));
+    EGR_HIP(hipMemsetAsync(x.p, 0, x.bytes, f.st));
+    EGR_TRY(egr_randn(nz.p, (int64_t)m->lat_h * m->lat_w * c.z_ch, rows, 0, nullptr, f.st));
+    const int rc = forward(f, x.p, nz.p, 0, y.p, nullptr);
+    EGR_HIP(hipStreamSynchronize(f.st));
+    *flops = sum;
     return rc;
 }
 
@@ -1746,17 +1663,17 @@ extern "C" int egr_flashsr_create_from_file(egr_flashsr** out, const char* path,
             total += (bytes[i] + 255) & ~(size_t)255;
         }
         EGR_CHECK(ok, EGR_ERR_ARG, "%s: corrupt tensor index", path);
-        char* dev = nullptr;
-        if (hipMalloc((void**)&dev, total + 256) != hipSuccess) {
+        DevBuf blob;
+        if (!blob.alloc(total + 256)) {
             set_error("hipMalloc of %zu bytes for the weight blob failed", total + 256);
             return EGR_ERR_ALLOC;
         }
+        char* const dev = blob.as<char>();
         size_t dpos = 0;
         for (int i = 0; i < nt; ++i) {
             if (bytes[i]) {
                 const hipError_t ce = hipMemcpy(dev + dpos, buf.data() + offs[i], bytes[i], hipMemcpyHostToDevice);
                 if (ce != hipSuccess) {
-                    hipFree(dev);
                     set_error("hipMemcpy of tensor %s -> %s", names[i].c_str(), hipGetErrorString(ce));
                     return EGR_ERR_HIP;
                 }
@@ -1765,9 +1682,7 @@ extern "C" int egr_flashsr_create_from_file(egr_flashsr** out, const char* path,
             ds[i].data = (const float*)(dev + dpos);
             dpos += (bytes[i] + 255) & ~(size_t)255;
         }
-        const int rc = egr_flashsr_create(out, &cfg, ds.data(), nt, flags, stream);
-        hipFree(dev);
-        return rc;
+        return egr_flashsr_create(out, &cfg, ds.data(), nt, flags, stream);   // (synchronises before it returns; the blob goes after)
     } catch (const std::bad_alloc&) {
         set_error("%s: out of host memory while reading the weight blob", path);
         return EGR_ERR_ALLOC;

@@ -287,3 +287,77 @@ def test_fat_llama_next_to_a_flashsr_forward_on_another_stream(pack):
         assert torch.equal(y_sr, ref_sr)
         assert all(torch.equal(y, ref_fl) for y in y_fl)
     e.close()
+
+
+def test_no_entry_point_leaves_call_state_behind(pack):
+    """Every entry point that walks the graph -- flop_count, infer (plain, profiled, in two row groups), warmup, forward on either
+    operand scheme -- called in turn on ONE handle of the reach config of tests/test_gpu_flashsr_flags.py (one handle of it reaches
+    every operator path): each output and stage tap equals, bit for bit, what a FRESH handle under the same setting returns, the flop
+    count is the same at both ends, and the warm-up pass adds no profile record and does not count as a call."""
+    from egregora_amd import flashsr_arch as A, native
+    from test_gpu_flashsr_flags import ROWS, SEED, V, built, reach_config
+    cfg = reach_config()
+    P = A.init_params(cfg, 0)
+    L = native.lib()
+    x = (0.3 * torch.randn(ROWS, cfg.chunk, generator=torch.Generator().manual_seed(31))).cuda()
+    ids = torch.tensor([3, 4, 5, 6], dtype=torch.int64, device="cuda")
+
+    def forward(e, nz):
+        st = {}
+        y = e.c_forward(x, nz, stages=st)
+        torch.cuda.synchronize()
+        return [y.clone()] + [st[k].clone() for k in STAGES]
+
+    def infer(e):
+        y = e.c_infer(x, ids, SEED)
+        torch.cuda.synchronize()
+        return y
+
+    def records(h):
+        """Launches in the handle's profile, over all kinds."""
+        n, total = C.c_int(), 0
+        native.check(L.egr_flashsr_profile(h, 0, None, 0, None, None, None, C.byref(n)), "egr_flashsr_profile")
+        for i in range(n.value):
+            buf, la = C.create_string_buffer(128), C.c_int64()
+            native.check(L.egr_flashsr_profile(h, i, buf, 128, C.byref(la), None, None, None), "egr_flashsr_profile")
+            total += la.value
+        return total
+
+    # references: a fresh handle per setting
+    with built(cfg, P, V()) as e:
+        nz = e.noise(ROWS, ids, SEED)
+        want_inf = infer(e)
+    with built(cfg, P, V()) as e:
+        want_fwd = forward(e, nz)
+    with built(cfg, P, V()) as e:
+        e.set_split("f16x2+forward")
+        want_fwd_h2 = forward(e, nz)
+    with built(cfg, P, V()) as e:
+        native.check(L.egr_flashsr_set_streams(C.c_void_p(e.handle), 2, 2), "egr_flashsr_set_streams")
+        want_inf_groups = infer(e)
+    assert not torch.equal(want_fwd[0], want_fwd_h2[0])                                                 # the operand schemes do differ
+
+    with built(cfg, P, V()) as e:
+        h = C.c_void_p(e.handle)
+        flops = e.flop_count(ROWS)                                                   # 1
+        assert flops > 0
+        assert torch.equal(infer(e), want_inf)                                       # 2
+        native.check(L.egr_flashsr_set_profiling(h, 2), "egr_flashsr_set_profiling")  # 3
+        assert torch.equal(infer(e), want_inf)
+        n_rec, calls = records(h), e.split_info()["calls"]
+        assert n_rec > 0 and calls == 2
+        native.check(L.egr_flashsr_warmup(h, ROWS, native.stream_ptr()), "egr_flashsr_warmup")       # 4
+        assert records(h) == n_rec and e.split_info()["calls"] == calls
+        native.check(L.egr_flashsr_set_profiling(h, 0), "egr_flashsr_set_profiling")  # 5
+        assert records(h) == 0
+        e.set_split("f16x2+forward")                                                 # 6
+        for k, a, b in zip(("out",) + STAGES, forward(e, nz), want_fwd_h2):
+            assert torch.equal(a, b), ("fp16-term forward", k)
+        e.set_split("f16x2")                                                         # 7
+        for k, a, b in zip(("out",) + STAGES, forward(e, nz), want_fwd):
+            assert torch.equal(a, b), ("bf16-term forward", k)
+        assert torch.equal(infer(e), want_inf)                                       # 8
+        native.check(L.egr_flashsr_set_streams(h, 2, 2), "egr_flashsr_set_streams")   # 9
+        assert torch.equal(infer(e), want_inf_groups)
+        assert e.flop_count(ROWS) == flops                                           # 10
+        assert e.split_info()["calls"] == calls + 2
