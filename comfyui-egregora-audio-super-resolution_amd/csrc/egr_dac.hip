@@ -6,9 +6,16 @@
 // kernel.  Workspace, device checks and the stage read are the handles' shared ones (egr_handle.h).  Activations are channels-last
 // [rows][L][C]; rows are independent mono signals.  Own kernels:
 //   k_dac_snake    x + sin^2(alpha x) / (alpha + 1e-9) per channel, and the row's max |y| for the contraction that reads y
-//   k_dac_conv_in  the Cin = 1, k = 7 input convolution (with the right zero pad to a multiple of the hop)
-//   k_dac_conv_out the Cout = 1, k = 7 output convolution with tanh: per input row seven partial dots, then a 7-term gather
+//   k_dac_conv_in  the Cin = 1, k = 7 input convolution of a window at a sample offset of the whole x (zeros outside [0, n): the right
+//                  pad to a multiple of the hop, and the true ends)
+//   k_dac_conv_out the Cout = 1, k = 7 output convolution with tanh: per input row seven partial dots, then a 7-term gather; stores a
+//                  range of the window at its place in the whole y
 //   k_dac_vq       all stages of the residual quantiser in one launch; a workgroup keeps the residuals and sums of its frames in LDS
+//   k_dac_from_codes  z from integer codes, on k_dac_vq's own out_proj chain (dac_out_proj)
+// The walks run on a window of latent frames (walk_encode_window / walk_decode_window); one pass is the window [0, F), a segmented
+// call (egr_dacseg_encode / _decode) runs the windows of egr_dacseg_plan one after the other through one arena and keeps
+// only the frames whose dependency cone lies inside their window: exact in exact arithmetic, fp32 round-off here, because the operand
+// scales come from each window's own row maxima.
 // Work is enqueued on the caller's stream; nothing synchronises (the workspace grows with hipMallocAsync on that stream; the launcher's
 // split-K scratch is allocated the first time a stream needs it).
 #include <algorithm>
@@ -70,17 +77,19 @@ __global__ __launch_bounds__(256) void k_dac_snake(const float* x, const float* 
     }
 }
 
-// y[r][l][c] = b[c] + sum_t w[t][c] x[r][l + t - 3], x [rows][n] read as zero outside [0, n), l < n_pad
+// y[r][l][c] = b[c] + sum_t w[t][c] x[r][x0 + l + t - 3] for the Lw samples of a window that begins at sample x0 of the whole
+// x [rows][n] (rows n apart), read as zero outside [0, n): the right pad to a multiple of the hop, and the true ends of the signal.
+// One pass is x0 = 0, Lw = n_pad.
 __global__ __launch_bounds__(256) void k_dac_conv_in(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ b,
-                                                     float* __restrict__ y, long long n, long long n_pad, int D, long long total) {
+                                                     float* __restrict__ y, long long n, long long x0, long long Lw, int D, long long total) {
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
         const int c = (int)(i % D);
-        const long long t = i / D, l = t % n_pad, r = t / n_pad;
+        const long long t = i / D, l = t % Lw, r = t / Lw;
         const float* xr = x + r * n;
         float acc = b[c];
 #pragma unroll
         for (int k = 0; k < 7; ++k) {
-            const long long li = l + k - 3;
+            const long long li = x0 + l + k - 3;
             const float xv = (li >= 0 && li < n) ? xr[li] : 0.f;
             acc = fmaf(w[k * D + c], xv, acc);
         }
@@ -88,14 +97,17 @@ __global__ __launch_bounds__(256) void k_dac_conv_in(const float* __restrict__ x
     }
 }
 
-// y[r][l] = tanh(b + sum_t sum_c w[t][c] x[r][l + t - 3][c]): a workgroup owns 64 outputs of one row; each wave turns input rows into
-// their seven partial dots (lanes stride the channels, a fixed butterfly sums them), then 64 threads gather seven partials each.
+// y[r][l] = tanh(b + sum_t sum_c w[t][c] x[r][l + t - 3][c]) over a window x [rows][L][C] (zero outside [0, L)), of which only the
+// outputs [o0, o1) are stored: output l goes to sample y0 + l of the whole y (rows ldy apart).  One pass is o0 = 0, o1 = L = ldy,
+// y0 = 0.  A workgroup owns 64 outputs of one row; each wave turns input rows into their seven partial dots (lanes stride the
+// channels, a fixed butterfly sums them), then 64 threads gather seven partials each.
 constexpr int DAC_OUT_TL = 64;
 __global__ __launch_bounds__(256) void k_dac_conv_out(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ b,
-                                                      float* __restrict__ y, long long L, int C) {
+                                                      float* __restrict__ y, long long L, int C, long long o0, long long o1, long long y0,
+                                                      long long ldy) {
     __shared__ float part[DAC_OUT_TL + 6][8];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const long long r = blockIdx.y, l0 = (long long)blockIdx.x * DAC_OUT_TL;
+    const long long r = blockIdx.y, l0 = o0 + (long long)blockIdx.x * DAC_OUT_TL;
     for (int j = wave; j < DAC_OUT_TL + 6; j += 4) {
         const long long li = l0 - 3 + j;
         float acc[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
@@ -118,11 +130,11 @@ __global__ __launch_bounds__(256) void k_dac_conv_out(const float* __restrict__ 
     }
     __syncthreads();
     const int o = threadIdx.x;
-    if (o < DAC_OUT_TL && l0 + o < L) {
+    if (o < DAC_OUT_TL && l0 + o < o1 && l0 + o < L) {
         float v = b[0];
 #pragma unroll
         for (int t = 0; t < 7; ++t) v += part[o + t][t];
-        y[(size_t)r * L + l0 + o] = tanhf(v);
+        y[(size_t)r * ldy + y0 + l0 + o] = tanhf(v);
     }
 }
 
@@ -141,6 +153,20 @@ struct VqP {
     int latent, cd, K, ncb, TF;
     long long total, F;
 };
+
+// One channel of a stage's out_proj on a stored codebook row: bias first, then the taps in ascending order.  k_dac_vq and
+// k_dac_from_codes both sum the stages' values of this chain in stage order from 0.f, so the same codes give the same bits of z.
+template <int CD>
+__device__ __forceinline__ float dac_out_proj(const float* __restrict__ wp, const float* __restrict__ crow, float q, int cd) {
+    if (CD == 8) {
+        const float4 w0 = *(const float4*)wp, w1 = *(const float4*)(wp + 4), c0 = *(const float4*)crow, c1 = *(const float4*)(crow + 4);
+        q = fmaf(w0.x, c0.x, q); q = fmaf(w0.y, c0.y, q); q = fmaf(w0.z, c0.z, q); q = fmaf(w0.w, c0.w, q);
+        q = fmaf(w1.x, c1.x, q); q = fmaf(w1.y, c1.y, q); q = fmaf(w1.z, c1.z, q); q = fmaf(w1.w, c1.w, q);
+    } else {
+        for (int j = 0; j < cd; ++j) q = fmaf(wp[j], crow[j], q);
+    }
+    return q;
+}
 
 template <int CD>
 __global__ __launch_bounds__(256) void k_dac_vq(const VqP p) {
@@ -232,15 +258,7 @@ __global__ __launch_bounds__(256) void k_dac_vq(const VqP p) {
         // out_proj of the stored codebook row, then z += q, r -= q
         const float* crow = p.cb + ((size_t)i * K + code) * cd;
         for (int c = sub; c < latent; c += 32) {
-            const float* wp = p.out_w + ((size_t)i * latent + c) * cd;
-            float q = p.out_b[(size_t)i * latent + c];
-            if (CD == 8) {
-                const float4 w0 = *(const float4*)wp, w1 = *(const float4*)(wp + 4), c0 = *(const float4*)crow, c1 = *(const float4*)(crow + 4);
-                q = fmaf(w0.x, c0.x, q); q = fmaf(w0.y, c0.y, q); q = fmaf(w0.z, c0.z, q); q = fmaf(w0.w, c0.w, q);
-                q = fmaf(w1.x, c1.x, q); q = fmaf(w1.y, c1.y, q); q = fmaf(w1.z, c1.z, q); q = fmaf(w1.w, c1.w, q);
-            } else {
-                for (int j = 0; j < cd; ++j) q = fmaf(wp[j], crow[j], q);
-            }
+            const float q = dac_out_proj<CD>(p.out_w + ((size_t)i * latent + c) * cd, crow, p.out_b[(size_t)i * latent + c], cd);
             myz[c] += q;
             myr[c] -= q;
         }
@@ -251,6 +269,33 @@ __global__ __launch_bounds__(256) void k_dac_vq(const VqP p) {
 
 size_t vq_lds_bytes(int K, int cd, int latent, int TF) {
     return ((size_t)K * cd + 2 * (size_t)TF * latent + 2 * (size_t)TF * cd) * sizeof(float) + (size_t)TF * sizeof(int);
+}
+
+// z[r][c][f] = sum over the stages i, in order, of out_proj_i(codebook_i[codes[r][i][f]])[c] (with bias, from the rows as stored:
+// DAC-P8), straight into [rows][latent][frames].  A thread owns one frame and DAC_FC_CH channels of it: the codes are read along f,
+// the out_proj rows are wave-uniform.  A code outside [0, K) reads row 0 (the engine refuses such codes; nothing is read outside
+// a codebook whatever arrives).
+constexpr int DAC_FC_CH = 8;
+template <int CD>
+__global__ __launch_bounds__(256) void k_dac_from_codes(const VqP p) {
+    const int cd = CD ? CD : p.cd, latent = p.latent;
+    const long long f = (long long)blockIdx.x * 256 + threadIdx.x, r = blockIdx.z;
+    const int c0 = blockIdx.y * DAC_FC_CH;
+    if (f >= p.F) return;
+    float acc[DAC_FC_CH];
+#pragma unroll
+    for (int u = 0; u < DAC_FC_CH; ++u) acc[u] = 0.f;
+    for (int i = 0; i < p.ncb; ++i) {
+        const unsigned code = (unsigned)p.codes[((size_t)r * p.ncb + i) * p.F + f];
+        const float* crow = p.cb + ((size_t)i * p.K + (code < (unsigned)p.K ? code : 0u)) * cd;
+#pragma unroll
+        for (int u = 0; u < DAC_FC_CH; ++u)
+            if (c0 + u < latent)                        // block-uniform
+                acc[u] += dac_out_proj<CD>(p.out_w + ((size_t)i * latent + c0 + u) * cd, crow, p.out_b[(size_t)i * latent + c0 + u], cd);
+    }
+#pragma unroll
+    for (int u = 0; u < DAC_FC_CH; ++u)
+        if (c0 + u < latent) p.z[((size_t)r * latent + c0 + u) * p.F + f] = acc[u];
 }
 
 // ------------------------------------------------------------------------------------------------------------------ the handle
@@ -313,6 +358,61 @@ int64_t decoded_len(const egr_dac_config& c, int64_t frames) {
     int64_t L = frames;
     for (int i = 0; i < c.n_dec; ++i) L = L >= 1 ? convtr_len(L, c.dec_rates[i]) : 0;
     return L;
+}
+
+// ---- the segment plan: how far a kept frame's dependency cone reaches, from the layer list itself
+struct Reach { int tr, k, s, d, p; };                 // Conv1d (tr = 0) or ConvTranspose1d (tr = 1)
+int64_t floor_div(int64_t a, int64_t b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }
+int64_t ceil_div(int64_t a, int64_t b) { return -floor_div(-a, b); }
+
+std::vector<Reach> layer_list(const egr_dac_config& c, int kind) {
+    std::vector<Reach> v;
+    auto units = [&] { for (int d : {1, 3, 9}) { v.push_back({0, 7, 1, d, 3 * d}); v.push_back({0, 1, 1, 1, 0}); } };
+    if (kind == EGR_DAC_ENCODE) {
+        v.push_back({0, 7, 1, 1, 3});
+        for (int i = 0; i < c.n_enc; ++i) { units(); v.push_back({0, 2 * c.enc_rates[i], c.enc_rates[i], 1, (c.enc_rates[i] + 1) / 2}); }
+        v.push_back({0, 3, 1, 1, 1});
+    } else {
+        v.push_back({0, 7, 1, 1, 3});
+        for (int i = 0; i < c.n_dec; ++i) { v.push_back({1, 2 * c.dec_rates[i], c.dec_rates[i], 1, (c.dec_rates[i] + 1) / 2}); units(); }
+        v.push_back({0, 7, 1, 1, 3});
+    }
+    return v;
+}
+
+// Frames of margin a window needs on the (left, right) of the frames it keeps.  The outputs of kept frame 0 -- the frame itself
+// (encode) or its H = prod dec_rates samples (decode) -- are walked back through the layers: a Conv1d output o reads
+// o s - p + t d, a ConvTranspose1d output j receives input i where j = i s - p + t (0 <= t < k).  Every rule commutes with a shift
+// by whole frames, so frame 0 stands for all.  A value is exact when this cone lies inside the window: whatever the window pads
+// with zeros at its cut ends then lies outside the cone.
+void seg_margins(const egr_dac_config& c, int kind, int64_t* left, int64_t* right) {
+    int64_t hop = 1, lo = 0, hi = 0;
+    if (kind == EGR_DAC_ENCODE) for (int i = 0; i < c.n_enc; ++i) hop *= c.enc_rates[i];
+    else for (int i = 0; i < c.n_dec; ++i) hop *= c.dec_rates[i];
+    if (kind == EGR_DAC_DECODE) hi = hop - 1;
+    const std::vector<Reach> v = layer_list(c, kind);
+    for (size_t i = v.size(); i-- > 0;) {
+        const Reach& r = v[i];
+        if (r.tr) { lo = ceil_div(lo + r.p - (r.k - 1), r.s); hi = floor_div(hi + r.p, r.s); }
+        else { lo = lo * r.s - r.p; hi = hi * r.s - r.p + (int64_t)(r.k - 1) * r.d; }
+    }
+    if (kind == EGR_DAC_ENCODE) {                        // samples [lo, hi] around frame 0's [0, hop) -> frames
+        *left = std::max<int64_t>(0, ceil_div(-lo, hop));
+        *right = std::max<int64_t>(0, ceil_div(hi + 1 - hop, hop));
+    } else {
+        *left = std::max<int64_t>(0, -lo);
+        *right = std::max<int64_t>(0, hi);
+    }
+}
+
+// Interior windows are widened to a multiple of this many frames: every level with at least 8 samples a frame is then a multiple of
+// 128 samples long, which is what k_conv1d_s3 asks of a row (one pass meets it only when the file's length happens to).
+constexpr int64_t DAC_SEG_ALIGN = 16;
+
+int64_t seg_window_max(const egr_dac_config& c, int kind, int64_t seg_frames) {
+    int64_t l, r;
+    seg_margins(c, kind, &l, &r);
+    return (seg_frames + l + r + DAC_SEG_ALIGN - 1) / DAC_SEG_ALIGN * DAC_SEG_ALIGN;
 }
 
 int check_config(const egr_dac_config* c, const char* who) {
@@ -446,6 +546,7 @@ struct Walk {
     char* base = nullptr; size_t off = 0;
     unsigned* amax_pool = nullptr; int amax_used = 0;
     int rc = EGR_OK;
+    bool notes = true;              // a segmented call records no stage
     float* take(size_t floats) {
         off = (off + 255) & ~(size_t)255;
         float* p = launch ? (float*)(base + off) : nullptr;
@@ -458,7 +559,7 @@ struct Walk {
         ++amax_used;
         return p;
     }
-    void note(int kind, int index, const float* p, int64_t count) { if (launch) m.stages.push_back({kind, index, p, count}); }
+    void note(int kind, int index, const float* p, int64_t count) { if (launch && notes) m.stages.push_back({kind, index, p, count}); }
     bool go() const { return launch && rc == EGR_OK; }
     // y = snake(x) (y may be x); returns the row maxima of y
     const unsigned* snake(const Snake& s, const float* x, float* y, int64_t L) {
@@ -514,7 +615,7 @@ size_t max_enc_tensor(const Dac& m, int rows, int64_t n_pad) {
 int launch_vq(Walk& w, const float* ze_cl, float* z_cl, int* codes, int64_t F) {
     Dac& m = w.m;
     const long long total = (long long)w.rows * F;
-    float* rdump = m.keep_vq_inputs ? w.take((size_t)m.cfg.n_codebooks * total * m.latent) : nullptr;
+    float* rdump = m.keep_vq_inputs && w.notes ? w.take((size_t)m.cfg.n_codebooks * total * m.latent) : nullptr;
     if (!w.go()) return w.rc;
     VqP p = m.vq;
     p.ze = ze_cl; p.z = z_cl; p.codes = codes; p.rdump = rdump; p.total = total; p.F = F; p.TF = m.TF;
@@ -526,23 +627,30 @@ int launch_vq(Walk& w, const float* ze_cl, float* z_cl, int* codes, int64_t F) {
     return EGR_OK;
 }
 
-int walk_encode(Walk& w, const float* x, int64_t n, float* z, int* codes) {
+// A window of the encoder: `frames` latent frames that begin at sample x0 of the whole x [rows][n]; the kept frames [k0, k1) of
+// the window (window-relative) go to frame `at` onwards of the whole-length channels-last ze_all [rows][F][latent].  One pass is
+// the window [0, F): x0 = 0, every frame kept, and the last convolution writes ze_all itself.
+struct EncWindow { int64_t x0, frames, k0, k1, at, F; };
+
+int walk_encode_window(Walk& w, const float* x, int64_t n, const EncWindow& win, float* ze_all) {
     Dac& m = w.m;
     const egr_dac_config& c = m.cfg;
-    int64_t n_pad, F;
-    lengths(c, n, &n_pad, &F, nullptr);
+    int64_t hop = 1;
+    for (int i = 0; i < c.n_enc; ++i) hop *= c.enc_rates[i];
+    const int64_t Lw = win.frames * hop;
     const int rows = w.rows;
+    w.amax_used = 0;
     w.amax_pool = (unsigned*)w.take((size_t)DAC_AMAX_SLOTS * rows * EGR_ROW_AMAX_STRIDE);
     if (w.go()) EGR_HIP(hipMemsetAsync(w.amax_pool, 0, (size_t)DAC_AMAX_SLOTS * rows * EGR_ROW_AMAX_STRIDE * 4, w.st));
-    const size_t mx = max_enc_tensor(m, rows, n_pad);
+    const size_t mx = max_enc_tensor(m, rows, Lw);
     float* S[3] = {w.take(mx), w.take(mx), w.take(mx)};
     int C = c.encoder_dim;
-    int64_t L = n_pad;
+    int64_t L = Lw;
     float* cur = w.take((size_t)rows * L * C);
     if (w.go()) {
         const long long total = (long long)rows * L * C;
         const unsigned nb = (unsigned)std::min<long long>((total + 255) / 256, 8192);
-        hipLaunchKernelGGL(k_dac_conv_in, dim3(nb), dim3(256), 0, w.st, x, m.in_w, m.in_b, cur, (long long)n, (long long)n_pad, C, total);
+        hipLaunchKernelGGL(k_dac_conv_in, dim3(nb), dim3(256), 0, w.st, x, m.in_w, m.in_b, cur, (long long)n, (long long)win.x0, (long long)Lw, C, total);
     }
     w.note(EGR_DAC_STAGE_ENC, 0, cur, (int64_t)rows * L * C);
     for (int i = 0; i < c.n_enc; ++i) {
@@ -556,15 +664,70 @@ int walk_encode(Walk& w, const float* x, int64_t n, float* z, int* codes) {
         cur = out; L = Lo; C *= 2;
         w.note(EGR_DAC_STAGE_ENC, i + 1, cur, (int64_t)rows * L * C);
     }
+    if (L != win.frames) { if (!w.rc) { set_error("DAC: a window of %lld frames encodes to %lld", (long long)win.frames, (long long)L); w.rc = EGR_ERR_UNSUPPORTED; } return w.rc; }
     float* a = other(S, cur);
     const unsigned* ra = w.snake(m.enc_s, cur, a, L);
-    float* ze = w.take((size_t)rows * L * m.latent);
+    const bool whole = win.k0 == 0 && win.k1 == L && win.at == 0 && L == win.F;
+    float* ze = whole ? ze_all : w.take((size_t)rows * L * m.latent);
     w.conv(m.enc_out, a, ra, ze, nullptr, m.enc_out.bias, L, L);
     w.note(EGR_DAC_STAGE_ENC, c.n_enc + 1, ze, (int64_t)rows * L * m.latent);
-    float* z_cl = w.take((size_t)rows * L * m.latent);
-    { const int rc = launch_vq(w, ze, z_cl, codes, L); if (rc) return rc; }
-    if (w.go()) { const int rc = egr_transpose_batched(z_cl, z, rows, (int)L, m.latent, w.st); if (rc) return rc; }
+    if (!whole && w.go())
+        EGR_HIP(hipMemcpy2DAsync(ze_all + (size_t)win.at * m.latent, (size_t)win.F * m.latent * 4, ze + (size_t)win.k0 * m.latent, (size_t)L * m.latent * 4,
+                                 (size_t)(win.k1 - win.k0) * m.latent * 4, (size_t)rows, hipMemcpyDeviceToDevice, w.st));
     if (w.go()) EGR_HIP(hipGetLastError());
+    return w.rc;
+}
+
+// quantiser and transposes over the whole-length ze_all [rows][F][latent]
+int walk_encode_tail(Walk& w, float* ze_all, int64_t F, float* z, int* codes, float* ze_out) {
+    Dac& m = w.m;
+    float* z_cl = w.take((size_t)w.rows * F * m.latent);
+    { const int rc = launch_vq(w, ze_all, z_cl, codes, F); if (rc) return rc; }
+    if (w.go()) { const int rc = egr_transpose_batched(z_cl, z, w.rows, (int)F, m.latent, w.st); if (rc) return rc; }
+    if (ze_out && w.go()) { const int rc = egr_transpose_batched(ze_all, ze_out, w.rows, (int)F, m.latent, w.st); if (rc) return rc; }
+    if (w.go()) EGR_HIP(hipGetLastError());
+    return w.rc;
+}
+
+// One pass: the window [0, F), every block output kept for egr_dac_stage.
+int walk_encode(Walk& w, const float* x, int64_t n, float* z, int* codes) {
+    int64_t F;
+    lengths(w.m.cfg, n, nullptr, &F, nullptr);
+    float* ze_all = w.take((size_t)w.rows * F * w.m.latent);
+    { const int rc = walk_encode_window(w, x, n, EncWindow{0, F, 0, F, 0, F}, ze_all); if (rc) return rc; }
+    return walk_encode_tail(w, ze_all, F, z, codes, nullptr);
+}
+
+// Segments of seg_frames frames (egr_dacseg_plan), one after the other on the stream through one arena behind the whole-length
+// ze_all; the quantiser then runs once over ze_all, in the arena the windows have left.  `sizing`: lay out the largest window a
+// segment of seg_frames can have instead (so that the arena depends on rows and seg_frames only), and the quantiser's buffers.
+int walk_encode_segmented(Walk& w, const float* x, int64_t n, float* z, int* codes, float* ze_out, int64_t seg_frames, bool sizing) {
+    Dac& m = w.m;
+    int64_t F, hop = 1;
+    lengths(m.cfg, n, nullptr, &F, nullptr);
+    for (int i = 0; i < m.cfg.n_enc; ++i) hop *= m.cfg.enc_rates[i];
+    float* ze_all = w.take((size_t)w.rows * F * m.latent);
+    const size_t arena = w.off;
+    size_t top = arena;
+    if (sizing) {
+        const int64_t Wmax = seg_window_max(m.cfg, EGR_DAC_ENCODE, seg_frames);
+        walk_encode_window(w, nullptr, n, EncWindow{0, Wmax, 0, 1, 0, Wmax + 1}, nullptr);
+        top = w.off;
+    } else {
+        int64_t nseg = 0;
+        EGR_TRY(egr_dacseg_plan(&m.cfg, EGR_DAC_ENCODE, n, seg_frames, 0, nullptr, &nseg));
+        for (int64_t j = 0; j < nseg; ++j) {
+            egr_dac_segment sp;
+            EGR_TRY(egr_dacseg_plan(&m.cfg, EGR_DAC_ENCODE, n, seg_frames, j, &sp, nullptr));
+            w.off = arena;
+            const EncWindow win{sp.win_lo * hop, sp.win_hi - sp.win_lo, sp.keep_lo - sp.win_lo, sp.keep_hi - sp.win_lo, sp.keep_lo, F};
+            { const int rc = walk_encode_window(w, x, n, win, ze_all); if (rc) return rc; }
+            top = std::max(top, w.off);
+        }
+    }
+    w.off = arena;
+    { const int rc = walk_encode_tail(w, ze_all, F, z, codes, ze_out); if (rc) return rc; }
+    w.off = std::max(top, w.off);
     return w.rc;
 }
 
@@ -579,10 +742,17 @@ int walk_quantize(Walk& w, const float* ze, int64_t F, float* z, int* codes) {
     return w.rc;
 }
 
-int walk_decode(Walk& w, const float* z, int64_t F, float* y) {
+// A window of the decoder: `frames` latent frames from frame f0 of the whole-length channels-last z_all [rows][F][latent] (or, z_all
+// null, the whole z [rows][latent][frames] as given: one pass).  Of the window's samples only [o0, o1) are stored, sample l at
+// y0 + l of the whole y (rows ldy apart).
+struct DecWindow { int64_t frames; const float* z_all; int64_t f0, F, o0, o1, y0, ldy; };
+
+int walk_decode_window(Walk& w, const float* z, const DecWindow& win, float* y) {
     Dac& m = w.m;
     const egr_dac_config& c = m.cfg;
     const int rows = w.rows;
+    const int64_t F = win.frames;
+    w.amax_used = 0;
     w.amax_pool = (unsigned*)w.take((size_t)DAC_AMAX_SLOTS * rows * EGR_ROW_AMAX_STRIDE);
     if (w.go()) EGR_HIP(hipMemsetAsync(w.amax_pool, 0, (size_t)DAC_AMAX_SLOTS * rows * EGR_ROW_AMAX_STRIDE * 4, w.st));
     size_t mx = (size_t)rows * F * std::max(m.latent, c.decoder_dim), mxY = 0;
@@ -603,7 +773,10 @@ int walk_decode(Walk& w, const float* z, int64_t F, float* y) {
     int64_t L = F;
     float* z_cl = S[0];
     const unsigned* rz = w.amax_slot();
-    if (w.go()) { const int rc = egr_transpose_batched(z, z_cl, rows, m.latent, (int)F, w.st); if (rc) return rc; }
+    if (w.go() && !win.z_all) { const int rc = egr_transpose_batched(z, z_cl, rows, m.latent, (int)F, w.st); if (rc) return rc; }
+    if (w.go() && win.z_all)
+        EGR_HIP(hipMemcpy2DAsync(z_cl, (size_t)F * m.latent * 4, win.z_all + (size_t)win.f0 * m.latent, (size_t)win.F * m.latent * 4, (size_t)F * m.latent * 4,
+                                 (size_t)rows, hipMemcpyDeviceToDevice, w.st));
     if (w.go()) { const int rc = egr_absmax_rows(z_cl, rows, F * m.latent, 1, 0, (float*)rz, w.st); if (rc) return rc; }
     int C = c.decoder_dim;
     float* cur = w.take((size_t)rows * L * C);
@@ -630,11 +803,50 @@ int walk_decode(Walk& w, const float* z, int64_t F, float* y) {
     }
     float* a = other(S, cur);
     w.snake(m.dec_s, cur, a, L);
-    if (w.go()) {
-        hipLaunchKernelGGL(k_dac_conv_out, dim3((unsigned)((L + DAC_OUT_TL - 1) / DAC_OUT_TL), (unsigned)rows), dim3(256), 0, w.st, a, m.out_w, m.out_b, y,
-                           (long long)L, C);
+    const int64_t o0 = std::max<int64_t>(0, win.o0), o1 = std::min(L, win.o1);
+    if (w.go() && o1 > o0) {
+        hipLaunchKernelGGL(k_dac_conv_out, dim3((unsigned)((o1 - o0 + DAC_OUT_TL - 1) / DAC_OUT_TL), (unsigned)rows), dim3(256), 0, w.st, a, m.out_w, m.out_b, y,
+                           (long long)L, C, (long long)o0, (long long)o1, (long long)win.y0, (long long)win.ldy);
         EGR_HIP(hipGetLastError());
     }
+    return w.rc;
+}
+
+// One pass: the window [0, F), every block output kept for egr_dac_stage.
+int walk_decode(Walk& w, const float* z, int64_t F, float* y) {
+    const int64_t n_dec = decoded_len(w.m.cfg, F);
+    return walk_decode_window(w, z, DecWindow{F, nullptr, 0, F, 0, n_dec, 0, n_dec}, y);
+}
+
+// z is transposed once into a whole-length channels-last buffer; every window copies its frame slice out of it.  `sizing` as in
+// walk_encode_segmented.
+int walk_decode_segmented(Walk& w, const float* z, int64_t F, float* y, int64_t seg_frames, bool sizing) {
+    Dac& m = w.m;
+    int64_t H = 1;
+    for (int i = 0; i < m.cfg.n_dec; ++i) H *= m.cfg.dec_rates[i];
+    const int64_t n_dec = decoded_len(m.cfg, F);
+    float* z_all = w.take((size_t)w.rows * F * m.latent);
+    const size_t arena = w.off;
+    size_t top = arena;
+    if (sizing) {
+        const int64_t Wmax = seg_window_max(m.cfg, EGR_DAC_DECODE, seg_frames);
+        walk_decode_window(w, nullptr, DecWindow{Wmax, nullptr, 0, Wmax, 0, 0, 0, 0}, nullptr);
+        top = w.off;
+    } else {
+        if (w.go()) { const int rc = egr_transpose_batched(z, z_all, w.rows, m.latent, (int)F, w.st); if (rc) return rc; }
+        int64_t nseg = 0;
+        EGR_TRY(egr_dacseg_plan(&m.cfg, EGR_DAC_DECODE, F, seg_frames, 0, nullptr, &nseg));
+        for (int64_t j = 0; j < nseg; ++j) {
+            egr_dac_segment sp;
+            EGR_TRY(egr_dacseg_plan(&m.cfg, EGR_DAC_DECODE, F, seg_frames, j, &sp, nullptr));
+            w.off = arena;
+            const int64_t base = sp.win_lo * H;                       // the whole-y position of the window's sample 0
+            const DecWindow win{sp.win_hi - sp.win_lo, z_all, sp.win_lo, F, sp.out_lo - base, sp.out_hi - base, base, n_dec};
+            { const int rc = walk_decode_window(w, nullptr, win, y); if (rc) return rc; }
+            top = std::max(top, w.off);
+        }
+    }
+    w.off = top;
     return w.rc;
 }
 
@@ -832,7 +1044,7 @@ extern "C" int egr_dac_encode(void* handle, const float* x, int rows, int64_t n,
     int64_t n_pad, F;
     lengths(m->cfg, n, &n_pad, &F, nullptr);
     EGR_CHECK(F >= 1, EGR_ERR_ARG, "egr_dac_encode: no frames");
-    EGR_CHECK((long long)rows * n_pad < (1LL << 31), EGR_ERR_UNSUPPORTED, "egr_dac_encode: rows * padded length = %lld does not index with an int (one pass only)",
+    EGR_CHECK((long long)rows * n_pad < (1LL << 31), EGR_ERR_UNSUPPORTED, "egr_dac_encode: rows * padded length = %lld does not index with an int (egr_dacseg_encode takes it)",
               (long long)rows * n_pad);
     return run(*m, rows, (hipStream_t)stream, [&](Walk& w) { return walk_encode(w, x, n, z, codes); });
 }
@@ -851,9 +1063,142 @@ extern "C" int egr_dac_decode(void* handle, const float* z, int rows, int64_t fr
     EGR_CHECK(z && y, EGR_ERR_ARG, "egr_dac_decode: null argument");
     const int64_t n_dec = decoded_len(m->cfg, frames);
     EGR_CHECK(n_dec >= 1, EGR_ERR_ARG, "egr_dac_decode: %lld frames decode to nothing", (long long)frames);
-    EGR_CHECK((long long)rows * n_dec < (1LL << 31), EGR_ERR_UNSUPPORTED, "egr_dac_decode: rows * decoded length = %lld does not index with an int (one pass only)",
+    EGR_CHECK((long long)rows * n_dec < (1LL << 31), EGR_ERR_UNSUPPORTED, "egr_dac_decode: rows * decoded length = %lld does not index with an int (egr_dacseg_decode takes it)",
               (long long)rows * n_dec);
     return run(*m, rows, (hipStream_t)stream, [&](Walk& w) { return walk_decode(w, z, frames, y); });
+}
+
+extern "C" int egr_dacseg_plan(const egr_dac_config* cfg, int kind, int64_t length, int64_t seg_frames, int64_t index, egr_dac_segment* seg,
+                                    int64_t* n_segments) {
+    { const int rc = check_config(cfg, "egr_dacseg_plan"); if (rc) return rc; }
+    EGR_CHECK((kind == EGR_DAC_ENCODE || kind == EGR_DAC_DECODE) && length >= 1 && seg_frames >= 1, EGR_ERR_ARG, "egr_dacseg_plan: bad argument");
+    const egr_dac_config& c = *cfg;
+    for (int i = 0; i < c.n_enc; ++i) EGR_CHECK(c.enc_rates[i] >= 2, EGR_ERR_UNSUPPORTED, "egr_dacseg_plan: an encoder rate of 1 is not cut into segments");
+    for (int i = 0; i < c.n_dec; ++i) EGR_CHECK(c.dec_rates[i] >= 2, EGR_ERR_UNSUPPORTED, "egr_dacseg_plan: a decoder rate of 1 is not cut into segments");
+    int64_t F = length, n_dec = 0, per = 1;              // per: samples a frame, of x (encode) or of y (decode)
+    if (kind == EGR_DAC_ENCODE) {
+        lengths(c, length, nullptr, &F, nullptr);
+        for (int i = 0; i < c.n_enc; ++i) per *= c.enc_rates[i];
+    } else {
+        n_dec = decoded_len(c, F);
+        for (int i = 0; i < c.n_dec; ++i) per *= c.dec_rates[i];
+    }
+    EGR_CHECK(F >= 1, EGR_ERR_ARG, "egr_dacseg_plan: no frames");
+    const int64_t nseg = (F + seg_frames - 1) / seg_frames;
+    if (n_segments) *n_segments = nseg;
+    if (!seg) return EGR_OK;
+    EGR_CHECK(index >= 0 && index < nseg, EGR_ERR_ARG, "egr_dacseg_plan: segment %lld of %lld", (long long)index, (long long)nseg);
+    int64_t ml, mr;
+    seg_margins(c, kind, &ml, &mr);
+    egr_dac_segment s;
+    s.keep_lo = index * seg_frames;
+    s.keep_hi = std::min(F, s.keep_lo + seg_frames);
+    s.win_lo = std::max<int64_t>(0, s.keep_lo - ml);
+    s.win_hi = std::min(F, s.keep_hi + mr);
+    int64_t extra = (DAC_SEG_ALIGN - (s.win_hi - s.win_lo) % DAC_SEG_ALIGN) % DAC_SEG_ALIGN;     // widen: left first, then right
+    const int64_t tl = std::min(extra, s.win_lo);
+    s.win_lo -= tl;
+    extra -= tl;
+    s.win_hi += std::min(extra, F - s.win_hi);
+    if (kind == EGR_DAC_ENCODE) {
+        s.in_lo = s.win_lo * per;
+        s.in_hi = std::min(length, s.win_hi * per);
+        s.out_lo = s.keep_lo;
+        s.out_hi = s.keep_hi;
+    } else {
+        s.in_lo = s.win_lo;
+        s.in_hi = s.win_hi;
+        s.out_lo = std::min(n_dec, s.keep_lo * per);
+        s.out_hi = index == nseg - 1 ? n_dec : std::min(n_dec, s.keep_hi * per);
+    }
+    *seg = s;
+    return EGR_OK;
+}
+
+namespace {
+// the largest seg_frames whose widest window still indexes with an int (rows * window samples), 0 when none does
+int64_t seg_frames_cap(const egr_dac_config& c, int kind, int rows) {
+    int64_t per = 1, ml, mr;
+    if (kind == EGR_DAC_ENCODE) for (int i = 0; i < c.n_enc; ++i) per *= c.enc_rates[i];
+    else for (int i = 0; i < c.n_dec; ++i) per *= c.dec_rates[i];
+    seg_margins(c, kind, &ml, &mr);
+    return std::max<int64_t>(0, ((1LL << 31) - 1) / ((int64_t)rows * per) - ml - mr - DAC_SEG_ALIGN);
+}
+int64_t clamp_seg_frames(const egr_dac_config& c, int kind, int rows, int64_t seg_frames, int64_t F) {
+    return std::min(std::min(seg_frames, F), seg_frames_cap(c, kind, rows));       // (more than F frames a segment is one window)
+}
+template <class F>
+int run_segmented(Dac& m, int rows, hipStream_t st, F walk) {
+    Walk dry{m, nullptr, false, rows};
+    dry.notes = false;
+    { const int rc = walk(dry, true); if (rc) return rc; }
+    EGR_TRY(m.ws.grow(dry.off + 256, st));
+    m.stages.clear();                                    // no stage survives a segmented call: egr_dac_stage then refuses
+    Walk w{m, st, true, rows};
+    w.notes = false;
+    w.base = (char*)m.ws.p;
+    return walk(w, false);
+}
+}  // namespace
+
+extern "C" size_t egr_dacseg_workspace_bytes(void* handle, int rows, int64_t seg_frames, int64_t n, int kind) {
+    Dac* m = (Dac*)handle;
+    if (!m || rows < 1 || rows > 65535 || n < 1 || seg_frames < 1 || (kind != EGR_DAC_ENCODE && kind != EGR_DAC_DECODE)) return 0;
+    int64_t F = 0;
+    lengths(m->cfg, n, nullptr, &F, nullptr);
+    if (F < 1) return 0;
+    const int64_t S = std::min(seg_frames, seg_frames_cap(m->cfg, kind, rows));     // (not clamped to F: the arena depends on rows and seg_frames only)
+    if (S < 1) return 0;
+    Walk dry{*m, nullptr, false, rows};
+    dry.notes = false;
+    if (kind == EGR_DAC_ENCODE) walk_encode_segmented(dry, nullptr, n, nullptr, nullptr, nullptr, S, true);
+    else walk_decode_segmented(dry, nullptr, F, nullptr, S, true);
+    return dry.rc ? 0 : dry.off + 256;
+}
+
+extern "C" size_t egr_dacseg_workspace_held(void* handle) { return handle ? ((Dac*)handle)->ws.bytes : 0; }
+
+extern "C" int egr_dacseg_encode(void* handle, const float* x, int rows, int64_t n, float* z, int* codes, float* ze_or_null, int64_t seg_frames,
+                                        void* stream) {
+    Dac* m = (Dac*)handle;
+    { const int rc = begin_call(m, "egr_dacseg_encode", rows, n); if (rc) return rc; }
+    EGR_CHECK(x && z && codes, EGR_ERR_ARG, "egr_dacseg_encode: null argument");
+    EGR_CHECK(seg_frames >= 1, EGR_ERR_ARG, "egr_dacseg_encode: seg_frames < 1");
+    int64_t F;
+    lengths(m->cfg, n, nullptr, &F, nullptr);
+    EGR_CHECK(F >= 1, EGR_ERR_ARG, "egr_dacseg_encode: no frames");
+    EGR_CHECK((long long)rows * F < (1LL << 31) / 32, EGR_ERR_UNSUPPORTED, "egr_dacseg_encode: rows * frames = %lld is more than the quantiser indexes",
+              (long long)rows * F);
+    const int64_t S = clamp_seg_frames(m->cfg, EGR_DAC_ENCODE, rows, seg_frames, F);
+    EGR_CHECK(S >= 1, EGR_ERR_UNSUPPORTED, "egr_dacseg_encode: %d rows leave no window that indexes with an int", rows);
+    return run_segmented(*m, rows, (hipStream_t)stream, [&](Walk& w, bool sizing) { return walk_encode_segmented(w, x, n, z, codes, ze_or_null, S, sizing); });
+}
+
+extern "C" int egr_dacseg_decode(void* handle, const float* z, int rows, int64_t frames, float* y, int64_t seg_frames, void* stream) {
+    Dac* m = (Dac*)handle;
+    { const int rc = begin_call(m, "egr_dacseg_decode", rows, frames); if (rc) return rc; }
+    EGR_CHECK(z && y, EGR_ERR_ARG, "egr_dacseg_decode: null argument");
+    EGR_CHECK(seg_frames >= 1, EGR_ERR_ARG, "egr_dacseg_decode: seg_frames < 1");
+    const int64_t F = frames, n_dec = decoded_len(m->cfg, F);
+    EGR_CHECK(n_dec >= 1, EGR_ERR_ARG, "egr_dacseg_decode: %lld frames decode to nothing", (long long)frames);
+    EGR_CHECK(F < (1LL << 31), EGR_ERR_UNSUPPORTED, "egr_dacseg_decode: %lld frames are more than the transpose indexes", (long long)F);
+    const int64_t S = clamp_seg_frames(m->cfg, EGR_DAC_DECODE, rows, seg_frames, F);
+    EGR_CHECK(S >= 1, EGR_ERR_UNSUPPORTED, "egr_dacseg_decode: %d rows leave no window that indexes with an int", rows);
+    return run_segmented(*m, rows, (hipStream_t)stream, [&](Walk& w, bool sizing) { return walk_decode_segmented(w, z, F, y, S, sizing); });
+}
+
+extern "C" int egr_dacseg_from_codes(void* handle, const int* codes, int rows, int64_t frames, float* z, void* stream) {
+    Dac* m = (Dac*)handle;
+    { const int rc = begin_call(m, "egr_dacseg_from_codes", rows, frames); if (rc) return rc; }
+    EGR_CHECK(codes && z, EGR_ERR_ARG, "egr_dacseg_from_codes: null argument");
+    EGR_CHECK((frames + 255) / 256 < (1LL << 31), EGR_ERR_UNSUPPORTED, "egr_dacseg_from_codes: too many frames");
+    VqP p = m->vq;
+    p.codes = (int*)codes; p.z = z; p.F = frames; p.total = (long long)rows * frames;
+    const dim3 grid((unsigned)((frames + 255) / 256), (unsigned)((m->latent + DAC_FC_CH - 1) / DAC_FC_CH), (unsigned)rows);
+    if (p.cd == 8) hipLaunchKernelGGL(k_dac_from_codes<8>, grid, dim3(256), 0, (hipStream_t)stream, p);
+    else hipLaunchKernelGGL(k_dac_from_codes<0>, grid, dim3(256), 0, (hipStream_t)stream, p);
+    EGR_HIP(hipGetLastError());
+    return EGR_OK;
 }
 
 extern "C" int egr_dac_stage(void* handle, int stage, int index, float* dst, int64_t capacity, int64_t* count, void* stream) {

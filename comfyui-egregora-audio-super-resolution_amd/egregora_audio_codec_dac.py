@@ -8,7 +8,8 @@ Deliberate, documented differences from the reference (SPEC.md 4e):
           reproduced: the C channels of a batch element are C mono rows, as upstream's own `compress` treats channels.
   DAC-Q2  rate conversion uses this pack's polyphase kernel (resample.resample_hq), not torchaudio.
   The checkpoint is never downloaded (dac_weights.discover); `device` is accepted and ignored, there is no CPU path.
-  The DICT also carries `codes`: a list over the batch of int64 [C, n_codebooks, frames].
+  The DICT also carries `codes`: a list over the batch of int64 [C, n_codebooks, frames]; Decode takes a DICT whose `latents` is
+  missing or empty from them (dac_engine.from_codes).  Inputs above the workspace budget run in segments (dac_engine.choose_path).
 """
 import torch
 
@@ -91,14 +92,19 @@ class Egregora_DAC_Decode:
         sr = int(codes.get("sample_rate", 48000))
         model_sr = int(codes.get("model_sample_rate", sr))
         latents_b = codes.get("latents", [])
-        if not latents_b:
+        codes_b = [] if latents_b else codes.get("codes", [])
+        if not latents_b and not codes_b:
             raise ValueError("codes.latents empty")
         eng = _engine(model_type)
         dev = torch.device("cuda", eng.device)
         outs = []
-        for z_list in latents_b:
+        for z_list in latents_b or codes_b:
             z = z_list[0] if isinstance(z_list, (list, tuple)) else z_list
-            z = z.to(dev).float()
+            if latents_b:
+                z = z.to(dev).float()
+            else:  # no latents: z from the integer codes [C, n_codebooks, frames], as upstream's decompress does
+                c = z.to(dev)
+                z = eng.from_codes(c.unsqueeze(0) if c.dim() == 2 else c)
             if z.dim() == 2:  # [latent, frames]: one row
                 z = z.unsqueeze(0)
             y = eng.decode(z)  # [C,T] at the model's rate

@@ -175,6 +175,12 @@ SIGNATURES = {
     "egr_dac_quantize": (_i, [_vp, _vp, _i, _i64, _vp, _vp, _vp]),
     "egr_dac_decode": (_i, [_vp, _vp, _i, _i64, _vp, _vp]),
     "egr_dac_stage": (_i, [_vp, _i, _i, _vp, _i64, C.POINTER(_i64), _vp]),
+    "egr_dacseg_plan": (_i, [_vp, _i, _i64, _i64, _i64, _vp, C.POINTER(_i64)]),
+    "egr_dacseg_encode": (_i, [_vp, _vp, _i, _i64, _vp, _vp, _vp, _i64, _vp]),
+    "egr_dacseg_decode": (_i, [_vp, _vp, _i, _i64, _vp, _i64, _vp]),
+    "egr_dacseg_workspace_bytes": (C.c_size_t, [_vp, _i, _i64, _i64, _i]),
+    "egr_dacseg_workspace_held": (C.c_size_t, [_vp]),
+    "egr_dacseg_from_codes": (_i, [_vp, _vp, _i, _i64, _vp, _vp]),
 }
 
 FSR_MAX = 8

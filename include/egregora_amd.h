@@ -777,6 +777,43 @@ int egr_dac_quantize(void* handle, const float* ze, int rows, int64_t frames, fl
 int egr_dac_decode(void* handle, const float* z, int rows, int64_t frames, float* y, void* stream);
 int egr_dac_stage(void* handle, int stage, int index, float* dst, int64_t capacity, int64_t* count, void* stream);
 
+/* Long inputs in segments: the egr_dacseg_* family, on the handle of egr_dac_create.  The codec has no state: every layer is a finite convolution, so a window of frames
+ * widened by the network's reach computes the frames in its middle exactly as one pass does.  One pass is the window [0, F).
+ *   egr_dacseg_plan : host only, no device or handle.  `kind` EGR_DAC_ENCODE: length = n samples; EGR_DAC_DECODE: length =
+ *                      frames.  Segment `index` of F frames cut every seg_frames, as half-open ranges: keep = the latent frames the
+ *                      segment answers for; win = the frames its walk runs on (keep widened by the margins, which the library
+ *                      derives from the layer list, clamped to [0, F), and widened further to a multiple of 16 frames where the
+ *                      file allows); in = samples of x (encode) or frames of z (decode) read; out = frames of ze / z / codes
+ *                      (encode) or samples of y (decode) written.  keep and out partition their axes.  seg NULL: only *n_segments.
+ *   egr_dacseg_encode / egr_dacseg_decode : the arguments of the one-pass calls (whole tensors on the device) and
+ *                      seg_frames >= 1 (else EGR_ERR_ARG; clamped to the largest whose window the walk indexes with an int).  Every
+ *                      window is enqueued on `stream`, nothing synchronises between them, nothing is kept from call to call.  The
+ *                      encoder's kept frames go to a whole-length channels-last ze, on which the quantiser and the transposes
+ *                      run ONCE after the last window; ze_or_null receives that encoder output [rows][latent][frames].  The
+ *                      decoder transposes z once.  Operand scales come from each window's own row maxima, so the result equals
+ *                      one pass to fp32 round-off, not bit for bit, and differs in the same way between two values of seg_frames;
+ *                      seg_frames >= frames is one window and returns the bits of egr_dac_encode / egr_dac_decode.  Encoder rows
+ *                      * frames stay below 2^26 (the quantiser's index).  egr_dac_stage after a segmented call: EGR_ERR_ARG.
+ *   egr_dacseg_workspace_bytes : what such a call grows the workspace to: a part that depends on (rows, seg_frames) only,
+ *                      plus whole-length buffers of 2 (encode) or 1 (decode) x latent_dim floats per frame and row.
+ *   egr_dacseg_workspace_held : bytes of workspace the handle holds now (it grows to the largest call so far and is kept).
+ *   egr_dacseg_from_codes : codes int32 [rows][n_codebooks][frames] -> z [rows][latent][frames], the sum over the stages of
+ *                      out_proj(codebook row) in the quantiser's own order and arithmetic: the codes of an encode give the bits of
+ *                      that encode's z.  A code outside [0, codebook_size) reads row 0.  Needs no workspace. */
+#define EGR_DAC_ENCODE 0
+#define EGR_DAC_DECODE 1
+typedef struct egr_dac_segment {
+    int64_t keep_lo, keep_hi, win_lo, win_hi, in_lo, in_hi, out_lo, out_hi;
+} egr_dac_segment;
+int egr_dacseg_plan(const egr_dac_config* cfg, int kind, int64_t length, int64_t seg_frames, int64_t index, egr_dac_segment* seg,
+                         int64_t* n_segments);
+int egr_dacseg_encode(void* handle, const float* x, int rows, int64_t n, float* z, int* codes, float* ze_or_null, int64_t seg_frames,
+                             void* stream);
+int egr_dacseg_decode(void* handle, const float* z, int rows, int64_t frames, float* y, int64_t seg_frames, void* stream);
+size_t egr_dacseg_workspace_bytes(void* handle, int rows, int64_t seg_frames, int64_t n, int kind);
+size_t egr_dacseg_workspace_held(void* handle);
+int egr_dacseg_from_codes(void* handle, const int* codes, int rows, int64_t frames, float* z, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

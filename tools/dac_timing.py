@@ -3,10 +3,14 @@
 
   python tools/dac_timing.py [--seconds 60] [--repeats 20] [--out FILE.json]
   python tools/dac_timing.py --kernels          # host only: the contraction kernel the launcher picks per layer class
+  python tools/dac_timing.py --seg-frames 64,256,1024,F [--rows 1]      # the same input in segments (profiles/dac_segmented.md)
+  python tools/dac_timing.py --seconds 600 --rows 2 --auto               # the engine's own path choice under its workspace budget
 
 60 s of mono audio at 44.1 kHz through a seeded synthetic model of the 44 kHz default size (tests/dac_torch.py; no real checkpoint
 is needed for a time).  `encode` (encoder + quantiser) and `decode` are timed separately on tensors that are already on the device;
-every call follows a warm-up call and ends in a device synchronise; median / min / max of the repeats.  The flops are the dense
+every call follows a warm-up call and ends in a device synchronise; median / min / max of the repeats.  --seg-frames times
+egr_dacseg_encode / egr_dacseg_decode per segment length on a fresh handle each (so that the workspace held is that
+length's), and names the kernels of an interior window's layers; F stands for the file's frame count (one window).  The flops are the dense
 multiply-adds of the convolutions counted from the shapes.  These figures are reported, not gated.  Without a device the timing fails;
 it has no fallback.  Kernel shares come from a run of its own:
   rocprofv3 --kernel-trace --stats --output-format csv -d OUT -o dac -- python tools/dac_timing.py --repeats 1
@@ -76,12 +80,71 @@ def layer_kernels(cfg, native, dac_engine, rows, n):
     return res
 
 
+def timed(fn, repeats):
+    import torch
+    fn()                                                        # warm-up
+    ts = []
+    for _ in range(repeats):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        ts.append(1e3 * (time.perf_counter() - t0))
+    return {"median": statistics.median(ts), "min": min(ts), "max": max(ts)}
+
+
+def segmented(a, cfg, rows, n, arch):
+    """--seg-frames / --auto: a fresh handle per segment length; ms, workspace held, kernels of an interior window."""
+    import torch
+    from egregora_amd import dac_engine as E, dac_weights, native
+    import dac_torch as R
+    model = dac_weights.DacModel(cfg, R.synthetic_state_dict(cfg, 17))
+    x = R.test_signal(rows, n, 9).cuda()
+    F = E.lengths(cfg, n)[1]
+    hop = R.hop(cfg)
+    runs = []
+    todo = [None] if a.auto else [F if s.strip() == "F" else int(s) for s in a.seg_frames.split(",")]
+    for seg in todo:
+        eng = E.DacEngine(model, torch.cuda.current_device())
+        rec = {"seg_frames": seg, "rows": rows, "samples": n, "frames": F}
+        z, codes = eng.encode(x, seg_frames=seg)
+        rec["encode_ms"] = timed(lambda: eng.encode(x, seg_frames=seg), a.repeats)
+        rec["held_after_encode"] = eng.workspace_held()
+        rec["chosen_encode"] = eng.last_seg_frames if seg is None else seg
+        y = eng.decode(z, seg_frames=seg)
+        rec["decode_ms"] = timed(lambda: eng.decode(z, seg_frames=seg), a.repeats)
+        rec["held"] = eng.workspace_held()
+        rec["chosen_decode"] = eng.last_seg_frames if seg is None else seg
+        rec["one_pass_workspace"] = eng.workspace_bytes(rows, n)
+        rec["finite"] = bool(torch.isfinite(y).all())
+        s_eff = rec["chosen_encode"]
+        if s_eff is not None and s_eff < F:                     # an interior window's layers (encode's margins; decode's differ by 2 + 2 frames)
+            i = E.segment_count(cfg, E.ENCODE, n, s_eff) // 2
+            p = E.segment_plan(cfg, E.ENCODE, n, s_eff, i)
+            rec["window_frames"] = p.win_hi - p.win_lo
+            rec["layer_kernels"] = layer_kernels(cfg, native, E, rows, (p.win_hi - p.win_lo) * hop)
+        runs.append(rec)
+        print(f"seg_frames {seg}: encode {rec['encode_ms']['median']:.2f} ms ({rec['encode_ms']['min']:.2f} .. {rec['encode_ms']['max']:.2f}), "
+              f"decode {rec['decode_ms']['median']:.2f} ms ({rec['decode_ms']['min']:.2f} .. {rec['decode_ms']['max']:.2f}), held {rec['held'] / 2 ** 20:.1f} MiB "
+              f"(one pass {rec['one_pass_workspace'] / 2 ** 20:.1f} MiB), chose {rec['chosen_encode']} / {rec['chosen_decode']}, window {rec.get('window_frames')}")
+        del eng, z, codes, y
+        torch.cuda.empty_cache()
+    out = {"arch": arch, "device": torch.cuda.get_device_name(0), "seconds_of_audio": a.seconds, "repeats": a.repeats, "runs": runs}
+    print("RESULT " + json.dumps(out))
+    if a.out:
+        Path(a.out).parent.mkdir(parents=True, exist_ok=True)
+        Path(a.out).write_text(json.dumps(out, indent=1) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seconds", type=float, default=60.0)
     ap.add_argument("--repeats", type=int, default=20)
     ap.add_argument("--kernels", action="store_true")
     ap.add_argument("--out", default="")
+    ap.add_argument("--rows", type=int, default=1)
+    ap.add_argument("--seg-frames", default="", help="comma-separated segment lengths in frames; F = the whole file")
+    ap.add_argument("--auto", action="store_true", help="time DacEngine.encode / decode on the path they choose themselves")
     a = ap.parse_args()
     import torch
     from packload import load_pack
@@ -89,13 +152,15 @@ def main():
     from egregora_amd import dac_engine, dac_weights, native
     import dac_torch as R
     cfg = R.config("W")
-    rows, n = 1, int(round(a.seconds * cfg["sample_rate"]))
+    rows, n = a.rows, int(round(a.seconds * cfg["sample_rate"]))
     kern = layer_kernels(cfg, native, dac_engine, rows, n)
     if a.kernels:
         for k, v in kern.items():
             print(f"{k:40s} {v}")
         return
     arch = native.require_device()
+    if a.seg_frames or a.auto:
+        return segmented(a, cfg, rows, n, arch)
     eng = dac_engine.DacEngine(dac_weights.DacModel(cfg, R.synthetic_state_dict(cfg, 17)), torch.cuda.current_device())
     x = R.test_signal(rows, n, 9).cuda()
     z, codes = eng.encode(x)
