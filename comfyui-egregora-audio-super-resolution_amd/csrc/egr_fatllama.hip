@@ -745,36 +745,26 @@ __global__ __launch_bounds__(256) void k_finalize(float* __restrict__ out, long 
 
 using namespace egr;
 
-int fl_upload(egr_fatllama_plan* p, const std::vector<float2>& h, const cplx** d) {
+// A host table as a device buffer the plan owns; *d: its address.
+template <class T> static int upload_bytes(egr_fatllama_plan* p, const void* h, size_t bytes, const T** d) {
     void* ptr = nullptr;
-    EGR_HIP(hipMalloc(&ptr, h.size() * sizeof(float2)));
-    p->dev_allocs.push_back(ptr);
-    EGR_HIP(hipMemcpy(ptr, h.data(), h.size() * sizeof(float2), hipMemcpyHostToDevice));
-    *d = (const cplx*)ptr;
+    EGR_HIP(hipMalloc(&ptr, bytes));
+    p->tables.emplace_back();
+    p->tables.back().p = ptr;
+    EGR_HIP(hipMemcpy(ptr, h, bytes, hipMemcpyHostToDevice));
+    *d = (const T*)ptr;
     return EGR_OK;
 }
 
-int fl_upload_d(egr_fatllama_plan* p, int L, const dcplx** d) {
-    std::vector<double2> h;
-    make_twiddles_d(h, L, 1, L);
-    void* ptr = nullptr;
-    EGR_HIP(hipMalloc(&ptr, h.size() * sizeof(double2)));
-    p->dev_allocs.push_back(ptr);
-    EGR_HIP(hipMemcpy(ptr, h.data(), h.size() * sizeof(double2), hipMemcpyHostToDevice));
-    *d = (const dcplx*)ptr;
-    return EGR_OK;
-}
+int fl_upload(egr_fatllama_plan* p, const std::vector<float2>& h, const cplx** d) { return upload_bytes(p, h.data(), h.size() * sizeof(float2), d); }
+
+int fl_upload_d(egr_fatllama_plan* p, int L, const dcplx** d) { return fl_upload_dtab(p, L, 1, L, d); }
 
 // exp(-2 pi i j num / den), j < count, as a double-precision device table
 int fl_upload_dtab(egr_fatllama_plan* p, int64_t count, int64_t num, int64_t den, const dcplx** d) {
     std::vector<double2> h;
     make_twiddles_d(h, count, num, den);
-    void* ptr = nullptr;
-    EGR_HIP(hipMalloc(&ptr, h.size() * sizeof(double2)));
-    p->dev_allocs.push_back(ptr);
-    EGR_HIP(hipMemcpy(ptr, h.data(), h.size() * sizeof(double2), hipMemcpyHostToDevice));
-    *d = (const dcplx*)ptr;
-    return EGR_OK;
+    return upload_bytes(p, h.data(), h.size() * sizeof(double2), d);
 }
 
 // butterfly-ordered stage tables of a compile-time schedule (R0, R1, R2; R2 = 1: two stages): for stage s >= 1 with
@@ -821,7 +811,7 @@ static void fill_info(const FlSplit& sp, int64_t info[EGR_FL_INFO_LEN]) {
 }
 
 static bool bluestein_length(int64_t want, FlSplit* sp_out);
-static bool pz_length(int64_t D, FlSplit* sp_out);
+static bool pz_length(int64_t D, const FlSwitches& sw, FlSplit* sp_out);
 // paired chirp-z kind for N real samples: 1 = even/odd packing (N even, D = N / 2), 2 = channel pairs (N odd, D = N)
 static inline int pz_kind_for(int64_t N) { return (N & 1) ? 2 : 1; }
 // LDS of k_rowconv: two rows, stages in place
@@ -838,6 +828,30 @@ static int blue_threads() {
     return t;
 }
 
+static FlSwitches fl_read_switches() {
+    auto num = [](const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; };
+    FlSwitches s;
+    const int streams = num("EGR_FL_STREAMS", s.streams), threads = num("EGR_FL_THREADS", s.threads);
+    if (streams == 1 || streams == 2) s.streams = streams;
+    if (threads == 256 || threads == 512 || threads == 1024) s.threads = threads;
+    s.graph = num("EGR_FL_GRAPH", 1) != 0;
+    s.sched = num("EGR_FL_SCHED", 1) != 0;
+    s.wl = num("EGR_FL_WL", 1) != 0;
+    s.twpow = num("EGR_FL_TWPOW", 1);
+    s.m1 = num("EGR_FL_M1", 0);
+    s.tc = num("EGR_FL_TC", 0);
+    s.legacy_chirpz = num("EGR_FL_LEGACY_CHIRPZ", 0) != 0;
+    s.pz_sched = num("EGR_PZ_SCHED", 1) != 0;
+    s.pz_colwl = num("EGR_PZ_COLWL", 1) != 0;
+    s.pz_pairwl = num("EGR_PZ_PAIRWL", 1) != 0;
+    s.pz_rowf = num("EGR_PZ_ROWF", 1) != 0;
+    if (const char* e = getenv("EGR_PZ_SPLIT")) {
+        int L = 0, nc = 0;
+        if (sscanf(e, "%d,%d", &L, &nc) == 2) { s.pz_split_L = L; s.pz_split_nc = nc; }
+    }
+    return s;
+}
+
 static const char* kUnsupported =
     "length %lld unsupported: needs even N whose half factors into 2 or 3 lengths (outer columns <= 2048, inner columns <= 1024, row <= 4096) with "
     "prime factors <= 13";
@@ -852,7 +866,7 @@ extern "C" int egr_fatllama_plan_query(int64_t n_in, int factor, int m1_hint, in
     info[2] = N / 2;
     if (!sp.ok) {
         const int kind = pz_kind_for(N);
-        if (N >= 2 && pz_length(kind == 1 ? N / 2 : N, &sp)) {      // paired chirp-z over P = sp.M complex points per state
+        if (N >= 2 && pz_length(kind == 1 ? N / 2 : N, fl_read_switches(), &sp)) {      // paired chirp-z over P = sp.M complex points per state
             fill_info(sp, info);
             info[0] = 2;
             info[2] = sp.M;
@@ -879,50 +893,108 @@ extern "C" int egr_fatllama_plan_destroy(egr_fatllama_plan* p) {
     if (!p) return EGR_OK;
     hipDeviceSynchronize();          // nothing of the plan may still be in flight when its graph, streams and buffers go
     fl_drop_graph(p);
-    pz_destroy(p);
-    for (void* q : p->dev_allocs) hipFree(q);
-    hipFree(p->d_work); hipFree(p->d_peaks); hipFree(p->d_bhat); hipFree(p->d_max2);
-    if (p->cap) hipStreamDestroy(p->cap);
-    if (p->side && p->side_owned) hipStreamDestroy(p->side);
-    if (p->ev_fork) hipEventDestroy(p->ev_fork);
-    if (p->ev_join) hipEventDestroy(p->ev_join);
-    for (auto e : p->ev) hipEventDestroy(e);
     delete p;
     return EGR_OK;
 }
 
-static int build_plan(egr_fatllama_plan** out, int64_t n_in, int channels, int factor, const FlSplit& sp,
+// ---- the launchers of the three kernel families (FlRowPass / FlColPass, egr_fatllama_int.h) ----
+static void row_launch(const FlRowPass& e, const egr_fatllama_plan* p, const RowP& R, cplx* work, int nch, hipStream_t st) {
+    hipLaunchKernelGGL(e.k, dim3(R.R / 2 + 1, nch), dim3(e.threads), e.lds, st, R, (long long)p->sp.M, work);
+}
+static void row_launch_wl(const FlRowPass& e, const egr_fatllama_plan* p, const RowP& R, cplx* work, int nch, hipStream_t st) {
+    hipLaunchKernelGGL(e.k_wl, dim3(R.R / 2 + 1, nch), dim3(e.threads), e.lds, st, R, p->wl_rt, (long long)p->sp.M, work);
+}
+static dim3 col_grid(const ColP& A, int nch) { return dim3(8 * A.tiles_per_xcd, nch * A.nplanes); }
+static void col_launch(const FlColPass& e, const egr_fatllama_plan* p, const ColP& A, const FlColIO& io, cplx* work, int nch, hipStream_t st) {
+    hipLaunchKernelGGL(e.k, col_grid(A, nch), dim3(e.threads), e.lds, st, A, (long long)p->sp.M, (long long)p->sp.N, io.thr, work, io.out, io.peak, io.thr_rel);
+}
+static void col_launch_wl(const FlColPass& e, const egr_fatllama_plan* p, const ColP& A, const FlColIO&, cplx* work, int nch, hipStream_t st) {
+    hipLaunchKernelGGL(e.k_wl, col_grid(A, nch), dim3(e.threads), e.lds, st, A, p->wl_ct, (long long)p->sp.M, work);
+}
+static void inner_launch_wl(const FlColPass& e, const egr_fatllama_plan* p, const ColP& B, const FlColIO&, cplx* work, int nch, hipStream_t st) {
+    hipLaunchKernelGGL(e.k_wlb, col_grid(B, nch), dim3(e.threads), e.lds, st, B, p->wl_it, (long long)p->sp.M, work);
+}
+static FlRowPass row_pass(FlRowFn k, int threads, size_t lds) { FlRowPass e{}; e.launch = row_launch; e.k = k; e.threads = threads; e.lds = lds; return e; }
+static FlRowPass row_pass_wl(WlRowFn k, const WlRowEntry& w) { FlRowPass e{}; e.launch = row_launch_wl; e.k_wl = k; e.threads = w.threads; e.lds = EGR_LDS(w.lds); return e; }
+static FlColPass col_pass(FlColFn k, int threads, size_t lds, const ColP* geo) {
+    FlColPass e{}; e.launch = col_launch; e.k = k; e.threads = threads; e.lds = lds; e.geo = geo; return e;
+}
+
+// The one place that knows which kernel serves which pass of a plan.  `families`: the compile-time schedules and the two-barrier
+// kernels serve the passes whose tables build_plan uploaded (the plan's lengths have an instantiation and EGR_FL_SCHED / EGR_FL_WL
+// allow it); without them every pass runs the run-time schedule at `threads` threads.
+static void fl_select_passes(const egr_fatllama_plan* p, int threads, bool families, FlPasses* ps) {
+    const FlSplit& sp = p->sp;
+    const int L = p->row.L;
+    const size_t lc = EGR_LDS(sp.lds_col), lb = EGR_LDS(sp.lds_colb), lr = EGR_LDS(sp.lds_row);
+    // the in-place schedules need one thread per butterfly (288 / 512 row, 200 column butterflies per stage): 512 threads; the
+    // column one serves two-level plans only
+    const bool sched_ok = families && threads == 512;
+    // the two-barrier row kernels: default hook, k_row_wl<.., 1> (level from the iteration's maximum and / or soft shrink), maximum only
+    if (const WlRowEntry* w = families && p->wl_rt.t1 ? wl_find(kWlRows, L) : nullptr) {
+        ps->row[FL_ROW_DEFAULT] = row_pass_wl(w->fn, *w);
+        ps->row[FL_ROW_VARIANT] = row_pass_wl(w->fn_variant, *w);
+        ps->row[FL_ROW_MAX] = row_pass_wl(w->fn_max, *w);
+    } else {
+        const bool rs1 = sched_ok && p->row.stw;
+        const size_t lds = rs1 ? row_sched_lds(L) : lr;
+        ps->row[FL_ROW_DEFAULT] = ps->row[FL_ROW_VARIANT] = row_pass(rs1 ? k_row<false, 1> : k_row<false>, threads, lds);
+        ps->row[FL_ROW_MAX] = row_pass(rs1 ? k_row<true, 1> : k_row<true>, threads, lds);
+    }
+    const ColP* A = &p->colA;
+    const bool cs2 = sched_ok && A->stw && sp.levels == 2;          // (at the scheduled column kernels' own workgroup size)
+    const FlColFn outer[2][3] = {{k_col<0>, k_col<1>, k_col<2>}, {k_col<0, 2>, k_col<1, 2>, k_col<2, 2>}};      // [cs2][opening, middle, closing]
+    for (int m = 0; m < 3; ++m) ps->col[m] = col_pass(outer[cs2][m], cs2 ? EGR_FL_COL_THREADS : threads, cs2 ? col_sched_lds(p) : lc, A);
+    if (const WlColEntry* w = families && p->wl_ct.t3 ? wl_find(kWlCols, A->L) : nullptr) {          // the middle pass only
+        FlColPass& e = ps->col[FL_COL_MID];
+        e.launch = col_launch_wl; e.k_wl = w->fn; e.threads = w->threads; e.lds = EGR_LDS(w->lds); e.geo = &p->wl_colA;
+    }
+    ps->inner[FL_INNER_FWD] = col_pass(k_col<4>, threads, lb, &p->colB);
+    ps->inner[FL_INNER_INV] = col_pass(k_col<3>, threads, lb, &p->colB);
+    if (const WlInnerEntry* w = families && p->wl_it ? wl_find(kWlInner, sp.M2) : nullptr)
+        for (int fwd = 0; fwd < 2; ++fwd) {
+            FlColPass& e = ps->inner[fwd];
+            e.launch = inner_launch_wl; e.k_wlb = fwd ? w->fwd : w->inv; e.threads = w->threads; e.lds = EGR_LDS(w->lds); e.geo = &p->wl_colB;
+        }
+}
+
+// `c` with the tile geometry of a kernel that takes `tc` columns per workgroup by thread index (a ragged last tile is fine)
+static ColP retiled(ColP c, int tc) {
+    c.TC = tc; c.TClog2 = 0; c.ntiles = ceil_div(c.ncols, tc); c.tiles_per_xcd = ceil_div(c.ntiles, 8);
+    return c;
+}
+
+// the kernels of this unit whose dynamic LDS may exceed the 64 KiB default
+static const void* const kBigLdsKernels[] = {
+    (const void*)k_col<0>, (const void*)k_col<1>, (const void*)k_col<2>, (const void*)k_col<3>, (const void*)k_col<4>, (const void*)k_col<5>,
+    (const void*)k_row<false>, (const void*)k_row<true>, (const void*)k_row<false, 1>, (const void*)k_row<true, 1>,
+    (const void*)k_col<0, 2>, (const void*)k_col<1, 2>, (const void*)k_col<2, 2>,
+    (const void*)k_colz<0, 0>, (const void*)k_colz<1, 1>, (const void*)k_colz<1, 2>, (const void*)k_colz<3, 1>, (const void*)k_colz<2, 0>,
+    (const void*)k_rowconv<true>, (const void*)k_rowconv<false>,
+};
+
+static int build_plan(egr_fatllama_plan** out, const FlSwitches& sw, int64_t n_in, int channels, int factor, const FlSplit& sp,
                       int64_t bluestein_n = 0, int pz_kind = 0, int64_t n_out = 0) {
-    egr_fatllama_plan* p = new egr_fatllama_plan();
-    p->n_in = n_in; p->C = channels; p->factor = factor; p->sp = sp; p->profiling = false;
+    // a failed build goes the way of every plan: egr_fatllama_plan_destroy waits for the device before anything is freed
+    std::unique_ptr<egr_fatllama_plan, int (*)(egr_fatllama_plan*)> owner(new egr_fatllama_plan(), egr_fatllama_plan_destroy);
+    egr_fatllama_plan* p = owner.get();
+    p->n_in = n_in; p->C = channels; p->factor = factor; p->sp = sp;
     p->n_out = n_out > 0 ? n_out : n_in * factor;
     p->bluestein = bluestein_n > 0;
-    p->pz_kind = pz_kind; p->pz = nullptr;
-    p->nstreams = 2;
-    if (const char* e = getenv("EGR_FL_STREAMS")) { const int t = atoi(e); if (t == 1 || t == 2) p->nstreams = t; }
-    p->side = nullptr; p->side_owned = 0; p->ev_fork = nullptr; p->ev_join = nullptr;
-    p->cap = nullptr; p->gexec = nullptr; p->g_thr = 0.f; p->g_groups = 0; p->g_hook_kind = 0;
-    p->use_graph = !(getenv("EGR_FL_GRAPH") && atoi(getenv("EGR_FL_GRAPH")) == 0);
-    p->threads = 512;    // 16 waves per CU at 2 workgroups per CU: measured 1.4x over 256
-    if (const char* e = getenv("EGR_FL_THREADS")) { const int t = atoi(e); if (t == 256 || t == 512 || t == 1024) p->threads = t; }
-    p->d_bhat = nullptr;
-    p->d_work = nullptr;
-    p->d_peaks = nullptr;
-    p->d_max2 = nullptr; p->max2_cap = 0;
+    p->pz_kind = pz_kind;
+    p->nstreams = sw.streams;
+    p->use_graph = sw.graph;
     hipGetDevice(&p->device);
     const int64_t M = sp.M, N = sp.N;
-    int rc = EGR_OK;
     std::vector<float2> h;
-    auto fail = [&](int code) { egr_fatllama_plan_destroy(p); return code; };
-    memset(&p->colA, 0, sizeof(ColP)); memset(&p->colB, 0, sizeof(ColP)); memset(&p->row, 0, sizeof(RowP));
     // ---- outer column pass A: L = M1, columns = M / M1 ----
     ColP& a = p->colA;
     a.f = sp.f1; a.L = sp.M1; a.ncols = (int)(M / sp.M1); a.nplanes = 1;
     a.TC = sp.TC; a.TClog2 = sp.TClog2; a.ntiles = ceil_div(a.ncols, a.TC); a.tiles_per_xcd = ceil_div(a.ntiles, 8);
     make_twiddles(h, sp.M1, 1, sp.M1);
-    if ((rc = fl_upload(p, h, &a.tw))) return fail(rc);
-    if ((rc = fl_upload_d(p, sp.M1, &a.twd))) return fail(rc);
-    if ((rc = fl_make_tw2(p, M, &a.big))) return fail(rc);
+    EGR_TRY(fl_upload(p, h, &a.tw));
+    EGR_TRY(fl_upload_d(p, sp.M1, &a.twd));
+    EGR_TRY(fl_make_tw2(p, M, &a.big));
     // ---- inner column pass B (3 levels): per k1 plane, L = M2, columns = M3 ----
     RowP& r = p->row;
     if (sp.levels == 3) {
@@ -930,38 +1002,32 @@ static int build_plan(egr_fatllama_plan** out, int64_t n_in, int channels, int f
         b.f = sp.f2; b.L = sp.M2; b.ncols = sp.M3; b.nplanes = sp.M1;
         b.TC = sp.TCb; b.TClog2 = sp.TCblog2; b.ntiles = ceil_div(b.ncols, b.TC); b.tiles_per_xcd = ceil_div(b.ntiles, 8);
         make_twiddles(h, sp.M2, 1, sp.M2);
-        if ((rc = fl_upload(p, h, &b.tw))) return fail(rc);
-        if ((rc = fl_upload_d(p, sp.M2, &b.twd))) return fail(rc);
-        if ((rc = fl_make_tw2(p, (int64_t)sp.M2 * sp.M3, &b.big))) return fail(rc);
+        EGR_TRY(fl_upload(p, h, &b.tw));
+        EGR_TRY(fl_upload_d(p, sp.M2, &b.twd));
+        EGR_TRY(fl_make_tw2(p, (int64_t)sp.M2 * sp.M3, &b.big));
         r.f = sp.f3; r.L = sp.M3; r.R = sp.M1 * sp.M2; r.Ma = sp.M1; r.Mb = sp.M2;
     } else {
         r.f = sp.f2; r.L = sp.M2; r.R = sp.M1; r.Ma = sp.M1; r.Mb = 1;
     }
     make_twiddles(h, r.L, 1, r.L);
-    if ((rc = fl_upload(p, h, &r.tw))) return fail(rc);
-    if ((rc = fl_upload_d(p, r.L, &r.twd))) return fail(rc);
-    if ((rc = fl_upload_dtab(p, r.L, 1, 2 * (int64_t)r.L, &r.wk))) return fail(rc);
+    EGR_TRY(fl_upload(p, h, &r.tw));
+    EGR_TRY(fl_upload_d(p, r.L, &r.twd));
+    EGR_TRY(fl_upload_dtab(p, r.L, 1, 2 * (int64_t)r.L, &r.wk));
     {   // W_N^o for o < R, as hi/lo tables over the range [0, R)
         int sh = 0;
         while ((1LL << (2 * sh)) < r.R) ++sh;
-        if ((rc = fl_upload_dtab(p, ((int64_t)r.R >> sh) + 1, 1LL << sh, N, &r.wo.hi))) return fail(rc);
-        if ((rc = fl_upload_dtab(p, 1LL << sh, 1, N, &r.wo.lo))) return fail(rc);
+        EGR_TRY(fl_upload_dtab(p, ((int64_t)r.R >> sh) + 1, 1LL << sh, N, &r.wo.hi));
+        EGR_TRY(fl_upload_dtab(p, 1LL << sh, 1, N, &r.wo.lo));
         r.wo.sh = sh;
     }
     r.inv_M = (float)(1.0 / (double)M);
     r.inv_M_d = 1.0 / (double)M;
-    // compile-time schedules for the hot factor lengths (EGR_FL_SCHED=0: always the run-time schedule)
-    p->row_sched = p->col_sched = 0;
-    {
-        const bool off = getenv("EGR_FL_SCHED") && atoi(getenv("EGR_FL_SCHED")) == 0;
-        if (!off && !p->bluestein && r.L == 2304) { if ((rc = fl_upload_sched_tables(p, {EGR_FL_ROW_RADICES}, &r.stw))) return fail(rc); p->row_sched = 1; }
-        if (!off && !p->bluestein && a.L == 625 && a.TC >= 2 && a.TC <= EGR_FL_COL_TC) { if ((rc = fl_upload_sched_tables(p, {EGR_FL_COL_RADICES}, &a.stw))) return fail(rc); p->col_sched = 2; }
-    }
-    // the two-barrier loop kernels (egr_fatllama_wl.h) for rows of 2304 / outer columns of 625 points; EGR_FL_WL=0 keeps the
-    // stage-by-stage kernels
-    p->wl_row = p->wl_col = 0;
-    {
-        const bool off = getenv("EGR_FL_WL") && atoi(getenv("EGR_FL_WL")) == 0;
+    // stage tables of the compile-time schedules for the hot factor lengths (EGR_FL_SCHED=0: always the run-time schedule)
+    if (sw.sched && !p->bluestein && r.L == 2304) EGR_TRY(fl_upload_sched_tables(p, {EGR_FL_ROW_RADICES}, &r.stw));
+    if (sw.sched && !p->bluestein && a.L == 625 && a.TC >= 2 && a.TC <= EGR_FL_COL_TC) EGR_TRY(fl_upload_sched_tables(p, {EGR_FL_COL_RADICES}, &a.stw));
+    // tables of the two-barrier loop kernels (egr_fatllama_wl.h) where the row / outer column / inner column length has an instantiation;
+    // EGR_FL_WL=0 keeps the stage-by-stage kernels
+    if (sw.wl && !p->bluestein) {
         auto table = [&](int n, int m, int T, const cplx** d, const cplx** dlo) {          // [n][m]: W_T^(i j), and its low parts
             std::vector<float2> t, tl;
             t.resize((size_t)n * m); tl.resize((size_t)n * m);
@@ -977,108 +1043,61 @@ static int build_plan(egr_fatllama_plan** out, int64_t n_in, int channels, int f
             const int rc2 = fl_upload(p, t, d);
             return rc2 ? rc2 : fl_upload(p, tl, dlo);
         };
-        p->wl_row_entry = nullptr;
-        if (!off && !p->bluestein)
-            for (const WlRowEntry& e : kWlRows)
-                if (e.L == r.L) {
-                    const int qq = e.q * e.q;
-                    if ((rc = table(qq, e.n1, e.L, &p->wl_rt.t1, &p->wl_rt.t1l))) return fail(rc);
-                    if ((rc = table(e.q, e.q, qq, &p->wl_rt.t2, &p->wl_rt.t2l))) return fail(rc);
-                    if ((rc = fl_upload_dtab(p, e.q, 1, qq, &p->wl_rt.t2d))) return fail(rc);
-                    const long double ang = -3.14159265358979323846264338327950288L / (long double)e.q;         // W_(2Q)
-                    p->wl_rt.hook_step = make_double2((double)cosl(ang), (double)sinl(ang));
-                    p->wl_row_entry = &e;
-                    p->wl_row = 1;
-                }
-        if (!off && !p->bluestein && wl_col_radix(a.L)) {
-            const int r = wl_col_radix(a.L);
-            if ((rc = table(r, r, r * r, &p->wl_ct.t3, &p->wl_ct.t3l))) return fail(rc);
-            p->wl_col = 1;
+        if (const WlRowEntry* e = wl_find(kWlRows, r.L)) {
+            const int qq = e->q * e->q;
+            EGR_TRY(table(qq, e->n1, e->L, &p->wl_rt.t1, &p->wl_rt.t1l));
+            EGR_TRY(table(e->q, e->q, qq, &p->wl_rt.t2, &p->wl_rt.t2l));
+            EGR_TRY(fl_upload_dtab(p, e->q, 1, qq, &p->wl_rt.t2d));
+            const long double ang = -3.14159265358979323846264338327950288L / (long double)e->q;         // W_(2Q)
+            p->wl_rt.hook_step = make_double2((double)cosl(ang), (double)sinl(ang));
         }
-        p->wl_inner = 0; p->wl_it = nullptr;
-        if (!off && !p->bluestein && sp.levels == 3 && wl_inner_supported(sp.M2)) {
-            int la, lb, tcw;
-            wl_inner_geometry(sp.M2, &la, &lb, &tcw);
+        if (const WlColEntry* e = wl_find(kWlCols, a.L)) {
+            EGR_TRY(table(e->r, e->r, e->L, &p->wl_ct.t3, &p->wl_ct.t3l));
+            p->wl_colA = retiled(a, e->tc);
+        }
+        if (const WlInnerEntry* e = sp.levels == 3 ? wl_find(kWlInner, sp.M2) : nullptr) {
             const cplx* itl = nullptr;
-            if ((rc = table(lb, la, sp.M2, &p->wl_it, &itl))) return fail(rc);
-            p->wl_colB = p->colB;
-            p->wl_colB.TC = tcw; p->wl_colB.TClog2 = 0;
-            p->wl_colB.ntiles = ceil_div(p->colB.ncols, tcw); p->wl_colB.tiles_per_xcd = ceil_div(p->wl_colB.ntiles, 8);
-            p->wl_inner = 1;
+            EGR_TRY(table(e->lb, e->la, sp.M2, &p->wl_it, &itl));
+            p->wl_colB = retiled(p->colB, e->tcw);
         }
     }
     const int nstates = pz_kind == 2 ? (channels + 1) / 2 : channels;      // a paired chirp-z state of kind 2 carries two channels
-    if (hipMalloc((void**)&p->d_work, (size_t)nstates * M * sizeof(float2)) != hipSuccess ||
-        hipMalloc((void**)&p->d_peaks, 3 * channels * sizeof(unsigned)) != hipSuccess) {
-        set_error("hipMalloc of the %lld-byte loop state failed", (long long)(channels * M * 8));
-        return fail(EGR_ERR_ALLOC);
-    }
+    EGR_CHECK(p->d_work.alloc((size_t)nstates * M * sizeof(float2)) && p->d_peaks.alloc(3 * channels * sizeof(unsigned)), EGR_ERR_ALLOC,
+              "hipMalloc of the %lld-byte loop state failed", (long long)(channels * M * 8));
     // dynamic LDS above the 64 KiB default needs an explicit opt-in per kernel.  The attribute is a process-wide cap per kernel, so it
     // is always raised to the CU's 160 KiB (a later, smaller plan must not lower it under an earlier plan's needs); what a plan
     // actually requests is checked here.
-    const int lc = EGR_LDS_MAX, lrow = EGR_LDS_MAX;
-    if (!pz_kind && (std::max(sp.lds_col, sp.lds_colb) > (size_t)EGR_LDS_MAX || sp.lds_row > (size_t)EGR_LDS_MAX)) {
-        set_error("plan needs %zu / %zu bytes of LDS per workgroup (limit %d)", std::max(sp.lds_col, sp.lds_colb), sp.lds_row, EGR_LDS_MAX);
-        return fail(EGR_ERR_UNSUPPORTED);
+    EGR_CHECK(pz_kind || (std::max(sp.lds_col, sp.lds_colb) <= (size_t)EGR_LDS_MAX && sp.lds_row <= (size_t)EGR_LDS_MAX), EGR_ERR_UNSUPPORTED,
+              "plan needs %zu / %zu bytes of LDS per workgroup (limit %d)", std::max(sp.lds_col, sp.lds_colb), sp.lds_row, EGR_LDS_MAX);
+    for (const void* k : kBigLdsKernels) {
+        const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, EGR_LDS_MAX);
+        EGR_CHECK(e == hipSuccess, EGR_ERR_HIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) -> %s", hipGetErrorString(e));
     }
-    hipError_t e = hipSuccess;
-    e = hipFuncSetAttribute((const void*)k_col<0>, hipFuncAttributeMaxDynamicSharedMemorySize, lc);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_col<1>, hipFuncAttributeMaxDynamicSharedMemorySize, lc);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_col<2>, hipFuncAttributeMaxDynamicSharedMemorySize, lc);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_col<3>, hipFuncAttributeMaxDynamicSharedMemorySize, lc);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_col<4>, hipFuncAttributeMaxDynamicSharedMemorySize, lc);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_col<5>, hipFuncAttributeMaxDynamicSharedMemorySize, lc);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_row<false>, hipFuncAttributeMaxDynamicSharedMemorySize, lrow);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_row<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lrow);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_row<false, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, lrow);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_row<true, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, lrow);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_col<0, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, lc);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_col<1, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, lc);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_col<2, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, lc);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_colz<0, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, lc);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_colz<1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, lc);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_colz<1, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, lc);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_colz<3, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, lc);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_colz<2, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, lc);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_rowconv<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lrow);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)k_rowconv<false>, hipFuncAttributeMaxDynamicSharedMemorySize, lrow);
-    if (e != hipSuccess) {
-        set_error("hipFuncSetAttribute(MaxDynamicSharedMemorySize) -> %s", hipGetErrorString(e));
-        return fail(EGR_ERR_HIP);
-    }
+    fl_select_passes(p, 256, false, &p->single);
+    p->single.col[FL_COL_CLOSE].k = k_col<5>;          // a single pass ends plain: out = d, not y + d
     if (p->pz_kind) {
-        if ((rc = pz_build(p, p->pz_kind))) return fail(rc);
+        EGR_TRY(pz_build(p, p->pz_kind, sw));
     } else if (p->bluestein) {
         // chirp tables for W_(2N)^r and bhat = FFT_P(b)/P computed once with the plan's own passes
         ChirpP& c = p->chirp;
         c.N = (unsigned long long)bluestein_n;
         c.inv_N = (float)(1.0 / (double)bluestein_n);
         c.inv_2N_d = 1.0 / (2.0 * (double)bluestein_n);
-        if ((rc = fl_make_tw2(p, 2 * bluestein_n, &c.w))) return fail(rc);
-        if (hipMalloc((void**)&p->d_bhat, (size_t)M * sizeof(float2)) != hipSuccess) {
-            set_error("hipMalloc of the %lld-byte chirp spectrum failed", (long long)(M * 8));
-            return fail(EGR_ERR_ALLOC);
-        }
-        const dim3 blk(256);
-        hipLaunchKernelGGL(k_chirp_b, dim3(2048), blk, 0, 0, c, (long long)M, p->d_bhat);
-        hipLaunchKernelGGL(k_col<4>, dim3(8 * a.tiles_per_xcd, 1), blk, EGR_LDS(sp.lds_col), 0, a, (long long)M, (long long)N, 0.f, p->d_bhat,
-                           (float*)nullptr, (unsigned*)nullptr);
-        if (sp.levels == 3)
-            hipLaunchKernelGGL(k_col<4>, dim3(8 * p->colB.tiles_per_xcd, p->colB.nplanes), blk, EGR_LDS(sp.lds_colb), 0, p->colB,
-                               (long long)M, (long long)N, 0.f, p->d_bhat, (float*)nullptr, (unsigned*)nullptr);
+        EGR_TRY(fl_make_tw2(p, 2 * bluestein_n, &c.w));
+        EGR_CHECK(p->d_bhat.alloc((size_t)M * sizeof(float2)), EGR_ERR_ALLOC, "hipMalloc of the %lld-byte chirp spectrum failed", (long long)(M * 8));
+        cplx* bhat = p->d_bhat.as<cplx>();
+        const FlColIO none{0.f, nullptr, nullptr, nullptr};
+        hipLaunchKernelGGL(k_chirp_b, dim3(2048), dim3(256), 0, 0, c, (long long)M, bhat);
+        col_pass(k_col<4>, 256, EGR_LDS(sp.lds_col), &a)(p, none, bhat, 1, 0);          // the forward pass over the OUTER columns too
+        if (sp.levels == 3) p->single.inner[FL_INNER_FWD](p, none, bhat, 1, 0);
         hipLaunchKernelGGL(k_rowconv<false>, dim3((r.R + EGR_FL_CONV_ROWS - 1) / EGR_FL_CONV_ROWS, 1), dim3(EGR_FL_CONV_THREADS), rowconv_lds(r.L), 0, r.f, r.L, r.R, r.tw,
-                           (const cplx*)nullptr, (float)(1.0 / (double)M), (long long)M, p->d_bhat);
-        if (hipDeviceSynchronize() != hipSuccess || hipGetLastError() != hipSuccess) {
-            set_error("building the Bluestein chirp spectrum failed");
-            return fail(EGR_ERR_HIP);
-        }
+                           (const cplx*)nullptr, (float)(1.0 / (double)M), (long long)M, bhat);
+        EGR_CHECK(hipDeviceSynchronize() == hipSuccess && hipGetLastError() == hipSuccess, EGR_ERR_HIP, "building the Bluestein chirp spectrum failed");
     }
-    {   // stage twiddles W^2..W^(r-1) by multiplication from one loaded W^1 (default) or all loaded (EGR_FL_TWPOW=0)
-        int v = 1;
-        if (const char* e2 = getenv("EGR_FL_TWPOW")) v = atoi(e2);
-        p->colA.f.tw_pow = v; p->colB.f.tw_pow = v; p->row.f.tw_pow = v;
-    }
-    *out = p;
+    // stage twiddles W^2..W^(r-1) by multiplication from one loaded W^1 (default) or all loaded (EGR_FL_TWPOW=0)
+    p->colA.f.tw_pow = p->wl_colA.f.tw_pow = p->colB.f.tw_pow = p->row.f.tw_pow = sw.twpow;
+    fl_select_passes(p, sw.threads, true, &p->loop);
+    *out = owner.release();
     return EGR_OK;
 }
 
@@ -1111,12 +1130,12 @@ static bool bluestein_length(int64_t want, FlSplit* sp_out) {
 // nc % 8 == 0 (4-column tiles in mirrored pairs), rows of at most 4096 points (one row per workgroup, stages in place), columns
 // of at most 2048; smallest cost, where a plan whose column-tile pair does not fit one in-place call (L > 1024) and a third level
 // pay their extra barriers / passes.
-static bool pz_length(int64_t D, FlSplit* sp_out) {
+static bool pz_length(int64_t D, const FlSwitches& sw, FlSplit* sp_out) {
     const int64_t want = 2 * D - 1;
     const int64_t limit = want < 64 ? 4096 : want + want / 2;
-    if (const char* e = getenv("EGR_PZ_SPLIT")) {            // dev: "L,nc" forces the factorisation
-        int L = 0, nc = 0;
-        if (sscanf(e, "%d,%d", &L, &nc) == 2 && (int64_t)L * nc >= want && nc % 8 == 0) {
+    {   // dev: EGR_PZ_SPLIT="L,nc" forces the factorisation (unset: 0 x 0, shorter than any `want`)
+        const int L = sw.pz_split_L, nc = sw.pz_split_nc;
+        if ((int64_t)L * nc >= want && nc % 8 == 0) {
             FlSplit sp = plan_split_explicit(2 * (int64_t)L * nc, L, nc, 1, 4);
             if (sp.ok && sp.TC == 4) { *sp_out = sp; return true; }
         }
@@ -1146,7 +1165,7 @@ static bool pz_length(int64_t D, FlSplit* sp_out) {
             if (v % L) continue;
             const int64_t nc = v / L;
             if (nc % 8) continue;
-            const bool sched = nc <= 16384 && pz_sched_has((int)L, (int)nc);       // compile-time schedules on both passes
+            const bool sched = nc <= 16384 && sw.pz_sched && pz_sched_has((int)L, (int)nc);       // compile-time schedules on both passes
             if (nc > 4096 && !sched) continue;
             FftDesc f1, f2;
             if (!make_schedule((int)L, &f1) || !make_schedule((int)nc, &f2)) continue;
@@ -1174,21 +1193,21 @@ static bool pz_length(int64_t D, FlSplit* sp_out) {
 }
 
 static int create_for_length(egr_fatllama_plan** out, int64_t n_in, int channels, int factor, int64_t N, int m1_hint, int tc_hint) {
-    if (m1_hint <= 0) { if (const char* e = getenv("EGR_FL_M1")) m1_hint = atoi(e); }
-    if (tc_hint <= 0) { if (const char* e = getenv("EGR_FL_TC")) tc_hint = atoi(e); }
+    const FlSwitches sw = fl_read_switches();
+    if (m1_hint <= 0) m1_hint = sw.m1;
+    if (tc_hint <= 0) tc_hint = sw.tc;
     FlSplit sp = plan_split(N, m1_hint, tc_hint);
     // the 625-point column schedule is instantiated for one tile width
     if (tc_hint <= 0 && sp.ok && sp.levels == 2 && sp.M1 == 625 && sp.TC != EGR_FL_COL_TC) sp = plan_split(N, m1_hint, EGR_FL_COL_TC);
     if (!sp.ok) {
         const int kind = pz_kind_for(N);
         const int64_t D = kind == 1 ? N / 2 : N;
-        if (N >= 2 && !(getenv("EGR_FL_LEGACY_CHIRPZ") && atoi(getenv("EGR_FL_LEGACY_CHIRPZ"))) && pz_length(D, &sp))
-            return build_plan(out, n_in, channels, factor, sp, D, kind, N);
-        if (N >= 2 && bluestein_length(2 * N - 1, &sp)) return build_plan(out, n_in, channels, factor, sp, N, 0, N);
+        if (N >= 2 && !sw.legacy_chirpz && pz_length(D, sw, &sp)) return build_plan(out, sw, n_in, channels, factor, sp, D, kind, N);
+        if (N >= 2 && bluestein_length(2 * N - 1, &sp)) return build_plan(out, sw, n_in, channels, factor, sp, N, 0, N);
         set_error(kUnsupported, (long long)N);
         return EGR_ERR_UNSUPPORTED;
     }
-    return build_plan(out, n_in, channels, factor, sp, 0, 0, N);
+    return build_plan(out, sw, n_in, channels, factor, sp, 0, 0, N);
 }
 
 // The preamble of the egr_fatllama_plan_create* entry points: `out` reset, sizes in range (the chirp-z ones need n_in * factor >= 2;
@@ -1229,11 +1248,12 @@ extern "C" int egr_fatllama_plan_create_chirpz(egr_fatllama_plan** out, int64_t 
     EGR_CHECK(kind == 2 || (kind == 1 && !(N & 1)), EGR_ERR_ARG, "chirp-z kind %d does not fit N=%lld", kind, (long long)N);
     FlSplit sp;
     const int64_t D = kind == 1 ? N / 2 : N;
-    if (!pz_length(D, &sp)) {
+    const FlSwitches sw = fl_read_switches();
+    if (!pz_length(D, sw, &sp)) {
         set_error("no convolution length found for D=%lld", (long long)D);
         return EGR_ERR_UNSUPPORTED;
     }
-    return build_plan(out, n_in, channels, factor, sp, D, kind);
+    return build_plan(out, sw, n_in, channels, factor, sp, D, kind);
 }
 
 extern "C" int egr_fatllama_plan_create_bluestein(egr_fatllama_plan** out, int64_t n_in, int channels, int factor) {
@@ -1244,7 +1264,7 @@ extern "C" int egr_fatllama_plan_create_bluestein(egr_fatllama_plan** out, int64
         set_error("no convolution length found for N=%lld", (long long)N);
         return EGR_ERR_UNSUPPORTED;
     }
-    return build_plan(out, n_in, channels, factor, sp, N);
+    return build_plan(out, fl_read_switches(), n_in, channels, factor, sp, N);
 }
 
 extern "C" int egr_fatllama_plan_create_ex(egr_fatllama_plan** out, int64_t n_in, int channels, int factor, int m1,
@@ -1255,7 +1275,7 @@ extern "C" int egr_fatllama_plan_create_ex(egr_fatllama_plan** out, int64_t n_in
         set_error("explicit split %d x %d x %d does not fit N=%lld", m1, m2, m3, (long long)(n_in * factor));
         return EGR_ERR_UNSUPPORTED;
     }
-    return build_plan(out, n_in, channels, factor, sp);
+    return build_plan(out, fl_read_switches(), n_in, channels, factor, sp);
 }
 
 // dev: one k_row and one k_col<1> launch over the plan's state with per-workgroup phase stamps (100 MHz wall clock);
@@ -1264,31 +1284,23 @@ extern "C" int egr_fatllama_trace_once(egr_fatllama_plan* p, void* stream) {
     EGR_CHECK(p && !p->bluestein, EGR_ERR_ARG, "packed plan wanted");
     hipStream_t st = (hipStream_t)stream;
     const int C = p->C;
-    const long long M = p->sp.M, N = p->sp.N;
-    ColP A = p->colA; RowP R = p->row;
+    // through the loop's own selection: the kernels, workgroup sizes and tile geometry an iteration launches
+    const FlRowPass& row = p->loop.row[FL_ROW_DEFAULT];
+    const FlColPass& mid = p->loop.col[FL_COL_MID];
+    ColP A = *mid.geo; RowP R = p->row;
     R.thr2 = 0.36f; R.thr = 0.6f;
-    const dim3 gA(8 * A.tiles_per_xcd, C), grow(R.R / 2 + 1, C), blk(p->threads);
+    const dim3 gA = col_grid(A, C), grow(R.R / 2 + 1, C);
     const size_t nblk = (size_t)std::max(gA.x * gA.y, grow.x * grow.y);
-    long long* tr = nullptr;
-    EGR_HIP(hipMalloc((void**)&tr, nblk * 8 * sizeof(long long)));
+    DevBuf trbuf;
+    EGR_CHECK(trbuf.alloc(nblk * 8 * sizeof(long long)), EGR_ERR_HIP, "hipMalloc of %zu trace stamps failed", nblk * 8);
+    long long* tr = trbuf.as<long long>();
     std::vector<long long> h(nblk * 8);
     for (int which = 0; which < 2; ++which) {
         EGR_HIP(hipMemsetAsync(tr, 0, nblk * 8 * sizeof(long long), st));
         R.trace = tr; A.trace = tr;
         for (int rep = 0; rep < 3; ++rep) {          // the last repetition's stamps survive
-            if (which == 0) {
-                if (p->wl_row) {
-                    const WlRowEntry* e = (const WlRowEntry*)p->wl_row_entry;
-                    hipLaunchKernelGGL(e->fn, grow, dim3(e->threads), EGR_LDS(e->lds), st, R, p->wl_rt, M, p->d_work);
-                }
-                else if (p->row_sched == 1) hipLaunchKernelGGL((k_row<false, 1>), grow, blk, row_sched_lds(R.L), st, R, M, p->d_work);
-                else hipLaunchKernelGGL(k_row<false>, grow, blk, EGR_LDS(p->sp.lds_row), st, R, M, p->d_work);
-            } else {
-                if (p->wl_col) {
-                    wl_launch_col(A, p->wl_ct, M, p->d_work, C, st);
-                } else if (p->col_sched == 2) hipLaunchKernelGGL((k_col<1, 2>), gA, dim3(EGR_FL_COL_THREADS), col_sched_lds(p), st, A, M, N, 0.6f, p->d_work, (float*)nullptr, (unsigned*)nullptr, (const unsigned*)nullptr);
-                else hipLaunchKernelGGL(k_col<1>, gA, blk, EGR_LDS(p->sp.lds_col), st, A, M, N, 0.6f, p->d_work, (float*)nullptr, (unsigned*)nullptr);
-            }
+            if (which == 0) row(p, R, p->work(), C, st);
+            else mid.launch(mid, p, A, FlColIO{0.6f, nullptr, nullptr, nullptr}, p->work(), C, st);
         }
         EGR_HIP(hipStreamSynchronize(st));
         EGR_HIP(hipMemcpy(h.data(), tr, nblk * 8 * sizeof(long long), hipMemcpyDeviceToHost));
@@ -1317,7 +1329,6 @@ extern "C" int egr_fatllama_trace_once(egr_fatllama_plan* p, void* stream) {
             printf("   %-9s min %.2f  median %.2f  max %.2f us\n", which == 0 ? rn[i] : cn[i], v[0], v[v.size() / 2], v.back());
         }
     }
-    hipFree(tr);
     return EGR_OK;
 }
 
@@ -1329,40 +1340,27 @@ extern "C" int egr_fatllama_set_profiling(egr_fatllama_plan* p, int enable) {
 
 void fl_prof_begin(egr_fatllama_plan* p, int kind, hipStream_t st, size_t* slot) {
     if (!p->profiling) return;
-    if (*slot + 2 > p->ev.size()) {
-        hipEvent_t a, b;
-        hipEventCreate(&a); hipEventCreate(&b);
-        p->ev.push_back(a); p->ev.push_back(b);
+    if (*slot >= p->ev.size()) {
+        p->ev.emplace_back();
+        p->ev.back().create();
         p->ev_kind.push_back(kind);
     } else {
-        p->ev_kind[*slot / 2] = kind;
+        p->ev_kind[*slot] = kind;
     }
-    hipEventRecord(p->ev[*slot], st);
+    hipEventRecord(p->ev[*slot].a, st);
 }
 void fl_prof_end(egr_fatllama_plan* p, hipStream_t st, size_t* slot) {
     if (!p->profiling) return;
-    hipEventRecord(p->ev[*slot + 1], st);
-    *slot += 2;
+    hipEventRecord(p->ev[*slot].b, st);
+    *slot += 1;
 }
 
 // k_finalize over `out`, or (out == nullptr) one workgroup that only leaves the joint peak in joint_out
 static void launch_finalize(egr_fatllama_plan* p, float* out, unsigned flags, const float* joint_in, float* joint_out, hipStream_t st) {
     const long long Nr = out ? (long long)p->n_out : 0LL;
-    hipLaunchKernelGGL(k_finalize, out ? dim3(fl_grid(Nr), p->C) : dim3(1, 1), dim3(out ? 256 : 64), 0, st, out, Nr, p->C, flags, p->d_peaks,
-                       p->d_peaks + p->C, joint_in, joint_out);
+    hipLaunchKernelGGL(k_finalize, out ? dim3(fl_grid(Nr), p->C) : dim3(1, 1), dim3(out ? 256 : 64), 0, st, out, Nr, p->C, flags, p->peaks(),
+                       p->peaks() + p->C, joint_in, joint_out);
 }
-
-namespace {
-// one egr_fatllama_enhance call
-struct FlCall {
-    egr_fatllama_plan* p; float* out; int max_iter; float thr; unsigned flags; hipStream_t st;      // as given
-    bool relative, recompute;
-    int soft;
-    float thr0;                  // time-domain level of the opening pass: thr, thr * max|y| (relative, thr0_rel) or none (-1: every sample kept)
-    const unsigned* thr0_rel;
-    unsigned* peak_out;
-};
-}  // namespace
 
 // Argument and flag checks; clears the peaks and the ring of spectrum maxima of the relative threshold.
 static int enhance_begin(FlCall& c, const float* x) {
@@ -1380,22 +1378,20 @@ static int enhance_begin(FlCall& c, const float* x) {
     c.recompute = c.relative && (c.flags & EGR_FL_THR_RECOMPUTE) != 0;
     const bool no_init = (c.flags & EGR_FL_NO_INIT_THR) != 0;
     c.thr0 = no_init ? -1.0f : c.thr;
-    c.thr0_rel = (c.relative && !no_init) ? p->d_peaks + 2 * C : nullptr;
-    c.peak_out = p->d_peaks + C;
-    EGR_HIP(hipMemsetAsync(p->d_peaks, 0, 3 * C * sizeof(unsigned), c.st));
+    c.thr0_rel = (c.relative && !no_init) ? p->peaks() + 2 * C : nullptr;
+    c.peak_out = p->peaks() + C;
+    EGR_HIP(hipMemsetAsync(p->peaks(), 0, 3 * C * sizeof(unsigned), c.st));
     if (c.relative && c.max_iter > 0) {
-        // a ring of EGR_FL_MAX_RING slots (fl_max2_*): iteration it reads slot it, leaves the next maximum in slot it + 1 and clears
-        // slot it + 2 (mod ring).  The legacy chirp-z loop keeps one slot per iteration.
-        const size_t nslots = (p->bluestein && !p->pz) ? (size_t)c.max_iter : (size_t)EGR_FL_MAX_RING;
-        const size_t need = nslots * C * EGR_FL_MAX_STRIDE;
+        // the ring of fl_max2_slot; the legacy chirp-z loop keeps one slot per iteration
+        const size_t need = fl_max2_words((p->bluestein && !p->pz) ? (size_t)c.max_iter : (size_t)EGR_FL_MAX_RING, C);
         if (need > p->max2_cap) {
             const int rc = fl_drop_graph(p);      // it recorded the old ring
             if (rc) return rc;
-            if (p->d_max2) { EGR_HIP(hipFree(p->d_max2)); p->d_max2 = nullptr; p->max2_cap = 0; }
-            EGR_HIP(hipMalloc((void**)&p->d_max2, need * sizeof(unsigned)));
+            p->max2_cap = 0;
+            EGR_CHECK(p->d_max2.alloc(need * sizeof(unsigned)), EGR_ERR_HIP, "hipMalloc of the %zu-word ring of maxima failed", need);
             p->max2_cap = need;
         }
-        EGR_HIP(hipMemsetAsync(p->d_max2, 0, need * sizeof(unsigned), c.st));
+        EGR_HIP(hipMemsetAsync(p->max2(), 0, need * sizeof(unsigned), c.st));
     }
     return EGR_OK;
 }
@@ -1404,7 +1400,7 @@ static int enhance_begin(FlCall& c, const float* x) {
 static void launch_prepare(const FlCall& c, const float* x) {
     egr_fatllama_plan* p = c.p;
     hipLaunchKernelGGL(k_prepare, dim3(fl_grid(p->n_in), p->C), dim3(256), 0, c.st, x, c.out, (long long)p->n_in, p->factor > 0 ? p->factor : 1,
-                       (c.flags & EGR_FL_PCM_IN) ? 1 : 0, (c.flags & EGR_FL_ZERO_STUFF) ? 1 : 0, p->d_peaks, p->d_peaks + 2 * p->C,
+                       (c.flags & EGR_FL_PCM_IN) ? 1 : 0, (c.flags & EGR_FL_ZERO_STUFF) ? 1 : 0, p->peaks(), p->peaks() + 2 * p->C,
                        (c.flags & EGR_FL_INTERP_LINSPACE) ? 1 : 0, (long long)p->n_out);
 }
 
@@ -1415,18 +1411,24 @@ static int loop_none(const FlCall& c) {
     return EGR_OK;
 }
 
+// The inner column pass on the run-time-schedule kernels at `threads` threads: the chirp-z loops bring workgroup sizes of their own.
+static void launch_inner_rt(const egr_fatllama_plan* p, bool forward, int threads, const FlColIO& io, cplx* work, int nstates, hipStream_t st) {
+    FlColPass e = p->single.inner[forward];
+    e.threads = threads;
+    e(p, io, work, nstates, st);
+}
+
 // The convolution with the chirp of the legacy chirp-z passes: row FFT, times Bhat, inverse row FFT (inside the inner column pass
 // of a three-level plan) over all C states.
 static void legacy_conv(egr_fatllama_plan* p, dim3 blk, float thr, float* out, unsigned* pk, hipStream_t st) {
-    const long long P = p->sp.M, N = p->sp.N;
     const bool three = p->sp.levels == 3;
-    const ColP& B = p->colB;
     const RowP& R = p->row;
-    const dim3 gB(8 * B.tiles_per_xcd, p->C * (three ? B.nplanes : 1)), grc((R.R + EGR_FL_CONV_ROWS - 1) / EGR_FL_CONV_ROWS, p->C);
-    const size_t lb = EGR_LDS(p->sp.lds_colb);
-    if (three) hipLaunchKernelGGL(k_col<4>, gB, blk, lb, st, B, P, N, thr, p->d_work, out, pk);
-    hipLaunchKernelGGL(k_rowconv<true>, grc, dim3(EGR_FL_CONV_THREADS), rowconv_lds(R.L), st, R.f, R.L, R.R, R.tw, (const cplx*)p->d_bhat, 1.0f, P, p->d_work);
-    if (three) hipLaunchKernelGGL(k_col<3>, gB, blk, lb, st, B, P, N, thr, p->d_work, out, pk);
+    const dim3 grc((R.R + EGR_FL_CONV_ROWS - 1) / EGR_FL_CONV_ROWS, p->C);
+    const FlColIO io{thr, out, pk, nullptr};
+    if (three) launch_inner_rt(p, true, blk.x, io, p->work(), p->C, st);
+    hipLaunchKernelGGL(k_rowconv<true>, grc, dim3(EGR_FL_CONV_THREADS), rowconv_lds(R.L), st, R.f, R.L, R.R, R.tw, p->d_bhat.as<const cplx>(), 1.0f,
+                       (long long)p->sp.M, p->work());
+    if (three) launch_inner_rt(p, false, blk.x, io, p->work(), p->C, st);
 }
 
 // The legacy full-complex chirp-z loop: one state of P >= 2N - 1 points per channel, one stream, plain launches.
@@ -1442,118 +1444,83 @@ static int loop_legacy_chirpz(const FlCall& c) {
     const dim3 gA(8 * A.tiles_per_xcd, C), blk(blue_threads());
     const size_t lc = EGR_LDS(p->sp.lds_col);
     auto conv = [&]() { legacy_conv(p, blk, thr, out, peak_out, st); };
-    hipLaunchKernelGGL((k_colz<0, 0>), gA, blk, lc, st, A, cp, P, c.thr0, thr2, p->d_work, out, peak_out, c.thr0_rel);
+    hipLaunchKernelGGL((k_colz<0, 0>), gA, blk, lc, st, A, cp, P, c.thr0, thr2, p->work(), out, peak_out, c.thr0_rel);
     for (int it = 0; it < c.max_iter; ++it) {
         conv();
         if (c.relative) {                 // this iteration's spectrum maximum first (same pass, no write-back)
-            cp.max2_out = p->d_max2 + (size_t)it * C * EGR_FL_MAX_STRIDE;
-            hipLaunchKernelGGL((k_colz<3, 1>), gA, blk, lc, st, A, cp, P, thr, thr2, p->d_work, out, peak_out, (const unsigned*)nullptr);
+            cp.max2_out = p->max2() + fl_max2_words((size_t)it, C);
+            hipLaunchKernelGGL((k_colz<3, 1>), gA, blk, lc, st, A, cp, P, thr, thr2, p->work(), out, peak_out, (const unsigned*)nullptr);
             cp.max2 = cp.max2_out;
         }
-        hipLaunchKernelGGL((k_colz<1, 1>), gA, blk, lc, st, A, cp, P, thr, thr2, p->d_work, out, peak_out);
+        hipLaunchKernelGGL((k_colz<1, 1>), gA, blk, lc, st, A, cp, P, thr, thr2, p->work(), out, peak_out);
         conv();
         if (it + 1 < c.max_iter)
-            hipLaunchKernelGGL((k_colz<1, 2>), gA, blk, lc, st, A, cp, P, thr, thr2, p->d_work, out, peak_out);
+            hipLaunchKernelGGL((k_colz<1, 2>), gA, blk, lc, st, A, cp, P, thr, thr2, p->work(), out, peak_out);
     }
-    hipLaunchKernelGGL((k_colz<2, 0>), gA, blk, lc, st, A, cp, P, thr, thr2, p->d_work, out, peak_out);
+    hipLaunchKernelGGL((k_colz<2, 0>), gA, blk, lc, st, A, cp, P, thr, thr2, p->work(), out, peak_out);
     return EGR_OK;
 }
 
 // The packed-real loop: two channel groups as concurrent pipelines (fl_run_pipelines), one group's k_row overlapping the
-// other's k_col.
+// other's k_col.  Which kernel serves a pass is the plan's choice (p->loop, fl_select_passes).
 static int loop_packed(const FlCall& c) {
     egr_fatllama_plan* p = c.p;
     const int C = p->C, max_iter = c.max_iter;
     const long long M = p->sp.M, N = p->sp.N;
     const bool three = p->sp.levels == 3, relative = c.relative, recompute = c.recompute;
-    const float thr = c.thr;
-    const ColP &A = p->colA, &B = p->colB;
+    const FlPasses& ps = p->loop;
     RowP R = p->row;
-    R.thr2 = thr * thr;
-    R.thr = thr;
+    R.thr2 = c.thr * c.thr;
+    R.thr = c.thr;
     R.soft = c.soft;
-    const dim3 gA(8 * A.tiles_per_xcd, C), gB(8 * B.tiles_per_xcd, C * (three ? B.nplanes : 1)), grow(R.R / 2 + 1, C), blk(p->threads);
-    const size_t lc = EGR_LDS(p->sp.lds_col), lb = EGR_LDS(p->sp.lds_colb), lr = EGR_LDS(p->sp.lds_row);
+    const FlRowPass& hook = ps.row[(relative || R.soft != 0) ? FL_ROW_VARIANT : FL_ROW_DEFAULT];
     const int ngroups = (p->nstreams == 2 && C >= 2) ? 2 : 1;
-    // the in-place schedules need one thread per butterfly (288 / 512 row, 200 column butterflies per stage): 512 threads
-    const bool sched_ok = p->threads == 512;
-    const dim3 blkc(EGR_FL_COL_THREADS);      // the scheduled column kernels' own workgroup size
-    const bool rs1 = p->row_sched == 1 && sched_ok, cs2 = p->col_sched == 2 && sched_ok && !three;
-    // the two-barrier kernels serve the default hook (hard threshold against an absolute level) and the middle column pass
-    const WlRowEntry* wle = (const WlRowEntry*)p->wl_row_entry;
-    const bool wl_variant = relative || R.soft != 0;          // k_row_wl<.., 1>: level from the iteration's maximum and / or soft shrink
-    const bool wlr = p->wl_row != 0 && wle, wlc = p->wl_col != 0;
-    const size_t lrs = row_sched_lds(R.L), lcs = col_sched_lds(p);
-    auto max2_slot = [&](int it, int ch0) { return p->d_max2 + ((size_t)(it % EGR_FL_MAX_RING) * C + ch0) * EGR_FL_MAX_STRIDE; };
     size_t slot = 0;
     // One group's launches for iterations [it0, it1); `first` adds the opening time-domain pass, `last` the closing one.
     auto run_group = [&](hipStream_t s0, int g, int it0, int it1, bool first, bool last, bool prof) {
         const int c0 = g == 0 ? 0 : C / 2, cn = ngroups == 1 ? C : (g == 0 ? C / 2 : C - C / 2);
-        hipStream_t sg = g == 0 ? s0 : p->side;
-        cplx* wk = p->d_work + (size_t)c0 * M;
-        float* og = c.out + (size_t)c0 * N;
-        unsigned* pk = c.peak_out + c0;
-        const dim3 gAg(gA.x, cn), gBg(gB.x, cn * (three ? B.nplanes : 1)), growg(grow.x, cn);
-        auto inner = [&](bool forward) {          // the inner column pass of a three-level plan
-            if (p->wl_inner) wl_launch_inner(p->wl_colB, p->wl_it, forward, M, wk, cn, sg);
-            else if (forward) hipLaunchKernelGGL(k_col<4>, gBg, blk, lb, sg, B, M, N, thr, wk, og, pk);
-            else hipLaunchKernelGGL(k_col<3>, gBg, blk, lb, sg, B, M, N, thr, wk, og, pk);
+        hipStream_t sg = g == 0 ? s0 : p->side.s;
+        cplx* wk = p->work() + (size_t)c0 * M;
+        const FlColIO io{c.thr, c.out + (size_t)c0 * N, c.peak_out + c0, nullptr};
+        auto timed = [&](int kind, const FlColPass& pass) {
+            if (prof) fl_prof_begin(p, kind, sg, &slot);
+            pass(p, io, wk, cn, sg);
+            if (prof) fl_prof_end(p, sg, &slot);
         };
         if (first) {
-            if (cs2) hipLaunchKernelGGL((k_col<0, 2>), gAg, blkc, lcs, sg, A, M, N, c.thr0, wk, og, pk, c.thr0_rel ? c.thr0_rel + c0 : nullptr);
-            else hipLaunchKernelGGL(k_col<0>, gAg, blk, lc, sg, A, M, N, c.thr0, wk, og, pk, c.thr0_rel ? c.thr0_rel + c0 : nullptr);
-            if (three) inner(true);
+            ps.col[FL_COL_OPEN](p, FlColIO{c.thr0, io.out, io.peak, c.thr0_rel ? c.thr0_rel + c0 : nullptr}, wk, cn, sg);
+            if (three) ps.inner[FL_INNER_FWD](p, io, wk, cn, sg);
         }
         // the spectrum maximum by a pass of its own (forward row transforms + split, no write-back): only the FIRST iteration
         // needs it -- d0 = T0(y) is not the image of a shrunk spectrum -- every later one finds the maximum its predecessor's hook left
         auto max_pass = [&](int it) {
             RowP Rm = R;
-            Rm.max2_out = max2_slot(it, c0);
-            if (wlr) hipLaunchKernelGGL(wle->fn_max, growg, dim3(wle->threads), EGR_LDS(wle->lds), sg, Rm, p->wl_rt, M, wk);
-            else if (rs1) hipLaunchKernelGGL((k_row<true, 1>), growg, blk, lrs, sg, Rm, M, wk);
-            else hipLaunchKernelGGL(k_row<true>, growg, blk, lr, sg, Rm, M, wk);
+            Rm.max2_out = fl_max2_slot(p->max2(), C, it, c0);
+            ps.row[FL_ROW_MAX](p, Rm, wk, cn, sg);
         };
         if (first && relative) max_pass(0);
         for (int it = it0; it < it1; ++it) {
             RowP Rg = R;
             if (relative) {
                 if (recompute && it > 0) max_pass(it);
-                Rg.max2 = max2_slot(it, c0);
-                Rg.max2_next = recompute ? nullptr : max2_slot(it + 1, c0);
-                Rg.max2_zero = max2_slot(it + 2, c0);
+                Rg.max2 = fl_max2_slot(p->max2(), C, it, c0);
+                Rg.max2_next = recompute ? nullptr : fl_max2_slot(p->max2(), C, it + 1, c0);
+                Rg.max2_zero = fl_max2_slot(p->max2(), C, it + 2, c0);
             }
             if (prof) fl_prof_begin(p, 0, sg, &slot);
-            if (wlr && wl_variant) hipLaunchKernelGGL(wle->fn_variant, growg, dim3(wle->threads), EGR_LDS(wle->lds), sg, Rg, p->wl_rt, M, wk);
-            else if (wlr) hipLaunchKernelGGL(wle->fn, growg, dim3(wle->threads), EGR_LDS(wle->lds), sg, Rg, p->wl_rt, M, wk);
-            else if (rs1) hipLaunchKernelGGL((k_row<false, 1>), growg, blk, lrs, sg, Rg, M, wk);
-            else hipLaunchKernelGGL(k_row<false>, growg, blk, lr, sg, Rg, M, wk);
+            hook(p, Rg, wk, cn, sg);
             if (prof) fl_prof_end(p, sg, &slot);
-            if (three) {
-                if (prof) fl_prof_begin(p, 2, sg, &slot);
-                inner(false);
-                if (prof) fl_prof_end(p, sg, &slot);
-            }
+            if (three) timed(2, ps.inner[FL_INNER_INV]);
             if (it + 1 < max_iter) {
-                if (prof) fl_prof_begin(p, 1, sg, &slot);
-                if (wlc) wl_launch_col(A, p->wl_ct, M, wk, cn, sg);
-                else if (cs2) hipLaunchKernelGGL((k_col<1, 2>), gAg, blkc, lcs, sg, A, M, N, thr, wk, og, pk, (const unsigned*)nullptr);
-                else hipLaunchKernelGGL(k_col<1>, gAg, blk, lc, sg, A, M, N, thr, wk, og, pk);
-                if (prof) fl_prof_end(p, sg, &slot);
-                if (three) {
-                    if (prof) fl_prof_begin(p, 2, sg, &slot);
-                    inner(true);
-                    if (prof) fl_prof_end(p, sg, &slot);
-                }
+                timed(1, ps.col[FL_COL_MID]);
+                if (three) timed(2, ps.inner[FL_INNER_FWD]);
             }
         }
-        if (last) {
-            if (cs2) hipLaunchKernelGGL((k_col<2, 2>), gAg, blkc, lcs, sg, A, M, N, thr, wk, og, pk, (const unsigned*)nullptr);
-            else hipLaunchKernelGGL(k_col<2>, gAg, blk, lc, sg, A, M, N, thr, wk, og, pk);
-        }
+        if (last) ps.col[FL_COL_CLOSE](p, io, wk, cn, sg);
     };
     // every iteration is a middle iteration (the maximum pass of the relative threshold belongs to the opening pass);
     // EGR_FL_THR_RECOMPUTE uses plain launches
-    return fl_run_pipelines(p, c.st, ngroups, max_iter, 0, !recompute, thr, R.soft | (relative ? 2 : 0), run_group);
+    return fl_run_pipelines(p, c.st, ngroups, max_iter, 0, !recompute, c.thr, R.soft | (relative ? 2 : 0), run_group);
 }
 
 extern "C" int egr_fatllama_enhance(egr_fatllama_plan* p, const float* x, float* out, int max_iter, float thr,
@@ -1562,8 +1529,7 @@ extern "C" int egr_fatllama_enhance(egr_fatllama_plan* p, const float* x, float*
     int rc = enhance_begin(c, x);
     if (rc) return rc;
     launch_prepare(c, x);
-    rc = max_iter == 0 ? loop_none(c) : p->pz ? pz_loop(p, out, max_iter, thr, c.thr0, c.thr0_rel, flags, c.peak_out, c.st)
-         : p->bluestein ? loop_legacy_chirpz(c) : loop_packed(c);
+    rc = max_iter == 0 ? loop_none(c) : p->pz ? pz_loop(c) : p->bluestein ? loop_legacy_chirpz(c) : loop_packed(c);
     if (rc) return rc;
     if ((flags & (EGR_FL_NORMALIZE | EGR_FL_AUTOSCALE | EGR_FL_NODE_POST)) && !(flags & EGR_FL_DEFER_FINALIZE))
         launch_finalize(p, out, flags, nullptr, nullptr, c.st);
@@ -1595,10 +1561,8 @@ extern "C" int egr_fatllama_finalize(egr_fatllama_plan* p, float* out, unsigned 
 // does not own it.  Drops a captured loop graph (it recorded the previous stream).
 extern "C" int egr_fatllama_set_side_stream(egr_fatllama_plan* p, void* stream) {
     EGR_CHECK(p && stream, EGR_ERR_ARG, "null plan / stream");
-    if (p->side == (hipStream_t)stream) return EGR_OK;
-    if (p->side && p->side_owned) EGR_HIP(hipStreamDestroy(p->side));
-    p->side = (hipStream_t)stream;
-    p->side_owned = 0;
+    if (p->side.s == (hipStream_t)stream) return EGR_OK;
+    p->side.borrow((hipStream_t)stream);          // (a stream the plan created goes)
     return fl_drop_graph(p);
 }
 
@@ -1614,7 +1578,7 @@ extern "C" int egr_fatllama_last_peaks(egr_fatllama_plan* p, float* host_pin, fl
     EGR_CHECK(p && host_pin && host_pout, EGR_ERR_ARG, "null argument");
     std::vector<unsigned> h(2 * p->C);
     EGR_HIP(hipStreamSynchronize((hipStream_t)stream));
-    EGR_HIP(hipMemcpy(h.data(), p->d_peaks, h.size() * sizeof(unsigned), hipMemcpyDeviceToHost));
+    EGR_HIP(hipMemcpy(h.data(), p->peaks(), h.size() * sizeof(unsigned), hipMemcpyDeviceToHost));
     for (int c = 0; c < p->C; ++c) {
         memcpy(&host_pin[c], &h[c], 4);
         memcpy(&host_pout[c], &h[p->C + c], 4);
@@ -1627,10 +1591,10 @@ extern "C" int egr_fatllama_kernel_times3(egr_fatllama_plan* p, double ms_avg[3]
     double sum[3] = {0, 0, 0};
     int64_t cnt[3] = {0, 0, 0};
     EGR_HIP(hipDeviceSynchronize());
-    for (size_t i = 0; i + 1 < p->ev.size() && i / 2 < p->ev_kind.size(); i += 2) {
+    for (size_t i = 0; i < p->ev.size() && i < p->ev_kind.size(); ++i) {
         float ms = 0.f;
-        if (hipEventElapsedTime(&ms, p->ev[i], p->ev[i + 1]) != hipSuccess) continue;
-        const int k = p->ev_kind[i / 2];
+        if (hipEventElapsedTime(&ms, p->ev[i].a, p->ev[i].b) != hipSuccess) continue;
+        const int k = p->ev_kind[i];
         if (k < 0 || k > 2) continue;
         sum[k] += ms;
         cnt[k] += 1;
@@ -1656,27 +1620,21 @@ extern "C" int egr_fatllama_kernel_times(egr_fatllama_plan* p, double* row_ms_av
 
 // inner column pass of a three-level plan over `nstates` consecutive states (used by the chirp-z loops around their row pass)
 void fl_launch_inner(egr_fatllama_plan* p, bool forward, cplx* work, int nstates, hipStream_t st) {
-    const ColP& B = p->colB;
-    const dim3 gB(8 * B.tiles_per_xcd, nstates * B.nplanes), blk(1024);
-    const long long M = p->sp.M, N = p->sp.N;
-    if (forward) hipLaunchKernelGGL(k_col<4>, gB, blk, EGR_LDS(p->sp.lds_colb), st, B, M, N, 0.f, work, (float*)nullptr, (unsigned*)nullptr);
-    else hipLaunchKernelGGL(k_col<3>, gB, blk, EGR_LDS(p->sp.lds_colb), st, B, M, N, 0.f, work, (float*)nullptr, (unsigned*)nullptr);
+    launch_inner_rt(p, forward, 1024, FlColIO{0.f, nullptr, nullptr, nullptr}, work, nstates, st);
 }
 
 // One forward transform, the row pass with the hook `R` selects, one inverse, on the run-time-schedule kernels: src -> dst ([C][N] reals
 // each; src is only read, by the MODE 0 pass).
 static void launch_single_pass(egr_fatllama_plan* p, const RowP& R, const float* src, float* dst, hipStream_t st) {
     const int C = p->C;
-    const long long M = p->sp.M, N = p->sp.N;
     const bool three = p->sp.levels == 3;
-    const ColP &A = p->colA, &B = p->colB;
-    const dim3 gA(8 * A.tiles_per_xcd, C), gB(8 * B.tiles_per_xcd, C * (three ? B.nplanes : 1)), grow(R.R / 2 + 1, C), blk(256);
-    const size_t lc = EGR_LDS(p->sp.lds_col), lb = EGR_LDS(p->sp.lds_colb), lr = EGR_LDS(p->sp.lds_row);
-    hipLaunchKernelGGL(k_col<0>, gA, blk, lc, st, A, M, N, -1.0f, p->d_work, const_cast<float*>(src), (unsigned*)nullptr);
-    if (three) hipLaunchKernelGGL(k_col<4>, gB, blk, lb, st, B, M, N, 0.f, p->d_work, dst, (unsigned*)nullptr);
-    hipLaunchKernelGGL(k_row<false>, grow, blk, lr, st, R, M, p->d_work);
-    if (three) hipLaunchKernelGGL(k_col<3>, gB, blk, lb, st, B, M, N, 0.f, p->d_work, dst, (unsigned*)nullptr);
-    hipLaunchKernelGGL(k_col<5>, gA, blk, lc, st, A, M, N, 0.f, p->d_work, dst, (unsigned*)nullptr);
+    const FlPasses& ps = p->single;
+    const FlColIO to_dst{0.f, dst, nullptr, nullptr};
+    ps.col[FL_COL_OPEN](p, FlColIO{-1.0f, const_cast<float*>(src), nullptr, nullptr}, p->work(), C, st);
+    if (three) ps.inner[FL_INNER_FWD](p, to_dst, p->work(), C, st);
+    ps.row[FL_ROW_DEFAULT](p, R, p->work(), C, st);
+    if (three) ps.inner[FL_INNER_INV](p, to_dst, p->work(), C, st);
+    ps.col[FL_COL_CLOSE](p, to_dst, p->work(), C, st);
 }
 
 // y = irfft(rfft(x) * gain): one forward transform, a real per-bin gain, one inverse, on the plan's passes.
@@ -1712,14 +1670,14 @@ extern "C" int egr_band_filter(egr_fatllama_plan* p, const float* x, int64_t ban
         float* xs = const_cast<float*>(x);          // read only (MODE 0 pass)
         ChirpP cp = p->chirp;
         cp.band = 1; cp.band_lo = (unsigned long long)band_lo;
-        unsigned* pk = p->d_peaks + C;
+        unsigned* pk = p->peaks() + C;
         auto conv = [&]() { legacy_conv(p, blk, 0.f, y, pk, st); };
-        hipLaunchKernelGGL((k_colz<0, 0>), gA, blk, lc, st, A, cp, P, -1.0f, 0.f, p->d_work, xs, pk);
+        hipLaunchKernelGGL((k_colz<0, 0>), gA, blk, lc, st, A, cp, P, -1.0f, 0.f, p->work(), xs, pk);
         conv();
-        hipLaunchKernelGGL((k_colz<1, 1>), gA, blk, lc, st, A, cp, P, 0.f, 0.f, p->d_work, y, pk);
+        hipLaunchKernelGGL((k_colz<1, 1>), gA, blk, lc, st, A, cp, P, 0.f, 0.f, p->work(), y, pk);
         conv();
         EGR_HIP(hipMemsetAsync(y, 0, (size_t)C * cp.N * sizeof(float), st));      // the closing pass adds d to what y holds
-        hipLaunchKernelGGL((k_colz<2, 0>), gA, blk, lc, st, A, cp, P, 0.f, 0.f, p->d_work, y, pk);
+        hipLaunchKernelGGL((k_colz<2, 0>), gA, blk, lc, st, A, cp, P, 0.f, 0.f, p->work(), y, pk);
     }
     EGR_HIP(hipGetLastError());
     return EGR_OK;

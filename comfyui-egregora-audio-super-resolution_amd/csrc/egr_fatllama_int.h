@@ -8,10 +8,12 @@
 
 #include <algorithm>
 #include <initializer_list>
+#include <memory>
 #include <vector>
 
 #include "egr_common.h"
 #include "egr_fft_device.h"
+#include "egr_handle.h"
 #include "egr_plan.h"
 
 #define EGR_LDS_MAX (152 * 1024)      // dynamic LDS a kernel may ask for: the 160 KiB of a gfx950 CU minus room for its static arrays
@@ -31,6 +33,8 @@
 #endif
 #define EGR_LDS(bytes) ((size_t)(bytes) + EGR_LDS_GUARD)
 #define EGR_LDS_BASE(smem) ((smem) + EGR_LDS_HEAD)
+
+struct egr_fatllama_plan;
 
 namespace egr {
 
@@ -212,47 +216,121 @@ __device__ __forceinline__ cplx chirp(const ChirpP& c, unsigned long long n) {
 }
 
 
-struct PzPlan;          // egr_fatllama_pz.hip
+// Ring of the relative threshold's maxima: iteration `it` reads slot it, leaves the next maximum in slot it + 1 and clears slot it + 2
+// (mod EGR_FL_MAX_RING); `ch0` is the first channel of the launch.
+inline size_t fl_max2_words(size_t nslots, int C) { return nslots * C * EGR_FL_MAX_STRIDE; }
+inline unsigned* fl_max2_slot(unsigned* ring, int C, int it, int ch0) {
+    return ring + fl_max2_words((size_t)(it % EGR_FL_MAX_RING), C) + (size_t)ch0 * EGR_FL_MAX_STRIDE;
+}
+
+// Developer switches (environment), read by fl_read_switches() (egr_fatllama.hip) at the top of every plan build and of egr_fatllama_plan_query: the
+// tests and bench.py change them between plan builds of one process.  EGR_FL_BLUE_THREADS alone is read once per process (blue_threads()).
+struct FlSwitches {
+    int streams = 2;              // EGR_FL_STREAMS: channel groups run as concurrent pipelines (1 or 2)
+    bool graph = true;            // EGR_FL_GRAPH=0: plain launches instead of graph replay
+    int threads = 512;            // EGR_FL_THREADS: workgroup size of the loop kernels (256, 512, 1024); 16 waves per CU at 2 workgroups
+                                  // per CU measured 1.4x over 256
+    bool sched = true;            // EGR_FL_SCHED=0: always the run-time schedule
+    bool wl = true;               // EGR_FL_WL=0: the stage-by-stage kernels instead of the two-barrier ones (egr_fatllama_wl.h)
+    int twpow = 1;                // EGR_FL_TWPOW=0: every stage twiddle loaded instead of W^2..W^(r-1) by multiplication from W^1
+    int m1 = 0, tc = 0;           // EGR_FL_M1 / EGR_FL_TC: the planner's hints where the caller gives none
+    bool legacy_chirpz = false;   // EGR_FL_LEGACY_CHIRPZ=1: the full-complex chirp-z instead of the paired one
+    bool pz_sched = true, pz_colwl = true, pz_pairwl = true, pz_rowf = true;      // EGR_PZ_SCHED / _COLWL / _PAIRWL / _ROWF = 0
+    int pz_split_L = 0, pz_split_nc = 0;                                          // EGR_PZ_SPLIT="L,nc" forces the paired factorisation
+};
+
+struct PzPlan;                                                   // egr_fatllama_pz.hip
+struct PzPlanDelete { void operator()(PzPlan* z) const; };
+
+// ---- kernel selection of the packed loop ----
+// A pass can run on one of three kernel families with different signatures: the run-time schedule (k_row / k_col), the compile-time
+// schedule (k_row<., 1> / k_col<., 2>) and the two-barrier kernels (k_row_wl / k_col_wl / k_colb_wl).  fl_select_passes
+// (egr_fatllama.hip) picks kernel, workgroup size, dynamic LDS and tile geometry once per plan; a launch is one indirect call.
+typedef void (*FlRowFn)(RowP, long long, cplx*);
+typedef void (*FlColFn)(ColP, long long, long long, float, cplx*, float*, unsigned*, const unsigned*);
+typedef void (*WlRowFn)(RowP, WlRowT, long long, cplx*);
+typedef void (*WlColFn)(ColP, WlColT, long long, cplx*);
+typedef void (*WlInnerFn)(ColP, const cplx*, long long, cplx*);
+
+// what a column pass takes besides the state (the two-barrier kernels use none of it)
+struct FlColIO { float thr; float* out; unsigned* peak; const unsigned* thr_rel; };
+
+// `launch` issues the pass over `nch` consecutive states from `work` with the call's copy of the pass parameters
+struct FlRowPass {
+    void (*launch)(const FlRowPass&, const egr_fatllama_plan*, const RowP&, cplx* work, int nch, hipStream_t);
+    union { FlRowFn k; WlRowFn k_wl; };
+    int threads;
+    size_t lds;
+    void operator()(const egr_fatllama_plan* p, const RowP& R, cplx* work, int nch, hipStream_t st) const { launch(*this, p, R, work, nch, st); }
+};
+struct FlColPass {
+    void (*launch)(const FlColPass&, const egr_fatllama_plan*, const ColP&, const FlColIO&, cplx* work, int nch, hipStream_t);
+    union { FlColFn k; WlColFn k_wl; WlInnerFn k_wlb; };
+    int threads;
+    size_t lds;
+    const ColP* geo;       // the plan's ColP with this kernel's tile geometry
+    void operator()(const egr_fatllama_plan* p, const FlColIO& io, cplx* work, int nch, hipStream_t st) const { launch(*this, p, *geo, io, work, nch, st); }
+};
+enum { FL_ROW_DEFAULT, FL_ROW_VARIANT, FL_ROW_MAX };      // hard threshold against an absolute level; relative and / or soft; maximum only
+enum { FL_COL_OPEN, FL_COL_MID, FL_COL_CLOSE };
+enum { FL_INNER_INV, FL_INNER_FWD };                      // indexed by `forward`
+struct FlPasses {
+    FlRowPass row[3];
+    FlColPass col[3];
+    FlColPass inner[2];
+};
 }  // namespace egr
 
 struct egr_fatllama_plan {
-    int64_t n_in;
-    int64_t n_out;        // real samples per channel the loop runs on: n_in * factor, or the explicit length of egr_fatllama_plan_create_n (factor 0)
-    int C, factor, device;
-    egr::FlSplit sp;
-    egr::ColP colA, colB;
-    egr::RowP row;
-    std::vector<void*> dev_allocs;
-    bool bluestein;       // lengths outside the packed-real plans: chirp-z over P = sp.M complex points
-    int pz_kind;          // 0: packed-real plan or the legacy full-complex chirp-z; 1 / 2: paired chirp-z (egr_fatllama_pz.hip)
-    egr::PzPlan* pz;
-    egr::ChirpP chirp;
-    egr::cplx* d_bhat;         // FFT_P(b) / P in the passes' transposed layout
-    egr::cplx* d_work;
-    unsigned* d_peaks;   // [3*C]: peak_in[C], peak_out[C], peak_y[C]
-    unsigned* d_max2;    // [max2_cap]: ring of per-(iteration, channel) max |X|^2 slots of the relative-threshold variant (fl_max2_*)
-    size_t max2_cap;
-    bool profiling;
-    int threads;                  // workgroup size of the loop kernels (256 or 512)
-    int row_sched, col_sched;     // compile-time schedule ids of the loop kernels (0: run-time schedule)
-    int wl_row, wl_col;           // the two-barrier kernels of egr_fatllama_wl.h serve the row / outer column pass of the loop
-    const void* wl_row_entry;     // WlRowEntry of the row length (k_row_wl<N1, Q>)
-    int wl_inner;                 // ... and k_colb_wl the inner column pass of a three-level plan
-    egr::ColP wl_colB;            // colB with the tile geometry of k_colb_wl
-    const egr::cplx* wl_it;       // [LB][LA]: W_L^(b c) of the inner length
-    egr::WlRowT wl_rt;
-    egr::WlColT wl_ct;
-    int nstreams;                 // channel groups run as concurrent pipelines (1 or 2)
-    hipStream_t side;             // second pipeline's stream (forked from / joined to the caller's stream by events)
-    int side_owned;               // 0: `side` was handed in by egr_fatllama_set_side_stream (not destroyed with the plan)
-    hipEvent_t ev_fork, ev_join;
-    hipStream_t cap;              // private capture stream
-    hipGraphExec_t gexec;         // EGR_FL_MAX_RING captured loop iterations of all pipelines (fl_run_pipelines)
-    float g_thr; int g_groups, g_hook_kind;      // what gexec was captured for: threshold, pipelines, hook kind (soft | relative << 1)
-    int use_graph;
-    std::vector<hipEvent_t> ev;   // pairs (start, stop) tagged by kind
-    std::vector<int> ev_kind;     // 0 = row, 1 = outer column pass, 2 = inner column pass
+    int64_t n_in = 0;
+    int64_t n_out = 0;    // real samples per channel the loop runs on: n_in * factor, or the explicit length of egr_fatllama_plan_create_n (factor 0)
+    int C = 0, factor = 0, device = 0;
+    egr::FlSplit sp{};
+    egr::ColP colA{}, colB{};
+    egr::RowP row{};
+    std::vector<egr::DevBuf> tables;      // twiddle and schedule tables (fl_upload*)
+    bool bluestein = false;   // lengths outside the packed-real plans: chirp-z over P = sp.M complex points
+    int pz_kind = 0;          // 0: packed-real plan or the legacy full-complex chirp-z; 1 / 2: paired chirp-z (egr_fatllama_pz.hip)
+    std::unique_ptr<egr::PzPlan, egr::PzPlanDelete> pz;
+    egr::ChirpP chirp{};
+    egr::DevBuf d_bhat;       // FFT_P(b) / P in the passes' transposed layout
+    egr::DevBuf d_work;
+    egr::DevBuf d_peaks;      // [3*C]: peak_in[C], peak_out[C], peak_y[C]
+    egr::DevBuf d_max2;       // [max2_cap]: ring of per-(iteration, channel) max |X|^2 slots of the relative-threshold variant (fl_max2_*)
+    size_t max2_cap = 0;
+    egr::cplx* work() const { return d_work.as<egr::cplx>(); }
+    unsigned* peaks() const { return d_peaks.as<unsigned>(); }
+    unsigned* max2() const { return d_max2.as<unsigned>(); }
+    bool profiling = false;
+    egr::FlPasses loop{};         // the loop's passes: every family the plan's lengths, the switches and `threads` allow
+    egr::FlPasses single{};       // run-time-schedule kernels at 256 threads: the single-pass users, the chirp-z paths' inner passes
+    egr::ColP wl_colA{}, wl_colB{};      // colA / colB with the tile geometry of k_col_wl / k_colb_wl
+    const egr::cplx* wl_it = nullptr;    // [LB][LA]: W_L^(b c) of the inner length
+    egr::WlRowT wl_rt{};
+    egr::WlColT wl_ct{};
+    int nstreams = 2;             // channel groups run as concurrent pipelines (1 or 2)
+    egr::Stream side;             // second pipeline's stream (forked from / joined to the caller's stream by events): created by the
+                                  // plan, or handed in by egr_fatllama_set_side_stream (then not destroyed with the plan)
+    egr::EventPair fork_join;     // a: fork, b: join
+    egr::Stream cap;              // private capture stream
+    hipGraphExec_t gexec = nullptr;      // EGR_FL_MAX_RING captured loop iterations of all pipelines (fl_run_pipelines)
+    float g_thr = 0.f; int g_groups = 0, g_hook_kind = 0;      // what gexec was captured for: threshold, pipelines, hook kind (soft | relative << 1)
+    int use_graph = 1;
+    std::vector<egr::EventPair> ev;      // (start, stop) per profiled launch, tagged by kind
+    std::vector<int> ev_kind;            // 0 = row, 1 = outer column pass, 2 = inner column pass
 };
+
+namespace egr {
+// one egr_fatllama_enhance call
+struct FlCall {
+    egr_fatllama_plan* p; float* out; int max_iter; float thr; unsigned flags; hipStream_t st;      // as given
+    bool relative, recompute;
+    int soft;
+    float thr0;                  // time-domain level of the opening pass: thr, thr * max|y| (relative, thr0_rel) or none (-1: every sample kept)
+    const unsigned* thr0_rel;
+    unsigned* peak_out;
+};
+}  // namespace egr
 
 
 // host helpers defined in egr_fatllama.hip
@@ -289,21 +367,15 @@ static inline int fl_run_pipelines(egr_fatllama_plan* p, hipStream_t st, int ngr
                                    float thr, int hook_kind, RunGroup&& run_group) {
     constexpr int CH = 25;
     static_assert(CH == EGR_FL_MAX_RING, "the captured iterations address the ring of maxima by iteration mod CH");
-    if (ngroups == 2 && !p->side) {
-        EGR_HIP(hipStreamCreateWithFlags(&p->side, hipStreamNonBlocking));
-        p->side_owned = 1;
-    }
-    if (ngroups == 2 && !p->ev_fork) {
-        EGR_HIP(hipEventCreateWithFlags(&p->ev_fork, hipEventDisableTiming));
-        EGR_HIP(hipEventCreateWithFlags(&p->ev_join, hipEventDisableTiming));
-    }
+    if (ngroups == 2 && !p->side.s) EGR_HIP(p->side.create());
+    if (ngroups == 2 && !p->fork_join.a) EGR_HIP(p->fork_join.create(hipEventDisableTiming));
     // fork: the side stream waits for what s0 holds so far; join: s0 waits for the side stream (one pipeline: nothing to do)
     auto link = [&](hipEvent_t ev, hipStream_t from, hipStream_t to) -> int {
         if (ngroups == 2) { EGR_HIP(hipEventRecord(ev, from)); EGR_HIP(hipStreamWaitEvent(to, ev, 0)); }
         return EGR_OK;
     };
-    auto fork = [&](hipStream_t s0) { return link(p->ev_fork, s0, p->side); };
-    auto join = [&](hipStream_t s0) { return link(p->ev_join, p->side, s0); };
+    auto fork = [&](hipStream_t s0) { return link(p->fork_join.a, s0, p->side.s); };
+    auto join = [&](hipStream_t s0) { return link(p->fork_join.b, p->side.s, s0); };
     const bool profiling = p->profiling;
     const int n_graph = (graph_allowed && !profiling && p->use_graph && max_iter > 2 * CH) ? (max_iter - 1 - pre) / CH : 0;
     int rc = fork(st);
@@ -317,17 +389,17 @@ static inline int fl_run_pipelines(egr_fatllama_plan* p, hipStream_t st, int ngr
             if (rc) return rc;
             hipGraph_t graph = nullptr;
             // captured on a private stream (the caller's may be the legacy default stream, which cannot capture)
-            if (!p->cap) EGR_HIP(hipStreamCreateWithFlags(&p->cap, hipStreamNonBlocking));
-            EGR_HIP(hipStreamBeginCapture(p->cap, hipStreamCaptureModeThreadLocal));
-            rc = fork(p->cap);
+            if (!p->cap.s) EGR_HIP(p->cap.create());
+            hipStream_t cap = p->cap.s;
+            EGR_HIP(hipStreamBeginCapture(cap, hipStreamCaptureModeThreadLocal));
+            rc = fork(cap);
             // max_iter > 2 CH: every one of the iterations [pre, pre + CH) is a "middle" iteration
-            if (!rc) for (int g = 0; g < ngroups; ++g) run_group(p->cap, g, pre, pre + CH, false, false, false);
-            if (!rc) rc = join(p->cap);
-            hipError_t ce = hipStreamEndCapture(p->cap, &graph);
+            if (!rc) for (int g = 0; g < ngroups; ++g) run_group(cap, g, pre, pre + CH, false, false, false);
+            if (!rc) rc = join(cap);
+            hipError_t ce = hipStreamEndCapture(cap, &graph);
             if (rc || ce != hipSuccess) {          // leave no half-captured state behind: the next call starts from scratch
                 if (graph) hipGraphDestroy(graph);
-                hipStreamDestroy(p->cap);
-                p->cap = nullptr;
+                p->cap.reset();
                 if (rc) return rc;
                 EGR_HIP(ce);
             }
@@ -345,10 +417,8 @@ static inline int fl_run_pipelines(egr_fatllama_plan* p, hipStream_t st, int ngr
 }
 
 // paired chirp-z (egr_fatllama_pz.hip)
-int pz_build(egr_fatllama_plan* p, int kind);
+int pz_build(egr_fatllama_plan* p, int kind, const egr::FlSwitches& sw);
 long long pz_canary_failures();    // -1 without EGR_LDS_CANARY
-bool pz_sched_has(int L, int nc);  // column length L and row length nc both have compile-time schedules
-void pz_destroy(egr_fatllama_plan* p);
-int pz_loop(egr_fatllama_plan* p, float* out, int max_iter, float thr, float thr0, const unsigned* thr0_rel, unsigned flags,
-            unsigned* peak_out, hipStream_t st);
+bool pz_sched_has(int L, int nc);  // column length L and row length nc both have compile-time schedules (whatever EGR_PZ_SCHED says)
+int pz_loop(const egr::FlCall& c);
 int pz_band_filter(egr_fatllama_plan* p, const float* x, int64_t band_lo, float* y, hipStream_t st);

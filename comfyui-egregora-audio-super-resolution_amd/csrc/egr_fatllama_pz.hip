@@ -992,22 +992,23 @@ typedef void (*PzColFn)(PzP, float, cplx*, float*, unsigned*, const unsigned*);
 typedef void (*PzRowFn)(const cplx*, const cplx*, long long, cplx*);
 
 struct PzPlan {
-    PzP p;
-    cplx* d_bhat;
-    int nstates;
+    PzP p{};
+    DevBuf d_bhat;
+    int nstates = 0;
     // kernels of this plan: the spectrum pass (and its reduction-only form), the crop pass, the opening / closing passes
-    PzPairFn pair, pairmax;
-    PzColFn crop, first, last;
-    int threads_pair, threads_pairmax, threads_crop, threads_col;
-    int col_sched;               // column length with a compile-time schedule (0: run-time schedule)
-    const cplx* stw_row;         // stage tables of the compile-time row schedule (nullptr: run-time schedule)
-    PzRowFn rowconv, rowconv_conj;
-    int threads_row;
-    const void* crop_wl;         // PzColWlEntry of the two-barrier crop pass (nullptr: k_pzcol<1>)
-    const void* pair_wl;         // PzPairWlEntry::fn of the four-barrier spectrum pass (nullptr: k_pzpair)
-    const cplx* crop_wl_tab;     // [LB][LA]: W_L^(b c)
-    size_t lds_col, lds_pair, lds_row;
+    PzPairFn pair = nullptr, pairmax = nullptr;
+    PzColFn crop = nullptr, first = nullptr, last = nullptr;
+    int threads_pair = 0, threads_pairmax = 0, threads_crop = 0, threads_col = 0;
+    int col_sched = 0;                            // column length with a compile-time schedule (0: run-time schedule)
+    const cplx* stw_row = nullptr;                // stage tables of the compile-time row schedule (nullptr: run-time schedule)
+    PzRowFn rowconv = nullptr, rowconv_conj = nullptr;
+    int threads_row = 512;
+    const PzColWlEntry* crop_wl = nullptr;        // the two-barrier crop pass (nullptr: k_pzcol<1>)
+    PzPairWlFn pair_wl = nullptr;                 // the four-barrier spectrum pass (nullptr: k_pzpair)
+    const cplx* crop_wl_tab = nullptr;            // [LB][LA]: W_L^(b c)
+    size_t lds_col = 0, lds_pair = 0, lds_row = 0;
 };
+void PzPlanDelete::operator()(PzPlan* z) const { delete z; }
 
 // Lengths with a compile-time schedule.  Columns X(L, R0, R1, R2): 512 .. 1024 in steps of 3 - 9 %; rows Y(NC, R0, R1, R2, R3):
 // 1024 .. 16384 by powers of two -- so every convolution length from 0.5 M to 16.7 M points has a plan P = L x NC within 9 %
@@ -1039,18 +1040,10 @@ static const PzRowEntry kPzRows[] = {PZ_ROW_LIST(PZ_ROW_ENTRY)};
 using namespace egr;
 
 bool pz_sched_has(int L, int nc) {
-    if (getenv("EGR_PZ_SCHED") && atoi(getenv("EGR_PZ_SCHED")) == 0) return false;
     bool col = false, row = false;
     for (const PzSchedEntry& e : kPzSched) col = col || e.L == L;
     for (const PzRowEntry& e : kPzRows) row = row || e.NC == nc;
     return col && row;
-}
-
-void pz_destroy(egr_fatllama_plan* p) {
-    if (!p->pz) return;
-    if (p->pz->d_bhat) hipFree(p->pz->d_bhat);
-    delete p->pz;
-    p->pz = nullptr;
 }
 
 static int pick_threads(int elements) {          // in-place stages hold up to 8 elements per thread; whole multiples of 256
@@ -1058,13 +1051,9 @@ static int pick_threads(int elements) {          // in-place stages hold up to 8
     return t < 256 ? 256 : (t > 1024 ? 1024 : t);
 }
 
-int pz_build(egr_fatllama_plan* plan, int kind) {
-    PzPlan* z = new PzPlan();
-    memset(&z->p, 0, sizeof(PzP));
-    z->d_bhat = nullptr;
-    z->stw_row = nullptr;
-    z->col_sched = 0;
-    plan->pz = z;
+int pz_build(egr_fatllama_plan* plan, int kind, const FlSwitches& sw) {
+    plan->pz.reset(new PzPlan());
+    PzPlan* z = plan->pz.get();
     const FlSplit& sp = plan->sp;
     const ColP& a = plan->colA;
     const RowP& r = plan->row;
@@ -1094,7 +1083,7 @@ int pz_build(egr_fatllama_plan* plan, int kind) {
     z->nstates = kind == 1 ? plan->C : (plan->C + 1) / 2;
     int rc;
     if ((rc = fl_make_tw2(plan, 2 * (int64_t)q.D, &q.w))) return rc;
-    EGR_CHECK(q.L * q.TC <= 8 * 1024 && (r.L <= 8 * 512 || pz_sched_has(q.L, r.L)), EGR_ERR_UNSUPPORTED, "tile too large for the in-place stages (L=%d TC=%d row=%d)", q.L, q.TC, r.L);
+    EGR_CHECK(q.L * q.TC <= 8 * 1024 && (r.L <= 8 * 512 || (sw.pz_sched && pz_sched_has(q.L, r.L))), EGR_ERR_UNSUPPORTED, "tile too large for the in-place stages (L=%d TC=%d row=%d)", q.L, q.TC, r.L);
     // ---- kernels: run-time schedule by default (in-place stages hold up to 8 elements per thread) ----
     const bool fuse = 2 * q.L * q.TC <= 8 * 1024;
     z->threads_col = z->threads_crop = pick_threads(q.L * q.TC);
@@ -1103,8 +1092,7 @@ int pz_build(egr_fatllama_plan* plan, int kind) {
     z->pair = fuse ? k_pzpair<false, PzRt<true>> : k_pzpair<false, PzRt<false>>;
     z->pairmax = fuse ? k_pzpair<true, PzRt<true>> : k_pzpair<true, PzRt<false>>;
     // compile-time schedules where the plan's lengths have one
-    const bool sched_on = !(getenv("EGR_PZ_SCHED") && atoi(getenv("EGR_PZ_SCHED")) == 0);
-    if (sched_on && q.TC == 4)
+    if (sw.pz_sched && q.TC == 4)
         for (const PzSchedEntry& e : kPzSched)
             if (e.L == q.L) {
                 if ((rc = fl_upload_sched_tables(plan, {e.r0, e.r1, e.r2}, &q.stw))) return rc;
@@ -1113,8 +1101,7 @@ int pz_build(egr_fatllama_plan* plan, int kind) {
                 z->col_sched = e.L;
             }
     // the crop pass on the two-barrier kernel where the column length has an instantiation (EGR_PZ_COLWL=0: k_pzcol<1>)
-    z->crop_wl = nullptr; z->crop_wl_tab = nullptr; z->pair_wl = nullptr;
-    if (!(getenv("EGR_PZ_COLWL") && atoi(getenv("EGR_PZ_COLWL")) == 0) && q.nc % 8 == 0 && !(sp.levels == 3))
+    if (sw.pz_colwl && q.nc % 8 == 0 && !(sp.levels == 3))
         for (const PzColWlEntry& e : kPzColWl)
             if (e.L == q.L) {
                 std::vector<float2> t((size_t)e.L);
@@ -1127,12 +1114,10 @@ int pz_build(egr_fatllama_plan* plan, int kind) {
                 if ((rc = fl_upload(plan, t, &z->crop_wl_tab))) return rc;
                 z->crop_wl = &e;
                 // the spectrum pass too, for even/odd packing (kind 1); channel pairs (kind 2, rows of 8192) measure 2 % slower with it
-                if (q.TC == 4 && kind == 1 && !(getenv("EGR_PZ_PAIRWL") && atoi(getenv("EGR_PZ_PAIRWL")) == 0))
-                    for (const PzPairWlEntry& pe : kPzPairWl) if (pe.L == q.L) z->pair_wl = (const void*)pe.fn;
+                if (q.TC == 4 && kind == 1 && sw.pz_pairwl)
+                    for (const PzPairWlEntry& pe : kPzPairWl) if (pe.L == q.L) z->pair_wl = pe.fn;
             }
-    z->rowconv = z->rowconv_conj = nullptr;
-    z->threads_row = 512;
-    if (sched_on)
+    if (sw.pz_sched)
         for (const PzRowEntry& e : kPzRows)
             if (e.NC == r.L) {
                 if (e.r3 > 1) rc = fl_upload_sched_tables(plan, {e.r0, e.r1, e.r2, e.r3}, &z->stw_row);
@@ -1143,7 +1128,7 @@ int pz_build(egr_fatllama_plan* plan, int kind) {
             }
     // three-stage rows (1024 / 2048 / 4096 points): the kernel with the outer stages fused into the memory accesses (EGR_PZ_ROWF=0:
     // k_pz_rowconv_s); same tables, same LDS footprint
-    if (z->rowconv && !(getenv("EGR_PZ_ROWF") && atoi(getenv("EGR_PZ_ROWF")) == 0)) {
+    if (z->rowconv && sw.pz_rowf) {
         if (r.L == 4096) { z->rowconv = k_pz_rowconv_f<false, 4096, 16, 16>; z->rowconv_conj = k_pz_rowconv_f<true, 4096, 16, 16>; }
         else if (r.L == 2048) { z->rowconv = k_pz_rowconv_f<false, 2048, 16, 8>; z->rowconv_conj = k_pz_rowconv_f<true, 2048, 16, 8>; }
         else if (r.L == 1024) { z->rowconv = k_pz_rowconv_f<false, 1024, 8, 8>; z->rowconv_conj = k_pz_rowconv_f<true, 1024, 8, 8>; }
@@ -1165,14 +1150,10 @@ int pz_build(egr_fatllama_plan* plan, int kind) {
     }
     // ---- Bhat = FFT_P(b) / P in double precision, stored in the passes' order ----
     const long long P = q.P;
-    double2 *b0 = nullptr, *b1 = nullptr;
-    if (hipMalloc((void**)&b0, (size_t)P * sizeof(double2)) != hipSuccess || hipMalloc((void**)&b1, (size_t)P * sizeof(double2)) != hipSuccess ||
-        hipMalloc((void**)&z->d_bhat, (size_t)P * sizeof(cplx)) != hipSuccess) {
-        if (b0) hipFree(b0);
-        if (b1) hipFree(b1);
-        set_error("hipMalloc of the %lld-point chirp spectrum failed", P);
-        return EGR_ERR_ALLOC;
-    }
+    DevBuf buf0, buf1;          // ping-pong of the stages: freed when this function returns, behind the synchronisation below (or hipFree's own)
+    EGR_CHECK(buf0.alloc((size_t)P * sizeof(double2)) && buf1.alloc((size_t)P * sizeof(double2)) && z->d_bhat.alloc((size_t)P * sizeof(cplx)), EGR_ERR_ALLOC,
+              "hipMalloc of the %lld-point chirp spectrum failed", P);
+    double2 *b0 = buf0.as<double2>(), *b1 = buf1.as<double2>();
     const int nb = (int)std::min<long long>((P + 255) / 256, 8192);
     hipLaunchKernelGGL(k_pz_chirp_b, dim3(nb), dim3(256), 0, 0, q.D, q.inv_2D, P, b0);
     {
@@ -1188,15 +1169,10 @@ int pz_build(egr_fatllama_plan* plan, int kind) {
         while (rem % 2 == 0) stage(2);
         while (rem % 9 == 0) stage(9);
         for (int pr : {3, 5, 7, 11, 13}) while (rem % pr == 0) stage(pr);
-        if (rem != 1) {
-            hipFree(b0); hipFree(b1);
-            set_error("convolution length %lld has a prime factor above 13", P);
-            return EGR_ERR_UNSUPPORTED;
-        }
+        EGR_CHECK(rem == 1, EGR_ERR_UNSUPPORTED, "convolution length %lld has a prime factor above 13", P);
     }
-    hipLaunchKernelGGL(k_pz_bhat_store, dim3(nb), dim3(256), 0, 0, (const double2*)b0, P, r.L, r.Ma, r.Mb, 1.0 / (double)P, z->d_bhat);
+    hipLaunchKernelGGL(k_pz_bhat_store, dim3(nb), dim3(256), 0, 0, (const double2*)b0, P, r.L, r.Ma, r.Mb, 1.0 / (double)P, z->d_bhat.as<cplx>());
     const hipError_t se = hipDeviceSynchronize();
-    hipFree(b0); hipFree(b1);
     if (se != hipSuccess || hipGetLastError() != hipSuccess) {
         set_error("building the chirp spectrum failed: %s", hipGetErrorString(se));
         return EGR_ERR_HIP;
@@ -1214,10 +1190,10 @@ struct PzRun {
         if (three) fl_launch_inner(plan, true, work, ns, st);
         if (prof) fl_prof_begin(plan, 0, st, slot);
         if (z->rowconv) {
-            hipLaunchKernelGGL(conj ? z->rowconv_conj : z->rowconv, dim3(r.R, ns), dim3(z->threads_row), z->lds_row, st, z->stw_row, (const cplx*)z->d_bhat, z->p.P, work);
+            hipLaunchKernelGGL(conj ? z->rowconv_conj : z->rowconv, dim3(r.R, ns), dim3(z->threads_row), z->lds_row, st, z->stw_row, z->d_bhat.as<const cplx>(), z->p.P, work);
         } else {
-            if (conj) hipLaunchKernelGGL(k_pz_rowconv<true>, dim3(r.R, ns), dim3(512), z->lds_row, st, r.f, r.L, r.tw, (const cplx*)z->d_bhat, z->p.P, work);
-            else hipLaunchKernelGGL(k_pz_rowconv<false>, dim3(r.R, ns), dim3(512), z->lds_row, st, r.f, r.L, r.tw, (const cplx*)z->d_bhat, z->p.P, work);
+            if (conj) hipLaunchKernelGGL(k_pz_rowconv<true>, dim3(r.R, ns), dim3(512), z->lds_row, st, r.f, r.L, r.tw, z->d_bhat.as<const cplx>(), z->p.P, work);
+            else hipLaunchKernelGGL(k_pz_rowconv<false>, dim3(r.R, ns), dim3(512), z->lds_row, st, r.f, r.L, r.tw, z->d_bhat.as<const cplx>(), z->p.P, work);
         }
         if (prof) fl_prof_end(plan, st, slot);
         if (three) fl_launch_inner(plan, false, work, ns, st);
@@ -1227,8 +1203,8 @@ struct PzRun {
         if (prof && !maxonly) fl_prof_begin(plan, 1, st, slot);
         if (maxonly) hipLaunchKernelGGL(z->pairmax, g, dim3(z->threads_pairmax), z->lds_pair, st, q, h, work);
         else if (z->pair_wl) {
-            const PzColWlEntry* e = (const PzColWlEntry*)z->crop_wl;          // same geometry: 8 column slots, max(LA, LB) threads each
-            hipLaunchKernelGGL((PzPairWlFn)z->pair_wl, g, dim3(e->threads), EGR_LDS(e->lds), st, q, h, z->crop_wl_tab, work);
+            const PzColWlEntry* e = z->crop_wl;          // same geometry: 8 column slots, max(LA, LB) threads each
+            hipLaunchKernelGGL(z->pair_wl, g, dim3(e->threads), EGR_LDS(e->lds), st, q, h, z->crop_wl_tab, work);
         } else hipLaunchKernelGGL(z->pair, g, dim3(z->threads_pair), z->lds_pair, st, q, h, work);
         if (prof && !maxonly) fl_prof_end(plan, st, slot);
     }
@@ -1236,19 +1212,23 @@ struct PzRun {
 }  // namespace
 
 // The loop between k_prepare and k_finalize: `out` holds y, receives y + d; per-channel peaks -> peak_out.
-int pz_loop(egr_fatllama_plan* plan, float* out, int max_iter, float thr, float thr0, const unsigned* thr0_rel, unsigned flags,
-            unsigned* peak_out, hipStream_t st) {
-    PzPlan* z = plan->pz;
+int pz_loop(const FlCall& c) {
+    egr_fatllama_plan* plan = c.p;
+    PzPlan* z = plan->pz.get();
+    const int max_iter = c.max_iter;
     EGR_CHECK(z != nullptr && max_iter >= 1, EGR_ERR_ARG, "paired chirp-z plan / iteration count");
     const PzP& q = z->p;
     const int C = plan->C;
-    const bool relative = (flags & EGR_FL_THR_RELATIVE) != 0;
-    const bool recompute = relative && (flags & EGR_FL_THR_RECOMPUTE) != 0;
-    auto max2_slot = [&](int it, int ch0) { return plan->d_max2 + ((size_t)(it % EGR_FL_MAX_RING) * C + ch0) * EGR_FL_MAX_STRIDE; };
+    const bool relative = c.relative, recompute = c.recompute;
+    const float thr = c.thr, thr0 = c.thr0;
+    const unsigned* thr0_rel = c.thr0_rel;
+    float* out = c.out;
+    unsigned* peak_out = c.peak_out;
+    auto max2_slot = [&](int it, int ch0) { return fl_max2_slot(plan->max2(), C, it, ch0); };
     PzHook h;
     memset(&h, 0, sizeof(h));
     h.thr = thr;
-    h.soft = (flags & EGR_FL_THR_SOFT) ? 1 : 0;
+    h.soft = c.soft;
     PzRun run{plan, z, plan->sp.levels == 3};
     // states are independent until k_finalize: two groups of states run as concurrent pipelines on two streams
     const int ns_all = z->nstates;
@@ -1257,8 +1237,8 @@ int pz_loop(egr_fatllama_plan* plan, float* out, int max_iter, float thr, float 
     // One group's launches: `first` adds the opening pass, iterations [it0, it1), `last` the closing pass.
     auto run_group = [&](hipStream_t s0, int g, int it0, int it1, bool first, bool last, bool profiling) {
         const int sb = g == 0 ? 0 : ns_all / 2, ns = ngroups == 1 ? ns_all : (g == 0 ? ns_all / 2 : ns_all - ns_all / 2);
-        hipStream_t sg = g == 0 ? s0 : plan->side;
-        cplx* work = plan->d_work + (size_t)sb * q.P;
+        hipStream_t sg = g == 0 ? s0 : plan->side.s;
+        cplx* work = plan->work() + (size_t)sb * q.P;
         // the kernels index channels from the state id: shift the per-channel arrays so that state 0 of the group is local state 0
         const int ch0 = q.kind == 1 ? sb : 2 * sb;
         PzP qg = q;
@@ -1286,7 +1266,7 @@ int pz_loop(egr_fatllama_plan* plan, float* out, int max_iter, float thr, float 
             if (it + 1 < max_iter) {
                 if (p_it) fl_prof_begin(plan, 2, sg, &slot);
                 if (z->crop_wl) {
-                    const PzColWlEntry* e = (const PzColWlEntry*)z->crop_wl;
+                    const PzColWlEntry* e = z->crop_wl;
                     const int nt8 = q.nc / 8, tpx8 = ceil_div(nt8, 8);
                     hipLaunchKernelGGL(e->fn, dim3(8 * tpx8, ns), dim3(e->threads), EGR_LDS(e->lds), sg, qg, z->crop_wl_tab, nt8, tpx8, work);
                 } else
@@ -1300,14 +1280,14 @@ int pz_loop(egr_fatllama_plan* plan, float* out, int max_iter, float thr, float 
     // (two pipelines: 113.9 -> 103.4 ms per 800 iterations of 60 s + 2 samples; a single pipeline measures the same either way).
     // Relative threshold: iteration 0 (the one with a maximum pass of its own, behind its first convolution) stays outside the graph;
     // EGR_FL_THR_RECOMPUTE uses plain launches.
-    return fl_run_pipelines(plan, st, ngroups, max_iter, relative ? 1 : 0, !recompute && ngroups == 2, thr, h.soft | (relative ? 2 : 0),
+    return fl_run_pipelines(plan, c.st, ngroups, max_iter, relative ? 1 : 0, !recompute && ngroups == 2, thr, h.soft | (relative ? 2 : 0),
                             run_group);
 }
 
 // y = irfft(rfft(x) * [k >= band_lo]) per channel on a paired chirp-z plan (factor 1): first pass without a threshold, one
 // convolution, the band hook, the conjugate convolution, closing pass onto a zeroed y.
 int pz_band_filter(egr_fatllama_plan* plan, const float* x, int64_t band_lo, float* y, hipStream_t st) {
-    PzPlan* z = plan->pz;
+    PzPlan* z = plan->pz.get();
     EGR_CHECK(z != nullptr, EGR_ERR_ARG, "paired chirp-z plan wanted");
     const PzP& q = z->p;
     PzHook h;
@@ -1316,15 +1296,15 @@ int pz_band_filter(egr_fatllama_plan* plan, const float* x, int64_t band_lo, flo
     h.band_lo = (unsigned long long)band_lo;
     PzRun run{plan, z, plan->sp.levels == 3};
     const int ns = z->nstates;
-    unsigned* pk = plan->d_peaks + plan->C;
+    unsigned* pk = plan->peaks() + plan->C;
     size_t slot = 0;
     const dim3 gc(8 * q.tiles_per_xcd, ns), bc(z->threads_col);
-    hipLaunchKernelGGL(z->first, gc, bc, z->lds_col, st, q, -1.0f, plan->d_work, const_cast<float*>(x), pk, (const unsigned*)nullptr);
-    run.conv(false, plan->d_work, ns, st, false, &slot);
-    run.pair(q, h, false, plan->d_work, ns, st, false, &slot);
-    run.conv(true, plan->d_work, ns, st, false, &slot);
+    hipLaunchKernelGGL(z->first, gc, bc, z->lds_col, st, q, -1.0f, plan->work(), const_cast<float*>(x), pk, (const unsigned*)nullptr);
+    run.conv(false, plan->work(), ns, st, false, &slot);
+    run.pair(q, h, false, plan->work(), ns, st, false, &slot);
+    run.conv(true, plan->work(), ns, st, false, &slot);
     EGR_HIP(hipMemsetAsync(y, 0, (size_t)plan->C * q.N * sizeof(float), st));      // the closing pass adds d to what y holds
-    hipLaunchKernelGGL(z->last, gc, bc, z->lds_col, st, q, 0.f, plan->d_work, y, pk, (const unsigned*)nullptr);
+    hipLaunchKernelGGL(z->last, gc, bc, z->lds_col, st, q, 0.f, plan->work(), y, pk, (const unsigned*)nullptr);
     EGR_HIP(hipGetLastError());
     return EGR_OK;
 }

@@ -60,7 +60,6 @@ template <int R, int TC> struct WlCol {
     static constexpr int THREADS = ((R * TC + 63) / 64) * 64;
     static constexpr int LDS = R * R * TC * 8;
 };
-static inline int wl_col_radix(int L) { return L == 625 ? 25 : (L == 441 ? 21 : 0); }      // column lengths with a k_col_wl instantiation
 // The factors 1/2 of the real split are folded away: the hook works on 2 X (exact: a power of two commutes with every rounding),
 // compares against 4 thr^2 / 2 t, and the 1/4 this leaves joins 1/M.  The scaling by 1/M is a product with a two-term float value
 // (sc_hi + sc_lo = 1/(4M) to 2^-48: one rounding per result, as the product in double it replaces) -- a float 1/M alone carries a
@@ -421,9 +420,8 @@ __global__ __launch_bounds__((WlRow<N1, Q>::THREADS)) void k_row_wl(RowP p, WlRo
     EGR_STAMP(p, 5);
 }
 
-// row lengths with a k_row_wl instantiation: EGR_WL_ROW_LIST(X), X(L, N1, Q)
+// row lengths with a k_row_wl instantiation: EGR_WL_ROW_LIST(X), X(L, N1, Q); the kernel types (WlRowFn ...) are in egr_fatllama_int.h
 #include "egr_wl_rows.h"
-typedef void (*WlRowFn)(RowP, WlRowT, long long, cplx*);
 struct WlRowEntry { int L, n1, q, threads, lds; WlRowFn fn, fn_variant, fn_max; };      // hooks 0 / 1 / 2
 #define EGR_WL_ROW_ENTRY(LL, A, B) {LL, A, B, WlRow<A, B>::THREADS, WlRow<A, B>::LDS, k_row_wl<A, B, 0>, k_row_wl<A, B, 1>, k_row_wl<A, B, 2>},
 static const WlRowEntry kWlRows[] = {EGR_WL_ROW_LIST(EGR_WL_ROW_ENTRY)};
@@ -514,16 +512,10 @@ __global__ __launch_bounds__((WlCol<R, TC>::THREADS), EGR_WL_COL_WAVES) void k_c
     }
     EGR_STAMP(p, 4);
 }
-// A: the plan's outer ColP (columns of 625 or 441 points); ny = grid.y (channels x planes)
-template <int R, int TC>
-static inline void wl_launch_col_t(ColP A, const WlColT& tb, long long M, cplx* work, int ny, hipStream_t st) {
-    A.TC = TC; A.TClog2 = 0; A.ntiles = (A.ncols + TC - 1) / TC; A.tiles_per_xcd = (A.ntiles + 7) / 8;      // (a ragged last tile is fine)
-    hipLaunchKernelGGL((k_col_wl<R, TC>), dim3(8 * A.tiles_per_xcd, ny), dim3(WlCol<R, TC>::THREADS), EGR_LDS((WlCol<R, TC>::LDS)), st, A, tb, M, work);
-}
-static inline void wl_launch_col(const ColP& A, const WlColT& tb, long long M, cplx* work, int ny, hipStream_t st) {
-    if (A.L == 441) wl_launch_col_t<21, 12>(A, tb, M, work, ny, st);
-    else wl_launch_col_t<25, 8>(A, tb, M, work, ny, st);
-}
+// column lengths with a k_col_wl instantiation: L = R x R points in tiles of TC columns (a ragged last tile is fine); grid.y = channels x planes
+struct WlColEntry { int L, r, tc, threads, lds; WlColFn fn; };
+#define EGR_WL_COL_ENTRY(R, TC) {R * R, R, TC, WlCol<R, TC>::THREADS, WlCol<R, TC>::LDS, k_col_wl<R, TC>}
+static const WlColEntry kWlCols[] = {EGR_WL_COL_ENTRY(25, 8), EGR_WL_COL_ENTRY(21, 12)};
 
 // k_colb_wl -- the INNER column pass of a three-level plan (length L = LA x LB <= 144 over n2 inside each k1 plane, stride M3), one
 // barrier: thread (b, col) loads n2 = LB a + b, radix-LA in registers, x W_L^(b c), transpose through LDS, thread (c, col) does the
@@ -620,38 +612,15 @@ __global__ __launch_bounds__((WlInner<LA, LB>::THREADS)) void k_colb_wl(ColP p, 
     X(56, 7, 8) X(60, 6, 10) X(63, 7, 9) X(64, 8, 8) X(72, 8, 9) X(80, 8, 10) X(90, 9, 10) X(96, 8, 12) \
     X(100, 10, 10) X(120, 10, 12) X(144, 12, 12)
 
-static bool wl_inner_supported(int L) {
-    switch (L) {
-#define X(LL, LA, LB) case LL:
-        EGR_WL_INNER_LIST(X)
-#undef X
-        return true;
-        default: return false;
-    }
-}
-static void wl_inner_geometry(int L, int* la, int* lb, int* tcw) {
-    switch (L) {
-#define X(LL, LA, LB) case LL: *la = LA; *lb = LB; *tcw = WlInner<LA, LB>::TCW; return;
-        EGR_WL_INNER_LIST(X)
-#undef X
-        default: *la = *lb = *tcw = 0;
-    }
-}
-// B: the plan's inner ColP with TC / ntiles / tiles_per_xcd set for WlInner<LA, LB>::TCW
-template <int LA, int LB> static void wl_launch_inner_t(const ColP& B, const cplx* tab, bool forward, long long M, cplx* work, int nstates, hipStream_t st) {
-    using G = WlInner<LA, LB>;
-    const dim3 grid(8 * B.tiles_per_xcd, nstates * B.nplanes), blk(G::THREADS);
-    const size_t lds = EGR_LDS(G::LDS);
-    if (forward) hipLaunchKernelGGL((k_colb_wl<LA, LB, true>), grid, blk, lds, st, B, tab, M, work);
-    else hipLaunchKernelGGL((k_colb_wl<LA, LB, false>), grid, blk, lds, st, B, tab, M, work);
-}
-static void wl_launch_inner(const ColP& B, const cplx* tab, bool forward, long long M, cplx* work, int nstates, hipStream_t st) {
-    switch (B.L) {
-#define X(LL, LA, LB) case LL: wl_launch_inner_t<LA, LB>(B, tab, forward, M, work, nstates, st); break;
-        EGR_WL_INNER_LIST(X)
-#undef X
-        default: break;
-    }
+// the ColP of a launch is the plan's inner one with TC / ntiles / tiles_per_xcd set for tcw columns per workgroup
+struct WlInnerEntry { int L, la, lb, tcw, threads, lds; WlInnerFn fwd, inv; };
+#define EGR_WL_INNER_ENTRY(LL, LA, LB) {LL, LA, LB, WlInner<LA, LB>::TCW, WlInner<LA, LB>::THREADS, WlInner<LA, LB>::LDS, k_colb_wl<LA, LB, true>, k_colb_wl<LA, LB, false>},
+static const WlInnerEntry kWlInner[] = {EGR_WL_INNER_LIST(EGR_WL_INNER_ENTRY)};
+
+// the entry of length L in one of the tables above (nullptr: no instantiation)
+template <class E, size_t N> static const E* wl_find(const E (&table)[N], int L) {
+    for (const E& e : table) if (e.L == L) return &e;
+    return nullptr;
 }
 
 }  // namespace egr

@@ -36,6 +36,8 @@ namespace {
 using egr::set_error;
 using egr::ConvCall;
 using egr::ConvChoice;
+using egr::DevBuf;         // egr_handle.h
+using egr::EventPair;
 
 enum { ACT_NONE = 0, ACT_SILU = 1, ACT_TANH = 2, ACT_LEAKY = 3, ACT_LOGCLAMP = 4 };
 enum { EW_ADD = 0, EW_AXPBY = 1, EW_SILU = 2, EW_SCALE = 3, EW_COPY = 4, EW_ADD_SCALE = 5 };
@@ -60,30 +62,6 @@ struct HipSlabs {
     void put(void* base) { hipFree(base); }
 };
 typedef egr::Arena<HipSlabs> Arena;
-
-// a hipMalloc'ed buffer and its hipFree (move-only); whoever must wait for the device before a free does so before reset()
-struct DevBuf {
-    void* p = nullptr;
-    DevBuf() {}
-    DevBuf(DevBuf&& o) noexcept : p(o.p) { o.p = nullptr; }
-    DevBuf& operator=(DevBuf&& o) noexcept { if (this != &o) { reset(); p = o.p; o.p = nullptr; } return *this; }
-    ~DevBuf() { reset(); }
-    bool alloc(size_t bytes) { reset(); if (hipMalloc(&p, bytes) != hipSuccess) p = nullptr; return p != nullptr; }
-    void reset() { if (p) hipFree(p); p = nullptr; }
-    void* release() { void* q = p; p = nullptr; return q; }
-    template <class T> T* as() const { return (T*)p; }
-};
-
-// the two events around a timed launch (move-only; empty until create())
-struct EventPair {
-    hipEvent_t a = nullptr, b = nullptr;
-    EventPair() {}
-    EventPair(EventPair&& o) noexcept : a(o.a), b(o.b) { o.a = o.b = nullptr; }
-    EventPair& operator=(EventPair&& o) noexcept { if (this != &o) { reset(); a = o.a; b = o.b; o.a = o.b = nullptr; } return *this; }
-    ~EventPair() { reset(); }
-    void create() { hipEventCreate(&a); hipEventCreate(&b); }
-    void reset() { if (a) hipEventDestroy(a); if (b) hipEventDestroy(b); a = b = nullptr; }
-};
 
 struct Ten {                       // an fp32 activation owned by the arena (move-only)
     Arena* a = nullptr;

@@ -1,5 +1,6 @@
 // What the model handles that live inside the library (DfnCore, Dac) share around a call: the kept workspace, the device checks and the
-// stage copy-out.  WPE (caller-owned workspace) and the Fat-Llama plan (owns its buffers) have lifetimes of their own.
+// stage copy-out; and the move-only owners of device resources (DevBuf, EventPair, Stream) that the FlashSR handle and the Fat-Llama plan
+// hold as members.  WPE (caller-owned workspace) has a lifetime of its own.
 #pragma once
 #include "egr_common.h"
 
@@ -46,6 +47,46 @@ struct Workspace {
         p = nullptr;
         bytes = 0;
     }
+};
+
+// a hipMalloc'ed buffer and its hipFree (move-only); whoever must wait for the device before a free does so before reset()
+struct DevBuf {
+    void* p = nullptr;
+    DevBuf() {}
+    DevBuf(DevBuf&& o) noexcept : p(o.p) { o.p = nullptr; }
+    DevBuf& operator=(DevBuf&& o) noexcept { if (this != &o) { reset(); p = o.p; o.p = nullptr; } return *this; }
+    ~DevBuf() { reset(); }
+    bool alloc(size_t bytes) { reset(); if (hipMalloc(&p, bytes) != hipSuccess) p = nullptr; return p != nullptr; }
+    void reset() { if (p) hipFree(p); p = nullptr; }
+    void* release() { void* q = p; p = nullptr; return q; }
+    template <class T> T* as() const { return (T*)p; }
+};
+
+// the two events around a timed launch, or a fork / join pair (move-only; empty until create())
+struct EventPair {
+    hipEvent_t a = nullptr, b = nullptr;
+    EventPair() {}
+    EventPair(EventPair&& o) noexcept : a(o.a), b(o.b) { o.a = o.b = nullptr; }
+    EventPair& operator=(EventPair&& o) noexcept { if (this != &o) { reset(); a = o.a; b = o.b; o.a = o.b = nullptr; } return *this; }
+    ~EventPair() { reset(); }
+    hipError_t create(unsigned flags = hipEventDefault) {
+        const hipError_t e = hipEventCreateWithFlags(&a, flags);
+        return e != hipSuccess ? e : hipEventCreateWithFlags(&b, flags);
+    }
+    void reset() { if (a) hipEventDestroy(a); if (b) hipEventDestroy(b); a = b = nullptr; }
+};
+
+// a non-blocking stream the holder created (destroyed with it), or one handed in by the caller (left alone)
+struct Stream {
+    hipStream_t s = nullptr;
+    bool owned = false;
+    Stream() {}
+    Stream(const Stream&) = delete;
+    Stream& operator=(const Stream&) = delete;
+    ~Stream() { reset(); }
+    hipError_t create() { reset(); const hipError_t e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking); owned = e == hipSuccess; return e; }
+    void borrow(hipStream_t theirs) { reset(); s = theirs; }
+    void reset() { if (s && owned) hipStreamDestroy(s); s = nullptr; owned = false; }
 };
 
 // The stage read of the C ABI: *count = n always; a null dst only asks for it; else n floats of src go to dst (device to device, on `stream`).

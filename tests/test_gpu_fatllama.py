@@ -151,6 +151,43 @@ def test_three_level_plan_matches_oracle(pack, n, split):
     assert float(np.max(np.abs(got - want))) <= 2e-5 * scale
 
 
+@pytest.mark.parametrize("n,split", [(36864, (8, 2304, 1)), (480000, None)])
+def test_compile_time_schedules_only_with_512_thread_workgroups(pack, n, split):
+    """The compile-time schedules (k_row<., 1> for rows of 2304 points, k_col<., 2> for columns of 625) have one thread per butterfly of a
+    512-thread workgroup.  At EGR_FL_THREADS=256 (and EGR_FL_WL=0, so that the two-barrier kernels are out of the way) a plan whose
+    lengths have such a schedule must run the run-time-schedule kernels instead, exactly as with EGR_FL_SCHED=0: the same bits, and
+    within the float32 oracle's 2e-5 of the peak.  8 x 2304 is the smallest plan whose rows have a compile-time schedule; 480 000
+    samples get the planner's 625 x 384."""
+    from egregora_amd import fatllama_engine as fe
+    if split is None:
+        info = fe.plan_info(n, 1)
+        assert (info["M1"], info["M2"], info["levels"]) == (625, 384, 2), info
+    x = synth(2, n, seed=n)
+
+    def run(env):
+        old = {k: os.environ.get(k) for k in env}
+        os.environ.update(env)
+        try:
+            fe.release_plans()                      # the switches are read when a plan is built
+            y = run_gpu(pack, x, 1, 3, 0.6, split=split)
+            fe.release_plans()
+        finally:
+            for k, v in old.items():
+                if v is None:
+                    os.environ.pop(k, None)
+                else:
+                    os.environ[k] = v
+        return y
+
+    a = run({"EGR_FL_WL": "0", "EGR_FL_THREADS": "256"})
+    b = run({"EGR_FL_WL": "0", "EGR_FL_SCHED": "0", "EGR_FL_THREADS": "256"})
+    np.testing.assert_array_equal(a, b)
+    want = ofl.enhance_channels(x, 1, 3, 0.6, normalize=False, autoscale=False)
+    err, scale = float(np.max(np.abs(a - want))), float(np.max(np.abs(want)))
+    print(f"\nn = {n}, 256 threads: max |device - oracle32| {err:.3e} of peak {scale:.0f} ({err / scale:.2e})")
+    assert err <= 2e-5 * scale
+
+
 @pytest.mark.parametrize("n,split,levels", [(9600000, (1875, 2560, 1), 2), (9600000, None, 3), (19200000, None, 3)])
 def test_long_inputs_wide_columns_and_three_levels(pack, n, split, levels):
     """200 s mono at 48 kHz as two levels with 1875-point outer columns on 4-column tiles (above the 1024 points of an 8-column
