@@ -48,12 +48,13 @@ struct ConvP {
     // kernel from row_amax[m / rows_div] (bits of that row's max |x|, written by the producer or by k_absmax_rows): the scaled
     // maximum lands in [2^14, 2^15), whatever the level of the row, and the result of a row depends on that row alone.
     // out_scale (1 / w_scale; 1 for every other kernel) and the row's inverse scale multiply the accumulators before bias /
-    // residual / activation.
+    // residual / activation.  2 = ONE fp16 term of the same pre-scaled operands: plane 0 of the scheme-1 pack, the same row scales,
+    // out_scale and epilogue; one product per 16 k instead of three (opt-in reduced precision, csrc/egr_s3_split.h).
     int sch;
     float out_scale;
     const unsigned* row_amax;
     int rows_div;
-    // scheme 1, optional: out_amax[m / rows_div] is raised to max |y| over the GEMM rows of each batch row (after bias / residual /
+    // schemes 1 and 2, optional: out_amax[m / rows_div] is raised to max |y| over the GEMM rows of each batch row (after bias / residual /
     // activation) -- the row maxima of y for the NEXT split contraction that reads it, without a pass over y.  Not with split-K.
     unsigned* out_amax;
     // k_conv3x3_is, optional: GroupNorm partial statistics of y -- part[(unit) * (Cout / 4) + quad] = (sum, sum of squares) over the 32
@@ -62,7 +63,7 @@ struct ConvP {
     float2* gn_part;
 };
 
-// scheme 1: the power of two that brings a row whose largest magnitude has the bits `amax_bits` into [2^14, 2^15), and its
+// schemes 1 and 2: the power of two that brings a row whose largest magnitude has the bits `amax_bits` into [2^14, 2^15), and its
 // inverse (both normal floats for every row: the biased exponent e of the maximum is clamped to [15, 254], i.e. rows below 2^-112
 // are treated as 2^-112 -- they are zero for every purpose of the graph -- and inf / nan maxima get a scale that lets them
 // propagate as they would in fp32).  The epilogue applies the inverse and 1 / w_scale as two exact multiplications.
@@ -406,10 +407,11 @@ struct ConvCall : egr_conv_desc {
     ConvCall() : egr_conv_desc() { B = H = W = OH = OW = KH = KW = stride = dil = osy = osx = OHF = OWF = nz = 1; w_scale = 1.f; }
 };
 
-// The weight operand of a call: the two fp16 terms (scheme 1) where x's row maxima over batch_rows rows are given and the weight holds
-// them, else the three bf16 terms where it holds those, else -- or when the call cannot run on the split kernels -- the fp32 pack.
-inline void set_weight(ConvCall& c, const PreparedWeight& w, const unsigned* row_amax, int batch_rows, bool split = true) {
-    if (split && row_amax && w.w2) { c.w3 = w.w2; c.sch = 1; c.w_scale = w.w_scale; c.row_amax = (const float*)row_amax; c.batch_rows = batch_rows; }
+// The weight operand of a call: the two fp16 terms (scheme 1; h_sch = 2: their first plane alone, scheme 2) where x's row maxima over
+// batch_rows rows are given and the weight holds them, else the three bf16 terms where it holds those, else -- or when the call cannot
+// run on the split kernels -- the fp32 pack.
+inline void set_weight(ConvCall& c, const PreparedWeight& w, const unsigned* row_amax, int batch_rows, bool split = true, int h_sch = 1) {
+    if (split && row_amax && w.w2) { c.w3 = w.w2; c.sch = h_sch; c.w_scale = w.w_scale; c.row_amax = (const float*)row_amax; c.batch_rows = batch_rows; }
     else if (split && w.w3) c.w3 = w.w3;
     else c.w = w.w;
 }
@@ -429,7 +431,10 @@ struct ConvChoice {
 // it back (`ran`, optional); the thread's last launch backs egr_conv_last_kernel.
 ConvChoice conv_choose(const ConvP& p);
 std::string conv_choice_name(const ConvChoice& k);
-int conv_call(const ConvCall& c, hipStream_t st, ConvChoice* ran = nullptr);
+// fast_mode: the caller is the FlashSR handle's one-term mode, which runs a scheme-2 call on scheme 1 where h1_pays says the one-term
+// instantiation measured no faster than its two-term twin (the operator API, egr_conv_h1, always runs what it is asked for)
+int conv_call(const ConvCall& c, hipStream_t st, ConvChoice* ran = nullptr, bool fast_mode = false);
+bool h1_pays(const ConvChoice& k);
 // 4 KiB of zeros on the current device (created on first use, one per device)
 int zero_page(const float** out);
 
@@ -442,7 +447,7 @@ void launch_conv_s3(const ConvChoice& k, hipStream_t st, const ConvP& p);
 // input-stationary stride-1 1-D convolution (k_conv1d_s3): false when the shape does not qualify, else k holds the instantiation
 bool conv1d_s3_applies(const ConvP& p, ConvChoice& k);
 void launch_conv1d_s3(const ConvChoice& k, hipStream_t st, const ConvP& p);
-// egr_nn_conv3x3.hip: input-stationary 3x3 convolution of big images (k_conv3x3_isp, scheme 1; optional fused input GroupNorm)
+// egr_nn_conv3x3.hip: input-stationary 3x3 convolution of big images (k_conv3x3_isp, scheme 1; k_conv3x3_isp<..., 2>, scheme 2; optional fused input GroupNorm)
 bool conv3x3_is_applies(const ConvP& p, ConvChoice& k);
 void launch_conv3x3_is(const ConvChoice& k, hipStream_t st, const ConvP& p);
 // egr_nn_amp.hip: the instantiation egr_amp_unit_h2 launches, spelled as conv_choice_name spells the convolutions

@@ -214,7 +214,12 @@ struct egr_flashsr {
     // through tile choices; no value can leave fp16's range (the scale comes from the row's own maximum), so there is nothing to
     // verify or re-run, and the call is as asynchronous as the bf16 one.
     bool h2 = true;                                   // scheme available (off: EGR_FSR_SPLIT_BF16X3, EGREGORA_FLASHSR_SPLIT=bf16x3, f32 MFMA)
-    bool h2_fwd = false;                              // egr_flashsr_forward too runs the fp16 terms (set_split 2: stage taps for tests)
+    bool h2_fwd = false;                              // egr_flashsr_forward too runs the fp16 terms (set_split 2 / 4: stage taps for tests)
+    // Fast mode (EGR_FSR_FAST_F16, EGREGORA_FLASHSR_SPLIT=f16x1, set_split 3 / 4): the contractions the fp16 scheme serves run on ONE
+    // fp16 term per operand (scheme 2: plane 0 of the same packs, the same row maxima and scales, the same graph walk) -- except the
+    // fused AMP unit, the thin-end kernels and the attention products, which stay as they are, and the instantiations whose one-term
+    // form measured no faster (egr::h1_pays): those launches keep scheme 1.  Reduced precision, opt-in.
+    bool h1 = false;
     int h2_nweights = 0;                              // contraction weights that hold fp16 terms
     bool out_amax_on = true;                          // contraction epilogues leave the row maxima of their outputs (EGREGORA_FLASHSR_OUT_AMAX=0: off)
     int direct3x3_max_cout = 128;                     // EGREGORA_FLASHSR_DIRECT3X3_MAX_COUT (0: off): see gn_conv3
@@ -240,11 +245,12 @@ struct Fwd {
     hipStream_t st;                    // = cx->st
     int R;                             // batch rows
     bool h2;                           // runs the fp16 operand terms (else three bf16 terms)
+    int h_sch;                         // ... two of them per operand (1) or, in the handle's fast mode, one (2)
     std::vector<ProfRec>* prof;        // where timed launches are recorded, up to prof_level (0: nowhere)
     int prof_level;
     double* flops;                     // sum of contraction flops as executed, or null
     Fwd(const M& model, FsrCtx* c, int rows, bool fp16_terms, std::vector<ProfRec>* rec = nullptr, int level = 0, double* flop_sum = nullptr)
-        : m(model), cx(c), st(c->st), R(rows), h2(fp16_terms), prof(rec), prof_level(rec ? level : 0), flops(flop_sum) {}
+        : m(model), cx(c), st(c->st), R(rows), h2(fp16_terms), h_sch(model.h1 ? 2 : 1), prof(rec), prof_level(rec ? level : 0), flops(flop_sum) {}
     void count(double fl) { if (flops) *flops += fl; }
 };
 
@@ -523,8 +529,8 @@ int s3_launch(Fwd& f, const Wt* w, const std::string& key, ConvCall& c, int64_t 
             c.out_amax = (float*)*y_rs;
         }
     }
-    egr::set_weight(c, *w, use ? *x_rs : nullptr, f.R, split);
-    return egr::conv_call(c, f.st, ran);
+    egr::set_weight(c, *w, use ? *x_rs : nullptr, f.R, split, f.h_sch);
+    return egr::conv_call(c, f.st, ran, true);
 }
 
 // general convolution described by `c`: the caller fills geometry, epilogue and any explicit bias / residual by name; conv() allocates
@@ -737,9 +743,9 @@ int gn_conv3(Fwd& f, Ten& y, const Ten& x, const std::string& norm_key, float ep
             ConvCall c;
             c.x = x.p; c.bias = bt; c.res = res; c.y = y.p; c.gn_scale = sc.p; c.gn_shift = sh.p; c.gn_silu = 1;
             c.B = B; c.H = c.OH = c.OHF = H; c.W = c.OW = c.OWF = W; c.Cin = Cin; c.Cout = wd->Cout; c.KH = c.KW = 3; c.pad_t = c.pad_l = 1;
-            egr::set_weight(c, *wd, bound, B);
+            egr::set_weight(c, *wd, bound, B, true, f.h_sch);
             c.out_amax = (float*)y.rs; c.gn_part = gpart;
-            return timed(f, 2.0 * B * H * W * (double)wd->Cout * 9 * Cin, conv_key.c_str(), [&](ConvChoice* ran) { return egr::conv_call(c, f.st, ran); });
+            return timed(f, 2.0 * B * H * W * (double)wd->Cout * 9 * Cin, conv_key.c_str(), [&](ConvChoice* ran) { return egr::conv_call(c, f.st, ran, true); });
         }
     }
     const bool wino = f.m.has(conv_key + ".weight.wino") && H % 2 == 0 && W % 2 == 0;
@@ -1283,6 +1289,8 @@ extern "C" int egr_flashsr_create(egr_flashsr** out, const egr_flashsr_config* c
               cfg->voc_n_rates >= 1 && cfg->voc_n_rates <= EGR_FSR_MAX && cfg->voc_n_kernels >= 1 && cfg->voc_n_kernels <= EGR_FSR_MAX &&
               cfg->voc_n_dils >= 1 && cfg->voc_n_dils <= EGR_FSR_MAX && cfg->unet_n_attn >= 0 && cfg->unet_n_attn <= EGR_FSR_MAX,
               EGR_ERR_ARG, "egr_flashsr_config: level / rate counts out of range");
+    EGR_CHECK(!(flags & EGR_FSR_FAST_F16) || !(flags & (EGR_FSR_F32_MFMA | EGR_FSR_SPLIT_BF16X3)), EGR_ERR_ARG,
+              "egr_flashsr_create: EGR_FSR_FAST_F16 runs on the fp16 weight terms, which EGR_FSR_F32_MFMA / EGR_FSR_SPLIT_BF16X3 do not keep");
     egr_flashsr* m = new egr_flashsr();
     m->cfg = *cfg;
     m->flags = flags;
@@ -1292,7 +1300,11 @@ extern "C" int egr_flashsr_create(egr_flashsr** out, const egr_flashsr_config* c
     if (const char* e = getenv("EGREGORA_FLASHSR_STREAMS")) { const int g = atoi(e); if (g >= 1 && g <= 4) m->max_groups = g; }
     if (const char* e = getenv("EGREGORA_FLASHSR_WINOGRAD_MIN_CH")) m->wino_min_ch = atoi(e);
     m->h2 = !(flags & (EGR_FSR_F32_MFMA | EGR_FSR_SPLIT_BF16X3));
-    if (const char* e = getenv("EGREGORA_FLASHSR_SPLIT")) { if (!strcmp(e, "bf16x3")) m->h2 = false; }
+    if (const char* e = getenv("EGREGORA_FLASHSR_SPLIT")) {
+        if (!strcmp(e, "bf16x3")) m->h2 = false;
+        else if (!strcmp(e, "f16x1") && m->h2) m->flags |= EGR_FSR_FAST_F16;     // (a handle without fp16 terms cannot run the mode: its flags decide)
+    }
+    m->h1 = m->h2 && (m->flags & EGR_FSR_FAST_F16) != 0;
     if (const char* e = getenv("EGREGORA_FLASHSR_ROWS")) { const int r = atoi(e); if (r >= 1) m->rows_per_pass = r; }
     if (const char* e = getenv("EGREGORA_FLASHSR_OUT_AMAX")) m->out_amax_on = atoi(e) != 0;
     if (const char* e = getenv("EGREGORA_FLASHSR_DIRECT3X3_MAX_COUT")) m->direct3x3_max_cout = atoi(e);
@@ -1483,12 +1495,21 @@ extern "C" int egr_flashsr_split_info(egr_flashsr* m, int* enabled, int* weights
 }
 
 // scheme: 0 = three bf16 terms always, 1 = two fp16 terms with per-row device-side scales in egr_flashsr_infer (needs a handle
-// created with the scheme available), 2 = as 1 and egr_flashsr_forward runs the fp16 terms as well (stage taps for tests)
+// created with the scheme available), 2 = as 1 and egr_flashsr_forward runs the fp16 terms as well (stage taps for tests);
+// 3 = one fp16 term (the fast mode) in egr_flashsr_infer, 4 = as 3 and in egr_flashsr_forward.  The fp16 pack serves 1 .. 4: no repacking.
 extern "C" int egr_flashsr_set_split(egr_flashsr* m, int scheme) {
-    EGR_CHECK(m && scheme >= 0 && scheme <= 2, EGR_ERR_ARG, "bad argument");
+    EGR_CHECK(m && scheme >= 0 && scheme <= 4, EGR_ERR_ARG, "bad argument");
     EGR_CHECK(scheme == 0 || m->h2_nweights > 0, EGR_ERR_UNSUPPORTED, "this handle holds no fp16 weight terms");
     m->h2 = scheme >= 1;
-    m->h2_fwd = scheme == 2;
+    m->h2_fwd = scheme == 2 || scheme == 4;
+    m->h1 = scheme >= 3;
+    return EGR_OK;
+}
+
+// the value egr_flashsr_set_split would have to be given to reach the handle's current state
+extern "C" int egr_flashsr_split_scheme(egr_flashsr* m, int* scheme) {
+    EGR_CHECK(m && scheme, EGR_ERR_ARG, "null argument");
+    *scheme = !m->h2_ready() ? 0 : (m->h1 ? 3 : 1) + (m->h2_fwd ? 1 : 0);
     return EGR_OK;
 }
 

@@ -41,11 +41,15 @@ namespace egr {
 // operand ds_read_b128 per MFMA, and ONE workgroup barrier per channel chunk (the patch hand-over) instead of one per slab: 4 instead of
 // 72.  3.52 -> 3.39 ms per 26-row layer stand-alone, same bits (profiles/r06/conv3x3_weights_in_registers.txt); the kernel runs at the
 // board's power limit like the GEMM, so what it bought is the energy of the LDS traffic it no longer makes.
-template <int BN, int CC, bool GN, bool SILU>
-__global__ __launch_bounds__(256, 2) void k_conv3x3_isp(ConvP p) {
+// SCH: operand scheme, 1 (two fp16 terms) or 2 (one: the patch is split into one plane and a slab keeps ONE weight-fragment register
+// set, plane 0 of the same pack; same phase schedule).  The body is shared; the kernels below are its two entry points: the
+// two-term kernel keeps the name it has in every profile, the one-term kernel carries its scheme as k_conv_s3 does.
+template <int BN, int CC, bool GN, bool SILU, int SCH>
+__device__ __forceinline__ void conv3x3_isp_body(const ConvP& p) {
     typedef S3Cfg<128, BN> TC;
     constexpr int TM = TC::TM, TN = TC::TN, NCH = CC / 8, NSL = CC / 16, PW = 34, PR = 6, RMAX = PR * PW;
-    constexpr int NP = 2, NIT = (RMAX * NCH + 255) / 256, SPC = 9 * NSL;      // SPC: slabs per chunk
+    constexpr int NP = s3_planes<SCH>(), NIT = (RMAX * NCH + 255) / 256, SPC = 9 * NSL;      // SPC: slabs per chunk
+    constexpr int NT = NP * (NP + 1) / 2;                 // products per sub-tile pair and slab: 3 (two terms) or 1
     static_assert(CC == 32 && NIT == 4 && 256 % NCH == 0 && SPC % 2 == 0, "four patch items per thread, all of one 8-channel group");
     __shared__ uint4 As[2][NP][RMAX * NCH + 8];           // (+ 8 dump slots: threads without a fourth patch item store there, branch-free)
     __shared__ float os_tab[128];
@@ -74,7 +78,7 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_isp(ConvP p) {
     f32x16 acc[TM][TN];
     zero_acc(acc);
 
-    const size_t b_slab = (size_t)p.Cout * 2 * NP;     // 16-byte chunks of one 16-k slab of the weight pack
+    const size_t b_slab = (size_t)p.Cout * 2 * s3_pack_planes<SCH>();     // 16-byte chunks of one 16-k slab of the weight pack
     const int cpt = p.Cin / 16;                  // slabs per tap in the weight pack
     const uint4* zq = (const uint4*)p.zeros;
     const int nchunks = p.Cin / CC;
@@ -138,9 +142,9 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_isp(ConvP p) {
 #pragma unroll
         for (int q = 0; q < 8; ++q) x[q] = ok ? x[q] : 0.f;  // zero padding applies AFTER the normalisation
         uint4 q[3];
-        split_x8<1>(make_float4(x[0], x[1], x[2], x[3]), make_float4(x[4], x[5], x[6], x[7]), a_scale, q);
+        split_x8<SCH>(make_float4(x[0], x[1], x[2], x[3]), make_float4(x[4], x[5], x[6], x[7]), a_scale, q);
         As[abuf][0][slot] = q[0];
-        As[abuf][1][slot] = q[1];
+        if constexpr (NP > 1) As[abuf][1][slot] = q[1];
     };
 
     // slab S (compile-time) of chunk cc: tap S / 2, 16-k half S % 2; multiplies the weight fragments of register buffer S & 1 with patch
@@ -170,14 +174,14 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_isp(ConvP p) {
         if (S == 8) halo_finish(hu2, hv2, hok2, hslot2, cc + 1, ab ^ 1);
         if (S == 10) halo_finish(hu3, hv3, hok3, hslot3, cc + 1, ab ^ 1);
         // weights as the first operand: transposed accumulators, 16-byte stores (conv_epilogue_t)
-        mma_terms<1, true, TM, TN>(aq, bq, acc);
+        mma_terms<SCH, true, TM, TN>(aq, bq, acc);
         if (S == 4 || S == 6 || S == 8 || S == 10) {
             // the item's ~70 VALU / transcendental instructions go BETWEEN the slab's MFMAs, six per MFMA (the machine scheduler
             // otherwise issues them as one block in front: ~350 cycles in which this wave feeds nothing to the matrix pipe)
 #pragma unroll
-            for (int k = 0; k < TM * TN * 3; ++k) {
+            for (int k = 0; k < TM * TN * NT; ++k) {         // (one term: a third of the MFMAs, three times the share each)
                 __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(0x402, 6, 0);
+                __builtin_amdgcn_sched_group_barrier(0x402, 18 / NT, 0);
             }
         }
     };
@@ -202,7 +206,13 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3_isp(ConvP p) {
     if (om) out_amax_commit(p, om_tab, (b * p.H + y0) * p.W + x0, 1);
 }
 
-// true when the input-stationary 3x3 kernel applies (scheme 1, big images, Cin <= 512, one image < 2^31 elements): k then holds its
+template <int BN, int CC, bool GN, bool SILU>
+__global__ __launch_bounds__(256, 2) void k_conv3x3_isp(ConvP p) { conv3x3_isp_body<BN, CC, GN, SILU, 1>(p); }
+// the one-term form: an overload with the scheme as a fifth parameter, k_conv3x3_isp<BN, 32, GN, SILU, 2>
+template <int BN, int CC, bool GN, bool SILU, int SCH>
+__global__ __launch_bounds__(256, 2) void k_conv3x3_isp(ConvP p) { static_assert(SCH == 2, "the two-term kernel is the four-parameter one"); conv3x3_isp_body<BN, CC, GN, SILU, SCH>(p); }
+
+// true when the input-stationary 3x3 kernel applies (schemes 1 and 2, big images, Cin <= 512, one image < 2^31 elements): k then holds its
 // instantiation and grid
 bool conv3x3_is_applies(const ConvP& p, ConvChoice& k) {
     static const bool off = getenv("EGR_S3_CONV3X3") && atoi(getenv("EGR_S3_CONV3X3")) == 0;
@@ -221,7 +231,10 @@ bool conv3x3_is_applies(const ConvP& p, ConvChoice& k) {
 
 void launch_conv3x3_is(const ConvChoice& k, hipStream_t st, const ConvP& p) {
 #define C3_LAUNCH(GN_, SILU_)                                                                                        \
-    if (k.bn == 128) hipLaunchKernelGGL((k_conv3x3_isp<128, 32, GN_, SILU_>), k.grid, dim3(256), 0, st, p);          \
+    if (k.sch == 2) {                                                                                                \
+        if (k.bn == 128) hipLaunchKernelGGL((k_conv3x3_isp<128, 32, GN_, SILU_, 2>), k.grid, dim3(256), 0, st, p);     \
+        else hipLaunchKernelGGL((k_conv3x3_isp<64, 32, GN_, SILU_, 2>), k.grid, dim3(256), 0, st, p);                  \
+    } else if (k.bn == 128) hipLaunchKernelGGL((k_conv3x3_isp<128, 32, GN_, SILU_>), k.grid, dim3(256), 0, st, p);   \
     else hipLaunchKernelGGL((k_conv3x3_isp<64, 32, GN_, SILU_>), k.grid, dim3(256), 0, st, p)
     if (k.silu) { C3_LAUNCH(true, true); }
     else if (k.gn) { C3_LAUNCH(true, false); }

@@ -492,10 +492,11 @@ __global__ void k_spin(long long ticks, unsigned* sink) {
 static int conv_check(const ConvCall& c) {
     EGR_CHECK(c.x && (c.w || c.w3) && c.y, EGR_ERR_ARG, "null x/w/y");
     EGR_CHECK(c.nz >= 1 && c.nz <= 65535, EGR_ERR_ARG, "bad nz");
-    EGR_CHECK(c.sch == 0 || (c.w3 && c.w_scale > 0.f && c.row_amax && c.batch_rows >= 1 && ((long long)c.B * c.OH * c.OW) % c.batch_rows == 0),
+    EGR_CHECK(c.sch >= 0 && c.sch <= 2, EGR_ERR_ARG, "bad operand scheme %d: 0 (three bf16 terms), 1 (two fp16 terms) or 2 (one fp16 term)", c.sch);
+    EGR_CHECK(c.sch == 0 || (c.w3 &&c.w_scale > 0.f && c.row_amax && c.batch_rows >= 1 && ((long long)c.B * c.OH * c.OW) % c.batch_rows == 0),
               EGR_ERR_ARG, "bad operand scheme: needs w_scale > 0, row_amax and a batch row count that divides the GEMM rows");
-    EGR_CHECK(!c.w3 || ((c.Cin % BK) == 0 && (((uintptr_t)c.x) & 15) == 0 && (((uintptr_t)c.w3) & 15) == 0 && (!c.gn_scale || c.sch == 1)), EGR_ERR_ARG,
-              "split conv needs Cin %% 16 == 0, 16-byte aligned x / w3 and no fused input affine (scheme 1: only the input-stationary 3x3 kernel fuses one)");
+    EGR_CHECK(!c.w3 || ((c.Cin % BK) == 0 && (((uintptr_t)c.x) & 15) == 0 && (((uintptr_t)c.w3) & 15) == 0 && (!c.gn_scale || c.sch >= 1)), EGR_ERR_ARG,
+              "split conv needs Cin %% 16 == 0, 16-byte aligned x / w3 and no fused input affine (schemes 1, 2: only the input-stationary 3x3 kernel fuses one)");
     EGR_CHECK(!c.gn_scale || (c.gn_shift && (c.Cin % BK) == 0 && (((uintptr_t)c.x) & 15) == 0), EGR_ERR_ARG,
               "fused input affine needs Cin %% 16 == 0 and a 16-byte aligned input");
     EGR_CHECK(c.B >= 1 && c.H >= 1 && c.W >= 1 && c.Cin >= 1 && c.OH >= 1 && c.OW >= 1 && c.Cout >= 1 && c.KH >= 1 && c.KW >= 1 && c.stride >= 1 &&
@@ -579,7 +580,7 @@ std::string conv_choice_name(const ConvChoice& k) {
         case CONV_IGEMM: snprintf(b, sizeof(b), "k_conv_igemm<%d, %s, %s>", k.bn, tf(k.vec), tf(k.gn)); break;
         case CONV_S3: snprintf(b, sizeof(b), "k_conv_s3<%d, %d, %d, %s, %d>", k.bm, k.bn, k.pf, tf(k.zs), k.sch); break;
         case CONV1D_S3: snprintf(b, sizeof(b), "k_conv1d_s3<%d, %d, %d>", k.bn, k.cc, k.sch); break;
-        case CONV3X3_IS: snprintf(b, sizeof(b), "k_conv3x3_isp<%d, 32, %s, %s>", k.bn, tf(k.gn), tf(k.silu)); break;
+        case CONV3X3_IS: snprintf(b, sizeof(b), "k_conv3x3_isp<%d, 32, %s, %s%s>", k.bn, tf(k.gn), tf(k.silu), k.sch == 2 ? ", 2" : ""); break;
     }
     return b;
 }
@@ -592,7 +593,7 @@ static int conv_resolve(const ConvCall& c, ConvP& p, ConvChoice& k) {
     p = conv_params(c);
     k = conv_choose(p);
     if (k.family == CONV_NONE) {
-        set_error("egr_conv_h2_gn: the shape does not qualify for the input-stationary 3x3 kernel (stride 1, pad 1, H %% 4 == 0, W %% 32 == 0, "
+        set_error("egr_conv_h2_gn / egr_conv_h1_gn: the shape does not qualify for the input-stationary 3x3 kernel (stride 1, pad 1, H %% 4 == 0, W %% 32 == 0, "
                   "Cin %% 32 == 0, >= 512 tiles, one batch row per image)");
         return EGR_ERR_UNSUPPORTED;
     }
@@ -601,9 +602,15 @@ static int conv_resolve(const ConvCall& c, ConvP& p, ConvChoice& k) {
     return EGR_OK;
 }
 
-int conv_call(const ConvCall& c, hipStream_t st, ConvChoice* ran) {
+// One-term instantiations that were NOT faster than their two-term twins by more than the twins' own run-to-run spread, interleaved
+// inside a full-size 13-row forward (profiles/flashsr_fast.md, tools/flashsr_fast_measure.py): the 128 x 64 implicit-GEMM tile -- the
+// transformer blocks' short-K linears, 20 us launches that end before the matrix pipe matters (0.0205 against 0.0203 ms, spread 0.0003).
+bool h1_pays(const ConvChoice& k) { return !(k.family == CONV_S3 && k.bm == 128 && k.bn == 64 && !k.zs); }
+
+int conv_call(const ConvCall& c, hipStream_t st, ConvChoice* ran, bool fast_mode) {
     ConvP p; ConvChoice k;
     { const int rc = conv_resolve(c, p, k); if (rc) return rc; }
+    if (fast_mode && k.sch == 2 && !h1_pays(k)) k.sch = p.sch = 1;     // (same pack, same row maxima, same tile: only the instantiation differs)
     p.ksplit = k.ksplit; p.kt_per = k.kt_per; p.zs_nzb = k.zs_nzb;
     { const int rc = zero_page(&p.zeros); if (rc) return rc; }     // (every kernel below reads padded / out-of-range rows from it)
     if (k.ksplit > 1) { const int rc = splitk_workspace((size_t)k.ksplit * p.M * p.Cout * sizeof(float), st, &p.ws); if (rc) return rc; }
@@ -708,11 +715,11 @@ extern "C" int egr_conv_s3(const float* x, const void* w3, const float* bias, co
 
 // The same on two fp16 terms per operand (csrc/egr_nn_gemm_s3.hip, scheme 1): w2 = egr_split2h_pack(w, w_scale); the scales of the
 // batch rows are derived in the kernel from row_amax (include/egregora_amd.h has the contract).
-extern "C" int egr_conv_h2(const float* x, const void* w2, const float* bias, const float* bias_b, const float* res, float* y,
-                           int B, int H, int W, int Cin, int OH, int OW, int Cout, int KH, int KW, int stride, int dil,
-                           int pad_t, int pad_l, int up2, int act, float act_param, int osy, int osx, int ooy, int oox,
-                           int OHF, int OWF, int nz, int64_t zx, int64_t zw2, int64_t zy, float w_scale, const float* row_amax,
-                           int batch_rows, float* out_amax, void* stream) {
+static int conv_h(int sch, const float* x, const void* w2, const float* bias, const float* bias_b, const float* res, float* y,
+                  int B, int H, int W, int Cin, int OH, int OW, int Cout, int KH, int KW, int stride, int dil,
+                  int pad_t, int pad_l, int up2, int act, float act_param, int osy, int osx, int ooy, int oox,
+                  int OHF, int OWF, int nz, int64_t zx, int64_t zw2, int64_t zy, float w_scale, const float* row_amax,
+                  int batch_rows, float* out_amax, void* stream) {
     EGR_CHECK(w2 && row_amax, EGR_ERR_ARG, "null w2 / row_amax");
     ConvCall c;
     c.x = x; c.w3 = w2; c.bias = bias; c.bias_b = bias_b; c.res = res; c.y = y;
@@ -720,21 +727,54 @@ extern "C" int egr_conv_h2(const float* x, const void* w2, const float* bias, co
     c.stride = stride; c.dil = dil; c.pad_t = pad_t; c.pad_l = pad_l; c.up2 = up2; c.act = act; c.act_param = act_param;
     c.osy = osy; c.osx = osx; c.ooy = ooy; c.oox = oox; c.OHF = OHF; c.OWF = OWF;
     c.nz = nz; c.zx = zx; c.zw = zw2; c.zy = zy;
-    c.sch = 1; c.w_scale = w_scale; c.row_amax = row_amax; c.batch_rows = batch_rows; c.out_amax = out_amax;
+    c.sch = sch; c.w_scale = w_scale; c.row_amax = row_amax; c.batch_rows = batch_rows; c.out_amax = out_amax;
     return conv_call(c, (hipStream_t)stream);
+}
+
+extern "C" int egr_conv_h2(const float* x, const void* w2, const float* bias, const float* bias_b, const float* res, float* y,
+                           int B, int H, int W, int Cin, int OH, int OW, int Cout, int KH, int KW, int stride, int dil,
+                           int pad_t, int pad_l, int up2, int act, float act_param, int osy, int osx, int ooy, int oox,
+                           int OHF, int OWF, int nz, int64_t zx, int64_t zw2, int64_t zy, float w_scale, const float* row_amax,
+                           int batch_rows, float* out_amax, void* stream) {
+    return conv_h(1, x, w2, bias, bias_b, res, y, B, H, W, Cin, OH, OW, Cout, KH, KW, stride, dil, pad_t, pad_l, up2, act, act_param, osy, osx, ooy,
+                  oox, OHF, OWF, nz, zx, zw2, zy, w_scale, row_amax, batch_rows, out_amax, stream);
+}
+
+// The same call on ONE fp16 term per operand (scheme 2: plane 0 of the same w2 pack, a third of the matrix instructions; opt-in
+// reduced precision, include/egregora_amd.h).
+extern "C" int egr_conv_h1(const float* x, const void* w2, const float* bias, const float* bias_b, const float* res, float* y,
+                           int B, int H, int W, int Cin, int OH, int OW, int Cout, int KH, int KW, int stride, int dil,
+                           int pad_t, int pad_l, int up2, int act, float act_param, int osy, int osx, int ooy, int oox,
+                           int OHF, int OWF, int nz, int64_t zx, int64_t zw2, int64_t zy, float w_scale, const float* row_amax,
+                           int batch_rows, float* out_amax, void* stream) {
+    return conv_h(2, x, w2, bias, bias_b, res, y, B, H, W, Cin, OH, OW, Cout, KH, KW, stride, dil, pad_t, pad_l, up2, act, act_param, osy, osx, ooy,
+                  oox, OHF, OWF, nz, zx, zw2, zy, w_scale, row_amax, batch_rows, out_amax, stream);
 }
 
 // 3x3 stride-1 pad-1 convolution on two fp16 terms with the producer's GroupNorm (+ SiLU) applied to x while it is loaded; only the
 // input-stationary kernel (k_conv3x3_isp) serves it, else EGR_ERR_UNSUPPORTED with nothing launched (contract: include/egregora_amd.h).
-extern "C" int egr_conv_h2_gn(const float* x, const float* gn_scale, const float* gn_shift, int gn_silu, const void* w2, const float* bias,
-                              const float* res, float* y, int B, int H, int W, int Cin, int Cout, int act, float w_scale, const float* row_amax,
-                              float* out_amax, void* gn_part, void* stream) {
+static int conv_h_gn(int sch, const float* x, const float* gn_scale, const float* gn_shift, int gn_silu, const void* w2, const float* bias,
+                     const float* res, float* y, int B, int H, int W, int Cin, int Cout, int act, float w_scale, const float* row_amax,
+                     float* out_amax, void* gn_part, void* stream) {
     EGR_CHECK(w2 && row_amax && gn_scale && gn_shift, EGR_ERR_ARG, "null w2 / row_amax / gn_scale / gn_shift");
     ConvCall c;
     c.x = x; c.w3 = w2; c.bias = bias; c.res = res; c.y = y; c.gn_scale = gn_scale; c.gn_shift = gn_shift; c.gn_silu = gn_silu;
     c.B = B; c.H = c.OH = c.OHF = H; c.W = c.OW = c.OWF = W; c.Cin = Cin; c.Cout = Cout; c.KH = c.KW = 3; c.pad_t = c.pad_l = 1; c.act = act;
-    c.sch = 1; c.w_scale = w_scale; c.row_amax = row_amax; c.batch_rows = B; c.out_amax = out_amax; c.gn_part = gn_part;
+    c.sch = sch; c.w_scale = w_scale; c.row_amax = row_amax; c.batch_rows = B; c.out_amax = out_amax; c.gn_part = gn_part;
     return conv_call(c, (hipStream_t)stream);
+}
+
+extern "C" int egr_conv_h2_gn(const float* x, const float* gn_scale, const float* gn_shift, int gn_silu, const void* w2, const float* bias,
+                              const float* res, float* y, int B, int H, int W, int Cin, int Cout, int act, float w_scale, const float* row_amax,
+                              float* out_amax, void* gn_part, void* stream) {
+    return conv_h_gn(1, x, gn_scale, gn_shift, gn_silu, w2, bias, res, y, B, H, W, Cin, Cout, act, w_scale, row_amax, out_amax, gn_part, stream);
+}
+
+// egr_conv_h2_gn on one fp16 term per operand (k_conv3x3_isp<..., 2>); refused for the same shapes
+extern "C" int egr_conv_h1_gn(const float* x, const float* gn_scale, const float* gn_shift, int gn_silu, const void* w2, const float* bias,
+                              const float* res, float* y, int B, int H, int W, int Cin, int Cout, int act, float w_scale, const float* row_amax,
+                              float* out_amax, void* gn_part, void* stream) {
+    return conv_h_gn(2, x, gn_scale, gn_shift, gn_silu, w2, bias, res, y, B, H, W, Cin, Cout, act, w_scale, row_amax, out_amax, gn_part, stream);
 }
 
 extern "C" int egr_bgemm(const float* a, const float* b, float* c, int nb1, int nb2, int M, int N, int K, int lda,

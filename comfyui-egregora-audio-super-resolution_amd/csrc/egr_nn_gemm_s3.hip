@@ -109,7 +109,7 @@ __global__ __launch_bounds__(256, 2) void k_conv_s3(ConvP p) {
     typedef S3Cfg<BM, BN> TC;
     constexpr int TM = TC::TM, TN = TC::TN;
     constexpr int AP = BM / 128;                                  // A chunks (8 k of one row) per thread per slab
-    constexpr int NP = SCH ? 2 : 3;                               // operand planes (terms of the split)
+    constexpr int NP = s3_planes<SCH>();                          // operand planes (terms of the split)
     __shared__ uint4 As[2][NP][BM * 2];
     __shared__ uint4 Bs[2][NP][BN * 2];
     __shared__ float os_tab[SCH ? BM : 1];                        // scheme 1: output scale of every row of the block tile
@@ -144,8 +144,8 @@ __global__ __launch_bounds__(256, 2) void k_conv_s3(ConvP p) {
     // ---- A: thread owns 8 consecutive k (half ah) of tile rows ar (and ar + 128 when BM = 256) ----
     // (plain scalars on purpose: arrays captured by the lambdas below end up in scratch)
     const int ar = tid >> 1, ah = tid & 1;
-    float a_scale0 = 1.f, a_scale1 = 1.f;                         // scheme 1: the operand scales of this thread's rows
-    if constexpr (SCH == 1) {
+    float a_scale0 = 1.f, a_scale1 = 1.f;                         // schemes 1, 2: the operand scales of this thread's rows
+    if constexpr (SCH != 0) {
         for (int r = tid; r < BM; r += 256) {
             os_tab[r] = h2_row_inv(p.row_amax[(size_t)(min(m0 + r, p.M - 1) / p.rows_div) * EGR_ROW_AMAX_STRIDE]);
             om_tab[r] = 0u;
@@ -207,7 +207,7 @@ __global__ __launch_bounds__(256, 2) void k_conv_s3(ConvP p) {
 
     // ---- B: 2*NP*BN 16-byte chunks per slab (NP planes x BN channels x 2 halves), up to 6 per thread ----
     constexpr int NBQ = 2 * NP * BN;
-    const size_t b_slab = (size_t)p.Cout * 2 * NP;               // uint4 per slab
+    const size_t b_slab = (size_t)p.Cout * 2 * s3_pack_planes<SCH>();   // uint4 per slab (scheme 2: plane 0 of the two-plane pack)
 #define S3_BSETUP(I, PTR, STEP, SLOT)                                                                                \
     const uint4* PTR;                                                                                                \
     unsigned STEP;                                                                                                   \
@@ -331,15 +331,15 @@ __global__ __launch_bounds__(256, 2) void k_conv_s3(ConvP p) {
             const int done = kt + 1;
             const int zl = done / ktiles_all;
             if (done - zl * ktiles_all == 0) {
-                store_tile_plain<TM, TN, SCH == 1>(p, acc, p.y + (size_t)(zl - 1) * p.zy, m0, n0, wm0, wn0, os_tab);
+                store_tile_plain<TM, TN, SCH != 0>(p, acc, p.y + (size_t)(zl - 1) * p.zy, m0, n0, wm0, wn0, os_tab);
                 zero_acc(acc);
             }
         }
         __syncthreads();
     };
 
-    if constexpr (SCH == 1 && TM <= 2 && BM == 128) {
-        // fp16 scheme, 128-row tiles: with half the matrix work per slab the loop was bound by the latency of the activation loads
+    if constexpr (SCH != 0 && TM <= 2 && BM == 128) {
+        // fp16 schemes, 128-row tiles: with half the matrix work per slab the loop was bound by the latency of the activation loads
         // (every A line is read by one workgroup only -- an HBM / MALL miss -- and had one slab to arrive).  Here the A tile is
         // requested TWO slabs ahead through two alternating register sets (8 registers each) and the weight tile, an L2 hit shared
         // by every row tile, one slab ahead; B is issued before A so that the wait for B (vmcnt counts in order) leaves the newer A
@@ -373,10 +373,10 @@ __global__ __launch_bounds__(256, 2) void k_conv_s3(ConvP p) {
         };
         auto storeA = [&](const SA& ra, int buf) {
             uint4 q[3];
-            split_x8<1>(ra.a0, ra.a1, a_scale0, q);
+            split_x8<SCH>(ra.a0, ra.a1, a_scale0, q);
             {
             As[buf][0][a_slot] = q[0];
-            As[buf][1][a_slot] = q[1];
+            if constexpr (NP > 1) As[buf][1][a_slot] = q[1];
             }
         };
         auto storeB = [&](const SB& rb, int buf) {
@@ -398,9 +398,9 @@ __global__ __launch_bounds__(256, 2) void k_conv_s3(ConvP p) {
 #pragma unroll
             for (int i = 0; i < TM; ++i)
 #pragma unroll
-                for (int q = 0; q < 2; ++q) a[i][q] = As[cur][q][(wm0 + i * 32) * 2 + o_slot];
+                for (int q = 0; q < NP; ++q) a[i][q] = As[cur][q][(wm0 + i * 32) * 2 + o_slot];
 #pragma unroll
-            for (int q = 0; q < 2; ++q) b[0][q] = Bs[cur][q][wn0 * 2 + o_slot];
+            for (int q = 0; q < NP; ++q) b[0][q] = Bs[cur][q][wn0 * 2 + o_slot];
             // The weight tile needs no arithmetic: it goes to LDS and its successor is requested before anything else (pinned: the
             // machine scheduler otherwise sinks the requests below the MFMAs).  The activation tile's split, its LDS stores and the
             // request for A(t+3) are left to the scheduler to spread over the MFMAs: that request has two slabs to land, so it may
@@ -422,10 +422,12 @@ __global__ __launch_bounds__(256, 2) void k_conv_s3(ConvP p) {
             for (int j = 0; j < TN; ++j) {
                 if (j + 1 < TN) {
 #pragma unroll
-                    for (int q = 0; q < 2; ++q) b[(j + 1) & 1][q] = Bs[cur][q][(wn0 + (j + 1) * 32) * 2 + o_slot];
+                    for (int q = 0; q < NP; ++q) b[(j + 1) & 1][q] = Bs[cur][q][(wn0 + (j + 1) * 32) * 2 + o_slot];
                 }
-                mma_term<1, true, 1, 0, TM, 1>(a, b + (j & 1), acc, 0, j);
-                mma_term<1, true, 0, 1, TM, 1>(a, b + (j & 1), acc, 0, j);
+                if constexpr (NP > 1) {
+                    mma_term<1, true, 1, 0, TM, 1>(a, b + (j & 1), acc, 0, j);
+                    mma_term<1, true, 0, 1, TM, 1>(a, b + (j & 1), acc, 0, j);
+                }
                 mma_term<1, true, 0, 0, TM, 1>(a, b + (j & 1), acc, 0, j);
             }
             if (FULL || t + 2 < n) b_adv();
@@ -490,8 +492,8 @@ __global__ __launch_bounds__(256, 2) void k_conv_s3(ConvP p) {
         }
         if (kt < kt_end) slab(kt, 0, s0, TailT());
     }
-    unsigned* const om = (SCH == 1 && !ZS && p.out_amax && p.ksplit <= 1) ? om_tab : nullptr;
-    if (!ZS) conv_epilogue<TM, TN, SCH == 1>(p, acc, m0, n0, wm0, wn0, nullptr, os_tab, om);
+    unsigned* const om = (SCH != 0 && !ZS && p.out_amax && p.ksplit <= 1) ? om_tab : nullptr;
+    if (!ZS) conv_epilogue<TM, TN, SCH != 0>(p, acc, m0, n0, wm0, wn0, nullptr, os_tab, om);
     if (om) out_amax_commit(p, om_tab, m0, BM);
 }
 
@@ -548,10 +550,14 @@ void launch_conv_s3(const ConvChoice& k, hipStream_t st, const ConvP& p_in) {
     typedef std::integral_constant<int, 0> I0;
     typedef std::integral_constant<int, 1> I1;
     typedef std::integral_constant<int, 2> I2;
-    if (k.zs) {                                   // (the two-term fp16 scheme: PF = 1, 128 rows only)
-        if (k.sch) { if (bn == 256) S3_LAUNCH(128, 256, 1, true, 1); else S3_LAUNCH(128, 128, 1, true, 1); }
+    if (k.zs) {                                   // (the fp16 schemes: PF = 1, 128 rows only)
+        if (k.sch == 2) { if (bn == 256) S3_LAUNCH(128, 256, 1, true, 2); else S3_LAUNCH(128, 128, 1, true, 2); }
+        else if (k.sch) { if (bn == 256) S3_LAUNCH(128, 256, 1, true, 1); else S3_LAUNCH(128, 128, 1, true, 1); }
         else { if (bn == 256) S3_LAUNCH(128, 256, 1, true, 0); else S3_LAUNCH(128, 128, 1, true, 0); }
-    } else if (bn == 256) { if (k.sch) S3_LAUNCH(128, 256, 1, false, 1); else S3_LAUNCH(128, 256, 1, false, 0); }
+    } else if (bn == 256) {
+        if (k.sch == 2) S3_LAUNCH(128, 256, 1, false, 2); else if (k.sch) S3_LAUNCH(128, 256, 1, false, 1); else S3_LAUNCH(128, 256, 1, false, 0);
+    }
+    else if (k.sch == 2) narrow(I1(), I2());
     else if (k.sch) narrow(I1(), I1());
     else if (k.bm == 256) S3_LAUNCH(256, 128, 1, false, 0);
     else if (k.pf == 2) narrow(I2(), I0());
@@ -627,7 +633,7 @@ template <int BN, int CC, int SCH = 0>
 __global__ __launch_bounds__(256, 2) void k_conv1d_s3(ConvP p) {
     typedef S3Cfg<128, BN> TC;
     constexpr int TM = TC::TM, TN = TC::TN, NCH = CC / 8, NSL = CC / 16, RMAX = 128 + 50;
-    constexpr int NP = SCH ? 2 : 3;
+    constexpr int NP = s3_planes<SCH>();
     __shared__ uint4 As[NP][RMAX * NCH];
     __shared__ uint4 Bs[2][NP][BN * 2];
     __shared__ float os_tab[SCH ? 128 : 1];
@@ -635,8 +641,8 @@ __global__ __launch_bounds__(256, 2) void k_conv1d_s3(ConvP p) {
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int wm0 = (wave / TC::WN) * (128 / TC::WM), wn0 = (wave % TC::WN) * (BN / TC::WN);
     const int L = p.W, b = blockIdx.z, l0 = blockIdx.x * 128, n0 = blockIdx.y * BN;
-    float a_scale = 1.f;                         // scheme 1: the tile lies inside ONE batch row (launch_conv1d_s3: rows_div % 128 == 0)
-    if constexpr (SCH == 1) {
+    float a_scale = 1.f;                         // schemes 1, 2: the tile lies inside ONE batch row (launch_conv1d_s3: rows_div % 128 == 0)
+    if constexpr (SCH != 0) {
         const unsigned bits = p.row_amax[(size_t)((b * L + l0) / p.rows_div) * EGR_ROW_AMAX_STRIDE];
         a_scale = h2_row_scale(bits);
         if (tid < 128) os_tab[tid] = h2_row_inv(bits);
@@ -650,7 +656,7 @@ __global__ __launch_bounds__(256, 2) void k_conv1d_s3(ConvP p) {
 
     // B tiles: 2*NP*BN chunks per slab, up to 3 per thread (as in k_conv_s3)
     constexpr int NBQ = 2 * NP * BN;
-    const size_t b_slab = (size_t)p.Cout * 2 * NP;
+    const size_t b_slab = (size_t)p.Cout * 2 * s3_pack_planes<SCH>();
     const int cpt = p.Cin / 16;                  // slabs per tap in the weight pack
 #define C1_BSETUP(I, OFF, SLOT, OK)                                                                               \
     size_t OFF;                                                                                                      \
@@ -742,8 +748,8 @@ __global__ __launch_bounds__(256, 2) void k_conv1d_s3(ConvP p) {
         }
         if (sg + 1 < stotal) store_b(cur ^ 1, nx);   // buffer cur^1 was last read in iteration sg-1, before this barrier
         if (sg + 5 < stotal) load_b(sg + 5, nx);
-        // scheme 1: weights as the first operand -- transposed accumulators, 16-byte stores (conv_epilogue_t)
-        mma_terms<SCH, SCH == 1, TM, TN>(aq, bq, acc);
+        // schemes 1, 2: weights as the first operand -- transposed accumulators, 16-byte stores (conv_epilogue_t)
+        mma_terms<SCH, SCH != 0, TM, TN>(aq, bq, acc);
         if (s + 1 == spc) __syncthreads();       // last slab of the chunk: everyone is done with the halo tile
     };
 
@@ -788,7 +794,10 @@ bool conv1d_s3_applies(const ConvP& p, ConvChoice& k) {
 void launch_conv1d_s3(const ConvChoice& k, hipStream_t st, const ConvP& p) {
     with_bn(k.bn, [&](auto n) {
         constexpr int BN = decltype(n)::value;
-        if (p.sch) {
+        if (p.sch == 2) {
+            if (k.cc == 32) hipLaunchKernelGGL((k_conv1d_s3<BN, 32, 2>), k.grid, dim3(256), 0, st, p);
+            else hipLaunchKernelGGL((k_conv1d_s3<BN, 16, 2>), k.grid, dim3(256), 0, st, p);
+        } else if (p.sch) {
             if (k.cc == 32) hipLaunchKernelGGL((k_conv1d_s3<BN, 32, 1>), k.grid, dim3(256), 0, st, p);
             else hipLaunchKernelGGL((k_conv1d_s3<BN, 16, 1>), k.grid, dim3(256), 0, st, p);
         } else {
@@ -821,7 +830,7 @@ struct GemmS3P {
 template <int BN, int SCH = 0>
 __global__ __launch_bounds__(256, 2) void k_bgemm_s3(GemmS3P p) {
     typedef S3Cfg<128, BN> TC;
-    constexpr int TM = TC::TM, TN = TC::TN, NP = SCH ? 2 : 3;
+    constexpr int TM = TC::TM, TN = TC::TN, NP = s3_planes<SCH>();
     __shared__ uint4 As[2][NP][128 * 2];
     __shared__ uint4 Bs[2][NP][BN * 2];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;

@@ -1,6 +1,6 @@
 // Device helpers shared by the split-operand contraction kernels (egr_nn_gemm_s3.hip: implicit-GEMM / 1-D / batched kernels;
 // egr_nn_conv3x3.hip: the input-stationary 3x3 kernels): the exact operand splits (three bf16 terms / two fp16 terms of the
-// pre-scaled operand), the partial-product sequences, the LDS slots of operand and halo tiles, and the wave layout of a block tile.
+// pre-scaled operand / one fp16 term of it), the partial-product sequences, the LDS slots of operand and halo tiles, and the wave layout of a block tile.
 #pragma once
 #include "egr_conv.h"
 #include "egr_rowmax.h"
@@ -62,11 +62,35 @@ __device__ __forceinline__ void split2h_x8(const float4& u, const float4& v, flo
     split2h_pair(v.z, v.w, s, q0.w, q1.w);
 }
 
+// ---- scheme 2: ONE fp16 term of the pre-scaled operand, h0 = f16(x s) with the s of scheme 1 (the row's maximum in [2^14, 2^15):
+// nothing overflows, and an element keeps 11 significand bits down to 2^-29 of its row's maximum).  The weight operand is plane 0 of
+// the scheme-1 pack, f16(w w_scale); one exact product a0 b0 per 16 k accumulated in fp32.  The result is the fp32-accumulated
+// contraction of the ROUNDED operands (each within 2^-12 relative of its fp32 value): a third of scheme 1's matrix instructions and
+// half its LDS operand bytes, for previews and batch jobs that do not need fp32-grade results.  Opt-in only (egr_conv_h1,
+// EGR_FSR_FAST_F16); scales, epilogue and row maxima are those of scheme 1.
+__device__ __forceinline__ uint32_t pk_f16_scaled(float a, float b, float s) {   // RNE (v_cvt_pk_f16_f32); a -> bits 0..15
+    const f32x2 v = {a * s, b * s};
+    return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, f16x2));
+}
+
+__device__ __forceinline__ void split1h_x8(const float4& u, const float4& v, float s, uint4& q0) {
+    q0.x = pk_f16_scaled(u.x, u.y, s);
+    q0.y = pk_f16_scaled(u.z, u.w, s);
+    q0.z = pk_f16_scaled(v.x, v.y, s);
+    q0.w = pk_f16_scaled(v.z, v.w, s);
+}
+
+// Operand planes (terms of the split) a kernel of scheme SCH keeps per tile, and the planes per 16-k slab of the weight pack it reads
+// (scheme 2 reads plane 0 of the two-plane pack of scheme 1: the slab stride stays that pack's).
+template <int SCH> __host__ __device__ constexpr int s3_planes() { static_assert(SCH >= 0 && SCH <= 2, "operand scheme"); return SCH == 0 ? 3 : (SCH == 1 ? 2 : 1); }
+template <int SCH> __host__ __device__ constexpr int s3_pack_planes() { return SCH == 0 ? 3 : 2; }
+
 // the operand split of scheme SCH into its NP planes q[0..NP)
 template <int SCH>
 __device__ __forceinline__ void split_x8(const float4& u, const float4& v, float s, uint4 (&q)[3]) {
     if constexpr (SCH == 0) split3_x8(u, v, q[0], q[1], q[2]);
-    else split2h_x8(u, v, s, q[0], q[1]);
+    else if constexpr (SCH == 1) split2h_x8(u, v, s, q[0], q[1]);
+    else split1h_x8(u, v, s, q[0]);
 }
 
 // <BM, BN> block tile, 4 waves.  256x128: waves 2x2, each 128x64 (TM 4, TN 2; the large-M workhorse: half the split work and
@@ -108,7 +132,7 @@ __device__ __forceinline__ void mma_term(const uint4 (*a)[NA], const uint4 (*b)[
 }
 
 // All terms of scheme SCH for one 16-k slab, smallest terms first (the large products then meet a sum that already holds the small
-// ones): scheme 0 (2,0) (0,2) (1,1) (1,0) (0,1) (0,0), scheme 1 (1,0) (0,1) (0,0).  The order is TERM-outer, sub-tile-inner: an MFMA
+// ones): scheme 0 (2,0) (0,2) (1,1) (1,0) (0,1) (0,0), scheme 1 (1,0) (0,1) (0,0), scheme 2 (0,0).  The order is TERM-outer, sub-tile-inner: an MFMA
 // that accumulates into the register block its predecessor wrote waits for that result, so each term runs across all TA x TB
 // accumulator blocks before the next term returns to the first of them and consecutive MFMAs are independent.  (All terms of one
 // block back to back would be the same sum in the same order per block, with every MFMA waiting for the one before it.)
@@ -119,8 +143,10 @@ __device__ __forceinline__ void mma_terms(const uint4 (*a)[NA], const uint4 (*b)
         mma_term<0, WFIRST, 0, 2, TA, TB>(a, b, acc, i0, j0);
         mma_term<0, WFIRST, 1, 1, TA, TB>(a, b, acc, i0, j0);
     }
-    mma_term<SCH, WFIRST, 1, 0, TA, TB>(a, b, acc, i0, j0);
-    mma_term<SCH, WFIRST, 0, 1, TA, TB>(a, b, acc, i0, j0);
+    if constexpr (SCH != 2) {
+        mma_term<SCH, WFIRST, 1, 0, TA, TB>(a, b, acc, i0, j0);
+        mma_term<SCH, WFIRST, 0, 1, TA, TB>(a, b, acc, i0, j0);
+    }
     mma_term<SCH, WFIRST, 0, 0, TA, TB>(a, b, acc, i0, j0);
 }
 

@@ -43,7 +43,8 @@ class FlashSREngine:
     MFMA_MODE = os.environ.get("EGREGORA_FLASHSR_MFMA", "bf16x3")
     # operand scheme of egr_flashsr_infer's split contractions: "f16x2" = two fp16 terms, one power-of-two scale per (tensor, batch
     # row) derived on the device from that row's own maximum (include/egregora_amd.h egr_flashsr_set_split), "bf16x3" = always
-    # three bf16 terms.  egr_flashsr_forward / the operator API use the bf16 terms.
+    # three bf16 terms.  egr_flashsr_forward / the operator API use the bf16 terms.  "f16x1" = the opt-in fast mode: ONE fp16 term
+    # per operand where "f16x2" runs two (EGR_FSR_FAST_F16): reduced precision, outside the pack's accuracy statement (SPEC.md).
     SPLIT = os.environ.get("EGREGORA_FLASHSR_SPLIT", "f16x2")
     # F(2x2,3x3) paid from 256 channels (its transforms move 4x the tensor); F(4x4,3x3) moves 2.25x and pays from 128
     WINO_MIN_CH = int(os.environ.get("EGREGORA_FLASHSR_WINOGRAD_MIN_CH", "128"))
@@ -96,13 +97,14 @@ class FlashSREngine:
         return t
 
     def handle_flags(self) -> int:
-        f = native.FSR_F32_MFMA if self.mfma != "bf16x3" else 0
+        f = native.FSR_F32_MFMA if getattr(self, "mfma", self.MFMA_MODE) != "bf16x3" else 0
         f |= native.FSR_NO_WINOGRAD if self.WINO_MIN_CH >= (1 << 20) else 0
         f |= 0 if self.WINO_F4 else native.FSR_NO_WINO_F4
         f |= 0 if self.GN_PARTIALS else native.FSR_NO_GN_PARTIALS
-        f |= 0 if self.thin else native.FSR_NO_THIN_ENDS
+        f |= 0 if getattr(self, "thin", self.THIN_ENDS) else native.FSR_NO_THIN_ENDS
         f |= native.FSR_NO_FUSE_GN if self.FUSE_GN == "0" else 0
         f |= native.FSR_SPLIT_BF16X3 if self.SPLIT == "bf16x3" else 0
+        f |= native.FSR_FAST_F16 if self.SPLIT == "f16x1" else 0
         return f
 
     @property
@@ -180,8 +182,10 @@ class FlashSREngine:
             native.check(self.L.egr_flashsr_warmup(C.c_void_p(self.handle), int(rows), self._st()), "egr_flashsr_warmup")
 
     def set_split(self, scheme: str):
-        """"bf16x3" or "f16x2" for the following c_infer calls (the latter needs an engine built with SPLIT = "f16x2")."""
-        code = {"bf16x3": 0, "f16x2": 1, "f16x2+forward": 2}[scheme]     # the last: c_forward too runs the fp16 operand terms (tests)
+        """"bf16x3", "f16x2" or "f16x1" for the following c_infer calls (the latter two need an engine built with fp16 weight terms:
+        SPLIT = "f16x2" or "f16x1"; one pack serves both, nothing is repacked)."""
+        # "+forward": c_forward too runs the fp16 operand terms (tests)
+        code = {"bf16x3": 0, "f16x2": 1, "f16x2+forward": 2, "f16x1": 3, "f16x1+forward": 4}[scheme]
         native.check(self.L.egr_flashsr_set_split(C.c_void_p(self.handle), code), "egr_flashsr_set_split")
 
     def set_arena_cap_gb(self, gb: float):
@@ -191,10 +195,12 @@ class FlashSREngine:
 
     def split_info(self) -> dict:
         """enabled: c_infer runs two fp16 terms per operand with per-row scales derived on the device; weights: contraction weights that
-        hold fp16 terms; calls: c_infer calls made on the scheme (include/egregora_amd.h egr_flashsr_set_split)."""
-        en, nw, calls = C.c_int(), C.c_int(), C.c_int64()
+        hold fp16 terms; calls: c_infer calls made on the scheme; scheme: the egr_flashsr_set_split value in force (3 / 4: the one-term
+        fast mode) (include/egregora_amd.h egr_flashsr_set_split)."""
+        en, nw, calls, sch = C.c_int(), C.c_int(), C.c_int64(), C.c_int()
+        native.check(self.L.egr_flashsr_split_scheme(C.c_void_p(self.handle), C.byref(sch)), "egr_flashsr_split_scheme")
         native.check(self.L.egr_flashsr_split_info(C.c_void_p(self.handle), C.byref(en), C.byref(nw), C.byref(calls)), "egr_flashsr_split_info")
-        return dict(enabled=bool(en.value), weights=nw.value, calls=calls.value)
+        return dict(enabled=bool(en.value), weights=nw.value, calls=calls.value, scheme=sch.value)
 
     def c_profile(self, fn, ops: bool = False) -> dict:
         """{kernel instantiation: (launches, flops, ms)} of the MFMA contraction launches the handle made while fn() ran; ops=True adds

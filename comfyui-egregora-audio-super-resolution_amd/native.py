@@ -98,6 +98,8 @@ SIGNATURES = {
     "egr_conv_h2_gn": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp]),
     "egr_gn_operand_bound": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),
     "egr_conv_h2": (_i, [_vp] * 6 + [_i] * 15 + [_f] + [_i] * 7 + [_i64] * 3 + [_f, _vp, _i, _vp, _vp]),
+    "egr_conv_h1": (_i, [_vp] * 6 + [_i] * 15 + [_f] + [_i] * 7 + [_i64] * 3 + [_f, _vp, _i, _vp, _vp]),
+    "egr_conv_h1_gn": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp]),
     "egr_winograd_input": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "egr_groupnorm_coeff": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp]),
     "egr_conv_nhwc_gn": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp] + [_i] * 13 + [_vp]),
@@ -149,6 +151,7 @@ SIGNATURES = {
     "egr_flashsr_set_streams": (_i, [_vp, _i, _i]),
     "egr_flashsr_set_split": (_i, [_vp, _i]),
     "egr_flashsr_split_info": (_i, [_vp, _vp, _vp, _vp]),
+    "egr_flashsr_split_scheme": (_i, [_vp, _vp]),
     "egr_flashsr_set_arena_cap": (_i, [_vp, C.c_double]),
     "egr_flashsr_set_profiling": (_i, [_vp, _i]),
     "egr_flashsr_profile": (_i, [_vp, _i, C.c_char_p, C.c_size_t, C.POINTER(_i64), C.POINTER(C.c_double), C.POINTER(C.c_double),
@@ -186,6 +189,7 @@ SIGNATURES = {
 FSR_MAX = 8
 FSR_F32_MFMA, FSR_NO_WINOGRAD, FSR_NO_WINO_F4, FSR_NO_GN_PARTIALS, FSR_NO_THIN_ENDS, FSR_NO_FUSE_GN = 0x01, 0x02, 0x04, 0x08, 0x10, 0x20
 FSR_SPLIT_BF16X3 = 0x40
+FSR_FAST_F16 = 0x80
 
 
 class FlashSRConfigC(C.Structure):

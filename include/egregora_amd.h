@@ -444,6 +444,20 @@ int egr_conv_h2(const float* x, const void* w2, const float* bias, const float* 
 int egr_conv_h2_gn(const float* x, const float* gn_scale, const float* gn_shift, int gn_silu, const void* w2, const float* bias,
                    const float* res, float* y, int B, int H, int W, int Cin, int Cout, int act, float w_scale, const float* row_amax,
                    float* out_amax, void* gn_part, void* stream);
+/* The same two calls on ONE fp16 term per operand (scheme 2 of csrc/egr_nn_gemm_s3.hip): x s -> h0 = f16(x s) with the per-row s of
+ * egr_conv_h2, weights = plane 0 of the SAME w2 pack (f16(w w_scale)), one exact product h0 h0 per 16 k accumulated in fp32 -- a third
+ * of egr_conv_h2's matrix instructions and half its LDS operand bytes.  REDUCED PRECISION, opt-in: the result is the fp32-accumulated
+ * contraction of operands rounded to 11 significand bits (each within 2^-12 relative of its fp32 value, the row scale keeps every
+ * element down to 2^-29 of its row's maximum in fp16's normal range), i.e. |y - exact| <= ~2^-11 sum |x| |w| -- outside the 1e-3 dB
+ * statement of SPEC.md.  Everything else is egr_conv_h2's: arguments, preconditions, row_amax / out_amax / gn_part contracts, the
+ * shapes refused (EGR_ERR_UNSUPPORTED, nothing launched), the tile choices; a row's bits depend on that row alone. */
+int egr_conv_h1(const float* x, const void* w2, const float* bias, const float* bias_b, const float* res, float* y, int B,
+                int H, int W, int Cin, int OH, int OW, int Cout, int KH, int KW, int stride, int dil, int pad_t, int pad_l,
+                int up2, int act, float act_param, int osy, int osx, int ooy, int oox, int OHF, int OWF, int nz, int64_t zx,
+                int64_t zw2, int64_t zy, float w_scale, const float* row_amax, int batch_rows, float* out_amax, void* stream);
+int egr_conv_h1_gn(const float* x, const float* gn_scale, const float* gn_shift, int gn_silu, const void* w2, const float* bias,
+                   const float* res, float* y, int B, int H, int W, int Cin, int Cout, int act, float w_scale, const float* row_amax,
+                   float* out_amax, void* gn_part, void* stream);
 int egr_gn_operand_bound(const float* scale, const float* shift, int B, int C, const float* x_row_amax, float* bound, void* stream);
 int egr_conv_s3(const float* x, const void* w3, const float* bias, const float* bias_b, const float* res, float* y, int B,
                 int H, int W, int Cin, int OH, int OW, int Cout, int KH, int KW, int stride, int dil, int pad_t, int pad_l,
@@ -452,8 +466,8 @@ int egr_conv_s3(const float* x, const void* w3, const float* bias, const float* 
 
 /* One convolution call as data: the union of what egr_conv_nhwc / _placed / _gn, egr_conv_s3, egr_conv_h2 / _gn and
  * egr_gemm_zbatched accept (those functions fill it and hand it to one launcher, csrc/egr_nn_gemm.hip).  w3 is the split pack of
- * either scheme (sch 0: egr_split3_pack, three bf16 terms; sch 1: egr_split2h_pack, two fp16 terms) and zw counts floats of w or
- * 16-byte units of w3. */
+ * either scheme (sch 0: egr_split3_pack, three bf16 terms; sch 1: egr_split2h_pack, two fp16 terms; sch 2: the same pack, its
+ * first term alone -- egr_conv_h1; accepted wherever sch 1 is, with the same zw) and zw counts floats of w or 16-byte units of w3. */
 typedef struct egr_conv_desc {
     const float* x; const float* w; const void* w3; const float* bias; const float* bias_b; const float* res; float* y;
     int B, H, W, Cin, OH, OW, Cout, KH, KW, stride, dil, pad_t, pad_l, up2, act;
@@ -634,6 +648,8 @@ typedef struct egr_tensor_desc {
 #define EGR_FSR_NO_THIN_ENDS   0x10u
 #define EGR_FSR_NO_FUSE_GN     0x20u
 #define EGR_FSR_SPLIT_BF16X3   0x40u /* egr_flashsr_infer never uses the two-term fp16 operand scheme (no fp16 weight terms are kept) */
+#define EGR_FSR_FAST_F16       0x80u /* opt-in fast mode: ONE fp16 term per operand where the default runs two (see egr_flashsr_set_split);
+                                        with EGR_FSR_F32_MFMA or EGR_FSR_SPLIT_BF16X3: EGR_ERR_ARG */
 int egr_flashsr_default_config(egr_flashsr_config* cfg);       /* the declared full-size table */
 int egr_flashsr_create(egr_flashsr** out, const egr_flashsr_config* cfg, const egr_tensor_desc* tensors, int n_tensors,
                        unsigned flags, void* stream);           /* repacks on `stream`, synchronises before returning */
@@ -661,6 +677,16 @@ int egr_flashsr_set_rows_per_pass(egr_flashsr* h, int rows);
  * three-term bf16 kernels; egr_flashsr_forward always is, unless egr_flashsr_set_split(h, 2) (stage taps of the fp16 path for
  * the tests).  The mel projection and the attention products always run on bf16 terms.
  * egr_flashsr_split_info: enabled, contraction weights holding fp16 terms, egr_flashsr_infer calls made on the scheme.
+ * FAST MODE (scheme 3; creation flag EGR_FSR_FAST_F16 or EGREGORA_FLASHSR_SPLIT=f16x1): every contraction that scheme 1 runs on
+ * k_conv_s3 / k_conv1d_s3 / k_conv3x3_isp runs on ONE fp16 term per operand instead (egr_conv_h1: plane 0 of the same weight packs,
+ * the same row maxima and scales, the same launches in the same order with the contraction kernels swapped), with fp32 accumulation
+ * and fp32 activations in memory -- except on the 128 x 64 implicit-GEMM tile, whose one-term form measured no faster than its
+ * two-term twin (profiles/flashsr_fast.md): those launches keep scheme 1.  Left as they are: the fused AMP unit (snake arithmetic, not matrix work, is its time), the
+ * thin-end kernels, the attention products (k_bgemm_s3) and the mel projection.  The result is reduced-precision -- for previews,
+ * batch jobs and listening tests -- and outside the accuracy statement of SPEC.md; purity holds as in scheme 1 (a row's bits depend
+ * on that row alone).  set_split(h, 4): as 3, and egr_flashsr_forward too (stage taps for the tests, as 2 does for scheme 1).  A live
+ * handle switches among 0, 1 and 3 without repacking; 3 / 4 on a handle without fp16 terms: EGR_ERR_UNSUPPORTED; other values:
+ * EGR_ERR_ARG.  egr_flashsr_split_scheme: the set_split value in force (0 when the handle holds no fp16 terms).
  *
  * WHEN egr_flashsr_infer BLOCKS THE HOST: it does not, in the steady state -- all work is enqueued on `stream` (and on the
  * handle's side streams, forked from and joined to `stream` by events).  The FIRST call with a given (row count, lowpass) shape
@@ -668,6 +694,7 @@ int egr_flashsr_set_rows_per_pass(egr_flashsr* h, int rows);
  * two spin kernels to verify its side streams (~1 ms).  x and y must stay valid until the work has run, as for any kernel. */
 int egr_flashsr_set_split(egr_flashsr* h, int scheme);
 int egr_flashsr_split_info(egr_flashsr* h, int* enabled, int* weights, int64_t* calls);
+int egr_flashsr_split_scheme(egr_flashsr* h, int* scheme);
 /* Concurrent row groups inside egr_flashsr_infer: a pass of >= 2 * min_group_rows rows is split into up to max_groups (1..4,
  * default 2; EGREGORA_FLASHSR_STREAMS) contiguous groups run as simultaneous forwards on side streams the handle creates and
  * verifies to sit on other hardware queues than the caller's; fork / join by events, so the call still looks single-stream. */
