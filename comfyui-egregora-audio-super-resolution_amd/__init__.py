@@ -9,7 +9,8 @@ nor a GPU -- the nodes raise at run() time when either is missing.
 The evaluation pack's loudness meter, 1770 gain match and ABX nodes (egregora_audio_eval_loudness.py) are registered only when the
 environment variable EGREGORA_EVAL_NODES is "1" at import; the WPE dereverberation node (egregora_audio_enhance_wpe.py) only when
 EGREGORA_ENHANCE_NODES is "1", the Descript Audio Codec encode / decode nodes (egregora_audio_codec_dac.py) only when
-EGREGORA_CODEC_NODES is "1".  Without them the registered set is the one listed above.
+EGREGORA_CODEC_NODES is "1", the FlashSR batch node (egregora_audio_super_resolution_batch.py: a list of clips in packed waves) only
+when EGREGORA_BATCH_NODES is "1".  Without them the registered set is the one listed above.
 """
 import os
 
@@ -53,5 +54,10 @@ if os.environ.get("EGREGORA_CODEC_NODES") == "1":
     from .egregora_audio_codec_dac import (NODE_CLASS_MAPPINGS as DAC_MAP, NODE_DISPLAY_NAME_MAPPINGS as DAC_NAMES)
     NODE_CLASS_MAPPINGS.update(DAC_MAP)
     NODE_DISPLAY_NAME_MAPPINGS.update(DAC_NAMES)
+
+if os.environ.get("EGREGORA_BATCH_NODES") == "1":
+    from .egregora_audio_super_resolution_batch import (NODE_CLASS_MAPPINGS as BATCH_MAP, NODE_DISPLAY_NAME_MAPPINGS as BATCH_NAMES)
+    NODE_CLASS_MAPPINGS.update(BATCH_MAP)
+    NODE_DISPLAY_NAME_MAPPINGS.update(BATCH_NAMES)
 
 __all__ = ["NODE_CLASS_MAPPINGS", "NODE_DISPLAY_NAME_MAPPINGS"]

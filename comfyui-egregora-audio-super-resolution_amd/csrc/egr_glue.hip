@@ -23,6 +23,53 @@ __global__ __launch_bounds__(256) void k_pcm16(const float* __restrict__ x, floa
     }
 }
 
+// ---------------------------------------------------------------- chunk slice, WOLA and polyphase resampling: per-sample bodies
+// The arithmetic of one output sample is stated once here; the single-clip kernels (k_chunk_gather, k_wola, k_resample_poly) and
+// the many-track kernels (k_*_tracks) below only differ in how a thread finds its sample.
+__device__ __forceinline__ float chunk_sample(const float* __restrict__ xc, long long total, long long start, long long j) {
+    const long long i = start + j;
+    return (i < total) ? xc[i] : 0.f;
+}
+
+// pr: row of chunk 0 of this channel; consecutive chunks of the channel lie row_stride rows of lp floats apart
+__device__ __forceinline__ float wola_sample(const float* __restrict__ pr, long long row_stride, long long nchunks, long long lp,
+                                             long long total, long long win, long long hop, const float* __restrict__ window,
+                                             long long i) {
+    long long k_lo = (i < win) ? 0 : (i - win) / hop + 1;
+    long long k_hi = i / hop;
+    if (k_hi > nchunks - 1) k_hi = nchunks - 1;
+    float acc = 0.f, ws = 0.f;
+    for (long long k = k_lo; k <= k_hi; ++k) {
+        const long long start = k * hop;
+        long long L = total - start;
+        if (L > win) L = win;
+        if (L > lp) L = lp;
+        const long long j = i - start;
+        if (j < L) {
+            const float w = window[j];
+            const float y = pr[(size_t)k * row_stride * lp + j];
+            acc = __fadd_rn(acc, __fmul_rn(y, w));
+            ws = __fadd_rn(ws, w);
+        }
+    }
+    if (ws == 0.f) ws = 1.f;
+    return __fdiv_rn(acc, ws);
+}
+
+// Rational-rate polyphase FIR, same definition and float32 accumulation order as scipy.signal.resample_poly
+// (upfirdn with zero extension): y[m] = sum_k h[m*down - k*up + half] * x[k], k ascending, unfused mul/add.
+__device__ __forceinline__ float resample_sample(const float* __restrict__ xc, long long n_in, int up, int down,
+                                                 const float* __restrict__ h, int half, long long m) {
+    const long long hl = 2LL * half;
+    const long long t = m * down + half;
+    long long k_hi = t / up;
+    if (k_hi > n_in - 1) k_hi = n_in - 1;
+    long long k_lo = t - hl <= 0 ? 0 : (t - hl + up - 1) / up;
+    float acc = 0.f;
+    for (long long k = k_lo; k <= k_hi; ++k) acc = __fadd_rn(acc, __fmul_rn(xc[k], h[t - k * up]));
+    return acc;
+}
+
 __global__ __launch_bounds__(256) void k_chunk_gather(const float* __restrict__ x, int C, long long total,
                                                        long long win, long long hop, int chunk_begin,
                                                        float* __restrict__ chunks) {
@@ -31,10 +78,8 @@ __global__ __launch_bounds__(256) void k_chunk_gather(const float* __restrict__ 
     const float* xc = x + (size_t)c * total;
     float* dst = chunks + ((size_t)k * C + c) * win;
     for (long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x; j < win;
-         j += (long long)gridDim.x * blockDim.x) {
-        const long long i = start + j;
-        dst[j] = (i < total) ? xc[i] : 0.f;
-    }
+         j += (long long)gridDim.x * blockDim.x)
+        dst[j] = chunk_sample(xc, total, start, j);
 }
 
 __global__ __launch_bounds__(256) void k_wola(const float* __restrict__ preds, int nchunks, int C, long long lp,
@@ -42,47 +87,75 @@ __global__ __launch_bounds__(256) void k_wola(const float* __restrict__ preds, i
                                                const float* __restrict__ window, float* __restrict__ out) {
     const int c = blockIdx.y;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
-         i += (long long)gridDim.x * blockDim.x) {
-        long long k_lo = (i < win) ? 0 : (i - win) / hop + 1;
-        long long k_hi = i / hop;
-        if (k_hi > nchunks - 1) k_hi = nchunks - 1;
-        float acc = 0.f, ws = 0.f;
-        for (long long k = k_lo; k <= k_hi; ++k) {
-            const long long start = k * hop;
-            long long L = total - start;
-            if (L > win) L = win;
-            if (L > lp) L = lp;
-            const long long j = i - start;
-            if (j < L) {
-                const float w = window[j];
-                const float y = preds[((size_t)k * C + c) * lp + j];
-                acc = __fadd_rn(acc, __fmul_rn(y, w));
-                ws = __fadd_rn(ws, w);
-            }
-        }
-        if (ws == 0.f) ws = 1.f;
-        out[(size_t)c * total + i] = __fdiv_rn(acc, ws);
-    }
+         i += (long long)gridDim.x * blockDim.x)
+        out[(size_t)c * total + i] = wola_sample(preds + (size_t)c * lp, C, nchunks, lp, total, win, hop, window, i);
 }
 
-// Rational-rate polyphase FIR, same definition and float32 accumulation order as scipy.signal.resample_poly
-// (upfirdn with zero extension): y[m] = sum_k h[m*down - k*up + half] * x[k], k ascending, unfused mul/add.
 __global__ __launch_bounds__(256) void k_resample_poly(const float* __restrict__ x, long long n_in, long long n_out,
                                                         int up, int down, const float* __restrict__ h, int half,
                                                         float* __restrict__ y) {
     const int c = blockIdx.y;
     const float* xc = x + (size_t)c * n_in;
     float* yc = y + (size_t)c * n_out;
-    const long long hl = 2LL * half;
     for (long long m = (long long)blockIdx.x * blockDim.x + threadIdx.x; m < n_out;
-         m += (long long)gridDim.x * blockDim.x) {
-        const long long t = m * down + half;
-        long long k_hi = t / up;
-        if (k_hi > n_in - 1) k_hi = n_in - 1;
-        long long k_lo = t - hl <= 0 ? 0 : (t - hl + up - 1) / up;
-        float acc = 0.f;
-        for (long long k = k_lo; k <= k_hi; ++k) acc = __fadd_rn(acc, __fmul_rn(xc[k], h[t - k * up]));
-        yc[m] = acc;
+         m += (long long)gridDim.x * blockDim.x)
+        yc[m] = resample_sample(xc, n_in, up, down, h, half, m);
+}
+
+// ---------------------------------------------------------------- many tracks per launch (a track = one channel of one clip)
+// Work mapping: a FLAT index over the samples the launch writes -- a launch's size is the sum of its tracks' lengths, whatever the
+// longest one is, and no grid dimension counts tracks or rows.  A workgroup's 256 consecutive samples mostly belong to one track:
+// the group searches the table's ascending output offsets once for its first sample (the same value in every lane), each thread
+// then steps forward over the few track starts inside the group's stretch.
+// last t in [0, n) with tab[t * stride + col] <= i; the column ascends and starts at 0
+__device__ __forceinline__ int track_of(const long long* __restrict__ tab, int n, int stride, int col, long long i) {
+    int lo = 0, hi = n - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (tab[(size_t)mid * stride + col] <= i) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
+// rows[r] = (track offset into x, track length, chunk index k); chunks [n_rows][win]
+__global__ __launch_bounds__(256) void k_chunk_gather_tracks(const float* __restrict__ x, const long long* __restrict__ rows,
+                                                              long long n_rows, long long win, long long hop,
+                                                              float* __restrict__ chunks) {
+    const long long n = n_rows * win;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+        const long long r = i / win, j = i - r * win;
+        const long long* e = rows + r * 3;
+        chunks[i] = chunk_sample(x + e[0], e[1], e[2] * hop, j);
+    }
+}
+
+// tracks[t] = (first row, row stride, n_chunks, total, out offset); out offsets ascend back to back from 0 to total_out
+__global__ __launch_bounds__(256) void k_wola_tracks(const float* __restrict__ preds, const long long* __restrict__ tracks,
+                                                      int n_tracks, long long total_out, long long lp, long long win,
+                                                      long long hop, const float* __restrict__ window, float* __restrict__ out) {
+    for (long long base = (long long)blockIdx.x * 256; base < total_out; base += (long long)gridDim.x * 256) {
+        int t = track_of(tracks, n_tracks, 5, 4, base);
+        const long long i = base + threadIdx.x;
+        if (i >= total_out) continue;
+        while (t + 1 < n_tracks && tracks[(size_t)(t + 1) * 5 + 4] <= i) ++t;
+        const long long* e = tracks + (size_t)t * 5;
+        const long long m = i - e[4];
+        if (m < e[3]) out[i] = wola_sample(preds + (size_t)e[0] * lp, e[1], e[2], lp, e[3], win, hop, window, m);
+    }
+}
+
+// tracks[t] = (in offset, n_in, out offset, n_out); out offsets ascend back to back from 0 to total_out
+__global__ __launch_bounds__(256) void k_resample_poly_tracks(const float* __restrict__ x, const long long* __restrict__ tracks,
+                                                               int n_tracks, long long total_out, int up, int down,
+                                                               const float* __restrict__ h, int half, float* __restrict__ y) {
+    for (long long base = (long long)blockIdx.x * 256; base < total_out; base += (long long)gridDim.x * 256) {
+        int t = track_of(tracks, n_tracks, 4, 2, base);
+        const long long i = base + threadIdx.x;
+        if (i >= total_out) continue;
+        while (t + 1 < n_tracks && tracks[(size_t)(t + 1) * 4 + 2] <= i) ++t;
+        const long long* e = tracks + (size_t)t * 4;
+        const long long m = i - e[2];
+        if (m < e[3]) y[i] = resample_sample(x + e[0], e[1], up, down, h, half, m);
     }
 }
 
@@ -689,6 +762,36 @@ extern "C" int egr_resample_poly(const float* x, int channels, int64_t n_in, int
     EGR_CHECK(n_out == (n_in * up + down - 1) / down, EGR_ERR_ARG, "n_out must be ceil(n_in*up/down)");
     hipLaunchKernelGGL(k_resample_poly, dim3(grid_for(n_out), channels), dim3(256), 0, (hipStream_t)stream, x,
                        (long long)n_in, (long long)n_out, up, down, h, half, y);
+    EGR_HIP(hipGetLastError());
+    return EGR_OK;
+}
+
+extern "C" int egr_chunk_gather_tracks(const float* x, const int64_t* rows, int n_rows, int64_t win, int64_t hop, float* chunks,
+                                       void* stream) {
+    EGR_CHECK(x && rows && chunks && n_rows >= 0 && win >= 1 && hop >= 1, EGR_ERR_ARG, "bad argument");
+    if (n_rows == 0) return EGR_OK;
+    hipLaunchKernelGGL(k_chunk_gather_tracks, dim3(grid_for((long long)n_rows * win)), dim3(256), 0, (hipStream_t)stream, x,
+                       (const long long*)rows, (long long)n_rows, (long long)win, (long long)hop, chunks);
+    EGR_HIP(hipGetLastError());
+    return EGR_OK;
+}
+
+extern "C" int egr_wola_tracks(const float* preds, const int64_t* tracks, int n_tracks, int64_t total_out, int64_t lp, int64_t win,
+                               int64_t hop, const float* window, float* out, void* stream) {
+    EGR_CHECK(preds && tracks && window && out && n_tracks >= 1 && total_out >= 1 && lp >= 1 && win >= 1 && hop >= 1, EGR_ERR_ARG,
+              "bad argument");
+    hipLaunchKernelGGL(k_wola_tracks, dim3(grid_for(total_out)), dim3(256), 0, (hipStream_t)stream, preds, (const long long*)tracks,
+                       n_tracks, (long long)total_out, (long long)lp, (long long)win, (long long)hop, window, out);
+    EGR_HIP(hipGetLastError());
+    return EGR_OK;
+}
+
+extern "C" int egr_resample_poly_tracks(const float* x, const int64_t* tracks, int n_tracks, int64_t total_out, int up, int down,
+                                        const float* h, int half, float* y, void* stream) {
+    EGR_CHECK(x && tracks && h && y && n_tracks >= 1 && total_out >= 1 && up >= 1 && down >= 1 && half >= 0, EGR_ERR_ARG,
+              "bad argument");
+    hipLaunchKernelGGL(k_resample_poly_tracks, dim3(grid_for(total_out)), dim3(256), 0, (hipStream_t)stream, x,
+                       (const long long*)tracks, n_tracks, (long long)total_out, up, down, h, half, y);
     EGR_HIP(hipGetLastError());
     return EGR_OK;
 }

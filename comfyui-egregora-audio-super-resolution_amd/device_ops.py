@@ -54,6 +54,45 @@ def wola_stitch(preds: torch.Tensor, total: int, win: int, hop: int) -> torch.Te
     return out
 
 
+# ------------------------------------------------------------------ ragged glue: many tracks (one channel of one clip) per call
+# Flat float32 buffers hold the tracks back to back; small int64 device tables say where (flashsr_engine.wave_tables /
+# resample_table build them; include/egregora_amd.h states the columns).
+def _chk_table(t, cols, what):
+    if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.int64 and t.is_contiguous() and t.dim() == 2 and t.shape[1] == cols):
+        raise RuntimeError(f"{what}: want a contiguous int64 CUDA table with {cols} columns")
+
+
+def resample_poly_tracks(x: torch.Tensor, table: torch.Tensor, total_out: int, up: int, down: int, h: torch.Tensor, half: int,
+                         y: torch.Tensor) -> torch.Tensor:
+    """One rate group: table [T,4] = (in offset into x, n_in, out offset into y, n_out); y[0 .. total_out) is written."""
+    _chk(x, "resample_poly_tracks"), _chk(y, "resample_poly_tracks"), _chk_table(table, 4, "resample_poly_tracks")
+    if y.numel() < total_out:
+        raise RuntimeError("resample_poly_tracks: output buffer shorter than total_out")
+    native.check(native.lib().egr_resample_poly_tracks(native.ptr(x), native.ptr(table), table.shape[0], int(total_out), int(up), int(down),
+                                                       native.ptr(h), int(half), native.ptr(y), native.stream_ptr()),
+                 "egr_resample_poly_tracks")
+    return y
+
+
+def chunk_gather_tracks(x: torch.Tensor, table: torch.Tensor, win: int, hop: int) -> torch.Tensor:
+    """table [R,3] = (track offset into x, track length, chunk index) -> [R, win] zero-padded rows."""
+    _chk(x, "chunk_gather_tracks"), _chk_table(table, 3, "chunk_gather_tracks")
+    out = torch.empty((table.shape[0], win), dtype=torch.float32, device=x.device)
+    native.check(native.lib().egr_chunk_gather_tracks(native.ptr(x), native.ptr(table), table.shape[0], int(win), int(hop),
+                                                      native.ptr(out), native.stream_ptr()), "egr_chunk_gather_tracks")
+    return out
+
+
+def wola_tracks(preds: torch.Tensor, table: torch.Tensor, total_out: int, win: int, hop: int) -> torch.Tensor:
+    """preds [R, lp], table [T,5] = (first row, row stride, n_chunks, total, out offset) -> flat [total_out]: every track's Hann WOLA."""
+    _chk(preds, "wola_tracks"), _chk_table(table, 5, "wola_tracks")
+    out = torch.empty((int(total_out),), dtype=torch.float32, device=preds.device)
+    w = hann_window(win, preds.device)
+    native.check(native.lib().egr_wola_tracks(native.ptr(preds), native.ptr(table), table.shape[0], int(total_out), preds.shape[1],
+                                              int(win), int(hop), native.ptr(w), native.ptr(out), native.stream_ptr()), "egr_wola_tracks")
+    return out
+
+
 def stft_mag(x: torch.Tensor, n_fft: int = 2048, hop: int = 512) -> torch.Tensor:
     """[T] or [C,T] -> [n_fft/2+1, frames] (a transposed view of the frame-major device buffer), matching
     the reference's _stft_mag layout (egregora_audio_eval_pack.py:389-402)."""

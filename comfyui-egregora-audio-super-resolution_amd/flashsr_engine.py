@@ -26,7 +26,7 @@ from typing import Dict, List, Optional, Tuple
 
 import torch
 
-from . import device_ops, flashsr_arch as arch, native, shard
+from . import audio_glue, device_ops, flashsr_arch as arch, native, shard
 
 ACT_NONE, ACT_SILU, ACT_TANH, ACT_LEAKY, ACT_LOGCLAMP = 0, 1, 2, 3, 4
 EW_ADD, EW_AXPBY, EW_SILU, EW_SCALE, EW_COPY, EW_ADD_SCALE = 0, 1, 2, 3, 4, 5
@@ -438,3 +438,274 @@ def infer_block(x_ct: torch.Tensor, lo: int, hi: int, win: int, hop: int, lowpas
            torch.arange(Cn, device=x_ct.device, dtype=torch.int64)[None, :]).reshape(-1)
     y = infer_rows(eng, chunks.view(-1, win), ids, SEED, lowpass=bool(lowpass))
     return y.view(hi - lo, Cn, win)
+
+
+# ---------------------------------------------------------------------------------------------------- many clips in packed waves
+# A TRACK is one channel of one clip.  Rows of different clips share one egr_flashsr_infer call (a row's result is a function of
+# (weights, row, seed, row id) alone); the ragged glue around that call reads small int64 device tables built here (DESIGN.md
+# section 4.6, include/egregora_amd.h egr_resample_poly_tracks / egr_chunk_gather_tracks / egr_wola_tracks).
+DEFAULT_BATCH_ROWS = 1024          # about 1 GB of rows in and 1 GB out at the model's 245760-sample chunk
+
+
+def n_chunks_for(total: int, win: int, hop: int) -> int:
+    """len(audio_glue.spans(total, win, hop)) without the list."""
+    if total <= 0:
+        return 0
+    return 1 if total <= win else 1 + -(-(total - win) // hop)
+
+
+def resampled_len(n: int, src_sr: int, dst_sr: int) -> int:
+    """Length resample.resample_hq gives n samples: ceil(n * up / down)."""
+    if int(src_sr) == int(dst_sr):
+        return int(n)
+    from . import resample
+    up, down = resample.rates(src_sr, dst_sr)
+    return (int(n) * up + down - 1) // down
+
+
+def clip_rows(channels: int, n: int, sr: int, win: int, hop: int) -> int:
+    """Rows (chunks x channels) a [channels, n] clip at rate sr puts on the model's batch dimension."""
+    return int(channels) * n_chunks_for(resampled_len(n, sr, audio_glue.REQ_SR), win, hop)
+
+
+def wave_budget(max_rows: Optional[int] = None) -> int:
+    """Row budget of a wave: max_rows, else EGREGORA_FLASHSR_BATCH_ROWS, else 1024, rounded DOWN to a multiple of ROWS_PER_PASS (so only
+    the last pass of a wave is partial), never below one pass."""
+    if max_rows is None:
+        max_rows = int(os.environ.get("EGREGORA_FLASHSR_BATCH_ROWS", str(DEFAULT_BATCH_ROWS)))
+    rpp = max(1, ROWS_PER_PASS)
+    return max(rpp, (int(max_rows) // rpp) * rpp)
+
+
+def plan_waves(row_counts: List[int], max_rows: Optional[int] = None) -> List[List[int]]:
+    """Clip indices per wave, in input order.  A wave closes before the clip that would take it past the budget (wave_budget); a clip
+    is never split, so one with more rows than the budget is a wave of its own; clips of zero rows are in no wave."""
+    budget = wave_budget(max_rows)
+    waves: List[List[int]] = []
+    cur: List[int] = []
+    used = 0
+    for i, r in enumerate(row_counts):
+        if r <= 0:
+            continue
+        if cur and used + r > budget:
+            waves.append(cur)
+            cur, used = [], 0
+        cur.append(i)
+        used += r
+    if cur:
+        waves.append(cur)
+    return waves
+
+
+def resample_table(in_offsets: List[int], n_ins: List[int], up: int, down: int):
+    """egr_resample_poly_tracks' table for one rate group: int64 [T,4] rows (in offset, n_in, out offset, n_out) with
+    n_out = ceil(n_in * up / down) and the outputs back to back from 0; -> (table, total_out)."""
+    import numpy as np
+    n_in = np.asarray(n_ins, dtype=np.int64).reshape(-1)
+    n_out = (n_in * up + down - 1) // down
+    ends = np.cumsum(n_out)
+    tab = np.stack([np.asarray(in_offsets, dtype=np.int64).reshape(-1), n_in, ends - n_out, n_out], axis=1)
+    return np.ascontiguousarray(tab), int(ends[-1]) if len(ends) else 0
+
+
+def wave_tables(shapes: List[Tuple[int, int]], offsets: List[int], win: int, hop: int) -> dict:
+    """Tables of one wave at 48 kHz.  shapes[i] = (C, T) of clip i, offsets[i] = where its channel 0 starts in the flat input
+    (channel c at offsets[i] + c * T).  Rows inside a clip are chunk-major then channel -- the order the single-clip path views as
+    [n, C, win] -- and carry the ids the clip would have alone (k * C + c).
+      rows   int64 [R,3]: (track offset, track length, chunk index k)            -> egr_chunk_gather_tracks
+      ids    int64 [R]:   k * C + c                                               -> egr_flashsr_infer row_ids
+      tracks int64 [T,5]: (first row, row stride C, n_chunks, total, out offset)  -> egr_wola_tracks
+      clip_out [(out offset, C, T)] per clip (a clip's [C,T] result is contiguous), total_out."""
+    import numpy as np
+    rows, ids, tracks, clip_out = [], [], [], []
+    row0, out = 0, 0
+    for (Cn, T), off in zip(shapes, offsets):
+        n = n_chunks_for(T, win, hop)
+        k = np.repeat(np.arange(n, dtype=np.int64), Cn)
+        c = np.tile(np.arange(Cn, dtype=np.int64), n)
+        rows.append(np.stack([off + c * T, np.full_like(k, T), k], axis=1))
+        ids.append(k * Cn + c)
+        cc = np.arange(Cn, dtype=np.int64)
+        tracks.append(np.stack([row0 + cc, np.full_like(cc, Cn), np.full_like(cc, n), np.full_like(cc, T), out + cc * T], axis=1))
+        clip_out.append((out, Cn, T))
+        row0 += n * Cn
+        out += Cn * T
+    cat = lambda parts, cols: np.ascontiguousarray(np.concatenate(parts, axis=0)) if parts else np.zeros((0,) + cols, dtype=np.int64)
+    return dict(rows=cat(rows, (3,)), ids=cat(ids, ()), tracks=cat(tracks, (5,)), clip_out=clip_out, total_out=out, n_rows=row0)
+
+
+def _upscale_single(x: torch.Tensor, sr: int, lowpass: bool, output_sr: int, win: int, hop: int, eng: FlashSREngine) -> torch.Tensor:
+    """The single-clip flow of the node (egregora_audio_super_resolution.py run / upscale_48k) for a clip the packed path leaves out:
+    its result, or its error."""
+    from . import resample
+    x = x.to(eng.dev, torch.float32).contiguous()
+    if sr != audio_glue.REQ_SR:
+        x = resample.resample_hq(x, sr, audio_glue.REQ_SR)
+    total = x.shape[1]
+    n = n_chunks_for(total, win, hop)
+    if n == 0:
+        y = torch.zeros((1, max(1, total)), dtype=torch.float32, device=x.device)      # upscale_48k's answer (reference :234-235)
+    else:
+        y = device_ops.wola_stitch(infer_block(x, 0, n, win, hop, lowpass, eng), total, win, hop)
+    if output_sr != audio_glue.REQ_SR:
+        y = resample.resample_hq(y, audio_glue.REQ_SR, output_sr)
+    return y.cpu()
+
+
+class _Wave:
+    """One enqueued wave: the pinned result, the event behind its download, and where each clip's [C,T] lies in it."""
+    __slots__ = ("host", "event", "clip_out", "clips", "rows", "calls")
+
+
+def _enqueue_wave(eng: FlashSREngine, clips, idx: List[int], lowpass: bool, output_sr: int, win: int, hop: int) -> _Wave:
+    import numpy as np
+    from . import resample
+    dev = eng.dev
+    REQ = audio_glue.REQ_SR
+    # raw samples: host clips first (one pinned upload), device clips behind them (device copies)
+    order = sorted(idx, key=lambda i: clips[i][0].is_cuda)
+    raw_off, pos = {}, 0
+    for i in order:
+        raw_off[i] = pos
+        pos += clips[i][0].numel()
+    n_raw = pos
+    n_host = sum(clips[i][0].numel() for i in order if not clips[i][0].is_cuda)
+    # 48 kHz layout: a 48 kHz clip stays where it was uploaded; every other rate is one group resampled into a region behind the raw
+    # samples, the group's tracks back to back
+    groups: Dict[int, List[int]] = {}
+    for i in idx:
+        if int(clips[i][1]) != REQ:
+            groups.setdefault(int(clips[i][1]), []).append(i)
+    off48, shapes48, group_tabs = {}, {}, []
+    pos = n_raw
+    for sr in sorted(groups):
+        up, down = resample.rates(sr, REQ)
+        ins, lens = [], []
+        for i in groups[sr]:
+            Cn, T = clips[i][0].shape
+            ins += [raw_off[i] + c * T for c in range(Cn)]
+            lens += [T] * Cn
+        tab, total = resample_table(ins, lens, up, down)
+        t = 0
+        for i in groups[sr]:
+            Cn = clips[i][0].shape[0]
+            off48[i] = pos + int(tab[t, 2])
+            shapes48[i] = (Cn, int(tab[t, 3]))
+            t += Cn
+        group_tabs.append((up, down, pos, total, tab))
+        pos += total
+    n_buf = pos
+    for i in idx:
+        if i not in off48:
+            off48[i], shapes48[i] = raw_off[i], tuple(clips[i][0].shape)
+    wt = wave_tables([shapes48[i] for i in idx], [off48[i] for i in idx], win, hop)
+    clip_out, total_out = wt["clip_out"], wt["total_out"]
+    out_tab = None
+    if output_sr != REQ:
+        up_o, down_o = resample.rates(REQ, output_sr)
+        out_tab, total_res = resample_table(wt["tracks"][:, 4], wt["tracks"][:, 3], up_o, down_o)
+        t, clip_out = 0, []
+        for i in idx:
+            Cn = shapes48[i][0]
+            clip_out.append((int(out_tab[t, 2]), Cn, int(out_tab[t, 3])))
+            t += Cn
+    # every table of the wave in one pinned buffer, one copy
+    parts = [g[4].reshape(-1) for g in group_tabs] + [wt["rows"].reshape(-1), wt["ids"], wt["tracks"].reshape(-1)]
+    if out_tab is not None:
+        parts.append(out_tab.reshape(-1))
+    flat = np.concatenate(parts)
+    tab_host = torch.empty(flat.size, dtype=torch.int64, pin_memory=True)
+    tab_host.numpy()[:] = flat
+    tab_dev = tab_host.to(dev, non_blocking=True)
+    cuts = np.cumsum([0] + [p.size for p in parts])
+    dev_part = lambda j, cols: tab_dev[int(cuts[j]):int(cuts[j + 1])].view(-1, cols) if cols else tab_dev[int(cuts[j]):int(cuts[j + 1])]
+    # samples
+    buf = torch.empty(n_buf, dtype=torch.float32, device=dev)
+    if n_host:
+        stage = torch.empty(n_host, dtype=torch.float32, pin_memory=True)
+        for i in order:
+            x = clips[i][0]
+            if not x.is_cuda:
+                stage[raw_off[i]:raw_off[i] + x.numel()].view(x.shape).copy_(x)
+        buf[:n_host].copy_(stage, non_blocking=True)
+    for i in order:
+        x = clips[i][0]
+        if x.is_cuda:
+            buf[raw_off[i]:raw_off[i] + x.numel()].view(x.shape).copy_(x)
+    calls = 0
+    for j, (up, down, base, total, _) in enumerate(group_tabs):
+        h, half = resample.filter_for(up, down, dev)
+        device_ops.resample_poly_tracks(buf, dev_part(j, 4), total, up, down, h, half, buf[base:base + total])
+        calls += 1
+    g = len(group_tabs)
+    rows = device_ops.chunk_gather_tracks(buf, dev_part(g, 3), win, hop)
+    preds = infer_rows(eng, rows, dev_part(g + 1, 0), SEED, lowpass=bool(lowpass))
+    y = device_ops.wola_tracks(preds, dev_part(g + 2, 5), total_out, win, hop)
+    calls += 3
+    if out_tab is not None:
+        h, half = resample.filter_for(up_o, down_o, dev)
+        y = device_ops.resample_poly_tracks(y, dev_part(g + 3, 4), total_res, up_o, down_o, h, half,
+                                            torch.empty(total_res, dtype=torch.float32, device=dev))
+        calls += 1
+    w = _Wave()
+    w.host = torch.empty(y.numel(), dtype=torch.float32, pin_memory=True)
+    w.host.copy_(y, non_blocking=True)
+    w.event = torch.cuda.Event()
+    w.event.record()
+    w.clip_out, w.clips, w.rows, w.calls = clip_out, list(idx), wt["n_rows"], calls
+    return w
+
+
+def upscale_many(clips, lowpass, output_sr: int = 48000, *, win: int = audio_glue.CHUNK_SAMPLES, hop: int = audio_glue.HOP_SAMPLES,
+                 max_rows: Optional[int] = None, eng: Optional[FlashSREngine] = None, stats: Optional[dict] = None) -> List[torch.Tensor]:
+    """Many clips through FlashSR in packed waves.  clips: [([C,T] float32 tensor on the host or the device, sr)], channel counts,
+    lengths and rates free; -> [C, T_out] float32 host tensors in input order, each what the node's flow gives the clip alone up to
+    fp32 round-off from tile choices (they follow a forward's row count; one clip alone in its wave: the same bits).
+
+    Per wave (plan_waves): one pinned upload of the samples and one of the tables, one egr_resample_poly_tracks per source rate other
+    than 48 kHz, one egr_chunk_gather_tracks, one egr_flashsr_infer over all rows (ids k * C + c counted from 0 in each clip, seed SEED),
+    one egr_wola_tracks, one egr_resample_poly_tracks when output_sr != 48000, one download: the number of library calls follows the
+    number of rates, not of clips.  Wave n + 1 is enqueued before the host waits for wave n's download (one stream, one event per
+    wave).  A clip without samples, or of a shape the single-clip flow rejects, goes through that flow and gets its result or its
+    error (the error names the clip's index).  stats, when given, receives waves (clip indices per wave), rows and library_calls
+    (one entry per wave)."""
+    win, hop, output_sr = int(win), int(hop), int(output_sr)
+    native.require_device()
+    eng = eng or ensure_ready()
+    if win != eng.cfg.chunk:
+        raise RuntimeError(f"chunk length {win} != model chunk {eng.cfg.chunk}")
+    clips = [(x, int(sr)) for x, sr in clips]
+    packed = [torch.is_tensor(x) and x.dim() == 2 and x.shape[0] >= 1 and x.shape[1] >= 1 and x.is_floating_point() and sr >= 1
+              for x, sr in clips]
+    row_counts = [clip_rows(x.shape[0], x.shape[1], sr, win, hop) if ok else 0 for (x, sr), ok in zip(clips, packed)]
+    waves = plan_waves(row_counts, max_rows)
+    results: List[Optional[torch.Tensor]] = [None] * len(clips)
+    done: List[Tuple[List[int], int, int]] = []               # (clip indices, rows, library calls) per finished wave
+
+    def finish(w: _Wave):
+        w.event.synchronize()
+        for i, (off, Cn, T) in zip(w.clips, w.clip_out):
+            results[i] = w.host[off:off + Cn * T].view(Cn, T).clone()
+        w.host = None                                           # the pinned buffer goes back before the next wave asks for one
+        done.append((w.clips, w.rows, w.calls))
+
+    with torch.cuda.device(eng.dev):
+        for i, ((x, sr), ok) in enumerate(zip(clips, packed)):
+            if not ok:
+                try:
+                    results[i] = _upscale_single(torch.as_tensor(x), sr, bool(lowpass), output_sr, win, hop, eng)
+                except Exception as ex:      # noqa: BLE001 -- the single-clip flow's own error, with the clip's place in the list
+                    raise RuntimeError(f"clip {i}: {ex}") from ex
+        pending = None
+        for idx in waves:
+            cur = _enqueue_wave(eng, clips, idx, bool(lowpass), output_sr, win, hop)
+            if pending is not None:
+                finish(pending)
+            pending = cur
+        if pending is not None:
+            finish(pending)
+    if stats is not None:
+        stats["waves"] = [w[0] for w in done]
+        stats["rows"] = [w[1] for w in done]
+        stats["library_calls"] = [w[2] for w in done]
+    return results

@@ -86,6 +86,9 @@ SIGNATURES = {
     "egr_wola_stitch": (_i, [_vp, _i, _i, _i64, _i64, _i64, _i64, _vp, _vp, _vp]),
     "egr_chunk_gather": (_i, [_vp, _i, _i64, _i64, _i64, _i, _i, _vp, _vp]),
     "egr_resample_poly": (_i, [_vp, _i, _i64, _i, _i, _vp, _i, _vp, _i64, _vp]),
+    "egr_resample_poly_tracks": (_i, [_vp, _vp, _i, _i64, _i, _i, _vp, _i, _vp, _vp]),
+    "egr_chunk_gather_tracks": (_i, [_vp, _vp, _i, _i64, _i64, _vp, _vp]),
+    "egr_wola_tracks": (_i, [_vp, _vp, _i, _i64, _i64, _i64, _i64, _vp, _vp, _vp]),
     "egr_conv_nhwc": (_i, [_vp] * 6 + [_i] * 15 + [_f, _vp]),
     "egr_conv_nhwc_placed": (_i, [_vp] * 6 + [_i] * 15 + [_f] + [_i] * 6 + [_vp]),
     "egr_split3_pack": (_i, [_vp, _vp, _i64, _i, _vp]),

@@ -37,6 +37,15 @@ def rates(src_sr: int, dst_sr: int):
     return int(dst_sr) // g, int(src_sr) // g
 
 
+def filter_for(up: int, down: int, device):
+    """(taps on `device`, half) of design_filter(up, down), designed once per (up, down, device)."""
+    key = (up, down, str(device))
+    if key not in _FILTERS:
+        h, half = design_filter(up, down)
+        _FILTERS[key] = (torch.from_numpy(h).to(device), half)
+    return _FILTERS[key]
+
+
 def resample_hq(x_ct: torch.Tensor, src_sr: int, dst_sr: int) -> torch.Tensor:
     """[C,T] float32 CUDA -> [C, ceil(T*up/down)] float32 CUDA."""
     if int(src_sr) == int(dst_sr):
@@ -45,11 +54,7 @@ def resample_hq(x_ct: torch.Tensor, src_sr: int, dst_sr: int) -> torch.Tensor:
         raise RuntimeError("resample_hq wants a [C,T] tensor on the GPU")
     x = x_ct.to(torch.float32).contiguous()
     up, down = rates(src_sr, dst_sr)
-    key = (up, down, str(x.device))
-    if key not in _FILTERS:
-        h, half = design_filter(up, down)
-        _FILTERS[key] = (torch.from_numpy(h).to(x.device), half)
-    h, half = _FILTERS[key]
+    h, half = filter_for(up, down, x.device)
     C, n_in = x.shape
     n_out = (n_in * up + down - 1) // down
     y = torch.empty((C, n_out), dtype=torch.float32, device=x.device)

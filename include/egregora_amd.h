@@ -369,6 +369,29 @@ int egr_chunk_gather(const float* x, int channels, int64_t total, int64_t win, i
 int egr_resample_poly(const float* x, int channels, int64_t n_in, int up, int down, const float* h, int half, float* y,
                       int64_t n_out, void* stream);
 
+/* The three calls above for MANY clips at once.  A track is one channel of one clip; tracks lie in flat float buffers at 64-bit
+ * offsets that small device tables of int64 give (row-major, built by the host, read by the kernels).  Per output sample the
+ * arithmetic is the single-clip call's own (one set of device functions serves both), so each track's output is bit-equal to
+ * that call on the track alone.  Work is mapped by a flat index over the samples a call writes: its cost follows the sum of the
+ * track lengths, not the longest track, and no grid dimension counts tracks or rows (any n_tracks / n_rows that fits an int).
+ * The tables are not validated (that would need a host synchronisation): the offsets must stay inside the buffers.  No atomics;
+ * only enqueues work on `stream`.
+ *
+ * egr_resample_poly_tracks -- one rate group, every track shares (up, down, h, half):
+ *   tracks [n_tracks][4] = (in offset into x, n_in >= 1, out offset into y, n_out = ceil(n_in*up/down)); the out offsets ascend
+ *   back to back from 0 (out[t+1] = out[t] + n_out[t]) and end at total_out; y[0 .. total_out) is written.
+ * egr_chunk_gather_tracks -- chunks [n_rows][win], row r = x[off + k*hop .. + win) of its track, zero beyond the track's length:
+ *   rows [n_rows][3] = (track offset into x, track length, chunk index k).
+ * egr_wola_tracks -- egr_wola_stitch per track on preds [.][lp]; chunk k of a track is row first_row + k*row_stride:
+ *   tracks [n_tracks][5] = (first row, row stride = the clip's channel count, n_chunks >= 1, total >= 1, out offset into out); the
+ *   out offsets ascend back to back from 0 and end at total_out; out[0 .. total_out) is written. */
+int egr_resample_poly_tracks(const float* x, const int64_t* tracks, int n_tracks, int64_t total_out, int up, int down,
+                             const float* h, int half, float* y, void* stream);
+int egr_chunk_gather_tracks(const float* x, const int64_t* rows, int n_rows, int64_t win, int64_t hop, float* chunks,
+                            void* stream);
+int egr_wola_tracks(const float* preds, const int64_t* tracks, int n_tracks, int64_t total_out, int64_t lp, int64_t win,
+                    int64_t hop, const float* window, float* out, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * FlashSR network operators (channels-last activations, exact fp32).  Together they stand in for the
  * upstream call `self._model(x, lowpass_input=...)` at egregora_audio_super_resolution.py:366-369; the
