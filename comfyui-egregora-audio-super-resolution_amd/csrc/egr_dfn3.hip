@@ -12,6 +12,9 @@
 //   k_dfn_synth      : libdf frame_synthesis (unnormalised inverse real DFT in double, window); k_dfn_ola: overlap-add + trim
 // Work is enqueued on the caller's stream; nothing synchronises (the workspace grows with hipMallocAsync on that stream).
 // DeepFilterNet2 (egr_dfn2_*) reuses these kernels and the host path around them; its own kernels follow them.
+// Many clips in one ragged pass (egr_dfn*_enhance_tracks): the kernels that look along the frame axis are templates on
+// TRK; TRK = false is the uniform [C][nF] form above, TRK = true finds a row's track and its frame within the track in the Tracks
+// tables.  The arithmetic is stated once, in the shared body.
 #include <math.h>
 #include <string.h>
 
@@ -35,16 +38,50 @@ constexpr int GRU_PER_THREAD = GRU_TASKS * GRU_K;           // 192
 static_assert(GRU_NGLB % GRU_K == 0 && GRU_NGLB > 0, "streamed W_hh part is whole tasks");
 constexpr int DFN_LDS_MAX = 152 * 1024;                     // dynamic LDS cap: a gfx950 CU's 160 KiB minus room for static arrays
 
+// ------------------------------------------------------------------------------------------------ tracks
+// Device tables of a tracks call.  A track is one channel of one clip; track b's nF_b frames are rows [foff[b], foff[b + 1]) of every
+// workspace buffer (R = foff[n] rows in all), its n_b samples sit at xoff[b] of x48 / y and at [soff[b], soff[b + 1]) of the flat index
+// over all output samples.  n = 0: not a tracks call.
+struct Tracks {
+    const int* foff = nullptr;             // [n + 1]
+    const int* trk = nullptr;              // [R] the track of a packed row
+    const int64_t* xoff = nullptr;         // [n]
+    const int64_t* soff = nullptr;         // [n + 1]
+    int n = 0;
+};
+
+// the track whose samples hold flat index i: the largest b < n with soff[b] <= i
+__device__ __forceinline__ int track_of(const int64_t* __restrict__ soff, int n, int64_t i) {
+    int lo = 0, hi = n;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (soff[mid] <= i) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
 // ------------------------------------------------------------------------------------------------ analysis / features
 // Block (f, b) analyses frame f0 + f of channel b into row f of spec [C][nF][Fq] (f0 = 0: the whole file; a segment otherwise).
+// TRK: block r analyses packed row r, frame r - foff[b] of its track b (T, nF, f0 unused).
+template <bool TRK>
 __global__ __launch_bounds__(256) void k_dfn_analysis(const float* __restrict__ x, int64_t T, int nF, int64_t f0, int N, int hop,
                                                        const double2* __restrict__ tw, const float* __restrict__ win, float wnorm,
-                                                       float2* __restrict__ spec) {
+                                                       float2* __restrict__ spec, Tracks tk) {
     extern __shared__ double sm[];
     double* fr = sm;                       // N windowed samples
     double2* tws = (double2*)(sm + N);     // N twiddles
-    const int f = blockIdx.x, b = blockIdx.y, Fq = N / 2 + 1;
+    const int Fq = N / 2 + 1;
+    int f = blockIdx.x, b = blockIdx.y;
+    int64_t row = (int64_t)b * nF + f;
     const float* xb = x + (int64_t)b * T;
+    if constexpr (TRK) {
+        row = blockIdx.x;
+        b = tk.trk[row];
+        f = (int)row - tk.foff[b];
+        xb = x + tk.xoff[b];
+        T = tk.soff[b + 1] - tk.soff[b];
+        f0 = 0;
+    }
     const int64_t s0 = (f0 + f) * hop - (N - hop);
     for (int n = threadIdx.x; n < N; n += blockDim.x) {
         const int64_t s = s0 + n;
@@ -62,7 +99,7 @@ __global__ __launch_bounds__(256) void k_dfn_analysis(const float* __restrict__ 
             idx += k;
             if (idx >= N) idx -= N;
         }
-        spec[((int64_t)b * nF + f) * Fq + k] = make_float2((float)(re * (double)wnorm), (float)(im * (double)wnorm));
+        spec[row * Fq + k] = make_float2((float)(re * (double)wnorm), (float)(im * (double)wnorm));
     }
 }
 
@@ -85,25 +122,36 @@ __global__ void k_dfn_erb_db(const float2* __restrict__ spec, int64_t rows, int 
 // ([C][nD] rows) when that is >= 0; rows [zlo, zhi) of the destination are zeroed.  The whole file: src0 = 0, cnt = nS = nD = nF,
 // shift = -la, zlo = max(nF - la, 0), zhi = nF, state null.  A segment continues the lane states in state [C][E + nbdf] (read unless
 // `init`, which starts from the linspace values; written back at the end).
+// TRK: C tracks; lane (b, l) scans its track's own rows [foff[b], foff[b + 1]) as a whole file of that many frames (shift = -la, the
+// zeroed tail the track's last la rows; init, no state).
 struct ScanArgs {
     const float* db; const float2* spec; float* ferb; float2* fspec; float* state;
     int C, nS, src0, cnt, nD, shift, zlo, zhi, Fq, E, nbdf, la, init;
     float alpha;
+    const int* foff;
 };
 
+template <bool TRK>
 __global__ void k_dfn_norm_scan(ScanArgs p) {
-    const int E = p.E, nbdf = p.nbdf, Fq = p.Fq, cnt = p.cnt;
+    const int E = p.E, nbdf = p.nbdf, Fq = p.Fq;
     const int lanes = E + nbdf;
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= p.C * lanes) return;
     const int b = i / lanes, l = i - b * lanes;
     const float a = p.alpha, a1 = 1.f - p.alpha;
     constexpr int U = 16;
+    int cnt = p.cnt, zlo = p.zlo, zhi = p.zhi;
+    int64_t srow = (int64_t)b * p.nS + p.src0, drow = (int64_t)b * p.nD;      // rows of input 0 in db / spec and of output 0
+    if constexpr (TRK) {
+        srow = drow = p.foff[b];
+        cnt = zhi = p.foff[b + 1] - p.foff[b];
+        zlo = cnt - p.la > 0 ? cnt - p.la : 0;
+    }
     if (l < E) {
         float s = -60.f + (-90.f + 60.f) * (E > 1 ? (float)l / (float)(E - 1) : 0.f);
         if (!p.init) s = p.state[i];
-        const float* src = p.db + ((int64_t)b * p.nS + p.src0) * E + l;
-        float* dst = p.ferb + (int64_t)b * p.nD * E + l;
+        const float* src = p.db + srow * E + l;
+        float* dst = p.ferb + drow * E + l;
         for (int t0 = 0; t0 < cnt; t0 += U) {
             float v[U];
 #pragma unroll
@@ -117,14 +165,14 @@ __global__ void k_dfn_norm_scan(ScanArgs p) {
                 }
             }
         }
-        for (int t = p.zlo; t < p.zhi; ++t) dst[(int64_t)t * E] = 0.f;
+        for (int t = zlo; t < zhi; ++t) dst[(int64_t)t * E] = 0.f;
         if (p.state) p.state[i] = s;
     } else {
         const int f = l - E;
         float s = 0.001f + (0.0001f - 0.001f) * (nbdf > 1 ? (float)f / (float)(nbdf - 1) : 0.f);
         if (!p.init) s = p.state[i];
-        const float2* src = p.spec + ((int64_t)b * p.nS + p.src0) * Fq + f;
-        float2* dst = p.fspec + (int64_t)b * p.nD * nbdf + f;
+        const float2* src = p.spec + srow * Fq + f;
+        float2* dst = p.fspec + drow * nbdf + f;
         for (int t0 = 0; t0 < cnt; t0 += U) {
             float2 v[U];
 #pragma unroll
@@ -139,7 +187,7 @@ __global__ void k_dfn_norm_scan(ScanArgs p) {
                 }
             }
         }
-        for (int t = p.zlo; t < p.zhi; ++t) dst[(int64_t)t * nbdf] = make_float2(0.f, 0.f);
+        for (int t = zlo; t < zhi; ++t) dst[(int64_t)t * nbdf] = make_float2(0.f, 0.f);
         if (p.state) p.state[i] = s;
     }
 }
@@ -147,10 +195,13 @@ __global__ void k_dfn_norm_scan(ScanArgs p) {
 // ------------------------------------------------------------------------------------------------ convolutions (NHWC: [B][T][F][C])
 // t0 is the global frame index of row 0 of x and y (0: the whole file), hist [B][kt - 1][Fin][Cin] the kt - 1 input rows in front of
 // row 0 (read only where the global index is >= 0; null with t0 = 0).
+// TRK (B = 1, T = R packed rows, t0 = 0, no hist): a row's frame index is the one within its track, so the rows in front of a track's
+// frame 0, which are the previous track's, are skipped like the rows in front of a file.
 struct ConvArgs {
     const float* x; const float* w; const float* scale; const float* shift; const float* res; float* y; const float* hist;
     int64_t t0;
     int B, T, Fin, Cin, Fout, Cout, groups, kt, kf, fstride, fpad, transposed, act;
+    const int* trk; const int* foff;
 };
 
 __device__ __forceinline__ float act_fn(float v, int act) {
@@ -160,6 +211,7 @@ __device__ __forceinline__ float act_fn(float v, int act) {
     return v;
 }
 
+template <bool TRK>
 __global__ void k_dfn_conv(ConvArgs p) {
     const int64_t n = (int64_t)p.B * p.T * p.Fout * p.Cout;
     const int cig = p.Cin / p.groups, cog = p.Cout / p.groups;
@@ -168,8 +220,13 @@ __global__ void k_dfn_conv(ConvArgs p) {
         int64_t r = i / p.Cout;
         const int fo = (int)(r % p.Fout);
         r /= p.Fout;
-        const int t = (int)(r % p.T);
+        int t = (int)(r % p.T);
         const int b = (int)(r / p.T);
+        int64_t r0 = (int64_t)b * p.T;             // the row of frame 0
+        if constexpr (TRK) {
+            r0 = p.foff[p.trk[r]];
+            t = (int)(r - r0);
+        }
         const int g = co / cog;
         float acc = 0.f;
         if (!p.transposed) {
@@ -177,7 +234,7 @@ __global__ void k_dfn_conv(ConvArgs p) {
             for (int it = 0; it < p.kt; ++it) {
                 const int ti = t - (p.kt - 1) + it;
                 if (p.t0 + ti < 0) continue;
-                const float* xr = ti >= 0 ? p.x + ((int64_t)b * p.T + ti) * p.Fin * p.Cin
+                const float* xr = ti >= 0 ? p.x + (r0 + ti) * p.Fin * p.Cin
                                           : p.hist + ((int64_t)b * (p.kt - 1) + (ti + p.kt - 1)) * p.Fin * p.Cin;
                 for (int j = 0; j < p.kf; ++j) {
                     const int fi = fo * p.fstride - p.fpad + j;
@@ -194,7 +251,7 @@ __global__ void k_dfn_conv(ConvArgs p) {
                 if (num < 0 || num % p.fstride) continue;
                 const int fi = num / p.fstride;
                 if (fi >= p.Fin) continue;
-                const float* xv = p.x + (((int64_t)b * p.T + t) * p.Fin + fi) * p.Cin + g * cig;
+                const float* xv = p.x + ((r0 + t) * p.Fin + fi) * p.Cin + g * cig;
                 for (int c = 0; c < cig; ++c) acc = fmaf(xv[c], p.w[(((int64_t)(g * cig + c)) * cog + col) * p.kf + j], acc);
             }
         }
@@ -238,15 +295,23 @@ __global__ void k_dfn_hist_push(const float* __restrict__ x, float* hist, int B,
 // gate sums to LDS, one barrier, the H gate updates, one barrier.  proj = W_ih x + b_ih of all frames comes from one GEMM beforehand.
 // h_in [C][H] is the state in front of step 0 (null: zeros), h_out [C][H] takes the state after the last step (null: not kept); they
 // may be the same array.
+// TRK: workgroup b runs track b: its rows of proj / out start at packed row foff[b], its step count is foff[b + 1] - foff[b] (nF
+// unused).  The two table values are read once, in front of the step loop, and are dead in it.
+template <bool TRK>
 __global__ __launch_bounds__(GRU_THREADS) void k_dfn_gru(const float* __restrict__ proj, const float* __restrict__ whh_pk,
                                                           const float* __restrict__ bhh, int H, int nF, float* __restrict__ out,
-                                                          const float* h_in, float* h_out) {
+                                                          const float* h_in, float* h_out, const int* __restrict__ foff) {
     __shared__ float wl[GRU_NLDS * GRU_THREADS];
     __shared__ float hs[GRU_HMAX];
     __shared__ float gs[3 * GRU_HMAX];
     const int t = threadIdx.x, lane = t % GRU_SEG, b = blockIdx.x;
-    const float* pb = proj + (int64_t)b * nF * 3 * H;
-    float* ob = out + (int64_t)b * nF * H;
+    int64_t row0 = (int64_t)b * nF;
+    if constexpr (TRK) {
+        row0 = foff[b];
+        nF = foff[b + 1] - foff[b];
+    }
+    const float* pb = proj + row0 * 3 * H;
+    float* ob = out + row0 * H;
     float wr[GRU_NREG];
 #pragma unroll
     for (int e = 0; e < GRU_NREG; ++e) wr[e] = whh_pk[(int64_t)e * GRU_THREADS + t];
@@ -321,42 +386,67 @@ __global__ __launch_bounds__(GRU_THREADS) void k_dfn_gru(const float* __restrict
 // [C][nS] rows from global frame spec_lo.  mask, coefs (and alpha) hold [C][S] rows from global frame a; a row in front of a comes from
 // the history arrays [C][P][...] (P_m rows of mask, look rows of coefs and alpha), which hold the rows just before a.  The whole file:
 // asm_lo = spec_lo = a = 0, nA = nS = S = nF, no history.
+// TRK (C = 1, nA = nS = S = R packed rows, asm_lo = spec_lo = a = 0, no history): a row's frame and the file's length nF are those of
+// its track, so the deep-filter window stops at the track's last frame and never reads the next track's rows.
 struct AsmArgs {
     const float2* spec; const float* mask; const float* coefs; const float* alpha;
     const float* mask_h; const float* coefs_h; const float* alpha_h; const int* band_of; float2* out;
     int64_t nF, asm_lo, spec_lo, a;
     int C, nA, nS, S, P_m, Fq, E, nbdf, order, look;
+    const int* trk; const int* foff;
 };
 
-// row l of cur [C][S][len] (l >= 0) or row l + P of hist [C][P][len] (l < 0), channel b
-__device__ __forceinline__ const float* lag_row(const float* cur, const float* hist, int64_t b, int l, int S, int P, int len) {
-    return l >= 0 ? cur + (b * S + l) * len : hist + (b * P + (l + P)) * len;
+// row l of channel b's rows of cur, which start at row cb (l >= 0), or row l + P of hist [C][P][len] (l < 0)
+__device__ __forceinline__ const float* lag_row(const float* cur, const float* hist, int64_t cb, int64_t b, int l, int P, int len) {
+    return l >= 0 ? cur + (cb + l) * len : hist + (b * P + (l + P)) * len;
 }
 
+// What an assemble thread knows of its output row r: t the frame within the file (track), b the channel (track), nF its frames, cb the
+// row of frame a in mask / coefs / alpha, sb the row of frame 0 in spec (row of frame ts: sb + ts).
+struct AsmRow { int64_t t, b, nF, cb, sb; };
+
+template <bool TRK>
+__device__ __forceinline__ AsmRow asm_row(const AsmArgs& p, int64_t r) {
+    AsmRow w;
+    if constexpr (TRK) {
+        w.b = p.trk[r];
+        w.cb = w.sb = p.foff[w.b];
+        w.t = r - w.cb;
+        w.nF = p.foff[w.b + 1] - w.cb;
+    } else {
+        w.t = p.asm_lo + r % p.nA;
+        w.b = r / p.nA;
+        w.nF = p.nF;
+        w.cb = w.b * p.S;
+        w.sb = w.b * p.nS - p.spec_lo;
+    }
+    return w;
+}
+
+template <bool TRK>
 __global__ void k_dfn_assemble(AsmArgs p) {
     const int Fq = p.Fq, nbdf = p.nbdf, order = p.order, look = p.look;
     const int64_t n = (int64_t)p.C * p.nA * Fq;
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         const int f = (int)(i % Fq);
-        const int64_t r = i / Fq;                  // b * nA + local frame
-        const int64_t t = p.asm_lo + r % p.nA;     // global frame
-        const int64_t b = r / p.nA;
+        const AsmRow w = asm_row<TRK>(p, i / Fq);
+        const int64_t t = w.t, b = w.b;            // global frame, channel
         const int la = (int)(t - p.a);             // row of mask / coefs relative to a
         float2 y;
         if (f < nbdf) {
-            const float* c = lag_row(p.coefs, p.coefs_h, b, la, p.S, look, nbdf * 2 * order) + f * 2 * order;
+            const float* c = lag_row(p.coefs, p.coefs_h, w.cb, b, la, look, nbdf * 2 * order) + f * 2 * order;
             float re = 0.f, im = 0.f;
             for (int k = 0; k < order; ++k) {
                 const int64_t ts = t - (order - 1 - look) + k;
-                if (ts < 0 || ts >= p.nF) continue;
-                const float2 s = p.spec[(b * p.nS + (ts - p.spec_lo)) * Fq + f];
+                if (ts < 0 || ts >= w.nF) continue;
+                const float2 s = p.spec[(w.sb + ts) * Fq + f];
                 re = fmaf(s.x, c[2 * k], fmaf(-s.y, c[2 * k + 1], re));
                 im = fmaf(s.x, c[2 * k + 1], fmaf(s.y, c[2 * k], im));
             }
             y = make_float2(re, im);
         } else {
-            const float m = lag_row(p.mask, p.mask_h, b, la, p.S, p.P_m, p.E)[p.band_of[f]];
-            const float2 s = p.spec[(b * p.nS + (t - p.spec_lo)) * Fq + f];
+            const float m = lag_row(p.mask, p.mask_h, w.cb, b, la, p.P_m, p.E)[p.band_of[f]];
+            const float2 s = p.spec[(w.sb + t) * Fq + f];
             y = make_float2(s.x * m, s.y * m);
         }
         p.out[i] = y;
@@ -391,12 +481,23 @@ __global__ __launch_bounds__(256) void k_dfn_synth(const float2* __restrict__ sp
 // Output samples [out_lo, out_lo + cnt) of every channel of y [C][T].  frames [C][nA][N] are the synthesised frames from global frame
 // asm_lo of a file of nF frames, hist [C][ov - 1][N] the ov - 1 frames in front of them (the whole file: asm_lo = out_lo = 0, nA = nF,
 // cnt = T, no history).
+// TRK (C = 1, cnt = the samples of all tracks, asm_lo = out_lo = 0, no history): a flat index over the output samples; thread i finds
+// its track b in soff, writes sample i - soff[b] of it at y + xoff[b] and reads the track's own frames, rows foff[b] onwards.
+template <bool TRK>
 __global__ void k_dfn_ola(const float* __restrict__ frames, const float* __restrict__ hist, int C, int nA, int64_t asm_lo, int64_t nF,
-                          int N, int hop, int64_t T, int64_t out_lo, int64_t cnt, float* __restrict__ y) {
+                          int N, int hop, int64_t T, int64_t out_lo, int64_t cnt, float* __restrict__ y, Tracks tk) {
     const int64_t n = (int64_t)C * cnt;
     const int d = N - hop, ov = N / hop;
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t b = i / cnt, s = out_lo + (i - b * cnt);
+        int64_t b = i / cnt, s = out_lo + (i - b * cnt);
+        int64_t fb = b * nA, yb = b * T;           // the row of frame asm_lo in frames, the channel's first sample in y
+        if constexpr (TRK) {
+            b = track_of(tk.soff, tk.n, i);
+            s = i - tk.soff[b];
+            fb = tk.foff[b];
+            nF = tk.foff[b + 1] - fb;
+            yb = tk.xoff[b];
+        }
         const int64_t o = s + d;
         const int64_t k = o / hop;
         const int j = (int)(o - k * hop);
@@ -405,9 +506,9 @@ __global__ void k_dfn_ola(const float* __restrict__ frames, const float* __restr
             const int64_t fk = k - m;
             if (fk < 0 || fk >= nF) continue;
             const int64_t lf = fk - asm_lo;
-            acc += lf >= 0 ? frames[(b * nA + lf) * N + m * hop + j] : hist[(b * (ov - 1) + (lf + ov - 1)) * N + m * hop + j];
+            acc += lf >= 0 ? frames[(fb + lf) * N + m * hop + j] : hist[(b * (ov - 1) + (lf + ov - 1)) * N + m * hop + j];
         }
-        y[b * T + s] = acc;
+        y[yb + s] = acc;
     }
 }
 
@@ -426,20 +527,27 @@ constexpr int G2_HMAX = 128;                // per-group width k_dfn2_gru holds 
 // step: K values of h_{t-1} from LDS (double buffer, zero beyond h), 3K FMAs, an S-lane xor sum of the three gate sums, the update
 // (every lane of the row group computes it; lane 0 stores), one barrier.  proj = W_ih x of all frames (egr_bgemm); b_ih is added here.
 // Store: layer output at its P4 position (shuffled when `shuffle`), and sum_out = sum_in + it (sum_in null: the first layer).
-template <int K>
+// TRK: a 1-D grid, workgroup b G + g runs group g of track b over its own rows [foff[b], foff[b + 1]) (nF unused).
+template <int K, bool TRK>
 __global__ __launch_bounds__(512) void k_dfn2_gru(const float* __restrict__ proj, const float* __restrict__ whh_pk,
                                                    const float* __restrict__ bih, const float* __restrict__ bhh, int G, int h, int S,
                                                    int nF, int shuffle, const float* __restrict__ sum_in, float* __restrict__ out,
-                                                   float* __restrict__ sum_out, const float* h_in, float* h_out) {
+                                                   float* __restrict__ sum_out, const float* h_in, float* h_out,
+                                                   const int* __restrict__ foff) {
     __shared__ float hs[2][G2_HMAX];
     const int t = threadIdx.x, NT = h * S, j = t / S, s = t - j * S;
-    const int g = blockIdx.x, b = blockIdx.y, H = G * h, H3 = 3 * H;
-    const float* pb = proj + (int64_t)b * nF * H3 + g * 3 * h;
+    const int g = TRK ? blockIdx.x % G : blockIdx.x, b = TRK ? blockIdx.x / G : blockIdx.y, H = G * h, H3 = 3 * H;
+    int64_t row0 = (int64_t)b * nF;
+    if constexpr (TRK) {
+        row0 = foff[b];
+        nF = foff[b + 1] - foff[b];
+    }
+    const float* pb = proj + row0 * H3 + g * 3 * h;
     const int n = g * h + j;                                   // pre-shuffle output index
     const int pos = shuffle ? (n % G) * h + n / G : n;         // P3: output g' h + j' takes pre-shuffle j' G + g'
-    float* ob = out + (int64_t)b * nF * H + pos;
-    float* sb = sum_out + (int64_t)b * nF * H + pos;
-    const float* si = sum_in ? sum_in + (int64_t)b * nF * H + pos : nullptr;
+    float* ob = out + row0 * H + pos;
+    float* sb = sum_out + row0 * H + pos;
+    const float* si = sum_in ? sum_in + row0 * H + pos : nullptr;
     float w[3 * K];
     const float* wp = whh_pk + (int64_t)g * 3 * K * NT + t;
 #pragma unroll
@@ -515,33 +623,33 @@ __global__ void k_dfn2_alpha(const float* __restrict__ c, const float* __restric
 }
 
 // P7: S_m = mask X on every bin; below nb_df Y = alpha DF(S_m) + (1 - alpha) S_m, DF the DFN3-P5 window over the masked frames.
+template <bool TRK>
 __global__ void k_dfn2_assemble(AsmArgs p) {
     const int Fq = p.Fq, nbdf = p.nbdf, order = p.order, look = p.look, E = p.E;
     const int64_t n = (int64_t)p.C * p.nA * Fq;
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         const int f = (int)(i % Fq);
-        const int64_t r = i / Fq;                  // b * nA + local frame
-        const int64_t t = p.asm_lo + r % p.nA;     // global frame
-        const int64_t b = r / p.nA;
+        const AsmRow w = asm_row<TRK>(p, i / Fq);
+        const int64_t t = w.t, b = w.b;            // global frame, channel
         const int la = (int)(t - p.a);             // row of mask / coefs / alpha relative to a
         const int band = p.band_of[f];
-        const float m = lag_row(p.mask, p.mask_h, b, la, p.S, p.P_m, E)[band];
-        const float2 s = p.spec[(b * p.nS + (t - p.spec_lo)) * Fq + f];
+        const float m = lag_row(p.mask, p.mask_h, w.cb, b, la, p.P_m, E)[band];
+        const float2 s = p.spec[(w.sb + t) * Fq + f];
         const float2 sm = make_float2(s.x * m, s.y * m);
         float2 y = sm;
         if (f < nbdf) {
-            const float* c = lag_row(p.coefs, p.coefs_h, b, la, p.S, look, nbdf * 2 * order) + f * 2 * order;
+            const float* c = lag_row(p.coefs, p.coefs_h, w.cb, b, la, look, nbdf * 2 * order) + f * 2 * order;
             float re = 0.f, im = 0.f;
             for (int k = 0; k < order; ++k) {
                 const int64_t ts = t - (order - 1 - look) + k;
-                if (ts < 0 || ts >= p.nF) continue;
-                const float ms = lag_row(p.mask, p.mask_h, b, (int)(ts - p.a), p.S, p.P_m, E)[band];
-                const float2 x = p.spec[(b * p.nS + (ts - p.spec_lo)) * Fq + f];
+                if (ts < 0 || ts >= w.nF) continue;
+                const float ms = lag_row(p.mask, p.mask_h, w.cb, b, (int)(ts - p.a), p.P_m, E)[band];
+                const float2 x = p.spec[(w.sb + ts) * Fq + f];
                 const float2 xm = make_float2(x.x * ms, x.y * ms);
                 re = fmaf(xm.x, c[2 * k], fmaf(-xm.y, c[2 * k + 1], re));
                 im = fmaf(xm.x, c[2 * k + 1], fmaf(xm.y, c[2 * k], im));
             }
-            const float a = lag_row(p.alpha, p.alpha_h, b, la, p.S, look, 1)[0], a1 = 1.f - a;
+            const float a = lag_row(p.alpha, p.alpha_h, w.cb, b, la, look, 1)[0], a1 = 1.f - a;
             y = make_float2(re * a + sm.x * a1, im * a + sm.y * a1);
         }
         p.out[i] = y;
@@ -566,6 +674,8 @@ struct Conv {                 // one convolution with its (optional) BN affine
     // a segmented call only (null / 0 in a one-pass call): the kt - 1 input rows in front of the segment, the segment's first frame
     float* hist = nullptr;
     int64_t t0 = 0;
+    // a tracks call only: the row -> track and track -> first row tables (Tracks), for the convolutions that look back in time
+    const int* trk = nullptr; const int* foff = nullptr;
 };
 
 struct DfnDims {              // the hyper-parameters the shared code reads, from egr_dfn3_config / egr_dfn2_config
@@ -593,6 +703,30 @@ struct SegState {             // what a segmented call carries besides the GRU s
 
 constexpr int N_HIST_CONV = 9;
 
+// Pinned host memory a tracks call copies its tables from, so that the copy is asynchronous, and the event behind the last such copy:
+// the next call waits for that copy alone (not for the stream's other work) before it overwrites the memory.
+struct TableStage {
+    void* p = nullptr;
+    size_t bytes = 0;
+    hipEvent_t copied = nullptr;
+    int reserve(size_t need) {
+        if (!copied) EGR_HIP(hipEventCreateWithFlags(&copied, hipEventDisableTiming));
+        else EGR_HIP(hipEventSynchronize(copied));
+        if (need <= bytes) return EGR_OK;
+        if (p) EGR_HIP(hipHostFree(p));
+        p = nullptr;
+        bytes = 0;
+        EGR_HIP(hipHostMalloc(&p, need, hipHostMallocDefault));
+        bytes = need;
+        return EGR_OK;
+    }
+    void release() {
+        if (copied) { (void)hipEventSynchronize(copied); (void)hipEventDestroy(copied); }
+        if (p) (void)hipHostFree(p);
+        p = nullptr; bytes = 0; copied = nullptr;
+    }
+};
+
 struct DfnCore {
     DfnDims d;
     int device = 0, Fq = 0, embd = 0;
@@ -603,9 +737,12 @@ struct DfnCore {
     Conv erb0, erb_dw[3], erb_pw[3], df0, df0_pw, df1_dw, df1_pw, path[4], ct_dw[3], ct_pw[3], out0, convp, convp_pw;
     // workspace of the last call
     Workspace ws;
+    TableStage stage;                       // tracks calls only
     int lastC = 0, lastF = 0; int64_t lastT = 0;
     bool segmented = false;                 // the last call was a segmented one (its buffers hold the last segment only)
+    bool packed = false;                    // the last call was a tracks call (its buffers hold packed rows, not [C][nF])
     SegState sg;
+    Tracks tk;                              // a tracks call only (n = 0 otherwise): its tables, which live in the workspace
     Bufs B;
     // GRU layers in the order encoder (1), ERB decoder (emb_num_layers - 1), DF decoder (df_num_layers)
     int ngru() const { return d.emb_num_layers + d.df_num_layers; }
@@ -668,6 +805,7 @@ int conv(const Conv& L, const float* x, float* y, int B, int T, int Fin, int fst
     p.x = x; p.w = L.w; p.scale = L.scale; p.shift = L.shift; p.res = res; p.y = y; p.hist = L.hist; p.t0 = L.t0;
     p.B = B; p.T = T; p.Fin = Fin; p.Cin = L.cin; p.Cout = L.cout; p.groups = L.groups; p.kt = L.kt; p.kf = L.kf; p.fstride = fstride;
     p.transposed = L.transposed; p.act = act;
+    p.trk = L.trk; p.foff = L.foff;
     if (L.transposed) {
         p.fpad = L.kf / 2;
         p.Fout = (Fin - 1) * fstride - 2 * p.fpad + (L.kf - 1) + L.kf / 2 + 1;
@@ -676,7 +814,9 @@ int conv(const Conv& L, const float* x, float* y, int B, int T, int Fin, int fst
         p.Fout = (Fin + 2 * p.fpad - L.kf) / fstride + 1;
     }
     if (Fout_ret) *Fout_ret = p.Fout;
-    hipLaunchKernelGGL(k_dfn_conv, dim3(grid_for((int64_t)B * T * p.Fout * p.Cout)), dim3(256), 0, st, p);
+    const dim3 grid(grid_for((int64_t)B * T * p.Fout * p.Cout));
+    if (L.trk && L.kt > 1) hipLaunchKernelGGL(k_dfn_conv<true>, grid, dim3(256), 0, st, p);        // kt = 1: a row reads its own row only
+    else hipLaunchKernelGGL(k_dfn_conv<false>, grid, dim3(256), 0, st, p);
     if (L.hist) hist_push(x, L.hist, B, T, L.kt - 1, Fin * L.cin, st);
     return EGR_OK;
 }
@@ -695,10 +835,11 @@ int rows_op(const float* a, const float* bias, const float* res, float* y, int64
 // ---- run stages, in the order both run()s call them; the models' own launches come between encoder_convs and erb_decoder_convs and
 // ---- between erb_decoder_convs and df_pathway_and_coefs, their assemble kernel before synthesis
 // Grows the workspace to `need` bytes on `st` and notes the call's shape; the caller lays its buffers out over m.ws afterwards.
-int ensure_workspace(DfnCore& m, size_t need, int C, int nF, int64_t T, bool segmented, hipStream_t st) {
+int ensure_workspace(DfnCore& m, size_t need, int C, int nF, int64_t T, bool segmented, hipStream_t st, bool packed = false) {
     EGR_TRY(m.ws.grow(need, st));
     m.lastC = C; m.lastF = nF; m.lastT = T;
     m.segmented = segmented;
+    m.packed = packed;
     return EGR_OK;
 }
 
@@ -708,11 +849,25 @@ void features(const DfnCore& m, const float* x, int C, int nF, int64_t T, hipStr
     const Bufs& B = m.B;
     const int N = d.fft_size, E = d.nb_erb, nb = d.nb_df, la = d.conv_lookahead;
     const int64_t R = (int64_t)C * nF;
-    hipLaunchKernelGGL(k_dfn_analysis, dim3(nF, C), dim3(256), (size_t)N * 24, st, x, T, nF, (int64_t)0, N, d.hop_size, m.tw, m.win, m.wnorm,
-                       B.spec);
+    hipLaunchKernelGGL(k_dfn_analysis<false>, dim3(nF, C), dim3(256), (size_t)N * 24, st, x, T, nF, (int64_t)0, N, d.hop_size, m.tw, m.win,
+                       m.wnorm, B.spec, Tracks());
     hipLaunchKernelGGL(k_dfn_erb_db, dim3(grid_for(R * E)), dim3(256), 0, st, B.spec, R, m.Fq, E, m.band_lo, m.band_w, B.db);
-    ScanArgs p{B.db, B.spec, B.ferb, B.fspec, nullptr, C, nF, 0, nF, nF, -la, nF - la > 0 ? nF - la : 0, nF, m.Fq, E, nb, la, 1, d.norm_alpha};
-    hipLaunchKernelGGL(k_dfn_norm_scan, dim3((C * (E + nb) + 63) / 64), dim3(64), 0, st, p);
+    ScanArgs p{B.db, B.spec, B.ferb, B.fspec, nullptr, C, nF, 0, nF, nF, -la, nF - la > 0 ? nF - la : 0, nF, m.Fq, E, nb, la, 1, d.norm_alpha,
+               nullptr};
+    hipLaunchKernelGGL(k_dfn_norm_scan<false>, dim3((C * (E + nb) + 63) / 64), dim3(64), 0, st, p);
+}
+
+// The same over the R packed rows of a tracks call (m.tk): every track is a whole file of its own.
+void features_tracks(const DfnCore& m, const float* x, int64_t R, hipStream_t st) {
+    const DfnDims& d = m.d;
+    const Bufs& B = m.B;
+    const int N = d.fft_size, E = d.nb_erb, nb = d.nb_df, la = d.conv_lookahead;
+    hipLaunchKernelGGL(k_dfn_analysis<true>, dim3((unsigned)R), dim3(256), (size_t)N * 24, st, x, (int64_t)0, 0, (int64_t)0, N, d.hop_size,
+                       m.tw, m.win, m.wnorm, B.spec, m.tk);
+    hipLaunchKernelGGL(k_dfn_erb_db, dim3(grid_for(R * E)), dim3(256), 0, st, B.spec, R, m.Fq, E, m.band_lo, m.band_w, B.db);
+    ScanArgs p{B.db, B.spec, B.ferb, B.fspec, nullptr, m.tk.n, 0, 0, 0, 0, -la, 0, 0, m.Fq, E, nb, la, 1, d.norm_alpha, m.tk.foff};
+    // one lane per (track, band / bin); not a grid-stride kernel (at most 2^18 tracks x 2113 lanes: the index fits an int)
+    hipLaunchKernelGGL(k_dfn_norm_scan<true>, dim3((unsigned)(((int64_t)m.tk.n * (E + nb) + 63) / 64)), dim3(64), 0, st, p);
 }
 
 struct EncWidths { int F1 = 0, F2 = 0, F3 = 0, Fc = 0; };      // frequency widths of e1, e2, e3 and c1
@@ -768,21 +923,24 @@ int df_pathway_and_coefs(const DfnCore& m, int C, int nF, const float* bias, hip
 }
 
 // spec_e (written by the model's assemble kernel: nA frames from global frame asm_lo of nF) -> y[out_lo, out_lo + cnt).  The whole
-// file: nA = nF, asm_lo = out_lo = 0, cnt = T.
+// file: nA = nF, asm_lo = out_lo = 0, cnt = T.  A tracks call (m.tk): C = 1, nA = the packed rows, cnt = the samples of all tracks.
 int synthesis(const DfnCore& m, int C, int nA, int64_t asm_lo, int64_t nF, int64_t T, int64_t out_lo, int64_t cnt, float* y,
               hipStream_t st) {
     const int N = m.d.fft_size;
     if (nA > 0)
         hipLaunchKernelGGL(k_dfn_synth, dim3(nA, C), dim3(256), (size_t)(m.Fq + N) * 16, st, m.B.spec_e, nA, N, m.tw, m.win, m.B.frames);
-    if (cnt > 0)
-        hipLaunchKernelGGL(k_dfn_ola, dim3(grid_for((int64_t)C * cnt)), dim3(256), 0, st, m.B.frames, m.sg.frames_h, C, nA, asm_lo, nF, N,
-                           m.d.hop_size, T, out_lo, cnt, y);
+    if (cnt > 0 && m.tk.n)
+        hipLaunchKernelGGL(k_dfn_ola<true>, dim3(grid_for((int64_t)C * cnt)), dim3(256), 0, st, m.B.frames, m.sg.frames_h, C, nA, asm_lo, nF,
+                           N, m.d.hop_size, T, out_lo, cnt, y, m.tk);
+    else if (cnt > 0)
+        hipLaunchKernelGGL(k_dfn_ola<false>, dim3(grid_for((int64_t)C * cnt)), dim3(256), 0, st, m.B.frames, m.sg.frames_h, C, nA, asm_lo, nF,
+                           N, m.d.hop_size, T, out_lo, cnt, y, Tracks());
     EGR_HIP(hipGetLastError());
     return EGR_OK;
 }
 
 // The arguments of the models' assemble kernels: nA frames from asm_lo; spec holds nS frames from spec_lo, mask / coefs / alpha S
-// frames from a (one-pass: everything the whole file from 0).
+// frames from a (one-pass: everything the whole file from 0; a tracks call: C = 1 and the packed rows as one file from 0).
 AsmArgs assemble_args(const DfnCore& m, const float* alpha, int C, int64_t nF, int64_t asm_lo, int nA, int64_t spec_lo, int nS,
                       int64_t a, int S) {
     const DfnDims& d = m.d;
@@ -793,6 +951,7 @@ AsmArgs assemble_args(const DfnCore& m, const float* alpha, int C, int64_t nF, i
     p.nF = nF; p.asm_lo = asm_lo; p.spec_lo = spec_lo; p.a = a;
     p.C = C; p.nA = nA; p.nS = nS; p.S = S; p.P_m = d.df_order - 1; p.Fq = m.Fq; p.E = d.nb_erb; p.nbdf = d.nb_df; p.order = d.df_order;
     p.look = d.df_lookahead;
+    p.trk = m.tk.trk; p.foff = m.tk.foff;
     return p;
 }
 
@@ -940,7 +1099,8 @@ int upload(DfnCore& m, const char* who, const Image& im) {
         set_error("%s: fft_size %d needs %zu / %zu bytes of LDS (limit %d)", who, N, lds_an, lds_syn, DFN_LDS_MAX);
         ea = hipErrorInvalidValue;
     }
-    if (ea == hipSuccess) ea = hipFuncSetAttribute((const void*)k_dfn_analysis, hipFuncAttributeMaxDynamicSharedMemorySize, DFN_LDS_MAX);
+    if (ea == hipSuccess) ea = hipFuncSetAttribute((const void*)k_dfn_analysis<false>, hipFuncAttributeMaxDynamicSharedMemorySize, DFN_LDS_MAX);
+    if (ea == hipSuccess) ea = hipFuncSetAttribute((const void*)k_dfn_analysis<true>, hipFuncAttributeMaxDynamicSharedMemorySize, DFN_LDS_MAX);
     if (ea == hipSuccess) ea = hipFuncSetAttribute((const void*)k_dfn_synth, hipFuncAttributeMaxDynamicSharedMemorySize, DFN_LDS_MAX);
     if (ea != hipSuccess) {
         if (lds_an <= (size_t)DFN_LDS_MAX && lds_syn <= (size_t)DFN_LDS_MAX)
@@ -980,6 +1140,7 @@ int enhance_checks(const DfnCore* m, const char* who, const float* x48, int chan
 void destroy(DfnCore& m) {
     DeviceScope dev(m.device);
     m.ws.release();
+    m.stage.release();
     if (m.dev_w) (void)hipFree(m.dev_w);
 }
 
@@ -1014,6 +1175,7 @@ template <class Own>
 int stage_copy(const DfnCore& m, const char* who, int stage, float* dst, int64_t capacity, int64_t* count, void* stream, Own own) {
     EGR_CHECK(m.ws.p, EGR_ERR_ARG, "%s: no enhance call yet", who);
     EGR_CHECK(!m.segmented, EGR_ERR_ARG, "%s: the last call was segmented; stages belong to one-pass calls", who);
+    EGR_CHECK(!m.packed, EGR_ERR_ARG, "%s: the last call was a tracks call; stages belong to one-pass calls", who);
     const float* src = nullptr;
     int64_t n = 0;
     own(stage, &src, &n);
@@ -1058,7 +1220,19 @@ struct Gru {
     const float* wih = nullptr; const float* bih = nullptr; const float* bhh = nullptr; float* whh_pk = nullptr;
     int in = 0, H = 0;
     float* hst = nullptr;                   // a segmented call only: the state [C][H] across the cuts
+    const int* foff = nullptr; int ntr = 0; // a tracks call only: Tracks::foff and the number of tracks (one workgroup each)
 };
+
+// One dense layer over nF steps of C channels, or (foff) over the ntr tracks' own rows; h: the carried state or null.
+void launch_gru(const float* proj, const float* whh_pk, const float* bhh, int H, int C, int nF, float* out, float* h, const int* foff,
+                int ntr, hipStream_t st) {
+    if (foff)
+        hipLaunchKernelGGL(k_dfn_gru<true>, dim3(ntr), dim3(GRU_THREADS), 0, st, proj, whh_pk, bhh, H, 0, out, (const float*)nullptr,
+                           (float*)nullptr, foff);
+    else
+        hipLaunchKernelGGL(k_dfn_gru<false>, dim3(C), dim3(GRU_THREADS), 0, st, proj, whh_pk, bhh, H, nF, out, (const float*)h, h,
+                           (const int*)nullptr);
+}
 
 struct Dfn3 {
     egr_dfn3_config cfg;
@@ -1082,11 +1256,12 @@ int gru_layer(const Gru& g, const float* x, float* proj, float* out, int C, int 
     const int64_t R = (int64_t)C * nF;
     EGR_TRY(egr_bgemm(x, g.wih, proj, 1, 1, (int)R, 3 * g.H, g.in, g.in, g.in, 3 * g.H, 0, 0, 0, 0, 0, 0, 1, 1.f, st));
     EGR_TRY(rows_op(proj, g.bih, nullptr, proj, R * 3 * g.H, 3 * g.H, 0, st));
-    hipLaunchKernelGGL(k_dfn_gru, dim3(C), dim3(GRU_THREADS), 0, st, proj, g.whh_pk, g.bhh, g.H, nF, out, g.hst, g.hst);
+    launch_gru(proj, g.whh_pk, g.bhh, g.H, C, nF, out, g.hst, g.foff, g.ntr, st);
     return EGR_OK;
 }
 
-// features (ferb, fspec) -> mask, coefs over nF frames of C channels: the whole file, or one segment
+// features (ferb, fspec) -> mask, coefs over nF frames of C channels: the whole file, or one segment; or, with the tables bound
+// (bind_tracks), over C = 1 x nF = R packed rows
 int network(Dfn3& m, int C, int nF, hipStream_t st) {
     const egr_dfn3_config& c = m.cfg;
     DfnCore& k = m.core;
@@ -1137,7 +1312,9 @@ int network(Dfn3& m, int C, int nF, hipStream_t st) {
 
 // mask + deep filter
 void assemble(const Dfn3& m, const AsmArgs& p, hipStream_t st) {
-    hipLaunchKernelGGL(k_dfn_assemble, dim3(grid_for((int64_t)p.C * p.nA * p.Fq)), dim3(256), 0, st, p);
+    const dim3 grid(grid_for((int64_t)p.C * p.nA * p.Fq));
+    if (p.trk) hipLaunchKernelGGL(k_dfn_assemble<true>, grid, dim3(256), 0, st, p);
+    else hipLaunchKernelGGL(k_dfn_assemble<false>, grid, dim3(256), 0, st, p);
 }
 
 // ------------------------------------------------------------------------------------------------ DeepFilterNet2
@@ -1145,6 +1322,7 @@ struct GGru {                 // one GroupedGRU layer: G GRUs of width h on inpu
     const float* wih = nullptr; const float* bih = nullptr; const float* bhh = nullptr; float* whh_pk = nullptr;
     int in = 0, H = 0, G = 1, h = 0, K = 0, S = 1, shuffle = 0;
     float* hst = nullptr;                   // a segmented call only: the state [C][H] across the cuts, groups in pre-shuffle order
+    const int* foff = nullptr; int ntr = 0; // a tracks call only: Tracks::foff and the number of tracks (gru_groups workgroups each)
     bool dense() const { return h > G2_HMAX; }
 };
 
@@ -1187,14 +1365,20 @@ int glinear(const float* x, const float* w, const float* bias, float* lin, float
     return epi(lin, bias, res, y, rows * out, out, shuf ? G : 1, act, st);
 }
 
-void launch_ggru(const GGru& g, const float* proj, const float* sum_in, float* out, float* sum_out, int C, int nF, hipStream_t st) {
-    const dim3 grid(g.G, C), block(g.h * g.S);
-    if (g.K == 16)
-        hipLaunchKernelGGL(k_dfn2_gru<16>, grid, block, 0, st, proj, g.whh_pk, g.bih, g.bhh, g.G, g.h, g.S, nF, g.shuffle, sum_in, out, sum_out,
-                           g.hst, g.hst);
+template <int K>
+void launch_ggru_k(const GGru& g, const float* proj, const float* sum_in, float* out, float* sum_out, int C, int nF, hipStream_t st) {
+    const dim3 block(g.h * g.S);
+    if (g.foff)
+        hipLaunchKernelGGL((k_dfn2_gru<K, true>), dim3((unsigned)g.G * g.ntr), block, 0, st, proj, g.whh_pk, g.bih, g.bhh, g.G, g.h, g.S, 0,
+                           g.shuffle, sum_in, out, sum_out, (const float*)nullptr, (float*)nullptr, g.foff);
     else
-        hipLaunchKernelGGL(k_dfn2_gru<32>, grid, block, 0, st, proj, g.whh_pk, g.bih, g.bhh, g.G, g.h, g.S, nF, g.shuffle, sum_in, out, sum_out,
-                           g.hst, g.hst);
+        hipLaunchKernelGGL((k_dfn2_gru<K, false>), dim3(g.G, C), block, 0, st, proj, g.whh_pk, g.bih, g.bhh, g.G, g.h, g.S, nF, g.shuffle,
+                           sum_in, out, sum_out, (const float*)g.hst, g.hst, (const int*)nullptr);
+}
+
+void launch_ggru(const GGru& g, const float* proj, const float* sum_in, float* out, float* sum_out, int C, int nF, hipStream_t st) {
+    if (g.K == 16) launch_ggru_k<16>(g, proj, sum_in, out, sum_out, C, nF, st);
+    else launch_ggru_k<32>(g, proj, sum_in, out, sum_out, C, nF, st);
 }
 
 // x [C * nF][in] -> out (the layer output as passed on) and sum_out (= sum_in + out) [C * nF][H] through one GroupedGRU layer
@@ -1204,7 +1388,7 @@ int ggru_layer(const GGru& g, const float* x, float* proj, const float* sum_in, 
     EGR_TRY(egr_bgemm(x, g.wih, proj, 1, g.G, (int)R, h3, I, g.in, I, 3 * g.H, 0, I, 0, (int64_t)h3 * I, 0, h3, 1, 1.f, st));
     if (g.dense()) {                       // G = 1 and H > 128: a plain nn.GRU layer, no shuffle
         EGR_TRY(rows_op(proj, g.bih, nullptr, proj, R * 3 * g.H, 3 * g.H, 0, st));
-        hipLaunchKernelGGL(k_dfn_gru, dim3(C), dim3(GRU_THREADS), 0, st, proj, g.whh_pk, g.bhh, g.H, nF, out, g.hst, g.hst);
+        launch_gru(proj, g.whh_pk, g.bhh, g.H, C, nF, out, g.hst, g.foff, g.ntr, st);
         return rows_op(out, nullptr, sum_in, sum_out, R * g.H, g.H, 0, st);
     }
     launch_ggru(g, proj, sum_in, out, sum_out, C, nF, st);
@@ -1261,7 +1445,9 @@ int network(Dfn2& m, int C, int nF, hipStream_t st) {
 
 // mask, then deep filter (P7)
 void assemble(const Dfn2& m, const AsmArgs& p, hipStream_t st) {
-    hipLaunchKernelGGL(k_dfn2_assemble, dim3(grid_for((int64_t)p.C * p.nA * p.Fq)), dim3(256), 0, st, p);
+    const dim3 grid(grid_for((int64_t)p.C * p.nA * p.Fq));
+    if (p.trk) hipLaunchKernelGGL(k_dfn2_assemble<true>, grid, dim3(256), 0, st, p);
+    else hipLaunchKernelGGL(k_dfn2_assemble<false>, grid, dim3(256), 0, st, p);
 }
 
 inline const float* alpha_of(const Dfn3&) { return nullptr; }
@@ -1288,15 +1474,27 @@ void hist_convs(Core& k, ConvT* c[N_HIST_CONV], int fin[N_HIST_CONV]) {
     for (int i = 0; i < N_HIST_CONV; ++i) { c[i] = cs[i]; fin[i] = fs[i]; }
 }
 
-// A one-pass call carries nothing: no histories, no states, frame 0 first.
+// Every call starts from this: no histories, no states, frame 0 first, no track tables.  A one-pass call runs like that.
 template <class M>
-void unbind_segments(M& m) {
+void unbind(M& m) {
     Conv* c[N_HIST_CONV];
     int fin[N_HIST_CONV];
     hist_convs(m.core, c, fin);
-    for (int i = 0; i < N_HIST_CONV; ++i) { c[i]->hist = nullptr; c[i]->t0 = 0; }
-    for (auto& g : m.grus) g.hst = nullptr;
+    for (int i = 0; i < N_HIST_CONV; ++i) { c[i]->hist = nullptr; c[i]->t0 = 0; c[i]->trk = c[i]->foff = nullptr; }
+    for (auto& g : m.grus) { g.hst = nullptr; g.foff = nullptr; g.ntr = 0; }
     m.core.sg = SegState();
+    m.core.tk = Tracks();
+}
+
+// A tracks call: the layers that look along the frame axis (the convolutions with kt > 1 possible, the recurrences) get the tables.
+template <class M>
+void bind_tracks(M& m, const Tracks& tk) {
+    Conv* c[N_HIST_CONV];
+    int fin[N_HIST_CONV];
+    hist_convs(m.core, c, fin);
+    for (int i = 0; i < N_HIST_CONV; ++i) { c[i]->trk = tk.trk; c[i]->foff = tk.foff; }
+    for (auto& g : m.grus) { g.foff = tk.foff; g.ntr = tk.n; }
+    m.core.tk = tk;
 }
 
 template <class M>
@@ -1307,11 +1505,115 @@ int run(M& m, const float* x, int C, int64_t T, float* y, hipStream_t st) {
     EGR_TRY(ensure_workspace(k, workspace_need(m, C, nF), C, nF, T, false, st));
     Take take{(char*)k.ws.p};
     layout(m, Rows{R, R, R}, take, k.B, m.X);
-    unbind_segments(m);
+    unbind(m);
     features(k, x, C, nF, T, st);
     EGR_TRY(network(m, C, nF, st));
     assemble(m, assemble_args(k, alpha_of(m), C, nF, 0, nF, 0, nF, 0, nF), st);
     return synthesis(k, C, nF, 0, nF, T, 0, T, y, st);
+}
+
+// Tracks: every buffer holds the tracks' frames back to back, R rows; behind the buffers sit the tables.
+struct TrackTable {           // measures of a host table; the image of Tracks is soff [n + 1] | xoff [n] (int64), foff [n + 1] | trk [R] (int)
+    int n = 0;
+    int64_t R = 0, total = 0;                                // packed rows, samples of all tracks
+    int64_t floats() const { return 2 * (2 * (int64_t)n + 1) + (n + 1) + R; }      // the image's size in 4-byte units
+};
+
+// Checks a host table [n_tracks][2] = (offset, n) and measures it.  Nothing is allocated.
+int track_table(const DfnCore* m, const char* who, const int64_t* tracks, int n_tracks, TrackTable* tt) {
+    EGR_CHECK(m && tracks && n_tracks >= 1, EGR_ERR_ARG, "%s: bad argument", who);
+    const int64_t n_max = MAX_FRAMES * m->d.hop_size;        // a longer track alone has too many frames
+    int64_t R = 0, total = 0;
+    for (int b = 0; b < n_tracks; ++b) {
+        const int64_t off = tracks[2 * b], n = tracks[2 * b + 1];
+        EGR_CHECK(off >= 0 && n >= 1, EGR_ERR_ARG, "%s: track %d: offset %lld, n %lld", who, b, (long long)off, (long long)n);
+        EGR_CHECK(n <= n_max, EGR_ERR_UNSUPPORTED, "%s: track %d is too long", who, b);
+        R += m->frames_of(n);
+        total += n;
+        EGR_CHECK(R <= MAX_FRAMES, EGR_ERR_UNSUPPORTED, "%s: the tracks have more than %lld frames together", who, (long long)MAX_FRAMES);
+    }
+    tt->n = n_tracks;
+    tt->R = R;
+    tt->total = total;
+    return EGR_OK;
+}
+
+// The image of a checked table into `image` (tt.floats() 4-byte units).
+void fill_tables(const DfnCore& m, const int64_t* tracks, int n_tracks, void* image) {
+    int64_t* soff = (int64_t*)image;
+    int64_t* xoff = soff + n_tracks + 1;
+    int* foff = (int*)(xoff + n_tracks);
+    int* trk = foff + n_tracks + 1;
+    int64_t s = 0;
+    int r = 0;
+    for (int b = 0; b < n_tracks; ++b) {
+        soff[b] = s;
+        xoff[b] = tracks[2 * b];
+        foff[b] = r;
+        const int nF = (int)m.frames_of(tracks[2 * b + 1]);
+        for (int f = 0; f < nF; ++f) trk[r + f] = b;
+        s += tracks[2 * b + 1];
+        r += nF;
+    }
+    soff[n_tracks] = s;
+    foff[n_tracks] = r;
+}
+
+template <class M>
+size_t tracks_need(const M& m, const TrackTable& tt, Bufs& B, typename M::Extra& X, char* base, float** table) {
+    Take take{base};
+    layout(m, Rows{tt.R, tt.R, tt.R}, take, B, X);
+    float* t = take(tt.floats());
+    if (table) *table = t;
+    return take.off;
+}
+
+template <class M>
+size_t tracks_workspace(const M* m, const char* who, const int64_t* tracks, int n_tracks) {
+    TrackTable tt;
+    if (track_table(m ? &m->core : nullptr, who, tracks, n_tracks, &tt) != EGR_OK) return 0;
+    Bufs B;
+    typename M::Extra X;
+    return tracks_need(*m, tt, B, X, nullptr, nullptr);
+}
+
+template <class M>
+int run_tracks(M* mp, const char* who, const float* x, const int64_t* tracks, int n_tracks, float* y, hipStream_t st) {
+    EGR_CHECK(mp && x && y, EGR_ERR_ARG, "%s: bad argument", who);
+    M& m = *mp;
+    DfnCore& k = m.core;
+    TrackTable tt;
+    EGR_TRY(track_table(&k, who, tracks, n_tracks, &tt));                    // every refusal comes before anything is allocated
+    EGR_TRY(check_current_device(who, k.device));
+    const size_t table_bytes = sizeof(float) * (size_t)tt.floats();
+    EGR_TRY(k.stage.reserve(table_bytes));
+    fill_tables(k, tracks, n_tracks, k.stage.p);
+    const int R = (int)tt.R;
+    {
+        Bufs B;
+        typename M::Extra X;
+        EGR_TRY(ensure_workspace(k, tracks_need(m, tt, B, X, nullptr, nullptr), 1, R, tt.total, false, st, true));
+    }
+    float* table = nullptr;
+    tracks_need(m, tt, k.B, m.X, (char*)k.ws.p, &table);
+    EGR_HIP(hipMemcpyAsync(table, k.stage.p, table_bytes, hipMemcpyHostToDevice, st));      // one copy for all tables
+    EGR_HIP(hipEventRecord(k.stage.copied, st));
+    Tracks tk;
+    tk.soff = (const int64_t*)table;
+    tk.xoff = tk.soff + n_tracks + 1;
+    tk.foff = (const int*)(tk.xoff + n_tracks);
+    tk.trk = tk.foff + n_tracks + 1;
+    tk.n = n_tracks;
+    unbind(m);
+    bind_tracks(m, tk);
+    features_tracks(k, x, R, st);
+    int rc = network(m, 1, R, st);
+    if (rc == EGR_OK) {
+        assemble(m, assemble_args(k, alpha_of(m), 1, R, 0, R, 0, R, 0, R), st);
+        rc = synthesis(k, 1, R, 0, R, tt.total, 0, tt.total, y, st);
+    }
+    unbind(m);                                                               // the tables belong to this call only
+    return rc;
 }
 
 // Segments: the buffers hold seg_frames network frames (plus the lookahead and deep-filter rows of spec, the lagged
@@ -1369,6 +1671,7 @@ int run_segmented(M& m, const float* x, int C, int64_t T, float* y, int64_t seg_
     EGR_TRY(ensure_workspace(k, segment_need(m, C, S), C, 0, T, true, st));
     SegLayout L;
     layout_segments(m, C, S, (char*)k.ws.p, k.B, m.X, L);
+    unbind(m);
     Conv* hc[N_HIST_CONV];
     int fin[N_HIST_CONV];
     hist_convs(k, hc, fin);
@@ -1385,15 +1688,15 @@ int run_segmented(M& m, const float* x, int C, int64_t T, float* y, int64_t seg_
         const int Sj = (int)(sp.net_hi - sp.net_lo), nS = (int)(sp.spec_hi - sp.spec_lo);
         const int nA = sp.asm_hi > sp.asm_lo ? (int)(sp.asm_hi - sp.asm_lo) : 0;
         const int64_t Rs = (int64_t)C * nS;
-        hipLaunchKernelGGL(k_dfn_analysis, dim3(nS, C), dim3(256), (size_t)N * 24, st, x, T, nS, sp.spec_lo, N, d.hop_size, k.tw, k.win,
-                           k.wnorm, B.spec);
+        hipLaunchKernelGGL(k_dfn_analysis<false>, dim3(nS, C), dim3(256), (size_t)N * 24, st, x, T, nS, sp.spec_lo, N, d.hop_size, k.tw,
+                           k.win, k.wnorm, B.spec, Tracks());
         hipLaunchKernelGGL(k_dfn_erb_db, dim3(grid_for(Rs * E)), dim3(256), 0, st, B.spec, Rs, k.Fq, E, k.band_lo, k.band_w, B.db);
         // input frames [scan_lo, scan_hi) -> feature rows t - la; the rows >= nF - la of this segment are zero
         int64_t zlo = nF - la - sp.net_lo;
         zlo = zlo < 0 ? 0 : (zlo > Sj ? Sj : zlo);
         ScanArgs sa{B.db, B.spec, B.ferb, B.fspec, k.sg.norm, C, nS, (int)(sp.scan_lo - sp.spec_lo), (int)(sp.scan_hi - sp.scan_lo), Sj,
-                    (int)(sp.scan_lo - la - sp.net_lo), (int)zlo, Sj, k.Fq, E, nb, la, j == 0, d.norm_alpha};
-        hipLaunchKernelGGL(k_dfn_norm_scan, dim3((C * (E + nb) + 63) / 64), dim3(64), 0, st, sa);
+                    (int)(sp.scan_lo - la - sp.net_lo), (int)zlo, Sj, k.Fq, E, nb, la, j == 0, d.norm_alpha, nullptr};
+        hipLaunchKernelGGL(k_dfn_norm_scan<false>, dim3((C * (E + nb) + 63) / 64), dim3(64), 0, st, sa);
         for (int i = 0; i < N_HIST_CONV; ++i) hc[i]->t0 = sp.net_lo;
         EGR_TRY(network(m, C, Sj, st));
         // the assemble step lags the network by df_lookahead frames: its rows in front of net_lo come from the histories
@@ -1528,6 +1831,14 @@ extern "C" size_t egr_dfn3_segment_workspace_bytes(void* handle, int channels, i
     return egr::segment_need(*(const egr::Dfn3*)handle, channels, seg_frames);
 }
 
+extern "C" int egr_dfn3_enhance_tracks(void* handle, const float* x48, const int64_t* tracks, int n_tracks, float* y, void* stream) {
+    return egr::run_tracks((egr::Dfn3*)handle, "egr_dfn3_enhance_tracks", x48, tracks, n_tracks, y, (hipStream_t)stream);
+}
+
+extern "C" size_t egr_dfn3_tracks_workspace_bytes(void* handle, const int64_t* tracks, int n_tracks) {
+    return egr::tracks_workspace((const egr::Dfn3*)handle, "egr_dfn3_tracks_workspace_bytes", tracks, n_tracks);
+}
+
 extern "C" size_t egr_dfn3_workspace_held(void* handle) {
     return handle ? ((const egr::Dfn3*)handle)->core.ws.bytes : 0;
 }
@@ -1548,8 +1859,7 @@ extern "C" int egr_dfn3_time_gru(void* handle, int layer, int channels, int64_t 
     return time_gru_harness(m ? &m->core : nullptr, "egr_dfn3_time_gru", layer, channels, steps, false, us_per_step,
                             [&](const float* proj, float* out, float*, int nF) {
         const Gru& g = m->grus[layer];
-        hipLaunchKernelGGL(k_dfn_gru, dim3(channels), dim3(GRU_THREADS), 0, 0, proj, g.whh_pk, g.bhh, g.H, nF, out, (const float*)nullptr,
-                           (float*)nullptr);
+        launch_gru(proj, g.whh_pk, g.bhh, g.H, channels, nF, out, nullptr, nullptr, 0, 0);
     });
 }
 
@@ -1680,6 +1990,14 @@ extern "C" size_t egr_dfn2_segment_workspace_bytes(void* handle, int channels, i
     return egr::segment_need(*(const egr::Dfn2*)handle, channels, seg_frames);
 }
 
+extern "C" int egr_dfn2_enhance_tracks(void* handle, const float* x48, const int64_t* tracks, int n_tracks, float* y, void* stream) {
+    return egr::run_tracks((egr::Dfn2*)handle, "egr_dfn2_enhance_tracks", x48, tracks, n_tracks, y, (hipStream_t)stream);
+}
+
+extern "C" size_t egr_dfn2_tracks_workspace_bytes(void* handle, const int64_t* tracks, int n_tracks) {
+    return egr::tracks_workspace((const egr::Dfn2*)handle, "egr_dfn2_tracks_workspace_bytes", tracks, n_tracks);
+}
+
 extern "C" size_t egr_dfn2_workspace_held(void* handle) {
     return handle ? ((const egr::Dfn2*)handle)->core.ws.bytes : 0;
 }
@@ -1707,11 +2025,11 @@ extern "C" int egr_dfn2_time_gru(void* handle, int layer, int channels, int64_t 
                             [&](const float* proj, float* out, float* sum, int nF) {
         const GGru& g = m->grus[layer];
         if (g.dense())
-            hipLaunchKernelGGL(k_dfn_gru, dim3(channels), dim3(GRU_THREADS), 0, 0, proj, g.whh_pk, g.bhh, g.H, nF, out, (const float*)nullptr,
-                           (float*)nullptr);
+            launch_gru(proj, g.whh_pk, g.bhh, g.H, channels, nF, out, nullptr, nullptr, 0, 0);
         else {
-            GGru z = g;                                             // no carried state
+            GGru z = g;                                             // no carried state, no tracks
             z.hst = nullptr;
+            z.foff = nullptr;
             launch_ggru(z, proj, nullptr, out, sum, channels, nF, 0);
         }
     });

@@ -7,12 +7,15 @@ the current stream.  DfnEngine is the engine of both models; this module holds t
 A long input runs in segments of `seg_frames` network frames with the state carried across the cuts (egr_dfn*_enhance_segmented,
 DESIGN.md 7.3): the same bits as the one-pass call, a workspace that depends on seg_frames and not on the length.  enhance() picks the
 path with choose_path() from the workspace budget EGREGORA_DFN_WORKSPACE_GB.
+
+Many clips go through enhance_many(): their channels run side by side in one ragged pass per wave (egr_dfn*_enhance_tracks,
+DESIGN.md 7.7), every clip with the bits of enhance() on it alone; plan_waves() packs the waves under the same budget.
 """
 import ctypes as C
 import os
 import threading
 from pathlib import Path
-from typing import Callable, Dict, NamedTuple, Optional, Tuple
+from typing import Callable, Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
@@ -112,6 +115,33 @@ def choose_path(nF: int, one_pass_bytes: int, budget_bytes: int, bytes_for: Call
     return lo * SEGMENT_STEP
 
 
+def plan_waves(channels: Sequence[int], frames: Sequence[int], bytes_for: Callable[[List[int]], int], budget_bytes: int,
+               max_frames: int = ONE_PASS_MAX_FRAMES) -> Tuple[List[List[int]], List[int]]:
+    """Waves of enhance_many: (clip indices per wave, clips that run alone).  Clip i has channels[i] tracks of frames[i] frames each;
+    bytes_for(indices) is the workspace of one ragged call over those clips (it grows with every clip added).  A clip stays whole.
+    The clips are taken by frame count, longest first (ties in input order), so that the recurrences of a wave's rows end together,
+    and a wave closes before the clip that would take it past budget_bytes or past max_frames frames in all.  A clip over either
+    limit on its own is in no wave but in the second list: it runs through enhance(), which segments."""
+    order = sorted(range(len(frames)), key=lambda i: -int(frames[i]))
+    rows = lambda i: int(channels[i]) * int(frames[i])
+    waves: List[List[int]] = []
+    alone: List[int] = []
+    cur: List[int] = []
+    used = 0
+    for i in order:
+        if rows(i) > max_frames or bytes_for([i]) > budget_bytes:
+            alone.append(i)
+            continue
+        if cur and (used + rows(i) > max_frames or bytes_for(cur + [i]) > budget_bytes):
+            waves.append(cur)
+            cur, used = [], 0
+        cur.append(i)
+        used += rows(i)
+    if cur:
+        waves.append(cur)
+    return waves, sorted(alone)
+
+
 def config_common(s, m):
     """The fields both config structs fill alike, from a validated model m."""
     c, sd = m.cfg, m.sd
@@ -184,6 +214,73 @@ class DfnEngine:
                 native.check(self._fn("enhance_segmented")(self.h, native.ptr(x), ch, n, native.ptr(y), int(seg_frames), native.stream_ptr()),
                              f"{self.prefix}_enhance_segmented")
         return y
+
+    def frames_of(self, n: int) -> int:
+        """Frames of an n-sample track: (n + fft_size) // hop_size."""
+        return (int(n) + self._cfg.fft_size) // self._cfg.hop_size
+
+    @staticmethod
+    def _track_table(offsets: Sequence[int], lengths: Sequence[int]):
+        import numpy as np
+        tab = np.ascontiguousarray(np.stack([np.asarray(offsets, dtype=np.int64).reshape(-1),
+                                             np.asarray(lengths, dtype=np.int64).reshape(-1)], axis=1))
+        return tab, tab.ctypes.data_as(C.c_void_p)
+
+    def tracks_workspace_bytes(self, lengths: Sequence[int]) -> int:
+        """The workspace of enhance_tracks over tracks of these lengths (it follows the sum of their frames); 0 for a set of lengths
+        the call refuses."""
+        tab, p = self._track_table([0] * len(lengths), lengths)
+        return int(self._fn("tracks_workspace_bytes")(self.h, p, len(lengths)))
+
+    def enhance_tracks(self, x: torch.Tensor, offsets: Sequence[int], lengths: Sequence[int], y: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """One ragged pass (egr_dfn*_enhance_tracks).  x: a flat float32 buffer on this engine's device; track b (one
+        channel of one clip) is x[offsets[b] : offsets[b] + lengths[b]], its output lands at the same place of y (flat, x's size when
+        not given; what no track covers is left unwritten).  Every track gets the bits enhance() gives it alone."""
+        if x.dim() != 1 or not x.is_cuda or x.device.index != self.device or x.dtype != torch.float32 or not x.is_contiguous():
+            raise ValueError(f"{self.prefix}: expected a flat contiguous float32 buffer on cuda:{self.device}")
+        if len(offsets) != len(lengths):
+            raise ValueError(f"{self.prefix}: {len(offsets)} offsets, {len(lengths)} lengths")
+        y = torch.empty_like(x) if y is None else y
+        tab, p = self._track_table(offsets, lengths)
+        with torch.cuda.device(self.device):
+            native.check(self._fn("enhance_tracks")(self.h, native.ptr(x), p, len(lengths), native.ptr(y), native.stream_ptr()),
+                         f"{self.prefix}_enhance_tracks")
+        return y
+
+    def enhance_many(self, rows: Sequence[torch.Tensor], stats: Optional[dict] = None) -> List[torch.Tensor]:
+        """rows: [C_i, T_i] float32 tensors on this engine's device -> tensors of the same shapes there, on the current stream, each
+        with the bits of enhance() on that clip alone.  The clips are packed into waves (plan_waves: workspace budget
+        EGREGORA_DFN_WORKSPACE_GB, at most ONE_PASS_MAX_FRAMES frames), one enhance_tracks call per wave; a clip over a limit on its own
+        goes through enhance(), which segments.  The results of a wave are views of that wave's one output buffer.  stats, when
+        given, receives waves (clip indices per wave) and alone."""
+        for i, x in enumerate(rows):
+            if not torch.is_tensor(x) or x.dim() != 2 or x.shape[0] < 1 or x.shape[1] < 1 or not x.is_cuda or x.device.index != self.device:
+                raise ValueError(f"{self.prefix}: clip {i}: expected a non-empty [C, T] tensor on cuda:{self.device}")
+        shapes = [(int(x.shape[0]), int(x.shape[1])) for x in rows]
+        frames = [self.frames_of(T) for _, T in shapes]
+        lengths_of = lambda idx: [shapes[i][1] for i in idx for _ in range(shapes[i][0])]
+        waves, alone = plan_waves([c for c, _ in shapes], frames, lambda idx: self.tracks_workspace_bytes(lengths_of(idx)),
+                                  workspace_budget_bytes())
+        out: List[Optional[torch.Tensor]] = [None] * len(rows)
+        for i in alone:
+            out[i] = self.enhance(rows[i])
+        for idx in waves:
+            x = torch.cat([rows[i].to(torch.float32).reshape(-1) for i in idx])
+            offs, lens, pos = [], [], 0
+            for i in idx:
+                c, T = shapes[i]
+                offs += [pos + k * T for k in range(c)]
+                lens += [T] * c
+                pos += c * T
+            y = self.enhance_tracks(x, offs, lens)
+            pos = 0
+            for i in idx:
+                c, T = shapes[i]
+                out[i] = y[pos:pos + c * T].view(c, T)
+                pos += c * T
+        if stats is not None:
+            stats["waves"], stats["alone"] = [list(w) for w in waves], list(alone)
+        return out
 
     def workspace_bytes(self, channels: int, n: int) -> int:
         return int(self._fn("workspace_bytes")(self.h, int(channels), int(n)))

@@ -67,6 +67,10 @@ SIGNATURES = {
     "egr_dfn2_enhance_segmented": (_i, [_vp, _vp, _i, _i64, _vp, _i64, _vp]),
     "egr_dfn2_segment_workspace_bytes": (C.c_size_t, [_vp, _i, _i64]),
     "egr_dfn2_workspace_held": (C.c_size_t, [_vp]),
+    "egr_dfn3_enhance_tracks": (_i, [_vp, _vp, _vp, _i, _vp, _vp]),
+    "egr_dfn3_tracks_workspace_bytes": (C.c_size_t, [_vp, _vp, _i]),
+    "egr_dfn2_enhance_tracks": (_i, [_vp, _vp, _vp, _i, _vp, _vp]),
+    "egr_dfn2_tracks_workspace_bytes": (C.c_size_t, [_vp, _vp, _i]),
     "egr_shift_fir": (_i, [_vp, _i, _i64, _i64, _vp, _i, _vp, _i64, _vp]),
     "egr_gcc_phat": (_i, [_vp, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp]),
     "egr_band_filter": (_i, [_vp, _vp, _i64, _vp, _vp]),

@@ -267,6 +267,22 @@ int egr_dfn2_enhance_segmented(void* handle, const float* x48, int channels, int
 size_t egr_dfn2_segment_workspace_bytes(void* handle, int channels, int64_t seg_frames);
 size_t egr_dfn2_workspace_held(void* handle);
 
+/* Many clips in one ragged pass, for both models.  A track is one channel of one clip.  tracks is a HOST array
+ * [n_tracks][2] = (offset of the track in x48 and in y, n >= 1 samples); x48 and y are flat device buffers, a track's output has its
+ * input's length at the same offset (tracks must not overlap).  Track b has nF_b = (n_b + fft_size) / hop_size frames; every workspace
+ * buffer holds the tracks' frames back to back, R = sum nF_b rows, so cost and workspace follow the sum of the lengths.  Every track's
+ * output has the bits of egr_dfnX_enhance on that track alone.
+ *   egr_dfnX_enhance_tracks         : builds its device tables in the workspace, uploads them with one asynchronous copy and enqueues
+ *                                     everything on `stream`; nothing synchronises and nothing is carried from call to call.
+ *                                     n_tracks < 1, a null pointer, a negative offset or an n < 1 is EGR_ERR_ARG, R above 2^31 / 4096
+ *                                     = 524287 frames EGR_ERR_UNSUPPORTED, both before anything is allocated or enqueued.
+ *                                     egr_dfnX_stage after it is EGR_ERR_ARG (stages belong to one-pass calls)
+ *   egr_dfnX_tracks_workspace_bytes : the workspace of such a call (0 for a table the call refuses) */
+int egr_dfn3_enhance_tracks(void* handle, const float* x48, const int64_t* tracks, int n_tracks, float* y, void* stream);
+size_t egr_dfn3_tracks_workspace_bytes(void* handle, const int64_t* tracks, int n_tracks);
+int egr_dfn2_enhance_tracks(void* handle, const float* x48, const int64_t* tracks, int n_tracks, float* y, void* stream);
+size_t egr_dfn2_tracks_workspace_bytes(void* handle, const int64_t* tracks, int n_tracks);
+
 /* Linear-interpolation resampler of the "Resample Audio (HQ)" node's fallback branch: y[c][j] = np.interp at
  * j * n_in / n_out input samples, clamped to the last sample (egregora_audio_eval_pack.py:515-519). */
 int egr_resample_linear(const float* x, int channels, int64_t n_in, float* y, int64_t n_out, void* stream);
