@@ -415,7 +415,8 @@ __global__ __launch_bounds__(256) void k_snake_aa_tiled(const float* __restrict_
 // Register-blocked version (K = 12): a thread owns one channel and a run of J consecutive output positions.  Its x window
 // (J + 10 values, lanes run over channels so every load is a coalesced row segment) and the 2J + 10 up-rate samples it needs
 // live in registers with compile-time indices: no LDS, no barriers, (2J+10)/J sin per output (2.6 at J = 16) and 6 + ~6 FMAs
-// per up-rate sample.  Halo re-reads (10/J of the tile) hit L1/L2.  Runs at the tensor edges substitute the clamped
+// per up-rate sample.  Halo re-reads (10/J of the tile) are left to L1/L2, where about a fifth of them miss (FETCH_SIZE 1.19x the
+// tensor in the forward): k_snake_aa_span below is the default, this kernel stays behind EGR_SNAKE_SPAN=0.  Runs at the tensor edges substitute the clamped
 // up-rate samples with predicated selects (same code path, same arithmetic).
 template <int J>
 __global__ __launch_bounds__(256) void k_snake_aa_reg(const float* __restrict__ x, const float* __restrict__ alpha,
@@ -480,6 +481,93 @@ __global__ __launch_bounds__(256) void k_snake_aa_reg(const float* __restrict__ 
     // (measured inside the forward, 91 launches: 146 us per launch without the maxima; with them 156 us at <= 8192 workgroups and one
     // checked commit per workgroup, 181 us at 32768, 165 - 202 us with per-wave or unchecked commits; one commit per workgroup of a
     // 100 k-workgroup grid: 2.7 ms -- same-line atomics serialise at ~25 ns)
+    if (row_amax) row_amax_commit_wg(row_amax + (size_t)b * EGR_ROW_AMAX_STRIDE, ymax);          // (uniform branch: every thread arrives)
+}
+
+// The same with every x loaded once and every up-rate sample (and its __sinf) computed once: a thread owns one channel and a span of
+// S consecutive runs, and between runs keeps the 10 window samples xw[J .. J+9] and the 10 up-rate samples sv[2J .. 2J+9] in
+// registers as the next run's xw[0 .. 9] / sv[0 .. 9] (2 + 10 / (S J) sin per output instead of 2.6).  The carried up-rate samples
+// are the ones the next run would compute from the same x with the same expression; at the tensor's end they may already hold the
+// clamped sample, which is what the next run's substitution would write there again.  Lanes still run over channels.
+template <int J>
+__global__ __launch_bounds__(256) void k_snake_aa_span(const float* __restrict__ x, const float* __restrict__ alpha,
+                                                       const float* __restrict__ beta, const float* __restrict__ filt,
+                                                       float* __restrict__ y, int L, int C, int nruns, int S, int nspans,
+                                                       unsigned* __restrict__ row_amax) {
+    const int b = blockIdx.y;
+    const long long per_row = (long long)nspans * C;
+    float ymax = 0.f;
+    for (long long gid = (long long)blockIdx.x * 256 + threadIdx.x; gid < per_row; gid += (long long)gridDim.x * 256) {
+    const int c = (int)(gid % C);
+    const int span = (int)(gid / C);
+    const int r0 = span * S, r1 = r0 + S < nruns ? r0 + S : nruns;
+    float f[12];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) f[k] = filt[k];
+    const float a = __expf(alpha[c]), ib = 1.0f / (__expf(beta[c]) + 1e-9f);
+    const float* xb = x + (size_t)b * L * C + c;
+    float* yb = y + (size_t)b * L * C + c;
+    const int L2 = 2 * L;
+    float xw[J + 10];                            // xw[i] = xp[l0 + i] = x[clamp(l0 - 5 + i)] (replicate padding of 5)
+    float sv[2 * J + 10];                        // up-rate sample i = 2 l0 - 5 + q: taps xw[5 + (q>>1) - j] * f[(q&1) + 2j]
+#pragma unroll
+    for (int i = 0; i < 10; ++i) {               // the span's first run has no predecessor: its first 10 of each
+        int src = r0 * J - 5 + i;
+        src = src < 0 ? 0 : (src > L - 1 ? L - 1 : src);
+        xw[i] = xb[(size_t)src * C];
+    }
+#pragma unroll
+    for (int q = 0; q < 10; ++q) {
+        float u = 0.f;
+#pragma unroll
+        for (int j = 0; j < 6; ++j) u += xw[5 + (q >> 1) - j] * f[(q & 1) + 2 * j];
+        u *= 2.0f;
+        const float sn = __sinf(u * a);
+        sv[q] = u + ib * sn * sn;
+    }
+#pragma unroll 1
+    for (int run = r0; run < r1; ++run) {
+    const int l0 = run * J;
+#pragma unroll
+    for (int i = 10; i < J + 10; ++i) {
+        int src = l0 - 5 + i;
+        src = src < 0 ? 0 : (src > L - 1 ? L - 1 : src);
+        xw[i] = xb[(size_t)src * C];
+    }
+#pragma unroll
+    for (int q = 10; q < 2 * J + 10; ++q) {
+        float u = 0.f;
+#pragma unroll
+        for (int j = 0; j < 6; ++j) u += xw[5 + (q >> 1) - j] * f[(q & 1) + 2 * j];
+        u *= 2.0f;
+        const float sn = __sinf(u * a);
+        sv[q] = u + ib * sn * sn;
+    }
+    const int i0 = 2 * l0 - 5;
+    if (i0 < 0 || i0 + 2 * J + 9 > L2 - 1) {     // runs at the tensor edges: up-rate indices clamp to [0, 2L-1]
+        float s_first = 0.f, s_last = 0.f;
+#pragma unroll
+        for (int q = 0; q < 2 * J + 10; ++q) {
+            if (i0 + q == 0) s_first = sv[q];
+            if (i0 + q == L2 - 1) s_last = sv[q];
+        }
+#pragma unroll
+        for (int q = 0; q < 2 * J + 10; ++q) {
+            if (i0 + q < 0) sv[q] = s_first;
+            if (i0 + q > L2 - 1) sv[q] = s_last;
+        }
+    }
+#pragma unroll
+    for (int jj = 0; jj < J; ++jj) {             // output l0 + jj = sum_k f[k] * s[2 (l0 + jj) - 5 + k]
+        float acc = 0.f;
+#pragma unroll
+        for (int k = 0; k < 12; ++k) acc += f[k] * sv[2 * jj + k];
+        if (l0 + jj < L) { yb[(size_t)(l0 + jj) * C] = acc; ymax = fmaxf(ymax, fabsf(acc)); }
+    }
+#pragma unroll
+    for (int i = 0; i < 10; ++i) { xw[i] = xw[J + i]; sv[i] = sv[2 * J + i]; }
+    }
+    }
     if (row_amax) row_amax_commit_wg(row_amax + (size_t)b * EGR_ROW_AMAX_STRIDE, ymax);          // (uniform branch: every thread arrives)
 }
 
@@ -1042,6 +1130,17 @@ extern "C" int egr_snake_aa_ra(const float* x, const float* alpha, const float* 
         constexpr int J = 16;
         const int nruns = (L + J - 1) / J;
         static const int max_wg = getenv("EGR_SNAKE_WG") ? atoi(getenv("EGR_SNAKE_WG")) : 8192;
+        // EGR_SNAKE_SPAN (read once): unset = k_snake_aa_span with the span chosen below, n >= 1 = spans of n runs, 0 = k_snake_aa_reg
+        static const int span_env = getenv("EGR_SNAKE_SPAN") ? atoi(getenv("EGR_SNAKE_SPAN")) : -1;
+        if (span_env != 0) {
+            // 8 runs per thread (10 halo samples in 138), halved while the launch has fewer than four workgroups per compute unit
+            int S = span_env > 0 ? span_env : 8;
+            // (forward's snake total with every launch at 2 / 4 / 8 / 16 / 32 runs: 76 / 69 / 72 / 87 / 119 ms; this rule: 71 ms)
+            if (span_env < 0) while (S > 1 && (long long)((nruns + S - 1) / S) * C * B < 256LL * 1024) S >>= 1;
+            const int nspans = (nruns + S - 1) / S;
+            hipLaunchKernelGGL((k_snake_aa_span<J>), dim3(row_grid_x((long long)nspans * C, B, max_wg), (unsigned)B), dim3(256), 0, st, x, alpha, beta, filt, y,
+                               L, C, nruns, S, nspans, (unsigned*)row_amax);
+        } else
         hipLaunchKernelGGL((k_snake_aa_reg<J>), dim3(row_grid_x((long long)nruns * C, B, max_wg), (unsigned)B), dim3(256), 0, st, x, alpha, beta, filt, y, L, C,
                            nruns, (unsigned*)row_amax);
         row_amax = nullptr;                      // done in the kernel

@@ -148,6 +148,134 @@ __global__ __launch_bounds__(256) void k_wino4_in(const float* __restrict__ x, i
     if (row_amax) row_amax_commit(row_amax + (size_t)b * EGR_ROW_AMAX_STRIDE, vmax);                  // once per wave, every lane arrives together
 }
 
+// One tile of the band walk below.  FIRST: the band's top tile loads all six rows; every other tile loads rows 2 .. 5 and takes rows
+// 0 and 1 from `cy`, the rows 4 and 5 the tile above left there after the affine, SiLU and edge masking (the same function of the same
+// input elements: the same bits).  The arithmetic is k_wino4_in's, expression for expression.
+// Addresses are a wave-uniform base (the image; the V plane) plus a 32-bit lane offset, a third of the registers that 36 64-bit lane
+// addresses take (the launcher sends tensors past 4 GiB per image or plane to k_wino4_in).  An out-of-image tap loads the nearest
+// in-image element instead of element 0; it is zeroed below either way.
+template <bool GN, bool SILU, bool FIRST>
+__device__ __forceinline__ void wino4_in_tile(const float* __restrict__ xb, int H, int W, int C, int tx, int ty, const unsigned (&co)[6],
+                                              const float4& sc, const float4& sh, float4* __restrict__ cy, float* __restrict__ V,
+                                              unsigned o, size_t zs, float& vmax) {
+    constexpr int R0 = FIRST ? 0 : 2;
+    float4 d[6][6];                                       // d[r][q]: row r, column q of the tile
+#pragma unroll
+    for (int r = R0; r < 6; ++r) {
+        int iy = 4 * ty - 1 + r;
+        iy = iy < 0 ? 0 : (iy > H - 1 ? H - 1 : iy);
+        const unsigned ro = (unsigned)iy * (unsigned)W * (unsigned)C;
+#pragma unroll
+        for (int q = 0; q < 6; ++q) d[r][q] = *(const float4*)(xb + (ro + co[q]));
+    }
+    const bool interior = ty > 0 && tx > 0 && 4 * ty + 4 < H && 4 * tx + 4 < W;
+    if (GN) {
+#pragma unroll
+        for (int r = R0; r < 6; ++r)
+#pragma unroll
+            for (int q = 0; q < 6; ++q) {
+                float4 v = d[r][q];
+                v = make_float4(v.x * sc.x + sh.x, v.y * sc.y + sh.y, v.z * sc.z + sh.z, v.w * sc.w + sh.w);
+                if (SILU) {
+                    v.x = v.x / (1.f + __expf(-v.x)); v.y = v.y / (1.f + __expf(-v.y));
+                    v.z = v.z / (1.f + __expf(-v.z)); v.w = v.w / (1.f + __expf(-v.w));
+                }
+                d[r][q] = v;
+            }
+    }
+    if (!interior) {
+#pragma unroll
+        for (int r = R0; r < 6; ++r) {
+            const int iy = 4 * ty - 1 + r;
+#pragma unroll
+            for (int q = 0; q < 6; ++q) {
+                const int ix = 4 * tx - 1 + q;
+                if (!((unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W)) d[r][q] = make_float4(0.f, 0.f, 0.f, 0.f);
+            }
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < 6; ++q) {
+        if (!FIRST) { d[0][q] = cy[256 * q]; d[1][q] = cy[256 * (6 + q)]; }
+        cy[256 * q] = d[4][q];                            // the column transform below overwrites d: the carried rows are copies
+        cy[256 * (6 + q)] = d[5][q];
+    }
+#pragma unroll
+    for (int q = 0; q < 6; ++q) {                         // B^T d : transform the columns in place
+        float4 col[6], o6[6];
+#pragma unroll
+        for (int r = 0; r < 6; ++r) col[r] = d[r][q];
+        bt6(col, o6);
+#pragma unroll
+        for (int r = 0; r < 6; ++r) d[r][q] = o6[r];
+    }
+#pragma unroll
+    for (int r = 0; r < 6; ++r) {                         // (.) B == B^T applied along the row
+        float4 row[6];
+        bt6(d[r], row);
+#pragma unroll
+        for (int q = 0; q < 6; ++q) {
+            st_f4(V + (size_t)(6 * r + q) * zs + o, row[q]);
+            vmax = amax4(row[q], vmax);
+        }
+    }
+}
+
+// The same transform, every input element fetched once per workgroup patch.  A workgroup owns a contiguous patch of one image's tile
+// grid for a slice of channel quads: 2^lq quads x 2^lx tile columns x 2^ly bands of `bh` tile rows (lq + lx + ly = 8).  A thread keeps
+// its (tx, c4) and walks its band downwards: rows 4 and 5 of a tile are rows 0 and 1 of the next, so a tile below the band's top costs
+// 24 loads instead of 36 and two rows of __expf less.  The two rows wait in LDS slots of the thread's own (no barrier; 12 b128 writes
+// and reads per tile): kept in registers next to d[6][6] they took every instantiation past 256 registers, one wave per SIMD
+// instead of two, where 48 KiB of LDS leaves the two workgroups per compute unit.  The one-column overlap between tx and tx +- 1 is between
+// threads of one workgroup (the second reader finds the line in the CU's L1 or the XCD's L2).  What is left are the patch borders:
+// chunks are numbered with vertical neighbours consecutive, and the chunks of workgroups b, b + 8, b + 16 ... (observed to share
+// an XCD, hence an L2; gridDim.x is a multiple of 8) are consecutive, so the two readers of a border row mostly share an L2.  Nothing
+// but speed depends on that placement.
+template <bool GN, bool SILU>
+__global__ __launch_bounds__(256) void k_wino4_in_band(const float* __restrict__ x, int B, int H, int W, int C, int TH, int TW,
+                                                        const float* __restrict__ gsc, const float* __restrict__ gsh,
+                                                        float* __restrict__ V, unsigned* __restrict__ row_amax, int lq, int lx,
+                                                        int bh, int nbx, int nby, int nchunks) {
+    __shared__ float4 carry[12 * 256];                    // carry[256 i + thread]: 48 KiB, two workgroups per compute unit as the registers allow
+    const int C4 = C >> 2;
+    const size_t zs = (size_t)B * TH * TW * C;
+    const int b = blockIdx.y;
+    const float* xb = x + (size_t)b * H * W * C;          // image b; plane 0 of image b's tiles
+    float* Vb = V + (size_t)b * TH * TW * C;
+    const int cq = threadIdx.x & ((1 << lq) - 1), txl = (threadIdx.x >> lq) & ((1 << lx) - 1), tyl = threadIdx.x >> (lq + lx);
+    const int ly = 8 - lq - lx;
+    const int per_xcd = (nchunks + 7) >> 3, wg_per_xcd = gridDim.x >> 3;
+    float vmax = 0.f;
+    for (int k = blockIdx.x >> 3; k < per_xcd; k += wg_per_xcd) {
+        const int chunk = (blockIdx.x & 7) * per_xcd + k;
+        if (chunk >= nchunks) break;
+        const int by = chunk % nby, bx = (chunk / nby) % nbx, sl = chunk / (nby * nbx);
+        const int c4 = (sl << lq) + cq, tx = (bx << lx) + txl, ty0 = ((by << ly) + tyl) * bh;
+        if (c4 >= C4 || tx >= TW || ty0 >= TH) continue;
+        const int ty1 = ty0 + bh < TH ? ty0 + bh : TH;
+        float4 sc = make_float4(0.f, 0.f, 0.f, 0.f), sh = sc;
+        if (GN) {      // producer's GroupNorm (+SiLU) fused into the transform; padding stays zero
+            sc = *(const float4*)(gsc + (size_t)b * C + 4 * c4);
+            sh = *(const float4*)(gsh + (size_t)b * C + 4 * c4);
+        }
+        unsigned co[6];                                   // lane offset of the tile's column q in an image row, clamped into the image
+#pragma unroll
+        for (int q = 0; q < 6; ++q) {
+            int ix = 4 * tx - 1 + q;
+            ix = ix < 0 ? 0 : (ix > W - 1 ? W - 1 : ix);
+            co[q] = (unsigned)ix * (unsigned)C + 4u * (unsigned)c4;
+        }
+        unsigned o = ((unsigned)ty0 * (unsigned)TW + (unsigned)tx) * (unsigned)C + 4u * (unsigned)c4;
+        wino4_in_tile<GN, SILU, true>(xb, H, W, C, tx, ty0, co, sc, sh, carry + threadIdx.x, Vb, o, zs, vmax);
+#pragma unroll 1
+        for (int ty = ty0 + 1; ty < ty1; ++ty) {
+            o += (unsigned)TW * (unsigned)C;
+            wino4_in_tile<GN, SILU, false>(xb, H, W, C, tx, ty, co, sc, sh, carry + threadIdx.x, Vb, o, zs, vmax);
+        }
+    }
+    if (row_amax) row_amax_commit(row_amax + (size_t)b * EGR_ROW_AMAX_STRIDE, vmax);                  // once per wave, every lane arrives together
+}
+
 // y[b][4ty+a][4tx+c][n] = act((A^T M A)[a][c] + bias[n] + res[...]),  M[6 i + j][t][n].  RES / SILU are compile-time (loads
 // of the residual are then hoisted above the arithmetic instead of being waited for one by one).
 // STATS: each thread also writes (sum, sum of squares) of its 64 outputs to part[t][n4] -- the GroupNorm statistics of y are
@@ -284,9 +412,41 @@ extern "C" int egr_winograd4_input_ra(const float* x, const float* gn_scale, con
                   (!gn_scale || gn_shift), EGR_ERR_ARG, "F(4x4,3x3) input transform needs H, W, C multiples of 4");
     const int TH = H / 4, TW = W / 4;
     EGR_CHECK(B <= 65535, EGR_ERR_ARG, "too many images");
-    const dim3 g(row_grid_x((long long)TH * TW * (C / 4), B), (unsigned)B), blk(256);
+    const dim3 blk(256);
     hipStream_t st = (hipStream_t)stream;
     unsigned* ra = (unsigned*)row_amax;
+    // EGR_W4_BAND (read once): unset = the band walk with the band height chosen below, n >= 1 = that band height, 0 = k_wino4_in
+    static const int band_env = getenv("EGR_W4_BAND") ? atoi(getenv("EGR_W4_BAND")) : -1;
+    if (band_env != 0 && (long long)H * W * C < (1LL << 30)) {      // (32-bit lane offsets: an image of 4 GiB or more takes k_wino4_in)
+        const int C4 = C / 4;
+        // workgroup shape: up to 16 quads (256 B per tile and row: whole cache lines) x up to 16 tile columns (the patch's side
+        // columns are 2 in 4 * 16 + 2), what is left of the 256 threads goes to more quads, then to bands side by side
+        int lq = 0, lx = 0;
+        while (lq < 4 && (1 << lq) < C4) ++lq;
+        while (lx < 4 && (1 << lx) < TW) ++lx;
+        while (lq + lx < 8 && (1 << lq) < C4) ++lq;
+        while (lq + lx < 8 && (1 << lx) < TW) ++lx;
+        const int ly = 8 - lq - lx;
+        const int nsl = (C4 + (1 << lq) - 1) >> lq, nbx = (TW + (1 << lx) - 1) >> lx;
+        // band height: 8 tile rows (2 border rows in 34), halved while the launch has fewer than three workgroups per compute unit
+        int bh = band_env > 0 ? band_env : 8;
+        auto chunks_at = [&](int h) { return (long long)nsl * nbx * (((TH + h - 1) / h + (1 << ly) - 1) >> ly); };
+        // (forward's k_wino4_in_band total at thresholds 384 / 768 / 1536 / 3072: 115 / 116 / 123 / 130 ms; every layer at 8: 133 ms)
+        if (band_env < 0) while (bh > 1 && chunks_at(bh) * B < 768) bh >>= 1;
+        const int nby = ((TH + bh - 1) / bh + (1 << ly) - 1) >> ly;
+        const long long nchunks = chunks_at(bh);
+        EGR_CHECK(nchunks < (1LL << 30), EGR_ERR_ARG, "tensor too large");
+        long long gx = (nchunks + 7) & ~7LL, cap = (4096 / B) & ~7;
+        if (cap < 8) cap = 8;
+        if (gx > cap) gx = cap;
+        const dim3 g((unsigned)gx, (unsigned)B);
+#define W4I(G_, S_) hipLaunchKernelGGL((k_wino4_in_band<G_, S_>), g, blk, 0, st, x, B, H, W, C, TH, TW, gn_scale, gn_shift, V, ra, lq, lx, bh, nbx, nby, (int)nchunks)
+        if (!gn_scale) W4I(false, false); else if (gn_silu) W4I(true, true); else W4I(true, false);
+#undef W4I
+        EGR_HIP(hipGetLastError());
+        return EGR_OK;
+    }
+    const dim3 g(row_grid_x((long long)TH * TW * (C / 4), B), (unsigned)B);
     if (!gn_scale) hipLaunchKernelGGL((k_wino4_in<false, false>), g, blk, 0, st, x, B, H, W, C, TH, TW, gn_scale, gn_shift, V, ra);
     else if (gn_silu) hipLaunchKernelGGL((k_wino4_in<true, true>), g, blk, 0, st, x, B, H, W, C, TH, TW, gn_scale, gn_shift, V, ra);
     else hipLaunchKernelGGL((k_wino4_in<true, false>), g, blk, 0, st, x, B, H, W, C, TH, TW, gn_scale, gn_shift, V, ra);
