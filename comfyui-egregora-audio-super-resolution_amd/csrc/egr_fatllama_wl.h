@@ -73,6 +73,18 @@ __device__ __forceinline__ WlScale wl_scale(const double scd) {
     return s;
 }
 __device__ __forceinline__ float wl_scaled(const float v, const WlScale s) { return fmaf(v, s.hi, v * s.lo); }
+// The soft gain 1 - t / |X| of a bin that passed the comparison (m2 = |2 X|^2 > 0, tlevx2 = 2 t >= 0) through v_rsq_f32.  The instruction
+// flushes a subnormal input to zero and returns inf (measured on gfx950, profiles/fatllama_levels.md): with a zero level (thr = 0, or a
+// relative level whose maximum underflowed) that was 0 * inf = NaN, with a tiny one t * inf -- into the state and, through
+// fl_max2_commit, into every later iteration's level.  Below the normal range m2 is scaled by 2^64 and the result by 2^32, both exact,
+// so a zero level gives gain 1 and a subnormal square its own gain (as 1 - t / |X| in k_row); such a square carries only a few
+// significant bits and may sit a little under (2 t)^2 rounded, hence the clamp there.  For a normal m2 the arithmetic is what it was.
+__device__ __forceinline__ float wl_soft_gain(const float m2, const float tlevx2) {
+    const bool sub = m2 < 1.17549435e-38f;                                  // FLT_MIN
+    const float r = __builtin_amdgcn_rsqf(sub ? m2 * 0x1p+64f : m2);
+    const float g = 1.f - tlevx2 * (sub ? r * 0x1p+32f : r);
+    return sub ? fmaxf(g, 0.f) : g;
+}
 template <int HOOK>
 __device__ __forceinline__ float wl_pair_hook(const cplx Za, const cplx Zb, const dcplx Wkd, const float thr2x4, const float tlevx2, const int soft,
                                               const WlScale sc, cplx& na, cplx& nb) {
@@ -97,7 +109,7 @@ __device__ __forceinline__ float wl_pair_hook(const cplx Za, const cplx Zb, cons
             if (!km) Xm = make_float2(0.f, 0.f);
             mxn = 0.25f * fmaxf(kk ? mk2 : 0.f, km ? mm2 : 0.f);                          // max |S(X)|^2: the next iteration's spectrum
         } else {
-            const float gk = kk ? 1.f - tlevx2 * __builtin_amdgcn_rsqf(mk2) : 0.f, gm = km ? 1.f - tlevx2 * __builtin_amdgcn_rsqf(mm2) : 0.f;
+            const float gk = kk ? wl_soft_gain(mk2, tlevx2) : 0.f, gm = km ? wl_soft_gain(mm2, tlevx2) : 0.f;
             Xk.x *= gk; Xk.y *= gk; Xm.x *= gm; Xm.y *= gm;
             mxn = 0.25f * fmaxf(gk * gk * mk2, gm * gm * mm2);                            // |g X|^2 = g^2 |X|^2
         }
