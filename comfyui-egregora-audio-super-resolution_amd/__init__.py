@@ -11,7 +11,8 @@ environment variable EGREGORA_EVAL_NODES is "1" at import; the WPE dereverberati
 EGREGORA_ENHANCE_NODES is "1", the Descript Audio Codec encode / decode nodes (egregora_audio_codec_dac.py) only when
 EGREGORA_CODEC_NODES is "1", the FlashSR batch node (egregora_audio_super_resolution_batch.py: a list of clips in packed waves) only
 when EGREGORA_BATCH_NODES is "1", the DeepFilterNet batch node (egregora_audio_enhance_dfn_batch.py: a list of clips in ragged passes)
-only when EGREGORA_DENOISE_BATCH_NODES is "1".  Without them the registered set is the one listed above.
+only when EGREGORA_DENOISE_BATCH_NODES is "1", the codec's batch nodes (egregora_audio_codec_dac_batch.py: a list of clips in padded
+passes) only when EGREGORA_CODEC_BATCH_NODES is "1".  Without them the registered set is the one listed above.
 """
 import os
 
@@ -65,5 +66,10 @@ if os.environ.get("EGREGORA_DENOISE_BATCH_NODES") == "1":
     from .egregora_audio_enhance_dfn_batch import (NODE_CLASS_MAPPINGS as DFN_BATCH_MAP, NODE_DISPLAY_NAME_MAPPINGS as DFN_BATCH_NAMES)
     NODE_CLASS_MAPPINGS.update(DFN_BATCH_MAP)
     NODE_DISPLAY_NAME_MAPPINGS.update(DFN_BATCH_NAMES)
+
+if os.environ.get("EGREGORA_CODEC_BATCH_NODES") == "1":
+    from .egregora_audio_codec_dac_batch import (NODE_CLASS_MAPPINGS as DAC_BATCH_MAP, NODE_DISPLAY_NAME_MAPPINGS as DAC_BATCH_NAMES)
+    NODE_CLASS_MAPPINGS.update(DAC_BATCH_MAP)
+    NODE_DISPLAY_NAME_MAPPINGS.update(DAC_BATCH_NAMES)
 
 __all__ = ["NODE_CLASS_MAPPINGS", "NODE_DISPLAY_NAME_MAPPINGS"]

@@ -12,10 +12,14 @@
 //                  range of the window at its place in the whole y
 //   k_dac_vq       all stages of the residual quantiser in one launch; a workgroup keeps the residuals and sums of its frames in LDS
 //   k_dac_from_codes  z from integer codes, on k_dac_vq's own out_proj chain (dac_out_proj)
+//   k_dac_mask_frames  a many call's decoder input: zero beyond each row's own frames
 // The walks run on a window of latent frames (walk_encode_window / walk_decode_window); one pass is the window [0, F), a segmented
 // call (egr_dacseg_encode / _decode) runs the windows of egr_dacseg_plan one after the other through one arena and keeps
 // only the frames whose dependency cone lies inside their window: exact in exact arithmetic, fp32 round-off here, because the operand
 // scales come from each window's own row maxima.
+// A many call (egr_dacmany_encode / _decode) is the window [0, pad_frames) over rows of their own lengths: k_dac_snake<true>
+// stores +0.0f at and beyond a row's length at its level, k_dac_conv_in<true> reads each row's own [0, n) of a flat x, so every
+// convolution sees at a row's end the zero padding the single call gives it; the per-row tables live in the Walk of that call.
 // Work is enqueued on the caller's stream; nothing synchronises (the workspace grows with hipMallocAsync on that stream; the launcher's
 // split-K scratch is allocated the first time a stream needs it).
 #include <algorithm>
@@ -37,16 +41,22 @@ constexpr int DAC_AMAX_SLOTS = 8 * 7 + 4;          // snakes of one side (7 per 
 
 // ------------------------------------------------------------------------------------------------------------------ kernels
 // y = x + sin^2(alpha[c] x) * inva[c] over rows of per_row = L * C floats (in place when y == x); row_amax[r * EGR_ROW_AMAX_STRIDE]
-// (zeroed by the host) is raised to the row's max |y|.
+// (zeroed by the host) is raised to the row's max |y|.  RAG (a many call): row r holds len[r] valid positions of
+// C floats; beyond them y is +0.0f, x is not read there and nothing there raises the row's maximum.  (A position is C floats, so with
+// C % 4 == 0 the boundary falls between two float4.)
+template <bool RAG>
 __global__ __launch_bounds__(256) void k_dac_snake(const float* x, const float* __restrict__ alpha, const float* __restrict__ inva, float* y,
-                                                   long long per_row, int C, unsigned* __restrict__ row_amax) {
+                                                   long long per_row, int C, unsigned* __restrict__ row_amax, const int* __restrict__ len) {
     __shared__ float wmax[4];
     const int r = blockIdx.y;
     const float* xr = x + (size_t)r * per_row;
     float* yr = y + (size_t)r * per_row;
+    long long valid = per_row;
+    if (RAG) { const long long v = (long long)len[r] * C; valid = v < per_row ? v : per_row; }
     float vm = 0.f;
     if ((C & 3) == 0) {
         for (long long i = ((long long)blockIdx.x * 256 + threadIdx.x) * 4; i < per_row; i += (long long)gridDim.x * 1024) {
+            if (RAG && i >= valid) { *(float4*)(yr + i) = make_float4(0.f, 0.f, 0.f, 0.f); continue; }
             const int c = (int)(i % C);
             const float4 v = *(const float4*)(xr + i), a = *(const float4*)(alpha + c), q = *(const float4*)(inva + c);
             float4 o;
@@ -60,6 +70,7 @@ __global__ __launch_bounds__(256) void k_dac_snake(const float* x, const float* 
         }
     } else {
         for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < per_row; i += (long long)gridDim.x * 256) {
+            if (RAG && i >= valid) { yr[i] = 0.f; continue; }
             const int c = (int)(i % C);
             const float v = xr[i], t = sinf(alpha[c] * v), o = fmaf(t * t, inva[c], v);
             yr[i] = o;
@@ -79,13 +90,17 @@ __global__ __launch_bounds__(256) void k_dac_snake(const float* x, const float* 
 
 // y[r][l][c] = b[c] + sum_t w[t][c] x[r][x0 + l + t - 3] for the Lw samples of a window that begins at sample x0 of the whole
 // x [rows][n] (rows n apart), read as zero outside [0, n): the right pad to a multiple of the hop, and the true ends of the signal.
-// One pass is x0 = 0, Lw = n_pad.
+// One pass is x0 = 0, Lw = n_pad.  RAG (a many call): row r is the rows[r][1] samples at rows[r][0] of a flat x, each row with its own
+// [0, n).
+template <bool RAG>
 __global__ __launch_bounds__(256) void k_dac_conv_in(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ b,
-                                                     float* __restrict__ y, long long n, long long x0, long long Lw, int D, long long total) {
+                                                     float* __restrict__ y, long long n_all, long long x0, long long Lw, int D, long long total,
+                                                     const long long* __restrict__ rows) {
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
         const int c = (int)(i % D);
         const long long t = i / D, l = t % Lw, r = t / Lw;
-        const float* xr = x + r * n;
+        const long long n = RAG ? rows[2 * r + 1] : n_all;
+        const float* xr = x + (RAG ? rows[2 * r] : r * n);
         float acc = b[c];
 #pragma unroll
         for (int k = 0; k < 7; ++k) {
@@ -94,6 +109,15 @@ __global__ __launch_bounds__(256) void k_dac_conv_in(const float* __restrict__ x
             acc = fmaf(w[k * D + c], xv, acc);
         }
         y[i] = acc;
+    }
+}
+
+// z [rows][P][latent] channels-last: frames at or beyond frames[r] of row r become +0.0f (a many call's decoder input: the operand
+// scale of the input convolution then comes from the row's own frames, and the convolution sees the zeros of a row that ends there).
+__global__ __launch_bounds__(256) void k_dac_mask_frames(float* __restrict__ z, const int* __restrict__ frames, long long P, int latent, long long total) {
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
+        const long long t = i / latent;
+        if (t % P >= frames[t / P]) z[i] = 0.f;
     }
 }
 
@@ -332,6 +356,7 @@ struct Dac {
     float* d_f32 = nullptr;         // fp32 packs of the convolutions the split kernels do not take
     void* d_w2 = nullptr;           // fp16 term packs
     Workspace ws;
+    TableStage tables;              // many calls only: the host side of their per-row tables
     std::vector<StageRec> stages;
 };
 
@@ -499,6 +524,7 @@ void destroy(Dac* m) {
     {
         DeviceScope dev(m->device);
         m->ws.release();
+        m->tables.release();
         if (m->d_misc) (void)hipFree(m->d_misc);
         if (m->d_f32) (void)hipFree(m->d_f32);
         if (m->d_w2) (void)hipFree(m->d_w2);
@@ -546,7 +572,10 @@ struct Walk {
     char* base = nullptr; size_t off = 0;
     unsigned* amax_pool = nullptr; int amax_used = 0;
     int rc = EGR_OK;
-    bool notes = true;              // a segmented call records no stage
+    bool notes = true;              // a segmented or many call records no stage
+    // a many call binds its device tables here; null: every row is whole (one pass, segments)
+    const int* lens = nullptr;      // [levels][rows]: the valid positions of each row at each level of the side that runs
+    const long long* xrows = nullptr;   // [rows][2]: (offset, n) of each row in the flat x (encode)
     float* take(size_t floats) {
         off = (off + 255) & ~(size_t)255;
         float* p = launch ? (float*)(base + off) : nullptr;
@@ -562,13 +591,14 @@ struct Walk {
     void note(int kind, int index, const float* p, int64_t count) { if (launch && notes) m.stages.push_back({kind, index, p, count}); }
     bool go() const { return launch && rc == EGR_OK; }
     // y = snake(x) (y may be x); returns the row maxima of y
-    const unsigned* snake(const Snake& s, const float* x, float* y, int64_t L) {
+    const unsigned* snake(const Snake& s, const float* x, float* y, int64_t L, int level) {
         unsigned* slot = amax_slot();
         if (!go()) return slot;
         const long long per_row = (long long)L * s.C;
         long long nb = (per_row / ((s.C & 3) ? 1 : 4) + 255) / 256;
         nb = std::max(1LL, std::min(nb, std::max(1LL, 2048LL / rows)));
-        hipLaunchKernelGGL(k_dac_snake, dim3((unsigned)nb, (unsigned)rows), dim3(256), 0, st, x, s.alpha, s.inva, y, per_row, s.C, slot);
+        if (lens) hipLaunchKernelGGL(k_dac_snake<true>, dim3((unsigned)nb, (unsigned)rows), dim3(256), 0, st, x, s.alpha, s.inva, y, per_row, s.C, slot, lens + (size_t)level * rows);
+        else hipLaunchKernelGGL(k_dac_snake<false>, dim3((unsigned)nb, (unsigned)rows), dim3(256), 0, st, x, s.alpha, s.inva, y, per_row, s.C, slot, (const int*)nullptr);
         return slot;
     }
     void conv(const Conv& c, const float* x, const unsigned* x_amax, float* y, const float* res, const float* bias, int64_t Lin, int64_t Lout) {
@@ -590,11 +620,11 @@ float* other(float* const S[3], const float* a, const float* b = nullptr) {
 }
 
 // x -> snake -> k7 dilated -> snake -> k1 + x, into `out` (or a scratch buffer when out is null); returns where the result is
-float* run_res_unit(Walk& w, const ResUnit& u, float* cur, float* const S[3], float* out, int64_t L) {
+float* run_res_unit(Walk& w, const ResUnit& u, float* cur, float* const S[3], float* out, int64_t L, int level) {
     float* a = other(S, cur), *b = other(S, cur, a);
-    const unsigned* ra = w.snake(u.s1, cur, a, L);
+    const unsigned* ra = w.snake(u.s1, cur, a, L, level);
     w.conv(u.c7, a, ra, b, nullptr, u.c7.bias, L, L);
-    const unsigned* rb = w.snake(u.s2, b, b, L);
+    const unsigned* rb = w.snake(u.s2, b, b, L, level);
     float* y = out ? out : a;
     w.conv(u.c1, b, rb, y, cur, u.c1.bias, L, L);
     return y;
@@ -650,14 +680,15 @@ int walk_encode_window(Walk& w, const float* x, int64_t n, const EncWindow& win,
     if (w.go()) {
         const long long total = (long long)rows * L * C;
         const unsigned nb = (unsigned)std::min<long long>((total + 255) / 256, 8192);
-        hipLaunchKernelGGL(k_dac_conv_in, dim3(nb), dim3(256), 0, w.st, x, m.in_w, m.in_b, cur, (long long)n, (long long)win.x0, (long long)Lw, C, total);
+        if (w.xrows) hipLaunchKernelGGL(k_dac_conv_in<true>, dim3(nb), dim3(256), 0, w.st, x, m.in_w, m.in_b, cur, (long long)n, (long long)win.x0, (long long)Lw, C, total, w.xrows);
+        else hipLaunchKernelGGL(k_dac_conv_in<false>, dim3(nb), dim3(256), 0, w.st, x, m.in_w, m.in_b, cur, (long long)n, (long long)win.x0, (long long)Lw, C, total, (const long long*)nullptr);
     }
     w.note(EGR_DAC_STAGE_ENC, 0, cur, (int64_t)rows * L * C);
     for (int i = 0; i < c.n_enc; ++i) {
         const EncBlock& b = m.enc[i];
-        for (int u = 0; u < 3; ++u) cur = run_res_unit(w, b.ru[u], cur, S, nullptr, L);
+        for (int u = 0; u < 3; ++u) cur = run_res_unit(w, b.ru[u], cur, S, nullptr, L, i);
         float* a = other(S, cur);
-        const unsigned* ra = w.snake(b.s, cur, a, L);
+        const unsigned* ra = w.snake(b.s, cur, a, L, i);
         const int64_t Lo = conv_len(L, c.enc_rates[i]);
         float* out = w.take((size_t)rows * Lo * C * 2);
         w.conv(b.down, a, ra, out, nullptr, b.down.bias, L, Lo);
@@ -666,7 +697,7 @@ int walk_encode_window(Walk& w, const float* x, int64_t n, const EncWindow& win,
     }
     if (L != win.frames) { if (!w.rc) { set_error("DAC: a window of %lld frames encodes to %lld", (long long)win.frames, (long long)L); w.rc = EGR_ERR_UNSUPPORTED; } return w.rc; }
     float* a = other(S, cur);
-    const unsigned* ra = w.snake(m.enc_s, cur, a, L);
+    const unsigned* ra = w.snake(m.enc_s, cur, a, L, c.n_enc);
     const bool whole = win.k0 == 0 && win.k1 == L && win.at == 0 && L == win.F;
     float* ze = whole ? ze_all : w.take((size_t)rows * L * m.latent);
     w.conv(m.enc_out, a, ra, ze, nullptr, m.enc_out.bias, L, L);
@@ -777,6 +808,10 @@ int walk_decode_window(Walk& w, const float* z, const DecWindow& win, float* y) 
     if (w.go() && win.z_all)
         EGR_HIP(hipMemcpy2DAsync(z_cl, (size_t)F * m.latent * 4, win.z_all + (size_t)win.f0 * m.latent, (size_t)win.F * m.latent * 4, (size_t)F * m.latent * 4,
                                  (size_t)rows, hipMemcpyDeviceToDevice, w.st));
+    if (w.go() && w.lens) {                              // level 0 of a many decode: each row's own frames
+        const long long total = (long long)rows * F * m.latent;
+        hipLaunchKernelGGL(k_dac_mask_frames, dim3((unsigned)std::min<long long>((total + 255) / 256, 8192)), dim3(256), 0, w.st, z_cl, w.lens, (long long)F, m.latent, total);
+    }
     if (w.go()) { const int rc = egr_absmax_rows(z_cl, rows, F * m.latent, 1, 0, (float*)rz, w.st); if (rc) return rc; }
     int C = c.decoder_dim;
     float* cur = w.take((size_t)rows * L * C);
@@ -785,7 +820,7 @@ int walk_decode_window(Walk& w, const float* z, const DecWindow& win, float* y) 
     for (int i = 0; i < c.n_dec; ++i) {
         const DecBlock& b = m.dec[i];
         float* a = other(S, cur);
-        const unsigned* ra = w.snake(b.s, cur, a, L);
+        const unsigned* ra = w.snake(b.s, cur, a, L, i);
         // ConvTranspose1d: a GEMM onto [tap][co] columns of every input sample, gathered by egr_col2im_convtr1d
         if (w.go()) {
             ConvCall cc;
@@ -798,11 +833,11 @@ int walk_decode_window(Walk& w, const float* z, const DecWindow& win, float* y) 
         if (w.go()) w.rc = egr_col2im_convtr1d(Y, b.up.bias, nullptr, up, rows, (int)L, (int)Lo, b.c_out, b.k, b.stride, b.pad, w.st);
         cur = up; L = Lo; C = b.c_out;
         float* out = w.take((size_t)rows * L * C);
-        for (int u = 0; u < 3; ++u) cur = run_res_unit(w, b.ru[u], cur, S, u == 2 ? out : nullptr, L);
+        for (int u = 0; u < 3; ++u) cur = run_res_unit(w, b.ru[u], cur, S, u == 2 ? out : nullptr, L, i + 1);
         w.note(EGR_DAC_STAGE_DEC, i + 1, cur, (int64_t)rows * L * C);
     }
     float* a = other(S, cur);
-    w.snake(m.dec_s, cur, a, L);
+    w.snake(m.dec_s, cur, a, L, c.n_dec);
     const int64_t o0 = std::max<int64_t>(0, win.o0), o1 = std::min(L, win.o1);
     if (w.go() && o1 > o0) {
         hipLaunchKernelGGL(k_dac_conv_out, dim3((unsigned)((o1 - o0 + DAC_OUT_TL - 1) / DAC_OUT_TL), (unsigned)rows), dim3(256), 0, w.st, a, m.out_w, m.out_b, y,
@@ -1199,6 +1234,150 @@ extern "C" int egr_dacseg_from_codes(void* handle, const int* codes, int rows, i
     else hipLaunchKernelGGL(k_dac_from_codes<0>, grid, dim3(256), 0, (hipStream_t)stream, p);
     EGR_HIP(hipGetLastError());
     return EGR_OK;
+}
+
+// ---- many clips in one padded pass: rows of their own lengths inside tensors of the longest
+namespace {
+struct ManyShape { int64_t P = 0, L = 0; size_t table_bytes = 0; };      // padded frames, padded samples (x for encode, y for decode)
+
+// every refusal of a many call that depends on (rows, pad_frames, kind) alone
+int many_shape(const Dac* m, const char* who, int rows, int64_t pad_frames, int kind, ManyShape* out) {
+    EGR_CHECK(m, EGR_ERR_ARG, "%s: null handle", who);
+    EGR_CHECK(kind == EGR_DAC_ENCODE || kind == EGR_DAC_DECODE, EGR_ERR_ARG, "%s: kind %d", who, kind);
+    EGR_CHECK(rows >= 1 && rows <= 65535, EGR_ERR_ARG, "%s: rows = %d outside 1 .. 65535", who, rows);
+    EGR_CHECK(pad_frames >= 1, EGR_ERR_ARG, "%s: pad_frames = %lld < 1", who, (long long)pad_frames);
+    EGR_CHECK(pad_frames <= (1LL << 26) / rows, EGR_ERR_UNSUPPORTED, "%s: rows * pad_frames = %lld * %lld is more than the quantiser indexes (2^26)", who,
+              (long long)rows, (long long)pad_frames);
+    const egr_dac_config& c = m->cfg;
+    ManyShape s;
+    s.P = pad_frames;
+    if (kind == EGR_DAC_ENCODE) {
+        s.L = pad_frames;
+        for (int i = 0; i < c.n_enc; ++i) s.L *= c.enc_rates[i];
+        int64_t F = s.L;
+        for (int i = 0; i < c.n_enc; ++i) F = conv_len(F, c.enc_rates[i]);
+        EGR_CHECK(F == pad_frames, EGR_ERR_UNSUPPORTED, "%s: pad_frames = %lld frames of samples encode to %lld frames", who, (long long)pad_frames, (long long)F);
+        s.table_bytes = (size_t)rows * 2 * sizeof(int64_t) + (size_t)(c.n_enc + 1) * rows * sizeof(int);
+    } else {
+        s.L = decoded_len(c, pad_frames);
+        EGR_CHECK(s.L >= 1, EGR_ERR_ARG, "%s: pad_frames = %lld frames decode to nothing", who, (long long)pad_frames);
+        s.table_bytes = (size_t)(c.n_dec + 1) * rows * sizeof(int);
+    }
+    EGR_CHECK((long long)rows * s.L < (1LL << 31), EGR_ERR_UNSUPPORTED, "%s: rows * padded samples = %lld does not index with an int (pad_frames too large)", who,
+              (long long)rows * s.L);
+    *out = s;
+    return EGR_OK;
+}
+
+// The tables go up with one copy from the handle's pinned memory (filled by the caller), then the window [0, P) runs with them bound.
+int bind_tables(Walk& w, const ManyShape& s, char** tab) {
+    *tab = (char*)w.take((s.table_bytes + 3) / 4);
+    if (!w.go()) return w.rc;
+    EGR_HIP(hipMemcpyAsync(*tab, w.m.tables.p, s.table_bytes, hipMemcpyHostToDevice, w.st));        // one copy for all tables
+    EGR_HIP(hipEventRecord(w.m.tables.copied, w.st));
+    return EGR_OK;
+}
+
+int walk_many_encode(Walk& w, const float* x, const ManyShape& s, float* z, int* codes, float* ze_out) {
+    char* tab = nullptr;
+    EGR_TRY(bind_tables(w, s, &tab));
+    if (w.go()) { w.xrows = (const long long*)tab; w.lens = (const int*)(tab + (size_t)w.rows * 2 * sizeof(int64_t)); }
+    float* ze_all = w.take((size_t)w.rows * s.P * w.m.latent);
+    { const int rc = walk_encode_window(w, x, 0, EncWindow{0, s.P, 0, s.P, 0, s.P}, ze_all); if (rc) return rc; }
+    return walk_encode_tail(w, ze_all, s.P, z, codes, ze_out);
+}
+
+int walk_many_decode(Walk& w, const float* z, const ManyShape& s, float* y) {
+    char* tab = nullptr;
+    EGR_TRY(bind_tables(w, s, &tab));
+    if (w.go()) w.lens = (const int*)tab;
+    return walk_decode_window(w, z, DecWindow{s.P, nullptr, 0, s.P, 0, s.L, 0, s.L}, y);
+}
+
+// as run_segmented: no stage survives; the tables live in the Walk, so the handle carries nothing into the next call
+template <class F>
+int run_many(Dac& m, int rows, hipStream_t st, F walk) {
+    Walk dry{m, nullptr, false, rows};
+    dry.notes = false;
+    { const int rc = walk(dry); if (rc) return rc; }
+    EGR_TRY(m.ws.grow(dry.off + 256, st));
+    m.stages.clear();
+    Walk w{m, st, true, rows};
+    w.notes = false;
+    w.base = (char*)m.ws.p;
+    return walk(w);
+}
+}  // namespace
+
+extern "C" size_t egr_dacmany_workspace_bytes(void* handle, int rows, int64_t pad_frames, int kind) {
+    Dac* m = (Dac*)handle;
+    ManyShape s;
+    if (many_shape(m, "egr_dacmany_workspace_bytes", rows, pad_frames, kind, &s)) return 0;
+    Walk dry{*m, nullptr, false, rows};
+    dry.notes = false;
+    if (kind == EGR_DAC_ENCODE) walk_many_encode(dry, nullptr, s, nullptr, nullptr, nullptr);
+    else walk_many_decode(dry, nullptr, s, nullptr);
+    return dry.rc ? 0 : dry.off + 256;
+}
+
+extern "C" int egr_dacmany_encode(void* handle, const float* x_flat, const int64_t* rows_host, int rows, int64_t pad_frames, float* z, int* codes,
+                                  float* ze_or_null, void* stream) {
+    const char* who = "egr_dacmany_encode";
+    Dac* m = (Dac*)handle;
+    ManyShape s;
+    EGR_TRY(many_shape(m, who, rows, pad_frames, EGR_DAC_ENCODE, &s));
+    EGR_CHECK(x_flat && rows_host && z && codes, EGR_ERR_ARG, "%s: null argument", who);
+    const egr_dac_config& c = m->cfg;
+    for (int r = 0; r < rows; ++r) {
+        const int64_t off = rows_host[2 * r], n = rows_host[2 * r + 1];
+        EGR_CHECK(off >= 0, EGR_ERR_ARG, "%s: row %d has a negative offset (%lld)", who, r, (long long)off);
+        EGR_CHECK(n >= 1, EGR_ERR_ARG, "%s: row %d has n = %lld < 1", who, r, (long long)n);
+        int64_t F;
+        lengths(c, n, nullptr, &F, nullptr);
+        EGR_CHECK(F >= 1 && F <= pad_frames, EGR_ERR_ARG, "%s: pad_frames = %lld is below row %d (n = %lld samples, %lld frames)", who, (long long)pad_frames, r,
+                  (long long)n, (long long)F);
+    }
+    EGR_TRY(check_current_device(who, m->device));
+    EGR_TRY(m->tables.reserve(s.table_bytes));
+    int64_t* xr = (int64_t*)m->tables.p;
+    int* lens = (int*)(xr + (size_t)rows * 2);
+    for (int r = 0; r < rows; ++r) {
+        xr[2 * r] = rows_host[2 * r];
+        xr[2 * r + 1] = rows_host[2 * r + 1];
+        int64_t L;
+        lengths(c, rows_host[2 * r + 1], &L, nullptr, nullptr);
+        for (int i = 0; i <= c.n_enc; ++i) {
+            lens[(size_t)i * rows + r] = (int)L;
+            if (i < c.n_enc) L = conv_len(L, c.enc_rates[i]);
+        }
+    }
+    return run_many(*m, rows, (hipStream_t)stream, [&](Walk& w) { return walk_many_encode(w, x_flat, s, z, codes, ze_or_null); });
+}
+
+extern "C" int egr_dacmany_decode(void* handle, const float* z, const int64_t* frames_host, int rows, int64_t pad_frames, float* y, void* stream) {
+    const char* who = "egr_dacmany_decode";
+    Dac* m = (Dac*)handle;
+    ManyShape s;
+    EGR_TRY(many_shape(m, who, rows, pad_frames, EGR_DAC_DECODE, &s));
+    EGR_CHECK(z && frames_host && y, EGR_ERR_ARG, "%s: null argument", who);
+    const egr_dac_config& c = m->cfg;
+    for (int r = 0; r < rows; ++r) {
+        EGR_CHECK(frames_host[r] >= 1, EGR_ERR_ARG, "%s: row %d has frames = %lld < 1", who, r, (long long)frames_host[r]);
+        EGR_CHECK(frames_host[r] <= pad_frames, EGR_ERR_ARG, "%s: pad_frames = %lld is below row %d (%lld frames)", who, (long long)pad_frames, r,
+                  (long long)frames_host[r]);
+        EGR_CHECK(decoded_len(c, frames_host[r]) >= 1, EGR_ERR_ARG, "%s: row %d: %lld frames decode to nothing", who, r, (long long)frames_host[r]);
+    }
+    EGR_TRY(check_current_device(who, m->device));
+    EGR_TRY(m->tables.reserve(s.table_bytes));
+    int* lens = (int*)m->tables.p;
+    for (int r = 0; r < rows; ++r) {
+        int64_t L = frames_host[r];
+        for (int i = 0; i <= c.n_dec; ++i) {
+            lens[(size_t)i * rows + r] = (int)L;
+            if (i < c.n_dec) L = convtr_len(L, c.dec_rates[i]);
+        }
+    }
+    return run_many(*m, rows, (hipStream_t)stream, [&](Walk& w) { return walk_many_decode(w, z, s, y); });
 }
 
 extern "C" int egr_dac_stage(void* handle, int stage, int index, float* dst, int64_t capacity, int64_t* count, void* stream) {

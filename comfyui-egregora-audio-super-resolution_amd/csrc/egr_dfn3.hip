@@ -703,30 +703,6 @@ struct SegState {             // what a segmented call carries besides the GRU s
 
 constexpr int N_HIST_CONV = 9;
 
-// Pinned host memory a tracks call copies its tables from, so that the copy is asynchronous, and the event behind the last such copy:
-// the next call waits for that copy alone (not for the stream's other work) before it overwrites the memory.
-struct TableStage {
-    void* p = nullptr;
-    size_t bytes = 0;
-    hipEvent_t copied = nullptr;
-    int reserve(size_t need) {
-        if (!copied) EGR_HIP(hipEventCreateWithFlags(&copied, hipEventDisableTiming));
-        else EGR_HIP(hipEventSynchronize(copied));
-        if (need <= bytes) return EGR_OK;
-        if (p) EGR_HIP(hipHostFree(p));
-        p = nullptr;
-        bytes = 0;
-        EGR_HIP(hipHostMalloc(&p, need, hipHostMallocDefault));
-        bytes = need;
-        return EGR_OK;
-    }
-    void release() {
-        if (copied) { (void)hipEventSynchronize(copied); (void)hipEventDestroy(copied); }
-        if (p) (void)hipHostFree(p);
-        p = nullptr; bytes = 0; copied = nullptr;
-    }
-};
-
 struct DfnCore {
     DfnDims d;
     int device = 0, Fq = 0, embd = 0;

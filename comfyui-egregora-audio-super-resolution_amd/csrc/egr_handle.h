@@ -1,5 +1,5 @@
 // What the model handles that live inside the library (DfnCore, Dac) share around a call: the kept workspace, the device checks and the
-// stage copy-out; and the move-only owners of device resources (DevBuf, EventPair, Stream) that the FlashSR handle and the Fat-Llama plan
+// stage copy-out and the pinned staging of per-row tables (TableStage); and the move-only owners of device resources (DevBuf, EventPair, Stream) that the FlashSR handle and the Fat-Llama plan
 // hold as members.  WPE (caller-owned workspace) has a lifetime of its own.
 #pragma once
 #include "egr_common.h"
@@ -46,6 +46,30 @@ struct Workspace {
         (void)hipDeviceSynchronize();
         p = nullptr;
         bytes = 0;
+    }
+};
+
+// Pinned host memory a tracks call copies its tables from, so that the copy is asynchronous, and the event behind the last such copy:
+// the next call waits for that copy alone (not for the stream's other work) before it overwrites the memory.
+struct TableStage {
+    void* p = nullptr;
+    size_t bytes = 0;
+    hipEvent_t copied = nullptr;
+    int reserve(size_t need) {
+        if (!copied) EGR_HIP(hipEventCreateWithFlags(&copied, hipEventDisableTiming));
+        else EGR_HIP(hipEventSynchronize(copied));
+        if (need <= bytes) return EGR_OK;
+        if (p) EGR_HIP(hipHostFree(p));
+        p = nullptr;
+        bytes = 0;
+        EGR_HIP(hipHostMalloc(&p, need, hipHostMallocDefault));
+        bytes = need;
+        return EGR_OK;
+    }
+    void release() {
+        if (copied) { (void)hipEventSynchronize(copied); (void)hipEventDestroy(copied); }
+        if (p) (void)hipHostFree(p);
+        p = nullptr; bytes = 0; copied = nullptr;
     }
 };
 

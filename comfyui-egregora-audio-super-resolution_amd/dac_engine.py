@@ -8,7 +8,7 @@ import ctypes as C
 import os
 import threading
 from pathlib import Path
-from typing import Callable, NamedTuple, Optional, Tuple
+from typing import Callable, List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
@@ -62,6 +62,14 @@ SEGMENT_ALIGN = 16                          # interior windows are widened to a 
 # windows leave too few workgroups and it turns to split-K: profiles/dac_segmented.md); its margins (8 + 8 frames, widened to a
 # multiple of 16) are under 1 % of the work, its workspace about 3 GiB a row.
 SEGMENT_STEP = 2048
+# Many clips in one padded pass.  plan_waves closes a wave before the clip that would take its padding share
+# 1 - sum(frames) / (rows * pad_frames) above MAX_PAD_SHARE.  Cost follows rows x longest, and at 2-12 s a clip the contractions are
+# already full, so padding is paid in full: on the 200-clip corpus of profiles/dac_batch.md 0.05 was the fastest of 0.02 .. 0.5 for
+# both directions (the first guess, 0.25, lost to the per-clip loop on decode).
+MAX_PAD_SHARE = 0.05
+MANY_MAX_ROWS = 65535                       # the kernels' grid.y
+MANY_MAX_SAMPLES = 2 ** 31                  # rows x padded samples stay below it (int indices of the contraction launcher)
+MANY_MAX_FRAMES = 2 ** 26                   # rows x pad_frames stay at or below it (the quantiser's index)
 
 
 class Segment(NamedTuple):
@@ -170,6 +178,73 @@ def choose_path(frames: int, one_pass_bytes: int, budget_bytes: int, bytes_for: 
         else:
             hi = mid
     return lo * SEGMENT_STEP
+
+
+def default_pad_frames(longest: int) -> int:
+    """The padded length a many call takes by default: the longest row rounded up to a multiple of SEGMENT_ALIGN frames when it has
+    at least that many (every level is then a multiple of 128 samples: k_conv1d_s3's condition), else as it is."""
+    longest = int(longest)
+    return -(-longest // SEGMENT_ALIGN) * SEGMENT_ALIGN if longest >= SEGMENT_ALIGN else longest
+
+
+def level_lengths(cfg: dict, kind: int, length: int) -> List[int]:
+    """The valid positions of one row at every level of one side, input to output: ENCODE from n samples (n_padded, then
+    conv_length per rate: n_enc + 1 values, the last its frames), DECODE from its frames (convtr_length per rate: n_dec + 1 values,
+    the last its decoded samples).  The host twin of the tables egr_dacmany_encode / _decode upload."""
+    if kind == ENCODE:
+        out = [lengths(cfg, int(length))[0]]
+        for s in cfg["encoder_rates"]:
+            out.append(conv_length(out[-1], s))
+        return out
+    out = [int(length)]
+    for s in cfg["decoder_rates"]:
+        out.append(convtr_length(out[-1], s))
+    return out
+
+
+def padded_samples(cfg: dict, kind: int, pad_frames: int) -> int:
+    """Samples a row of pad_frames frames has on the wide side: of x (ENCODE) or of y (DECODE)."""
+    return pad_frames * dac_weights.hop(cfg) if kind == ENCODE else decoded_length(cfg, pad_frames)
+
+
+class Wave(NamedTuple):
+    clips: Tuple[int, ...]                  # indices into plan_waves' input, longest first
+    rows: int
+    pad_frames: int
+
+
+def plan_waves(clips: Sequence[Tuple[int, int]], bytes_for: Callable[[int, int], int], budget_bytes: int,
+               samples_for: Callable[[int], int], max_pad_share: Optional[float] = None) -> Tuple[List[Wave], List[int]]:
+    """clips: (rows, frames) per clip.  -> (waves, alone).  Clips stay whole and are taken longest first (ties in input order); a
+    wave's pad_frames is default_pad_frames of its first (longest) clip.  A wave closes before the clip that would take
+    bytes_for(rows, pad_frames) past budget_bytes, rows past MANY_MAX_ROWS, rows x samples_for(pad_frames) to MANY_MAX_SAMPLES, rows x
+    pad_frames past MANY_MAX_FRAMES, or the padding share above max_pad_share (default MAX_PAD_SHARE, read at the call).  alone: the
+    clips that exceed a limit on their own; they take the single path, which segments."""
+    share = MAX_PAD_SHARE if max_pad_share is None else float(max_pad_share)
+
+    def fits(rows, pad):
+        return (rows <= MANY_MAX_ROWS and rows * samples_for(pad) < MANY_MAX_SAMPLES and rows * pad <= MANY_MAX_FRAMES
+                and 0 < bytes_for(rows, pad) <= budget_bytes)
+
+    order = sorted(range(len(clips)), key=lambda i: (-int(clips[i][1]), i))
+    waves, alone, cur, rows, pad, used = [], [], [], 0, 0, 0
+    for i in order:
+        r, f = int(clips[i][0]), int(clips[i][1])
+        if r < 1 or f < 1:
+            raise ValueError(f"plan_waves: clip {i} has {r} rows of {f} frames")
+        if cur and (not fits(rows + r, pad) or 1.0 - (used + r * f) / ((rows + r) * pad) > share):
+            waves.append(Wave(tuple(cur), rows, pad))
+            cur = []
+        if not cur:
+            rows, pad, used = 0, default_pad_frames(f), 0
+            if not fits(r, pad):
+                alone.append(i)
+                continue
+        cur.append(i)
+        rows, used = rows + r, used + r * f
+    if cur:
+        waves.append(Wave(tuple(cur), rows, pad))
+    return waves, alone
 
 
 def config_c(cfg: dict) -> native.DacConfigC:
@@ -326,6 +401,134 @@ class DacEngine:
             native.check(native.lib().egr_dacseg_from_codes(self.h, native.ptr(c32), rows, frames, native.ptr(z), native.stream_ptr()),
                          "egr_dacseg_from_codes")
         return z
+
+    # ---- many clips in one padded pass
+    def many_workspace_bytes(self, rows: int, pad_frames: int, kind: int = ENCODE) -> int:
+        """egr_dacmany_workspace_bytes: 0 for a shape the many calls refuse."""
+        return int(native.lib().egr_dacmany_workspace_bytes(self.h, int(rows), int(pad_frames), int(kind)))
+
+    def encode_rows(self, x_flat: torch.Tensor, offsets: Sequence[int], lengths: Sequence[int], pad_frames: Optional[int] = None,
+                    return_ze: bool = False):
+        """Rows of their own lengths in one pass: row r is the lengths[r] samples at offsets[r] of the flat float32 device tensor
+        x_flat (what lies between rows is never read).  -> (z [rows, latent, pad_frames], codes [rows, n_codebooks, pad_frames]
+        [, ze]); row r holds lengths(n_r)[1] frames, the rest is unspecified.  pad_frames None: default_pad_frames(longest row)."""
+        if x_flat.dim() != 1 or not x_flat.is_cuda or x_flat.device.index != self.device or x_flat.dtype != torch.float32:
+            raise ValueError(f"DAC encode_rows: expected a flat float32 tensor on cuda:{self.device}")
+        x_flat = x_flat.contiguous()
+        rows = len(lengths)
+        if rows < 1 or len(offsets) != rows:
+            raise ValueError(f"DAC encode_rows: {len(offsets)} offsets, {rows} lengths")
+        for o, n in zip(offsets, lengths):
+            if int(n) >= 1 and int(o) >= 0 and int(o) + int(n) > x_flat.numel():
+                raise ValueError(f"DAC encode_rows: row [{o}, {int(o) + int(n)}) lies outside x_flat ({x_flat.numel()} samples)")
+        longest = max(self.lengths(max(1, int(n)))[1] for n in lengths)
+        P = default_pad_frames(longest) if pad_frames is None else int(pad_frames)
+        table = (C.c_int64 * (2 * rows))(*[int(v) for pair in zip(offsets, lengths) for v in pair])
+        z, codes = self._outputs(rows, max(P, 1))
+        ze = torch.empty_like(z) if return_ze else None
+        with torch.cuda.device(self.device):
+            native.check(native.lib().egr_dacmany_encode(self.h, native.ptr(x_flat), table, rows, P, native.ptr(z), native.ptr(codes),
+                                                         native.ptr(ze) if return_ze else None, native.stream_ptr()), "egr_dacmany_encode")
+        return (z, codes, ze) if return_ze else (z, codes)
+
+    def decode_rows(self, z_padded: torch.Tensor, frames: Sequence[int], pad_frames: Optional[int] = None) -> torch.Tensor:
+        """z_padded [rows, latent, >= longest] with row r's own frames[r] frames in front (the rest is ignored: it may hold anything)
+        -> y [rows, decoded_length(pad_frames)]; row r holds decoded_length(frames[r]) samples.  pad_frames None:
+        default_pad_frames(longest row); z_padded is cut or widened to it."""
+        z = self._rows(z_padded, "decode_rows", 3)
+        rows, lat, have = z.shape
+        if lat != self.cfg["latent_dim"] or len(frames) != rows:
+            raise ValueError(f"DAC decode_rows: z {tuple(z.shape)}, {len(frames)} frame counts, latent_dim {self.cfg['latent_dim']}")
+        longest = max(int(f) for f in frames)
+        if longest > have:
+            raise ValueError(f"DAC decode_rows: a row of {longest} frames, z_padded holds {have}")
+        P = default_pad_frames(longest) if pad_frames is None else int(pad_frames)
+        if P != have and P >= 1:
+            zp = torch.zeros((rows, lat, P), dtype=torch.float32, device=z.device)
+            zp[:, :, :min(P, have)] = z[:, :, :min(P, have)]
+            z = zp
+        table = (C.c_int64 * rows)(*[int(f) for f in frames])
+        y = torch.empty((rows, max(1, decoded_length(self.cfg, max(P, 1)))), dtype=torch.float32, device=z.device)
+        with torch.cuda.device(self.device):
+            native.check(native.lib().egr_dacmany_decode(self.h, native.ptr(z), table, rows, P, native.ptr(y), native.stream_ptr()),
+                         "egr_dacmany_decode")
+        return y
+
+    def _plan(self, shapes: Sequence[Tuple[int, int]], kind: int) -> Tuple[List[Wave], List[int]]:
+        return plan_waves(shapes, lambda rows, pad: self.many_workspace_bytes(rows, pad, kind), workspace_budget_bytes(),
+                          lambda pad: padded_samples(self.cfg, kind, pad))
+
+    def encode_many(self, clips: Sequence[torch.Tensor], stats: Optional[dict] = None) -> List[Tuple[torch.Tensor, torch.Tensor]]:
+        """clips: [C_i, T_i] device tensors at the model's rate -> [(z_i [C_i, latent, F_i], codes_i [C_i, n_codebooks, F_i])] in
+        input order, one encode_rows per wave of plan_waves; a clip that exceeds a limit on its own goes through encode().  stats,
+        when given, receives waves (the Wave list) and alone."""
+        clips = [self._rows(x, "encode_many", 2) for x in clips]
+        waves, alone = self._plan([(x.shape[0], self.lengths(x.shape[1])[1]) for x in clips], ENCODE)
+        if stats is not None:
+            stats.update(waves=waves, alone=alone)
+        out: List = [None] * len(clips)
+        for w in waves:
+            offs, lens, pos = [], [], 0
+            for i in w.clips:
+                c, T = clips[i].shape
+                offs += [pos + k * T for k in range(c)]
+                lens += [T] * c
+                pos += c * T
+            flat = torch.cat([clips[i].reshape(-1) for i in w.clips]) if len(w.clips) > 1 else clips[w.clips[0]].reshape(-1)
+            z, codes = self.encode_rows(flat, offs, lens, w.pad_frames)
+            r = 0
+            for i in w.clips:
+                c, F = clips[i].shape[0], self.lengths(clips[i].shape[1])[1]
+                out[i] = (z[r:r + c, :, :F].contiguous(), codes[r:r + c, :, :F].contiguous())
+                r += c
+        for i in alone:
+            out[i] = self.encode(clips[i])
+        return out
+
+    def decode_many(self, items: Sequence[torch.Tensor], stats: Optional[dict] = None) -> List[torch.Tensor]:
+        """items: z_i [C_i, latent, F_i] float or codes_i [C_i, n_codebooks, F_i] of an integer dtype, on the device -> [y_i [C_i,
+        decoded_length(F_i)]] in input order, one decode_rows per wave.  Codes are padded with code 0 to the wave's pad_frames and go
+        through from_codes (which refuses codes outside the codebook); the decode masks what the padding made."""
+        for i, t in enumerate(items):
+            want = self.cfg["latent_dim"] if t.is_floating_point() else self.cfg["n_codebooks"]
+            if t.dim() != 3 or not t.is_cuda or t.device.index != self.device or 0 in t.shape or t.shape[1] != want:
+                raise ValueError(f"DAC decode_many: item {i}: expected [C, {want}, frames] on cuda:{self.device}, got {tuple(t.shape)} on {t.device}")
+        waves, alone = self._plan([(t.shape[0], t.shape[2]) for t in items], DECODE)
+        if stats is not None:
+            stats.update(waves=waves, alone=alone)
+        out: List = [None] * len(items)
+        dev = f"cuda:{self.device}"
+        for w in waves:
+            P = w.pad_frames
+            zp = torch.zeros((w.rows, self.cfg["latent_dim"], P), dtype=torch.float32, device=dev)
+            code_rows = sum(items[i].shape[0] for i in w.clips if not items[i].is_floating_point())
+            cp = torch.zeros((code_rows, self.cfg["n_codebooks"], P), dtype=torch.int32, device=dev) if code_rows else None
+            r, rc, where = 0, 0, []
+            for i in w.clips:
+                t = items[i]
+                c, F = t.shape[0], t.shape[2]
+                if t.is_floating_point():
+                    zp[r:r + c, :, :F] = t
+                else:
+                    cp[rc:rc + c, :, :F] = t
+                    where.append((r, rc, c))
+                    rc += c
+                r += c
+            if cp is not None:
+                zc = self.from_codes(cp)
+                for r0, c0, c in where:
+                    zp[r0:r0 + c] = zc[c0:c0 + c]
+            frames = [items[i].shape[2] for i in w.clips for _ in range(items[i].shape[0])]
+            y = self.decode_rows(zp, frames, P)
+            r = 0
+            for i in w.clips:
+                c, F = items[i].shape[0], items[i].shape[2]
+                out[i] = y[r:r + c, :decoded_length(self.cfg, F)].contiguous()
+                r += c
+        for i in alone:
+            t = items[i]
+            out[i] = self.decode(t.float() if t.is_floating_point() else self.from_codes(t))
+        return out
 
     def keep_stages(self, enable: bool = True):
         """Have the quantiser write the residual entering each stage ("vq_in"; n_codebooks extra latent frames per frame: off by default)."""

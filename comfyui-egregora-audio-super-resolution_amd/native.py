@@ -191,6 +191,9 @@ SIGNATURES = {
     "egr_dacseg_workspace_bytes": (C.c_size_t, [_vp, _i, _i64, _i64, _i]),
     "egr_dacseg_workspace_held": (C.c_size_t, [_vp]),
     "egr_dacseg_from_codes": (_i, [_vp, _vp, _i, _i64, _vp, _vp]),
+    "egr_dacmany_workspace_bytes": (C.c_size_t, [_vp, _i, _i64, _i]),
+    "egr_dacmany_encode": (_i, [_vp, _vp, _vp, _i, _i64, _vp, _vp, _vp, _vp]),
+    "egr_dacmany_decode": (_i, [_vp, _vp, _vp, _i, _i64, _vp, _vp]),
 }
 
 FSR_MAX = 8

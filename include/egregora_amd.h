@@ -880,6 +880,27 @@ size_t egr_dacseg_workspace_bytes(void* handle, int rows, int64_t seg_frames, in
 size_t egr_dacseg_workspace_held(void* handle);
 int egr_dacseg_from_codes(void* handle, const int* codes, int rows, int64_t frames, float* z, void* stream);
 
+/* Many clips in one padded pass: the egr_dacmany_* family, on the handle of egr_dac_create.  Rows of their own
+ * lengths run inside tensors of pad_frames frames; every snake stores +0.0f at and beyond a row's own length at its level, the
+ * input convolution reads each row's own [0, n) and the decoder's input is zeroed beyond a row's own frames, so every convolution
+ * sees at a row's end the zero padding the single call gives it.  A row equals its single call to fp32 round-off (the launcher
+ * chooses tiles from the padded shape), bit for bit where the shapes coincide; no row depends on another row's values.
+ *   egr_dacmany_encode : x_flat device floats; rows_host [rows][2] = (offset, n) of each row in x_flat, on the HOST (read before
+ *                      the call returns).  z, ze_or_null [rows][latent][pad_frames], codes [rows][n_codebooks][pad_frames].
+ *   egr_dacmany_decode : z [rows][latent][pad_frames]; frames_host [rows] on the host; y [rows][decoded length of pad_frames].
+ *                      Beyond a row's own frames / samples the outputs are unspecified (codes stay inside [0, codebook_size), nothing
+ *                      is NaN for finite inputs).  pad_frames >= the longest row is the caller's choice.
+ *   egr_dacmany_workspace_bytes : what such a call grows the workspace to (kind EGR_DAC_ENCODE / EGR_DAC_DECODE); 0 for arguments
+ *                      the calls refuse.
+ * Refused with EGR_ERR_ARG / EGR_ERR_UNSUPPORTED before anything is allocated or enqueued: rows < 1 (or above 65535), a row with
+ * n < 1 or frames < 1, a negative offset, pad_frames below the longest row, rows * padded samples >= 2^31, rows * pad_frames > 2^26.
+ * The per-row tables go up with one asynchronous copy from pinned memory the handle keeps; nothing synchronises and nothing is kept
+ * from call to call.  egr_dac_stage after a many call: EGR_ERR_ARG. */
+size_t egr_dacmany_workspace_bytes(void* handle, int rows, int64_t pad_frames, int kind);
+int egr_dacmany_encode(void* handle, const float* x_flat, const int64_t* rows_host, int rows, int64_t pad_frames, float* z, int* codes,
+                       float* ze_or_null, void* stream);
+int egr_dacmany_decode(void* handle, const float* z, const int64_t* frames_host, int rows, int64_t pad_frames, float* y, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
