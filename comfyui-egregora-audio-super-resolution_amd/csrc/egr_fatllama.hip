@@ -595,18 +595,16 @@ __global__ __launch_bounds__(256) void k_chirp_b(ChirpP cp, long long P, cplx* _
 // linspace (SPEC.md "interp"): y[j] = interp(j (n_in - 1) / (n_out - 1), arange(n_in), x) -- numpy.interp on the endpoint-inclusive
 // grid numpy.linspace(0, n_in - 1, n_out), evaluated like numpy (double: slope * (pos - i) + x[i], last point exactly x[n_in - 1]);
 // n_out need not be a multiple of n_in (factor_mode "ratio_then_int").
-__global__ __launch_bounds__(256) void k_prepare(const float* __restrict__ x, float* __restrict__ y, long long n_in,
-                                                  int f, int pcm_in, int zero_stuff, unsigned* __restrict__ peak_in,
-                                                  unsigned* __restrict__ peak_y, int linspace = 0, long long n_out = 0) {
+// One channel row: xc -> yc (n_in f samples; n_out with linspace), the row's peaks into *peak_in / *peak_y.  Shared by k_prepare (the
+// rows of one plan) and k_prepare_rows (rows of their own lengths, egr_flmany_enhance).
+__device__ __forceinline__ void fl_prepare_row(const float* __restrict__ xc, float* __restrict__ yc, long long n_in, int f, int pcm_in,
+                                               int zero_stuff, unsigned* __restrict__ peak_in, unsigned* __restrict__ peak_y, int linspace,
+                                               long long n_out, float* red) {
 #pragma clang fp contract(off)      // the roundings below are the PCM arithmetic of the reference, written out
-    __shared__ float red[8];
-    const int ch = blockIdx.y;
-    const float* xc = x + (size_t)ch * n_in;
-    float* yc = y + (size_t)ch * n_in * f;
     const float ff = (float)f;
     float mx = 0.f, my = 0.f;
     if (linspace) {
-        float* yo = y + (size_t)ch * n_out;
+        float* yo = yc;
         auto q = [&](float a) -> float {
             if (!pcm_in) return a;
             long long qa = (long long)rintf(__fmul_rn(a, 32767.0f));
@@ -633,8 +631,8 @@ __global__ __launch_bounds__(256) void k_prepare(const float* __restrict__ x, fl
         mx = block_max(mx, red);
         my = block_max(my, red);
         if (threadIdx.x == 0) {
-            atomic_max_abs(peak_in + ch, mx);
-            atomic_max_abs(peak_y + ch, my);
+            atomic_max_abs(peak_in, mx);
+            atomic_max_abs(peak_y, my);
         }
         return;
     }
@@ -670,9 +668,34 @@ __global__ __launch_bounds__(256) void k_prepare(const float* __restrict__ x, fl
     mx = block_max(mx, red);
     my = block_max(my, red);
     if (threadIdx.x == 0) {
-        atomic_max_abs(peak_in + ch, mx);
-        atomic_max_abs(peak_y + ch, my);
+        atomic_max_abs(peak_in, mx);
+        atomic_max_abs(peak_y, my);
     }
+}
+
+__global__ __launch_bounds__(256) void k_prepare(const float* __restrict__ x, float* __restrict__ y, long long n_in,
+                                                  int f, int pcm_in, int zero_stuff, unsigned* __restrict__ peak_in,
+                                                  unsigned* __restrict__ peak_y, int linspace = 0, long long n_out = 0) {
+    __shared__ float red[8];
+    const int ch = blockIdx.y;
+    fl_prepare_row(x + (size_t)ch * n_in, linspace ? y + (size_t)ch * n_out : y + (size_t)ch * n_in * f, n_in, f, pcm_in, zero_stuff,
+                   peak_in + ch, peak_y + ch, linspace, n_out, red);
+}
+
+// A channel row of a wave (egr_flmany_*): its own lengths and places in the flat x and y / out buffers, and the channel rows
+// [c_lo, c_hi) of its clip (the joint peak of k_finalize_rows).
+struct FlRagRow {
+    long long x_off, y_off, n_in, n_out;
+    int factor, c_lo, c_hi, pad_;
+};
+// k_prepare for rows of their own lengths: blockIdx.y = channel row; the grid covers the longest row
+__global__ __launch_bounds__(256) void k_prepare_rows(const float* __restrict__ x, float* __restrict__ y, const FlRagRow* __restrict__ rows,
+                                                       int pcm_in, int zero_stuff, unsigned* __restrict__ peak_in, unsigned* __restrict__ peak_y,
+                                                       int linspace) {
+    __shared__ float red[8];
+    const int ch = blockIdx.y;
+    const FlRagRow r = rows[ch];
+    fl_prepare_row(x + r.x_off, y + r.y_off, r.n_in, r.factor, pcm_in, zero_stuff, peak_in + ch, peak_y + ch, linspace, r.n_out, red);
 }
 
 // max_iter == 0 path: out = y + (|y|>thr ? y : 0), peaks
@@ -698,15 +721,15 @@ __global__ __launch_bounds__(256) void k_noiter(float* __restrict__ y, long long
 // joint_ext (optional): the peak of channels this plan does NOT hold -- the other ranks' of a channel-parallel run
 // (egr_fatllama_joint_peak on every rank, one all-reduce(MAX) of that float, egr_fatllama_finalize): max is exact, so the result is
 // the single-plan result bit for bit.  joint_dst (optional, k_joint_peak): where this plan's own joint peak goes; nothing else is done.
-__global__ __launch_bounds__(256) void k_finalize(float* __restrict__ out, long long N, int C, unsigned flags,
-                                                   const unsigned* __restrict__ peak_in,
-                                                   const unsigned* __restrict__ peak_out,
-                                                   const float* __restrict__ joint_ext, float* __restrict__ joint_dst) {
+// One channel row `ch` (samples oc[0 .. N)) of a signal whose channels are the rows [c_lo, c_hi) of the peak arrays.  Shared by
+// k_finalize (c_lo = 0, c_hi = C) and k_finalize_rows.
+__device__ __forceinline__ void fl_finalize_row(float* __restrict__ oc, long long N, int c_lo, int c_hi, int ch, unsigned flags,
+                                                const unsigned* __restrict__ peak_in, const unsigned* __restrict__ peak_out,
+                                                const float* __restrict__ joint_ext, float* __restrict__ joint_dst) {
 #pragma clang fp contract(off)      // the roundings below are the PCM arithmetic of the reference, written out
-    const int ch = blockIdx.y;
     float s_auto = 1.f;
     float joint = 0.f;
-    for (int c = 0; c < C; ++c) {
+    for (int c = c_lo; c < c_hi; ++c) {
         const float pi = __uint_as_float(peak_in[c]), po = __uint_as_float(peak_out[c]);
         float s = 1.f, m = po;
         if ((flags & EGR_FL_AUTOSCALE) && po > 0.f) {
@@ -725,7 +748,6 @@ __global__ __launch_bounds__(256) void k_finalize(float* __restrict__ out, long 
     const bool do_norm = (flags & EGR_FL_NORMALIZE) && joint > 0.f;
     float peak_final = do_norm ? 1.0f : joint;
     const bool patch = (flags & EGR_FL_NODE_POST) && peak_final > 1.0f;
-    float* oc = out + (size_t)ch * N;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < N;
          i += (long long)gridDim.x * blockDim.x) {
         float v = oc[i];
@@ -739,6 +761,22 @@ __global__ __launch_bounds__(256) void k_finalize(float* __restrict__ out, long 
         }
         oc[i] = v;
     }
+}
+
+__global__ __launch_bounds__(256) void k_finalize(float* __restrict__ out, long long N, int C, unsigned flags,
+                                                   const unsigned* __restrict__ peak_in,
+                                                   const unsigned* __restrict__ peak_out,
+                                                   const float* __restrict__ joint_ext, float* __restrict__ joint_dst) {
+    const int ch = blockIdx.y;
+    fl_finalize_row(out + (size_t)ch * N, N, 0, C, ch, flags, peak_in, peak_out, joint_ext, joint_dst);
+}
+
+// k_finalize for rows of their own lengths: autoscale, the joint peak and the write patch over the channel rows of the row's own clip
+__global__ __launch_bounds__(256) void k_finalize_rows(float* __restrict__ out, const FlRagRow* __restrict__ rows, unsigned flags,
+                                                        const unsigned* __restrict__ peak_in, const unsigned* __restrict__ peak_out) {
+    const int ch = blockIdx.y;
+    const FlRagRow r = rows[ch];
+    fl_finalize_row(out + r.y_off, r.n_out, r.c_lo, r.c_hi, ch, flags, peak_in, peak_out, nullptr, nullptr);
 }
 
 }  // namespace egr
@@ -1759,6 +1797,250 @@ extern "C" int egr_gcc_phat(egr_fatllama_plan* p, const float* a, int64_t na, co
 }
 
 // ---- EGR_LDS_CANARY (debug builds): guard-band failures since the library was loaded, and a self-test of the guards' placement ----
+// ---- waves of clips on one paired chirp-z plan (egr_flmany_*) ----
+// Clips whose lengths have no packed plan share the convolution length P of the largest of them (the cyclic convolution is exact for
+// any P >= 2 D - 1) and run as states of the same launches; what depends on a clip's own D sits in a row table (PzRowP).
+namespace {
+struct FlManyClip { int64_t n_in, N; int factor, channels, kind, levels; int64_t D, P_own; int state0, nstates, row0; };
+struct FlManyState { int clip, nch, row; int64_t D; PzGeo geo; };
+struct FlManyShape {
+    std::vector<FlManyClip> clips;
+    std::vector<FlManyState> states;
+    FlSplit sp{};                 // the wave's plan: pz_length of the largest D
+    int kind = 0, rows = 0, gpx = 0, big = -1;      // big: the clip with the largest D
+    int bad_clip = -1, reason = 0;
+    int64_t bytes = 0, x_total = 0, out_total = 0;
+    int distinct = 0;
+    bool linspace = false;        // some clip's n_out is not n_in * factor: EGR_FL_INTERP_LINSPACE is required
+};
+const char* const kFlManyReason[] = {"", "its length has a packed plan", "its chirp-z plan has three levels", "its chirp-z kind differs from clip 0's",
+                                     "the wave would exceed 1024 channel rows", "no convolution length for it", "EGR_FL_LEGACY_CHIRPZ is set"};
+}  // namespace
+
+// Host only.  rc != EGR_OK: an argument is out of range.  Otherwise shape->bad_clip < 0 says that the clips form one wave.
+static int flmany_shape(int n_clips, const int64_t* n_in, const int* factor, const int64_t* n_out, const int* channels, FlManyShape* shape) {
+    EGR_CHECK(n_clips >= 1 && n_in && factor && channels, EGR_ERR_ARG, "egr_flmany: %d clips / null array", n_clips);
+    const FlSwitches sw = fl_read_switches();
+    FlManyShape& w = *shape;
+    w.clips.resize((size_t)n_clips);
+    auto refuse = [&](int i, int why) { if (w.bad_clip < 0) { w.bad_clip = i; w.reason = why; } };
+    int64_t Dmax = 0, rows = 0;
+    for (int i = 0; i < n_clips; ++i) {
+        FlManyClip& c = w.clips[(size_t)i];
+        EGR_CHECK(n_in[i] >= 1 && factor[i] >= 1 && channels[i] >= 1 && (!n_out || n_out[i] == 0 || n_out[i] >= n_in[i]), EGR_ERR_ARG,
+                  "egr_flmany: clip %d: n_in=%lld factor=%d channels=%d out of range", i, (long long)n_in[i], factor[i], channels[i]);
+        c.n_in = n_in[i]; c.factor = factor[i]; c.channels = channels[i];
+        c.N = (n_out && n_out[i] > 0) ? n_out[i] : n_in[i] * factor[i];
+        if (c.N != c.n_in * c.factor) { w.linspace = true; c.factor = 1; }
+        EGR_CHECK(c.N >= 2, EGR_ERR_ARG, "egr_flmany: clip %d has %lld output samples", i, (long long)c.N);
+        rows += c.channels;
+        c.kind = 0; c.levels = 0; c.D = 0; c.P_own = 0;
+        if (plan_split(c.N, sw.m1, sw.tc).ok) { refuse(i, 1); continue; }
+        c.kind = pz_kind_for(c.N);
+        c.D = c.kind == 1 ? c.N / 2 : c.N;
+        FlSplit sp;
+        if (!pz_length(c.D, sw, &sp)) { c.kind = 0; refuse(i, 5); continue; }
+        c.P_own = sp.M; c.levels = sp.levels;
+        if (sw.legacy_chirpz) refuse(i, 6);
+        if (sp.levels != 2) refuse(i, 2);
+        if (c.kind != w.clips[0].kind) refuse(i, 3);
+        if (c.D > Dmax) { Dmax = c.D; w.big = i; w.sp = sp; }
+    }
+    w.rows = (int)std::min<int64_t>(rows, 1 << 30);
+    if (rows > EGR_FLMANY_MAX_ROWS) refuse(n_clips - 1, 4);
+    if (w.bad_clip >= 0) return EGR_OK;
+    w.kind = w.clips[0].kind;
+    const int nc = (int)(w.sp.M / w.sp.M1);
+    std::vector<int64_t> ds;
+    int row = 0;
+    for (int i = 0; i < n_clips; ++i) {
+        FlManyClip& c = w.clips[(size_t)i];
+        c.state0 = (int)w.states.size(); c.row0 = row;
+        c.nstates = w.kind == 1 ? c.channels : (c.channels + 1) / 2;
+        for (int j = 0; j < c.nstates; ++j) {
+            FlManyState st;
+            st.clip = i; st.D = c.D;
+            st.nch = w.kind == 1 ? 1 : std::min(2, c.channels - 2 * j);
+            st.row = row + (w.kind == 1 ? j : 2 * j);
+            st.geo = pz_row_geometry((unsigned long long)c.D, nc, w.sp.TC);
+            w.gpx = std::max(w.gpx, st.geo.g_per_xcd);
+            w.states.push_back(st);
+        }
+        row += c.channels;
+        w.x_total += (int64_t)c.channels * c.n_in;
+        w.out_total += (int64_t)c.channels * (c.N + (c.N & 1));       // every channel slice starts on an 8-byte boundary (float2 accesses of kind 1)
+        ds.push_back(c.D);
+    }
+    std::sort(ds.begin(), ds.end());
+    w.distinct = (int)(std::unique(ds.begin(), ds.end()) - ds.begin());
+    const int64_t P = w.sp.M, ns = (int64_t)w.states.size();
+    // the states, one chirp spectrum per distinct D, the two double-precision scratch buffers of the build, peaks and tables
+    w.bytes = ns * P * 8 + (int64_t)w.distinct * P * 8 + 2 * P * 16 + 3 * 2 * ns * 4 + ns * (int64_t)sizeof(PzRowP) + (int64_t)w.rows * (int64_t)sizeof(FlRagRow);
+    return EGR_OK;
+}
+
+extern "C" int egr_flmany_query(int n_clips, const int64_t* n_in, const int* factor, const int64_t* n_out, const int* channels, int64_t* info) {
+    EGR_CHECK(info != nullptr, EGR_ERR_ARG, "info is null");
+    FlManyShape w;
+    EGR_TRY(flmany_shape(n_clips, n_in, factor, n_out, channels, &w));
+    int64_t total_ch = 0;
+    for (const FlManyClip& c : w.clips) total_ch += c.channels;
+    memset(info, 0, sizeof(int64_t) * (size_t)(EGR_FLMANY_HEAD + EGR_FLMANY_REC * ((int64_t)n_clips + total_ch)));
+    info[0] = w.bad_clip < 0 ? 1 : 0;
+    info[6] = w.rows;
+    info[10] = w.bad_clip; info[11] = w.reason;
+    for (int i = 0; i < n_clips; ++i) {
+        const FlManyClip& c = w.clips[(size_t)i];
+        int64_t* r = info + EGR_FLMANY_HEAD + EGR_FLMANY_REC * (int64_t)i;
+        r[0] = c.kind; r[1] = c.D; r[2] = c.P_own; r[3] = c.levels; r[4] = c.N;
+        if (w.bad_clip < 0) { r[5] = c.state0; r[6] = c.nstates; r[7] = c.row0; }
+    }
+    if (w.bad_clip >= 0) return EGR_OK;
+    info[1] = w.kind; info[2] = w.sp.M1; info[3] = w.sp.M / w.sp.M1; info[4] = w.sp.M; info[5] = (int64_t)w.states.size();
+    info[7] = w.bytes; info[8] = w.sp.TC; info[9] = w.sp.levels; info[12] = w.gpx; info[13] = w.x_total; info[14] = w.out_total;
+    info[15] = w.distinct;
+    for (size_t j = 0; j < w.states.size(); ++j) {
+        const FlManyState& st = w.states[j];
+        int64_t* r = info + EGR_FLMANY_HEAD + EGR_FLMANY_REC * ((int64_t)n_clips + (int64_t)j);
+        r[0] = st.clip; r[1] = st.geo.s; r[2] = st.geo.c0; r[3] = st.geo.iDr; r[4] = st.geo.cDr; r[5] = st.geo.G; r[6] = st.D; r[7] = st.nch;
+    }
+    return EGR_OK;
+}
+
+struct egr_flmany {
+    egr_fatllama_plan* base = nullptr;      // the plan of the wave's P, kind and state count: kernels, tables, streams, loop graph
+    FlManyShape shape;
+    std::vector<int64_t> x_off, out_off;    // per channel row, in floats
+    egr::DevBuf d_bhat;                     // [distinct D but the largest][P]: the largest D's spectrum is the base plan's own
+    egr::DevBuf d_tw;                       // the W_(2D) hi / lo tables of every distinct D
+    egr::DevBuf d_rows, d_rag;              // PzRowP per state, FlRagRow per channel row
+    int64_t max_n_in = 0, max_n_out = 0;
+};
+
+extern "C" int egr_flmany_destroy(egr_flmany* w) {
+    if (!w) return EGR_OK;
+    egr_fatllama_plan_destroy(w->base);      // (waits for the device: nothing of the wave is in flight when its buffers go)
+    delete w;
+    return EGR_OK;
+}
+
+extern "C" int egr_flmany_create(egr_flmany** out, int n_clips, const int64_t* n_in, const int* factor, const int64_t* n_out, const int* channels) {
+    EGR_CHECK(out != nullptr, EGR_ERR_ARG, "out is null");
+    *out = nullptr;
+    std::unique_ptr<egr_flmany, int (*)(egr_flmany*)> owner(new egr_flmany(), egr_flmany_destroy);
+    egr_flmany* w = owner.get();
+    FlManyShape& sh = w->shape;
+    EGR_TRY(flmany_shape(n_clips, n_in, factor, n_out, channels, &sh));
+    EGR_CHECK(sh.bad_clip < 0, EGR_ERR_UNSUPPORTED, "egr_flmany_create: clip %d cannot join the wave: %s", sh.bad_clip, kFlManyReason[sh.reason]);
+    const FlSwitches sw = fl_read_switches();
+    const int ns = (int)sh.states.size();
+    const FlManyClip& big = sh.clips[(size_t)sh.big];
+    // the base plan: the largest clip's lengths, one channel per channel row (kind 2: two per state, so that a lone channel keeps its slot)
+    const int c_base = sh.kind == 1 ? ns : 2 * ns;
+    EGR_TRY(build_plan(&w->base, sw, big.N, c_base, 1, sh.sp, big.D, sh.kind, big.N));
+    egr_fatllama_plan* p = w->base;
+    EGR_TRY(pz_rows_prepare(p));
+    const int64_t P = sh.sp.M;
+    // ---- per distinct D: the chirp spectrum (device, double precision, one synchronisation for all) and the W_(2D) tables (one upload) ----
+    std::vector<int64_t> ds;
+    for (const FlManyClip& c : sh.clips) ds.push_back(c.D);
+    std::sort(ds.begin(), ds.end());
+    ds.erase(std::unique(ds.begin(), ds.end()), ds.end());
+    const size_t nd = ds.size();
+    std::vector<double2> tw, part;
+    std::vector<size_t> tw_hi(nd), tw_lo(nd);
+    std::vector<int> tw_sh(nd);
+    for (size_t d = 0; d < nd; ++d) {
+        const int64_t T = 2 * ds[d];
+        int shb = 0;
+        while ((1LL << (2 * shb)) < T) ++shb;          // as fl_make_tw2
+        tw_sh[d] = shb;
+        tw_hi[d] = tw.size();
+        make_twiddles_d(part, (T >> shb) + 1, 1LL << shb, T);
+        tw.insert(tw.end(), part.begin(), part.end());
+        tw_lo[d] = tw.size();
+        make_twiddles_d(part, 1LL << shb, 1, T);
+        tw.insert(tw.end(), part.begin(), part.end());
+    }
+    egr::DevBuf scratch0, scratch1;
+    EGR_CHECK(w->d_tw.alloc(tw.size() * sizeof(double2)) && w->d_rows.alloc((size_t)ns * sizeof(PzRowP)) && w->d_rag.alloc((size_t)sh.rows * sizeof(FlRagRow)) &&
+              (nd < 2 || (w->d_bhat.alloc((nd - 1) * (size_t)P * sizeof(cplx)) && scratch0.alloc((size_t)P * sizeof(double2)) && scratch1.alloc((size_t)P * sizeof(double2)))),
+              EGR_ERR_ALLOC, "egr_flmany_create: hipMalloc of the wave's tables (%zu chirp spectra of %lld points) failed", nd, (long long)P);
+    EGR_HIP(hipMemcpy(w->d_tw.p, tw.data(), tw.size() * sizeof(double2), hipMemcpyHostToDevice));
+    std::vector<const cplx*> bh(nd);
+    for (size_t d = 0; d < nd; ++d) {
+        if (d + 1 == nd) { bh[d] = pz_plan_bhat(p); continue; }          // the largest D: built by pz_build
+        cplx* dst = w->d_bhat.as<cplx>() + d * (size_t)P;
+        bh[d] = dst;
+        EGR_TRY(pz_bhat_enqueue(p, (unsigned long long)ds[d], scratch0.p, scratch1.p, dst));
+    }
+    // ---- the row tables ----
+    std::vector<FlRagRow> rag((size_t)sh.rows);
+    w->x_off.resize((size_t)sh.rows); w->out_off.resize((size_t)sh.rows);
+    int64_t xo = 0, yo = 0;
+    for (const FlManyClip& c : sh.clips) {
+        for (int j = 0; j < c.channels; ++j) {
+            FlRagRow& r = rag[(size_t)(c.row0 + j)];
+            r.x_off = xo; r.y_off = yo; r.n_in = c.n_in; r.n_out = c.N; r.factor = c.factor; r.c_lo = c.row0; r.c_hi = c.row0 + c.channels; r.pad_ = 0;
+            w->x_off[(size_t)(c.row0 + j)] = xo; w->out_off[(size_t)(c.row0 + j)] = yo;
+            xo += c.n_in; yo += c.N + (c.N & 1);
+        }
+        w->max_n_in = std::max(w->max_n_in, c.n_in); w->max_n_out = std::max(w->max_n_out, c.N);
+    }
+    std::vector<PzRowP> rows((size_t)ns);
+    for (int j = 0; j < ns; ++j) {
+        const FlManyState& st = sh.states[(size_t)j];
+        const size_t d = (size_t)(std::lower_bound(ds.begin(), ds.end(), st.D) - ds.begin());
+        PzRowP& r = rows[(size_t)j];
+        r.D = (unsigned long long)st.D; r.inv_2D = 1.0 / (2.0 * (double)st.D); r.inv_D = 1.0 / (double)st.D;
+        r.w.hi = w->d_tw.as<const dcplx>() + tw_hi[d]; r.w.lo = w->d_tw.as<const dcplx>() + tw_lo[d]; r.w.sh = tw_sh[d];
+        r.bhat = bh[d];
+        r.N = sh.clips[(size_t)st.clip].N;
+        r.ya = rag[(size_t)st.row].y_off;
+        r.yb = st.nch == 2 ? rag[(size_t)st.row + 1].y_off : r.ya;
+        r.s = st.geo.s; r.odd = st.geo.odd; r.c0 = st.geo.c0; r.iDr = st.geo.iDr; r.cDr = st.geo.cDr; r.G = st.geo.G; r.g_per_xcd = st.geo.g_per_xcd;
+        r.cha = st.row;
+        r.chb = sh.kind == 1 ? st.row : (st.nch == 2 ? st.row + 1 : -1);
+    }
+    EGR_HIP(hipMemcpy(w->d_rows.p, rows.data(), rows.size() * sizeof(PzRowP), hipMemcpyHostToDevice));
+    EGR_HIP(hipMemcpy(w->d_rag.p, rag.data(), rag.size() * sizeof(FlRagRow), hipMemcpyHostToDevice));
+    const hipError_t se = hipDeviceSynchronize();          // the scratch buffers go when this function returns
+    EGR_CHECK(se == hipSuccess && hipGetLastError() == hipSuccess, EGR_ERR_HIP, "egr_flmany_create: building the chirp spectra failed: %s", hipGetErrorString(se));
+    *out = owner.release();
+    return EGR_OK;
+}
+
+extern "C" int egr_flmany_layout(egr_flmany* w, int64_t* x_off, int64_t* out_off, int64_t totals[2]) {
+    EGR_CHECK(w && x_off && out_off && totals, EGR_ERR_ARG, "egr_flmany_layout: null argument");
+    std::copy(w->x_off.begin(), w->x_off.end(), x_off);
+    std::copy(w->out_off.begin(), w->out_off.end(), out_off);
+    totals[0] = w->shape.x_total; totals[1] = w->shape.out_total;
+    return EGR_OK;
+}
+
+extern "C" int egr_flmany_enhance(egr_flmany* w, const float* x_flat, float* out_flat, int max_iter, float thr, unsigned flags, void* stream) {
+    EGR_CHECK(w && w->base, EGR_ERR_ARG, "egr_flmany_enhance: null wave");
+    EGR_CHECK(max_iter >= 1, EGR_ERR_ARG, "egr_flmany_enhance: max_iter=%d < 1", max_iter);
+    EGR_CHECK(!(flags & (EGR_FL_THR_RECOMPUTE | EGR_FL_DEFER_FINALIZE)), EGR_ERR_UNSUPPORTED,
+              "egr_flmany_enhance: EGR_FL_THR_RECOMPUTE and EGR_FL_DEFER_FINALIZE are not supported on a wave");
+    EGR_CHECK(!w->shape.linspace || (flags & EGR_FL_INTERP_LINSPACE), EGR_ERR_ARG, "a wave with an explicit output length needs EGR_FL_INTERP_LINSPACE");
+    egr_fatllama_plan* p = w->base;
+    FlCall c{p, out_flat, max_iter, thr, flags, (hipStream_t)stream};
+    EGR_TRY(enhance_begin(c, x_flat));          // flag checks; clears the peaks and the ring of maxima (both indexed by channel row)
+    c.rows = w->d_rows.as<const PzRowP>();
+    c.rows_gpx = w->shape.gpx;
+    const FlRagRow* rag = w->d_rag.as<const FlRagRow>();
+    const int rows = w->shape.rows;
+    hipLaunchKernelGGL(k_prepare_rows, dim3(fl_grid(std::max(w->max_n_in, w->max_n_out)), rows), dim3(256), 0, c.st, x_flat, out_flat, rag,
+                       (flags & EGR_FL_PCM_IN) ? 1 : 0, (flags & EGR_FL_ZERO_STUFF) ? 1 : 0, p->peaks(), p->peaks() + 2 * p->C,
+                       (flags & EGR_FL_INTERP_LINSPACE) ? 1 : 0);
+    EGR_TRY(pz_loop(c));
+    if (flags & (EGR_FL_NORMALIZE | EGR_FL_AUTOSCALE | EGR_FL_NODE_POST))
+        hipLaunchKernelGGL(k_finalize_rows, dim3(fl_grid(w->max_n_out), rows), dim3(256), 0, c.st, out_flat, rag, flags, p->peaks(), p->peaks() + p->C);
+    EGR_HIP(hipGetLastError());
+    return EGR_OK;
+}
+
 namespace egr {
 __global__ void k_canary_selftest(int where, int payload_bytes) {
     extern __shared__ __attribute__((aligned(16))) char smem[];

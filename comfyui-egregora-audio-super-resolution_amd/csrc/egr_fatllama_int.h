@@ -242,6 +242,26 @@ struct FlSwitches {
 struct PzPlan;                                                   // egr_fatllama_pz.hip
 struct PzPlanDelete { void operator()(PzPlan* z) const; };
 
+// Where index 0 of a length-D transform sits inside a convolution of nc columns in tiles of TC, and the mirror geometry of its
+// spectrum pass (egr_fatllama_pz.hip): computed by pz_row_geometry for a plan's own D and for every row of a wave.
+struct PzGeo { int s, odd, c0, iDr, cDr, G, g_per_xcd; };
+PzGeo pz_row_geometry(unsigned long long D, int nc, int TC);
+
+// One state of a wave of clips that share a convolution length P but not the transform length D (egr_flmany_*): what the paired
+// chirp-z kernels take from PzP for a plan's single D, per state.  A kernel that is handed a table of these replaces the
+// D-dependent fields of its copy of PzP by rows[blockIdx.y] before anything else.
+struct PzRowP {
+    unsigned long long D;
+    double inv_2D, inv_D;
+    Tw2 w;                      // W_(2D)^r
+    const cplx* bhat;           // FFT_P(b_D) / P in the passes' order
+    long long N;                // real samples per channel
+    long long ya, yb;           // offsets of the state's channel slices in the flat y / out buffer (yb = ya for a lone channel)
+    int s, odd, c0, iDr, cDr, G, g_per_xcd;
+    int cha, chb;               // wave-global channel ids (peaks, relative levels, ring of maxima); kind 1: chb = cha; kind 2 without
+                                // a second channel: chb = -1
+};
+
 // ---- kernel selection of the packed loop ----
 // A pass can run on one of three kernel families with different signatures: the run-time schedule (k_row / k_col), the compile-time
 // schedule (k_row<., 1> / k_col<., 2>) and the two-barrier kernels (k_row_wl / k_col_wl / k_colb_wl).  fl_select_passes
@@ -329,6 +349,8 @@ struct FlCall {
     float thr0;                  // time-domain level of the opening pass: thr, thr * max|y| (relative, thr0_rel) or none (-1: every sample kept)
     const unsigned* thr0_rel;
     unsigned* peak_out;
+    const PzRowP* rows;          // a wave's row table (device), one entry per state of the plan; nullptr: the plan's own D for every state
+    int rows_gpx;                // with rows: the largest g_per_xcd of the table (grid of the spectrum pass)
 };
 }  // namespace egr
 
@@ -418,6 +440,11 @@ static inline int fl_run_pipelines(egr_fatllama_plan* p, hipStream_t st, int ngr
 
 // paired chirp-z (egr_fatllama_pz.hip)
 int pz_build(egr_fatllama_plan* p, int kind, const egr::FlSwitches& sw);
+// a wave's side of a paired chirp-z plan: raises the LDS cap of the row-table kernels; enqueues (default stream, no synchronisation)
+// the double-precision build of FFT_P(b_D) / P into `bhat` through two scratch buffers of P double2 each
+int pz_rows_prepare(egr_fatllama_plan* p);
+const egr::cplx* pz_plan_bhat(const egr_fatllama_plan* p);          // the plan's own chirp spectrum
+int pz_bhat_enqueue(const egr_fatllama_plan* p, unsigned long long D, void* scratch0, void* scratch1, egr::cplx* bhat);
 long long pz_canary_failures();    // -1 without EGR_LDS_CANARY
 bool pz_sched_has(int L, int nc);  // column length L and row length nc both have compile-time schedules (whatever EGR_PZ_SCHED says)
 int pz_loop(const egr::FlCall& c);

@@ -81,6 +81,31 @@ __device__ __forceinline__ dcplx pz_chirp(const PzP& p, unsigned long long k) { 
     return tw2d(p.w, (unsigned)r);
 }
 
+// The channels of state `st` and their slices of the flat y / out buffer.  ROWS (a wave, egr_flmany_*): the state's row replaces the
+// D-dependent fields of the kernel's copy of `p` and names the channels; else they follow from the state id and the plan's one N.
+struct PzCh {
+    int cha, chb;               // chb is only used where hasb
+    bool hasb;                  // kind 1: true (chb = cha); kind 2: the state carries a second channel
+    float *Ya, *Yb;
+};
+template <bool ROWS>
+__device__ __forceinline__ PzCh pz_state(PzP& p, const PzRowP* __restrict__ rows, int st, float* out) {
+    PzCh c;
+    if (ROWS) {
+        const PzRowP r = rows[st];
+        p.D = r.D; p.inv_2D = r.inv_2D; p.inv_D = r.inv_D; p.w = r.w; p.N = r.N;
+        p.s = r.s; p.odd = r.odd; p.c0 = r.c0; p.iDr = r.iDr; p.cDr = r.cDr; p.G = r.G; p.g_per_xcd = r.g_per_xcd;
+        c.cha = r.cha; c.chb = r.chb; c.hasb = r.chb >= 0;
+        c.Ya = out + r.ya; c.Yb = out + r.yb;
+    } else {
+        c.cha = p.kind == 1 ? st : 2 * st; c.chb = p.kind == 1 ? st : 2 * st + 1;
+        c.hasb = c.chb < p.C;
+        c.Ya = out + (size_t)c.cha * p.N;
+        c.Yb = out + (size_t)(c.hasb ? c.chb : c.cha) * p.N;
+    }
+    return c;
+}
+
 // dev ablations (wrong results): EGR_PZ_ABL_NOTW drops the four-step twiddles, _NOFFT the in-LDS transforms, _NOHOOK the pair hook
 // Four-step twiddles of one thread's tile elements.  A thread's elements e = tid + k T (k < NE) sit in ONE column (T is a multiple of
 // the tile width) at rows i0 + k di, so their twiddles W_P^(col (i0 + k di)) are a geometric run: two double table products per
@@ -180,15 +205,18 @@ template <int NCOLS, int R0, int R1, int R2, int R3 = 1> struct PzSched {
 // MODE 1: crop  (twiddle^-1 -> IFFT -> positions outside [s, s + D) zeroed -> FFT -> twiddle)
 // MODE 2: last  (twiddle^-1 -> IFFT -> z = conj(w) c -> out = y + d, per-channel peak)
 // thr_rel (MODE 0, optional): per-channel max|y| as float bits; the level becomes thr * max|y|.
-template <int MODE, class F>
+// rows (ROWS): the wave's table, one entry per state of the launch; out, peak_out and thr_rel are then the wave's whole arrays.
+template <int MODE, class F, bool ROWS = false>
 __global__ __launch_bounds__(F::MAXT, F::MINW1) void k_pzcol(PzP p, float thr, cplx* __restrict__ work, float* __restrict__ out,
-                                                unsigned* __restrict__ peak_out, const unsigned* __restrict__ thr_rel) {
+                                                unsigned* __restrict__ peak_out, const unsigned* __restrict__ thr_rel,
+                                                const PzRowP* __restrict__ rows) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     EGR_LDS_CANARY_ARM(smem);
     __shared__ float red[16];
     const int tile = (blockIdx.x & 7) * p.tiles_per_xcd + (blockIdx.x >> 3);
     if (tile >= p.ntiles) return;
     const int st = blockIdx.y;
+    const PzCh ch = pz_state<ROWS>(p, rows, st, out);
     const int TC = p.TC, lg = p.TClog2, L = p.L, nc = p.nc;
     const int c0 = tile * TC;
     cplx* cur = (cplx*)EGR_LDS_BASE(smem);
@@ -197,10 +225,10 @@ __global__ __launch_bounds__(F::MAXT, F::MINW1) void k_pzcol(PzP p, float thr, c
     const unsigned long long D = p.D;
     const long long s = p.s;
     // channels of this state
-    const int cha = p.kind == 1 ? st : 2 * st, chb = p.kind == 1 ? st : 2 * st + 1;
-    const bool hasb = chb < p.C;
-    float* Ya = out + (size_t)cha * p.N;
-    float* Yb = out + (size_t)(hasb ? chb : cha) * p.N;
+    const int cha = ch.cha, chb = ch.chb;
+    const bool hasb = ch.hasb;
+    float* Ya = ch.Ya;
+    float* Yb = ch.Yb;
     // this thread's column and its twiddle run (the workgroup size is a multiple of TC, at most 8 elements per thread)
     const int tcol = c0 + ((int)threadIdx.x & (TC - 1));
     PzTwRun<F::NE1> twr;
@@ -306,8 +334,9 @@ template <int LA, int LB> struct PzColWl {
     static constexpr int LBP = LB | 1;
     static constexpr int LDS = LA * LBP * TC * 8;
 };
-template <int LA, int LB>
-__global__ __launch_bounds__((PzColWl<LA, LB>::THREADS)) void k_pzcol_wl(PzP p, const cplx* __restrict__ tab, int ntiles, int tiles_per_xcd, cplx* __restrict__ work) {
+template <int LA, int LB, bool ROWS = false>
+__global__ __launch_bounds__((PzColWl<LA, LB>::THREADS)) void k_pzcol_wl(PzP p, const cplx* __restrict__ tab, int ntiles, int tiles_per_xcd, cplx* __restrict__ work,
+                                                                         const PzRowP* __restrict__ rows) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     EGR_LDS_CANARY_ARM(smem);
     using G = PzColWl<LA, LB>;
@@ -316,6 +345,7 @@ __global__ __launch_bounds__((PzColWl<LA, LB>::THREADS)) void k_pzcol_wl(PzP p, 
     const int tile = (blockIdx.x & 7) * tiles_per_xcd + (blockIdx.x >> 3);
     if (tile >= ntiles) return;
     const int st = blockIdx.y;
+    if (ROWS) pz_state<true>(p, rows, st, nullptr);
     const int nc = p.nc;
     cplx* lds = (cplx*)EGR_LDS_BASE(smem);
     const int tid = threadIdx.x;
@@ -374,32 +404,31 @@ __global__ __launch_bounds__((PzColWl<LA, LB>::THREADS)) void k_pzcol_wl(PzP p, 
         }
     }
 }
-typedef void (*PzColWlFn)(PzP, const cplx*, int, int, cplx*);
-struct PzColWlEntry { int L, la, lb, threads, lds; PzColWlFn fn; };
+typedef void (*PzColWlFn)(PzP, const cplx*, int, int, cplx*, const PzRowP*);
+struct PzColWlEntry { int L, la, lb, threads, lds; PzColWlFn fn, fn_rows; };
 #define PZ_COLWL_LIST(X) X(512, 16, 32) X(560, 20, 28) X(600, 24, 25) X(640, 20, 32) X(672, 24, 28) X(720, 24, 30) X(768, 24, 32) X(800, 25, 32) \
     X(840, 28, 30) X(900, 30, 30) X(960, 30, 32) X(1024, 32, 32)
-#define PZ_COLWL_ENTRY(LEN, A, B) {LEN, A, B, PzColWl<A, B>::THREADS, PzColWl<A, B>::LDS, k_pzcol_wl<A, B>},
+#define PZ_COLWL_ENTRY(LEN, A, B) {LEN, A, B, PzColWl<A, B>::THREADS, PzColWl<A, B>::LDS, k_pzcol_wl<A, B>, k_pzcol_wl<A, B, true>},
 static const PzColWlEntry kPzColWl[] = {PZ_COLWL_LIST(PZ_COLWL_ENTRY)};
 
 // Carried maximum of the relative threshold (PzHook::max2_next): per-wave maxima to LDS in front of a barrier the kernel has anyway,
 // ONE commit per workgroup and channel behind it; workgroup g = 0 of a state clears the ring slot two iterations ahead.
 // the carried maxima of this state's channel(s), requested at the kernel's top (an L2 miss -- the slots were written by memory-side atomics --
 // that the inverse transform in front of the hook covers)
-__device__ __forceinline__ void pz_max_prefetch(const PzP& p, const PzHook& h, int st, float& m2a, float& m2b) {
+__device__ __forceinline__ void pz_max_prefetch(const PzP& p, const PzHook& h, const PzCh& ch, float& m2a, float& m2b) {
     m2a = m2b = 0.f;
     if (!h.max2) return;
-    const int cha = p.kind == 1 ? st : 2 * st, chb = p.kind == 1 ? st : 2 * st + 1;
-    m2a = fl_max2_read(h.max2, cha);
-    m2b = p.kind == 1 ? m2a : fl_max2_read(h.max2, chb < p.C ? chb : cha);
+    m2a = fl_max2_read(h.max2, ch.cha);
+    m2b = p.kind == 1 ? m2a : fl_max2_read(h.max2, ch.hasb ? ch.chb : ch.cha);
 }
 __device__ __forceinline__ void pz_max_stage(const PzHook& h, float mxa, float mxb, float* red) {
     if (!h.max2_next) return;
     mxa = wave_max(mxa); mxb = wave_max(mxb);
     if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6] = mxa; red[16 + (threadIdx.x >> 6)] = mxb; }
 }
-__device__ __forceinline__ void pz_max_commit(const PzP& p, const PzHook& h, int st, int g, const float* red) {
-    const int cha = p.kind == 1 ? st : 2 * st, chb = p.kind == 1 ? st : 2 * st + 1;
-    const bool hasb = p.kind == 2 && chb < p.C;
+__device__ __forceinline__ void pz_max_commit(const PzP& p, const PzHook& h, const PzCh& ch, int g, const float* red) {
+    const int cha = ch.cha, chb = ch.chb;
+    const bool hasb = p.kind == 2 && ch.hasb;
     if (h.max2_zero && g == 0 && threadIdx.x < EGR_FL_MAX_SUB) {
         fl_max2_clear(h.max2_zero, cha, threadIdx.x);
         if (hasb) fl_max2_clear(h.max2_zero, chb, threadIdx.x);
@@ -532,19 +561,23 @@ __device__ __forceinline__ void pz_pair_hook(const PzP& p, const PzHook& h, AT a
 // Spectrum pass on a tile pair: right tile = columns rs .. rs + TC - 1, left tile = their mirror images (cDr - c) mod nc in
 // ascending order.  LDS holds both tiles interleaved: element i of right column t at i * 2TC + t, of left column t at
 // i * 2TC + TC + t.  MAXONLY: no write-back; max |X|^2 per channel -> h.max2_out (the relative threshold's reduction).
-template <bool MAXONLY, class F>
-__global__ __launch_bounds__(F::MAXT, F::MINW2) void k_pzpair(PzP p, PzHook h, cplx* __restrict__ work) {
+// ROWS: the grid is the wave's largest g_per_xcd; a row with fewer tile pairs per XCD leaves the surplus workgroups idle (their g would
+// alias another XCD's pairs, which `g >= G` does not catch).
+template <bool MAXONLY, class F, bool ROWS = false>
+__global__ __launch_bounds__(F::MAXT, F::MINW2) void k_pzpair(PzP p, PzHook h, cplx* __restrict__ work, const PzRowP* __restrict__ rows) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     EGR_LDS_CANARY_ARM(smem);
     __shared__ float red[32];
+    const int st = blockIdx.y;
+    const PzCh ch = pz_state<ROWS>(p, rows, st, nullptr);
+    if (ROWS && (int)(blockIdx.x >> 3) >= p.g_per_xcd) return;
     const int g = (blockIdx.x & 7) * p.g_per_xcd + (blockIdx.x >> 3);
     if (g >= p.G) return;
-    const int st = blockIdx.y;
     const int TC = p.TC, lg = p.TClog2, L = p.L, nc = p.nc, TC2 = 2 * TC;
     cplx* cur = (cplx*)EGR_LDS_BASE(smem);
     cplx* W = work + (size_t)st * p.P;
     float m2a, m2b;
-    pz_max_prefetch(p, h, st, m2a, m2b);
+    pz_max_prefetch(p, h, ch, m2a, m2b);
     const unsigned long long D = p.D;
     const long long s = p.s;
     const int rs = (p.c0 + g * TC) % nc;
@@ -579,8 +612,8 @@ __global__ __launch_bounds__(F::MAXT, F::MINW2) void k_pzpair(PzP p, PzHook h, c
     F::run(cur, p, TC2, lg + 1, true);
 
     // ---- pair hook (pz_pair_hook) ----
-    const int cha = p.kind == 1 ? st : 2 * st, chb = p.kind == 1 ? st : 2 * st + 1;
-    const bool hasb = chb < p.C;
+    const int cha = ch.cha, chb = ch.chb;
+    const bool hasb = ch.hasb;
     float mxa = 0.f, mxb = 0.f;
     const int nel = L * TC;
     pz_pair_hook<MAXONLY>(p, h, [&](int i, int slot) { return cur + (size_t)i * TC2 + slot; }, st, rs, rmask, selfmask, mxa, mxb, m2a, m2b);
@@ -604,7 +637,7 @@ __global__ __launch_bounds__(F::MAXT, F::MINW2) void k_pzpair(PzP p, PzHook h, c
     }
     pz_max_stage(h, mxa, mxb, red);
     __syncthreads();
-    pz_max_commit(p, h, st, g, red);
+    pz_max_commit(p, h, ch, g, red);
     F::run(cur, p, TC2, lg + 1, false);
 #pragma unroll
     for (int k = 0; k < F::NE2; ++k) {
@@ -619,24 +652,27 @@ __global__ __launch_bounds__(F::MAXT, F::MINW2) void k_pzpair(PzP p, PzHook h, c
 // rows n = c + LA d of its column; it parks them in ITS OWN LDS row (element i of column slot q at ((i % LA) LBP + i / LA) 8 + q),
 // the pair hook runs on that layout (pz_pair_hook), the thread takes its rows back (cropping the left tile), and the forward
 // transform proceeds as in k_pzcol_wl.  One 48 KB buffer, no write-after-read hazard between threads at any point.
-template <int LA, int LB>
-__global__ __launch_bounds__((PzColWl<LA, LB>::THREADS)) void k_pzpair_wl(PzP p, PzHook h, const cplx* __restrict__ tab, cplx* __restrict__ work) {
+template <int LA, int LB, bool ROWS = false>
+__global__ __launch_bounds__((PzColWl<LA, LB>::THREADS)) void k_pzpair_wl(PzP p, PzHook h, const cplx* __restrict__ tab, cplx* __restrict__ work,
+                                                                          const PzRowP* __restrict__ rows) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     EGR_LDS_CANARY_ARM(smem);
     using G = PzColWl<LA, LB>;
     constexpr int TC = 4, TC2 = 8, LBP = G::LBP, L = LA * LB;
     __shared__ cplx ts[L];
     __shared__ float red[32];
+    const int st = blockIdx.y;
+    const PzCh ch = pz_state<ROWS>(p, rows, st, nullptr);
+    if (ROWS && (int)(blockIdx.x >> 3) >= p.g_per_xcd) return;
     const int g = (blockIdx.x & 7) * p.g_per_xcd + (blockIdx.x >> 3);
     if (g >= p.G) return;
-    const int st = blockIdx.y;
     const int nc = p.nc;
     cplx* lds = (cplx*)EGR_LDS_BASE(smem);
     const int tid = threadIdx.x;
     const int b = tid >> 3, cl = tid & 7;
     for (int e = tid; e < L; e += G::THREADS) ts[e] = tab[e];
     float m2a, m2b;
-    pz_max_prefetch(p, h, st, m2a, m2b);
+    pz_max_prefetch(p, h, ch, m2a, m2b);
     const unsigned long long D = p.D;
     const long long s = p.s;
     const int rs = (p.c0 + g * TC) % nc;
@@ -693,7 +729,7 @@ __global__ __launch_bounds__((PzColWl<LA, LB>::THREADS)) void k_pzpair_wl(PzP p,
     pz_pair_hook<false>(p, h, [&](int i, int slot) { const int q = i / LA; return lds + ((i - q * LA) * LBP + q) * TC2 + slot; }, st, rs, rmask, selfmask, mxa, mxb, m2a, m2b);
     pz_max_stage(h, mxa, mxb, red);
     __syncthreads();
-    pz_max_commit(p, h, st, g, red);
+    pz_max_commit(p, h, ch, g, red);
     if (b < LA) {
         const int c = b;
 #pragma unroll
@@ -721,21 +757,22 @@ __global__ __launch_bounds__((PzColWl<LA, LB>::THREADS)) void k_pzpair_wl(PzP p,
         }
     }
 }
-typedef void (*PzPairWlFn)(PzP, PzHook, const cplx*, cplx*);
-struct PzPairWlEntry { int L; PzPairWlFn fn; };
-#define PZ_PAIRWL_ENTRY(LEN, A, B) {LEN, k_pzpair_wl<A, B>},
+typedef void (*PzPairWlFn)(PzP, PzHook, const cplx*, cplx*, const PzRowP*);
+struct PzPairWlEntry { int L; PzPairWlFn fn, fn_rows; };
+#define PZ_PAIRWL_ENTRY(LEN, A, B) {LEN, k_pzpair_wl<A, B>, k_pzpair_wl<A, B, true>},
 static const PzPairWlEntry kPzPairWl[] = {PZ_COLWL_LIST(PZ_PAIRWL_ENTRY)};
 
 // One row of length L per workgroup: FFT . x bhat (CONJ: x conj(bhat)) . IFFT, stages in place.  The row's bhat entries are
 // requested before the forward transform (registers), so their latency is off the dependent chain.
-template <bool CONJ>
+// ROWS: the chirp spectrum is the state's own (rows[blockIdx.y].bhat), `bhat` is unused.
+template <bool CONJ, bool ROWS = false>
 __global__ __launch_bounds__(512) void k_pz_rowconv(FftDesc f, int L, const cplx* __restrict__ tw, const cplx* __restrict__ bhat,
-                                                     long long P, cplx* __restrict__ work) {
+                                                     long long P, cplx* __restrict__ work, const PzRowP* __restrict__ rows) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     EGR_LDS_CANARY_ARM(smem);
     cplx* cur = (cplx*)EGR_LDS_BASE(smem);
     cplx* g = work + (size_t)blockIdx.y * P + (size_t)blockIdx.x * L;
-    const cplx* bh = bhat + (size_t)blockIdx.x * L;
+    const cplx* bh = (ROWS ? rows[blockIdx.y].bhat : bhat) + (size_t)blockIdx.x * L;
     if ((L & 1) == 0) {
         float4 b[4];
 #pragma unroll
@@ -783,16 +820,16 @@ __global__ __launch_bounds__(512) void k_pz_rowconv(FftDesc f, int L, const cplx
 #ifndef EGR_PZ_ROW_PAD
 #define EGR_PZ_ROW_PAD 4
 #endif
-template <bool CONJ, int NC, int R0, int R1, int R2, int R3>
+template <bool CONJ, int NC, int R0, int R1, int R2, int R3, bool ROWS = false>
 __global__ __launch_bounds__(NC / 16) void k_pz_rowconv_s(const cplx* __restrict__ stw, const cplx* __restrict__ bhat, long long P,
-                                                          cplx* __restrict__ work) {
+                                                          cplx* __restrict__ work, const PzRowP* __restrict__ rows) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     EGR_LDS_CANARY_ARM(smem);
     constexpr int L = NC, T = NC / 16, PSH = EGR_PZ_ROW_PAD;
     static_assert(R0 * R1 * R2 * R3 == NC, "schedule does not match the row length");
     cplx* cur = (cplx*)EGR_LDS_BASE(smem);
     cplx* g = work + (size_t)blockIdx.y * P + (size_t)blockIdx.x * L;
-    const cplx* bh = bhat + (size_t)blockIdx.x * L;
+    const cplx* bh = (ROWS ? rows[blockIdx.y].bhat : bhat) + (size_t)blockIdx.x * L;
     float4 b[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) b[j] = *(const float4*)(bh + 2 * (int)threadIdx.x + j * 2 * T);
@@ -836,16 +873,16 @@ __global__ __launch_bounds__(NC / 16) void k_pz_rowconv_s(const cplx* __restrict
 // of ITS last-stage butterflies of the inverse (stored straight to global memory).  Only the middle stage of each transform runs
 // in place in LDS.  8 LDS passes per element instead of 16, 7 barriers instead of 13; same butterflies, tables and arithmetic per
 // element as k_pz_rowconv_s (results agree to round-off; the order of the twiddle products is the same).
-template <bool CONJ, int NC, int R1, int R2>
+template <bool CONJ, int NC, int R1, int R2, bool ROWS = false>
 __global__ __launch_bounds__(NC / 16) void k_pz_rowconv_f(const cplx* __restrict__ stw, const cplx* __restrict__ bhat, long long P,
-                                                          cplx* __restrict__ work) {
+                                                          cplx* __restrict__ work, const PzRowP* __restrict__ rows) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     EGR_LDS_CANARY_ARM(smem);
     constexpr int L = NC, T = NC / 16, PSH = EGR_PZ_ROW_PAD, NB2 = 16 / R2, NS2 = 16 * R1, RS2 = sched_row_stride(R2);
     static_assert(16 * R1 * R2 == NC && NS2 == NC / R2, "three-stage schedule 16 R1 R2");
     cplx* cur = (cplx*)EGR_LDS_BASE(smem);
     cplx* g = work + (size_t)blockIdx.y * P + (size_t)blockIdx.x * L;
-    const cplx* bh = bhat + (size_t)blockIdx.x * L;
+    const cplx* bh = (ROWS ? rows[blockIdx.y].bhat : bhat) + (size_t)blockIdx.x * L;
     const cplx* stw2 = stw + 16 * sched_row_stride(R1);          // table of the last stage (lds_fft_sched_inplace's layout)
     const int tid = threadIdx.x;
     cplx v[16], bq[16];
@@ -987,24 +1024,31 @@ __global__ __launch_bounds__(256) void k_pz_bhat_store(const double2* __restrict
     }
 }
 
-typedef void (*PzPairFn)(PzP, PzHook, cplx*);
-typedef void (*PzColFn)(PzP, float, cplx*, float*, unsigned*, const unsigned*);
-typedef void (*PzRowFn)(const cplx*, const cplx*, long long, cplx*);
+typedef void (*PzPairFn)(PzP, PzHook, cplx*, const PzRowP*);
+typedef void (*PzColFn)(PzP, float, cplx*, float*, unsigned*, const unsigned*, const PzRowP*);
+typedef void (*PzRowFn)(const cplx*, const cplx*, long long, cplx*, const PzRowP*);
+typedef void (*PzRowRtFn)(FftDesc, int, const cplx*, const cplx*, long long, cplx*, const PzRowP*);
+
+// the kernels of one plan; a plan holds the set for its own D (ROWS = false) and the set that takes a wave's row table
+struct PzKernels {
+    PzPairFn pair = nullptr, pairmax = nullptr;   // the spectrum pass and its reduction-only form
+    PzColFn crop = nullptr, first = nullptr, last = nullptr;      // the crop pass, the opening / closing passes
+    PzRowFn rowconv = nullptr, rowconv_conj = nullptr;            // compile-time row schedule (nullptr: rowconv_rt)
+    PzRowRtFn rowconv_rt = nullptr, rowconv_rt_conj = nullptr;
+    PzColWlFn crop_wl = nullptr;                  // the two-barrier crop pass (nullptr: crop)
+    PzPairWlFn pair_wl = nullptr;                 // the four-barrier spectrum pass (nullptr: pair)
+};
 
 struct PzPlan {
     PzP p{};
     DevBuf d_bhat;
     int nstates = 0;
-    // kernels of this plan: the spectrum pass (and its reduction-only form), the crop pass, the opening / closing passes
-    PzPairFn pair = nullptr, pairmax = nullptr;
-    PzColFn crop = nullptr, first = nullptr, last = nullptr;
+    PzKernels k, kr;                              // kr: the same choice among the kernels that take a row table
     int threads_pair = 0, threads_pairmax = 0, threads_crop = 0, threads_col = 0;
     int col_sched = 0;                            // column length with a compile-time schedule (0: run-time schedule)
     const cplx* stw_row = nullptr;                // stage tables of the compile-time row schedule (nullptr: run-time schedule)
-    PzRowFn rowconv = nullptr, rowconv_conj = nullptr;
     int threads_row = 512;
-    const PzColWlEntry* crop_wl = nullptr;        // the two-barrier crop pass (nullptr: k_pzcol<1>)
-    PzPairWlFn pair_wl = nullptr;                 // the four-barrier spectrum pass (nullptr: k_pzpair)
+    const PzColWlEntry* crop_wl = nullptr;        // geometry of the two-barrier crop pass (nullptr: k_pzcol<1>)
     const cplx* crop_wl_tab = nullptr;            // [LB][LA]: W_L^(b c)
     size_t lds_col = 0, lds_pair = 0, lds_row = 0;
 };
@@ -1022,17 +1066,19 @@ void PzPlanDelete::operator()(PzPlan* z) const { delete z; }
 
 struct PzSchedEntry {
     int L, r0, r1, r2;
-    PzPairFn pair;
-    PzColFn crop;
+    PzPairFn pair, pair_rows;
+    PzColFn crop, crop_rows;
     int threads_pair, threads_crop;
 };
-#define PZ_ENTRY(LEN, A, B, C) {LEN, A, B, C, k_pzpair<false, PzSched<8, A, B, C>>, k_pzcol<1, PzSched<4, A, B, C>>, PzSched<8, A, B, C>::THREADS, PzSched<4, A, B, C>::THREADS},
+#define PZ_ENTRY(LEN, A, B, C) {LEN, A, B, C, k_pzpair<false, PzSched<8, A, B, C>>, k_pzpair<false, PzSched<8, A, B, C>, true>, \
+    k_pzcol<1, PzSched<4, A, B, C>>, k_pzcol<1, PzSched<4, A, B, C>, true>, PzSched<8, A, B, C>::THREADS, PzSched<4, A, B, C>::THREADS},
 static const PzSchedEntry kPzSched[] = {PZ_SCHED_LIST(PZ_ENTRY)};
 struct PzRowEntry {
     int NC, r0, r1, r2, r3;
-    PzRowFn fn, fn_conj;
+    PzRowFn fn, fn_conj, fn_rows, fn_conj_rows;
 };
-#define PZ_ROW_ENTRY(NC, A, B, C, D) {NC, A, B, C, D, k_pz_rowconv_s<false, NC, A, B, C, D>, k_pz_rowconv_s<true, NC, A, B, C, D>},
+#define PZ_ROW_ENTRY(NC, A, B, C, D) {NC, A, B, C, D, k_pz_rowconv_s<false, NC, A, B, C, D>, k_pz_rowconv_s<true, NC, A, B, C, D>, \
+    k_pz_rowconv_s<false, NC, A, B, C, D, true>, k_pz_rowconv_s<true, NC, A, B, C, D, true>},
 static const PzRowEntry kPzRows[] = {PZ_ROW_LIST(PZ_ROW_ENTRY)};
 
 }  // namespace egr
@@ -1049,6 +1095,48 @@ bool pz_sched_has(int L, int nc) {
 static int pick_threads(int elements) {          // in-place stages hold up to 8 elements per thread; whole multiples of 256
     int t = ((elements + 7) / 8 + 255) / 256 * 256;
     return t < 256 ? 256 : (t > 1024 ? 1024 : t);
+}
+
+PzGeo egr::pz_row_geometry(unsigned long long D, int nc, int TC) {
+    PzGeo g;
+    g.odd = (int)(D & 1ULL);
+    const int m = 2 * TC, dm = (int)(D % (unsigned long long)m);
+    // D odd: Dr = D + 2 s = -1 (mod 2 TC) -> both tiles of a pair are whole aligned tiles; D even: Dr = 0 (mod 2 TC)
+    g.s = g.odd ? ((m - 1 - dm) % m + m) % m / 2 : ((m - dm) % m) / 2;
+    const unsigned long long Dr = D + 2ULL * (unsigned long long)g.s;
+    g.iDr = (int)(Dr / (unsigned long long)nc);
+    g.cDr = (int)(Dr % (unsigned long long)nc);
+    g.c0 = g.odd ? (g.cDr + 1) / 2 : g.cDr / 2;
+    g.G = nc / (2 * TC) + (g.odd ? 0 : 1);
+    g.g_per_xcd = ceil_div(g.G, 8);
+    return g;
+}
+
+// FFT_P(b_D) / P in double precision, stored in the passes' order: launches on the default stream, no synchronisation
+static int pz_bhat_launch(unsigned long long D, long long P, const RowP& r, double2* b0, double2* b1, cplx* bhat) {
+    const int nb = (int)std::min<long long>((P + 255) / 256, 8192);
+    hipLaunchKernelGGL(k_pz_chirp_b, dim3(nb), dim3(256), 0, 0, D, 1.0 / (2.0 * (double)D), P, b0);
+    {
+        long long rem = P, Ns = 1;
+        auto stage = [&](int R) {
+            hipLaunchKernelGGL(k_pz_dfft_stage, dim3((int)std::min<long long>((P / R + 255) / 256, 8192)), dim3(256), 0, 0, (const double2*)b0, b1, P, R, Ns);
+            std::swap(b0, b1);
+            Ns *= R; rem /= R;
+        };
+        while (rem % 16 == 0) stage(16);
+        while (rem % 8 == 0) stage(8);
+        while (rem % 4 == 0) stage(4);
+        while (rem % 2 == 0) stage(2);
+        while (rem % 9 == 0) stage(9);
+        for (int pr : {3, 5, 7, 11, 13}) while (rem % pr == 0) stage(pr);
+        EGR_CHECK(rem == 1, EGR_ERR_UNSUPPORTED, "convolution length %lld has a prime factor above 13", P);
+    }
+    hipLaunchKernelGGL(k_pz_bhat_store, dim3(nb), dim3(256), 0, 0, (const double2*)b0, P, r.L, r.Ma, r.Mb, 1.0 / (double)P, bhat);
+    return EGR_OK;
+}
+const cplx* pz_plan_bhat(const egr_fatllama_plan* plan) { return plan->pz->d_bhat.as<const cplx>(); }
+int pz_bhat_enqueue(const egr_fatllama_plan* plan, unsigned long long D, void* scratch0, void* scratch1, cplx* bhat) {
+    return pz_bhat_launch(D, plan->pz->p.P, plan->row, (double2*)scratch0, (double2*)scratch1, bhat);
 }
 
 int pz_build(egr_fatllama_plan* plan, int kind, const FlSwitches& sw) {
@@ -1070,15 +1158,8 @@ int pz_build(egr_fatllama_plan* plan, int kind, const FlSwitches& sw) {
     EGR_CHECK(q.nc % (2 * q.TC) == 0, EGR_ERR_UNSUPPORTED, "paired chirp-z needs columns %% (2 TC) == 0 (nc=%d TC=%d)", q.nc, q.TC);
     EGR_CHECK(q.P >= 2 * (long long)q.D - 1, EGR_ERR_UNSUPPORTED, "convolution length %lld too short for D=%llu", q.P, q.D);
     {
-        const int m = 2 * q.TC, dm = (int)(q.D % (unsigned long long)m);
-        // D odd: Dr = D + 2 s = -1 (mod 2 TC) -> both tiles of a pair are whole aligned tiles; D even: Dr = 0 (mod 2 TC)
-        q.s = q.odd ? ((m - 1 - dm) % m + m) % m / 2 : ((m - dm) % m) / 2;
-        const unsigned long long Dr = q.D + 2ULL * (unsigned long long)q.s;
-        q.iDr = (int)(Dr / (unsigned long long)q.nc);
-        q.cDr = (int)(Dr % (unsigned long long)q.nc);
-        q.c0 = q.odd ? (q.cDr + 1) / 2 : q.cDr / 2;
-        q.G = q.nc / (2 * q.TC) + (q.odd ? 0 : 1);
-        q.g_per_xcd = ceil_div(q.G, 8);
+        const PzGeo g = pz_row_geometry(q.D, q.nc, q.TC);
+        q.s = g.s; q.iDr = g.iDr; q.cDr = g.cDr; q.c0 = g.c0; q.G = g.G; q.g_per_xcd = g.g_per_xcd;
     }
     z->nstates = kind == 1 ? plan->C : (plan->C + 1) / 2;
     int rc;
@@ -1088,15 +1169,22 @@ int pz_build(egr_fatllama_plan* plan, int kind, const FlSwitches& sw) {
     const bool fuse = 2 * q.L * q.TC <= 8 * 1024;
     z->threads_col = z->threads_crop = pick_threads(q.L * q.TC);
     z->threads_pair = z->threads_pairmax = fuse ? pick_threads(2 * q.L * q.TC) : pick_threads(q.L * q.TC);
-    z->first = k_pzcol<0, PzRt<true>>; z->crop = k_pzcol<1, PzRt<true>>; z->last = k_pzcol<2, PzRt<true>>;
-    z->pair = fuse ? k_pzpair<false, PzRt<true>> : k_pzpair<false, PzRt<false>>;
-    z->pairmax = fuse ? k_pzpair<true, PzRt<true>> : k_pzpair<true, PzRt<false>>;
+    PzKernels &k = z->k, &kr = z->kr;
+    k.first = k_pzcol<0, PzRt<true>>; k.crop = k_pzcol<1, PzRt<true>>; k.last = k_pzcol<2, PzRt<true>>;
+    k.pair = fuse ? k_pzpair<false, PzRt<true>> : k_pzpair<false, PzRt<false>>;
+    k.pairmax = fuse ? k_pzpair<true, PzRt<true>> : k_pzpair<true, PzRt<false>>;
+    k.rowconv_rt = k_pz_rowconv<false>; k.rowconv_rt_conj = k_pz_rowconv<true>;
+    kr.first = k_pzcol<0, PzRt<true>, true>; kr.crop = k_pzcol<1, PzRt<true>, true>; kr.last = k_pzcol<2, PzRt<true>, true>;
+    kr.pair = fuse ? k_pzpair<false, PzRt<true>, true> : k_pzpair<false, PzRt<false>, true>;
+    kr.pairmax = fuse ? k_pzpair<true, PzRt<true>, true> : k_pzpair<true, PzRt<false>, true>;
+    kr.rowconv_rt = k_pz_rowconv<false, true>; kr.rowconv_rt_conj = k_pz_rowconv<true, true>;
     // compile-time schedules where the plan's lengths have one
     if (sw.pz_sched && q.TC == 4)
         for (const PzSchedEntry& e : kPzSched)
             if (e.L == q.L) {
                 if ((rc = fl_upload_sched_tables(plan, {e.r0, e.r1, e.r2}, &q.stw))) return rc;
-                z->pair = e.pair; z->crop = e.crop;
+                k.pair = e.pair; k.crop = e.crop;
+                kr.pair = e.pair_rows; kr.crop = e.crop_rows;
                 z->threads_pair = e.threads_pair; z->threads_crop = e.threads_crop;
                 z->col_sched = e.L;
             }
@@ -1113,9 +1201,10 @@ int pz_build(egr_fatllama_plan* plan, int kind, const FlSwitches& sw) {
                     }
                 if ((rc = fl_upload(plan, t, &z->crop_wl_tab))) return rc;
                 z->crop_wl = &e;
+                k.crop_wl = e.fn; kr.crop_wl = e.fn_rows;
                 // the spectrum pass too, for even/odd packing (kind 1); channel pairs (kind 2, rows of 8192) measure 2 % slower with it
                 if (q.TC == 4 && kind == 1 && sw.pz_pairwl)
-                    for (const PzPairWlEntry& pe : kPzPairWl) if (pe.L == q.L) z->pair_wl = pe.fn;
+                    for (const PzPairWlEntry& pe : kPzPairWl) if (pe.L == q.L) { k.pair_wl = pe.fn; kr.pair_wl = pe.fn_rows; }
             }
     if (sw.pz_sched)
         for (const PzRowEntry& e : kPzRows)
@@ -1123,15 +1212,19 @@ int pz_build(egr_fatllama_plan* plan, int kind, const FlSwitches& sw) {
                 if (e.r3 > 1) rc = fl_upload_sched_tables(plan, {e.r0, e.r1, e.r2, e.r3}, &z->stw_row);
                 else rc = fl_upload_sched_tables(plan, {e.r0, e.r1, e.r2}, &z->stw_row);
                 if (rc) return rc;
-                z->rowconv = e.fn; z->rowconv_conj = e.fn_conj;
+                k.rowconv = e.fn; k.rowconv_conj = e.fn_conj;
+                kr.rowconv = e.fn_rows; kr.rowconv_conj = e.fn_conj_rows;
                 z->threads_row = e.NC / 16;
             }
     // three-stage rows (1024 / 2048 / 4096 points): the kernel with the outer stages fused into the memory accesses (EGR_PZ_ROWF=0:
     // k_pz_rowconv_s); same tables, same LDS footprint
-    if (z->rowconv && sw.pz_rowf) {
-        if (r.L == 4096) { z->rowconv = k_pz_rowconv_f<false, 4096, 16, 16>; z->rowconv_conj = k_pz_rowconv_f<true, 4096, 16, 16>; }
-        else if (r.L == 2048) { z->rowconv = k_pz_rowconv_f<false, 2048, 16, 8>; z->rowconv_conj = k_pz_rowconv_f<true, 2048, 16, 8>; }
-        else if (r.L == 1024) { z->rowconv = k_pz_rowconv_f<false, 1024, 8, 8>; z->rowconv_conj = k_pz_rowconv_f<true, 1024, 8, 8>; }
+    if (k.rowconv && sw.pz_rowf) {
+#define PZ_ROWF(NC, A, B) { k.rowconv = k_pz_rowconv_f<false, NC, A, B>; k.rowconv_conj = k_pz_rowconv_f<true, NC, A, B>; \
+                            kr.rowconv = k_pz_rowconv_f<false, NC, A, B, true>; kr.rowconv_conj = k_pz_rowconv_f<true, NC, A, B, true>; }
+        if (r.L == 4096) PZ_ROWF(4096, 16, 16)
+        else if (r.L == 2048) PZ_ROWF(2048, 16, 8)
+        else if (r.L == 1024) PZ_ROWF(1024, 8, 8)
+#undef PZ_ROWF
     }
     z->lds_col = EGR_LDS((size_t)q.L * q.TC * sizeof(cplx));
     z->lds_pair = EGR_LDS(2 * (size_t)q.L * q.TC * sizeof(cplx));
@@ -1140,10 +1233,10 @@ int pz_build(egr_fatllama_plan* plan, int kind, const FlSwitches& sw) {
     EGR_CHECK(z->lds_pair <= (size_t)EGR_LDS_MAX && z->lds_row <= (size_t)EGR_LDS_MAX, EGR_ERR_UNSUPPORTED, "plan needs %zu / %zu bytes of LDS", z->lds_pair, z->lds_row);
     // the attribute is a process-wide cap per kernel: always the CU's maximum (see build_plan)
     auto attr = [&](const void* fn, size_t) { if (e == hipSuccess) e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, EGR_LDS_MAX); };
-    attr((const void*)z->first, z->lds_col); attr((const void*)z->crop, z->lds_col); attr((const void*)z->last, z->lds_col);
-    attr((const void*)z->pair, z->lds_pair); attr((const void*)z->pairmax, z->lds_pair);
-    if (z->rowconv) { attr((const void*)z->rowconv, z->lds_row); attr((const void*)z->rowconv_conj, z->lds_row); }
-    else { attr((const void*)k_pz_rowconv<false>, z->lds_row); attr((const void*)k_pz_rowconv<true>, z->lds_row); }
+    attr((const void*)k.first, z->lds_col); attr((const void*)k.crop, z->lds_col); attr((const void*)k.last, z->lds_col);
+    attr((const void*)k.pair, z->lds_pair); attr((const void*)k.pairmax, z->lds_pair);
+    if (k.rowconv) { attr((const void*)k.rowconv, z->lds_row); attr((const void*)k.rowconv_conj, z->lds_row); }
+    else { attr((const void*)k.rowconv_rt, z->lds_row); attr((const void*)k.rowconv_rt_conj, z->lds_row); }
     if (e != hipSuccess) {
         set_error("hipFuncSetAttribute(MaxDynamicSharedMemorySize) -> %s", hipGetErrorString(e));
         return EGR_ERR_HIP;
@@ -1153,29 +1246,26 @@ int pz_build(egr_fatllama_plan* plan, int kind, const FlSwitches& sw) {
     DevBuf buf0, buf1;          // ping-pong of the stages: freed when this function returns, behind the synchronisation below (or hipFree's own)
     EGR_CHECK(buf0.alloc((size_t)P * sizeof(double2)) && buf1.alloc((size_t)P * sizeof(double2)) && z->d_bhat.alloc((size_t)P * sizeof(cplx)), EGR_ERR_ALLOC,
               "hipMalloc of the %lld-point chirp spectrum failed", P);
-    double2 *b0 = buf0.as<double2>(), *b1 = buf1.as<double2>();
-    const int nb = (int)std::min<long long>((P + 255) / 256, 8192);
-    hipLaunchKernelGGL(k_pz_chirp_b, dim3(nb), dim3(256), 0, 0, q.D, q.inv_2D, P, b0);
-    {
-        long long rem = P, Ns = 1;
-        auto stage = [&](int R) {
-            hipLaunchKernelGGL(k_pz_dfft_stage, dim3((int)std::min<long long>((P / R + 255) / 256, 8192)), dim3(256), 0, 0, (const double2*)b0, b1, P, R, Ns);
-            std::swap(b0, b1);
-            Ns *= R; rem /= R;
-        };
-        while (rem % 16 == 0) stage(16);
-        while (rem % 8 == 0) stage(8);
-        while (rem % 4 == 0) stage(4);
-        while (rem % 2 == 0) stage(2);
-        while (rem % 9 == 0) stage(9);
-        for (int pr : {3, 5, 7, 11, 13}) while (rem % pr == 0) stage(pr);
-        EGR_CHECK(rem == 1, EGR_ERR_UNSUPPORTED, "convolution length %lld has a prime factor above 13", P);
-    }
-    hipLaunchKernelGGL(k_pz_bhat_store, dim3(nb), dim3(256), 0, 0, (const double2*)b0, P, r.L, r.Ma, r.Mb, 1.0 / (double)P, z->d_bhat.as<cplx>());
+    if ((rc = pz_bhat_launch(q.D, P, r, buf0.as<double2>(), buf1.as<double2>(), z->d_bhat.as<cplx>()))) return rc;
     const hipError_t se = hipDeviceSynchronize();
     if (se != hipSuccess || hipGetLastError() != hipSuccess) {
         set_error("building the chirp spectrum failed: %s", hipGetErrorString(se));
         return EGR_ERR_HIP;
+    }
+    return EGR_OK;
+}
+
+// The row-table kernels of the plan's choice get the LDS cap the plan's own kernels got in pz_build (the two-barrier kernels stay
+// under the default).
+int pz_rows_prepare(egr_fatllama_plan* plan) {
+    PzPlan* z = plan->pz.get();
+    EGR_CHECK(z != nullptr, EGR_ERR_ARG, "paired chirp-z plan wanted");
+    const PzKernels& k = z->kr;
+    const void* fns[] = {(const void*)k.first, (const void*)k.crop, (const void*)k.last, (const void*)k.pair, (const void*)k.pairmax,
+                         k.rowconv ? (const void*)k.rowconv : (const void*)k.rowconv_rt, k.rowconv ? (const void*)k.rowconv_conj : (const void*)k.rowconv_rt_conj};
+    for (const void* fn : fns) {
+        const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, EGR_LDS_MAX);
+        EGR_CHECK(e == hipSuccess, EGR_ERR_HIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) -> %s", hipGetErrorString(e));
     }
     return EGR_OK;
 }
@@ -1185,33 +1275,39 @@ struct PzRun {
     egr_fatllama_plan* plan;
     PzPlan* z;
     bool three;
+    const PzRowP* rows;          // the states' rows of a wave (the launch's first state first), or nullptr
+    const PzKernels& k() const { return rows ? z->kr : z->k; }
     void conv(bool conj, cplx* work, int ns, hipStream_t st, bool prof, size_t* slot) const {
         const RowP& r = plan->row;
+        const PzKernels& kk = k();
         if (three) fl_launch_inner(plan, true, work, ns, st);
         if (prof) fl_prof_begin(plan, 0, st, slot);
-        if (z->rowconv) {
-            hipLaunchKernelGGL(conj ? z->rowconv_conj : z->rowconv, dim3(r.R, ns), dim3(z->threads_row), z->lds_row, st, z->stw_row, z->d_bhat.as<const cplx>(), z->p.P, work);
+        if (kk.rowconv) {
+            hipLaunchKernelGGL(conj ? kk.rowconv_conj : kk.rowconv, dim3(r.R, ns), dim3(z->threads_row), z->lds_row, st, z->stw_row, z->d_bhat.as<const cplx>(), z->p.P, work, rows);
         } else {
-            if (conj) hipLaunchKernelGGL(k_pz_rowconv<true>, dim3(r.R, ns), dim3(512), z->lds_row, st, r.f, r.L, r.tw, z->d_bhat.as<const cplx>(), z->p.P, work);
-            else hipLaunchKernelGGL(k_pz_rowconv<false>, dim3(r.R, ns), dim3(512), z->lds_row, st, r.f, r.L, r.tw, z->d_bhat.as<const cplx>(), z->p.P, work);
+            hipLaunchKernelGGL(conj ? kk.rowconv_rt_conj : kk.rowconv_rt, dim3(r.R, ns), dim3(512), z->lds_row, st, r.f, r.L, r.tw, z->d_bhat.as<const cplx>(), z->p.P, work, rows);
         }
         if (prof) fl_prof_end(plan, st, slot);
         if (three) fl_launch_inner(plan, false, work, ns, st);
     }
-    void pair(const PzP& q, const PzHook& h, bool maxonly, cplx* work, int ns, hipStream_t st, bool prof, size_t* slot) const {
-        const dim3 g(8 * q.g_per_xcd, ns);
+    // gpx: workgroups per XCD of the grid (the plan's g_per_xcd; a wave's largest)
+    void pair(const PzP& q, int gpx, const PzHook& h, bool maxonly, cplx* work, int ns, hipStream_t st, bool prof, size_t* slot) const {
+        const PzKernels& kk = k();
+        const dim3 g(8 * gpx, ns);
         if (prof && !maxonly) fl_prof_begin(plan, 1, st, slot);
-        if (maxonly) hipLaunchKernelGGL(z->pairmax, g, dim3(z->threads_pairmax), z->lds_pair, st, q, h, work);
-        else if (z->pair_wl) {
+        if (maxonly) hipLaunchKernelGGL(kk.pairmax, g, dim3(z->threads_pairmax), z->lds_pair, st, q, h, work, rows);
+        else if (kk.pair_wl) {
             const PzColWlEntry* e = z->crop_wl;          // same geometry: 8 column slots, max(LA, LB) threads each
-            hipLaunchKernelGGL(z->pair_wl, g, dim3(e->threads), EGR_LDS(e->lds), st, q, h, z->crop_wl_tab, work);
-        } else hipLaunchKernelGGL(z->pair, g, dim3(z->threads_pair), z->lds_pair, st, q, h, work);
+            hipLaunchKernelGGL(kk.pair_wl, g, dim3(e->threads), EGR_LDS(e->lds), st, q, h, z->crop_wl_tab, work, rows);
+        } else hipLaunchKernelGGL(kk.pair, g, dim3(z->threads_pair), z->lds_pair, st, q, h, work, rows);
         if (prof && !maxonly) fl_prof_end(plan, st, slot);
     }
 };
 }  // namespace
 
 // The loop between k_prepare and k_finalize: `out` holds y, receives y + d; per-channel peaks -> peak_out.
+// With a row table (c.rows, a wave of clips): state st runs on rows[st]; the rows name wave-global channels and offsets into `out`, so
+// a group of states shifts the TABLE and leaves out, peak_out, thr0_rel and the ring of maxima where they are.
 int pz_loop(const FlCall& c) {
     egr_fatllama_plan* plan = c.p;
     PzPlan* z = plan->pz.get();
@@ -1224,12 +1320,15 @@ int pz_loop(const FlCall& c) {
     const unsigned* thr0_rel = c.thr0_rel;
     float* out = c.out;
     unsigned* peak_out = c.peak_out;
+    const PzRowP* rows = c.rows;
+    const int gpx = rows ? c.rows_gpx : q.g_per_xcd;
+    EGR_CHECK(!rows || (gpx >= 1 && plan->sp.levels == 2), EGR_ERR_ARG, "a row table needs a two-level plan and its largest g_per_xcd");
     auto max2_slot = [&](int it, int ch0) { return fl_max2_slot(plan->max2(), C, it, ch0); };
     PzHook h;
     memset(&h, 0, sizeof(h));
     h.thr = thr;
     h.soft = c.soft;
-    PzRun run{plan, z, plan->sp.levels == 3};
+    const bool three = plan->sp.levels == 3;
     // states are independent until k_finalize: two groups of states run as concurrent pipelines on two streams
     const int ns_all = z->nstates;
     const int ngroups = (plan->nstreams == 2 && ns_all >= 2) ? 2 : 1;
@@ -1239,14 +1338,17 @@ int pz_loop(const FlCall& c) {
         const int sb = g == 0 ? 0 : ns_all / 2, ns = ngroups == 1 ? ns_all : (g == 0 ? ns_all / 2 : ns_all - ns_all / 2);
         hipStream_t sg = g == 0 ? s0 : plan->side.s;
         cplx* work = plan->work() + (size_t)sb * q.P;
+        const PzRun run{plan, z, three, rows ? rows + sb : nullptr};
+        const PzKernels& kk = run.k();
         // the kernels index channels from the state id: shift the per-channel arrays so that state 0 of the group is local state 0
-        const int ch0 = q.kind == 1 ? sb : 2 * sb;
+        // (a row table carries wave-global channels: nothing but the table shifts)
+        const int ch0 = rows ? 0 : (q.kind == 1 ? sb : 2 * sb);
         PzP qg = q;
         qg.C = C - ch0;
         float* og = out + (size_t)ch0 * q.N;
         unsigned* pk = peak_out + ch0;
         const dim3 gc(8 * q.tiles_per_xcd, ns), bc(z->threads_col);
-        if (first) hipLaunchKernelGGL(z->first, gc, bc, z->lds_col, sg, qg, thr0, work, og, pk, thr0_rel ? thr0_rel + ch0 : nullptr);
+        if (first) hipLaunchKernelGGL(kk.first, gc, bc, z->lds_col, sg, qg, thr0, work, og, pk, thr0_rel ? thr0_rel + ch0 : nullptr, run.rows);
         for (int it = it0; it < it1; ++it) {
             const bool p_it = profiling && g == 0 && it >= max_iter - 3;      // events around the last iterations of group 0
             run.conv(false, work, ns, sg, p_it, &slot);
@@ -1255,26 +1357,26 @@ int pz_loop(const FlCall& c) {
                 // the spectrum maximum from a read-only pass only where no hook has left it: iteration 0 (or every one, on request)
                 if (it == 0 || recompute) {
                     hg.max2_out = max2_slot(it, ch0);
-                    run.pair(qg, hg, true, work, ns, sg, false, &slot);
+                    run.pair(qg, gpx, hg, true, work, ns, sg, false, &slot);
                 }
                 hg.max2 = max2_slot(it, ch0);
                 hg.max2_next = recompute ? nullptr : max2_slot(it + 1, ch0);
                 hg.max2_zero = max2_slot(it + 2, ch0);
             }
-            run.pair(qg, hg, false, work, ns, sg, p_it, &slot);
+            run.pair(qg, gpx, hg, false, work, ns, sg, p_it, &slot);
             run.conv(true, work, ns, sg, false, &slot);
             if (it + 1 < max_iter) {
                 if (p_it) fl_prof_begin(plan, 2, sg, &slot);
-                if (z->crop_wl) {
+                if (kk.crop_wl) {
                     const PzColWlEntry* e = z->crop_wl;
                     const int nt8 = q.nc / 8, tpx8 = ceil_div(nt8, 8);
-                    hipLaunchKernelGGL(e->fn, dim3(8 * tpx8, ns), dim3(e->threads), EGR_LDS(e->lds), sg, qg, z->crop_wl_tab, nt8, tpx8, work);
+                    hipLaunchKernelGGL(kk.crop_wl, dim3(8 * tpx8, ns), dim3(e->threads), EGR_LDS(e->lds), sg, qg, z->crop_wl_tab, nt8, tpx8, work, run.rows);
                 } else
-                hipLaunchKernelGGL(z->crop, gc, dim3(z->threads_crop), z->lds_col, sg, qg, thr, work, og, pk, (const unsigned*)nullptr);
+                hipLaunchKernelGGL(kk.crop, gc, dim3(z->threads_crop), z->lds_col, sg, qg, thr, work, og, pk, (const unsigned*)nullptr, run.rows);
                 if (p_it) fl_prof_end(plan, sg, &slot);
             }
         }
-        if (last) hipLaunchKernelGGL(z->last, gc, bc, z->lds_col, sg, qg, thr, work, og, pk, (const unsigned*)nullptr);
+        if (last) hipLaunchKernelGGL(kk.last, gc, bc, z->lds_col, sg, qg, thr, work, og, pk, (const unsigned*)nullptr, run.rows);
     };
     // The four launches of a middle iteration are the same every iteration: fl_run_pipelines replays them from a captured graph
     // (two pipelines: 113.9 -> 103.4 ms per 800 iterations of 60 s + 2 samples; a single pipeline measures the same either way).
@@ -1294,17 +1396,17 @@ int pz_band_filter(egr_fatllama_plan* plan, const float* x, int64_t band_lo, flo
     memset(&h, 0, sizeof(h));
     h.band = 1;
     h.band_lo = (unsigned long long)band_lo;
-    PzRun run{plan, z, plan->sp.levels == 3};
+    PzRun run{plan, z, plan->sp.levels == 3, nullptr};
     const int ns = z->nstates;
     unsigned* pk = plan->peaks() + plan->C;
     size_t slot = 0;
     const dim3 gc(8 * q.tiles_per_xcd, ns), bc(z->threads_col);
-    hipLaunchKernelGGL(z->first, gc, bc, z->lds_col, st, q, -1.0f, plan->work(), const_cast<float*>(x), pk, (const unsigned*)nullptr);
+    hipLaunchKernelGGL(z->k.first, gc, bc, z->lds_col, st, q, -1.0f, plan->work(), const_cast<float*>(x), pk, (const unsigned*)nullptr, (const PzRowP*)nullptr);
     run.conv(false, plan->work(), ns, st, false, &slot);
-    run.pair(q, h, false, plan->work(), ns, st, false, &slot);
+    run.pair(q, q.g_per_xcd, h, false, plan->work(), ns, st, false, &slot);
     run.conv(true, plan->work(), ns, st, false, &slot);
     EGR_HIP(hipMemsetAsync(y, 0, (size_t)plan->C * q.N * sizeof(float), st));      // the closing pass adds d to what y holds
-    hipLaunchKernelGGL(z->last, gc, bc, z->lds_col, st, q, 0.f, plan->work(), y, pk, (const unsigned*)nullptr);
+    hipLaunchKernelGGL(z->k.last, gc, bc, z->lds_col, st, q, 0.f, plan->work(), y, pk, (const unsigned*)nullptr, (const PzRowP*)nullptr);
     EGR_HIP(hipGetLastError());
     return EGR_OK;
 }

@@ -16,6 +16,7 @@ FL_THR_RELATIVE, FL_THR_SOFT, FL_NO_INIT_THR, FL_ZERO_STUFF, FL_INTERP_LINSPACE 
 FL_DEFER_FINALIZE = 0x400    # enhance stops behind out = y + d; egr_fatllama_joint_peak / _finalize complete it (channel-parallel runs)
 FL_THR_RECOMPUTE = 0x200     # with FL_THR_RELATIVE: a maximum pass in every iteration instead of the carried maximum (tests, A/B)
 FL_INFO_LEN = 48
+FLMANY_HEAD, FLMANY_REC, FLMANY_MAX_ROWS = 16, 8, 1024      # egr_flmany_query (include/egregora_amd.h)
 ABI_VERSION = 5          # include/egregora_amd.h EGR_ABI_VERSION
 
 # name -> (restype, argtypes); must list every symbol of include/egregora_amd.h
@@ -41,6 +42,11 @@ SIGNATURES = {
     "egr_fatllama_kernel_times": (_i, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(_i64),
                                        C.POINTER(_i64)]),
     "egr_fatllama_kernel_times3": (_i, [_vp, C.POINTER(C.c_double), C.POINTER(_i64)]),
+    "egr_flmany_query": (_i, [_i, C.POINTER(_i64), C.POINTER(_i), C.POINTER(_i64), C.POINTER(_i), C.POINTER(_i64)]),
+    "egr_flmany_create": (_i, [C.POINTER(_vp), _i, C.POINTER(_i64), C.POINTER(_i), C.POINTER(_i64), C.POINTER(_i)]),
+    "egr_flmany_layout": (_i, [_vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]),
+    "egr_flmany_enhance": (_i, [_vp, _vp, _vp, _i, _f, _u, _vp]),
+    "egr_flmany_destroy": (_i, [_vp]),
     "egr_lds_canary_failures": (C.c_longlong, []),
     "egr_lds_canary_selftest": (C.c_longlong, [_i]),
     "egr_pcm16_roundtrip": (_i, [_vp, _vp, _i64, _f, _f, _vp]),

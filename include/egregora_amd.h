@@ -141,6 +141,40 @@ int egr_fatllama_kernel_times(egr_fatllama_plan* plan, double* row_ms_avg, doubl
  * [2] second column pass (inner pass of a three-level plan; chirp-z: the crop pass k_pzcol<1>). */
 int egr_fatllama_kernel_times3(egr_fatllama_plan* plan, double ms_avg[3], int64_t launches[3]);
 
+/* Many clips in one pass.  Clips whose lengths have no packed plan -- the paired chirp-z lengths above: nearly every
+ * real file -- can share ONE convolution length P (the cyclic convolution is exact for any P >= 2 D - 1): a wave runs them as states of
+ * the same launches, with everything that depends on a clip's own transform length D in a per-state row table.  All clips of a wave
+ * are of one chirp-z kind and the plan of the largest has two levels; the largest clip computes what egr_fatllama_enhance computes
+ * for it alone, bit for bit, and so does every clip whose own P is the wave's.
+ *   egr_flmany_query   : host only.  Clip i has n_in[i] samples in channels[i] channels and n_out[i] output samples (0, or n_out NULL:
+ *                        n_in[i] * factor[i]; another value: the egr_fatllama_plan_create_n reading, enhance then needs
+ *                        EGR_FL_INTERP_LINSPACE).  info holds EGR_FLMANY_HEAD + EGR_FLMANY_REC * (n_clips + sum channels) values:
+ *                          head  [0] 1 = the clips form a wave, [1] kind, [2] L, [3] nc, [4] P = L nc (those of the largest D alone),
+ *                                [5] states, [6] channel rows, [7] bytes of device memory the wave allocates, [8] TC, [9] levels,
+ *                                [10] the first clip that cannot join (-1: none), [11] why (1 packed length, 2 three-level plan,
+ *                                3 another kind than clip 0, 4 more than EGR_FLMANY_MAX_ROWS channel rows, 5 no length, 6 legacy chirp-z
+ *                                forced by the environment), [12] largest tile pairs per XCD, [13] / [14] floats of the flat x / out
+ *                                buffers, [15] distinct D
+ *                          clip  {kind (0: packed plan), D, its own P, its own levels, N, first state, states, first channel row}
+ *                          state {clip, s, c0, iDr, cDr, G, D, channels} -- the row geometry, from the function plan builds use
+ *                        (states only when [0] is 1)
+ *   egr_flmany_create  : EGR_ERR_UNSUPPORTED, naming the clip, before anything is allocated unless the clips form a wave
+ *   egr_flmany_layout  : where channel row r (clips in order, their channels in order) starts in the flat buffers, in floats:
+ *                        x rows are packed, out rows start on 8-byte boundaries; totals = {x floats, out floats}
+ *   egr_flmany_enhance : egr_fatllama_enhance for every clip: x_flat -> out_flat (device).  max_iter >= 1; autoscale, the joint
+ *                        peak and the write patch run over a clip's own channels.  Flags as egr_fatllama_enhance, except
+ *                        EGR_FL_THR_RECOMPUTE and EGR_FL_DEFER_FINALIZE (EGR_ERR_UNSUPPORTED before any launch).  Only enqueues. */
+typedef struct egr_flmany egr_flmany;
+#define EGR_FLMANY_HEAD 16
+#define EGR_FLMANY_REC 8
+#define EGR_FLMANY_MAX_ROWS 1024
+int egr_flmany_query(int n_clips, const int64_t* n_in, const int* factor, const int64_t* n_out, const int* channels, int64_t* info);
+int egr_flmany_create(egr_flmany** out, int n_clips, const int64_t* n_in, const int* factor, const int64_t* n_out, const int* channels);
+int egr_flmany_layout(egr_flmany* wave, int64_t* x_off, int64_t* out_off, int64_t totals[2]);
+int egr_flmany_enhance(egr_flmany* wave, const float* x_flat, float* out_flat, int max_iter, float threshold, unsigned flags,
+                       void* stream);
+int egr_flmany_destroy(egr_flmany* wave);
+
 /* Debug builds only (make -C csrc CANARY=1 -> -DEGR_LDS_CANARY): every dynamic LDS region of the Fat-Llama kernels carries a 64-byte
  * guard band on either side, armed at kernel start and checked at kernel exit.  egr_lds_canary_failures: workgroups that found a
  * guard overwritten since the library was loaded (-1: this build has no canaries).  egr_lds_canary_selftest(where): one launch that
