@@ -13,8 +13,9 @@ EGREGORA_CODEC_NODES is "1", the FlashSR batch node (egregora_audio_super_resolu
 when EGREGORA_BATCH_NODES is "1", the DeepFilterNet batch node (egregora_audio_enhance_dfn_batch.py: a list of clips in ragged passes)
 only when EGREGORA_DENOISE_BATCH_NODES is "1", the codec's batch nodes (egregora_audio_codec_dac_batch.py: a list of clips in padded
 passes) only when EGREGORA_CODEC_BATCH_NODES is "1", the Fat-Llama batch node (egregora_fat_llama_gpu_batch.py: a list of clips in
-waves that share one chirp-z convolution length) only when EGREGORA_FATLLAMA_BATCH_NODES is "1".  Without them the registered set is
-the one listed above.
+waves that share one chirp-z convolution length) only when EGREGORA_FATLLAMA_BATCH_NODES is "1", the WPE batch node
+(egregora_audio_enhance_wpe_batch.py: a list of clips in one ragged pass per wave) only when EGREGORA_ENHANCE_BATCH_NODES is "1".
+Without them the registered set is the one listed above.
 """
 import os
 
@@ -78,5 +79,10 @@ if os.environ.get("EGREGORA_FATLLAMA_BATCH_NODES") == "1":
     from .egregora_fat_llama_gpu_batch import (NODE_CLASS_MAPPINGS as FL_BATCH_MAP, NODE_DISPLAY_NAME_MAPPINGS as FL_BATCH_NAMES)
     NODE_CLASS_MAPPINGS.update(FL_BATCH_MAP)
     NODE_DISPLAY_NAME_MAPPINGS.update(FL_BATCH_NAMES)
+
+if os.environ.get("EGREGORA_ENHANCE_BATCH_NODES") == "1":
+    from .egregora_audio_enhance_wpe_batch import (NODE_CLASS_MAPPINGS as WPE_BATCH_MAP, NODE_DISPLAY_NAME_MAPPINGS as WPE_BATCH_NAMES)
+    NODE_CLASS_MAPPINGS.update(WPE_BATCH_MAP)
+    NODE_DISPLAY_NAME_MAPPINGS.update(WPE_BATCH_NAMES)
 
 __all__ = ["NODE_CLASS_MAPPINGS", "NODE_DISPLAY_NAME_MAPPINGS"]

@@ -4,8 +4,13 @@
 //                LDS, all in double; then the filter sweep and the next iteration's weights
 //   k_wpe_istft  inverse transform, synthesis window and overlap-add as a gather (no atomics)
 // Spectra are complex64 in memory; everything between them and the final X is double (SPEC WPE-P6).
+// Each kernel's body is a __device__ function that takes the workgroup's place as arguments.  The kernels above pass blockIdx (one clip
+// per call); k_wpe_stft_many, k_wpe_iter_many and k_wpe_istft_many look the place up in device tables (egr_wpemany_dereverb: many clips in
+// 2 + iterations launches, flat 1-D grids, every clip with the bits of its single call).
 #include <math.h>
+#include <string.h>
 
+#include <algorithm>
 #include <map>
 #include <mutex>
 #include <tuple>
@@ -13,27 +18,27 @@
 
 #include "egr_common.h"
 #include "egr_fft_device.h"
+#include "egr_handle.h"
 #include "egr_plan.h"
 #include "egr_stft_tables.h"
 #include "egr_wpe_index.h"
 
 namespace egr {
 
-constexpr int WPE_FT = 8;            // frames per workgroup of k_wpe_stft: 64-byte store runs
-constexpr int WPE_SEG = 8;           // hop-long output segments per workgroup of k_wpe_istft
+// (WPE_FT, WPE_SEG: frames per workgroup of k_wpe_stft, segments per workgroup of k_wpe_istft -- egr_wpe_index.h)
 constexpr int WPE_LDS_MAX = 160 * 1024;
 constexpr double WPE_PSD_FLOOR = 1e-10, WPE_PIVOT_FLOOR = 1e-13;
 
 // ------------------------------------------------------------------------------------------------------------ analysis
 // Workgroup (tile of WPE_FT frames, channel).  Frame t covers samples t hop - (n_fft - hop) + [0, n_fft) of x, zeros outside [0, n).
-__global__ __launch_bounds__(256) void k_wpe_stft(const float* __restrict__ x, int C, long long n, int n_fft, int hop, int frames,
-                                                   const float* __restrict__ win, FftDesc fd, const cplx* __restrict__ tw,
-                                                   const cplx* __restrict__ wsplit, cplx* __restrict__ Y) {
+// (tile, c: the workgroup's place, blockIdx of the single call, a table lookup of the many-clip one)
+__device__ __forceinline__ void wpe_stft_tile(const float* __restrict__ x, int C, long long n, int n_fft, int hop, int frames,
+                                              const float* __restrict__ win, FftDesc fd, const cplx* __restrict__ tw,
+                                              const cplx* __restrict__ wsplit, cplx* __restrict__ Y, long long tile, int c) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     cplx* buf = (cplx*)smem;                                   // [WPE_FT][Mh]
     const int Mh = n_fft / 2;
-    const int c = blockIdx.y;
-    const long long t0 = (long long)blockIdx.x * WPE_FT;
+    const long long t0 = tile * WPE_FT;
     const long long pad = n_fft - hop;
     const float* xc = x + (size_t)c * n;
     for (int fr = 0; fr < WPE_FT; ++fr) {
@@ -63,19 +68,36 @@ __global__ __launch_bounds__(256) void k_wpe_stft(const float* __restrict__ x, i
     }
 }
 
+__global__ __launch_bounds__(256) void k_wpe_stft(const float* __restrict__ x, int C, long long n, int n_fft, int hop, int frames,
+                                                   const float* __restrict__ win, FftDesc fd, const cplx* __restrict__ tw,
+                                                   const cplx* __restrict__ wsplit, cplx* __restrict__ Y) {
+    wpe_stft_tile(x, C, n, n_fft, hop, frames, win, fd, tw, wsplit, Y, (long long)blockIdx.x, (int)blockIdx.y);
+}
+
+// Many clips: a flat grid over the frame tiles of every (clip, channel) track; off = the prefix table of tiles (egr_wpe_index.h).
+__global__ __launch_bounds__(256) void k_wpe_stft_many(const float* __restrict__ x, const WpeClip* __restrict__ clips,
+                                                        const long long* __restrict__ off, int n_clips, int C, int n_fft, int hop,
+                                                        const float* __restrict__ win, FftDesc fd, const cplx* __restrict__ tw,
+                                                        const cplx* __restrict__ wsplit, char* __restrict__ ws) {
+    int i, c;
+    long long tile;
+    wpe_many_track(off, n_clips, C, (long long)blockIdx.x, &i, &c, &tile);
+    const WpeClip q = clips[i];
+    wpe_stft_tile(x + q.x_off, C, q.n, n_fft, hop, (int)q.frames, win, fd, tw, wsplit, (cplx*)(ws + q.ws_off), tile, c);
+}
+
 // ------------------------------------------------------------------------------------------------------------ synthesis
 // Workgroup (run of WPE_SEG hop-long segments of the faded signal, channel): the n_fft / hop + WPE_SEG - 1 frames that touch the run
 // are inverse-transformed one after the other, in ascending frame order, and every thread adds its own samples -- the sum order of
 // an output sample is fixed, so the result is the same bits on every call.
-__global__ __launch_bounds__(256) void k_wpe_istft(const cplx* __restrict__ Y, int C, int frames, int n_fft, int hop,
-                                                    const float* __restrict__ wsyn, FftDesc fd, const cplx* __restrict__ tw,
-                                                    const cplx* __restrict__ wsplit, float* __restrict__ y, long long n_out) {
+__device__ __forceinline__ void wpe_istft_run(const cplx* __restrict__ Y, int C, int frames, int n_fft, int hop,
+                                              const float* __restrict__ wsyn, FftDesc fd, const cplx* __restrict__ tw,
+                                              const cplx* __restrict__ wsplit, float* __restrict__ y, long long n_out, long long run, int c) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int Mh = n_fft / 2, R = n_fft / hop;
     cplx* buf = (cplx*)smem;                                   // [Mh]
     float* acc = (float*)(buf + Mh);                           // [WPE_SEG hop]
-    const int c = blockIdx.y;
-    const long long j0 = (long long)blockIdx.x * WPE_SEG;
+    const long long j0 = run * WPE_SEG;
     const int na = WPE_SEG * hop;
     const float inv_mh = 1.0f / (float)Mh;
     for (int a = threadIdx.x; a < na; a += blockDim.x) acc[a] = 0.f;
@@ -110,6 +132,25 @@ __global__ __launch_bounds__(256) void k_wpe_istft(const cplx* __restrict__ Y, i
     }
 }
 
+__global__ __launch_bounds__(256) void k_wpe_istft(const cplx* __restrict__ Y, int C, int frames, int n_fft, int hop,
+                                                    const float* __restrict__ wsyn, FftDesc fd, const cplx* __restrict__ tw,
+                                                    const cplx* __restrict__ wsplit, float* __restrict__ y, long long n_out) {
+    wpe_istft_run(Y, C, frames, n_fft, hop, wsyn, fd, tw, wsplit, y, n_out, (long long)blockIdx.x, (int)blockIdx.y);
+}
+
+// Many clips: a flat grid over the segment runs of every track; the spectra read are the clip's X, behind its Y in its block.
+__global__ __launch_bounds__(256) void k_wpe_istft_many(const char* __restrict__ ws, const WpeClip* __restrict__ clips,
+                                                         const long long* __restrict__ off, int n_clips, int C, int n_fft, int hop,
+                                                         const float* __restrict__ wsyn, FftDesc fd, const cplx* __restrict__ tw,
+                                                         const cplx* __restrict__ wsplit, float* __restrict__ y) {
+    int i, c;
+    long long run;
+    wpe_many_track(off, n_clips, C, (long long)blockIdx.x, &i, &c, &run);
+    const WpeClip q = clips[i];
+    wpe_istft_run((const cplx*)(ws + q.ws_off + q.spec_bytes), C, (int)q.frames, n_fft, hop, wsyn, fd, tw, wsplit, y + q.y_off, q.n_out,
+                  run, c);
+}
+
 // ------------------------------------------------------------------------------------------------------------ one iteration
 __device__ __forceinline__ double wpe_block_max(double v, double* red) {
     __syncthreads();
@@ -142,11 +183,11 @@ static __host__ __device__ inline WpeLds wpe_lds(const WpeGeom& g) {
 
 // Y: [bins][D][T] complex64.  inv_in: [bins][T] double, or NULL: the weights come from Y itself (first iteration) and are left in
 // ws_inv.  X (LAST only): [bins][D][T] complex64.  G: NULL or [bins][K][D] complex double.  inv_out: NULL or [bins][T] double.
+// f: the bin (blockIdx.x of the single call; the many-clip call passes its clip's arrays and the bin of its flat index).
 template <int NB, bool LAST>
-__global__ __launch_bounds__(WPE_THREADS) void k_wpe_iter(const cplx* __restrict__ Y, const double* __restrict__ inv_in, int D, int T,
-                                                           int taps, int delay, cplx* __restrict__ X, double2* __restrict__ G,
-                                                           double* __restrict__ inv_out, int* __restrict__ flags,
-                                                           double* __restrict__ ws_inv) {
+__device__ __forceinline__ void wpe_iter_bin(const cplx* __restrict__ Y, const double* __restrict__ inv_in, int D, int T, int taps,
+                                             int delay, cplx* __restrict__ X, double2* __restrict__ G, double* __restrict__ inv_out,
+                                             int* __restrict__ flags, double* __restrict__ ws_inv, const size_t f) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const WpeGeom g = wpe_geom(D, taps, delay);
     const WpeLds L = wpe_lds(g);
@@ -159,7 +200,6 @@ __global__ __launch_bounds__(WPE_THREADS) void k_wpe_iter(const cplx* __restrict
     double* red = (double*)(smem + L.red);
     double* ldiag = (double*)(smem + L.ldiag);
     const int tid = threadIdx.x;
-    const size_t f = blockIdx.x;
     const cplx* Yf = Y + f * (size_t)D * T;
     const double* inv = inv_in ? inv_in + f * (size_t)T : ws_inv + f * (size_t)T;
 
@@ -330,6 +370,30 @@ __global__ __launch_bounds__(WPE_THREADS) void k_wpe_iter(const cplx* __restrict
     }
 }
 
+template <int NB, bool LAST>
+__global__ __launch_bounds__(WPE_THREADS) void k_wpe_iter(const cplx* __restrict__ Y, const double* __restrict__ inv_in, int D, int T,
+                                                           int taps, int delay, cplx* __restrict__ X, double2* __restrict__ G,
+                                                           double* __restrict__ inv_out, int* __restrict__ flags,
+                                                           double* __restrict__ ws_inv) {
+    wpe_iter_bin<NB, LAST>(Y, inv_in, D, T, taps, delay, X, G, inv_out, flags, ws_inv, (size_t)blockIdx.x);
+}
+
+// Many clips: workgroup clip * bins + bin of a flat grid.  in_sel: -1 (first iteration: the weights come from Y and stay in inv[0]) or
+// the inv buffer read; out_sel: -1 (last iteration) or the inv buffer written.  X is written by the LAST instantiation alone.
+template <int NB, bool LAST>
+__global__ __launch_bounds__(WPE_THREADS) void k_wpe_iter_many(char* __restrict__ ws, const WpeClip* __restrict__ clips, int bins, int D,
+                                                                int taps, int delay, int in_sel, int out_sel) {
+    int i, f;
+    wpe_many_pair((long long)blockIdx.x, bins, &i, &f);
+    const WpeClip q = clips[i];
+    char* base = ws + q.ws_off;
+    double* inv0 = (double*)(base + 2 * q.spec_bytes);
+    double* inv1 = (double*)(base + 2 * q.spec_bytes + q.inv_bytes);
+    wpe_iter_bin<NB, LAST>((const cplx*)base, in_sel < 0 ? nullptr : (in_sel ? inv1 : inv0), D, (int)q.frames, taps, delay,
+                           (cplx*)(base + q.spec_bytes), nullptr, out_sel < 0 ? nullptr : (out_sel ? inv1 : inv0),
+                           (int*)(base + 2 * q.spec_bytes + 2 * q.inv_bytes), inv0, (size_t)f);
+}
+
 // ------------------------------------------------------------------------------------------------------------ host
 struct WpeWindows {
     float *win, *wsyn;
@@ -378,7 +442,10 @@ static int wpe_raise_lds() {
     std::lock_guard<std::mutex> lk(g_wpe_mu);
     if (g_wpe_attr[dev]) return EGR_OK;
     const void* fns[] = {(const void*)k_wpe_stft, (const void*)k_wpe_istft, (const void*)k_wpe_iter<1, false>,
-                         (const void*)k_wpe_iter<1, true>, (const void*)k_wpe_iter<2, false>, (const void*)k_wpe_iter<2, true>};
+                         (const void*)k_wpe_iter<1, true>, (const void*)k_wpe_iter<2, false>, (const void*)k_wpe_iter<2, true>,
+                         (const void*)k_wpe_stft_many, (const void*)k_wpe_istft_many, (const void*)k_wpe_iter_many<1, false>,
+                         (const void*)k_wpe_iter_many<1, true>, (const void*)k_wpe_iter_many<2, false>,
+                         (const void*)k_wpe_iter_many<2, true>};
     for (const void* fn : fns) EGR_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, WPE_LDS_MAX));
     g_wpe_attr[dev] = true;
     return EGR_OK;
@@ -408,6 +475,74 @@ static int wpe_check_iter(int channels, int64_t frames, int taps, int delay, Wpe
 }
 
 static size_t wpe_align(size_t b) { return (b + 255) & ~(size_t)255; }
+
+// ---- many clips per call: the plan is host arithmetic alone, so that every refusal comes before anything is allocated
+struct WpeManyPlan {
+    std::vector<WpeClip> clips;            // longest first: the long workgroups are dispatched first
+    std::vector<long long> stft_off, istft_off;
+    size_t table_off = 0, table_bytes = 0, total = 0;
+    WpeGeom g;
+    WpeLds L;
+};
+static std::map<int, TableStage> g_wpe_stage;                        // device -> pinned staging of the tables (under g_wpe_mu)
+
+// what wpe_check_framing refuses, without its tables: n_fft even, 4 .. 4096, no prime factor of n_fft / 2 above 13
+static bool wpe_nfft_ok(int n_fft) {
+    if (n_fft < 4 || (n_fft % 2) != 0 || n_fft > 4096) return false;
+    int m = n_fft / 2;
+    for (int p = 2; p <= 13; ++p)
+        while (m % p == 0) m /= p;
+    return m == 1;
+}
+
+static int wpe_many_plan(const int64_t* tab, int n_clips, int channels, int n_fft, int hop, int taps, int delay, WpeManyPlan* P) {
+    EGR_CHECK(tab && n_clips >= 1 && channels >= 1, EGR_ERR_ARG, "WPE: want a table of n_clips >= 1 clips of channels >= 1");
+    EGR_CHECK(wpe_nfft_ok(n_fft), EGR_ERR_UNSUPPORTED, "WPE: n_fft=%d must be even, <= 4096, n_fft/2 without a prime factor above 13", n_fft);
+    EGR_CHECK(wpe_framing_ok(n_fft, hop), EGR_ERR_UNSUPPORTED, "WPE: hop=%d must divide n_fft=%d with n_fft / hop >= 2", hop, n_fft);
+    const long long bins = n_fft / 2 + 1, lim = (1LL << 31) - 4096;
+    for (int i = 0; i < n_clips; ++i)
+        EGR_CHECK(tab[3 * i] >= 0 && tab[3 * i + 1] >= 1 && tab[3 * i + 2] >= 0, EGR_ERR_ARG, "WPE: clip %d: offsets %lld, %lld, n=%lld", i,
+                  (long long)tab[3 * i], (long long)tab[3 * i + 2], (long long)tab[3 * i + 1]);
+    int64_t longest = 1;
+    for (int i = 0; i < n_clips; ++i) {
+        const int64_t n = tab[3 * i + 1];
+        EGR_CHECK(n < (1LL << 48) && wpe_frames(n, n_fft, hop) < lim, EGR_ERR_UNSUPPORTED, "WPE: clip %d: n=%lld gives too many frames", i,
+                  (long long)n);
+        longest = std::max(longest, wpe_frames(n, n_fft, hop));
+    }
+    int rc = wpe_check_iter(channels, longest, taps, delay, &P->g, &P->L);
+    if (rc) return rc;
+    EGR_CHECK((long long)n_clips * bins < lim, EGR_ERR_UNSUPPORTED, "WPE: %d clips x %lld bins exceed one grid", n_clips, bins);
+    std::vector<int> order((size_t)n_clips);
+    for (int i = 0; i < n_clips; ++i) order[i] = i;
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return tab[3 * a + 1] > tab[3 * b + 1]; });
+    P->clips.resize((size_t)n_clips);
+    P->stft_off.assign((size_t)n_clips + 1, 0);
+    P->istft_off.assign((size_t)n_clips + 1, 0);
+    size_t off = 0;
+    for (int j = 0; j < n_clips; ++j) {
+        const int i = order[j];
+        WpeClip& q = P->clips[j];
+        q.x_off = tab[3 * i];
+        q.n = tab[3 * i + 1];
+        q.y_off = tab[3 * i + 2];
+        q.frames = wpe_frames(q.n, n_fft, hop);
+        q.n_out = q.frames * hop - (n_fft - hop);
+        q.spec_bytes = (long long)wpe_align((size_t)bins * channels * q.frames * sizeof(float2));
+        q.inv_bytes = (long long)wpe_align((size_t)bins * q.frames * sizeof(double));
+        q.ws_off = (long long)off;
+        off += 2 * (size_t)q.spec_bytes + 2 * (size_t)q.inv_bytes + wpe_align((size_t)bins * sizeof(int));
+        EGR_CHECK(off < ((size_t)1 << 60), EGR_ERR_UNSUPPORTED, "WPE: the clips' workspace exceeds 2^60 bytes");
+        P->stft_off[j + 1] = P->stft_off[j] + (long long)channels * wpe_stft_tiles(q.frames);
+        P->istft_off[j + 1] = P->istft_off[j] + (long long)channels * wpe_istft_runs(q.frames, n_fft, hop);
+    }
+    EGR_CHECK(P->stft_off[n_clips] < lim && P->istft_off[n_clips] < lim, EGR_ERR_UNSUPPORTED, "WPE: %lld frame tiles exceed one grid",
+              P->stft_off[n_clips]);
+    P->table_off = off;
+    P->table_bytes = (size_t)n_clips * sizeof(WpeClip) + 2 * ((size_t)n_clips + 1) * sizeof(long long);
+    P->total = off + wpe_align(P->table_bytes);
+    return EGR_OK;
+}
 
 }  // namespace egr
 
@@ -517,4 +652,67 @@ extern "C" int egr_wpe_dereverb(const float* x, int channels, int64_t n, int n_f
         if (rc) return rc;
     }
     return egr_wpe_istft(Xs, channels, frames, n_fft, hop, y, n_out, stream);
+}
+
+extern "C" size_t egr_wpemany_workspace_bytes(const int64_t* clips, int n_clips, int channels, int n_fft, int hop, int taps) {
+    WpeManyPlan P;
+    if (wpe_many_plan(clips, n_clips, channels, n_fft, hop, taps, 1, &P) != EGR_OK) return 0;
+    return P.total;
+}
+
+extern "C" int egr_wpemany_dereverb(const float* x, const int64_t* clips, int n_clips, int channels, int n_fft, int hop, int taps,
+                                    int delay, int iterations, float* y, void* ws, size_t ws_bytes, void* stream) {
+    EGR_CHECK(x && y && ws && clips && iterations >= 1, EGR_ERR_ARG, "bad argument");
+    WpeManyPlan P;
+    int rc = wpe_many_plan(clips, n_clips, channels, n_fft, hop, taps, delay, &P);
+    if (rc) return rc;
+    EGR_CHECK(ws_bytes >= P.total, EGR_ERR_ARG, "WPE: workspace of %zu bytes, %zu needed", ws_bytes, P.total);
+    StftTables t;
+    rc = wpe_check_framing(n_fft, hop, &t);
+    if (rc) return rc;
+    WpeWindows w;
+    rc = wpe_windows(n_fft, hop, &w);
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    char* base = (char*)ws;
+    const WpeClip* dclips = (const WpeClip*)(base + P.table_off);
+    const long long* dstft = (const long long*)(dclips + n_clips);
+    const long long* distft = dstft + n_clips + 1;
+    {   // the three tables go up in one asynchronous copy from pinned memory
+        int dev = 0;
+        EGR_HIP(hipGetDevice(&dev));
+        std::lock_guard<std::mutex> lk(g_wpe_mu);
+        TableStage& stage = g_wpe_stage[dev];
+        rc = stage.reserve(P.table_bytes);
+        if (rc) return rc;
+        char* h = (char*)stage.p;
+        memcpy(h, P.clips.data(), (size_t)n_clips * sizeof(WpeClip));
+        memcpy(h + (size_t)n_clips * sizeof(WpeClip), P.stft_off.data(), ((size_t)n_clips + 1) * sizeof(long long));
+        memcpy(h + (size_t)n_clips * sizeof(WpeClip) + ((size_t)n_clips + 1) * sizeof(long long), P.istft_off.data(),
+               ((size_t)n_clips + 1) * sizeof(long long));
+        EGR_HIP(hipMemcpyAsync(base + P.table_off, h, P.table_bytes, hipMemcpyHostToDevice, st));
+        EGR_HIP(hipEventRecord(stage.copied, st));
+    }
+    const int bins = n_fft / 2 + 1;
+    hipLaunchKernelGGL(k_wpe_stft_many, dim3((unsigned)P.stft_off[n_clips]), dim3(256), (size_t)WPE_FT * (n_fft / 2) * sizeof(float2), st, x,
+                       dclips, dstft, n_clips, channels, n_fft, hop, w.win, t.fd, t.tw, t.wsplit, base);
+    EGR_HIP(hipGetLastError());
+    const dim3 grid((unsigned)((long long)n_clips * bins)), block(WPE_THREADS);
+    const bool two = P.g.nblocks > WPE_THREADS;
+    for (int it = 0; it < iterations; ++it) {
+        const bool last = it == iterations - 1;
+        // the single call's buffers: iteration 0 leaves its own weights in inv[0]; iteration it reads inv[it & 1], writes inv[(it + 1) & 1]
+        const int in_sel = it == 0 ? -1 : (it & 1), out_sel = last ? -1 : ((it + 1) & 1);
+#define EGR_WPE_LAUNCH(NB, LASTV)                                                                                                  \
+    hipLaunchKernelGGL((k_wpe_iter_many<NB, LASTV>), grid, block, P.L.total, st, base, dclips, bins, channels, taps, delay, in_sel, out_sel)
+        if (last) { if (two) EGR_WPE_LAUNCH(2, true); else EGR_WPE_LAUNCH(1, true); }
+        else      { if (two) EGR_WPE_LAUNCH(2, false); else EGR_WPE_LAUNCH(1, false); }
+#undef EGR_WPE_LAUNCH
+        EGR_HIP(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_wpe_istft_many, dim3((unsigned)P.istft_off[n_clips]), dim3(256),
+                       (size_t)(n_fft / 2) * sizeof(float2) + (size_t)WPE_SEG * hop * sizeof(float), st, (const char*)base, dclips, distft,
+                       n_clips, channels, n_fft, hop, w.wsyn, t.fd, t.tw, t.wsplit, y);
+    EGR_HIP(hipGetLastError());
+    return EGR_OK;
 }

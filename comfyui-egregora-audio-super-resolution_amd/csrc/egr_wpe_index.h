@@ -1,5 +1,6 @@
 // Index, accumulation and filter code of k_wpe_iter (egr_wpe.hip), kept free of device-only constructs so that the same text compiles for the
 // host: tools/wpe_host_check.cpp walks it thread by thread under -fsanitize=address,undefined against the sequential definition.
+// The index code of the many-clip kernels (flat index -> clip and bin, flat tile -> track) is at the end; tools/wpemany_host_check.cpp walks it.
 //
 // One bin's statistics are the lower-left part of  Z diag(inv) Z^H,  Z = [Ytilde (K rows) ; Y (D rows)],  M = K + D rows, K columns:
 //   rows r < K, columns c <= r :  R[r][c] = sum_t inv[t] Ytilde_r[t] conj(Ytilde_c[t])          (lower triangle of R)
@@ -25,6 +26,8 @@ namespace egr {
 constexpr int WPE_THREADS = 256;
 constexpr int WPE_MAX_K = 64;
 constexpr int WPE_MAX_HIST = 128;   // delay + taps - 1
+constexpr int WPE_FT = 8;           // frames per workgroup of k_wpe_stft: 64-byte store runs
+constexpr int WPE_SEG = 8;          // hop-long output segments per workgroup of k_wpe_istft
 
 struct WpeGeom {
     int D, taps, delay;
@@ -133,6 +136,48 @@ EGR_WPE_HD void wpe_filter_sum(const WpeGeom& g, const wpe_c32* tile, const wpe_
         }
     *xr = sr + cr;
     *xi = si + ci;
+}
+
+// ---- many clips per launch (egr_wpemany_dereverb; tools/wpemany_host_check.cpp walks this part).  No grid dimension counts clips or
+// tracks: k_wpe_iter_many's flat workgroup index is clip * bins + bin, and the analysis and synthesis kernels find their clip in
+// a prefix table of tiles (runs): off[i] = first flat tile of clip i, off[n] = all tiles, clip i holding C equal stretches, one per
+// channel.  Every clip has at least one tile per channel, so the table ascends strictly.
+struct WpeClip {                 // one row of the device table, longest clip first
+    long long x_off, y_off;      // the clip's [C][n] input in x and its [C][n_out] output in y, in floats
+    long long n, n_out;
+    long long ws_off;            // the clip's block of the workspace, in bytes: Y, X, inv[0], inv[1], flags as the single call lays them out
+    long long spec_bytes, inv_bytes;
+    long long frames;
+};
+
+// workgroups one channel of a clip brings to the analysis and to the synthesis grid
+EGR_WPE_HD long long wpe_stft_tiles(long long frames) { return (frames + WPE_FT - 1) / WPE_FT; }
+EGR_WPE_HD long long wpe_istft_runs(long long frames, int n_fft, int hop) { return (frames - 1 + n_fft / hop + WPE_SEG - 1) / WPE_SEG; }
+
+EGR_WPE_HD void wpe_many_pair(long long idx, int bins, int* clip, int* bin) {
+    const long long c = idx / bins;
+    *clip = (int)c;
+    *bin = (int)(idx - c * bins);
+}
+
+// last i in [0, n) with off[i] <= tile (off[0] = 0)
+EGR_WPE_HD int wpe_many_find(const long long* off, int n, long long tile) {
+    int lo = 0, hi = n - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (off[mid] <= tile) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
+// flat tile -> clip, channel and the tile's index inside that channel
+EGR_WPE_HD void wpe_many_track(const long long* off, int n, int C, long long tile, int* clip, int* c, long long* local) {
+    const int i = wpe_many_find(off, n, tile);
+    const long long r = tile - off[i], per = (off[i + 1] - off[i]) / C;
+    const long long ch = r / per;
+    *clip = i;
+    *c = (int)ch;
+    *local = r - ch * per;
 }
 
 }  // namespace egr

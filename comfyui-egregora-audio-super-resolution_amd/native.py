@@ -182,6 +182,8 @@ SIGNATURES = {
     "egr_wpe_istft": (_i, [_vp, _i, _i64, _i, _i, _vp, _i64, _vp]),
     "egr_wpe_iterate": (_i, [_vp, _vp, _i, _i, _i64, _i, _i, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     "egr_wpe_dereverb": (_i, [_vp, _i, _i64, _i, _i, _i, _i, _i, _vp, _i64, _vp, C.c_size_t, _vp]),
+    "egr_wpemany_workspace_bytes": (C.c_size_t, [C.POINTER(_i64), _i, _i, _i, _i, _i]),
+    "egr_wpemany_dereverb": (_i, [_vp, C.POINTER(_i64), _i, _i, _i, _i, _i, _i, _i, _vp, _vp, C.c_size_t, _vp]),
     "egr_dac_lengths": (_i, [_vp, _i64, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)]),
     "egr_dac_create": (_i, [C.POINTER(_vp), _vp, _vp, _i64, _i]),
     "egr_dac_destroy": (_i, [_vp]),

@@ -3,6 +3,7 @@
 Spectra are complex64 [bins][channels][frames]; every statistic, the factorisation and the filter sum run in double on the device
 (WPE-P6).  There is no CPU path: a configuration outside the limits raises RuntimeError, a framing outside WPE-P3 is reported by
 `framing_supported` so that the node can pass its input through as the reference's `except` branch does.
+`dereverb_many` runs a list of clips of one channel count in one egr_wpemany_dereverb call.
 """
 import numpy as np
 import torch
@@ -141,3 +142,65 @@ def dereverb(x: torch.Tensor, n_fft: int, hop: int, taps: int, delay: int, itera
     native.check(L.egr_wpe_dereverb(native.ptr(x), C, n, n_fft, hop, taps, delay, iterations, native.ptr(y), n_out, native.ptr(ws),
                                     ws.numel(), native.stream_ptr()), "egr_wpe_dereverb")
     return y
+
+
+def clip_table(lengths, channels: int, n_fft: int, hop: int):
+    """The host table of egr_wpemany_*: clips packed one after the other in x and in y.  lengths: samples per channel of each clip ->
+    (ctypes int64 [n][3] of (offset in x, n, offset in y), floats of x, floats of y)."""
+    import ctypes
+    tab = (ctypes.c_int64 * (3 * len(lengths)))()
+    xo = yo = 0
+    for i, n in enumerate(lengths):
+        tab[3 * i], tab[3 * i + 1], tab[3 * i + 2] = xo, int(n), yo
+        xo += channels * int(n)
+        yo += channels * out_length(int(n), n_fft, hop) if n >= 1 else 0
+    return tab, xo, yo
+
+
+def many_workspace_bytes(lengths, channels: int, n_fft: int, hop: int, taps: int) -> int:
+    """egr_wpemany_workspace_bytes of a wave of clips (host only): 0 for a wave the call would refuse."""
+    tab, _, _ = clip_table(lengths, channels, n_fft, hop)
+    return int(native.lib().egr_wpemany_workspace_bytes(tab, len(lengths), channels, n_fft, hop, taps))
+
+
+def many_layout(lengths, channels: int, n_fft: int, hop: int):
+    """Where egr_wpemany_dereverb keeps each clip in its workspace (include/egregora_amd.h): per clip, in input order, the byte offsets
+    {"Y", "X", "inv0", "inv1", "flags"} and "frames".  The blocks follow one another longest clip first, equal lengths in input order."""
+    bins = n_fft // 2 + 1
+    al = lambda b: (b + 255) & ~255
+    out, off = [None] * len(lengths), 0
+    for i in sorted(range(len(lengths)), key=lambda i: -int(lengths[i])):
+        fr = frames(int(lengths[i]), n_fft, hop)
+        spec, inv = al(bins * channels * fr * 8), al(bins * fr * 8)
+        out[i] = {"Y": off, "X": off + spec, "inv0": off + 2 * spec, "inv1": off + 2 * spec + inv, "flags": off + 2 * spec + 2 * inv,
+                  "frames": fr}
+        off += 2 * spec + 2 * inv + al(bins * 4)
+    return out
+
+
+def dereverb_many(xs, n_fft: int, hop: int, taps: int, delay: int, iterations: int):
+    """A list of [C, T_i] float32 CUDA tensors of one channel count -> [C, out_length(T_i)] tensors, each the bits of `dereverb` on
+    that clip alone, in ONE egr_wpemany_dereverb call: 2 + iterations launches whatever the number of clips.  The results are views
+    of one flat tensor."""
+    xs = [_rows(x) for x in xs]
+    if not xs:
+        return []
+    C = xs[0].shape[0]
+    if any(x.shape[0] != C or x.device != xs[0].device for x in xs):
+        raise RuntimeError("WPE: the clips of one call share a channel count and a device")
+    check_limits(C, taps, n_fft)
+    if not framing_supported(n_fft, hop):
+        raise RuntimeError(f"WPE: hop = {hop} must divide n_fft = {n_fft} with n_fft / hop >= 2")
+    L = native.lib()
+    lengths = [x.shape[1] for x in xs]
+    tab, x_floats, y_floats = clip_table(lengths, C, n_fft, hop)
+    nbytes = int(L.egr_wpemany_workspace_bytes(tab, len(xs), C, n_fft, hop, taps))
+    if nbytes == 0:
+        raise RuntimeError("WPE: egr_wpemany_workspace_bytes refuses this wave (limits of include/egregora_amd.h)")
+    dev = xs[0].device
+    x = xs[0].reshape(-1) if len(xs) == 1 else torch.cat([v.reshape(-1) for v in xs])
+    y = torch.empty((y_floats,), dtype=torch.float32, device=dev)
+    ws = workspace(dev, nbytes)
+    native.check(L.egr_wpemany_dereverb(native.ptr(x), tab, len(xs), C, n_fft, hop, taps, delay, iterations, native.ptr(y), native.ptr(ws),
+                                        ws.numel(), native.stream_ptr()), "egr_wpemany_dereverb")
+    return [y[tab[3 * i + 2]:tab[3 * i + 2] + C * out_length(n, n_fft, hop)].view(C, -1) for i, n in enumerate(lengths)]

@@ -836,6 +836,25 @@ int egr_wpe_iterate(const void* Y, const double* inv_in, int bins, int channels,
 int egr_wpe_dereverb(const float* x, int channels, int64_t n, int n_fft, int hop, int taps, int delay, int iterations, float* y,
                      int64_t n_out, void* ws, size_t ws_bytes, void* stream);
 
+/* Many clips in one WPE call: 2 + iterations launches whatever n_clips is, every clip with the bits egr_wpe_dereverb
+ * gives it alone (a clip's spectra, weights and filter never touch another clip's; nothing is padded).
+ *   clips : HOST array [n_clips][3] of (offset of the clip in x, n >= 1 samples per channel, offset of the clip in y), in floats.  A clip
+ *           lies as [channels][n] at its offset in x and comes back as [channels][frames hop - (n_fft - hop)] at its offset in y; the
+ *           clips must not overlap.  All clips share `channels` and the five widget values.  The table may come in any order; the
+ *           device works through it longest clip first.
+ *   ws    : egr_wpemany_workspace_bytes bytes (device).  Each clip owns one block laid out as the single call's workspace (Y and X
+ *           [bins][channels][frames_i] complex64, two weight buffers [bins][frames_i] double, flags [bins] int; each part rounded up
+ *           to 256 bytes), the blocks one after the other from offset 0 in the order longest clip first (equal lengths in table
+ *           order), the device tables behind them.  The tables go up in one asynchronous copy from pinned memory.
+ * Refused before any allocation, copy or launch: EGR_ERR_ARG for n_clips < 1, a null pointer, a negative offset, n < 1, taps,
+ * delay or iterations < 1, a workspace that is too small; EGR_ERR_UNSUPPORTED for what egr_wpe_dereverb refuses (framing, n_fft,
+ * channels taps > 64, delay + taps - 1 > 128, the LDS limit), for a clip of 2^31 - 4096 frames or more and for a table whose
+ * (clip, bin) pairs, frame tiles or segment runs exceed one grid.  egr_wpemany_workspace_bytes (host only) returns 0 for a table the
+ * call would refuse. */
+size_t egr_wpemany_workspace_bytes(const int64_t* clips, int n_clips, int channels, int n_fft, int hop, int taps);
+int egr_wpemany_dereverb(const float* x, const int64_t* clips, int n_clips, int channels, int n_fft, int hop, int taps, int delay,
+                         int iterations, float* y, void* ws, size_t ws_bytes, void* stream);
+
 /* Descript Audio Codec forward pass (csrc/egr_dac.hip; SPEC.md 4e): encoder, residual vector quantiser and decoder
  * of a DAC model, the job of the reference's Egregora_DAC_Encode / Egregora_DAC_Decode nodes
  * (egregora_audio_enhance_extras.py:730-857) as their docstrings describe it.  Rows are mono signals (DAC-Q1).
