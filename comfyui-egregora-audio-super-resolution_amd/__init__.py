@@ -14,7 +14,9 @@ when EGREGORA_BATCH_NODES is "1", the DeepFilterNet batch node (egregora_audio_e
 only when EGREGORA_DENOISE_BATCH_NODES is "1", the codec's batch nodes (egregora_audio_codec_dac_batch.py: a list of clips in padded
 passes) only when EGREGORA_CODEC_BATCH_NODES is "1", the Fat-Llama batch node (egregora_fat_llama_gpu_batch.py: a list of clips in
 waves that share one chirp-z convolution length) only when EGREGORA_FATLLAMA_BATCH_NODES is "1", the WPE batch node
-(egregora_audio_enhance_wpe_batch.py: a list of clips in one ragged pass per wave) only when EGREGORA_ENHANCE_BATCH_NODES is "1".
+(egregora_audio_enhance_wpe_batch.py: a list of clips in one ragged pass per wave) only when EGREGORA_ENHANCE_BATCH_NODES is "1", the
+evaluation batch nodes (egregora_audio_eval_batch.py: lists of clips scored and metered in one ragged pass per wave) only when
+EGREGORA_EVAL_BATCH_NODES is "1".
 Without them the registered set is the one listed above.
 """
 import os
@@ -84,5 +86,10 @@ if os.environ.get("EGREGORA_ENHANCE_BATCH_NODES") == "1":
     from .egregora_audio_enhance_wpe_batch import (NODE_CLASS_MAPPINGS as WPE_BATCH_MAP, NODE_DISPLAY_NAME_MAPPINGS as WPE_BATCH_NAMES)
     NODE_CLASS_MAPPINGS.update(WPE_BATCH_MAP)
     NODE_DISPLAY_NAME_MAPPINGS.update(WPE_BATCH_NAMES)
+
+if os.environ.get("EGREGORA_EVAL_BATCH_NODES") == "1":
+    from .egregora_audio_eval_batch import (NODE_CLASS_MAPPINGS as EVAL_BATCH_MAP, NODE_DISPLAY_NAME_MAPPINGS as EVAL_BATCH_NAMES)
+    NODE_CLASS_MAPPINGS.update(EVAL_BATCH_MAP)
+    NODE_DISPLAY_NAME_MAPPINGS.update(EVAL_BATCH_NAMES)
 
 __all__ = ["NODE_CLASS_MAPPINGS", "NODE_DISPLAY_NAME_MAPPINGS"]

@@ -7,7 +7,9 @@
 #include <vector>
 
 #include "egr_common.h"
+#include "egr_eval_index.h"
 #include "egr_fft_device.h"
+#include "egr_handle.h"
 #include "egr_plan.h"
 #include "egr_stft_tables.h"
 
@@ -107,15 +109,7 @@ __global__ __launch_bounds__(256) void k_resample_poly(const float* __restrict__
 // longest one is, and no grid dimension counts tracks or rows.  A workgroup's 256 consecutive samples mostly belong to one track:
 // the group searches the table's ascending output offsets once for its first sample (the same value in every lane), each thread
 // then steps forward over the few track starts inside the group's stretch.
-// last t in [0, n) with tab[t * stride + col] <= i; the column ascends and starts at 0
-__device__ __forceinline__ int track_of(const long long* __restrict__ tab, int n, int stride, int col, long long i) {
-    int lo = 0, hi = n - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (tab[(size_t)mid * stride + col] <= i) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
+// (track_of, the search, is in egr_eval_index.h: host and device share it)
 
 // rows[r] = (track offset into x, track length, chunk index k); chunks [n_rows][win]
 __global__ __launch_bounds__(256) void k_chunk_gather_tracks(const float* __restrict__ x, const long long* __restrict__ rows,
@@ -159,17 +153,11 @@ __global__ __launch_bounds__(256) void k_resample_poly_tracks(const float* __res
     }
 }
 
-// One workgroup per frame: mono downmix, window, half-length complex FFT in LDS, real split, |X|.
-__global__ __launch_bounds__(256) void k_stft_mag(const float* __restrict__ x, int C, long long n, int n_fft, int hop,
-                                                   const float* __restrict__ window, FftDesc fd,
-                                                   const cplx* __restrict__ tw, const cplx* __restrict__ wsplit,
-                                                   float* __restrict__ out) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int Mh = n_fft / 2;
-    cplx* cur = (cplx*)smem;
-    cplx* alt = cur + Mh;
-    const long long f = blockIdx.x;
-    const long long s0 = f * hop;
+// One frame of the STFT magnitude, by one workgroup of 256: mono downmix (rows ld apart), window, half-length complex FFT in LDS; the
+// transform is left in cur (lds_fft may have swapped cur and alt).  k_stft_mag and k_pair_frames (egr_metrics_pairs) both call it.
+__device__ __forceinline__ void stft_frame_fft(const float* __restrict__ x, int C, long long ld, long long n, long long s0, int Mh,
+                                               const float* __restrict__ window, const FftDesc& fd, const cplx* __restrict__ tw,
+                                               cplx*& cur, cplx*& alt) {
     const float invC = (float)C;
     for (int e = threadIdx.x; e < Mh; e += blockDim.x) {
         float v[2];
@@ -180,7 +168,7 @@ __global__ __launch_bounds__(256) void k_stft_mag(const float* __restrict__ x, i
             if (t < n) {
                 m = x[t];
                 if (C > 1) {
-                    for (int c = 1; c < C; ++c) m = __fadd_rn(m, x[(size_t)c * n + t]);
+                    for (int c = 1; c < C; ++c) m = __fadd_rn(m, x[(size_t)c * ld + t]);
                     m = __fdiv_rn(m, invC);
                 }
             }
@@ -190,15 +178,31 @@ __global__ __launch_bounds__(256) void k_stft_mag(const float* __restrict__ x, i
     }
     __syncthreads();
     lds_fft<false>(cur, alt, fd, tw, 1, 0, 1, Mh, false);
+}
+
+// real split of the half-length transform in cur, |X[k]| for k in [0, Mh]
+__device__ __forceinline__ float stft_bin_mag(const cplx* cur, int Mh, const cplx* __restrict__ wsplit, int k) {
+    const cplx Za = cur[k == Mh ? 0 : k];
+    const cplx Zb = cur[(k == 0 || k == Mh) ? 0 : Mh - k];
+    const cplx E = make_float2(0.5f * (Za.x + Zb.x), 0.5f * (Za.y - Zb.y));
+    const cplx O = make_float2(0.5f * (Za.y + Zb.y), -0.5f * (Za.x - Zb.x));
+    const cplx X = cadd(E, cmul(wsplit[k], O));
+    return sqrtf(X.x * X.x + X.y * X.y);
+}
+
+// One workgroup per frame: mono downmix, window, half-length complex FFT in LDS, real split, |X|.
+__global__ __launch_bounds__(256) void k_stft_mag(const float* __restrict__ x, int C, long long n, int n_fft, int hop,
+                                                   const float* __restrict__ window, FftDesc fd,
+                                                   const cplx* __restrict__ tw, const cplx* __restrict__ wsplit,
+                                                   float* __restrict__ out) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int Mh = n_fft / 2;
+    cplx* cur = (cplx*)smem;
+    cplx* alt = cur + Mh;
+    const long long f = blockIdx.x;
+    stft_frame_fft(x, C, n, n, f * hop, Mh, window, fd, tw, cur, alt);
     float* o = out + (size_t)f * (Mh + 1);
-    for (int k = threadIdx.x; k <= Mh; k += blockDim.x) {
-        const cplx Za = cur[k == Mh ? 0 : k];
-        const cplx Zb = cur[(k == 0 || k == Mh) ? 0 : Mh - k];
-        const cplx E = make_float2(0.5f * (Za.x + Zb.x), 0.5f * (Za.y - Zb.y));
-        const cplx O = make_float2(0.5f * (Za.y + Zb.y), -0.5f * (Za.x - Zb.x));
-        const cplx X = cadd(E, cmul(wsplit[k], O));
-        o[k] = sqrtf(X.x * X.x + X.y * X.y);
-    }
+    for (int k = threadIdx.x; k <= Mh; k += blockDim.x) o[k] = stft_bin_mag(cur, Mh, wsplit, k);
 }
 
 static std::mutex g_stft_mu;
@@ -228,6 +232,12 @@ int stft_tables(int n_fft, StftTables* out) {
 // ---------------------------------------------------------------- evaluation metrics (egregora_audio_eval_pack.py:405-429)
 // per[f] = sqrt(mean_k (20 log10(A[f][k] + eps) - 20 log10(B[f][k] + eps))^2 + 1e-12), float32 terms like the reference,
 // the bin sum in double.  One workgroup per frame.
+__device__ __forceinline__ double lsd_bin_term(float a, float b) {
+    const float la = 20.0f * log10f(a + 1e-12f), lb = 20.0f * log10f(b + 1e-12f);
+    const float d = la - lb;
+    return (double)(d * d);
+}
+
 __global__ __launch_bounds__(256) void k_lsd_frames(const float* __restrict__ SA, const float* __restrict__ SB, int nb,
                                                      float* __restrict__ per) {
     __shared__ double red[256];
@@ -236,9 +246,7 @@ __global__ __launch_bounds__(256) void k_lsd_frames(const float* __restrict__ SA
     const float* b = SB + f * nb;
     double acc = 0.0;
     for (int k = threadIdx.x; k < nb; k += 256) {
-        const float la = 20.0f * log10f(a[k] + 1e-12f), lb = 20.0f * log10f(b[k] + 1e-12f);
-        const float d = la - lb;
-        acc += (double)(d * d);
+        acc += lsd_bin_term(a[k], b[k]);
     }
     red[threadIdx.x] = acc;
     __syncthreads();
@@ -270,8 +278,9 @@ __device__ __forceinline__ unsigned f2key(float x) {
 __device__ __forceinline__ float key2f(unsigned k) {
     return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
 }
-__global__ __launch_bounds__(1024) void k_order_stats2(const float* __restrict__ v, long long n, long long k0, long long k1,
-                                                        float* __restrict__ out2) {
+// the selection, by one workgroup of 1024 threads; k_order_stats2 and k_pair_lsd_reduce (egr_metrics_pairs) both call it
+__device__ __forceinline__ void order_stats2_block(const float* __restrict__ v, long long n, long long k0, long long k1,
+                                                   float* __restrict__ out2) {
     __shared__ unsigned hist[256];
     __shared__ unsigned s_prefix;
     __shared__ long long s_k;
@@ -303,6 +312,11 @@ __global__ __launch_bounds__(1024) void k_order_stats2(const float* __restrict__
         if (threadIdx.x == 0) out2[which] = key2f(s_prefix);
         __syncthreads();
     }
+}
+
+__global__ __launch_bounds__(1024) void k_order_stats2(const float* __restrict__ v, long long n, long long k0, long long k1,
+                                                        float* __restrict__ out2) {
+    order_stats2_block(v, n, k0, k1, out2);
 }
 
 // SI-SDR terms on the mono downmixes (mean over channels in float32, like the reference's .mean(axis=0); sums in double):
@@ -523,10 +537,11 @@ __global__ __launch_bounds__(256) void k_mono_mean(const float* __restrict__ x, 
 }
 
 // out[f] = mean(mono[f hop .. f hop + blk)^2) in double (the block is cut at n), one workgroup per block
-__global__ __launch_bounds__(256) void k_frame_meansq(const float* __restrict__ x, int C, long long n, long long blk, long long hop,
-                                                      double* __restrict__ out) {
+// block f of one signal, by one workgroup of 256; thread 0 stores.  k_frame_meansq and k_frame_meansq_tracks both call it.
+__device__ __forceinline__ void frame_meansq_block(const float* __restrict__ x, int C, long long n, long long blk, long long hop,
+                                                   long long f, double* __restrict__ dst) {
     __shared__ double red[256];
-    const long long a = (long long)blockIdx.x * hop, b = a + blk < n ? a + blk : n;
+    const long long a = f * hop, b = a + blk < n ? a + blk : n;
     double acc = 0.0;
     for (long long i = a + threadIdx.x; i < b; i += 256) {
         const double m = (double)mono_mean(x, C, n, i);
@@ -538,7 +553,20 @@ __global__ __launch_bounds__(256) void k_frame_meansq(const float* __restrict__ 
         if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
         __syncthreads();
     }
-    if (threadIdx.x == 0) out[blockIdx.x] = red[0] / (double)(b - a);
+    if (threadIdx.x == 0) *dst = red[0] / (double)(b - a);
+}
+
+__global__ __launch_bounds__(256) void k_frame_meansq(const float* __restrict__ x, int C, long long n, long long blk, long long hop,
+                                                      double* __restrict__ out) {
+    frame_meansq_block(x, C, n, blk, hop, (long long)blockIdx.x, out + blockIdx.x);
+}
+
+// the blocks of every clip's K-weighted mono (one channel), one workgroup per (clip, block) found in prefix column `col`; out is flat
+__global__ __launch_bounds__(256) void k_frame_meansq_tracks(const float* __restrict__ mono, const long long* __restrict__ tab, int n_clips,
+                                                             int col, long long blk, long long hop, double* __restrict__ out) {
+    long long f;
+    const long long* e = tab + (size_t)loud_item_of(tab, n_clips, col, (long long)blockIdx.x, &f) * LT_COLS;
+    frame_meansq_block(mono + e[LT_MONO], 1, e[LT_N], blk, hop, f, out + blockIdx.x);
 }
 
 // ---------------------------------------------------------------- evaluation pack loudness meter (egregora_audio_eval_pack.py:132-214)
@@ -546,11 +574,10 @@ __global__ __launch_bounds__(256) void k_frame_meansq(const float* __restrict__ 
 // k_kweight's (same roundings, same order, same restart W samples ahead of the thread's L-sample chunk), the mean is mono_mean's
 // (rows added in order, one division).  CT > 0: CT channels advance together with their states in registers (x read once, mono
 // written once).  CT = 0: any channel count, one channel after the other, the running sum kept in the thread's own stretch of mono.
+// One thread's L-sample chunk starting at s < n; k_kweight_mono and k_kweight_mono_tracks (egr_loudness_tracks) both call it.
 template <int CT>
-__global__ __launch_bounds__(64) void k_kweight_mono(const float* __restrict__ x, int C, long long n, float a1, float kf, int L, int W,
-                                                     float* __restrict__ mono) {
-    const long long s = ((long long)blockIdx.x * 64 + threadIdx.x) * L;
-    if (s >= n) return;
+__device__ __forceinline__ void kweight_mono_chunk(const float* __restrict__ x, int C, long long n, float a1, float kf, long long s, int L,
+                                                   int W, float* __restrict__ mono) {
     long long i0 = s - W - 1;
     if (i0 < 0) i0 = 0;
     const long long e = s + L < n ? s + L : n;
@@ -604,33 +631,73 @@ __global__ __launch_bounds__(64) void k_kweight_mono(const float* __restrict__ x
     }
 }
 
+template <int CT>
+__global__ __launch_bounds__(64) void k_kweight_mono(const float* __restrict__ x, int C, long long n, float a1, float kf, int L, int W,
+                                                     float* __restrict__ mono) {
+    const long long s = ((long long)blockIdx.x * 64 + threadIdx.x) * L;
+    if (s >= n) return;
+    kweight_mono_chunk<CT>(x, C, n, a1, kf, s, L, W, mono);
+}
+
+// tab: LT_COLS int64 per clip (egr_eval_index.h).  Flat thread index over every clip's chunks: a wave's 64 chunks may belong to
+// several clips, each thread looks its own up.
+template <int CT>
+__global__ __launch_bounds__(64) void k_kweight_mono_tracks(const float* __restrict__ x, const long long* __restrict__ tab, int n_clips,
+                                                            long long total_chunks, int C, float a1, float kf, int L, int W,
+                                                            float* __restrict__ mono) {
+    const long long g = (long long)blockIdx.x * 64 + threadIdx.x;
+    if (g >= total_chunks) return;
+    long long j;
+    const long long* e = tab + (size_t)loud_item_of(tab, n_clips, LT_CHUNK0, g, &j) * LT_COLS;
+    kweight_mono_chunk<CT>(x + e[LT_OFF], C, e[LT_N], a1, kf, j * L, L, W, mono + e[LT_MONO]);
+}
+
 // *slot (bits of a non-negative float, zeroed by the call) raised to max_m |y[m]|, y = resample_poly(mono_mean(x), up, 1) with
 // k_resample_poly's per-output accumulation (down = 1) on the channel mean formed on the fly; the up * n samples are never stored.
 // up = 1: y is the channel mean itself (scipy returns a copy, no filter).
-__global__ __launch_bounds__(256) void k_true_peak(const float* __restrict__ x, int C, long long n, int up, const float* __restrict__ h,
-                                                   int half, unsigned* __restrict__ slot) {
+// sample m of the oversampled channel mean; k_true_peak and k_true_peak_tracks both call it
+__device__ __forceinline__ float true_peak_sample(const float* __restrict__ x, int C, long long n, int up, const float* __restrict__ h,
+                                                  int half, long long m) {
+    if (up == 1) return mono_mean(x, C, n, m);
+    const long long hl = 2LL * half;
+    const long long t = m + half;
+    long long k_hi = t / up;
+    if (k_hi > n - 1) k_hi = n - 1;
+    const long long k_lo = t - hl <= 0 ? 0 : (t - hl + up - 1) / up;
+    float acc = 0.f;
+    for (long long k = k_lo; k <= k_hi; ++k) acc = __fadd_rn(acc, __fmul_rn(mono_mean(x, C, n, k), h[t - k * up]));
+    return acc;
+}
+
+// the workgroup's maximum (256 threads) raises *slot; an integer maximum of non-negative float bits: any order gives the same value
+__device__ __forceinline__ void true_peak_commit(float mx, unsigned* __restrict__ slot) {
     __shared__ float red[4];
-    const long long n_out = n * up, hl = 2LL * half;
-    float mx = 0.f;
-    for (long long m = (long long)blockIdx.x * 256 + threadIdx.x; m < n_out; m += (long long)gridDim.x * 256) {
-        float acc;
-        if (up == 1) {
-            acc = mono_mean(x, C, n, m);
-        } else {
-            const long long t = m + half;
-            long long k_hi = t / up;
-            if (k_hi > n - 1) k_hi = n - 1;
-            const long long k_lo = t - hl <= 0 ? 0 : (t - hl + up - 1) / up;
-            acc = 0.f;
-            for (long long k = k_lo; k <= k_hi; ++k) acc = __fadd_rn(acc, __fmul_rn(mono_mean(x, C, n, k), h[t - k * up]));
-        }
-        mx = fmaxf(mx, fabsf(acc));
-    }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
     __syncthreads();
     if (threadIdx.x == 0) atomicMax(slot, __float_as_uint(fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]))));
+}
+
+__global__ __launch_bounds__(256) void k_true_peak(const float* __restrict__ x, int C, long long n, int up, const float* __restrict__ h,
+                                                   int half, unsigned* __restrict__ slot) {
+    const long long n_out = n * up;
+    float mx = 0.f;
+    for (long long m = (long long)blockIdx.x * 256 + threadIdx.x; m < n_out; m += (long long)gridDim.x * 256)
+        mx = fmaxf(mx, fabsf(true_peak_sample(x, C, n, up, h, half, m)));
+    true_peak_commit(mx, slot);
+}
+
+// one workgroup per 256-sample tile of one clip's oversampled signal; slots[clip] as k_true_peak's slot
+__global__ __launch_bounds__(256) void k_true_peak_tracks(const float* __restrict__ x, const long long* __restrict__ tab, int n_clips, int C,
+                                                          int up, const float* __restrict__ h, int half, unsigned* __restrict__ slots) {
+    long long tile;
+    const int c = loud_item_of(tab, n_clips, LT_TILE0, (long long)blockIdx.x, &tile);
+    const long long* e = tab + (size_t)c * LT_COLS;
+    const long long m = tile * LT_TILE + threadIdx.x;
+    float mx = 0.f;
+    if (m < e[LT_N] * up) mx = fmaxf(mx, fabsf(true_peak_sample(x + e[LT_OFF], C, e[LT_N], up, h, half, m)));
+    true_peak_commit(mx, slots + c);
 }
 
 template <int K>
@@ -691,6 +758,230 @@ __global__ __launch_bounds__(256) void k_band_sums(const float* __restrict__ x, 
         v[0] += a * a; v[1] += a; v[2] += s * a; v[3] += b * b; v[4] += b; v[5] += s * b;
     }
     block_add_f64<6>(v, out);
+}
+
+// ---------------------------------------------------------------- many (reference, processed) pairs per call (egr_metrics_pairs)
+// tab: MP_COLS int64 per pair (egr_eval_index.h).  Every grid is flat and equals its work count.  No floating-point atomics: a pair's
+// eight numbers are sums in a fixed order over that pair's own frames and chunks, whatever else the call holds.
+//
+// One workgroup per (pair, frame): side A's frame is transformed and its magnitudes kept in registers (at most PF_MAGS per thread,
+// n_fft = 8192), then side B's in the same two LDS buffers; per[flat frame] as k_lsd_frames forms it from the two magnitude arrays
+// (same bins per thread in the same order, same tree), which here never reach memory.  The tree reuses the transform's LDS.
+constexpr int PF_MAGS = (8192 / 2 + 1 + 255) / 256;
+__global__ __launch_bounds__(256) void k_pair_frames(const float* __restrict__ a, const float* __restrict__ b, const long long* __restrict__ tab,
+                                                     int n_pairs, int n_fft, int hop, const float* __restrict__ window, FftDesc fd,
+                                                     const cplx* __restrict__ tw, const cplx* __restrict__ wsplit, float* __restrict__ per) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int Mh = n_fft / 2;
+    cplx* cur = (cplx*)smem;
+    cplx* alt = cur + Mh;
+    long long f;
+    const long long* e = tab + (size_t)metrics_frame_of(tab, n_pairs, (long long)blockIdx.x, &f) * MP_COLS;
+    const long long n = e[MP_N], s0 = f * hop;
+    stft_frame_fft(a + e[MP_OFF_A], (int)e[MP_CA], e[MP_LD_A], n, s0, Mh, window, fd, tw, cur, alt);
+    float ma[PF_MAGS];
+#pragma unroll
+    for (int j = 0; j < PF_MAGS; ++j) {
+        const int k = threadIdx.x + 256 * j;
+        ma[j] = k <= Mh ? stft_bin_mag(cur, Mh, wsplit, k) : 0.f;
+    }
+    __syncthreads();
+    stft_frame_fft(b + e[MP_OFF_B], (int)e[MP_CB], e[MP_LD_B], n, s0, Mh, window, fd, tw, cur, alt);
+    double acc = 0.0;
+#pragma unroll
+    for (int j = 0; j < PF_MAGS; ++j) {
+        const int k = threadIdx.x + 256 * j;
+        if (k <= Mh) acc += lsd_bin_term(ma[j], stft_bin_mag(cur, Mh, wsplit, k));
+    }
+    __syncthreads();
+    double* red = (double*)smem;
+    red[threadIdx.x] = acc;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) per[blockIdx.x] = sqrtf((float)(red[0] / (Mh + 1)) + 1e-12f);
+}
+
+// One workgroup per pair: out8[0] = sum of the pair's per[] in double (thread i takes frames i, i + 1024, ...; a tree), out8[1], out8[2] =
+// the order statistics MP_KLO, MP_KHI of per[] (k_order_stats2's selection), out8[3] = frames.
+__global__ __launch_bounds__(1024) void k_pair_lsd_reduce(const float* __restrict__ per, const long long* __restrict__ tab,
+                                                          double* __restrict__ out8) {
+    __shared__ double red[1024];
+    __shared__ float o2[2];
+    const long long* e = tab + (size_t)blockIdx.x * MP_COLS;
+    const float* v = per + e[MP_FRAME0];
+    const long long n = e[MP_FRAMES];
+    double acc = 0.0;
+    for (long long i = threadIdx.x; i < n; i += 1024) acc += (double)v[i];
+    red[threadIdx.x] = acc;
+    __syncthreads();
+    for (int o = 512; o > 0; o >>= 1) {
+        if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+        __syncthreads();
+    }
+    order_stats2_block(v, n, e[MP_KLO], e[MP_KHI], o2);
+    if (threadIdx.x == 0) {
+        double* o = out8 + (size_t)blockIdx.x * 8;
+        o[0] = red[0]; o[1] = (double)o2[0]; o[2] = (double)o2[1]; o[3] = (double)n;
+    }
+}
+
+// One workgroup per chunk of EGR_METRICS_CHUNK samples of one pair (the last chunk of a pair is short; none spans two pairs):
+//   MODE 0: part = (<s_hat, s>, <s, s>)       MODE 1: alpha = out8[4] / (out8[5] + 1e-20), part = (|alpha s|^2, |s_hat - alpha s|^2)
+// on the mono downmixes (mono_mean), s = side A, s_hat = side B; k_sisdr's terms, summed per chunk.
+template <int MODE>
+__global__ __launch_bounds__(256) void k_pair_sisdr_part(const float* __restrict__ a, const float* __restrict__ b,
+                                                         const long long* __restrict__ tab, int n_pairs, const double* __restrict__ out8,
+                                                         double2* __restrict__ part) {
+    __shared__ double r0[256], r1[256];
+    long long first, len;
+    const int p = metrics_chunk_of(tab, n_pairs, (long long)blockIdx.x, &first, &len);
+    const long long* e = tab + (size_t)p * MP_COLS;
+    const float* s = a + e[MP_OFF_A];
+    const float* sh = b + e[MP_OFF_B];
+    const int cs = (int)e[MP_CA], csh = (int)e[MP_CB];
+    const long long lds = e[MP_LD_A], ldh = e[MP_LD_B];
+    const double alpha = MODE ? out8[(size_t)p * 8 + 4] / (out8[(size_t)p * 8 + 5] + 1e-20) : 0.0;
+    double a0 = 0.0, a1 = 0.0;
+    for (long long i = first + threadIdx.x; i < first + len; i += 256) {
+        const double x = (double)mono_mean(s, cs, lds, i), y = (double)mono_mean(sh, csh, ldh, i);
+        if (MODE == 0) {
+            a0 += y * x;
+            a1 += x * x;
+        } else {
+            const double t = alpha * x, d = y - t;
+            a0 += t * t;
+            a1 += d * d;
+        }
+    }
+    r0[threadIdx.x] = a0;
+    r1[threadIdx.x] = a1;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (threadIdx.x < o) { r0[threadIdx.x] += r0[threadIdx.x + o]; r1[threadIdx.x] += r1[threadIdx.x + o]; }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) part[blockIdx.x] = make_double2(r0[0], r1[0]);
+}
+
+// One workgroup per pair: the pair's chunk sums added in a fixed order (thread i takes chunks i, i + 256, ... ascending; a tree) into
+// out8[4 + 2 mode], out8[5 + 2 mode].
+__global__ __launch_bounds__(256) void k_pair_sisdr_reduce(const double2* __restrict__ part, const long long* __restrict__ tab, int mode,
+                                                           double* __restrict__ out8) {
+    __shared__ double r0[256], r1[256];
+    const long long* e = tab + (size_t)blockIdx.x * MP_COLS;
+    const double2* v = part + e[MP_CHUNK0];
+    const long long nc = metrics_chunks(e[MP_N]);
+    double a0 = 0.0, a1 = 0.0;
+    for (long long i = threadIdx.x; i < nc; i += 256) { a0 += v[i].x; a1 += v[i].y; }
+    r0[threadIdx.x] = a0;
+    r1[threadIdx.x] = a1;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (threadIdx.x < o) { r0[threadIdx.x] += r0[threadIdx.x + o]; r1[threadIdx.x] += r1[threadIdx.x + o]; }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        out8[(size_t)blockIdx.x * 8 + 4 + 2 * mode] = r0[0];
+        out8[(size_t)blockIdx.x * 8 + 5 + 2 * mode] = r1[0];
+    }
+}
+
+// The restart rule of the K-weighting kernels, stated once: a thread restarts the recurrence W samples ahead of its L-sample chunk,
+// k^W < 6e-12 (below float32 resolution of the state), W at least 64, L = W / 3 rounded up.  egr_kweight, egr_loudness_frames and
+// egr_loudness_tracks all take their chunking from here, which is what keeps their results bit-equal.
+static inline void kweight_chunking(float k, int* L, int* W) {
+    int w = (int)ceil(26.0 / -log((double)k));
+    if (w < 64) w = 64;
+    *W = w;
+    *L = (w + 2) / 3;
+}
+
+static std::mutex g_eval_mu;
+static std::map<int, TableStage> g_eval_stage;      // device -> pinned staging of the tables (under g_eval_mu)
+static inline size_t eval_align(size_t b) { return (b + 255) & ~(size_t)255; }
+
+// the table goes up in one asynchronous copy from pinned memory
+static int eval_upload(const std::vector<long long>& tab, void* dst, hipStream_t st) {
+    int dev = 0;
+    EGR_HIP(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> lk(g_eval_mu);
+    TableStage& stage = g_eval_stage[dev];
+    const size_t bytes = tab.size() * sizeof(long long);
+    const int rc = stage.reserve(bytes);
+    if (rc) return rc;
+    memcpy(stage.p, tab.data(), bytes);
+    EGR_HIP(hipMemcpyAsync(dst, stage.p, bytes, hipMemcpyHostToDevice, st));
+    EGR_HIP(hipEventRecord(stage.copied, st));
+    return EGR_OK;
+}
+
+static const char* eval_why(int r) {
+    return r == EVAL_SHORT ? "n < 1" : r == EVAL_BAD_ROW ? "channels outside 1 .. 65535 or a row stride below n"
+         : r == EVAL_OFFSET ? "an offset, stride or length is negative or past what the index type holds"
+                            : "the running total of frames, chunks, blocks or tiles leaves one grid (workgroups x threads < 2^32)";
+}
+
+struct MetricsPlan {
+    std::vector<long long> tab;
+    long long frames = 0, chunks = 0;
+    size_t per_off = 0, part_off = 0, total = 0;
+    int launches = 0;
+};
+
+// every refusal of egr_metrics_pairs that needs no pointer: host arithmetic only
+static int metrics_plan(const int64_t* pairs, int n_pairs, int n_fft, int hop, int flags, MetricsPlan* P) {
+    EGR_CHECK(pairs && n_pairs >= 1, EGR_ERR_ARG, "egr_metrics_pairs: no pairs");
+    EGR_CHECK(n_pairs <= EVAL_MAX_PAIRS, EGR_ERR_UNSUPPORTED, "egr_metrics_pairs: n_pairs=%d is above %lld, one 1024-thread workgroup per pair",
+              n_pairs, EVAL_MAX_PAIRS);
+    EGR_CHECK(flags >= 1 && flags <= 3, EGR_ERR_ARG, "egr_metrics_pairs: flags=%d asks for neither LSD (1) nor SI-SDR (2)", flags);
+    EGR_CHECK(hop >= 1, EGR_ERR_ARG, "egr_metrics_pairs: hop=%d", hop);
+    EGR_CHECK(n_fft >= 2 && (n_fft % 2) == 0 && n_fft <= 8192, EGR_ERR_UNSUPPORTED, "egr_metrics_pairs: n_fft=%d must be even and <= 8192",
+              n_fft);
+    FftDesc fd;
+    EGR_CHECK(make_schedule(n_fft / 2, &fd, 127), EGR_ERR_UNSUPPORTED, "egr_metrics_pairs: n_fft=%d: n_fft/2 has a prime factor above 127",
+              n_fft);
+    P->tab.assign((size_t)n_pairs * MP_COLS, 0);
+    for (int p = 0; p < n_pairs; ++p) {
+        const int r = metrics_fill((const long long*)pairs + (size_t)p * MP_IN_COLS, n_fft, hop, &P->frames, &P->chunks,
+                                   P->tab.data() + (size_t)p * MP_COLS);
+        EGR_CHECK(r == EVAL_OK, r == EVAL_TOTAL ? EGR_ERR_UNSUPPORTED : EGR_ERR_ARG, "egr_metrics_pairs: pair %d: %s", p, eval_why(r));
+    }
+    P->per_off = eval_align(P->tab.size() * sizeof(long long));
+    P->part_off = P->per_off + eval_align((flags & 1) ? (size_t)P->frames * sizeof(float) : 0);
+    P->total = P->part_off + eval_align((flags & 2) ? (size_t)P->chunks * sizeof(double2) : 0);
+    P->launches = ((flags & 1) ? 2 : 0) + ((flags & 2) ? 4 : 0);
+    return EGR_OK;
+}
+
+struct LoudPlan {
+    std::vector<long long> tab;
+    LoudTotals t = {0, 0, 0, 0, 0};
+    int L = 0, W = 0;
+    size_t mono_off = 0, total = 0;
+    int launches = 0;
+};
+
+static int loud_plan(const int64_t* clips, int n_clips, int channels, float k, int64_t blk_a, int64_t hop_a, int64_t blk_b, int64_t hop_b,
+                     int up, LoudPlan* P) {
+    EGR_CHECK(clips && n_clips >= 1, EGR_ERR_ARG, "egr_loudness_tracks: no clips");
+    EGR_CHECK(n_clips <= EVAL_MAX_GRID_256, EGR_ERR_UNSUPPORTED, "egr_loudness_tracks: n_clips=%d is above %lld", n_clips, EVAL_MAX_GRID_256);
+    EGR_CHECK(channels >= 1 && channels <= 65535 && k > 0.f && k < 1.f, EGR_ERR_ARG, "egr_loudness_tracks: channels=%d, k=%g", channels, k);
+    EGR_CHECK(blk_a >= 1 && hop_a >= 1 && blk_b >= 0 && (blk_b == 0 || hop_b >= 1) && up >= 0 && up <= 64, EGR_ERR_ARG,
+              "egr_loudness_tracks: bad block family or oversampling factor");
+    kweight_chunking(k, &P->L, &P->W);
+    P->tab.assign((size_t)n_clips * LT_COLS, 0);
+    for (int c = 0; c < n_clips; ++c) {
+        const int r = loud_fill((const long long*)clips + (size_t)c * LT_IN_COLS, channels, P->L, blk_a, hop_a, blk_b, hop_b, up, &P->t,
+                                P->tab.data() + (size_t)c * LT_COLS);
+        EGR_CHECK(r == EVAL_OK, r == EVAL_TOTAL ? EGR_ERR_UNSUPPORTED : EGR_ERR_ARG, "egr_loudness_tracks: clip %d: %s", c, eval_why(r));
+    }
+    P->mono_off = eval_align(P->tab.size() * sizeof(long long));
+    P->total = P->mono_off + eval_align((size_t)P->t.mono * sizeof(float));
+    P->launches = 2 + (blk_b ? 1 : 0) + (up ? 1 : 0);
+    return EGR_OK;
 }
 
 static inline int grid_for(long long n) {
@@ -926,9 +1217,8 @@ extern "C" int egr_shift_fir(const float* x, int channels, int64_t n_in, int64_t
 
 extern "C" int egr_kweight(const float* x, int channels, int64_t n, float one_minus_k, float k, float* y, void* stream) {
     EGR_CHECK(x && y && channels >= 1 && channels <= 65535 && n >= 1 && k > 0.f && k < 1.f, EGR_ERR_ARG, "bad argument");
-    int W = (int)ceil(26.0 / -log((double)k));       // k^W < 6e-12
-    if (W < 64) W = 64;
-    const int L = (W + 2) / 3;
+    int L, W;
+    kweight_chunking(k, &L, &W);
     const long long chunks = (n + L - 1) / L;
     hipLaunchKernelGGL(k_kweight, dim3((unsigned)((chunks + 63) / 64), channels), dim3(64), 0, (hipStream_t)stream, x, (long long)n,
                        one_minus_k, k, L, W, y);
@@ -962,9 +1252,8 @@ extern "C" int egr_loudness_frames(const float* x, int channels, int64_t n, floa
     EGR_CHECK(frames_b == 0 || (out_b && blk_b >= 1 && hop_b >= 1 && frames_b >= 1 && frames_b < (1LL << 31) && (frames_b - 1) * hop_b < n),
               EGR_ERR_ARG, "bad second block family");
     hipStream_t st = (hipStream_t)stream;
-    int W = (int)ceil(26.0 / -log((double)k));       // the restart rule of egr_kweight: k^W < 6e-12
-    if (W < 64) W = 64;
-    const int L = (W + 2) / 3;
+    int L, W;
+    kweight_chunking(k, &L, &W);
     const long long chunks = (n + L - 1) / L;
     const dim3 grid((unsigned)((chunks + 63) / 64));
     const long long nn = (long long)n;
@@ -1022,6 +1311,120 @@ extern "C" int egr_band_sums(const float* x, const float* y, int64_t n, double* 
     hipStream_t st = (hipStream_t)stream;
     EGR_HIP(hipMemsetAsync(out6, 0, 6 * sizeof(double), st));
     hipLaunchKernelGGL(k_band_sums, dim3(grid_for(n) > 1024 ? 1024 : grid_for(n)), dim3(256), 0, st, x, y, (long long)n, out6);
+    EGR_HIP(hipGetLastError());
+    return EGR_OK;
+}
+
+extern "C" size_t egr_metrics_pairs_workspace_bytes(const int64_t* pairs, int n_pairs, int n_fft, int hop, int flags) {
+    MetricsPlan P;
+    if (metrics_plan(pairs, n_pairs, n_fft, hop, flags, &P) != EGR_OK) return 0;
+    return P.total;
+}
+
+extern "C" int egr_metrics_pairs(const float* a, const float* b, const int64_t* pairs, int n_pairs, int n_fft, int hop, int flags,
+                                 const float* window, double* out8, float* per_out, void* ws, size_t ws_bytes, int* launches,
+                                 void* stream) {
+    MetricsPlan P;
+    int rc = metrics_plan(pairs, n_pairs, n_fft, hop, flags, &P);
+    if (rc) return rc;
+    EGR_CHECK(a && b && out8 && ws && ((flags & 1) == 0 || window), EGR_ERR_ARG, "egr_metrics_pairs: null pointer");
+    EGR_CHECK(ws_bytes >= P.total, EGR_ERR_ARG, "egr_metrics_pairs: workspace of %zu bytes, %zu needed", ws_bytes, P.total);
+    EGR_CHECK(((uintptr_t)ws & 15) == 0 && ((uintptr_t)out8 & 7) == 0, EGR_ERR_ARG,
+              "egr_metrics_pairs: the workspace must be 16-byte aligned (int64 table, double2 partial sums), out8 8-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    char* base = (char*)ws;
+    const long long* tab = (const long long*)base;
+    StftTables t;
+    if (flags & 1) {
+        rc = stft_tables(n_fft, &t);
+        if (rc) return rc;
+    }
+    rc = eval_upload(P.tab, base, st);
+    if (rc) return rc;
+    if (launches) *launches = P.launches;
+    if (flags & 1) {
+        float* per = per_out ? per_out : (float*)(base + P.per_off);
+        size_t lds = (size_t)2 * (n_fft / 2) * sizeof(float2);
+        if (lds < 256 * sizeof(double)) lds = 256 * sizeof(double);          // the tree of the bin sums reuses the transform's buffers
+        hipLaunchKernelGGL(k_pair_frames, dim3((unsigned)P.frames), dim3(256), lds, st, a, b, tab, n_pairs, n_fft, hop, window, t.fd, t.tw,
+                           t.wsplit, per);
+        EGR_HIP(hipGetLastError());
+        hipLaunchKernelGGL(k_pair_lsd_reduce, dim3((unsigned)n_pairs), dim3(1024), 0, st, (const float*)per, tab, out8);
+        EGR_HIP(hipGetLastError());
+    }
+    if (flags & 2) {
+        double2* part = (double2*)(base + P.part_off);
+        hipLaunchKernelGGL(k_pair_sisdr_part<0>, dim3((unsigned)P.chunks), dim3(256), 0, st, a, b, tab, n_pairs, (const double*)out8, part);
+        EGR_HIP(hipGetLastError());
+        hipLaunchKernelGGL(k_pair_sisdr_reduce, dim3((unsigned)n_pairs), dim3(256), 0, st, (const double2*)part, tab, 0, out8);
+        EGR_HIP(hipGetLastError());
+        hipLaunchKernelGGL(k_pair_sisdr_part<1>, dim3((unsigned)P.chunks), dim3(256), 0, st, a, b, tab, n_pairs, (const double*)out8, part);
+        EGR_HIP(hipGetLastError());
+        hipLaunchKernelGGL(k_pair_sisdr_reduce, dim3((unsigned)n_pairs), dim3(256), 0, st, (const double2*)part, tab, 1, out8);
+    }
+    EGR_HIP(hipGetLastError());
+    return EGR_OK;
+}
+
+extern "C" int64_t egr_metrics_pairs_frames(const int64_t* pairs, int n_pairs, int n_fft, int hop) {
+    MetricsPlan P;
+    if (metrics_plan(pairs, n_pairs, n_fft, hop, 1, &P) != EGR_OK) return 0;
+    return P.frames;
+}
+
+extern "C" int egr_kweight_chunking(float k, int* chunk, int* restart) {
+    EGR_CHECK(chunk && restart && k > 0.f && k < 1.f, EGR_ERR_ARG, "egr_kweight_chunking: k=%g", k);
+    kweight_chunking(k, chunk, restart);
+    return EGR_OK;
+}
+
+extern "C" size_t egr_loudness_tracks_workspace_bytes(const int64_t* clips, int n_clips, int channels, float k, int64_t blk_a, int64_t hop_a,
+                                                      int64_t blk_b, int64_t hop_b, int up) {
+    LoudPlan P;
+    if (loud_plan(clips, n_clips, channels, k, blk_a, hop_a, blk_b, hop_b, up, &P) != EGR_OK) return 0;
+    return P.total;
+}
+
+extern "C" int egr_loudness_tracks(const float* x, const int64_t* clips, int n_clips, int channels, float one_minus_k, float k, int64_t blk_a,
+                                   int64_t hop_a, int64_t blk_b, int64_t hop_b, int up, const float* h, int half, double* out, void* ws,
+                                   size_t ws_bytes, int* launches, void* stream) {
+    LoudPlan P;
+    int rc = loud_plan(clips, n_clips, channels, k, blk_a, hop_a, blk_b, hop_b, up, &P);
+    if (rc) return rc;
+    EGR_CHECK(x && out && ws && half >= 0 && (up <= 1 || h), EGR_ERR_ARG, "egr_loudness_tracks: null pointer");
+    EGR_CHECK(ws_bytes >= P.total, EGR_ERR_ARG, "egr_loudness_tracks: workspace of %zu bytes, %zu needed", ws_bytes, P.total);
+    EGR_CHECK(((uintptr_t)ws & 7) == 0 && ((uintptr_t)out & 7) == 0, EGR_ERR_ARG,
+              "egr_loudness_tracks: the workspace (int64 table) and out (doubles) must be 8-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    char* base = (char*)ws;
+    const long long* tab = (const long long*)base;
+    float* mono = (float*)(base + P.mono_off);
+    rc = eval_upload(P.tab, base, st);
+    if (rc) return rc;
+    if (launches) *launches = P.launches;
+    const dim3 grid((unsigned)((P.t.chunks + 63) / 64));
+#define EGR_KW_TRACKS(CT) \
+    hipLaunchKernelGGL(k_kweight_mono_tracks<CT>, grid, dim3(64), 0, st, x, tab, n_clips, P.t.chunks, channels, one_minus_k, k, P.L, P.W, mono)
+    switch (channels) {
+    case 1: EGR_KW_TRACKS(1); break;
+    case 2: EGR_KW_TRACKS(2); break;
+    case 3: EGR_KW_TRACKS(3); break;
+    case 4: EGR_KW_TRACKS(4); break;
+    default: EGR_KW_TRACKS(0); break;
+    }
+#undef EGR_KW_TRACKS
+    EGR_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_frame_meansq_tracks, dim3((unsigned)P.t.fa), dim3(256), 0, st, (const float*)mono, tab, n_clips, (int)LT_FA0,
+                       (long long)blk_a, (long long)hop_a, out);
+    EGR_HIP(hipGetLastError());
+    if (blk_b)
+        hipLaunchKernelGGL(k_frame_meansq_tracks, dim3((unsigned)P.t.fb), dim3(256), 0, st, (const float*)mono, tab, n_clips, (int)LT_FB0,
+                           (long long)blk_b, (long long)hop_b, out + P.t.fa);
+    if (up) {
+        unsigned* slots = (unsigned*)(out + P.t.fa + P.t.fb);
+        EGR_HIP(hipMemsetAsync(slots, 0, (size_t)n_clips * sizeof(unsigned), st));
+        hipLaunchKernelGGL(k_true_peak_tracks, dim3((unsigned)P.t.tiles), dim3(256), 0, st, x, tab, n_clips, channels, up, h, half, slots);
+    }
     EGR_HIP(hipGetLastError());
     return EGR_OK;
 }

@@ -114,6 +114,81 @@ def _stft_frames(x: torch.Tensor, n_fft: int, hop: int) -> torch.Tensor:
     return stft_mag(x, n_fft, hop).t()
 
 
+def lsd_ranks(frames: int):
+    """(position, lower rank, upper rank) of numpy's linear 95th percentile over `frames` values."""
+    pos = 0.95 * (frames - 1)                       # numpy percentile, method="linear"
+    lo = int(np.floor(pos))
+    return pos, lo, min(lo + 1, frames - 1)
+
+
+def lsd_finish(total: float, v_lo: float, v_hi: float, frames: int):
+    """The host's part of the LSD: (mean, p95) from the double sum of the per-frame values and the two order statistics.  lsd and
+    eval_many.metrics_many both end here."""
+    pos, lo, _ = lsd_ranks(frames)
+    t = pos - lo
+    p95 = v_hi - (v_hi - v_lo) * (1.0 - t) if t >= 0.5 else v_lo + (v_hi - v_lo) * t
+    return float(np.float32(total / frames)), float(np.float32(p95))
+
+
+def si_sdr_finish(tt: float, ee: float) -> float:
+    """The host's part of the SI-SDR: dB from |alpha s|^2 and |s_hat - alpha s|^2.  si_sdr and eval_many.metrics_many both end here."""
+    return float(10.0 * np.log10((tt + 1e-20) / (ee + 1e-20)))
+
+
+METRICS_LSD, METRICS_SI_SDR = 1, 2          # egr_metrics_pairs flags
+METRICS_CHUNK = 4096                        # EGR_METRICS_CHUNK (csrc/egr_eval_index.h)
+MAX_GRID_256 = (2 ** 32 - 1) // 256         # EVAL_MAX_GRID_256: frames, chunks, blocks or peak tiles one call holds (one workgroup each)
+MAX_PAIRS = (2 ** 32 - 1) // 1024           # EVAL_MAX_PAIRS
+
+
+def pairs_table(rows):
+    """[(offset a, channels a, stride a, offset b, channels b, stride b, n)] -> the host table of egr_metrics_pairs."""
+    import ctypes as C
+    return (C.c_int64 * (7 * len(rows)))(*[int(v) for r in rows for v in r])
+
+
+def metrics_pairs_workspace_bytes(rows, n_fft: int, hop: int, flags: int) -> int:
+    """Host only; 0 for a table the call refuses (native.last_error() says why)."""
+    return int(native.lib().egr_metrics_pairs_workspace_bytes(pairs_table(rows), len(rows), int(n_fft), int(hop), int(flags)))
+
+
+def metrics_pairs(a, b, rows, n_fft: int = 2048, hop: int = 512, flags: int = 3, want_per: bool = False, device=None):
+    """Many pairs in one egr_metrics_pairs call and one device -> host copy.  a, b: flat float32 CUDA buffers, or device addresses
+    (int, with `device`) that the offsets of rows count from; rows as pairs_table.
+    -> (out8 float64 host array [n_pairs, 8], per float32 host array of all pairs' per-frame values or None, kernel launches)."""
+    import ctypes as C
+
+    def addr(x):
+        if isinstance(x, int):
+            return C.c_void_p(x)
+        _chk(x, "metrics_pairs")
+        return native.ptr(x)
+    pa, pb = addr(a), addr(b)
+    if device is None:
+        if isinstance(a, int):
+            raise RuntimeError("metrics_pairs: `device` is required when a and b are device addresses")
+        device = a.device
+    n_pairs = len(rows)
+    tab = pairs_table(rows)
+    L = native.lib()
+    need = int(L.egr_metrics_pairs_workspace_bytes(tab, n_pairs, int(n_fft), int(hop), int(flags)))
+    if need == 0:
+        raise RuntimeError(f"egr_metrics_pairs refused: {native.last_error()}")
+    frames = int(L.egr_metrics_pairs_frames(tab, n_pairs, int(n_fft), int(hop))) if want_per and (flags & METRICS_LSD) else 0
+    buf = torch.zeros((8 * n_pairs + (frames + 1) // 2,), dtype=torch.float64, device=device)      # out8, then per[] (float32)
+    ws = torch.empty((need,), dtype=torch.uint8, device=device)
+    w = hann_window(int(n_fft), device) if flags & METRICS_LSD else None
+    launches = C.c_int(0)
+    native.check(L.egr_metrics_pairs(pa, pb, tab, n_pairs, int(n_fft), int(hop), int(flags),
+                                     native.ptr(w) if w is not None else None, native.ptr(buf),
+                                     C.c_void_p(buf.data_ptr() + 64 * n_pairs) if frames else None, native.ptr(ws), need,
+                                     C.byref(launches), native.stream_ptr()), "egr_metrics_pairs")
+    host = buf.cpu()
+    out8 = host[:8 * n_pairs].numpy().reshape(n_pairs, 8)
+    per = host[8 * n_pairs:].view(torch.float32)[:frames].numpy() if frames else None
+    return out8, per, launches.value
+
+
 def lsd(a: torch.Tensor, b: torch.Tensor, n_fft: int = 2048, hop: int = 512):
     """(mean, p95) log-spectral distance in dB between two [C,T] / [T] CUDA signals of equal length, as the reference's
     _stft_mag + _lsd (egregora_audio_eval_pack.py:389-411): everything per sample / per bin runs on the device; the host
@@ -127,15 +202,11 @@ def lsd(a: torch.Tensor, b: torch.Tensor, n_fft: int = 2048, hop: int = 512):
                  "egr_lsd_frames")
     tot = torch.empty((1,), dtype=torch.float64, device=SA.device)
     native.check(L.egr_sum_f64(native.ptr(per), frames, native.ptr(tot), native.stream_ptr()), "egr_sum_f64")
-    pos = 0.95 * (frames - 1)                       # numpy percentile, method="linear"
-    lo = int(np.floor(pos))
-    hi = min(lo + 1, frames - 1)
+    _, lo, hi = lsd_ranks(frames)
     o2 = torch.empty((2,), dtype=torch.float32, device=SA.device)
     native.check(L.egr_order_stats2(native.ptr(per), frames, lo, hi, native.ptr(o2), native.stream_ptr()), "egr_order_stats2")
     v_lo, v_hi = (float(v) for v in o2.cpu())
-    t = pos - lo
-    p95 = v_hi - (v_hi - v_lo) * (1.0 - t) if t >= 0.5 else v_lo + (v_hi - v_lo) * t
-    return float(np.float32(float(tot.cpu()) / frames)), float(np.float32(p95))
+    return lsd_finish(float(tot.cpu()), v_lo, v_hi, frames)
 
 
 def si_sdr(s: torch.Tensor, s_hat: torch.Tensor) -> float:
@@ -152,7 +223,7 @@ def si_sdr(s: torch.Tensor, s_hat: torch.Tensor) -> float:
     native.check(native.lib().egr_si_sdr_terms(native.ptr(s), s.shape[0], s.shape[1], native.ptr(s_hat), s_hat.shape[0],
                                                 s_hat.shape[1], n, native.ptr(out), native.stream_ptr()), "egr_si_sdr_terms")
     _, _, tt, ee = (float(v) for v in out.cpu())
-    return float(10.0 * np.log10((tt + 1e-20) / (ee + 1e-20)))
+    return si_sdr_finish(tt, ee)
 
 
 def resample_linear(x_ct: torch.Tensor, n_out: int) -> torch.Tensor:

@@ -93,6 +93,13 @@ SIGNATURES = {
     "egr_sum_f64": (_i, [_vp, _i64, _vp, _vp]),
     "egr_order_stats2": (_i, [_vp, _i64, _i64, _i64, _vp, _vp]),
     "egr_si_sdr_terms": (_i, [_vp, _i, _i64, _vp, _i, _i64, _i64, _vp, _vp]),
+    "egr_metrics_pairs_workspace_bytes": (C.c_size_t, [C.POINTER(_i64), _i, _i, _i, _i]),
+    "egr_metrics_pairs_frames": (_i64, [C.POINTER(_i64), _i, _i, _i]),
+    "egr_kweight_chunking": (_i, [_f, C.POINTER(_i), C.POINTER(_i)]),
+    "egr_metrics_pairs": (_i, [_vp, _vp, C.POINTER(_i64), _i, _i, _i, _i, _vp, _vp, _vp, _vp, C.c_size_t, C.POINTER(_i), _vp]),
+    "egr_loudness_tracks_workspace_bytes": (C.c_size_t, [C.POINTER(_i64), _i, _i, _f, _i64, _i64, _i64, _i64, _i]),
+    "egr_loudness_tracks": (_i, [_vp, C.POINTER(_i64), _i, _i, _f, _f, _i64, _i64, _i64, _i64, _i, _vp, _i, _vp, _vp, C.c_size_t,
+                                 C.POINTER(_i), _vp]),
     "egr_wola_stitch": (_i, [_vp, _i, _i, _i64, _i64, _i64, _i64, _vp, _vp, _vp]),
     "egr_chunk_gather": (_i, [_vp, _i, _i64, _i64, _i64, _i, _i, _vp, _vp]),
     "egr_resample_poly": (_i, [_vp, _i, _i64, _i, _i, _vp, _i, _vp, _i64, _vp]),

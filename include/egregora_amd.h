@@ -388,6 +388,56 @@ int egr_order_stats2(const float* v, int64_t n, int64_t k_lo, int64_t k_hi, floa
 int egr_si_sdr_terms(const float* s, int cs, int64_t stride_s, const float* s_hat, int csh, int64_t stride_sh, int64_t n,
                      double* out4, void* stream);
 
+/* Many (reference, processed) pairs scored in one call: what egr_stft_mag x 2 + egr_lsd_frames + egr_sum_f64 +
+ * egr_order_stats2 + egr_si_sdr_terms compute for one pair, for n_pairs pairs in a constant number of launches.
+ *   a, b   : flat device float buffers holding the references and the processed signals
+ *   pairs  : HOST table, 7 int64 per pair: offset of the reference in a, its channels, its row stride; offset of the processed
+ *            signal in b, its channels, its row stride; n = min(len_a, len_b) >= 1 (samples per row that are scored)
+ *   flags  : 1 = LSD terms, 2 = SI-SDR terms, 3 = both
+ *   window : device float[n_fft] as for egr_stft_mag (may be NULL without flag 1)
+ *   out8   : device double [n_pairs][8] = {sum of per[], the two order statistics of numpy's linear 95th percentile of per[] (ranks
+ *            floor(0.95 (frames - 1)) and the next, capped), frames, <s_hat,s>, <s,s>, |alpha s|^2, |s_hat - alpha s|^2}; per[] are the
+ *            pair's frames = 1 + max(0, (n - n_fft) / hop) values of egr_lsd_frames.  Entries of a term that was not asked for are not written.
+ *   per_out: NULL, or device float[sum of frames]: the pairs' per[] back to back in table order
+ *   ws     : egr_metrics_pairs_workspace_bytes bytes (device); *launches (may be NULL) receives the kernel launches of the call:
+ *            2 for LSD, 4 for SI-SDR, 6 for both, whatever n_pairs is
+ * per[] and the order statistics have the bits of the single calls; the sums are formed without floating-point atomics in a fixed
+ * order over the pair's own frames and EGR_METRICS_CHUNK = 4096-sample chunks, so a pair's eight numbers do not depend on the other pairs,
+ * on their order or on the run.  Every grid equals its work count and HIP launches no grid of 2^32 work-items or more: the frames of all
+ * pairs together, and their chunks, stay at or below 2^24 - 1 (256-thread workgroups), n_pairs at or below 2^22 - 1 (1024 threads).
+ * Refused before any allocation, copy or launch, naming the pair where one is at fault: EGR_ERR_ARG for n_pairs < 1, a null pointer,
+ * flags outside 1..3, hop < 1, n < 1, channels outside 1..65535, a stride below n, a negative offset or one past 2^60, a workspace that
+ * is too small; EGR_ERR_UNSUPPORTED for n_fft odd, above 8192 or with a prime factor of n_fft / 2 above 127, and for frame or chunk
+ * totals above 2^24 - 1 or n_pairs above 2^22 - 1.  ws must be 16-byte aligned, out8 8-byte aligned (EGR_ERR_ARG).
+ * egr_metrics_pairs_frames (host only) returns the sum of the pairs' frames, the length of per_out, or 0 for a refused table.
+ * egr_metrics_pairs_workspace_bytes (host only) returns 0 for what the call refuses, with the reason in
+ * egr_last_error.  Only enqueues work on `stream` (the table goes up in one asynchronous copy). */
+size_t egr_metrics_pairs_workspace_bytes(const int64_t* pairs, int n_pairs, int n_fft, int hop, int flags);
+int64_t egr_metrics_pairs_frames(const int64_t* pairs, int n_pairs, int n_fft, int hop);
+int egr_metrics_pairs(const float* a, const float* b, const int64_t* pairs, int n_pairs, int n_fft, int hop, int flags,
+                      const float* window, double* out8, float* per_out, void* ws, size_t ws_bytes, int* launches, void* stream);
+
+/* The clips of one (sample rate, channel count) group through the loudness meter in one call: per clip what egr_loudness_frames and
+ * egr_true_peak compute, bit for bit (the single calls hold no floating-point atomics; the peak is an integer maximum).
+ *   x      : flat device float buffer; clips: HOST table, 2 int64 per clip: offset of the clip's [channels][n] block in x, n >= 1
+ *   blk_b  : 0 skips the second block family; up: 0 skips the true peak, 1 takes max |mono|, else h / half as for egr_true_peak
+ *   out    : device doubles: every clip's frames_a = 1 + max(0, (n - blk_a) / hop_a) values back to back in table order, then every
+ *            clip's frames_b values, then (up >= 1) n_clips 4-byte float peaks
+ *   ws     : egr_loudness_tracks_workspace_bytes bytes (device); *launches (may be NULL): 2, plus 1 with blk_b, plus 1 with up
+ * Refused before any allocation, copy or launch, naming the clip: EGR_ERR_ARG for n_clips < 1, a null pointer, channels outside
+ * 1..65535, k outside (0, 1), a block or hop < 1, up outside 0..64, n < 1, a bad offset, a small workspace; EGR_ERR_UNSUPPORTED when the
+ * blocks of either family or the 256-sample peak tiles of all clips together exceed 2^24 - 1 (256-thread workgroups, no grid of 2^32
+ * work-items or more), or the thread chunks 64 (2^26 - 1).  ws and out must be 8-byte aligned (EGR_ERR_ARG).  The workspace entry
+ * point is host only and returns 0 for what the call refuses.  Only enqueues work on `stream`.
+ * egr_kweight_chunking (host only): the chunk length L and the restart W that egr_kweight, egr_loudness_frames and egr_loudness_tracks
+ * derive from k (W = ceil(26 / -ln k), at least 64; L = ceil(W / 3)): thread t of the K-weighting kernels owns samples [t L, t L + L). */
+int egr_kweight_chunking(float k, int* chunk, int* restart);
+size_t egr_loudness_tracks_workspace_bytes(const int64_t* clips, int n_clips, int channels, float k, int64_t blk_a, int64_t hop_a,
+                                           int64_t blk_b, int64_t hop_b, int up);
+int egr_loudness_tracks(const float* x, const int64_t* clips, int n_clips, int channels, float one_minus_k, float k, int64_t blk_a,
+                        int64_t hop_a, int64_t blk_b, int64_t hop_b, int up, const float* h, int half, double* out, void* ws,
+                        size_t ws_bytes, int* launches, void* stream);
+
 /* STFT magnitude, Hann-windowed frames, no centring, mono downmix = mean over channels:
  *   frames = 1 + max(0,(n - n_fft)/hop); out: [frames][n_fft/2+1] float32 (frame-major; the reference's
  *   array is the transpose).  window: device float[n_fft] (caller supplies np.hanning(n_fft) so the
