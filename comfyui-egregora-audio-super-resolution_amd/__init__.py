@@ -16,7 +16,8 @@ passes) only when EGREGORA_CODEC_BATCH_NODES is "1", the Fat-Llama batch node (e
 waves that share one chirp-z convolution length) only when EGREGORA_FATLLAMA_BATCH_NODES is "1", the WPE batch node
 (egregora_audio_enhance_wpe_batch.py: a list of clips in one ragged pass per wave) only when EGREGORA_ENHANCE_BATCH_NODES is "1", the
 evaluation batch nodes (egregora_audio_eval_batch.py: lists of clips scored and metered in one ragged pass per wave) only when
-EGREGORA_EVAL_BATCH_NODES is "1".
+EGREGORA_EVAL_BATCH_NODES is "1", the null-test batch nodes (egregora_null_test_batch.py: lists of pairs aligned, gain-matched and nulled
+in ragged passes per wave) only when EGREGORA_NULLTEST_BATCH_NODES is "1".
 Without them the registered set is the one listed above.
 """
 import os
@@ -91,5 +92,10 @@ if os.environ.get("EGREGORA_EVAL_BATCH_NODES") == "1":
     from .egregora_audio_eval_batch import (NODE_CLASS_MAPPINGS as EVAL_BATCH_MAP, NODE_DISPLAY_NAME_MAPPINGS as EVAL_BATCH_NAMES)
     NODE_CLASS_MAPPINGS.update(EVAL_BATCH_MAP)
     NODE_DISPLAY_NAME_MAPPINGS.update(EVAL_BATCH_NAMES)
+
+if os.environ.get("EGREGORA_NULLTEST_BATCH_NODES") == "1":
+    from .egregora_null_test_batch import (NODE_CLASS_MAPPINGS as NULL_BATCH_MAP, NODE_DISPLAY_NAME_MAPPINGS as NULL_BATCH_NAMES)
+    NODE_CLASS_MAPPINGS.update(NULL_BATCH_MAP)
+    NODE_DISPLAY_NAME_MAPPINGS.update(NULL_BATCH_NAMES)
 
 __all__ = ["NODE_CLASS_MAPPINGS", "NODE_DISPLAY_NAME_MAPPINGS"]

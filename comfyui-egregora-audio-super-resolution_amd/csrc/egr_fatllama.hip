@@ -21,10 +21,14 @@
 #define EGR_BFLY_HILO 15
 #endif
 #include "egr_fatllama_int.h"
+#include "egr_null_index.h"
+
+#include <map>
+#include <mutex>
 
 namespace egr {
 
-// MODE 0: first   (y -> time threshold -> FFT -> twiddle -> state)          [outermost pass only]
+// MODE 0: first  (y -> time threshold -> FFT -> twiddle -> state)          [outermost pass only]
 // MODE 1: middle  (state -> twiddle^-1 -> IFFT -> FFT -> twiddle -> state)  [outermost pass only]
 // MODE 2: last    (state -> twiddle^-1 -> IFFT -> out = y + d, peak)        [outermost pass only]
 // MODE 3: inverse (state -> twiddle^-1 -> IFFT -> state)                    [inner pass of a 3-level plan]
@@ -1663,16 +1667,20 @@ void fl_launch_inner(egr_fatllama_plan* p, bool forward, cplx* work, int nstates
 
 // One forward transform, the row pass with the hook `R` selects, one inverse, on the run-time-schedule kernels: src -> dst ([C][N] reals
 // each; src is only read, by the MODE 0 pass).
-static void launch_single_pass(egr_fatllama_plan* p, const RowP& R, const float* src, float* dst, hipStream_t st) {
-    const int C = p->C;
+// The passes address state `ch` at work + ch M and its samples at src / dst + ch N and take the number of states from the launch, so
+// `rows` states in a caller's `work` ([rows][M] complex) run on a plan of any channel count: its tables depend on the length alone.
+static void launch_single_pass_rows(egr_fatllama_plan* p, const RowP& R, const float* src, float* dst, cplx* work, int rows, hipStream_t st) {
     const bool three = p->sp.levels == 3;
     const FlPasses& ps = p->single;
     const FlColIO to_dst{0.f, dst, nullptr, nullptr};
-    ps.col[FL_COL_OPEN](p, FlColIO{-1.0f, const_cast<float*>(src), nullptr, nullptr}, p->work(), C, st);
-    if (three) ps.inner[FL_INNER_FWD](p, to_dst, p->work(), C, st);
-    ps.row[FL_ROW_DEFAULT](p, R, p->work(), C, st);
-    if (three) ps.inner[FL_INNER_INV](p, to_dst, p->work(), C, st);
-    ps.col[FL_COL_CLOSE](p, to_dst, p->work(), C, st);
+    ps.col[FL_COL_OPEN](p, FlColIO{-1.0f, const_cast<float*>(src), nullptr, nullptr}, work, rows, st);
+    if (three) ps.inner[FL_INNER_FWD](p, to_dst, work, rows, st);
+    ps.row[FL_ROW_DEFAULT](p, R, work, rows, st);
+    if (three) ps.inner[FL_INNER_INV](p, to_dst, work, rows, st);
+    ps.col[FL_COL_CLOSE](p, to_dst, work, rows, st);
+}
+static void launch_single_pass(egr_fatllama_plan* p, const RowP& R, const float* src, float* dst, hipStream_t st) {
+    launch_single_pass_rows(p, R, src, dst, p->work(), p->C, st);
 }
 
 // y = irfft(rfft(x) * gain): one forward transform, a real per-bin gain, one inverse, on the plan's passes.
@@ -1734,9 +1742,9 @@ __global__ __launch_bounds__(256) void k_phat_pack(const float* __restrict__ a, 
 }
 
 // cc_c = concat(cc[-(n/2-1):], cc[:n/2+1]), centre = n/2: cc_c[j] = cc[(j + n/2 + 1) mod n].  First maximum of
-// cc_c[centre - ms .. centre + ms]; out = {index (int bits), cc_c[idx-1], cc_c[idx], cc_c[idx+1]}.  ONE workgroup.
-__global__ __launch_bounds__(1024) void k_phat_peak(const float2* __restrict__ y, long long n, long long ms,
-                                                     float* __restrict__ out4) {
+// cc_c[centre - ms .. centre + ms]; out = {index (int bits), cc_c[idx-1], cc_c[idx], cc_c[idx+1]}.  ONE workgroup of 1024 threads;
+// k_phat_peak and k_phat_peak_pairs (egr_nullmany_delays) both call it.
+__device__ __forceinline__ void phat_peak_search(const float2* __restrict__ y, long long n, long long ms, float* __restrict__ out4) {
     __shared__ float bv[1024];
     __shared__ long long bi[1024];
     const long long centre = n / 2, sl = centre - ms, cnt = 2 * ms + 1;
@@ -1768,6 +1776,35 @@ __global__ __launch_bounds__(1024) void k_phat_peak(const float2* __restrict__ y
     }
 }
 
+__global__ __launch_bounds__(1024) void k_phat_peak(const float2* __restrict__ y, long long n, long long ms,
+                                                     float* __restrict__ out4) {
+    phat_peak_search(y, n, ms, out4);
+}
+
+// ---- many pairs of one transform length (egr_nullmany_delays).  tab: ND_COLS int64 per pair (egr_null_index.h) ----
+// One workgroup per 256-sample tile of one pair's row of z: z[pair][i] = (mono a[i], mono b[i]) below the pair's common length, zero
+// above; the downmix is mono_mean's (what egr_mono_mean would have stored first).
+__global__ __launch_bounds__(256) void k_phat_pack_pairs(const float* __restrict__ a, const float* __restrict__ b,
+                                                         const long long* __restrict__ tab, long long n, float2* __restrict__ z) {
+    long long first;
+    const int p = delays_tile_of(n, (long long)blockIdx.x, &first);
+    const long long* e = tab + (size_t)p * ND_COLS;
+    const long long i = first + threadIdx.x;
+    if (i >= n) return;
+    float2 v = make_float2(0.f, 0.f);
+    if (i < e[ND_N]) {
+        v.x = mono_mean(a + e[ND_OFF_A], (int)e[ND_CA], e[ND_LD_A], i);
+        v.y = mono_mean(b + e[ND_OFF_B], (int)e[ND_CB], e[ND_LD_B], i);
+    }
+    z[(size_t)p * n + i] = v;
+}
+
+// one workgroup per pair: k_phat_peak's search on the pair's correlation within its own max_shift
+__global__ __launch_bounds__(1024) void k_phat_peak_pairs(const float2* __restrict__ y, const long long* __restrict__ tab, long long n,
+                                                           float* __restrict__ out4) {
+    phat_peak_search(y + (size_t)blockIdx.x * n, n, tab[(size_t)blockIdx.x * ND_COLS + ND_MS], out4 + (size_t)blockIdx.x * 4);
+}
+
 }  // namespace egr
 
 using namespace egr;
@@ -1793,6 +1830,97 @@ extern "C" int egr_gcc_phat(egr_fatllama_plan* p, const float* a, int64_t na, co
     launch_single_pass(p, R, z, y, st);          // (one channel: the plan's C, checked above)
     hipLaunchKernelGGL(k_phat_peak, dim3(1), dim3(1024), 0, st, (const float2*)y, n, (long long)max_shift, out4);
     EGR_HIP(hipGetLastError());
+    return EGR_OK;
+}
+
+// ---- egr_nullmany_delays: egr_gcc_phat for the pairs of one transform length in one pack, one run of the passes, one peak launch ----
+namespace {
+struct DelaysPlan {
+    std::vector<long long> tab;
+    long long tiles = 0;
+    size_t z_off = 0, y_off = 0, work_off = 0, total = 0;
+};
+inline size_t nd_align(size_t b) { return (b + 255) & ~(size_t)255; }
+
+// every refusal that needs neither a pointer nor the plan: host arithmetic only
+int delays_plan(const int64_t* pairs, int n_pairs, int64_t n, DelaysPlan* P) {
+    EGR_CHECK(pairs && n_pairs >= 1, EGR_ERR_ARG, "egr_nullmany_delays: no pairs");
+    EGR_CHECK(n >= 4 && (n & (n - 1)) == 0 && n <= (1LL << 40), EGR_ERR_ARG, "egr_nullmany_delays: n=%lld is not a power of two in 4 .. 2^40",
+              (long long)n);
+    EGR_CHECK(n_pairs <= NULL_MAX_GROUP_ROWS, EGR_ERR_UNSUPPORTED,
+              "egr_nullmany_delays: pair %lld: a transform group holds at most %lld rows (gridDim.y of the passes), n_pairs=%d",
+              NULL_MAX_GROUP_ROWS, NULL_MAX_GROUP_ROWS, n_pairs);
+    P->tab.assign((size_t)n_pairs * ND_COLS, 0);
+    for (int p = 0; p < n_pairs; ++p) {
+        const int r = delays_fill((const long long*)pairs + (size_t)p * ND_COLS, n, &P->tiles, P->tab.data() + (size_t)p * ND_COLS);
+        if (r == NULL_OK) continue;
+        const long long* in = (const long long*)pairs + (size_t)p * ND_COLS;
+        EGR_CHECK(r != NULL_MAX_SHIFT, EGR_ERR_ARG, "egr_nullmany_delays: pair %d: max_shift out of range (%lld, n = %lld)", p, in[ND_MS], (long long)n);
+        EGR_CHECK(r != NULL_LENGTH, EGR_ERR_ARG, "egr_nullmany_delays: pair %d: its common length %lld belongs to the transform length %lld, not %lld",
+                  p, in[ND_N], null_transform_length(in[ND_N]), (long long)n);
+        EGR_CHECK(false, r == NULL_TOTAL ? EGR_ERR_UNSUPPORTED : EGR_ERR_ARG, "egr_nullmany_delays: pair %d: %s", p,
+                  r == NULL_SHORT ? "a common length below 1 (an empty side)" : r == NULL_BAD_ROW ? "channels outside 1 .. 65535 or a row stride below n"
+                  : r == NULL_OFFSET ? "an offset, stride or length is negative or past what the index type holds"
+                                     : "the running total of pack tiles leaves one grid (workgroups x threads < 2^32)");
+    }
+    const size_t row = (size_t)n * sizeof(float2);
+    P->z_off = nd_align(P->tab.size() * sizeof(long long));
+    P->y_off = P->z_off + nd_align((size_t)n_pairs * row);
+    P->work_off = P->y_off + nd_align((size_t)n_pairs * row);
+    P->total = P->work_off + nd_align((size_t)n_pairs * row);
+    return EGR_OK;
+}
+
+std::mutex g_nd_mu;
+std::map<int, TableStage> g_nd_stage;      // device -> pinned staging of the table (under g_nd_mu)
+}  // namespace
+
+extern "C" size_t egr_nullmany_delays_workspace_bytes(const int64_t* pairs, int n_pairs, int64_t n) {
+    DelaysPlan P;
+    if (delays_plan(pairs, n_pairs, n, &P) != EGR_OK) return 0;
+    return P.total;
+}
+
+extern "C" int egr_nullmany_delays(egr_fatllama_plan* p, const float* a, const float* b, const int64_t* pairs, int n_pairs, float* out4,
+                                   void* ws, size_t ws_bytes, int* launches, void* stream) {
+    EGR_CHECK(p != nullptr, EGR_ERR_ARG, "egr_nullmany_delays: null plan");
+    EGR_CHECK(!p->bluestein && p->factor == 1 && (p->sp.M & (p->sp.M - 1)) == 0, EGR_ERR_UNSUPPORTED,
+              "egr_nullmany_delays needs a packed-real plan for 2 n samples, n a power of two");
+    const long long n = p->sp.M;
+    DelaysPlan P;
+    int rc = delays_plan(pairs, n_pairs, n, &P);
+    if (rc) return rc;
+    EGR_CHECK(a && b && out4 && ws, EGR_ERR_ARG, "egr_nullmany_delays: null pointer");
+    EGR_CHECK(ws_bytes >= P.total, EGR_ERR_ARG, "egr_nullmany_delays: workspace of %zu bytes, %zu needed", ws_bytes, P.total);
+    EGR_CHECK(((uintptr_t)ws & 15) == 0, EGR_ERR_ARG, "egr_nullmany_delays: the workspace must be 16-byte aligned (int64 table, complex rows)");
+    const long long planes = std::max(p->colA.nplanes, p->sp.levels == 3 ? p->colB.nplanes : 1);
+    EGR_CHECK((long long)n_pairs * planes <= NULL_MAX_GROUP_ROWS, EGR_ERR_UNSUPPORTED,
+              "egr_nullmany_delays: %d pairs on %lld planes of the plan's column pass exceed gridDim.y", n_pairs, planes);
+    hipStream_t st = (hipStream_t)stream;
+    char* base = (char*)ws;
+    {
+        std::lock_guard<std::mutex> lk(g_nd_mu);
+        TableStage& stage = g_nd_stage[p->device];
+        const size_t bytes = P.tab.size() * sizeof(long long);
+        rc = stage.reserve(bytes);
+        if (rc) return rc;
+        memcpy(stage.p, P.tab.data(), bytes);
+        EGR_HIP(hipMemcpyAsync(base, stage.p, bytes, hipMemcpyHostToDevice, st));
+        EGR_HIP(hipEventRecord(stage.copied, st));
+    }
+    const long long* tab = (const long long*)base;
+    float* z = (float*)(base + P.z_off);
+    float* y = (float*)(base + P.y_off);
+    RowP R = p->row;
+    R.gain = nullptr;
+    R.phat = 1;
+    hipLaunchKernelGGL(k_phat_pack_pairs, dim3((unsigned)P.tiles), dim3(256), 0, st, a, b, tab, n, (float2*)z);
+    EGR_HIP(hipGetLastError());
+    launch_single_pass_rows(p, R, z, y, (cplx*)(base + P.work_off), n_pairs, st);
+    EGR_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_phat_peak_pairs, dim3((unsigned)n_pairs), dim3(1024), 0, st, (const float2*)y, tab, n, out4);
+    EGR_HIP(hipGetLastError());
+    if (launches) *launches = 2 + (p->sp.levels == 3 ? 5 : 3);
     return EGR_OK;
 }
 

@@ -10,6 +10,7 @@
 #include "egr_eval_index.h"
 #include "egr_fft_device.h"
 #include "egr_handle.h"
+#include "egr_null_index.h"
 #include "egr_plan.h"
 #include "egr_stft_tables.h"
 
@@ -525,13 +526,7 @@ __global__ __launch_bounds__(64) void k_kweight(const float* __restrict__ x, lon
     }
 }
 
-// mean over channels as numpy's float32 .mean(axis=0): rows added in order, one division
-__device__ __forceinline__ float mono_mean(const float* __restrict__ x, int C, long long ld, long long i) {
-    float m = x[i];
-    for (int c = 1; c < C; ++c) m = __fadd_rn(m, x[(size_t)c * ld + i]);
-    return C > 1 ? __fdiv_rn(m, (float)C) : m;
-}
-
+// (mono_mean, the float32 mean over channels, lives in egr_null_index.h: egr_fatllama.hip forms the same downmix)
 __global__ __launch_bounds__(256) void k_mono_mean(const float* __restrict__ x, int C, long long ld, long long n, float* __restrict__ y) {
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) y[i] = mono_mean(x, C, ld, i);
 }
@@ -889,6 +884,127 @@ __global__ __launch_bounds__(256) void k_pair_sisdr_reduce(const double2* __rest
     }
 }
 
+// ---------------------------------------------------------------- many pairs through the null test (egr_nullmany_*)
+// tab: SF_COLS int64 per (pair, channel) row (egr_null_index.h).  One workgroup per 256-sample output tile of one row; k_shift_fir's
+// sums.  The tile's 256 + m - 1 samples of the shifted signal go to LDS once (zero outside [0, n_in) on either index) and the taps
+// with them; a zero product added in k_shift_fir's order leaves the accumulator's bits as they are (it starts at +0 and never
+// becomes -0), so the result has k_shift_fir's bits.  (A form that read every term from global memory as k_shift_fir does gave the
+// same bits 1.5x to 1.85x slower: profiles/null_batch.md.)
+__global__ __launch_bounds__(256) void k_shift_fir_rows(const float* __restrict__ x, const long long* __restrict__ tab, int n_rows,
+                                                        const float* __restrict__ taps, int m, float* __restrict__ y) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    long long first, len;
+    const long long* e = tab + (size_t)shiftfir_tile_of(tab, n_rows, (long long)blockIdx.x, &first, &len) * SF_COLS;
+    const float* xr = x + e[SF_IN];
+    float* yr = y + e[SF_OUT];
+    const long long n_in = e[SF_N_IN], shift = e[SF_SHIFT], i = first + threadIdx.x;
+    if (e[SF_TAPS] < 0) {          // (the same for the whole workgroup)
+        if ((long long)threadIdx.x < len) {
+            const long long j = i - shift;
+            yr[i] = (i < n_in && j >= 0 && j < n_in) ? xr[j] : 0.f;
+        }
+        return;
+    }
+    const float* h = taps + (size_t)e[SF_TAPS] * m;
+    const int off = (m - 1) / 2;
+    float* S = (float*)smem;
+    float* H = S + NULL_TILE + m - 1;
+    const long long s0 = first + off - (m - 1);
+    for (int q = threadIdx.x; q < NULL_TILE + m - 1; q += 256) {
+        const long long si = s0 + q, j = si - shift;
+        S[q] = (si >= 0 && si < n_in && j >= 0 && j < n_in) ? xr[j] : 0.f;
+    }
+    for (int k = threadIdx.x; k < m; k += 256) H[k] = h[k];
+    __syncthreads();
+    if ((long long)threadIdx.x < len) {
+        float acc = 0.f;
+        if (i < n_in)
+            for (int k = 0; k < m; ++k) acc += H[k] * S[threadIdx.x + m - 1 - k];
+        yr[i] = acc;
+    }
+}
+
+// tab: NM_COLS int64 per pair; prm: {gain g, least-squares k, sign, k in use} per pair.  One workgroup per chunk of NULL_CHUNK samples of
+// one pair: matched = fl(aligned g) (egr_eltwise's product), b' = k in use ? fl(matched k) : matched, null = fl(a + sgn b') (k_null_mix);
+// part[chunk] = {sum mono(null)^2, count(|null| > 1), sum a, sum b', sum a b', sum a a, sum b' b'} over the mono downmixes in double
+// (k_null_mix's and k_pair_stats' terms).  STORE: matched, null and (k in use) b' are written to the pair's [channels][n] blocks.
+template <bool STORE>
+__global__ __launch_bounds__(256) void k_nullmany_mix(const float* __restrict__ a, const float* __restrict__ b, const long long* __restrict__ tab,
+                                                      const float4* __restrict__ prm, int n_pairs, float* __restrict__ matched,
+                                                      float* __restrict__ nul, float* __restrict__ scaled, double* __restrict__ part) {
+    __shared__ double red[NULL_SUMS - 1][256];
+    long long first, len;
+    const int p = mix_chunk_of(tab, n_pairs, (long long)blockIdx.x, &first, &len);
+    const long long* e = tab + (size_t)p * NM_COLS;
+    const float* A = a + e[NM_OFF_A];
+    const float* B = b + e[NM_OFF_B];
+    const long long lda = e[NM_LD_A], ldb = e[NM_LD_B], n = e[NM_N], o = e[NM_OUT];
+    const int C = (int)e[NM_CH];
+    const float4 q = prm[p];
+    const float g = q.x, kf = q.y, sgn = q.z;
+    const bool use_k = q.w != 0.f;
+    double v[NULL_SUMS - 1] = {0, 0, 0, 0, 0, 0, 0};
+    for (long long i = first + threadIdx.x; i < first + len; i += 256) {
+        float mn = 0.f, ma = 0.f, mb = 0.f;
+        for (int c = 0; c < C; ++c) {
+            const float av = A[(size_t)c * lda + i];
+            const float mt = __fmul_rn(B[(size_t)c * ldb + i], g);
+            const float bp = use_k ? __fmul_rn(mt, kf) : mt;
+            const float d = __fadd_rn(av, sgn * bp);
+            if (STORE) {
+                const size_t w = (size_t)o + (size_t)c * n + i;
+                matched[w] = mt;
+                nul[w] = d;
+                if (use_k) scaled[w] = bp;
+            }
+            if (fabsf(d) > 1.0f) v[1] += 1.0;
+            mn = c ? __fadd_rn(mn, d) : d;
+            ma = c ? __fadd_rn(ma, av) : av;
+            mb = c ? __fadd_rn(mb, bp) : bp;
+        }
+        if (C > 1) { mn = __fdiv_rn(mn, (float)C); ma = __fdiv_rn(ma, (float)C); mb = __fdiv_rn(mb, (float)C); }
+        const double dn = mn, x = ma, yv = mb;
+        v[0] += dn * dn; v[2] += x; v[3] += yv; v[4] += x * yv; v[5] += x * x; v[6] += yv * yv;
+    }
+#pragma unroll
+    for (int k = 0; k < NULL_SUMS - 1; ++k) red[k][threadIdx.x] = v[k];
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (threadIdx.x < s) {
+#pragma unroll
+            for (int k = 0; k < NULL_SUMS - 1; ++k) red[k][threadIdx.x] += red[k][threadIdx.x + s];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x < NULL_SUMS) part[(size_t)blockIdx.x * NULL_SUMS + threadIdx.x] = threadIdx.x < NULL_SUMS - 1 ? red[threadIdx.x][0] : 0.0;
+}
+
+// One workgroup per pair: the pair's chunk sums added in a fixed order (thread i takes chunks i, i + 256, ... ascending; a tree) into
+// out8[pair]: k_pair_sisdr_reduce's scheme for the seven sums.
+__global__ __launch_bounds__(256) void k_nullmany_reduce(const double* __restrict__ part, const long long* __restrict__ tab,
+                                                         double* __restrict__ out8) {
+    __shared__ double red[NULL_SUMS - 1][256];
+    const long long* e = tab + (size_t)blockIdx.x * NM_COLS;
+    const double* v = part + (size_t)e[NM_CHUNK0] * NULL_SUMS;
+    const long long nc = mix_chunks(e[NM_N]);
+    double acc[NULL_SUMS - 1] = {0, 0, 0, 0, 0, 0, 0};
+    for (long long i = threadIdx.x; i < nc; i += 256) {
+#pragma unroll
+        for (int k = 0; k < NULL_SUMS - 1; ++k) acc[k] += v[(size_t)i * NULL_SUMS + k];
+    }
+#pragma unroll
+    for (int k = 0; k < NULL_SUMS - 1; ++k) red[k][threadIdx.x] = acc[k];
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (threadIdx.x < s) {
+#pragma unroll
+            for (int k = 0; k < NULL_SUMS - 1; ++k) red[k][threadIdx.x] += red[k][threadIdx.x + s];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x < NULL_SUMS) out8[(size_t)blockIdx.x * NULL_SUMS + threadIdx.x] = threadIdx.x < NULL_SUMS - 1 ? red[threadIdx.x][0] : 0.0;
+}
+
 // The restart rule of the K-weighting kernels, stated once: a thread restarts the recurrence W samples ahead of its L-sample chunk,
 // k^W < 6e-12 (below float32 resolution of the state), W at least 64, L = W / 3 rounded up.  egr_kweight, egr_loudness_frames and
 // egr_loudness_tracks all take their chunking from here, which is what keeps their results bit-equal.
@@ -981,6 +1097,55 @@ static int loud_plan(const int64_t* clips, int n_clips, int channels, float k, i
     P->mono_off = eval_align(P->tab.size() * sizeof(long long));
     P->total = P->mono_off + eval_align((size_t)P->t.mono * sizeof(float));
     P->launches = 2 + (blk_b ? 1 : 0) + (up ? 1 : 0);
+    return EGR_OK;
+}
+
+static const char* null_why(int r) {
+    return r == NULL_SHORT ? "a length below 1 (an empty side)" : r == NULL_BAD_ROW ? "channels outside 1 .. 65535 or a row stride below n"
+         : r == NULL_OFFSET ? "an offset, stride, shift or length is negative or past what the index type holds"
+         : r == NULL_CHANNELS ? "operands could not be broadcast together: the two sides differ in channel count"
+         : r == NULL_TAPS    ? "its row of the taps table is outside -1 .. n_tap_rows - 1"
+                             : "the running total of tiles or chunks leaves one grid (workgroups x threads < 2^32)";
+}
+
+struct ShiftFirPlan {
+    std::vector<long long> tab;
+    long long tiles = 0;
+    size_t total = 0;
+};
+
+// every refusal of egr_nullmany_shift_fir that needs no pointer: host arithmetic only
+static int shiftfir_plan(const int64_t* rows, int n_rows, int n_tap_rows, int taps, ShiftFirPlan* P) {
+    EGR_CHECK(rows && n_rows >= 1, EGR_ERR_ARG, "egr_nullmany_shift_fir: no rows");
+    EGR_CHECK(n_rows <= EVAL_MAX_GRID_256, EGR_ERR_UNSUPPORTED, "egr_nullmany_shift_fir: n_rows=%d is above %lld", n_rows, EVAL_MAX_GRID_256);
+    EGR_CHECK(n_tap_rows >= 0 && taps >= 0 && taps <= NULL_MAX_TAPS && (n_tap_rows == 0 || taps >= 1), EGR_ERR_ARG,
+              "egr_nullmany_shift_fir: n_tap_rows=%d, taps=%d (at most %d)", n_tap_rows, taps, NULL_MAX_TAPS);
+    P->tab.assign((size_t)n_rows * SF_COLS, 0);
+    for (int r = 0; r < n_rows; ++r) {
+        const int why = shiftfir_fill((const long long*)rows + (size_t)r * SF_IN_COLS, n_tap_rows, &P->tiles, P->tab.data() + (size_t)r * SF_COLS);
+        EGR_CHECK(why == NULL_OK, why == NULL_TOTAL ? EGR_ERR_UNSUPPORTED : EGR_ERR_ARG, "egr_nullmany_shift_fir: row %d: %s", r, null_why(why));
+    }
+    P->total = eval_align(P->tab.size() * sizeof(long long));
+    return EGR_OK;
+}
+
+struct MixPlan {
+    std::vector<long long> tab;          // the int64 rows, then two int64 per pair holding its four float parameters
+    long long chunks = 0;
+    size_t prm_off = 0, part_off = 0, total = 0;
+};
+
+static int mix_plan(const int64_t* pairs, int n_pairs, MixPlan* P) {
+    EGR_CHECK(pairs && n_pairs >= 1, EGR_ERR_ARG, "egr_nullmany_mix: no pairs");
+    EGR_CHECK(n_pairs <= EVAL_MAX_GRID_256, EGR_ERR_UNSUPPORTED, "egr_nullmany_mix: n_pairs=%d is above %lld", n_pairs, EVAL_MAX_GRID_256);
+    P->prm_off = eval_align((size_t)n_pairs * NM_COLS * sizeof(long long));
+    P->tab.assign(P->prm_off / sizeof(long long) + (size_t)n_pairs * 2, 0);
+    for (int p = 0; p < n_pairs; ++p) {
+        const int why = mix_fill((const long long*)pairs + (size_t)p * NM_IN_COLS, &P->chunks, P->tab.data() + (size_t)p * NM_COLS);
+        EGR_CHECK(why == NULL_OK, why == NULL_TOTAL ? EGR_ERR_UNSUPPORTED : EGR_ERR_ARG, "egr_nullmany_mix: pair %d: %s", p, null_why(why));
+    }
+    P->part_off = eval_align(P->tab.size() * sizeof(long long));
+    P->total = P->part_off + eval_align((size_t)P->chunks * NULL_SUMS * sizeof(double));
     return EGR_OK;
 }
 
@@ -1425,6 +1590,74 @@ extern "C" int egr_loudness_tracks(const float* x, const int64_t* clips, int n_c
         EGR_HIP(hipMemsetAsync(slots, 0, (size_t)n_clips * sizeof(unsigned), st));
         hipLaunchKernelGGL(k_true_peak_tracks, dim3((unsigned)P.t.tiles), dim3(256), 0, st, x, tab, n_clips, channels, up, h, half, slots);
     }
+    EGR_HIP(hipGetLastError());
+    return EGR_OK;
+}
+
+extern "C" size_t egr_nullmany_shift_fir_workspace_bytes(const int64_t* rows, int n_rows, int n_tap_rows, int taps) {
+    ShiftFirPlan P;
+    if (shiftfir_plan(rows, n_rows, n_tap_rows, taps, &P) != EGR_OK) return 0;
+    return P.total;
+}
+
+extern "C" int egr_nullmany_shift_fir(const float* x, const int64_t* rows, int n_rows, const float* taps_tab, int n_tap_rows, int taps,
+                                      float* y, void* ws, size_t ws_bytes, int* launches, void* stream) {
+    ShiftFirPlan P;
+    int rc = shiftfir_plan(rows, n_rows, n_tap_rows, taps, &P);
+    if (rc) return rc;
+    EGR_CHECK(x && y && ws && (n_tap_rows == 0 || taps_tab), EGR_ERR_ARG, "egr_nullmany_shift_fir: null pointer");
+    EGR_CHECK(ws_bytes >= P.total, EGR_ERR_ARG, "egr_nullmany_shift_fir: workspace of %zu bytes, %zu needed", ws_bytes, P.total);
+    EGR_CHECK(((uintptr_t)ws & 7) == 0, EGR_ERR_ARG, "egr_nullmany_shift_fir: the workspace (int64 table) must be 8-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    rc = eval_upload(P.tab, ws, st);
+    if (rc) return rc;
+    if (launches) *launches = 1;
+    const long long* tab = (const long long*)ws;
+    const int m = n_tap_rows ? taps : 0;
+    hipLaunchKernelGGL(k_shift_fir_rows, dim3((unsigned)P.tiles), dim3(256), (size_t)(NULL_TILE + 2 * m) * sizeof(float), st, x, tab, n_rows,
+                       taps_tab, m, y);
+    EGR_HIP(hipGetLastError());
+    return EGR_OK;
+}
+
+extern "C" size_t egr_nullmany_mix_workspace_bytes(const int64_t* pairs, int n_pairs) {
+    MixPlan P;
+    if (mix_plan(pairs, n_pairs, &P) != EGR_OK) return 0;
+    return P.total;
+}
+
+extern "C" int egr_nullmany_mix(const float* a, const float* b, const int64_t* pairs, const float* params, int n_pairs, float* matched,
+                                float* null_out, float* scaled, double* out8, void* ws, size_t ws_bytes, int* launches, void* stream) {
+    MixPlan P;
+    int rc = mix_plan(pairs, n_pairs, &P);
+    if (rc) return rc;
+    EGR_CHECK(a && b && params && out8 && ws, EGR_ERR_ARG, "egr_nullmany_mix: null pointer");
+    const bool store = matched || null_out;
+    EGR_CHECK(!store || (matched && null_out), EGR_ERR_ARG, "egr_nullmany_mix: matched and null_out go together (both null: sums only)");
+    for (int p = 0; p < n_pairs; ++p) {
+        const float* q = params + (size_t)p * 4;
+        EGR_CHECK(q[2] == 1.0f || q[2] == -1.0f, EGR_ERR_ARG, "egr_nullmany_mix: pair %d: sign %g is neither 1 nor -1", p, (double)q[2]);
+        EGR_CHECK(q[3] == 0.0f || (store && scaled), EGR_ERR_ARG,
+                  "egr_nullmany_mix: pair %d: a least-squares factor needs the stored mode and the `scaled` output", p);
+    }
+    EGR_CHECK(ws_bytes >= P.total, EGR_ERR_ARG, "egr_nullmany_mix: workspace of %zu bytes, %zu needed", ws_bytes, P.total);
+    EGR_CHECK(((uintptr_t)ws & 15) == 0 && ((uintptr_t)out8 & 7) == 0, EGR_ERR_ARG,
+              "egr_nullmany_mix: the workspace must be 16-byte aligned (int64 table, float4 parameters), out8 8-byte aligned");
+    memcpy(P.tab.data() + P.prm_off / sizeof(long long), params, (size_t)n_pairs * 4 * sizeof(float));
+    hipStream_t st = (hipStream_t)stream;
+    char* base = (char*)ws;
+    rc = eval_upload(P.tab, base, st);
+    if (rc) return rc;
+    if (launches) *launches = 2;
+    const long long* tab = (const long long*)base;
+    const float4* prm = (const float4*)(base + P.prm_off);
+    double* part = (double*)(base + P.part_off);
+    if (store)
+        hipLaunchKernelGGL(k_nullmany_mix<true>, dim3((unsigned)P.chunks), dim3(256), 0, st, a, b, tab, prm, n_pairs, matched, null_out, scaled, part);
+    else
+        hipLaunchKernelGGL(k_nullmany_mix<false>, dim3((unsigned)P.chunks), dim3(256), 0, st, a, b, tab, prm, n_pairs, matched, null_out, scaled, part);
+    EGR_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_nullmany_reduce, dim3((unsigned)n_pairs), dim3(256), 0, st, (const double*)part, tab, out8);
     EGR_HIP(hipGetLastError());
     return EGR_OK;
 }

@@ -253,7 +253,21 @@ def xcorr_delay(a: torch.Tensor, b: torch.Tensor, sr: int, max_shift_smp: int) -
     native.check(native.lib().egr_gcc_phat(C.c_void_p(plan), native.ptr(a), a.numel(), native.ptr(b), b.numel(),
                                            int(max_shift_smp), native.ptr(work), native.ptr(out4), native.stream_ptr()),
                  "egr_gcc_phat")
-    o = out4.cpu()
+    return xcorr_refine(out4.cpu(), n)
+
+
+def xcorr_transform_length(na: int, nb: int) -> int:
+    """The power of two the GCC-PHAT transform of two signals of na and nb samples runs at (the rule of xcorr_delay above)."""
+    n = 1
+    while n < na + nb:
+        n <<= 1
+    return n
+
+
+def xcorr_refine(out4: torch.Tensor, n: int) -> float:
+    """The host's part of the delay estimate: egr_gcc_phat's four floats (host tensor) -> lag in samples with the parabolic refinement
+    and quirk Q8.  xcorr_delay and null_many.delays_many both end here."""
+    o = out4.reshape(4)
     rel = int(o[:1].view(torch.int32)[0])
     y0, y1, y2 = (float(v) for v in o[1:])
     centre = n // 2
@@ -315,7 +329,13 @@ def k_weight(x_ct: torch.Tensor, sr: int) -> torch.Tensor:
 def integrated_lufs(x_ct: torch.Tensor, sr: int) -> float:
     """The suite's gated loudness (integrated_lufs, egregora_null_test_suite.py:143-165): K-weighting and the 400 ms block
     energies on the device, the gate over the few block values on the host in the reference's own expressions."""
-    ms = block_mean_squares(k_weight(x_ct, sr), max(1, int(round(0.400 * sr))), max(1, int(round(0.100 * sr)))) + 1e-20
+    return lufs_gate(block_mean_squares(k_weight(x_ct, sr), max(1, int(round(0.400 * sr))), max(1, int(round(0.100 * sr)))))
+
+
+def lufs_gate(ms: np.ndarray) -> float:
+    """The host's part of the suite's loudness: the -10 LU gate over the 400 ms block mean squares.  integrated_lufs and the many-pair
+    path (null_many) both end here."""
+    ms = ms + 1e-20
     ungated = -0.691 + 10.0 * np.log10(np.mean(ms))
     keep = (-0.691 + 10.0 * np.log10(ms)) >= ungated - 10.0
     if np.any(keep):

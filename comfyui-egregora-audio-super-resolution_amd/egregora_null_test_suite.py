@@ -60,20 +60,34 @@ def frac_delay_taps(frac: float, taps: int) -> np.ndarray:
     return h / np.sum(h)
 
 
-def apply_delay(x: torch.Tensor, delay_samples: float, taps: int, n_out: int) -> torch.Tensor:
-    """[C,N] CUDA -> [C,n_out]: reference _apply_frac_delay_CN followed by _pad_or_crop_CN."""
-    C, N = x.shape
-    y = torch.empty((C, n_out), dtype=torch.float32, device=x.device)
-    shift, h, m = 0, None, 0
+def delay_rule(delay_samples: float, taps: int, n_in: int):
+    """-> (integer shift, FIR taps or None) for a delay of `delay_samples` on n_in samples: what egr_shift_fir is given.  apply_delay and
+    null_many.shift_fir_many both take it from here."""
+    shift, hh = 0, None
     if abs(delay_samples) >= 1e-6:
         int_d = int(math.floor(abs(delay_samples)))
         frac = abs(delay_samples) - int_d
         shift = int_d if delay_samples >= 0 else -int_d
-        if int_d >= N:
-            shift = N if delay_samples >= 0 else -N          # everything shifted out: zeros, as the reference's guards leave them
+        if int_d >= n_in:
+            shift = n_in if delay_samples >= 0 else -n_in    # everything shifted out: zeros, as the reference's guards leave them
         if frac > 1e-6:
             hh = frac_delay_taps(frac, taps)
-            h, m = torch.from_numpy(hh).to(x.device), hh.size
+    return shift, hh
+
+
+def corr_finish(sa, sb, ab, aa, bb, n, invert_b=True) -> float:
+    """corr_coef from the five double sums over the mono downmixes (:440-447); null_stage and null_many both end here."""
+    cov = ab - sa * sb / n
+    den = math.sqrt(max(aa - sa * sa / n, 0.0)) * math.sqrt(max(bb - sb * sb / n, 0.0)) + 1e-20
+    return float(np.float32((cov if invert_b else -cov) / den))
+
+
+def apply_delay(x: torch.Tensor, delay_samples: float, taps: int, n_out: int) -> torch.Tensor:
+    """[C,N] CUDA -> [C,n_out]: reference _apply_frac_delay_CN followed by _pad_or_crop_CN."""
+    C, N = x.shape
+    y = torch.empty((C, n_out), dtype=torch.float32, device=x.device)
+    shift, hh = delay_rule(delay_samples, taps, N)
+    h, m = (None, 0) if hh is None else (torch.from_numpy(hh).to(x.device), hh.size)
     native.check(native.lib().egr_shift_fir(native.ptr(x), C, N, shift, native.ptr(h) if h is not None else None, m,
                                             native.ptr(y), n_out, native.stream_ptr()), "egr_shift_fir")
     return y
@@ -108,10 +122,7 @@ def null_stage(A, B, sr, invert_b=True, least_squares_scale=False, compute_corr=
     null, null_ss, overs = device_ops.null_mix(A, B, n, k, invert_b)
     m = {}
     if compute_corr:
-        sa, sb, ab, aa, bb = device_ops.pair_stats(A, B, n, k)
-        cov = ab - sa * sb / n
-        den = math.sqrt(max(aa - sa * sa / n, 0.0)) * math.sqrt(max(bb - sb * sb / n, 0.0)) + 1e-20
-        m["corr_coef"] = float(np.float32((cov if invert_b else -cov) / den))
+        m["corr_coef"] = corr_finish(*device_ops.pair_stats(A, B, n, k), n, invert_b)
     if compute_null_rms:
         m["null_rms_dbfs"] = 10.0 * math.log10(null_ss / n + 1e-20)
     if compute_null_lufs:

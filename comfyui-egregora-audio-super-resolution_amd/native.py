@@ -100,6 +100,12 @@ SIGNATURES = {
     "egr_loudness_tracks_workspace_bytes": (C.c_size_t, [C.POINTER(_i64), _i, _i, _f, _i64, _i64, _i64, _i64, _i]),
     "egr_loudness_tracks": (_i, [_vp, C.POINTER(_i64), _i, _i, _f, _f, _i64, _i64, _i64, _i64, _i, _vp, _i, _vp, _vp, C.c_size_t,
                                  C.POINTER(_i), _vp]),
+    "egr_nullmany_delays_workspace_bytes": (C.c_size_t, [C.POINTER(_i64), _i, _i64]),
+    "egr_nullmany_delays": (_i, [_vp, _vp, _vp, C.POINTER(_i64), _i, _vp, _vp, C.c_size_t, C.POINTER(_i), _vp]),
+    "egr_nullmany_shift_fir_workspace_bytes": (C.c_size_t, [C.POINTER(_i64), _i, _i, _i]),
+    "egr_nullmany_shift_fir": (_i, [_vp, C.POINTER(_i64), _i, _vp, _i, _i, _vp, _vp, C.c_size_t, C.POINTER(_i), _vp]),
+    "egr_nullmany_mix_workspace_bytes": (C.c_size_t, [C.POINTER(_i64), _i]),
+    "egr_nullmany_mix": (_i, [_vp, _vp, C.POINTER(_i64), C.POINTER(_f), _i, _vp, _vp, _vp, _vp, _vp, C.c_size_t, C.POINTER(_i), _vp]),
     "egr_wola_stitch": (_i, [_vp, _i, _i, _i64, _i64, _i64, _i64, _vp, _vp, _vp]),
     "egr_chunk_gather": (_i, [_vp, _i, _i64, _i64, _i64, _i, _i, _vp, _vp]),
     "egr_resample_poly": (_i, [_vp, _i, _i64, _i, _i, _vp, _i, _vp, _i64, _vp]),

@@ -438,6 +438,50 @@ int egr_loudness_tracks(const float* x, const int64_t* clips, int n_clips, int c
                         int64_t hop_a, int64_t blk_b, int64_t hop_b, int up, const float* h, int half, double* out, void* ws,
                         size_t ws_bytes, int* launches, void* stream);
 
+/* The null-test suite for many (reference, processed) pairs per call: what egr_mono_mean x 2 + egr_gcc_phat, egr_shift_fir,
+ * and egr_eltwise + egr_null_mix + egr_pair_stats compute for one pair, in a number of launches that does not depend on the pairs.  All
+ * tables are HOST int64 arrays; offsets count floats from the buffer the call names.  Every grid equals its work count (at most 2^24 - 1
+ * 256-thread workgroups); no kernel here uses floating-point atomics: a pair's numbers do not depend on the other pairs, their order or
+ * the run.  Every refusal that needs no pointer is decided from the tables before anything is copied or launched and names its pair
+ * (row) in egr_last_error; the *_workspace_bytes entry points are host only and return 0 for what the call refuses.
+ *
+ * egr_nullmany_delays: GCC-PHAT for pairs that share the transform length n (the power of two with n >= 2 n_common, the single path's).
+ *   plan  : a packed-real plan for 2 n samples (egr_fatllama_plan_create(&plan, 2 n, channels, 1, ...)), any channel count: the states
+ *           live in ws, not in the plan
+ *   pairs : 8 int64 per pair: offset of side A in a, its channels, its row stride; the same for side B in b; n_common = min(len_a, len_b)
+ *           >= 1; max_shift (samples, 0 <= max_shift < n / 2 - 1)
+ *   out4  : device float [n_pairs][4] = egr_gcc_phat's out4 of each pair, bit for bit (the downmixes are egr_mono_mean's)
+ *   ws    : 16-byte aligned; the table, then z, the correlation and the passes' state: 24 n bytes per pair
+ *   at most 65535 pairs per call (gridDim.y of the passes; fewer on a three-level plan, refused by the call).  *launches: 5, or 7 on a
+ *   three-level plan.  EGR_ERR_ARG for an empty side, channels outside 1..65535, a stride below n_common, a bad offset, a common length
+ *   whose transform length is not n, max_shift out of range; EGR_ERR_UNSUPPORTED for more than 65535 pairs or pack tiles beyond one grid.
+ *
+ * egr_nullmany_shift_fir: egr_shift_fir for rows of different lengths, bit for bit.
+ *   rows  : 6 int64 per row: offset of the input row in x, n_in >= 1, integer shift, row of taps_tab or -1 (no taps: y = shifted x),
+ *           offset of the output row in y, n_out >= 1
+ *   taps_tab : device float [n_tap_rows][taps] (NULL with n_tap_rows = 0); taps <= 4096
+ *   ws    : 8-byte aligned, the table.  One launch: a tile's 256 + taps - 1 samples are staged in LDS once.
+ *
+ * egr_nullmany_mix: per pair matched = fl(b g), b' = use_k ? fl(matched k) : matched, null = fl(a + sign b').
+ *   pairs : 8 int64 per pair: offset of the reference in a, its channels, its row stride; the same for the aligned signal in b; n >= 1
+ *           samples per row; offset of the pair's [channels][n] block in each of matched / null_out / scaled.  The two channel counts
+ *           must be equal (EGR_ERR_ARG, "operands could not be broadcast together")
+ *   params: HOST float [n_pairs][4] = {g, k, sign (1 or -1), use_k (0 or 1)}
+ *   matched, null_out : device outputs, both NULL for the sums alone; scaled: device output of b', needed when some use_k is 1
+ *   out8  : device double [n_pairs][8] = {sum mono(null)^2, count(|null| > 1) over all channels, sum a, sum b', sum a b', sum a a,
+ *           sum b' b', 0} over the float32 channel means, summed in double per 4096-sample chunk of the pair and then over its chunks in
+ *           a fixed order
+ *   ws    : 16-byte aligned (table, parameters, chunk sums); out8 8-byte aligned.  Two launches. */
+size_t egr_nullmany_delays_workspace_bytes(const int64_t* pairs, int n_pairs, int64_t n);
+int egr_nullmany_delays(egr_fatllama_plan* plan, const float* a, const float* b, const int64_t* pairs, int n_pairs, float* out4, void* ws,
+                        size_t ws_bytes, int* launches, void* stream);
+size_t egr_nullmany_shift_fir_workspace_bytes(const int64_t* rows, int n_rows, int n_tap_rows, int taps);
+int egr_nullmany_shift_fir(const float* x, const int64_t* rows, int n_rows, const float* taps_tab, int n_tap_rows, int taps, float* y,
+                           void* ws, size_t ws_bytes, int* launches, void* stream);
+size_t egr_nullmany_mix_workspace_bytes(const int64_t* pairs, int n_pairs);
+int egr_nullmany_mix(const float* a, const float* b, const int64_t* pairs, const float* params, int n_pairs, float* matched,
+                     float* null_out, float* scaled, double* out8, void* ws, size_t ws_bytes, int* launches, void* stream);
+
 /* STFT magnitude, Hann-windowed frames, no centring, mono downmix = mean over channels:
  *   frames = 1 + max(0,(n - n_fft)/hop); out: [frames][n_fft/2+1] float32 (frame-major; the reference's
  *   array is the transpose).  window: device float[n_fft] (caller supplies np.hanning(n_fft) so the
