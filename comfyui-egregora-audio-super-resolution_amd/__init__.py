@@ -17,7 +17,8 @@ waves that share one chirp-z convolution length) only when EGREGORA_FATLLAMA_BAT
 (egregora_audio_enhance_wpe_batch.py: a list of clips in one ragged pass per wave) only when EGREGORA_ENHANCE_BATCH_NODES is "1", the
 evaluation batch nodes (egregora_audio_eval_batch.py: lists of clips scored and metered in one ragged pass per wave) only when
 EGREGORA_EVAL_BATCH_NODES is "1", the null-test batch nodes (egregora_null_test_batch.py: lists of pairs aligned, gain-matched and nulled
-in ragged passes per wave) only when EGREGORA_NULLTEST_BATCH_NODES is "1".
+in ragged passes per wave) only when EGREGORA_NULLTEST_BATCH_NODES is "1", the resampler's batch node
+(egregora_audio_resample_batch.py: a list of clips with one library call per source rate) only when EGREGORA_RESAMPLE_BATCH_NODES is "1".
 Without them the registered set is the one listed above.
 """
 import os
@@ -97,5 +98,10 @@ if os.environ.get("EGREGORA_NULLTEST_BATCH_NODES") == "1":
     from .egregora_null_test_batch import (NODE_CLASS_MAPPINGS as NULL_BATCH_MAP, NODE_DISPLAY_NAME_MAPPINGS as NULL_BATCH_NAMES)
     NODE_CLASS_MAPPINGS.update(NULL_BATCH_MAP)
     NODE_DISPLAY_NAME_MAPPINGS.update(NULL_BATCH_NAMES)
+
+if os.environ.get("EGREGORA_RESAMPLE_BATCH_NODES") == "1":
+    from .egregora_audio_resample_batch import (NODE_CLASS_MAPPINGS as RS_BATCH_MAP, NODE_DISPLAY_NAME_MAPPINGS as RS_BATCH_NAMES)
+    NODE_CLASS_MAPPINGS.update(RS_BATCH_MAP)
+    NODE_DISPLAY_NAME_MAPPINGS.update(RS_BATCH_NAMES)
 
 __all__ = ["NODE_CLASS_MAPPINGS", "NODE_DISPLAY_NAME_MAPPINGS"]

@@ -1,7 +1,8 @@
 """Many clips through `Egregora DAC Encode` / `Egregora DAC Decode` at once: encode_many / decode_many.
 
 Per clip they do what the single nodes do -- rate conversion to the model's rate, the codec, rate conversion back -- but the clips
-share the launches: one egr_resample_poly_tracks per source rate and direction (the bits of the single call's resample.resample_hq),
+share the launches: one egr_resample_poly_tracks per source rate and direction (the bits of the single call's resample.resample_hq;
+with EGREGORA_SINC_RESAMPLE=1 one egr_resample_sinc_tracks, the bits of resample.resample_sinc: resample.codec_resample decides),
 and the codec through DacEngine.encode_many / decode_many (one egr_dacmany_encode / _decode per wave, rows of their own lengths
 inside tensors of the wave's longest).  The clips go up in one transfer and the results come down in one transfer per tensor kind.
 A clip's result equals the single node's to fp32 round-off (the launcher chooses tiles from the padded shape), not bit for bit.
@@ -10,8 +11,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 
-from . import dac_engine, dac_weights, native
-from .dfn_many import resample_group
+from . import dac_engine, dac_weights, native, resample
 
 
 def engine_for(model_type: str) -> "dac_engine.DacEngine":
@@ -31,7 +31,7 @@ def _to_rate(xs: List[torch.Tensor], srs: Sequence[int], target: Optional[int], 
     out = list(xs)
     for sr, idx in groups.items():
         a, b = (target, sr) if back else (sr, target)
-        for i, y in zip(idx, resample_group([xs[i] for i in idx], a, b)):
+        for i, y in zip(idx, resample.codec_resample([xs[i] for i in idx], a, b)):
             out[i] = y
     return out
 

@@ -6,7 +6,8 @@ Registered only when the environment variable EGREGORA_CODEC_NODES is "1" at imp
 Deliberate, documented differences from the reference (SPEC.md 4e):
   DAC-Q1  the reference hands `model.encode` a 2-D [C, T] tensor and `model.decode` a Python list, which upstream rejects.  Not
           reproduced: the C channels of a batch element are C mono rows, as upstream's own `compress` treats channels.
-  DAC-Q2  rate conversion uses this pack's polyphase kernel (resample.resample_hq), not torchaudio.
+  DAC-Q2  rate conversion uses this pack's polyphase kernel (resample.resample_hq), not torchaudio.  With EGREGORA_SINC_RESAMPLE=1
+          (read at call time) it uses the windowed-sinc kernel at torchaudio's defaults, as the reference does (resample.codec_resample).
   The checkpoint is never downloaded (dac_weights.discover); `device` is accepted and ignored, there is no CPU path.
   The DICT also carries `codes`: a list over the batch of int64 [C, n_codebooks, frames]; Decode takes a DICT whose `latents` is
   missing or empty from them (dac_engine.from_codes).  Inputs above the workspace budget run in segments (dac_engine.choose_path).
@@ -54,7 +55,7 @@ class Egregora_DAC_Encode:
         for b in range(B):
             x = wav[b].to(dev)  # [C,T]: C mono rows (DAC-Q1)
             if sr != model_sr:
-                x = resample.resample_hq(x, sr, model_sr)
+                x = resample.codec_resample(x, sr, model_sr)
             z, codes = eng.encode(x)
             z_all.append([z.cpu()])
             codes_all.append(codes.to(torch.int64).cpu())
@@ -109,7 +110,7 @@ class Egregora_DAC_Decode:
                 z = z.unsqueeze(0)
             y = eng.decode(z)  # [C,T] at the model's rate
             if model_sr != sr:
-                y = resample.resample_hq(y, model_sr, sr)
+                y = resample.codec_resample(y, model_sr, sr)
             outs.append(y.unsqueeze(0).cpu())
         y_cat = torch.cat(outs, dim=0)  # [B,C,T]
         audio = _make_audio(sr=sr, wav=y_cat)

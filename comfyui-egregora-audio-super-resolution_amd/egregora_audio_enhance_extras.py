@@ -15,7 +15,10 @@ float32 roundings placed exactly where numpy places them in the reference (oracl
 Deliberate, documented differences from the reference:
   Q6  adaptive_vad_source = "none" (and "rnnoise" without pyrnnoise) makes the reference raise a broadcast ValueError for
       every input longer than 10 ms (:672-687); here the strength is simply constant.
-  Q7  rate conversion to / from 48 kHz uses this pack's scipy-polyphase kernel instead of df.io.resample.
+  Q7  rate conversion to / from 48 kHz uses this pack's scipy-polyphase kernel instead of df.io.resample.  This stays so under
+      EGREGORA_SINC_RESAMPLE=1 (which moves the Resample node's "torchaudio" mode and the codec nodes onto the windowed-sinc kernel,
+      resample.resample_sinc): the parameters df.io.resample passes to its resampler are not in the reference, so there is no
+      definition to restate for this stage.
 """
 from typing import Callable, Optional
 

@@ -5,6 +5,8 @@ INPUT_TYPES / RETURN_TYPES / RETURN_NAMES / FUNCTION / CATEGORY and `execute` si
 STFT, per-frame LSD, the percentile's order statistics, the SI-SDR sums and both resamplers run in libegregora_amd.so
 (csrc/egr_glue.hip); the host keeps only the AUDIO coercion rules of the reference (`to_internal_audio`,
 `_normalize_CN`, `make_audio`, :60-103).  No CPU fallback: without the library or a gfx950 device `execute` raises.
+`Resample Audio (HQ)`'s mode "torchaudio" is linear interpolation (torchaudio is not a dependency) unless EGREGORA_SINC_RESAMPLE=1,
+when it runs the windowed-sinc kernel with the reference's parameters and the kaiser_beta widget (resample.resample_sinc).
 The reference's other four evaluation nodes (loudness meter, 1770 gain match, ABX Prepare / Judge) live in
 egregora_audio_eval_loudness.py and are registered when EGREGORA_EVAL_NODES=1.
 """
@@ -76,6 +78,11 @@ class Resample_Audio_HQ:
             # scipy.signal.resample_poly(x[c], up, down) per channel on the device (egr_resample_poly); the reference's
             # kaiser_beta widget only feeds its torchaudio branch (:509-512)
             y = resample.resample_hq(x, src_sr, int(target_sr))
+        elif mode == "torchaudio" and resample.reference_torchaudio_enabled():
+            # EGREGORA_SINC_RESAMPLE=1 (read here, at call time): the reference's torchaudio branch (:512-515) restated on the device,
+            # AF.resample(wf, src, dst, lowpass_filter_width=64, rolloff=0.945, resampling_method="kaiser_window", beta=kaiser_beta)
+            y = resample.resample_sinc(x, src_sr, int(target_sr), lowpass_filter_width=64, rolloff=0.945, method="sinc_interp_kaiser",
+                                       beta=float(kaiser_beta))
         else:
             # "linear", and "torchaudio" where torchaudio is absent (this pack does not depend on it): the reference's
             # np.interp fallback (:514-519)

@@ -110,6 +110,8 @@ SIGNATURES = {
     "egr_chunk_gather": (_i, [_vp, _i, _i64, _i64, _i64, _i, _i, _vp, _vp]),
     "egr_resample_poly": (_i, [_vp, _i, _i64, _i, _i, _vp, _i, _vp, _i64, _vp]),
     "egr_resample_poly_tracks": (_i, [_vp, _vp, _i, _i64, _i, _i, _vp, _i, _vp, _vp]),
+    "egr_resample_sinc": (_i, [_vp, _i, _i64, _i, _i, _i, _i, _vp, _vp, _u, _vp, _i64, _vp]),
+    "egr_resample_sinc_tracks": (_i, [_vp, _vp, _i, _i64, _i, _i, _i, _i, _vp, _vp, _u, _vp, _vp]),
     "egr_chunk_gather_tracks": (_i, [_vp, _vp, _i, _i64, _i64, _vp, _vp]),
     "egr_wola_tracks": (_i, [_vp, _vp, _i, _i64, _i64, _i64, _i64, _vp, _vp, _vp]),
     "egr_conv_nhwc": (_i, [_vp] * 6 + [_i] * 15 + [_f, _vp]),

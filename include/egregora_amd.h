@@ -536,6 +536,33 @@ int egr_chunk_gather_tracks(const float* x, const int64_t* rows, int n_rows, int
 int egr_wola_tracks(const float* preds, const int64_t* tracks, int n_tracks, int64_t total_out, int64_t lp, int64_t win,
                     int64_t hop, const float* window, float* out, void* stream);
 
+/* Windowed-sinc rational-rate resampler with the definition of torchaudio.functional.resample (SPEC.md 4f; the reference's
+ * "torchaudio" mode of Resample Audio (HQ), egregora_audio_eval_pack.py:512-515, and its codec path,
+ * egregora_audio_enhance_extras.py:66-75 and :777).  o = src / gcd, n = dst / gcd, width = ceil(lowpass_filter_width * o / base).
+ * The host designs the per-phase taps in float64 (resample.design_sinc) and passes the COMPACT table: per phase only the `run`
+ * contiguous taps with |t| < lowpass_filter_width, zero filled to the same count (1 <= run <= 2*width + o),
+ *   table      device float[run][n], tap-major: table[s*n + p] is tap first_tap[p] + s of phase p;
+ *   first_tap  device int32[n], each inside [0, 2*width + o - run] (values outside are clamped into it).
+ * Output m = i*n + p of a track is sum_s table[s*n + p] * x[i*o + first_tap[p] - width + s], s ascending, x zero outside the
+ * clip, one float32 fused multiply-add per tap: the same bits whichever kernel variant runs and in both calls.
+ *   x [channels][n_in], y [channels][n_out], n_out = ceil(n_in*n/o).
+ * Two kernel variants: a workgroup stages the input span of its 256 outputs in LDS when that span is at most 4096 floats for
+ * (o, n, width) (never a matter of a clip's length), otherwise every thread reads x from global memory; EGR_SINC_FORCE_DIRECT in
+ * `flags` takes the second one always.
+ * egr_resample_sinc_tracks is the many-clip form with egr_resample_poly_tracks' contract: tracks [n_tracks][4] = (in offset
+ * into x, n_in >= 1, out offset into y, n_out = ceil(n_in*n/o)), out offsets back to back from 0 to total_out, a flat grid over
+ * total_out, the table not validated.
+ * Refused before anything is launched (EGR_ERR_ARG, or EGR_ERR_UNSUPPORTED for the two caps; egr_last_error says which):
+ * lengths or counts below 1, channels outside [1, 65535], o or n outside [1, 2^24], width outside [1, 2^28], run outside
+ * [1, 2*width + o], n*run above 2^29 floats, n_in above 2^44 or n_in*n above 2^60, n_out other than ceil(n_in*n/o), more than
+ * 2^32 - 256 outputs in one call, more tracks than outputs, unknown flag bits, null pointers.  No atomics; both only enqueue
+ * work on `stream`. */
+#define EGR_SINC_FORCE_DIRECT 0x1u
+int egr_resample_sinc(const float* x, int channels, int64_t n_in, int o, int n, int width, int run, const float* table,
+                      const int32_t* first_tap, unsigned flags, float* y, int64_t n_out, void* stream);
+int egr_resample_sinc_tracks(const float* x, const int64_t* tracks, int n_tracks, int64_t total_out, int o, int n, int width,
+                             int run, const float* table, const int32_t* first_tap, unsigned flags, float* y, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * FlashSR network operators (channels-last activations, exact fp32).  Together they stand in for the
  * upstream call `self._model(x, lowpass_input=...)` at egregora_audio_super_resolution.py:366-369; the
