@@ -1273,9 +1273,7 @@ int many_shape(const Dac* m, const char* who, int rows, int64_t pad_frames, int 
 int bind_tables(Walk& w, const ManyShape& s, char** tab) {
     *tab = (char*)w.take((s.table_bytes + 3) / 4);
     if (!w.go()) return w.rc;
-    EGR_HIP(hipMemcpyAsync(*tab, w.m.tables.p, s.table_bytes, hipMemcpyHostToDevice, w.st));        // one copy for all tables
-    EGR_HIP(hipEventRecord(w.m.tables.copied, w.st));
-    return EGR_OK;
+    return w.m.tables.upload(*tab, s.table_bytes, w.st);        // one copy for all tables
 }
 
 int walk_many_encode(Walk& w, const float* x, const ManyShape& s, float* z, int* codes, float* ze_out) {

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "egr_handle.h"
+#include "egr_ragged_index.h"
 
 namespace egr {
 namespace {
@@ -49,16 +50,6 @@ struct Tracks {
     const int64_t* soff = nullptr;         // [n + 1]
     int n = 0;
 };
-
-// the track whose samples hold flat index i: the largest b < n with soff[b] <= i
-__device__ __forceinline__ int track_of(const int64_t* __restrict__ soff, int n, int64_t i) {
-    int lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (soff[mid] <= i) lo = mid; else hi = mid;
-    }
-    return lo;
-}
 
 // ------------------------------------------------------------------------------------------------ analysis / features
 // Block (f, b) analyses frame f0 + f of channel b into row f of spec [C][nF][Fq] (f0 = 0: the whole file; a segment otherwise).
@@ -492,7 +483,7 @@ __global__ void k_dfn_ola(const float* __restrict__ frames, const float* __restr
         int64_t b = i / cnt, s = out_lo + (i - b * cnt);
         int64_t fb = b * nA, yb = b * T;           // the row of frame asm_lo in frames, the channel's first sample in y
         if constexpr (TRK) {
-            b = track_of(tk.soff, tk.n, i);
+            b = track_of((const long long*)tk.soff, tk.n, 1, 0, i);      // egr_ragged_index.h: the largest b < n with soff[b] <= i
             s = i - tk.soff[b];
             fb = tk.foff[b];
             nF = tk.foff[b + 1] - fb;
@@ -1572,8 +1563,7 @@ int run_tracks(M* mp, const char* who, const float* x, const int64_t* tracks, in
     }
     float* table = nullptr;
     tracks_need(m, tt, k.B, m.X, (char*)k.ws.p, &table);
-    EGR_HIP(hipMemcpyAsync(table, k.stage.p, table_bytes, hipMemcpyHostToDevice, st));      // one copy for all tables
-    EGR_HIP(hipEventRecord(k.stage.copied, st));
+    EGR_TRY(k.stage.upload(table, table_bytes, st));      // one copy for all tables
     Tracks tk;
     tk.soff = (const int64_t*)table;
     tk.xoff = tk.soff + n_tracks + 1;

@@ -1,41 +1,21 @@
 // Index arithmetic of the many-pair metrics and the many-clip loudness meter (egr_metrics_pairs, egr_loudness_tracks in egr_glue.hip),
 // kept free of device-only constructs so that the same text compiles for the host: tools/evalmany_host_check.cpp walks it under
 // -fsanitize=address,undefined.  The host fills one table row per pair / clip with these functions (every refusal is decided here, from
-// integers alone, before anything is allocated or launched); the kernels find their row in the ascending prefix columns with track_of.
+// integers alone, before anything is allocated or launched); the kernels find their row in the ascending prefix columns with track_of
+// (egr_ragged_index.h).
 #pragma once
 
-#if defined(__HIPCC__)
-#include <hip/hip_runtime.h>
-#define EGR_EVAL_HD __host__ __device__ __forceinline__
-#else
-#define EGR_EVAL_HD inline
-#endif
+#include "egr_ragged_index.h"
 
 namespace egr {
 
 constexpr int EGR_METRICS_CHUNK = 4096;          // samples per SI-SDR partial sum: one workgroup of 256 threads, 16 samples each
-// Every grid equals its work count, and HIP launches no grid with gridDim.x * blockDim.x >= 2^32: a total's cap follows from the block
-// size of the kernel that consumes it.  The host refuses a table beyond a cap before anything is copied or launched.
-constexpr long long EVAL_MAX_WORK_ITEMS = 4294967295LL;
-constexpr long long eval_max_grid(int threads) { return EVAL_MAX_WORK_ITEMS / threads; }
-constexpr long long EVAL_MAX_GRID_256 = eval_max_grid(256);          // 2^24 - 1: frames, SI-SDR chunks, loudness blocks, peak tiles
+// (the caps of a grid and of an offset are in egr_ragged_index.h)
 constexpr long long EVAL_MAX_PAIRS = eval_max_grid(1024);            // 2^22 - 1: k_pair_lsd_reduce has one 1024-thread workgroup per pair
 constexpr long long EVAL_MAX_KW_CHUNKS = eval_max_grid(64) * 64;     // thread chunks of k_kweight_mono_tracks: 64 to a workgroup
-constexpr long long EVAL_MAX_OFF = 1LL << 60;    // offsets, strides and lengths in floats: sums of two stay inside int64
-
-// last t in [0, n) with tab[t * stride + col] <= i; the column ascends and starts at 0
-EGR_EVAL_HD int track_of(const long long* __restrict__ tab, int n, int stride, int col, long long i) {
-    int lo = 0, hi = n - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (tab[(size_t)mid * stride + col] <= i) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
 
 // frames = 1 + max(0, (n - block) / hop): the frame rule of egr_stft_mag and of the loudness block families
-EGR_EVAL_HD long long eval_frames(long long n, long long block, long long hop) { return 1 + (n > block ? (n - block) / hop : 0); }
-EGR_EVAL_HD long long eval_ceil_div(long long a, long long b) { return (a + b - 1) / b; }
+EGR_HD long long eval_frames(long long n, long long block, long long hop) { return 1 + (n > block ? (n - block) / hop : 0); }
 
 enum EvalRefusal { EVAL_OK = 0, EVAL_SHORT = 1, EVAL_BAD_ROW = 2, EVAL_OFFSET = 3, EVAL_TOTAL = 4 };
 
@@ -44,17 +24,17 @@ constexpr int MP_IN_COLS = 7;
 // Device row (12 int64): the caller's seven, then frames, first flat frame, first flat chunk, the two ranks of numpy's linear 95th percentile.
 enum { MP_OFF_A = 0, MP_CA, MP_LD_A, MP_OFF_B, MP_CB, MP_LD_B, MP_N, MP_FRAMES, MP_FRAME0, MP_CHUNK0, MP_KLO, MP_KHI, MP_COLS };
 
-EGR_EVAL_HD long long metrics_chunks(long long n) { return eval_ceil_div(n, EGR_METRICS_CHUNK); }
+EGR_HD long long metrics_chunks(long long n) { return eval_ceil_div(n, EGR_METRICS_CHUNK); }
 
 // side (offset, channels, stride) holding n samples per row: the last float read is offset + (channels - 1) stride + n - 1
-EGR_EVAL_HD bool eval_side_ok(long long off, long long ch, long long ld, long long n) {
+EGR_HD bool eval_side_ok(long long off, long long ch, long long ld, long long n) {
     if (off < 0 || off > EVAL_MAX_OFF || ch < 1 || ch > 65535 || ld < n || ld > EVAL_MAX_OFF / 65536) return false;
     return off + (ch - 1) * ld + n <= EVAL_MAX_OFF;
 }
 
 // One row of the device table from one caller's row; *frame0 / *chunk0 are the running totals (in: this pair's first, out: the next
 // pair's).  Nothing is written on a refusal.
-EGR_EVAL_HD int metrics_fill(const long long* in, int n_fft, int hop, long long* frame0, long long* chunk0, long long* row) {
+EGR_HD int metrics_fill(const long long* in, int n_fft, int hop, long long* frame0, long long* chunk0, long long* row) {
     const long long n = in[6];
     if (n < 1) return EVAL_SHORT;
     if (n > EVAL_MAX_OFF) return EVAL_OFFSET;
@@ -75,18 +55,13 @@ EGR_EVAL_HD int metrics_fill(const long long* in, int n_fft, int hop, long long*
 }
 
 // flat frame -> pair and the frame inside the pair; flat chunk -> pair and the chunk's first sample and length inside the pair
-EGR_EVAL_HD int metrics_frame_of(const long long* tab, int n_pairs, long long flat, long long* f) {
+EGR_HD int metrics_frame_of(const long long* tab, int n_pairs, long long flat, long long* f) {
     const int p = track_of(tab, n_pairs, MP_COLS, MP_FRAME0, flat);
     *f = flat - tab[(size_t)p * MP_COLS + MP_FRAME0];
     return p;
 }
-EGR_EVAL_HD int metrics_chunk_of(const long long* tab, int n_pairs, long long flat, long long* first, long long* len) {
-    const int p = track_of(tab, n_pairs, MP_COLS, MP_CHUNK0, flat);
-    const long long* e = tab + (size_t)p * MP_COLS;
-    *first = (flat - e[MP_CHUNK0]) * EGR_METRICS_CHUNK;
-    const long long left = e[MP_N] - *first;
-    *len = left < EGR_METRICS_CHUNK ? left : EGR_METRICS_CHUNK;
-    return p;
+EGR_HD int metrics_chunk_of(const long long* tab, int n_pairs, long long flat, long long* first, long long* len) {
+    return tile_of(tab, n_pairs, MP_COLS, MP_CHUNK0, MP_N, EGR_METRICS_CHUNK, flat, first, len);
 }
 
 // ---- clips of one (sample rate, channel count) group.  Caller's row (2 int64): offset of the clip's [C][n] block in x, n.
@@ -99,7 +74,7 @@ constexpr int LT_TILE = 256;
 struct LoudTotals { long long mono, chunks, fa, fb, tiles; };
 
 // blk_b = 0: no second family (its column stays a copy of the first, never searched); up = 0: no true peak
-EGR_EVAL_HD int loud_fill(const long long* in, int channels, int L, long long blk_a, long long hop_a, long long blk_b, long long hop_b,
+EGR_HD int loud_fill(const long long* in, int channels, int L, long long blk_a, long long hop_a, long long blk_b, long long hop_b,
                           int up, LoudTotals* t, long long* row) {
     const long long n = in[1];
     if (n < 1) return EVAL_SHORT;
@@ -118,7 +93,7 @@ EGR_EVAL_HD int loud_fill(const long long* in, int channels, int L, long long bl
 }
 
 // flat index in one of the prefix columns -> clip and the index inside the clip
-EGR_EVAL_HD int loud_item_of(const long long* tab, int n_clips, int col, long long flat, long long* local) {
+EGR_HD int loud_item_of(const long long* tab, int n_clips, int col, long long flat, long long* local) {
     const int c = track_of(tab, n_clips, LT_COLS, col, flat);
     *local = flat - tab[(size_t)c * LT_COLS + col];
     return c;

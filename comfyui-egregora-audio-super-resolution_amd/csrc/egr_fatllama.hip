@@ -23,9 +23,6 @@
 #include "egr_fatllama_int.h"
 #include "egr_null_index.h"
 
-#include <map>
-#include <mutex>
-
 namespace egr {
 
 // MODE 0: first  (y -> time threshold -> FFT -> twiddle -> state)          [outermost pass only]
@@ -1871,8 +1868,6 @@ int delays_plan(const int64_t* pairs, int n_pairs, int64_t n, DelaysPlan* P) {
     return EGR_OK;
 }
 
-std::mutex g_nd_mu;
-std::map<int, TableStage> g_nd_stage;      // device -> pinned staging of the table (under g_nd_mu)
 }  // namespace
 
 extern "C" size_t egr_nullmany_delays_workspace_bytes(const int64_t* pairs, int n_pairs, int64_t n) {
@@ -1898,16 +1893,8 @@ extern "C" int egr_nullmany_delays(egr_fatllama_plan* p, const float* a, const f
               "egr_nullmany_delays: %d pairs on %lld planes of the plan's column pass exceed gridDim.y", n_pairs, planes);
     hipStream_t st = (hipStream_t)stream;
     char* base = (char*)ws;
-    {
-        std::lock_guard<std::mutex> lk(g_nd_mu);
-        TableStage& stage = g_nd_stage[p->device];
-        const size_t bytes = P.tab.size() * sizeof(long long);
-        rc = stage.reserve(bytes);
-        if (rc) return rc;
-        memcpy(stage.p, P.tab.data(), bytes);
-        EGR_HIP(hipMemcpyAsync(base, stage.p, bytes, hipMemcpyHostToDevice, st));
-        EGR_HIP(hipEventRecord(stage.copied, st));
-    }
+    rc = upload_table({{P.tab.data(), P.tab.size() * sizeof(long long)}}, base, st);
+    if (rc) return rc;
     const long long* tab = (const long long*)base;
     float* z = (float*)(base + P.z_off);
     float* y = (float*)(base + P.y_off);

@@ -110,7 +110,7 @@ __global__ __launch_bounds__(256) void k_resample_poly(const float* __restrict__
 // longest one is, and no grid dimension counts tracks or rows.  A workgroup's 256 consecutive samples mostly belong to one track:
 // the group searches the table's ascending output offsets once for its first sample (the same value in every lane), each thread
 // then steps forward over the few track starts inside the group's stretch.
-// (track_of, the search, is in egr_eval_index.h: host and device share it)
+// (track_of, the search, is in egr_ragged_index.h: host and device share it)
 
 // rows[r] = (track offset into x, track length, chunk index k); chunks [n_rows][win]
 __global__ __launch_bounds__(256) void k_chunk_gather_tracks(const float* __restrict__ x, const long long* __restrict__ rows,
@@ -1015,24 +1015,7 @@ static inline void kweight_chunking(float k, int* L, int* W) {
     *L = (w + 2) / 3;
 }
 
-static std::mutex g_eval_mu;
-static std::map<int, TableStage> g_eval_stage;      // device -> pinned staging of the tables (under g_eval_mu)
 static inline size_t eval_align(size_t b) { return (b + 255) & ~(size_t)255; }
-
-// the table goes up in one asynchronous copy from pinned memory
-static int eval_upload(const std::vector<long long>& tab, void* dst, hipStream_t st) {
-    int dev = 0;
-    EGR_HIP(hipGetDevice(&dev));
-    std::lock_guard<std::mutex> lk(g_eval_mu);
-    TableStage& stage = g_eval_stage[dev];
-    const size_t bytes = tab.size() * sizeof(long long);
-    const int rc = stage.reserve(bytes);
-    if (rc) return rc;
-    memcpy(stage.p, tab.data(), bytes);
-    EGR_HIP(hipMemcpyAsync(dst, stage.p, bytes, hipMemcpyHostToDevice, st));
-    EGR_HIP(hipEventRecord(stage.copied, st));
-    return EGR_OK;
-}
 
 static const char* eval_why(int r) {
     return r == EVAL_SHORT ? "n < 1" : r == EVAL_BAD_ROW ? "channels outside 1 .. 65535 or a row stride below n"
@@ -1504,7 +1487,7 @@ extern "C" int egr_metrics_pairs(const float* a, const float* b, const int64_t* 
         rc = stft_tables(n_fft, &t);
         if (rc) return rc;
     }
-    rc = eval_upload(P.tab, base, st);
+    rc = upload_table({{P.tab.data(), P.tab.size() * sizeof(long long)}}, base, st);
     if (rc) return rc;
     if (launches) *launches = P.launches;
     if (flags & 1) {
@@ -1564,7 +1547,7 @@ extern "C" int egr_loudness_tracks(const float* x, const int64_t* clips, int n_c
     char* base = (char*)ws;
     const long long* tab = (const long long*)base;
     float* mono = (float*)(base + P.mono_off);
-    rc = eval_upload(P.tab, base, st);
+    rc = upload_table({{P.tab.data(), P.tab.size() * sizeof(long long)}}, base, st);
     if (rc) return rc;
     if (launches) *launches = P.launches;
     const dim3 grid((unsigned)((P.t.chunks + 63) / 64));
@@ -1609,7 +1592,7 @@ extern "C" int egr_nullmany_shift_fir(const float* x, const int64_t* rows, int n
     EGR_CHECK(ws_bytes >= P.total, EGR_ERR_ARG, "egr_nullmany_shift_fir: workspace of %zu bytes, %zu needed", ws_bytes, P.total);
     EGR_CHECK(((uintptr_t)ws & 7) == 0, EGR_ERR_ARG, "egr_nullmany_shift_fir: the workspace (int64 table) must be 8-byte aligned");
     hipStream_t st = (hipStream_t)stream;
-    rc = eval_upload(P.tab, ws, st);
+    rc = upload_table({{P.tab.data(), P.tab.size() * sizeof(long long)}}, ws, st);
     if (rc) return rc;
     if (launches) *launches = 1;
     const long long* tab = (const long long*)ws;
@@ -1646,7 +1629,7 @@ extern "C" int egr_nullmany_mix(const float* a, const float* b, const int64_t* p
     memcpy(P.tab.data() + P.prm_off / sizeof(long long), params, (size_t)n_pairs * 4 * sizeof(float));
     hipStream_t st = (hipStream_t)stream;
     char* base = (char*)ws;
-    rc = eval_upload(P.tab, base, st);
+    rc = upload_table({{P.tab.data(), P.tab.size() * sizeof(long long)}}, base, st);
     if (rc) return rc;
     if (launches) *launches = 2;
     const long long* tab = (const long long*)base;

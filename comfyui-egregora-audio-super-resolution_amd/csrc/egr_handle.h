@@ -4,6 +4,12 @@
 #pragma once
 #include "egr_common.h"
 
+#include <string.h>
+
+#include <initializer_list>
+#include <map>
+#include <mutex>
+
 namespace egr {
 
 #define EGR_TRY(x) do { int rc__ = (x); if (rc__ != EGR_OK) return rc__; } while (0)
@@ -66,12 +72,43 @@ struct TableStage {
         bytes = need;
         return EGR_OK;
     }
+    // the copy of the first `n` staged bytes to dst (device) on st, and the event behind it
+    int upload(void* dst, size_t n, hipStream_t st) {
+        EGR_HIP(hipMemcpyAsync(dst, p, n, hipMemcpyHostToDevice, st));
+        EGR_HIP(hipEventRecord(copied, st));
+        return EGR_OK;
+    }
     void release() {
         if (copied) { (void)hipEventSynchronize(copied); (void)hipEventDestroy(copied); }
         if (p) (void)hipHostFree(p);
         p = nullptr; bytes = 0; copied = nullptr;
     }
 };
+
+// Tables of a call that has no handle to keep a stage in (the eval and null-test calls of egr_glue.hip, egr_nullmany_delays,
+// egr_wpemany_dereverb): the spans go, back to back, through the current device's stage of one registry and up to dst in one
+// asynchronous copy.  One registry for all of them: a call waits (in reserve) for the previous table copy on its device, whichever
+// family made it -- a few kilobytes, the same wait each family made on its own previous copy when it had a stage to itself.
+// The stage is the CURRENT device's (hipGetDevice), the one the call launches on: egr_nullmany_delays, which used to take its plan's
+// device, runs on that device like every other call of a plan.
+struct TableSpan {
+    const void* p;
+    size_t bytes;
+};
+inline int upload_table(std::initializer_list<TableSpan> spans, void* dst, hipStream_t st) {
+    static std::mutex mu;
+    static std::map<int, TableStage> stages;      // device -> pinned staging (under mu)
+    int dev = 0;
+    EGR_HIP(hipGetDevice(&dev));
+    size_t bytes = 0;
+    for (const TableSpan& s : spans) bytes += s.bytes;
+    std::lock_guard<std::mutex> lk(mu);
+    TableStage& stage = stages[dev];
+    EGR_TRY(stage.reserve(bytes));
+    char* h = (char*)stage.p;
+    for (const TableSpan& s : spans) { memcpy(h, s.p, s.bytes); h += s.bytes; }
+    return stage.upload(dst, bytes, st);
+}
 
 // a hipMalloc'ed buffer and its hipFree (move-only); whoever must wait for the device before a free does so before reset()
 struct DevBuf {

@@ -2,7 +2,7 @@
 // egr_glue.hip), kept free of device-only constructs so that the same text compiles for the host: tools/nullmany_host_check.cpp walks it
 // under -fsanitize=address,undefined.  As in egr_eval_index.h the host fills one table row per pair / row with these functions (every
 // refusal is decided here, from integers alone, before anything is allocated or launched) and the kernels find their row in the ascending
-// prefix columns with track_of.  Every grid is flat and equals its work count.
+// prefix columns with track_of / tile_of (egr_ragged_index.h).  eval_side_ok and the chunk length are egr_eval_index.h's.  Every grid is flat and equals its work count.
 #pragma once
 
 #include "egr_eval_index.h"
@@ -19,7 +19,7 @@ enum NullRefusal { NULL_OK = 0, NULL_SHORT = 1, NULL_BAD_ROW = 2, NULL_OFFSET = 
                    NULL_CHANNELS = 7, NULL_TAPS = 8 };
 
 // the single path's rule (device_ops.xcorr_delay): n = 1; while (n < na + nb) n <<= 1, with na = nb = n_common
-EGR_EVAL_HD long long null_transform_length(long long n_common) {
+EGR_HD long long null_transform_length(long long n_common) {
     long long n = 1;
     while (n < 2 * n_common) n <<= 1;
     return n;
@@ -29,10 +29,10 @@ EGR_EVAL_HD long long null_transform_length(long long n_common) {
 // n_common = min(len_a, len_b); max_shift in samples.  All rows of one call share the transform length n.
 enum { ND_OFF_A = 0, ND_CA, ND_LD_A, ND_OFF_B, ND_CB, ND_LD_B, ND_N, ND_MS, ND_COLS };
 
-EGR_EVAL_HD long long delays_tiles(long long n) { return eval_ceil_div(n, NULL_TILE); }
+EGR_HD long long delays_tiles(long long n) { return eval_ceil_div(n, NULL_TILE); }
 
 // *tile0: the running total of pack tiles (in: this pair's first, out: the next pair's)
-EGR_EVAL_HD int delays_fill(const long long* in, long long n, long long* tile0, long long* row) {
+EGR_HD int delays_fill(const long long* in, long long n, long long* tile0, long long* row) {
     const long long nc = in[ND_N];
     if (nc < 1) return NULL_SHORT;
     if (nc > EVAL_MAX_OFF / 4) return NULL_OFFSET;
@@ -47,7 +47,7 @@ EGR_EVAL_HD int delays_fill(const long long* in, long long n, long long* tile0, 
 }
 
 // flat pack tile -> pair and the tile's first sample (every pair has the same number of tiles)
-EGR_EVAL_HD int delays_tile_of(long long n, long long flat, long long* first) {
+EGR_HD int delays_tile_of(long long n, long long flat, long long* first) {
     const long long t = delays_tiles(n);
     *first = (flat % t) * NULL_TILE;
     return (int)(flat / t);
@@ -58,7 +58,7 @@ EGR_EVAL_HD int delays_tile_of(long long n, long long flat, long long* first) {
 constexpr int SF_IN_COLS = 6;
 enum { SF_IN = 0, SF_N_IN, SF_SHIFT, SF_TAPS, SF_OUT, SF_N_OUT, SF_TILE0, SF_SPARE, SF_COLS };
 
-EGR_EVAL_HD int shiftfir_fill(const long long* in, long long n_tap_rows, long long* tile0, long long* row) {
+EGR_HD int shiftfir_fill(const long long* in, long long n_tap_rows, long long* tile0, long long* row) {
     const long long n_in = in[SF_N_IN], n_out = in[SF_N_OUT];
     if (n_in < 1 || n_out < 1) return NULL_SHORT;
     if (n_in > EVAL_MAX_OFF / 4 || n_out > EVAL_MAX_OFF / 4 || in[SF_SHIFT] > EVAL_MAX_OFF / 4 || in[SF_SHIFT] < -(EVAL_MAX_OFF / 4)) return NULL_OFFSET;
@@ -74,13 +74,8 @@ EGR_EVAL_HD int shiftfir_fill(const long long* in, long long n_tap_rows, long lo
 }
 
 // flat output tile -> row, the tile's first output sample and its length
-EGR_EVAL_HD int shiftfir_tile_of(const long long* tab, int n_rows, long long flat, long long* first, long long* len) {
-    const int r = track_of(tab, n_rows, SF_COLS, SF_TILE0, flat);
-    const long long* e = tab + (size_t)r * SF_COLS;
-    *first = (flat - e[SF_TILE0]) * NULL_TILE;
-    const long long left = e[SF_N_OUT] - *first;
-    *len = left < NULL_TILE ? left : NULL_TILE;
-    return r;
+EGR_HD int shiftfir_tile_of(const long long* tab, int n_rows, long long flat, long long* first, long long* len) {
+    return tile_of(tab, n_rows, SF_COLS, SF_TILE0, SF_N_OUT, NULL_TILE, flat, first, len);
 }
 
 // ---- mix.  Caller's row (8 int64): offset of the reference in a, its channels, its row stride; the same for the aligned signal in b;
@@ -89,9 +84,9 @@ EGR_EVAL_HD int shiftfir_tile_of(const long long* tab, int n_rows, long long fla
 constexpr int NM_IN_COLS = 8;
 enum { NM_OFF_A = 0, NM_LD_A, NM_OFF_B, NM_LD_B, NM_CH, NM_N, NM_OUT, NM_CHUNK0, NM_COLS };
 
-EGR_EVAL_HD long long mix_chunks(long long n) { return eval_ceil_div(n, NULL_CHUNK); }
+EGR_HD long long mix_chunks(long long n) { return eval_ceil_div(n, NULL_CHUNK); }
 
-EGR_EVAL_HD int mix_fill(const long long* in, long long* chunk0, long long* row) {
+EGR_HD int mix_fill(const long long* in, long long* chunk0, long long* row) {
     const long long n = in[6];
     if (n < 1) return NULL_SHORT;
     if (n > EVAL_MAX_OFF / 65536) return NULL_OFFSET;
@@ -107,13 +102,8 @@ EGR_EVAL_HD int mix_fill(const long long* in, long long* chunk0, long long* row)
 }
 
 // flat chunk -> pair, the chunk's first sample and its length (no chunk spans two pairs)
-EGR_EVAL_HD int mix_chunk_of(const long long* tab, int n_pairs, long long flat, long long* first, long long* len) {
-    const int p = track_of(tab, n_pairs, NM_COLS, NM_CHUNK0, flat);
-    const long long* e = tab + (size_t)p * NM_COLS;
-    *first = (flat - e[NM_CHUNK0]) * NULL_CHUNK;
-    const long long left = e[NM_N] - *first;
-    *len = left < NULL_CHUNK ? left : NULL_CHUNK;
-    return p;
+EGR_HD int mix_chunk_of(const long long* tab, int n_pairs, long long flat, long long* first, long long* len) {
+    return tile_of(tab, n_pairs, NM_COLS, NM_CHUNK0, NM_N, NULL_CHUNK, flat, first, len);
 }
 
 #if defined(__HIPCC__)

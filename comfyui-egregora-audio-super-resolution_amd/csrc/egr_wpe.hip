@@ -484,7 +484,6 @@ struct WpeManyPlan {
     WpeGeom g;
     WpeLds L;
 };
-static std::map<int, TableStage> g_wpe_stage;                        // device -> pinned staging of the tables (under g_wpe_mu)
 
 // what wpe_check_framing refuses, without its tables: n_fft even, 4 .. 4096, no prime factor of n_fft / 2 above 13
 static bool wpe_nfft_ok(int n_fft) {
@@ -678,21 +677,11 @@ extern "C" int egr_wpemany_dereverb(const float* x, const int64_t* clips, int n_
     const WpeClip* dclips = (const WpeClip*)(base + P.table_off);
     const long long* dstft = (const long long*)(dclips + n_clips);
     const long long* distft = dstft + n_clips + 1;
-    {   // the three tables go up in one asynchronous copy from pinned memory
-        int dev = 0;
-        EGR_HIP(hipGetDevice(&dev));
-        std::lock_guard<std::mutex> lk(g_wpe_mu);
-        TableStage& stage = g_wpe_stage[dev];
-        rc = stage.reserve(P.table_bytes);
-        if (rc) return rc;
-        char* h = (char*)stage.p;
-        memcpy(h, P.clips.data(), (size_t)n_clips * sizeof(WpeClip));
-        memcpy(h + (size_t)n_clips * sizeof(WpeClip), P.stft_off.data(), ((size_t)n_clips + 1) * sizeof(long long));
-        memcpy(h + (size_t)n_clips * sizeof(WpeClip) + ((size_t)n_clips + 1) * sizeof(long long), P.istft_off.data(),
-               ((size_t)n_clips + 1) * sizeof(long long));
-        EGR_HIP(hipMemcpyAsync(base + P.table_off, h, P.table_bytes, hipMemcpyHostToDevice, st));
-        EGR_HIP(hipEventRecord(stage.copied, st));
-    }
+    // the three tables go up in one asynchronous copy from pinned memory
+    rc = upload_table({{P.clips.data(), (size_t)n_clips * sizeof(WpeClip)},
+                       {P.stft_off.data(), ((size_t)n_clips + 1) * sizeof(long long)},
+                       {P.istft_off.data(), ((size_t)n_clips + 1) * sizeof(long long)}}, base + P.table_off, st);
+    if (rc) return rc;
     const int bins = n_fft / 2 + 1;
     hipLaunchKernelGGL(k_wpe_stft_many, dim3((unsigned)P.stft_off[n_clips]), dim3(256), (size_t)WPE_FT * (n_fft / 2) * sizeof(float2), st, x,
                        dclips, dstft, n_clips, channels, n_fft, hop, w.win, t.fd, t.tw, t.wsplit, base);

@@ -9,14 +9,13 @@
 // tid, tid + 256, ... and keeps their 16 complex-double sums in registers over the whole frame sweep.
 #pragma once
 
+#include "egr_ragged_index.h"
+
 #if defined(__HIPCC__)
-#include <hip/hip_runtime.h>
-#define EGR_WPE_HD __host__ __device__ __forceinline__
 typedef float2 wpe_c32;
 typedef double2 wpe_c64;
 #else
 #include <math.h>
-#define EGR_WPE_HD inline
 struct wpe_c32 { float x, y; };
 struct wpe_c64 { double x, y; };
 #endif
@@ -38,7 +37,7 @@ struct WpeGeom {
     int tri, nblocks;  // blocks in the triangle over the first nbk block rows; all blocks
 };
 
-EGR_WPE_HD WpeGeom wpe_geom(int D, int taps, int delay) {
+EGR_HD WpeGeom wpe_geom(int D, int taps, int delay) {
     WpeGeom g;
     g.D = D; g.taps = taps; g.delay = delay;
     g.K = D * taps;
@@ -54,7 +53,7 @@ EGR_WPE_HD WpeGeom wpe_geom(int D, int taps, int delay) {
 }
 
 // block b -> (block row, block column): the triangle row by row, then the full-width block rows below it
-EGR_WPE_HD void wpe_block(const WpeGeom& g, int b, int* bi, int* bj) {
+EGR_HD void wpe_block(const WpeGeom& g, int b, int* bi, int* bj) {
     if (b < g.tri) {
         int r = 0;
         while ((r + 1) * (r + 2) / 2 <= b) ++r;
@@ -68,7 +67,7 @@ EGR_WPE_HD void wpe_block(const WpeGeom& g, int b, int* bi, int* bj) {
 }
 
 // offset of row r's sample for tile frame 0 inside the tile [D][LDT] (tile column H is the tile's first frame)
-EGR_WPE_HD int wpe_row_base(const WpeGeom& g, int r) {
+EGR_HD int wpe_row_base(const WpeGeom& g, int r) {
     if (r < g.K) {
         const int k = r / g.D, d = r - k * g.D;
         return d * g.LDT + (g.taps - 1 - k);          // H - delay - k
@@ -77,13 +76,13 @@ EGR_WPE_HD int wpe_row_base(const WpeGeom& g, int r) {
 }
 
 // tile element e (0 .. D LDT - 1) of the tile starting at frame t0 -> channel and frame (frame outside [0, T): zero)
-EGR_WPE_HD void wpe_tile_src(const WpeGeom& g, int e, int t0, int* d, int* t) {
+EGR_HD void wpe_tile_src(const WpeGeom& g, int e, int t0, int* d, int* t) {
     *d = e / g.LDT;
     *t = t0 - g.H + (e - *d * g.LDT);
 }
 
 // one tile's contribution to a 4 x 4 block: acc[i][j] += a_i[t] conj(b_j[t]) inv[t]
-EGR_WPE_HD void wpe_acc_block(const wpe_c32* tile, const double* invt, int nt, const int (&rb)[4], const int (&cb)[4], double (&ar)[16],
+EGR_HD void wpe_acc_block(const wpe_c32* tile, const double* invt, int nt, const int (&rb)[4], const int (&cb)[4], double (&ar)[16],
                               double (&ai)[16]) {
     for (int t = 0; t < nt; ++t) {
         const double w = invt[t];
@@ -107,7 +106,7 @@ EGR_WPE_HD void wpe_acc_block(const wpe_c32* tile, const double* invt, int nt, c
 // s + c += a b with the rounding errors of the product (fma) and of the sum (two-sum) collected in c: the pair carries the running
 // sum to about twice the precision of a double.  Contraction is off so that the sum below stays the plain rounded s + p the
 // two-sum identity needs.
-EGR_WPE_HD void wpe_mac2(double a, double b, double& s, double& c) {
+EGR_HD void wpe_mac2(double a, double b, double& s, double& c) {
 #if defined(__clang__)
 #pragma clang fp contract(off)
 #endif
@@ -121,7 +120,7 @@ EGR_WPE_HD void wpe_mac2(double a, double b, double& s, double& c) {
 // (stacked row i = k D + d sits at tile column taps - 1 - k + tl of channel d; Y itself at column H + tl); gh is row e of GH.
 // Where the prediction cancels the observation the terms are much larger than X, and the next weights 1 / |X|^2 would carry a
 // plain double sum's eps |terms| / |X|; the compensated sum leaves eps |X|.
-EGR_WPE_HD void wpe_filter_sum(const WpeGeom& g, const wpe_c32* tile, const wpe_c64* gh, int e, int tl, double* xr, double* xi) {
+EGR_HD void wpe_filter_sum(const WpeGeom& g, const wpe_c32* tile, const wpe_c64* gh, int e, int tl, double* xr, double* xi) {
     const wpe_c32 yv = tile[e * g.LDT + g.H + tl];
     double sr = (double)yv.x, si = (double)yv.y, cr = 0.0, ci = 0.0;
     int i = 0;
@@ -151,28 +150,18 @@ struct WpeClip {                 // one row of the device table, longest clip fi
 };
 
 // workgroups one channel of a clip brings to the analysis and to the synthesis grid
-EGR_WPE_HD long long wpe_stft_tiles(long long frames) { return (frames + WPE_FT - 1) / WPE_FT; }
-EGR_WPE_HD long long wpe_istft_runs(long long frames, int n_fft, int hop) { return (frames - 1 + n_fft / hop + WPE_SEG - 1) / WPE_SEG; }
+EGR_HD long long wpe_stft_tiles(long long frames) { return (frames + WPE_FT - 1) / WPE_FT; }
+EGR_HD long long wpe_istft_runs(long long frames, int n_fft, int hop) { return (frames - 1 + n_fft / hop + WPE_SEG - 1) / WPE_SEG; }
 
-EGR_WPE_HD void wpe_many_pair(long long idx, int bins, int* clip, int* bin) {
+EGR_HD void wpe_many_pair(long long idx, int bins, int* clip, int* bin) {
     const long long c = idx / bins;
     *clip = (int)c;
     *bin = (int)(idx - c * bins);
 }
 
-// last i in [0, n) with off[i] <= tile (off[0] = 0)
-EGR_WPE_HD int wpe_many_find(const long long* off, int n, long long tile) {
-    int lo = 0, hi = n - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (off[mid] <= tile) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
-
 // flat tile -> clip, channel and the tile's index inside that channel
-EGR_WPE_HD void wpe_many_track(const long long* off, int n, int C, long long tile, int* clip, int* c, long long* local) {
-    const int i = wpe_many_find(off, n, tile);
+EGR_HD void wpe_many_track(const long long* off, int n, int C, long long tile, int* clip, int* c, long long* local) {
+    const int i = track_of(off, n, 1, 0, tile);
     const long long r = tile - off[i], per = (off[i + 1] - off[i]) / C;
     const long long ch = r / per;
     *clip = i;

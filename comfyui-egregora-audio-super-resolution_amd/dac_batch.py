@@ -17,29 +17,13 @@ from pathlib import Path
 
 import numpy as np
 
-AUDIO_SUFFIXES = (".wav", ".flac")
+try:
+    from .batch_cli import AUDIO_SUFFIXES, batches, discover, load_pack, read_all, read_clip, write_wav
+except ImportError:          # run as a script, or loaded by path: batch_cli.py lies next to this file
+    sys.path.append(str(Path(__file__).resolve().parent))
+    from batch_cli import AUDIO_SUFFIXES, batches, discover, load_pack, read_all, read_clip, write_wav
+
 MAX_BATCH_SECONDS = 1200.0        # channel-seconds a batch holds on the device before it is encoded (about 0.2 GB of samples)
-
-
-def _load_pack():
-    import importlib.util
-    here = Path(__file__).resolve().parent
-    spec = importlib.util.spec_from_file_location("egregora_amd", here / "__init__.py", submodule_search_locations=[str(here)])
-    mod = importlib.util.module_from_spec(spec)
-    sys.modules["egregora_amd"] = mod
-    spec.loader.exec_module(mod)
-    return mod
-
-
-def discover(in_dir: Path, suffixes):
-    """Relative paths of the files under in_dir with one of the suffixes, sorted."""
-    return sorted(p.relative_to(in_dir) for p in in_dir.rglob("*") if p.is_file() and p.suffix.lower() in suffixes)
-
-
-def read_clip(path: Path):
-    """-> ([C, T] float32 tensor, sample rate)."""
-    from egregora_amd import audio_glue, audio_io
-    return audio_glue.upscaler_input(audio_io.read_audio(str(path)))
 
 
 def read_codes(path: Path) -> dict:
@@ -56,29 +40,6 @@ def write_codes(path: Path, r: dict, model_type: str):
     path.parent.mkdir(parents=True, exist_ok=True)
     np.savez(str(path), codes=r["codes"].numpy().astype(np.int32), sample_rate=np.int64(r["sample_rate"]),
              model_sample_rate=np.int64(r["model_sample_rate"]), model_type=np.str_(model_type), n_samples=np.int64(r["n_samples"]))
-
-
-def batches(items, seconds_of, budget: float):
-    """items grouped in order; a batch closes before the item that would take it past the budget."""
-    cur, used = [], 0.0
-    for it in items:
-        s = seconds_of(it)
-        if cur and used + s > budget:
-            yield cur
-            cur, used = [], 0.0
-        cur.append(it)
-        used += s
-    if cur:
-        yield cur
-
-
-def _read_all(in_dir: Path, files, reader, skipped):
-    for rel in files:
-        try:
-            yield rel, reader(in_dir / rel)
-        except Exception as ex:      # noqa: BLE001 -- any reader error skips the file
-            skipped.append(rel)
-            print(f"SKIP {rel}: {ex}")
 
 
 def parser() -> argparse.ArgumentParser:
@@ -102,18 +63,18 @@ def main(argv=None) -> int:
     if args.model_dir:
         os.environ["EGREGORA_DAC_MODEL_DIR"] = str(args.model_dir)
     if "egregora_amd" not in sys.modules:
-        _load_pack()
-    from egregora_amd import dac_many, wavio
+        load_pack()
+    from egregora_amd import dac_many
     skipped = []
     if not args.decode:
-        clips = _read_all(in_dir, discover(in_dir, AUDIO_SUFFIXES), read_clip, skipped)
+        clips = read_all(in_dir, discover(in_dir, AUDIO_SUFFIXES), read_clip, skipped)
         for b in batches(clips, lambda it: it[1][0].shape[0] * it[1][0].shape[1] / it[1][1], args.max_seconds):
             for (rel, (x, sr)), r in zip(b, dac_many.encode_many([c for _, c in b], args.model_type)):
                 dst = (out_dir / rel).with_suffix(".npz")
                 write_codes(dst, r, args.model_type)
                 print(f"{rel} -> {dst} [{r['codes'].shape[0]} ch, {r['codes'].shape[2]} frames, {r['n_samples']} samples @ {sr} Hz]")
     else:
-        items = _read_all(in_dir, discover(in_dir, (".npz",)), read_codes, skipped)
+        items = read_all(in_dir, discover(in_dir, (".npz",)), read_codes, skipped)
         for b in batches(items, lambda it: it[1]["codes"].shape[0] * it[1]["n_samples"] / it[1]["sample_rate"], args.max_seconds):
             for rel, d in b:
                 if d["model_type"] != args.model_type:
@@ -124,10 +85,7 @@ def main(argv=None) -> int:
                     import torch
                     y = torch.nn.functional.pad(y, (0, n - y.shape[1]))
                 y = y[:, :n]
-                dst = (out_dir / rel).with_suffix(".wav")
-                dst.parent.mkdir(parents=True, exist_ok=True)
-                wavio.write_wav_pcm16(str(dst), y.numpy().T, d["sample_rate"])
-                print(f"{rel} -> {dst} [{y.shape[0]} ch, {y.shape[1]} samples @ {d['sample_rate']} Hz]")
+                print(write_wav(out_dir, rel, y, d["sample_rate"]))
     print("OK")
     return 1 if skipped else 0
 

@@ -13,6 +13,7 @@ from typing import Callable, List, NamedTuple, Optional, Sequence, Tuple
 import torch
 
 from . import dac_weights, native
+from .many_common import budget_bytes, track_rows
 
 WORKSPACE_GB_ENV, WORKSPACE_GB_DEFAULT = "EGREGORA_DAC_WORKSPACE_GB", "64"
 _CACHE = {}
@@ -24,7 +25,7 @@ def workspace_budget_gb() -> float:
 
 
 def workspace_budget_bytes() -> int:
-    return int(workspace_budget_gb() * 2 ** 30)
+    return budget_bytes(WORKSPACE_GB_ENV, WORKSPACE_GB_DEFAULT)
 
 
 def conv_length(L: int, s: int) -> int:
@@ -468,12 +469,7 @@ class DacEngine:
             stats.update(waves=waves, alone=alone)
         out: List = [None] * len(clips)
         for w in waves:
-            offs, lens, pos = [], [], 0
-            for i in w.clips:
-                c, T = clips[i].shape
-                offs += [pos + k * T for k in range(c)]
-                lens += [T] * c
-                pos += c * T
+            offs, lens = track_rows([tuple(clips[i].shape) for i in w.clips])
             flat = torch.cat([clips[i].reshape(-1) for i in w.clips]) if len(w.clips) > 1 else clips[w.clips[0]].reshape(-1)
             z, codes = self.encode_rows(flat, offs, lens, w.pad_frames)
             r = 0

@@ -56,7 +56,7 @@ def wola_stitch(preds: torch.Tensor, total: int, win: int, hop: int) -> torch.Te
 
 # ------------------------------------------------------------------ ragged glue: many tracks (one channel of one clip) per call
 # Flat float32 buffers hold the tracks back to back; small int64 device tables say where (flashsr_engine.wave_tables /
-# resample_table build them; include/egregora_amd.h states the columns).
+# resample.poly_track_table build them; include/egregora_amd.h states the columns).
 def _chk_table(t, cols, what):
     if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.int64 and t.is_contiguous() and t.dim() == 2 and t.shape[1] == cols):
         raise RuntimeError(f"{what}: want a contiguous int64 CUDA table with {cols} columns")

@@ -18,24 +18,13 @@ import threading
 from concurrent.futures import ThreadPoolExecutor
 from pathlib import Path
 
-SUFFIXES = (".wav", ".flac")
+try:
+    from .batch_cli import discover, load_pack, read_clip, write_wav
+except ImportError:          # run as a script, or loaded by path: batch_cli.py lies next to this file
+    sys.path.append(str(Path(__file__).resolve().parent))
+    from batch_cli import discover, load_pack, read_clip, write_wav
 MAX_BATCH_FRAMES = 131072        # about 18 GB of workspace at 139 KB per frame and row
 FFT, HOP = 960, 480              # both models' framing at 48 kHz; only the batch rule counts with it
-
-
-def _load_pack():
-    import importlib.util
-    here = Path(__file__).resolve().parent
-    spec = importlib.util.spec_from_file_location("egregora_amd", here / "__init__.py", submodule_search_locations=[str(here)])
-    mod = importlib.util.module_from_spec(spec)
-    sys.modules["egregora_amd"] = mod
-    spec.loader.exec_module(mod)
-    return mod
-
-
-def discover(in_dir: Path):
-    """Relative paths of the audio files under in_dir, sorted."""
-    return sorted(p.relative_to(in_dir) for p in in_dir.rglob("*") if p.is_file() and p.suffix.lower() in SUFFIXES)
 
 
 def clip_frames(channels: int, n: int, sr: int) -> int:
@@ -44,21 +33,16 @@ def clip_frames(channels: int, n: int, sr: int) -> int:
     return int(channels) * ((n48 + FFT) // HOP)
 
 
-def _decode(path: Path):
-    from egregora_amd import audio_glue, audio_io
-    return audio_glue.upscaler_input(audio_io.read_audio(str(path)))
-
-
 def _batches(in_dir: Path, files, pool, workers: int, budget: int, skipped):
     """Decoded clips grouped into batches (a batch closes before the clip that would take it past the budget): yields
     [(relative path, [C,T] tensor, sr)].  At most two pool-widths of files are decoded ahead of the consumer."""
     ahead = 2 * workers
-    futs = [(rel, pool.submit(_decode, in_dir / rel)) for rel in files[:ahead]]
+    futs = [(rel, pool.submit(read_clip, in_dir / rel)) for rel in files[:ahead]]
     nxt, cur, used = len(futs), [], 0
     while futs:
         rel, f = futs.pop(0)
         if nxt < len(files):
-            futs.append((files[nxt], pool.submit(_decode, in_dir / files[nxt])))
+            futs.append((files[nxt], pool.submit(read_clip, in_dir / files[nxt])))
             nxt += 1
         try:
             x, sr = f.result()
@@ -115,18 +99,12 @@ def main(argv=None) -> int:
     if args.model_dir:
         os.environ["EGREGORA_DFN_MODEL_DIR"] = str(args.model_dir)
     if "egregora_amd" not in sys.modules:
-        _load_pack()
-    from egregora_amd import dfn_many, wavio
+        load_pack()
+    from egregora_amd import dfn_many
     files = discover(in_dir)
     widgets = widgets_of(args)
     skipped, writes = [], []
     ready: "queue.Queue" = queue.Queue(maxsize=1)           # one decoded batch waits while the GPU works on the one before it
-
-    def write(rel, y, sr):
-        dst = (out_dir / rel).with_suffix(".wav")
-        dst.parent.mkdir(parents=True, exist_ok=True)
-        wavio.write_wav_pcm16(str(dst), y.numpy().T, sr)
-        return rel, dst, y.shape, sr
 
     workers = min(16, os.cpu_count() or 1)
     with ThreadPoolExecutor(max_workers=workers) as pool:
@@ -146,10 +124,9 @@ def main(argv=None) -> int:
             if isinstance(b, BaseException):
                 raise b
             ys = dfn_many.denoise_many([(x, sr) for _, x, sr in b], args.model, **widgets)
-            writes += [pool.submit(write, rel, y, sr) for (rel, _, sr), y in zip(b, ys)]
+            writes += [pool.submit(write_wav, out_dir, rel, y, sr) for (rel, _, sr), y in zip(b, ys)]
         for w in writes:
-            rel, dst, shape, sr = w.result()
-            print(f"{rel} -> {dst} [{shape[0]} ch, {shape[1]} samples @ {sr} Hz]")
+            print(w.result())
     print("OK")
     return 1 if skipped else 0
 

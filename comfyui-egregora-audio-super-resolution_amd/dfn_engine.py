@@ -20,6 +20,7 @@ from typing import Callable, Dict, List, NamedTuple, Optional, Sequence, Tuple
 import torch
 
 from . import dfn_weights, native
+from .many_common import budget_bytes, track_rows
 
 _CACHE: Dict[Tuple[str, str, int], "DfnEngine"] = {}
 _LOCK = threading.Lock()
@@ -91,7 +92,7 @@ def segment_plan_c(fft_size: int, hop_size: int, conv_lookahead: int, df_order: 
 
 
 def workspace_budget_bytes() -> int:
-    return int(float(os.environ.get(WORKSPACE_GB_ENV, WORKSPACE_GB_DEFAULT)) * 2 ** 30)
+    return budget_bytes(WORKSPACE_GB_ENV, WORKSPACE_GB_DEFAULT)
 
 
 def choose_path(nF: int, one_pass_bytes: int, budget_bytes: int, bytes_for: Callable[[int], int]) -> Optional[int]:
@@ -266,12 +267,7 @@ class DfnEngine:
             out[i] = self.enhance(rows[i])
         for idx in waves:
             x = torch.cat([rows[i].to(torch.float32).reshape(-1) for i in idx])
-            offs, lens, pos = [], [], 0
-            for i in idx:
-                c, T = shapes[i]
-                offs += [pos + k * T for k in range(c)]
-                lens += [T] * c
-                pos += c * T
+            offs, lens = track_rows([shapes[i] for i in idx])
             y = self.enhance_tracks(x, offs, lens)
             pos = 0
             for i in idx:

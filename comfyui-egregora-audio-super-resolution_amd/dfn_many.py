@@ -10,12 +10,13 @@ the single node gives it.
 The packed path is taken exactly when the single node would run the native engine: no backend registered with set_enhancer, upstream
 `df` not importable, a model directory of the chosen model found.  Otherwise the clips go through the single node one by one.
 """
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import List, Optional, Sequence, Tuple
 
 import torch
 
-from . import device_ops, native, resample
+from . import native, resample
 from . import egregora_audio_enhance_extras as extras
+from .many_common import check_clips, group_by_rate
 
 WIDGET_DEFAULTS = dict(device="auto", use_postfilter=False, limit_ceiling=True, stereo_mode="per_channel", frame_ms=20, strength=0.65,
                        mix_curve="equal_power", adaptive_vad_source="rms", adaptive_mode="more_on_noise", adaptive_amount=0.45,
@@ -39,40 +40,6 @@ def native_engine(dfn_model: str, device: Optional[int] = None):
     return None
 
 
-def resample_group(xs: Sequence[torch.Tensor], src_sr: int, dst_sr: int) -> List[torch.Tensor]:
-    """[C_i, T_i] device tensors at src_sr -> [C_i, ceil(T_i up / down)] at dst_sr with one egr_resample_poly_tracks call: the bits of
-    resample.resample_hq on each."""
-    up, down = resample.rates(src_sr, dst_sr)
-    dev = xs[0].device
-    flat = torch.cat([x.to(torch.float32).reshape(-1) for x in xs])
-    ins, lens, pos = [], [], 0
-    for x in xs:
-        c, T = x.shape
-        ins += [pos + k * T for k in range(c)]
-        lens += [T] * c
-        pos += c * T
-    from .flashsr_engine import resample_table
-    tab, total = resample_table(ins, lens, up, down)
-    h, half = resample.filter_for(up, down, dev)
-    tab_dev = torch.from_numpy(tab).to(dev)
-    y = device_ops.resample_poly_tracks(flat, tab_dev, total, up, down, h, half, torch.empty(total, dtype=torch.float32, device=dev))
-    out, t = [], 0
-    for x in xs:
-        c = x.shape[0]
-        o, n = int(tab[t, 2]), int(tab[t, 3])
-        out.append(y[o:o + c * n].view(c, n))
-        t += c
-    return out
-
-
-def _by_rate(srs: Sequence[int]) -> Dict[int, List[int]]:
-    groups: Dict[int, List[int]] = {}
-    for i, sr in enumerate(srs):
-        if sr != 48000:
-            groups.setdefault(sr, []).append(i)
-    return groups
-
-
 def denoise_many(clips: Sequence[Tuple[torch.Tensor, int]], dfn_model: str = "DeepFilterNet2", *, stats: Optional[dict] = None,
                  **widgets) -> List[torch.Tensor]:
     """clips: [([C,T] float tensor on the host or the device, sample_rate)]; widgets: the single node's, by name (WIDGET_DEFAULTS).
@@ -83,10 +50,7 @@ def denoise_many(clips: Sequence[Tuple[torch.Tensor, int]], dfn_model: str = "De
         raise TypeError(f"denoise_many: unknown widget(s) {sorted(unknown)}")
     w = dict(WIDGET_DEFAULTS, **widgets)
     native.require_device()
-    clips = [(x, int(sr)) for x, sr in clips]
-    for i, (x, sr) in enumerate(clips):
-        if not torch.is_tensor(x) or x.dim() != 2 or x.shape[0] < 1 or x.shape[1] < 1 or sr < 1:
-            raise ValueError(f"denoise_many: clip {i}: expected a non-empty [C, T] tensor and a positive sample rate")
+    clips = check_clips("denoise_many", clips)
     eng = native_engine(dfn_model, torch.cuda.current_device()) if clips else None
     if stats is not None:
         stats["packed"] = eng is not None
@@ -102,13 +66,14 @@ def denoise_many(clips: Sequence[Tuple[torch.Tensor, int]], dfn_model: str = "De
         dry.append(x.contiguous().cuda())
     with torch.cuda.device(eng.device):
         dry48: List[torch.Tensor] = list(dry)
-        for sr, idx in _by_rate(srs).items():
-            for i, y in zip(idx, resample_group([dry[i] for i in idx], sr, 48000)):
+        groups = group_by_rate(srs, 48000)
+        for sr, idx in groups.items():
+            for i, y in zip(idx, resample.resample_poly_group([dry[i] for i in idx], sr, 48000)):
                 dry48[i] = y
         wet48 = eng.enhance_many(dry48, stats=stats)
         wet: List[torch.Tensor] = list(wet48)
-        for sr, idx in _by_rate(srs).items():
-            for i, y in zip(idx, resample_group([wet48[i] for i in idx], 48000, sr)):
+        for sr, idx in groups.items():
+            for i, y in zip(idx, resample.resample_poly_group([wet48[i] for i in idx], 48000, sr)):
                 wet[i] = y
         ys = []
         for i, d in enumerate(dry):

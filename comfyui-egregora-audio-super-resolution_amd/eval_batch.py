@@ -16,9 +16,10 @@ import sys
 from pathlib import Path
 
 try:
-    from .dac_batch import AUDIO_SUFFIXES, _load_pack, batches, discover, read_clip
-except ImportError:          # run as a script: the directory of this file is on the path
-    from dac_batch import AUDIO_SUFFIXES, _load_pack, batches, discover, read_clip
+    from .batch_cli import batches, discover, load_pack, read_clip
+except ImportError:          # run as a script, or loaded by path: batch_cli.py lies next to this file
+    sys.path.append(str(Path(__file__).resolve().parent))
+    from batch_cli import batches, discover, load_pack, read_clip
 
 MAX_BATCH_SECONDS = 2400.0        # channel-seconds a batch holds on the device (about 0.5 GB of samples)
 
@@ -37,8 +38,8 @@ def parser() -> argparse.ArgumentParser:
 
 def pair_up(ref_dir: Path, proc_dir: Path):
     """-> ([(key, reference path, processed path)], [unpaired relative paths]); key = the relative path without its suffix."""
-    refs = {p.with_suffix("").as_posix(): p for p in discover(ref_dir, AUDIO_SUFFIXES)}
-    procs = {p.with_suffix("").as_posix(): p for p in discover(proc_dir, AUDIO_SUFFIXES)}
+    refs = {p.with_suffix("").as_posix(): p for p in discover(ref_dir)}
+    procs = {p.with_suffix("").as_posix(): p for p in discover(proc_dir)}
     both = sorted(set(refs) & set(procs))
     alone = sorted([f"{ref_dir / refs[k]}" for k in set(refs) - set(procs)] + [f"{proc_dir / procs[k]}" for k in set(procs) - set(refs)])
     return [(k, ref_dir / refs[k], proc_dir / procs[k]) for k in both], alone
@@ -53,7 +54,7 @@ def main(argv=None) -> int:
     if not args.max_seconds > 0:
         raise SystemExit("--max-seconds must be positive")
     if "egregora_amd" not in sys.modules:
-        _load_pack()
+        load_pack()
     from egregora_amd import eval_many
     pairs, alone = pair_up(ref_dir, proc_dir)
     bad = len(alone)

@@ -6,20 +6,18 @@ copy, whatever the number of clips.  Nothing is padded: the kernels find their p
 result with the single path's own expressions (device_ops.lsd_finish / si_sdr_finish, loudness.measure_finish).  Host tensors go up
 one by one, as the single nodes send them; tensors that are already on the device are addressed where they lie.
 """
-import os
 from typing import List, Optional, Sequence, Tuple
 
 import torch
 
 from . import device_ops, loudness, native
+from .many_common import budget_bytes
 
 DEFAULT_WAVE_GB = 4.0          # EGREGORA_EVAL_WAVE_GB
 
 
 def wave_budget(max_bytes: Optional[int] = None) -> int:
-    if max_bytes is not None:
-        return int(max_bytes)
-    return int(float(os.environ.get("EGREGORA_EVAL_WAVE_GB", DEFAULT_WAVE_GB)) * (1 << 30))
+    return budget_bytes("EGREGORA_EVAL_WAVE_GB", DEFAULT_WAVE_GB, max_bytes)
 
 
 def plan_waves(item_bytes: Sequence[int], max_bytes: Optional[int] = None, item_work: Optional[Sequence[int]] = None,

@@ -14,9 +14,10 @@ import sys
 from pathlib import Path
 
 try:
-    from .dac_batch import AUDIO_SUFFIXES, _load_pack, _read_all, batches, discover
-except ImportError:          # run as a script: the directory of this file is on the path
-    from dac_batch import AUDIO_SUFFIXES, _load_pack, _read_all, batches, discover
+    from .batch_cli import AUDIO_SUFFIXES, batches, discover, load_pack, read_all, write_wav
+except ImportError:          # run as a script, or loaded by path: batch_cli.py lies next to this file
+    sys.path.append(str(Path(__file__).resolve().parent))
+    from batch_cli import AUDIO_SUFFIXES, batches, discover, load_pack, read_all, write_wav
 
 MAX_BATCH_SECONDS = 2400.0        # channel-seconds a batch holds on the device (about 0.5 GB of samples in, as much out at factor 1)
 
@@ -48,19 +49,16 @@ def main(argv=None) -> int:
     if not args.max_seconds > 0 or args.max_iterations < 1:
         raise SystemExit("--max-seconds must be positive and --max-iterations at least 1")
     if "egregora_amd" not in sys.modules:
-        _load_pack()
-    from egregora_amd import fatllama_many, wavio
+        load_pack()
+    from egregora_amd import fatllama_many
     skipped = []
-    clips = _read_all(in_dir, discover(in_dir, AUDIO_SUFFIXES), read_clip, skipped)
+    clips = read_all(in_dir, discover(in_dir, AUDIO_SUFFIXES), read_clip, skipped)
     for b in batches(clips, lambda it: it[1][0].shape[0] * it[1][0].shape[1] / it[1][1], args.max_seconds):
         stats = {}
         res = fatllama_many.enhance_many([c for _, c in b], args.max_iterations, args.threshold, args.bitrate, not args.no_normalize,
                                          not args.no_autoscale, stats=stats)
         for (rel, (x, sr)), (y, sr_out) in zip(b, res):
-            dst = (out_dir / rel).with_suffix(".wav")
-            dst.parent.mkdir(parents=True, exist_ok=True)
-            wavio.write_wav_pcm16(str(dst), y.numpy().T, sr_out)
-            print(f"{rel} -> {dst} [{y.shape[0]} ch, {y.shape[1]} samples @ {sr_out} Hz]")
+            print(write_wav(out_dir, rel, y, sr_out))
         print(f"batch of {len(b)}: {stats['waves']} waves, {stats['fallbacks']} one by one")
     print("OK")
     return 1 if skipped else 0

@@ -14,7 +14,7 @@ from typing import List, Optional, Sequence, Tuple
 import torch
 
 from . import fatllama_engine, native
-from .dac_many import _download, _upload
+from .many_common import budget_bytes, check_clips, download, upload
 
 MAX_ROWS = native.FLMANY_MAX_ROWS       # channel rows of a wave (egr_flmany_create's limit)
 DEFAULT_WAVE_GB = 16.0                  # EGREGORA_FATLLAMA_WAVE_GB: device bytes a wave may allocate
@@ -60,8 +60,7 @@ def wave_bytes(P: int, states: int, distinct: int, rows: int) -> int:
 def _caps(max_rows, max_bytes, slack):
     if max_rows is None:
         max_rows = MAX_ROWS
-    if max_bytes is None:
-        max_bytes = int(float(os.environ.get("EGREGORA_FATLLAMA_WAVE_GB", DEFAULT_WAVE_GB)) * (1 << 30))
+    max_bytes = budget_bytes("EGREGORA_FATLLAMA_WAVE_GB", DEFAULT_WAVE_GB, max_bytes)
     if slack is None:
         slack = float(os.environ.get("EGREGORA_FATLLAMA_WAVE_SLACK", DEFAULT_WAVE_SLACK))
     return int(max_rows), int(max_bytes), float(slack)
@@ -169,10 +168,7 @@ def enhance_many(clips: Sequence[Tuple[torch.Tensor, int]], max_iterations: int,
     """clips: [([C, T] float tensor on the host or the device, sample_rate)] -> [(float32 [C, n_out] host tensor, sr_out)] in input
     order, each what EgregoraFatLlamaGPU returns for the clip alone (module docstring).  Runs on the current device; stats (optional
     dict) receives {"waves", "rows": per wave, "padding": per wave, "fallbacks", "wave_clips": clip indices per wave}."""
-    clips = [(x, int(sr)) for x, sr in clips]
-    for i, (x, sr) in enumerate(clips):
-        if not torch.is_tensor(x) or x.dim() != 2 or x.shape[0] < 1 or x.shape[1] < 1 or sr < 1:
-            raise ValueError(f"enhance_many: clip {i}: expected a non-empty [C, T] tensor and a positive sample rate")
+    clips = check_clips("enhance_many", clips)
     if stats is not None:
         stats.update({"waves": 0, "rows": [], "padding": [], "fallbacks": 0, "wave_clips": []})
     if not clips:
@@ -185,7 +181,7 @@ def enhance_many(clips: Sequence[Tuple[torch.Tensor, int]], max_iterations: int,
     single_only = (int(max_iterations) < 1 or bool(flags & native.FL_THR_RECOMPUTE) or
                    os.environ.get("EGR_FL_LEGACY_CHIRPZ", "0") not in ("", "0"))
     waves, fallbacks, padding = plan_waves(specs, single_only=single_only)
-    xs = [x.contiguous() for x in _upload([x for x, _ in clips], dev, torch.float32)]
+    xs = [x.contiguous() for x in upload([x for x, _ in clips], dev, torch.float32)]
     ys: List = [None] * len(clips)
     for wave, pad in zip(waves, padding):
         w = Wave([specs[i] for i in wave])
@@ -206,4 +202,4 @@ def enhance_many(clips: Sequence[Tuple[torch.Tensor, int]], max_iterations: int,
                                                bool(toggle_autoscale), pcm_in=True, node_post=True, n_out=n_out or None)
     if stats is not None:
         stats["fallbacks"] = len(fallbacks)
-    return [(y, r[2]) for y, r in zip(_download(ys), reqs)]
+    return [(y, r[2]) for y, r in zip(download(ys), reqs)]

@@ -16,27 +16,11 @@ import threading
 from concurrent.futures import ThreadPoolExecutor
 from pathlib import Path
 
-SUFFIXES = (".wav", ".flac")
-
-
-def _load_pack():
-    import importlib.util
-    here = Path(__file__).resolve().parent
-    spec = importlib.util.spec_from_file_location("egregora_amd", here / "__init__.py", submodule_search_locations=[str(here)])
-    mod = importlib.util.module_from_spec(spec)
-    sys.modules["egregora_amd"] = mod
-    spec.loader.exec_module(mod)
-    return mod
-
-
-def discover(in_dir: Path):
-    """Relative paths of the audio files under in_dir, sorted."""
-    return sorted(p.relative_to(in_dir) for p in in_dir.rglob("*") if p.is_file() and p.suffix.lower() in SUFFIXES)
-
-
-def _decode(path: Path):
-    from egregora_amd import audio_glue, audio_io
-    return audio_glue.upscaler_input(audio_io.read_audio(str(path)))
+try:
+    from .batch_cli import discover, load_pack, read_clip, write_wav
+except ImportError:          # run as a script, or loaded by path: batch_cli.py lies next to this file
+    sys.path.append(str(Path(__file__).resolve().parent))
+    from batch_cli import discover, load_pack, read_clip, write_wav
 
 
 def _batches(in_dir: Path, files, pool, workers: int, budget: int, win: int, hop: int, skipped):
@@ -44,12 +28,12 @@ def _batches(in_dir: Path, files, pool, workers: int, budget: int, win: int, hop
     budget): yields [(relative path, [C,T] tensor, sr)].  At most two pool-widths of files are decoded ahead of the consumer."""
     from egregora_amd import flashsr_engine
     ahead = 2 * workers
-    futs = [(rel, pool.submit(_decode, in_dir / rel)) for rel in files[:ahead]]
+    futs = [(rel, pool.submit(read_clip, in_dir / rel)) for rel in files[:ahead]]
     nxt, cur, used = len(futs), [], 0
     while futs:
         rel, f = futs.pop(0)
         if nxt < len(files):
-            futs.append((files[nxt], pool.submit(_decode, in_dir / files[nxt])))
+            futs.append((files[nxt], pool.submit(read_clip, in_dir / files[nxt])))
             nxt += 1
         try:
             x, sr = f.result()
@@ -87,19 +71,13 @@ def main(argv=None) -> int:
     else:
         os.environ.setdefault("EGREGORA_FLASHSR_CKPT_DIR", str(args.ckpt_dir))
     if "egregora_amd" not in sys.modules:
-        _load_pack()
-    from egregora_amd import audio_glue, flashsr_engine, wavio
+        load_pack()
+    from egregora_amd import audio_glue, flashsr_engine
     files = discover(in_dir)
     budget = flashsr_engine.wave_budget(args.max_rows)
     win, hop = audio_glue.CHUNK_SAMPLES, audio_glue.HOP_SAMPLES
     skipped, writes = [], []
     ready: "queue.Queue" = queue.Queue(maxsize=1)           # one decoded wave waits while the GPU works on the one before it
-
-    def write(rel, y):
-        dst = (out_dir / rel).with_suffix(".wav")
-        dst.parent.mkdir(parents=True, exist_ok=True)
-        wavio.write_wav_pcm16(str(dst), y.numpy().T, args.target_sr)
-        return rel, dst, y.shape
 
     workers = min(16, os.cpu_count() or 1)
     with ThreadPoolExecutor(max_workers=workers) as pool:
@@ -119,10 +97,9 @@ def main(argv=None) -> int:
             if isinstance(b, BaseException):
                 raise b
             ys = flashsr_engine.upscale_many([(x, sr) for _, x, sr in b], bool(args.lowpass_input), args.target_sr, max_rows=budget)
-            writes += [pool.submit(write, rel, y) for (rel, _, _), y in zip(b, ys)]
+            writes += [pool.submit(write_wav, out_dir, rel, y, args.target_sr) for (rel, _, _), y in zip(b, ys)]
         for w in writes:
-            rel, dst, shape = w.result()
-            print(f"{rel} -> {dst} [{shape[0]} ch, {shape[1]} samples @ {args.target_sr} Hz]")
+            print(w.result())
     print("OK")
     return 1 if skipped else 0
 

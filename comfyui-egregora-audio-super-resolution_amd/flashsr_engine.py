@@ -26,7 +26,8 @@ from typing import Dict, List, Optional, Tuple
 
 import torch
 
-from . import audio_glue, device_ops, flashsr_arch as arch, native, shard
+from . import audio_glue, device_ops, flashsr_arch as arch, native, resample, shard
+from .many_common import group_by_rate, track_rows
 
 ACT_NONE, ACT_SILU, ACT_TANH, ACT_LEAKY, ACT_LOGCLAMP = 0, 1, 2, 3, 4
 EW_ADD, EW_AXPBY, EW_SILU, EW_SCALE, EW_COPY, EW_ADD_SCALE = 0, 1, 2, 3, 4, 5
@@ -458,7 +459,6 @@ def resampled_len(n: int, src_sr: int, dst_sr: int) -> int:
     """Length resample.resample_hq gives n samples: ceil(n * up / down)."""
     if int(src_sr) == int(dst_sr):
         return int(n)
-    from . import resample
     up, down = resample.rates(src_sr, dst_sr)
     return (int(n) * up + down - 1) // down
 
@@ -497,17 +497,6 @@ def plan_waves(row_counts: List[int], max_rows: Optional[int] = None) -> List[Li
     return waves
 
 
-def resample_table(in_offsets: List[int], n_ins: List[int], up: int, down: int):
-    """egr_resample_poly_tracks' table for one rate group: int64 [T,4] rows (in offset, n_in, out offset, n_out) with
-    n_out = ceil(n_in * up / down) and the outputs back to back from 0; -> (table, total_out)."""
-    import numpy as np
-    n_in = np.asarray(n_ins, dtype=np.int64).reshape(-1)
-    n_out = (n_in * up + down - 1) // down
-    ends = np.cumsum(n_out)
-    tab = np.stack([np.asarray(in_offsets, dtype=np.int64).reshape(-1), n_in, ends - n_out, n_out], axis=1)
-    return np.ascontiguousarray(tab), int(ends[-1]) if len(ends) else 0
-
-
 def wave_tables(shapes: List[Tuple[int, int]], offsets: List[int], win: int, hop: int) -> dict:
     """Tables of one wave at 48 kHz.  shapes[i] = (C, T) of clip i, offsets[i] = where its channel 0 starts in the flat input
     (channel c at offsets[i] + c * T).  Rows inside a clip are chunk-major then channel -- the order the single-clip path views as
@@ -537,7 +526,6 @@ def wave_tables(shapes: List[Tuple[int, int]], offsets: List[int], win: int, hop
 def _upscale_single(x: torch.Tensor, sr: int, lowpass: bool, output_sr: int, win: int, hop: int, eng: FlashSREngine) -> torch.Tensor:
     """The single-clip flow of the node (egregora_audio_super_resolution.py run / upscale_48k) for a clip the packed path leaves out:
     its result, or its error."""
-    from . import resample
     x = x.to(eng.dev, torch.float32).contiguous()
     if sr != audio_glue.REQ_SR:
         x = resample.resample_hq(x, sr, audio_glue.REQ_SR)
@@ -559,7 +547,6 @@ class _Wave:
 
 def _enqueue_wave(eng: FlashSREngine, clips, idx: List[int], lowpass: bool, output_sr: int, win: int, hop: int) -> _Wave:
     import numpy as np
-    from . import resample
     dev = eng.dev
     REQ = audio_glue.REQ_SR
     # raw samples: host clips first (one pinned upload), device clips behind them (device copies)
@@ -572,20 +559,17 @@ def _enqueue_wave(eng: FlashSREngine, clips, idx: List[int], lowpass: bool, outp
     n_host = sum(clips[i][0].numel() for i in order if not clips[i][0].is_cuda)
     # 48 kHz layout: a 48 kHz clip stays where it was uploaded; every other rate is one group resampled into a region behind the raw
     # samples, the group's tracks back to back
-    groups: Dict[int, List[int]] = {}
-    for i in idx:
-        if int(clips[i][1]) != REQ:
-            groups.setdefault(int(clips[i][1]), []).append(i)
+    groups = {sr: [idx[j] for j in js] for sr, js in group_by_rate([int(clips[i][1]) for i in idx], REQ).items()}
     off48, shapes48, group_tabs = {}, {}, []
     pos = n_raw
     for sr in sorted(groups):
         up, down = resample.rates(sr, REQ)
         ins, lens = [], []
-        for i in groups[sr]:
-            Cn, T = clips[i][0].shape
-            ins += [raw_off[i] + c * T for c in range(Cn)]
-            lens += [T] * Cn
-        tab, total = resample_table(ins, lens, up, down)
+        for i in groups[sr]:                    # (a clip's channels lie back to back from raw_off[i]; the clips of a group need not)
+            rows = track_rows([tuple(clips[i][0].shape)], raw_off[i])
+            ins += rows[0]
+            lens += rows[1]
+        tab, total = resample.poly_track_table(ins, lens, up, down)
         t = 0
         for i in groups[sr]:
             Cn = clips[i][0].shape[0]
@@ -603,7 +587,7 @@ def _enqueue_wave(eng: FlashSREngine, clips, idx: List[int], lowpass: bool, outp
     out_tab = None
     if output_sr != REQ:
         up_o, down_o = resample.rates(REQ, output_sr)
-        out_tab, total_res = resample_table(wt["tracks"][:, 4], wt["tracks"][:, 3], up_o, down_o)
+        out_tab, total_res = resample.poly_track_table(wt["tracks"][:, 4], wt["tracks"][:, 3], up_o, down_o)
         t, clip_out = 0, []
         for i in idx:
             Cn = shapes48[i][0]

@@ -9,19 +9,16 @@ EgregoraAudioSuperResolution node (resample to 48 kHz, chunked FlashSR on the MI
 already in flashsr_arch names).
 """
 import argparse
-import importlib.util
 import os
 import sys
 from pathlib import Path
 
 
-def _load_pack():
-    here = Path(__file__).resolve().parent
-    spec = importlib.util.spec_from_file_location("egregora_amd", here / "__init__.py", submodule_search_locations=[str(here)])
-    mod = importlib.util.module_from_spec(spec)
-    sys.modules["egregora_amd"] = mod
-    spec.loader.exec_module(mod)
-    return mod
+try:
+    from .batch_cli import load_pack
+except ImportError:          # run as a script, or loaded by path: batch_cli.py lies next to this file
+    sys.path.append(str(Path(__file__).resolve().parent))
+    from batch_cli import load_pack
 
 
 def main(argv=None):
@@ -42,7 +39,7 @@ def main(argv=None):
         os.environ.setdefault("EGREGORA_FLASHSR_WEIGHTS", str(ck))
     else:
         os.environ.setdefault("EGREGORA_FLASHSR_CKPT_DIR", str(args.ckpt_dir))
-    pack = sys.modules.get("egregora_amd") or _load_pack()
+    pack = sys.modules.get("egregora_amd") or load_pack()
     from egregora_amd import wavio
     wav, sr = wavio.read_wav(args.inp)                       # [S] or [S,C], like sf.read(always_2d=False)
     node = pack.NODE_CLASS_MAPPINGS["EgregoraAudioUpscaler"]()

@@ -20,10 +20,11 @@ import sys
 from pathlib import Path
 
 try:
-    from .dac_batch import _load_pack, batches, read_clip
+    from .batch_cli import batches, load_pack, read_clip
     from .eval_batch import MAX_BATCH_SECONDS, pair_up
-except ImportError:          # run as a script: the directory of this file is on the path
-    from dac_batch import _load_pack, batches, read_clip
+except ImportError:          # run as a script, or loaded by path: batch_cli.py lies next to this file
+    sys.path.append(str(Path(__file__).resolve().parent))
+    from batch_cli import batches, load_pack, read_clip
     from eval_batch import MAX_BATCH_SECONDS, pair_up
 
 _ON = ("fractional", "compute_corr", "compute_null_rms", "compute_null_lufs", "compute_lsd")
@@ -59,7 +60,7 @@ def main(argv=None) -> int:
     if not args.max_seconds > 0:
         raise SystemExit("--max-seconds must be positive")
     if "egregora_amd" not in sys.modules:
-        _load_pack()
+        load_pack()
     from egregora_amd import null_many, wavio
     pairs, alone = pair_up(ref_dir, proc_dir)
     bad = len(alone)

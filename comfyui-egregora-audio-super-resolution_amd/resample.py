@@ -15,7 +15,8 @@ from math import gcd
 import numpy as np
 import torch
 
-from . import native
+from . import device_ops, native
+from .many_common import clip_views, track_rows
 
 _FILTERS = {}
 
@@ -65,6 +66,37 @@ def resample_hq(x_ct: torch.Tensor, src_sr: int, dst_sr: int) -> torch.Tensor:
     native.check(native.lib().egr_resample_poly(native.ptr(x), C, n_in, up, down, native.ptr(h), half, native.ptr(y),
                                                 n_out, native.stream_ptr()), "egr_resample_poly")
     return y
+
+
+def poly_track_table(in_offsets, n_ins, up: int, down: int):
+    """egr_resample_poly_tracks' table for one rate group: int64 [T,4] rows (in offset, n_in, out offset, n_out) with
+    n_out = ceil(n_in * up / down) and the outputs back to back from 0; -> (table, total_out)."""
+    n_in = np.asarray(n_ins, dtype=np.int64).reshape(-1)
+    n_out = (n_in * up + down - 1) // down
+    ends = np.cumsum(n_out)
+    tab = np.stack([np.asarray(in_offsets, dtype=np.int64).reshape(-1), n_in, ends - n_out, n_out], axis=1)
+    return np.ascontiguousarray(tab), int(ends[-1]) if len(ends) else 0
+
+
+def poly_group_flat(flat: torch.Tensor, shapes, src_sr: int, dst_sr: int, y: torch.Tensor = None):
+    """One egr_resample_poly_tracks call on clips that already lie back to back in `flat` ([C_i][T_i] each, shapes = [(C_i, T_i)]):
+    -> (y, table); many_common.clip_views(y, table, shapes) are the clips' results.  y: a flat device buffer to write from its
+    start, or None for a fresh one."""
+    up, down = rates(src_sr, dst_sr)
+    tab, total = poly_track_table(*track_rows(shapes), up, down)
+    h, half = filter_for(up, down, flat.device)
+    if y is None:
+        y = torch.empty(total, dtype=torch.float32, device=flat.device)
+    device_ops.resample_poly_tracks(flat, torch.from_numpy(tab).to(flat.device), total, up, down, h, half, y)
+    return y, tab
+
+
+def resample_poly_group(xs, src_sr: int, dst_sr: int):
+    """[C_i, T_i] device tensors at src_sr -> [C_i, ceil(T_i up / down)] at dst_sr with one egr_resample_poly_tracks call: the bits of
+    resample_hq on each."""
+    shapes = [tuple(x.shape) for x in xs]
+    flat = torch.cat([x.to(torch.float32).reshape(-1) for x in xs])
+    return clip_views(*poly_group_flat(flat, shapes, src_sr, dst_sr), shapes)
 
 
 # ------------------------------------------------------------------ windowed sinc: torchaudio.functional.resample's definition
@@ -215,33 +247,24 @@ def sinc_track_table(ins, lens, o: int, n: int):
 
 def sinc_group_flat(flat: torch.Tensor, shapes, src_sr: int, dst_sr: int, y: torch.Tensor = None, *, flags: int = 0, **params):
     """One egr_resample_sinc_tracks call on clips that already lie back to back in `flat` ([C_i][T_i] each, shapes = [(C_i, T_i)]):
-    -> (y, [(offset, C_i, n_out_i)]), clip i's result at y[offset : offset + C_i n_out_i].  y: a flat device buffer to write from
-    its start, or None for a fresh one."""
+    -> (y, table); many_common.clip_views(y, table, shapes) are the clips' results.  y: a flat device buffer to write from its
+    start, or None for a fresh one."""
     table, first_tap, (o, n, width, run) = sinc_filter_for(flat.device, src_sr, dst_sr, **params)
-    ins, lens, pos = [], [], 0
-    for c, T in shapes:
-        ins += [pos + k * T for k in range(c)]
-        lens += [T] * c
-        pos += c * T
-    tab, total = sinc_track_table(ins, lens, o, n)
+    tab, total = sinc_track_table(*track_rows(shapes), o, n)
     if y is None:
         y = torch.empty(total, dtype=torch.float32, device=flat.device)
     sinc_tracks(flat, torch.from_numpy(tab).to(flat.device), total, (o, n, width, run), table, first_tap, y, flags)
-    where, t = [], 0
-    for c, _ in shapes:
-        where.append((int(tab[t, 2]), c, int(tab[t, 3])))
-        t += c
-    return y, where
+    return y, tab
 
 
 def resample_sinc_group(xs, src_sr: int, dst_sr: int, *, flags: int = 0, **params):
     """[C_i, T_i] device tensors at src_sr -> [C_i, ceil(T_i n / o)] at dst_sr with one egr_resample_sinc_tracks call: the bits of
-    resample_sinc on each (the twin of dfn_many.resample_group)."""
+    resample_sinc on each (the twin of resample_poly_group)."""
     if int(src_sr) == int(dst_sr):
         return [x.to(torch.float32) for x in xs]
+    shapes = [tuple(x.shape) for x in xs]
     flat = torch.cat([x.to(torch.float32).reshape(-1) for x in xs])
-    y, where = sinc_group_flat(flat, [tuple(x.shape) for x in xs], src_sr, dst_sr, flags=flags, **params)
-    return [y[off:off + c * n_out].view(c, n_out) for off, c, n_out in where]
+    return clip_views(*sinc_group_flat(flat, shapes, src_sr, dst_sr, flags=flags, **params), shapes)
 
 
 def sinc_tracks(x: torch.Tensor, tab_dev: torch.Tensor, total_out: int, geo, table: torch.Tensor, first_tap: torch.Tensor,
@@ -260,11 +283,10 @@ def sinc_tracks(x: torch.Tensor, tab_dev: torch.Tensor, total_out: int, geo, tab
 # defaults there (Hann, lowpass_filter_width 6, rolloff 0.99); this pack's polyphase kernel is deviation DAC-Q2 and stays the default.
 def codec_resample(x, src_sr: int, dst_sr: int):
     """One [C,T] device tensor, or a list of them (one library call for the list), from src_sr to dst_sr: resample_sinc /
-    resample_sinc_group at torchaudio's defaults when reference_torchaudio_enabled(), else resample_hq / dfn_many.resample_group."""
+    resample_sinc_group at torchaudio's defaults when reference_torchaudio_enabled(), else resample_hq / resample_poly_group."""
     many = isinstance(x, (list, tuple))
     if reference_torchaudio_enabled():
         return resample_sinc_group(x, src_sr, dst_sr) if many else resample_sinc(x, src_sr, dst_sr)
     if many:
-        from .dfn_many import resample_group
-        return resample_group(x, src_sr, dst_sr)
+        return resample_poly_group(x, src_sr, dst_sr)
     return resample_hq(x, src_sr, dst_sr)

@@ -7,28 +7,15 @@ resample.resample_sinc at the node's filter: lowpass_filter_width 64, rolloff 0.
 up in one transfer (through one pinned buffer) and the results come down in one transfer; a clip already at the target rate passes through untouched.
 "torchaudio" here always means the windowed-sinc kernel: the corpus path has no linear fallback to preserve, and "linear" is refused.
 """
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import List, Optional, Sequence, Tuple
 
 import torch
 
-from . import device_ops, native, resample
+from . import native, resample
+from .many_common import check_clips, group_by_rate
 
 MODES = ("auto", "scipy_polyphase", "torchaudio")
 NODE_FILTER = dict(lowpass_filter_width=64, rolloff=0.945, method="sinc_interp_kaiser")      # the reference's call (:512-515)
-
-
-def _poly_group_flat(flat: torch.Tensor, shapes, src_sr: int, dst_sr: int, y: torch.Tensor):
-    """dfn_many.resample_group's call on clips that already lie back to back in `flat`, written from the start of y."""
-    from .flashsr_engine import resample_table
-    up, down = resample.rates(src_sr, dst_sr)
-    ins, lens, pos = [], [], 0
-    for c, T in shapes:
-        ins += [pos + k * T for k in range(c)]
-        lens += [T] * c
-        pos += c * T
-    tab, total = resample_table(ins, lens, up, down)
-    h, half = resample.filter_for(up, down, flat.device)
-    device_ops.resample_poly_tracks(flat, torch.from_numpy(tab).to(flat.device), total, up, down, h, half, y)
 
 
 def out_len(T: int, src_sr: int, dst_sr: int) -> int:
@@ -46,14 +33,8 @@ def resample_many(clips: Sequence[Tuple[torch.Tensor, int]], target_sr: int = 48
     if mode not in MODES:
         raise ValueError(f"resample_many: mode must be one of {MODES} (got {mode!r})")
     target_sr = int(target_sr)
-    clips = [(x, int(sr)) for x, sr in clips]
-    for i, (x, sr) in enumerate(clips):
-        if not torch.is_tensor(x) or x.dim() != 2 or x.shape[0] < 1 or x.shape[1] < 1 or sr < 1:
-            raise ValueError(f"resample_many: clip {i}: expected a non-empty [C, T] tensor and a positive sample rate")
-    groups: Dict[int, List[int]] = {}
-    for i, (_, sr) in enumerate(clips):
-        if sr != target_sr:
-            groups.setdefault(sr, []).append(i)
+    clips = check_clips("resample_many", clips)
+    groups = group_by_rate([sr for _, sr in clips], target_sr)
     if stats is not None:
         stats["calls"], stats["groups"] = len(groups), {sr: len(idx) for sr, idx in groups.items()}
     out: List[Optional[torch.Tensor]] = [None if sr != target_sr else (x.to(torch.float32).cpu() if to_host else x.to(torch.float32))
@@ -92,7 +73,7 @@ def resample_many(clips: Sequence[Tuple[torch.Tensor, int]], target_sr: int = 48
         if mode == "torchaudio":
             resample.sinc_group_flat(flat[ipos:ipos + n_g], shapes, sr, target_sr, y[opos:opos + o_g], beta=float(kaiser_beta), **NODE_FILTER)
         else:
-            _poly_group_flat(flat[ipos:ipos + n_g], shapes, sr, target_sr, y[opos:opos + o_g])
+            resample.poly_group_flat(flat[ipos:ipos + n_g], shapes, sr, target_sr, y[opos:opos + o_g])
         ipos, opos = ipos + n_g, opos + o_g
     if to_host:
         host = torch.empty(n_out, dtype=torch.float32, pin_memory=True)

@@ -6,13 +6,12 @@ iterations launches whatever the number of clips.  A clip's spectra, weights and
 (a wave costs the sum of its clips) and every clip gets the bits the single node gives it.  WPE runs at each clip's own sample rate:
 rates need no grouping.  The clips go up in one transfer and come down in one.
 """
-import os
 from typing import List, Optional, Sequence, Tuple
 
 import torch
 
 from . import native, wpe_engine
-from .dac_many import _download, _upload
+from .many_common import budget_bytes, check_clips, download, upload
 
 WIDGET_DEFAULTS = dict(taps=10, delay=3, iterations=3, n_fft=1024, hop=256, use_float32=True)
 DEFAULT_WAVE_GB = 16.0          # EGREGORA_WPE_WAVE_GB
@@ -34,8 +33,7 @@ def plan_waves(specs: Sequence[Tuple[int, int]], max_bytes: Optional[int] = None
     The clips of a channel count fill a wave in input order until the next one would take its workspace past max_bytes; a clip whose
     own wave is over the budget (or that the many-clip call refuses, such as a clip of 2^31 - 4096 frames) goes alone.  max_bytes
     defaults to EGREGORA_WPE_WAVE_GB GiB, 16 when unset: Fat-Llama's choice for its waves, taken over as it is, not a measurement."""
-    if max_bytes is None:
-        max_bytes = int(float(os.environ.get("EGREGORA_WPE_WAVE_GB", DEFAULT_WAVE_GB)) * (1 << 30))
+    max_bytes = budget_bytes("EGREGORA_WPE_WAVE_GB", DEFAULT_WAVE_GB, max_bytes)
     groups = {}
     for i, (c, n) in enumerate(specs):
         groups.setdefault(int(c), []).append(i)
@@ -69,10 +67,7 @@ def dereverb_many(clips: Sequence[Tuple[torch.Tensor, int]], *, stats: Optional[
     raises RuntimeError before anything is launched.  stats, when given, receives {"waves", "alone", "wave_bytes", "wave_clips"}."""
     w = _widgets("dereverb_many", widgets)
     taps, delay, iterations, n_fft, hop = w["taps"], w["delay"], w["iterations"], w["n_fft"], w["hop"]
-    clips = [(x, int(sr)) for x, sr in clips]
-    for i, (x, sr) in enumerate(clips):
-        if not torch.is_tensor(x) or x.dim() != 2 or x.shape[0] < 1 or sr < 1:
-            raise ValueError(f"dereverb_many: clip {i}: expected a [C, T] tensor and a positive sample rate")
+    clips = check_clips("dereverb_many", clips, allow_empty=True)
     for x, _ in clips:
         wpe_engine.check_limits(x.shape[0], taps, n_fft)
     if stats is not None:
@@ -92,14 +87,14 @@ def dereverb_many(clips: Sequence[Tuple[torch.Tensor, int]], *, stats: Optional[
     native.require_device()
     dev = torch.device("cuda", torch.cuda.current_device())
     waves, alone, wave_bytes = plan_waves([tuple(clips[i][0].shape) for i in run], n_fft=n_fft, hop=hop, taps=taps)
-    xs = [x.contiguous() for x in _upload([clips[i][0] for i in run], dev, torch.float32)]
+    xs = [x.contiguous() for x in upload([clips[i][0] for i in run], dev, torch.float32)]
     out: List = [None] * len(run)
     for wave in waves:                  # (the waves reuse one workspace in stream order; each has a flat result of its own)
         for j, y in zip(wave, wpe_engine.dereverb_many([xs[j] for j in wave], n_fft, hop, taps, delay, iterations)):
             out[j] = y
     for j in alone:
         out[j] = wpe_engine.dereverb(xs[j], n_fft, hop, taps, delay, iterations)
-    for j, y in zip(run, _download(out)):
+    for j, y in zip(run, download(out)):
         ys[j] = y
     if stats is not None:
         stats.update({"waves": len(waves), "alone": len(alone), "wave_bytes": list(wave_bytes),

@@ -96,12 +96,12 @@ def test_wave_tables_against_spans(pack):
 
 
 def test_resample_table(pack):
-    from egregora_amd import flashsr_engine as E
-    tab, total = E.resample_table([100, 0, 50], [1, 11, 4001], 160, 147)
+    from egregora_amd import resample
+    tab, total = resample.poly_track_table([100, 0, 50], [1, 11, 4001], 160, 147)
     n_out = [-(-n * 160 // 147) for n in (1, 11, 4001)]
     assert tab.dtype == np.int64 and tab.tolist() == [[100, 1, 0, n_out[0]], [0, 11, n_out[0], n_out[1]], [50, 4001, n_out[0] + n_out[1], n_out[2]]]
     assert total == sum(n_out)
-    assert E.resample_table([0], [10], 3, 1)[0].tolist() == [[0, 10, 0, 30]]
+    assert resample.poly_track_table([0], [10], 3, 1)[0].tolist() == [[0, 10, 0, 30]]
 
 
 # ---------------------------------------------------------------- node surface

@@ -74,7 +74,7 @@ def test_resample_poly_tracks_equals_resample_hq(pack, src, dst, lens):
             ins.append(pos + c * x.shape[1])
             n_ins.append(x.shape[1])
         pos += x.numel()
-    tab, total = E.resample_table(ins, n_ins, up, down)
+    tab, total = resample.poly_track_table(ins, n_ins, up, down)
     h, half = resample.filter_for(up, down, flat.device)
     assert half == 10 * max(up, down)
     y = torch.full((total + 5,), 7.0, device="cuda")

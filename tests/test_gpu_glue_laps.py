@@ -276,7 +276,7 @@ def test_resample_poly_tracks_with_boundaries_past_the_lap(pack, up, down):
             ins.append(pos + c * x.shape[1])
             n_ins.append(x.shape[1])
         pos += x.size
-    tab, total = E.resample_table(ins, n_ins, up, down)
+    tab, total = resample.poly_track_table(ins, n_ins, up, down)
     starts = tab[:, 2].tolist()
     assert total >= lap_n(lap) and tab[0, 3] >= lap + 100 and all(s > lap for s in starts[1:])
     assert marks["at256"] in starts[1:] and marks["at256"] % 256 == 0 and marks["atlap"] in starts[1:] and marks["atlap"] % lap == 0

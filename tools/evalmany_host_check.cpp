@@ -7,6 +7,10 @@
 // crossing into the next pair.  The refusals (n < 1, bad channels or stride, offsets at the edge of int64, totals past what one grid of
 // the consuming kernel's block size can launch: workgroups x threads < 2^32) must come
 // back as codes without any overflow.  Tables: the edge lengths of the frame rule and of the chunking, one pair, and 1000 random rows.
+// walk_shared walks the two functions of csrc/egr_ragged_index.h that every ragged header builds on: track_of against a linear scan
+// (ascending columns of 1, 2, 3 and 1000 rows, row strides 1 and 8, every query from 0 to past the last entry) and tile_of against the
+// written-out rule of each of its three callers (metrics chunks, shift-FIR tiles, mix chunks) on rows whose last tile is full, holds
+// one sample, or follows a full one by one sample.
 // Exit status 0 = all pass.
 #include <stdint.h>
 #include <stdio.h>
@@ -15,6 +19,7 @@
 #include <vector>
 
 #include "../comfyui-egregora-audio-super-resolution_amd/csrc/egr_eval_index.h"
+#include "../comfyui-egregora-audio-super-resolution_amd/csrc/egr_null_index.h"
 
 using namespace egr;
 
@@ -164,9 +169,71 @@ static int refusals() {
     return 0;
 }
 
+// the search as a scan: the last t with tab[t * stride + col] <= i
+static int scan_of(const long long* tab, int n, int stride, int col, long long i) {
+    int t = 0;
+    for (int k = 1; k < n; ++k)
+        if (tab[(size_t)k * stride + col] <= i) t = k;
+    return t;
+}
+
+static int walk_shared() {
+    // track_of: heap tables of exactly n rows; the searched column ascends strictly from 0 (every caller's rows hold at least one tile
+    // or sample), the other columns descend so that a read of the wrong column shows
+    for (int n : {1, 2, 3, 1000})
+        for (int stride : {1, 8}) {
+            const int col = stride == 1 ? 0 : 5;
+            long long* tab = (long long*)malloc((size_t)n * stride * sizeof(long long));
+            long long at = 0;
+            for (int t = 0; t < n; ++t) {
+                for (int c = 0; c < stride; ++c) tab[(size_t)t * stride + c] = 1000000 - t;
+                tab[(size_t)t * stride + col] = at;
+                at += 1 + urand(n == 1000 ? 40 : 3);
+            }
+            for (long long i = 0; i < at + 5; ++i) {
+                const int got = track_of(tab, n, stride, col, i), want = scan_of(tab, n, stride, col, i);
+                if (got != want) FAIL("track_of: %d rows, stride %d: %lld -> %d, want %d", n, stride, i, got, want);
+            }
+            free(tab);
+        }
+    // tile_of against the rule each caller wrote out before it: row by scan, first = (flat - first tile) tile, len = min(left, tile)
+    struct Rule { const char* who; int cols, col_first, col_len, tile; };
+    const Rule rules[3] = {{"metrics_chunk_of", MP_COLS, MP_CHUNK0, MP_N, EGR_METRICS_CHUNK}, {"shiftfir_tile_of", SF_COLS, SF_TILE0, SF_N_OUT, NULL_TILE},
+                           {"mix_chunk_of", NM_COLS, NM_CHUNK0, NM_N, NULL_CHUNK}};
+    for (const Rule& r : rules) {
+        const long long T = r.tile, lens[] = {T, T + 1, 1, 2 * T, 1, 3 * T + 1, T - 1, T};      // last tiles of T, 1, 1, T, 1, 1, T - 1, T samples
+        const int n = (int)(sizeof(lens) / sizeof(lens[0]));
+        long long* tab = (long long*)malloc((size_t)n * r.cols * sizeof(long long));
+        long long tiles = 0;
+        for (int t = 0; t < n; ++t) {
+            for (int c = 0; c < r.cols; ++c) tab[(size_t)t * r.cols + c] = -7;
+            tab[(size_t)t * r.cols + r.col_first] = tiles;
+            tab[(size_t)t * r.cols + r.col_len] = lens[t];
+            tiles += (lens[t] + T - 1) / T;
+        }
+        for (long long flat = 0; flat < tiles; ++flat) {
+            const int want = scan_of(tab, n, r.cols, r.col_first, flat);
+            const long long* e = tab + (size_t)want * r.cols;
+            const long long wfirst = (flat - e[r.col_first]) * T, left = e[r.col_len] - wfirst, wlen = left < T ? left : T;
+            long long first = -1, len = -1, f2 = -1, l2 = -1;
+            const int got = tile_of(tab, n, r.cols, r.col_first, r.col_len, r.tile, flat, &first, &len);
+            const int named = r.cols == MP_COLS && r.col_first == MP_CHUNK0 ? metrics_chunk_of(tab, n, flat, &f2, &l2)
+                            : r.col_first == SF_TILE0 ? shiftfir_tile_of(tab, n, flat, &f2, &l2) : mix_chunk_of(tab, n, flat, &f2, &l2);
+            if (got != want || first != wfirst || len != wlen || wlen < 1)
+                FAIL("tile_of as %s: tile %lld -> row %d [%lld, +%lld), want row %d [%lld, +%lld)", r.who, flat, got, first, len, want, wfirst, wlen);
+            if (named != want || f2 != wfirst || l2 != wlen) FAIL("%s: tile %lld -> row %d [%lld, +%lld)", r.who, flat, named, f2, l2);
+            const bool last = flat + 1 == tiles || tab[(size_t)(want + 1) * r.cols + r.col_first] == flat + 1;
+            if (last ? wfirst + wlen != lens[want] : wlen != T) FAIL("%s: tile %lld of row %d holds %lld samples", r.who, flat, want, wlen);
+        }
+        free(tab);
+    }
+    printf("track_of and tile_of ok\n");
+    return 0;
+}
+
 int main() {
     const long long CH = EGR_METRICS_CHUNK;
-    int bad = 0;
+    int bad = walk_shared();
     bad |= walk_pairs("frame-rule", {1, 511, 512, 512 + 63, 512 + 64, 512 + 65, 5000}, 512, 64);
     bad |= walk_pairs("chunk-rule", {CH - 1, CH, CH + 1, 2 * CH + 3, 1, 3 * CH}, 512, 64);
     bad |= walk_pairs("single", {60000}, 2048, 512);
